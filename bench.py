@@ -6,7 +6,7 @@ One step = Model.forward_with_cond_scale (cond_scale 1 -> one Model.forward, NS2
 replicas each denoising its own 32-utterance shard (weak scaling; no data-path collective inside the loop; the
 path's single RCCL all-gather of the generated latents runs once after the K steps and is inside the timed region).
 
-    python bench.py [--gpus N --steps K --warmup W] [--precision hybrid|mixed|half|exact|fast] [--graph]
+    python bench.py [--gpus N --steps K --warmup W] [--precision hybrid|mixed|half|exact|fast] [--graph] [--dump-outputs DIR]
 
 `--gpus N` with N > 1 re-executes itself under `python -m torch.distributed.run --nproc-per-node N` (one rank per GPU,
 backend "nccl" = RCCL) unless it already runs under one (RANK / WORLD_SIZE set by the driver's own launcher).
@@ -233,6 +233,30 @@ def cpu_baseline(sd, dim, depth, B, n):
                        f"1-utterance warm-up: {el:.2f} s, {cores} threads = physical cores (oracle/_ref archive absent)")
 
 
+DUMP_BUDGET_BYTES = 48 << 20      # --dump-outputs: all arrays together stay under 64 MB
+
+
+def dump_outputs(path, arrays):
+    """Write each array as path/<name>.npy (float32).  When the whole set exceeds DUMP_BUDGET_BYTES, every array keeps the same
+    seeded sample of its rows (leading dims flattened, last dim whole; torch.randperm(rows, seed 0)[:k], sorted): the same rows on
+    every run with the same arguments, so two builds can be compared element for element."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: v.detach().float().cpu() for k, v in arrays.items()}
+    sample = sum(v.numel() * 4 for v in arrays.values()) > DUMP_BUDGET_BYTES
+    for name, v in arrays.items():
+        rows = v.reshape(-1, v.shape[-1]) if sample else v
+        note = "whole"
+        if sample:
+            k = min(rows.shape[0], DUMP_BUDGET_BYTES // len(arrays) // (4 * rows.shape[1]))
+            idx = torch.randperm(rows.shape[0], generator=torch.Generator().manual_seed(0))[:k].sort().values
+            note = f"rows sample {k} of {rows.shape[0]}"
+            rows = rows[idx]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(rows.numpy()))
+        print(f"dump-outputs: {name}.npy {list(v.shape)} -> {list(rows.shape)} ({note})", file=sys.stderr)
+
+
 def free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -265,7 +289,13 @@ def main():
                     help="BASELINE config 3 instead of the headline: dim_prompt=512, condition_on_prompt, prompt of 103 codec "
                          "frames, frame-aligned cond")
     ap.add_argument("--cond-scale", type=float, default=1.0, help="with --conditioned: classifier-free guidance scale (NS2:914-927)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned to DIR/<name>.npy (float32): latents (the "
+                         "DDIM-updated batch, all ranks) and prediction (rank 0's model output); above 48 MiB in all, the same fixed "
+                         "seeded sample of rows of each (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     # ---- N > 1 without a launcher: become one (the driver may call `python bench.py --gpus N` directly)
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
@@ -301,8 +331,10 @@ def main():
         mkw = dict(dim_prompt=512, condition_on_prompt=True) if conditioned else {}
         return Model(dim=dim, depth=depth, **mkw).to(dev).eval()
 
-    def measure(model, precision, steps, warmup, conditioned=False, cond_scale=1.0, graph=False, profile=True):
-        """W untimed + exactly K timed steps; returns (elapsed s of the K steps [max over ranks], kernel ms, launches)"""
+    def measure(model, precision, steps, warmup, conditioned=False, cond_scale=1.0, graph=False, profile=True, outputs=None):
+        """W untimed + exactly K timed steps; returns (elapsed s of the K steps [max over ranks], kernel ms, launches).
+        outputs (a dict): receives copies of what the last timed step handed its caller, taken after the timed region --
+        "latents" (the DDIM-updated batch; all ranks' shards when gathered) and "prediction" (this rank's model output)"""
         model.precision = precision                      # re-packs the same parameters in the other plane format
         dim = model.dim
         g = torch.Generator().manual_seed(100 + rank)
@@ -320,10 +352,13 @@ def main():
         use_table = not args.no_time_table
         row_buf = torch.empty(lib.ns2_model_table_cols(model._ensure_native().handle), device=dev) if (use_table and graph) else None
 
+        last = {}
+
         def step(row=None):
             kw = dict(fwd_kw) if row is None else dict(fwd_kw, cond_row=row)
             out = model.forward_with_cond_scale(audio, t_cur, cond_scale=cond_scale, **kw)
             ops.ddim_step(audio, out, t_cur, t_nxt, "v", "sigmoid", 1.0, out=audio)
+            last["prediction"] = out                     # a graph replay rewrites the captured step's own output tensor
 
         with torch.no_grad():
             cg = None
@@ -365,6 +400,9 @@ def main():
             kern_ms, kern_n = ctypes.c_double(0), ctypes.c_int64(0)
             if prof_mask:
                 _lib.check(lib.ns2_model_profile_end(ns.handle, ctypes.byref(kern_ms), ctypes.byref(kern_n)), "profile_end")
+            if outputs is not None:
+                outputs["latents"] = (gathered if world > 1 else audio).clone()
+                outputs["prediction"] = last["prediction"].clone()
         el = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         if world > 1:
             dist.all_reduce(el, op=dist.ReduceOp.MAX)
@@ -418,9 +456,13 @@ def main():
     # ================================================================== headline
     dim, depth = args.dim, args.depth
     model = make_model(dim, depth, args.conditioned)
+    outputs = {} if args.dump_outputs else None
     elapsed, kern_ms_v, kern_n_v = measure(model, args.precision, args.steps, args.warmup, args.conditioned,
-                                           args.cond_scale if args.conditioned else 1.0, args.graph)
+                                           args.cond_scale if args.conditioned else 1.0, args.graph, outputs=outputs)
     steps_per_s = world * args.steps / elapsed
+    if outputs is not None and rank == 0:
+        dump_outputs(args.dump_outputs, outputs)
+    del outputs
     extra = {}
     if rank == 0 and world == 1 and not args.graph:
         sd_cpu = {k: v.detach().cpu() for k, v in model.state_dict().items()}

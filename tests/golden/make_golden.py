@@ -238,12 +238,65 @@ def gen_loss(ns2):
     print("loss", losses)
 
 
+def gen_reference_cases(ns2):
+    """What three CPU tests used to read off the live reference (tests/test_oracle.py::test_oracle_vs_live_reference,
+    tests/test_host_cpu.py::test_encoder_composites_equal_the_reference, tests/test_compat_reference.py::
+    test_our_loss_equals_the_reference_loss_bit_for_bit), recorded so that they run without it: per case the constructor kwargs,
+    the key -> shape map and weight seed (weights rebuilt with tests/golden/gen.py), the inputs, and the reference's outputs."""
+    fix = dict(kind="reference_cases", torch_version=torch.__version__)
+
+    def seeded(m, seed):
+        shapes = {k: tuple(v.shape) for k, v in m.state_dict().items()}
+        m.load_state_dict(make_weights(shapes, seed=seed))
+        return dict(shapes=shapes, weight_seed=seed)
+
+    # Model.forward_with_cond_scale (NS2:914-927), conditioned, small resampler
+    torch.manual_seed(0)
+    kw = dict(dim=64, depth=1, dim_prompt=48, condition_on_prompt=True, num_latents_m=8, resampler_depth=1)
+    m = ns2.Model(**kw).eval()
+    case = dict(kwargs=kw, **seeded(m, 71))
+    x = torch.randn(2, 33, 64); t = torch.rand(2)
+    prompt = torch.randn(2, 7, 48); cond = torch.randn(2, 48, 33)
+    with torch.no_grad():
+        outs = {cs: m.forward_with_cond_scale(x, t, prompt=prompt, cond=cond, cond_scale=cs) for cs in (1.0, 0.7)}
+    fix["cond_scale"] = dict(case, x=x, times=t, prompt=prompt, cond=cond, outputs=outs)
+    # SpeechPromptEncoder (NS2:289-341) and PhonemeEncoder (NS2:228-287), no dropout
+    torch.manual_seed(0)
+    kw = dict(dim_codebook=32, dims=(48, 64), depth=2, dropout=0.)
+    r = ns2.SpeechPromptEncoder(**kw)
+    case = dict(kwargs=kw, **seeded(r, 72))
+    x = torch.randn(2, 20, 32)
+    with torch.no_grad():
+        fix["speech_prompt_encoder"] = dict(case, x=x, out=r(x))
+    kw = dict(num_tokens=50, dim=32, dim_hidden=64, depth=2, conv_dropout=0.)
+    r = ns2.PhonemeEncoder(**kw).eval()
+    case = dict(kwargs=kw, **seeded(r, 73))
+    ids = torch.randint(0, 50, (2, 17)); ids[1, 12:] = -1
+    with torch.no_grad():
+        fix["phoneme_encoder"] = dict(case, ids=ids, out=r(ids, mask=ids >= 0))
+    # NaturalSpeech2.forward (NS2:1503-1684) per objective, the RNG seeded right before the call (it draws times and noise)
+    losses = {}
+    for objective in ("v", "eps", "x0"):
+        rm = ns2.Model(dim=64, depth=1)
+        case = seeded(rm, 74)
+        dr = ns2.NaturalSpeech2(model=rm, codec=None, target_sample_hz=24000, objective=objective)
+        torch.manual_seed(5)
+        with torch.no_grad():
+            losses[objective] = float(dr(make_input("audio", (3, 20, 64), seed=9)))
+    fix["loss"] = dict(case, kwargs=dict(dim=64, depth=1), audio_seed=9, rng_seed=5, losses=losses)
+    torch.save(fix, os.path.join(OUT, "reference_cases.pt"))
+    print("reference cases", losses)
+
+
 if __name__ == "__main__":
     if sys.argv[1:] == ["grads"]:                 # only the fixtures added in round 4
         ns2 = load_reference()
         for name, spec in GRAD_CASES.items():
             gen_grad_case(ns2, name, spec)
         gen_loss(ns2)
+        sys.exit(0)
+    if sys.argv[1:] == ["reference_cases"]:
+        gen_reference_cases(load_reference())
         sys.exit(0)
     gen_rvq()                     # before the reference stubs shadow torchaudio (transformers probes it)
     ns2 = load_reference()
@@ -257,3 +310,4 @@ if __name__ == "__main__":
     for name, spec in GRAD_CASES.items():
         gen_grad_case(ns2, name, spec)
     gen_loss(ns2)
+    gen_reference_cases(ns2)

@@ -1,5 +1,5 @@
 """The drop-in at the reference's OWN boundary: `compat.hip_backed_model_class(ref.Model)` inside the
-unmodified reference `NaturalSpeech2`.  Needs /root/reference, i.e. runs in the build container only (no GPU there): what
+unmodified reference `NaturalSpeech2`.  Most of it needs the reference checkout (runs where it is present; no GPU there): what
 can be checked without a device is that the subclass IS a reference `Model` with the reference's parameters, that the
 reference's training path keeps working through it, that the reference's sampler reaches the HIP entry point with the
 arguments the HIP path expects (it then refuses to run on CPU: no fallback), and that the result of the reference's loop
@@ -16,10 +16,11 @@ from oracle import ns2_oracle as O
 from oracle.ref_stub import load_reference, reference_available
 from tests.golden.gen import make_input, make_weights
 
-pytestmark = pytest.mark.skipif(not reference_available(), reason="live reference only exists in the build container")
+needs_ref = pytest.mark.skipif(not reference_available(), reason="live reference only exists in the build container")
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 
 
+@needs_ref
 def test_subclass_is_a_reference_model_with_reference_parameters():
     ns2 = load_reference()
     H = hip_backed_model_class(ns2.Model)
@@ -35,6 +36,7 @@ def test_subclass_is_a_reference_model_with_reference_parameters():
     assert a._hip_cfg["depth"] == 2 and a._hip_cfg["num_latents_m"] == 32 and a._hip_cfg["condition_on_prompt"] is True
 
 
+@needs_ref
 def test_reference_naturalspeech2_trains_and_samples_through_the_subclass():
     ns2 = load_reference()
     H = hip_backed_model_class(ns2.Model)
@@ -79,24 +81,22 @@ def test_reference_naturalspeech2_trains_and_samples_through_the_subclass():
 
 def test_our_loss_equals_the_reference_loss_bit_for_bit():
     """NaturalSpeech2.forward of this package vs the reference's on identical weights and RNG state (incl. the [b]*[b,1,1]
-    broadcast of NS2:1668), for all objectives."""
-    ns2 = load_reference()
+    broadcast of NS2:1668), for all objectives; the reference's losses are recorded in tests/golden/reference_cases.pt
+    (make_golden.py gen_reference_cases)."""
     from naturalspeech2_pytorch_amd import NaturalSpeech2
+    fix = torch.load(os.path.join(GOLD, "reference_cases.pt"), weights_only=False)["loss"]
     for objective in ("v", "eps", "x0"):
-        torch.manual_seed(1)
-        rm = ns2.Model(dim=64, depth=1)
-        ours = Model(dim=64, depth=1)
-        ours.load_state_dict(rm.state_dict())
-        audio = make_input("audio", (3, 20, 64), seed=9)
-        dr = ns2.NaturalSpeech2(model=rm, codec=None, target_sample_hz=24000, objective=objective)
+        ours = Model(**fix["kwargs"])
+        ours.load_state_dict(make_weights(fix["shapes"], seed=fix["weight_seed"]))
+        audio = make_input("audio", (3, 20, 64), seed=fix["audio_seed"])
         do = NaturalSpeech2(ours, codec=None, target_sample_hz=24000, objective=objective)
-        torch.manual_seed(5)
-        lr = dr(audio)
-        torch.manual_seed(5)
+        lr = fix["losses"][objective]
+        torch.manual_seed(fix["rng_seed"])
         lo = do(audio)
-        assert abs(lr.item() - lo.item()) < 2e-6 * max(1., abs(lr.item())), (objective, lr.item(), lo.item())
+        assert abs(lr - lo.item()) < 2e-6 * max(1., abs(lr)), (objective, lr, lo.item())
 
 
+@needs_ref
 @pytest.mark.parametrize("use_flash_attn", [True, False])
 def test_upstream_cannot_run_with_a_prompt_mask(use_flash_attn):
     """`Model.forward(prompt_mask=)` (NS2:929-937) is unrunnable upstream: the resampler's attention puts its 32 latents in front of
@@ -122,6 +122,7 @@ def test_upstream_cannot_run_with_a_prompt_mask(use_flash_attn):
         h(x, t, prompt=prompt, prompt_mask=mask, cond=cond)
 
 
+@needs_ref
 def test_codec_subclass_passes_the_reference_type_check_and_keeps_the_codec_surface():
     """VERDICT r5 missing #2: `codec: Optional[Union[SoundStream, EncodecWrapper]]` (NS2:1166).  compat.hip_backed_codec_class(EncodecWrapper)
     is a subclass of the class the reference imports (here: the stand-in class oracle/ref_stub.py installs for audiolm_pytorch's), is
