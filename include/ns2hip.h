@@ -51,8 +51,9 @@ extern "C" {
 const char* ns2_last_error(void);
 int ns2_version(void);
 /* test hook: force the GEMM kernel variant (0 = dispatch by shape, 1 = 128x128 register-staged, 2 = 256x256 LDS-DMA,
- * 3 = dispatch by shape but never split K, 4 = dispatch by shape but never the round-6 kernels (ffconv_kernel.h, gemm3_kernel.h), 5 = dispatch by shape but
- * those kernels whenever a call is eligible, whatever its size) */
+ * 3 = dispatch by shape but never split K, 4 = dispatch by shape but never the dedicated kernels (ffconv_kernel.h, gemm3_kernel.h,
+ * wavenet3_kernel.h), 5 = dispatch by shape but never split K, and those kernels whenever a call is eligible, whatever its size).
+ * 1 and 2 never split K either. */
 int ns2_debug_force_gemm(int kernel);
 /* Split-K of small products.  ns2_model_forward* lend a region of their workspace to every GEMM of the pass: a product with too
  * few output tiles to fill the chip runs as K slices into fixed slots plus a second launch that adds the slots in order and

@@ -23,6 +23,7 @@
 // staging pass and the ds_read_b128 fragment reads are bank-conflict free (80 = 5 x 16 B, 5 coprime to the
 // 16 slots of a 256-B bank row).  Tile ids are remapped so that consecutive ids share an XCD L2 (T1).
 #include "gemm_epi_fast.h"
+#include "gemm_route.h"
 
 namespace ns2 {
 
@@ -563,12 +564,11 @@ __global__ __launch_bounds__(256) void splitk_finish_f32_norm_kernel(const float
   if (ok) store_cols4(g.nrm_hi + row * pld(g.nrm_ld, nil), c, o[0], o[1], o[2], o[3], g.nrm_fmt, nil);
 }
 
-hipError_t launch_gemm1(const GemmArgs& g, int precision, hipStream_t s);
-// g: validated by launch_gemm, formats resolved; S slices of c K tiles per tap
+// S slices of c K tiles per tap (plan_gemm); every slot must lie inside the lent scratch
 hipError_t launch_gemm_splitk(const GemmArgs& g, int precision, int S, int c, hipStream_t s) {
   const int ldp = (g.N + 63) & ~63;
   const long slot = (long)g.M * ldp;
-  if (!g.sk_ws || S < 2 || c < 1 || S * slot > g.sk_ws_floats || g.epi == EPI_WAVENET || g.nz > 1) return hipErrorInvalidValue;
+  if (!g.sk_ws || S < 2 || c < 1 || S * slot > g.sk_ws_floats) return hipErrorInvalidValue;
   GemmArgs p = g;
   p.epi = EPI_F32; p.bias = nullptr; p.bias2 = nullptr; p.resid = nullptr; p.act = 0; p.film = nullptr;
   p.out_f = g.sk_ws; p.ldo_f = ldp; p.out_f_zs = slot;
@@ -607,8 +607,7 @@ hipError_t launch_gemm_splitk(const GemmArgs& g, int precision, int S, int c, hi
   return hipGetLastError();
 }
 
-hipError_t launch_gemm1(const GemmArgs& g, int precision, hipStream_t s) {      // formats already validated by launch_gemm
-  if (g.M <= 0 || g.N <= 0 || g.nkt <= 0) return hipErrorInvalidValue;
+hipError_t launch_gemm1(const GemmArgs& g, int precision, hipStream_t s) {
   switch (precision) {
     case 3: return launch_epi<3, false>(g, s);
     case 4: return launch_epi<2, true>(g, s);

@@ -25,6 +25,7 @@
 #include "ffconv_kernel.h"
 #include "gemm3_kernel.h"
 #include "wavenet3_kernel.h"
+#include "gemm_route.h"
 
 namespace ns2 {
 
@@ -960,7 +961,7 @@ static hipError_t launch2_one(const GemmArgs& g, hipStream_t s) {
 // N = taps * tr_kp output columns, nkt = 32-token K tiles PER SLICE, nz = slices, out_f / out_f_zs / ldo_f = the fp32 slots.
 hipError_t launch_gemm_tr(const GemmArgs& g, int precision, hipStream_t s) {
   if (precision != 3 && precision != 4) return hipErrorInvalidValue;
-  if (!g.a_hi || g.a_lo != g.a_hi + 32 || !g.w_hi || g.w_lo != g.w_hi + 32 || !g.out_f) return hipErrorInvalidValue;
+  if (!g.a_hi || !g.a_lo || !planes_ok(g.a_hi, g.a_lo) || !g.w_hi || !g.w_lo || !planes_ok(g.w_hi, g.w_lo) || !g.out_f) return hipErrorInvalidValue;
   if (g.M <= 0 || g.N <= 0 || g.nkt <= 0 || g.kt_per_tap != g.nkt || g.conv_taps != 0 || g.epi != EPI_F32 || g.nz < 1) return hipErrorInvalidValue;
   if (g.tr_tokens <= 0 || g.tr_kp <= 0 || (g.tr_kp & 31) || (g.lda & 31) || (g.ldw & 31) || g.tr_taps < 0) return hipErrorInvalidValue;
   if (g.tr_taps > 1 && (g.seq_len < 32 || g.dil < 1)) return hipErrorInvalidValue;      // the in-tile utterance position wraps at most once
@@ -982,21 +983,32 @@ static hipError_t launch2_epi(const GemmArgs& g, hipStream_t s) {
   return hipErrorInvalidValue;
 }
 
-hipError_t launch_gemm1(const GemmArgs& g, int precision, hipStream_t s);   // gemm.hip (128x128 register-staged kernel)
-hipError_t launch_gemm_splitk(const GemmArgs& g, int precision, int S, int c, hipStream_t s);   // gemm.hip: K slices + finish launch
-
 // Test hook (ns2_debug_force_gemm / NS2_GEMM): the only switch of the GEMM family, process-wide by design, atomic so that two
-// host threads (one per device) may read it while a test flips it.  -1: read NS2_GEMM once; 0 auto; 1 / 2 force a kernel.
+// host threads (one per device) may read it while a test flips it.  -1: read NS2_GEMM once.  gemm_hook() is the one place that
+// decodes the modes of include/ns2hip.h; a value outside 0 ... 5 is mode 0.
+struct GemmHook {
+  int force_tile;            // 128 / 256: every product on that kernel; 0: chosen by shape
+  bool allow_splitk;         // small products split K when the caller lent scratch
+  bool allow_dedicated;      // the dedicated kernels take the wide products they are eligible for
+  bool dedicated_any_size;   // ... and every product they are eligible for, ahead of split K and the tile choice
+};
 static std::atomic<int> g_forced_kernel{-1};
 void force_gemm_kernel(int k) { g_forced_kernel.store(k, std::memory_order_relaxed); }
-static int forced_kernel() {
+static GemmHook gemm_hook() {
   int f = g_forced_kernel.load(std::memory_order_relaxed);
   if (f < 0) {
     const char* e = getenv("NS2_GEMM");
     f = e ? atoi(e) : 0;
     g_forced_kernel.store(f, std::memory_order_relaxed);
   }
-  return f;
+  switch (f) {
+    case 1: return {128, false, false, false};
+    case 2: return {256, false, false, false};
+    case 3: return {0, false, true, false};     // by shape, never split K (the split's A/B)
+    case 4: return {0, true, false, false};     // by shape, never a dedicated kernel (their A/B)
+    case 5: return {0, false, true, true};      // the dedicated kernels whatever the size (tests), never split K
+    default: return {0, true, true, false};     // 0: by shape
+  }
 }
 
 // Split-K plan of a product M x N over nkt K tiles of 32 (kt_per_tap per tap): S slices of c K tiles of EVERY tap, S = 1 = do not
@@ -1018,27 +1030,55 @@ void splitk_plan(int M, int N, int nkt, int kt_per_tap, bool epi_f32, long scrat
   *S_out = S; *c_out = c;
 }
 
-// Dispatch: the 256x256 LDS-DMA kernel for wide outputs, the 128x128 kernel when N <= 128 (half of a 256-wide tile
-// would be padding, e.g. the dim=128 model's d x d projections).  W rows are padded to 256 by the packers.
-// Does this product take the one-launch 128 x 128 kernel whose workgroups own whole rows (N == 128), so that its fp32 epilogue can run
-// the RMSNorm that follows (GemmArgs::nrm_*)?  Not when K is split (the finishing launch runs the epilogue) or the big kernel is forced.
-// Two cases: (a) K is split (small batches): the flat finishing launch owns whole rows whatever the tile -- N = 128, 256 or 512;
-// (b) one launch of the 128 x 128 kernel with N == 128 == BN and M % 128 == 0 (the dim = 128 model at full batch).
+// The dedicated kernel that takes g, or Tile256 when none does
+static GemmRoute dedicated_route(const GemmArgs& g, int precision) {
+  if (ffconv3_eligible(g, precision)) return GemmRoute::FfConv3;      // the FF causal conv of the one-half-product plans on full row tiles
+  if (gemm3_eligible(g, precision)) return GemmRoute::Linear3;        // the mixed linear products on full row tiles
+  if (wavenet3_eligible(g, precision)) return GemmRoute::Wavenet3;    // the hybrid plan's Wavenet block on full row tiles
+  return GemmRoute::Tile256;
+}
+
+GemmPlan plan_gemm(const GemmArgs& g, int precision) {
+  const GemmHook h = gemm_hook();
+  if (h.dedicated_any_size) {
+    const GemmRoute r = dedicated_route(g, precision);
+    if (r != GemmRoute::Tile256) return {r, 1, g.kt_per_tap};
+  }
+  // Small products (a batch of 1 ... 4 utterances) split K when the caller lent scratch (splitk_plan above).
+  if (h.allow_splitk && g.sk_ws && g.epi != EPI_WAVENET && g.nz <= 1 && !g.dil_z && g.ksplit == 0) {
+    int S, c;
+    splitk_plan(g.M, g.N, g.nkt, g.kt_per_tap, g.epi == EPI_F32, g.sk_ws_floats, &S, &c);
+    if (S >= 2) return {GemmRoute::SplitK, S, c};
+  }
+  // The 256 x 256 kernel for wide outputs, the 128 x 128 kernel when N <= 128 (half of a 256-wide tile would be padding, e.g. the
+  // dim=128 model's d x d projections; W rows are padded to 256 by the packers) and for a product that would put at most 64 blocks
+  // of 256 x 256 on the 256 CUs (4 x the blocks, a quarter of the serial work each): 1 x 1024-frame steps measured 4 % faster with
+  // it, 4 x 1024 slower (exp_small_m_kernel.py).  A wide product the dedicated kernels are eligible for runs on them.
+  const long blocks256 = (long)((g.M + 255) / 256) * ((g.N + 255) / 256) * (g.nz > 0 ? g.nz : 1);
+  const bool wide = h.force_tile ? h.force_tile == 256 : g.N > 128 && blocks256 > 64;
+  const GemmRoute r = !wide ? GemmRoute::Tile128 : h.allow_dedicated ? dedicated_route(g, precision) : GemmRoute::Tile256;
+  return {r, 1, g.kt_per_tap};
+}
+
+// Does launch_gemm honour the RMSNorm that follows this product (GemmArgs::nrm_*) in its epilogue?  Where the route's workgroups own
+// whole rows: (a) K is split (small batches): the flat finishing launch, N = 128, 256 or 512; (b) one launch of the 128 x 128 kernel
+// with N == 128 == BN and M % 128 == 0 (the dim = 128 model at full batch).
 bool gemm_fuses_norm(const GemmArgs& g, int precision) {
   if (g.epi != EPI_F32 || g.M <= 0 || g.act != 0 || g.nz > 1 || g.ksplit != 0 || g.dil_z) return false;
   if ((g.ldo_f & 3) || (reinterpret_cast<uintptr_t>(g.out_f) & 15) || (g.resid && ((g.ldr & 3) || (reinterpret_cast<uintptr_t>(g.resid) & 15)))) return false;
-  const int f = forced_kernel();
-  if ((f == 0 || f == 4) && g.sk_ws) {
-    int S, c;
-    splitk_plan(g.M, g.N, g.nkt, g.kt_per_tap, true, g.sk_ws_floats, &S, &c);
-    if (S >= 2) return g.N == 128 || g.N == 256 || g.N == 512;
+  GemmArgs n = g;
+  n.w_tl = nullptr;      // planned as it runs with the norm requested: the lean linear kernel takes no norm (gemm3_eligible)
+  switch (plan_gemm(n, precision).route) {
+    case GemmRoute::SplitK: return g.N == 128 || g.N == 256 || g.N == 512;
+    case GemmRoute::Tile128: return g.N == 128 && (g.M % 128) == 0;
+    default: return false;
   }
-  (void)precision;
-  return f != 2 && g.N == 128 && (g.M % 128) == 0;
 }
 
-hipError_t launch_gemm(const GemmArgs& g_in, int precision, hipStream_t s) {
-  GemmArgs g = g_in;
+// launch_gemm's validation: resolves the default formats (-1) of g's outputs and checks its shape, planes and the norm request.
+// Plane pointers must match the formats: IEEE-half planes are dense (no lo pointer), FMT_H8 and the bf16 x3 operands are
+// interleaved lines (a lo plane means lo == hi + 32, ns2_common.h).
+static hipError_t resolve_gemm_args(GemmArgs& g, int precision) {
   if (precision < 1 || precision > 4) return hipErrorInvalidValue;
   if (g.nrm_hi) {
     const bool nil = g.nrm_lo != nullptr;
@@ -1050,38 +1090,29 @@ hipError_t launch_gemm(const GemmArgs& g_in, int precision, hipStream_t s) {
   const int op_fmt = precision == 2 ? FMT_F16 : (precision == 4 ? FMT_H8 : FMT_BF16);
   if (g.out_fmt < 0) g.out_fmt = op_fmt;
   if (g.vt_fmt < 0) g.vt_fmt = (precision == 2 || precision == 4) ? FMT_F16 : FMT_BF16;
-  // operand / output plane pointers must match the formats: IEEE-half planes are dense (no lo pointer), FMT_H8 and the
-  // bf16 x3 operands are interleaved lines (lo == hi + 32)
   if (precision == 2 && (g.a_lo || g.w_lo)) return hipErrorInvalidValue;
   if ((precision == 3 || precision == 4) && (!g.a_lo || !g.w_lo)) return hipErrorInvalidValue;
   if (g.out_hi && ((g.out_fmt == FMT_F16 && g.out_lo) || (g.out_fmt == FMT_H8 && !g.out_lo))) return hipErrorInvalidValue;
   if (g.vt_hi && g.vt_fmt == FMT_F16 && g.vt_lo) return hipErrorInvalidValue;
   if (g.M <= 0 || g.N <= 0 || g.nkt <= 0 || g.kt_per_tap <= 0 || (g.nkt % g.kt_per_tap)) return hipErrorInvalidValue;
-  // a lo plane means the interleaved layout: lo = hi + 32 (ns2_common.h)
-  if (!planes_ok(g.a_hi, g.a_lo) || !planes_ok(g.w_hi, g.w_lo) || !planes_ok(g.out_hi, g.out_lo) ||
-      !planes_ok(g.vt_hi, g.vt_lo))
+  if (!planes_ok(g.a_hi, g.a_lo) || !planes_ok(g.w_hi, g.w_lo) || !planes_ok(g.out_hi, g.out_lo) || !planes_ok(g.vt_hi, g.vt_lo))
     return hipErrorInvalidValue;
-  const int f = forced_kernel();
-  if (f == 5 && ffconv3_eligible(g, precision)) return launch_ffconv3(g, s);      // test hook: the dedicated kernels whatever the size
-  if (f == 5 && gemm3_eligible(g, precision)) return launch_gemm3(g, s);
-  if (f == 5 && wavenet3_eligible(g, precision)) return launch_wavenet3(g, s);
-  // Small products (a batch of 1 ... 4 utterances) split K when the caller lent scratch (splitk_plan above).
-  // (f == 3: automatic kernel choice, never split -- A/B hook.)
-  if ((f == 0 || f == 4) && g.sk_ws && g.epi != EPI_WAVENET && g.nz <= 1 && !g.dil_z && g.ksplit == 0) {
-    int S, c;
-    splitk_plan(g.M, g.N, g.nkt, g.kt_per_tap, g.epi == EPI_F32, g.sk_ws_floats, &S, &c);
-    if (S >= 2) return launch_gemm_splitk(g, precision, S, c, s);
+  return hipSuccess;
+}
+
+hipError_t launch_gemm(const GemmArgs& g_in, int precision, hipStream_t s) {
+  GemmArgs g = g_in;
+  const hipError_t e = resolve_gemm_args(g, precision);
+  if (e != hipSuccess) return e;
+  const GemmPlan p = plan_gemm(g, precision);
+  switch (p.route) {
+    case GemmRoute::SplitK: return launch_gemm_splitk(g, precision, p.S, p.c, s);
+    case GemmRoute::Tile128: return launch_gemm1(g, precision, s);
+    case GemmRoute::FfConv3: return launch_ffconv3(g, s);
+    case GemmRoute::Linear3: return launch_gemm3(g, s);
+    case GemmRoute::Wavenet3: return launch_wavenet3(g, s);
+    case GemmRoute::Tile256: break;
   }
-  // a product that would put at most 64 blocks of 256 x 256 on the 256 CUs runs on the 128 x 128 kernel (4 x the blocks, a
-  // quarter of the serial work each): 1 x 1024-frame steps measured 4 % faster with it, 4 x 1024 slower (exp_small_m_kernel.py)
-  const long blocks256 = (long)((g.M + 255) / 256) * ((g.N + 255) / 256) * (g.nz > 0 ? g.nz : 1);
-  const bool big = (f == 2) || (f != 1 && g.N > 128 && !((f == 0 || f >= 3) && blocks256 <= 64));
-  if (!big) return launch_gemm1(g, precision, s);
-  // the FF causal conv of the one-half-product plans on full row tiles: its own kernel (ffconv_kernel.h)
-  if ((f == 0 || f == 3) && ffconv3_eligible(g, precision)) return launch_ffconv3(g, s);
-  // the mixed linear products on full row tiles: the lean kernel (gemm3_kernel.h)
-  if ((f == 0 || f == 3) && gemm3_eligible(g, precision)) return launch_gemm3(g, s);
-  if ((f == 0 || f == 3) && wavenet3_eligible(g, precision)) return launch_wavenet3(g, s);
   switch (precision) {
     case 3: return launch2_epi<3, false>(g, s);
     case 4: return launch2_epi<2, true>(g, s);

@@ -97,10 +97,10 @@ struct GemmArgs {
 // precision: 3 = bf16 x3 ("exact"), 1 = bf16 ("fast"), 2 = one IEEE-half product ("half"), 4 = half product + both
 // first-order correction terms on the fp8 MFMA ("mixed", FMT_H8 operands).  Dispatches gemm.hip / gemm2.hip by shape.
 hipError_t launch_gemm(const GemmArgs& g, int precision, hipStream_t s);
-bool gemm_fuses_norm(const GemmArgs& g, int precision);                 // gemm2.hip: the shape takes the 128 x 128 kernel's whole-row epilogue (no split-K)
+bool gemm_fuses_norm(const GemmArgs& g, int precision);                 // gemm2.hip: launch_gemm would run the norm nrm_* requests in the product's epilogue
 hipError_t launch_gemm_tr(const GemmArgs& g, int precision, hipStream_t s);   // gemm2.hip: both operands read transposed (precision 3 / 4)
 void splitk_plan(int M, int N, int nkt, int kt_per_tap, bool epi_f32, long scratch_floats, int* S, int* c);   // gemm2.hip; S = 1: no split
-void force_gemm_kernel(int k);                                          // 0 auto, 1 = 128x128, 2 = 256x256, 3 = auto without split-K, 4 = auto without the dedicated FF-conv kernel, 5 = auto with it whatever the size (test hook); a forced kernel never splits K
+void force_gemm_kernel(int k);                                          // test hook, the modes of ns2_debug_force_gemm (include/ns2hip.h); decoded by gemm2.hip gemm_hook()
 // the dedicated FF causal conv kernel (ffconv_kernel.h, compiled in gemm2.hip): tiled weight images
 size_t ffconv3_tiled_bytes_of(int N, int Cp);
 hipError_t ffconv3_build_tiles(const bf16_t* w_hi, int ldw, int Cp, int rows_p, int N, bf16_t* out, hipStream_t s);
