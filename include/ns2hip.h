@@ -173,6 +173,33 @@ int ns2_transpose_f32(const float* in, int batch, int R, int C, float* out, void
 /* nn.Embedding gather, ids < 0 -> pad_id (PhonemeEncoder NS2:281-284) */
 int ns2_embedding(const int64_t* ids, const float* table, float* out, int64_t n, int dim, int64_t pad_id, void* stream);
 
+/* ------------------------------------------------------------------ DurationPitchPredictor and text-conditioned sampling
+ * (NS2:344-527, 87-104, 164-175, 1449-1455, 1476-1483).  The trunk's convolutions are ns2_linear_* calls (conv_taps = k,
+ * pad_left = k / 2), its RMSNorm and attention the entries above; these are the pieces around them.
+ * ns2_groupnorm_silu: nn.GroupNorm(groups, C) + SiLU (Block, NS2:346-369) over token-major fp32 rows x [B * n, C], statistics
+ * per (utterance, group) over n x C / groups values, eps as given; resid (may be null) [B * n, C] is added after the SiLU (the
+ * second Block of a ResnetBlock, NS2:394-398).  Outputs: out_f32 [B * n, C] and / or operand planes (out_hi, out_lo, ldo = C)
+ * in the format of `precision`.  C / groups must be a multiple of 4 (and C of 32 for planes); fp32 buffers 16-byte aligned.
+ * workspace = ns2_groupnorm_workspace_bytes(B, n, C, groups) bytes of caller-owned scratch: per-chunk (count, mean, M2)
+ * partials in fixed slots, combined in a fixed order -- the result is bit-reproducible. */
+int64_t ns2_groupnorm_workspace_bytes(int B, int n, int C, int groups);
+int ns2_groupnorm_silu(const float* x, int B, int n, int C, int groups, const float* weight, const float* bias, float eps,
+                       const float* resid, float* out_f32, uint16_t* out_hi, uint16_t* out_lo, int ldo, int precision,
+                       void* workspace, int64_t workspace_bytes, void* stream);
+/* totals[b] = sum_i int(duration[b, i]) (generate_mask_from_repeats, NS2:87-92; negative durations count as 0 frames):
+ * the caller reads max(totals) = n_frames for ns2_length_regulate */
+int ns2_length_regulate_totals(const float* duration, int B, int n_ph, int* totals, void* stream);
+/* the length regulator of NaturalSpeech2.sample (NS2:1478-1483): frame f < n_frames of utterance b takes the phoneme whose
+ * [exclusive, inclusive) prefix of int(duration[b]) holds f (none past the utterance's total: zeros), and
+ * out[b, :, f] = enc[b, ph, :] + pitch_table[f0_to_coarse(pitch[b, ph]), :]   (NS2:164-175, 1449-1455)
+ * duration / pitch [B, n_ph], enc [B, n_ph, D], pitch_table [>= 256, D], out [B, D, n_frames]; mel_min / mel_max = the fp32
+ * constants 1127 log(1 + f0_min / 700) / 1127 log(1 + f0_max / 700) of f0_to_coarse.  n_ph <= 8192. */
+int ns2_length_regulate(const float* duration, const float* pitch, const float* enc, const float* pitch_table, int B, int n_ph,
+                        int D, int n_frames, float mel_min, float mel_max, float* out, void* stream);
+/* out[m] = act(x[m, :K] . w + bias[0]), act = ReLU when relu != 0 (to_pred: Linear(dim, 1) + ReLU, NS2:467-471); bias may be
+ * null; K and ldx multiples of 4, x and w 16-byte aligned */
+int ns2_row_dot(const float* x, int ldx, int M, int K, const float* w, const float* bias, int relu, float* out, void* stream);
+
 /* one DDIM update (NS2:1396-1430): audio <- f(audio, model_out, times, times_next).  objective 0 'v', 1 'eps', 2 'x0';
  * schedule 0 sigmoid, 1 cosine, 2 linear (NS2:1133-1148) */
 int ns2_ddim_step(const float* audio, const float* model_out, float* out, const float* times, const float* times_next,

@@ -73,6 +73,11 @@ SIGNATURES = {
     "ns2_time_embed": (I, [P, P, P, P, P, P, I, I, I, I, P, L, P]),
     "ns2_transpose_f32": (I, [P, I, I, I, P, P]),
     "ns2_embedding": (I, [P, P, P, L, I, L, P]),
+    "ns2_groupnorm_workspace_bytes": (L, [I, I, I, I]),
+    "ns2_groupnorm_silu": (I, [P, I, I, I, I, P, P, F, P, P, P, P, I, I, P, L, P]),
+    "ns2_length_regulate_totals": (I, [P, I, I, P, P]),
+    "ns2_length_regulate": (I, [P, P, P, P, I, I, I, I, F, F, P, P]),
+    "ns2_row_dot": (I, [P, I, I, I, P, P, I, P, P]),
     "ns2_ddim_step": (I, [P, P, P, P, P, I, L, I, I, F, P]),
     "ns2_cfg_mix": (I, [P, P, P, L, F, P]),
     "ns2_seanet_prep": (I, [P, I, I, P, I, I, L, I, I, I, I, P, P, I, I, P]),

@@ -139,3 +139,61 @@ def phoneme_encoder_autograd(enc, ids, mask=None):
     h = F.silu(_causal_conv(h, enc.conv[1]))
     h = F.dropout(h, enc.conv_dropout, enc.training)
     return transformer_forward_autograd(enc.transformer, h, mask=mask)
+
+
+# ---- DurationPitchPredictor (NS2:344-527) and the length regulator of text-conditioned sampling (NS2:87-104, 164-175, 1449-1455)
+def _dp_trunk_autograd(tr, x, prompts, training):
+    p = tr.dropout if training else 0.
+    k = tr.kernel_size
+    for convs, norm, attn in tr.layers:
+        for blk in convs:
+            if tr.use_resnet_block:                                   # ResnetBlock: h = Blocks(x); out = h + x (NS2:394-398)
+                h = x.transpose(1, 2)
+                for b in blk.blocks:
+                    h = F.conv1d(h, b.proj.weight, b.proj.bias, padding=k // 2)
+                    h = F.dropout(F.silu(F.group_norm(h, b.norm.num_groups, b.norm.weight, b.norm.bias, b.norm.eps)), p, training)
+                x = (h + x.transpose(1, 2)).transpose(1, 2)
+            else:                                                     # ConvBlock (NS2:402-409)
+                h = F.silu(F.conv1d(x.transpose(1, 2), blk[1].weight, blk[1].bias, padding=k // 2))
+                x = F.dropout(h, p, training).transpose(1, 2)
+        x = _attention(_rmsnorm(x, norm), attn, tr.heads, context=prompts, include_queries=True, dropout_p=p) + x
+    head = tr.to_pred[0]
+    return F.relu(F.linear(x, head.weight, head.bias)[..., 0])
+
+
+def duration_pitch_autograd(dp, x, prompts):
+    if isinstance(dp.phoneme_token_emb, torch.nn.Embedding):
+        x = dp.phoneme_token_emb(x)
+    return tuple(_dp_trunk_autograd(tr, x, prompts, dp.training) for tr in (dp.to_duration_pred, dp.to_pitch_pred))
+
+
+def f0_to_coarse(f0, f0_bin=256, f0_max=1100.0, f0_min=50.0):
+    """NS2:164-175 in the same fp32 operations"""
+    f0_mel_max = 1127 * torch.log(1 + torch.tensor(f0_max) / 700)
+    f0_mel_min = 1127 * torch.log(1 + torch.tensor(f0_min) / 700)
+    f0_mel = 1127 * (1 + f0 / 700).log()
+    pos = f0_mel > 0
+    f0_mel = torch.where(pos, (f0_mel - f0_mel_min.to(f0.device)) * (f0_bin - 2) / (f0_mel_max - f0_mel_min).to(f0.device) + 1, f0_mel)
+    f0_mel = f0_mel.masked_fill(f0_mel <= 1, 1.)
+    f0_mel = f0_mel.masked_fill(f0_mel > f0_bin - 1, f0_bin - 1)
+    return (f0_mel + 0.5).int()
+
+
+def length_regulate(duration, pitch, enc, pitch_table):
+    """generate_mask_from_repeats + expand_encodings (NS2:87-104, 1449-1455) as a gather: frame f of utterance b takes the
+    phoneme whose [exclusive, inclusive) prefix of int(duration) holds f, zeros past the utterance's total.  The reference's 0/1
+    mask einsum sums one product x * 1 with zeros, so enc[ph] + pitch_table[coarse[ph]] is bit-identical to it.  Negative
+    durations (the predictor's ReLU never makes one) count as 0 frames.  -> [B, D, n_frames]"""
+    reps = duration.int().clamp(min=0)
+    cum = reps.cumsum(dim=-1)
+    totals = cum[:, -1]
+    n_frames = int(totals.max().item())
+    frames = torch.arange(n_frames, device=duration.device)
+    ph = torch.searchsorted(cum.contiguous(), frames[None].expand(cum.shape[0], -1).contiguous().to(cum.dtype), right=True)
+    valid = frames[None] < totals[:, None]
+    ph = ph.clamp(max=cum.shape[1] - 1)
+    e = torch.gather(enc, 1, ph[..., None].expand(-1, -1, enc.shape[-1]))
+    pe = F.embedding(f0_to_coarse(pitch).long(), pitch_table)
+    pe = torch.gather(pe, 1, ph[..., None].expand(-1, -1, pe.shape[-1]))
+    out = torch.where(valid[..., None], e + pe, torch.zeros((), dtype=e.dtype, device=e.device))
+    return out.transpose(1, 2)

@@ -1,0 +1,322 @@
+// The pieces of the DurationPitchPredictor (NS2:344-527) and of the text-conditioned sampling path (NS2:87-104, 164-175,
+// 1449-1455, 1476-1483) that the GEMM kernels do not cover:
+//   - GroupNorm(groups, C) + SiLU (+ residual) over token-major rows [B * n, C] (Block / ResnetBlock, NS2:346-400): a
+//     statistics pass writing per-chunk partials to fixed slots, then an apply pass that combines them in a fixed order
+//     (Chan et al.) -- deterministic and bit-reproducible, no atomics;
+//   - the length regulator (generate_mask_from_repeats + f0_to_coarse + expand_encodings): a gather plus one fp32 add, which
+//     is what the reference's 0/1 mask einsum computes bit for bit;
+//   - the to_pred heads (Linear(dim, 1) + ReLU, NS2:467-471) as a row dot product.
+// The convolutions, RMSNorm and attention of the trunk are the existing GEMM / norm / attention kernels.
+#include <hip/hip_runtime.h>
+
+#include "ns2_common.h"
+#include "ns2_host.h"
+
+namespace ns2 {
+
+// ---------------------------------------------------------------- GroupNorm + SiLU (NS2:346-369)
+// Statistics of one (utterance, group) are taken over n x cg values (cg = C / groups), relative to a shift K = the group's
+// first value in the utterance: for activations with a large common offset (mean 100, std 1) x - K is exact and the
+// partials stay small, so neither the mean nor the variance loses digits to cancellation (no E[x^2] - E[x]^2 anywhere).
+constexpr int GN_THREADS = 256;
+constexpr int GN_PER_THREAD = 16;
+constexpr int GN_CHUNK = GN_THREADS * GN_PER_THREAD;     // values per partial slot
+constexpr int GN_APPLY_ROWS = 16;
+
+static inline int gn_chunk_rows(int cg) { return cg >= GN_CHUNK ? 1 : GN_CHUNK / cg; }
+static inline int gn_chunks(int n, int cg) { return (n + gn_chunk_rows(cg) - 1) / gn_chunk_rows(cg); }
+
+struct Welford { float n, mean, m2; };
+
+// Chan, Golub & LeVeque: merge two (count, mean, M2) summaries; a is the earlier one in the fixed combine order
+NS2_DEVINL Welford chan(const Welford& a, const Welford& b) {
+  if (b.n == 0.f) return a;
+  if (a.n == 0.f) return b;
+  const float n = a.n + b.n, d = b.mean - a.mean, f = b.n / n;
+  return Welford{n, a.mean + d * f, a.m2 + b.m2 + d * d * a.n * f};
+}
+
+struct GnArgs {
+  const float* x; const float* weight; const float* bias; const float* resid;
+  float* out_f; bf16_t* out_hi; bf16_t* out_lo; int ldo; int fmt;
+  float4* part; int B, n, C, groups, cg, chunk_rows, nchunks; float eps;
+};
+
+// grid (nchunks, groups, B): slot (b, g, chunk) <- (count, mean, M2) of the chunk's values minus K
+__global__ __launch_bounds__(GN_THREADS) void gn_stats_kernel(const GnArgs a) {
+  const int chunk = blockIdx.x, g = blockIdx.y, b = blockIdx.z, t = threadIdx.x;
+  const float* xb = a.x + (long)b * a.n * a.C + (long)g * a.cg;
+  const float K = xb[0];
+  const int r0 = chunk * a.chunk_rows;
+  const int rows = min(a.chunk_rows, a.n - r0);
+  const int total = rows * a.cg;
+  float v[GN_PER_THREAD];
+  int cnt = 0;
+  float s = 0.f;
+#pragma unroll
+  for (int i = 0; i < GN_PER_THREAD; ++i) {
+    const int idx = t + GN_THREADS * i;
+    v[i] = 0.f;
+    if (idx < total) {
+      const int r = idx / a.cg, c = idx - r * a.cg;
+      v[i] = xb[(long)(r0 + r) * a.C + c] - K;
+      s += v[i];
+      ++cnt;
+    }
+  }
+  Welford w{(float)cnt, 0.f, 0.f};
+  if (cnt > 0) {
+    w.mean = s / (float)cnt;
+    float m2 = 0.f;
+#pragma unroll
+    for (int i = 0; i < GN_PER_THREAD; ++i)
+      if (t + GN_THREADS * i < total) { const float d = v[i] - w.mean; m2 += d * d; }
+    w.m2 = m2;
+  }
+  // fixed tree inside the wave (lane l takes lane l + o), then the four waves in order
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    Welford p{__shfl_down(w.n, o, 64), __shfl_down(w.mean, o, 64), __shfl_down(w.m2, o, 64)};
+    if ((t & 63) + o < 64 && ((t & 63) & (2 * o - 1)) == 0) w = chan(w, p);
+  }
+  __shared__ Welford wv[GN_THREADS / 64];
+  if ((t & 63) == 0) wv[t >> 6] = w;
+  __syncthreads();
+  if (t == 0) {
+    Welford r = wv[0];
+    for (int i = 1; i < GN_THREADS / 64; ++i) r = chan(r, wv[i]);
+    a.part[((long)b * a.groups + g) * a.nchunks + chunk] = make_float4(r.n, r.mean, r.m2, 0.f);
+  }
+}
+
+// grid (ceil(n / GN_APPLY_ROWS), B): y = silu((x - mean) * rstd * weight + bias) (+ resid), fp32 and / or operand planes
+__global__ __launch_bounds__(GN_THREADS) void gn_apply_kernel(const GnArgs a) {
+  const int b = blockIdx.y, t = threadIdx.x;
+  extern __shared__ float gs[];           // [groups] shift, [groups] shifted mean, [groups] rstd
+  float* sK = gs; float* sM = gs + a.groups; float* sR = gs + 2 * a.groups;
+  for (int g = t; g < a.groups; g += GN_THREADS) {
+    const float4* p = a.part + ((long)b * a.groups + g) * a.nchunks;
+    Welford w{p[0].x, p[0].y, p[0].z};
+    for (int i = 1; i < a.nchunks; ++i) w = chan(w, Welford{p[i].x, p[i].y, p[i].z});
+    sK[g] = a.x[(long)b * a.n * a.C + (long)g * a.cg];
+    sM[g] = w.mean;
+    sR[g] = 1.0f / sqrtf(w.m2 / w.n + a.eps);      // biased variance, as nn.GroupNorm
+  }
+  __syncthreads();
+  const int r0 = blockIdx.x * GN_APPLY_ROWS;
+  const int q = a.C >> 2;                          // float4 columns per row
+  const bool il = a.out_lo != nullptr || a.fmt == FMT_H8;
+  for (int it = t; it < GN_APPLY_ROWS * q; it += GN_THREADS) {
+    const int r = r0 + it / q, c = (it % q) * 4;
+    if (r >= a.n) break;
+    const long row = (long)b * a.n + r;
+    const int g = c / a.cg;                        // cg % 4 == 0: the four columns share a group
+    const float4 xv = *reinterpret_cast<const float4*>(a.x + row * a.C + c);
+    const float4 wv = *reinterpret_cast<const float4*>(a.weight + c);
+    const float4 bv = *reinterpret_cast<const float4*>(a.bias + c);
+    const float K = sK[g], m = sM[g], rs = sR[g];
+    float o[4] = {((xv.x - K) - m) * rs * wv.x + bv.x, ((xv.y - K) - m) * rs * wv.y + bv.y,
+                  ((xv.z - K) - m) * rs * wv.z + bv.z, ((xv.w - K) - m) * rs * wv.w + bv.w};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = siluf(o[e]);
+    if (a.resid) {
+      const float4 rv = *reinterpret_cast<const float4*>(a.resid + row * a.C + c);
+      o[0] += rv.x; o[1] += rv.y; o[2] += rv.z; o[3] += rv.w;
+    }
+    if (a.out_f) *reinterpret_cast<float4*>(a.out_f + row * a.C + c) = make_float4(o[0], o[1], o[2], o[3]);
+    if (a.out_hi) store_cols4(a.out_hi + row * pld(a.ldo, il), c, o[0], o[1], o[2], o[3], a.fmt, il);
+  }
+}
+
+// ---------------------------------------------------------------- length regulator (NS2:87-104, 164-175, 1449-1455)
+constexpr int LR_THREADS = 256;
+constexpr int LR_TF = 64;                // frames per tile
+constexpr int LR_TD = 32;                // channels per tile
+
+// repeats.int() of a ReLU output; a negative duration (never produced by the predictor) counts as 0 frames
+NS2_DEVINL int dur_frames(float d) { const int r = (int)d; return r > 0 ? r : 0; }
+
+// f0_to_coarse (NS2:164-175) in the reference's fp32 operation order; mel_min / mel_max are the reference's fp32 constants
+NS2_DEVINL int f0_coarse(float f0, float mel_min, float mel_max) {
+#pragma clang fp contract(off)
+  float m = 1127.0f * logf(1.0f + f0 / 700.0f);
+  if (m > 0.f) m = (m - mel_min) * 254.0f / (mel_max - mel_min) + 1.0f;
+  if (m <= 1.0f) m = 1.0f;
+  if (m > 255.0f) m = 255.0f;
+  const int c = (int)(m + 0.5f);
+  return c < 1 ? 1 : (c > 255 ? 255 : c);          // NaN pitch: keep the table read in bounds
+}
+
+// inclusive prefix sum of the utterance's frame counts into cum[n_ph] (LDS or global), by the whole block; returns the total
+NS2_DEVINL int block_cumsum(const float* dur, int n_ph, int* cum, int* part) {
+  const int t = threadIdx.x;
+  const int per = (n_ph + LR_THREADS - 1) / LR_THREADS;
+  const int i0 = min(t * per, n_ph), i1 = min(i0 + per, n_ph);
+  int s = 0;
+  for (int i = i0; i < i1; ++i) s += dur_frames(dur[i]);
+  part[t] = s;
+  __syncthreads();
+  for (int o = 1; o < LR_THREADS; o <<= 1) {         // Hillis-Steele over the 256 segment sums (integers: exact)
+    const int v = t >= o ? part[t - o] : 0;
+    __syncthreads();
+    part[t] += v;
+    __syncthreads();
+  }
+  if (cum) {
+    s = part[t] - s;                                 // exclusive prefix of this segment
+    for (int i = i0; i < i1; ++i) { s += dur_frames(dur[i]); cum[i] = s; }
+  }
+  const int total = part[LR_THREADS - 1];
+  __syncthreads();
+  return total;
+}
+
+__global__ __launch_bounds__(LR_THREADS) void lr_totals_kernel(const float* dur, int n_ph, int* totals) {
+  __shared__ int part[LR_THREADS];
+  const int b = blockIdx.x;
+  const int tot = block_cumsum(dur + (long)b * n_ph, n_ph, nullptr, part);
+  if (threadIdx.x == 0) totals[b] = tot;
+}
+
+// grid (ceil(n_frames / LR_TF), ceil(D / LR_TD), B); dynamic LDS: cum[n_ph]
+__global__ __launch_bounds__(LR_THREADS) void lr_expand_kernel(const float* dur, const float* pitch, const float* enc,
+                                                               const float* table, int n_ph, int D, int n_frames, float mel_min,
+                                                               float mel_max, float* out) {
+  extern __shared__ int cum[];
+  __shared__ int part[LR_THREADS];
+  __shared__ int s_ph[LR_TF], s_co[LR_TF];
+  __shared__ float tile[LR_TF][LR_TD + 1];
+  const int b = blockIdx.z, f0 = blockIdx.x * LR_TF, d0 = blockIdx.y * LR_TD, t = threadIdx.x;
+  const int total = block_cumsum(dur + (long)b * n_ph, n_ph, cum, part);
+  if (t < LR_TF) {
+    const int f = f0 + t;
+    int ph = -1;
+    if (f < total) {                                 // first phoneme whose inclusive prefix exceeds f
+      int lo = 0, hi = n_ph - 1;
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (cum[mid] > f) hi = mid; else lo = mid + 1;
+      }
+      ph = lo;
+    }
+    s_ph[t] = ph;
+    s_co[t] = ph >= 0 ? f0_coarse(pitch[(long)b * n_ph + ph], mel_min, mel_max) : 0;
+  }
+  __syncthreads();
+  // gather along channels (coalesced reads of enc / table rows) ...
+  for (int i = t; i < LR_TF * LR_TD; i += LR_THREADS) {
+    const int j = i / LR_TD, d = i % LR_TD;
+    float v = 0.f;
+    const int ph = s_ph[j];
+    if (ph >= 0 && d0 + d < D)
+      v = enc[((long)b * n_ph + ph) * D + d0 + d] + table[(long)s_co[j] * D + d0 + d];
+    tile[j][d] = v;
+  }
+  __syncthreads();
+  // ... and write along frames: out [B, D, n_frames]
+  for (int i = t; i < LR_TF * LR_TD; i += LR_THREADS) {
+    const int d = i / LR_TF, j = i % LR_TF;
+    if (d0 + d < D && f0 + j < n_frames) out[((long)b * D + d0 + d) * n_frames + f0 + j] = tile[j][d];
+  }
+}
+
+// ---------------------------------------------------------------- to_pred heads (NS2:467-471): one wave per row
+__global__ __launch_bounds__(256) void row_dot_kernel(const float* x, int ldx, int M, int K, const float* w, const float* bias,
+                                                      int relu, float* out) {
+  const int lane = threadIdx.x & 63;
+  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= M) return;
+  const float* xr = x + row * ldx;
+  float s = 0.f;
+  for (int c = lane * 4; c < K; c += 256) {
+    const float4 a = *reinterpret_cast<const float4*>(xr + c), b = *reinterpret_cast<const float4*>(w + c);
+    s += a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w;
+  }
+  s = wave_sum(s);
+  if (lane == 0) {
+    if (bias) s += bias[0];
+    out[row] = relu ? fmaxf(s, 0.f) : s;
+  }
+}
+
+}  // namespace ns2
+
+using namespace ns2;
+
+#define DP_HIPRET(expr)                                                              \
+  do {                                                                               \
+    hipError_t _e = (expr);                                                          \
+    if (_e != hipSuccess) {                                                          \
+      set_error("%s:%d %s -> %s", __FILE__, __LINE__, #expr, hipGetErrorString(_e)); \
+      return NS2_ERR_HIP;                                                            \
+    }                                                                                \
+  } while (0)
+#define DP_ARGCHK(cond, msg) \
+  do {                       \
+    if (!(cond)) {           \
+      set_error("%s", msg);  \
+      return NS2_ERR_ARG;    \
+    }                        \
+  } while (0)
+
+extern "C" int64_t ns2_groupnorm_workspace_bytes(int B, int n, int C, int groups) {
+  if (B <= 0 || n <= 0 || groups <= 0 || C <= 0 || C % groups) return 0;
+  return (int64_t)B * groups * gn_chunks(n, C / groups) * (int64_t)sizeof(float4);
+}
+
+extern "C" int ns2_groupnorm_silu(const float* x, int B, int n, int C, int groups, const float* weight, const float* bias, float eps,
+                                  const float* resid, float* out_f32, uint16_t* out_hi, uint16_t* out_lo, int ldo, int precision,
+                                  void* workspace, int64_t workspace_bytes, void* stream) {
+  DP_ARGCHK(x && weight && bias && (out_f32 || out_hi) && B > 0 && n > 0 && groups > 0 && groups <= 1024,
+            "ns2_groupnorm_silu: bad arguments");
+  DP_ARGCHK(C % groups == 0 && (C / groups) % 4 == 0, "ns2_groupnorm_silu: C / groups must be a multiple of 4");
+  DP_ARGCHK(precision >= 1 && precision <= 4, "ns2_groupnorm_silu: precision must be 1 .. 4");
+  DP_ARGCHK(!out_hi || (C % 32 == 0 && ldo == C), "ns2_groupnorm_silu: plane output needs C % 32 == 0 and ldo == C");
+  DP_ARGCHK(precision != 2 || !out_lo, "ns2_groupnorm_silu: precision 2 (fp16) has no lo plane");
+  DP_ARGCHK(precision != 3 || !out_hi || out_lo, "ns2_groupnorm_silu: precision 3 planes need the lo plane");
+  DP_ARGCHK(workspace && workspace_bytes >= ns2_groupnorm_workspace_bytes(B, n, C, groups), "ns2_groupnorm_silu: workspace too small");
+  DP_ARGCHK(((uintptr_t)x | (uintptr_t)weight | (uintptr_t)bias | (uintptr_t)resid | (uintptr_t)out_f32 | (uintptr_t)workspace) % 16 == 0,
+            "ns2_groupnorm_silu: fp32 buffers must be 16-byte aligned");
+  GnArgs a;
+  a.x = x; a.weight = weight; a.bias = bias; a.resid = resid; a.out_f = out_f32;
+  a.out_hi = reinterpret_cast<bf16_t*>(out_hi); a.out_lo = reinterpret_cast<bf16_t*>(out_lo); a.ldo = ldo;
+  a.fmt = precision == 2 ? FMT_F16 : (precision == 4 ? FMT_H8 : FMT_BF16);
+  a.part = reinterpret_cast<float4*>(workspace);
+  a.B = B; a.n = n; a.C = C; a.groups = groups; a.cg = C / groups; a.chunk_rows = gn_chunk_rows(a.cg);
+  a.nchunks = gn_chunks(n, a.cg); a.eps = eps;
+  DP_ARGCHK(a.cg <= GN_CHUNK, "ns2_groupnorm_silu: C / groups must be at most 4096");
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(gn_stats_kernel, dim3(a.nchunks, groups, B), dim3(GN_THREADS), 0, s, a);
+  DP_HIPRET(hipGetLastError());
+  hipLaunchKernelGGL(gn_apply_kernel, dim3((n + GN_APPLY_ROWS - 1) / GN_APPLY_ROWS, B), dim3(GN_THREADS),
+                     3 * groups * sizeof(float), s, a);
+  DP_HIPRET(hipGetLastError());
+  return NS2_OK;
+}
+
+extern "C" int ns2_length_regulate_totals(const float* duration, int B, int n_ph, int* totals, void* stream) {
+  DP_ARGCHK(duration && totals && B > 0 && n_ph > 0, "ns2_length_regulate_totals: bad arguments");
+  hipLaunchKernelGGL(lr_totals_kernel, dim3(B), dim3(LR_THREADS), 0, (hipStream_t)stream, duration, n_ph, totals);
+  DP_HIPRET(hipGetLastError());
+  return NS2_OK;
+}
+
+extern "C" int ns2_length_regulate(const float* duration, const float* pitch, const float* enc, const float* pitch_table, int B,
+                                   int n_ph, int D, int n_frames, float mel_min, float mel_max, float* out, void* stream) {
+  DP_ARGCHK(duration && pitch && enc && pitch_table && out && B > 0 && n_ph > 0 && D > 0 && n_frames > 0,
+            "ns2_length_regulate: bad arguments");
+  DP_ARGCHK(n_ph <= 8192, "ns2_length_regulate: at most 8192 phonemes per utterance");
+  hipLaunchKernelGGL(lr_expand_kernel, dim3((n_frames + LR_TF - 1) / LR_TF, (D + LR_TD - 1) / LR_TD, B), dim3(LR_THREADS),
+                     (size_t)n_ph * sizeof(int), (hipStream_t)stream, duration, pitch, enc, pitch_table, n_ph, D, n_frames, mel_min,
+                     mel_max, out);
+  DP_HIPRET(hipGetLastError());
+  return NS2_OK;
+}
+
+extern "C" int ns2_row_dot(const float* x, int ldx, int M, int K, const float* w, const float* bias, int relu, float* out, void* stream) {
+  DP_ARGCHK(x && w && out && M > 0 && K > 0 && K % 4 == 0 && ldx % 4 == 0 && ldx >= K, "ns2_row_dot: bad arguments");
+  DP_ARGCHK(((uintptr_t)x | (uintptr_t)w) % 16 == 0, "ns2_row_dot: x and w must be 16-byte aligned");
+  hipLaunchKernelGGL(row_dot_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, ldx, M, K, w, bias, relu, out);
+  DP_HIPRET(hipGetLastError());
+  return NS2_OK;
+}

@@ -6,17 +6,21 @@ reference's own call signatures:
     .forward(audio, text=None, text_lens=None, mel=None, mel_lens=None, codes=None, prompt=None, pitch=None, ...)       NS2:1503-1515
     .ddim_sample(shape, prompt=None, time_difference=None, cond_scale=1., cond=None)                                     NS2:1380
 
-What runs where.  The per-step path (Model + DDIM update), the codec's RVQ encode/decode and the two conditioning encoders
-built from the plain Transformer (`prompt_enc` = SpeechPromptEncoder, `phoneme_enc` = PhonemeEncoder) are HIP.  The rest of
-the conditioning front-end — DurationPitchPredictor, Aligner, mel / pitch extraction, the tokenizer (OUT OF SCOPE)
-— is not rebuilt: a caller hands over what those modules would have produced through two extra keyword arguments that the
-reference signature tolerates (`forward` takes **kwargs):
+What runs where.  The per-step path (Model + DDIM update), the codec's RVQ encode/decode, the two conditioning encoders
+built from the plain Transformer (`prompt_enc` = SpeechPromptEncoder, `phoneme_enc` = PhonemeEncoder) and, with
+`build_duration_pitch=True`, the DurationPitchPredictor and the length regulator behind `sample(text=...)` (NS2:1476-1483;
+duration_pitch.py) are HIP.  The rest of the conditioning front-end — Aligner, mel / pitch extraction, the tokenizer (SURVEY
+§2: OUT OF SCOPE) — is not rebuilt.  By default (no predictor: the state_dict has no `duration_pitch.*` keys) and for
+`forward`, a caller hands over what those modules would have produced through two extra keyword arguments that the reference
+signature tolerates (`forward` takes **kwargs):
 
     cond        [b, dim_prompt, n_c]   the frame-aligned phoneme+pitch conditioning (reference: `expand_encodings`, NS2:1449-1455)
     prompt_enc  [b, n_p, dim_prompt]   the encoded prompt (reference: `self.prompt_enc(prompt)`, NS2:1475 / 1543)
 
-`text`, `text_lens`, `mel`, `mel_lens`, `pitch` are accepted as in the reference; only the branch that would need an
-out-of-scope module (no `cond` given) raises, with a NotImplementedError naming it.  `phoneme_enc`, `prompt_enc` and
+`text`, `text_lens`, `mel`, `mel_lens`, `pitch` are accepted as in the reference; only the branch that would need a module
+that is not built (no `cond` given) raises, with a NotImplementedError naming it.  One difference from the reference: when
+every predicted duration truncates to 0 frames, `sample(text=...)` raises a ValueError (the reference fails with a shape
+error inside `cond_to_model_dim`).  `phoneme_enc`, `prompt_enc` and
 `pitch_emb` are constructed like upstream (same state_dict keys; load reference checkpoints of a conditional wrapper with
 `strict=False`, the out-of-scope members have no counterpart here).
 
@@ -76,7 +80,8 @@ class NaturalSpeech2(nn.Module):
                  pitch_emb_pp_hidden_dim: int = 512, calc_pitch_with_pyworld=True, mel_hop_length=160,
                  audio_to_mel_kwargs: dict = dict(), scale=1., duration_loss_weight=1., pitch_loss_weight=1.,
                  aligner_loss_weight=1., aligner_bin_loss_weight=0.,
-                 encoder_precision="exact"):           # not in the reference: precision mode of the two HIP encoders
+                 encoder_precision="exact",            # not in the reference: precision mode of the HIP encoders (and predictor)
+                 build_duration_pitch: bool = False):  # not in the reference: build the DurationPitchPredictor (sample(text=...))
         super().__init__()
         assert _is_denoiser(model), "model must be a Model (this package's, or compat.HipBackedModel over the reference's class)"
         self.conditional = model.condition_on_prompt
@@ -94,7 +99,10 @@ class NaturalSpeech2(nn.Module):
             self.prompt_enc = SpeechPromptEncoder(dim_codebook=dim_codebook, precision=encoder_precision)
             self.pitch_emb = nn.Embedding(pitch_emb_dim, pitch_emb_pp_hidden_dim)
             self.aligner_bin_loss_weight = aligner_bin_loss_weight
-            # DurationPitchPredictor, Aligner, AudioToMel, ForwardSumLoss / BinLoss (NS2:1224-1240): out of scope, not built
+            if build_duration_pitch:                                                  # NS2:1234
+                from .duration_pitch import DurationPitchPredictor
+                self.duration_pitch = DurationPitchPredictor(dim=duration_pitch_dim, precision=encoder_precision)
+            # Aligner, AudioToMel, ForwardSumLoss / BinLoss (NS2:1224-1240): out of scope, not built
 
         assert codec is None or model.dim == codec.codebook_dim, \
             f"transformer model dimension {model.dim} must be equal to codec dimension {codec.codebook_dim}"   # NS2:1244
@@ -245,10 +253,30 @@ class NaturalSpeech2(nn.Module):
     def refresh_weights(self):
         """run boundary: every HIP module re-checks its packed weights against the parameters' CONTENT (writes through `.data` --
         what ema_pytorch does to the copy of this whole object it samples from, NS2:1793-1801 -- bump no version counter)"""
-        for name in ("model", "prompt_enc", "phoneme_enc", "codec"):
+        for name in ("model", "prompt_enc", "phoneme_enc", "duration_pitch", "codec"):
             mod = getattr(self, name, None)
             if mod is not None and hasattr(mod, "refresh_weights"):
                 mod.refresh_weights()
+
+    @torch.no_grad()
+    def text_to_cond(self, text, prompt_enc):
+        """NS2:1476-1483: phoneme_enc(text) -> DurationPitchPredictor -> the length regulator (durations truncated to whole
+        frames, pitch embedded through f0_to_coarse) -> the frame-aligned conditioning [b, dim_prompt, n_frames], n_frames = the
+        longest utterance (one host read, the reference's `.item()`).  Every duration truncating to 0 frames leaves nothing to
+        condition on: the reference fails there inside cond_to_model_dim; here it is a ValueError."""
+        assert hasattr(self, "duration_pitch"), "construct NaturalSpeech2 with build_duration_pitch=True"
+        phoneme_enc = self.phoneme_enc(text)
+        duration, pitch = self.duration_pitch(phoneme_enc, prompt_enc)
+        table = self.pitch_emb.weight
+        if phoneme_enc.is_cuda:
+            cond = ops.length_regulate(duration.float().contiguous(), pitch.float().contiguous(),
+                                       phoneme_enc.float().contiguous(), table.detach().float().contiguous())
+        else:
+            from .autograd_path import length_regulate
+            cond = length_regulate(duration, pitch, phoneme_enc, table)
+        if cond.shape[-1] == 0:
+            raise ValueError("every predicted duration truncates to 0 frames: there is no aligned conditioning to sample from")
+        return cond
 
     @torch.no_grad()
     def sample(self, *, length, prompt=None, batch_size=1, cond_scale=1., text=None, text_lens=None,
@@ -260,10 +288,13 @@ class NaturalSpeech2(nn.Module):
         if self.conditional:
             assert (prompt is not None or prompt_enc is not None) and (text is not None or cond is not None)   # NS2:1473
             p_enc = self._encode_prompt(prompt, prompt_enc)
-            if cond is None:
+            if cond is None and not hasattr(self, "duration_pitch"):
                 raise NotImplementedError(
                     "sample(text=...) derives the aligned conditioning with the DurationPitchPredictor (NS2:1478-1483), which is "
-                    "outside the HIP hot path: pass the aligned conditioning as `cond=` [b, dim_prompt, n_frames]")
+                    "not built by default: construct with `build_duration_pitch=True`, or pass the aligned conditioning as "
+                    "`cond=` [b, dim_prompt, n_frames]")
+            if cond is None:
+                cond = self.text_to_cond(text, p_enc)
             batch_size = p_enc.shape[0]
         elif prompt is not None:
             batch_size = prompt.shape[0]                                               # NS2:1485-1486

@@ -1,0 +1,172 @@
+"""`DurationPitchPredictor` (NS2:344-527) and the length regulator of text-conditioned sampling (NS2:87-104, 164-175,
+1449-1455, 1476-1483).
+
+Each of the two trunks (`to_duration_pred`, `to_pitch_pred`) runs `depth` layers of [conv stack -> RMSNorm -> attention whose
+keys / values are cat(norm(x), encoded prompts) (cross_attn_include_queries) -> residual], then Linear(dim, 1) + ReLU.  On the
+HIP path the "same"-padded convolutions are the shifted-row GEMMs (conv_taps = k, pad_left = k // 2), a `ConvBlock` takes its
+SiLU in the GEMM epilogue, a `ResnetBlock`'s GroupNorm + SiLU (+ residual) is csrc/duration_pitch.hip, RMSNorm / attention are
+the hot path's kernels and the heads are a row dot product.  Under autograd (or on the CPU) the differentiable composite of
+autograd_path.py runs instead.  Same constructor keywords and state_dict keys as the reference classes.
+"""
+import torch
+from torch import nn
+
+from . import ops
+from ._cache import PackedCache
+from .model import _Attention, _NoParams, _RMSNorm, _PRECISIONS
+from .transformer import needs_autograd
+
+
+class _Block(nn.Module):                        # Block (NS2:346-369): Conv1d -> GroupNorm -> SiLU -> Dropout
+    def __init__(self, dim, dim_out, kernel, groups=8):
+        super().__init__()
+        self.proj = nn.Conv1d(dim, dim_out, kernel, padding=kernel // 2)
+        self.norm = nn.GroupNorm(groups, dim_out)
+
+
+class _ResnetBlock(nn.Module):                  # ResnetBlock (NS2:371-400) with dim == dim_out: res_conv is the identity
+    def __init__(self, dim, kernel, num_convs=2):
+        super().__init__()
+        self.blocks = nn.Sequential(*[_Block(dim, dim, kernel) for _ in range(num_convs)])
+        self.res_conv = nn.Identity()
+
+
+def _conv_block(dim, kernel):                   # ConvBlock (NS2:402-409): Rearrange, Conv1d, SiLU, Dropout, Rearrange
+    return nn.Sequential(_NoParams(), nn.Conv1d(dim, dim, kernel, padding=kernel // 2), _NoParams(), _NoParams(), _NoParams())
+
+
+class DurationPitchPredictorTrunk(nn.Module):   # NS2:411-481
+    def __init__(self, dim=512, depth=10, kernel_size=3, dim_context=None, heads=8, dim_head=64, dropout=0.2,
+                 use_resnet_block=True, num_convs_per_resnet_block=2, num_convolutions_per_block=3, use_flash_attn=False):
+        super().__init__()
+        self.dim, self.kernel_size, self.heads, self.dim_head, self.dropout = dim, kernel_size, heads, dim_head, dropout
+        self.use_resnet_block = use_resnet_block
+        conv = (lambda: _ResnetBlock(dim, kernel_size, num_convs_per_resnet_block)) if use_resnet_block else \
+            (lambda: _conv_block(dim, kernel_size))
+        self.layers = nn.ModuleList([
+            nn.ModuleList([nn.Sequential(*[conv() for _ in range(num_convolutions_per_block)]), _RMSNorm(dim),
+                           _Attention(dim, dim_head, heads, dim_context=dim_context)])
+            for _ in range(depth)])
+        self.to_pred = nn.Sequential(nn.Linear(dim, 1), _NoParams(), _NoParams())
+
+
+class DurationPitchPredictor(nn.Module):
+    def __init__(self, *, dim, num_phoneme_tokens=None, tokenizer=None, dim_encoded_prompts=None, num_convolutions_per_block=3,
+                 use_resnet_block=True, num_convs_per_resnet_block=2, depth=10, kernel_size=3, heads=8, dim_head=64,
+                 dim_hidden=512, dropout=0.2, use_flash_attn=False, precision="exact"):
+        super().__init__()
+        if kernel_size % 2 == 0:
+            raise ValueError(f"kernel_size must be odd: Conv1d(padding=k // 2) with an even k ({kernel_size}) changes the length")
+        if dim_hidden % 32 != 0:
+            raise ValueError(f"dim_hidden must be a multiple of 32 (GroupNorm groups of 4-column vectors, 32-column operand lines), got {dim_hidden}")
+        assert precision in _PRECISIONS, f"precision must be one of {sorted(_PRECISIONS)}"
+        assert dim_head in (32, 64, 128), "the HIP attention kernel is built for head dims 32, 64 and 128"
+        self.tokenizer = tokenizer
+        if num_phoneme_tokens is None and tokenizer is not None:
+            num_phoneme_tokens = tokenizer.vocab_size
+        dim_encoded_prompts = dim if dim_encoded_prompts is None else dim_encoded_prompts
+        self.phoneme_token_emb = nn.Embedding(num_phoneme_tokens, dim) if num_phoneme_tokens is not None else nn.Identity()
+        kw = dict(dim=dim_hidden, depth=depth, kernel_size=kernel_size, dim_context=dim_encoded_prompts, heads=heads,
+                  dim_head=dim_head, dropout=dropout, use_resnet_block=use_resnet_block,
+                  num_convs_per_resnet_block=num_convs_per_resnet_block, num_convolutions_per_block=num_convolutions_per_block,
+                  use_flash_attn=use_flash_attn)
+        self.to_pitch_pred = DurationPitchPredictorTrunk(**kw)
+        self.to_duration_pred = DurationPitchPredictorTrunk(**kw)
+        self.to_duration_pred.load_state_dict(self.to_pitch_pred.state_dict())      # copy.deepcopy upstream (NS2:509)
+        self.precision, self.dim_hidden, self.dropout = precision, dim_hidden, dropout
+        self._cache = PackedCache(fingerprint_every=1)      # once per utterance: check the content on every call (EMA copies)
+
+    def forward(self, x, encoded_prompts, prompt_mask=None):
+        """x: token ids [b, n] (with num_phoneme_tokens) or phoneme encodings [b, n, dim_hidden]; encoded_prompts [b, n_p,
+        dim_hidden].  Returns (duration, pitch), each [b, n]."""
+        if not torch.is_tensor(x):
+            raise NotImplementedError("List[str] input needs the tokenizer / espeak front-end (out of scope); pass token ids or "
+                                      "phoneme encodings")
+        if prompt_mask is not None:
+            raise NotImplementedError("prompt_mask is not supported: the reference's Attend applies it to keys = cat(queries, "
+                                      "prompts), which a [b, n_p] mask does not cover (NS2:1060-1066)")
+        if needs_autograd(self, x if x.is_floating_point() else None) or not x.is_cuda:
+            from .autograd_path import duration_pitch_autograd
+            return duration_pitch_autograd(self, x, encoded_prompts)
+        return self._forward_hip(x, encoded_prompts)
+
+    def refresh_weights(self):
+        self._cache.refresh(self.parameters())
+
+    # ------------------------------------------------------------------ HIP path
+    def _build_packed(self):
+        prec = _PRECISIONS[self.precision]
+
+        def f32(t):
+            return t.detach().float().contiguous()
+
+        trunks = []
+        for tr in (self.to_duration_pred, self.to_pitch_pred):
+            layers = []
+            for convs, norm, attn in tr.layers:
+                if tr.use_resnet_block:
+                    cs = [[(ops.PackedWeight(f32(b.proj.weight), precision=prec), f32(b.proj.bias), f32(b.norm.weight),
+                            f32(b.norm.bias), b.norm.num_groups, b.norm.eps) for b in rb.blocks] for rb in convs]
+                else:
+                    cs = [(ops.PackedWeight(f32(cb[1].weight), precision=prec), f32(cb[1].bias)) for cb in convs]
+                layers.append(dict(convs=cs, gamma=f32(norm.gamma), q=ops.PackedWeight(f32(attn.to_q.weight), precision=prec),
+                                   kv=ops.PackedWeight(f32(attn.to_kv.weight), precision=prec),
+                                   out=ops.PackedWeight(f32(attn.to_out.weight), precision=prec)))
+            head = tr.to_pred[0]
+            trunks.append(dict(layers=layers, w_pred=f32(head.weight).reshape(-1), b_pred=f32(head.bias)))
+        return trunks
+
+    @torch.no_grad()
+    def _forward_hip(self, x, encoded_prompts):
+        if self.training and self.dropout > 0:
+            raise NotImplementedError("dropout is a training-time feature; the HIP path is inference-only (call .eval(), or run "
+                                      "under autograd for the composite)")
+        if isinstance(self.phoneme_token_emb, nn.Embedding):
+            V = self.phoneme_token_emb.num_embeddings
+            if x.is_floating_point() or int(x.min()) < 0 or int(x.max()) >= V:
+                raise IndexError(f"phoneme token ids must be integers in [0, {V})")
+            x = ops.embedding(x, self.phoneme_token_emb.weight.detach().float().contiguous(), 0)
+        b, n, d = x.shape
+        np_ = encoded_prompts.shape[1]
+        if d != self.dim_hidden or encoded_prompts.shape[-1] != self.dim_hidden or encoded_prompts.shape[0] != b:
+            raise ValueError(f"phoneme encodings and encoded prompts must both be [b, *, {self.dim_hidden}] "
+                             f"(keys are cat(queries, prompts), NS2:1060-1061); got {tuple(x.shape)} and {tuple(encoded_prompts.shape)}")
+        prec = _PRECISIONS[self.precision]
+        packed = self._cache.get(self.parameters(), self._build_packed, extra=(self.precision,))
+        h0 = x.reshape(b * n, d).float().contiguous()
+        # the prompt rows of every attention context, split once: context planes [b, n + n_p] = [norm(x) rows | prompt rows]
+        pp = ops.split(encoded_prompts.reshape(b * np_, d).float().contiguous(), precision=prec)
+        ctx = ops._out_planes(b * (n + np_), d, x.device, prec)
+        ctx.buf.view(b, n + np_, -1)[:, n:].copy_(pp.buf.view(b, np_, -1))
+        outs = [self._trunk_hip(tr, h0, b, n, np_, ctx, prec) for tr in packed]
+        return outs[0].reshape(b, n).to(x.dtype), outs[1].reshape(b, n).to(x.dtype)
+
+    def _trunk_hip(self, tr, h, b, n, np_, ctx, prec):
+        k = self.to_pitch_pred.kernel_size
+        H, dh = self.to_pitch_pred.heads, self.to_pitch_pred.dim_head
+        conv_kw = dict(conv_taps=k, dilation=1, seq_len=n, pad_left=k // 2, precision=prec)
+        for L in tr["layers"]:
+            a = ops.split(h, precision=prec)
+            if self.to_pitch_pred.use_resnet_block:
+                for rb in L["convs"]:                # ResnetBlock: out = silu(gn(conv(... silu(gn(conv(x)))))) + x
+                    xin, last = h, len(rb) - 1
+                    for j, (pw, cb, gw, gb, groups, eps) in enumerate(rb):
+                        y = ops.linear_f32(pw, a, bias=cb, **conv_kw)
+                        if j < last:
+                            a = ops.groupnorm_silu(y, b, gw, gb, groups, eps, want_f32=False, precision=prec)
+                        else:
+                            h, a = ops.groupnorm_silu(y, b, gw, gb, groups, eps, resid=xin, precision=prec)
+            else:
+                for i, (pw, cb) in enumerate(L["convs"]):   # ConvBlock: conv + SiLU in the GEMM epilogue
+                    if i + 1 < len(L["convs"]):
+                        a = ops.linear_split(pw, a, bias=cb, act=1, **conv_kw)
+                    else:
+                        h = ops.linear_f32(pw, a, bias=cb, act=1, **conv_kw)
+            xn = ops.rmsnorm(h, gamma=L["gamma"], precision=prec)
+            ctx.buf.view(b, n + np_, -1)[:, :n].copy_(xn.buf.view(b, n, -1))
+            inner = H * dh
+            q = ops.linear_split(L["q"], xn, precision=prec, out_precision=2 if prec == 4 else None)   # attention operand format
+            kk, vt = ops.linear_qkv(L["kv"], ctx, seq_len=n + np_, split_col=inner, precision=prec)
+            o = ops.attention(q, kk, vt, b, H, n, n + np_, precision=prec, head_dim=dh)
+            h = ops.linear_f32(L["out"], o, resid=h, precision=prec)
+        return ops.row_dot(h, tr["w_pred"], tr["b_pred"], relu=True)

@@ -278,6 +278,60 @@ def embedding(ids: torch.Tensor, table: torch.Tensor, pad_id: int) -> torch.Tens
     return out
 
 
+def groupnorm_silu(x: torch.Tensor, B: int, weight: torch.Tensor, bias: torch.Tensor, groups: int = 8, eps: float = 1e-5,
+                   resid: Optional[torch.Tensor] = None, want_f32: bool = True, precision: Optional[int] = None):
+    """GroupNorm(groups, C) + SiLU (+ resid after the SiLU) over token-major fp32 rows x [B * n, C] (ns2_groupnorm_silu).
+    Returns the fp32 rows, the operand planes of `precision` (when given), or (rows, planes)."""
+    x = _f32(x)
+    M, C = x.shape
+    n = M // B
+    assert n * B == M, "rows must be B utterances of equal length"
+    lib = _lib.load()
+    ws = torch.empty(max(lib.ns2_groupnorm_workspace_bytes(B, n, C, groups), 16), dtype=torch.uint8, device=x.device)
+    of = torch.empty(M, C, dtype=torch.float32, device=x.device) if want_f32 else None
+    pl = _out_planes(M, C, x.device, precision) if precision is not None else None
+    check(lib.ns2_groupnorm_silu(x.data_ptr(), B, n, C, groups, _f32(weight).data_ptr(), _f32(bias).data_ptr(), float(eps),
+                                 _p(None if resid is None else _f32(resid)), _p(of), pl.hi if pl else None, pl.lo if pl else None,
+                                 C, pl.precision if pl else 3, ws.data_ptr(), ws.numel(), _stream()), "ns2_groupnorm_silu")
+    if of is not None and pl is not None:
+        return of, pl
+    return of if of is not None else pl
+
+
+# f0_to_coarse's fp32 constants, evaluated as the reference does (NS2:164-166)
+F0_MEL_MIN = float(1127 * torch.log(1 + torch.tensor(50.0) / 700))
+F0_MEL_MAX = float(1127 * torch.log(1 + torch.tensor(1100.0) / 700))
+
+
+def length_regulate(duration: torch.Tensor, pitch: torch.Tensor, enc: torch.Tensor, pitch_table: torch.Tensor) -> torch.Tensor:
+    """duration / pitch [B, n_ph], enc [B, n_ph, D], pitch_table [>= 256, D] -> the frame-aligned conditioning [B, D, n_frames]
+    of NaturalSpeech2.sample (ns2_length_regulate).  n_frames = the longest utterance's sum of int(duration): one host read,
+    as the reference's `.item()` (NS2:92)."""
+    duration, pitch, enc, table = _f32(duration), _f32(pitch), _f32(enc), _f32(pitch_table)
+    B, n_ph = duration.shape
+    D = enc.shape[-1]
+    assert pitch.shape == (B, n_ph) and enc.shape == (B, n_ph, D) and table.shape[1] == D and table.shape[0] >= 256
+    lib = _lib.load()
+    totals = torch.empty(B, dtype=torch.int32, device=duration.device)
+    check(lib.ns2_length_regulate_totals(duration.data_ptr(), B, n_ph, totals.data_ptr(), _stream()), "ns2_length_regulate_totals")
+    n_frames = int(totals.max().item())
+    out = torch.empty(B, D, n_frames, dtype=torch.float32, device=duration.device)
+    if n_frames > 0:
+        check(lib.ns2_length_regulate(duration.data_ptr(), pitch.data_ptr(), enc.data_ptr(), table.data_ptr(), B, n_ph, D, n_frames,
+                                      F0_MEL_MIN, F0_MEL_MAX, out.data_ptr(), _stream()), "ns2_length_regulate")
+    return out
+
+
+def row_dot(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, relu: bool = False) -> torch.Tensor:
+    """x [M, K] . w [K] (+ bias[0]) (ReLU) -> [M] (ns2_row_dot): a Linear(K, 1) head"""
+    x, w = _f32(x), _f32(w.reshape(-1))
+    M, K = x.shape
+    out = torch.empty(M, dtype=torch.float32, device=x.device)
+    check(_lib.load().ns2_row_dot(x.data_ptr(), K, M, K, w.data_ptr(), _p(None if bias is None else _f32(bias)), int(relu),
+                                  out.data_ptr(), _stream()), "ns2_row_dot")
+    return out
+
+
 def _skinny_ws(B, K, J, device):
     n = _lib.load().ns2_skinny_linear_workspace_bytes(B, K, J)
     return torch.empty(max(n, 16), dtype=torch.uint8, device=device), n
