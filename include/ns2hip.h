@@ -200,6 +200,35 @@ int ns2_length_regulate(const float* duration, const float* pitch, const float* 
  * null; K and ldx multiples of 4, x and w 16-byte aligned */
 int ns2_row_dot(const float* x, int ldx, int M, int K, const float* w, const float* bias, int relu, float* out, void* stream);
 
+/* ---- Aligner (aligner.py) and the text-conditioned training pass (NS2:1524-1602).  Lengths are int32 [B] on the device,
+ * clamped to [0, size] as create_mask (utils.py:28-33) would; nothing here reads device data on the host. */
+/* planes [M, ldo] <- ReLU(x [M, N]) in the operand format of `precision`, columns N .. ldo - 1 zero (AlignerNet's ReLUs between
+ * its convolutions, aligner.py:30-51); N % 4 == 0, ldo % 32 == 0 */
+int ns2_relu_split(const float* x, int M, int N, uint16_t* out_hi, uint16_t* out_lo, int ldo, int precision, void* stream);
+/* AlignerNet attention (aligner.py:72-90): queries [B * T, C], keys [B * n, C] fp32 token-major; aln_log [B, 1, T, n] =
+ * the Euclidean distance summed in fp32 (no negation, no temperature), -FLT_MAX at phonemes >= text_lens[b]; aln_soft
+ * [B, n, T] = softmax over phonemes, transposed (a fully masked row is uniform).  n <= 1024, C <= 256 */
+int ns2_align_attn(const float* queries, const float* keys, const int* text_lens, int B, int T, int n, int C, float* aln_log,
+                   float* aln_soft, void* stream);
+/* maximum_path (aligner.py:97-130) of value [B, t_x, t_y] fp32 under the prefix masks text_lens x mel_lens: path [B, t_x, t_y]
+ * 0/1 fp32, bit for bit the reference's (ties stay, direction 1 outside the mask, backtrack from row text_len - 1), and
+ * durations [B, t_x] int32 = its row sums.  t_x <= 1024, t_y <= 8192; workspace = ns2_maximum_path_workspace_bytes bytes
+ * (the per-column path rows, plus the direction bits when t_x_pad * t_y / 8 bytes exceed 128 KiB of LDS) */
+int64_t ns2_maximum_path_workspace_bytes(int B, int t_x, int t_y);
+int ns2_maximum_path(const float* value, const int* text_lens, const int* mel_lens, int B, int t_x, int t_y, float* path,
+                     int* durations, void* workspace, int64_t workspace_bytes, void* stream);
+/* average_over_durations (utils.py:4-26): pitch [B, T] (the reference's [B, 1, T]), durations [B, n] int32 -> out [B, n] = mean
+ * of the non-zero frames of each phoneme from fp32 prefix sums, 0 where none.  T, n <= 8192 */
+int ns2_average_over_durations(const float* pitch, const int* durations, int B, int T, int n, float* out, void* stream);
+/* backward of expand_encodings with durations (NS2:1449-1455, the forward is ns2_length_regulate): d_cond [B, D, n_frames],
+ * duration / pitch [B, n] fp32 -> d_enc [B, n, D] = sum of d_cond over each phoneme's frames, d_table [n_bins, D] (null: skip)
+ * = sum over (b, i) in ascending order of the rows of d_enc whose f0_to_coarse(pitch) is the bin.  No atomics: bit-reproducible.
+ * workspace = ns2_expand_backward_workspace_bytes(B, n) bytes */
+int64_t ns2_expand_backward_workspace_bytes(int B, int n);
+int ns2_expand_backward(const float* d_cond, const float* duration, const float* pitch, int B, int n, int D, int n_frames, int n_bins,
+                        float mel_min, float mel_max, float* d_enc, float* d_table, void* workspace, int64_t workspace_bytes,
+                        void* stream);
+
 /* one DDIM update (NS2:1396-1430): audio <- f(audio, model_out, times, times_next).  objective 0 'v', 1 'eps', 2 'x0';
  * schedule 0 sigmoid, 1 cosine, 2 linear (NS2:1133-1148) */
 int ns2_ddim_step(const float* audio, const float* model_out, float* out, const float* times, const float* times_next,

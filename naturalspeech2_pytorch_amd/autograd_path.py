@@ -197,3 +197,62 @@ def length_regulate(duration, pitch, enc, pitch_table):
     pe = torch.gather(pe, 1, ph[..., None].expand(-1, -1, pe.shape[-1]))
     out = torch.where(valid[..., None], e + pe, torch.zeros((), dtype=e.dtype, device=e.device))
     return out.transpose(1, 2)
+
+
+# ---- Aligner (aligner.py of the reference) and the text-conditioned training pass (utils.py:4-26, NS2:1449-1455)
+def aligner_net_autograd(net, queries, keys, mask=None):
+    """AlignerNet.forward (aligner.py:62-90): (attn [b, 1, T, n], attn_logp [b, 1, T, n]); attn_logp is the plain distance"""
+    k = F.conv1d(keys, net.key_layers[0].weight, net.key_layers[0].bias, padding=1).relu()
+    k = F.conv1d(k, net.key_layers[2].weight, net.key_layers[2].bias)
+    q = F.conv1d(queries, net.query_layers[0].weight, net.query_layers[0].bias, padding=1).relu()
+    q = F.conv1d(q, net.query_layers[2].weight, net.query_layers[2].bias).relu()
+    q = F.conv1d(q, net.query_layers[4].weight, net.query_layers[4].bias)
+    logp = torch.cdist(q.transpose(1, 2), k.transpose(1, 2))[:, None]
+    if mask is not None:
+        logp = logp.masked_fill(~mask.bool()[..., None, :], -torch.finfo(logp.dtype).max)
+    return logp.softmax(dim=-1), logp
+
+
+def maximum_path_composite(value, mask, const=None):
+    """maximum_path (aligner.py:97-130) as a PyTorch loop: the DP over columns from v = 0 (ties stay), directions forced to 1
+    outside the mask, the backtrack from row mask[:, :, 0].sum() - 1 with Python's negative indexing, the path times the mask"""
+    dev = value.device
+    neg = torch.tensor(float("-inf"), device=dev) if const is None else const
+    value = value * mask
+    b, t_x, t_y = value.shape
+    v = torch.zeros(b, t_x, dtype=torch.float32, device=dev)
+    rows = torch.arange(t_x, device=dev)
+    stay = torch.empty(b, t_x, t_y, dtype=torch.bool, device=dev)
+    for j in range(t_y):
+        above = torch.cat((neg.expand(b, 1).to(v.dtype), v[:, :-1]), dim=1)
+        s = v >= above
+        stay[:, :, j] = s
+        v = torch.where(rows[None] <= j, torch.where(s, v, above) + value[:, :, j], neg.to(v.dtype))
+    stay = stay | ~mask.bool()
+    idx = mask[:, :, 0].sum(1).long() - 1
+    path = torch.zeros(b, t_x, t_y, dtype=torch.float32, device=dev)
+    bi = torch.arange(b, device=dev)
+    for j in range(t_y - 1, -1, -1):
+        path[bi, idx, j] = 1
+        idx = idx + stay[bi, idx, j].long() - 1
+    return (path * mask.float()).to(value.dtype)
+
+
+def average_over_durations_composite(values, durs):
+    """utils.py:4-26: differences of fp32 prefix sums of the values and of their non-zero count at the phonemes' frame ends"""
+    ends = torch.cumsum(durs, dim=1).long()
+    starts = F.pad(ends[:, :-1], (1, 0))
+    nz = F.pad(torch.cumsum(values != 0.0, dim=2), (1, 0))
+    cs = F.pad(torch.cumsum(values, dim=2), (1, 0))
+    f = values.shape[1]
+    e, s = ends[:, None].expand(-1, f, -1), starts[:, None].expand(-1, f, -1)
+    sums = (torch.gather(cs, 2, e) - torch.gather(cs, 2, s)).to(values.dtype)
+    cnt = (torch.gather(nz, 2, e) - torch.gather(nz, 2, s)).to(values.dtype)
+    return torch.where(cnt == 0.0, cnt, sums / cnt).to(values.dtype)
+
+
+def expand_with_path(enc, path, pitch, table):
+    """expand_encodings (NS2:1449-1455): enc [b, n, D], path [b, n, T] 0/1, pitch [b, n] -> [b, D, T], the reference's two
+    0/1 einsums (each frame sums one product x * 1 with zeros)"""
+    pe = F.embedding(f0_to_coarse(pitch).long(), table)
+    return torch.einsum("bnt,bnd->bdt", path, enc) + torch.einsum("bnt,bnd->bdt", path, pe)

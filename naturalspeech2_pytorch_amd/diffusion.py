@@ -9,7 +9,8 @@ reference's own call signatures:
 What runs where.  The per-step path (Model + DDIM update), the codec's RVQ encode/decode, the two conditioning encoders
 built from the plain Transformer (`prompt_enc` = SpeechPromptEncoder, `phoneme_enc` = PhonemeEncoder) and, with
 `build_duration_pitch=True`, the DurationPitchPredictor and the length regulator behind `sample(text=...)` (NS2:1476-1483;
-duration_pitch.py) are HIP.  The rest of the conditioning front-end — Aligner, mel / pitch extraction, the tokenizer (SURVEY
+duration_pitch.py) and, with `build_aligner=True`, the Aligner and the expansion behind `forward(text=..., mel=..., pitch=...)`
+(NS2:1524-1602; aligner.py) are HIP.  The rest of the conditioning front-end — mel / pitch extraction, the tokenizer (SURVEY
 §2: OUT OF SCOPE) — is not rebuilt.  By default (no predictor: the state_dict has no `duration_pitch.*` keys) and for
 `forward`, a caller hands over what those modules would have produced through two extra keyword arguments that the reference
 signature tolerates (`forward` takes **kwargs):
@@ -81,7 +82,8 @@ class NaturalSpeech2(nn.Module):
                  audio_to_mel_kwargs: dict = dict(), scale=1., duration_loss_weight=1., pitch_loss_weight=1.,
                  aligner_loss_weight=1., aligner_bin_loss_weight=0.,
                  encoder_precision="exact",            # not in the reference: precision mode of the HIP encoders (and predictor)
-                 build_duration_pitch: bool = False):  # not in the reference: build the DurationPitchPredictor (sample(text=...))
+                 build_duration_pitch: bool = False,   # not in the reference: build the DurationPitchPredictor (sample(text=...))
+                 build_aligner: bool = False):         # not in the reference: build the Aligner (forward(text=..., mel=..., pitch=...))
         super().__init__()
         assert _is_denoiser(model), "model must be a Model (this package's, or compat.HipBackedModel over the reference's class)"
         self.conditional = model.condition_on_prompt
@@ -102,7 +104,15 @@ class NaturalSpeech2(nn.Module):
             if build_duration_pitch:                                                  # NS2:1234
                 from .duration_pitch import DurationPitchPredictor
                 self.duration_pitch = DurationPitchPredictor(dim=duration_pitch_dim, precision=encoder_precision)
-            # Aligner, AudioToMel, ForwardSumLoss / BinLoss (NS2:1224-1240): out of scope, not built
+            if build_aligner:                                                         # NS2:1235, 1238-1239
+                from .aligner import Aligner, BinLoss, ForwardSumLoss
+                self.aligner = Aligner(dim_in=aligner_dim_in, dim_hidden=aligner_dim_hidden, attn_channels=aligner_attn_channels,
+                                       precision=encoder_precision)
+                self.aligner_loss = ForwardSumLoss()
+                self.bin_loss = BinLoss()
+            # AudioToMel (NS2:1224-1230): out of scope, not built
+        else:
+            assert not build_aligner, "the Aligner belongs to a conditional model (condition_on_prompt=True)"
 
         assert codec is None or model.dim == codec.codebook_dim, \
             f"transformer model dimension {model.dim} must be equal to codec dimension {codec.codebook_dim}"   # NS2:1244
@@ -253,7 +263,7 @@ class NaturalSpeech2(nn.Module):
     def refresh_weights(self):
         """run boundary: every HIP module re-checks its packed weights against the parameters' CONTENT (writes through `.data` --
         what ema_pytorch does to the copy of this whole object it samples from, NS2:1793-1801 -- bump no version counter)"""
-        for name in ("model", "prompt_enc", "phoneme_enc", "duration_pitch", "codec"):
+        for name in ("model", "prompt_enc", "phoneme_enc", "duration_pitch", "aligner", "codec"):
             mod = getattr(self, name, None)
             if mod is not None and hasattr(mod, "refresh_weights"):
                 mod.refresh_weights()
@@ -307,14 +317,69 @@ class NaturalSpeech2(nn.Module):
         return audio
 
     # ------------------------------------------------------------------ training loss (NS2:1503-1684)
+    def text_forward_cond(self, text, text_lens, mel, mel_lens, pitch, prompt_enc, return_aux_losses=False):
+        """NS2:1524-1602 up to the conditioning: masks from the lengths, the Aligner, average_over_durations and the expansion
+        of the phoneme encodings + pitch embeddings into exactly T_mel = mel.shape[-1] frames.  Unlike the reference, the
+        caller's `text_lens` / `mel_lens` are not clamped in place: clamped copies are used.  On CUDA the Aligner runs its HIP
+        path under no_grad (the returned loss depends on it only through the hard path) and the lengths go straight to the
+        kernels: no host read.  With return_aux_losses the Aligner runs its differentiable composite and the auxiliary terms
+        of NS2:1587-1602 are returned as a dict.  -> (cond, aux or None)"""
+        from .aligner import average_over_durations, create_mask, expand_encodings
+        b, n = text.shape[0], text.shape[-1]
+        dev = text.device
+        text_lens = torch.full((b,), n, device=dev, dtype=torch.long) if text_lens is None else text_lens.clamp(max=n)
+        T = mel.shape[-1]
+        mel_lens = torch.full((b,), T, device=dev, dtype=torch.long) if mel_lens is None else mel_lens.clamp(max=T)
+        phoneme_enc = self.phoneme_enc(text)                                           # [b, n, dim_hidden]
+        if return_aux_losses or not phoneme_enc.is_cuda:
+            text_mask, mel_mask = create_mask(text_lens, n)[:, None], create_mask(mel_lens, T)[:, None]
+            with torch.set_grad_enabled(return_aux_losses and torch.is_grad_enabled()):
+                aln_hard, aln_soft, aln_log, aln_mask = self.aligner._forward_composite(phoneme_enc, text_mask, mel, mel_mask)
+        else:
+            with torch.no_grad():
+                aln_hard, aln_soft, aln_log, aln_mask = self.aligner.forward_lengths(phoneme_enc.detach(), text_lens, mel, mel_lens)
+        pitch = average_over_durations(pitch, aln_hard)                                # [b, 1, n]
+        cond = expand_encodings(phoneme_enc, aln_hard, aln_mask, pitch[:, 0], self.pitch_emb.weight)
+        if not return_aux_losses:
+            return cond, None
+        assert hasattr(self, "duration_pitch"), "return_aux_losses needs the predictor: construct with build_duration_pitch=True"
+        duration_pred, pitch_pred = self.duration_pitch(phoneme_enc, prompt_enc)
+        duration_loss = F.l1_loss(aln_hard, duration_pred)
+        pitch_loss = F.l1_loss(pitch[:, 0], pitch_pred)
+        align_loss = self.aligner_loss(aln_log, text_lens, mel_lens)
+        bin_loss = None
+        if self.aligner_bin_loss_weight > 0.:
+            bin_loss = self.bin_loss(aln_mask, aln_log, text_lens) * self.aligner_bin_loss_weight
+            align_loss = align_loss + bin_loss
+        aux = duration_loss * self.duration_loss_weight + pitch_loss * self.pitch_loss_weight + align_loss * self.aligner_loss_weight
+        return cond, dict(duration=duration_loss, pitch=pitch_loss, align=align_loss, bin=bin_loss, aux=aux)
+
     def forward(self, audio, text=None, text_lens=None, mel=None, mel_lens=None, codes=None, prompt=None, pitch=None,
-                *args, cond=None, prompt_enc=None, times=None, noise=None, **kwargs):
+                *args, cond=None, prompt_enc=None, times=None, noise=None, return_aux_losses=False, **kwargs):
         """Reference signature; `cond`, `prompt_enc` (module docstring) and `times`, `noise` (deterministic parity tests) are
-        the keyword-only extras.  The model call runs the autograd composite when gradients are required."""
+        the keyword-only extras.  The model call runs the autograd composite when gradients are required.
+
+        With `build_aligner=True` and no `cond`, `text`, `mel` [b, aligner_dim_in, T_mel] and `pitch` [b, 1, T_mel] derive the
+        conditioning as NS2:1524-1602 does (text_forward_cond).  The value returned is the reference's: its auxiliary duration /
+        pitch / alignment losses are computed and dropped upstream, so they are not computed here.  `return_aux_losses=True`
+        (not in the reference, needs build_duration_pitch=True) returns (loss, dict(duration=, pitch=, align=, bin=, aux=)),
+        the only way to train the Aligner and the predictor."""
         is_raw = audio.ndim == 2
         p_enc = None
+        aux = None
+        if return_aux_losses and (not self.conditional or cond is not None):
+            raise ValueError("return_aux_losses needs the text-conditioned path: text=, mel=, pitch= and no cond=")
         if self.conditional:
             p_enc = self._encode_prompt(prompt, prompt_enc)
+            if cond is None and hasattr(self, "aligner"):
+                assert text is not None, "forward(text=...) needs the phoneme ids"
+                if mel is None:
+                    raise NotImplementedError("forward(text=...) without `mel` needs AudioToMel (NS2:1561-1567), which is outside "
+                                              "the HIP hot path: pass the mel frames as `mel=` [b, aligner_dim_in, T_mel]")
+                if pitch is None:
+                    raise NotImplementedError("forward(text=...) without `pitch` needs the pyworld / kaldi pitch extraction "
+                                              "(NS2:1546-1559), which is outside the HIP hot path: pass `pitch=` [b, 1, T_mel]")
+                cond, aux = self.text_forward_cond(text, text_lens, mel, mel_lens, pitch, p_enc, return_aux_losses)
             if cond is None:
                 raise NotImplementedError(
                     "forward(text=..., mel=..., pitch=...) derives the aligned conditioning with the Aligner, the "
@@ -343,9 +408,10 @@ class NaturalSpeech2(nn.Module):
         # [b, 1, b] and the mean equals mean(loss) * mean(weight) -- kept bit-compatible with the reference.
         loss = (loss * weight).mean()
         if self.rvq_cross_entropy_loss_weight == 0 or codes is None:                  # NS2:1672-1673
-            return loss
+            return loss if aux is None else (loss, aux)
         x_start = {"x0": lambda: pred, "eps": lambda: _safe_div(audio - sigma * pred, alpha),
                    "v": lambda: alpha * audio - sigma * pred}[self.objective]()
         assert self.codec is not None and hasattr(self.codec, "rq"), "the RVQ cross-entropy term needs codec.rq (NS2:1682)"
         _, ce_loss = self.codec.rq(x_start, codes)
-        return loss + self.rvq_cross_entropy_loss_weight * ce_loss                    # NS2:1684 (duration_pitch_loss is 0 upstream)
+        loss = loss + self.rvq_cross_entropy_loss_weight * ce_loss                    # NS2:1684 (duration_pitch_loss is 0 upstream)
+        return loss if aux is None else (loss, aux)

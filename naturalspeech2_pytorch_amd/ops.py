@@ -431,3 +431,83 @@ def rvq_decode(codes: torch.Tensor, codebooks: torch.Tensor) -> torch.Tensor:
     check(_lib.load().ns2_rvq_decode(codes.contiguous().data_ptr(), cb.data_ptr(), emb.data_ptr(), M, Q, C, D, _stream()),
           "ns2_rvq_decode")
     return emb
+
+
+# ---- Aligner and the text-conditioned training pass (csrc/aligner.hip).  Lengths are int32 [B] device tensors.
+def _lens(t: torch.Tensor) -> torch.Tensor:
+    assert t.is_cuda and t.dim() == 1, "lengths are [B] CUDA tensors"
+    return t.to(torch.int32).contiguous()
+
+
+def relu_split(x: torch.Tensor, ldo: Optional[int] = None, precision: int = 3) -> Planes:
+    """fp32 [M, N] -> operand planes of ReLU(x) [M, ldo], padding columns zero (ns2_relu_split)"""
+    x = _f32(x)
+    M, N = x.shape
+    out = _out_planes(M, ldo or round_up(N, 32), x.device, precision)
+    check(_lib.load().ns2_relu_split(x.data_ptr(), M, N, out.hi, out.lo, out.ld, out.precision, _stream()), "ns2_relu_split")
+    return out
+
+
+def align_attn(queries: torch.Tensor, keys: torch.Tensor, text_lens: torch.Tensor, B: int):
+    """queries [B * T, C], keys [B * n, C] -> (aln_log [B, 1, T, n], aln_soft [B, n, T]) (ns2_align_attn)"""
+    q, k = _f32(queries), _f32(keys)
+    C = q.shape[1]
+    T, n = q.shape[0] // B, k.shape[0] // B
+    tl = _lens(text_lens)             # held until the launch: a freed temporary could be reused by the next allocation
+    log = torch.empty(B, 1, T, n, dtype=torch.float32, device=q.device)
+    soft = torch.empty(B, n, T, dtype=torch.float32, device=q.device)
+    check(_lib.load().ns2_align_attn(q.data_ptr(), k.data_ptr(), tl.data_ptr(), B, T, n, C, log.data_ptr(),
+                                     soft.data_ptr(), _stream()), "ns2_align_attn")
+    return log, soft
+
+
+def maximum_path(value: torch.Tensor, text_lens: torch.Tensor, mel_lens: torch.Tensor):
+    """value [B, t_x, t_y] fp32 -> (path [B, t_x, t_y] 0/1 fp32, durations [B, t_x] int32) (ns2_maximum_path)"""
+    value = _f32(value)
+    B, t_x, t_y = value.shape
+    lib = _lib.load()
+    n = lib.ns2_maximum_path_workspace_bytes(B, t_x, t_y)
+    ws = torch.empty(max(n, 16), dtype=torch.uint8, device=value.device)
+    path = torch.empty_like(value)
+    dur = torch.empty(B, t_x, dtype=torch.int32, device=value.device)
+    tl, ml = _lens(text_lens), _lens(mel_lens)       # held until the launch
+    check(lib.ns2_maximum_path(value.data_ptr(), tl.data_ptr(), ml.data_ptr(), B, t_x, t_y, path.data_ptr(),
+                               dur.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "ns2_maximum_path")
+    return path, dur
+
+
+def average_over_durations(pitch: torch.Tensor, durations: torch.Tensor) -> torch.Tensor:
+    """pitch [B, T] fp32, durations [B, n] int -> [B, n] (ns2_average_over_durations)"""
+    pitch = _f32(pitch)
+    d = durations.to(torch.int32).contiguous()
+    B, T = pitch.shape
+    out = torch.empty(B, d.shape[1], dtype=torch.float32, device=pitch.device)
+    check(_lib.load().ns2_average_over_durations(pitch.data_ptr(), d.data_ptr(), B, T, d.shape[1], out.data_ptr(), _stream()),
+          "ns2_average_over_durations")
+    return out
+
+
+def expand_frames(duration: torch.Tensor, pitch: torch.Tensor, enc: torch.Tensor, pitch_table: torch.Tensor, n_frames: int) -> torch.Tensor:
+    """the length regulator into exactly n_frames frames (ns2_length_regulate, no host read): [B, D, n_frames]"""
+    duration, pitch, enc, table = _f32(duration), _f32(pitch), _f32(enc), _f32(pitch_table)
+    B, n_ph = duration.shape
+    D = enc.shape[-1]
+    assert pitch.shape == (B, n_ph) and enc.shape == (B, n_ph, D) and table.shape[1] == D and table.shape[0] >= 256
+    out = torch.empty(B, D, n_frames, dtype=torch.float32, device=duration.device)
+    check(_lib.load().ns2_length_regulate(duration.data_ptr(), pitch.data_ptr(), enc.data_ptr(), table.data_ptr(), B, n_ph, D, n_frames,
+                                          F0_MEL_MIN, F0_MEL_MAX, out.data_ptr(), _stream()), "ns2_length_regulate")
+    return out
+
+
+def expand_backward(d_cond: torch.Tensor, duration: torch.Tensor, pitch: torch.Tensor, n_bins: Optional[int]):
+    """gradients of expand_frames: (d_enc [B, n, D], d_table [n_bins, D] or None) (ns2_expand_backward)"""
+    d_cond, duration, pitch = _f32(d_cond), _f32(duration), _f32(pitch)
+    B, D, n_frames = d_cond.shape
+    n = duration.shape[1]
+    lib = _lib.load()
+    ws = torch.empty(max(lib.ns2_expand_backward_workspace_bytes(B, n), 16), dtype=torch.uint8, device=d_cond.device)
+    d_enc = torch.empty(B, n, D, dtype=torch.float32, device=d_cond.device)
+    d_table = torch.empty(n_bins, D, dtype=torch.float32, device=d_cond.device) if n_bins else None
+    check(lib.ns2_expand_backward(d_cond.data_ptr(), duration.data_ptr(), pitch.data_ptr(), B, n, D, n_frames, n_bins or 0, F0_MEL_MIN,
+                                  F0_MEL_MAX, d_enc.data_ptr(), _p(d_table), ws.data_ptr(), ws.numel(), _stream()), "ns2_expand_backward")
+    return d_enc, d_table
