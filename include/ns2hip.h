@@ -229,6 +229,15 @@ int ns2_expand_backward(const float* d_cond, const float* duration, const float*
                         float mel_min, float mel_max, float* d_enc, float* d_table, void* workspace, int64_t workspace_bytes,
                         void* stream);
 
+/* ---- AudioToMel (audio_to_mel.py, NS2:181-224): audio [B, L] fp32 -> out [B, n_mels, T], T = 1 + L / hop_length.  The frames
+ * are those of torch.stft(center=True, pad_mode="reflect", onesided=True), power |X|^2, mel = fb^T power summed in ascending
+ * bins, and with log_db 10 log10(max(mel, 1e-10)).  Tables (host-built, fp64 rounded to fp32): window [n_fft] (Hann zero-padded
+ * centred), twiddle [n_fft] complex (cos, sin)(-2 pi k / n_fft); the filterbank compactly as fb_meta [3][n_mels] int32 = first
+ * bin, number of bins, offset into fb_w [n_w], with first + number <= n_bins (the bins read) <= n_fft / 2 + 1.  n_fft a power of
+ * two in [256, 2048], 1 <= hop_length <= n_fft, n_mels <= 256, L > n_fft / 2.  No atomics: bit-reproducible per utterance. */
+int ns2_audio_to_mel(const float* audio, int B, int64_t L, int n_fft, int hop_length, const float* window, const float* twiddle,
+                     const int* fb_meta, const float* fb_w, int n_w, int n_mels, int n_bins, int log_db, float* out, void* stream);
+
 /* one DDIM update (NS2:1396-1430): audio <- f(audio, model_out, times, times_next).  objective 0 'v', 1 'eps', 2 'x0';
  * schedule 0 sigmoid, 1 cosine, 2 linear (NS2:1133-1148) */
 int ns2_ddim_step(const float* audio, const float* model_out, float* out, const float* times, const float* times_next,

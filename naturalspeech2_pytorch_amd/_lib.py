@@ -85,6 +85,7 @@ SIGNATURES = {
     "ns2_average_over_durations": (I, [P, P, I, I, I, P, P]),
     "ns2_expand_backward_workspace_bytes": (L, [I, I]),
     "ns2_expand_backward": (I, [P, P, P, I, I, I, I, I, F, F, P, P, P, L, P]),
+    "ns2_audio_to_mel": (I, [P, I, L, I, I, P, P, P, P, I, I, I, I, P, P]),
     "ns2_ddim_step": (I, [P, P, P, P, P, I, L, I, I, F, P]),
     "ns2_cfg_mix": (I, [P, P, P, L, F, P]),
     "ns2_seanet_prep": (I, [P, I, I, P, I, I, L, I, I, I, I, P, P, I, I, P]),

@@ -10,7 +10,8 @@ What runs where.  The per-step path (Model + DDIM update), the codec's RVQ encod
 built from the plain Transformer (`prompt_enc` = SpeechPromptEncoder, `phoneme_enc` = PhonemeEncoder) and, with
 `build_duration_pitch=True`, the DurationPitchPredictor and the length regulator behind `sample(text=...)` (NS2:1476-1483;
 duration_pitch.py) and, with `build_aligner=True`, the Aligner and the expansion behind `forward(text=..., mel=..., pitch=...)`
-(NS2:1524-1602; aligner.py) are HIP.  The rest of the conditioning front-end — mel / pitch extraction, the tokenizer (SURVEY
+(NS2:1524-1602; aligner.py) are HIP, and so is AudioToMel (audio_to_mel.py), which turns raw audio into the Aligner's mel
+frames when `forward` gets no `mel`.  The rest of the conditioning front-end — pitch extraction, the tokenizer (SURVEY
 §2: OUT OF SCOPE) — is not rebuilt.  By default (no predictor: the state_dict has no `duration_pitch.*` keys) and for
 `forward`, a caller hands over what those modules would have produced through two extra keyword arguments that the reference
 signature tolerates (`forward` takes **kwargs):
@@ -96,6 +97,11 @@ class NaturalSpeech2(nn.Module):
         if self.conditional:                                                          # NS2:1218-1240, in-scope members only
             from .encoders import PhonemeEncoder, SpeechPromptEncoder
             self.mel_hop_length = mel_hop_length
+            from .audio_to_mel import AudioToMel                                       # NS2:1221-1230 (no parameters, no buffers)
+            audio_to_mel_kwargs = dict(audio_to_mel_kwargs)                           # the caller's dict is not updated
+            if self.target_sample_hz is not None:
+                audio_to_mel_kwargs.update(sampling_rate=self.target_sample_hz)
+            self.audio_to_mel = AudioToMel(n_mels=aligner_dim_in, hop_length=mel_hop_length, **audio_to_mel_kwargs)
             self.calc_pitch_with_pyworld = calc_pitch_with_pyworld
             self.phoneme_enc = PhonemeEncoder(tokenizer=tokenizer, num_tokens=num_phoneme_tokens, precision=encoder_precision)
             self.prompt_enc = SpeechPromptEncoder(dim_codebook=dim_codebook, precision=encoder_precision)
@@ -110,7 +116,6 @@ class NaturalSpeech2(nn.Module):
                                        precision=encoder_precision)
                 self.aligner_loss = ForwardSumLoss()
                 self.bin_loss = BinLoss()
-            # AudioToMel (NS2:1224-1230): out of scope, not built
         else:
             assert not build_aligner, "the Aligner belongs to a conditional model (condition_on_prompt=True)"
 
@@ -373,12 +378,16 @@ class NaturalSpeech2(nn.Module):
             p_enc = self._encode_prompt(prompt, prompt_enc)
             if cond is None and hasattr(self, "aligner"):
                 assert text is not None, "forward(text=...) needs the phoneme ids"
-                if mel is None:
-                    raise NotImplementedError("forward(text=...) without `mel` needs AudioToMel (NS2:1561-1567), which is outside "
-                                              "the HIP hot path: pass the mel frames as `mel=` [b, aligner_dim_in, T_mel]")
+                if mel is None and not is_raw:
+                    raise NotImplementedError("forward(text=...) without `mel` computes it with AudioToMel (NS2:1561-1567), which "
+                                              "needs raw audio [b, samples], not latents: pass the raw audio, or the mel frames as "
+                                              "`mel=` [b, aligner_dim_in, T_mel]")
                 if pitch is None:
                     raise NotImplementedError("forward(text=...) without `pitch` needs the pyworld / kaldi pitch extraction "
                                               "(NS2:1546-1559), which is outside the HIP hot path: pass `pitch=` [b, 1, T_mel]")
+                if mel is None:                                                       # NS2:1561-1567; mel_lens default to full
+                    with torch.no_grad():
+                        mel = self.audio_to_mel(audio)[..., :pitch.shape[-1]]
                 cond, aux = self.text_forward_cond(text, text_lens, mel, mel_lens, pitch, p_enc, return_aux_losses)
             if cond is None:
                 raise NotImplementedError(

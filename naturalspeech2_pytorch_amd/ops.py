@@ -511,3 +511,20 @@ def expand_backward(d_cond: torch.Tensor, duration: torch.Tensor, pitch: torch.T
     check(lib.ns2_expand_backward(d_cond.data_ptr(), duration.data_ptr(), pitch.data_ptr(), B, n, D, n_frames, n_bins or 0, F0_MEL_MIN,
                                   F0_MEL_MAX, d_enc.data_ptr(), _p(d_table), ws.data_ptr(), ws.numel(), _stream()), "ns2_expand_backward")
     return d_enc, d_table
+
+
+# ---- AudioToMel (csrc/audio_to_mel.hip)
+def audio_to_mel(audio: torch.Tensor, n_fft: int, hop_length: int, n_mels: int, log: bool, plan: dict) -> torch.Tensor:
+    """audio [B, L] fp32 -> [B, n_mels, 1 + L // hop_length] (ns2_audio_to_mel); `plan`: the device tables of
+    audio_to_mel._plan (window, twiddle, meta, weights) and their sizes n_w, n_bins"""
+    audio = _f32(audio)
+    B, L = audio.shape
+    T = 1 + L // hop_length
+    out = torch.empty(B, n_mels, T, dtype=torch.float32, device=audio.device)
+    lib = _lib.load()
+    for b0 in range(0, B, 65535):                 # grid.y holds at most 65535 utterances
+        nb = min(65535, B - b0)
+        check(lib.ns2_audio_to_mel(audio[b0].data_ptr(), nb, L, n_fft, hop_length, plan["window"].data_ptr(),
+                                   plan["twiddle"].data_ptr(), plan["meta"].data_ptr(), plan["weights"].data_ptr(), plan["n_w"],
+                                   n_mels, plan["n_bins"], int(bool(log)), out[b0].data_ptr(), _stream()), "ns2_audio_to_mel")
+    return out
