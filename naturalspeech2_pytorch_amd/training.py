@@ -29,6 +29,7 @@ of the conditioned model (NS2:532-579) runs on the same Functions (`_resampler`)
 chain rule, tap flips, shifts and layouts of THIS file are checked against torch autograd without a GPU; the kernels behind
 `HipBackend` are checked one by one and end to end on the MI355X (`tests/test_backward_gpu.py`).
 """
+import contextlib
 import ctypes
 import math
 import weakref
@@ -63,6 +64,31 @@ def _p(t):
     return None if t is None else t.data_ptr()
 
 
+class _Pack:
+    """one entry of `_PackedCache.map`"""
+    __slots__ = ("pw", "sig", "shapes", "src", "refs", "pass_id", "parts")
+
+    def __init__(self, pw, sig, shapes, src, refs, pass_id, parts):
+        self.pw = pw                # the PackedWeight
+        self.sig = sig              # ((data_ptr, _version) of every parameter) when the pack was last refreshed
+        self.shapes = shapes        # shapes of the source matrices: a refresh in place needs the same ones
+        self.src = src              # the source tensors, kept alive until the stream has consumed them
+        self.refs = refs            # weak references to the parameters
+        self.pass_id = pass_id      # the pass that last refreshed the pack
+        self.parts = parts          # where the pack's values live in the parameters' storage (`get`), or None
+
+
+class _RepackTable:
+    """the one launch per pass (ns2_weights_repack, then ns2_weights_retile for packs with tile images): this object holds everything
+    the two launches read -- the device descriptor table and the array of tiled handles"""
+    __slots__ = ("sig", "table", "n", "total", "keys", "tiled", "nt")
+
+    def __init__(self, sig, table, n, total, keys, tiled):
+        self.sig, self.table, self.n, self.total, self.keys = sig, table, n, total, keys
+        self.nt = len(tiled)
+        self.tiled = (ctypes.c_void_p * self.nt)(*tiled) if tiled else None
+
+
 class _PackedCache:
     """Packed weights of a training run: packed once, refreshed IN PLACE (`ns2_weight_update`: no allocation, no
     synchronisation).  When: the first request of every training PASS (`begin_pass`, called by `model_forward_train`) for a weight
@@ -79,7 +105,7 @@ class _PackedCache:
         self.map = {}
         self.precision = precision
         self.pass_id = 0
-        self._table = None          # (signature, device table, parts kept alive, n, total_blocks): every trainable pack, one launch per pass
+        self._table = None          # _RepackTable: every trainable pack, one launch per pass
         self.lean = self.LEAN       # give mixed linear packs the tile images of the lean kernel (class attribute: the A/B of tools/exp_graphed_train.py)
 
     # ---- one launch per pass (ns2_weights_repack): possible once every entry has told where its values live (`parts`)
@@ -102,52 +128,52 @@ class _PackedCache:
 
     def _signature(self):
         # (storage and trainability of every parameter: a re-allocated, frozen or unfrozen parameter rebuilds the table)
-        return tuple((k, tuple((p.data_ptr(), p.requires_grad) for p in (r() for r in v[4]) if p is not None)) for k, v in self.map.items())
+        return tuple((k, tuple((p.data_ptr(), p.requires_grad) for p in (r() for r in v.refs) if p is not None)) for k, v in self.map.items())
 
     def _repack_all(self):
         """every trainable entry with a `parts` description in one launch; False when some entry cannot be described"""
-        if not self.map or any(v[6] is None or any(r() is None for r in v[4]) for v in self.map.values()):
+        if not self.map or any(v.parts is None or any(r() is None for r in v.refs) for v in self.map.values()):
             return False
         lib = _lib.load()
         sig = self._signature()
-        if self._table is None or self._table[0] != sig:
+        if self._table is None or self._table.sig != sig:
             parts, keys = [], set()
             for k, v in self.map.items():
-                params = [r() for r in v[4]]
+                params = [r() for r in v.refs]
                 if not any(p.requires_grad for p in params):
                     continue
                 keys.add(k)
-                for (idx, mode, row0, col0) in v[6]:
-                    parts.append(self._part(_lib.RepackPart, v[0], params[idx], mode, row0, col0))
+                for (idx, mode, row0, col0) in v.parts:
+                    parts.append(self._part(_lib.RepackPart, v.pw, params[idx], mode, row0, col0))
             if not parts:
                 return False
             arr = (_lib.RepackPart * len(parts))(*parts)
             nbytes = lib.ns2_weights_repack_table_bytes(len(parts))
-            dev = next(r() for v in self.map.values() for r in v[4]).device
+            dev = next(r() for v in self.map.values() for r in v.refs).device
             table = torch.empty(nbytes, dtype=torch.uint8, device=dev)
             total = ctypes.c_int64(0)
             check(lib.ns2_weights_repack_build(arr, len(parts), table.data_ptr(), nbytes, ctypes.byref(total), _s()), "ns2_weights_repack_build")
-            tiled = [self.map[k][0].handle.value for k in keys if getattr(self.map[k][0], "tiled", False)]
-            self._table = (sig, table, len(parts), total.value, keys, (ctypes.c_void_p * len(tiled))(*tiled) if tiled else None, len(tiled))
-        _, table, n, total, _, tiled, nt = self._table
-        check(lib.ns2_weights_repack(table.data_ptr(), n, total, _s()), "ns2_weights_repack")
-        if nt:                                # the lean kernels' tile images follow their packs (one small launch per tiled weight)
-            check(lib.ns2_weights_retile(tiled, nt, _s()), "ns2_weights_retile")
+            tiled = [self.map[k].pw.handle.value for k in keys if getattr(self.map[k].pw, "tiled", False)]
+            self._table = _RepackTable(sig, table, len(parts), total.value, keys, tiled)
+        t = self._table
+        check(lib.ns2_weights_repack(t.table.data_ptr(), t.n, t.total, _s()), "ns2_weights_repack")
+        if t.nt:                              # the lean kernels' tile images follow their packs (one small launch per tiled weight)
+            check(lib.ns2_weights_retile(t.tiled, t.nt, _s()), "ns2_weights_retile")
         return True
 
     def begin_pass(self):
         self.pass_id += 1
         if _WEIGHTS_FROZEN:                  # `with training.weights_unchanged():` -- the packs of the last pass are these weights' (stamp them fresh)
-            for k, v in list(self.map.items()):
-                self.map[k] = (v[0], v[1], v[2], v[3], v[4], self.pass_id, v[6])
+            for v in self.map.values():
+                v.pass_id = self.pass_id
             return
         if self.pass_id > 1 and self._repack_all():
-            for k in self._table[4]:                                         # what the launch re-packed is fresh for this pass
+            for k in self._table.keys:                                       # what the launch re-packed is fresh for this pass
                 v = self.map[k]                                              # (a frozen weight is not in the table: its version rule stands)
-                self.map[k] = (v[0], tuple((p.data_ptr(), p._version) for p in (r() for r in v[4])), v[2], v[3], v[4], self.pass_id, v[6])
+                v.sig, v.pass_id = tuple((p.data_ptr(), p._version) for p in (r() for r in v.refs)), self.pass_id
 
     def _purge(self):
-        dead = [k for k, v in self.map.items() if any(r() is None for r in v[4])]
+        dead = [k for k, v in self.map.items() if any(r() is None for r in v.refs)]
         for k in dead:
             del self.map[k]
         if dead:
@@ -160,27 +186,27 @@ class _PackedCache:
         `make_src` builds the same matrix as a tensor for the first pack (and for entries without `parts`)."""
         sig = tuple((p.data_ptr(), p._version) for p in params)
         hit = self.map.get(key)
-        if hit is not None and any(r() is not p for r, p in zip(hit[4], params)):
+        if hit is not None and any(r() is not p for r, p in zip(hit.refs, params)):
             hit = None
-        refs = tuple(weakref.ref(p) for p in params)
         if hit is None:
             self._purge()                    # a miss is rare (first step of a model): drop the packs of models that no longer exist
             self._table = None
-        if hit is not None and hit[1] == sig and (hit[5] == self.pass_id or not any(p.requires_grad for p in params)):
-            return hit[0]
+        if hit is not None and hit.sig == sig and (hit.pass_id == self.pass_id or not any(p.requires_grad for p in params)):
+            return hit.pw
         src = make_src()
         src = src if isinstance(src, tuple) else (src, None)
         w, extra = (t.detach().float().contiguous() if t is not None else None for t in src)
-        if hit is not None and hit[2] == (tuple(w.shape), None if extra is None else tuple(extra.shape)):
-            check(_lib.load().ns2_weight_update(hit[0].handle, w.data_ptr(), _p(extra), _s()), "ns2_weight_update")
-            self.map[key] = (hit[0], sig, hit[2], (w, extra), refs, self.pass_id, parts)  # keep the sources alive until the stream has consumed them
-            return hit[0]
+        shapes = (tuple(w.shape), None if extra is None else tuple(extra.shape))
+        if hit is not None and hit.shapes == shapes:
+            check(_lib.load().ns2_weight_update(hit.pw.handle, w.data_ptr(), _p(extra), _s()), "ns2_weight_update")
+            hit.sig, hit.src, hit.pass_id, hit.parts = sig, (w, extra), self.pass_id, parts
+            return hit.pw
         pw = ops.PackedWeight(w, extra1x1=extra, precision=self.precision, **pack_kw)
         if self.precision == 4 and w.ndim == 2 and extra is None and not pack_kw.get("geglu") and w.shape[1] >= 96 and self.lean:
             pw.tile_linear()                 # round 6: the lean mixed linear kernel (csrc/gemm3_kernel.h) for the forward and dgrad products
             pw.tiled = True                  # on whole 256-row tiles -- bit-identical to gemm2_kernel<2, *>, 10-15 % faster
         self._table = None                   # (a hit whose source changed shape gets a NEW pack: the re-pack table still names the old one's storage)
-        self.map[key] = (pw, sig, (tuple(w.shape), None if extra is None else tuple(extra.shape)), (w, extra), refs, self.pass_id, parts)
+        self.map[key] = _Pack(pw, sig, shapes, (w, extra), tuple(weakref.ref(p) for p in params), self.pass_id, parts)
         return pw
 
 
@@ -429,8 +455,9 @@ class HipBackend:
 
 
 _BACKEND = None            # a substitute installed by the tests (tests/emu_backend.py)
-_HIP = {}                  # (device index, precision) -> HipBackend, each with its own packed-weight cache and re-pack table (ADVICE r5:
-                           # models on two GPUs of one process must not share a device table)
+_HIP = {}                  # (device index, precision) -> HipBackend of the eager passes, each with its own packed-weight cache and re-pack
+                           # table (models on two GPUs of one process must not share a device table)
+_REGISTRY = _HIP           # the registry backend() consults: _HIP, or a GraphedTrainStep's own while it warms up and captures (`_registry`)
 _CUR_DEV = None            # device index of the graph being built (None: the current device)
 _CUR_PREC = 3              # the arithmetic of the graph being BUILT (model_forward_train sets it around its Functions' forwards)
 _CUR_SCALE = None          # ... and its loss scale (None: exact arithmetic)
@@ -443,9 +470,20 @@ def backend():
         return _BACKEND
     dev = _CUR_DEV if _CUR_DEV is not None else (torch.cuda.current_device() if torch.cuda.is_available() else -1)
     key = (dev, _CUR_PREC)
-    if key not in _HIP:
-        _HIP[key] = HipBackend(_CUR_PREC)
-    return _HIP[key]
+    if key not in _REGISTRY:
+        _REGISTRY[key] = HipBackend(_CUR_PREC)
+    return _REGISTRY[key]
+
+
+@contextlib.contextmanager
+def _registry(reg):
+    """`with _registry(reg):` -- backend() takes its HipBackends from `reg` (and creates them there) instead of `_HIP`"""
+    global _REGISTRY
+    prev, _REGISTRY = _REGISTRY, reg
+    try:
+        yield
+    finally:
+        _REGISTRY = prev
 
 
 _WEIGHTS_FROZEN = False
@@ -512,15 +550,21 @@ class _Scale:
         ev.record()
         return buf, ev
 
+    @staticmethod
+    def _moved(before):
+        """did the range counters move since `before` (a `_peek()`)?  Waits for the work enqueued so far (one event synchronisation).
+        False when either peek is None."""
+        after = None if before is None else _Scale._peek()
+        if after is None:
+            return False
+        after[1].synchronize()
+        return bool((after[0] != before[0]).any().item())
+
     def overflowed(self) -> bool:
         """did a conversion of this pass (forward activations, scaled gradients) leave the IEEE-half range?  Call after `backward()`;
         waits for the pass (one event synchronisation).  True: the gradients of this step are clamped somewhere -- skip the optimizer
         step (and train on with `train_precision="exact"` if it keeps happening: bf16 planes have the fp32 range)."""
-        if self._before is None:
-            return False
-        after, ev = self._peek()
-        ev.synchronize()
-        return bool((after != self._before[0]).any().item())
+        return self._moved(self._before)
 
     def choose(self, g):
         amax = g.detach().abs().amax().clamp_min(1e-30).float()
@@ -1121,6 +1165,11 @@ class GraphedTrainStep:
     generator -- so the replay runs the same kernels on the same operands: loss and gradients are bit-identical to the eager pass
     (tests/test_round6_gpu.py::test_graphed_training_step).
 
+    The graph owns what its kernels read: the warm passes and the capture take their backends from a registry of this object's own
+    (`_registry`), not from `_HIP`, so the packed weights, the repack table and the array of tiled handles the replays read live exactly
+    as long as the graph.  Eager passes (a ragged last batch), other graphs and other models may run between replays, and nothing they
+    do -- nor `_HIP.clear()` -- frees that state.
+
         step = GraphedTrainStep(lambda a, t, n: diffusion(a, times=t, noise=n), (audio, times, noise), model)
         loss = step(audio, times, noise)          # .grad of every trainable parameter of `model` is now this batch's gradient
         optimizer.step()                          # outside the graph (`zero_grad` between replays is unnecessary and harmless)
@@ -1143,19 +1192,20 @@ class GraphedTrainStep:
         self.inputs = [t.detach().clone() for t in example_inputs]
         assert self.inputs and self.inputs[0].is_cuda, "GraphedTrainStep captures a HIP graph: inputs live on the GPU"
         self.params = [p for _, p in named]
-        self._subs = {"root." + k: p.detach().requires_grad_(True) for k, p in named}      # kept: the packs of the captured kernels hang on them
+        self._subs = {"root." + k: p.detach().requires_grad_(True) for k, p in named}
+        self._backends = {}                               # the HipBackends of the warm passes and the capture: what the replays read
         leaves = list(self._subs.values())
         fn = _LossOf(root, loss_fn)
         run = lambda: torch.func.functional_call(fn, self._subs, tuple(self.inputs))       # noqa: E731
         cur = torch.cuda.current_stream()
         side = torch.cuda.Stream()
         side.wait_stream(cur)
-        with torch.cuda.stream(side):                     # warm passes: packs, tile images, split-K plans, function attributes all exist
+        with _registry(self._backends), torch.cuda.stream(side):   # warm passes: packs, tile images, split-K plans, function attributes all exist
             for _ in range(max(2, warmup)):               # (two at least: the first packs the substitutes' weights, the second builds the
                 torch.autograd.grad(run(), leaves, allow_unused=True)      # one-launch repack table -- a synchronising build, not capturable)
         cur.wait_stream(side)
         self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
+        with _registry(self._backends), torch.cuda.graph(self.graph):
             loss = run()
             grads = torch.autograd.grad(loss, leaves, allow_unused=True)
         self.loss = loss.detach()
@@ -1174,8 +1224,4 @@ class GraphedTrainStep:
         return self.loss
 
     def overflowed(self) -> bool:
-        if self._before is None:
-            return False
-        after, ev = _Scale._peek()
-        ev.synchronize()
-        return bool((after != self._before[0]).any().item())
+        return _Scale._moved(self._before)

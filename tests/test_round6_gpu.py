@@ -363,12 +363,15 @@ def test_mixed_training_unscales_the_gradients_of_cond_and_prompt_and_reports_ov
 
 # ---------------------------------------------------------------------------------------------- the training pass as one HIP graph
 @pytest.mark.parametrize("tprec", ["exact", "mixed"])
-@pytest.mark.parametrize("conditioned", [False, True], ids=["uncond", "cond"])
-def test_graphed_training_step(tprec, conditioned):
+@pytest.mark.parametrize("conditioned, graph_first", [(False, False), (True, False), (False, True), (True, True)],
+                         ids=["uncond", "cond", "uncond-graph_first", "cond-graph_first"])
+def test_graphed_training_step(tprec, conditioned, graph_first):
     """training.GraphedTrainStep: loss + backward of a fixed shape captured once, replayed per batch (NS2:1635 + NS2:1886 off the Python
     launch path).  The replay must be the eager pass bit for bit -- loss and every parameter's .grad -- on the captured batch AND on a new
     batch copied into the static inputs, after an in-place optimizer step in between (the one repack launch inside the graph reads the
-    parameters' own storage), with conditioning dropout drawn inside the graph."""
+    parameters' own storage), with conditioning dropout drawn inside the graph.  graph_first: the graph is built before any eager pass,
+    and every eager backend is dropped and its memory returned (`training._HIP.clear()`, `empty_cache`) before each replay -- the packs
+    and the repack table the replay reads are the graph's own."""
     from naturalspeech2_pytorch_amd import NaturalSpeech2, training
     kw = dict(dim=128, depth=2)
     if conditioned:
@@ -398,11 +401,15 @@ def test_graphed_training_step(tprec, conditioned):
     opt = torch.optim.SGD(m.parameters(), lr=1e-3)
     try:
         b0, b1 = batch(72), batch(74)
-        keep = loss_fn(*b0)                                          # an eager pass whose autograd graph stays referenced (a training loop's
-        keep.backward(retain_graph=True)                             # `loss` variable): its AccumulateGrad nodes live on the default stream
+        if not graph_first:
+            keep = loss_fn(*b0)                                      # an eager pass whose autograd graph stays referenced (a training loop's
+            keep.backward(retain_graph=True)                         # `loss` variable): its AccumulateGrad nodes live on the default stream
         step = training.GraphedTrainStep(loss_fn, b0, m)
         for ins in (b0, b1):
             l_e, g_e = eager(ins)
+            if graph_first:
+                training._HIP.clear()
+                torch.cuda.empty_cache()
             for p in m.parameters():
                 p.grad = None                                        # (eager grads gone: the replay must write its own static ones)
             l_g = step(*ins).detach().clone()
@@ -442,7 +449,7 @@ def test_retile_keeps_the_lean_kernels_images_current_under_the_one_launch_refre
             loss.backward()
             out.append((loss.detach().clone(), m.wavenet.init_conv.weight.grad.clone(), getattr(m.transformer.to_pred, "1").weight.grad.clone()))
             opt.step()
-        tiled = sum(1 for bk in training._HIP.values() for v in bk.packs.map.values() if getattr(v[0], "tiled", False))
+        tiled = sum(1 for bk in training._HIP.values() for v in bk.packs.map.values() if getattr(v.pw, "tiled", False))
         return out, tiled
 
     try:

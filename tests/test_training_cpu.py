@@ -66,29 +66,106 @@ def test_training_functions_match_autograd_composite(emu, cond):
     print("worst parameter gradient:", worst)
 
 
-def test_packed_cache_refreshes_in_place_and_never_serves_a_dead_parameter():
-    """the training packs are keyed by id(parameter): a recycled id must not return another tensor's pack"""
-    from naturalspeech2_pytorch_amd.training import _PackedCache
-    made = []
+def test_packed_cache_refreshes_in_place_and_never_serves_a_dead_parameter(monkeypatch):
+    """the training packs are keyed by id(parameter): a recycled id must not return another tensor's pack.  A moved version refreshes the
+    pack in place (ns2_weight_update: same pack); from the second pass on, one ns2_weights_repack launch refreshes every trainable pack
+    and stamps it fresh for the pass; a miss drops the re-pack table (it names the storage of the packs it was built for)."""
+    import naturalspeech2_pytorch_amd.training as T
+    made, calls = [], []
 
     class FakePW:
         def __init__(self, w, extra1x1=None, precision=3):
             self.handle = len(made)
             made.append(tuple(w.shape))
 
-    import naturalspeech2_pytorch_amd.training as T
-    orig = T.ops.PackedWeight
-    T.ops.PackedWeight = FakePW
+    class FakeLib:
+        def ns2_weight_update(self, h, src, extra, s):
+            calls.append(("update", h))
+            return 0
+
+        def ns2_weights_repack_table_bytes(self, n):
+            return 64 * n
+
+        def ns2_weights_repack_build(self, arr, n, table, nbytes, total, s):
+            calls.append(("build", n))
+            return 0
+
+        def ns2_weights_repack(self, table, n, total, s):
+            calls.append(("repack", n))
+            return 0
+
+    monkeypatch.setattr(T.ops, "PackedWeight", FakePW)
+    monkeypatch.setattr(T._lib, "load", FakeLib)
+    monkeypatch.setattr(T, "_s", lambda: None)
+    c = T._PackedCache()
+    w = torch.nn.Parameter(torch.randn(4, 4))
+    a = c.get(("f", id(w)), (w,), lambda: w)
+    assert c.get(("f", id(w)), (w,), lambda: w) is a and len(made) == 1
+    e = c.map[("f", id(w))]
+    assert e.pw is a and e.refs[0]() is w and e.shapes == ((4, 4), None) and e.parts is None
+    with torch.no_grad():
+        w.mul_(2)                                           # a version bump: the same pack, refreshed in place from the new values
+    assert c.get(("f", id(w)), (w,), lambda: w) is a and len(made) == 1 and calls == [("update", a.handle)]
+    assert c.map[("f", id(w))] is e and e.sig == ((w.data_ptr(), w._version),) and torch.equal(e.src[0], w)
+    w2 = torch.nn.Parameter(torch.randn(4, 4))
+    b = c.get(("f", id(w)), (w2,), lambda: w2)          # same key, another live object: a miss, never `a`
+    assert b is not a and len(made) == 2
+
+    calls.clear()
+    c = T._PackedCache()
+    c.begin_pass()                                          # pass 1 packs
+    v = torch.nn.Parameter(torch.randn(6, 4))
+    pv = c.get(("g", id(v)), (v,), lambda: v, parts=[(0, "n", 0, 0)])
+    c.begin_pass()                                          # pass 2: the table is built, one launch re-packs the entry
+    t = c._table
+    assert calls == [("build", 1), ("repack", 1)] and t.keys == {("g", id(v))} and t.n == 1 and t.nt == 0 and t.tiled is None
+    assert c.map[("g", id(v))].pass_id == 2 and c.get(("g", id(v)), (v,), lambda: v) is pv and len(calls) == 2
+    c.begin_pass()                                          # pass 3: the same table, one launch
+    assert c._table is t and calls[2:] == [("repack", 1)]
+    c.get(("h", id(w)), (w,), lambda: w)                    # a miss (a new weight): the table is dropped
+    assert c._table is None
+
+
+def test_overflowed_is_false_when_a_peek_is_none(monkeypatch):
+    """`_Scale.overflowed` and `GraphedTrainStep.overflowed` compare the range counters with the snapshot taken before the pass; a peek
+    that returns None (no device, no library, a stream under capture) means "no overflow seen", never a TypeError"""
+    class Ev:
+        def synchronize(self):
+            pass
+
+    counters = [torch.zeros(5, dtype=torch.int32)]
+    monkeypatch.setattr(training._Scale, "_peek", staticmethod(lambda: None if counters[0] is None else (counters[0], Ev())))
+    sc = training._Scale()
+    step = object.__new__(training.GraphedTrainStep)
+    step._before = sc._before
+    assert not sc.overflowed() and not step.overflowed()
+    counters[0] = torch.ones(5, dtype=torch.int32)
+    assert sc.overflowed() and step.overflowed()
+    counters[0] = None
+    assert not sc.overflowed() and not step.overflowed()
+    sc._before = step._before = None
+    assert not sc.overflowed() and not step.overflowed()
+
+
+def test_backend_inside_a_private_registry_leaves_hip_alone(emu):
+    """GraphedTrainStep warms up and captures against a registry of its own: backend() there neither reads nor adds to `_HIP`, and a
+    `set_backend` substitute still comes first"""
+    mine = {}
+    with training._registry(mine):
+        assert not isinstance(training.backend(), training.HipBackend) and not mine
+    prev = training.set_backend(None)
+    before = dict(training._HIP)
+    key, eager = (torch.cuda.current_device() if torch.cuda.is_available() else -1, 3), object()
     try:
-        c = _PackedCache()
-        w = torch.nn.Parameter(torch.randn(4, 4))
-        a = c.get(("f", id(w)), (w,), lambda: w)
-        assert c.get(("f", id(w)), (w,), lambda: w) is a and len(made) == 1
-        w2 = torch.nn.Parameter(torch.randn(4, 4))
-        b = c.get(("f", id(w)), (w2,), lambda: w2)          # same key, another live object: a miss, never `a`
-        assert b is not a and len(made) == 2
+        training._HIP[key] = eager                          # what backend() returns outside the registry
+        with training._registry(mine):
+            bk = training.backend()
+            assert isinstance(bk, training.HipBackend) and training.backend() is bk and mine == {key: bk}
+        assert training._HIP == {**before, key: eager} and training.backend() is eager
     finally:
-        T.ops.PackedWeight = orig
+        training._HIP.clear()
+        training._HIP.update(before)
+        training.set_backend(prev)
 
 
 def test_cond_projections_fn_unused_outputs_and_views(emu):
