@@ -6,7 +6,13 @@ One step = Model.forward_with_cond_scale (cond_scale 1 -> one Model.forward, NS2
 replicas each denoising its own 32-utterance shard (weak scaling; no data-path collective inside the loop; the
 path's single RCCL all-gather of the generated latents runs once after the K steps and is inside the timed region).
 
-    python bench.py [--gpus N --steps K --warmup W] [--precision hybrid|mixed|half|exact|fast] [--graph] [--dump-outputs DIR]
+    python bench.py [--gpus N --steps K --warmup W] [--precision hybrid|mixed|half|exact|fast] [--graph] [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline needs: it sets up, runs W untimed and K timed steps, writes `--dump-outputs` and
+prints the line (`roofline` comes from events recorded inside those timed steps, not from a run of its own).  `--full` adds
+everything else below, each part from runs of its own after the timed steps: the other precision modes, the live parity
+checks, the side workloads, the CPU baseline with the reference-vs-HIP comparison at the benched shape, and with N > 1 the
+`collective` block.
 
 `--gpus N` with N > 1 re-executes itself under `python -m torch.distributed.run --nproc-per-node N` (one rank per GPU,
 backend "nccl" = RCCL) unless it already runs under one (RANK / WORLD_SIZE set by the driver's own launcher).
@@ -14,15 +20,15 @@ backend "nccl" = RCCL) unless it already runs under one (RANK / WORLD_SIZE set b
 Default precision is "hybrid", a per-site plan: every contraction is one IEEE-half product plus BOTH first-order
 correction terms evaluated in one block-scaled fp8 MFMA per 32-deep k block ("mixed"), except the
 feed-forward causal conv (43 % of the FLOPs), which runs as the half product alone -- 6e-5-class error against the fp32
-reference (>10x inside the 1e-3 tolerance of BASELINE.json; sweep in tests/test_parity_r2_gpu.py, quoted in `parity`).
-The same JSON line reports, from short extra measurements on the same weights, `mixed_mode` (correction terms
+reference (>10x inside the 1e-3 tolerance of BASELINE.json; sweep in tests/test_parity_r2_gpu.py, quoted in `parity` under --full).
+With --full the same JSON line reports, from short extra measurements on the same weights, `mixed_mode` (correction terms
 everywhere), `half_mode` (the half product alone everywhere: faster, error 8e-4 = a thin margin) and `exact_mode`
 (bf16 x3, 1e-5), and `side` = the other BASELINE configs (RVQ config 4, conditioned config 3, d128 config 2), each with
 its own parity flag and roofline.
 
 Prints ONE JSON line on rank 0.  `roofline` is measured live with HIP events recorded by the executor on the launch stream
 around every launch of the dominant kernel symbol (hybrid: gemm2_kernel<1, EPI_SPLIT, true> = the 12 FF causal convs;
-other modes: gemm2_kernel<*, EPI_SPLIT, *> = the 12 FF causal convs + wavenet init conv + skip GEMM); `cpu_baseline` times the
+other modes: gemm2_kernel<*, EPI_SPLIT, *> = the 12 FF causal convs + wavenet init conv + skip GEMM); `cpu_baseline` (--full) times the
 reference's OWN `Model.forward` (unmodified source from the oracle/_ref archive, CPU SDPA attention, the benched weights) on the host
 cores: two timed forwards of the full batch of 32 after a warm-up, the minimum reported (kind "port" = the oracle restatement, only
 when the archive is absent).  Round 4: the steps read the run's time-conditioning table (built inside the timed region, as
@@ -274,17 +280,20 @@ def main():
                     help="hybrid (default): half product + fp8 correction terms, FF causal conv half only, ~6e-5 from the fp32 "
                          "reference; mixed: correction terms everywhere, ~5e-5; half: one fp16 product, ~8e-4 (thin margin); "
                          "exact: bf16x3 split, 1e-5; fast: bf16, ~1e-2 (outside the tolerance)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the short mixed/half/exact-mode measurements")
-    ap.add_argument("--no-side", action="store_true", help="skip the side workloads (RVQ config 4, conditioned config 3, d128 config 2)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the other precision modes, the live parity checks, the side workloads, the "
+                         "CPU baseline and (N > 1) the collective timing; a plain run does the headline alone")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the short mixed/half/exact-mode measurements")
+    ap.add_argument("--no-side", action="store_true", help="with --full: skip the side workloads (RVQ config 4, conditioned config 3, d128 config 2)")
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--frames", type=int, default=1024)
     ap.add_argument("--dim", type=int, default=512)
     ap.add_argument("--depth", type=int, default=12)
     ap.add_argument("--graph", action="store_true", help="replay the step from a HIP graph (no live per-kernel events)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-time-table", action="store_true",
                     help="recompute the time-conditioning projections inside every step (rounds 1-3) instead of reading the run's table (A/B)")
-    ap.add_argument("--no-parity", action="store_true", help="skip the live parity forward (profile runs: keeps the kernel trace to the timed workload)")
+    ap.add_argument("--no-parity", action="store_true", help="with --full: skip the live parity forwards")
     ap.add_argument("--conditioned", action="store_true",
                     help="BASELINE config 3 instead of the headline: dim_prompt=512, condition_on_prompt, prompt of 103 codec "
                          "frames, frame-aligned cond")
@@ -406,7 +415,7 @@ def main():
         el = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         if world > 1:
             dist.all_reduce(el, op=dist.ReduceOp.MAX)
-            if profile:        # the headline measurement: what the job's one collective costs, apart from the loop (every rank calls it)
+            if profile and args.full:        # what the job's one collective costs, apart from the loop (every rank calls it)
                 COLL.update(D.collective_report(audio, 1e3 * elapsed / steps))
         assert torch.isfinite(audio).all()
         return el.item(), kern_ms.value, kern_n.value
@@ -464,7 +473,7 @@ def main():
         dump_outputs(args.dump_outputs, outputs)
     del outputs
     extra = {}
-    if rank == 0 and world == 1 and not args.graph:
+    if args.full and rank == 0 and world == 1 and not args.graph:
         sd_cpu = {k: v.detach().cpu() for k, v in model.state_dict().items()}
         parity = {"live_rel_err_vs_fp32_oracle": {} if args.no_parity else
                   {args.precision: live_parity(model, sd_cpu, args.precision, args.conditioned)}, "tolerance": 1e-3}
@@ -502,9 +511,9 @@ def main():
     del model
     torch.cuda.empty_cache()
 
-    # ================================================================== side workloads (rank 0, single GPU)
+    # ================================================================== side workloads (--full; rank 0, single GPU)
     side = None
-    if rank == 0 and world == 1 and not args.no_side and not args.conditioned and not args.graph:
+    if args.full and rank == 0 and world == 1 and not args.no_side and not args.conditioned and not args.graph:
         from oracle import ns2_oracle as O
         from oracle import rvq_oracle as R
         side = {}

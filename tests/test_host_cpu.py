@@ -341,6 +341,14 @@ def test_parity_record_is_complete():
     assert m and os.path.join(ROOT, "profiles", m.group(1)) == PR.TRACKED, "bench.py and tests/parity_record.py must name the same file"
 
 
+def test_bench_offers_full():
+    """bench.py --full (off by default) is what adds the runs beyond the headline; the options that trim it still parse"""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0, r.stderr[-2000:]
+    for opt in ("--full", "--no-secondary", "--no-side", "--no-cpu-baseline", "--no-parity", "--dump-outputs"):
+        assert opt in r.stdout, opt
+
+
 def test_bench_dump_outputs_whole_or_the_same_seeded_rows(tmp_path):
     """bench.py --dump-outputs: a set under the budget is written whole; the headline's set (2 x 32 x 1024 x 512 fp32) keeps the same
     seeded rows of every array, identical from call to call, float32, under 64 MB in all"""

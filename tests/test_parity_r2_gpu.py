@@ -751,11 +751,11 @@ def test_naturalspeech2_with_codec_composition():
 
 
 # ------------------------------------------------------------------------------------------ bench.py is driver-runnable
-def _run_bench(extra, env=None):
+def _run_bench(extra, env=None, full=True):
     import subprocess
     import sys
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "2", "--frames", "128",
-           "--dim", "64", "--depth", "1", "--no-secondary", "--no-side", "--no-cpu-baseline"] + extra
+           "--dim", "64", "--depth", "1", "--no-secondary", "--no-side", "--no-cpu-baseline"] + (["--full"] if full else []) + extra
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=dict(os.environ, **(env or {})))
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -769,6 +769,14 @@ def test_bench_line_single_gpu():
     assert line["config"]["precision"] == "hybrid" and line["parity"]["live_rel_err_vs_fp32_oracle"]["hybrid"] < 2.5e-4
     line = _run_bench(["--gpus", "1", "--precision", "mixed"])
     assert line["roofline"]["launches"] == 2 * 3                                                       # + wavenet init conv + skip GEMM
+
+
+def test_plain_bench_line_is_the_headline_alone():
+    """Without --full the line carries the headline and the roofline of its own timed steps, and nothing from other runs."""
+    line = _run_bench(["--gpus", "1"], full=False)
+    assert line["n_gpus"] == 1 and line["value"] > 0 and line["ms_per_step"] > 0 and line["roofline"]["launches"] == 2 * 1
+    assert line["parity"] is None and line["cpu_baseline"] is None and "side" not in line and "gpu_over_cpu" not in line
+    assert not any(k.endswith("_mode") for k in line)
 
 
 def test_bench_self_spawns_ranks_without_a_launcher():

@@ -18,8 +18,8 @@ timeout 200 python tools/trace_blocks.py --prec 2 --which ffin,qkv,ffout 2>&1 | 
 done
 unset NS2_LIB
 for i in 1 2; do
-NS2_LIB=$NEW timeout 300 python bench.py --steps 10 --warmup 3 --no-side --no-secondary --no-cpu-baseline > $OUT/bench_new_$i.json 2> $OUT/bench_new_$i.err
-timeout 300 python bench.py --steps 10 --warmup 3 --no-side --no-secondary --no-cpu-baseline > $OUT/bench_old_$i.json 2> $OUT/bench_old_$i.err
+NS2_LIB=$NEW timeout 300 python bench.py --steps 10 --warmup 3 --no-side --no-secondary --no-cpu-baseline --full > $OUT/bench_new_$i.json 2> $OUT/bench_new_$i.err
+timeout 300 python bench.py --steps 10 --warmup 3 --no-side --no-secondary --no-cpu-baseline --full > $OUT/bench_old_$i.json 2> $OUT/bench_old_$i.err
 done
 python - <<PY
 import json,glob

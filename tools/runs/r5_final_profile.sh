@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/final_r5
 rm -rf $OUT; mkdir -p $OUT
 cd $R
-python bench.py --steps 20 --warmup 3 > $OUT/bench_default.json 2> $OUT/bench_default.err
+python bench.py --steps 20 --warmup 3 --full > $OUT/bench_default.json 2> $OUT/bench_default.err
 cd /tmp && export TMPDIR=/tmp
 prof() { n=$1; shift; rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$n -- "$@" > $OUT/prof_$n.log 2>&1; cp $(ls $OUT/prof_$n/*/*kernel_stats.csv | head -1) $OUT/${n}_kernel_stats.csv; rm -rf $OUT/prof_$n; }
 prof bench_hybrid python $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-secondary --no-side --no-parity
