@@ -516,6 +516,32 @@ typedef struct {
 } ns2_attn_bwd_args;
 int ns2_attention_bwd(const ns2_attn_bwd_args* args, void* stream);
 
+/* ---- training of the conditioning encoders (NS2:228-341, 1073-1115; trained jointly with the denoiser: NS2:1538-1543, 1635) ----
+ * The `_masked` family = ns2_attention_lse / ns2_attention_bwd with the two things Transformer's attention has and Model's has not:
+ *   key_mask  [B, Nk] bytes, 1 = attend (ATT:92-94, 136-138; NULL = none).  Masked keys have P = 0 and dK = dV = 0.  Every utterance must
+ *             keep at least one key (the caller checks: the reference produces NaN there).
+ *   dropout_p in [0, 1) on the softmax output (ATT:100-101, 146): O = sum_k P_k keep_k / (1 - p) v_k, lse unchanged.  keep is a stateless
+ *             function of (seed, call, b, h, q, k) -- csrc/dropout_keep.h, DESIGN.md §9 -- so forward and backward agree without storing
+ *             it.  seed = two 32-bit words in DEVICE memory, read by the kernels (a captured graph sees the words of each replay);
+ *             call = index of the attention inside the pass.  The backward takes the values its forward got.  dropout_p == 0: no
+ *             dropout, the seed is not read (may be NULL) and the kernels without dropout run.
+ * precision 3 only.  With key_mask == NULL and dropout_p == 0 the unmasked kernels run (bit-identical to the plain entry points). */
+int ns2_attention_lse_masked(const uint16_t* q_hi, const uint16_t* q_lo, int ldq, int q_col0, const uint16_t* k_hi, const uint16_t* k_lo,
+                             int ldk, int k_col0, const uint16_t* vt_hi, const uint16_t* vt_lo, int vt_ld, uint16_t* o_hi, uint16_t* o_lo,
+                             int ldo, int B, int H, int Nq, int Nk, float scale, float* lse, int precision, int o_precision,
+                             const uint8_t* key_mask, float dropout_p, const uint32_t* seed, unsigned call, void* stream);
+int ns2_attention_bwd_masked(const ns2_attn_bwd_args* args, const uint8_t* key_mask, float dropout_p, const uint32_t* seed, unsigned call,
+                             void* stream);
+/* debugging / tests: out [B, H, Nq, Nk] bytes, 1 where the kernels above keep P[b, h, q, k] */
+int ns2_dropout_keep_mask(const uint32_t* seed, unsigned call, float dropout_p, int B, int H, int Nq, int Nk, uint8_t* out, void* stream);
+/* SiLU of the encoders' k = 9 convolutions (NS2:247, 306-311) on the fp32 pre-activation x [M, ldx], C columns, and its backward
+ * dx = dy silu'(x).  Leading dimensions multiples of 4, 16-byte aligned pointers. */
+int ns2_silu_fwd(const float* x, int64_t ldx, int64_t M, int C, float* out, int64_t ldo, void* stream);
+int ns2_silu_bwd(const float* dy, int64_t lddy, const float* x, int64_t ldx, int64_t M, int C, float* dx, int64_t lddx, void* stream);
+/* gradient of PhonemeEncoder's token embedding (NS2:281-284): dw [rows, d] = sum of dy [M, lddy] rows per id, negative ids counting as
+ * pad_id (an ordinary row of the table, as upstream); summed in ascending token order: bit-reproducible */
+int ns2_embedding_bwd(const int64_t* ids, int64_t M, int pad_id, const float* dy, int64_t lddy, int rows, int d, float* dw, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -151,6 +151,13 @@ SIGNATURES = {
     "ns2_attention_lse": (I, [P, P, I, I, P, P, I, I, P, P, I, P, P, I, I, I, I, I, F, P, I, I, P]),
     "ns2_attention_delta": (I, [P, L, P, P, I, I, I, I, P, I, P]),
     "ns2_attention_bwd": (I, [POINTER(AttnBwdArgs), P]),
+    # ---- training of the conditioning encoders
+    "ns2_attention_lse_masked": (I, [P, P, I, I, P, P, I, I, P, P, I, P, P, I, I, I, I, I, F, P, I, I, P, F, P, ctypes.c_uint, P]),
+    "ns2_attention_bwd_masked": (I, [POINTER(AttnBwdArgs), P, F, P, ctypes.c_uint, P]),
+    "ns2_dropout_keep_mask": (I, [P, ctypes.c_uint, F, I, I, I, I, P, P]),
+    "ns2_silu_fwd": (I, [P, L, L, I, P, L, P]),
+    "ns2_silu_bwd": (I, [P, L, P, L, L, I, P, L, P]),
+    "ns2_embedding_bwd": (I, [P, L, I, P, L, I, I, P, P]),
 }
 
 NS2_UNAVAILABLE = 1          # include/ns2hip.h: "this fast path does not apply here" (not an error)

@@ -116,7 +116,8 @@ def model_forward_autograd(m, x, times, prompt=None, cond=None, cond_drop_prob=N
 
 
 # ---- the plain Transformer and the two conditioning encoders under autograd (NS2:1073-1115, 228-341): joint training of
-# prompt_enc / phoneme_enc with the denoiser (NS2:1538-1543) needs gradients through them; the HIP forwards are inference-only.
+# prompt_enc / phoneme_enc with the denoiser (NS2:1538-1543) needs gradients through them.  The default (`train_backend="composite"`), the
+# CPU path, and the fall-back of `train_backend="hip"` (training.py: `*_forward_train`) for what `training.encoder_unsupported_reason` names.
 def transformer_forward_autograd(tr, x, mask=None):
     p = tr.dropout if tr.training else 0.
     for norm1, attn, norm2, ff in tr.layers:

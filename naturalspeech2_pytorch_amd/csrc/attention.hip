@@ -18,6 +18,7 @@
 // NSPLIT = 3 evaluates both products as hi*hi + hi*lo + lo*hi (fp32-class accuracy), NSPLIT = 1 hi only.
 #include "ns2_common.h"
 #include "ns2_kernels.h"
+#include "dropout_keep.h"
 
 namespace ns2 {
 
@@ -50,8 +51,11 @@ NS2_DEVINL uint4 mask_chunk(uint4 v, int nvalid) {
 // the loop is VALU-bound (softmax) and lock-stepped by one barrier per tile, so a third wave per SIMD is what overlaps one
 // wave's exp / max / convert work with another's MFMAs.  Four waves (<= 128 VGPRs) spills 60+ registers.
 // WLSE: also write the log-sum-exp the backward kernels recompute P from (training); a separate instantiation, so the inference
-// kernels keep their register allocation (three waves per SIMD is a one-register margin, see above)
-template <int NSPLIT, bool F16, int NW, bool WLSE, int D = 64>
+// kernels keep their register allocation (three waves per SIMD is a one-register margin, see above).
+// DROP (with WLSE only): the attention dropout of the encoders' training pass (ATT:100-101) -- P is multiplied by keep / (1 - p)
+// AFTER the running sum l is taken, so O = sum_k P_k keep_k / (1 - p) v_k and the log-sum-exp is the plain one; keep = dropout_keep.h.
+// Again a separate instantiation: every kernel without it compiles to what it was.
+template <int NSPLIT, bool F16, int NW, bool WLSE, int D = 64, bool DROP = false>
 __global__ __launch_bounds__(64 * NW, ((NSPLIT == 3 && D == 128) ? 1 : (NSPLIT == 3 || D == 128) ? 2 : 3)) void attn_kernel(const AttnArgs a) {
   using G = AtGeom<D>;
   constexpr int DC = D / 16;                         // 16-deep k chunks of the q . k contraction
@@ -152,6 +156,8 @@ __global__ __launch_bounds__(64 * NW, ((NSPLIT == 3 && D == 128) ? 1 : (NSPLIT =
     for (int r = 0; r < 16; ++r) ot[dt][r] = 0.f;
   float m_run = -INFINITY, l_run = 0.f;
   const float sl2 = a.scale * 1.4426950408889634f;
+  uint32_t drop_row = 0u;                              // head key + q * (its multiplier): the part of the counter this lane's query fixes
+  if constexpr (DROP) drop_row = drop_head_key(a.drop_seed[0], a.drop_seed[1], a.drop_call, (uint32_t)(b * a.H + h)) + (uint32_t)qrow * 0x9E3779B1u;
 
   const int ntiles = (a.Nk + 63) / 64;
   Regs rg;
@@ -214,8 +220,13 @@ __global__ __launch_bounds__(64 * NW, ((NSPLIT == 3 && D == 128) ? 1 : (NSPLIT =
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(st[js][r], sl2, -m_new));
-        st[js][r] = p;
         psum += p;
+        if constexpr (DROP) {
+          const uint32_t key = (uint32_t)(key0 + 32 * js + 16 * (r >> 3) + 8 * hi + (r & 7));
+          st[js][r] = drop_mix(drop_row + key * 0x27D4EB2Fu) >= a.drop_thr ? p * a.drop_scale : 0.f;
+        } else {
+          st[js][r] = p;
+        }
       }
     l_run = l_run * alpha + psum;
     if (__any(alpha != 1.0f)) {                           // the running maximum rarely moves after the first tiles
@@ -279,16 +290,16 @@ __global__ __launch_bounds__(64 * NW, ((NSPLIT == 3 && D == 128) ? 1 : (NSPLIT =
   }
 }
 
-template <int NSPLIT, bool F16, int NW, bool WLSE, int D = 64>
+template <int NSPLIT, bool F16, int NW, bool WLSE, int D = 64, bool DROP = false>
 static hipError_t launch_attn_w(const AttnArgs& a, hipStream_t s) {
   const size_t lds = 2 * (NSPLIT == 3 ? 2 : 1) * (AtGeom<D>::KPLANE + AtGeom<D>::VPLANE);
   static DynLdsAttr attr;
   {
-    hipError_t e = attr.ensure(reinterpret_cast<const void*>(&attn_kernel<NSPLIT, F16, NW, WLSE, D>), (int)lds);
+    hipError_t e = attr.ensure(reinterpret_cast<const void*>(&attn_kernel<NSPLIT, F16, NW, WLSE, D, DROP>), (int)lds);
     if (e != hipSuccess) return e;
   }
   dim3 grid(((a.Nq + 32 * NW - 1) / (32 * NW)) * a.H * a.B);
-  hipLaunchKernelGGL((attn_kernel<NSPLIT, F16, NW, WLSE, D>), grid, dim3(64 * NW), lds, s, a);
+  hipLaunchKernelGGL((attn_kernel<NSPLIT, F16, NW, WLSE, D, DROP>), grid, dim3(64 * NW), lds, s, a);
   return hipGetLastError();
 }
 template <int NSPLIT, bool F16>
@@ -297,6 +308,10 @@ static hipError_t launch_attn_t(const AttnArgs& a, hipStream_t s) {
   if (D == 32) return a.lse ? hipErrorInvalidValue : launch_attn_w<NSPLIT, F16, 4, false, 32>(a, s);      // (the backward kernels have a head dim of 64:
   if (D == 128) return a.lse ? hipErrorInvalidValue : launch_attn_w<NSPLIT, F16, 4, false, 128>(a, s);    //  training.unsupported_reason)
   if (D != 64) return hipErrorInvalidValue;
+  if (a.drop_seed) {                                   // attention dropout: the training kernel of precision 3 only
+    if constexpr (NSPLIT == 3) { if (a.lse) return launch_attn_w<NSPLIT, F16, 4, true, 64, true>(a, s); }
+    return hipErrorInvalidValue;
+  }
   if constexpr (NSPLIT == 3) { if (a.lse) return launch_attn_w<NSPLIT, F16, 4, true>(a, s); }   // training runs in precision 3
   else if (a.lse) return hipErrorInvalidValue;
   return launch_attn_w<NSPLIT, F16, 4, false>(a, s);

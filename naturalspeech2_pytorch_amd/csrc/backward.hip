@@ -18,6 +18,7 @@
 #include <cstdlib>
 #include "ns2_common.h"
 #include "ns2_kernels.h"
+#include "dropout_keep.h"
 
 namespace ns2 {
 
@@ -558,6 +559,7 @@ hipError_t launch_attn_delta(const float* dO, long lddo, const bf16_t* o_hi, con
 // block (4 adjacent chunks) over the four 64-B quarters -- both conflict free.  A DMA instruction moves 4 rows (8 full lines).
 __device__ __attribute__((aligned(256))) bf16_t ab2_zero_page[128];
 __device__ float ab2_inf_zero[2] = {INFINITY, 0.f};      // the statistics of a query beyond Nq: lse = +inf (P = 0), delta = 0
+__device__ unsigned char ab2_mask_01[2] = {0, 1};        // MD: the mask byte of a key beyond Nk (0) and of every key when there is no mask (1)
 typedef __attribute__((address_space(3))) void ab2_lds_void_t;
 typedef const __attribute__((address_space(1))) void ab2_gbl_void_t;
 typedef __attribute__((ext_vector_type(4))) short ab2_v4s;
@@ -565,7 +567,12 @@ typedef __attribute__((address_space(3))) ab2_v4s ab2_lds_v4s_t;
 constexpr int AB2_ROW = 256, AB2_MAT = 64 * AB2_ROW, AB2_STAGE = 2 * AB2_MAT;
 NS2_DEVINL int ab2_f(int r) { return ((r & 3) << 2) | ((r >> 2) & 3); }
 
-template <int ROLE>
+// MD = the encoders' training pass (a separate instantiation: the kernels of the denoiser's pass keep their code and registers): a
+// key-padding mask -- masked keys have P = 0: role 0 per walked row (the tile's 64 mask bytes arrive in LDS with the tile), role 1 for
+// the whole own row, which ends with dK = dV = 0 -- and the
+// attention dropout of dropout_keep.h: with keep' = keep / (1 - p),  dP = (dO V^T) keep' ; dS = P (dP - delta) ; dV^T += dO^T (P keep'),
+// delta = rowsum(dO * O) of the post-dropout O as attn_delta_kernel computes it.
+template <int ROLE, bool MD = false>
 __global__ __launch_bounds__(256, 2) void attn_bwd2_kernel(const AttnBwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   float* s_stat = reinterpret_cast<float*>(smem + 2 * AB2_STAGE);       // [stage][lse 64 | delta 64] (role 1)
@@ -604,6 +611,17 @@ __global__ __launch_bounds__(256, 2) void attn_bwd2_kernel(const AttnBwdArgs a) 
     lse_own = a.lse[((long)b * a.H + h) * a.Nq + orow];
     del_own = a.delta[((long)b * a.H + h) * a.Nq + orow];
   }
+  // MD: the part of the dropout counter the own row fixes, and (role 1) whether the own key is padding
+  uint32_t drop_own = 0u;
+  bool own_masked = false;
+  const unsigned char* km = nullptr;
+  if constexpr (MD) {
+    if (a.drop_seed)
+      drop_own = drop_head_key(a.drop_seed[0], a.drop_seed[1], a.drop_call, (uint32_t)(b * a.H + h)) +
+                 (uint32_t)orow * (ROLE == 0 ? 0x9E3779B1u : 0x27D4EB2Fu);
+    km = a.kmask ? a.kmask + (long)b * a.Nk : nullptr;
+    if (ROLE == 1 && km && own_ok) own_masked = km[orow] == 0;
+  }
 
   // walked-side sources (row-major): Y (scores; transposed for acc1), Yg (dP; role 1: transposed for acc2)
   const bf16_t* yb = ROLE == 0 ? a.k_hi : a.q_hi;
@@ -640,6 +658,16 @@ __global__ __launch_bounds__(256, 2) void attn_bwd2_kernel(const AttnBwdArgs a) 
       // The ordering that matters (this wave's vmcnt(0) + the barrier at the top of the next iteration) is explicit below.
       const unsigned dst = (unsigned)(size_t)(sb + (j >> 4) * AB2_MAT + (j & 15) * 1024);
       asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" :: "v"(p), "s"(dst) : "memory", "m0");
+    }
+    if constexpr (ROLE == 0 && MD) {
+      // the key-padding mask of the 64 walked keys travels like role 1's statistics (one byte per lane, a zero-extended word each in LDS):
+      // a plain load inside the loop would make the compiler wait for the whole in-order queue, the prefetched tile included
+      if (wave == 0) {
+        const int key = r0 + lane;
+        const unsigned char* p = key < a.Nk ? (km ? km + key : ab2_mask_01 + 1) : ab2_mask_01;
+        const unsigned dst = (unsigned)(size_t)(s_stat + stage * 128);
+        asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_ubyte %0, off" :: "v"(p), "s"(dst) : "memory", "m0");
+      }
     }
     if constexpr (ROLE == 1) {
       // the 64 queries' lse (wave 0) and delta (wave 1) travel the same way, 4 bytes per lane: an ordinary load here would sit in the
@@ -743,13 +771,31 @@ __global__ __launch_bounds__(256, 2) void attn_bwd2_kernel(const AttnBwdArgs a) 
           ls[0] = l0.x; ls[1] = l0.y; ls[2] = l0.z; ls[3] = l0.w; ls[4] = l1.x; ls[5] = l1.y; ls[6] = l1.z; ls[7] = l1.w;
           dl[0] = d0.x; dl[1] = d0.y; dl[2] = d0.z; dl[3] = d0.w; dl[4] = d1.x; dl[5] = d1.y; dl[6] = d1.z; dl[7] = d1.w;
         }
+        int mk[8] = {1, 1, 1, 1, 1, 1, 1, 1};                                            // MD, role 0: the walked keys' mask words
+        if constexpr (ROLE == 0 && MD) {
+          const int* c_km = reinterpret_cast<const int*>(c_lse) + 32 * js + 16 * g1 + 8 * hi;
+          const int4 m0 = *reinterpret_cast<const int4*>(c_km), m1 = *reinterpret_cast<const int4*>(c_km + 4);
+          mk[0] = m0.x; mk[1] = m0.y; mk[2] = m0.z; mk[3] = m0.w; mk[4] = m1.x; mk[5] = m1.y; mk[6] = m1.z; mk[7] = m1.w;
+        }
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
           const int r = 8 * g1 + e;
           float p = __builtin_amdgcn_exp2f(__builtin_fmaf(stt[r], sl2, -ls[e]));
           if (ROLE == 0 && r0 + 32 * js + 16 * g1 + 8 * hi + e >= Nwalk) p = 0.f;      // keys beyond Nk (role 1: lse = +inf did it)
-          pv[r] = p;
-          dsv[r] = p * (dp[r] - dl[e]);
+          if constexpr (MD) {
+            const int w = r0 + 32 * js + 16 * g1 + 8 * hi + e;                           // the walked row
+            if (ROLE == 0 ? mk[e] == 0 : own_masked) p = 0.f;
+            // (drop_thr = 0 without dropout: every value passes, the factor is 1)
+            const bool keep = drop_mix(drop_own + (uint32_t)w * (ROLE == 0 ? 0x27D4EB2Fu : 0x9E3779B1u)) >= a.drop_thr;
+            // (selects on finished values: dS below keeps the form of the other branch.  dropout_p = 0 never comes here -- the host runs
+            // the kernels without dropout for it)
+            const float dpk = keep ? dp[r] * a.drop_scale : 0.f;
+            pv[r] = keep ? p * a.drop_scale : 0.f;
+            dsv[r] = p * (dpk - dl[e]);
+          } else {
+            pv[r] = p;
+            dsv[r] = p * (dp[r] - dl[e]);
+          }
         }
       }
       // ---- accumulate: acc1 += Y^T dS^T (dQ^T or dK^T), acc2 += Yg^T P^T (dV^T, role 1); the transposed fragments come out of the row-major tiles
@@ -823,15 +869,15 @@ __global__ __launch_bounds__(256, 2) void attn_bwd2_kernel(const AttnBwdArgs a) 
     }
 }
 
-template <int ROLE>
+template <int ROLE, bool MD = false>
 static hipError_t launch_attn_bwd2_role(const AttnBwdArgs& a, hipStream_t s) {
   const size_t lds = 2 * AB2_STAGE + 2 * 128 * sizeof(float);
   static DynLdsAttr attr;
-  hipError_t e = attr.ensure(reinterpret_cast<const void*>(&attn_bwd2_kernel<ROLE>), (int)lds);
+  hipError_t e = attr.ensure(reinterpret_cast<const void*>(&attn_bwd2_kernel<ROLE, MD>), (int)lds);
   if (e != hipSuccess) return e;
   const int nown = ROLE == 0 ? a.Nq : a.Nk;
   dim3 grid(((nown + 127) / 128) * a.H * a.B);
-  hipLaunchKernelGGL((attn_bwd2_kernel<ROLE>), grid, dim3(256), lds, s, a);
+  hipLaunchKernelGGL((attn_bwd2_kernel<ROLE, MD>), grid, dim3(256), lds, s, a);
   return hipGetLastError();
 }
 
@@ -848,9 +894,115 @@ hipError_t launch_attention_bwd(const AttnBwdArgs& a, hipStream_t s) {
   }
   if (want_kv && !a.gp_kv && (!a.dk || !a.dv || ((a.lddk | a.lddv | a.dk_col0 | a.dv_col0) & 3))) return hipErrorInvalidValue;
   if (want_q && !a.gp_q && ((a.lddq & 3) || (a.dq_col0 & 3))) return hipErrorInvalidValue;
+  if (a.kmask || a.drop_seed) {                        // the encoders' pass: mask and / or dropout
+    if (a.drop_seed ? !(a.drop_scale >= 1.f) : (a.drop_thr != 0u || a.drop_scale != 1.f)) return hipErrorInvalidValue;
+    if (want_q) { hipError_t e = launch_attn_bwd2_role<0, true>(a, s); if (e != hipSuccess) return e; }
+    if (want_kv) { hipError_t e = launch_attn_bwd2_role<1, true>(a, s); if (e != hipSuccess) return e; }
+    return hipSuccess;
+  }
   if (want_q) { hipError_t e = launch_attn_bwd2_role<0>(a, s); if (e != hipSuccess) return e; }
   if (want_kv) { hipError_t e = launch_attn_bwd2_role<1>(a, s); if (e != hipSuccess) return e; }
   return hipSuccess;
+}
+
+// ================================================================================================ SiLU of the k = 9 convolutions (NS2:247, 306-311)
+// The inference path runs SiLU in the GEMM epilogue (act = 1) and keeps no pre-activation; training keeps the fp32 pre-activation
+// and uses this pointwise pair: y = x / (1 + exp(-x)) ; dx = dy s (1 + x (1 - s)), s = 1 / (1 + exp(-x)).  A thread owns 4 columns of a row
+// (one float4 each way), one pass.
+template <bool BWD>
+__global__ __launch_bounds__(256) void silu_kernel(const float* x, long ldx, const float* dy, long lddy, long M, int C, float* out, long ldo) {
+  const int chunks = (C + 3) >> 2;
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= M * chunks) return;
+  const long row = idx / chunks;
+  const int c = (int)(idx - row * chunks) * 4;
+  const bool full = c + 3 < C;
+  float xv[4] = {0.f, 0.f, 0.f, 0.f}, gv[4] = {0.f, 0.f, 0.f, 0.f}, o[4];
+  if (full) {
+    const float4 t = *reinterpret_cast<const float4*>(x + row * ldx + c);
+    xv[0] = t.x; xv[1] = t.y; xv[2] = t.z; xv[3] = t.w;
+    if constexpr (BWD) {
+      const float4 g = *reinterpret_cast<const float4*>(dy + row * lddy + c);
+      gv[0] = g.x; gv[1] = g.y; gv[2] = g.z; gv[3] = g.w;
+    }
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (c + e < C) {
+        xv[e] = x[row * ldx + c + e];
+        if constexpr (BWD) gv[e] = dy[row * lddy + c + e];
+      }
+  }
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    if constexpr (BWD) {
+      const float sg = 1.0f / (1.0f + expf(-xv[e]));
+      o[e] = gv[e] * sg * (1.0f + xv[e] * (1.0f - sg));
+    } else {
+      o[e] = siluf(xv[e]);
+    }
+  }
+  if (full) {
+    *reinterpret_cast<float4*>(out + row * ldo + c) = make_float4(o[0], o[1], o[2], o[3]);
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (c + e < C) out[row * ldo + c + e] = o[e];
+  }
+}
+static bool silu_vec_ok(const float* p, long ld) { return (ld & 3) == 0 && (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+hipError_t launch_silu_fwd(const float* x, long ldx, long M, int C, float* out, long ldo, hipStream_t s) {
+  if (M <= 0 || C <= 0 || ldx < C || ldo < C || !silu_vec_ok(x, ldx) || !silu_vec_ok(out, ldo)) return hipErrorInvalidValue;
+  const long n = M * ((C + 3) >> 2);
+  hipLaunchKernelGGL((silu_kernel<false>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, ldx, (const float*)nullptr, 0L, M, C, out, ldo);
+  return hipGetLastError();
+}
+hipError_t launch_silu_bwd(const float* dy, long lddy, const float* x, long ldx, long M, int C, float* dx, long lddx, hipStream_t s) {
+  if (M <= 0 || C <= 0 || ldx < C || lddy < C || lddx < C || !silu_vec_ok(x, ldx) || !silu_vec_ok(dy, lddy) || !silu_vec_ok(dx, lddx))
+    return hipErrorInvalidValue;
+  const long n = M * ((C + 3) >> 2);
+  hipLaunchKernelGGL((silu_kernel<true>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, ldx, dy, lddy, M, C, dx, lddx);
+  return hipGetLastError();
+}
+
+// ================================================================================================ embedding gradient (NS2:281-284)
+// dW[v, c] = sum over the tokens m with ids[m] == v (negative ids count as pad_id) of dy[m, c], in ascending m: a fixed order, so the
+// gradient is bit-reproducible (an atomic scatter is not).  One workgroup per table row and 256 columns; the ids are read wave-uniformly.
+// The table has a few hundred rows at most (phonemes), so every workgroup scanning all M ids costs less than sorting them would.
+__global__ __launch_bounds__(256) void embedding_bwd_kernel(const long long* ids, long M, int pad_id, const float* dy, long lddy, int d, float* dw) {
+  const int v = blockIdx.x;
+  const int c = blockIdx.y * 256 + threadIdx.x;
+  float acc = 0.f;
+  for (long m = 0; m < M; ++m) {
+    long long id = ids[m];
+    if (id < 0) id = pad_id;
+    if (id == v && c < d) acc += dy[m * lddy + c];
+  }
+  if (c < d) dw[(long)v * d + c] = acc;
+}
+hipError_t launch_embedding_bwd(const long long* ids, long M, int pad_id, const float* dy, long lddy, int rows, int d, float* dw, hipStream_t s) {
+  if (M <= 0 || rows <= 0 || d <= 0 || lddy < d || pad_id < 0 || pad_id >= rows) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(embedding_bwd_kernel, dim3((unsigned)rows, (unsigned)((d + 255) / 256)), dim3(256), 0, s, ids, M, pad_id, dy, lddy, d, dw);
+  return hipGetLastError();
+}
+
+// ================================================================================================ the dropout keep mask as bytes (tests, debugging)
+// out[b, h, q, k] = 1 where the training attention kernels keep P[b, h, q, k] (dropout_keep.h), for the seed words in device memory
+__global__ __launch_bounds__(256) void dropout_keep_mask_kernel(const uint32_t* seed, uint32_t call, uint32_t thr, int BH, int Nq, int Nk, unsigned char* out) {
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  const long n = (long)BH * Nq * Nk;
+  if (idx >= n) return;
+  const int k = (int)(idx % Nk);
+  const long t = idx / Nk;
+  const int q = (int)(t % Nq), bh = (int)(t / Nq);
+  out[idx] = drop_value(drop_head_key(seed[0], seed[1], call, (uint32_t)bh), (uint32_t)q, (uint32_t)k) >= thr ? 1 : 0;
+}
+hipError_t launch_dropout_keep_mask(const uint32_t* seed, uint32_t call, float p, int B, int H, int Nq, int Nk, unsigned char* out, hipStream_t s) {
+  if (!seed || !out || B <= 0 || H <= 0 || Nq <= 0 || Nk <= 0 || !(p >= 0.f) || !(p < 1.f)) return hipErrorInvalidValue;
+  const long n = (long)B * H * Nq * Nk;
+  if ((n + 255) / 256 > 0x7fffffffL) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(dropout_keep_mask_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, seed, call, drop_threshold(p), B * H, Nq, Nk, out);
+  return hipGetLastError();
 }
 
 NS2_DEFINE_SATURATION_READER(backward)

@@ -127,6 +127,9 @@ struct AttnArgs {
   const unsigned char* kmask;                            // optional key-padding mask [B, Nk], 1 = attend (ATT:92-94, 136-138)
   float* lse;                                            // optional [B, H, Nq]: log2 of the softmax denominator of the SCALED scores
                                                          // (m + log2 l), what the backward kernels recompute P from; null = not wanted
+  // attention dropout of the training kernel (dropout_keep.h; needs lse and precision 3): drop_seed = two 32-bit words in DEVICE memory
+  // (null = no dropout), drop_thr = round(p 2^32), drop_scale = 1 / (1 - p), drop_call = index of this attention inside the pass
+  const uint32_t* drop_seed = nullptr; uint32_t drop_thr = 0u, drop_call = 0u; float drop_scale = 1.f;
 };                                                       // precision: 3 bf16x3, 1 bf16, 2 and 4: one IEEE-half product
 hipError_t launch_attention(const AttnArgs& a, int precision, hipStream_t s);
 
@@ -314,7 +317,17 @@ struct AttnBwdArgs {
   // dgrad and wgrad GEMMs, nothing else): gp planes [rows, gp_ld] in format gp_fmt (FMT_BF16 hi / lo lines or FMT_H8), dq at columns
   // dq_col0 + 64 h of row b Nq + q, dk / dv at dk_col0 / dv_col0 of row b Nk + k; gp_q / gp_kv say which halves go there
   bf16_t* gp_hi; bf16_t* gp_lo; int gp_ld, gp_fmt, gp_q, gp_kv;
+  // the encoders' training pass: key-padding mask [B, Nk] (1 = attend; null = none) and attention dropout as in AttnArgs (drop_seed null =
+  // none).  Either one selects the MD instantiations of the kernel; without them the kernels of the denoiser's pass run, unchanged.
+  const unsigned char* kmask; const uint32_t* drop_seed; uint32_t drop_thr, drop_call; float drop_scale;
 };
 hipError_t launch_attention_bwd(const AttnBwdArgs& a, hipStream_t s);
+
+// the encoders' training pass (backward.hip): SiLU forward / backward on fp32 rows, the deterministic embedding gradient, and the
+// dropout keep mask of dropout_keep.h as bytes [B, H, Nq, Nk]
+hipError_t launch_silu_fwd(const float* x, long ldx, long M, int C, float* out, long ldo, hipStream_t s);
+hipError_t launch_silu_bwd(const float* dy, long lddy, const float* x, long ldx, long M, int C, float* dx, long lddx, hipStream_t s);
+hipError_t launch_embedding_bwd(const long long* ids, long M, int pad_id, const float* dy, long lddy, int rows, int d, float* dw, hipStream_t s);
+hipError_t launch_dropout_keep_mask(const uint32_t* seed, uint32_t call, float p, int B, int H, int Nq, int Nk, unsigned char* out, hipStream_t s);
 
 }  // namespace ns2

@@ -84,7 +84,8 @@ class NaturalSpeech2(nn.Module):
                  aligner_loss_weight=1., aligner_bin_loss_weight=0.,
                  encoder_precision="exact",            # not in the reference: precision mode of the HIP encoders (and predictor)
                  build_duration_pitch: bool = False,   # not in the reference: build the DurationPitchPredictor (sample(text=...))
-                 build_aligner: bool = False):         # not in the reference: build the Aligner (forward(text=..., mel=..., pitch=...))
+                 build_aligner: bool = False,          # not in the reference: build the Aligner (forward(text=..., mel=..., pitch=...))
+                 encoder_train_backend="composite"):   # not in the reference: "hip" trains phoneme_enc / prompt_enc on the HIP kernels (training.py)
         super().__init__()
         assert _is_denoiser(model), "model must be a Model (this package's, or compat.HipBackedModel over the reference's class)"
         self.conditional = model.condition_on_prompt
@@ -103,8 +104,9 @@ class NaturalSpeech2(nn.Module):
                 audio_to_mel_kwargs.update(sampling_rate=self.target_sample_hz)
             self.audio_to_mel = AudioToMel(n_mels=aligner_dim_in, hop_length=mel_hop_length, **audio_to_mel_kwargs)
             self.calc_pitch_with_pyworld = calc_pitch_with_pyworld
-            self.phoneme_enc = PhonemeEncoder(tokenizer=tokenizer, num_tokens=num_phoneme_tokens, precision=encoder_precision)
-            self.prompt_enc = SpeechPromptEncoder(dim_codebook=dim_codebook, precision=encoder_precision)
+            self.phoneme_enc = PhonemeEncoder(tokenizer=tokenizer, num_tokens=num_phoneme_tokens, precision=encoder_precision,
+                                              train_backend=encoder_train_backend)
+            self.prompt_enc = SpeechPromptEncoder(dim_codebook=dim_codebook, precision=encoder_precision, train_backend=encoder_train_backend)
             self.pitch_emb = nn.Embedding(pitch_emb_dim, pitch_emb_pp_hidden_dim)
             self.aligner_bin_loss_weight = aligner_bin_loss_weight
             if build_duration_pitch:                                                  # NS2:1234

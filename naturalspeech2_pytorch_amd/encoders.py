@@ -3,6 +3,11 @@
 CausalConv1d k=9 + SiLU -> Transformer).  They run once per utterance, not per denoising step; they reuse the hot path's
 kernels: the k=9 convolutions are 9-tap shifted-row GEMMs with the SiLU in the epilogue (csrc/gemm*.hip, pad_left/act).
 Same constructor keywords and state_dict keys as the reference classes; string input (tokenizer / espeak) is out of scope.
+
+Training (the reference trains both jointly with the denoiser, NS2:1538-1543): `train_backend="composite"` (default) runs the PyTorch
+composite of autograd_path.py under autograd; `train_backend="hip"` runs `training.speech_prompt_encoder_forward_train` /
+`training.phoneme_encoder_forward_train` -- forward and backward on the HIP training kernels ("same" and causal k = 9 convolutions with
+their dgrad / wgrad GEMMs, SiLU on the kept pre-activation, deterministic embedding gradient, masked attention with dropout).
 """
 from typing import Tuple
 
@@ -12,7 +17,7 @@ from torch import nn
 from . import ops
 from ._cache import PackedCache
 from .model import _NoParams, _PRECISIONS
-from .transformer import Transformer, needs_autograd
+from .transformer import TRAIN_BACKENDS, Transformer, needs_autograd, use_hip_training
 
 
 class _ConvStack(PackedCache):
@@ -30,8 +35,10 @@ class _ConvStack(PackedCache):
 
 class SpeechPromptEncoder(nn.Module):
     def __init__(self, dim_codebook, dims: Tuple[int, ...] = (256, 2048, 2048, 2048, 2048, 512, 512, 512), *, depth=6, heads=8,
-                 dim_head=64, dropout=0.2, kernel_size=9, padding=4, use_flash_attn=True, precision="exact"):
+                 dim_head=64, dropout=0.2, kernel_size=9, padding=4, use_flash_attn=True, precision="exact", train_backend="composite"):
         super().__init__()
+        assert train_backend in TRAIN_BACKENDS, f"train_backend must be one of {TRAIN_BACKENDS}"
+        self.train_backend = train_backend
         dims = [dim_codebook, *dims]
         self.dim, self.dim_out = dims[0], dims[-1]
         assert precision in _PRECISIONS, f"precision must be one of {sorted(_PRECISIONS)}"
@@ -42,14 +49,17 @@ class SpeechPromptEncoder(nn.Module):
         mods.append(_NoParams())
         self.conv = nn.Sequential(*mods)                      # same indices as the reference Sequential (Rearrange, conv, SiLU, ...)
         self.transformer = Transformer(dim=dims[-1], depth=depth, heads=heads, dim_head=dim_head, dropout=dropout,
-                                       use_flash=use_flash_attn, precision=precision)
+                                       use_flash=use_flash_attn, precision=precision, train_backend=train_backend)
         self._stack = _ConvStack()
 
     def forward(self, x):
-        """Under autograd (the reference trains prompt_enc jointly, NS2:1542-1543) the differentiable composite runs; inference
-        runs in the HIP kernels."""
+        """Under autograd (the reference trains prompt_enc jointly, NS2:1542-1543) the HIP training path (`train_backend="hip"`) or the
+        differentiable composite runs; inference runs in the forward-only HIP kernels."""
         assert x.shape[-1] == self.dim
         if needs_autograd(self, x):
+            if use_hip_training(self, x):
+                from .training import speech_prompt_encoder_forward_train
+                return speech_prompt_encoder_forward_train(self, x)
             from .autograd_path import speech_prompt_encoder_autograd
             return speech_prompt_encoder_autograd(self, x)
         return self._forward_hip(x)
@@ -77,8 +87,10 @@ class SpeechPromptEncoder(nn.Module):
 
 class PhonemeEncoder(nn.Module):
     def __init__(self, *, tokenizer=None, num_tokens=None, dim=512, dim_hidden=512, kernel_size=9, depth=6, dim_head=64, heads=8,
-                 conv_dropout=0.2, attn_dropout=0., use_flash=False, precision="exact"):
+                 conv_dropout=0.2, attn_dropout=0., use_flash=False, precision="exact", train_backend="composite"):
         super().__init__()
+        assert train_backend in TRAIN_BACKENDS, f"train_backend must be one of {TRAIN_BACKENDS}"
+        self.train_backend = train_backend
         if tokenizer is not None and num_tokens is None:
             num_tokens = tokenizer.vocab_size
         assert num_tokens is not None, "token ids are required (the text front-end is out of scope)"
@@ -89,13 +101,16 @@ class PhonemeEncoder(nn.Module):
         self.kernel_size, self.dim_hidden, self.precision, self.conv_dropout = kernel_size, dim_hidden, precision, conv_dropout
         self.conv = nn.Sequential(_NoParams(), nn.Conv1d(dim, dim_hidden, kernel_size), _NoParams(), _NoParams(), _NoParams())
         self.transformer = Transformer(dim=dim_hidden, depth=depth, dim_head=dim_head, heads=heads, dropout=attn_dropout,
-                                       use_flash=use_flash, precision=precision)
+                                       use_flash=use_flash, precision=precision, train_backend=train_backend)
         self._stack = _ConvStack()
 
     def forward(self, x, mask=None):
         if not torch.is_tensor(x):
             raise NotImplementedError("List[str] input needs the tokenizer / espeak front-end (out of scope); pass token ids")
         if needs_autograd(self):
+            if use_hip_training(self, x, mask):
+                from .training import phoneme_encoder_forward_train
+                return phoneme_encoder_forward_train(self, x, mask)
             from .autograd_path import phoneme_encoder_autograd
             return phoneme_encoder_autograd(self, x, mask)
         return self._forward_hip(x, mask)

@@ -25,6 +25,12 @@ time embedding, SiLU, cat, mean-pool, `torch.where` null selects) and `torch.cat
 PerceiverResampler's context (NS2:1060-1061).  Autograd chains them with the Functions above; since round 5 the 32-token resampler
 of the conditioned model (NS2:532-579) runs on the same Functions (`_resampler`), so no contraction of `Model`'s backward is a torch op.
 
+The conditioning encoders (`Transformer`, `PhonemeEncoder`, `SpeechPromptEncoder` with `train_backend="hip"`; NS2:228-341, 1073-1115,
+trained jointly: NS2:1538-1543) run on the same Functions -- `transformer_forward_train`, `phoneme_encoder_forward_train`,
+`speech_prompt_encoder_forward_train` near the end of this file: `AttnFn` / `FeedForwardFn` with a learned-gamma RMSNorm in front,
+key-padding mask and dropout in the attention forward / backward (csrc/dropout_keep.h), `GemmFn(pad_left=)` for the "same" k = 9
+convolutions, `SiluFn`, `EmbeddingFn`; exact arithmetic only.
+
 `Backend` is the seam the CPU tests use: `tests/emu_backend.py` restates every backend call with plain torch ops on CPU, so the
 chain rule, tap flips, shifts and layouts of THIS file are checked against torch autograd without a GPU; the kernels behind
 `HipBackend` are checked one by one and end to end on the MI355X (`tests/test_backward_gpu.py`).
@@ -286,6 +292,48 @@ class HipBackend:
                                          B, H, Nq, Nk, 0.125, lse.data_ptr(), 3, self.prec, _s()), "ns2_attention_lse")
         return o, lse
 
+    def attention_masked(self, q, q_col0, k, k_col0, vt, B, H, Nq, Nk, kmask=None, drop=None):
+        """`attention` with a key-padding mask (uint8 [B, Nk], 1 = attend) and / or dropout on P (`drop` = (p, seed tensor on the device, call
+        index): csrc/dropout_keep.h) -- the attention of the conditioning encoders' training pass"""
+        assert self.prec == 3, "the encoders train in the exact arithmetic"
+        o = ops._out_planes(B * Nq, H * 64, q.device, self.prec)
+        lse = torch.empty(B, H, Nq, dtype=torch.float32, device=q.device)
+        p, seed, call = drop if drop is not None else (0.0, None, 0)
+        check(self.lib.ns2_attention_lse_masked(q.hi, q.lo, q.ld, q_col0, k.hi, k.lo, k.ld, k_col0, vt.ptr(), vt.ptr() + 64, vt.ld, o.hi, o.lo, H * 64,
+                                                B, H, Nq, Nk, 0.125, lse.data_ptr(), 3, self.prec, _p(kmask), p, _p(seed), call, _s()),
+              "ns2_attention_lse_masked")
+        return o, lse
+
+    def dropout_keep_mask(self, seed, call, p, B, H, Nq, Nk):
+        """debugging / tests: the keep mask the training attention kernels apply for these arguments, uint8 [B, H, Nq, Nk]"""
+        out = torch.empty(B, H, Nq, Nk, dtype=torch.uint8, device=seed.device)
+        check(self.lib.ns2_dropout_keep_mask(seed.data_ptr(), call, p, B, H, Nq, Nk, out.data_ptr(), _s()), "ns2_dropout_keep_mask")
+        return out
+
+    def silu_fwd(self, pre, C):
+        """SiLU of the fp32 pre-activation pre [M, >= C] -> fp32 [M, round_up(C, 32)] (columns >= C not written)"""
+        out = torch.empty(pre.shape[0], round_up(C, 32), dtype=torch.float32, device=pre.device)
+        check(self.lib.ns2_silu_fwd(pre.data_ptr(), pre.stride(0), pre.shape[0], C, out.data_ptr(), out.stride(0), _s()), "ns2_silu_fwd")
+        return out
+
+    def silu_bwd(self, dy, pre, C):
+        dx = torch.empty(pre.shape[0], round_up(C, 32), dtype=torch.float32, device=pre.device)
+        check(self.lib.ns2_silu_bwd(dy.data_ptr(), dy.stride(0), pre.data_ptr(), pre.stride(0), pre.shape[0], C, dx.data_ptr(), dx.stride(0), _s()),
+              "ns2_silu_bwd")
+        return dx
+
+    def embedding(self, ids, table, pad_id):
+        return ops.embedding(ids, table, pad_id)
+
+    def embedding_bwd(self, ids, dy, rows, pad_id):
+        """d table [rows, d] from dy [M, >= d] rows, summed per id in ascending token order (bit-reproducible; negative ids = pad_id)"""
+        d = dy.shape[1]
+        ids = ids.reshape(-1).to(torch.int64).contiguous()
+        dw = torch.empty(rows, d, dtype=torch.float32, device=dy.device)
+        check(self.lib.ns2_embedding_bwd(ids.data_ptr(), ids.numel(), pad_id, dy.data_ptr(), dy.stride(0), rows, d, dw.data_ptr(), _s()),
+              "ns2_embedding_bwd")
+        return dw
+
     # ---- rows = batch entries: the conditioning Linears (weight-streaming kernel of the inference path, fp32)
     def skinny(self, x, wt, bias=None):
         """x [R, K] @ wt [K, J] (+ bias) in fp32 (ns2_skinny_linear: deterministic split-K)"""
@@ -431,7 +479,11 @@ class HipBackend:
         """uninitialised operand planes [M, round_up(C, 32)] in the backend's GEMM format (a kernel is about to fill every column)"""
         return ops._out_planes(M, round_up(C, 32), torch.device("cuda", torch.cuda.current_device()), self.prec)
 
-    def attention_bwd(self, q, q_col0, k, k_col0, v, v_col0, do_row, lse, delta, B, H, Nq, Nk, dq=None, dkv=None, planes=None):
+    def attention_bwd_masked(self, *args, kmask=None, drop=None, **kw):
+        """`attention_bwd` of a forward that ran `attention_masked` with the same `kmask` / `drop`"""
+        self.attention_bwd(*args, **kw, _masked=(kmask, drop))
+
+    def attention_bwd(self, q, q_col0, k, k_col0, v, v_col0, do_row, lse, delta, B, H, Nq, Nk, dq=None, dkv=None, planes=None, _masked=None):
         """dq: (fp32 tensor [B*Nq, ld], col0) or None; dkv: (tensor [B*Nk, ld], k col0, v col0) or None;
         planes: (operand planes [B*N, ld], dq col0, dk col0, dv col0) -- self attention: the three gradients leave the kernels as the
         operand of the q | k | v projection's dgrad / wgrad GEMMs instead of fp32 + a conversion pass"""
@@ -451,6 +503,11 @@ class HipBackend:
             assert gp.precision == self.prec
             a.gp_hi, a.gp_lo, a.gp_ld, a.gp_precision, a.gp_q, a.gp_kv = gp.hi, gp.lo, gp.ld, self.prec, 1, 1
         a.B, a.H, a.Nq, a.Nk, a.scale = B, H, Nq, Nk, 0.125
+        if _masked is not None:
+            kmask, drop = _masked
+            p, seed, call = drop if drop is not None else (0.0, None, 0)
+            check(self.lib.ns2_attention_bwd_masked(ctypes.byref(a), _p(kmask), p, _p(seed), call, _s()), "ns2_attention_bwd_masked")
+            return
         check(self.lib.ns2_attention_bwd(ctypes.byref(a), _s()), "ns2_attention_bwd")
 
 
@@ -643,19 +700,24 @@ def _dw(dw, w):
     return dw if w.ndim == 3 else dw[:, :, 0]
 
 
-def _grads(bk, dy, C, xp, K, taps=0, dil=1, seq_len=0, need_row=True, need_w=True, need_b=False):
+def _grads(bk, dy, C, xp, K, taps=0, dil=1, seq_len=0, need_row=True, need_w=True, need_b=False, pad_left=-1):
     """what the backward of y = conv_or_linear(x) (+ b) needs from dy fp32 [M, >= C]: its row planes (the dgrad GEMM's operand), the
     weight gradient dW [C, K, T] against xp = the operand planes the forward GEMM read, the bias gradient.  The weight gradient comes
     from the row planes themselves where the kernel can (ns2_wgrad_rows: LDS transpose reads), else through transposed copies
-    (narrow gradients: the dim = 128 model).  -> (dy_row or None, dW or None, db or None)"""
+    (narrow gradients: the dim = 128 model).  `pad_left` >= 0 and != taps - 1: a NON-causal conv (SpeechPromptEncoder's Conv1d(k = 9, padding = 4),
+    NS2:306-311): tap t read x[n - (pad_left - t) dil], rows shifted in BOTH directions -- the transposed copies take any signed shift
+    (tplanes_kernel zero-fills outside the utterance), the row-plane kernel's tap offsets are the causal ones, so this case always goes
+    through the copies.  -> (dy_row or None, dW or None, db or None)"""
     T = max(taps, 1)
-    if need_w and bk.wgrad_rows_ok(C, T, K, seq_len, dy.shape[0]):
+    causal = pad_left < 0 or pad_left == taps - 1
+    if causal and need_w and bk.wgrad_rows_ok(C, T, K, seq_len, dy.shape[0]):
         row, _, db = bk.grad_prep(dy, C, want_row=True, want_colsum=need_b)
         return row, bk.wgrad_rows(row, xp, C, T, K, dil, seq_len), db
     row, dy_t, db = bk.grad_prep(dy, C, want_row=need_row, want_t=need_w, want_colsum=need_b)
     dw = None
     if need_w:
-        xt = bk.transpose(xp, 0, round_up(K, 32), seq_len if taps else 0, _shifts(taps, dil))
+        shifts = _shifts(taps, dil) if causal else tuple((pad_left - t) * dil for t in range(taps))
+        xt = bk.transpose(xp, 0, round_up(K, 32), seq_len if taps else 0, shifts)
         dw = bk.wgrad(dy_t, xt, C, T, K)
     return row, dw, db
 
@@ -663,17 +725,21 @@ def _grads(bk, dy, C, xp, K, taps=0, dil=1, seq_len=0, need_row=True, need_w=Tru
 # =============================================================================================== Functions
 class GemmFn(torch.autograd.Function):
     """y = conv_or_linear(x) + b (+ resid);  x [M, Cin] fp32, w [Cout, Cin(, k)], causal with dilation `dil` inside utterances of
-    `seq_len` tokens (NS2:583-595)"""
+    `seq_len` tokens (NS2:583-595).  `pad_left` >= 0: a conv with that many zero rows in front instead of the causal k - 1 (nn.Conv1d(k,
+    padding = pad_left), NS2:306-311): its dgrad is the forward kernel on the tap-flipped weight with pad_left' = k - 1 - pad_left"""
 
     @staticmethod
-    def forward(ctx, x, w, b, resid, seq_len, dil):
+    def forward(ctx, x, w, b, resid, seq_len, dil, pad_left=-1):
         bk = ctx.bk = backend()
         ctx.sc = _CUR_SCALE
         taps = _taps(w)
+        if pad_left == taps - 1 or not taps:
+            pad_left = -1
         xp = bk.split(x)
-        y = bk.gemm_f32(_fwd_pack(bk, w), xp, bias=b, resid=resid, taps=taps, dil=dil, seq_len=seq_len if taps else 0)
+        kw = {} if pad_left < 0 else {"pad_left": pad_left}
+        y = bk.gemm_f32(_fwd_pack(bk, w), xp, bias=b, resid=resid, taps=taps, dil=dil, seq_len=seq_len if taps else 0, **kw)
         ctx.save_for_backward(w, b)
-        ctx.xp, ctx.cfg = xp, (taps, dil, seq_len, x.shape[1], resid is not None)
+        ctx.xp, ctx.cfg, ctx.pad_left = xp, (taps, dil, seq_len, x.shape[1], resid is not None), pad_left
         return y[:, :w.shape[0]]
 
     @staticmethod
@@ -685,12 +751,15 @@ class GemmFn(torch.autograd.Function):
         dy = dy if dy.stride(1) == 1 else dy.contiguous()
         # (frozen weights / a gradient wanted for the input only -- guidance: no wgrad GEMM, no transposes, no workspace: ADVICE r4)
         need_w, need_b = ctx.needs_input_grad[1], b is not None and ctx.needs_input_grad[2]
-        dy_row, dw, db = _grads(bk, dy, cout, ctx.xp, cin, taps, dil, seq_len, need_row=ctx.needs_input_grad[0], need_w=need_w, need_b=need_b)
+        pl = ctx.pad_left
+        dy_row, dw, db = _grads(bk, dy, cout, ctx.xp, cin, taps, dil, seq_len, need_row=ctx.needs_input_grad[0], need_w=need_w, need_b=need_b,
+                                pad_left=pl)
         dw = _dw(dw, w) if need_w else None
         dx = None
         if ctx.needs_input_grad[0]:
-            dx = bk.gemm_f32(_bwd_pack(bk, w), dy_row, taps=taps, dil=dil, seq_len=seq_len if taps else 0, pad_left=0 if taps else -1)[:, :cin]
-        return dx, *_un(ctx, dw, db), (dy if has_resid else None), None, None
+            pl_b = (0 if pl < 0 else taps - 1 - pl) if taps else -1
+            dx = bk.gemm_f32(_bwd_pack(bk, w), dy_row, taps=taps, dil=dil, seq_len=seq_len if taps else 0, pad_left=pl_b)[:, :cin]
+        return dx, *_un(ctx, dw, db), (dy if has_resid else None), None, None, None
 
 
 class WavenetBlockFn(torch.autograd.Function):
@@ -741,15 +810,22 @@ class AttnFn(torch.autograd.Function):
     """h + to_out(attention(q, k, v)) with q = to_q(norm(h)), k, v = to_kv(context or norm(h)); norm = RMSNorm with the adaptive
     (gamma, beta) of `film` (Model, NS2:727-746) -- heads of 64, non-causal, no mask (ATT:77-155).  `film = None`: no norm in front
     (the PerceiverResampler's attention, NS2:574: its context = cat(latents, prompt) is formed by the caller, so the part of the
-    context gradient that belongs to the latents reaches them through torch's cat)"""
+    context gradient that belongs to the latents reaches them through torch's cat).
+    The plain `Transformer` of the conditioning encoders (NS2:1073-1115) adds three things, all absent by default (same kernels, same
+    bits as before): `gamma` -- the learned-gamma RMSNorm in front (with `film = None`); `kmask` -- key-padding mask, uint8 [B, Nk],
+    1 = attend (ATT:92-94); `drop` = (p, seed tensor, call index) -- dropout on the softmax output (ATT:100-101; csrc/dropout_keep.h)."""
 
     @staticmethod
-    def forward(ctx, h, film, ctxt, wq, wkv, wout, seq_len, heads, ctx_len):
+    def forward(ctx, h, film, ctxt, wq, wkv, wout, seq_len, heads, ctx_len, gamma=None, kmask=None, drop=None):
         bk = ctx.bk = backend()
         ctx.sc = _CUR_SCALE
         M, d = h.shape
         B, a = M // seq_len, heads * 64
-        xn = bk.rmsnorm(h, seq_len, cond=film) if film is not None else bk.split(h)
+        assert film is None or gamma is None
+        if film is not None:
+            xn = bk.rmsnorm(h, seq_len, cond=film)
+        else:
+            xn = bk.rmsnorm(h, seq_len, gamma=gamma) if gamma is not None else bk.split(h)
         if ctxt is None:                                                    # self attention: one GEMM for q | k | v
             wqkv = bk.pack(("qkv", id(wq), id(wkv)), (wq, wkv), lambda: torch.cat((wq.detach(), wkv.detach()), 0),
                            parts=[(0, "n", 0, 0), (1, "n", a, 0)])
@@ -761,22 +837,31 @@ class AttnFn(torch.autograd.Function):
             kv = bk.gemm_split(_fwd_pack(bk, wkv), cp, attn=True)
             k, v, qc, kc, vc, Nk = kv, kv, 0, 0, a, ctx_len
         vt = bk.transpose(v, vc, a, Nk, per_batch=True)
-        o, lse = bk.attention(q, qc, k, kc, vt, B, heads, seq_len, Nk)
+        if kmask is None and drop is None:
+            o, lse = bk.attention(q, qc, k, kc, vt, B, heads, seq_len, Nk)
+        else:
+            o, lse = bk.attention_masked(q, qc, k, kc, vt, B, heads, seq_len, Nk, kmask=kmask, drop=drop)
         y = bk.gemm_f32(_fwd_pack(bk, wout), o, resid=h)
-        ctx.save_for_backward(h, film, wq, wkv, wout, lse)
-        ctx.pl, ctx.cfg = (xn, q, k, v, o, cp), (seq_len, heads, Nk, qc, kc, vc, ctxt is not None)
+        ctx.save_for_backward(h, film, wq, wkv, wout, lse, gamma)
+        ctx.pl, ctx.cfg, ctx.md = (xn, q, k, v, o, cp), (seq_len, heads, Nk, qc, kc, vc, ctxt is not None), (kmask, drop)
         return y[:, :d]
 
     @staticmethod
     def backward(ctx, dy):
         bk = ctx.bk
-        h, film, wq, wkv, wout, lse = ctx.saved_tensors
+        h, film, wq, wkv, wout, lse, gamma = ctx.saved_tensors
         xn, q, k, v, o, cp = ctx.pl
         seq_len, heads, Nk, qc, kc, vc, cross = ctx.cfg
+        kmask, drop = ctx.md
         M, d = h.shape
         B, a = M // seq_len, heads * 64
         dy = dy if dy.stride(1) == 1 else dy.contiguous()
         ng = ctx.needs_input_grad                                           # (h, film, ctxt, wq, wkv, wout, ...)
+        if kmask is None and drop is None:
+            attention_bwd = bk.attention_bwd
+        else:
+            def attention_bwd(*args, **kw):
+                bk.attention_bwd_masked(*args, kmask=kmask, drop=drop, **kw)
         dy_row, dwout, _ = _grads(bk, dy, d, o, a, need_w=ng[5])
         dwout = dwout[:, :, 0] if ng[5] else None
         do = bk.gemm_f32(_bwd_pack(bk, wout), dy_row)                       # [M, a]
@@ -788,11 +873,11 @@ class AttnFn(torch.autograd.Function):
             if not need_w or bk.wgrad_rows_ok(3 * a, 1, d, 0, M):
                 # dq | dk | dv feed two GEMMs only (the projection's dgrad and wgrad): they leave the attention backward as operand planes
                 g_row = bk.new_planes(M, 3 * a)
-                bk.attention_bwd(q, qc, k, kc, v, vc, do_row, lse, delta, B, heads, seq_len, Nk, planes=(g_row, 0, a, 2 * a))
+                attention_bwd(q, qc, k, kc, v, vc, do_row, lse, delta, B, heads, seq_len, Nk, planes=(g_row, 0, a, 2 * a))
                 dwqkv = bk.wgrad_rows(g_row, xn, 3 * a, 1, d) if need_w else None
             else:
                 dqkv = torch.empty(M, 3 * a, dtype=torch.float32, device=h.device)
-                bk.attention_bwd(q, qc, k, kc, v, vc, do_row, lse, delta, B, heads, seq_len, Nk, dq=(dqkv, 0), dkv=(dqkv, a, 2 * a))
+                attention_bwd(q, qc, k, kc, v, vc, do_row, lse, delta, B, heads, seq_len, Nk, dq=(dqkv, 0), dkv=(dqkv, a, 2 * a))
                 g_row, dwqkv, _ = _grads(bk, dqkv, 3 * a, xn, d, need_w=need_w)
             dwq = dwkv = None
             if need_w:
@@ -804,44 +889,52 @@ class AttnFn(torch.autograd.Function):
         else:
             dq = torch.empty(M, a, dtype=torch.float32, device=h.device)
             dkv = torch.empty(B * Nk, 2 * a, dtype=torch.float32, device=h.device)
-            bk.attention_bwd(q, qc, k, kc, v, vc, do_row, lse, delta, B, heads, seq_len, Nk, dq=(dq, 0), dkv=(dkv, 0, a))
+            attention_bwd(q, qc, k, kc, v, vc, do_row, lse, delta, B, heads, seq_len, Nk, dq=(dq, 0), dkv=(dkv, 0, a))
             q_row, dwq, _ = _grads(bk, dq, a, xn, d, need_w=ng[3])
             dwq = dwq[:, :, 0] if ng[3] else None
             dxn = bk.gemm_f32(_bwd_pack(bk, wq), q_row)
             kv_row, dwkv, _ = _grads(bk, dkv, 2 * a, cp, d, need_row=ng[2], need_w=ng[4])
             dwkv = dwkv[:, :, 0] if ng[4] else None
             dctx = bk.gemm_f32(_bwd_pack(bk, wkv), kv_row)[:, :d] if ng[2] else None
-        if film is None:
-            dh, dfilm = dy[:, :d] + dxn[:, :d], None
-        else:
+        dgamma = None
+        if film is not None:
             dh, dfilm, _ = bk.rmsnorm_bwd(h, dxn, B, seq_len, d, cond=film, dx_add=dy)
-        dfilm, dwq, dwkv, dwout = _un(ctx, dfilm, dwq, dwkv, dwout)
-        return dh, dfilm, dctx, dwq, dwkv, dwout, None, None, None
+        elif gamma is not None:
+            dh, dfilm, dgamma = bk.rmsnorm_bwd(h, dxn, B, seq_len, d, gamma=gamma, dx_add=dy)
+        else:
+            dh, dfilm = dy[:, :d] + dxn[:, :d], None
+        dfilm, dwq, dwkv, dwout, dgamma = _un(ctx, dfilm, dwq, dwkv, dwout, dgamma)
+        return dh, dfilm, dctx, dwq, dwkv, dwout, None, None, None, dgamma, None, None
 
 
 class FeedForwardFn(torch.autograd.Function):
     """h + Linear(CausalConv1d_k3(GEGLU(Linear(norm(h)))))   (NS2:1004-1025 with the adaptive RMSNorm in front, NS2:805-807).
-    `film = None`: no norm; `wc = None`: no conv -- the PerceiverResampler's FeedForward (NS2:564, 575)"""
+    `film = None`: no norm; `wc = None`: no conv -- the PerceiverResampler's FeedForward (NS2:564, 575); `gamma` (with `film = None`): the
+    learned-gamma RMSNorm in front -- the plain Transformer's FeedForward (NS2:1098-1101)"""
 
     @staticmethod
-    def forward(ctx, h, film, w1, b1, wc, bc, w2, b2, seq_len):
+    def forward(ctx, h, film, w1, b1, wc, bc, w2, b2, seq_len, gamma=None):
         bk = ctx.bk = backend()
         ctx.sc = _CUR_SCALE
         M, d = h.shape
         f = w2.shape[1]
-        xn = bk.rmsnorm(h, seq_len, cond=film) if film is not None else bk.split(h)
+        assert film is None or gamma is None
+        if film is not None:
+            xn = bk.rmsnorm(h, seq_len, cond=film)
+        else:
+            xn = bk.rmsnorm(h, seq_len, gamma=gamma) if gamma is not None else bk.split(h)
         pre = bk.gemm_f32(_fwd_pack(bk, w1), xn, bias=b1)                   # [M, 2 f]: x | gate
         hp = bk.geglu_fwd(pre, f)
         cp = bk.gemm_split(_fwd_pack(bk, wc), hp, bias=bc, taps=3, dil=1, seq_len=seq_len) if wc is not None else hp
         y = bk.gemm_f32(_fwd_pack(bk, w2), cp, bias=b2, resid=h)
-        ctx.save_for_backward(h, film, w1, wc, w2, pre)
+        ctx.save_for_backward(h, film, w1, wc, w2, pre, gamma)
         ctx.pl, ctx.cfg = (xn, hp, cp), (seq_len, f)
         return y[:, :d]
 
     @staticmethod
     def backward(ctx, dy):
         bk = ctx.bk
-        h, film, w1, wc, w2, pre = ctx.saved_tensors
+        h, film, w1, wc, w2, pre, gamma = ctx.saved_tensors
         xn, hp, cp = ctx.pl
         seq_len, f = ctx.cfg
         M, d = h.shape
@@ -871,11 +964,14 @@ class FeedForwardFn(torch.autograd.Function):
         p_row, dw1, db1 = _grads(bk, dpre, 2 * f, xn, d, need_w=ng[2], need_b=ng[3])
         dw1 = dw1[:, :, 0] if ng[2] else None
         dxn = bk.gemm_f32(_bwd_pack(bk, w1), p_row)
-        if film is None:
-            dh, dfilm = dy[:, :d] + dxn[:, :d], None
-        else:
+        dgamma = None
+        if film is not None:
             dh, dfilm, _ = bk.rmsnorm_bwd(h, dxn, B, seq_len, d, cond=film, dx_add=dy)
-        return dh, *_un(ctx, dfilm, dw1, db1, dwc, dbc, dw2, db2), None
+        elif gamma is not None:
+            dh, dfilm, dgamma = bk.rmsnorm_bwd(h, dxn, B, seq_len, d, gamma=gamma, dx_add=dy)
+        else:
+            dh, dfilm = dy[:, :d] + dxn[:, :d], None
+        return dh, *_un(ctx, dfilm, dw1, db1, dwc, dbc, dw2, db2), None, *_un(ctx, dgamma)
 
 
 class NormLinearFn(torch.autograd.Function):
@@ -920,6 +1016,39 @@ class RmsNormFn(torch.autograd.Function):
         dy = dy if dy.stride(1) == 1 else dy.contiguous()
         dh, _, dgamma = ctx.bk.rmsnorm_bwd(h, dy, 1, M, d, gamma=gamma)      # one "utterance" of M rows: the norm is per row
         return dh, *_un(ctx, dgamma)
+
+
+class SiluFn(torch.autograd.Function):
+    """SiLU on fp32 rows with the pre-activation kept (the encoders' k = 9 convolutions, NS2:247, 306-311: inference runs it in the GEMM
+    epilogue and keeps nothing)"""
+
+    @staticmethod
+    def forward(ctx, pre):
+        bk = ctx.bk = backend()
+        ctx.save_for_backward(pre)
+        return bk.silu_fwd(pre, pre.shape[1])[:, :pre.shape[1]]
+
+    @staticmethod
+    def backward(ctx, dy):
+        pre, = ctx.saved_tensors
+        dy = dy if dy.stride(1) == 1 else dy.contiguous()
+        return ctx.bk.silu_bwd(dy, pre, pre.shape[1])[:, :pre.shape[1]]
+
+
+class EmbeddingFn(torch.autograd.Function):
+    """token_emb(ids) with negative ids read as `pad_id` (NS2:281-284) -> [M, d]; the table's gradient is summed per id in a fixed order
+    (bit-reproducible, unlike index_add_ on the GPU); the padding row gets its gradient like any other row, as upstream"""
+
+    @staticmethod
+    def forward(ctx, ids, table, pad_id):
+        bk = ctx.bk = backend()
+        ctx.ids, ctx.pad_id, ctx.rows = ids, pad_id, table.shape[0]
+        return bk.embedding(ids, table.detach(), pad_id).reshape(ids.numel(), table.shape[1])
+
+    @staticmethod
+    def backward(ctx, dy):
+        dy = dy if dy.stride(1) == 1 else dy.contiguous()
+        return None, ctx.bk.embedding_bwd(ctx.ids, dy, ctx.rows, ctx.pad_id), None
 
 
 class SkinnyLinearFn(torch.autograd.Function):
@@ -1117,6 +1246,110 @@ def _forward_train(m, x, times, prompt, cond, cond_drop_prob):
     tp = m.transformer.to_pred
     out = NormLinearFn.apply(_c(h), getattr(tp, "0").gamma, getattr(tp, "1").weight, n)
     return out.reshape(b, n, d).to(x.dtype)
+
+
+# =============================================================================================== the conditioning encoders under autograd
+@contextlib.contextmanager
+def _encoder_pass(x):
+    """the encoders train in the exact arithmetic whatever the denoiser next to them uses (the gradient that reaches them has left its
+    scaled domain: `_ScaleOut` on prompt / cond in `_forward_train`)"""
+    global _CUR_PREC, _CUR_SCALE, _CUR_DEV
+    prev = (_CUR_PREC, _CUR_SCALE, _CUR_DEV)
+    _CUR_PREC, _CUR_SCALE, _CUR_DEV = 3, None, (x.device.index if x.is_cuda else None)
+    bk = backend()
+    if hasattr(bk, "packs"):
+        bk.packs.begin_pass()
+    try:
+        yield
+    finally:
+        _CUR_PREC, _CUR_SCALE, _CUR_DEV = prev
+
+
+def _key_mask(mask, b, n):
+    """bool [b, n] (True = attend) -> uint8 for the kernels.  An utterance with no valid key is rejected (the reference's softmax over a
+    fully masked row is NaN); the check reads the mask back, so it is left to the warm passes when a graph is being captured."""
+    if mask is None:
+        return None
+    if mask.dtype != torch.bool or tuple(mask.shape) != (b, n):
+        raise ValueError(f"the key-padding mask must be boolean [b, n] = [{b}, {n}], got {mask.dtype} {tuple(mask.shape)}")
+    capturing = mask.is_cuda and torch.cuda.is_current_stream_capturing()
+    if not capturing and not bool(mask.any(dim=1).all()):
+        raise ValueError("the key-padding mask leaves an utterance without a single valid key")
+    return mask.to(torch.uint8).contiguous()
+
+
+def _transformer_train(tr, h, b, n, mask):
+    d = tr.dim
+    km = _key_mask(mask, b, n)
+    p = float(tr.dropout) if tr.training else 0.
+    seed = None
+    if p > 0:
+        # one seed per pass, the layer index tells the attentions apart.  Drawn ON THE DEVICE by PyTorch's generator (graph-aware: a replay
+        # of a captured pass draws anew) and read there by the kernels.  `tr.dropout_seed` (an int64 tensor of one element) replaces the
+        # draw: reproducing a pass; `tr.last_dropout_seed` is what the last pass used.
+        seed = getattr(tr, "dropout_seed", None)
+        if seed is None:
+            seed = torch.empty(1, dtype=torch.int64, device=h.device).random_()
+        assert seed.dtype == torch.int64 and seed.numel() == 1 and seed.device == h.device
+        tr.last_dropout_seed = seed
+    for li, (norm1, attn, norm2, ff) in enumerate(tr.layers):
+        h = AttnFn.apply(_c(h), None, None, attn.to_q.weight, attn.to_kv.weight, attn.to_out.weight, n, tr.heads, 0, norm1.gamma, km,
+                         (p, seed, li) if p > 0 else None)
+        l1, l2 = getattr(ff, "0"), getattr(ff, "2")
+        h = FeedForwardFn.apply(_c(h), None, l1.weight, l1.bias, None, None, l2.weight, l2.bias, n, norm2.gamma)
+    if hasattr(tr.norm, "gamma"):
+        h = RmsNormFn.apply(_c(h), tr.norm.gamma)
+    return h.reshape(b, n, d)
+
+
+def transformer_forward_train(tr, x, mask=None):
+    """`Transformer.forward` (NS2:1073-1115) as a differentiable graph on the Functions above: per layer RMSNorm(gamma) -> self attention
+    (key-padding mask, dropout on P in training mode) + residual, RMSNorm(gamma) -> Linear -> GEGLU -> Linear + residual; final norm"""
+    b, n, d = x.shape
+    with _encoder_pass(x):
+        return _transformer_train(tr, _c(x.float()).reshape(b * n, d), b, n, mask).to(x.dtype)
+
+
+def speech_prompt_encoder_forward_train(enc, x):
+    """`SpeechPromptEncoder.forward` (NS2:289-341): the "same" k = 9 convolutions as GEMMs with pad_left = padding, SiLU on the kept fp32
+    pre-activation, then the Transformer"""
+    b, n, _ = x.shape
+    with _encoder_pass(x):
+        h = _c(x.float()).reshape(b * n, enc.dim)
+        for m in enc.conv:
+            if isinstance(m, torch.nn.Conv1d):
+                h = SiluFn.apply(_c(GemmFn.apply(_c(h), m.weight, m.bias, None, n, 1, enc.padding)))
+        return _transformer_train(enc.transformer, h, b, n, None).to(x.dtype)
+
+
+def phoneme_encoder_forward_train(enc, ids, mask=None):
+    """`PhonemeEncoder.forward` on token ids (NS2:228-287): embedding (padded ids -> pad_id), CausalConv1d k = 9 + SiLU, conv dropout
+    (F.dropout on the fp32 activations: pointwise plumbing), then the Transformer under the key-padding mask"""
+    b, n = ids.shape
+    with _encoder_pass(ids):
+        h = EmbeddingFn.apply(ids, enc.token_emb.weight, enc.pad_id)
+        conv = enc.conv[1]
+        h = SiluFn.apply(_c(GemmFn.apply(_c(h), conv.weight, conv.bias, None, n, 1)))
+        h = F.dropout(h, enc.conv_dropout, enc.training)
+        return _transformer_train(enc.transformer, h, b, n, mask)
+
+
+def encoder_unsupported_reason(module, mask=None):
+    """None when the `*_forward_train` functions above can run `module` (a `Transformer`, `PhonemeEncoder` or `SpeechPromptEncoder`) with
+    this key mask, else why not -- the counterpart of `unsupported_reason` for `Model`: the caller falls back to the composite"""
+    tr = getattr(module, "transformer", module)
+    if tr.dim_head != 64:
+        return f"dim_head={tr.dim_head} (the HIP attention backward kernels have a head dim of 64)"
+    if tr.dim % 32:
+        return f"dim={tr.dim} is not a multiple of 32"
+    if tr.causal:
+        return "causal=True (the training attention kernels are non-causal)"
+    for name, p in module.named_parameters():
+        if p.dtype != torch.float32:
+            return f"parameter {name} is {p.dtype} (fp32 master weights are required)"
+    if mask is not None and (not torch.is_tensor(mask) or mask.dtype != torch.bool or mask.ndim != 2):
+        return "the key-padding mask is not a boolean [b, n] tensor"
+    return None
 
 
 def available(device):

@@ -2,6 +2,11 @@
 without conv, optional key-padding mask), the block `PhonemeEncoder` / `SpeechPromptEncoder` are built from.  It is not on
 the per-step path; it shares the hot path's HIP kernels and is composed here from the op-level C ABI.
 Same constructor keywords and state_dict keys as the reference class.
+
+Under autograd (`needs_autograd`) the forward-only kernels do not apply.  `train_backend="composite"` (the default) then runs the
+PyTorch composite of autograd_path.py; `train_backend="hip"` runs `training.transformer_forward_train`: forward and backward on
+the HIP training kernels, key-padding mask and attention dropout included, falling back to the composite for
+CPU tensors and for what `training.encoder_unsupported_reason` names.
 """
 import torch
 from torch import nn
@@ -39,10 +44,25 @@ def needs_autograd(module, x=None):
     return False
 
 
+TRAIN_BACKENDS = ("composite", "hip")
+
+
+def use_hip_training(module, x, mask=None):
+    """does a call that needs autograd run the HIP training path of training.py (`train_backend="hip"`, GPU tensors, a module and mask the
+    kernels are written for) -- else the PyTorch composite, exactly as `Model` falls back through `training.unsupported_reason`"""
+    if getattr(module, "train_backend", "composite") != "hip" or not (torch.is_tensor(x) and x.is_cuda):
+        return False
+    from . import training
+    return training.available(x.device) and training.encoder_unsupported_reason(module, mask) is None
+
+
 class Transformer(nn.Module):
     def __init__(self, dim, *, depth, causal=False, dim_head=64, heads=8, use_flash=False, dropout=0., ff_mult=4,
-                 final_norm=False, precision="exact"):
+                 final_norm=False, precision="exact", train_backend="composite"):
         super().__init__()
+        assert train_backend in TRAIN_BACKENDS, f"train_backend must be one of {TRAIN_BACKENDS}"
+        self.train_backend = train_backend
+        self.dropout_seed = None                # train_backend="hip": an int64 tensor [1] replaces the per-pass draw of the attention dropout seed
         assert dim_head in (32, 64, 128), "the HIP attention kernel is built for head dims 32, 64 (the reference default) and 128"
         self.dim, self.depth, self.heads, self.causal, self.dropout, self.dim_head = dim, depth, heads, causal, dropout, dim_head
         assert precision in _PRECISIONS, f"precision must be one of {sorted(_PRECISIONS)}"
@@ -81,11 +101,14 @@ class Transformer(nn.Module):
 
     def forward(self, x, mask=None):
         """x [b, n, dim]; mask: optional bool [b, n] key-padding mask (True = attend).  Under autograd (training: the reference
-        trains its encoders jointly with the denoiser, NS2:1538-1543) the differentiable composite of autograd_path.py runs
-        instead of the forward-only HIP kernels."""
+        trains its encoders jointly with the denoiser, NS2:1538-1543) the forward-only HIP kernels do not apply: the HIP training
+        path runs with `train_backend="hip"`, else the differentiable composite of autograd_path.py."""
         if self.causal:
             raise NotImplementedError("causal=True is not used by any reference caller of Transformer (NS2:252, 315)")
         if self._needs_autograd(x):
+            if use_hip_training(self, x, mask):
+                from .training import transformer_forward_train
+                return transformer_forward_train(self, x, mask)
             from .autograd_path import transformer_forward_autograd
             return transformer_forward_autograd(self, x, mask)
         return self._forward_hip(x, mask)
@@ -95,7 +118,8 @@ class Transformer(nn.Module):
         if self.causal:
             raise NotImplementedError("causal=True is not used by any reference caller of Transformer (NS2:252, 315)")
         if self.training and self.dropout > 0:
-            raise NotImplementedError("attention dropout is a training-time feature; the HIP path is inference-only")
+            raise NotImplementedError("attention dropout is a training-time feature; this forward-only path is for inference "
+                                      "(training runs through forward(): training.transformer_forward_train or the composite)")
         b, n, d = x.shape
         prec = _PRECISIONS[self.precision]
         a = self.heads * self.dim_head
