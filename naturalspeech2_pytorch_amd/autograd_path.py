@@ -1,6 +1,6 @@
 """Differentiable PyTorch composite of `Model.forward`: fp32 torch ops on the module's own parameters.
 
-Since round 4 training has HIP kernels of its own (`training.py`: forward AND backward in libns2hip, `train_backend="hip"`, the
+Since round 4 training has HIP kernels of its own (the `training/` package: forward AND backward in libns2hip, `train_backend="hip"`, the
 default of this package's `Model` on an MI355X; NS2:1635, NS2:1886).  This composite is what is left for the cases those kernels do
 not take -- CPU tensors (the CPU test-suite), `train_backend="composite"`, a model `training.unsupported_reason` rejects (a head
 dimension other than 64 in the backward kernels, non-fp32 parameters) -- and the yardstick bench.py times beside the HIP training
@@ -117,7 +117,7 @@ def model_forward_autograd(m, x, times, prompt=None, cond=None, cond_drop_prob=N
 
 # ---- the plain Transformer and the two conditioning encoders under autograd (NS2:1073-1115, 228-341): joint training of
 # prompt_enc / phoneme_enc with the denoiser (NS2:1538-1543) needs gradients through them.  The default (`train_backend="composite"`), the
-# CPU path, and the fall-back of `train_backend="hip"` (training.py: `*_forward_train`) for what `training.encoder_unsupported_reason` names.
+# CPU path, and the fall-back of `train_backend="hip"` (training/encoder_pass.py: `*_forward_train`) for what `training.encoder_unsupported_reason` names.
 def transformer_forward_autograd(tr, x, mask=None):
     p = tr.dropout if tr.training else 0.
     for norm1, attn, norm2, ff in tr.layers:

@@ -43,11 +43,11 @@ def hip_backed_model_class(reference_model_cls):
             self._hip_init({k: cfg[k] for k in _CFG_KEYS}, precision)
             assert train_backend in ("reference", "hip") and train_precision in ("exact", "mixed")
             self.train_backend = train_backend
-            self.train_precision = train_precision            # arithmetic of train_backend="hip" (training.py)
+            self.train_precision = train_precision            # arithmetic of train_backend="hip" (training/passes.py: TRAIN_PRECISIONS)
 
         def _forward_autograd(self, x, times, prompt=None, prompt_mask=None, cond=None, cond_drop_prob=None):
             """train_backend="reference" (default): the reference's own forward under torch autograd -- the loss is upstream's bit for
-            bit.  "hip": forward AND backward in libns2hip (training.py), through the reference's own parameters; the unmodified
+            bit.  "hip": forward AND backward in libns2hip (training/model_pass.py), through the reference's own parameters; the unmodified
             reference `Trainer` / `NaturalSpeech2.forward` (NS2:1635, 1886) then trains on the HIP kernels."""
             if self.train_backend == "hip" and x.is_cuda and prompt_mask is None:
                 # (a prompt_mask goes to the reference's own forward below, which raises on it: model.py _PROMPT_MASK_MSG)

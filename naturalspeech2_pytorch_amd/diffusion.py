@@ -85,7 +85,7 @@ class NaturalSpeech2(nn.Module):
                  encoder_precision="exact",            # not in the reference: precision mode of the HIP encoders (and predictor)
                  build_duration_pitch: bool = False,   # not in the reference: build the DurationPitchPredictor (sample(text=...))
                  build_aligner: bool = False,          # not in the reference: build the Aligner (forward(text=..., mel=..., pitch=...))
-                 encoder_train_backend="composite"):   # not in the reference: "hip" trains phoneme_enc / prompt_enc on the HIP kernels (training.py)
+                 encoder_train_backend="composite"):   # not in the reference: "hip" trains phoneme_enc / prompt_enc on the HIP kernels (training/encoder_pass.py)
         super().__init__()
         assert _is_denoiser(model), "model must be a Model (this package's, or compat.HipBackedModel over the reference's class)"
         self.conditional = model.condition_on_prompt

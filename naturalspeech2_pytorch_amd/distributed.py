@@ -108,7 +108,7 @@ class GradientAllReducer:
     """Data-parallel training step for `NaturalSpeech2.forward` (NS2:1635, NS2:1886: the reference hands this to
     accelerate / DDP): one process per GPU, replicated weights, each rank's loss on its own shard of the batch, gradients averaged
     with bucketed `all_reduce`s (backend "nccl" == RCCL over xGMI) that start WHILE backward is still running.  The backward
-    arithmetic underneath is the HIP training path (training.py); this is the collective around it, built for the xGMI topology:
+    arithmetic underneath is the HIP training path (the training/ package); this is the collective around it, built for the xGMI topology:
 
       * xGMI is point-to-point (7 links x ~153 GB/s per GPU) and a ring all-reduce is bound per link, so buckets are LARGE
         (default 64 MiB: the 1.04 GB of fp32 gradients of the d512/L12 model = 17 collectives, each long enough to run at link

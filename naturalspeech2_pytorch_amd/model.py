@@ -443,7 +443,7 @@ class HipDenoiserMixin:
         stochastic = self._hip_cfg["condition_on_prompt"] and p not in (0, 0., 1, 1.)
         if needs_grad or stochastic:
             # training (loss.backward(), NS2:1635/1886) and per-utterance stochastic conditioning dropout (a training /
-            # validation feature, NS2:79-85) run the differentiable path: on an MI355X the HIP training kernels (training.py),
+            # validation feature, NS2:79-85) run the differentiable path: on an MI355X the HIP training kernels (training/model_pass.py),
             # on the CPU the PyTorch composite; sampling never gets here
             self._native.autograd_seen = True
             return self._forward_autograd(x, times, prompt=prompt, prompt_mask=prompt_mask, cond=cond, cond_drop_prob=cond_drop_prob)
@@ -653,7 +653,7 @@ class Model(HipDenoiserMixin, nn.Module):
         self.transformer = tr
 
         self.train_backend = "hip"                    # "composite": the PyTorch composite also on the GPU (A/B, tests)
-        self.train_precision = "exact"                # "mixed": half product + fp8 correction terms under a loss scale (training.py `_Scale`)
+        self.train_precision = "exact"                # "mixed": half product + fp8 correction terms under a loss scale (training/passes.py `_Scale`)
         self._hip_init(dict(dim=dim, depth=depth, dim_head=dim_head, heads=heads, ff_mult=ff_mult, wavenet_layers=wavenet_layers,
                             wavenet_stacks=wavenet_stacks, dim_cond_mult=dim_cond_mult, condition_on_prompt=condition_on_prompt,
                             dim_prompt=dim_prompt, num_latents_m=num_latents_m, resampler_depth=resampler_depth), precision)
@@ -665,7 +665,7 @@ class Model(HipDenoiserMixin, nn.Module):
 
     def _forward_autograd(self, x, times, prompt=None, prompt_mask=None, cond=None, cond_drop_prob=None):
         """forward under autograd (loss.backward(), NS2:1635 / 1886).  Parameters on an MI355X: the HIP training path
-        (training.py: forward and backward kernels of libns2hip behind torch.autograd.Functions).  `train_backend = "composite"`
+        (training/model_pass.py: forward and backward kernels of libns2hip behind torch.autograd.Functions).  `train_backend = "composite"`
         (or NS2_TRAIN_BACKEND=composite), and parameters on the CPU (BASELINE config 1 as the reference runs it): the PyTorch
         composite of autograd_path.py."""
         return _train_forward(self, x, times, prompt, cond, cond_drop_prob, prompt_mask=prompt_mask)

@@ -1,0 +1,90 @@
+"""The training step (loss + backward) of a fixed shape as one HIP graph"""
+import torch
+
+from .passes import _registry, _Scale
+
+
+class _LossOf(torch.nn.Module):
+    """`loss_fn` as the forward of a module that owns `root`: lets torch.func.functional_call run it on substitute parameters"""
+
+    def __init__(self, root, loss_fn):
+        super().__init__()
+        self.root, self.loss_fn = root, loss_fn
+
+    def forward(self, *inputs):
+        return self.loss_fn(*inputs)
+
+
+class GraphedTrainStep:
+    """`loss = loss_fn(*inputs); loss.backward()` of a FIXED shape captured once in a HIP graph and replayed per step.
+
+    Why: a d512 / L12 training pass enqueues ~2 000 launches from Python (the autograd Functions of functions.py are coarse, but each is a
+    dozen library calls); on a host whose cores are shared the enqueue, not the GPU, set the step time (98 ms vs 151 ms for the same
+    kernels, profiles/README.md), and at BASELINE config 1's size (d128 / L6, 4 x 1024) the GPU waits for Python: 20 ms eager, 12 ms
+    replayed.  Everything this package launches is capture-safe after a warm pass -- the weight packs are refreshed by ONE
+    `ns2_weights_repack` launch that reads the parameters' own storage (`_PackedCache._repack_all`), the loss scale of the mixed
+    arithmetic is chosen on the device (`_Scale.choose`), buffers come from PyTorch's allocator (its graph-private pool during
+    capture), random draws (conditioning dropout, times / noise when `loss_fn` draws them) go through PyTorch's graph-aware
+    generator -- so the replay runs the same kernels on the same operands: loss and gradients are bit-identical to the eager pass
+    (tests/test_round6_gpu.py::test_graphed_training_step).
+
+    The graph owns what its kernels read: the warm passes and the capture take their backends from a registry of this object's own
+    (`_registry`), not from `_HIP`, so the packed weights, the repack table and the array of tiled handles the replays read live exactly
+    as long as the graph.  Eager passes (a ragged last batch), other graphs and other models may run between replays, and nothing they
+    do -- nor `_HIP.clear()` -- frees that state.
+
+        step = GraphedTrainStep(lambda a, t, n: diffusion(a, times=t, noise=n), (audio, times, noise), model)
+        loss = step(audio, times, noise)          # .grad of every trainable parameter of `model` is now this batch's gradient
+        optimizer.step()                          # outside the graph (`zero_grad` between replays is unnecessary and harmless)
+
+    `module`: the nn.Module (or a list of them) whose trainable parameters `loss_fn` reaches.  During the warm passes and the capture
+    the module runs on SUBSTITUTE leaves over the same storage (torch.func.functional_call): a parameter's own AccumulateGrad node lives
+    on the stream it was created on -- the default stream whenever an eager pass's `loss` is still referenced -- and the autograd engine
+    would tie that stream into the capture (observed: a crash inside hipStreamEndCapture; tools/exp_graph_crash.py).  The gradients
+    come back from torch.autograd.grad as the graph's own tensors and are attached as `.grad` after every replay.
+
+    The parameters must be updated IN PLACE (every torch optimizer does); re-create the object after changing shapes, freezing /
+    unfreezing parameters or loading a state dict into NEW storage.  `overflowed()` is `_Scale.overflowed` for the replayed pass.
+    Tensor hooks on the parameters do not run during a replay (`distributed.GradientAllReducer` overlaps its all-reduces with an EAGER
+    backward through such hooks): a data-parallel loop on the graph all-reduces `step.grads` after the call instead."""
+
+    def __init__(self, loss_fn, example_inputs, module, warmup=2):
+        root = module if isinstance(module, torch.nn.Module) else torch.nn.ModuleList(list(module))
+        named = [(k, p) for k, p in root.named_parameters() if p.requires_grad]
+        assert named, "GraphedTrainStep: no trainable parameter"
+        self.inputs = [t.detach().clone() for t in example_inputs]
+        assert self.inputs and self.inputs[0].is_cuda, "GraphedTrainStep captures a HIP graph: inputs live on the GPU"
+        self.params = [p for _, p in named]
+        self._subs = {"root." + k: p.detach().requires_grad_(True) for k, p in named}
+        self._backends = {}                               # the HipBackends of the warm passes and the capture: what the replays read
+        leaves = list(self._subs.values())
+        fn = _LossOf(root, loss_fn)
+        run = lambda: torch.func.functional_call(fn, self._subs, tuple(self.inputs))       # noqa: E731
+        cur = torch.cuda.current_stream()
+        side = torch.cuda.Stream()
+        side.wait_stream(cur)
+        with _registry(self._backends), torch.cuda.stream(side):   # warm passes: packs, tile images, split-K plans, function attributes all exist
+            for _ in range(max(2, warmup)):               # (two at least: the first packs the substitutes' weights, the second builds the
+                torch.autograd.grad(run(), leaves, allow_unused=True)      # one-launch repack table -- a synchronising build, not capturable)
+        cur.wait_stream(side)
+        self.graph = torch.cuda.CUDAGraph()
+        with _registry(self._backends), torch.cuda.graph(self.graph):
+            loss = run()
+            grads = torch.autograd.grad(loss, leaves, allow_unused=True)
+        self.loss = loss.detach()
+        self.grads = list(grads)                          # the graph's own tensors: every replay writes them, __call__ attaches them as .grad
+        self._before = None
+
+    def __call__(self, *inputs):
+        assert len(inputs) == len(self.inputs)
+        for s, t in zip(self.inputs, inputs):
+            if t is not s:
+                s.copy_(t)
+        self._before = _Scale._peek()
+        self.graph.replay()
+        for p, g in zip(self.params, self.grads):         # (whatever a zero_grad(set_to_none=True) or an eager pass in between left there)
+            p.grad = g
+        return self.loss
+
+    def overflowed(self) -> bool:
+        return _Scale._moved(self._before)

@@ -1,0 +1,147 @@
+"""`Model.forward` under autograd: the denoiser's training pass on the Functions of functions.py"""
+import math
+
+import torch
+import torch.nn.functional as F
+
+from .functions import AttnFn, CondProjectionsFn, FeedForwardFn, GemmFn, NormLinearFn, RmsNormFn, WavenetBlockFn, _c, _lin
+from .passes import TRAIN_PRECISIONS, _enter, _ScaleIn, training_pass
+
+
+def _resampler(pr, prompt, heads):
+    """PerceiverResampler (NS2:532-579) on the Functions of functions.py: per layer latents += Attention(latents, context = cat(latents,
+    proj(prompt))) and latents += FeedForward(latents) (no norms in front, no conv), then RMSNorm * gamma.  Round 4 ran this part of
+    the conditioned model's graph as the PyTorch composite (0.2 % of the FLOPs, but the one piece of `Model`'s backward on torch ops)."""
+    b, n_p, _ = prompt.shape
+    pc = getattr(pr, "proj_context", None)
+    px = _c(prompt).reshape(b * n_p, -1)
+    if isinstance(pc, torch.nn.Linear):                                      # dim_prompt != dim (NS2:548)
+        px = GemmFn.apply(px, pc.weight, pc.bias, None, 0, 1)
+    Lm, d = pr.latents.shape
+    px = px.reshape(b, n_p, d)
+    lat = _enter(pr.latents)[None].expand(b, -1, -1).reshape(b * Lm, d)      # (a copy: its gradient sums over the batch into pr.latents)
+    for attn, ff in pr.layers:
+        context = torch.cat((lat.reshape(b, Lm, d), px), dim=1).reshape(b * (Lm + n_p), d)     # cross_attn_include_queries, NS2:1060-1061
+        lat = AttnFn.apply(_c(lat), None, context, attn.to_q.weight, attn.to_kv.weight, attn.to_out.weight, Lm, heads, Lm + n_p)
+        l1, l2 = getattr(ff, "0"), getattr(ff, "2")
+        lat = FeedForwardFn.apply(_c(lat), None, l1.weight, l1.bias, None, None, l2.weight, l2.bias, Lm)
+    return RmsNormFn.apply(_c(lat), pr.norm.gamma).reshape(b, Lm, d)
+
+
+def model_forward_train(m, x, times, prompt=None, cond=None, cond_drop_prob=None):
+    """`Model.forward` (NS2:929-1000) as a differentiable graph whose token-sized arithmetic is HIP (package docstring).
+    `m` owns the reference's parameters (this package's `Model` or `compat.HipBackedModel`).  `m.train_precision`: "exact"
+    (default: bf16 x3) or "mixed" (IEEE-half product + fp8 correction terms on FMT_H8 operands under a loss scale, `passes._Scale`)."""
+    tp = getattr(m, "train_precision", "exact")
+    assert tp in TRAIN_PRECISIONS, f"train_precision must be one of {sorted(TRAIN_PRECISIONS)}"
+    with training_pass(TRAIN_PRECISIONS[tp], x) as p:
+        out = _forward_train(m, x, times, prompt, cond, cond_drop_prob)
+        if p.scale is not None:
+            m._last_loss_scale = p.scale             # (inspection / tests: the scale the last backward chose)
+            out = _ScaleIn.apply(out, p.scale)
+        return out
+
+
+def _forward_train(m, x, times, prompt, cond, cond_drop_prob):
+    b, n, d = x.shape
+    M = b * n
+    p = m.cond_drop_prob if cond_drop_prob is None else cond_drop_prob
+    heads = m._hip_cfg["heads"]
+    # ---- rows = batch entries: time embedding and every conditioning projection (PyTorch ops, see the package docstring)
+    w = getattr(m.to_time_cond, "0").weights
+    tt = times.float()[:, None]
+    fr = tt * w[None] * 2 * math.pi
+    t = F.silu(_lin(getattr(m.to_time_cond, "1"), torch.cat((tt, fr.sin(), fr.cos()), dim=-1)))
+    c = None
+    h = _enter(x.float().reshape(M, d))              # (mixed arithmetic: the token-sized gradients below here are loss-scaled)
+    if m.condition_on_prompt:
+        assert prompt is not None and cond is not None
+
+        def mask():
+            if p == 1:
+                return torch.ones(b, dtype=torch.bool, device=x.device)
+            if p == 0:
+                return torch.zeros(b, dtype=torch.bool, device=x.device)
+            return torch.rand(b, device=x.device) < p
+
+        dm = mask()
+        pc = F.silu(_lin(getattr(m.to_prompt_cond, "1"), prompt.float().mean(dim=1)))
+        pc = torch.where(dm[:, None], m.null_prompt_cond, pc)
+        t = torch.cat((t, pc), dim=-1)
+        # (`prompt` and `cond` come from trainable modules upstream -- the prompt / phoneme encoders, NS2:1635 -- so their gradients
+        # leave the scaled domain like x's: ADVICE r5)
+        c = torch.where(dm[:, None, None], _enter(m.null_prompt_tokens), _resampler(m.perceiver_resampler, _enter(prompt.float()), heads))   # [b, Lm, d]
+        # cond_to_model_dim: 1x1 conv over channel-first cond (NS2:978) = a Linear over the frames
+        n_c = cond.shape[-1]
+        cm = GemmFn.apply(_enter(_c(cond.float().transpose(1, 2)).reshape(b * n_c, -1)), m.cond_to_model_dim.weight, m.cond_to_model_dim.bias, None,
+                          n_c, 1)
+        cm = cm.reshape(b, n_c, d)
+        cm = torch.where(mask()[:, None, None], _enter(m.null_cond).t()[None], cm)
+        if n_c > n:
+            cm = cm[:, :n]
+        elif n_c < n:
+            cm = F.pad(cm, (0, 0, 0, n - n_c))
+        h = h + _c(cm).reshape(M, d)
+        c2 = _c(c.float()).reshape(b * c.shape[1], d)
+    t = _c(t)
+    # every conditioning projection of the pass at once (CondProjectionsFn), in the order the graph below consumes them
+    lins = [blk.to_time_cond for st in m.wavenet.stacks for blk in st.blocks]
+    for layer in m.transformer.layers:
+        lins += [getattr(layer, str(i)).to_gamma_beta for i in ((0, 2, 4) if m.condition_on_prompt else (0, 4))]
+    if all(l.bias is not None for l in lins):
+        films = dict(zip(map(id, lins), CondProjectionsFn.apply(t, *[q for l in lins for q in (l.weight, l.bias)])))
+    else:                                                                    # (the reference's Linears all carry a bias)
+        films = {}
+
+    def film_of(lin):
+        f = films.get(id(lin))
+        return f if f is not None else _lin(lin, t)
+
+    wn = m.wavenet
+    h0 = GemmFn.apply(h, wn.init_conv.weight, wn.init_conv.bias, None, n, 1)
+    cols = [h0] * m._hip_cfg["wavenet_layers"]
+    skip = None
+    for st in wn.stacks:
+        nxt = []
+        for i, blk in enumerate(st.blocks):
+            z = WavenetBlockFn.apply(_c(cols[i]), film_of(blk.to_time_cond), blk.conv.weight, blk.conv.bias, blk.res_conv.weight,
+                                     blk.res_conv.bias, n, 2 ** i)
+            nxt.append(z)
+            if blk.skip_conv is not None:                                    # sum of the skip convs (NS2:685-686, 725) as a chain of residuals
+                skip = GemmFn.apply(_c(z), blk.skip_conv.weight, blk.skip_conv.bias, skip if skip is None else _c(skip), n, 1)
+        cols = nxt
+    h = GemmFn.apply(_c(skip), wn.final_conv.weight, wn.final_conv.bias, None, n, 1)
+    for layer in m.transformer.layers:
+        a1 = getattr(layer, "1")
+        h = AttnFn.apply(_c(h), film_of(getattr(layer, "0").to_gamma_beta), None, a1.to_q.weight, a1.to_kv.weight, a1.to_out.weight, n, heads, 0)
+        if m.condition_on_prompt:
+            a3 = getattr(layer, "3")
+            h = AttnFn.apply(_c(h), film_of(getattr(layer, "2").to_gamma_beta), c2, a3.to_q.weight, a3.to_kv.weight, a3.to_out.weight, n,
+                             heads, c.shape[1])
+        ff = getattr(layer, "5")
+        l1, cv, l2 = getattr(ff, "0"), getattr(getattr(ff, "2"), "1"), getattr(ff, "3")
+        h = FeedForwardFn.apply(_c(h), film_of(getattr(layer, "4").to_gamma_beta), l1.weight, l1.bias, cv.weight, cv.bias, l2.weight, l2.bias, n)
+    tp = m.transformer.to_pred
+    out = NormLinearFn.apply(_c(h), getattr(tp, "0").gamma, getattr(tp, "1").weight, n)
+    return out.reshape(b, n, d).to(x.dtype)
+
+
+def available(device):
+    """the HIP training path needs the library and parameters on an MI355X"""
+    return device.type == "cuda" and torch.cuda.is_available()
+
+
+def unsupported_reason(m):
+    """None when `model_forward_train` can run `m`, else why not.  The Functions are written for what the inference executor
+    accepts (ns2_model_create): heads of 64 (q / k / v column offsets, the attention kernels' head dim, scale 1/8), dim a multiple
+    of 32 (whole 32-column lines per operand row), fp32 parameters (the packs and the returned gradients are fp32).  Anything else
+    must not reach the kernels (a `dim_head=32` model would read past its packed qkv planes)."""
+    cfg = m._hip_cfg
+    if cfg["dim_head"] != 64:
+        return f"dim_head={cfg['dim_head']} (the HIP attention kernels have a head dim of 64)"
+    if cfg["dim"] % 32:
+        return f"dim={cfg['dim']} is not a multiple of 32"
+    for name, p in m.named_parameters():
+        if p.dtype != torch.float32:
+            return f"parameter {name} is {p.dtype} (fp32 master weights are required)"
+    return None

@@ -48,7 +48,7 @@ TRAIN_BACKENDS = ("composite", "hip")
 
 
 def use_hip_training(module, x, mask=None):
-    """does a call that needs autograd run the HIP training path of training.py (`train_backend="hip"`, GPU tensors, a module and mask the
+    """does a call that needs autograd run the HIP training path of training/encoder_pass.py (`train_backend="hip"`, GPU tensors, a module and mask the
     kernels are written for) -- else the PyTorch composite, exactly as `Model` falls back through `training.unsupported_reason`"""
     if getattr(module, "train_backend", "composite") != "hip" or not (torch.is_tensor(x) and x.is_cuda):
         return False

@@ -1,6 +1,6 @@
 """TEST INFRASTRUCTURE: a plain-torch (CPU) restatement of every `training.HipBackend` call, with the SAME layout contracts
 (padded leading dimensions, transposed planes stacked per tap, shifts inside utterances, fixed column offsets), so that the host
-logic of `naturalspeech2_pytorch_amd/training.py` -- chain rule, tap flips, shift signs, which tensor is saved for what -- is
+logic of `naturalspeech2_pytorch_amd/training/` (functions.py, model_pass.py, encoder_pass.py) -- chain rule, tap flips, shift signs, which tensor is saved for what -- is
 checked against torch autograd without a GPU (tests/test_training_cpu.py).  Never imported by the product.
 
 Semantics restated from the kernels' contracts:
@@ -285,7 +285,7 @@ def mixed_mm(a, w_t):
 
 class MixedEmuBackend(EmuBackend):
     """EmuBackend whose contractions (forward, dgrad, wgrad) round their operands like FMT_H8 lines: values beyond the IEEE-half range
-    are clamped and tiny ones lose their bits -- what the loss scale of training._Scale is for (tests/test_training_cpu.py)"""
+    are clamped and tiny ones lose their bits -- what the loss scale of training.passes._Scale is for (tests/test_training_cpu.py)"""
     name = "emu-mixed"
 
     def _mm(self, a, w_t):

@@ -19,6 +19,7 @@ if not torch.cuda.is_available():
     pytest.skip("needs an MI355X", allow_module_level=True)
 
 from naturalspeech2_pytorch_amd import Model, NaturalSpeech2, ops, training  # noqa: E402
+from naturalspeech2_pytorch_amd.training import functions  # noqa: E402
 from naturalspeech2_pytorch_amd.compat import hip_backed_model_class  # noqa: E402
 from naturalspeech2_pytorch_amd.autograd_path import model_forward_autograd  # noqa: E402
 from oracle.ref_stub import load_reference, reference_available  # noqa: E402
@@ -131,7 +132,7 @@ def test_dgrad_is_the_forward_kernel_on_the_flipped_weight(cout, cin, taps, dil,
         y = x @ w.t()
     (y * dy).sum().backward()
     wp = _W(w)
-    pw = training._bwd_pack(HB, wp.t)
+    pw = functions._bwd_pack(HB, wp.t)
     dyp = HB.split(dy.to(DEV))
     dx = HB.gemm_f32(pw, dyp, taps=taps, dil=dil, seq_len=seq if taps else 0, pad_left=0 if taps else -1)[:, :cin].cpu()
     assert rel(dx, x.grad) < 2e-5

@@ -1,7 +1,7 @@
 """Round-5 GPU tests.
 
   * every gradient of the CONDITIONED model at the headline architecture (d512 / L12, 2 x 512 frames) against the
-    reference's own autograd -- with the PerceiverResampler's backward now on the HIP Functions (training._resampler).
+    reference's own autograd -- with the PerceiverResampler's backward now on the HIP Functions (training.model_pass._resampler).
   * a frozen model with only x.requires_grad runs no weight-gradient GEMM and still returns the reference's dL/dx.
   (The helper loop of the tap-shared conv for half-empty column tiles -- gemm2.hip `helper` -- is covered by the shapes of
   tests/test_kernels_gpu.py::test_causal_conv whose last column tile has at most 128 valid columns: Cout = 300, 100, 341.)
@@ -334,7 +334,7 @@ def test_packs_follow_freezing_and_unfreezing():
 @pytest.mark.parametrize("fused", [True, False])
 def test_fused_optimizer_steps_reach_the_packed_weights(fused):
     """torch.optim.Adam(fused=True) updates parameters in place WITHOUT moving their version counters; the packed GEMM weights of the
-    HIP training path must follow anyway (training._PackedCache: refreshed at the first use of every pass).  The same seven steps on the
+    HIP training path must follow anyway (training.packs._PackedCache: refreshed at the first use of every pass).  The same seven steps on the
     PyTorch composite are the witness: same losses step by step (the first step's losses are equal to 1e-6; Adam's sign-like first
     updates then amplify the 1e-5 gradient differences somewhat)."""
     from naturalspeech2_pytorch_amd import NaturalSpeech2

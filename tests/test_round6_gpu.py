@@ -322,7 +322,7 @@ def test_config2_d128_at_its_stated_size_32x1024():
 
 # ---------------------------------------------------------------------------------------------- mixed training, external conditioning inputs
 def test_mixed_training_unscales_the_gradients_of_cond_and_prompt_and_reports_overflow():
-    """train_precision="mixed" runs its backward on loss-scaled gradients (training._Scale).  `prompt` and `cond` come from trainable
+    """train_precision="mixed" runs its backward on loss-scaled gradients (training.passes._Scale).  `prompt` and `cond` come from trainable
     modules upstream (SpeechPromptEncoder, the phoneme / pitch encoders: NS2:1635), so their gradients must leave the scaled domain
     like x's -- round 5 returned them 2^27 times too large.  Conditioned d128 / L2 on the MI355X: every gradient incl. d/dprompt and
     d/dcond of the mixed arithmetic against the exact one; `_Scale.overflowed()` is False on a sane pass and True once a conversion
@@ -370,9 +370,10 @@ def test_graphed_training_step(tprec, conditioned, graph_first):
     launch path).  The replay must be the eager pass bit for bit -- loss and every parameter's .grad -- on the captured batch AND on a new
     batch copied into the static inputs, after an in-place optimizer step in between (the one repack launch inside the graph reads the
     parameters' own storage), with conditioning dropout drawn inside the graph.  graph_first: the graph is built before any eager pass,
-    and every eager backend is dropped and its memory returned (`training._HIP.clear()`, `empty_cache`) before each replay -- the packs
+    and every eager backend is dropped and its memory returned (`passes._HIP.clear()`, `empty_cache`) before each replay -- the packs
     and the repack table the replay reads are the graph's own."""
     from naturalspeech2_pytorch_amd import NaturalSpeech2, training
+    from naturalspeech2_pytorch_amd.training import passes
     kw = dict(dim=128, depth=2)
     if conditioned:
         kw.update(dim_prompt=96, condition_on_prompt=True, cond_drop_prob=0.)
@@ -408,7 +409,7 @@ def test_graphed_training_step(tprec, conditioned, graph_first):
         for ins in (b0, b1):
             l_e, g_e = eager(ins)
             if graph_first:
-                training._HIP.clear()
+                passes._HIP.clear()
                 torch.cuda.empty_cache()
             for p in m.parameters():
                 p.grad = None                                        # (eager grads gone: the replay must write its own static ones)
@@ -430,11 +431,11 @@ def test_retile_keeps_the_lean_kernels_images_current_under_the_one_launch_refre
     one-launch refresh.  Off by default (`_PackedCache.LEAN`: measured slower, profiles/r06_training_graph_ab.txt); here it is switched on:
     mixed-arithmetic losses and gradients over three optimizer steps must equal the default path's bit for bit -- the lean kernel is
     bit-identical to gemm2_kernel<2, *>, so any difference is a stale image."""
-    from naturalspeech2_pytorch_amd import training
+    from naturalspeech2_pytorch_amd.training import packs, passes
 
     def run(lean):
-        training._PackedCache.LEAN = lean
-        training._HIP.clear()                                        # fresh backends: the flag is read when a cache is created
+        packs._PackedCache.LEAN = lean
+        passes._HIP.clear()                                        # fresh backends: the flag is read when a cache is created
         m = Model(dim=256, depth=1)
         m.load_state_dict(make_weights({k: tuple(v.shape) for k, v in m.state_dict().items()}, seed=97))
         m = m.to(DEV).train()
@@ -449,7 +450,7 @@ def test_retile_keeps_the_lean_kernels_images_current_under_the_one_launch_refre
             loss.backward()
             out.append((loss.detach().clone(), m.wavenet.init_conv.weight.grad.clone(), getattr(m.transformer.to_pred, "1").weight.grad.clone()))
             opt.step()
-        tiled = sum(1 for bk in training._HIP.values() for v in bk.packs.map.values() if getattr(v.pw, "tiled", False))
+        tiled = sum(1 for bk in passes._HIP.values() for v in bk.packs.map.values() if getattr(v.pw, "tiled", False))
         return out, tiled
 
     try:
@@ -460,8 +461,8 @@ def test_retile_keeps_the_lean_kernels_images_current_under_the_one_launch_refre
             assert torch.equal(l0, l1) and torch.equal(a0, a1) and torch.equal(b0, b1)
         assert not torch.equal(ref[0][0], ref[2][0])                  # the steps did change the weights
     finally:
-        training._PackedCache.LEAN = False
-        training._HIP.clear()
+        packs._PackedCache.LEAN = False
+        passes._HIP.clear()
         ops.saturation_count(reset=True)
 
 

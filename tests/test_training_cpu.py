@@ -1,4 +1,4 @@
-"""Host logic of the HIP training path (`naturalspeech2_pytorch_amd/training.py`) on CPU: the autograd Functions run on
+"""Host logic of the HIP training path (`naturalspeech2_pytorch_amd/training/`) on CPU: the autograd Functions run on
 `tests/emu_backend.EmuBackend` -- a plain-torch restatement of every backend call with the kernels' layout contracts -- and every
 parameter gradient is compared with torch autograd through the PyTorch composite (`autograd_path.model_forward_autograd`, itself
 pinned to the reference's goldens in test_host_cpu.py).  What this pins: the chain rule inside the Functions, the transposed /
@@ -9,6 +9,7 @@ import torch
 
 from naturalspeech2_pytorch_amd import Model, training
 from naturalspeech2_pytorch_amd.autograd_path import model_forward_autograd
+from naturalspeech2_pytorch_amd.training import passes
 from tests.emu_backend import EmuBackend
 from tests.golden.gen import make_input, make_weights
 
@@ -70,7 +71,7 @@ def test_packed_cache_refreshes_in_place_and_never_serves_a_dead_parameter(monke
     """the training packs are keyed by id(parameter): a recycled id must not return another tensor's pack.  A moved version refreshes the
     pack in place (ns2_weight_update: same pack); from the second pass on, one ns2_weights_repack launch refreshes every trainable pack
     and stamps it fresh for the pass; a miss drops the re-pack table (it names the storage of the packs it was built for)."""
-    import naturalspeech2_pytorch_amd.training as T
+    import naturalspeech2_pytorch_amd.training.packs as T
     made, calls = [], []
 
     class FakePW:
@@ -96,7 +97,7 @@ def test_packed_cache_refreshes_in_place_and_never_serves_a_dead_parameter(monke
 
     monkeypatch.setattr(T.ops, "PackedWeight", FakePW)
     monkeypatch.setattr(T._lib, "load", FakeLib)
-    monkeypatch.setattr(T, "_s", lambda: None)
+    monkeypatch.setattr(T, "_stream", lambda: None)
     c = T._PackedCache()
     w = torch.nn.Parameter(torch.randn(4, 4))
     a = c.get(("f", id(w)), (w,), lambda: w)
@@ -134,8 +135,8 @@ def test_overflowed_is_false_when_a_peek_is_none(monkeypatch):
             pass
 
     counters = [torch.zeros(5, dtype=torch.int32)]
-    monkeypatch.setattr(training._Scale, "_peek", staticmethod(lambda: None if counters[0] is None else (counters[0], Ev())))
-    sc = training._Scale()
+    monkeypatch.setattr(passes._Scale, "_peek", staticmethod(lambda: None if counters[0] is None else (counters[0], Ev())))
+    sc = passes._Scale()
     step = object.__new__(training.GraphedTrainStep)
     step._before = sc._before
     assert not sc.overflowed() and not step.overflowed()
@@ -151,27 +152,27 @@ def test_backend_inside_a_private_registry_leaves_hip_alone(emu):
     """GraphedTrainStep warms up and captures against a registry of its own: backend() there neither reads nor adds to `_HIP`, and a
     `set_backend` substitute still comes first"""
     mine = {}
-    with training._registry(mine):
+    with passes._registry(mine):
         assert not isinstance(training.backend(), training.HipBackend) and not mine
     prev = training.set_backend(None)
-    before = dict(training._HIP)
+    before = dict(passes._HIP)
     key, eager = (torch.cuda.current_device() if torch.cuda.is_available() else -1, 3), object()
     try:
-        training._HIP[key] = eager                          # what backend() returns outside the registry
-        with training._registry(mine):
+        passes._HIP[key] = eager                          # what backend() returns outside the registry
+        with passes._registry(mine):
             bk = training.backend()
             assert isinstance(bk, training.HipBackend) and training.backend() is bk and mine == {key: bk}
-        assert training._HIP == {**before, key: eager} and training.backend() is eager
+        assert passes._HIP == {**before, key: eager} and training.backend() is eager
     finally:
-        training._HIP.clear()
-        training._HIP.update(before)
+        passes._HIP.clear()
+        passes._HIP.update(before)
         training.set_backend(prev)
 
 
 def test_cond_projections_fn_unused_outputs_and_views(emu):
     """CondProjectionsFn alone against torch autograd: several Linears of different widths on the same rows, one output unused (its
     gradient arrives as None and must count as zeros), parameter gradients returned as row blocks of ONE product."""
-    from naturalspeech2_pytorch_amd.training import CondProjectionsFn
+    from naturalspeech2_pytorch_amd.training.functions import CondProjectionsFn
     torch.manual_seed(3)
     B, K = 5, 24
     sizes = (16, 8, 40)
@@ -194,6 +195,72 @@ def test_cond_projections_fn_unused_outputs_and_views(emu):
            [b.grad if b.grad is not None else torch.zeros_like(b) for b in bs]
     for g, r in zip(got, want):
         assert torch.allclose(g, r, atol=1e-4), (g - r).abs().max()
+
+
+def test_cond_projections_fn_keeps_the_backend_of_its_forward(emu):
+    """every Function runs its backward on the backend its forward took (`ctx.bk`): by then the pass that selected it is over.  Backend A is
+    installed for `apply`, backend B for `backward`: B sees nothing, A the forward's product and the two of the backward (dt, dW)."""
+    from naturalspeech2_pytorch_amd.training.functions import CondProjectionsFn
+
+    class Recording(EmuBackend):
+        def skinny(self, *a, **k):
+            self.calls.append("skinny")
+            return super().skinny(*a, **k)
+
+    torch.manual_seed(4)
+    l1, l2 = torch.nn.Linear(16, 8), torch.nn.Linear(16, 4)
+    t = torch.randn(2, 16, requires_grad=True)
+    a, b = Recording(), Recording()
+    training.set_backend(a)                                 # (the `emu` fixture restores what was there before the test)
+    y1, y2 = CondProjectionsFn.apply(t, l1.weight, l1.bias, l2.weight, l2.bias)
+    assert a.calls == ["skinny"]
+    training.set_backend(b)
+    (y1.sum() + y2.square().sum()).backward()
+    assert b.calls == [] and a.calls == ["skinny"] * 3, (a.calls, b.calls)
+    ref = torch.autograd.grad(l1(t).sum() + l2(t).square().sum(), (t, l2.weight))
+    assert torch.allclose(t.grad, ref[0], atol=1e-5) and torch.allclose(l2.weight.grad, ref[1], atol=1e-5)
+
+
+def test_a_pass_that_fails_while_it_begins_restores_the_pass_state():
+    """`passes.training_pass` alone sets and restores the pass state (precision, loss scale, device), and its `finally` covers everything
+    after the state is set: a `packs.begin_pass()` that raises (it launches ns2_weights_repack: a HIP error there) must leave the state as
+    it was before the call -- for the denoiser's pass (mixed: the scale has been constructed by then) and for an encoder pass, here begun
+    inside another pass so that "as it was" is not the default state."""
+    from naturalspeech2_pytorch_amd.transformer import Transformer
+
+    class Packs:
+        fail = True
+
+        def begin_pass(self, frozen=False):
+            if self.fail:
+                raise RuntimeError("ns2_weights_repack: HIP error")
+
+    bk = EmuBackend()
+    bk.packs = Packs()
+    prev = training.set_backend(bk)
+    try:
+        m = Model(dim=64, depth=1, wavenet_layers=2, wavenet_stacks=1)
+        m.train_precision = "mixed"
+        x = make_input("x", (1, 8, 64), seed=6)
+        before = passes.current()
+        assert before == (3, None, None)
+        with pytest.raises(RuntimeError, match="ns2_weights_repack"):
+            training.model_forward_train(m, x, make_input("times", (1,), seed=6, uniform=True))
+        assert passes.current() is before
+        tr = Transformer(64, depth=1)
+        with pytest.raises(RuntimeError, match="ns2_weights_repack"):
+            training.transformer_forward_train(tr, x)
+        assert passes.current() is before
+        bk.packs.fail = False
+        with passes.training_pass(training.TRAIN_PRECISIONS["mixed"], x) as outer:
+            assert passes.current() is outer and outer.precision == 4 and outer.scale is not None
+            bk.packs.fail = True
+            with pytest.raises(RuntimeError, match="ns2_weights_repack"):
+                training.transformer_forward_train(tr, x)
+            assert passes.current() is outer
+        assert passes.current() is before
+    finally:
+        training.set_backend(prev)
 
 
 def _golden_grad_case(name):
@@ -307,7 +374,7 @@ def test_training_path_refuses_shapes_the_kernels_are_not_written_for():
 @pytest.mark.parametrize("cond", [False, True], ids=["uncond", "cond"])
 def test_mixed_training_arithmetic_needs_and_gets_its_loss_scale(cond):
     """train_precision="mixed": the GEMMs of forward, dgrad and wgrad multiply FMT_H8 operands (IEEE half + e5m2 correction terms).
-    With the gradient of a mean-reduced loss (~1e-7 per element) the unscaled pass loses everything; under training._Scale -- a power
+    With the gradient of a mean-reduced loss (~1e-7 per element) the unscaled pass loses everything; under passes._Scale -- a power
     of two chosen from the incoming gradient, token-sized gradients kept scaled between the Functions, parameter / conditioning /
     input gradients unscaled where they leave -- every gradient matches fp32 autograd like the exact arithmetic does.  Host logic
     on the emulated backend (tests/emu_backend.MixedEmuBackend); the kernels: tests/test_backward_gpu.py."""
@@ -360,7 +427,7 @@ def test_repack_parts_describe_the_sources_the_packs_were_made_from():
     elements, possibly negative).  Walking the parameter through those strides on the CPU must rebuild exactly the matrix `make_src`
     hands to the first pack -- for the forward pack, the dgrad pack of a Linear (W^T), of a causal conv (W^T with flipped taps) and
     the q | kv concatenations (two parts, by rows / by columns)."""
-    from naturalspeech2_pytorch_amd.training import _PackedCache
+    from naturalspeech2_pytorch_amd.training.packs import _PackedCache
 
     class PW:
         handle = 0

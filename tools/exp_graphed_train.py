@@ -4,6 +4,7 @@ import argparse, os, sys, time
 import torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from naturalspeech2_pytorch_amd import Model, NaturalSpeech2, training  # noqa: E402
+from naturalspeech2_pytorch_amd.training import packs  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--headline", action="store_true")
@@ -11,7 +12,7 @@ ap.add_argument("--lean", action="store_true", help="mixed linear packs WITH the
 args = ap.parse_args()
 dev = torch.device("cuda:0")
 if args.lean:
-    training._PackedCache.LEAN = True
+    packs._PackedCache.LEAN = True
 cases = [("d128_L6_b4", dict(dim=128, depth=6), 4, 1024), ("cond_d128_L2_b3", dict(dim=128, depth=2, dim_prompt=128, condition_on_prompt=True), 3, 512)]
 if args.headline:
     cases.append(("d512_L12_b32", dict(dim=512, depth=12), 32, 1024))
