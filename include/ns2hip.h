@@ -313,12 +313,20 @@ int ns2_debug_lstm_inject_abort(int n);
  * Synchronises the device: call it between sampling runs, not per step.  A non-zero count means the model needs
  * precision 3 (bf16 planes: fp32 exponent range). */
 int ns2_saturation_count(int reset, int64_t* count);
-/* The same counters without a synchronisation: enqueues, on `stream`, copies of the four per-translation-unit counters (cumulative
- * since the last reset) into host4[0..3] -- host memory that stays valid until the stream reaches this point (pinned memory for a
- * truly asynchronous copy).  The caller records an event behind it and reads the values once the event has completed; the host-side
- * `Model` does so every few forwards, so that calls from ANY wrapper (this package's sampler, the reference's own
- * NaturalSpeech2 / Trainer around compat.HipBackedModel, a bare Model.forward) notice clamped activations. */
-int ns2_saturation_peek_async(unsigned int* host4, void* stream);
+/* The counters behind that total.  Every source file of the library whose kernels convert to the IEEE-half formats owns one and
+ * registers it when the library is loaded: ns2_saturation_counters is how many there are (no GPU needed; -1 if the library was built
+ * with more than its registry holds, and the other entry points then fail), ns2_saturation_counter_name(i) the source file of
+ * counter i (NULL outside 0 <= i < count). */
+int ns2_saturation_counters(void);
+const char* ns2_saturation_counter_name(int i);
+/* The same counters without a synchronisation: enqueues, on `stream`, one copy per registered counter (cumulative since the last
+ * reset) into host[0..n), n = ns2_saturation_counters() -- host memory that stays valid until the stream reaches this point (pinned
+ * memory for a truly asynchronous copy).  capacity < n is an argument error and nothing is written.  The order of the words is
+ * unspecified: sum them, or compare them with an earlier peek.  The caller records an event behind it and reads the values once
+ * the event has completed; the host-side `Model` does so every few forwards, so that calls from ANY wrapper (this package's sampler,
+ * the reference's own NaturalSpeech2 / Trainer around compat.HipBackedModel, a bare Model.forward) notice clamped activations, and
+ * a training loop under the mixed arithmetic compares a peek before the pass with one after it (an overflowed step). */
+int ns2_saturation_peek(unsigned int* host, int capacity, void* stream);
 
 /* EnCodec RVQ (HFENC:364-369, 424-447; reference call sites NS2:1445, NS2:1611, NS2:1496).
  * cb_norm: [Q, C] scratch filled by ns2_rvq_prepare (once per codebook set). codes: [M, Q] int64; emb/residual [M, D] or null */
@@ -398,17 +406,13 @@ void ns2_model_destroy(ns2_model* m);
  *   4 = "mixed": FMT_H8 lines, one IEEE-half product + both correction terms on the fp8 MFMA (2 MFMA units instead of 3).  IEEE half
  *       stops at 65504 and loses precision below 6e-5, so the caller scales the loss (a power of two; every gradient is linear in
  *       it) -- the reference trains under accelerate's fp16 mixed precision the same way (NS2:1710-1711, 1723-1726).  Values that
- *       leave the half range are counted (ns2_saturation_count): an overflowed step is detected, not silently clamped.
+ *       leave the half range are counted (ns2_saturation_count, ns2_saturation_peek): an overflowed step is detected, not silently clamped.
  *       The attention products stay bf16 x3 at both precisions (q / k / v / dO planes are bf16 hi / lo: ns2_linear_split_as).
  * The contractions reuse the forward GEMM family:
  *   dgrad  dX = dY W   : ns2_linear_f32 on a SECOND pack of the weight -- ns2_weight_pack of W^T ([in, out, taps] with the taps
  *                        flipped), conv_taps as in the forward, pad_left = 0 (the gradient of a causal conv looks ahead);
  *   wgrad  dW = dY^T X : ns2_wgrad on TRANSPOSED planes (contraction over the tokens), split over fixed slots + fixed-order sum.
  * Every reduction of this section is slot based and summed in a fixed order: gradients are deterministic, no atomics. */
-
-/* the training kernels' share of the range guard, stream-ordered and non-synchronising (one word, pinned host memory); the gradient
- * GEMMs' own conversions are in ns2_saturation_peek_async's words.  ns2_saturation_count sums all of them. */
-int ns2_saturation_peek_train_async(unsigned int* host1, void* stream);
 
 /* re-pack a weight IN PLACE from new fp32 values (same shape / flags as the ns2_weight_pack call that made it): stream-ordered,
  * no allocation, no synchronisation -- the per-step refresh of an optimizer's weights */

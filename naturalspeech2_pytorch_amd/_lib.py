@@ -100,7 +100,9 @@ SIGNATURES = {
     "ns2_lstm_abort_count": (I, [I, POINTER(c_int64)]),
     "ns2_debug_lstm_inject_abort": (I, [I]),
     "ns2_saturation_count": (I, [I, POINTER(c_int64)]),
-    "ns2_saturation_peek_async": (I, [P, P]),
+    "ns2_saturation_counters": (I, []),
+    "ns2_saturation_counter_name": (c_char_p, [I]),
+    "ns2_saturation_peek": (I, [P, I, P]),
     "ns2_rvq_prepare": (I, [P, P, I, I, I, P]),
     "ns2_rvq_encode": (I, [P, P, P, P, P, P, P, I, I, I, I, F, P]),
     "ns2_rvq_decode": (I, [P, P, P, I, I, I, I, P]),
@@ -128,7 +130,6 @@ SIGNATURES = {
     "ns2_weight_tile_linear": (I, [P, P]),
     "ns2_weight_tile_wavenet": (I, [P, P]),
     "ns2_conv3_input_ld": (I, [I]),
-    "ns2_saturation_peek_train_async": (I, [P, P]),
     "ns2_grad_prep_slices": (L, [I, L]),
     "ns2_grad_prep": (I, [P, L, I, I, I, I, P, P, I, P, P, L, I, I, P, I, P]),
     "ns2_planes_transpose": (I, [P, P, I, I, I, I, I, I, P, P, L, I, I, I, P]),

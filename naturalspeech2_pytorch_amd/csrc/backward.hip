@@ -1005,6 +1005,4 @@ hipError_t launch_dropout_keep_mask(const uint32_t* seed, uint32_t call, float p
   return hipGetLastError();
 }
 
-NS2_DEFINE_SATURATION_READER(backward)
-
 }  // namespace ns2

@@ -19,6 +19,27 @@ void set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
+// the range-guard counters of the library, one per translation unit that includes ns2_common.h (ns2_sat_registry.h).  Filled by static
+// initialisers of OTHER translation units, in no particular order: a function-local static (zero-initialised storage, no allocation, no
+// HIP call), so it exists whoever registers first, and the library still loads where there is no GPU.
+namespace {
+struct SatRegistry { SatCounter c[SAT_COUNTERS_MAX]; int n; bool full; };
+SatRegistry& sat_registry() {
+  static SatRegistry r;
+  return r;
+}
+}  // namespace
+void register_sat_counter(const SatCounter& c) {
+  SatRegistry& r = sat_registry();
+  if (r.n < SAT_COUNTERS_MAX) r.c[r.n++] = c;
+  else r.full = true;
+}
+const SatCounter* sat_counters(int* n) {
+  const SatRegistry& r = sat_registry();
+  *n = r.n;
+  return r.full ? nullptr : r.c;
+}
+
 }  // namespace ns2
 
 using namespace ns2;
@@ -43,7 +64,7 @@ static inline int prec_ok(int p) { return p >= 1 && p <= 4; }
 static inline int op_fmt(int p) { return p == 2 ? FMT_F16 : (p == 4 ? FMT_H8 : FMT_BF16); }
 
 extern "C" const char* ns2_last_error(void) { return g_err; }
-extern "C" int ns2_version(void) { return 116; }   // 116: ns2_groupnorm_silu, ns2_length_regulate(_totals), ns2_row_dot (duration_pitch.hip); 115: ns2_weights_retile; 114: ns2_attention_hd (head dims 32 / 64 / 128), ns2_model_create takes dim_head 32 / 128; 113: ns2_weight_tile_conv3 + ns2_conv3_input_ld (the dedicated FF causal conv kernel, ffconv_kernel.h), ns2_weight_tile_linear (gemm3_kernel.h), ns2_weight_tile_wavenet (wavenet3_kernel.h), ns2_debug_force_gemm(4 / 5); 112: ns2_seanet_resblock_narrow; 111: training entry points take a precision (3 = bf16 x3, 4 = mixed on FMT_H8 lines), ns2_linear_split_as; 110: backward pass (capi_train.cpp: ns2_wgrad, ns2_attention_bwd, ...), ns2_weight_update; 109: ns2_seanet_conv_narrow; 108: ns2_seanet_prep2; 107: ns2_lstm2 (two LSTM layers, one launch); 106: ns2_saturation_peek_async; 105: ns2_lstm_layer takes the scratch size (persistent recurrence); 104: model precision 5 (per-site plan); 103: precision 2 / 4 at op level, caller-owned skinny-linear scratch
+extern "C" int ns2_version(void) { return 117; }   // 117: the range-guard counters register themselves: ns2_saturation_counters / _counter_name / _peek replace ns2_saturation_peek_async / _peek_train_async; 116: ns2_groupnorm_silu, ns2_length_regulate(_totals), ns2_row_dot (duration_pitch.hip); 115: ns2_weights_retile; 114: ns2_attention_hd (head dims 32 / 64 / 128), ns2_model_create takes dim_head 32 / 128; 113: ns2_weight_tile_conv3 + ns2_conv3_input_ld (the dedicated FF causal conv kernel, ffconv_kernel.h), ns2_weight_tile_linear (gemm3_kernel.h), ns2_weight_tile_wavenet (wavenet3_kernel.h), ns2_debug_force_gemm(4 / 5); 112: ns2_seanet_resblock_narrow; 111: training entry points take a precision (3 = bf16 x3, 4 = mixed on FMT_H8 lines), ns2_linear_split_as; 110: backward pass (capi_train.cpp: ns2_wgrad, ns2_attention_bwd, ...), ns2_weight_update; 109: ns2_seanet_conv_narrow; 108: ns2_seanet_prep2; 107: ns2_lstm2 (two LSTM layers, one launch); 106: ns2_saturation_peek_async; 105: ns2_lstm_layer takes the scratch size (persistent recurrence); 104: model precision 5 (per-site plan); 103: precision 2 / 4 at op level, caller-owned skinny-linear scratch
 extern "C" int ns2_debug_force_gemm(int kernel) {
   ARGCHK(kernel >= 0 && kernel <= 5, "ns2_debug_force_gemm: 0 auto, 1 = 128x128 kernel, 2 = 256x256 kernel, 3 = auto without split-K, 4 = auto without the dedicated kernels (FF conv, lean linear, lean Wavenet), 5 = auto without split-K, the dedicated kernels whenever eligible");
   force_gemm_kernel(kernel);
@@ -357,18 +378,41 @@ extern "C" int ns2_lstm2(const float* xproj1, int64_t ld_x, const float* w_hh1, 
   return NS2_OK;
 }
 
+// The range guard's entry points loop over the registered counters; a registration that did not fit is an error the caller sees.
+#define SAT_FULL_MSG "more translation units registered a range counter than SAT_COUNTERS_MAX holds"
 extern "C" int ns2_saturation_count(int reset, int64_t* count) {
   ARGCHK(count != nullptr, "ns2_saturation_count: null pointer");
+  int n = 0;
+  const SatCounter* regs = sat_counters(&n);
+  ARGCHK(regs != nullptr, "ns2_saturation_count: " SAT_FULL_MSG);
   HIPRET(hipDeviceSynchronize());                    // a diagnostic read between sampling runs, never on a launch path
-  const unsigned int parts[5] = {saturation_read_gemm(reset != 0), saturation_read_gemm2(reset != 0),
-                                 saturation_read_attention(reset != 0), saturation_read_elementwise(reset != 0),
-                                 saturation_read_backward(reset != 0)};
   int64_t tot = 0;
-  for (unsigned int p : parts) {
+  for (int i = 0; i < n; ++i) {
+    const unsigned int p = regs[i].read(reset != 0);
     ARGCHK(p != ~0u, "ns2_saturation_count: could not read the device counter");
     tot += p;
   }
   *count = tot;
+  return NS2_OK;
+}
+extern "C" int ns2_saturation_counters(void) {
+  int n = 0;
+  return sat_counters(&n) ? n : -1;
+}
+extern "C" const char* ns2_saturation_counter_name(int i) {
+  int n = 0;
+  const SatCounter* regs = sat_counters(&n);
+  if (!regs || i < 0 || i >= n) return nullptr;
+  const char* slash = strrchr(regs[i].file, '/');
+  return slash ? slash + 1 : regs[i].file;
+}
+extern "C" int ns2_saturation_peek(unsigned int* host, int capacity, void* stream) {
+  ARGCHK(host != nullptr, "ns2_saturation_peek: null pointer");
+  int n = 0;
+  const SatCounter* regs = sat_counters(&n);
+  ARGCHK(regs != nullptr, "ns2_saturation_peek: " SAT_FULL_MSG);
+  ARGCHK(capacity >= n, "ns2_saturation_peek: fewer words than registered counters (ns2_saturation_counters)");
+  for (int i = 0; i < n; ++i) HIPRET(regs[i].peek(host + i, (hipStream_t)stream));
   return NS2_OK;
 }
 
@@ -384,16 +428,6 @@ extern "C" int ns2_lstm_abort_count(int reset, int64_t* count) {
   const unsigned int v = lstm_abort_read(reset != 0);
   ARGCHK(v != ~0u, "ns2_lstm_abort_count: could not read the device counter");
   *count = v;
-  return NS2_OK;
-}
-
-extern "C" int ns2_saturation_peek_async(unsigned int* host4, void* stream) {
-  ARGCHK(host4 != nullptr, "ns2_saturation_peek_async: null pointer");
-  hipStream_t s = (hipStream_t)stream;
-  HIPRET(saturation_peek_gemm(host4 + 0, s));
-  HIPRET(saturation_peek_gemm2(host4 + 1, s));
-  HIPRET(saturation_peek_attention(host4 + 2, s));
-  HIPRET(saturation_peek_elementwise(host4 + 3, s));
   return NS2_OK;
 }
 

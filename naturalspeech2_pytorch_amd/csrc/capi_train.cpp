@@ -95,14 +95,6 @@ extern "C" int ns2_weights_repack(const void* table_device, int n, int64_t total
   return NS2_OK;
 }
 
-// the training kernels' share of the range guard (ns2_saturation_count sums it in; this is its stream-ordered, non-synchronising
-// read for a training loop under the mixed arithmetic: one word into pinned host memory)
-extern "C" int ns2_saturation_peek_train_async(unsigned int* host1, void* stream) {
-  ARGCHK(host1 != nullptr, "ns2_saturation_peek_train_async: null pointer");
-  HIPRET(saturation_peek_backward(host1, (hipStream_t)stream));
-  return NS2_OK;
-}
-
 extern "C" int64_t ns2_grad_prep_slices(int M, int64_t ld_t) { return M > 0 ? (int64_t)tplanes_slices(M, (long)ld_t) : 0; }
 
 extern "C" int ns2_grad_prep(const float* x, int64_t ldx, int M, int C, int seq_len, int shift, uint16_t* row_hi, uint16_t* row_lo,

@@ -1477,6 +1477,4 @@ unsigned int lstm_abort_read(bool reset) {
   return v;
 }
 
-NS2_DEFINE_SATURATION_READER(elementwise)
-
 }  // namespace ns2

@@ -1131,6 +1131,4 @@ hipError_t gemm3_build_tiles(const bf16_t* w_hi, int ldk, int rows_p, bf16_t* ou
 size_t wavenet3_tiles_bytes(int rows_p, int dp, int nz, int phase) { return phase == 1 ? wavenet3_tiles1_bytes(rows_p, dp, nz) : wavenet3_tiles2_bytes(rows_p, dp, nz); }
 hipError_t wavenet3_build_tiles(const bf16_t* w_hi, int rows_p, int dp, int nz, bf16_t* t1, bf16_t* t2, hipStream_t s) { return launch_wavenet3_tiles(w_hi, rows_p, dp, nz, t1, t2, s); }
 
-NS2_DEFINE_SATURATION_READER(gemm2)
-
 }  // namespace ns2

@@ -18,6 +18,7 @@
 #include <stdint.h>
 
 #include "ns2_fmt.h"
+#include "ns2_sat_registry.h"
 
 typedef uint16_t bf16_t;                                           // raw bf16 bits
 typedef __attribute__((ext_vector_type(8))) short bf16x8;          // MFMA A/B fragment (4 VGPRs)
@@ -68,21 +69,27 @@ NS2_DEVINL void split2(float a, float b, uint32_t& hi, uint32_t& lo) {
 // keeps everything finite but is WRONG, silently (measured: weights x8 on a random-init d128/L6 model -> relative error 1.0
 // at precisions 2 and 4, 1e-5 at precision 3 whose bf16 planes have the fp32 exponent range).  Every conversion that clamps
 // (or meets a NaN) bumps a per-device counter; the host reads it after a sampling run (ns2_saturation_count) and fails
-// loudly.  One static counter per translation unit (no relocatable device code); capi.cpp sums them.
+// loudly.  One static counter per translation unit (no relocatable device code).  Including this header is all it takes to be
+// guarded: the translation unit registers its counter's two host-side readers when the library is loaded (ns2_sat_registry.h), and
+// capi.cpp's ns2_saturation_count / ns2_saturation_peek loop over the registry.
 static __device__ unsigned int ns2_sat_counter;
 NS2_DEVINL void note_out_of_range(float a, float b, float limit) {
   if (!(fabsf(a) <= limit) || !(fabsf(b) <= limit)) atomicAdd(&ns2_sat_counter, 1u);
 }
-#define NS2_DEFINE_SATURATION_READER(tu)                                                              \
-  unsigned int saturation_read_##tu(bool reset) {                                                     \
-    unsigned int v = 0;                                                                               \
-    if (hipMemcpyFromSymbol(&v, HIP_SYMBOL(ns2_sat_counter), sizeof v) != hipSuccess) return ~0u;     \
-    if (reset && v) { const unsigned int z = 0; (void)hipMemcpyToSymbol(HIP_SYMBOL(ns2_sat_counter), &z, sizeof z); } \
-    return v;                                                                                         \
-  }                                                                                                   \
-  hipError_t saturation_peek_##tu(unsigned int* dst, hipStream_t s) {                                 \
-    return hipMemcpyFromSymbolAsync(dst, HIP_SYMBOL(ns2_sat_counter), sizeof(unsigned int), 0, hipMemcpyDeviceToHost, s); \
-  }
+namespace {
+unsigned int sat_read_tu(bool reset) {
+  unsigned int v = 0;
+  if (hipMemcpyFromSymbol(&v, HIP_SYMBOL(ns2_sat_counter), sizeof v) != hipSuccess) return ~0u;
+  if (reset && v) { const unsigned int z = 0; (void)hipMemcpyToSymbol(HIP_SYMBOL(ns2_sat_counter), &z, sizeof z); }
+  return v;
+}
+hipError_t sat_peek_tu(unsigned int* dst, hipStream_t s) {
+  return hipMemcpyFromSymbolAsync(dst, HIP_SYMBOL(ns2_sat_counter), sizeof(unsigned int), 0, hipMemcpyDeviceToHost, s);
+}
+const struct SatRegistrar {
+  SatRegistrar() { ns2::register_sat_counter({sat_read_tu, sat_peek_tu, __BASE_FILE__}); }
+} sat_registrar;
+}  // namespace
 
 // ---- IEEE half operands ("half" precision: ONE fp16 product per contraction, fp32 accumulate).  fp16 carries 11
 // significand bits against bf16's 8, so a single product lands at ~5e-4 end to end where bf16 needs the 3-product split

@@ -23,6 +23,7 @@ from torch import nn
 from . import _lib
 from ._lib import ModelConfig, check
 from ._cache import tensors_fingerprint
+from ._range_guard import RangePeek
 
 
 # ------------------------------------------------------------------------------------------ parameter holders
@@ -105,8 +106,7 @@ class _NativeState:
         self.calls_since_refresh = 0
         self.mode_flag = None            # module.training at the last HIP forward
         self.autograd_seen = False       # an autograd forward ran since the last HIP forward (a training step happened)
-        self.sat_pinned = None           # pinned int32[4]: target of ns2_saturation_peek_async
-        self.sat_event = None
+        self.sat_peek = RangePeek()      # the asynchronous read of the range counters, in flight or not
         self.sat_seen = 0                # counter total already accounted for
         self.calls_since_peek = 0
         self.peek_now = True             # read the counters right behind the next forward (first forward of a run)
@@ -135,7 +135,7 @@ class _NativeState:
         self.sig = None
         self.fingerprint = None
         self.cond_cache = {}
-        self.sat_event = None
+        self.sat_peek.drop()
         self.chk_ref = self.chk_event = None
 
     def __del__(self):
@@ -184,7 +184,7 @@ class HipDenoiserMixin:
         if fp != ns.fingerprint:
             ns.release()
             return True
-        if self._range_guarded() and ns.sat_event is None:
+        if self._range_guarded() and not ns.sat_peek.in_flight():
             # run boundary: what the per-device counters hold by now (another model, a codec run) is not this run's
             from . import ops
             ns.sat_seen = ops.saturation_count(reset=False, device=next(self.parameters()).device)
@@ -250,13 +250,13 @@ class HipDenoiserMixin:
             return
         if sync:
             self._peek_saturation()
-        ev = ns.sat_event
-        if ev is None or not (sync or ev.query()):
+        pk = ns.sat_peek
+        if not pk.in_flight() or not (sync or pk.done()):
             return
         if sync:
-            ev.synchronize()
-        ns.sat_event = None
-        tot = int(ns.sat_pinned.sum().item())
+            pk.wait()
+        tot = pk.total()
+        pk.drop()
         new, ns.sat_seen = tot - ns.sat_seen, tot
         if new > 0:
             raise _lib.Ns2Error(
@@ -266,16 +266,7 @@ class HipDenoiserMixin:
 
     def _peek_saturation(self):
         ns = self._native
-        dev = next(self.parameters()).device
-        if ns.sat_pinned is None:
-            ns.sat_pinned = torch.zeros(4, dtype=torch.int32).pin_memory()
-        with torch.cuda.device(dev):
-            if ns.sat_event is not None:
-                ns.sat_event.synchronize()          # the pinned words are about to be rewritten
-            check(_lib.load().ns2_saturation_peek_async(ns.sat_pinned.data_ptr(), torch.cuda.current_stream().cuda_stream),
-                  "ns2_saturation_peek_async")
-            ns.sat_event = torch.cuda.Event()
-            ns.sat_event.record()
+        ns.sat_peek.take(next(self.parameters()).device)
         ns.calls_since_peek = 0
 
     def _apply(self, fn, *args, **kwargs):               # .to() / .cuda() / .float(): parameters move or are rewritten
@@ -337,7 +328,7 @@ class HipDenoiserMixin:
         if self._range_guarded():          # what the device counters hold already (other models, earlier runs) is not ours
             from . import ops
             ns.sat_seen = ops.saturation_count(reset=False, device=dev)
-            ns.sat_event = None
+            ns.sat_peek.drop()
         return ns
 
     def _workspace(self, ns, B, N, n_prompt, n_cond):
@@ -493,7 +484,7 @@ class HipDenoiserMixin:
     def _after_hip_forward(self, ns):
         if self._range_guarded() and not torch.cuda.is_current_stream_capturing():
             ns.calls_since_peek += 1
-            if ns.sat_event is None and (ns.peek_now or ns.calls_since_peek >= self.SAT_PEEK_EVERY):
+            if not ns.sat_peek.in_flight() and (ns.peek_now or ns.calls_since_peek >= self.SAT_PEEK_EVERY):
                 self._peek_saturation()
                 ns.peek_now = False
         ns.last_call = time.monotonic()

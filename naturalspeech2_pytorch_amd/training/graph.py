@@ -1,7 +1,8 @@
 """The training step (loss + backward) of a fixed shape as one HIP graph"""
 import torch
 
-from .passes import _registry, _Scale
+from .._range_guard import RangePeek, moved
+from .passes import _registry
 
 
 class _LossOf(torch.nn.Module):
@@ -80,11 +81,11 @@ class GraphedTrainStep:
         for s, t in zip(self.inputs, inputs):
             if t is not s:
                 s.copy_(t)
-        self._before = _Scale._peek()
+        self._before = RangePeek().take(self.inputs[0].device)
         self.graph.replay()
         for p, g in zip(self.params, self.grads):         # (whatever a zero_grad(set_to_none=True) or an eager pass in between left there)
             p.grad = g
         return self.loss
 
     def overflowed(self) -> bool:
-        return _Scale._moved(self._before)
+        return moved(self._before)

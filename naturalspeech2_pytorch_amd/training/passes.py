@@ -6,7 +6,7 @@ from typing import NamedTuple, Optional
 
 import torch
 
-from .. import _lib
+from .._range_guard import RangePeek, moved
 from .backend import HipBackend
 
 TRAIN_PRECISIONS = {"exact": 3, "mixed": 4}
@@ -27,44 +27,17 @@ class _Scale:
     (`model._last_loss_scale.overflowed()` after `loss.backward()`)."""
     TARGET = 64.0
 
-    def __init__(self):
+    def __init__(self, device=None):
         self.s = None
         self.inv = None
-        self._before = self._peek()          # stream-ordered: the counters as they stand when the pass is enqueued
-
-    @staticmethod
-    def _peek():
-        """the five range counters of the device (ns2_saturation_peek_async: forward GEMMs / attention / pointwise;
-        ns2_saturation_peek_train_async: the training kernels), copied to pinned memory on the current stream -- no synchronisation"""
-        if not torch.cuda.is_available() or torch.cuda.is_current_stream_capturing():
-            return None                      # (under capture GraphedTrainStep peeks around the replay instead)
-        try:
-            lib = _lib.load()
-        except Exception:
-            return None
-        buf = torch.zeros(5, dtype=torch.int32).pin_memory()
-        s = torch.cuda.current_stream().cuda_stream
-        _lib.check(lib.ns2_saturation_peek_async(buf.data_ptr(), s), "ns2_saturation_peek_async")
-        _lib.check(lib.ns2_saturation_peek_train_async(buf.data_ptr() + 16, s), "ns2_saturation_peek_train_async")
-        ev = torch.cuda.Event()
-        ev.record()
-        return buf, ev
-
-    @staticmethod
-    def _moved(before):
-        """did the range counters move since `before` (a `_peek()`)?  Waits for the work enqueued so far (one event synchronisation).
-        False when either peek is None."""
-        after = None if before is None else _Scale._peek()
-        if after is None:
-            return False
-        after[1].synchronize()
-        return bool((after[0] != before[0]).any().item())
+        self._before = RangePeek().take(device)      # stream-ordered: the counters of the pass's device as they stand when it is enqueued
+                                                     # (None under capture: GraphedTrainStep peeks around the replay instead)
 
     def overflowed(self) -> bool:
         """did a conversion of this pass (forward activations, scaled gradients) leave the IEEE-half range?  Call after `backward()`;
         waits for the pass (one event synchronisation).  True: the gradients of this step are clamped somewhere -- skip the optimizer
         step (and train on with `train_precision="exact"` if it keeps happening: bf16 planes have the fp32 range)."""
-        return self._moved(self._before)
+        return moved(self._before)
 
     def choose(self, g):
         amax = g.detach().abs().amax().clamp_min(1e-30).float()
@@ -178,7 +151,8 @@ def training_pass(precision, like):
     global _PASS
     prev = _PASS
     try:
-        _PASS = _Pass(precision, _Scale() if precision == TRAIN_PRECISIONS["mixed"] else None, like.device.index if like.is_cuda else None)
+        dev = like.device.index if like.is_cuda else None
+        _PASS = _Pass(precision, _Scale(dev) if precision == TRAIN_PRECISIONS["mixed"] else None, dev)
         bk = backend()
         if hasattr(bk, "packs"):
             bk.packs.begin_pass(frozen=_WEIGHTS_FROZEN)

@@ -130,17 +130,28 @@ def test_packed_cache_refreshes_in_place_and_never_serves_a_dead_parameter(monke
 def test_overflowed_is_false_when_a_peek_is_none(monkeypatch):
     """`_Scale.overflowed` and `GraphedTrainStep.overflowed` compare the range counters with the snapshot taken before the pass; a peek
     that returns None (no device, no library, a stream under capture) means "no overflow seen", never a TypeError"""
+    import os
+    from naturalspeech2_pytorch_amd import _lib, _range_guard
+
     class Ev:
         def synchronize(self):
             pass
 
-    counters = [torch.zeros(5, dtype=torch.int32)]
-    monkeypatch.setattr(passes._Scale, "_peek", staticmethod(lambda: None if counters[0] is None else (counters[0], Ev())))
+    n = _lib.load().ns2_saturation_counters() if os.path.exists(_lib.LIB_PATH) else 9      # one word per registered counter
+    counters = [torch.zeros(n, dtype=torch.int32)]
+
+    def take(self, device=None):
+        if counters[0] is None:
+            return None
+        self.words, self.event, self.device = counters[0], Ev(), device
+        return self
+
+    monkeypatch.setattr(_range_guard.RangePeek, "take", take)
     sc = passes._Scale()
     step = object.__new__(training.GraphedTrainStep)
     step._before = sc._before
     assert not sc.overflowed() and not step.overflowed()
-    counters[0] = torch.ones(5, dtype=torch.int32)
+    counters[0] = torch.ones(n, dtype=torch.int32)
     assert sc.overflowed() and step.overflowed()
     counters[0] = None
     assert not sc.overflowed() and not step.overflowed()
