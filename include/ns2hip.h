@@ -546,6 +546,23 @@ int ns2_silu_bwd(const float* dy, int64_t lddy, const float* x, int64_t ldx, int
  * pad_id (an ordinary row of the table, as upstream); summed in ascending token order: bit-reproducible */
 int ns2_embedding_bwd(const int64_t* ids, int64_t M, int pad_id, const float* dy, int64_t lddy, int rows, int d, float* dw, void* stream);
 
+/* ---- training of the DurationPitchPredictor (NS2:344-527; its duration / pitch L1 terms, NS2:1578-1589) ----
+ * The training FORWARD of GroupNorm + SiLU (+ residual) is ns2_groupnorm_silu with an fp32 output: the caller keeps its workspace, which
+ * holds the per-chunk (count, mean, M2) slots.  ns2_groupnorm_silu_bwd takes that buffer as `stats` and combines the slots in the same
+ * order with the same code, so it normalises with the forward's mean and rstd bit for bit.  With xh = (x - mean) rstd, z = xh w + b,
+ * dz = dy silu'(z):  dweight_dbias [2 C] = (sum dz xh | sum dz) over all rows;  dx = rstd (dz w - s1 / N - xh s2 / N), s1 = sum dz w,
+ * s2 = sum dz w xh per (utterance, group), N = n C / groups.  (The residual's gradient is dy itself.)  dy [B n, lddy], x and dx [B n, C].
+ * Column sums per 32-row chunk go to fixed slots of the workspace and are added in a fixed order: no atomics, bit-reproducible. */
+int64_t ns2_groupnorm_silu_bwd_workspace_bytes(int B, int n, int C);
+int ns2_groupnorm_silu_bwd(const float* dy, int64_t lddy, const float* x, int B, int n, int C, int groups, const float* weight,
+                           const float* bias, float eps, const void* stats, int64_t stats_bytes, float* dx, float* dweight_dbias,
+                           void* workspace, int64_t workspace_bytes, void* stream);
+/* backward of out = relu(h . w + b) (ns2_row_dot with relu): g = dout where out > 0 else 0;  dh [M, lddh] = g w;  dw_db [K + 1] =
+ * (sum_m g h[m, :] | sum_m g), from per-64-row slots added in a fixed order.  K, ldh, lddh multiples of 4. */
+int64_t ns2_row_dot_relu_bwd_workspace_bytes(int64_t M, int K);
+int ns2_row_dot_relu_bwd(const float* dout, const float* out, const float* h, int64_t ldh, const float* w, int64_t M, int K, float* dh,
+                         int64_t lddh, float* dw_db, void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -159,6 +159,11 @@ SIGNATURES = {
     "ns2_silu_fwd": (I, [P, L, L, I, P, L, P]),
     "ns2_silu_bwd": (I, [P, L, P, L, L, I, P, L, P]),
     "ns2_embedding_bwd": (I, [P, L, I, P, L, I, I, P, P]),
+    # ---- training of the DurationPitchPredictor
+    "ns2_groupnorm_silu_bwd_workspace_bytes": (L, [I, I, I]),
+    "ns2_groupnorm_silu_bwd": (I, [P, L, P, I, I, I, I, P, P, F, P, L, P, P, P, L, P]),
+    "ns2_row_dot_relu_bwd_workspace_bytes": (L, [L, I]),
+    "ns2_row_dot_relu_bwd": (I, [P, P, P, L, P, L, I, P, L, P, P, L, P]),
 }
 
 NS2_UNAVAILABLE = 1          # include/ns2hip.h: "this fast path does not apply here" (not an error)

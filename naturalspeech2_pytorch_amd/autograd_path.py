@@ -144,6 +144,7 @@ def phoneme_encoder_autograd(enc, ids, mask=None):
 
 # ---- DurationPitchPredictor (NS2:344-527) and the length regulator of text-conditioned sampling (NS2:87-104, 164-175, 1449-1455)
 def _dp_trunk_autograd(tr, x, prompts, training):
+    # the trunk hands `dropout` to its Attention only; Block / ConvBlock keep their own default 0 (NS2:430-446): no dropout after the convolutions
     p = tr.dropout if training else 0.
     k = tr.kernel_size
     for convs, norm, attn in tr.layers:
@@ -152,11 +153,10 @@ def _dp_trunk_autograd(tr, x, prompts, training):
                 h = x.transpose(1, 2)
                 for b in blk.blocks:
                     h = F.conv1d(h, b.proj.weight, b.proj.bias, padding=k // 2)
-                    h = F.dropout(F.silu(F.group_norm(h, b.norm.num_groups, b.norm.weight, b.norm.bias, b.norm.eps)), p, training)
+                    h = F.silu(F.group_norm(h, b.norm.num_groups, b.norm.weight, b.norm.bias, b.norm.eps))
                 x = (h + x.transpose(1, 2)).transpose(1, 2)
             else:                                                     # ConvBlock (NS2:402-409)
-                h = F.silu(F.conv1d(x.transpose(1, 2), blk[1].weight, blk[1].bias, padding=k // 2))
-                x = F.dropout(h, p, training).transpose(1, 2)
+                x = F.silu(F.conv1d(x.transpose(1, 2), blk[1].weight, blk[1].bias, padding=k // 2)).transpose(1, 2)
         x = _attention(_rmsnorm(x, norm), attn, tr.heads, context=prompts, include_queries=True, dropout_p=p) + x
     head = tr.to_pred[0]
     return F.relu(F.linear(x, head.weight, head.bias)[..., 0])

@@ -352,3 +352,35 @@ extern "C" int ns2_embedding_bwd(const int64_t* ids, int64_t M, int pad_id, cons
   HIPRET(launch_embedding_bwd((const long long*)ids, (long)M, pad_id, dy, (long)lddy, rows, d, dw, (hipStream_t)stream));
   return NS2_OK;
 }
+
+// ---- training of the DurationPitchPredictor (kernels: duration_pitch.hip)
+extern "C" int64_t ns2_groupnorm_silu_bwd_workspace_bytes(int B, int n, int C) {
+  if (B <= 0 || n <= 0 || C <= 0) return 0;
+  return ((int64_t)B * gn_bwd_row_chunks(n) + B) * 2 * C * (int64_t)sizeof(float);
+}
+extern "C" int ns2_groupnorm_silu_bwd(const float* dy, int64_t lddy, const float* x, int B, int n, int C, int groups, const float* weight,
+                                      const float* bias, float eps, const void* stats, int64_t stats_bytes, float* dx, float* dweight_dbias,
+                                      void* workspace, int64_t workspace_bytes, void* stream) {
+  ARGCHK(dy && x && weight && bias && stats && dx && dweight_dbias && workspace, "ns2_groupnorm_silu_bwd: null pointer");
+  ARGCHK(B > 0 && n > 0 && groups > 0 && C > 0 && C % groups == 0 && (C / groups) % 4 == 0, "ns2_groupnorm_silu_bwd: C / groups must be a multiple of 4");
+  ARGCHK(stats_bytes >= ns2_groupnorm_workspace_bytes(B, n, C, groups), "ns2_groupnorm_silu_bwd: stats = the workspace ns2_groupnorm_silu filled (too small)");
+  ARGCHK(workspace_bytes >= ns2_groupnorm_silu_bwd_workspace_bytes(B, n, C), "ns2_groupnorm_silu_bwd: workspace too small");
+  ARGCHK(((uintptr_t)dy | (uintptr_t)x | (uintptr_t)weight | (uintptr_t)bias | (uintptr_t)stats | (uintptr_t)dx | (uintptr_t)workspace) % 16 == 0,
+         "ns2_groupnorm_silu_bwd: buffers must be 16-byte aligned");
+  float* slots = (float*)workspace;
+  float* colsum = slots + (int64_t)B * gn_bwd_row_chunks(n) * 2 * C;
+  HIPRET(launch_groupnorm_silu_bwd(dy, (long)lddy, x, B, n, C, groups, weight, bias, eps, stats, dx, dweight_dbias, slots, colsum, (hipStream_t)stream));
+  return NS2_OK;
+}
+extern "C" int64_t ns2_row_dot_relu_bwd_workspace_bytes(int64_t M, int K) {
+  if (M <= 0 || K <= 0) return 0;
+  return (int64_t)row_dot_bwd_chunks((long)M) * (K + 1) * (int64_t)sizeof(float);
+}
+extern "C" int ns2_row_dot_relu_bwd(const float* dout, const float* out, const float* h, int64_t ldh, const float* w, int64_t M, int K, float* dh,
+                                    int64_t lddh, float* dw_db, void* workspace, int64_t workspace_bytes, void* stream) {
+  ARGCHK(dout && out && h && w && dh && dw_db && workspace, "ns2_row_dot_relu_bwd: null pointer");
+  ARGCHK(workspace_bytes >= ns2_row_dot_relu_bwd_workspace_bytes(M, K), "ns2_row_dot_relu_bwd: workspace too small");
+  ARGCHK(((uintptr_t)h | (uintptr_t)w | (uintptr_t)dh) % 16 == 0, "ns2_row_dot_relu_bwd: h, w and dh must be 16-byte aligned");
+  HIPRET(launch_row_dot_relu_bwd(dout, out, h, (long)ldh, w, (long)M, K, dh, (long)lddh, dw_db, (float*)workspace, (hipStream_t)stream));
+  return NS2_OK;
+}

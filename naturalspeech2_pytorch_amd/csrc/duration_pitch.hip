@@ -5,7 +5,9 @@
 //     (Chan et al.) -- deterministic and bit-reproducible, no atomics;
 //   - the length regulator (generate_mask_from_repeats + f0_to_coarse + expand_encodings): a gather plus one fp32 add, which
 //     is what the reference's 0/1 mask einsum computes bit for bit;
-//   - the to_pred heads (Linear(dim, 1) + ReLU, NS2:467-471) as a row dot product.
+//   - the to_pred heads (Linear(dim, 1) + ReLU, NS2:467-471) as a row dot product;
+//   - for training the predictor (training/duration_pitch_pass.py): the backward of GroupNorm + SiLU, which recombines the forward's own
+//     statistics slots (bit-equal mean and rstd) and sums in fixed slots like the forward, and the backward of the heads.
 // The convolutions, RMSNorm and attention of the trunk are the existing GEMM / norm / attention kernels.
 #include <hip/hip_runtime.h>
 
@@ -89,19 +91,25 @@ __global__ __launch_bounds__(GN_THREADS) void gn_stats_kernel(const GnArgs a) {
   }
 }
 
+// (shift, shifted mean, rstd) of group g of utterance b from the statistics slots, combined in slot order.  The ONE place that does it:
+// the forward's apply pass and both passes of the backward call it, so the backward normalises with the forward's bits.
+NS2_DEVINL void gn_group_stats(const float4* part, const float* x, int b, int g, int groups, int nchunks, int n, int C, int cg, float eps,
+                               float& K, float& mean, float& rstd) {
+  const float4* p = part + ((long)b * groups + g) * nchunks;
+  Welford w{p[0].x, p[0].y, p[0].z};
+  for (int i = 1; i < nchunks; ++i) w = chan(w, Welford{p[i].x, p[i].y, p[i].z});
+  K = x[(long)b * n * C + (long)g * cg];
+  mean = w.mean;
+  rstd = 1.0f / sqrtf(w.m2 / w.n + eps);           // biased variance, as nn.GroupNorm
+}
+
 // grid (ceil(n / GN_APPLY_ROWS), B): y = silu((x - mean) * rstd * weight + bias) (+ resid), fp32 and / or operand planes
 __global__ __launch_bounds__(GN_THREADS) void gn_apply_kernel(const GnArgs a) {
   const int b = blockIdx.y, t = threadIdx.x;
   extern __shared__ float gs[];           // [groups] shift, [groups] shifted mean, [groups] rstd
   float* sK = gs; float* sM = gs + a.groups; float* sR = gs + 2 * a.groups;
-  for (int g = t; g < a.groups; g += GN_THREADS) {
-    const float4* p = a.part + ((long)b * a.groups + g) * a.nchunks;
-    Welford w{p[0].x, p[0].y, p[0].z};
-    for (int i = 1; i < a.nchunks; ++i) w = chan(w, Welford{p[i].x, p[i].y, p[i].z});
-    sK[g] = a.x[(long)b * a.n * a.C + (long)g * a.cg];
-    sM[g] = w.mean;
-    sR[g] = 1.0f / sqrtf(w.m2 / w.n + a.eps);      // biased variance, as nn.GroupNorm
-  }
+  for (int g = t; g < a.groups; g += GN_THREADS)
+    gn_group_stats(a.part, a.x, b, g, a.groups, a.nchunks, a.n, a.C, a.cg, a.eps, sK[g], sM[g], sR[g]);
   __syncthreads();
   const int r0 = blockIdx.x * GN_APPLY_ROWS;
   const int q = a.C >> 2;                          // float4 columns per row
@@ -125,6 +133,165 @@ __global__ __launch_bounds__(GN_THREADS) void gn_apply_kernel(const GnArgs a) {
     }
     if (a.out_f) *reinterpret_cast<float4*>(a.out_f + row * a.C + c) = make_float4(o[0], o[1], o[2], o[3]);
     if (a.out_hi) store_cols4(a.out_hi + row * pld(a.ldo, il), c, o[0], o[1], o[2], o[3], a.fmt, il);
+  }
+}
+
+// ---------------------------------------------------------------- GroupNorm + SiLU backward (training the predictor)
+// With xh = (x - mean) rstd, z = xh w + b, dz = dy silu'(z):   dbias_c = sum dz,  dweight_c = sum dz xh  (over utterances and rows),
+// dxh = dz w,  s1 = sum dxh,  s2 = sum dxh xh  (per utterance and group, N = n cg values),  dx = rstd (dxh - s1 / N - xh s2 / N).
+// s1 and s2 are the group's sums of w_c times the utterance's column sums of dz and dz xh, so ONE set of per-column partial sums serves the
+// parameter gradients and the group sums.  Two passes like the forward: gn_bwd_cols_kernel writes the column sums of a chunk of rows to
+// the chunk's own slot; ns2_reduce_slices' kernel adds the slots of an utterance, then the utterances, in a fixed order;
+// gn_bwd_apply_kernel forms s1 / N, s2 / N per group (ascending columns) and dx.  No atomics: bit-reproducible.
+// Both kernels stream float4s with a row's columns on consecutive lanes.
+constexpr int COLS_THREADS = 256;
+constexpr int GNB_ROWS = 32;              // rows per column-sum slot
+constexpr int RDB_ROWS = 64;              // ... of the head backward
+
+// The threads of a workgroup cover `qt` <= 256 float4 columns; COLS_THREADS / qt rows are in flight at once (row subgroup rsub).  Fold
+// the NV accumulators of the row subgroups into subgroup 0 in subgroup order.
+template <int NV>
+NS2_DEVINL void fold_row_subgroups(float (&acc)[NV], float* lds, int rsub, int rows_par, int t, int qt, bool active) {
+#pragma unroll
+  for (int e = 0; e < NV; ++e)
+    if (active) lds[e * COLS_THREADS + t] = acc[e];
+  __syncthreads();
+  if (active && rsub == 0)
+    for (int j = 1; j < rows_par; ++j)
+#pragma unroll
+      for (int e = 0; e < NV; ++e) acc[e] += lds[e * COLS_THREADS + j * qt + t];
+}
+
+struct GnBwdArgs {
+  const float* x; const float* dy; long lddy; const float* weight; const float* bias; const float4* part;
+  float* slots;            // [B * rchunks][2][C]: column sums of dz xh | dz over the chunk's rows
+  const float* colsum;     // [B][2][C]: the slots of an utterance added up
+  float* dx;
+  int B, n, C, groups, cg, nchunks, rchunks; float eps;
+};
+
+NS2_DEVINL float silu_grad(float z) {
+  const float sg = 1.0f / (1.0f + expf(-z));
+  return sg * (1.0f + z * (1.0f - sg));
+}
+
+// grid (ceil(C / 1024), rchunks, B); dynamic LDS: 3 * groups floats
+__global__ __launch_bounds__(COLS_THREADS) void gn_bwd_cols_kernel(const GnBwdArgs a) {
+  const int tile = blockIdx.x, rc = blockIdx.y, b = blockIdx.z, t = threadIdx.x;
+  extern __shared__ float gs[];
+  __shared__ float fold[8 * COLS_THREADS];
+  float* sK = gs; float* sM = gs + a.groups; float* sR = gs + 2 * a.groups;
+  for (int g = t; g < a.groups; g += COLS_THREADS)
+    gn_group_stats(a.part, a.x, b, g, a.groups, a.nchunks, a.n, a.C, a.cg, a.eps, sK[g], sM[g], sR[g]);
+  __syncthreads();
+  const int qt = min(COLS_THREADS, (a.C >> 2) - tile * COLS_THREADS);
+  const int rows_par = COLS_THREADS / qt;
+  const int rsub = t / qt, cq = t - rsub * qt;
+  const bool active = rsub < rows_par;
+  const int c = (tile * COLS_THREADS + cq) * 4;
+  float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  if (active) {
+    const int g = c / a.cg;
+    const float K = sK[g], m = sM[g], rs = sR[g];
+    const float4 wv = *reinterpret_cast<const float4*>(a.weight + c);
+    const float4 bv = *reinterpret_cast<const float4*>(a.bias + c);
+    const float w[4] = {wv.x, wv.y, wv.z, wv.w}, bi[4] = {bv.x, bv.y, bv.z, bv.w};
+    const int r1 = min(a.n, (rc + 1) * GNB_ROWS);
+    for (int r = rc * GNB_ROWS + rsub; r < r1; r += rows_par) {
+      const long row = (long)b * a.n + r;
+      const float4 xv = *reinterpret_cast<const float4*>(a.x + row * a.C + c);
+      const float4 gv = *reinterpret_cast<const float4*>(a.dy + row * a.lddy + c);
+      const float x[4] = {xv.x, xv.y, xv.z, xv.w}, dy[4] = {gv.x, gv.y, gv.z, gv.w};
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float xh = ((x[e] - K) - m) * rs;
+        const float dz = dy[e] * silu_grad(xh * w[e] + bi[e]);
+        acc[e] += dz * xh;
+        acc[4 + e] += dz;
+      }
+    }
+  }
+  fold_row_subgroups<8>(acc, fold, rsub, rows_par, t, qt, active);
+  if (active && rsub == 0) {
+    float* slot = a.slots + ((long)b * a.rchunks + rc) * 2 * a.C;
+    *reinterpret_cast<float4*>(slot + c) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+    *reinterpret_cast<float4*>(slot + a.C + c) = make_float4(acc[4], acc[5], acc[6], acc[7]);
+  }
+}
+
+// grid (ceil(n / GN_APPLY_ROWS), B); dynamic LDS: 5 * groups floats
+__global__ __launch_bounds__(GN_THREADS) void gn_bwd_apply_kernel(const GnBwdArgs a) {
+  const int b = blockIdx.y, t = threadIdx.x;
+  extern __shared__ float gs[];
+  float* sK = gs; float* sM = gs + a.groups; float* sR = gs + 2 * a.groups; float* s1 = gs + 3 * a.groups; float* s2 = gs + 4 * a.groups;
+  const float inv_n = 1.0f / ((float)a.n * (float)a.cg);
+  for (int g = t; g < a.groups; g += GN_THREADS) {
+    gn_group_stats(a.part, a.x, b, g, a.groups, a.nchunks, a.n, a.C, a.cg, a.eps, sK[g], sM[g], sR[g]);
+    const float* cs = a.colsum + (long)b * 2 * a.C;
+    float u = 0.f, v = 0.f;
+    for (int c = g * a.cg; c < (g + 1) * a.cg; ++c) {        // a group has a few dozen columns: ascending order, one thread
+      u += a.weight[c] * cs[a.C + c];
+      v += a.weight[c] * cs[c];
+    }
+    s1[g] = u * inv_n;
+    s2[g] = v * inv_n;
+  }
+  __syncthreads();
+  const int r0 = blockIdx.x * GN_APPLY_ROWS;
+  const int q = a.C >> 2;
+  for (int it = t; it < GN_APPLY_ROWS * q; it += GN_THREADS) {
+    const int r = r0 + it / q, c = (it % q) * 4;
+    if (r >= a.n) break;
+    const long row = (long)b * a.n + r;
+    const int g = c / a.cg;
+    const float4 xv = *reinterpret_cast<const float4*>(a.x + row * a.C + c);
+    const float4 gv = *reinterpret_cast<const float4*>(a.dy + row * a.lddy + c);
+    const float4 wv = *reinterpret_cast<const float4*>(a.weight + c);
+    const float4 bv = *reinterpret_cast<const float4*>(a.bias + c);
+    const float x[4] = {xv.x, xv.y, xv.z, xv.w}, dy[4] = {gv.x, gv.y, gv.z, gv.w};
+    const float w[4] = {wv.x, wv.y, wv.z, wv.w}, bi[4] = {bv.x, bv.y, bv.z, bv.w};
+    const float K = sK[g], m = sM[g], rs = sR[g], u = s1[g], v = s2[g];
+    float o[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float xh = ((x[e] - K) - m) * rs;
+      const float dxh = dy[e] * silu_grad(xh * w[e] + bi[e]) * w[e];
+      o[e] = rs * (dxh - u - xh * v);
+    }
+    *reinterpret_cast<float4*>(a.dx + row * a.C + c) = make_float4(o[0], o[1], o[2], o[3]);
+  }
+}
+
+// ---------------------------------------------------------------- to_pred heads, backward: out = relu(h . w + b)
+// g = dout where out > 0 (the same rows as pre > 0), else 0;  dh[m, :] = g[m] w;  dw = sum_m g[m] h[m, :];  db = sum_m g[m].
+// grid (ceil(K / 1024), ceil(M / RDB_ROWS)): slot [chunk][K + 1] = the chunk's dw | db; the slots are added in order by ns2_reduce_slices' kernel.
+__global__ __launch_bounds__(COLS_THREADS) void row_dot_bwd_kernel(const float* dout, const float* out, const float* h, long ldh,
+                                                                    const float* w, int M, int K, float* dh, long lddh, float* slots) {
+  const int tile = blockIdx.x, chunk = blockIdx.y, t = threadIdx.x;
+  __shared__ float fold[5 * COLS_THREADS];
+  const int qt = min(COLS_THREADS, (K >> 2) - tile * COLS_THREADS);
+  const int rows_par = COLS_THREADS / qt;
+  const int rsub = t / qt, cq = t - rsub * qt;
+  const bool active = rsub < rows_par;
+  const int c = (tile * COLS_THREADS + cq) * 4;
+  float acc[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+  if (active) {
+    const float4 wv = *reinterpret_cast<const float4*>(w + c);
+    const int m1 = min(M, (chunk + 1) * RDB_ROWS);
+    for (int m = chunk * RDB_ROWS + rsub; m < m1; m += rows_par) {
+      const float g = out[m] > 0.f ? dout[m] : 0.f;
+      const float4 hv = *reinterpret_cast<const float4*>(h + (long)m * ldh + c);
+      *reinterpret_cast<float4*>(dh + (long)m * lddh + c) = make_float4(g * wv.x, g * wv.y, g * wv.z, g * wv.w);
+      acc[0] += g * hv.x; acc[1] += g * hv.y; acc[2] += g * hv.z; acc[3] += g * hv.w;
+      acc[4] += g;
+    }
+  }
+  fold_row_subgroups<5>(acc, fold, rsub, rows_par, t, qt, active);
+  if (active && rsub == 0) {
+    float* slot = slots + (long)chunk * (K + 1);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) slot[c + e] = acc[e];
+    if (c == 0) slot[K] = acc[4];
   }
 }
 
@@ -237,6 +404,49 @@ __global__ __launch_bounds__(256) void row_dot_kernel(const float* x, int ldx, i
     if (bias) s += bias[0];
     out[row] = relu ? fmaxf(s, 0.f) : s;
   }
+}
+
+// ---- launchers of the training kernels (C entries: capi_train.cpp)
+int gn_bwd_row_chunks(int n) { return (n + GNB_ROWS - 1) / GNB_ROWS; }
+int row_dot_bwd_chunks(long M) { return (int)((M + RDB_ROWS - 1) / RDB_ROWS); }
+
+// stats = the workspace the forward (ns2_groupnorm_silu) left; slots [B * gn_bwd_row_chunks(n)][2 C]; colsum [B][2 C]; dwb [2 C] = dweight | dbias
+hipError_t launch_groupnorm_silu_bwd(const float* dy, long lddy, const float* x, int B, int n, int C, int groups, const float* weight,
+                                     const float* bias, float eps, const void* stats, float* dx, float* dwb, float* slots, float* colsum,
+                                     hipStream_t s) {
+  if (B <= 0 || n <= 0 || groups <= 0 || groups > 1024 || C <= 0 || C % groups || (C / groups) % 4 || C / groups > GN_CHUNK || lddy < C ||
+      (lddy & 3) || B > 65535)
+    return hipErrorInvalidValue;
+  GnBwdArgs a;
+  a.x = x; a.dy = dy; a.lddy = lddy; a.weight = weight; a.bias = bias; a.part = reinterpret_cast<const float4*>(stats);
+  a.slots = slots; a.colsum = colsum; a.dx = dx;
+  a.B = B; a.n = n; a.C = C; a.groups = groups; a.cg = C / groups; a.nchunks = gn_chunks(n, a.cg); a.rchunks = gn_bwd_row_chunks(n);
+  a.eps = eps;
+  const int q = C >> 2;
+  hipLaunchKernelGGL(gn_bwd_cols_kernel, dim3((q + COLS_THREADS - 1) / COLS_THREADS, a.rchunks, B), dim3(COLS_THREADS),
+                     3 * groups * sizeof(float), s, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  e = launch_reduce_slices(slots, B, a.rchunks, 2L * C, colsum, 0, s);          // per utterance: what the group sums need
+  if (e != hipSuccess) return e;
+  e = launch_reduce_slices(colsum, 1, B, 2L * C, dwb, 0, s);                    // over the utterances: dweight | dbias
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(gn_bwd_apply_kernel, dim3((n + GN_APPLY_ROWS - 1) / GN_APPLY_ROWS, B), dim3(GN_THREADS), 5 * groups * sizeof(float), s, a);
+  return hipGetLastError();
+}
+
+// slots [row_dot_bwd_chunks(M)][K + 1]; dwb [K + 1] = dw | db
+hipError_t launch_row_dot_relu_bwd(const float* dout, const float* out, const float* h, long ldh, const float* w, long M, int K, float* dh,
+                                   long lddh, float* dwb, float* slots, hipStream_t s) {
+  if (M <= 0 || M > 0x7fffffffL - RDB_ROWS || K <= 0 || (K & 3) || ldh < K || (ldh & 3) || lddh < K || (lddh & 3)) return hipErrorInvalidValue;
+  const int chunks = row_dot_bwd_chunks(M);
+  if (chunks > 65535) return hipErrorInvalidValue;
+  const int q = K >> 2;
+  hipLaunchKernelGGL(row_dot_bwd_kernel, dim3((q + COLS_THREADS - 1) / COLS_THREADS, chunks), dim3(COLS_THREADS), 0, s, dout, out, h, ldh, w,
+                     (int)M, K, dh, lddh, slots);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  return launch_reduce_slices(slots, 1, chunks, (long)K + 1, dwb, 0, s);
 }
 
 }  // namespace ns2

@@ -269,6 +269,14 @@ struct TPlanesArgs {
 hipError_t launch_tplanes(const TPlanesArgs& a, hipStream_t s);
 long tplanes_slices(int M, long ld_t);             // number of 64-row tiles (= colsum slots) of a non-per_batch launch
 hipError_t launch_reduce_slices(const float* partial, long outer, int S, long inner, float* out, int accumulate, hipStream_t s);
+// training the DurationPitchPredictor (duration_pitch.hip): backward of GroupNorm + SiLU from the forward's statistics slots, of the heads
+int gn_bwd_row_chunks(int n);
+int row_dot_bwd_chunks(long M);
+hipError_t launch_groupnorm_silu_bwd(const float* dy, long lddy, const float* x, int B, int n, int C, int groups, const float* weight,
+                                     const float* bias, float eps, const void* stats, float* dx, float* dwb, float* slots, float* colsum,
+                                     hipStream_t s);
+hipError_t launch_row_dot_relu_bwd(const float* dout, const float* out, const float* h, long ldh, const float* w, long M, int K, float* dh,
+                                   long lddh, float* dwb, float* slots, hipStream_t s);
 hipError_t launch_wgrad_reduce(const float* partial, int S, int R, long ldp, int T, int Kp, int K, float* out, hipStream_t s);
 hipError_t launch_film_gate_fwd(const float* h, long ldh, const float* film, int film_ld, int seq_len, long M, int d, float* out,
                                 long ldo, hipStream_t s);

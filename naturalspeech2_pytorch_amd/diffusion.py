@@ -85,7 +85,8 @@ class NaturalSpeech2(nn.Module):
                  encoder_precision="exact",            # not in the reference: precision mode of the HIP encoders (and predictor)
                  build_duration_pitch: bool = False,   # not in the reference: build the DurationPitchPredictor (sample(text=...))
                  build_aligner: bool = False,          # not in the reference: build the Aligner (forward(text=..., mel=..., pitch=...))
-                 encoder_train_backend="composite"):   # not in the reference: "hip" trains phoneme_enc / prompt_enc on the HIP kernels (training/encoder_pass.py)
+                 encoder_train_backend="composite",    # not in the reference: "hip" trains phoneme_enc / prompt_enc on the HIP kernels (training/encoder_pass.py)
+                 duration_pitch_train_backend="composite"):   # not in the reference: "hip" trains the DurationPitchPredictor on them (training/duration_pitch_pass.py)
         super().__init__()
         assert _is_denoiser(model), "model must be a Model (this package's, or compat.HipBackedModel over the reference's class)"
         self.conditional = model.condition_on_prompt
@@ -111,7 +112,8 @@ class NaturalSpeech2(nn.Module):
             self.aligner_bin_loss_weight = aligner_bin_loss_weight
             if build_duration_pitch:                                                  # NS2:1234
                 from .duration_pitch import DurationPitchPredictor
-                self.duration_pitch = DurationPitchPredictor(dim=duration_pitch_dim, precision=encoder_precision)
+                self.duration_pitch = DurationPitchPredictor(dim=duration_pitch_dim, precision=encoder_precision,
+                                                             train_backend=duration_pitch_train_backend)
             if build_aligner:                                                         # NS2:1235, 1238-1239
                 from .aligner import Aligner, BinLoss, ForwardSumLoss
                 self.aligner = Aligner(dim_in=aligner_dim_in, dim_hidden=aligner_dim_hidden, attn_channels=aligner_attn_channels,

@@ -6,7 +6,9 @@ keys / values are cat(norm(x), encoded prompts) (cross_attn_include_queries) -> 
 HIP path the "same"-padded convolutions are the shifted-row GEMMs (conv_taps = k, pad_left = k // 2), a `ConvBlock` takes its
 SiLU in the GEMM epilogue, a `ResnetBlock`'s GroupNorm + SiLU (+ residual) is csrc/duration_pitch.hip, RMSNorm / attention are
 the hot path's kernels and the heads are a row dot product.  Under autograd (or on the CPU) the differentiable composite of
-autograd_path.py runs instead.  Same constructor keywords and state_dict keys as the reference classes.
+autograd_path.py runs instead (`train_backend="composite"`, the default), or with `train_backend="hip"` on the GPU
+`training.duration_pitch_forward_train`: forward and backward on the HIP kernels.  Same constructor keywords and state_dict keys as
+the reference classes.
 """
 import torch
 from torch import nn
@@ -14,7 +16,7 @@ from torch import nn
 from . import ops
 from ._cache import PackedCache
 from .model import _Attention, _NoParams, _RMSNorm, _PRECISIONS
-from .transformer import needs_autograd
+from .transformer import TRAIN_BACKENDS, needs_autograd
 
 
 class _Block(nn.Module):                        # Block (NS2:346-369): Conv1d -> GroupNorm -> SiLU -> Dropout
@@ -53,8 +55,11 @@ class DurationPitchPredictorTrunk(nn.Module):   # NS2:411-481
 class DurationPitchPredictor(nn.Module):
     def __init__(self, *, dim, num_phoneme_tokens=None, tokenizer=None, dim_encoded_prompts=None, num_convolutions_per_block=3,
                  use_resnet_block=True, num_convs_per_resnet_block=2, depth=10, kernel_size=3, heads=8, dim_head=64,
-                 dim_hidden=512, dropout=0.2, use_flash_attn=False, precision="exact"):
+                 dim_hidden=512, dropout=0.2, use_flash_attn=False, precision="exact", train_backend="composite"):
         super().__init__()
+        assert train_backend in TRAIN_BACKENDS, f"train_backend must be one of {TRAIN_BACKENDS}"
+        self.train_backend = train_backend
+        self.dropout_seed = None                # train_backend="hip": an int64 tensor [1] replaces the per-pass draw of the attention dropout seed
         if kernel_size % 2 == 0:
             raise ValueError(f"kernel_size must be odd: Conv1d(padding=k // 2) with an even k ({kernel_size}) changes the length")
         if dim_hidden % 32 != 0:
@@ -86,6 +91,10 @@ class DurationPitchPredictor(nn.Module):
             raise NotImplementedError("prompt_mask is not supported: the reference's Attend applies it to keys = cat(queries, "
                                       "prompts), which a [b, n_p] mask does not cover (NS2:1060-1066)")
         if needs_autograd(self, x if x.is_floating_point() else None) or not x.is_cuda:
+            if self.train_backend == "hip" and x.is_cuda:          # (on the GPU this branch is entered under autograd only)
+                from . import training
+                if training.available(x.device) and training.duration_pitch_unsupported_reason(self) is None:
+                    return training.duration_pitch_forward_train(self, x, encoded_prompts)
             from .autograd_path import duration_pitch_autograd
             return duration_pitch_autograd(self, x, encoded_prompts)
         return self._forward_hip(x, encoded_prompts)

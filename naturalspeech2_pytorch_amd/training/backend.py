@@ -140,6 +140,46 @@ class HipBackend:
               "ns2_embedding_bwd")
         return dw
 
+    # ---- DurationPitchPredictor: GroupNorm + SiLU (+ residual) of a ResnetBlock, the Linear(dim, 1) + ReLU heads
+    def groupnorm_silu_fwd(self, x, B, n, weight, bias, groups, eps, resid=None):
+        """x fp32 [B n, >= C] -> (y [B n, C] fp32, the rows [B n, C] the kernel read, stats): `stats` holds the per-chunk statistics slots
+        of ns2_groupnorm_silu, which `groupnorm_silu_bwd` recombines (the same mean and rstd, bit for bit)"""
+        C = weight.shape[0]
+        x = self._rows(x[:, :C], C)
+        if resid is not None:
+            resid = self._rows(resid[:, :C], C)
+        y = torch.empty(B * n, C, dtype=torch.float32, device=x.device)
+        stats = torch.empty(self.lib.ns2_groupnorm_workspace_bytes(B, n, C, groups), dtype=torch.uint8, device=x.device)
+        check(self.lib.ns2_groupnorm_silu(x.data_ptr(), B, n, C, groups, weight.data_ptr(), bias.data_ptr(), float(eps), _p(resid), y.data_ptr(), None, None,
+                                          0, 3, stats.data_ptr(), stats.numel(), _stream()), "ns2_groupnorm_silu")
+        return y, x, stats
+
+    def groupnorm_silu_bwd(self, dy, x, stats, B, n, weight, bias, groups, eps):
+        """-> (dx [B n, C], dweight [C], dbias [C]); x, stats: what `groupnorm_silu_fwd` returned"""
+        C = weight.shape[0]
+        dx = torch.empty(B * n, C, dtype=torch.float32, device=x.device)
+        dwb = torch.empty(2 * C, dtype=torch.float32, device=x.device)
+        ws = torch.empty(self.lib.ns2_groupnorm_silu_bwd_workspace_bytes(B, n, C), dtype=torch.uint8, device=x.device)
+        check(self.lib.ns2_groupnorm_silu_bwd(dy.data_ptr(), dy.stride(0), x.data_ptr(), B, n, C, groups, weight.data_ptr(), bias.data_ptr(), float(eps),
+                                              stats.data_ptr(), stats.numel(), dx.data_ptr(), dwb.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+              "ns2_groupnorm_silu_bwd")
+        return dx, dwb[:C], dwb[C:]
+
+    def row_dot_relu(self, h, w, b):
+        """relu(h[:, :K] . w + b) -> [M]"""
+        return ops.row_dot(h, w, b, relu=True)
+
+    def row_dot_relu_bwd(self, dout, out, h, w):
+        """-> (dh [M, K], dw [K], db [1]) of out = relu(h . w + b)"""
+        M, K = h.shape[0], w.numel()
+        dout = dout if dout.is_contiguous() else dout.contiguous()
+        dh = torch.empty(M, K, dtype=torch.float32, device=h.device)
+        dwb = torch.empty(K + 1, dtype=torch.float32, device=h.device)
+        ws = torch.empty(self.lib.ns2_row_dot_relu_bwd_workspace_bytes(M, K), dtype=torch.uint8, device=h.device)
+        check(self.lib.ns2_row_dot_relu_bwd(dout.data_ptr(), out.data_ptr(), h.data_ptr(), h.stride(0), w.data_ptr(), M, K, dh.data_ptr(), K,
+                                            dwb.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "ns2_row_dot_relu_bwd")
+        return dh, dwb[:K], dwb[K:]
+
     # ---- rows = batch entries: the conditioning Linears (weight-streaming kernel of the inference path, fp32)
     def skinny(self, x, wt, bias=None):
         """x [R, K] @ wt [K, J] (+ bias) in fp32 (ns2_skinny_linear: deterministic split-K)"""

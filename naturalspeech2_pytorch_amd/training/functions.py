@@ -176,10 +176,14 @@ class AttnFn(torch.autograd.Function):
     context gradient that belongs to the latents reaches them through torch's cat).
     The plain `Transformer` of the conditioning encoders (NS2:1073-1115) adds three things, all absent by default (same kernels, same
     bits as before): `gamma` -- the learned-gamma RMSNorm in front (with `film = None`); `kmask` -- key-padding mask, uint8 [B, Nk],
-    1 = attend (ATT:92-94); `drop` = (p, seed tensor, call index) -- dropout on the softmax output (ATT:100-101; csrc/dropout_keep.h)."""
+    1 = attend (ATT:92-94); `drop` = (p, seed tensor, call index) -- dropout on the softmax output (ATT:100-101; csrc/dropout_keep.h).
+    The DurationPitchPredictor's attention (NS2:464, 1060-1061) reads an `h` that IS the norm's output (it is also part of the context, so
+    the caller forms it) and adds the PRE-norm rows: `resid` [M, d] replaces `h` as the residual (with `film = gamma = None`); `h` then gets
+    the q path's gradient only and `resid` the incoming one.  Absent by default, like the others."""
 
     @staticmethod
-    def forward(ctx, h, film, ctxt, wq, wkv, wout, seq_len, heads, ctx_len, gamma=None, kmask=None, drop=None):
+    def forward(ctx, h, film, ctxt, wq, wkv, wout, seq_len, heads, ctx_len, gamma=None, kmask=None, drop=None, resid=None):
+        assert resid is None or (film is None and gamma is None)
         bk = _begin(ctx)
         M, d = h.shape
         B, a = M // seq_len, heads * 64
@@ -199,9 +203,10 @@ class AttnFn(torch.autograd.Function):
             o, lse = bk.attention(q, qc, k, kc, vt, B, heads, seq_len, Nk)
         else:
             o, lse = bk.attention_masked(q, qc, k, kc, vt, B, heads, seq_len, Nk, kmask=kmask, drop=drop)
-        y = bk.gemm_f32(_fwd_pack(bk, wout), o, resid=h)
+        y = bk.gemm_f32(_fwd_pack(bk, wout), o, resid=h if resid is None else resid)
         ctx.save_for_backward(h, film, wq, wkv, wout, lse, gamma)
         ctx.pl, ctx.cfg, ctx.md = (xn, q, k, v, o, cp), (seq_len, heads, Nk, qc, kc, vc, ctxt is not None), (kmask, drop)
+        ctx.own_resid = resid is None
         return y[:, :d]
 
     @staticmethod
@@ -251,9 +256,13 @@ class AttnFn(torch.autograd.Function):
             dxn = bk.gemm_f32(_bwd_pack(bk, wq), q_row)
             kv_row, dwkv, _ = _grads(bk, dkv, 2 * a, cp, d, need_row=ng[2], need_w=ng[4])
             dctx = bk.gemm_f32(_bwd_pack(bk, wkv), kv_row)[:, :d] if ng[2] else None
-        dh, dfilm, dgamma = _norm_in_front_bwd(bk, h, dxn, dy, B, seq_len, film, gamma)
+        if ctx.own_resid:
+            dh, dfilm, dgamma = _norm_in_front_bwd(bk, h, dxn, dy, B, seq_len, film, gamma)
+            dresid = None
+        else:
+            dh, dfilm, dgamma, dresid = dxn[:, :d], None, None, dy
         dfilm, dwq, dwkv, dwout, dgamma = _un(ctx, dfilm, dwq, dwkv, dwout, dgamma)
-        return dh, dfilm, dctx, dwq, dwkv, dwout, None, None, None, dgamma, None, None
+        return dh, dfilm, dctx, dwq, dwkv, dwout, None, None, None, dgamma, None, None, dresid
 
 
 class FeedForwardFn(torch.autograd.Function):
@@ -366,6 +375,46 @@ class SiluFn(torch.autograd.Function):
         pre, = ctx.saved_tensors
         dy = _rowmajor(dy)
         return ctx.bk.silu_bwd(dy, pre, pre.shape[1])[:, :pre.shape[1]]
+
+
+class GroupNormSiluFn(torch.autograd.Function):
+    """silu(GroupNorm(x)) (+ resid) over the rows of utterances of `seq_len` tokens: a Block of the DurationPitchPredictor's ResnetBlock, the
+    last one with the ResnetBlock's input as `resid` (NS2:346-400).  The backward normalises with the forward's own statistics slots."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, resid, seq_len, groups, eps):
+        bk = _begin(ctx)
+        B = x.shape[0] // seq_len
+        y, rows, stats = bk.groupnorm_silu_fwd(x, B, seq_len, weight.detach(), bias.detach(), groups, eps, resid=resid)
+        ctx.save_for_backward(rows, weight, bias, stats)
+        ctx.cfg = (B, seq_len, groups, eps, resid is not None)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        rows, weight, bias, stats = ctx.saved_tensors
+        B, seq_len, groups, eps, has_resid = ctx.cfg
+        dy = _rowmajor(dy)
+        dx, dw, db = ctx.bk.groupnorm_silu_bwd(dy, rows, stats, B, seq_len, weight.detach(), bias.detach(), groups, eps)
+        return dx, *_un(ctx, dw, db), (dy if has_resid else None), None, None, None
+
+
+class RowDotReluFn(torch.autograd.Function):
+    """relu(Linear(dim, 1)(h)) -> [M]: a `to_pred` head of the DurationPitchPredictor (NS2:451-455); w [1, dim], b [1]"""
+
+    @staticmethod
+    def forward(ctx, h, w, b):
+        bk = _begin(ctx)
+        out = bk.row_dot_relu(h, w.detach().reshape(-1), b.detach())
+        ctx.save_for_backward(h, w, out)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        h, w, out = ctx.saved_tensors
+        dh, dw, db = ctx.bk.row_dot_relu_bwd(dout, out, h, w.detach().reshape(-1))
+        dw, db = _un(ctx, dw, db)
+        return dh, dw.reshape(w.shape), db
 
 
 class EmbeddingFn(torch.autograd.Function):
