@@ -55,6 +55,13 @@ int ns2_version(void);
  * wavenet3_kernel.h), 5 = dispatch by shape but never split K, and those kernels whenever a call is eligible, whatever its size).
  * 1 and 2 never split K either. */
 int ns2_debug_force_gemm(int kernel);
+/* test hook: the self-attention forward's kernel choice (0 = by eligibility, 1 = attn_kernel for every call, never the two-block
+ * kernel of attn_fast_kernel.h: its reference and A/B partner).  Process-wide like the hook above; NS2_ATTN in the environment sets
+ * the initial value.  Not to be flipped while a graph is being captured. */
+int ns2_debug_force_attention(int kernel);
+/* test hook: how many attention launches of this process took the two-block kernel so far (every other one took attn_kernel).
+ * A test reads it before and after a call to see which kernel the call was routed to. */
+int64_t ns2_debug_attention_fast_launches(void);
 /* Split-K of small products.  ns2_model_forward* lend a region of their workspace to every GEMM of the pass: a product with too
  * few output tiles to fill the chip runs as K slices into fixed slots plus a second launch that adds the slots in order and
  * applies the epilogue (deterministic).  The stand-alone GEMM entry points below have no workspace argument and never split --

@@ -16,9 +16,20 @@
 //   * O^T = V^T P^T accumulates with query = lane & 31 again, so the running rescale is a per-lane scalar;
 //   * V arrives already transposed ([b][h*64+d][n]) from the QKV GEMM epilogue (gemm.hip EPI_QKV).
 // NSPLIT = 3 evaluates both products as hi*hi + hi*lo + lo*hi (fp32-class accuracy), NSPLIT = 1 hi only.
+//
+// Two kernels live in this translation unit (one range-guard counter, ns2_common.h):
+//   * attn_kernel<NSPLIT, F16, NW, WLSE, D, DROP> below: every case -- all precisions, head dimensions 32 / 64 / 128, ragged and masked
+//     keys, the training forward with its log-sum-exp and dropout;
+//   * attn_fast_kernel<PF> (attn_fast_kernel.h): the inference self-attention of the one-half-product plans (precisions 2 / 4, D = 64,
+//     whole 64-key tiles, whole 256-row workgroups, no mask): a wave owns two query blocks, so every K / V^T fragment read from LDS and every staged tile
+//     serves twice the query rows, and O leaves through LDS as 16-byte stores.  Same arithmetic in the same order: bit-identical to
+//     attn_kernel<1, true, 4, false, 64>, which stays its reference and A/B partner behind ns2_debug_force_attention(1) / NS2_ATTN=1.
+// launch_attention routes: attn_fast_eligible() is the whole test.
 #include "ns2_common.h"
 #include "ns2_kernels.h"
 #include "dropout_keep.h"
+
+#include <cstdlib>
 
 namespace ns2 {
 
@@ -290,6 +301,12 @@ __global__ __launch_bounds__(64 * NW, ((NSPLIT == 3 && D == 128) ? 1 : (NSPLIT =
   }
 }
 
+}  // namespace ns2
+
+#include "attn_fast_kernel.h"
+
+namespace ns2 {
+
 template <int NSPLIT, bool F16, int NW, bool WLSE, int D = 64, bool DROP = false>
 static hipError_t launch_attn_w(const AttnArgs& a, hipStream_t s) {
   const size_t lds = 2 * (NSPLIT == 3 ? 2 : 1) * (AtGeom<D>::KPLANE + AtGeom<D>::VPLANE);
@@ -317,6 +334,48 @@ static hipError_t launch_attn_t(const AttnArgs& a, hipStream_t s) {
   return launch_attn_w<NSPLIT, F16, 4, false>(a, s);
 }
 
+// Test hook (ns2_debug_force_attention / NS2_ATTN), in the manner of gemm2.hip's gemm_hook(): process-wide by design, atomic so that
+// two host threads may read it while a test flips it.  -1: read NS2_ATTN once.  0: by eligibility, 1: attn_kernel for every call
+// (the reference and A/B partner of attn_fast_kernel); NS2_ATTN is stored as read, and every value but 1 behaves as 0.
+static std::atomic<int> g_forced_attention{-1};
+void force_attention_kernel(int k) { g_forced_attention.store(k, std::memory_order_relaxed); }
+static bool attn_fast_allowed() {
+  int f = g_forced_attention.load(std::memory_order_relaxed);
+  if (f < 0) {
+    const char* e = getenv("NS2_ATTN");
+    f = e ? atoi(e) : 0;
+    g_forced_attention.store(f, std::memory_order_relaxed);
+  }
+  return f != 1;
+}
+
+// Does attn_fast_kernel (attn_fast_kernel.h) take this call?  One IEEE-half product (the caller is launch_attn_t<1, true>: no lo
+// planes), head dimension 64, nothing but the plain forward (no log-sum-exp, dropout or key mask), whole 64-key tiles and whole
+// 256-row workgroups, an IEEE-half output format whose rows take 16-byte stores.  Everything else keeps attn_kernel.
+static bool attn_fast_eligible(const AttnArgs& a) {
+  if (!attn_fast_allowed()) return false;
+  if ((a.D != 0 && a.D != 64) || a.lse || a.drop_seed || a.kmask) return false;
+  if (a.q_lo || a.k_lo || a.vt_lo) return false;
+  if ((a.Nk & 63) || (a.Nq % AF_QB)) return false;
+  if (a.o_fmt != FMT_F16 && a.o_fmt != FMT_H8) return false;
+  return (a.ldo & 7) == 0 && (reinterpret_cast<uintptr_t>(a.o_hi) & 15) == 0;
+}
+// Launches that took attn_fast_kernel (ns2_debug_attention_fast_launches): the routing tests read it around a call, since the two
+// kernels give the same bits and the output cannot tell which one ran.
+static std::atomic<long long> g_fast_launches{0};
+long long attention_fast_launches() { return g_fast_launches.load(std::memory_order_relaxed); }
+template <int PF>
+static hipError_t launch_attn_fast(const AttnArgs& a, hipStream_t s) {
+  static DynLdsAttr attr;
+  g_fast_launches.fetch_add(1, std::memory_order_relaxed);
+  {
+    hipError_t e = attr.ensure(reinterpret_cast<const void*>(&attn_fast_kernel<PF>), AF_LDS);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL((attn_fast_kernel<PF>), dim3((a.Nq / AF_QB) * a.H * a.B), dim3(256), AF_LDS, s, a);
+  return hipGetLastError();
+}
+
 hipError_t launch_attention(const AttnArgs& a_in, int nsplit, hipStream_t s) {
   AttnArgs a = a_in;
   if (nsplit < 1 || nsplit > 4) return hipErrorInvalidValue;
@@ -336,6 +395,7 @@ hipError_t launch_attention(const AttnArgs& a_in, int nsplit, hipStream_t s) {
   }
   if (nsplit == 2) {                                  // "half" precision: fp16 hi-only planes, one product
     if (a.q_lo || a.k_lo || a.vt_lo) return hipErrorInvalidValue;
+    if (attn_fast_eligible(a)) return a.o_fmt == FMT_H8 ? launch_attn_fast<PF_H8>(a, s) : launch_attn_fast<PF_F16>(a, s);
     return launch_attn_t<1, true>(a, s);
   }
   if (a.o_fmt != FMT_BF16) return hipErrorInvalidValue;

@@ -133,6 +133,8 @@ struct AttnArgs {
   const uint32_t* drop_seed = nullptr; uint32_t drop_thr = 0u, drop_call = 0u; float drop_scale = 1.f;
 };                                                       // precision: 3 bf16x3, 1 bf16, 2 and 4: one IEEE-half product
 hipError_t launch_attention(const AttnArgs& a, int precision, hipStream_t s);
+long long attention_fast_launches();                                   // test hook: launches that took attn_fast_kernel so far (ns2_debug_attention_fast_launches)
+void force_attention_kernel(int k);                                     // test hook, the modes of ns2_debug_force_attention (include/ns2hip.h); decoded in attention.hip
 
 // RMSNorm (NS2:727-746): out = x / max(|x|, 1e-12) * sqrt(d) [* gamma] [* g_c + b_c]  -> split planes
 struct NormArgs {
