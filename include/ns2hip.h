@@ -30,7 +30,7 @@
  *       passes x_lo == x_hi + 32 (anything else is NS2_ERR_HIP / invalid value).  precision 3 needs this form.
  *     x_lo == NULL: the dense [rows, ld] hi plane alone (precision 1: bf16, precision 2: IEEE half).
  *     precision 4 operands use the interleaved form with the line [half(32) | e5m2(x)(32 B) | e5m2((x-half(x))*2^12)(32 B)]
- *       (x_lo == x_hi + 32 as above); the operands of ns2_attention (q, k, transposed values) are dense IEEE half at
+ *       (x_lo == x_hi + 32 as above); the operands of ns2_attention_fwd (q, k, transposed values) are dense IEEE half at
  *       precision 4, which is also what ns2_linear_qkv writes there.
  *     Transposed value planes (vt_hi, vt_lo, vt_ld) use the same rule along the key axis.
  */
@@ -135,7 +135,7 @@ int ns2_linear_geglu(const ns2_weight* w, const uint16_t* a_hi, const uint16_t* 
                      const float* packed_bias, uint16_t* out_hi, uint16_t* out_lo, int ldo, int precision, void* stream);
 int ns2_geglu_pack_bias(const float* bias, int f, float* packed, int packed_len, void* stream);
 /* fused q/k/v projection (NS2:1051-1053, 1063): columns < split_col -> planes [M, ldo]; columns >= split_col
- * (the values) -> transposed planes vt[b][col - split_col][n] with row stride vt_ld (for ns2_attention) */
+ * (the values) -> transposed planes vt[b][col - split_col][n] with row stride vt_ld (for ns2_attention_fwd) */
 int ns2_linear_qkv(const ns2_weight* w, const uint16_t* a_hi, const uint16_t* a_lo, int lda, int M, int seq_len,
                    int split_col, uint16_t* out_hi, uint16_t* out_lo, int ldo, uint16_t* vt_hi, uint16_t* vt_lo,
                    int vt_ld, int precision, void* stream);
@@ -147,19 +147,38 @@ int ns2_wavenet_block(const ns2_weight* w, const uint16_t* a_hi, const uint16_t*
                       int dilation, const float* conv_bias, const float* res_bias, const float* film, int film_ld,
                       uint16_t* out_hi, uint16_t* out_lo, int ldo, int precision, void* stream);
 
-/* Attend.forward (ATT:77-155), non-causal, head dim 64: o = softmax(q k^T * scale) v.
- * key_mask (may be null): key-padding mask [B, Nk] bytes, 1 = attend (ATT:92-94 / 136-138) */
-int ns2_attention(const uint16_t* q_hi, const uint16_t* q_lo, int ldq, int q_col0, const uint16_t* k_hi,
-                  const uint16_t* k_lo, int ldk, int k_col0, const uint16_t* vt_hi, const uint16_t* vt_lo, int vt_ld,
-                  uint16_t* o_hi, uint16_t* o_lo, int ldo, int B, int H, int Nq, int Nk, float scale,
-                  const uint8_t* key_mask, int precision, void* stream);
-
-/* the same with the head dimension named: 32, 64 or 128 (the reference's `dim_head` keyword, NS2:814-831 -> Attention ATT:77-155;
- * q / k columns of head h start at col0 + h * head_dim, vt rows at h * head_dim); scale is the caller's (dim_head ** -0.5) */
-int ns2_attention_hd(const uint16_t* q_hi, const uint16_t* q_lo, int ldq, int q_col0, const uint16_t* k_hi,
-                     const uint16_t* k_lo, int ldk, int k_col0, const uint16_t* vt_hi, const uint16_t* vt_lo, int vt_ld,
-                     uint16_t* o_hi, uint16_t* o_lo, int ldo, int B, int H, int Nq, int Nk, float scale,
-                     const uint8_t* key_mask, int precision, int head_dim, void* stream);
+/* Attend.forward (ATT:77-155), non-causal: o = softmax(q k^T * scale) v.  ONE argument block describes the call; a zero-initialised
+ * block plus the planes, the sizes, `scale` and `precision` is the plain forward, and every other field switches one feature on:
+ *   q / k      row-major planes [B * Nq, ldq] / [B * Nk, ldk]; head h at columns col0 + h * head_dim.
+ *   vt         transposed value planes [B][H * head_dim][vt_ld] (what ns2_linear_qkv writes); o [B * Nq, ldo], head h at h * head_dim.
+ *   head_dim   32, 64 or 128 (0 = 64): the reference's `dim_head` keyword (NS2:814-831 -> Attention ATT:77-155); scale is the
+ *              caller's (dim_head ** -0.5).
+ *   precision  1..4, the format of the operand planes (see the conventions above).  o_precision: the format of the output planes
+ *              when it is not the operands' (4 = FMT_H8 lines for a precision-4 out-projection behind a bf16 x3 attention, 3 = bf16
+ *              hi / lo lines; 0 = as `precision`).
+ *   key_mask   [B, Nk] bytes, 1 = attend (ATT:92-94, 136-138; plain `Transformer` NS2:1073-1115; NULL = none).  Masked keys have P = 0
+ *              (and dK = dV = 0 in the backward).  Every utterance must keep at least one key (the caller checks: the reference
+ *              produces NaN there).
+ *   lse        [B, H, Nq] (NULL = not wanted) = log2 of the softmax denominator of the scaled scores (m + log2 l): what the backward
+ *              recomputes P from.  Training runs in the exact arithmetic at the backward's head dimension: precision 3, head_dim 64.
+ *   dropout_p  in [0, 1), on the softmax output (ATT:100-101, 146): O = sum_k P_k keep_k / (1 - p) v_k, lse unchanged (and required).
+ *              keep is a stateless function of (seed, call, b, h, q, k) -- csrc/dropout_keep.h, DESIGN.md §9 -- so forward and backward
+ *              agree without storing it.  dropout_seed = two 32-bit words in DEVICE memory, read by the kernels (a captured graph sees
+ *              the words of each replay); dropout_call = index of the attention inside the pass.  The backward takes the values its
+ *              forward got.  dropout_p == 0: no dropout, the seed is not read (may be NULL) and the kernels without dropout run.
+ * With key_mask == NULL and dropout_p == 0 the unmasked kernels run. */
+typedef struct {
+  const uint16_t* q_hi; const uint16_t* q_lo; int ldq, q_col0;
+  const uint16_t* k_hi; const uint16_t* k_lo; int ldk, k_col0;
+  const uint16_t* vt_hi; const uint16_t* vt_lo; int vt_ld;
+  uint16_t* o_hi; uint16_t* o_lo; int ldo;
+  int B, H, Nq, Nk; float scale;
+  int head_dim, precision, o_precision;
+  const uint8_t* key_mask;
+  float* lse;
+  float dropout_p; const uint32_t* dropout_seed; unsigned dropout_call;
+} ns2_attn_args;
+int ns2_attention_fwd(const ns2_attn_args* args, void* stream);
 
 /* RMSNorm.forward (NS2:727-746).  gamma may be null; cond (may be null) holds [gamma_c | beta_c] per batch row */
 int ns2_rmsnorm(const float* x, int ldx, int M, int d, int seq_len, const float* gamma, const float* cond, int cond_ld,
@@ -496,14 +515,8 @@ int ns2_rmsnorm_bwd_slices(int seq_len);
 int ns2_rmsnorm_bwd(const float* x, int64_t ldx, const float* dy, int64_t lddy, const float* gamma, const float* cond, int cond_ld, int B,
                     int seq_len, int d, const float* dx_add, float* dx, int64_t lddx, float* cond_partial, float* gamma_partial, void* stream);
 
-/* ns2_attention that also returns lse [B, H, Nq] = log2 of the softmax denominator of the scaled scores (m + log2 l): what the
- * backward recomputes P from (ATT:77-155; no key-padding mask on this path: Model never passes one) */
-int ns2_attention_lse(const uint16_t* q_hi, const uint16_t* q_lo, int ldq, int q_col0, const uint16_t* k_hi, const uint16_t* k_lo, int ldk,
-                      int k_col0, const uint16_t* vt_hi, const uint16_t* vt_lo, int vt_ld, uint16_t* o_hi, uint16_t* o_lo, int ldo, int B,
-                      int H, int Nq, int Nk, float scale, float* lse, int precision, int o_precision, void* stream);
-/* (o_precision: the format of the output planes when it is not the operands': 4 = FMT_H8 lines for a precision-4 out-projection
- * behind a bf16 x3 attention; 0 = as `precision`) */
-/* delta[b, h, q] = sum_d dO[q, 64 h + d] * O[q, 64 h + d] (O from its operand planes, o_precision 3 or 4) */
+/* The training forward is ns2_attention_fwd with `lse` set.
+ * delta[b, h, q] = sum_d dO[q, 64 h + d] * O[q, 64 h + d] (O from its operand planes, o_precision 3 or 4) */
 int ns2_attention_delta(const float* d_out, int64_t ld_dout, const uint16_t* o_hi, const uint16_t* o_lo, int ldo, int B, int H, int Nq,
                         float* delta, int o_precision, void* stream);
 /* flash-attention backward, head dim 64: dq = scale * dS k, dk = scale * dS^T q, dv = P^T dO with P recomputed from lse and
@@ -524,25 +537,14 @@ typedef struct {
    * dgrad and wgrad GEMMs are their only consumers): planes [rows, gp_ld] of precision gp_precision (3: bf16 hi / lo lines, 4: FMT_H8),
    * dq at columns dq_col0 + 64 h of row b Nq + q, dk / dv at dk_col0 / dv_col0 + 64 h of row b Nk + k (column offsets multiples of 32) */
   uint16_t* gp_hi; uint16_t* gp_lo; int gp_ld, gp_precision, gp_q, gp_kv;
+  /* the mask and the dropout of the forward this is the backward of, as in ns2_attn_args (all zero: neither) */
+  const uint8_t* key_mask; float dropout_p; const uint32_t* dropout_seed; unsigned dropout_call;
 } ns2_attn_bwd_args;
 int ns2_attention_bwd(const ns2_attn_bwd_args* args, void* stream);
 
 /* ---- training of the conditioning encoders (NS2:228-341, 1073-1115; trained jointly with the denoiser: NS2:1538-1543, 1635) ----
- * The `_masked` family = ns2_attention_lse / ns2_attention_bwd with the two things Transformer's attention has and Model's has not:
- *   key_mask  [B, Nk] bytes, 1 = attend (ATT:92-94, 136-138; NULL = none).  Masked keys have P = 0 and dK = dV = 0.  Every utterance must
- *             keep at least one key (the caller checks: the reference produces NaN there).
- *   dropout_p in [0, 1) on the softmax output (ATT:100-101, 146): O = sum_k P_k keep_k / (1 - p) v_k, lse unchanged.  keep is a stateless
- *             function of (seed, call, b, h, q, k) -- csrc/dropout_keep.h, DESIGN.md §9 -- so forward and backward agree without storing
- *             it.  seed = two 32-bit words in DEVICE memory, read by the kernels (a captured graph sees the words of each replay);
- *             call = index of the attention inside the pass.  The backward takes the values its forward got.  dropout_p == 0: no
- *             dropout, the seed is not read (may be NULL) and the kernels without dropout run.
- * precision 3 only.  With key_mask == NULL and dropout_p == 0 the unmasked kernels run (bit-identical to the plain entry points). */
-int ns2_attention_lse_masked(const uint16_t* q_hi, const uint16_t* q_lo, int ldq, int q_col0, const uint16_t* k_hi, const uint16_t* k_lo,
-                             int ldk, int k_col0, const uint16_t* vt_hi, const uint16_t* vt_lo, int vt_ld, uint16_t* o_hi, uint16_t* o_lo,
-                             int ldo, int B, int H, int Nq, int Nk, float scale, float* lse, int precision, int o_precision,
-                             const uint8_t* key_mask, float dropout_p, const uint32_t* seed, unsigned call, void* stream);
-int ns2_attention_bwd_masked(const ns2_attn_bwd_args* args, const uint8_t* key_mask, float dropout_p, const uint32_t* seed, unsigned call,
-                             void* stream);
+ * Transformer's attention has two things Model's has not, a key-padding mask and dropout on the softmax output: the key_mask and
+ * dropout_* fields of ns2_attn_args / ns2_attn_bwd_args. */
 /* debugging / tests: out [B, H, Nq, Nk] bytes, 1 where the kernels above keep P[b, h, q, k] */
 int ns2_dropout_keep_mask(const uint32_t* seed, unsigned call, float dropout_p, int B, int H, int Nq, int Nk, uint8_t* out, void* stream);
 /* SiLU of the encoders' k = 9 convolutions (NS2:247, 306-311) on the fp32 pre-activation x [M, ldx], C columns, and its backward

@@ -27,6 +27,19 @@ F = c_float
 L = c_int64
 
 
+class AttnArgs(ctypes.Structure):
+    """ns2_attn_args (include/ns2hip.h), field for field"""
+    _fields_ = [("q_hi", P), ("q_lo", P), ("ldq", I), ("q_col0", I),
+                ("k_hi", P), ("k_lo", P), ("ldk", I), ("k_col0", I),
+                ("vt_hi", P), ("vt_lo", P), ("vt_ld", I),
+                ("o_hi", P), ("o_lo", P), ("ldo", I),
+                ("B", I), ("H", I), ("Nq", I), ("Nk", I), ("scale", F),
+                ("head_dim", I), ("precision", I), ("o_precision", I),
+                ("key_mask", P),
+                ("lse", P),
+                ("dropout_p", F), ("dropout_seed", P), ("dropout_call", ctypes.c_uint)]
+
+
 class AttnBwdArgs(ctypes.Structure):
     """ns2_attn_bwd_args (include/ns2hip.h), field for field"""
     _fields_ = [("q_hi", P), ("q_lo", P), ("ldq", I), ("q_col0", I),
@@ -38,7 +51,8 @@ class AttnBwdArgs(ctypes.Structure):
                 ("dk", P), ("lddk", I), ("dk_col0", I),
                 ("dv", P), ("lddv", I), ("dv_col0", I),
                 ("B", I), ("H", I), ("Nq", I), ("Nk", I), ("scale", F),
-                ("gp_hi", P), ("gp_lo", P), ("gp_ld", I), ("gp_precision", I), ("gp_q", I), ("gp_kv", I)]
+                ("gp_hi", P), ("gp_lo", P), ("gp_ld", I), ("gp_precision", I), ("gp_q", I), ("gp_kv", I),
+                ("key_mask", P), ("dropout_p", F), ("dropout_seed", P), ("dropout_call", ctypes.c_uint)]
 
 
 class RepackPart(ctypes.Structure):
@@ -67,8 +81,7 @@ SIGNATURES = {
     "ns2_geglu_pack_bias": (I, [P, I, P, I, P]),
     "ns2_linear_qkv": (I, [P, P, P, I, I, I, I, P, P, I, P, P, I, I, P]),
     "ns2_wavenet_block": (I, [P, P, P, I, I, I, I, P, P, P, I, P, P, I, I, P]),
-    "ns2_attention": (I, [P, P, I, I, P, P, I, I, P, P, I, P, P, I, I, I, I, I, F, P, I, P]),
-    "ns2_attention_hd": (I, [P, P, I, I, P, P, I, I, P, P, I, P, P, I, I, I, I, I, F, P, I, I, P]),
+    "ns2_attention_fwd": (I, [POINTER(AttnArgs), P]),
     "ns2_rmsnorm": (I, [P, I, I, I, I, P, P, I, P, P, I, P, I, I, P]),
     "ns2_skinny_linear_workspace_bytes": (L, [I, I, I]),
     "ns2_skinny_linear": (I, [P, I, P, P, P, I, I, I, I, I, P, L, P]),
@@ -151,12 +164,9 @@ SIGNATURES = {
     "ns2_geglu_bwd": (I, [P, L, P, L, L, I, P, L, P]),
     "ns2_rmsnorm_bwd_slices": (I, [I]),
     "ns2_rmsnorm_bwd": (I, [P, L, P, L, P, P, I, I, I, I, P, P, L, P, P, P]),
-    "ns2_attention_lse": (I, [P, P, I, I, P, P, I, I, P, P, I, P, P, I, I, I, I, I, F, P, I, I, P]),
     "ns2_attention_delta": (I, [P, L, P, P, I, I, I, I, P, I, P]),
     "ns2_attention_bwd": (I, [POINTER(AttnBwdArgs), P]),
     # ---- training of the conditioning encoders
-    "ns2_attention_lse_masked": (I, [P, P, I, I, P, P, I, I, P, P, I, P, P, I, I, I, I, I, F, P, I, I, P, F, P, ctypes.c_uint, P]),
-    "ns2_attention_bwd_masked": (I, [POINTER(AttnBwdArgs), P, F, P, ctypes.c_uint, P]),
     "ns2_dropout_keep_mask": (I, [P, ctypes.c_uint, F, I, I, I, I, P, P]),
     "ns2_silu_fwd": (I, [P, L, L, I, P, L, P]),
     "ns2_silu_bwd": (I, [P, L, P, L, L, I, P, L, P]),

@@ -64,7 +64,7 @@ static inline int prec_ok(int p) { return p >= 1 && p <= 4; }
 static inline int op_fmt(int p) { return p == 2 ? FMT_F16 : (p == 4 ? FMT_H8 : FMT_BF16); }
 
 extern "C" const char* ns2_last_error(void) { return g_err; }
-extern "C" int ns2_version(void) { return 118; }   // 118: ns2_debug_force_attention, ns2_debug_attention_fast_launches (attn_fast_kernel.h); 117: the range-guard counters register themselves: ns2_saturation_counters / _counter_name / _peek replace ns2_saturation_peek_async / _peek_train_async; 116: ns2_groupnorm_silu, ns2_length_regulate(_totals), ns2_row_dot (duration_pitch.hip); 115: ns2_weights_retile; 114: ns2_attention_hd (head dims 32 / 64 / 128), ns2_model_create takes dim_head 32 / 128; 113: ns2_weight_tile_conv3 + ns2_conv3_input_ld (the dedicated FF causal conv kernel, ffconv_kernel.h), ns2_weight_tile_linear (gemm3_kernel.h), ns2_weight_tile_wavenet (wavenet3_kernel.h), ns2_debug_force_gemm(4 / 5); 112: ns2_seanet_resblock_narrow; 111: training entry points take a precision (3 = bf16 x3, 4 = mixed on FMT_H8 lines), ns2_linear_split_as; 110: backward pass (capi_train.cpp: ns2_wgrad, ns2_attention_bwd, ...), ns2_weight_update; 109: ns2_seanet_conv_narrow; 108: ns2_seanet_prep2; 107: ns2_lstm2 (two LSTM layers, one launch); 106: ns2_saturation_peek_async; 105: ns2_lstm_layer takes the scratch size (persistent recurrence); 104: model precision 5 (per-site plan); 103: precision 2 / 4 at op level, caller-owned skinny-linear scratch
+extern "C" int ns2_version(void) { return 119; }   // 119: one argument block per attention direction: ns2_attention_fwd(ns2_attn_args) replaces ns2_attention / _hd / _lse / _lse_masked, ns2_attn_bwd_args carries the mask and dropout of the removed bwd_masked entry; 118: ns2_debug_force_attention, ns2_debug_attention_fast_launches (attn_fast_kernel.h); 117: the range-guard counters register themselves: ns2_saturation_counters / _counter_name / _peek replace ns2_saturation_peek_async / _peek_train_async; 116: ns2_groupnorm_silu, ns2_length_regulate(_totals), ns2_row_dot (duration_pitch.hip); 115: ns2_weights_retile; 114: ns2_attention_hd (head dims 32 / 64 / 128), ns2_model_create takes dim_head 32 / 128; 113: ns2_weight_tile_conv3 + ns2_conv3_input_ld (the dedicated FF causal conv kernel, ffconv_kernel.h), ns2_weight_tile_linear (gemm3_kernel.h), ns2_weight_tile_wavenet (wavenet3_kernel.h), ns2_debug_force_gemm(4 / 5); 112: ns2_seanet_resblock_narrow; 111: training entry points take a precision (3 = bf16 x3, 4 = mixed on FMT_H8 lines), ns2_linear_split_as; 110: backward pass (capi_train.cpp: ns2_wgrad, ns2_attention_bwd, ...), ns2_weight_update; 109: ns2_seanet_conv_narrow; 108: ns2_seanet_prep2; 107: ns2_lstm2 (two LSTM layers, one launch); 106: ns2_saturation_peek_async; 105: ns2_lstm_layer takes the scratch size (persistent recurrence); 104: model precision 5 (per-site plan); 103: precision 2 / 4 at op level, caller-owned skinny-linear scratch
 extern "C" int ns2_debug_force_gemm(int kernel) {
   ARGCHK(kernel >= 0 && kernel <= 5, "ns2_debug_force_gemm: 0 auto, 1 = 128x128 kernel, 2 = 256x256 kernel, 3 = auto without split-K, 4 = auto without the dedicated kernels (FF conv, lean linear, lean Wavenet), 5 = auto without split-K, the dedicated kernels whenever eligible");
   force_gemm_kernel(kernel);
@@ -236,29 +236,31 @@ extern "C" int ns2_wavenet_block(const ns2_weight* w, const uint16_t* a_hi, cons
                       ldo, 0, ldo, precision, (hipStream_t)stream, p1_half);
 }
 
-extern "C" int ns2_attention_hd(const uint16_t* q_hi, const uint16_t* q_lo, int ldq, int q_col0, const uint16_t* k_hi,
-                                const uint16_t* k_lo, int ldk, int k_col0, const uint16_t* vt_hi, const uint16_t* vt_lo, int vt_ld,
-                                uint16_t* o_hi, uint16_t* o_lo, int ldo, int B, int H, int Nq, int Nk, float scale,
-                                const uint8_t* key_mask, int precision, int head_dim, void* stream) {
-  ARGCHK(q_hi && k_hi && vt_hi && o_hi && prec_ok(precision), "ns2_attention: bad arguments");
-  ARGCHK(head_dim == 32 || head_dim == 64 || head_dim == 128, "ns2_attention: head_dim must be 32, 64 or 128");
-  AttnArgs a;
-  a.D = head_dim;
-  a.lse = nullptr;
-  a.q_hi = q_hi; a.q_lo = q_lo; a.ldq = ldq; a.q_col0 = q_col0;
-  a.k_hi = k_hi; a.k_lo = k_lo; a.ldk = ldk; a.k_col0 = k_col0;
-  a.vt_hi = vt_hi; a.vt_lo = vt_lo; a.vt_ld = vt_ld;
-  a.o_hi = o_hi; a.o_lo = o_lo; a.ldo = ldo; a.o_fmt = -1;
-  a.B = B; a.H = H; a.Nq = Nq; a.Nk = Nk; a.scale = scale; a.kmask = key_mask;
-  HIPRET(launch_attention(a, precision, (hipStream_t)stream));
+// The one translation of the C argument block into the kernels' (ns2_kernels.h AttnArgs, whose defaults are "nothing optional").
+// Everything ns2_attention_fwd refuses, it refuses here, before any HIP call; launch_attention judges the rest.
+static int attn_args_from(const ns2_attn_args* p, AttnArgs* out) {
+  ARGCHK(p != nullptr, "ns2_attention_fwd: null argument block");
+  ARGCHK(p->q_hi && p->k_hi && p->vt_hi && p->o_hi && prec_ok(p->precision), "ns2_attention_fwd: bad arguments");
+  ARGCHK(p->head_dim == 0 || p->head_dim == 32 || p->head_dim == 64 || p->head_dim == 128, "ns2_attention_fwd: head_dim must be 32, 64 or 128 (0 = 64)");
+  ARGCHK(p->o_precision == 0 || p->o_precision == 3 || p->o_precision == 4, "ns2_attention_fwd: o_precision 0 (= precision), 3 (bf16 hi / lo) or 4 (FMT_H8)");
+  AttnArgs& a = *out;                                  // default-constructed by the caller
+  a.D = p->head_dim ? p->head_dim : 64;
+  ARGCHK(!p->lse || (p->precision == 3 && a.D == 64), "ns2_attention_fwd: lse needs precision 3 and head_dim 64 (what the backward kernels take)");
+  ARGCHK(p->dropout_p == 0.f || p->lse, "ns2_attention_fwd: dropout needs lse (it belongs to the training forward)");
+  if (const char* bad = set_attn_dropout(a, p->dropout_p, p->dropout_seed, p->dropout_call)) { set_error("ns2_attention_fwd: %s", bad); return NS2_ERR_ARG; }
+  a.q_hi = p->q_hi; a.q_lo = p->q_lo; a.ldq = p->ldq; a.q_col0 = p->q_col0;
+  a.k_hi = p->k_hi; a.k_lo = p->k_lo; a.ldk = p->ldk; a.k_col0 = p->k_col0;
+  a.vt_hi = p->vt_hi; a.vt_lo = p->vt_lo; a.vt_ld = p->vt_ld;
+  a.o_hi = p->o_hi; a.o_lo = p->o_lo; a.ldo = p->ldo;
+  if (p->o_precision) a.o_fmt = op_fmt(p->o_precision);
+  a.B = p->B; a.H = p->H; a.Nq = p->Nq; a.Nk = p->Nk; a.scale = p->scale; a.kmask = p->key_mask; a.lse = p->lse;
   return NS2_OK;
 }
-extern "C" int ns2_attention(const uint16_t* q_hi, const uint16_t* q_lo, int ldq, int q_col0, const uint16_t* k_hi,
-                             const uint16_t* k_lo, int ldk, int k_col0, const uint16_t* vt_hi, const uint16_t* vt_lo, int vt_ld,
-                             uint16_t* o_hi, uint16_t* o_lo, int ldo, int B, int H, int Nq, int Nk, float scale,
-                             const uint8_t* key_mask, int precision, void* stream) {
-  return ns2_attention_hd(q_hi, q_lo, ldq, q_col0, k_hi, k_lo, ldk, k_col0, vt_hi, vt_lo, vt_ld, o_hi, o_lo, ldo, B, H, Nq, Nk, scale,
-                          key_mask, precision, 64, stream);
+extern "C" int ns2_attention_fwd(const ns2_attn_args* p, void* stream) {
+  AttnArgs a;
+  if (int rc = attn_args_from(p, &a)) return rc;
+  HIPRET(launch_attention(a, p->precision, (hipStream_t)stream));
+  return NS2_OK;
 }
 
 extern "C" int ns2_rmsnorm(const float* x, int ldx, int M, int d, int seq_len, const float* gamma, const float* cond, int cond_ld,

@@ -6,7 +6,6 @@
 #include <cstring>
 
 #include "ns2_host.h"
-#include "dropout_keep.h"
 
 using namespace ns2;
 
@@ -256,45 +255,6 @@ extern "C" int ns2_rmsnorm_bwd(const float* x, int64_t ldx, const float* dy, int
   return NS2_OK;
 }
 
-static int attention_lse_impl(const uint16_t* q_hi, const uint16_t* q_lo, int ldq, int q_col0, const uint16_t* k_hi, const uint16_t* k_lo,
-                              int ldk, int k_col0, const uint16_t* vt_hi, const uint16_t* vt_lo, int vt_ld, uint16_t* o_hi, uint16_t* o_lo,
-                              int ldo, int B, int H, int Nq, int Nk, float scale, float* lse, int precision, int o_precision,
-                              const unsigned char* key_mask, float dropout_p, const uint32_t* seed, unsigned call, void* stream);
-extern "C" int ns2_attention_lse(const uint16_t* q_hi, const uint16_t* q_lo, int ldq, int q_col0, const uint16_t* k_hi, const uint16_t* k_lo,
-                                 int ldk, int k_col0, const uint16_t* vt_hi, const uint16_t* vt_lo, int vt_ld, uint16_t* o_hi, uint16_t* o_lo,
-                                 int ldo, int B, int H, int Nq, int Nk, float scale, float* lse, int precision, int o_precision, void* stream) {
-  return attention_lse_impl(q_hi, q_lo, ldq, q_col0, k_hi, k_lo, ldk, k_col0, vt_hi, vt_lo, vt_ld, o_hi, o_lo, ldo, B, H, Nq, Nk, scale, lse,
-                            precision, o_precision, nullptr, 0.f, nullptr, 0u, stream);
-}
-// the encoders' training pass: + key-padding mask [B, Nk] bytes (1 = attend) and / or attention dropout (dropout_keep.h)
-extern "C" int ns2_attention_lse_masked(const uint16_t* q_hi, const uint16_t* q_lo, int ldq, int q_col0, const uint16_t* k_hi,
-                                        const uint16_t* k_lo, int ldk, int k_col0, const uint16_t* vt_hi, const uint16_t* vt_lo, int vt_ld,
-                                        uint16_t* o_hi, uint16_t* o_lo, int ldo, int B, int H, int Nq, int Nk, float scale, float* lse,
-                                        int precision, int o_precision, const uint8_t* key_mask, float dropout_p, const uint32_t* seed,
-                                        unsigned call, void* stream) {
-  ARGCHK(precision == 3, "ns2_attention_lse_masked: precision 3 (the encoders train in the exact arithmetic)");
-  ARGCHK(dropout_p >= 0.f && dropout_p < 1.f, "ns2_attention_lse_masked: dropout_p in [0, 1)");
-  ARGCHK(dropout_p == 0.f || seed != nullptr, "ns2_attention_lse_masked: dropout needs the seed words (device memory)");
-  return attention_lse_impl(q_hi, q_lo, ldq, q_col0, k_hi, k_lo, ldk, k_col0, vt_hi, vt_lo, vt_ld, o_hi, o_lo, ldo, B, H, Nq, Nk, scale, lse,
-                            precision, o_precision, key_mask, dropout_p, dropout_p > 0.f ? seed : nullptr, call, stream);
-}
-static int attention_lse_impl(const uint16_t* q_hi, const uint16_t* q_lo, int ldq, int q_col0, const uint16_t* k_hi, const uint16_t* k_lo,
-                              int ldk, int k_col0, const uint16_t* vt_hi, const uint16_t* vt_lo, int vt_ld, uint16_t* o_hi, uint16_t* o_lo,
-                              int ldo, int B, int H, int Nq, int Nk, float scale, float* lse, int precision, int o_precision,
-                              const unsigned char* key_mask, float dropout_p, const uint32_t* seed, unsigned call, void* stream) {
-  ARGCHK(q_hi && k_hi && vt_hi && o_hi && lse && precision >= 1 && precision <= 4, "ns2_attention_lse: bad arguments");
-  ARGCHK(o_precision == 0 || o_precision == 3 || o_precision == 4, "ns2_attention_lse: o_precision 0 (= precision), 3 (bf16 hi / lo) or 4 (FMT_H8)");
-  AttnArgs a;
-  a.D = 64;
-  a.q_hi = q_hi; a.q_lo = q_lo; a.ldq = ldq; a.q_col0 = q_col0;
-  a.k_hi = k_hi; a.k_lo = k_lo; a.ldk = ldk; a.k_col0 = k_col0;
-  a.vt_hi = vt_hi; a.vt_lo = vt_lo; a.vt_ld = vt_ld;
-  a.o_hi = o_hi; a.o_lo = o_lo; a.ldo = ldo; a.o_fmt = o_precision == 4 ? FMT_H8 : (o_precision == 3 ? FMT_BF16 : -1);
-  a.B = B; a.H = H; a.Nq = Nq; a.Nk = Nk; a.scale = scale; a.kmask = key_mask; a.lse = lse;
-  if (seed) { a.drop_seed = seed; a.drop_thr = drop_threshold(dropout_p); a.drop_call = call; a.drop_scale = 1.0f / (1.0f - dropout_p); }
-  HIPRET(launch_attention(a, precision, (hipStream_t)stream));
-  return NS2_OK;
-}
 extern "C" int ns2_attention_delta(const float* d_out, int64_t ld_dout, const uint16_t* o_hi, const uint16_t* o_lo, int ldo, int B, int H,
                                    int Nq, float* delta, int o_precision, void* stream) {
   ARGCHK(d_out && o_hi && delta, "ns2_attention_delta: null pointer");
@@ -302,11 +262,11 @@ extern "C" int ns2_attention_delta(const float* d_out, int64_t ld_dout, const ui
   HIPRET(launch_attn_delta(d_out, (long)ld_dout, o_hi, o_lo, ldo, B, H, Nq, delta, (hipStream_t)stream, o_precision == 4 ? FMT_H8 : FMT_BF16));
   return NS2_OK;
 }
-static int attention_bwd_impl(const ns2_attn_bwd_args* p, const unsigned char* key_mask, float dropout_p, const uint32_t* seed, unsigned call,
-                              void* stream) {
+extern "C" int ns2_attention_bwd(const ns2_attn_bwd_args* p, void* stream) {
   ARGCHK(p != nullptr, "ns2_attention_bwd: null argument block");
+  ARGCHK(p->gp_precision == 0 || p->gp_precision == 3 || p->gp_precision == 4, "ns2_attention_bwd: gp_precision 3 (bf16 hi / lo planes) or 4 (FMT_H8 lines)");
   AttnBwdArgs a;
-  memset(&a, 0, sizeof a);
+  if (const char* bad = set_attn_dropout(a, p->dropout_p, p->dropout_seed, p->dropout_call)) { set_error("ns2_attention_bwd: %s", bad); return NS2_ERR_ARG; }
   a.q_hi = p->q_hi; a.q_lo = p->q_lo; a.ldq = p->ldq; a.q_col0 = p->q_col0;
   a.k_hi = p->k_hi; a.k_lo = p->k_lo; a.ldk = p->ldk; a.k_col0 = p->k_col0;
   a.v_hi = p->v_hi; a.v_lo = p->v_lo; a.ldv = p->ldv; a.v_col0 = p->v_col0;
@@ -317,20 +277,10 @@ static int attention_bwd_impl(const ns2_attn_bwd_args* p, const unsigned char* k
   a.dv = p->dv; a.lddv = p->lddv; a.dv_col0 = p->dv_col0;
   a.B = p->B; a.H = p->H; a.Nq = p->Nq; a.Nk = p->Nk; a.scale = p->scale;
   a.gp_hi = p->gp_hi; a.gp_lo = p->gp_lo; a.gp_ld = p->gp_ld; a.gp_q = p->gp_q; a.gp_kv = p->gp_kv;
-  ARGCHK(p->gp_precision == 0 || p->gp_precision == 3 || p->gp_precision == 4, "ns2_attention_bwd: gp_precision 3 (bf16 hi / lo planes) or 4 (FMT_H8 lines)");
   a.gp_fmt = p->gp_precision == 4 ? FMT_H8 : FMT_BF16;
-  a.kmask = key_mask; a.drop_scale = 1.f;
-  if (seed) { a.drop_seed = seed; a.drop_thr = drop_threshold(dropout_p); a.drop_call = call; a.drop_scale = 1.0f / (1.0f - dropout_p); }
+  a.kmask = p->key_mask;
   HIPRET(launch_attention_bwd(a, (hipStream_t)stream));
   return NS2_OK;
-}
-extern "C" int ns2_attention_bwd(const ns2_attn_bwd_args* p, void* stream) { return attention_bwd_impl(p, nullptr, 0.f, nullptr, 0u, stream); }
-// the encoders' training pass: the same mask / dropout arguments as ns2_attention_lse_masked got in the forward
-extern "C" int ns2_attention_bwd_masked(const ns2_attn_bwd_args* p, const uint8_t* key_mask, float dropout_p, const uint32_t* seed, unsigned call,
-                                        void* stream) {
-  ARGCHK(dropout_p >= 0.f && dropout_p < 1.f, "ns2_attention_bwd_masked: dropout_p in [0, 1)");
-  ARGCHK(dropout_p == 0.f || seed != nullptr, "ns2_attention_bwd_masked: dropout needs the seed words (device memory)");
-  return attention_bwd_impl(p, key_mask, dropout_p, dropout_p > 0.f ? seed : nullptr, call, stream);
 }
 extern "C" int ns2_dropout_keep_mask(const uint32_t* seed, unsigned call, float dropout_p, int B, int H, int Nq, int Nk, uint8_t* out, void* stream) {
   ARGCHK(seed && out, "ns2_dropout_keep_mask: null pointer");

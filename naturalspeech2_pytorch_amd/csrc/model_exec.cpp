@@ -760,13 +760,11 @@ static int attention_call(const bf16_t* q_hi, const bf16_t* q_lo, int ldq, int q
                           hipStream_t s, int dim_head) {
   AttnArgs a;
   a.D = dim_head;
-  a.lse = nullptr;
   a.q_hi = q_hi; a.q_lo = q_lo; a.ldq = ldq; a.q_col0 = q_col0;
   a.k_hi = k_hi; a.k_lo = k_lo; a.ldk = ldk; a.k_col0 = k_col0;
   a.vt_hi = vt.hi; a.vt_lo = vt.lo; a.vt_ld = vt_ld;
   a.o_hi = o.hi; a.o_lo = o.lo; a.ldo = ldo; a.o_fmt = o.fmt;
   a.B = B; a.H = H; a.Nq = Nq; a.Nk = Nk; a.scale = 1.0f / sqrtf((float)dim_head);       // dim_head ** -0.5  (ATT:128 / SDPA default; 0.125 exactly at 64)
-  a.kmask = nullptr;
   HIPCHK(launch_attention(a, prec, s));
   return NS2_OK;
 }

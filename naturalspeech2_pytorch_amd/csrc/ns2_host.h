@@ -6,10 +6,23 @@
 
 #include "../../include/ns2hip.h"
 #include "ns2_kernels.h"
+#include "dropout_keep.h"
 
 namespace ns2 {
 
 void set_error(const char* fmt, ...);
+
+// The dropout fields of a C argument block (ns2_attn_args / ns2_attn_bwd_args) -> the drop_* fields of the kernels' block (AttnArgs /
+// AttnBwdArgs, whose defaults mean "none").  Returns what is wrong with them, or null.  p == 0: the seed is not read (may be null) and
+// the kernels without dropout run.
+template <class KernelArgs>
+inline const char* set_attn_dropout(KernelArgs& a, float p, const uint32_t* seed, unsigned call) {
+  if (!(p >= 0.f && p < 1.f)) return "dropout_p in [0, 1)";
+  if (p == 0.f) return nullptr;
+  if (!seed) return "dropout needs the seed words (device memory)";
+  a.drop_seed = seed; a.drop_thr = drop_threshold(p); a.drop_call = call; a.drop_scale = 1.0f / (1.0f - p);
+  return nullptr;
+}
 
 struct PackedW {                 // bf16 split-plane weight, rows padded to 128, K contiguous
   bf16_t* hi = nullptr; bf16_t* lo = nullptr;

@@ -114,19 +114,20 @@ size_t wavenet3_tiles_bytes(int rows_p, int dp, int nz, int phase);
 hipError_t wavenet3_build_tiles(const bf16_t* w_hi, int rows_p, int dp, int nz, bf16_t* t1, bf16_t* t2, hipStream_t s);                                                // activations' row length (elements) the kernel wants for Cp packed columns per tap
 constexpr long SPLITK_SCRATCH_FLOATS = 512L * 128 * 128;                // what any split needs at most: slices x output tiles <= 512 tiles of 128 x 128 (32 MiB)
 
-// flash attention forward, head dim 64, non-causal (ATT:77-155 hot path)
+// flash attention forward, head dim 64, non-causal (ATT:77-155 hot path).  Every field has a default: a default-constructed block is a
+// valid "nothing optional" block, and a caller names only what it uses (capi.cpp attn_args_from, model_exec.cpp attention_call)
 struct AttnArgs {
-  const bf16_t* q_hi; const bf16_t* q_lo; int ldq;     // [B*Nq, ldq], head h at columns q_col0 + 64h
-  const bf16_t* k_hi; const bf16_t* k_lo; int ldk;     // [B*Nk, ldk], head h at columns k_col0 + 64h
-  const bf16_t* vt_hi; const bf16_t* vt_lo; int vt_ld; // [B][H*64][vt_ld] transposed values
-  bf16_t* o_hi; bf16_t* o_lo; int ldo;                 // [B*Nq, ldo], head h at columns 64h
-  int o_fmt;                                           // PlaneFmt of o (-1: the operand format; FMT_H8 feeds a precision-4 GEMM)
-  int q_col0, k_col0;
-  int B, H, Nq, Nk;
-  int D;                                               // head dimension: 32, 64 or 128 (0 = 64); head h at columns col0 + D h, V^T rows H D per utterance
-  float scale;
-  const unsigned char* kmask;                            // optional key-padding mask [B, Nk], 1 = attend (ATT:92-94, 136-138)
-  float* lse;                                            // optional [B, H, Nq]: log2 of the softmax denominator of the SCALED scores
+  const bf16_t* q_hi = nullptr; const bf16_t* q_lo = nullptr; int ldq = 0;     // [B*Nq, ldq], head h at columns q_col0 + 64h
+  const bf16_t* k_hi = nullptr; const bf16_t* k_lo = nullptr; int ldk = 0;     // [B*Nk, ldk], head h at columns k_col0 + 64h
+  const bf16_t* vt_hi = nullptr; const bf16_t* vt_lo = nullptr; int vt_ld = 0; // [B][H*64][vt_ld] transposed values
+  bf16_t* o_hi = nullptr; bf16_t* o_lo = nullptr; int ldo = 0;                 // [B*Nq, ldo], head h at columns 64h
+  int o_fmt = -1;                                      // PlaneFmt of o (-1: the operand format; FMT_H8 feeds a precision-4 GEMM)
+  int q_col0 = 0, k_col0 = 0;
+  int B = 0, H = 0, Nq = 0, Nk = 0;
+  int D = 0;                                           // head dimension: 32, 64 or 128 (0 = 64); head h at columns col0 + D h, V^T rows H D per utterance
+  float scale = 0.f;
+  const unsigned char* kmask = nullptr;                  // optional key-padding mask [B, Nk], 1 = attend (ATT:92-94, 136-138)
+  float* lse = nullptr;                                  // optional [B, H, Nq]: log2 of the softmax denominator of the SCALED scores
                                                          // (m + log2 l), what the backward kernels recompute P from; null = not wanted
   // attention dropout of the training kernel (dropout_keep.h; needs lse and precision 3): drop_seed = two 32-bit words in DEVICE memory
   // (null = no dropout), drop_thr = round(p 2^32), drop_scale = 1 / (1 - p), drop_call = index of this attention inside the pass
@@ -301,23 +302,23 @@ int rmsnorm_bwd_slices(int seq_len);
 hipError_t launch_rmsnorm_bwd(const NormBwdArgs& a, hipStream_t s);
 hipError_t launch_attn_delta(const float* dO, long lddo, const bf16_t* o_hi, const bf16_t* o_lo, int ldo, int B, int H, int Nq, float* delta,
                              hipStream_t s, int o_fmt = 0);
-struct AttnBwdArgs {
-  const bf16_t* q_hi; const bf16_t* q_lo; int ldq, q_col0;        // [B*Nq, ldq], head h at columns q_col0 + 64 h
-  const bf16_t* k_hi; const bf16_t* k_lo; int ldk, k_col0;        // [B*Nk, ldk]
-  const bf16_t* v_hi; const bf16_t* v_lo; int ldv, v_col0;        // [B*Nk, ldv] values, ROW-major
-  const bf16_t* do_hi; const bf16_t* do_lo; int lddo;             // [B*Nq, lddo] gradient of the attention output, head h at 64 h
-  const float* lse; const float* delta;                           // [B, H, Nq]
-  float* dq; int lddq, dq_col0;                                   // fp32 outputs (null = not wanted; dk and dv come together)
-  float* dk; int lddk, dk_col0;
-  float* dv; int lddv, dv_col0;
-  int B, H, Nq, Nk; float scale;
+struct AttnBwdArgs {                                                // (every field defaulted, as in AttnArgs)
+  const bf16_t* q_hi = nullptr; const bf16_t* q_lo = nullptr; int ldq = 0, q_col0 = 0;    // [B*Nq, ldq], head h at columns q_col0 + 64 h
+  const bf16_t* k_hi = nullptr; const bf16_t* k_lo = nullptr; int ldk = 0, k_col0 = 0;    // [B*Nk, ldk]
+  const bf16_t* v_hi = nullptr; const bf16_t* v_lo = nullptr; int ldv = 0, v_col0 = 0;    // [B*Nk, ldv] values, ROW-major
+  const bf16_t* do_hi = nullptr; const bf16_t* do_lo = nullptr; int lddo = 0;             // [B*Nq, lddo] gradient of the attention output, head h at 64 h
+  const float* lse = nullptr; const float* delta = nullptr;                               // [B, H, Nq]
+  float* dq = nullptr; int lddq = 0, dq_col0 = 0;                                         // fp32 outputs (null = not wanted; dk and dv come together)
+  float* dk = nullptr; int lddk = 0, dk_col0 = 0;
+  float* dv = nullptr; int lddv = 0, dv_col0 = 0;
+  int B = 0, H = 0, Nq = 0, Nk = 0; float scale = 0.f;
   // round 5: the gradients as OPERAND PLANES instead of fp32 (what consumes dq | dk | dv of a self attention is the q | k | v projection's
   // dgrad and wgrad GEMMs, nothing else): gp planes [rows, gp_ld] in format gp_fmt (FMT_BF16 hi / lo lines or FMT_H8), dq at columns
   // dq_col0 + 64 h of row b Nq + q, dk / dv at dk_col0 / dv_col0 of row b Nk + k; gp_q / gp_kv say which halves go there
-  bf16_t* gp_hi; bf16_t* gp_lo; int gp_ld, gp_fmt, gp_q, gp_kv;
+  bf16_t* gp_hi = nullptr; bf16_t* gp_lo = nullptr; int gp_ld = 0, gp_fmt = 0, gp_q = 0, gp_kv = 0;
   // the encoders' training pass: key-padding mask [B, Nk] (1 = attend; null = none) and attention dropout as in AttnArgs (drop_seed null =
   // none).  Either one selects the MD instantiations of the kernel; without them the kernels of the denoiser's pass run, unchanged.
-  const unsigned char* kmask; const uint32_t* drop_seed; uint32_t drop_thr, drop_call; float drop_scale;
+  const unsigned char* kmask = nullptr; const uint32_t* drop_seed = nullptr; uint32_t drop_thr = 0u, drop_call = 0u; float drop_scale = 1.f;
 };
 hipError_t launch_attention_bwd(const AttnBwdArgs& a, hipStream_t s);
 

@@ -241,21 +241,33 @@ def wavenet_block(w: PackedWeight, a: Planes, seq_len: int, dilation: int, conv_
     return out
 
 
+def _attention_fwd(q: Planes, q_col0, k: Planes, k_col0, vt_hi, vt_lo, vt_ld, B, H, Nq, Nk, scale, precision, head_dim=64, o_precision=0,
+                   key_mask=None, want_lse=False, drop=None):
+    """The one place that fills a ns2_attn_args (include/ns2hip.h) and calls ns2_attention_fwd -> (o, lse or None).  vt_hi / vt_lo:
+    device addresses of the transposed value planes; o_precision: the format of o when it is not the operands' (0 = `precision`);
+    key_mask: uint8 [B, Nk] on the device; drop = (p, seed tensor on the device, call index) or None."""
+    o = _out_planes(B * Nq, H * head_dim, q.device, o_precision or precision)
+    lse = torch.empty(B, H, Nq, dtype=torch.float32, device=q.device) if want_lse else None
+    p, seed, call = drop if drop is not None else (0.0, None, 0)
+    a = _lib.AttnArgs(q_hi=q.hi, q_lo=q.lo, ldq=q.ld, q_col0=q_col0, k_hi=k.hi, k_lo=k.lo, ldk=k.ld, k_col0=k_col0,
+                      vt_hi=vt_hi, vt_lo=vt_lo, vt_ld=vt_ld, o_hi=o.hi, o_lo=o.lo, ldo=o.ld, B=B, H=H, Nq=Nq, Nk=Nk, scale=scale,
+                      head_dim=head_dim, precision=precision, o_precision=o_precision, key_mask=_p(key_mask), lse=_p(lse),
+                      dropout_p=p, dropout_seed=_p(seed), dropout_call=call)
+    check(_lib.load().ns2_attention_fwd(a, _stream()), "ns2_attention_fwd")
+    return o, lse
+
+
 def attention(q: Planes, k: Planes, vt: Planes, B: int, H: int, Nq: int, Nk: int, q_col0=0, k_col0=0, scale=None,
               precision=3, key_mask: Optional[torch.Tensor] = None, head_dim: int = 64) -> Planes:
     """vt: transposed value planes [B * H*head_dim, vt_ld]; key_mask: optional bool/uint8 [B, Nk], True = attend (ATT:92-94);
     head_dim 32 / 64 / 128, scale defaults to head_dim ** -0.5 (ATT:128)."""
     if scale is None:
         scale = head_dim ** -0.5
-    out = _out_planes(B * Nq, H * head_dim, q.device, precision)
     km = None
     if key_mask is not None:
         km = key_mask.to(torch.uint8).contiguous()
         assert km.shape == (B, Nk)
-    check(_lib.load().ns2_attention_hd(q.hi, q.lo, q.ld, q_col0, k.hi, k.lo, k.ld,
-                                       k_col0, vt.hi, vt.lo, vt.ld, out.hi, out.lo,
-                                       H * head_dim, B, H, Nq, Nk, scale, _p(km), precision, head_dim, _stream()), "ns2_attention_hd")
-    return out
+    return _attention_fwd(q, q_col0, k, k_col0, vt.hi, vt.lo, vt.ld, B, H, Nq, Nk, scale, precision, head_dim=head_dim, key_mask=km)[0]
 
 
 def rmsnorm(x: torch.Tensor, seq_len: int = 0, gamma=None, cond=None, want_f32=False, precision: int = 3):

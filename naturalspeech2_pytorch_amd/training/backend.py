@@ -1,6 +1,4 @@
 """The ctypes backend: every method of `HipBackend` = launches of libns2hip on the current stream (C ABI: include/ns2hip.h "training")"""
-import ctypes
-
 import torch
 
 from .. import _lib, ops
@@ -92,23 +90,15 @@ class HipBackend:
 
     def attention(self, q, q_col0, k, k_col0, vt, B, H, Nq, Nk):
         """bf16 x3 products on bf16 operands; the output o (the out-projection's operand) in the GEMM format"""
-        o = ops._out_planes(B * Nq, H * 64, q.device, self.prec)
-        lse = torch.empty(B, H, Nq, dtype=torch.float32, device=q.device)
-        check(self.lib.ns2_attention_lse(q.hi, q.lo, q.ld, q_col0, k.hi, k.lo, k.ld, k_col0, vt.ptr(), vt.ptr() + 64, vt.ld, o.hi, o.lo, H * 64,
-                                         B, H, Nq, Nk, 0.125, lse.data_ptr(), 3, self.prec, _stream()), "ns2_attention_lse")
-        return o, lse
+        return ops._attention_fwd(q, q_col0, k, k_col0, vt.ptr(), vt.ptr() + 64, vt.ld, B, H, Nq, Nk, 0.125, 3, o_precision=self.prec,
+                                  want_lse=True)
 
     def attention_masked(self, q, q_col0, k, k_col0, vt, B, H, Nq, Nk, kmask=None, drop=None):
         """`attention` with a key-padding mask (uint8 [B, Nk], 1 = attend) and / or dropout on P (`drop` = (p, seed tensor on the device, call
         index): csrc/dropout_keep.h) -- the attention of the conditioning encoders' training pass"""
         assert self.prec == 3, "the encoders train in the exact arithmetic"
-        o = ops._out_planes(B * Nq, H * 64, q.device, self.prec)
-        lse = torch.empty(B, H, Nq, dtype=torch.float32, device=q.device)
-        p, seed, call = drop if drop is not None else (0.0, None, 0)
-        check(self.lib.ns2_attention_lse_masked(q.hi, q.lo, q.ld, q_col0, k.hi, k.lo, k.ld, k_col0, vt.ptr(), vt.ptr() + 64, vt.ld, o.hi, o.lo, H * 64,
-                                                B, H, Nq, Nk, 0.125, lse.data_ptr(), 3, self.prec, _p(kmask), p, _p(seed), call, _stream()),
-              "ns2_attention_lse_masked")
-        return o, lse
+        return ops._attention_fwd(q, q_col0, k, k_col0, vt.ptr(), vt.ptr() + 64, vt.ld, B, H, Nq, Nk, 0.125, 3, o_precision=self.prec,
+                                  key_mask=kmask, want_lse=True, drop=drop)
 
     def dropout_keep_mask(self, seed, call, p, B, H, Nq, Nk):
         """debugging / tests: the keep mask the training attention kernels apply for these arguments, uint8 [B, H, Nq, Nk]"""
@@ -327,12 +317,14 @@ class HipBackend:
 
     def attention_bwd_masked(self, *args, kmask=None, drop=None, **kw):
         """`attention_bwd` of a forward that ran `attention_masked` with the same `kmask` / `drop`"""
-        self.attention_bwd(*args, **kw, _masked=(kmask, drop))
+        self.attention_bwd(*args, **kw, kmask=kmask, drop=drop)
 
-    def attention_bwd(self, q, q_col0, k, k_col0, v, v_col0, do_row, lse, delta, B, H, Nq, Nk, dq=None, dkv=None, planes=None, _masked=None):
+    def attention_bwd(self, q, q_col0, k, k_col0, v, v_col0, do_row, lse, delta, B, H, Nq, Nk, dq=None, dkv=None, planes=None, kmask=None,
+                      drop=None):
         """dq: (fp32 tensor [B*Nq, ld], col0) or None; dkv: (tensor [B*Nk, ld], k col0, v col0) or None;
         planes: (operand planes [B*N, ld], dq col0, dk col0, dv col0) -- self attention: the three gradients leave the kernels as the
-        operand of the q | k | v projection's dgrad / wgrad GEMMs instead of fp32 + a conversion pass"""
+        operand of the q | k | v projection's dgrad / wgrad GEMMs instead of fp32 + a conversion pass;
+        kmask / drop: what the forward (`attention_masked`) got, None = neither"""
         a = _lib.AttnBwdArgs()
         a.q_hi, a.q_lo, a.ldq, a.q_col0 = q.hi, q.lo, q.ld, q_col0
         a.k_hi, a.k_lo, a.ldk, a.k_col0 = k.hi, k.lo, k.ld, k_col0
@@ -349,9 +341,7 @@ class HipBackend:
             assert gp.precision == self.prec
             a.gp_hi, a.gp_lo, a.gp_ld, a.gp_precision, a.gp_q, a.gp_kv = gp.hi, gp.lo, gp.ld, self.prec, 1, 1
         a.B, a.H, a.Nq, a.Nk, a.scale = B, H, Nq, Nk, 0.125
-        if _masked is not None:
-            kmask, drop = _masked
-            p, seed, call = drop if drop is not None else (0.0, None, 0)
-            check(self.lib.ns2_attention_bwd_masked(ctypes.byref(a), _p(kmask), p, _p(seed), call, _stream()), "ns2_attention_bwd_masked")
-            return
-        check(self.lib.ns2_attention_bwd(ctypes.byref(a), _stream()), "ns2_attention_bwd")
+        a.key_mask = _p(kmask)
+        if drop is not None:
+            a.dropout_p, a.dropout_seed, a.dropout_call = drop[0], _p(drop[1]), drop[2]
+        check(self.lib.ns2_attention_bwd(a, _stream()), "ns2_attention_bwd")

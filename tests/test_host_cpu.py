@@ -92,13 +92,14 @@ def test_header_is_plain_c_and_a_c_caller_links_against_the_library(tmp_path):
     src = tmp_path / "caller.c"
     src.write_text(r'''
 #include <stdio.h>
+#include <stddef.h>
 #include <stdint.h>
 #include "ns2hip.h"
 int main(void) {
   /* addresses of entry points from every section of the header: unresolved symbols fail the link */
   typedef void (*fn_t)(void);
-  fn_t fns[] = {(fn_t)ns2_weight_pack, (fn_t)ns2_linear_f32, (fn_t)ns2_linear_qkv, (fn_t)ns2_attention,
-                       (fn_t)ns2_attention_hd, (fn_t)ns2_rmsnorm, (fn_t)ns2_rvq_encode, (fn_t)ns2_model_create,
+  fn_t fns[] = {(fn_t)ns2_weight_pack, (fn_t)ns2_linear_f32, (fn_t)ns2_linear_qkv, (fn_t)ns2_attention_fwd,
+                       (fn_t)ns2_rmsnorm, (fn_t)ns2_rvq_encode, (fn_t)ns2_model_create,
                        (fn_t)ns2_model_forward, (fn_t)ns2_ddim_step, (fn_t)ns2_weights_repack, (fn_t)ns2_weights_retile,
                        (fn_t)ns2_attention_bwd, (fn_t)ns2_weight_tile_linear, (fn_t)ns2_model_cond_stack};
   int n = 0;
@@ -106,6 +107,14 @@ int main(void) {
   ns2_model_config cfg;                       /* the config struct is plain ints */
   cfg.dim = 64; cfg.depth = 1; cfg.dim_head = 48; cfg.heads = 2;
   printf("%d %d %d %d\n", n, ns2_version(), ns2_conv3_input_ld(1365), (int)sizeof(cfg) % (int)sizeof(int));
+  /* the layout of the two attention argument blocks, for the ctypes mirrors: size, then offsets of a field of each kind */
+#define OFF(t, f) (int)offsetof(t, f)
+  printf("%d %d %d %d %d %d %d %d %d %d %d\n", (int)sizeof(ns2_attn_args), OFF(ns2_attn_args, q_lo), OFF(ns2_attn_args, k_hi),
+         OFF(ns2_attn_args, o_hi), OFF(ns2_attn_args, scale), OFF(ns2_attn_args, head_dim), OFF(ns2_attn_args, key_mask),
+         OFF(ns2_attn_args, lse), OFF(ns2_attn_args, dropout_p), OFF(ns2_attn_args, dropout_seed), OFF(ns2_attn_args, dropout_call));
+  printf("%d %d %d %d %d %d %d %d %d %d\n", (int)sizeof(ns2_attn_bwd_args), OFF(ns2_attn_bwd_args, k_hi), OFF(ns2_attn_bwd_args, lse),
+         OFF(ns2_attn_bwd_args, dq), OFF(ns2_attn_bwd_args, scale), OFF(ns2_attn_bwd_args, gp_hi), OFF(ns2_attn_bwd_args, gp_kv),
+         OFF(ns2_attn_bwd_args, key_mask), OFF(ns2_attn_bwd_args, dropout_p), OFF(ns2_attn_bwd_args, dropout_call));
   return ns2_debug_force_gemm(99) == 0;       /* argument errors come back as codes, nothing throws across the ABI */
 }
 ''')
@@ -115,7 +124,46 @@ int main(void) {
     subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-pedantic", "-I", inc, "-fsyntax-only", str(src)], check=True)
     subprocess.run(["gcc", "-std=c99", "-I", inc, str(src), "-o", str(exe), "-L", libdir, "-lns2hip", "-Wl,-rpath," + libdir], check=True)
     out = subprocess.run([str(exe)], check=True, capture_output=True, text=True, timeout=120).stdout.split()
-    assert out[0] == "15" and int(out[1]) >= 115 and int(out[2]) == 1408 and out[3] == "0", out
+    assert out[0] == "14" and int(out[1]) >= 115 and int(out[2]) == 1408 and out[3] == "0", out
+    # ... and the ctypes mirrors of the two attention argument blocks have the header's layout: same size, same field offsets
+    import ctypes
+
+    def layout(cls, fields):
+        return [ctypes.sizeof(cls)] + [getattr(cls, f).offset for f in fields]
+    fwd = layout(_lib.AttnArgs, ("q_lo", "k_hi", "o_hi", "scale", "head_dim", "key_mask", "lse", "dropout_p", "dropout_seed", "dropout_call"))
+    bwd = layout(_lib.AttnBwdArgs, ("k_hi", "lse", "dq", "scale", "gp_hi", "gp_kv", "key_mask", "dropout_p", "dropout_call"))
+    assert [int(v) for v in out[4:4 + len(fwd)]] == fwd, (out, fwd)
+    assert [int(v) for v in out[4 + len(fwd):]] == bwd and len(out) == 4 + len(fwd) + len(bwd), (out, bwd)
+
+
+def test_attention_entries_refuse_bad_argument_blocks_before_any_device_call():
+    """ns2_attention_fwd / ns2_attention_bwd validate their argument block on the host: each of these comes back as a non-zero code with a
+    message, and never reaches a HIP call (no GPU here; the dummy pointers are never dereferenced)."""
+    import ctypes
+    lib = _lib.load()
+
+    def fwd(**kw):
+        f = dict(q_hi=64, k_hi=128, vt_hi=192, o_hi=256, q_lo=96, k_lo=160, vt_lo=224, o_lo=288, ldq=64, ldk=64, vt_ld=64, ldo=64,
+                 B=1, H=1, Nq=8, Nk=8, scale=0.125, precision=3)
+        f.update(kw)
+        return _lib.AttnArgs(**f)
+
+    def refused(rc, entry, word):
+        """a non-zero code, and the message is this refusal's own (the last error is sticky: a stale one would not name `word`)"""
+        msg = (lib.ns2_last_error() or b"").decode()
+        return rc != 0 and msg.startswith(entry) and word in msg
+
+    assert refused(lib.ns2_attention_fwd(None, None), "ns2_attention_fwd", "null")
+    assert refused(lib.ns2_attention_fwd(fwd(head_dim=48), None), "ns2_attention_fwd", "head_dim must be")
+    assert refused(lib.ns2_attention_fwd(fwd(lse=512, head_dim=32), None), "ns2_attention_fwd", "lse needs")
+    assert refused(lib.ns2_attention_fwd(fwd(lse=512, precision=2), None), "ns2_attention_fwd", "lse needs")
+    assert refused(lib.ns2_attention_fwd(fwd(lse=512, dropout_p=0.2), None), "ns2_attention_fwd", "seed")
+    assert refused(lib.ns2_attention_fwd(fwd(dropout_p=0.2, dropout_seed=1024), None), "ns2_attention_fwd", "dropout needs lse")
+    assert refused(lib.ns2_attention_fwd(fwd(lse=512, dropout_p=1.0, dropout_seed=1024), None), "ns2_attention_fwd", "[0, 1)")
+    assert refused(lib.ns2_attention_bwd(None, None), "ns2_attention_bwd", "null")
+    bwd = _lib.AttnBwdArgs(q_hi=64, q_lo=96, k_hi=128, k_lo=160, v_hi=192, v_lo=224, do_hi=256, do_lo=288, lse=512, delta=768, dq=1024,
+                           ldq=64, ldk=64, ldv=64, lddo=64, lddq=64, B=1, H=1, Nq=8, Nk=8, scale=0.125, dropout_p=0.2)
+    assert refused(lib.ns2_attention_bwd(bwd, None), "ns2_attention_bwd", "seed")
 
 
 def test_transformer_state_dict_contract():
