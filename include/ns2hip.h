@@ -510,7 +510,9 @@ int ns2_film_gate_bwd(const float* dg, int64_t lddg, const float* h, int64_t ldh
 int ns2_geglu_fwd(const float* pre, int64_t ldp, int64_t M, int f, uint16_t* out_hi, uint16_t* out_lo, int ldo, int precision, void* stream);
 int ns2_geglu_bwd(const float* dh, int64_t lddh, const float* pre, int64_t ldp, int64_t M, int f, float* dpre, int64_t lddp, void* stream);
 /* RMSNorm backward (NS2:727-746): dx = (dx_add ? dx_add : 0) + dL/dx (dx may alias dx_add: the residual stream's gradient);
- * cond_partial [B * slices][2 d] -> the adaptive (gamma_c, beta_c) gradients, gamma_partial [B * slices][d] -> the learned gamma's */
+ * cond_partial [B * slices][2 d] -> the adaptive (gamma_c, beta_c) gradients, gamma_partial [B * slices][d] -> the learned gamma's.
+ * d: a multiple of 4, at most 2048; the leading dimensions multiples of 4.  A workgroup keeps 12 d floats in dynamic LDS: beyond
+ * d = 1365 that is more than 64 KiB (96 KiB at d = 2048), and the launcher raises the kernel's dynamic-LDS limit before it launches. */
 int ns2_rmsnorm_bwd_slices(int seq_len);
 int ns2_rmsnorm_bwd(const float* x, int64_t ldx, const float* dy, int64_t lddy, const float* gamma, const float* cond, int cond_ld, int B,
                     int seq_len, int d, const float* dx_add, float* dx, int64_t lddx, float* cond_partial, float* gamma_partial, void* stream);
