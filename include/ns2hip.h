@@ -31,7 +31,7 @@
  *     x_lo == NULL: the dense [rows, ld] hi plane alone (precision 1: bf16, precision 2: IEEE half).
  *     precision 4 operands use the interleaved form with the line [half(32) | e5m2(x)(32 B) | e5m2((x-half(x))*2^12)(32 B)]
  *       (x_lo == x_hi + 32 as above); the operands of ns2_attention_fwd (q, k, transposed values) are dense IEEE half at
- *       precision 4, which is also what ns2_linear_qkv writes there.
+ *       precision 4, which is also what the fused q | k | v form of ns2_linear writes there.
  *     Transposed value planes (vt_hi, vt_lo, vt_ld) use the same rule along the key axis.
  */
 #ifndef NS2HIP_H
@@ -94,22 +94,42 @@ int ns2_split_f32(const float* x, int ldx, int M, int d, uint16_t* out_hi, uint1
 int ns2_join_f32(const uint16_t* hi, const uint16_t* lo, int ld, float* out, int ldo, int64_t M, int d, int precision,
                  void* stream);
 
-/* nn.Linear / CausalConv1d as one GEMM (NS2:1051-1069, 1021-1024, 583-595).
- * conv_taps = 0 for a Linear, k for a Conv1d(kernel k) with `dilation`; seq_len = tokens per utterance (rows never read
- * across utterances); pad_left = zero frames in front of the sequence: -1 = causal (k-1, CausalConv1d NS2:583-595),
- * (k-1)/2 = the "same" padding of SpeechPromptEncoder's convs (NS2:316).  act: 0 none, 1 SiLU, 2 ELU (after the bias).
- * out = act(A W^T + bias) (+ resid), fp32 */
-int ns2_linear_f32(const ns2_weight* w, const uint16_t* a_hi, const uint16_t* a_lo, int lda, int M, int conv_taps,
-                   int dilation, int seq_len, const float* bias, const float* resid, int ldr, float* out, int ldo,
-                   int pad_left, int act, int precision, void* stream);
-/* same, output as split planes [M, ldo] */
-int ns2_linear_split(const ns2_weight* w, const uint16_t* a_hi, const uint16_t* a_lo, int lda, int M, int conv_taps,
-                     int dilation, int seq_len, const float* bias, uint16_t* out_hi, uint16_t* out_lo, int ldo,
-                     int pad_left, int act, int precision, void* stream);
+/* nn.Linear / Conv1d as one GEMM (NS2:1051-1069, 1021-1024, 583-595): out = act(A W^T + bias) (+ resid).  ONE argument block describes
+ * the call; a zero-initialised block plus `w`, the operand planes, `M`, `precision` and one output is the plain Linear, and every other
+ * field switches one feature on:
+ *   w, a, M    the packed weight; the activation planes [M, lda] in the operand format of `precision` (1 .. 4, see the conventions
+ *              above), lda >= the weight's columns padded to 32.
+ *   conv_taps  0 for a Linear, k for a Conv1d(kernel k) with `dilation`; seq_len = tokens per utterance (rows are never read across
+ *              utterances); pad_left = zero frames in front of the sequence: -1 = causal (k - 1, CausalConv1d NS2:583-595), (k - 1) / 2 =
+ *              the "same" padding of SpeechPromptEncoder's convs (NS2:316).  A zeroed block says 0, not causal: conv callers always set it.
+ *   bias, act  bias [rows] (NULL = none); act after the bias: 0 none, 1 SiLU, 2 ELU.
+ *   output     exactly one of  out_f32 [M, ldo_f] fp32, with the optional addend resid [M, ldr];
+ *                              out_hi / out_lo [M, ldo] planes (ldo even), in the operand format of out_precision (0 = as `precision`;
+ *              e.g. 3: bf16 hi / lo lines from a precision-4 product -- the q | k | v projection of the mixed training arithmetic, whose
+ *              attention stays bf16 x3; out_lo NULL for dense IEEE half, hi + 32 for interleaved lines).
+ *   vt_hi      non-NULL selects the fused q / k / v projection (NS2:1051-1053, 1063): columns < split_col -> the planes out [M, ldo],
+ *              columns >= split_col (the values) -> transposed planes vt[b][col - split_col][n] with row stride vt_ld >= seq_len (for
+ *              ns2_attention_fwd; both in the attention operands' format).  Needs seq_len; excludes bias, act, conv_taps, out_precision.
+ *   GEGLU      selected by the weight having been packed with geglu = 1: FeedForward's first half GEGLU(Linear(x)) (NS2:1004-1007, 1021).
+ *              bias is then the packed bias of ns2_geglu_pack_bias and required; out planes [M, ldo] with ldo = round_up(f, 32); excludes
+ *              conv_taps, act, out_f32, vt_hi, out_precision.
+ * Every refusal is an NS2_ERR_ARG whose message starts "ns2_linear:" and names the field, made before any device call. */
+typedef struct {
+  const ns2_weight* w;
+  const uint16_t* a_hi; const uint16_t* a_lo; int lda;
+  int M, precision;
+  int conv_taps, dilation, seq_len, pad_left;
+  const float* bias; int act;
+  float* out_f32; int ldo_f; const float* resid; int ldr;
+  uint16_t* out_hi; uint16_t* out_lo; int ldo, out_precision;
+  int split_col; uint16_t* vt_hi; uint16_t* vt_lo; int vt_ld;
+} ns2_linear_args;
+int ns2_linear(const ns2_linear_args* args, void* stream);
+int ns2_geglu_pack_bias(const float* bias, int f, float* packed, int packed_len, void* stream);
 /* The feed-forward causal conv (CausalConv1d(f, f, 3), NS2:1016 / 583-595) as one IEEE-half product has a kernel of its own
  * (csrc/ffconv_kernel.h).  It reads the weight as pre-tiled LDS images: ns2_weight_tile_conv3 builds them for a weight packed with
  * taps = 3 at precision 2 (one-time set-up, allocates once; ns2_weight_update keeps them current; after ns2_weights_repack call
- * ns2_weights_retile).  A later ns2_linear_split / ns2_linear_split_as call with that weight takes the kernel when: conv_taps = 3,
+ * ns2_weights_retile).  A later ns2_linear call with that weight and plane output takes the kernel when: conv_taps = 3,
  * dilation = 1, pad_left = -1, act = 0, M % 256 == 0, seq_len % 256 == 0, lda == ns2_conv3_input_ld(cols) (dense half rows padded to
  * a multiple of 128 columns; the padding is never multiplied), output dense half or FMT_H8 lines.  Results are bit-identical to the
  * general kernel's (same products, same summation order).  ns2_model_finalize does all of this for precisions 2 / 5 / 6. */
@@ -117,28 +137,13 @@ int ns2_weight_tile_conv3(ns2_weight* w, void* stream);
 int ns2_conv3_input_ld(int cols);
 /* The mixed linear products (precision 4, FMT_H8 operands) on full 256-row tiles have a lean kernel too (csrc/gemm3_kernel.h): same
  * arithmetic and summation order as the general kernel (bit-identical results), weights read as pre-tiled LDS images.
- * ns2_weight_tile_linear builds them for a weight packed with taps = 1 at precision 4 (also with geglu = 1); ns2_linear_f32 / _split /
- * _split_as / _qkv / _geglu then take the kernel when M % 256 == 0 and K >= 96.  Same life-cycle rules as ns2_weight_tile_conv3. */
+ * ns2_weight_tile_linear builds them for a weight packed with taps = 1 at precision 4 (also with geglu = 1); ns2_linear then takes the
+ * kernel, whatever the output, when M % 256 == 0 and K >= 96.  Same life-cycle rules as ns2_weight_tile_conv3. */
 int ns2_weight_tile_linear(ns2_weight* w, void* stream);
 /* ... and so has the WavenetResBlock of the hybrid plan (csrc/wavenet3_kernel.h; NS2:597-642): ns2_weight_tile_wavenet builds the tiled
  * images of a weight packed with taps = 3 and extra1x1 at precision 4 (square, channels % 256 == 0); ns2_wavenet_block at precision 5
  * then takes the lean kernel when M % 256 == 0, seq_len % 256 == 0 and dilation <= 128.  Bit-identical to the general kernel. */
 int ns2_weight_tile_wavenet(ns2_weight* w, void* stream);
-/* same, with the output planes in the format of ANOTHER precision (out_precision 3: bf16 hi / lo lines from a precision-4 product --
- * the q | k | v projection of the mixed training arithmetic, whose attention stays bf16 x3) */
-int ns2_linear_split_as(const ns2_weight* w, const uint16_t* a_hi, const uint16_t* a_lo, int lda, int M, int conv_taps,
-                        int dilation, int seq_len, const float* bias, uint16_t* out_hi, uint16_t* out_lo, int ldo,
-                        int pad_left, int act, int precision, int out_precision, void* stream);
-/* FeedForward first half: GEGLU(Linear(x)) (NS2:1004-1007, 1021); w packed with geglu=1; packed_bias from
- * ns2_geglu_pack_bias; out planes [M, ldo] with ldo = round_up(f, 32) */
-int ns2_linear_geglu(const ns2_weight* w, const uint16_t* a_hi, const uint16_t* a_lo, int lda, int M,
-                     const float* packed_bias, uint16_t* out_hi, uint16_t* out_lo, int ldo, int precision, void* stream);
-int ns2_geglu_pack_bias(const float* bias, int f, float* packed, int packed_len, void* stream);
-/* fused q/k/v projection (NS2:1051-1053, 1063): columns < split_col -> planes [M, ldo]; columns >= split_col
- * (the values) -> transposed planes vt[b][col - split_col][n] with row stride vt_ld (for ns2_attention_fwd) */
-int ns2_linear_qkv(const ns2_weight* w, const uint16_t* a_hi, const uint16_t* a_lo, int lda, int M, int seq_len,
-                   int split_col, uint16_t* out_hi, uint16_t* out_lo, int ldo, uint16_t* vt_hi, uint16_t* vt_lo,
-                   int vt_ld, int precision, void* stream);
 /* WavenetResBlock (NS2:597-642) in one launch: out = tanh(g)*sigmoid(g) + res_conv(x), g = conv_dil(x)*gamma_t+beta_t.
  * w packed with taps=3 and extra1x1 = res_conv.weight; film[b] = [gamma(dim) | beta(dim)] = to_time_cond(t).
  * precision 5 (this entry point only): precision-4 operands and weight; the dilated conv multiplies their IEEE-half parts as
@@ -150,7 +155,7 @@ int ns2_wavenet_block(const ns2_weight* w, const uint16_t* a_hi, const uint16_t*
 /* Attend.forward (ATT:77-155), non-causal: o = softmax(q k^T * scale) v.  ONE argument block describes the call; a zero-initialised
  * block plus the planes, the sizes, `scale` and `precision` is the plain forward, and every other field switches one feature on:
  *   q / k      row-major planes [B * Nq, ldq] / [B * Nk, ldk]; head h at columns col0 + h * head_dim.
- *   vt         transposed value planes [B][H * head_dim][vt_ld] (what ns2_linear_qkv writes); o [B * Nq, ldo], head h at h * head_dim.
+ *   vt         transposed value planes [B][H * head_dim][vt_ld] (what ns2_linear writes with vt_hi set); o [B * Nq, ldo], head h at h * head_dim.
  *   head_dim   32, 64 or 128 (0 = 64): the reference's `dim_head` keyword (NS2:814-831 -> Attention ATT:77-155); scale is the
  *              caller's (dim_head ** -0.5).
  *   precision  1..4, the format of the operand planes (see the conventions above).  o_precision: the format of the output planes
@@ -200,7 +205,7 @@ int ns2_transpose_f32(const float* in, int batch, int R, int C, float* out, void
 int ns2_embedding(const int64_t* ids, const float* table, float* out, int64_t n, int dim, int64_t pad_id, void* stream);
 
 /* ------------------------------------------------------------------ DurationPitchPredictor and text-conditioned sampling
- * (NS2:344-527, 87-104, 164-175, 1449-1455, 1476-1483).  The trunk's convolutions are ns2_linear_* calls (conv_taps = k,
+ * (NS2:344-527, 87-104, 164-175, 1449-1455, 1476-1483).  The trunk's convolutions are ns2_linear calls (conv_taps = k,
  * pad_left = k / 2), its RMSNorm and attention the entries above; these are the pieces around them.
  * ns2_groupnorm_silu: nn.GroupNorm(groups, C) + SiLU (Block, NS2:346-369) over token-major fp32 rows x [B * n, C], statistics
  * per (utterance, group) over n x C / groups values, eps as given; resid (may be null) [B * n, C] is added after the SiLU (the
@@ -272,7 +277,7 @@ int ns2_ddim_step(const float* audio, const float* model_out, float* out, const 
 int ns2_cfg_mix(const float* cond_out, const float* null_out, float* out, int64_t n, float cond_scale, void* stream);
 
 /* ------------------------------------------------------------------ EnCodec SEANet encoder / decoder pieces (HFENC:81-347)
- * The convolutions themselves are ns2_linear_* calls on channel-last rows (strided / transposed convolutions as 2-tap
+ * The convolutions themselves are ns2_linear calls on channel-last rows (strided / transposed convolutions as 2-tap
  * convolutions over rows regrouped by the stride); these are the pieces around them.
  * ns2_seanet_prep: fp32 x [B, in_prefix + T, C] (row stride ldx, the first in_prefix rows of every utterance skipped;
  *   + optional add [B, T, C]) -> optional ELU (HFENC:285-347) -> operand
@@ -433,9 +438,9 @@ void ns2_model_destroy(ns2_model* m);
  *       stops at 65504 and loses precision below 6e-5, so the caller scales the loss (a power of two; every gradient is linear in
  *       it) -- the reference trains under accelerate's fp16 mixed precision the same way (NS2:1710-1711, 1723-1726).  Values that
  *       leave the half range are counted (ns2_saturation_count, ns2_saturation_peek): an overflowed step is detected, not silently clamped.
- *       The attention products stay bf16 x3 at both precisions (q / k / v / dO planes are bf16 hi / lo: ns2_linear_split_as).
+ *       The attention products stay bf16 x3 at both precisions (q / k / v / dO planes are bf16 hi / lo: ns2_linear with out_precision = 3).
  * The contractions reuse the forward GEMM family:
- *   dgrad  dX = dY W   : ns2_linear_f32 on a SECOND pack of the weight -- ns2_weight_pack of W^T ([in, out, taps] with the taps
+ *   dgrad  dX = dY W   : ns2_linear (fp32 output) on a SECOND pack of the weight -- ns2_weight_pack of W^T ([in, out, taps] with the taps
  *                        flipped), conv_taps as in the forward, pad_left = 0 (the gradient of a causal conv looks ahead);
  *   wgrad  dW = dY^T X : ns2_wgrad on TRANSPOSED planes (contraction over the tokens), split over fixed slots + fixed-order sum.
  * Every reduction of this section is slot based and summed in a fixed order: gradients are deterministic, no atomics. */

@@ -27,6 +27,16 @@ F = c_float
 L = c_int64
 
 
+class LinearArgs(ctypes.Structure):
+    """ns2_linear_args (include/ns2hip.h), field for field"""
+    _fields_ = [("w", P), ("a_hi", P), ("a_lo", P), ("lda", I), ("M", I), ("precision", I),
+                ("conv_taps", I), ("dilation", I), ("seq_len", I), ("pad_left", I),
+                ("bias", P), ("act", I),
+                ("out_f32", P), ("ldo_f", I), ("resid", P), ("ldr", I),
+                ("out_hi", P), ("out_lo", P), ("ldo", I), ("out_precision", I),
+                ("split_col", I), ("vt_hi", P), ("vt_lo", P), ("vt_ld", I)]
+
+
 class AttnArgs(ctypes.Structure):
     """ns2_attn_args (include/ns2hip.h), field for field"""
     _fields_ = [("q_hi", P), ("q_lo", P), ("ldq", I), ("q_col0", I),
@@ -74,12 +84,8 @@ SIGNATURES = {
     "ns2_weight_free": (None, [P]),
     "ns2_split_f32": (I, [P, I, I, I, P, P, I, I, P]),
     "ns2_join_f32": (I, [P, P, I, P, I, L, I, I, P]),
-    "ns2_linear_f32": (I, [P, P, P, I, I, I, I, I, P, P, I, P, I, I, I, I, P]),
-    "ns2_linear_split": (I, [P, P, P, I, I, I, I, I, P, P, P, I, I, I, I, P]),
-    "ns2_linear_split_as": (I, [P, P, P, I, I, I, I, I, P, P, P, I, I, I, I, I, P]),
-    "ns2_linear_geglu": (I, [P, P, P, I, I, P, P, P, I, I, P]),
+    "ns2_linear": (I, [POINTER(LinearArgs), P]),
     "ns2_geglu_pack_bias": (I, [P, I, P, I, P]),
-    "ns2_linear_qkv": (I, [P, P, P, I, I, I, I, P, P, I, P, P, I, I, P]),
     "ns2_wavenet_block": (I, [P, P, P, I, I, I, I, P, P, P, I, P, P, I, I, P]),
     "ns2_attention_fwd": (I, [POINTER(AttnArgs), P]),
     "ns2_rmsnorm": (I, [P, I, I, I, I, P, P, I, P, P, I, P, I, I, P]),

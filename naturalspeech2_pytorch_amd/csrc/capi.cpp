@@ -45,26 +45,10 @@ const SatCounter* sat_counters(int* n) {
 using namespace ns2;
 
 
-#define HIPRET(expr)                                                                 \
-  do {                                                                               \
-    hipError_t _e = (expr);                                                          \
-    if (_e != hipSuccess) {                                                          \
-      set_error("%s:%d %s -> %s", __FILE__, __LINE__, #expr, hipGetErrorString(_e)); \
-      return NS2_ERR_HIP;                                                            \
-    }                                                                                \
-  } while (0)
-#define ARGCHK(cond, msg)            \
-  do {                               \
-    if (!(cond)) {                   \
-      set_error("%s", msg);          \
-      return NS2_ERR_ARG;            \
-    }                                \
-  } while (0)
 static inline int prec_ok(int p) { return p >= 1 && p <= 4; }
-static inline int op_fmt(int p) { return p == 2 ? FMT_F16 : (p == 4 ? FMT_H8 : FMT_BF16); }
 
 extern "C" const char* ns2_last_error(void) { return g_err; }
-extern "C" int ns2_version(void) { return 119; }   // 119: one argument block per attention direction: ns2_attention_fwd(ns2_attn_args) replaces ns2_attention / _hd / _lse / _lse_masked, ns2_attn_bwd_args carries the mask and dropout of the removed bwd_masked entry; 118: ns2_debug_force_attention, ns2_debug_attention_fast_launches (attn_fast_kernel.h); 117: the range-guard counters register themselves: ns2_saturation_counters / _counter_name / _peek replace ns2_saturation_peek_async / _peek_train_async; 116: ns2_groupnorm_silu, ns2_length_regulate(_totals), ns2_row_dot (duration_pitch.hip); 115: ns2_weights_retile; 114: ns2_attention_hd (head dims 32 / 64 / 128), ns2_model_create takes dim_head 32 / 128; 113: ns2_weight_tile_conv3 + ns2_conv3_input_ld (the dedicated FF causal conv kernel, ffconv_kernel.h), ns2_weight_tile_linear (gemm3_kernel.h), ns2_weight_tile_wavenet (wavenet3_kernel.h), ns2_debug_force_gemm(4 / 5); 112: ns2_seanet_resblock_narrow; 111: training entry points take a precision (3 = bf16 x3, 4 = mixed on FMT_H8 lines), ns2_linear_split_as; 110: backward pass (capi_train.cpp: ns2_wgrad, ns2_attention_bwd, ...), ns2_weight_update; 109: ns2_seanet_conv_narrow; 108: ns2_seanet_prep2; 107: ns2_lstm2 (two LSTM layers, one launch); 106: ns2_saturation_peek_async; 105: ns2_lstm_layer takes the scratch size (persistent recurrence); 104: model precision 5 (per-site plan); 103: precision 2 / 4 at op level, caller-owned skinny-linear scratch
+extern "C" int ns2_version(void) { return 120; }   // 120: one argument block per Linear / Conv1d product: ns2_linear(ns2_linear_args) replaces ns2_linear_f32 / _split / _split_as / _geglu / _qkv; 119: one argument block per attention direction: ns2_attention_fwd(ns2_attn_args) replaces ns2_attention / _hd / _lse / _lse_masked, ns2_attn_bwd_args carries the mask and dropout of the removed bwd_masked entry; 118: ns2_debug_force_attention, ns2_debug_attention_fast_launches (attn_fast_kernel.h); 117: the range-guard counters register themselves: ns2_saturation_counters / _counter_name / _peek replace ns2_saturation_peek_async / _peek_train_async; 116: ns2_groupnorm_silu, ns2_length_regulate(_totals), ns2_row_dot (duration_pitch.hip); 115: ns2_weights_retile; 114: ns2_attention_hd (head dims 32 / 64 / 128), ns2_model_create takes dim_head 32 / 128; 113: ns2_weight_tile_conv3 + ns2_conv3_input_ld (the dedicated FF causal conv kernel, ffconv_kernel.h), ns2_weight_tile_linear (gemm3_kernel.h), ns2_weight_tile_wavenet (wavenet3_kernel.h), ns2_debug_force_gemm(4 / 5); 112: ns2_seanet_resblock_narrow; 111: training entry points take a precision (3 = bf16 x3, 4 = mixed on FMT_H8 lines), ns2_linear_split_as; 110: backward pass (capi_train.cpp: ns2_wgrad, ns2_attention_bwd, ...), ns2_weight_update; 109: ns2_seanet_conv_narrow; 108: ns2_seanet_prep2; 107: ns2_lstm2 (two LSTM layers, one launch); 106: ns2_saturation_peek_async; 105: ns2_lstm_layer takes the scratch size (persistent recurrence); 104: model precision 5 (per-site plan); 103: precision 2 / 4 at op level, caller-owned skinny-linear scratch
 extern "C" int ns2_debug_force_gemm(int kernel) {
   ARGCHK(kernel >= 0 && kernel <= 5, "ns2_debug_force_gemm: 0 auto, 1 = 128x128 kernel, 2 = 256x256 kernel, 3 = auto without split-K, 4 = auto without the dedicated kernels (FF conv, lean linear, lean Wavenet), 5 = auto without split-K, the dedicated kernels whenever eligible");
   force_gemm_kernel(kernel);
@@ -105,7 +89,7 @@ extern "C" int ns2_weight_pack(const float* w, int rows, int cols, int taps, int
   return NS2_OK;
 }
 // Give a k = 3 conv weight packed for precision 2 (dense IEEE half) the tiled images of the dedicated FF causal conv kernel
-// (ffconv_kernel.h).  ns2_linear_split / ns2_linear_split_as then take that kernel whenever the call is eligible: dilation 1, causal
+// (ffconv_kernel.h).  ns2_linear calls with plane output then take that kernel whenever the call is eligible: dilation 1, causal
 // padding, no activation, M and seq_len multiples of 256, activations with rows of ns2_conv3_input_ld(cols) elements, FMT_H8 or dense
 // half output.  One-time set-up like ns2_weight_pack (allocates on the first call); ns2_weight_update refreshes the images with the pack.
 extern "C" int ns2_weight_tile_conv3(ns2_weight* w, void* stream) {
@@ -113,7 +97,7 @@ extern "C" int ns2_weight_tile_conv3(ns2_weight* w, void* stream) {
   return build_conv3_tiles(&w->owned, &w->w, (hipStream_t)stream);
 }
 // Give a linear weight (taps = 1; also the GEGLU packing) packed for precision 4 (FMT_H8 lines) the tiled images of the lean mixed linear
-// kernel (gemm3_kernel.h): ns2_linear_f32 / _split / _qkv / _geglu then take that kernel when M % 256 == 0 and K >= 96.  One-time set-up
+// kernel (gemm3_kernel.h): ns2_linear then takes that kernel, whatever the output, when M % 256 == 0 and K >= 96.  One-time set-up
 // (allocates on the first call); ns2_weight_update refreshes the images with the pack; after ns2_weights_repack, ns2_weights_retile does.
 extern "C" int ns2_weight_tile_linear(ns2_weight* w, void* stream) {
   ARGCHK(w && w->taps == 1 && !w->has_extra && w->w.fmt == FMT_H8 && w->w.nkt >= 3, "ns2_weight_tile_linear: a linear weight (taps = 1, K >= 96) packed for precision 4");
@@ -142,64 +126,76 @@ extern "C" void ns2_weight_free(ns2_weight* w) {
   delete w;
 }
 
-// the weight's element format must be the one the requested precision multiplies in (fp16 for 2, bf16 planes for 1 / 3)
-#define WFMT(w, precision, who) ARGCHK(op_fmt(precision) == (w)->w.fmt, who ": weight was packed for a different precision")
-
 extern "C" int ns2_split_f32(const float* x, int ldx, int M, int d, uint16_t* out_hi, uint16_t* out_lo, int ldo, int precision,
                              void* stream) {
   ARGCHK(x && out_hi && prec_ok(precision), "ns2_split_f32: bad arguments");
   ARGCHK(precision != 2 || !out_lo, "ns2_split_f32: precision 2 (fp16) has no lo plane");
-  HIPRET(launch_split(x, ldx, nullptr, 0, 0, 0, out_hi, out_lo, ldo, M, d, 0, (hipStream_t)stream, op_fmt(precision)));
+  HIPRET(launch_split(x, ldx, nullptr, 0, 0, 0, out_hi, out_lo, ldo, M, d, 0, (hipStream_t)stream, operand_fmt(precision)));
   return NS2_OK;
 }
 extern "C" int ns2_join_f32(const uint16_t* hi, const uint16_t* lo, int ld, float* out, int ldo, int64_t M, int d, int precision,
                             void* stream) {
   ARGCHK(hi && out && prec_ok(precision), "ns2_join_f32: bad arguments");
   ARGCHK(precision != 2 || !lo, "ns2_join_f32: precision 2 (fp16) has no lo plane");
-  HIPRET(launch_join(hi, lo, ld, out, ldo, (long)M, d, (hipStream_t)stream, op_fmt(precision)));
+  HIPRET(launch_join(hi, lo, ld, out, ldo, (long)M, d, (hipStream_t)stream, operand_fmt(precision)));
   return NS2_OK;
 }
 
-extern "C" int ns2_linear_f32(const ns2_weight* w, const uint16_t* a_hi, const uint16_t* a_lo, int lda, int M, int conv_taps,
-                              int dilation, int seq_len, const float* bias, const float* resid, int ldr, float* out, int ldo,
-                              int pad_left, int act, int precision, void* stream) {
-  ARGCHK(w && a_hi && out && prec_ok(precision), "ns2_linear_f32: bad arguments");
-  WFMT(w, precision, "ns2_linear_f32");
-  ARGCHK(!w->geglu && !w->has_extra && (conv_taps == 0 ? w->taps == 1 : w->taps == conv_taps), "ns2_linear_f32: weight packing does not match");
-  ARGCHK(lda >= w->cols_p, "ns2_linear_f32: lda smaller than the padded K");
-  ARGCHK(pad_left >= -1 && pad_left < (conv_taps > 0 ? conv_taps : 1) && (act >= 0 && act <= 2), "ns2_linear_f32: bad pad_left / act");
-  return gemm_f32(w->w, a_hi, a_lo, lda, M, conv_taps, dilation, seq_len, bias, resid, ldr, out, ldo, precision, (hipStream_t)stream,
-                  pad_left, act);
+// The one translation of a ns2_linear_args block into the kernels' (ns2_kernels.h GemmArgs, built on ns2_host.h gemm_args).  Everything
+// ns2_linear refuses, it refuses here, before any HIP call; what needs only the block comes before the first read of *w.
+static int linear_args_from(const ns2_linear_args* p, GemmArgs* out) {
+  ARGCHK(p != nullptr, "ns2_linear: null argument block");
+  ARGCHK(p->w != nullptr, "ns2_linear: w is null");
+  ARGCHK(p->a_hi != nullptr, "ns2_linear: a_hi is null");
+  ARGCHK(prec_ok(p->precision), "ns2_linear: precision must be 1 .. 4");
+  const bool planes = p->out_hi != nullptr, qkv = p->vt_hi != nullptr;
+  ARGCHK(planes || p->out_f32, "ns2_linear: no output (neither out_f32 nor out_hi)");
+  ARGCHK(!planes || !p->out_f32, "ns2_linear: both out_f32 and out_hi (exactly one output)");
+  ARGCHK(planes || !(qkv || p->out_precision), "ns2_linear: vt_hi and out_precision need out_hi, not out_f32");
+  ARGCHK(!planes || !p->resid, "ns2_linear: resid needs out_f32, not out_hi");
+  ARGCHK(p->pad_left >= -1 && p->pad_left < (p->conv_taps > 0 ? p->conv_taps : 1), "ns2_linear: pad_left must be -1 (causal) or in [0, conv_taps)");
+  ARGCHK(p->act >= 0 && p->act <= 2, "ns2_linear: act must be 0 (none), 1 (SiLU) or 2 (ELU)");
+  ARGCHK(p->out_precision == 0 || (prec_ok(p->out_precision) && (p->out_precision == 1 || (p->out_precision == 2) == (p->out_lo == nullptr))),
+         "ns2_linear: out_precision 0 (= precision) or 1 .. 4, and out_lo must be null for dense IEEE-half output, hi + 32 for interleaved lines");
+  ARGCHK(!qkv || !(p->bias || p->act || p->conv_taps || p->out_precision), "ns2_linear: vt_hi (the fused q | k | v) excludes bias, act, conv_taps and out_precision");
+  ARGCHK(!qkv || (p->seq_len > 0 && p->M % p->seq_len == 0 && (p->split_col % 32) == 0 && p->vt_ld >= p->seq_len && (p->vt_ld & 7) == 0),
+         "ns2_linear: bad q | k | v shapes (seq_len divides M, split_col a multiple of 32, vt_ld >= seq_len and a multiple of 8)");
+  ARGCHK(!planes || qkv || (p->ldo & 1) == 0, "ns2_linear: ldo must be even");
+  const ns2_weight& w = *p->w;
+  // the weight's element format must be the one the requested precision multiplies in (fp16 for 2, bf16 planes for 1 / 3)
+  ARGCHK(operand_fmt(p->precision) == w.w.fmt, "ns2_linear: w was packed for a different precision");
+  ARGCHK(!w.has_extra && (p->conv_taps == 0 ? w.taps == 1 : w.taps == p->conv_taps),
+         "ns2_linear: the packing of w does not match conv_taps (a weight with extra1x1 belongs to ns2_wavenet_block)");
+  ARGCHK(p->lda >= w.cols_p, "ns2_linear: lda smaller than the padded K of w");
+  ARGCHK(!qkv || p->split_col < w.w.N, "ns2_linear: split_col must lie below the rows of w");
+  GemmArgs& g = *out;
+  g = gemm_args(w.w, p->a_hi, p->a_lo, p->lda, p->M);
+  g.bias = p->bias;
+  if (w.geglu) {
+    ARGCHK(p->bias && planes && !(p->conv_taps || p->act || qkv || p->out_precision),
+           "ns2_linear: a geglu weight needs the packed bias and out_hi, and excludes conv_taps, act, out_f32, vt_hi and out_precision");
+    ARGCHK(p->ldo * 2 == w.w.N, "ns2_linear: ldo must be round_up(f, 32) for a geglu weight");
+    set_geglu(g, p->out_hi, p->out_lo, p->ldo);
+  } else if (qkv) {
+    set_qkv(g, p->precision, p->seq_len, p->split_col, p->out_hi, p->out_lo, p->ldo);
+    g.vt_hi = p->vt_hi; g.vt_lo = p->vt_lo; g.vt_ld = p->vt_ld;
+  } else {
+    if (p->conv_taps) set_conv(g, w.w, p->conv_taps, p->dilation, p->seq_len);
+    g.pad_left = p->pad_left; g.act = p->act;
+    if (planes) {
+      set_out_planes(g, EPI_SPLIT, p->out_hi, p->out_lo, p->ldo);
+      if (p->out_precision) g.out_fmt = operand_fmt(p->out_precision);
+    } else {
+      g.resid = p->resid; g.ldr = p->ldr; g.out_f = p->out_f32; g.ldo_f = p->ldo_f;
+    }
+  }
+  return NS2_OK;
 }
-extern "C" int ns2_linear_split(const ns2_weight* w, const uint16_t* a_hi, const uint16_t* a_lo, int lda, int M, int conv_taps,
-                                int dilation, int seq_len, const float* bias, uint16_t* out_hi, uint16_t* out_lo, int ldo,
-                                int pad_left, int act, int precision, void* stream) {
-  ARGCHK(w && a_hi && out_hi && prec_ok(precision), "ns2_linear_split: bad arguments");
-  WFMT(w, precision, "ns2_linear_split");
-  ARGCHK(!w->geglu && !w->has_extra && (conv_taps == 0 ? w->taps == 1 : w->taps == conv_taps), "ns2_linear_split: weight packing does not match");
-  ARGCHK(lda >= w->cols_p && (ldo & 1) == 0, "ns2_linear_split: bad leading dimensions");
-  ARGCHK(pad_left >= -1 && pad_left < (conv_taps > 0 ? conv_taps : 1) && (act >= 0 && act <= 2), "ns2_linear_split: bad pad_left / act");
-  return gemm_split(w->w, a_hi, a_lo, lda, M, conv_taps, dilation, seq_len, bias, out_hi, out_lo, ldo, precision, (hipStream_t)stream,
-                    pad_left, act);
-}
-extern "C" int ns2_linear_split_as(const ns2_weight* w, const uint16_t* a_hi, const uint16_t* a_lo, int lda, int M, int conv_taps,
-                                   int dilation, int seq_len, const float* bias, uint16_t* out_hi, uint16_t* out_lo, int ldo,
-                                   int pad_left, int act, int precision, int out_precision, void* stream) {
-  ARGCHK(w && a_hi && out_hi && prec_ok(precision) && prec_ok(out_precision), "ns2_linear_split_as: bad arguments");
-  WFMT(w, precision, "ns2_linear_split_as");
-  ARGCHK(!w->geglu && !w->has_extra && (conv_taps == 0 ? w->taps == 1 : w->taps == conv_taps), "ns2_linear_split_as: weight packing does not match");
-  ARGCHK(lda >= w->cols_p && (ldo & 1) == 0, "ns2_linear_split_as: bad leading dimensions");
-  ARGCHK(pad_left >= -1 && pad_left < (conv_taps > 0 ? conv_taps : 1) && (act >= 0 && act <= 2), "ns2_linear_split_as: bad pad_left / act");
-  ARGCHK(out_precision == 1 || (out_precision == 2) == (out_lo == nullptr), "ns2_linear_split_as: out_lo must be null for dense IEEE-half output, hi + 32 for interleaved lines");
-  return gemm_split(w->w, a_hi, a_lo, lda, M, conv_taps, dilation, seq_len, bias, out_hi, out_lo, ldo, precision, (hipStream_t)stream,
-                    pad_left, act, op_fmt(out_precision));
-}
-extern "C" int ns2_linear_geglu(const ns2_weight* w, const uint16_t* a_hi, const uint16_t* a_lo, int lda, int M,
-                                const float* packed_bias, uint16_t* out_hi, uint16_t* out_lo, int ldo, int precision, void* stream) {
-  ARGCHK(w && a_hi && out_hi && packed_bias && prec_ok(precision) && w->geglu, "ns2_linear_geglu: bad arguments");
-  WFMT(w, precision, "ns2_linear_geglu");
-  ARGCHK(ldo * 2 == w->w.N, "ns2_linear_geglu: ldo must be round_up(f, 32)");
-  return gemm_geglu(w->w, a_hi, a_lo, lda, M, packed_bias, out_hi, out_lo, ldo, precision, (hipStream_t)stream);
+extern "C" int ns2_linear(const ns2_linear_args* p, void* stream) {
+  GemmArgs g;
+  if (int rc = linear_args_from(p, &g)) return rc;
+  HIPRET(launch_gemm(g, p->precision, (hipStream_t)stream));
+  return NS2_OK;
 }
 extern "C" int ns2_geglu_pack_bias(const float* bias, int f, float* packed, int packed_len, void* stream) {
   ARGCHK(bias && packed && f > 0, "ns2_geglu_pack_bias: bad arguments");
@@ -214,15 +210,6 @@ extern "C" int ns2_geglu_pack_bias(const float* bias, int f, float* packed, int 
   (void)stream;
   return NS2_OK;
 }
-extern "C" int ns2_linear_qkv(const ns2_weight* w, const uint16_t* a_hi, const uint16_t* a_lo, int lda, int M, int seq_len,
-                              int split_col, uint16_t* out_hi, uint16_t* out_lo, int ldo, uint16_t* vt_hi, uint16_t* vt_lo,
-                              int vt_ld, int precision, void* stream) {
-  ARGCHK(w && a_hi && out_hi && vt_hi && prec_ok(precision), "ns2_linear_qkv: bad arguments");
-  WFMT(w, precision, "ns2_linear_qkv");
-  ARGCHK(seq_len > 0 && M % seq_len == 0 && (split_col % 32) == 0 && split_col < w->w.N && vt_ld >= seq_len && (vt_ld & 7) == 0,
-         "ns2_linear_qkv: bad shapes");
-  return gemm_qkv(w->w, a_hi, a_lo, lda, M, seq_len, split_col, out_hi, out_lo, ldo, vt_hi, vt_lo, vt_ld, precision, (hipStream_t)stream);
-}
 extern "C" int ns2_wavenet_block(const ns2_weight* w, const uint16_t* a_hi, const uint16_t* a_lo, int lda, int M, int seq_len,
                                  int dilation, const float* conv_bias, const float* res_bias, const float* film, int film_ld,
                                  uint16_t* out_hi, uint16_t* out_lo, int ldo, int precision, void* stream) {
@@ -230,10 +217,14 @@ extern "C" int ns2_wavenet_block(const ns2_weight* w, const uint16_t* a_hi, cons
   const int p1_half = precision == 5;
   if (p1_half) precision = 4;
   ARGCHK(w && a_hi && out_hi && conv_bias && res_bias && film && prec_ok(precision), "ns2_wavenet_block: bad arguments");
-  WFMT(w, precision, "ns2_wavenet_block");
+  ARGCHK(operand_fmt(precision) == w->w.fmt, "ns2_wavenet_block: weight was packed for a different precision");
   ARGCHK(w->taps == 3 && w->has_extra && seq_len > 0, "ns2_wavenet_block: weight must be packed with taps=3 and extra1x1");
-  return gemm_wavenet(w->w, a_hi, a_lo, lda, 0, M, seq_len, dilation, 0, 1, conv_bias, res_bias, 0, film, film_ld, 0, out_hi, out_lo,
-                      ldo, 0, ldo, precision, (hipStream_t)stream, p1_half);
+  GemmArgs g = gemm_args(w->w, a_hi, a_lo, lda, M);
+  set_wavenet(g, w->w, dilation, seq_len, precision, p1_half);
+  g.bias = conv_bias; g.bias2 = res_bias; g.film = film; g.film_ld = film_ld;
+  set_out_planes(g, EPI_WAVENET, out_hi, out_lo, ldo);
+  HIPRET(launch_gemm(g, precision, (hipStream_t)stream));
+  return NS2_OK;
 }
 
 // The one translation of the C argument block into the kernels' (ns2_kernels.h AttnArgs, whose defaults are "nothing optional").
@@ -252,7 +243,7 @@ static int attn_args_from(const ns2_attn_args* p, AttnArgs* out) {
   a.k_hi = p->k_hi; a.k_lo = p->k_lo; a.ldk = p->ldk; a.k_col0 = p->k_col0;
   a.vt_hi = p->vt_hi; a.vt_lo = p->vt_lo; a.vt_ld = p->vt_ld;
   a.o_hi = p->o_hi; a.o_lo = p->o_lo; a.ldo = p->ldo;
-  if (p->o_precision) a.o_fmt = op_fmt(p->o_precision);
+  if (p->o_precision) a.o_fmt = operand_fmt(p->o_precision);
   a.B = p->B; a.H = p->H; a.Nq = p->Nq; a.Nk = p->Nk; a.scale = p->scale; a.kmask = p->key_mask; a.lse = p->lse;
   return NS2_OK;
 }
@@ -270,7 +261,7 @@ extern "C" int ns2_rmsnorm(const float* x, int ldx, int M, int d, int seq_len, c
   ARGCHK(!cond || seq_len > 0, "ns2_rmsnorm: adaptive norm needs seq_len");
   NormArgs n;
   n.x = x; n.ldx = ldx; n.gamma = gamma; n.cond = cond; n.cond_ld = cond_ld;
-  n.out_hi = out_hi; n.out_lo = out_lo; n.ldo = out_hi ? ldo : d; n.out_f = out_f32; n.ldo_f = ldo_f; n.fmt = op_fmt(precision);
+  n.out_hi = out_hi; n.out_lo = out_lo; n.ldo = out_hi ? ldo : d; n.out_f = out_f32; n.ldo_f = ldo_f; n.fmt = operand_fmt(precision);
   n.M = M; n.d = d; n.seq_len = seq_len;
   HIPRET(launch_rmsnorm(n, (hipStream_t)stream));
   return NS2_OK;
@@ -323,7 +314,7 @@ extern "C" int ns2_seanet_prep(const float* x, int ldx, int in_prefix, const flo
                                int prefix, int im2col_k, uint16_t* out_hi, uint16_t* out_lo, int ldo, int precision, void* stream) {
   ARGCHK(x && out_hi && prec_ok(precision), "ns2_seanet_prep: bad arguments");
   HIPRET(launch_seanet_prep(x, ldx, in_prefix, add, ldadd, B, (long)T, C, elu, prefix, im2col_k, out_hi, out_lo, ldo,
-                            op_fmt(precision), (hipStream_t)stream));
+                            operand_fmt(precision), (hipStream_t)stream));
   return NS2_OK;
 }
 extern "C" int ns2_seanet_prep2(const float* x, int ldx, int in_prefix, int B, int64_t T, int C, int prefix, uint16_t* elu_hi,
@@ -331,7 +322,7 @@ extern "C" int ns2_seanet_prep2(const float* x, int ldx, int in_prefix, int B, i
                                 int raw_col0, int raw_cols, int precision, void* stream) {
   ARGCHK(x && (elu_hi || raw_hi) && prec_ok(precision), "ns2_seanet_prep2: bad arguments");
   HIPRET(launch_seanet_prep2(x, ldx, in_prefix, B, (long)T, C, prefix, elu_hi, elu_lo, elu_ld, elu_col0, elu_cols, raw_hi, raw_lo, raw_ld,
-                             raw_col0, raw_cols, op_fmt(precision), (hipStream_t)stream));
+                             raw_col0, raw_cols, operand_fmt(precision), (hipStream_t)stream));
   return NS2_OK;
 }
 extern "C" int ns2_seanet_conv_narrow(const float* x, int64_t ldx, int in_prefix, int B, int64_t T, int ci, int co, int k, int elu,

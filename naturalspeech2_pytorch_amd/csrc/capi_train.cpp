@@ -9,22 +9,6 @@
 
 using namespace ns2;
 
-#define HIPRET(expr)                                                                 \
-  do {                                                                               \
-    hipError_t _e = (expr);                                                          \
-    if (_e != hipSuccess) {                                                          \
-      set_error("%s:%d %s -> %s", __FILE__, __LINE__, #expr, hipGetErrorString(_e)); \
-      return NS2_ERR_HIP;                                                            \
-    }                                                                                \
-  } while (0)
-#define ARGCHK(cond, msg)            \
-  do {                               \
-    if (!(cond)) {                   \
-      set_error("%s", msg);          \
-      return NS2_ERR_ARG;            \
-    }                                \
-  } while (0)
-
 extern "C" int ns2_weight_update(ns2_weight* w, const float* w_src, const float* extra1x1, void* stream) {
   ARGCHK(w && w_src && w->d_map, "ns2_weight_update: null weight / source");
   ARGCHK((extra1x1 != nullptr) == (w->has_extra != 0), "ns2_weight_update: extra1x1 must be given iff the weight was packed with one");
@@ -107,7 +91,7 @@ extern "C" int ns2_grad_prep(const float* x, int64_t ldx, int M, int C, int seq_
   a.row_hi = row_hi; a.row_lo = row_lo; a.ld_row = ld_row;
   a.t_hi = t_hi; a.t_lo = t_lo; a.ld_t = (long)ld_t; a.per_batch = per_batch; a.t_rows_per_batch = t_rows; a.t_rows = t_rows;
   a.colsum_partial = colsum_partial;
-  a.fmt = precision == 4 ? FMT_H8 : FMT_BF16;
+  a.fmt = operand_fmt(precision);
   HIPRET(launch_tplanes(a, (hipStream_t)stream));
   return NS2_OK;
 }
@@ -121,7 +105,7 @@ extern "C" int ns2_planes_transpose(const uint16_t* in_hi, const uint16_t* in_lo
   memset(&a, 0, sizeof a);
   a.in_hi = in_hi; a.in_lo = in_lo; a.ld_in = ld_in; a.in_col0 = in_col0; a.M = M; a.C = C; a.seq_len = seq_len; a.shift = shift;
   a.t_hi = t_hi; a.t_lo = t_lo; a.ld_t = (long)ld_t; a.per_batch = per_batch; a.t_rows_per_batch = t_rows; a.t_rows = t_rows;
-  a.fmt = precision == 4 ? FMT_H8 : FMT_BF16;
+  a.fmt = operand_fmt(precision);
   HIPRET(launch_tplanes(a, (hipStream_t)stream));
   return NS2_OK;
 }
@@ -165,13 +149,11 @@ extern "C" int ns2_wgrad(const uint16_t* dyt_hi, const uint16_t* dyt_lo, const u
   const int S = wgrad_split(R, ncols, ld_t);
   ARGCHK(workspace_bytes >= (int64_t)S * R * ncols * (int64_t)sizeof(float), "ns2_wgrad: workspace too small (ns2_wgrad_workspace_bytes)");
   GemmArgs g;
-  memset(&g, 0, sizeof g);
   const int nkt = (int)(ld_t / 32) / S;
   g.a_hi = dyt_hi; g.a_lo = dyt_lo; g.lda = (int)ld_t;
   g.w_hi = xt_hi; g.w_lo = xt_lo; g.ldw = (int)ld_t;        // rows of X^T beyond T * Kp up to the next multiple of 256 must exist (zeros)
-  g.M = R; g.N = ncols; g.nkt = nkt; g.kt_per_tap = nkt; g.conv_taps = 0; g.dil = 1; g.mid_kt = -1;
+  g.M = R; g.N = ncols; g.nkt = nkt; g.kt_per_tap = nkt;
   g.nz = S; g.a_zs = (long)nkt * 32; g.w_zs = (long)nkt * 32; g.out_f_zs = (long)R * ncols;
-  g.pad_left = -1; g.out_fmt = -1; g.vt_fmt = -1;
   g.epi = EPI_F32; g.out_f = (float*)workspace; g.ldo_f = ncols;
   HIPRET(launch_gemm(g, precision, (hipStream_t)stream));
   HIPRET(launch_wgrad_reduce((const float*)workspace, S, R, ncols, T, Kp, K, dw, (hipStream_t)stream));
@@ -201,13 +183,11 @@ extern "C" int ns2_wgrad_rows(const uint16_t* dy_hi, const uint16_t* dy_lo, int 
   const int S = wgrad_split(R, ncols, ld_t);
   ARGCHK(workspace_bytes >= (int64_t)S * R * ncols * (int64_t)sizeof(float), "ns2_wgrad_rows: workspace too small (ns2_wgrad_workspace_bytes(R, T * Kp, round_up(M, 32)))");
   GemmArgs g;
-  memset(&g, 0, sizeof g);
   const int nkt = (int)(ld_t / 32) / S;
   g.a_hi = dy_hi; g.a_lo = dy_lo; g.lda = ld_dy;
   g.w_hi = x_hi; g.w_lo = x_lo; g.ldw = ld_x;
-  g.M = R; g.N = ncols; g.nkt = nkt; g.kt_per_tap = nkt; g.conv_taps = 0; g.dil = dil > 0 ? dil : 1; g.seq_len = T > 1 ? seq_len : 0; g.mid_kt = -1;
+  g.M = R; g.N = ncols; g.nkt = nkt; g.kt_per_tap = nkt; g.dil = dil > 0 ? dil : 1; g.seq_len = T > 1 ? seq_len : 0;
   g.nz = S; g.out_f_zs = (long)R * ncols;
-  g.pad_left = -1; g.out_fmt = -1; g.vt_fmt = -1;
   g.epi = EPI_F32; g.out_f = (float*)workspace; g.ldo_f = ncols;
   g.tr_tokens = (int)M; g.tr_kp = Kp; g.tr_taps = T > 1 ? T : 0;
   HIPRET(launch_gemm_tr(g, precision, (hipStream_t)stream));
@@ -232,7 +212,7 @@ extern "C" int ns2_geglu_fwd(const float* pre, int64_t ldp, int64_t M, int f, ui
                              void* stream) {
   ARGCHK(pre && out_hi && out_lo, "ns2_geglu_fwd: null pointer");
   ARGCHK(precision == 3 || precision == 4, "ns2_geglu_fwd: precision 3 (bf16 hi / lo planes) or 4 (FMT_H8 lines)");
-  HIPRET(launch_geglu_fwd(pre, (long)ldp, (long)M, f, out_hi, out_lo, ldo, (hipStream_t)stream, precision == 4 ? FMT_H8 : FMT_BF16));
+  HIPRET(launch_geglu_fwd(pre, (long)ldp, (long)M, f, out_hi, out_lo, ldo, (hipStream_t)stream, operand_fmt(precision)));
   return NS2_OK;
 }
 extern "C" int ns2_geglu_bwd(const float* dh, int64_t lddh, const float* pre, int64_t ldp, int64_t M, int f, float* dpre, int64_t lddp,
@@ -259,7 +239,7 @@ extern "C" int ns2_attention_delta(const float* d_out, int64_t ld_dout, const ui
                                    int Nq, float* delta, int o_precision, void* stream) {
   ARGCHK(d_out && o_hi && delta, "ns2_attention_delta: null pointer");
   ARGCHK(o_precision == 3 || o_precision == 4, "ns2_attention_delta: o_precision 3 (bf16 hi / lo planes) or 4 (FMT_H8 lines)");
-  HIPRET(launch_attn_delta(d_out, (long)ld_dout, o_hi, o_lo, ldo, B, H, Nq, delta, (hipStream_t)stream, o_precision == 4 ? FMT_H8 : FMT_BF16));
+  HIPRET(launch_attn_delta(d_out, (long)ld_dout, o_hi, o_lo, ldo, B, H, Nq, delta, (hipStream_t)stream, operand_fmt(o_precision)));
   return NS2_OK;
 }
 extern "C" int ns2_attention_bwd(const ns2_attn_bwd_args* p, void* stream) {
@@ -277,7 +257,7 @@ extern "C" int ns2_attention_bwd(const ns2_attn_bwd_args* p, void* stream) {
   a.dv = p->dv; a.lddv = p->lddv; a.dv_col0 = p->dv_col0;
   a.B = p->B; a.H = p->H; a.Nq = p->Nq; a.Nk = p->Nk; a.scale = p->scale;
   a.gp_hi = p->gp_hi; a.gp_lo = p->gp_lo; a.gp_ld = p->gp_ld; a.gp_q = p->gp_q; a.gp_kv = p->gp_kv;
-  a.gp_fmt = p->gp_precision == 4 ? FMT_H8 : FMT_BF16;
+  a.gp_fmt = operand_fmt(p->gp_precision);
   a.kmask = p->key_mask;
   HIPRET(launch_attention_bwd(a, (hipStream_t)stream));
   return NS2_OK;

@@ -1087,9 +1087,8 @@ static hipError_t resolve_gemm_args(GemmArgs& g, int precision) {
         (g.nrm_gamma && (reinterpret_cast<uintptr_t>(g.nrm_gamma) & 15)))
       return hipErrorInvalidValue;
   }
-  const int op_fmt = precision == 2 ? FMT_F16 : (precision == 4 ? FMT_H8 : FMT_BF16);
-  if (g.out_fmt < 0) g.out_fmt = op_fmt;
-  if (g.vt_fmt < 0) g.vt_fmt = (precision == 2 || precision == 4) ? FMT_F16 : FMT_BF16;
+  if (g.out_fmt < 0) g.out_fmt = operand_fmt(precision);
+  if (g.vt_fmt < 0) g.vt_fmt = attention_fmt(precision);
   if (precision == 2 && (g.a_lo || g.w_lo)) return hipErrorInvalidValue;
   if ((precision == 3 || precision == 4) && (!g.a_lo || !g.w_lo)) return hipErrorInvalidValue;
   if (g.out_hi && ((g.out_fmt == FMT_F16 && g.out_lo) || (g.out_fmt == FMT_H8 && !g.out_lo))) return hipErrorInvalidValue;

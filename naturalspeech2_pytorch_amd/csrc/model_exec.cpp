@@ -26,20 +26,6 @@
 
 namespace ns2 {
 
-#define HIPCHK(expr)                                                                     \
-  do {                                                                                   \
-    hipError_t _e = (expr);                                                              \
-    if (_e != hipSuccess) {                                                              \
-      set_error("%s:%d %s -> %s", __FILE__, __LINE__, #expr, hipGetErrorString(_e));     \
-      return NS2_ERR_HIP;                                                                \
-    }                                                                                    \
-  } while (0)
-#define NSCHK(expr)                  \
-  do {                               \
-    int _r = (expr);                 \
-    if (_r != NS2_OK) return _r;     \
-  } while (0)
-
 // kernel categories for ns2_model_profile_* (== kernel symbols in a rocprofv3 trace)
 enum { PC_GEMM_F32 = 0, PC_GEMM_SPLIT = 1, PC_GEMM_QKV = 2, PC_GEMM_GEGLU = 3, PC_GEMM_WAVENET = 4, PC_ATTENTION = 5, PC_NORM = 6,
        PC_GEMM_FFCONV = 7 /* the feed-forward causal conv alone (same kernel family as PC_GEMM_SPLIT) */ };
@@ -97,7 +83,7 @@ namespace ns2 {
 
 // ------------------------------------------------------------------------------------------------ packing helpers
 static int dev_alloc(std::vector<void*>* owned, void** p, size_t bytes) {
-  HIPCHK(hipMalloc(p, bytes ? bytes : 16));
+  HIPRET(hipMalloc(p, bytes ? bytes : 16));
   if (owned) owned->push_back(*p);
   return NS2_OK;
 }
@@ -143,7 +129,7 @@ static int alloc_packed(const PackCtx& pc, PackedW* w, int N, int ldk, int kt_pe
   NSCHK(dev_alloc(owned, (void**)&w->hi, bytes));
   w->lo = il ? w->hi + 32 : nullptr;
   w->fmt = pc.fmt;
-  HIPCHK(hipMemset(w->hi, 0, bytes));
+  HIPRET(hipMemset(w->hi, 0, bytes));
   return NS2_OK;
 }
 
@@ -152,14 +138,14 @@ static int alloc_packed(const PackCtx& pc, PackedW* w, int N, int ldk, int kt_pe
 static int pack_into(PackedW* w, const float* src, int C, int T, int Cp, const std::vector<int>& row_map, int row0, int k_off,
                      hipStream_t s) {
   int* d_map = nullptr;
-  HIPCHK(hipMalloc((void**)&d_map, row_map.size() * sizeof(int)));
-  HIPCHK(hipMemcpy(d_map, row_map.data(), row_map.size() * sizeof(int), hipMemcpyHostToDevice));
+  HIPRET(hipMalloc((void**)&d_map, row_map.size() * sizeof(int)));
+  HIPRET(hipMemcpy(d_map, row_map.data(), row_map.size() * sizeof(int), hipMemcpyHostToDevice));
   const size_t roff = (size_t)row0 * w->ldk * (w->lo ? 2 : 1);
   hipError_t e = launch_pack_weight(src, C, T, Cp, d_map, (int)row_map.size(), w->hi + roff, w->lo ? w->lo + roff : nullptr,
                                     w->ldk, k_off, s, w->fmt);
   if (e == hipSuccess) e = hipStreamSynchronize(s);
   (void)hipFree(d_map);
-  HIPCHK(e);
+  HIPRET(e);
   return NS2_OK;
 }
 
@@ -192,7 +178,7 @@ int build_conv3_tiles(std::vector<void*>* owned, PackedW* w, hipStream_t s) {
   if (w->fmt != FMT_F16 || w->lo || w->nkt != 3 * w->kt_per_tap) { set_error("build_conv3_tiles: not a dense IEEE-half k = 3 conv weight"); return NS2_ERR_ARG; }
   const int Cp = w->kt_per_tap * 32;
   if (!w->t3) NSCHK(dev_alloc(owned, (void**)&w->t3, ffconv3_tiled_bytes_of(w->N, Cp)));
-  HIPCHK(ffconv3_build_tiles(w->hi, w->ldk, Cp, w->rows_p, w->N, w->t3, s));
+  HIPRET(ffconv3_build_tiles(w->hi, w->ldk, Cp, w->rows_p, w->N, w->t3, s));
   return NS2_OK;
 }
 
@@ -201,7 +187,7 @@ int build_conv3_tiles(std::vector<void*>* owned, PackedW* w, hipStream_t s) {
 int build_lin_tiles(std::vector<void*>* owned, PackedW* w, hipStream_t s) {
   if (w->fmt != FMT_H8 || !w->lo || w->nkt != w->kt_per_tap || w->nkt < 3 || (w->rows_p & 255)) return NS2_OK;
   if (!w->tl) NSCHK(dev_alloc(owned, (void**)&w->tl, gemm3_tiled_bytes_of(w->rows_p, w->nkt)));
-  HIPCHK(gemm3_build_tiles(w->hi, w->ldk, w->rows_p, w->tl, s));
+  HIPRET(gemm3_build_tiles(w->hi, w->ldk, w->rows_p, w->tl, s));
   return NS2_OK;
 }
 
@@ -213,12 +199,12 @@ static int pack_geglu(const PackCtx& pc, PackedW* w, const float* src, int f, in
 
 static int pack_geglu_bias(std::vector<void*>* owned, float** out, const float* bias, int f, int rows_p) {
   std::vector<float> hb(2 * f), pb(rows_p, 0.f);
-  HIPCHK(hipMemcpy(hb.data(), bias, 2 * f * sizeof(float), hipMemcpyDeviceToHost));
+  HIPRET(hipMemcpy(hb.data(), bias, 2 * f * sizeof(float), hipMemcpyDeviceToHost));
   std::vector<int> m = geglu_row_map(f, rows_p);
   for (int i = 0; i < rows_p; ++i)
     if (m[i] >= 0) pb[i] = hb[m[i]];
   NSCHK(dev_alloc(owned, (void**)out, rows_p * sizeof(float)));
-  HIPCHK(hipMemcpy(*out, pb.data(), rows_p * sizeof(float), hipMemcpyHostToDevice));
+  HIPRET(hipMemcpy(*out, pb.data(), rows_p * sizeof(float), hipMemcpyHostToDevice));
   return NS2_OK;
 }
 
@@ -258,86 +244,13 @@ extern "C" int ns2_debug_lend_splitk_scratch(void* scratch, int64_t bytes) {
   tl_sk_ws = static_cast<float*>(scratch);
   return NS2_OK;
 }
-static GemmArgs base_args(const PackedW& w, const bf16_t* a_hi, const bf16_t* a_lo, int lda, int M) {
+GemmArgs gemm_args(const PackedW& w, const bf16_t* a_hi, const bf16_t* a_lo, int lda, int M) {
   GemmArgs g;
-  memset(&g, 0, sizeof(g));
   g.sk_ws = tl_sk_ws; g.sk_ws_floats = tl_sk_ws ? SPLITK_SCRATCH_FLOATS : 0;
   g.a_hi = a_hi; g.a_lo = a_lo; g.lda = lda;
   g.w_hi = w.hi; g.w_lo = w.lo; g.ldw = w.ldk; g.w_t3 = w.t3; g.w_tl = w.tl; g.w_tw1 = w.tw1; g.w_tw2 = w.tw2;
-  g.M = M; g.N = w.N; g.nkt = w.nkt; g.kt_per_tap = w.nkt; g.conv_taps = 0; g.dil = 1; g.mid_kt = -1;
-  g.nz = 1; g.pad_left = -1; g.act = 0; g.out_fmt = -1; g.vt_fmt = -1;
+  g.M = M; g.N = w.N; g.nkt = w.nkt; g.kt_per_tap = w.nkt;
   return g;
-}
-static void set_conv(GemmArgs& g, const PackedW& w, int taps, int dil, int seq_len) {
-  g.kt_per_tap = w.kt_per_tap; g.conv_taps = taps; g.dil = dil; g.seq_len = seq_len;
-}
-
-int gemm_f32(const PackedW& w, const bf16_t* a_hi, const bf16_t* a_lo, int lda, int M, int conv_taps, int dil, int seq_len,
-             const float* bias, const float* resid, int ldr, float* out, int ldo, int prec, hipStream_t s, int pad_left, int act) {
-  GemmArgs g = base_args(w, a_hi, a_lo, lda, M);
-  if (conv_taps) set_conv(g, w, conv_taps, dil, seq_len);
-  g.pad_left = pad_left; g.act = act;
-  g.epi = EPI_F32; g.bias = bias; g.resid = resid; g.ldr = ldr; g.out_f = out; g.ldo_f = ldo;
-  HIPCHK(launch_gemm(g, prec, s));
-  return NS2_OK;
-}
-// The residual stream's update followed by the RMSNorm that reads it (NS2:794-807): ONE launch where the GEMM's workgroups own whole
-// rows (dim = 128: the 128 x 128 kernel, gemm.hip), else the GEMM and rmsnorm_kernel.  `fused` tells the caller what happened (profile
-// categories).  cond_ld == 0 with cond != null: every utterance reads the same (gamma, beta) row (the time table).
-int gemm_f32_norm(const PackedW& w, const bf16_t* a_hi, const bf16_t* a_lo, int lda, int M, const float* bias, const float* resid, int ldr,
-                  float* out, int ldo, int prec, int seq_len, const float* gamma, const float* cond, int cond_ld, bf16_t* n_hi, bf16_t* n_lo,
-                  int n_ld, int n_fmt, hipStream_t s, bool* fused) {
-  GemmArgs g = base_args(w, a_hi, a_lo, lda, M);
-  g.epi = EPI_F32; g.bias = bias; g.resid = resid; g.ldr = ldr; g.out_f = out; g.ldo_f = ldo;
-  *fused = gemm_fuses_norm(g, prec);
-  if (*fused) {
-    g.nrm_hi = n_hi; g.nrm_lo = n_lo; g.nrm_ld = n_ld; g.nrm_fmt = n_fmt;
-    g.nrm_gamma = gamma; g.nrm_cond = cond; g.nrm_cond_ld = cond_ld; g.nrm_seq_len = seq_len;
-  }
-  HIPCHK(launch_gemm(g, prec, s));
-  return NS2_OK;
-}
-int gemm_split(const PackedW& w, const bf16_t* a_hi, const bf16_t* a_lo, int lda, int M, int conv_taps, int dil, int seq_len,
-               const float* bias, bf16_t* o_hi, bf16_t* o_lo, int ldo, int prec, hipStream_t s, int pad_left, int act, int out_fmt) {
-  GemmArgs g = base_args(w, a_hi, a_lo, lda, M);
-  if (conv_taps) set_conv(g, w, conv_taps, dil, seq_len);
-  g.pad_left = pad_left; g.act = act; g.out_fmt = out_fmt;
-  g.epi = EPI_SPLIT; g.bias = bias; g.out_hi = o_hi; g.out_lo = o_lo; g.ldo_s = ldo; g.out_ncols = ldo;
-  HIPCHK(launch_gemm(g, prec, s));
-  return NS2_OK;
-}
-int gemm_geglu(const PackedW& w, const bf16_t* a_hi, const bf16_t* a_lo, int lda, int M, const float* pbias, bf16_t* o_hi,
-               bf16_t* o_lo, int ldo, int prec, hipStream_t s, int out_fmt, int out_ncols) {
-  GemmArgs g = base_args(w, a_hi, a_lo, lda, M);
-  g.out_fmt = out_fmt;
-  g.epi = EPI_GEGLU; g.bias = pbias; g.out_hi = o_hi; g.out_lo = o_lo; g.ldo_s = ldo; g.out_ncols = out_ncols > 0 ? out_ncols : ldo;
-  HIPCHK(launch_gemm(g, prec, s));
-  return NS2_OK;
-}
-int gemm_qkv(const PackedW& w, const bf16_t* a_hi, const bf16_t* a_lo, int lda, int M, int seq_len, int split_col,
-             bf16_t* o_hi, bf16_t* o_lo, int ldo, bf16_t* vt_hi, bf16_t* vt_lo, int vt_ld, int prec, hipStream_t s, int att_fmt) {
-  GemmArgs g = base_args(w, a_hi, a_lo, lda, M);
-  g.epi = EPI_QKV; g.seq_len = seq_len; g.split_col = split_col;
-  g.out_fmt = (prec == 2 || prec == 4) ? FMT_F16 : FMT_BF16;        // q / k are attention operands: IEEE half also at precision 4
-  if (att_fmt >= 0) { g.out_fmt = att_fmt; g.vt_fmt = att_fmt; }   // ... unless the caller's attention runs in another format
-  g.out_hi = o_hi; g.out_lo = o_lo; g.ldo_s = ldo; g.out_ncols = split_col;
-  g.vt_hi = vt_hi; g.vt_lo = vt_lo; g.vt_ld = vt_ld; g.vt_rows = w.N - split_col;
-  HIPCHK(launch_gemm(g, prec, s));
-  return NS2_OK;
-}
-int gemm_wavenet(const PackedW& w, const bf16_t* a_hi, const bf16_t* a_lo, int lda, long a_zs, int M, int seq_len, int dil,
-                 int dil_z, int nz, const float* b_conv, const float* b_res, long bias_zs, const float* film, int film_ld,
-                 long film_zs, bf16_t* o_hi, bf16_t* o_lo, int ldo, long out_zs, int out_ncols, int prec, hipStream_t s, int p1_half) {
-  GemmArgs g = base_args(w, a_hi, a_lo, lda, M);
-  set_conv(g, w, 3, dil, seq_len);
-  g.p1_half = (prec == 4) ? p1_half : 0;
-  g.dil_z = dil_z; g.nz = nz; g.a_zs = a_zs; g.w_zs = (long)w.rows_p * w.ldk; g.bias_zs = bias_zs; g.film_zs = film_zs;
-  g.out_zs = out_zs;
-  g.mid_kt = 3 * w.kt_per_tap;
-  g.epi = EPI_WAVENET; g.bias = b_conv; g.bias2 = b_res; g.film = film; g.film_ld = film_ld;
-  g.out_hi = o_hi; g.out_lo = o_lo; g.ldo_s = ldo; g.out_ncols = out_ncols;
-  HIPCHK(launch_gemm(g, prec, s));
-  return NS2_OK;
 }
 
 }  // namespace ns2
@@ -391,7 +304,7 @@ extern "C" void ns2_model_destroy(ns2_model* m) {
 static int transpose_weight(ns2_model* m, const Param* w, float** out, hipStream_t s) {   // [R, C] -> K-major [C, R]
   const int R = (int)w->dims[0], C = (int)w->dims[1];
   NSCHK(dev_alloc(&m->owned, (void**)out, (size_t)R * C * sizeof(float)));
-  HIPCHK(launch_transpose_into(w->p, R, C, *out, R, 0, s));
+  HIPRET(launch_transpose_into(w->p, R, C, *out, R, 0, s));
   return NS2_OK;
 }
 
@@ -419,8 +332,8 @@ extern "C" int ns2_model_finalize(ns2_model* m, void* stream) {
     GETP(w, std::string(prefix) + ".weight");
     GETP(b, std::string(prefix) + ".bias");
     if (w->dims[0] != 2 * dim || w->dims[1] != m->Tc) { set_error("%s.weight has unexpected shape", prefix); return NS2_ERR_STATE; }
-    HIPCHK(launch_transpose_into(w->p, 2 * dim, m->Tc, m->wt_cond, m->Jtot, (long)slot * 2 * dim, s));
-    HIPCHK(hipMemcpyAsync(m->b_cond + (size_t)slot * 2 * dim, b->p, 2 * dim * sizeof(float), hipMemcpyDeviceToDevice, s));
+    HIPRET(launch_transpose_into(w->p, 2 * dim, m->Tc, m->wt_cond, m->Jtot, (long)slot * 2 * dim, s));
+    HIPRET(hipMemcpyAsync(m->b_cond + (size_t)slot * 2 * dim, b->p, 2 * dim * sizeof(float), hipMemcpyDeviceToDevice, s));
     return NS2_OK;
   };
   for (int st = 0; st < S; ++st)
@@ -447,7 +360,7 @@ extern "C" int ns2_model_finalize(ns2_model* m, void* stream) {
     NSCHK(dev_alloc(&m->owned, (void**)&W.hi, per * L * sizeof(bf16_t)));
     W.lo = il ? W.hi + 32 : nullptr;
     W.fmt = pc.fmt;
-    HIPCHK(hipMemset(W.hi, 0, per * L * sizeof(bf16_t)));
+    HIPRET(hipMemset(W.hi, 0, per * L * sizeof(bf16_t)));
     NSCHK(dev_alloc(&m->owned, (void**)&m->b_wn_conv[st], (size_t)L * dim * sizeof(float)));
     NSCHK(dev_alloc(&m->owned, (void**)&m->b_wn_res[st], (size_t)L * dim * sizeof(float)));
     for (int i = 0; i < L; ++i) {
@@ -457,8 +370,8 @@ extern "C" int ns2_model_finalize(ns2_model* m, void* stream) {
       PackedW view = W; view.hi = W.hi + per * i; view.lo = W.lo ? W.lo + per * i : nullptr;
       NSCHK(pack_into(&view, cw->p, dim, 3, m->dp, identity_map(dim, W.rows_p), 0, 0, s));
       NSCHK(pack_into(&view, rw->p, dim, 1, m->dp, identity_map(dim, W.rows_p), 0, 3 * m->dp, s));
-      HIPCHK(hipMemcpyAsync(m->b_wn_conv[st] + (size_t)i * dim, cb->p, dim * sizeof(float), hipMemcpyDeviceToDevice, s));
-      HIPCHK(hipMemcpyAsync(m->b_wn_res[st] + (size_t)i * dim, rb->p, dim * sizeof(float), hipMemcpyDeviceToDevice, s));
+      HIPRET(hipMemcpyAsync(m->b_wn_conv[st] + (size_t)i * dim, cb->p, dim * sizeof(float), hipMemcpyDeviceToDevice, s));
+      HIPRET(hipMemcpyAsync(m->b_wn_res[st] + (size_t)i * dim, rb->p, dim * sizeof(float), hipMemcpyDeviceToDevice, s));
     }
   }
   { // skip convs of the last stack, concatenated along K; summed bias (NS2:639-640, 685-686, 725)
@@ -468,11 +381,11 @@ extern "C" int ns2_model_finalize(ns2_model* m, void* stream) {
       snprintf(key, sizeof key, "wavenet.stacks.%d.blocks.%d.skip_conv", S - 1, i);
       GETP(w, std::string(key) + ".weight"); GETP(b, std::string(key) + ".bias");
       NSCHK(pack_into(&m->w_skip, w->p, dim, 1, m->dp, identity_map(dim, m->w_skip.rows_p), 0, i * m->dp, s));
-      HIPCHK(hipMemcpy(hb.data(), b->p, dim * sizeof(float), hipMemcpyDeviceToHost));
+      HIPRET(hipMemcpy(hb.data(), b->p, dim * sizeof(float), hipMemcpyDeviceToHost));
       for (int c = 0; c < dim; ++c) bsum[c] += hb[c];
     }
     NSCHK(dev_alloc(&m->owned, (void**)&m->b_skip, dim * sizeof(float)));
-    HIPCHK(hipMemcpy(m->b_skip, bsum.data(), dim * sizeof(float), hipMemcpyHostToDevice));
+    HIPRET(hipMemcpy(m->b_skip, bsum.data(), dim * sizeof(float), hipMemcpyHostToDevice));
   }
   { GETP(w, "wavenet.final_conv.weight"); GETP(b, "wavenet.final_conv.bias");
     NSCHK(pack_linear(pc, &m->w_final, w->p, dim, dim, 1, s)); m->b_final = b->p; }
@@ -546,7 +459,7 @@ extern "C" int ns2_model_finalize(ns2_model* m, void* stream) {
       if (W.fmt != FMT_H8) continue;
       NSCHK(dev_alloc(&m->owned, (void**)&W.tw1, wavenet3_tiles_bytes(W.rows_p, m->dp, L, 1)));
       NSCHK(dev_alloc(&m->owned, (void**)&W.tw2, wavenet3_tiles_bytes(W.rows_p, m->dp, L, 2)));
-      HIPCHK(wavenet3_build_tiles(W.hi, W.rows_p, m->dp, L, W.tw1, W.tw2, s));
+      HIPRET(wavenet3_build_tiles(W.hi, W.rows_p, m->dp, L, W.tw1, W.tw2, s));
     }
   // tiled images of the per-step mixed linear weights (gemm3_kernel.h): +1 copy of 12.6 MB per layer at d512
   NSCHK(build_lin_tiles(&m->owned, &m->w_skip, s)); NSCHK(build_lin_tiles(&m->owned, &m->w_final, s)); NSCHK(build_lin_tiles(&m->owned, &m->w_pred, s));
@@ -566,10 +479,10 @@ extern "C" int ns2_model_finalize(ns2_model* m, void* stream) {
     NSCHK(dev_alloc(&m->owned, (void**)&m->d_param_ptrs, ptrs.size() * sizeof(float*)));
     NSCHK(dev_alloc(&m->owned, (void**)&m->d_param_numels, numels.size() * sizeof(long)));
     NSCHK(dev_alloc(&m->owned, (void**)&m->d_param_sums, 2 * ptrs.size() * sizeof(float)));
-    HIPCHK(hipMemcpy(m->d_param_ptrs, ptrs.data(), ptrs.size() * sizeof(float*), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(m->d_param_numels, numels.data(), numels.size() * sizeof(long), hipMemcpyHostToDevice));
+    HIPRET(hipMemcpy(m->d_param_ptrs, ptrs.data(), ptrs.size() * sizeof(float*), hipMemcpyHostToDevice));
+    HIPRET(hipMemcpy(m->d_param_numels, numels.data(), numels.size() * sizeof(long), hipMemcpyHostToDevice));
   }
-  HIPCHK(hipStreamSynchronize(s));
+  HIPRET(hipStreamSynchronize(s));
   m->finalized = true;
   return NS2_OK;
 }
@@ -582,8 +495,8 @@ extern "C" int ns2_model_param_checksum(ns2_model* m, float* host_out, int capac
   if (!m || !m->finalized || !host_out) { set_error("ns2_model_param_checksum: model not finalized / null output"); return NS2_ERR_STATE; }
   if (capacity < 2 * m->n_params) { set_error("ns2_model_param_checksum: output holds fewer than 2 * ns2_model_param_count floats"); return NS2_ERR_ARG; }
   hipStream_t s = (hipStream_t)stream;
-  HIPCHK(launch_param_sample(m->d_param_ptrs, m->d_param_numels, m->n_params, m->d_param_sums, s));
-  HIPCHK(hipMemcpyAsync(host_out, m->d_param_sums, 2 * (size_t)m->n_params * sizeof(float), hipMemcpyDeviceToHost, s));
+  HIPRET(launch_param_sample(m->d_param_ptrs, m->d_param_numels, m->n_params, m->d_param_sums, s));
+  HIPRET(hipMemcpyAsync(host_out, m->d_param_sums, 2 * (size_t)m->n_params * sizeof(float), hipMemcpyDeviceToHost, s));
   return NS2_OK;
 }
 
@@ -744,14 +657,22 @@ static int tap_f32(ns2_model* m, const char* name, const float* src, int64_t n, 
   auto it = m->taps.find(name);
   if (it == m->taps.end()) return NS2_OK;
   if (it->second.second < n) { set_error("tap '%s' needs %lld elements", name, (long long)n); return NS2_ERR_ARG; }
-  HIPCHK(hipMemcpyAsync(it->second.first, src, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+  HIPRET(hipMemcpyAsync(it->second.first, src, n * sizeof(float), hipMemcpyDeviceToDevice, s));
   return NS2_OK;
 }
 static int tap_planes(ns2_model* m, const char* name, Planes p, int ld, int64_t M, int d, hipStream_t s) {
   auto it = m->taps.find(name);
   if (it == m->taps.end()) return NS2_OK;
   if (it->second.second < M * d) { set_error("tap '%s' needs %lld elements", name, (long long)(M * d)); return NS2_ERR_ARG; }
-  HIPCHK(launch_join(p.hi, p.lo, ld, it->second.first, d, M, d, s, p.fmt));
+  HIPRET(launch_join(p.hi, p.lo, ld, it->second.first, d, M, d, s, p.fmt));
+  return NS2_OK;
+}
+
+// The passes' products: gemm_args() on operand Planes, the output planes of an epilogue, the launch.  Everything else a call uses it names
+// by field (ns2_kernels.h GemmArgs; the derived fields: ns2_host.h set_*).
+static GemmArgs product(const PackedW& w, const Planes& a, int lda, int M) { return gemm_args(w, a.hi, a.lo, lda, M); }
+static int run_gemm(const GemmArgs& g, int prec, hipStream_t s) {
+  HIPRET(launch_gemm(g, prec, s));
   return NS2_OK;
 }
 
@@ -765,7 +686,7 @@ static int attention_call(const bf16_t* q_hi, const bf16_t* q_lo, int ldq, int q
   a.vt_hi = vt.hi; a.vt_lo = vt.lo; a.vt_ld = vt_ld;
   a.o_hi = o.hi; a.o_lo = o.lo; a.ldo = ldo; a.o_fmt = o.fmt;
   a.B = B; a.H = H; a.Nq = Nq; a.Nk = Nk; a.scale = 1.0f / sqrtf((float)dim_head);       // dim_head ** -0.5  (ATT:128 / SDPA default; 0.125 exactly at 64)
-  HIPCHK(launch_attention(a, prec, s));
+  HIPRET(launch_attention(a, prec, s));
   return NS2_OK;
 }
 
@@ -775,7 +696,7 @@ static int norm_call(const float* x, int ldx, int M, int d, int seq_len, const f
   n.x = x; n.ldx = ldx; n.gamma = gamma; n.cond = cond; n.cond_ld = cond_ld;
   n.out_hi = out.hi; n.out_lo = out.lo; n.ldo = ldo; n.out_f = out_f; n.ldo_f = ldo_f;
   n.M = M; n.d = d; n.seq_len = seq_len; n.fmt = out.fmt;
-  HIPCHK(launch_rmsnorm(n, s));
+  HIPRET(launch_rmsnorm(n, s));
   return NS2_OK;
 }
 
@@ -796,14 +717,14 @@ extern "C" int ns2_model_cond_stack(ns2_model* m, const void* state_a, const voi
     if (e != hipSuccess) return e;
     return hipMemcpyAsync(static_cast<char*>(dst) + bytes, sb, bytes, hipMemcpyDeviceToDevice, s);
   };
-  HIPCHK(put(o.prompt_cond, a.prompt_cond, b.prompt_cond, sizeof(float) * (size_t)B * m->dt));
-  HIPCHK(put(o.pbias, a.pbias, b.pbias, sizeof(float) * (size_t)B * m->Jtot));
-  HIPCHK(put(o.condadd, a.condadd, b.condadd, sizeof(float) * (size_t)B * n_cond * m->dim));
+  HIPRET(put(o.prompt_cond, a.prompt_cond, b.prompt_cond, sizeof(float) * (size_t)B * m->dt));
+  HIPRET(put(o.pbias, a.pbias, b.pbias, sizeof(float) * (size_t)B * m->Jtot));
+  HIPRET(put(o.condadd, a.condadd, b.condadd, sizeof(float) * (size_t)B * n_cond * m->dim));
   const bool il = fmts_for(op_precision(m->cfg.precision)).xatt_il;
   const size_t eb = sizeof(bf16_t) * (il ? 2 : 1);
   for (int l = 0; l < m->cfg.depth; ++l) {
-    HIPCHK(put(o.ck[l].hi, a.ck[l].hi, b.ck[l].hi, eb * (size_t)B * m->Lm * m->a));
-    HIPCHK(put(o.cvt[l].hi, a.cvt[l].hi, b.cvt[l].hi, eb * (size_t)B * m->a * a.Lmp));
+    HIPRET(put(o.ck[l].hi, a.ck[l].hi, b.ck[l].hi, eb * (size_t)B * m->Lm * m->a));
+    HIPRET(put(o.cvt[l].hi, a.cvt[l].hi, b.cvt[l].hi, eb * (size_t)B * m->a * a.Lmp));
   }
   // (the 32-byte header slot of a state is reserved and unread)
   return NS2_OK;
@@ -832,58 +753,72 @@ extern "C" int ns2_model_prepare_cond(ns2_model* m, const float* prompt, int n_p
   float* ctok = w.latf;      // resampled prompt tokens c [B*Lm, dim] fp32 (final norm output or null tokens)
   if (drop) {
     // NS2:954-958, 964-968, 982-986: null substitutes
-    HIPCHK(launch_bcast_rows(m->null_prompt_cond, cs.prompt_cond, B, m->dt, m->dt, s));
-    HIPCHK(launch_bcast_rows(m->null_prompt_tokens, ctok, B, (long)Lm * dim, (long)Lm * dim, s));
-    HIPCHK(launch_split(ctok, dim, nullptr, 0, 0, 0, w.cpl.hi, w.cpl.lo, dp, B * Lm, dim, 0, s, w.cpl.fmt));
-    HIPCHK(launch_bcast_rows(m->null_cond, cs.condadd, B * n_cond, dim, dim, s));
+    HIPRET(launch_bcast_rows(m->null_prompt_cond, cs.prompt_cond, B, m->dt, m->dt, s));
+    HIPRET(launch_bcast_rows(m->null_prompt_tokens, ctok, B, (long)Lm * dim, (long)Lm * dim, s));
+    HIPRET(launch_split(ctok, dim, nullptr, 0, 0, 0, w.cpl.hi, w.cpl.lo, dp, B * Lm, dim, 0, s, w.cpl.fmt));
+    HIPRET(launch_bcast_rows(m->null_cond, cs.condadd, B * n_cond, dim, dim, s));
   } else {
     // to_prompt_cond: mean over n -> Linear -> SiLU (NS2:858-862)
-    HIPCHK(launch_mean_rows(prompt, B, n_prompt, dprompt, w.pmean, s));
-    HIPCHK(launch_skinny_linear(w.pmean, dprompt, m->wt_prompt, m->b_prompt, cs.prompt_cond, m->dt, B, dprompt, m->dt, 1, w.skinny_ws,
+    HIPRET(launch_mean_rows(prompt, B, n_prompt, dprompt, w.pmean, s));
+    HIPRET(launch_skinny_linear(w.pmean, dprompt, m->wt_prompt, m->b_prompt, cs.prompt_cond, m->dt, B, dprompt, m->dt, 1, w.skinny_ws,
                                 w.skinny_ws_bytes, s));
     // perceiver resampler (NS2:532-579)
     const int Nctx = w.Nctx;
     if (m->has_proj) {
-      HIPCHK(launch_split(prompt, dprompt, nullptr, 0, 0, 0, w.ctxp.hi, w.ctxp.lo, dpp, B * n_prompt, dprompt, 0, s, w.ctxp.fmt));
-      NSCHK(gemm_f32(m->w_proj, w.ctxp.hi, w.ctxp.lo, dpp, B * n_prompt, 0, 1, 0, m->b_proj, nullptr, 0, w.projf, dim, prec, s));
-      HIPCHK(hipMemcpy2DAsync(w.ctxf + (size_t)Lm * dim, (size_t)Nctx * dim * 4, w.projf, (size_t)n_prompt * dim * 4,
+      HIPRET(launch_split(prompt, dprompt, nullptr, 0, 0, 0, w.ctxp.hi, w.ctxp.lo, dpp, B * n_prompt, dprompt, 0, s, w.ctxp.fmt));
+      GemmArgs g = product(m->w_proj, w.ctxp, dpp, B * n_prompt);
+      g.bias = m->b_proj; g.out_f = w.projf; g.ldo_f = dim;
+      NSCHK(run_gemm(g, prec, s));
+      HIPRET(hipMemcpy2DAsync(w.ctxf + (size_t)Lm * dim, (size_t)Nctx * dim * 4, w.projf, (size_t)n_prompt * dim * 4,
                               (size_t)n_prompt * dim * 4, B, hipMemcpyDeviceToDevice, s));
     } else {
-      HIPCHK(hipMemcpy2DAsync(w.ctxf + (size_t)Lm * dim, (size_t)Nctx * dim * 4, prompt, (size_t)n_prompt * dim * 4,
+      HIPRET(hipMemcpy2DAsync(w.ctxf + (size_t)Lm * dim, (size_t)Nctx * dim * 4, prompt, (size_t)n_prompt * dim * 4,
                               (size_t)n_prompt * dim * 4, B, hipMemcpyDeviceToDevice, s));
     }
-    HIPCHK(launch_bcast_rows(m->latents, w.latf, B, (long)Lm * dim, (long)Lm * dim, s));
+    HIPRET(launch_bcast_rows(m->latents, w.latf, B, (long)Lm * dim, (long)Lm * dim, s));
     for (size_t l = 0; l < m->rlayers.size(); ++l) {
       const ns2_model::RLayer& r = m->rlayers[l];
       // context = cat(latents, x)  (NS2:1060-1061, cross_attn_include_queries)
-      HIPCHK(hipMemcpy2DAsync(w.ctxf, (size_t)Nctx * dim * 4, w.latf, (size_t)Lm * dim * 4, (size_t)Lm * dim * 4, B,
+      HIPRET(hipMemcpy2DAsync(w.ctxf, (size_t)Nctx * dim * 4, w.latf, (size_t)Lm * dim * 4, (size_t)Lm * dim * 4, B,
                               hipMemcpyDeviceToDevice, s));
-      HIPCHK(launch_split(w.ctxf, dim, nullptr, 0, 0, 0, w.ctxp.hi, w.ctxp.lo, dp, B * Nctx, dim, 0, s, w.ctxp.fmt));
-      HIPCHK(launch_split(w.latf, dim, nullptr, 0, 0, 0, w.latp.hi, w.latp.lo, dp, B * Lm, dim, 0, s, w.latp.fmt));
-      NSCHK(gemm_split(r.q, w.latp.hi, w.latp.lo, dp, B * Lm, 0, 1, 0, nullptr, w.qk.hi, w.qk.lo, a, prec, s, -1, 0, w.qk.fmt));
-      NSCHK(gemm_qkv(r.kv, w.ctxp.hi, w.ctxp.lo, dp, B * Nctx, Nctx, a, w.rkv.hi, w.rkv.lo, a, w.rvt.hi, w.rvt.lo, w.Nctxp, prec, s));
+      HIPRET(launch_split(w.ctxf, dim, nullptr, 0, 0, 0, w.ctxp.hi, w.ctxp.lo, dp, B * Nctx, dim, 0, s, w.ctxp.fmt));
+      HIPRET(launch_split(w.latf, dim, nullptr, 0, 0, 0, w.latp.hi, w.latp.lo, dp, B * Lm, dim, 0, s, w.latp.fmt));
+      GemmArgs q = product(r.q, w.latp, dp, B * Lm), kv = product(r.kv, w.ctxp, dp, B * Nctx);
+      set_out_planes(q, EPI_SPLIT, w.qk.hi, w.qk.lo, a); q.out_fmt = w.qk.fmt;
+      NSCHK(run_gemm(q, prec, s));
+      set_qkv(kv, prec, Nctx, a, w.rkv.hi, w.rkv.lo, a); kv.vt_hi = w.rvt.hi; kv.vt_lo = w.rvt.lo; kv.vt_ld = w.Nctxp;
+      NSCHK(run_gemm(kv, prec, s));
       NSCHK(attention_call(w.qk.hi, w.qk.lo, a, 0, w.rkv.hi, w.rkv.lo, a, 0, w.rvt, w.Nctxp, w.o, a, B, H, Lm, Nctx, prec, s, m->cfg.dim_head));
-      NSCHK(gemm_f32(r.out, w.o.hi, w.o.lo, a, B * Lm, 0, 1, 0, nullptr, w.latf, dim, w.latf, dim, prec, s));
+      GemmArgs o = product(r.out, w.o, a, B * Lm);
+      o.resid = w.latf; o.ldr = dim; o.out_f = w.latf; o.ldo_f = dim;
+      NSCHK(run_gemm(o, prec, s));
       // FeedForward without conv (NS2:1009-1025)
-      HIPCHK(launch_split(w.latf, dim, nullptr, 0, 0, 0, w.latp.hi, w.latp.lo, dp, B * Lm, dim, 0, s, w.latp.fmt));
-      NSCHK(gemm_geglu(r.ffin, w.latp.hi, w.latp.lo, dp, B * Lm, r.b_ffin, w.ffh.hi, w.ffh.lo, fp, prec, s));
-      NSCHK(gemm_f32(r.ffout, w.ffh.hi, w.ffh.lo, fp, B * Lm, 0, 1, 0, r.b_ffout, w.latf, dim, w.latf, dim, prec, s));
+      HIPRET(launch_split(w.latf, dim, nullptr, 0, 0, 0, w.latp.hi, w.latp.lo, dp, B * Lm, dim, 0, s, w.latp.fmt));
+      GemmArgs ffin = product(r.ffin, w.latp, dp, B * Lm), ffout = product(r.ffout, w.ffh, fp, B * Lm);
+      set_geglu(ffin, w.ffh.hi, w.ffh.lo, fp); ffin.bias = r.b_ffin;
+      NSCHK(run_gemm(ffin, prec, s));
+      ffout.bias = r.b_ffout; ffout.resid = w.latf; ffout.ldr = dim; ffout.out_f = w.latf; ffout.ldo_f = dim;
+      NSCHK(run_gemm(ffout, prec, s));
     }
     // final RMSNorm (NS2:579): tokens in fp32 (tap) and as planes for the per-layer K/V projections
     NSCHK(norm_call(w.latf, dim, B * Lm, dim, 0, m->g_resampler, nullptr, 0, w.cpl, dp, w.latf, dim, s));
     // cond_to_model_dim: 1x1 conv over channel-first cond [B, dprompt, n_cond] (NS2:978)
-    HIPCHK(launch_transpose_f32(cond, B, dprompt, n_cond, w.condT, s));
-    HIPCHK(launch_split(w.condT, dprompt, nullptr, 0, 0, 0, w.ctxp.hi, w.ctxp.lo, dpp, B * n_cond, dprompt, 0, s, w.ctxp.fmt));
-    NSCHK(gemm_f32(m->w_cond2model, w.ctxp.hi, w.ctxp.lo, dpp, B * n_cond, 0, 1, 0, m->b_cond2model, nullptr, 0, cs.condadd, dim, prec, s));
+    HIPRET(launch_transpose_f32(cond, B, dprompt, n_cond, w.condT, s));
+    HIPRET(launch_split(w.condT, dprompt, nullptr, 0, 0, 0, w.ctxp.hi, w.ctxp.lo, dpp, B * n_cond, dprompt, 0, s, w.ctxp.fmt));
+    GemmArgs g = product(m->w_cond2model, w.ctxp, dpp, B * n_cond);
+    g.bias = m->b_cond2model; g.out_f = cs.condadd; g.ldo_f = dim;
+    NSCHK(run_gemm(g, prec, s));
   }
   NSCHK(tap_f32(m, "c", ctok, (int64_t)B * Lm * dim, s));
   // the prompt half of every conditioning projection of the step: rows dt .. 2 dt of the K-major weight (t = cat(time, prompt_cond), NS2:960)
-  HIPCHK(launch_skinny_linear(cs.prompt_cond, m->dt, m->wt_cond + (size_t)m->dt * m->Jtot, m->b_cond, cs.pbias, m->Jtot, B, m->dt, m->Jtot, 0,
+  HIPRET(launch_skinny_linear(cs.prompt_cond, m->dt, m->wt_cond + (size_t)m->dt * m->Jtot, m->b_cond, cs.pbias, m->Jtot, B, m->dt, m->Jtot, 0,
                               w.skinny_ws, w.skinny_ws_bytes, s));
   // per-layer cross-attention keys / values of the (step-invariant) context (NS2:1063 with context = c)
-  for (int l = 0; l < m->cfg.depth; ++l)
-    NSCHK(gemm_qkv(m->layers[l].ckv, w.cpl.hi, w.cpl.lo, dp, B * Lm, Lm, a, cs.ck[l].hi, cs.ck[l].lo, a, cs.cvt[l].hi, cs.cvt[l].lo,
-                   cs.Lmp, prec, s, cs.ck[l].fmt));
+  for (int l = 0; l < m->cfg.depth; ++l) {
+    GemmArgs kv = product(m->layers[l].ckv, w.cpl, dp, B * Lm);
+    set_qkv(kv, prec, Lm, a, cs.ck[l].hi, cs.ck[l].lo, a, cs.ck[l].fmt); kv.vt_hi = cs.cvt[l].hi; kv.vt_lo = cs.cvt[l].lo; kv.vt_ld = cs.Lmp;
+    NSCHK(run_gemm(kv, prec, s));
+  }
   return NS2_OK;
 }
 
@@ -892,16 +827,16 @@ static int prof_start(ns2_model* m, int cat, hipStream_t s) {
   if (!(m->prof_mask & (1u << cat))) return NS2_OK;
   if (m->prof_used == m->prof_events.size()) {
     hipEvent_t a, b;
-    HIPCHK(hipEventCreate(&a));
-    HIPCHK(hipEventCreate(&b));
+    HIPRET(hipEventCreate(&a));
+    HIPRET(hipEventCreate(&b));
     m->prof_events.push_back(std::make_pair(a, b));
   }
-  HIPCHK(hipEventRecord(m->prof_events[m->prof_used].first, s));
+  HIPRET(hipEventRecord(m->prof_events[m->prof_used].first, s));
   return NS2_OK;
 }
 static int prof_stop(ns2_model* m, int cat, hipStream_t s) {
   if (!(m->prof_mask & (1u << cat))) return NS2_OK;
-  HIPCHK(hipEventRecord(m->prof_events[m->prof_used].second, s));
+  HIPRET(hipEventRecord(m->prof_events[m->prof_used].second, s));
   m->prof_used++;
   return NS2_OK;
 }
@@ -922,9 +857,9 @@ extern "C" int ns2_model_profile_end(ns2_model* m, double* total_ms, int64_t* la
   if (!m || !total_ms || !launches) return NS2_ERR_ARG;
   double tot = 0.0;
   for (size_t i = 0; i < m->prof_used; ++i) {
-    HIPCHK(hipEventSynchronize(m->prof_events[i].second));
+    HIPRET(hipEventSynchronize(m->prof_events[i].second));
     float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, m->prof_events[i].first, m->prof_events[i].second));
+    HIPRET(hipEventElapsedTime(&ms, m->prof_events[i].first, m->prof_events[i].second));
     tot += ms;
   }
   *total_ms = tot;
@@ -965,46 +900,62 @@ static int forward_impl(ns2_model* m, const float* x, const float* times, const 
   const float* call = w.condall;     // [gamma | beta] blocks of all FiLM / adaptive-norm projections; row b at call + b * cld
   int cld = Jtot;
   if (cond_row) {
-    if (cond) HIPCHK(launch_add_row(cond_row, cs.pbias, w.condall, B, Jtot, s));     // time half (hoisted) + prompt half (per utterance)
+    if (cond) HIPRET(launch_add_row(cond_row, cs.pbias, w.condall, B, Jtot, s));     // time half (hoisted) + prompt half (per utterance)
     else { call = cond_row; cld = 0; }                                                // every utterance reads the same row
   } else {
-    HIPCHK(launch_time_embed(times, m->freqs, m->wt_time, m->b_time, w.tfeat, w.t, m->Tc, B, dim, m->dt, w.skinny_ws, w.skinny_ws_bytes, s));
+    HIPRET(launch_time_embed(times, m->freqs, m->wt_time, m->b_time, w.tfeat, w.t, m->Tc, B, dim, m->dt, w.skinny_ws, w.skinny_ws_bytes, s));
     if (cond)
-      HIPCHK(hipMemcpy2DAsync(w.t + m->dt, (size_t)m->Tc * 4, cs.prompt_cond, (size_t)m->dt * 4, (size_t)m->dt * 4, B,
+      HIPRET(hipMemcpy2DAsync(w.t + m->dt, (size_t)m->Tc * 4, cs.prompt_cond, (size_t)m->dt * 4, (size_t)m->dt * 4, B,
                               hipMemcpyDeviceToDevice, s));
     NSCHK(tap_f32(m, "t", w.t, (int64_t)B * m->Tc, s));
-    HIPCHK(launch_skinny_linear(w.t, m->Tc, m->wt_cond, m->b_cond, w.condall, Jtot, B, m->Tc, Jtot, 0, w.skinny_ws, w.skinny_ws_bytes, s));
+    HIPRET(launch_skinny_linear(w.t, m->Tc, m->wt_cond, m->b_cond, w.condall, Jtot, B, m->Tc, Jtot, 0, w.skinny_ws, w.skinny_ws_bytes, s));
   }
 
   // ---- x (+ aligned conditioning, NS2:976-992) -> split planes
-  HIPCHK(launch_split(x, dim, cond ? cs.condadd : nullptr, dim, n_cond, cond ? cs.n_cond_valid : 0, w.xs.hi, w.xs.lo, dp, M, dim, N, s, w.xs.fmt));
+  HIPRET(launch_split(x, dim, cond ? cs.condadd : nullptr, dim, n_cond, cond ? cs.n_cond_valid : 0, w.xs.hi, w.xs.lo, dp, M, dim, N, s, w.xs.fmt));
 
   // ---- wavenet (NS2:718-725)
-  PROF(PC_GEMM_SPLIT, gemm_split(m->w_init, w.xs.hi, w.xs.lo, dp, M, 3, 1, N, m->b_init, w.h0.hi, w.h0.lo, dp, prec, s));
+  {
+    GemmArgs g = product(m->w_init, w.xs, dp, M);
+    set_conv(g, m->w_init, 3, 1, N);
+    set_out_planes(g, EPI_SPLIT, w.h0.hi, w.h0.lo, dp); g.bias = m->b_init;
+    PROF(PC_GEMM_SPLIT, run_gemm(g, prec, s));
+  }
   NSCHK(tap_planes(m, "wavenet.init", w.h0, dp, M, dim, s));
   Planes cur = w.wA, prev = w.wB;
   for (int st = 0; st < S; ++st) {
-    const bf16_t* a_hi = (st == 0) ? w.h0.hi : prev.hi;
-    const bf16_t* a_lo = (st == 0) ? w.h0.lo : prev.lo;
-    const int lda = (st == 0) ? dp : L * dp;
-    const long a_zs = (st == 0) ? 0 : dp;
-    PROF(PC_GEMM_WAVENET, gemm_wavenet(m->w_wn[st], a_hi, a_lo, lda, a_zs, M, N, /*dil=*/1, /*dil_z=*/1, /*nz=*/L, m->b_wn_conv[st], m->b_wn_res[st],
-                       dim, call + (size_t)st * L * 2 * dim, cld, 2 * dim, cur.hi, cur.lo, L * dp, dp, dp, prec, s,
-                       /*p1_half=*/hybrid_plan(m->cfg.precision) ? 1 : 0));
+    // the L columns of the stack as grid-z layers: layer z reads column block z of the previous stack (all of them h0 for the first),
+    // runs at dilation 1 << z with its own matrix, biases and FiLM row, and writes column block z
+    GemmArgs g = (st == 0) ? product(m->w_wn[st], w.h0, dp, M) : product(m->w_wn[st], prev, L * dp, M);
+    set_wavenet(g, m->w_wn[st], 1, N, prec, hybrid_plan(m->cfg.precision) ? 1 : 0);
+    g.dil_z = 1; g.nz = L; g.a_zs = (st == 0) ? 0 : dp; g.bias_zs = dim; g.film_zs = 2 * dim; g.out_zs = dp;
+    g.bias = m->b_wn_conv[st]; g.bias2 = m->b_wn_res[st]; g.film = call + (size_t)st * L * 2 * dim; g.film_ld = cld;
+    g.out_hi = cur.hi; g.out_lo = cur.lo; g.ldo_s = L * dp; g.out_ncols = dp;
+    PROF(PC_GEMM_WAVENET, run_gemm(g, prec, s));
     snprintf(name, sizeof name, "wavenet.stack%d", st);
     NSCHK(tap_planes(m, name, cur, L * dp, M, L * dp, s));
     Planes tmp = prev; prev = cur; cur = tmp;
   }
   // sum of the 8 skip convs == one GEMM over the concatenated columns (NS2:639-640, 685-686, 725), then final_conv
-  PROF(PC_GEMM_SPLIT, gemm_split(m->w_skip, prev.hi, prev.lo, L * dp, M, 0, 1, 0, m->b_skip, w.ssum.hi, w.ssum.lo, dp, prec, s));
+  {
+    GemmArgs g = product(m->w_skip, prev, L * dp, M);
+    set_out_planes(g, EPI_SPLIT, w.ssum.hi, w.ssum.lo, dp); g.bias = m->b_skip;
+    PROF(PC_GEMM_SPLIT, run_gemm(g, prec, s));
+  }
   // Every update of the residual stream is followed by exactly one RMSNorm that reads it (NS2:794-807, 781-784): `update_then_norm` runs
-  // the pair as one launch where the GEMM's workgroups own whole rows (dim = 128; gemm_f32_norm), else as the GEMM + rmsnorm_kernel.
+  // the pair as one launch where the GEMM's workgroups own whole rows (dim = 128: the 128 x 128 kernel, gemm.hip; gemm_fuses_norm says
+  // so), else as the GEMM + rmsnorm_kernel.  cld == 0 with ncond != null: every utterance reads the same (gamma, beta) row (the time table).
   const float* cbase = call + (size_t)S * L * 2 * dim;
   auto update_then_norm = [&](const PackedW& pw, const Planes& a, int lda, const float* bias, bool add_resid, int gprec, const float* gamma,
                               const float* ncond, const Planes& nout) -> int {
-    bool fused = false;
-    PROF(PC_GEMM_F32, gemm_f32_norm(pw, a.hi, a.lo, lda, M, bias, add_resid ? w.xres : nullptr, dim, w.xres, dim, gprec, N, gamma, ncond, cld,
-                                    nout.hi, nout.lo, dp, nout.fmt, s, &fused));
+    GemmArgs g = product(pw, a, lda, M);
+    g.bias = bias; g.resid = add_resid ? w.xres : nullptr; g.ldr = dim; g.out_f = w.xres; g.ldo_f = dim;
+    const bool fused = gemm_fuses_norm(g, gprec);
+    if (fused) {
+      g.nrm_hi = nout.hi; g.nrm_lo = nout.lo; g.nrm_ld = dp; g.nrm_fmt = nout.fmt;
+      g.nrm_gamma = gamma; g.nrm_cond = ncond; g.nrm_cond_ld = cld; g.nrm_seq_len = N;
+    }
+    PROF(PC_GEMM_F32, run_gemm(g, gprec, s));
     if (!fused) PROF(PC_NORM, norm_call(w.xres, dim, M, dim, N, gamma, ncond, cld, nout, dp, nullptr, 0, s));
     return NS2_OK;
   };
@@ -1018,28 +969,37 @@ static int forward_impl(ns2_model* m, const float* x, const float* times, const 
     const ns2_model::Layer& ly = m->layers[l];
     const bool last = l + 1 == m->cfg.depth;
     // self attention (its norm ran behind the previous update)
-    PROF(PC_GEMM_QKV, gemm_qkv(ly.qkv, w.xn.hi, w.xn.lo, dp, M, N, 2 * a, w.qk.hi, w.qk.lo, 2 * a, w.vt.hi, w.vt.lo, w.Nkp, prec, s));
+    GemmArgs qkv = product(ly.qkv, w.xn, dp, M);
+    set_qkv(qkv, prec, N, 2 * a, w.qk.hi, w.qk.lo, 2 * a); qkv.vt_hi = w.vt.hi; qkv.vt_lo = w.vt.lo; qkv.vt_ld = w.Nkp;
+    PROF(PC_GEMM_QKV, run_gemm(qkv, prec, s));
     PROF(PC_ATTENTION, attention_call(w.qk.hi, w.qk.lo, 2 * a, 0, w.qk.hi, w.qk.lo, 2 * a, a, w.vt, w.Nkp, w.o, a, B, H, N, N, prec, s, m->cfg.dim_head));
     // out-projection + residual, then the norm of what follows: the cross attention (conditioned) or the feed-forward
     NSCHK(update_then_norm(ly.out, w.o, a, nullptr, true, prec, nullptr, layer_cond(l, cond ? 1 : m->nnorm - 1), cond ? w.xn : xn_ff));
     snprintf(name, sizeof name, "layer%d.attn", l);
     NSCHK(tap_f32(m, name, w.xres, (int64_t)M * dim, s));
     if (cond) {   // cross attention to the resampled prompt tokens (NS2:799-803)
-      PROF(PC_GEMM_SPLIT, gemm_split(ly.cq, w.xn.hi, w.xn.lo, dp, M, 0, 1, 0, nullptr, w.xq.hi, w.xq.lo, a, prec, s, -1, 0, w.xq.fmt));
+      GemmArgs cq = product(ly.cq, w.xn, dp, M);
+      set_out_planes(cq, EPI_SPLIT, w.xq.hi, w.xq.lo, a); cq.out_fmt = w.xq.fmt;
+      PROF(PC_GEMM_SPLIT, run_gemm(cq, prec, s));
       PROF(PC_ATTENTION, attention_call(w.xq.hi, w.xq.lo, a, 0, cs.ck[l].hi, cs.ck[l].lo, a, 0, cs.cvt[l], cs.Lmp, w.o, a, B, H, N, Lm, xprec, s, m->cfg.dim_head));
       NSCHK(update_then_norm(ly.cout, w.o, a, nullptr, true, prec, nullptr, layer_cond(l, m->nnorm - 1), xn_ff));
     }
     // feedforward: Linear -> GEGLU -> causal conv k3 -> Linear (NS2:1009-1025); precision 6: the whole branch on dense IEEE-half planes
-    PROF(PC_GEMM_GEGLU, gemm_geglu(ly.ffin, xn_ff.hi, xn_ff.lo, dp, M, ly.b_ffin, w.ffh_conv.hi, w.ffh_conv.lo, fpc, ff_prec, s, w.ffh_conv.fmt, fp));
-    PROF(PC_GEMM_FFCONV, gemm_split(ly.conv, w.ffh_conv.hi, w.ffh_conv.lo, fpc, M, 3, 1, N, ly.b_conv, ffc_ff.hi, ffc_ff.lo, fp,
-                                    conv_prec, s, -1, 0, ffc_ff.fmt));
+    GemmArgs ffin = product(ly.ffin, xn_ff, dp, M), conv = product(ly.conv, w.ffh_conv, fpc, M);
+    set_geglu(ffin, w.ffh_conv.hi, w.ffh_conv.lo, fpc, fp); ffin.bias = ly.b_ffin; ffin.out_fmt = w.ffh_conv.fmt;
+    PROF(PC_GEMM_GEGLU, run_gemm(ffin, ff_prec, s));
+    set_conv(conv, ly.conv, 3, 1, N);
+    set_out_planes(conv, EPI_SPLIT, ffc_ff.hi, ffc_ff.lo, fp); conv.bias = ly.b_conv; conv.out_fmt = ffc_ff.fmt;
+    PROF(PC_GEMM_FFCONV, run_gemm(conv, conv_prec, s));
     // FF-out + residual, then the next layer's self-attention norm -- or to_pred's RMSNorm (learned gamma, NS2:781-784) after the last
     NSCHK(update_then_norm(ly.ffout, ffc_ff, fp, ly.b_ffout, true, ff_prec, last ? m->g_pred : nullptr, last ? nullptr : layer_cond(l + 1, 0), w.xn));
     snprintf(name, sizeof name, "layer%d", l);
     NSCHK(tap_f32(m, name, w.xres, (int64_t)M * dim, s));
   }
   // to_pred: Linear on the normed stream (NS2:781-784)
-  PROF(PC_GEMM_F32, gemm_f32(m->w_pred, w.xn.hi, w.xn.lo, dp, M, 0, 1, 0, nullptr, nullptr, 0, out, dim, prec, s));
+  GemmArgs pred = product(m->w_pred, w.xn, dp, M);
+  pred.out_f = out; pred.ldo_f = dim;
+  PROF(PC_GEMM_F32, run_gemm(pred, prec, s));
   return NS2_OK;
 }
 
@@ -1084,8 +1044,8 @@ extern "C" int ns2_model_time_table(ns2_model* m, const float* times, int T, int
   float* ws = c.take<float>((int64_t)(wsb / sizeof(float)));
   for (int t0 = 0; t0 < T; t0 += 32) {
     const int nb = std::min(32, T - t0);
-    HIPCHK(launch_time_embed(times + t0, m->freqs, m->wt_time, m->b_time, feat, tt, m->dt, nb, m->dim, m->dt, ws, wsb, s, plan_B));
-    HIPCHK(launch_skinny_linear(tt, m->dt, m->wt_cond, cond ? nullptr : m->b_cond, table + (size_t)t0 * m->Jtot, m->Jtot, nb, kt, m->Jtot, 0, ws,
+    HIPRET(launch_time_embed(times + t0, m->freqs, m->wt_time, m->b_time, feat, tt, m->dt, nb, m->dim, m->dt, ws, wsb, s, plan_B));
+    HIPRET(launch_skinny_linear(tt, m->dt, m->wt_cond, cond ? nullptr : m->b_cond, table + (size_t)t0 * m->Jtot, m->Jtot, nb, kt, m->Jtot, 0, ws,
                                 wsb, s, plan_B));
   }
   return NS2_OK;

@@ -12,6 +12,28 @@ namespace ns2 {
 
 void set_error(const char* fmt, ...);
 
+// how an entry point gives up: a failed HIP call / a refused argument / a failed step -> the last error + the C ABI's code
+#define HIPRET(expr)                                                                 \
+  do {                                                                               \
+    hipError_t _e = (expr);                                                          \
+    if (_e != hipSuccess) {                                                          \
+      ns2::set_error("%s:%d %s -> %s", __FILE__, __LINE__, #expr, hipGetErrorString(_e)); \
+      return NS2_ERR_HIP;                                                            \
+    }                                                                                \
+  } while (0)
+#define ARGCHK(cond, msg)            \
+  do {                               \
+    if (!(cond)) {                   \
+      ns2::set_error("%s", msg);     \
+      return NS2_ERR_ARG;            \
+    }                                \
+  } while (0)
+#define NSCHK(expr)                  \
+  do {                               \
+    int _r = (expr);                 \
+    if (_r != NS2_OK) return _r;     \
+  } while (0)
+
 // The dropout fields of a C argument block (ns2_attn_args / ns2_attn_bwd_args) -> the drop_* fields of the kernels' block (AttnArgs /
 // AttnBwdArgs, whose defaults mean "none").  Returns what is wrong with them, or null.  p == 0: the seed is not read (may be null) and
 // the kernels without dropout run.
@@ -24,7 +46,7 @@ inline const char* set_attn_dropout(KernelArgs& a, float p, const uint32_t* seed
   return nullptr;
 }
 
-struct PackedW {                 // bf16 split-plane weight, rows padded to 128, K contiguous
+struct PackedW {                 // bf16 split-plane weight, rows padded to 256, K contiguous
   bf16_t* hi = nullptr; bf16_t* lo = nullptr;
   int rows_p = 0, ldk = 0, N = 0, nkt = 0, kt_per_tap = 0;
   int fmt = 0;                   // PlaneFmt: bf16 planes (precisions 1 / 3), dense IEEE half (2), FMT_H8 lines (4)
@@ -33,28 +55,41 @@ struct PackedW {                 // bf16 split-plane weight, rows padded to 128,
   bf16_t* t3 = nullptr;          // k = 3 conv weights in dense IEEE half: the tiled LDS images of the dedicated FF-conv kernel (ffconv_kernel.h), or null
 };
 
-int gemm_f32(const PackedW& w, const bf16_t* a_hi, const bf16_t* a_lo, int lda, int M, int conv_taps, int dil, int seq_len,
-             const float* bias, const float* resid, int ldr, float* out, int ldo, int prec, hipStream_t s, int pad_left = -1,
-             int act = 0);
-int gemm_f32_norm(const PackedW& w, const bf16_t* a_hi, const bf16_t* a_lo, int lda, int M, const float* bias, const float* resid, int ldr,
-                  float* out, int ldo, int prec, int seq_len, const float* gamma, const float* cond, int cond_ld, bf16_t* n_hi, bf16_t* n_lo,
-                  int n_ld, int n_fmt, hipStream_t s, bool* fused);
-int gemm_split(const PackedW& w, const bf16_t* a_hi, const bf16_t* a_lo, int lda, int M, int conv_taps, int dil, int seq_len,
-               const float* bias, bf16_t* o_hi, bf16_t* o_lo, int ldo, int prec, hipStream_t s, int pad_left = -1, int act = 0,
-               int out_fmt = -1);
-int gemm_geglu(const PackedW& w, const bf16_t* a_hi, const bf16_t* a_lo, int lda, int M, const float* pbias, bf16_t* o_hi,
-               bf16_t* o_lo, int ldo, int prec, hipStream_t s, int out_fmt = -1, int out_ncols = 0);   // out_ncols: columns written (zeros beyond f); 0 = ldo
-int gemm_qkv(const PackedW& w, const bf16_t* a_hi, const bf16_t* a_lo, int lda, int M, int seq_len, int split_col,
-             bf16_t* o_hi, bf16_t* o_lo, int ldo, bf16_t* vt_hi, bf16_t* vt_lo, int vt_ld, int prec, hipStream_t s, int att_fmt = -1);
-int gemm_wavenet(const PackedW& w, const bf16_t* a_hi, const bf16_t* a_lo, int lda, long a_zs, int M, int seq_len, int dil,
-                 int dil_z, int nz, const float* b_conv, const float* b_res, long bias_zs, const float* film, int film_ld,
-                 long film_zs, bf16_t* o_hi, bf16_t* o_lo, int ldo, long out_zs, int out_ncols, int prec, hipStream_t s, int p1_half = 0);
+// One host path from a packed weight to launch_gemm, shared by capi.cpp and model_exec.cpp.  A caller takes gemm_args(), names the
+// fields of ns2_kernels.h GemmArgs it uses (epilogue operands, outputs), and lets the setters below derive what only this layer knows.
+// gemm_args: the weight, the activations and this thread's split-K scratch (model_exec.cpp SplitKScope) in an otherwise default block
+GemmArgs gemm_args(const PackedW& w, const bf16_t* a_hi, const bf16_t* a_lo, int lda, int M);
+inline void set_conv(GemmArgs& g, const PackedW& w, int taps, int dil, int seq_len) {
+  g.kt_per_tap = w.kt_per_tap; g.conv_taps = taps; g.dil = dil; g.seq_len = seq_len;
+}
+inline void set_out_planes(GemmArgs& g, int epi, bf16_t* hi, bf16_t* lo, int ldo) {
+  g.epi = epi; g.out_hi = hi; g.out_lo = lo; g.ldo_s = ldo; g.out_ncols = ldo;
+}
+// EPI_GEGLU: out_ncols = columns written (zeros beyond f); 0 = ldo
+inline void set_geglu(GemmArgs& g, bf16_t* hi, bf16_t* lo, int ldo, int out_ncols = 0) {
+  set_out_planes(g, EPI_GEGLU, hi, lo, ldo);
+  if (out_ncols > 0) g.out_ncols = out_ncols;
+}
+// EPI_QKV: q | k (columns < split_col) are attention operands -- attention_fmt(prec), or att_fmt for both them and V^T when the
+// caller's attention runs in another format; the values fill vt_rows = N - split_col rows per utterance of the transposed planes
+inline void set_qkv(GemmArgs& g, int prec, int seq_len, int split_col, bf16_t* hi, bf16_t* lo, int ldo, int att_fmt = -1) {
+  set_out_planes(g, EPI_QKV, hi, lo, ldo);
+  g.seq_len = seq_len; g.split_col = split_col; g.out_ncols = split_col; g.vt_rows = g.N - split_col;
+  g.out_fmt = att_fmt >= 0 ? att_fmt : attention_fmt(prec);
+  if (att_fmt >= 0) g.vt_fmt = att_fmt;
+}
+// EPI_WAVENET: the dilated k = 3 conv, the gate at the K tile where the res conv's tap starts; nz > 1 steps through matrices laid back
+// to back.  p1_half (the dilated conv as one half product) exists at precision 4 only.
+inline void set_wavenet(GemmArgs& g, const PackedW& w, int dil, int seq_len, int prec, int p1_half) {
+  set_conv(g, w, 3, dil, seq_len);
+  g.epi = EPI_WAVENET; g.mid_kt = 3 * w.kt_per_tap; g.w_zs = (long)w.rows_p * w.ldk; g.p1_half = (prec == 4) ? p1_half : 0;
+}
 
 int pack_weight_public(const float* w, int rows, int cols, int taps, int geglu, const float* extra, int precision, PackedW* out,
                        std::vector<void*>* owned, hipStream_t s);
 std::vector<int> geglu_row_map(int f, int rows_p);
-int build_conv3_tiles(std::vector<void*>* owned, PackedW* w, hipStream_t s);
-int build_lin_tiles(std::vector<void*>* owned, PackedW* w, hipStream_t s);     // model_exec.cpp: (re)build w->tl (FMT_H8 packs; a no-op for other formats)   // model_exec.cpp: (re)build w->t3 from the row-major pack
+int build_conv3_tiles(std::vector<void*>* owned, PackedW* w, hipStream_t s);   // model_exec.cpp: (re)build w->t3 from the row-major pack
+int build_lin_tiles(std::vector<void*>* owned, PackedW* w, hipStream_t s);     // model_exec.cpp: (re)build w->tl (FMT_H8 packs; a no-op for other formats)
 
 }  // namespace ns2
 

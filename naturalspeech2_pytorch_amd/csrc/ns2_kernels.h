@@ -35,6 +35,11 @@ struct DynLdsAttr {
 // split-plane operands: a lo plane implies the interleaved [hi32|lo32] row layout, i.e. lo == hi + 32 (ns2_common.h)
 inline bool planes_ok(const bf16_t* hi, const bf16_t* lo) { return lo == nullptr || lo == hi + 32; }
 
+// The two format rules of a precision, each written once: what the GEMMs multiply in and write for each other (bf16 planes for 1 / 3, dense
+// IEEE half for 2, FMT_H8 lines for 4), and what the attention kernels read (q, k, V^T: IEEE half also at precision 4)
+inline int operand_fmt(int precision) { return precision == 2 ? FMT_F16 : (precision == 4 ? FMT_H8 : FMT_BF16); }
+inline int attention_fmt(int precision) { return (precision == 2 || precision == 4) ? FMT_F16 : FMT_BF16; }
+
 enum GemmEpilogue : int {
   EPI_F32 = 0,      // out_f = acc + bias (+ resid)
   EPI_SPLIT = 1,    // split planes = acc + bias
@@ -43,56 +48,57 @@ enum GemmEpilogue : int {
   EPI_WAVENET = 4,  // mid-loop FiLM + tanh*sigmoid gate, second K phase = res conv, split planes out
 };
 
+// Every field has a default: a default-constructed block is a valid "nothing optional" block (zero / null except the six sentinels
+// dil, mid_kt, nz, pad_left, out_fmt, vt_fmt), and a caller names only what it uses
 struct GemmArgs {
   // A operand: activations, bf16 split planes [M, lda]; every ld / column count in this struct is LOGICAL (the
   // physical row stride is 2*ld when the lo plane exists, see ns2_common.h); a_zs / out_zs are logical column offsets
-  const bf16_t* a_hi; const bf16_t* a_lo; int lda;
+  const bf16_t* a_hi = nullptr; const bf16_t* a_lo = nullptr; int lda = 0;
   // W operand: packed weights, bf16 split planes [ceil(N/128)*128, ldw], K contiguous
-  const bf16_t* w_hi; const bf16_t* w_lo; int ldw;
-  const bf16_t* w_tl;       // optional: the same FMT_H8 linear weight as tiled LDS images (gemm3_kernel.h); null = none
-  const bf16_t* w_tw1; const bf16_t* w_tw2;   // optional (EPI_WAVENET, hybrid plan): tiled images of the dilated conv's half parts / of the res conv (wavenet3_kernel.h)
-  const bf16_t* w_t3;       // optional: the same conv weight (k = 3, dense IEEE half) as tiled LDS images (ffconv_kernel.h); null = none
-  int M, N;          // N = valid output columns
-  int nkt;           // number of 32-wide K tiles (total, all taps/phases)
-  int kt_per_tap;    // K tiles per tap (plain linear: == nkt)
-  int conv_taps;     // taps [0, conv_taps) are causal-shifted by (conv_taps-1-tap)*dil rows; later taps unshifted
-  int dil; int dil_z;// dilation; if dil_z the effective dilation is dil << blockIdx-z
-  int seq_len;       // tokens per utterance (rows never read across an utterance start); 0 = no sequence structure
-  int mid_kt;        // EPI_WAVENET: K tile index at which the gate transform runs
-  int p1_half;       // EPI_WAVENET at precision 4: the taps before mid_kt run as ONE half product (no fp8 correction terms, the byte half of the lines is not fetched)
-  int epi;
+  const bf16_t* w_hi = nullptr; const bf16_t* w_lo = nullptr; int ldw = 0;
+  const bf16_t* w_tl = nullptr;   // optional: the same FMT_H8 linear weight as tiled LDS images (gemm3_kernel.h); null = none
+  const bf16_t* w_tw1 = nullptr; const bf16_t* w_tw2 = nullptr;   // optional (EPI_WAVENET, hybrid plan): tiled images of the dilated conv's half parts / of the res conv (wavenet3_kernel.h)
+  const bf16_t* w_t3 = nullptr;   // optional: the same conv weight (k = 3, dense IEEE half) as tiled LDS images (ffconv_kernel.h); null = none
+  int M = 0, N = 0;      // N = valid output columns
+  int nkt = 0;           // number of 32-wide K tiles (total, all taps/phases)
+  int kt_per_tap = 0;    // K tiles per tap (plain linear: == nkt)
+  int conv_taps = 0;     // taps [0, conv_taps) are causal-shifted by (conv_taps-1-tap)*dil rows; later taps unshifted
+  int dil = 1; int dil_z = 0;   // dilation; if dil_z the effective dilation is dil << blockIdx-z
+  int seq_len = 0;       // tokens per utterance (rows never read across an utterance start); 0 = no sequence structure
+  int mid_kt = -1;       // EPI_WAVENET: K tile index at which the gate transform runs
+  int p1_half = 0;       // EPI_WAVENET at precision 4: the taps before mid_kt run as ONE half product (no fp8 correction terms, the byte half of the lines is not fetched)
+  int epi = EPI_F32;
   // epilogue operands
-  const float* bias; const float* bias2;
-  const float* film; int film_ld;           // gamma at film[b*film_ld + col], beta at film[b*film_ld + N + col]
-  const float* resid; int ldr;
-  float* out_f; int ldo_f;
-  long out_f_zs;     // EPI_F32 with nz > 1: slice z writes out_f + z * out_f_zs (split-K partial sums of the weight gradients)
-  bf16_t* out_hi; bf16_t* out_lo; int ldo_s; int out_ncols;   // writes columns [0, out_ncols) (zero beyond N)
-  bf16_t* vt_hi; bf16_t* vt_lo; int vt_ld; int vt_rows; int split_col;
+  const float* bias = nullptr; const float* bias2 = nullptr;
+  const float* film = nullptr; int film_ld = 0;   // gamma at film[b*film_ld + col], beta at film[b*film_ld + N + col]
+  const float* resid = nullptr; int ldr = 0;
+  float* out_f = nullptr; int ldo_f = 0;
+  long out_f_zs = 0;     // EPI_F32 with nz > 1: slice z writes out_f + z * out_f_zs (split-K partial sums of the weight gradients)
+  bf16_t* out_hi = nullptr; bf16_t* out_lo = nullptr; int ldo_s = 0; int out_ncols = 0;   // writes columns [0, out_ncols) (zero beyond N)
+  bf16_t* vt_hi = nullptr; bf16_t* vt_lo = nullptr; int vt_ld = 0; int vt_rows = 0; int split_col = 0;
   // batching over blockIdx-z (wavenet columns): element offsets per z
-  int nz; long a_zs, w_zs, bias_zs, film_zs, out_zs;
-  int pad_left;      // conv: zero rows in front of the sequence (-1 = causal: conv_taps-1); k=9 'same' padding = 4
-  int act;           // 1 = SiLU after the bias (EPI_F32 / EPI_SPLIT)
-  int out_fmt;       // PlaneFmt of the split-plane output (ns2_common.h).  -1 = "the operand format of the precision":
-                     // bf16 planes for 1 / 3, dense IEEE half for 2, FMT_H8 for 4.  Attention operands (q, k: EPI_QKV
-                     // columns < split_col, the cross-attention q projection) are IEEE half also at precision 4.
-  int vt_fmt;        // PlaneFmt of the transposed value planes (FMT_BF16 or FMT_F16); -1 = the attention format of the precision
+  int nz = 1; long a_zs = 0, w_zs = 0, bias_zs = 0, film_zs = 0, out_zs = 0;
+  int pad_left = -1;     // conv: zero rows in front of the sequence (-1 = causal: conv_taps-1); k=9 'same' padding = 4
+  int act = 0;           // 1 = SiLU after the bias (EPI_F32 / EPI_SPLIT)
+  int out_fmt = -1;      // PlaneFmt of the split-plane output (ns2_common.h).  -1 = operand_fmt(precision).  Attention operands (q, k:
+                         // EPI_QKV columns < split_col, the cross-attention q projection) are attention_fmt(precision).
+  int vt_fmt = -1;       // PlaneFmt of the transposed value planes (FMT_BF16 or FMT_F16); -1 = attention_fmt(precision)
   // Split-K for products too small to fill the chip (a batch of 1 ... 4 utterances: 8 ... 100 output tiles on 256 CUs, each a
   // serial K loop).  The caller lends scratch (sk_ws: fp32, sk_ws_floats elements; null = never split); launch_gemm then runs
   // the 128x128 kernel over grid-z K slices writing raw fp32 partial sums into fixed slots and a second launch that adds the
   // slots in slot order and applies the requested epilogue -- deterministic.  ksplit is set by launch_gemm: K tiles of EVERY tap
   // one slice covers (slice z: input columns [z * ksplit * 32, ...) of each tap); 0 = the plain launch.
-  float* sk_ws; long sk_ws_floats;
-  int ksplit;
+  float* sk_ws = nullptr; long sk_ws_floats = 0;
+  int ksplit = 0;
   // EPI_F32 on the 128 x 128 kernel with N == 128 (the dim = 128 model: a workgroup owns WHOLE rows): the RMSNorm that follows the
   // residual stream's update (NS2:727-746, 794-807) inside the same epilogue -- out_f = acc + bias + resid as always, then
   // nrm planes = F.normalize(out_f row) * sqrt(N) [* nrm_gamma] [* cond_g + cond_b] in format nrm_fmt, the next GEMM's operand.
   // nrm_hi == null: not requested.  gemm_fuses_norm() says whether launch_gemm will honour it for a given shape.
-  bf16_t* nrm_hi; bf16_t* nrm_lo; int nrm_ld, nrm_fmt;
-  const float* nrm_gamma; const float* nrm_cond; int nrm_cond_ld, nrm_seq_len;
+  bf16_t* nrm_hi = nullptr; bf16_t* nrm_lo = nullptr; int nrm_ld = 0, nrm_fmt = 0;
+  const float* nrm_gamma = nullptr; const float* nrm_cond = nullptr; int nrm_cond_ld = 0, nrm_seq_len = 0;
   // launch_gemm_tr only (weight gradients from token-major planes, gemm2.hip TR): tokens the operands have, channels per tap block of
   // the N dimension (a multiple of 32), taps (0 / 1: no shift; tap t of a causal conv reads token m - (tr_taps - 1 - t) * dil)
-  int tr_tokens, tr_kp, tr_taps;
+  int tr_tokens = 0, tr_kp = 0, tr_taps = 0;
 };
 
 // precision: 3 = bf16 x3 ("exact"), 1 = bf16 ("fast"), 2 = one IEEE-half product ("half"), 4 = half product + both
@@ -105,13 +111,13 @@ void force_gemm_kernel(int k);                                          // test 
 // the dedicated FF causal conv kernel (ffconv_kernel.h, compiled in gemm2.hip): tiled weight images
 size_t ffconv3_tiled_bytes_of(int N, int Cp);
 hipError_t ffconv3_build_tiles(const bf16_t* w_hi, int ldw, int Cp, int rows_p, int N, bf16_t* out, hipStream_t s);
-int ffconv3_lda(int Cp);
+int ffconv3_lda(int Cp);                                                  // activations' row length (elements) the kernel wants for Cp packed columns per tap
 // the lean mixed linear kernel (gemm3_kernel.h, compiled in gemm2.hip): tiled weight images of an FMT_H8 pack [rows_p][ldk]
 size_t gemm3_tiled_bytes_of(int rows_p, int nkt);
 hipError_t gemm3_build_tiles(const bf16_t* w_hi, int ldk, int rows_p, bf16_t* out, hipStream_t s);
 // the lean Wavenet block kernel of the hybrid plan (wavenet3_kernel.h): tiled images of a stack's nz matrices [rows_p][4 dp]
 size_t wavenet3_tiles_bytes(int rows_p, int dp, int nz, int phase);
-hipError_t wavenet3_build_tiles(const bf16_t* w_hi, int rows_p, int dp, int nz, bf16_t* t1, bf16_t* t2, hipStream_t s);                                                // activations' row length (elements) the kernel wants for Cp packed columns per tap
+hipError_t wavenet3_build_tiles(const bf16_t* w_hi, int rows_p, int dp, int nz, bf16_t* t1, bf16_t* t2, hipStream_t s);
 constexpr long SPLITK_SCRATCH_FLOATS = 512L * 128 * 128;                // what any split needs at most: slices x output tiles <= 512 tiles of 128 x 128 (32 MiB)
 
 // flash attention forward, head dim 64, non-causal (ATT:77-155 hot path).  Every field has a default: a default-constructed block is a

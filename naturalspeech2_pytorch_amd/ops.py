@@ -169,12 +169,20 @@ class PackedWeight:
             pass
 
 
+def _linear(w: PackedWeight, a: Planes, M: int, precision: int, **fields):
+    """The one place that fills a ns2_linear_args (include/ns2hip.h) and calls ns2_linear.  `fields`: the block's other fields by name
+    (device addresses or ints; what is not named stays zero = feature off)."""
+    args = _lib.LinearArgs(w=w.handle, a_hi=a.hi, a_lo=a.lo, lda=a.ld, M=M, precision=precision, **fields)
+    check(_lib.load().ns2_linear(args, _stream()), "ns2_linear")
+
+
 def linear_f32(w: PackedWeight, a: Planes, M: Optional[int] = None, bias=None, resid=None, conv_taps=0, dilation=1,
-               seq_len=0, precision=3, pad_left=-1, act=0) -> torch.Tensor:
+               seq_len=0, precision=3, pad_left=-1, act=0, ldo: Optional[int] = None) -> torch.Tensor:
+    """-> fp32 [M, ldo] (ldo defaults to the weight's rows; columns beyond them are NOT written); resid: fp32 rows of any row stride"""
     M = M or a.rows
-    out = torch.empty(M, w.rows, dtype=torch.float32, device=a.device)
-    check(_lib.load().ns2_linear_f32(w.handle, a.hi, a.lo, a.ld, M, conv_taps, dilation, seq_len, _p(bias),
-                                     _p(resid), w.rows, out.data_ptr(), w.rows, pad_left, act, precision, _stream()), "ns2_linear_f32")
+    out = torch.empty(M, ldo or w.rows, dtype=torch.float32, device=a.device)
+    _linear(w, a, M, precision, conv_taps=conv_taps, dilation=dilation, seq_len=seq_len, pad_left=pad_left, bias=_p(bias), act=act,
+            out_f32=out.data_ptr(), ldo_f=out.shape[1], resid=_p(resid), ldr=resid.stride(0) if resid is not None else 0)
     return out
 
 
@@ -185,17 +193,13 @@ def conv3_input_ld(cols: int) -> int:
 
 def linear_split(w: PackedWeight, a: Planes, bias=None, conv_taps=0, dilation=1, seq_len=0, precision=3, ldo=None, pad_left=-1,
                  act=0, out_precision=None) -> Planes:
-    """out_precision: write the output planes in the operand format of another precision (ns2_linear_split_as), e.g. FMT_H8 lines (4)
-    from a precision-2 product -- what the hybrid plan's FF causal conv does"""
+    """out_precision: write the output planes in the operand format of another precision, e.g. FMT_H8 lines (4) from a precision-2
+    product -- what the hybrid plan's FF causal conv does -- or bf16 hi / lo lines (3) for the attention of the mixed training arithmetic"""
     M = a.rows
     ldo = ldo or round_up(w.rows, 32)
     out = _out_planes(M, ldo, a.device, out_precision or precision)
-    if out_precision is None:
-        check(_lib.load().ns2_linear_split(w.handle, a.hi, a.lo, a.ld, M, conv_taps, dilation, seq_len, _p(bias),
-                                           out.hi, out.lo, ldo, pad_left, act, precision, _stream()), "ns2_linear_split")
-    else:
-        check(_lib.load().ns2_linear_split_as(w.handle, a.hi, a.lo, a.ld, M, conv_taps, dilation, seq_len, _p(bias),
-                                              out.hi, out.lo, ldo, pad_left, act, precision, out_precision, _stream()), "ns2_linear_split_as")
+    _linear(w, a, M, precision, conv_taps=conv_taps, dilation=dilation, seq_len=seq_len, pad_left=pad_left, bias=_p(bias), act=act,
+            out_hi=out.hi, out_lo=out.lo, ldo=ldo, out_precision=out_precision or 0)
     return out
 
 
@@ -208,11 +212,9 @@ def geglu_pack_bias(bias: torch.Tensor, f: int) -> torch.Tensor:
 
 def linear_geglu(w: PackedWeight, a: Planes, packed_bias: torch.Tensor, precision=3) -> Planes:
     M = a.rows
-    f = w.rows // 2
-    ldo = round_up(f, 32)
+    ldo = round_up(w.rows // 2, 32)
     out = _out_planes(M, ldo, a.device, precision)
-    check(_lib.load().ns2_linear_geglu(w.handle, a.hi, a.lo, a.ld, M, packed_bias.data_ptr(), out.hi,
-                                       out.lo, ldo, precision, _stream()), "ns2_linear_geglu")
+    _linear(w, a, M, precision, bias=packed_bias.data_ptr(), out_hi=out.hi, out_lo=out.lo, ldo=ldo)
     return out
 
 
@@ -222,11 +224,9 @@ def linear_qkv(w: PackedWeight, a: Planes, seq_len: int, split_col: int, precisi
     B = M // seq_len
     vt_ld = round_up(seq_len, 32)
     out = _out_planes(M, split_col, a.device, precision, attention_operand=True)
-    vt_rows = w.rows - split_col
-    vt = _out_planes(B * vt_rows, vt_ld, a.device, precision, attention_operand=True, zero=True)
-    check(_lib.load().ns2_linear_qkv(w.handle, a.hi, a.lo, a.ld, M, seq_len, split_col, out.hi,
-                                     out.lo, split_col, vt.hi, vt.lo, vt_ld, precision, _stream()),
-          "ns2_linear_qkv")
+    vt = _out_planes(B * (w.rows - split_col), vt_ld, a.device, precision, attention_operand=True, zero=True)
+    _linear(w, a, M, precision, seq_len=seq_len, split_col=split_col, out_hi=out.hi, out_lo=out.lo, ldo=split_col,
+            vt_hi=vt.hi, vt_lo=vt.lo, vt_ld=vt_ld)
     return out, vt
 
 

@@ -58,23 +58,13 @@ class HipBackend:
 
     def gemm_f32(self, pw, a, bias=None, resid=None, taps=0, dil=1, seq_len=0, pad_left=-1):
         """-> fp32 [M, ldo] with ldo = round_up(N, 32); columns >= N are NOT written"""
-        M, N = a.rows, pw.rows
-        ldo = round_up(N, 32)
-        out = torch.empty(M, ldo, dtype=torch.float32, device=a.device)
-        ldr = resid.stride(0) if resid is not None else 0
-        check(self.lib.ns2_linear_f32(pw.handle, a.hi, a.lo, a.ld, M, taps, dil, seq_len, _p(bias), _p(resid), ldr, out.data_ptr(), ldo,
-                                      pad_left, 0, self.prec, _stream()), "ns2_linear_f32")
-        return out
+        return ops.linear_f32(pw, a, bias=bias, resid=resid, conv_taps=taps, dilation=dil, seq_len=seq_len, precision=self.prec,
+                              pad_left=pad_left, ldo=round_up(pw.rows, 32))
 
     def gemm_split(self, pw, a, bias=None, taps=0, dil=1, seq_len=0, attn=False):
         """-> operand planes; attn=True: attention operands (q | k | v), bf16 hi / lo lines whatever the GEMM arithmetic"""
-        if attn and self.prec != 3:
-            M, ldo = a.rows, round_up(pw.rows, 32)
-            out = ops.empty_planes(M, ldo, a.device)
-            check(self.lib.ns2_linear_split_as(pw.handle, a.hi, a.lo, a.ld, M, taps, dil, seq_len, _p(bias), out.hi, out.lo, ldo, -1, 0,
-                                               self.prec, 3, _stream()), "ns2_linear_split_as")
-            return out
-        return ops.linear_split(pw, a, bias=bias, conv_taps=taps, dilation=dil, seq_len=seq_len, precision=self.prec)
+        return ops.linear_split(pw, a, bias=bias, conv_taps=taps, dilation=dil, seq_len=seq_len, precision=self.prec,
+                                out_precision=3 if attn and self.prec != 3 else None)
 
     def film_gate_fwd(self, h, film, seq_len, d):
         out = torch.empty(h.shape[0], d, dtype=torch.float32, device=h.device)

@@ -98,7 +98,7 @@ def test_header_is_plain_c_and_a_c_caller_links_against_the_library(tmp_path):
 int main(void) {
   /* addresses of entry points from every section of the header: unresolved symbols fail the link */
   typedef void (*fn_t)(void);
-  fn_t fns[] = {(fn_t)ns2_weight_pack, (fn_t)ns2_linear_f32, (fn_t)ns2_linear_qkv, (fn_t)ns2_attention_fwd,
+  fn_t fns[] = {(fn_t)ns2_weight_pack, (fn_t)ns2_linear, (fn_t)ns2_attention_fwd,
                        (fn_t)ns2_rmsnorm, (fn_t)ns2_rvq_encode, (fn_t)ns2_model_create,
                        (fn_t)ns2_model_forward, (fn_t)ns2_ddim_step, (fn_t)ns2_weights_repack, (fn_t)ns2_weights_retile,
                        (fn_t)ns2_attention_bwd, (fn_t)ns2_weight_tile_linear, (fn_t)ns2_model_cond_stack};
@@ -107,7 +107,7 @@ int main(void) {
   ns2_model_config cfg;                       /* the config struct is plain ints */
   cfg.dim = 64; cfg.depth = 1; cfg.dim_head = 48; cfg.heads = 2;
   printf("%d %d %d %d\n", n, ns2_version(), ns2_conv3_input_ld(1365), (int)sizeof(cfg) % (int)sizeof(int));
-  /* the layout of the two attention argument blocks, for the ctypes mirrors: size, then offsets of a field of each kind */
+  /* the layout of the argument blocks, for the ctypes mirrors: size, then offsets of a field of each kind */
 #define OFF(t, f) (int)offsetof(t, f)
   printf("%d %d %d %d %d %d %d %d %d %d %d\n", (int)sizeof(ns2_attn_args), OFF(ns2_attn_args, q_lo), OFF(ns2_attn_args, k_hi),
          OFF(ns2_attn_args, o_hi), OFF(ns2_attn_args, scale), OFF(ns2_attn_args, head_dim), OFF(ns2_attn_args, key_mask),
@@ -115,6 +115,8 @@ int main(void) {
   printf("%d %d %d %d %d %d %d %d %d %d\n", (int)sizeof(ns2_attn_bwd_args), OFF(ns2_attn_bwd_args, k_hi), OFF(ns2_attn_bwd_args, lse),
          OFF(ns2_attn_bwd_args, dq), OFF(ns2_attn_bwd_args, scale), OFF(ns2_attn_bwd_args, gp_hi), OFF(ns2_attn_bwd_args, gp_kv),
          OFF(ns2_attn_bwd_args, key_mask), OFF(ns2_attn_bwd_args, dropout_p), OFF(ns2_attn_bwd_args, dropout_call));
+  printf("%d %d %d %d %d %d %d\n", (int)sizeof(ns2_linear_args), OFF(ns2_linear_args, a_hi), OFF(ns2_linear_args, lda), OFF(ns2_linear_args, out_f32),
+         OFF(ns2_linear_args, out_precision), OFF(ns2_linear_args, vt_hi), OFF(ns2_linear_args, vt_ld));
   return ns2_debug_force_gemm(99) == 0;       /* argument errors come back as codes, nothing throws across the ABI */
 }
 ''')
@@ -124,8 +126,8 @@ int main(void) {
     subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-pedantic", "-I", inc, "-fsyntax-only", str(src)], check=True)
     subprocess.run(["gcc", "-std=c99", "-I", inc, str(src), "-o", str(exe), "-L", libdir, "-lns2hip", "-Wl,-rpath," + libdir], check=True)
     out = subprocess.run([str(exe)], check=True, capture_output=True, text=True, timeout=120).stdout.split()
-    assert out[0] == "14" and int(out[1]) >= 115 and int(out[2]) == 1408 and out[3] == "0", out
-    # ... and the ctypes mirrors of the two attention argument blocks have the header's layout: same size, same field offsets
+    assert out[0] == "13" and int(out[1]) >= 120 and int(out[2]) == 1408 and out[3] == "0", out
+    # ... and the ctypes mirrors of the argument blocks have the header's layout: same size, same field offsets
     import ctypes
 
     def layout(cls, fields):
@@ -133,7 +135,9 @@ int main(void) {
     fwd = layout(_lib.AttnArgs, ("q_lo", "k_hi", "o_hi", "scale", "head_dim", "key_mask", "lse", "dropout_p", "dropout_seed", "dropout_call"))
     bwd = layout(_lib.AttnBwdArgs, ("k_hi", "lse", "dq", "scale", "gp_hi", "gp_kv", "key_mask", "dropout_p", "dropout_call"))
     assert [int(v) for v in out[4:4 + len(fwd)]] == fwd, (out, fwd)
-    assert [int(v) for v in out[4 + len(fwd):]] == bwd and len(out) == 4 + len(fwd) + len(bwd), (out, bwd)
+    assert [int(v) for v in out[4 + len(fwd):4 + len(fwd) + len(bwd)]] == bwd, (out, bwd)
+    lin = layout(_lib.LinearArgs, ("a_hi", "lda", "out_f32", "out_precision", "vt_hi", "vt_ld"))
+    assert [int(v) for v in out[4 + len(fwd) + len(bwd):]] == lin and len(out) == 4 + len(fwd) + len(bwd) + len(lin), (out, lin)
 
 
 def test_attention_entries_refuse_bad_argument_blocks_before_any_device_call():
@@ -164,6 +168,30 @@ def test_attention_entries_refuse_bad_argument_blocks_before_any_device_call():
     bwd = _lib.AttnBwdArgs(q_hi=64, q_lo=96, k_hi=128, k_lo=160, v_hi=192, v_lo=224, do_hi=256, do_lo=288, lse=512, delta=768, dq=1024,
                            ldq=64, ldk=64, ldv=64, lddo=64, lddq=64, B=1, H=1, Nq=8, Nk=8, scale=0.125, dropout_p=0.2)
     assert refused(lib.ns2_attention_bwd(bwd, None), "ns2_attention_bwd", "seed")
+
+
+def test_linear_entry_refuses_bad_argument_blocks_before_any_device_call():
+    """ns2_linear validates what needs only the block before it reads the weight or makes a HIP call: each of these comes back as a non-zero
+    code whose message starts with the entry's name and names the field (no GPU here; the dummy pointers are never dereferenced)."""
+    lib = _lib.load()
+
+    def lin(**kw):
+        f = dict(w=64, a_hi=128, a_lo=192, lda=64, M=64, precision=3, out_f32=256, ldo_f=64)
+        f.update(kw)
+        return _lib.LinearArgs(**f)
+
+    def refused(rc, word):
+        """(the last error is sticky: a stale message would not name `word`)"""
+        msg = (lib.ns2_last_error() or b"").decode()
+        return rc != 0 and msg.startswith("ns2_linear:") and word in msg
+
+    assert refused(lib.ns2_linear(None, None), "null argument block")
+    assert refused(lib.ns2_linear(lin(w=None), None), "w is null")
+    assert refused(lib.ns2_linear(lin(a_hi=None), None), "a_hi is null")
+    assert refused(lib.ns2_linear(lin(precision=0), None), "precision must be")
+    assert refused(lib.ns2_linear(lin(precision=5), None), "precision must be")
+    assert refused(lib.ns2_linear(lin(out_f32=None), None), "neither out_f32 nor out_hi")
+    assert refused(lib.ns2_linear(lin(out_hi=512, out_lo=576, ldo=64), None), "both out_f32 and out_hi")
 
 
 def test_transformer_state_dict_contract():
