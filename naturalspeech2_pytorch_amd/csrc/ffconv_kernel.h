@@ -265,7 +265,7 @@ struct Kern {
     ga.M = g.M; ga.N = g.N; ga.bias = g.bias; ga.out_hi = g.out; ga.out_lo = (PF == PF_H8) ? g.out + 32 : nullptr;
     ga.ldo_s = g.ldo; ga.out_ncols = g.out_ncols; ga.out_fmt = (PF == PF_H8) ? FMT_H8 : FMT_F16; ga.epi = EPI_SPLIT;
     if (col_base + 64 <= g.N) epi_planes_fast<PF, true>(c.acc, ga, 0, row_base, col_base, lane, smem + wave * EPI_LDS_WAVE_BYTES);
-    else gemm_epilogue<EPI_SPLIT, 4, 2>(c.acc, ga, 0, row_base, col_base, 0, lane);
+    else gemm_epilogue<EPI_SPLIT, 4>(c.acc, ga, 0, row_base, col_base, 0, lane);
   }
 
   static NS2_DEVINL void run(const Args& g) {

@@ -22,7 +22,7 @@
 // double-buffered (one barrier per K-tile), rows padded to 80 B so that both the 16-B ds_write of the
 // staging pass and the ds_read_b128 fragment reads are bank-conflict free (80 = 5 x 16 B, 5 coprime to the
 // 16 slots of a 256-B bank row).  Tile ids are remapped so that consecutive ids share an XCD L2 (T1).
-#include "gemm_epi_fast.h"
+#include "gemm_epi_dispatch.h"
 #include "gemm_route.h"
 
 namespace ns2 {
@@ -39,55 +39,6 @@ struct Stage {                                // registers holding one prefetche
 
 NS2_DEVINL uint4 ld16(const bf16_t* p) { return *reinterpret_cast<const uint4*>(p); }
 NS2_DEVINL uint4 zero16() { return make_uint4(0u, 0u, 0u, 0u); }
-
-// Interior 64 x 64 wave tile (every row and column valid): the streamlined epilogues of gemm_epi_fast.h through `wbuf`, the wave's
-// private LDS region of WBUF bytes.  Returns false when the tile, the alignment or the format asks for the generic path.
-// HALF / BF: which plane formats this caller can be asked for (a kernel on IEEE-half operands writes F16 / H8, one on bf16 operands
-// bf16 planes; the split-K finishing kernel serves both).
-template <int EPI, int WBUF, bool HALF, bool BF, bool BF_DENSE>
-NS2_DEVINL bool small_tile_fast_epilogue(f32x16 (&acc)[2][2], const GemmArgs& g, int z, int row_base, int col_base, int ocol_base, int lane,
-                                         unsigned char* wbuf) {
-  if constexpr (EPI == EPI_F32) return false;
-  if (row_base + 64 > g.M) return false;
-  const bool al = (reinterpret_cast<uintptr_t>(g.out_hi) & 15) == 0 && (g.ldo_s & 31) == 0;
-  auto planes = [&](auto&& fn) __attribute__((always_inline)) {
-    if (!al) return false;
-    if constexpr (HALF) {
-      if (g.out_fmt == FMT_F16 && !g.out_lo) { fn(std::integral_constant<int, PF_F16>{}); return true; }
-      if (g.out_fmt == FMT_H8) { fn(std::integral_constant<int, PF_H8>{}); return true; }
-    }
-    if constexpr (BF) {
-      if (g.out_fmt == FMT_BF16 && g.out_lo) { fn(std::integral_constant<int, PF_BF16IL>{}); return true; }
-    }
-    if constexpr (BF_DENSE) {
-      if (g.out_fmt == FMT_BF16 && !g.out_lo) { fn(std::integral_constant<int, PF_BF16>{}); return true; }
-    }
-    return false;
-  };
-  if constexpr (EPI == EPI_SPLIT) {
-    if (col_base + 64 <= g.N && g.act == 0)
-      return planes([&](auto pf) __attribute__((always_inline)) { epi_planes_fast<decltype(pf)::value, true, 2, WBUF>(acc, g, z, row_base, col_base, lane, wbuf); });
-  } else if constexpr (EPI == EPI_WAVENET) {
-    if (col_base + 64 <= g.N)
-      return planes([&](auto pf) __attribute__((always_inline)) { epi_planes_fast<decltype(pf)::value, false, 2, WBUF>(acc, g, z, row_base, col_base, lane, wbuf); });
-  } else if constexpr (EPI == EPI_GEGLU) {
-    static_assert(EPI != EPI_GEGLU || WBUF >= 9216, "64 staged rows of a 128-byte output line + pad");
-    if (ocol_base + 32 <= g.out_ncols)
-      return planes([&](auto pf) __attribute__((always_inline)) { epi_geglu_fast<decltype(pf)::value, 2>(acc, g, row_base, col_base, ocol_base, lane, wbuf); });
-  } else if constexpr (EPI == EPI_QKV) {
-    static_assert(EPI != EPI_QKV || WBUF >= 9216, "64 feature rows of 64 tokens + pad");
-    if (col_base + 64 <= g.N && !g.bias) {
-      if (col_base + 64 <= g.split_col)
-        return planes([&](auto pf) __attribute__((always_inline)) { epi_planes_fast<decltype(pf)::value, false, 2, WBUF>(acc, g, 0, row_base, col_base, lane, wbuf); });
-      if (col_base >= g.split_col && !g.vt_lo && g.seq_len > 0 && (g.seq_len & 63) == 0 && (g.vt_ld & 7) == 0 &&
-          (reinterpret_cast<uintptr_t>(g.vt_hi) & 15) == 0) {
-        if (HALF && g.vt_fmt == FMT_F16) { epi_vt_fast<true, 2>(acc, g, row_base, col_base, lane, wbuf); return true; }
-        if ((BF || BF_DENSE) && g.vt_fmt == FMT_BF16) { epi_vt_fast<false, 2>(acc, g, row_base, col_base, lane, wbuf); return true; }
-      }
-    }
-  }
-  return false;
-}
 
 template <int NSPLIT, int EPI, bool F16>
 __global__ __launch_bounds__(256, 2) void gemm_kernel(const GemmArgs g) {
@@ -178,7 +129,7 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const GemmArgs g) {
       for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.f;
 
   // epilogue coordinates of this lane
-  const int row_base = tm * BM + wm * 64;     // + mi*32 + (r&3) + 8*(r>>2) + 4*hi
+  const int row_base = tm * BM + wm * 64;     // + mi*32 + acc_row(r, hi)
   const int col_base = tn * BN + wn * 64;     // + ni*32 + l31
 
   // 32-column sub-tiles of this wave that hold real output columns (wave-uniform): the SEANet codec's 1 ... 32-channel
@@ -296,117 +247,9 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const GemmArgs g) {
     run_k(0, nkt, std::false_type{});
   }
 
-  // Round 3: interior wave tiles of the fp32 epilogue (the SEANet codec's 16 ... 128-channel convolutions run here, 80 k blocks
-  // per launch on the early layers) leave through the wave's share of the now idle LDS ring as 16-byte stores of whole row
-  // segments, with the bounds tested once per wave -- the generic epilogue below tests and branches per stored value.
-  if constexpr (EPI == EPI_F32) {
-    const int nvc = min(64, g.N - col_base);                     // valid columns of this wave tile
-    if (nvc <= 0) return;
-    if (row_base + 64 <= g.M && nvc >= 16 && (nvc & (nvc - 1)) == 0 && g.act == 0 && (g.ldo_f & 3) == 0 &&
-        (reinterpret_cast<uintptr_t>(g.out_f) & 15) == 0 &&
-        (!g.resid || ((g.ldr & 3) == 0 && (reinterpret_cast<uintptr_t>(g.resid) & 15) == 0))) {
-      // two passes of 32 rows: 32 x (64 fp32 + 16 B pad) = 8.5 KiB fits the wave's share of the ring in every arithmetic mode
-      // (10 KiB with one operand plane staged, 20 KiB with two; round 4: the single-plane kernels took the per-value path before)
-      constexpr int RS = 272;
-      unsigned char* wbuf = smem + wave * (STAGE_BYTES / 2);
-      const float bc0 = (g.bias && col_base + l31 < g.N) ? g.bias[col_base + l31] : 0.f;
-      const float bc1 = (g.bias && col_base + 32 + l31 < g.N) ? g.bias[col_base + 32 + l31] : 0.f;
-      const int lcpr = 31 - __builtin_clz(nvc >> 2);              // log2(16-byte chunks per row): 2, 3 or 4
-      const int lr0 = lane >> lcpr, ch = lane & ((1 << lcpr) - 1), rpi = 64 >> lcpr;
-      // Round 5 -- the RMSNorm behind a residual update, in the same epilogue (launch_gemm guarantees N == 128 == BN and M % 128 == 0,
-      // so this block owns 128 whole rows and all four waves are here): the lane keeps its 16 float4 of x, the row's sum of squares
-      // is 16 lanes of this wave + the partner wave's half (wn ^ 1) through 64 floats of LDS per wave, added in a fixed order.
-      if (g.nrm_hi) {
-        float4 keep[2][8];
-        float* s_part = reinterpret_cast<float*>(smem + wave * (STAGE_BYTES / 2) + 32 * RS);      // 64 floats in the slack behind the staged rows
-#pragma unroll
-        for (int mi = 0; mi < 2; ++mi) {
-#pragma unroll
-          for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-              const int lr = (r & 3) + 8 * (r >> 2) + 4 * hi;
-              *reinterpret_cast<float*>(wbuf + lr * RS + (ni * 32 + l31) * 4) = acc[mi][ni][r] + (ni ? bc1 : bc0);
-            }
-          __builtin_amdgcn_wave_barrier();
-#pragma unroll
-          for (int it = 0; it < 8; ++it) {                          // 64 columns: 16 lanes per row, 4 rows per iteration
-            const int lr = it * 4 + (lane >> 4);
-            float4 v = *reinterpret_cast<const float4*>(wbuf + lr * RS + (lane & 15) * 16);
-            const long row = row_base + mi * 32 + lr;
-            if (g.resid) {
-              const float4 rr = *reinterpret_cast<const float4*>(g.resid + row * g.ldr + col_base + (lane & 15) * 4);
-              v.x += rr.x; v.y += rr.y; v.z += rr.z; v.w += rr.w;
-            }
-            *reinterpret_cast<float4*>(g.out_f + row * g.ldo_f + col_base + (lane & 15) * 4) = v;
-            keep[mi][it] = v;
-            float ss = v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
-            ss += __shfl_xor(ss, 1, 64); ss += __shfl_xor(ss, 2, 64); ss += __shfl_xor(ss, 4, 64); ss += __shfl_xor(ss, 8, 64);
-            if ((lane & 15) == 0) s_part[mi * 32 + lr] = ss;
-          }
-          __builtin_amdgcn_wave_barrier();
-        }
-        __syncthreads();
-        const float* p0 = reinterpret_cast<const float*>(smem + (wm * 2 + 0) * (STAGE_BYTES / 2) + 32 * RS);
-        const float* p1 = reinterpret_cast<const float*>(smem + (wm * 2 + 1) * (STAGE_BYTES / 2) + 32 * RS);
-        const float scale = sqrtf((float)g.N);
-        const bool nil = g.nrm_lo != nullptr;
-        const int c = col_base + (lane & 15) * 4;
-        float gm[4] = {1.f, 1.f, 1.f, 1.f};
-        if (g.nrm_gamma) { const float4 t = *reinterpret_cast<const float4*>(g.nrm_gamma + c); gm[0] = t.x; gm[1] = t.y; gm[2] = t.z; gm[3] = t.w; }
-#pragma unroll
-        for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-          for (int it = 0; it < 8; ++it) {
-            const int lr = it * 4 + (lane >> 4);
-            const long row = row_base + mi * 32 + lr;
-            const float tot = p0[mi * 32 + lr] + p1[mi * 32 + lr];
-            const float inv = scale / fmaxf(sqrtf(tot), 1e-12f);   // F.normalize eps (NS2:727-746)
-            float o[4] = {keep[mi][it].x * inv, keep[mi][it].y * inv, keep[mi][it].z * inv, keep[mi][it].w * inv};
-            if (g.nrm_gamma) { o[0] *= gm[0]; o[1] *= gm[1]; o[2] *= gm[2]; o[3] *= gm[3]; }
-            if (g.nrm_cond) {
-              const float* gc = g.nrm_cond + (g.nrm_seq_len > 0 ? row / g.nrm_seq_len : 0) * (long)g.nrm_cond_ld;
-              const float4 t = *reinterpret_cast<const float4*>(gc + c), u = *reinterpret_cast<const float4*>(gc + g.N + c);
-              o[0] = o[0] * t.x + u.x; o[1] = o[1] * t.y + u.y; o[2] = o[2] * t.z + u.z; o[3] = o[3] * t.w + u.w;
-            }
-            store_cols4(g.nrm_hi + row * pld(g.nrm_ld, nil), c, o[0], o[1], o[2], o[3], g.nrm_fmt, nil);
-          }
-        return;
-      }
-#pragma unroll
-      for (int mi = 0; mi < 2; ++mi) {
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int lr = (r & 3) + 8 * (r >> 2) + 4 * hi;
-            *reinterpret_cast<float*>(wbuf + lr * RS + (ni * 32 + l31) * 4) = acc[mi][ni][r] + (ni ? bc1 : bc0);
-          }
-        __builtin_amdgcn_wave_barrier();
-        for (int it = 0; it < (32 >> (6 - lcpr)); ++it) {         // 32 rows / rpi
-          const int lr = it * rpi + lr0;
-          float4 v = *reinterpret_cast<const float4*>(wbuf + lr * RS + ch * 16);
-          const long row = row_base + mi * 32 + lr;
-          if (g.resid) {
-            const float4 rr = *reinterpret_cast<const float4*>(g.resid + row * g.ldr + col_base + ch * 4);
-            v.x += rr.x; v.y += rr.y; v.z += rr.z; v.w += rr.w;
-          }
-          *reinterpret_cast<float4*>(g.out_f + z * g.out_f_zs + row * g.ldo_f + col_base + ch * 4) = v;
-        }
-        __builtin_amdgcn_wave_barrier();
-      }
-      return;
-    }
-  }
-  // Round 4: interior wave tiles of the plane-writing epilogues take gemm_epi_fast.h's route too (the dim = 128 model's Wavenet
-  // blocks run here: 2048 blocks per launch whose generic epilogue -- a bounds test, a run-time format switch and a 2 ... 4 byte
-  // store per value -- cost more than their 16 K tiles; small batches put QKV / GEGLU here as well)
-  if constexpr (EPI != EPI_F32) {
-    constexpr int WBUF = STAGE_BYTES / 2;
-    if (small_tile_fast_epilogue<EPI, WBUF, F16, !F16, (!F16 && NSPLIT == 1)>(acc, g, z, row_base, col_base, tn * 64 + wn * 32, lane, smem + wave * WBUF))
-      return;
-  }
-  gemm_epilogue<EPI, 2, 2>(acc, g, z, row_base, col_base, tn * 64 + wn * 32, lane);
+  // the wave's share of the now idle LDS ring stages its tile (gemm_epi_dispatch.h): 10 KiB with one operand plane staged, 20 KiB with two
+  constexpr int WBUF = STAGE_BYTES / 2;
+  wave_tile_epilogue<EPI, 2, G1Formats<NSPLIT, F16>, WBUF>(acc, g, z, row_base, col_base, tn * 64 + wn * 32, lane, smem + wave * WBUF);
 }
 
 template <int NSPLIT, int EPI, bool F16>
@@ -437,7 +280,7 @@ static hipError_t launch_epi(const GemmArgs& g, hipStream_t s) {
 
 // ---- split-K, second launch: the slots of the first launch (raw fp32 partial sums, [S][M][ldp]) are added in slot order in
 // the accumulator layout of a 64 x 64 wave tile, then the REQUESTED epilogue runs on the sums -- the same device code the
-// one-launch product would have run (gemm_epi.h), so every format, bias, residual, V^T and range-guard rule holds unchanged.
+// one-launch product would have run (wave_tile_epilogue), so every format, bias, residual, V^T and range-guard rule holds unchanged.
 template <int EPI>
 __global__ __launch_bounds__(256) void splitk_finish_kernel(const GemmArgs g, const float* part, int S, long slot, int ldp) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -457,7 +300,7 @@ __global__ __launch_bounds__(256) void splitk_finish_kernel(const GemmArgs g, co
       const int col = min(col_base + ni * 32 + l31, g.N - 1);
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int row = min(row_base + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi, g.M - 1);
+        const int row = min(row_base + mi * 32 + acc_row(r, hi), g.M - 1);
         off[mi][ni][r] = row * ldp + col;
         acc[mi][ni][r] = 0.f;
       }
@@ -485,18 +328,21 @@ __global__ __launch_bounds__(256) void splitk_finish_kernel(const GemmArgs g, co
       const bool cok = col_base + ni * 32 + l31 < g.N;
 #pragma unroll
       for (int r = 0; r < 16; ++r)
-        if (!(cok && row_base + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi < g.M)) acc[mi][ni][r] = 0.f;
+        if (!(cok && row_base + mi * 32 + acc_row(r, hi) < g.M)) acc[mi][ni][r] = 0.f;
     }
-  if constexpr (EPI != EPI_F32) {
-    // interior wave tiles: the LDS-staged epilogues (gemm_epi_fast.h), as in the one-launch kernel
-    __shared__ __attribute__((aligned(16))) unsigned char fin_lds[4 * 9216];
-    if (small_tile_fast_epilogue<EPI, 9216, true, true, true>(acc, g, 0, row_base, col_base, tn * 64 + wn * 32, lane, fin_lds + wave * 9216)) return;
+  // the plane-writing epilogues stage interior wave tiles through LDS, as in the one-launch kernel; fp32 tiles that come here (unaligned
+  // destinations: the rest goes to splitk_finish_f32_kernel) are stored per value
+  constexpr int WBUF = EPI == EPI_F32 ? 0 : 9216;
+  unsigned char* wbuf = nullptr;
+  if constexpr (WBUF > 0) {
+    __shared__ __attribute__((aligned(16))) unsigned char fin_lds[4 * WBUF];
+    wbuf = fin_lds + wave * WBUF;
   }
-  gemm_epilogue<EPI, 2, 2>(acc, g, 0, row_base, col_base, tn * 64 + wn * 32, lane);
+  wave_tile_epilogue<EPI, 2, FinishFormats, WBUF>(acc, g, 0, row_base, col_base, tn * 64 + wn * 32, lane, wbuf);
 }
 
 // EPI_F32 needs no accumulator layout: one thread per 4 adjacent columns, 16-byte loads of every slot / the residual, 16-byte
-// store.  The same operation order per value as gemm_epilogue<EPI_F32>: (sum + bias) -> activation -> + residual.
+// store.  The same operation order per value as gemm_epilogue<EPI_F32> (gemm_epi.h): (sum + bias) -> activation -> + residual.
 __global__ __launch_bounds__(256) void splitk_finish_f32_kernel(const float* part, int S, long slot, int ldp, int M, int N, const float* bias,
                                                                 const float* resid, int ldr, int act, float* out, int ldo) {
   const int n4 = N >> 2;                                       // N % 4 == 0 (checked by the launcher)
@@ -552,16 +398,9 @@ __global__ __launch_bounds__(256) void splitk_finish_f32_norm_kernel(const float
     __syncthreads();
     ss = s_sum[2 * rloc] + s_sum[2 * rloc + 1];
   }
-  const float inv = sqrtf((float)(4 * N4)) / fmaxf(sqrtf(ss), 1e-12f);
-  float o[4] = {v.x * inv, v.y * inv, v.z * inv, v.w * inv};
-  if (g.nrm_gamma) { const float4 t = *reinterpret_cast<const float4*>(g.nrm_gamma + c); o[0] *= t.x; o[1] *= t.y; o[2] *= t.z; o[3] *= t.w; }
-  if (g.nrm_cond) {
-    const float* gc = g.nrm_cond + (g.nrm_seq_len > 0 ? row / g.nrm_seq_len : 0) * (long)g.nrm_cond_ld;
-    const float4 t = *reinterpret_cast<const float4*>(gc + c), u = *reinterpret_cast<const float4*>(gc + 4 * N4 + c);
-    o[0] = o[0] * t.x + u.x; o[1] = o[1] * t.y + u.y; o[2] = o[2] * t.z + u.z; o[3] = o[3] * t.w + u.w;
-  }
-  const bool nil = g.nrm_lo != nullptr;
-  if (ok) store_cols4(g.nrm_hi + row * pld(g.nrm_ld, nil), c, o[0], o[1], o[2], o[3], g.nrm_fmt, nil);
+  float gm[4];
+  norm_gamma4(g, c, gm);
+  if (ok) norm_tail_store4(g, 4 * N4, row, c, v, ss, gm);
 }
 
 // S slices of c K tiles per tap (plan_gemm); every slot must lie inside the lent scratch

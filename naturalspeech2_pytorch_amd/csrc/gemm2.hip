@@ -21,7 +21,7 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "gemm2_epilogue.h"
+#include "gemm_epi_dispatch.h"
 #include "ffconv_kernel.h"
 #include "gemm3_kernel.h"
 #include "wavenet3_kernel.h"

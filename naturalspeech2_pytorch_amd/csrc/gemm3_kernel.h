@@ -15,12 +15,12 @@
 //   * the K loop is unrolled over the two stages; an odd tile count peels one steady tile in front (tile 0 then starts in stage 1),
 //     so the last two tiles -- the ones with fewer requests and tighter waits -- are always (stage 0, stage 1).
 // Per accumulator: half product of k chunk 0, of k chunk 1, then the fp8 correction-term MFMA -- mma_quadrant's order: results are
-// bit-identical to gemm2_kernel<2, EPI, true>.  Epilogues: gemm2_epilogue.h, untouched.
+// bit-identical to gemm2_kernel<2, EPI, true>.  Epilogues: gemm_epi_dispatch.h, untouched.
 // Not handled here (gemm2_kernel / gemm_kernel keep them): M % 256 != 0, conv taps, grid-z batching, split-K, the other arithmetics.
 #pragma once
 #include <algorithm>
 
-#include "gemm2_epilogue.h"
+#include "gemm_epi_dispatch.h"
 
 namespace ns2 {
 namespace mx3 {

@@ -1,17 +1,43 @@
-// Shared epilogues of the GEMM kernels (gemm.hip: 128x128 tile; gemm2.hip: 256x256 tile).
-// A wave owns MI x NI accumulator tiles of v_mfma_f32_32x32x16_bf16 (C layout: col = lane&31,
-// row = (r&3) + 8*(r>>2) + 4*(lane>>5)), rows [row_base, row_base + 32*MI), cols [col_base, col_base + 32*NI).
+// Epilogue layer of the GEMM kernels (gemm.hip: 128x128 tile, 64-row wave tiles; gemm2.hip and its lean relatives: 256x256 tile,
+// 128-row wave tiles), three headers:
+//   gemm_epi.h           (this file) the accumulator layout, the Wavenet gate between the K phases, the fused RMSNorm tail and the
+//                        GENERIC epilogue: bounds, format and activation decided per stored value -- any tile, any alignment;
+//   gemm_epi_fast.h      the STAGED epilogues of whole wave tiles: through the wave's private LDS region, 16-byte stores;
+//   gemm_epi_dispatch.h  wave_tile_epilogue: the one place that decides between the two.
+// A wave owns MI x 2 accumulator tiles of v_mfma_f32_32x32x16_bf16 (C layout: col = lane & 31, row = acc_row(r, lane >> 5)),
+// rows [row_base, row_base + 32 * MI), cols [col_base, col_base + 64).  A row's stored bits do not depend on the path its tile took
+// (tests/test_kernels_gpu.py, test_epilogue_paths_store_identical_bits).
 #pragma once
 #include "ns2_common.h"
 #include "ns2_kernels.h"
 
 namespace ns2 {
 
+// row of accumulator register r inside its 32 x 32 tile (hi = lane >> 5)
+NS2_DEVINL constexpr int acc_row(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
+
+// value of lane ^ 1 (DPP quad_perm [1,0,3,2]): one VALU move, no LDS crossbar
+NS2_DEVINL float lane_xor1(float v) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));
+}
+
+// Pair adjacent columns for 4-byte stores of two 16-bit values: a lane holds rows 2rp (v0) and 2rp + 1 (v1) of its column; afterwards
+// the even lane holds row 2rp and the odd lane row 2rp + 1 of columns (l31 & ~1, l31 | 1) in (c_lo, c_hi).  Returns that row's
+// accumulator register.  The exchange is the DPP move (staged epilogues) or a shuffle (generic epilogue): the same values.
+template <bool DPP>
+NS2_DEVINL int pair_cols(bool odd, int rp, float v0, float v1, float& c_lo, float& c_hi) {
+  const float send = odd ? v0 : v1;
+  const float recv = DPP ? lane_xor1(send) : __shfl_xor(send, 1, 64);
+  c_lo = odd ? recv : v0;
+  c_hi = odd ? v1 : recv;
+  return 2 * rp + (odd ? 1 : 0);
+}
+
 // WavenetResBlock NS2:629-636: h = conv(x)+b ; h = h*gamma_t+beta_t ; h = tanh(h)*sigmoid(h) ; (then += res_conv(x)).
 // tanh(h)*sigmoid(h) = sign(h) * (1-u) * (h<0 ? u : 1) / (1+u^2),  u = exp(-|h|)   (one exp, no overflow)
 // `uni` (wave-uniform): the wave tile lies inside ONE utterance, so gamma / beta are per column and are loaded once per column tile
 // instead of once per element (with a row / seq_len division each).  The per-element structure (one small diamond per value) is
-// kept on purpose: a straight-line variant of this loop made the register allocator spill 100-300 VGPRs (gemm_epi_fast.h note).
+// kept on purpose: a straight-line variant of this loop made the register allocator spill 100-300 VGPRs.
 template <int MI, int NI>
 NS2_DEVINL void wavenet_midgate(f32x16 (&acc)[MI][NI], const GemmArgs& g, int z, int row_base, int col_base, int l31, int hi, bool uni = false) {
   const float* film = g.film + (long)z * g.film_zs;
@@ -30,7 +56,7 @@ NS2_DEVINL void wavenet_midgate(f32x16 (&acc)[MI][NI], const GemmArgs& g, int z,
       const float bet_u = (uni && cok) ? film_u[g.N + col] : 0.f;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int row = row_base + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+        const int row = row_base + mi * 32 + acc_row(r, hi);
         float v = 0.f;
         if (cok && row < g.M) {
           float gam = gam_u, bet = bet_u;
@@ -49,10 +75,29 @@ NS2_DEVINL void wavenet_midgate(f32x16 (&acc)[MI][NI], const GemmArgs& g, int z,
     }
 }
 
-// ocol_base: first output column of this wave for EPI_GEGLU (= half of the packed column index)
-template <int EPI, int MI, int NI>
-NS2_DEVINL void gemm_epilogue(f32x16 (&acc)[MI][NI], const GemmArgs& g, int z, int row_base, int col_base, int ocol_base,
-                              int lane) {
+// The RMSNorm behind a residual update (GemmArgs::nrm_*), after the row's sum of squares `ss` is known: x = columns c .. c + 3 of row
+// `row` of the N-column update, gm = gamma at those columns (read only with g.nrm_gamma).  One expression order for the fused
+// 128x128 epilogue and the split-K finishing pass; rmsnorm_kernel (elementwise.hip) multiplies in another order.
+NS2_DEVINL void norm_tail_store4(const GemmArgs& g, int N, long row, int c, const float4& x, float ss, const float (&gm)[4]) {
+  const float inv = sqrtf((float)N) / fmaxf(sqrtf(ss), 1e-12f);   // F.normalize eps (NS2:727-746)
+  float o[4] = {x.x * inv, x.y * inv, x.z * inv, x.w * inv};
+  if (g.nrm_gamma) { o[0] *= gm[0]; o[1] *= gm[1]; o[2] *= gm[2]; o[3] *= gm[3]; }
+  if (g.nrm_cond) {
+    const float* gc = g.nrm_cond + (g.nrm_seq_len > 0 ? row / g.nrm_seq_len : 0) * (long)g.nrm_cond_ld;
+    const float4 t = *reinterpret_cast<const float4*>(gc + c), u = *reinterpret_cast<const float4*>(gc + N + c);
+    o[0] = o[0] * t.x + u.x; o[1] = o[1] * t.y + u.y; o[2] = o[2] * t.z + u.z; o[3] = o[3] * t.w + u.w;
+  }
+  const bool nil = g.nrm_lo != nullptr;
+  store_cols4(g.nrm_hi + row * pld(g.nrm_ld, nil), c, o[0], o[1], o[2], o[3], g.nrm_fmt, nil);
+}
+NS2_DEVINL void norm_gamma4(const GemmArgs& g, int c, float (&gm)[4]) {
+  gm[0] = gm[1] = gm[2] = gm[3] = 1.f;
+  if (g.nrm_gamma) { const float4 t = *reinterpret_cast<const float4*>(g.nrm_gamma + c); gm[0] = t.x; gm[1] = t.y; gm[2] = t.z; gm[3] = t.w; }
+}
+
+// The generic epilogue.  ocol_base: first output column of this wave for EPI_GEGLU (= half of the packed column index)
+template <int EPI, int MI>
+NS2_DEVINL void gemm_epilogue(f32x16 (&acc)[MI][2], const GemmArgs& g, int z, int row_base, int col_base, int ocol_base, int lane) {
   const int l31 = lane & 31, hi = lane >> 5;
   const bool odd = lane & 1;
   const bool il = g.out_lo != nullptr;               // interleaved 128-B output lines: bf16 [hi32|lo32] or FMT_H8 (ns2_common.h)
@@ -62,13 +107,13 @@ NS2_DEVINL void gemm_epilogue(f32x16 (&acc)[MI][NI], const GemmArgs& g, int z, i
 #pragma unroll
     for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
-      for (int ni = 0; ni < NI; ++ni) {
+      for (int ni = 0; ni < 2; ++ni) {
         const int col = col_base + ni * 32 + l31;
         if (col >= g.N) continue;
         const float bc = g.bias ? g.bias[col] : 0.f;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int row = row_base + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+          const int row = row_base + mi * 32 + acc_row(r, hi);
           if (row >= g.M) continue;
           float v = acc[mi][ni][r] + bc;
           if (g.act) v = apply_act(v, g.act);
@@ -77,34 +122,19 @@ NS2_DEVINL void gemm_epilogue(f32x16 (&acc)[MI][NI], const GemmArgs& g, int z, i
         }
       }
   } else if constexpr (EPI == EPI_GEGLU) {
-    // wave tile = NI/2 x [x(32 cols) | gate(32 cols)] ; out[:, ocol] = gelu(gate) * x   (NS2:1006-1007)
-    static_assert(EPI != EPI_GEGLU || (NI % 2) == 0, "GEGLU needs 64-column [x|gate] groups");
-#pragma unroll
-    for (int np = 0; np < NI / 2; ++np) {
-    const int ocol = ocol_base + np * 32 + l31;
-    const int cx = col_base + np * 64 + l31, cg = cx + 32;
-    const float bx = g.bias[cx], bg = g.bias[cg];      // packed (padded) bias: always in range
+    // wave tile = [x(32 cols) | gate(32 cols)] ; out[:, ocol] = gelu(gate) * x   (NS2:1006-1007)
+    const int col = (ocol_base + l31) & ~1;
+    const float bx = g.bias[col_base + l31], bg = g.bias[col_base + 32 + l31];      // packed (padded) bias: always in range
 #pragma unroll
     for (int mi = 0; mi < MI; ++mi) {
 #pragma unroll
       for (int rp = 0; rp < 8; ++rp) {
-        float v0, v1;
-        {
-          const float x0 = acc[mi][2 * np][2 * rp] + bx, g0 = acc[mi][2 * np + 1][2 * rp] + bg;
-          const float x1 = acc[mi][2 * np][2 * rp + 1] + bx, g1 = acc[mi][2 * np + 1][2 * rp + 1] + bg;
-          v0 = gelu_erf(g0) * x0;
-          v1 = gelu_erf(g1) * x1;
-        }
-        // pair adjacent columns: even lane stores row 2rp, odd lane stores row 2rp+1 (two bf16 per 4-B store)
-        const float send = odd ? v0 : v1;
-        const float recv = __shfl_xor(send, 1, 64);
-        const float c_lo = odd ? recv : v0, c_hi = odd ? v1 : recv;
-        const int r = 2 * rp + (odd ? 1 : 0);
-        const int row = row_base + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-        const int col = ocol & ~1;
+        const float v0 = gelu_erf(acc[mi][1][2 * rp] + bg) * (acc[mi][0][2 * rp] + bx);
+        const float v1 = gelu_erf(acc[mi][1][2 * rp + 1] + bg) * (acc[mi][0][2 * rp + 1] + bx);
+        float c_lo, c_hi;
+        const int row = row_base + mi * 32 + acc_row(pair_cols<false>(odd, rp, v0, v1, c_lo, c_hi), hi);
         if (row < g.M && col < g.out_ncols) store_cols2(g.out_hi + (long)row * pld(g.ldo_s, il), col, c_lo, c_hi, g.out_fmt, il);
       }
-    }
     }
   } else {
     // EPI_SPLIT / EPI_QKV / EPI_WAVENET: split planes, optionally the tail columns transposed (V^T for attention)
@@ -114,7 +144,7 @@ NS2_DEVINL void gemm_epilogue(f32x16 (&acc)[MI][NI], const GemmArgs& g, int z, i
 #pragma unroll
     for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
-      for (int ni = 0; ni < NI; ++ni) {
+      for (int ni = 0; ni < 2; ++ni) {
         const int col = col_base + ni * 32 + l31;
         float bc = 0.f;
         if constexpr (EPI != EPI_WAVENET) bc = (bias && col < g.N) ? bias[col] : 0.f;   // wavenet biases were applied mid-loop
@@ -124,12 +154,8 @@ NS2_DEVINL void gemm_epilogue(f32x16 (&acc)[MI][NI], const GemmArgs& g, int z, i
           for (int rp = 0; rp < 8; ++rp) {
             float v0 = acc[mi][ni][2 * rp] + bc, v1 = acc[mi][ni][2 * rp + 1] + bc;
             if (EPI == EPI_SPLIT && g.act) { v0 = apply_act(v0, g.act); v1 = apply_act(v1, g.act); }
-            const float send = odd ? v0 : v1;
-            const float recv = __shfl_xor(send, 1, 64);
-            // columns (col&~1, col|1): even lane holds its own col then the neighbour's, odd lane the reverse
-            float c_lo = odd ? recv : v0, c_hi = odd ? v1 : recv;
-            const int r = 2 * rp + (odd ? 1 : 0);
-            const int row = row_base + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+            float c_lo, c_hi;
+            const int row = row_base + mi * 32 + acc_row(pair_cols<false>(odd, rp, v0, v1, c_lo, c_hi), hi);
             const int c0 = col & ~1;
             if (row < g.M && c0 < g.out_ncols) {
               if (c0 >= g.N) c_lo = 0.f;             // zero the K-padding columns of the next GEMM's operand
@@ -143,7 +169,7 @@ NS2_DEVINL void gemm_epilogue(f32x16 (&acc)[MI][NI], const GemmArgs& g, int z, i
           if (col < g.N) {
 #pragma unroll
             for (int gq = 0; gq < 4; ++gq) {
-              const int row0 = row_base + mi * 32 + 8 * gq + 4 * hi;
+              const int row0 = row_base + mi * 32 + acc_row(4 * gq, hi);
               if (row0 >= g.M) continue;
               const int b = row0 / g.seq_len, n0 = row0 - b * g.seq_len;
               // transposed values are attention operands: bf16 (with or without lo plane) or dense IEEE half, never FMT_H8
@@ -173,75 +199,6 @@ NS2_DEVINL void gemm_epilogue(f32x16 (&acc)[MI][NI], const GemmArgs& g, int z, i
           }
         }
       }
-  }
-}
-
-// ------------------------------------------------------------------------------------------------------------------
-// LDS-staged epilogue for the 256x256 kernel (wave tile 128x64, MI = 4, NI = 2).  The direct epilogue above issues one
-// 4-byte store per lane per two accumulator registers (64-B row segments): on short-K GEMMs (QKV, FF-in, out-proj) it
-// measured ~100 us of a 145 us launch.  Here every wave transposes its tile through a private 18 KiB LDS region
-// (free after the K loop) and writes full rows with 16-B stores per lane (128-B / 256-B contiguous segments).
-constexpr int EPI_LDS_WAVE_BYTES = 18432;     // 128 rows x (128 B + 16 B pad)
-
-NS2_DEVINL uint32_t pk2(float a, float b) { return cvt2(a, b); }
-
-// Measured (MI355X, M = 32768): the fp32 + residual epilogue gains 1.45x-1.65x on the whole launch (FF-out 218 -> 150 us);
-// LDS-staged variants of the bf16 split-plane epilogues were built too and were neutral (their cost is the store burst
-// itself, not store issue) -- only EPI_F32 has an LDS path.
-template <int EPI>
-NS2_DEVINL bool epi_lds_supported(const GemmArgs&, int) { return EPI == EPI_F32; }
-
-// NIT = accumulator column tiles of the wave, NI0 = first of the two column tiles this call stores
-template <int EPI, int NIT, int NI0>
-NS2_DEVINL void gemm_epilogue_lds(f32x16 (&acc)[4][NIT], const GemmArgs& g, int z, int row_base, int col_base, int ocol_base,
-                                  int lane, unsigned char* wbuf) {
-  const int l31 = lane & 31, hi = lane >> 5;
-  const bool odd = lane & 1;
-
-  if constexpr (EPI == EPI_F32) {
-    // two halves of 64 rows x 64 cols fp32, LDS rows of 272 B
-    constexpr int RS = 272;
-#pragma unroll
-    for (int half = 0; half < 2; ++half) {
-#pragma unroll
-      for (int mh = 0; mh < 2; ++mh)
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni) {
-          const int col = col_base + ni * 32 + l31;
-          const float bc = (g.bias && col < g.N) ? g.bias[col] : 0.f;
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int lr = mh * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-            float t = acc[half * 2 + mh][NI0 + ni][r] + bc;
-            if (g.act) t = apply_act(t, g.act);
-            *reinterpret_cast<float*>(wbuf + lr * RS + (ni * 32 + l31) * 4) = t;
-          }
-        }
-#pragma unroll
-      for (int it = 0; it < 16; ++it) {
-        const int lr = it * 4 + (lane >> 4), ch = lane & 15;
-        const int row = row_base + half * 64 + lr, col = col_base + ch * 4;
-        const float4 v = *reinterpret_cast<const float4*>(wbuf + lr * RS + ch * 16);
-        if (row < g.M && col < g.N) {
-          float o[4] = {v.x, v.y, v.z, v.w};
-          if (col + 3 < g.N) {
-            if (g.resid) {
-              const float4 rr = *reinterpret_cast<const float4*>(g.resid + (long)row * g.ldr + col);
-              o[0] += rr.x; o[1] += rr.y; o[2] += rr.z; o[3] += rr.w;
-            }
-            *reinterpret_cast<float4*>(g.out_f + z * g.out_f_zs + (long)row * g.ldo_f + col) = make_float4(o[0], o[1], o[2], o[3]);
-          } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-              if (col + e < g.N) {
-                float t = o[e];
-                if (g.resid) t += g.resid[(long)row * g.ldr + col + e];
-                g.out_f[z * g.out_f_zs + (long)row * g.ldo_f + col + e] = t;
-              }
-          }
-        }
-      }
-    }
   }
 }
 

@@ -96,10 +96,15 @@ const struct SatRegistrar {
 // (tools/precision_study.py); the price is range: values are clamped to +-65504 on conversion instead of becoming inf.
 typedef __attribute__((ext_vector_type(2))) _Float16 f16x2_t;
 typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-NS2_DEVINL uint32_t cvt2h(float a, float b) {         // {half(a) | half(b) << 16}, round to nearest even, saturating
-  note_out_of_range(a, b, 65504.f);
+// {half(a) | half(b) << 16}, round to nearest even, saturating.  _q ("quiet"): without the range note, for callers that track the
+// range themselves (RangeTrack, gemm_epi_fast.h)
+NS2_DEVINL uint32_t cvt2h_q(float a, float b) {
   f32x2_t v = {fminf(fmaxf(a, -65504.f), 65504.f), fminf(fmaxf(b, -65504.f), 65504.f)};
   return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, f16x2_t));
+}
+NS2_DEVINL uint32_t cvt2h(float a, float b) {
+  note_out_of_range(a, b, 65504.f);
+  return cvt2h_q(a, b);
 }
 // the same for values known to lie inside the half range (softmax probabilities): no clamp, no range guard
 NS2_DEVINL uint32_t cvt2h_inrange(float a, float b) {
@@ -127,9 +132,8 @@ constexpr int H8_E8M0_ONE = 127;
 constexpr float H8_MAX = 57344.0f;                // largest finite e5m2 (< 65504: one clamp serves the half and the e5m2 parts)
 typedef __attribute__((ext_vector_type(8))) int i32x8;
 
-// (a, b) -> packed halves, packed e5m2(a, b) and packed e5m2 of the scaled remainders (each in the low 16 bits)
-NS2_DEVINL void cvt2_h8(float a, float b, uint32_t& h16, uint32_t& h8, uint32_t& l8) {
-  note_out_of_range(a, b, H8_MAX);
+// (a, b) -> packed halves, packed e5m2(a, b) and packed e5m2 of the scaled remainders (each in the low 16 bits); _q as for cvt2h_q
+NS2_DEVINL void cvt2_h8_q(float a, float b, uint32_t& h16, uint32_t& h8, uint32_t& l8) {
   a = fminf(fmaxf(a, -H8_MAX), H8_MAX);
   b = fminf(fmaxf(b, -H8_MAX), H8_MAX);
   f32x2_t v = {a, b};
@@ -138,6 +142,10 @@ NS2_DEVINL void cvt2_h8(float a, float b, uint32_t& h16, uint32_t& h8, uint32_t&
   h16 = __builtin_bit_cast(uint32_t, h);
   h8 = (uint32_t)__builtin_amdgcn_cvt_pk_bf8_f32(a, b, 0, false) & 0xffffu;
   l8 = (uint32_t)__builtin_amdgcn_cvt_pk_bf8_f32(fminf(fmaxf(r.x, -H8_MAX), H8_MAX), fminf(fmaxf(r.y, -H8_MAX), H8_MAX), 0, false) & 0xffffu;
+}
+NS2_DEVINL void cvt2_h8(float a, float b, uint32_t& h16, uint32_t& h8, uint32_t& l8) {
+  note_out_of_range(a, b, H8_MAX);
+  cvt2_h8_q(a, b, h16, h8, l8);
 }
 NS2_DEVINL float bf8_to_f(uint32_t byte) {        // e5m2 -> fp32 (e5m2 is the top byte of an IEEE half)
   return (float)__builtin_bit_cast(_Float16, (uint16_t)(byte << 8));

@@ -13,7 +13,7 @@
 //     branch; 0 x w = 0 exactly) -- no zero page, no per-lane test at issue time;
 //   * the K loops are unrolled so that stage parity AND tap are immediates (6 tile bodies per iteration).
 // Summation order per accumulator = the old kernel's (chunk-major, tap-minor, k chunks in order; then the res-conv tiles): results are
-// bit-identical.  Mid-gate and epilogue: gemm_epi.h / gemm2_epilogue.h, untouched.
+// bit-identical.  Mid-gate and epilogue: gemm_epi.h / gemm_epi_dispatch.h, untouched.
 #pragma once
 #include "gemm3_kernel.h"
 

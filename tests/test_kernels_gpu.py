@@ -291,6 +291,75 @@ def test_wavenet_block(B, N, C, dil, prec, gemm_kernel):
         assert e5 > 2 * e, (e5, e)             # both kernels really took the half-product phase (the 128x128 one since round 4)
 
 
+def _raw(p):
+    """the stored bits of planes `p` as int16 [rows, planes, ld]: the hi plane, then (interleaved lines) the second line half"""
+    b = p.buf.view(torch.int16)
+    return b.reshape(p.rows, p.ld // 32, 2, 32).permute(0, 2, 1, 3).reshape(p.rows, 2, p.ld) if p.has_lo else b.reshape(p.rows, 1, p.ld)
+
+
+def _epi_f32(M, prec):
+    K, N = 512, 256
+    x, w = rnd(256, K, seed=40), rnd(N, K, seed=41, scale=1 / math.sqrt(K))
+    b, r = rnd(N, seed=42), rnd(256, N, seed=43)
+    y = ops.linear_f32(ops.PackedWeight(w, precision=prec), ops.split(x[:M], precision=prec), bias=b, resid=r[:M], precision=prec)
+    return [y]
+
+
+def _epi_split(M, prec):
+    K, N = 512, 256
+    x, w, b = rnd(256, K, seed=44), rnd(N, K, seed=45, scale=1 / math.sqrt(K)), rnd(N, seed=46)
+    return [_raw(ops.linear_split(ops.PackedWeight(w, precision=prec), ops.split(x[:M], precision=prec), bias=b, precision=prec))]
+
+
+def _epi_geglu(M, prec):
+    K, f = 512, 128
+    x, w, b = rnd(256, K, seed=47), rnd(2 * f, K, seed=48, scale=1 / math.sqrt(K)), rnd(2 * f, seed=49)
+    pw = ops.PackedWeight(w, geglu=True, precision=prec)
+    return [_raw(ops.linear_geglu(pw, ops.split(x[:M], precision=prec), ops.geglu_pack_bias(b, f), precision=prec))]
+
+
+def _epi_qkv(M, prec):
+    K, a_dim = 512, 256
+    x, w = rnd(256, K, seed=50), rnd(3 * a_dim, K, seed=51, scale=1 / math.sqrt(K))
+    qk, vt = ops.linear_qkv(ops.PackedWeight(w, precision=prec), ops.split(x[:M], precision=prec), seq_len=M, split_col=2 * a_dim, precision=prec)
+    assert (vt.rows, vt.ld) == (a_dim, 256)
+    return [_raw(qk), _raw(vt)[:, :, :255].transpose(0, 2)]          # V^T by token, like the rows of the other outputs
+
+
+def _epi_wavenet(M, prec):
+    C = 128
+    x = rnd(256, C, seed=52)
+    wc, wr = rnd(C, C, 3, seed=53, scale=1 / math.sqrt(3 * C)), rnd(C, C, 1, seed=54, scale=1 / math.sqrt(C))
+    bc, br, film = rnd(C, seed=55), rnd(C, seed=56), rnd(1, 2 * C, seed=57)
+    pw = ops.PackedWeight(wc, extra1x1=wr, precision=prec)
+    a = ops.split(x[:M], precision=prec)
+    return [_raw(ops.wavenet_block(pw, a, M, 2, bc, br, film, precision=p)) for p in ((4, 5) if prec == 4 else (prec,))]
+
+
+@pytest.mark.parametrize("prec", PRECS)
+@pytest.mark.parametrize("epi", [_epi_f32, _epi_split, _epi_geglu, _epi_qkv, _epi_wavenet], ids=["f32", "split", "geglu", "qkv", "wavenet"])
+def test_epilogue_paths_store_identical_bits(epi, prec, gemm_kernel):
+    """A row's stored bits must not depend on which epilogue path its wave tile took (the property the epilogue dispatcher,
+    gemm_epi_dispatch.h, relies on).  Every product runs twice on the same operands, one utterance: on 256 rows and on the first
+    255 of them (causal convolutions and row-wise products: rows 0..254 do not see row 255), and rows 0..254 are compared bit
+    for bit -- raw 16-bit and byte planes, fp32 with torch.equal.  Which run takes which path follows from the dispatcher's
+    conditions (N, the plane strides and the buffers are all aligned here):
+      * 256 rows: every wave tile is interior, so it leaves through the LDS-staged epilogues; seq_len = 256 is a multiple of the
+        wave tile's rows, so V^T takes the LDS transpose (dense 16-bit V^T: precisions 1, 2, 4) and the Wavenet gate reads
+        gamma / beta once per column;
+      * 255 rows: the last 64-row (128 x 128 kernel, split-K finish) or 128-row (256 x 256 kernel) wave tile has a row edge, so it
+        takes the per-value epilogue -- fp32 on the 256 x 256 kernel the bounds-checked staged one --, V^T the scalar stores
+        (seq_len % 4 != 0) and the Wavenet gate the per-element FiLM lookup.
+    K = 512 is 16 K tiles, the least the split-K route takes; the Wavenet block is never split, its third case repeats the
+    dispatch by shape.  The fp32 case under split K does not reach the dispatcher at all: with an aligned destination the sums are
+    finished by the flat splitk_finish_f32_kernel, the same code in both runs."""
+    full, part = epi(256, prec), epi(255, prec)
+    assert len(full) == len(part)
+    for f, p in zip(full, part):
+        assert p.shape[0] == 255 and f.shape[1:] == p.shape[1:]
+        assert torch.equal(f[:255], p)
+
+
 def attn_ref(q, k, v, scale):
     s = torch.einsum("bhid,bhjd->bhij", q, k) * scale
     return torch.einsum("bhij,bhjd->bhid", s.softmax(-1), v)

@@ -397,7 +397,7 @@ struct Kern {
         else if constexpr (EPI == 4) epi_h8_variant<false, true>(c.acc, ga, row_base, col_base, lane, wbuf);
         else epi_h8_variant<true, true>(c.acc, ga, row_base, col_base, lane, wbuf);
       }
-      else gemm_epilogue<EPI_SPLIT, 4, 2>(c.acc, ga, 0, row_base, col_base, 0, lane);
+      else gemm_epilogue<EPI_SPLIT, 4>(c.acc, ga, 0, row_base, col_base, 0, lane);
     }
   }
 
