@@ -59,6 +59,14 @@ int ns2_debug_force_gemm(int kernel);
  * kernel of attn_fast_kernel.h: its reference and A/B partner).  Process-wide like the hook above; NS2_ATTN in the environment sets
  * the initial value.  Not to be flipped while a graph is being captured. */
 int ns2_debug_force_attention(int kernel);
+/* test hook: how many utterance chains ns2_model_forward / ns2_model_forward_row run the row-dependent part of a step as (0 = the
+ * library's default, 1 = one chain: the whole batch on the caller's stream, 2 = two chains of ceil(B / 2) and floor(B / 2) utterances on
+ * the caller's stream and a stream the model owns, wherever the chain rule allows: every product keeps the kernel it takes for the whole
+ * batch, none splits K, each chain is whole 256-row tiles; never while the caller's stream is capturing or a debug tap is registered).
+ * Results are bit-identical either way.  Process-wide like the hooks above; NS2_CHAINS in the environment sets the initial value. */
+int ns2_debug_force_chains(int chains);
+/* test hook: the number of chains (1 or 2) the last forward of this process ran; 0 before the first */
+int ns2_debug_chains_last(void);
 /* test hook: how many attention launches of this process took the two-block kernel so far (every other one took attn_kernel).
  * A test reads it before and after a call to see which kernel the call was routed to. */
 int64_t ns2_debug_attention_fast_launches(void);
@@ -425,9 +433,14 @@ int ns2_model_param_checksum(ns2_model* m, float* host_out, int capacity, void* 
 int ns2_model_debug_tap(ns2_model* m, const char* name, float* dst, int64_t dst_elems);
 /* live kernel timing with HIP events on the caller's stream (bench.py roofline): category bits
  * 0 gemm<f32 epilogue> 1 gemm<split epilogue> 2 gemm<qkv> 3 gemm<geglu> 4 gemm<wavenet> 5 attention 6 rmsnorm.
- * _end synchronises on the recorded events and returns the summed kernel time and the number of launches. */
+ * _end synchronises on the recorded events and returns the summed kernel time and the number of launches.  A step that ran as two
+ * utterance chains (ns2_debug_force_chains) records each product's two parts on their own streams: `launches` counts the product once and
+ * `total_ms` adds both parts -- each measured while the other chain's kernels share the chip, so it overstates the product's cost alone. */
 int ns2_model_profile_begin(ns2_model* m, unsigned category_mask);
 int ns2_model_profile_end(ns2_model* m, double* total_ms, int64_t* launches);
+/* test hook, host arithmetic only (no device): the number of chains a forward of B utterances x N frames of a model of this
+ * configuration runs where two are wanted (the chain rule alone: not the capture / tap / force conditions) */
+int ns2_debug_chain_rule(const ns2_model_config* cfg, int B, int N, int* chains);
 void ns2_model_destroy(ns2_model* m);
 
 /* ------------------------------------------------------------------ training: the backward pass

@@ -77,6 +77,9 @@ SIGNATURES = {
     "ns2_debug_force_gemm": (I, [I]),
     "ns2_debug_force_attention": (I, [I]),
     "ns2_debug_attention_fast_launches": (L, []),
+    "ns2_debug_force_chains": (I, [I]),
+    "ns2_debug_chains_last": (I, []),
+    "ns2_debug_chain_rule": (I, [POINTER(ModelConfig), I, I, POINTER(c_int)]),
     "ns2_splitk_scratch_bytes": (L, []),
     "ns2_debug_splitk_plan": (I, [I, I, I, I, I, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     "ns2_debug_lend_splitk_scratch": (I, [P, L]),

@@ -23,6 +23,17 @@
 #include <vector>
 
 #include "ns2_host.h"
+#include "gemm_route.h"
+
+// Two utterance chains (forward_impl): NS2_CHAINS_DEFAULT = what a step runs when nothing is forced (1: one chain, 2: two chains wherever
+// the chain rule allows); NS2_CHAIN_SKEW = where chain 1 starts (0: with chain 0, 1: behind chain 0's init conv, 2: behind its Wavenet,
+// 3: behind its first out-projection).  Measured on the MI355X: profiles/chains_ab.json.
+#ifndef NS2_CHAINS_DEFAULT
+#define NS2_CHAINS_DEFAULT 2
+#endif
+#ifndef NS2_CHAIN_SKEW
+#define NS2_CHAIN_SKEW 0
+#endif
 
 namespace ns2 {
 
@@ -75,8 +86,16 @@ struct ns2_model {
   // debug taps
   std::map<std::string, std::pair<float*, int64_t>> taps;
   // live kernel timing (bench.py roofline): HIP events around the launches of the selected kernel categories
-  unsigned prof_mask = 0; size_t prof_used = 0;
+  unsigned prof_mask = 0; size_t prof_used = 0, prof_products = 0;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_events;
+  // two utterance chains (forward_impl): the stream of chain 1 and the fork / join events, created with the model -- nothing is created
+  // inside a forward -- and the described launches of the whole batch and of the two chains, kept so that a step allocates nothing
+  hipStream_t chain_stream = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+  struct Program;
+  Program* prog[3] = {nullptr, nullptr, nullptr};
+  // the chain rule's last verdict and what it was asked for: the verdict depends on the shape, the alignment of the caller's buffers and
+  // the GEMM test hook alone, so a run of steps asks once
+  struct { int B = 0, N = 0, n_cond = 0; unsigned hook_epoch = 0; uintptr_t align = 0; int chains = 0; } rule;
 };
 
 namespace ns2 {
@@ -265,13 +284,12 @@ static const Param* find_param(const ns2_model* m, const std::string& k) {
   const Param* var = find_param(m, key);                                            \
   if (!var) { set_error("missing parameter '%s'", std::string(key).c_str()); return NS2_ERR_STATE; }
 
-extern "C" int ns2_model_create(const ns2_model_config* cfg, ns2_model** out) {
-  if (!cfg || !out) { set_error("null argument"); return NS2_ERR_ARG; }
+// the derived sizes of a configuration (and what ns2_model_create refuses)
+static int derive_dims(ns2_model* m, const ns2_model_config* cfg) {
   if (cfg->dim_head != 32 && cfg->dim_head != 64 && cfg->dim_head != 128) { set_error("dim_head must be 32, 64 or 128 (the head dims the attention kernel is built for), got %d", cfg->dim_head); return NS2_ERR_ARG; }
   if (cfg->dim % 32) { set_error("dim must be a multiple of 32, got %d", cfg->dim); return NS2_ERR_ARG; }
   if (cfg->precision < 1 || cfg->precision > 6) { set_error("precision must be 1 (bf16), 2 (fp16), 3 (bf16 x3), 4 (fp16 + fp8 correction terms), 5 (4, with the FF causal conv and the Wavenet's dilated convs as one fp16 product) or 6 (5, with the whole feed-forward branch as fp16 products)"); return NS2_ERR_ARG; }
   if (cfg->wavenet_layers < 1 || cfg->wavenet_layers > 16 || cfg->wavenet_stacks < 1) { set_error("bad wavenet shape"); return NS2_ERR_ARG; }
-  ns2_model* m = new ns2_model();
   m->cfg = *cfg;
   m->dim = cfg->dim; m->a = cfg->heads * cfg->dim_head;
   m->f = (int)((double)cfg->dim * cfg->ff_mult * 2 / 3);           // int(dim * mult * 2 / 3)  NS2:1010
@@ -283,6 +301,18 @@ extern "C" int ns2_model_create(const ns2_model_config* cfg, ns2_model** out) {
   m->Lm = cfg->num_latents_m; m->dpp = rup(cfg->dim_prompt > 0 ? cfg->dim_prompt : cfg->dim, 32);
   m->nnorm = cfg->condition_on_prompt ? 3 : 2;
   m->Jtot = (m->S * m->L + cfg->depth * m->nnorm) * 2 * m->dim;
+  return NS2_OK;
+}
+
+static void destroy_model(ns2_model* m);
+static int create_chain_state(ns2_model* m);      // (with forward_impl)
+static void destroy_chain_state(ns2_model* m);
+extern "C" int ns2_model_create(const ns2_model_config* cfg, ns2_model** out) {
+  if (!cfg || !out) { set_error("null argument"); return NS2_ERR_ARG; }
+  ns2_model* m = new ns2_model();
+  int r = derive_dims(m, cfg);
+  if (r == NS2_OK) r = create_chain_state(m);
+  if (r != NS2_OK) { destroy_model(m); return r; }
   *out = m;
   return NS2_OK;
 }
@@ -294,8 +324,10 @@ extern "C" int ns2_model_set_param(ns2_model* m, const char* name, const float* 
   return NS2_OK;
 }
 
-extern "C" void ns2_model_destroy(ns2_model* m) {
+extern "C" void ns2_model_destroy(ns2_model* m) { destroy_model(m); }
+static void destroy_model(ns2_model* m) {
   if (!m) return;
+  destroy_chain_state(m);
   for (auto& e : m->prof_events) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
   for (void* p : m->owned) (void)hipFree(p);
   delete m;
@@ -543,8 +575,6 @@ struct Work {
   float* skinny_ws; size_t skinny_ws_bytes;     // split-K partial sums of the conditioning projections (caller-owned)
   float* sk_ws;                                 // split-K slots of the small-batch GEMMs (SPLITK_SCRATCH_FLOATS, ns2_kernels.h)
   Planes xs, h0, wA, wB, ssum, xn, qk, vt, o, ffh, ffc;
-  Planes xq;               // cross-attention queries [M, a] in the cross-attention operand format: a view of qk's memory
-  Planes ffh_conv;         // the FF conv's input: ffh itself, or (precision 5) a dense IEEE-half view of the same memory
   int Nkp;
   // prepare_cond scratch
   float *pmean, *ctxf, *latf, *condT, *projf;
@@ -579,14 +609,10 @@ static int64_t carve_work(const ns2_model* m, Work* w, void* base, int64_t cap, 
   w->ssum = take_planes(c, M * dp, il, f16);
   w->xn = take_planes(c, M * dp, il, f16);
   w->qk = take_planes(c, Mq * 2 * a, ail, afmt);
-  w->xq = w->qk;                                      // M x a interleaved (4 B / element) fits M x 2a dense 16-bit
-  w->xq.fmt = F.xatt; w->xq.lo = F.xatt_il ? w->xq.hi + 32 : nullptr;
   w->Nkp = rup(N, kpad);
   w->vt = take_planes(c, (int64_t)B * a * w->Nkp, ail, afmt);
   w->o = take_planes(c, Mq * a, il, f16);
   w->ffh = take_planes(c, Mq * std::max(fp, m->fpc), il, f16);      // (the conv's dense-half input view has rows of fpc elements)
-  w->ffh_conv = w->ffh;
-  if (hybrid_plan(m->cfg.precision)) { w->ffh_conv.lo = nullptr; w->ffh_conv.fmt = FMT_F16; }
   w->ffc = take_planes(c, M * fp, il, f16);
   if (m->cfg.condition_on_prompt && n_prompt > 0) {
     const int Lm = m->Lm;
@@ -676,9 +702,8 @@ static int run_gemm(const GemmArgs& g, int prec, hipStream_t s) {
   return NS2_OK;
 }
 
-static int attention_call(const bf16_t* q_hi, const bf16_t* q_lo, int ldq, int q_col0, const bf16_t* k_hi, const bf16_t* k_lo,
-                          int ldk, int k_col0, Planes vt, int vt_ld, Planes o, int ldo, int B, int H, int Nq, int Nk, int prec,
-                          hipStream_t s, int dim_head) {
+static AttnArgs attn_args(const bf16_t* q_hi, const bf16_t* q_lo, int ldq, int q_col0, const bf16_t* k_hi, const bf16_t* k_lo,
+                          int ldk, int k_col0, Planes vt, int vt_ld, Planes o, int ldo, int B, int H, int Nq, int Nk, int dim_head) {
   AttnArgs a;
   a.D = dim_head;
   a.q_hi = q_hi; a.q_lo = q_lo; a.ldq = ldq; a.q_col0 = q_col0;
@@ -686,17 +711,26 @@ static int attention_call(const bf16_t* q_hi, const bf16_t* q_lo, int ldq, int q
   a.vt_hi = vt.hi; a.vt_lo = vt.lo; a.vt_ld = vt_ld;
   a.o_hi = o.hi; a.o_lo = o.lo; a.ldo = ldo; a.o_fmt = o.fmt;
   a.B = B; a.H = H; a.Nq = Nq; a.Nk = Nk; a.scale = 1.0f / sqrtf((float)dim_head);       // dim_head ** -0.5  (ATT:128 / SDPA default; 0.125 exactly at 64)
-  HIPRET(launch_attention(a, prec, s));
+  return a;
+}
+static int attention_call(const bf16_t* q_hi, const bf16_t* q_lo, int ldq, int q_col0, const bf16_t* k_hi, const bf16_t* k_lo,
+                          int ldk, int k_col0, Planes vt, int vt_ld, Planes o, int ldo, int B, int H, int Nq, int Nk, int prec,
+                          hipStream_t s, int dim_head) {
+  HIPRET(launch_attention(attn_args(q_hi, q_lo, ldq, q_col0, k_hi, k_lo, ldk, k_col0, vt, vt_ld, o, ldo, B, H, Nq, Nk, dim_head), prec, s));
   return NS2_OK;
 }
 
-static int norm_call(const float* x, int ldx, int M, int d, int seq_len, const float* gamma, const float* cond, int cond_ld,
-                     Planes out, int ldo, float* out_f, int ldo_f, hipStream_t s) {
+static NormArgs norm_args(const float* x, int ldx, int M, int d, int seq_len, const float* gamma, const float* cond, int cond_ld,
+                          Planes out, int ldo, float* out_f, int ldo_f) {
   NormArgs n;
   n.x = x; n.ldx = ldx; n.gamma = gamma; n.cond = cond; n.cond_ld = cond_ld;
   n.out_hi = out.hi; n.out_lo = out.lo; n.ldo = ldo; n.out_f = out_f; n.ldo_f = ldo_f;
   n.M = M; n.d = d; n.seq_len = seq_len; n.fmt = out.fmt;
-  HIPRET(launch_rmsnorm(n, s));
+  return n;
+}
+static int norm_call(const float* x, int ldx, int M, int d, int seq_len, const float* gamma, const float* cond, int cond_ld,
+                     Planes out, int ldo, float* out_f, int ldo_f, hipStream_t s) {
+  HIPRET(launch_rmsnorm(norm_args(x, ldx, M, d, seq_len, gamma, cond, cond_ld, out, ldo, out_f, ldo_f), s));
   return NS2_OK;
 }
 
@@ -834,25 +868,24 @@ static int prof_start(ns2_model* m, int cat, hipStream_t s) {
   HIPRET(hipEventRecord(m->prof_events[m->prof_used].first, s));
   return NS2_OK;
 }
-static int prof_stop(ns2_model* m, int cat, hipStream_t s) {
+// counted: this launch is a logical product of the step (the whole batch, or chain 0's part of it); chain 1's part adds its time only
+static int prof_stop(ns2_model* m, int cat, bool counted, hipStream_t s) {
   if (!(m->prof_mask & (1u << cat))) return NS2_OK;
   HIPRET(hipEventRecord(m->prof_events[m->prof_used].second, s));
   m->prof_used++;
+  if (counted) m->prof_products++;
   return NS2_OK;
 }
-#define PROF(cat, call)                 \
-  do {                                  \
-    NSCHK(prof_start(m, cat, s));       \
-    NSCHK(call);                        \
-    NSCHK(prof_stop(m, cat, s));        \
-  } while (0)
 
 extern "C" int ns2_model_profile_begin(ns2_model* m, unsigned category_mask) {
   if (!m) return NS2_ERR_ARG;
   m->prof_mask = category_mask;
   m->prof_used = 0;
+  m->prof_products = 0;
   return NS2_OK;
 }
+// launches = logical products of the selected categories: the two parts of a product that ran as two chains count once, and total_ms
+// adds the time of both parts (each measured on its own stream, while the other chain's kernels share the chip: DESIGN section 6)
 extern "C" int ns2_model_profile_end(ns2_model* m, double* total_ms, int64_t* launches) {
   if (!m || !total_ms || !launches) return NS2_ERR_ARG;
   double tot = 0.0;
@@ -863,13 +896,282 @@ extern "C" int ns2_model_profile_end(ns2_model* m, double* total_ms, int64_t* la
     tot += ms;
   }
   *total_ms = tot;
-  *launches = (int64_t)m->prof_used;
+  *launches = (int64_t)m->prof_products;
   m->prof_mask = 0;
   m->prof_used = 0;
+  m->prof_products = 0;
   return NS2_OK;
 }
 
 // ------------------------------------------------------------------------------------------------ forward
+// The row-dependent part of a step -- everything behind the conditioning projections -- is DESCRIBED, as a list of launches over the
+// utterances [b0, b0 + B) of every buffer, apart from being ENQUEUED.  Every kernel of it is row-local or utterance-local and every
+// operand is batch-major, so the list of a part of the batch is the list of the whole batch with offset pointers and its own M / B:
+// no extra workspace.  forward_impl enqueues either the whole batch's list on the caller's stream (today's sequence), or the lists of
+// two halves ("chains") on two streams, alternating, so that the dispatcher has a second kernel to place workgroups from while one
+// chain's kernel drains, ramps, runs a partial last round or waits on HBM ("Two utterance chains").
+namespace {
+struct Launch {
+  enum Kind : int { GEMM, NORM, ATTN, SPLIT, TAP_F32, TAP_PLANES };
+  enum Mark : int { NONE = 0, INIT_CONV = 1, WAVENET = 2, OUT_PROJ = 3 };   // where chain 1 may be made to start (NS2_CHAIN_SKEW)
+  Kind kind = GEMM;
+  int cat = -1;                  // profile category (PC_*), -1 = not a timed product
+  int prec = 0;                  // GEMM / ATTN: the arithmetic of the call
+  int mark = NONE;
+  GemmArgs g; AttnArgs a; NormArgs n{};
+  // SPLIT: f (+ add) -> p;  TAP_F32: f -> the tap `name`;  TAP_PLANES: p -> the tap `name`
+  const float* f = nullptr; const float* add = nullptr; int add_rows = 0, add_valid = 0;
+  Planes p{}; int ld = 0; int64_t rows = 0; int d = 0, seq_len = 0;
+  char name[32] = {0};
+};
+}  // namespace
+struct ns2_model::Program { std::vector<Launch> v; };
+
+namespace {
+// rows [row0, ...) of planes whose rows have ld logical elements (the physical row is twice that where the lo plane exists)
+Planes rows_of(Planes p, int64_t row0, int64_t ld) {
+  const int64_t off = row0 * ld * (p.lo ? 2 : 1);
+  p.hi += off;
+  if (p.lo) p.lo += off;
+  return p;
+}
+// the same memory read in another format (a part of the batch keeps its views inside its own rows of the buffer)
+Planes view_as(Planes p, bool il, int fmt) { p.lo = il ? p.hi + 32 : nullptr; p.fmt = fmt; return p; }
+
+struct StepArgs {                // what forward_impl resolved for the whole batch
+  const float* x; float* out;
+  const float* call; int cld;    // [gamma | beta] blocks of all FiLM / adaptive-norm projections; row b at call + b * cld
+  int n_cond, N;
+};
+
+int enqueue(ns2_model* m, const Launch& l, bool counted, hipStream_t s);
+// where describe_rows puts a launch: onto a list (a chain, or the whole batch while the chain rule is still to be asked), or -- where one
+// chain is certain -- straight onto the stream, so that the kernels start while the rest is being described
+struct Sink {
+  std::vector<Launch>* prog; ns2_model* m; hipStream_t s; int rc;
+  void push_back(const Launch& l) {
+    if (prog) prog->push_back(l);
+    else if (rc == NS2_OK) rc = enqueue(m, l, true, s);
+  }
+};
+
+void describe_rows(const ns2_model* m, const Work& w0, const CondState* cs, const StepArgs& st, int b0, int B, Sink* prog) {
+  const bool cond = m->cfg.condition_on_prompt;
+  const int dim = m->dim, a = m->a, dp = m->dp, fp = m->fp, L = m->L, S = m->S, H = m->cfg.heads, prec = op_precision(m->cfg.precision);
+  const int N = st.N, M = B * N, Lm = m->Lm, fpc = m->fpc, cld = st.cld;
+  const int64_t r0 = (int64_t)b0 * N;
+  const int conv_prec = hybrid_plan(m->cfg.precision) ? 2 : prec;
+  const int ff_prec = ff_half_plan(m->cfg.precision) ? 2 : prec;
+  const Fmts F = fmts_for(prec);
+  const int xprec = F.xatt_prec;
+  // ---- this part's rows of every buffer
+  const float* x = st.x + r0 * dim;
+  float* out = st.out + r0 * dim;
+  float* xres = w0.xres + r0 * dim;
+  const float* call = st.call + (size_t)b0 * cld;
+  const Planes xs = rows_of(w0.xs, r0, dp), h0 = rows_of(w0.h0, r0, dp), ssum = rows_of(w0.ssum, r0, dp), xn = rows_of(w0.xn, r0, dp);
+  const Planes qk = rows_of(w0.qk, r0, 2 * a), o = rows_of(w0.o, r0, a), ffc = rows_of(w0.ffc, r0, fp);
+  const Planes vt = rows_of(w0.vt, b0, (int64_t)a * w0.Nkp);
+  const Planes ffh = rows_of(w0.ffh, r0, std::max(fp, fpc));
+  // views of the same rows in another format: cross-attention queries [M, a] (M x a interleaved fits M x 2a dense 16-bit), the FF conv's
+  // dense IEEE-half input (hybrid plans), and (precision 6) dense IEEE-half planes through the whole feed-forward branch
+  const Planes xq = view_as(qk, F.xatt_il, F.xatt);
+  const Planes ffh_conv = hybrid_plan(m->cfg.precision) ? view_as(ffh, false, FMT_F16) : ffh;
+  const Planes xn_ff = ff_half_plan(m->cfg.precision) ? view_as(xn, false, FMT_F16) : xn;
+  const Planes ffc_ff = ff_half_plan(m->cfg.precision) ? view_as(ffc, false, FMT_F16) : ffc;
+  const bool taps = !m->taps.empty();
+
+  auto gemm = [&](const GemmArgs& g, int gprec, int cat, int mark = Launch::NONE) {
+    Launch l; l.kind = Launch::GEMM; l.g = g; l.prec = gprec; l.cat = cat; l.mark = mark;
+    prog->push_back(l);
+  };
+  auto attention = [&](const AttnArgs& at, int aprec) {
+    Launch l; l.kind = Launch::ATTN; l.a = at; l.prec = aprec; l.cat = PC_ATTENTION;
+    prog->push_back(l);
+  };
+  auto tap_f = [&](const char* name, const float* src) {
+    if (!taps) return;
+    Launch l; l.kind = Launch::TAP_F32; l.f = src; l.rows = M; l.d = dim; snprintf(l.name, sizeof l.name, "%s", name);
+    prog->push_back(l);
+  };
+  auto tap_p = [&](const char* name, Planes p, int ld, int d) {
+    if (!taps) return;
+    Launch l; l.kind = Launch::TAP_PLANES; l.p = p; l.ld = ld; l.rows = M; l.d = d; snprintf(l.name, sizeof l.name, "%s", name);
+    prog->push_back(l);
+  };
+  char name[32];
+
+  // ---- x (+ aligned conditioning, NS2:976-992) -> split planes
+  {
+    Launch l; l.kind = Launch::SPLIT; l.f = x; l.d = dim; l.p = xs; l.ld = dp; l.rows = M; l.seq_len = N;
+    if (cond) { l.add = cs->condadd + (size_t)b0 * st.n_cond * dim; l.add_rows = st.n_cond; l.add_valid = cs->n_cond_valid; }
+    prog->push_back(l);
+  }
+  // ---- wavenet (NS2:718-725)
+  {
+    GemmArgs g = product(m->w_init, xs, dp, M);
+    set_conv(g, m->w_init, 3, 1, N);
+    set_out_planes(g, EPI_SPLIT, h0.hi, h0.lo, dp); g.bias = m->b_init;
+    gemm(g, prec, PC_GEMM_SPLIT, Launch::INIT_CONV);
+  }
+  tap_p("wavenet.init", h0, dp, dim);
+  Planes cur = rows_of(w0.wA, r0, (int64_t)L * dp), prev = rows_of(w0.wB, r0, (int64_t)L * dp);
+  for (int s_ = 0; s_ < S; ++s_) {
+    // the L columns of the stack as grid-z layers: layer z reads column block z of the previous stack (all of them h0 for the first),
+    // runs at dilation 1 << z with its own matrix, biases and FiLM row, and writes column block z
+    GemmArgs g = (s_ == 0) ? product(m->w_wn[s_], h0, dp, M) : product(m->w_wn[s_], prev, L * dp, M);
+    set_wavenet(g, m->w_wn[s_], 1, N, prec, hybrid_plan(m->cfg.precision) ? 1 : 0);
+    g.dil_z = 1; g.nz = L; g.a_zs = (s_ == 0) ? 0 : dp; g.bias_zs = dim; g.film_zs = 2 * dim; g.out_zs = dp;
+    g.bias = m->b_wn_conv[s_]; g.bias2 = m->b_wn_res[s_]; g.film = call + (size_t)s_ * L * 2 * dim; g.film_ld = cld;
+    g.out_hi = cur.hi; g.out_lo = cur.lo; g.ldo_s = L * dp; g.out_ncols = dp;
+    gemm(g, prec, PC_GEMM_WAVENET, s_ + 1 == S ? Launch::WAVENET : Launch::NONE);
+    snprintf(name, sizeof name, "wavenet.stack%d", s_);
+    tap_p(name, cur, L * dp, L * dp);
+    std::swap(prev, cur);
+  }
+  // sum of the 8 skip convs == one GEMM over the concatenated columns (NS2:639-640, 685-686, 725), then final_conv
+  {
+    GemmArgs g = product(m->w_skip, prev, L * dp, M);
+    set_out_planes(g, EPI_SPLIT, ssum.hi, ssum.lo, dp); g.bias = m->b_skip;
+    gemm(g, prec, PC_GEMM_SPLIT);
+  }
+  // Every update of the residual stream is followed by exactly one RMSNorm that reads it (NS2:794-807, 781-784): `update_then_norm` runs
+  // the pair as one launch where the GEMM's workgroups own whole rows (dim = 128: the 128 x 128 kernel, gemm.hip; gemm_fuses_norm says
+  // so), else as the GEMM + rmsnorm_kernel.  cld == 0 with ncond != null: every utterance reads the same (gamma, beta) row (the time table).
+  const float* cbase = call + (size_t)S * L * 2 * dim;
+  auto update_then_norm = [&](const PackedW& pw, const Planes& ap, int lda, const float* bias, bool add_resid, int gprec, const float* gamma,
+                              const float* ncond, const Planes& nout, int mark = Launch::NONE) {
+    GemmArgs g = product(pw, ap, lda, M);
+    g.bias = bias; g.resid = add_resid ? xres : nullptr; g.ldr = dim; g.out_f = xres; g.ldo_f = dim;
+    const bool fused = gemm_fuses_norm(g, gprec);
+    if (fused) {
+      g.nrm_hi = nout.hi; g.nrm_lo = nout.lo; g.nrm_ld = dp; g.nrm_fmt = nout.fmt;
+      g.nrm_gamma = gamma; g.nrm_cond = ncond; g.nrm_cond_ld = cld; g.nrm_seq_len = N;
+    }
+    gemm(g, gprec, PC_GEMM_F32, mark);
+    if (!fused) {
+      Launch l; l.kind = Launch::NORM; l.cat = PC_NORM;
+      l.n = norm_args(xres, dim, M, dim, N, gamma, ncond, cld, nout, dp, nullptr, 0);
+      prog->push_back(l);
+    }
+  };
+  auto layer_cond = [&](int l, int which) { return cbase + (size_t)l * m->nnorm * 2 * dim + (size_t)which * 2 * dim; };
+  // final_conv of the Wavenet -> the residual stream, normed for layer 0's self attention
+  update_then_norm(m->w_final, ssum, dp, m->b_final, false, prec, nullptr, layer_cond(0, 0), xn);
+  tap_f("wavenet.out", xres);
+
+  // ---- transformer (NS2:786-809)
+  for (int l = 0; l < m->cfg.depth; ++l) {
+    const ns2_model::Layer& ly = m->layers[l];
+    const bool last = l + 1 == m->cfg.depth;
+    // self attention (its norm ran behind the previous update)
+    GemmArgs qkv = product(ly.qkv, xn, dp, M);
+    set_qkv(qkv, prec, N, 2 * a, qk.hi, qk.lo, 2 * a); qkv.vt_hi = vt.hi; qkv.vt_lo = vt.lo; qkv.vt_ld = w0.Nkp;
+    gemm(qkv, prec, PC_GEMM_QKV);
+    attention(attn_args(qk.hi, qk.lo, 2 * a, 0, qk.hi, qk.lo, 2 * a, a, vt, w0.Nkp, o, a, B, H, N, N, m->cfg.dim_head), prec);
+    // out-projection + residual, then the norm of what follows: the cross attention (conditioned) or the feed-forward
+    update_then_norm(ly.out, o, a, nullptr, true, prec, nullptr, layer_cond(l, cond ? 1 : m->nnorm - 1), cond ? xn : xn_ff,
+                     l == 0 ? Launch::OUT_PROJ : Launch::NONE);
+    snprintf(name, sizeof name, "layer%d.attn", l);
+    tap_f(name, xres);
+    if (cond) {   // cross attention to the resampled prompt tokens (NS2:799-803)
+      const Planes ck = rows_of(cs->ck[l], (int64_t)b0 * Lm, a), cvt = rows_of(cs->cvt[l], b0, (int64_t)a * cs->Lmp);
+      GemmArgs cq = product(ly.cq, xn, dp, M);
+      set_out_planes(cq, EPI_SPLIT, xq.hi, xq.lo, a); cq.out_fmt = xq.fmt;
+      gemm(cq, prec, PC_GEMM_SPLIT);
+      attention(attn_args(xq.hi, xq.lo, a, 0, ck.hi, ck.lo, a, 0, cvt, cs->Lmp, o, a, B, H, N, Lm, m->cfg.dim_head), xprec);
+      update_then_norm(ly.cout, o, a, nullptr, true, prec, nullptr, layer_cond(l, m->nnorm - 1), xn_ff);
+    }
+    // feedforward: Linear -> GEGLU -> causal conv k3 -> Linear (NS2:1009-1025); precision 6: the whole branch on dense IEEE-half planes
+    GemmArgs ffin = product(ly.ffin, xn_ff, dp, M), conv = product(ly.conv, ffh_conv, fpc, M);
+    set_geglu(ffin, ffh_conv.hi, ffh_conv.lo, fpc, fp); ffin.bias = ly.b_ffin; ffin.out_fmt = ffh_conv.fmt;
+    gemm(ffin, ff_prec, PC_GEMM_GEGLU);
+    set_conv(conv, ly.conv, 3, 1, N);
+    set_out_planes(conv, EPI_SPLIT, ffc_ff.hi, ffc_ff.lo, fp); conv.bias = ly.b_conv; conv.out_fmt = ffc_ff.fmt;
+    gemm(conv, conv_prec, PC_GEMM_FFCONV);
+    // FF-out + residual, then the next layer's self-attention norm -- or to_pred's RMSNorm (learned gamma, NS2:781-784) after the last
+    update_then_norm(ly.ffout, ffc_ff, fp, ly.b_ffout, true, ff_prec, last ? m->g_pred : nullptr, last ? nullptr : layer_cond(l + 1, 0), xn);
+    snprintf(name, sizeof name, "layer%d", l);
+    tap_f(name, xres);
+  }
+  // to_pred: Linear on the normed stream (NS2:781-784)
+  GemmArgs pred = product(m->w_pred, xn, dp, M);
+  pred.out_f = out; pred.ldo_f = dim;
+  gemm(pred, prec, PC_GEMM_F32);
+}
+
+int enqueue(ns2_model* m, const Launch& l, bool counted, hipStream_t s) {
+  if (l.cat >= 0) NSCHK(prof_start(m, l.cat, s));
+  switch (l.kind) {
+    case Launch::GEMM: HIPRET(launch_gemm(l.g, l.prec, s)); break;
+    case Launch::NORM: HIPRET(launch_rmsnorm(l.n, s)); break;
+    case Launch::ATTN: HIPRET(launch_attention(l.a, l.prec, s)); break;
+    case Launch::SPLIT:
+      HIPRET(launch_split(l.f, l.d, l.add, l.d, l.add_rows, l.add_valid, l.p.hi, l.p.lo, l.ld, (int)l.rows, l.d, l.seq_len, s, l.p.fmt));
+      break;
+    case Launch::TAP_F32: NSCHK(tap_f32(m, l.name, l.f, l.rows * l.d, s)); break;
+    case Launch::TAP_PLANES: NSCHK(tap_planes(m, l.name, l.p, l.ld, l.rows, l.d, s)); break;
+  }
+  if (l.cat >= 0) NSCHK(prof_stop(m, l.cat, counted, s));
+  return NS2_OK;
+}
+
+// ---- the chain rule.  Two chains of ceil(B / 2) and floor(B / 2) utterances run only if every product of the step takes, for each
+// chain's M, the route launch_gemm takes for the whole batch (plan_gemm: the same kernel, hence the same order of every sum and the
+// same bits), no product splits K (the split's scratch is one region of the workspace: two chains would share it), a residual update
+// fuses its norm for all three or for none, and each chain is whole 256-row tiles (its rows of every buffer start on a tile and on the
+// 256-byte alignment the workspace carver gives the whole batch).  Pure host arithmetic over the described launches.
+bool same_plan(const std::vector<Launch>& whole, const std::vector<Launch>& part) {
+  if (whole.size() != part.size()) return false;
+  for (size_t i = 0; i < whole.size(); ++i) {
+    const Launch &a = whole[i], &b = part[i];
+    if (a.kind != b.kind) return false;
+    if (a.kind != Launch::GEMM) continue;
+    const GemmPlan pa = plan_gemm(a.g, a.prec), pb = plan_gemm(b.g, b.prec);
+    if (pa.route != pb.route || pa.S != 1 || pb.S != 1 || pa.c != pb.c || (a.g.nrm_hi != nullptr) != (b.g.nrm_hi != nullptr)) return false;
+  }
+  return true;
+}
+int chains_by_rule(const ns2_model* m, const Work& w, const CondState* cs, const StepArgs& st, int B, std::vector<Launch>* whole,
+                   std::vector<Launch>* c0, std::vector<Launch>* c1) {
+  const int B0 = (B + 1) / 2, B1 = B - B0;
+  if (B1 < 1 || (((int64_t)B0 * st.N) & 255) || (((int64_t)B1 * st.N) & 255)) return 1;
+  c0->clear(); c1->clear();
+  Sink s0{c0, nullptr, nullptr, NS2_OK}, s1{c1, nullptr, nullptr, NS2_OK};
+  describe_rows(m, w, cs, st, 0, B0, &s0);
+  describe_rows(m, w, cs, st, B0, B1, &s1);
+  return same_plan(*whole, *c0) && same_plan(*whole, *c1) ? 2 : 1;
+}
+
+// Test hook (ns2_debug_force_chains / NS2_CHAINS) in the manner of gemm2.hip's gemm_hook(): process-wide, atomic.  -1: read NS2_CHAINS
+// once.  0: the library's default (NS2_CHAINS_DEFAULT below), 1: one chain, 2: two chains wherever the rule allows.
+std::atomic<int> g_forced_chains{-1};
+std::atomic<int> g_chains_last{0};
+int chains_wanted() {
+  int f = g_forced_chains.load(std::memory_order_relaxed);
+  if (f < 0) {
+    const char* e = getenv("NS2_CHAINS");
+    f = e ? atoi(e) : 0;
+    if (f < 0 || f > 2) f = 0;
+    g_forced_chains.store(f, std::memory_order_relaxed);
+  }
+  return f ? f : NS2_CHAINS_DEFAULT;
+}
+}  // namespace
+
+namespace ns2 {
+// bumped by ns2_debug_force_gemm (capi.cpp): the routes plan_gemm gives may have changed, a cached verdict of the chain rule is stale
+static std::atomic<unsigned> g_gemm_hook_epoch{1};
+void gemm_hook_changed() { g_gemm_hook_epoch.fetch_add(1, std::memory_order_relaxed); }
+}  // namespace ns2
+
+extern "C" int ns2_debug_force_chains(int chains) {
+  ARGCHK(chains >= 0 && chains <= 2, "ns2_debug_force_chains: 0 = the default, 1 = one chain, 2 = two chains wherever the chain rule allows");
+  g_forced_chains.store(chains, std::memory_order_relaxed);
+  return NS2_OK;
+}
+extern "C" int ns2_debug_chains_last(void) { return g_chains_last.load(std::memory_order_relaxed); }
+
 // cond_row != null: the step's time conditioning comes from a row of the table ns2_model_time_table built ahead of the run
 // (the sampler's times are known up front and shared by the batch, NS2:1303-1308): no projection is launched in the step
 static int forward_impl(ns2_model* m, const float* x, const float* times, const float* cond_row, const void* cond_state, int n_cond, float* out,
@@ -887,21 +1189,14 @@ static int forward_impl(ns2_model* m, const float* x, const float* times, const 
   SplitKScope sk_scope(w.sk_ws);
   CondState cs;
   if (cond) carve_cond(m, &cs, const_cast<void*>(cond_state), 0, B, N, n_cond);
-  const int dim = m->dim, a = m->a, dp = m->dp, fp = m->fp, L = m->L, S = m->S, H = m->cfg.heads, prec = op_precision(m->cfg.precision);
-  const int M = B * N, Jtot = m->Jtot, Lm = m->Lm, fpc = m->fpc;
-  const int conv_prec = hybrid_plan(m->cfg.precision) ? 2 : prec;
-  const int ff_prec = ff_half_plan(m->cfg.precision) ? 2 : prec;
-  Planes xn_ff = w.xn, ffc_ff = w.ffc;                 // precision 6: dense IEEE-half views of the same memory
-  if (ff_half_plan(m->cfg.precision)) { xn_ff.lo = nullptr; xn_ff.fmt = FMT_F16; ffc_ff.lo = nullptr; ffc_ff.fmt = FMT_F16; }
-  const int xprec = fmts_for(prec).xatt_prec;
-  char name[64];
+  const int dim = m->dim, Jtot = m->Jtot;
 
-  // ---- t = to_time_cond(times) [, prompt_cond]  (NS2:944-960), then every conditioning projection of the step at once
-  const float* call = w.condall;     // [gamma | beta] blocks of all FiLM / adaptive-norm projections; row b at call + b * cld
-  int cld = Jtot;
+  // ---- t = to_time_cond(times) [, prompt_cond]  (NS2:944-960), then every conditioning projection of the step at once: the only
+  // batch-wide work of a step, on the caller's stream in front of the chains
+  StepArgs st{x, out, w.condall, Jtot, n_cond, N};
   if (cond_row) {
     if (cond) HIPRET(launch_add_row(cond_row, cs.pbias, w.condall, B, Jtot, s));     // time half (hoisted) + prompt half (per utterance)
-    else { call = cond_row; cld = 0; }                                                // every utterance reads the same row
+    else { st.call = cond_row; st.cld = 0; }                                          // every utterance reads the same row
   } else {
     HIPRET(launch_time_embed(times, m->freqs, m->wt_time, m->b_time, w.tfeat, w.t, m->Tc, B, dim, m->dt, w.skinny_ws, w.skinny_ws_bytes, s));
     if (cond)
@@ -911,95 +1206,135 @@ static int forward_impl(ns2_model* m, const float* x, const float* times, const 
     HIPRET(launch_skinny_linear(w.t, m->Tc, m->wt_cond, m->b_cond, w.condall, Jtot, B, m->Tc, Jtot, 0, w.skinny_ws, w.skinny_ws_bytes, s));
   }
 
-  // ---- x (+ aligned conditioning, NS2:976-992) -> split planes
-  HIPRET(launch_split(x, dim, cond ? cs.condadd : nullptr, dim, n_cond, cond ? cs.n_cond_valid : 0, w.xs.hi, w.xs.lo, dp, M, dim, N, s, w.xs.fmt));
-
-  // ---- wavenet (NS2:718-725)
-  {
-    GemmArgs g = product(m->w_init, w.xs, dp, M);
-    set_conv(g, m->w_init, 3, 1, N);
-    set_out_planes(g, EPI_SPLIT, w.h0.hi, w.h0.lo, dp); g.bias = m->b_init;
-    PROF(PC_GEMM_SPLIT, run_gemm(g, prec, s));
+  // ---- the row-dependent part: one chain on the caller's stream, or two on two streams
+  bool may_chain = chains_wanted() == 2 && B >= 2 && m->taps.empty();
+  if (may_chain) {
+    // a captured step keeps no parallel branches: one chain while the caller's stream is capturing (or cannot say)
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cap) != hipSuccess) { (void)hipGetLastError(); cap = hipStreamCaptureStatusActive; }
+    may_chain = cap == hipStreamCaptureStatusNone;
   }
-  NSCHK(tap_planes(m, "wavenet.init", w.h0, dp, M, dim, s));
-  Planes cur = w.wA, prev = w.wB;
-  for (int st = 0; st < S; ++st) {
-    // the L columns of the stack as grid-z layers: layer z reads column block z of the previous stack (all of them h0 for the first),
-    // runs at dilation 1 << z with its own matrix, biases and FiLM row, and writes column block z
-    GemmArgs g = (st == 0) ? product(m->w_wn[st], w.h0, dp, M) : product(m->w_wn[st], prev, L * dp, M);
-    set_wavenet(g, m->w_wn[st], 1, N, prec, hybrid_plan(m->cfg.precision) ? 1 : 0);
-    g.dil_z = 1; g.nz = L; g.a_zs = (st == 0) ? 0 : dp; g.bias_zs = dim; g.film_zs = 2 * dim; g.out_zs = dp;
-    g.bias = m->b_wn_conv[st]; g.bias2 = m->b_wn_res[st]; g.film = call + (size_t)st * L * 2 * dim; g.film_ld = cld;
-    g.out_hi = cur.hi; g.out_lo = cur.lo; g.ldo_s = L * dp; g.out_ncols = dp;
-    PROF(PC_GEMM_WAVENET, run_gemm(g, prec, s));
-    snprintf(name, sizeof name, "wavenet.stack%d", st);
-    NSCHK(tap_planes(m, name, cur, L * dp, M, L * dp, s));
-    Planes tmp = prev; prev = cur; cur = tmp;
-  }
-  // sum of the 8 skip convs == one GEMM over the concatenated columns (NS2:639-640, 685-686, 725), then final_conv
-  {
-    GemmArgs g = product(m->w_skip, prev, L * dp, M);
-    set_out_planes(g, EPI_SPLIT, w.ssum.hi, w.ssum.lo, dp); g.bias = m->b_skip;
-    PROF(PC_GEMM_SPLIT, run_gemm(g, prec, s));
-  }
-  // Every update of the residual stream is followed by exactly one RMSNorm that reads it (NS2:794-807, 781-784): `update_then_norm` runs
-  // the pair as one launch where the GEMM's workgroups own whole rows (dim = 128: the 128 x 128 kernel, gemm.hip; gemm_fuses_norm says
-  // so), else as the GEMM + rmsnorm_kernel.  cld == 0 with ncond != null: every utterance reads the same (gamma, beta) row (the time table).
-  const float* cbase = call + (size_t)S * L * 2 * dim;
-  auto update_then_norm = [&](const PackedW& pw, const Planes& a, int lda, const float* bias, bool add_resid, int gprec, const float* gamma,
-                              const float* ncond, const Planes& nout) -> int {
-    GemmArgs g = product(pw, a, lda, M);
-    g.bias = bias; g.resid = add_resid ? w.xres : nullptr; g.ldr = dim; g.out_f = w.xres; g.ldo_f = dim;
-    const bool fused = gemm_fuses_norm(g, gprec);
-    if (fused) {
-      g.nrm_hi = nout.hi; g.nrm_lo = nout.lo; g.nrm_ld = dp; g.nrm_fmt = nout.fmt;
-      g.nrm_gamma = gamma; g.nrm_cond = ncond; g.nrm_cond_ld = cld; g.nrm_seq_len = N;
+  // the rule's verdict: asked once per (shape, buffer alignment, GEMM hook), from the described launches of the whole batch and of both chains
+  const CondState* csp = cond ? &cs : nullptr;
+  int chains = 1;
+  bool described = false;                 // prog[1] / prog[2] hold this step's chains
+  if (may_chain) {
+    const unsigned epoch = g_gemm_hook_epoch.load(std::memory_order_relaxed);
+    const uintptr_t align = ((reinterpret_cast<uintptr_t>(workspace) | reinterpret_cast<uintptr_t>(cond_state) | reinterpret_cast<uintptr_t>(x) |
+                              reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(st.call)) & 255);
+    auto& r = m->rule;
+    if (r.chains == 0 || r.B != B || r.N != N || r.n_cond != n_cond || r.hook_epoch != epoch || r.align != align) {
+      std::vector<Launch>& whole = m->prog[0]->v;
+      whole.clear();
+      Sink list{&whole, nullptr, nullptr, NS2_OK};
+      describe_rows(m, w, csp, st, 0, B, &list);
+      r.chains = chains_by_rule(m, w, csp, st, B, &whole, &m->prog[1]->v, &m->prog[2]->v);
+      r.B = B; r.N = N; r.n_cond = n_cond; r.hook_epoch = epoch; r.align = align;
+      described = r.chains == 2;
     }
-    PROF(PC_GEMM_F32, run_gemm(g, gprec, s));
-    if (!fused) PROF(PC_NORM, norm_call(w.xres, dim, M, dim, N, gamma, ncond, cld, nout, dp, nullptr, 0, s));
-    return NS2_OK;
+    chains = r.chains;
+  }
+  g_chains_last.store(chains, std::memory_order_relaxed);
+  if (chains == 1) {                      // today's sequence, each launch enqueued as it is described
+    Sink now{nullptr, m, s, NS2_OK};
+    describe_rows(m, w, csp, st, 0, B, &now);
+    return now.rc;
+  }
+  if (!described) {
+    const int B0 = (B + 1) / 2;
+    m->prog[1]->v.clear(); m->prog[2]->v.clear();
+    Sink s0{&m->prog[1]->v, nullptr, nullptr, NS2_OK}, s1{&m->prog[2]->v, nullptr, nullptr, NS2_OK};
+    describe_rows(m, w, csp, st, 0, B0, &s0);
+    describe_rows(m, w, csp, st, B0, B - B0, &s1);
+  }
+  // Chain 0 on the caller's stream, chain 1 on the model's own; launches enqueued product by product, alternating.  Fork: chain 1 waits
+  // for an event recorded on the caller's stream -- behind the conditioning, and behind chain 0's first `lead` launches where a skew is
+  // compiled in (measured: every skew loses to none, profiles/chains_ab.json).  Join: the caller's stream waits for chain 1's to_pred --
+  // also when a launch in between failed, so that the caller's stream stays ordered behind whatever chain 1 has in flight on the
+  // caller's workspace.  No allocation, no synchronisation.
+  const std::vector<Launch>&c0 = m->prog[1]->v, &c1 = m->prog[2]->v;
+  size_t lead = 0;
+  for (size_t i = 0; i < c0.size() && NS2_CHAIN_SKEW; ++i)
+    if (c0[i].mark == NS2_CHAIN_SKEW) { lead = i + 1; break; }
+  for (size_t i = 0; i < lead; ++i) NSCHK(enqueue(m, c0[i], true, s));
+  HIPRET(hipEventRecord(m->ev_fork, s));
+  HIPRET(hipStreamWaitEvent(m->chain_stream, m->ev_fork, 0));
+  int rc = NS2_OK;
+  for (size_t i = 0; i < c1.size() && rc == NS2_OK; ++i) {
+    if (lead + i < c0.size()) rc = enqueue(m, c0[lead + i], true, s);
+    if (rc == NS2_OK) rc = enqueue(m, c1[i], false, m->chain_stream);
+  }
+  const hipError_t ej = hipEventRecord(m->ev_join, m->chain_stream);
+  const hipError_t ew = ej == hipSuccess ? hipStreamWaitEvent(s, m->ev_join, 0) : ej;
+  NSCHK(rc);
+  HIPRET(ew);
+  return NS2_OK;
+}
+
+// the second chain's stream (non-blocking: no implicit ordering against the legacy default stream), the fork / join events, the launch lists
+static int create_chain_state(ns2_model* m) {
+  for (auto& p : m->prog) { p = new ns2_model::Program(); p->v.reserve(16 + m->cfg.wavenet_stacks * 2 + m->cfg.depth * 16); }
+  HIPRET(hipStreamCreateWithFlags(&m->chain_stream, hipStreamNonBlocking));
+  HIPRET(hipEventCreateWithFlags(&m->ev_fork, hipEventDisableTiming));
+  HIPRET(hipEventCreateWithFlags(&m->ev_join, hipEventDisableTiming));
+  return NS2_OK;
+}
+static void destroy_chain_state(ns2_model* m) {
+  if (m->chain_stream) { (void)hipStreamSynchronize(m->chain_stream); (void)hipStreamDestroy(m->chain_stream); }
+  if (m->ev_fork) (void)hipEventDestroy(m->ev_fork);
+  if (m->ev_join) (void)hipEventDestroy(m->ev_join);
+  for (auto& p : m->prog) { delete p; p = nullptr; }
+}
+
+// The chain rule for a configuration, without a device: the packed weights of a step as ns2_model_finalize shapes them (sizes, formats,
+// which tiled images exist) behind placeholder addresses that are never read, the workspace carved at a placeholder base, and the same
+// describe_rows / chains_by_rule a forward runs.  *chains = what a forward of B x N frames runs where two chains are wanted.
+extern "C" int ns2_debug_chain_rule(const ns2_model_config* cfg, int B, int N, int* chains) {
+  if (!cfg || !chains || B <= 0 || N <= 0) { set_error("ns2_debug_chain_rule: bad arguments"); return NS2_ERR_ARG; }
+  ns2_model mm;
+  ns2_model* m = &mm;
+  NSCHK(derive_dims(m, cfg));
+  bf16_t* const fake = reinterpret_cast<bf16_t*>(uintptr_t(1) << 40);
+  float* const fakef = reinterpret_cast<float*>(fake);
+  const PackCtx pc = pack_ctx_for(nullptr, op_precision(cfg->precision));
+  const PackCtx pc_conv = hybrid_plan(cfg->precision) ? pack_ctx_for(nullptr, 2) : pc;
+  const PackCtx pc_ff = ff_half_plan(cfg->precision) ? pack_ctx_for(nullptr, 2) : pc;
+  auto shape = [&](PackedW* w, const PackCtx& c, int rows, int cols, int taps) {     // alloc_packed via pack_linear, + build_lin_tiles
+    const int Cp = rup(cols, 32);
+    w->N = rows; w->rows_p = rup(rows, 256); w->ldk = taps * Cp; w->nkt = w->ldk / 32; w->kt_per_tap = Cp / 32;
+    w->hi = fake; w->lo = c.il ? fake + 32 : nullptr; w->fmt = c.fmt;
+    if (w->fmt == FMT_H8 && w->lo && w->nkt == w->kt_per_tap && w->nkt >= 3 && !(w->rows_p & 255)) w->tl = fake;
   };
-  auto layer_cond = [&](int l, int which) { return cbase + (size_t)l * m->nnorm * 2 * dim + (size_t)which * 2 * dim; };
-  // final_conv of the Wavenet -> the residual stream, normed for layer 0's self attention
-  NSCHK(update_then_norm(m->w_final, w.ssum, dp, m->b_final, false, prec, nullptr, layer_cond(0, 0), w.xn));
-  NSCHK(tap_f32(m, "wavenet.out", w.xres, (int64_t)M * dim, s));
-
-  // ---- transformer (NS2:786-809)
-  for (int l = 0; l < m->cfg.depth; ++l) {
-    const ns2_model::Layer& ly = m->layers[l];
-    const bool last = l + 1 == m->cfg.depth;
-    // self attention (its norm ran behind the previous update)
-    GemmArgs qkv = product(ly.qkv, w.xn, dp, M);
-    set_qkv(qkv, prec, N, 2 * a, w.qk.hi, w.qk.lo, 2 * a); qkv.vt_hi = w.vt.hi; qkv.vt_lo = w.vt.lo; qkv.vt_ld = w.Nkp;
-    PROF(PC_GEMM_QKV, run_gemm(qkv, prec, s));
-    PROF(PC_ATTENTION, attention_call(w.qk.hi, w.qk.lo, 2 * a, 0, w.qk.hi, w.qk.lo, 2 * a, a, w.vt, w.Nkp, w.o, a, B, H, N, N, prec, s, m->cfg.dim_head));
-    // out-projection + residual, then the norm of what follows: the cross attention (conditioned) or the feed-forward
-    NSCHK(update_then_norm(ly.out, w.o, a, nullptr, true, prec, nullptr, layer_cond(l, cond ? 1 : m->nnorm - 1), cond ? w.xn : xn_ff));
-    snprintf(name, sizeof name, "layer%d.attn", l);
-    NSCHK(tap_f32(m, name, w.xres, (int64_t)M * dim, s));
-    if (cond) {   // cross attention to the resampled prompt tokens (NS2:799-803)
-      GemmArgs cq = product(ly.cq, w.xn, dp, M);
-      set_out_planes(cq, EPI_SPLIT, w.xq.hi, w.xq.lo, a); cq.out_fmt = w.xq.fmt;
-      PROF(PC_GEMM_SPLIT, run_gemm(cq, prec, s));
-      PROF(PC_ATTENTION, attention_call(w.xq.hi, w.xq.lo, a, 0, cs.ck[l].hi, cs.ck[l].lo, a, 0, cs.cvt[l], cs.Lmp, w.o, a, B, H, N, Lm, xprec, s, m->cfg.dim_head));
-      NSCHK(update_then_norm(ly.cout, w.o, a, nullptr, true, prec, nullptr, layer_cond(l, m->nnorm - 1), xn_ff));
-    }
-    // feedforward: Linear -> GEGLU -> causal conv k3 -> Linear (NS2:1009-1025); precision 6: the whole branch on dense IEEE-half planes
-    GemmArgs ffin = product(ly.ffin, xn_ff, dp, M), conv = product(ly.conv, w.ffh_conv, fpc, M);
-    set_geglu(ffin, w.ffh_conv.hi, w.ffh_conv.lo, fpc, fp); ffin.bias = ly.b_ffin; ffin.out_fmt = w.ffh_conv.fmt;
-    PROF(PC_GEMM_GEGLU, run_gemm(ffin, ff_prec, s));
-    set_conv(conv, ly.conv, 3, 1, N);
-    set_out_planes(conv, EPI_SPLIT, ffc_ff.hi, ffc_ff.lo, fp); conv.bias = ly.b_conv; conv.out_fmt = ffc_ff.fmt;
-    PROF(PC_GEMM_FFCONV, run_gemm(conv, conv_prec, s));
-    // FF-out + residual, then the next layer's self-attention norm -- or to_pred's RMSNorm (learned gamma, NS2:781-784) after the last
-    NSCHK(update_then_norm(ly.ffout, ffc_ff, fp, ly.b_ffout, true, ff_prec, last ? m->g_pred : nullptr, last ? nullptr : layer_cond(l + 1, 0), w.xn));
-    snprintf(name, sizeof name, "layer%d", l);
-    NSCHK(tap_f32(m, name, w.xres, (int64_t)M * dim, s));
+  const int dim = m->dim, a = m->a, f = m->f, L = m->L, S = m->S;
+  const bool cond = cfg->condition_on_prompt != 0;
+  shape(&m->w_init, pc, dim, dim, 3); m->b_init = fakef;
+  m->w_wn.resize(S); m->b_wn_conv.assign(S, fakef); m->b_wn_res.assign(S, fakef);
+  for (PackedW& W : m->w_wn) {
+    shape(&W, pc, dim, m->dp, 4); W.kt_per_tap = m->dp / 32;
+    if (hybrid_plan(cfg->precision) && (m->dp % 128) == 0 && (dim % 256) == 0 && W.fmt == FMT_H8) { W.tw1 = fake; W.tw2 = fake; }
   }
-  // to_pred: Linear on the normed stream (NS2:781-784)
-  GemmArgs pred = product(m->w_pred, w.xn, dp, M);
-  pred.out_f = out; pred.ldo_f = dim;
-  PROF(PC_GEMM_F32, run_gemm(pred, prec, s));
+  shape(&m->w_skip, pc, dim, L * m->dp, 1); m->b_skip = fakef;
+  shape(&m->w_final, pc, dim, dim, 1); m->b_final = fakef;
+  shape(&m->w_pred, pc, dim, dim, 1); m->g_pred = fakef;
+  m->layers.resize(cfg->depth);
+  for (ns2_model::Layer& ly : m->layers) {
+    shape(&ly.qkv, pc, 3 * a, dim, 1); shape(&ly.out, pc, dim, a, 1);
+    if (cond) { shape(&ly.cq, pc, a, dim, 1); shape(&ly.cout, pc, dim, a, 1); }
+    shape(&ly.ffin, pc_ff, 2 * rup(f, 32), dim, 1); ly.b_ffin = fakef;
+    shape(&ly.conv, pc_conv, f, f, 3); ly.b_conv = fakef;
+    if (pc_conv.fmt == FMT_F16) ly.conv.t3 = fake;
+    shape(&ly.ffout, pc_ff, dim, f, 1); ly.b_ffout = fakef;
+  }
+  Work w;
+  carve_work(m, &w, fake, 0, B, N, 0, 0);
+  CondState cs;
+  if (cond) carve_cond(m, &cs, fake, 0, B, N, N);
+  SplitKScope sk_scope(w.sk_ws);
+  const StepArgs st{fakef, fakef, w.condall, m->Jtot, N, N};
+  std::vector<Launch> whole, c0, c1;
+  Sink list{&whole, nullptr, nullptr, NS2_OK};
+  describe_rows(m, w, cond ? &cs : nullptr, st, 0, B, &list);
+  *chains = chains_by_rule(m, w, cond ? &cs : nullptr, st, B, &whole, &c0, &c1);
   return NS2_OK;
 }
 
