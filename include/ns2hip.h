@@ -592,6 +592,49 @@ int64_t ns2_row_dot_relu_bwd_workspace_bytes(int64_t M, int K);
 int ns2_row_dot_relu_bwd(const float* dout, const float* out, const float* h, int64_t ldh, const float* w, int64_t M, int K, float* dh,
                          int64_t lddh, float* dw_db, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- training of the Aligner (aligner.py; the only route that hands it a gradient is the forward-sum / bin loss of NS2:1587-1602) ----
+ * Exact arithmetic, fixed summation orders, no atomics: two runs give the same bits.  Lengths are int32 [B] on the device, clamped to
+ * [0, size]; nothing here reads device data on the host.  Limits: n <= 1024, T <= 8192, C <= 256. */
+/* ReLU between AlignerNet's convolutions (aligner.py:30-51) on the kept fp32 pre-activation x [M, ldx], C columns, and its backward
+ * dx = dy where x > 0.  Leading dimensions multiples of 4, 16-byte aligned pointers (as ns2_silu_fwd / ns2_silu_bwd). */
+int ns2_relu_fwd(const float* x, int64_t ldx, int64_t M, int C, float* out, int64_t ldo, void* stream);
+int ns2_relu_bwd(const float* dy, int64_t lddy, const float* x, int64_t ldx, int64_t M, int C, float* dx, int64_t lddx, void* stream);
+/* backward of ns2_align_attn (aligner.py:72-90: cdist, masked fill, softmax).  queries [B * T, C], keys [B * n, C], aln_log
+ * [B, 1, T, n] and aln_soft [B, n, T] as ns2_align_attn wrote them, g_log [B, 1, T, n] and g_soft [B, n, T] the gradients of the two
+ * outputs (either may be null).  With G = g_log + soft (g_soft - sum_i soft g_soft) on the live cells (i < text_lens[b]) and
+ * w = G / dist, w = 0 where the cell is masked or dist == 0 (torch.cdist's convention: never NaN or inf):
+ *   dq [B * T, C]: dq_t = sum_i w (q_t - k_i), phonemes in ascending order;
+ *   dk [B * n, C]: dk_i = sum_t w (k_i - q_t), per slice of 256 frames in ascending order, the slices through the fixed-order
+ *   slice reducer (ns2_reduce_slices' kernel).  The DIRECT form is summed (rowsum(w) q - w K cancels where q ~ k).
+ * workspace = ns2_align_attn_bwd_workspace_bytes bytes: w [B, T, n] fp32 + ceil(T / 256) slots of [B, n, C] fp32; 16-byte aligned. */
+int64_t ns2_align_attn_bwd_workspace_bytes(int B, int T, int n, int C);
+int ns2_align_attn_bwd(const float* queries, const float* keys, const float* aln_log, const float* aln_soft, const float* g_log,
+                       const float* g_soft, const int* text_lens, int B, int T, int n, int C, float* dq, float* dk, void* workspace,
+                       int64_t workspace_bytes, void* stream);
+/* ForwardSumLoss and BinLoss (aligner.py:132-167, 169-183) on aln_log [B, 1, T, n]; each loss is requested by a non-null output
+ * pointer (a device scalar), both share the row statistics.
+ * Forward-sum: per frame t < mel_lens[b] the log-softmax over [blank_logprob | aln_log[t, 0 .. L - 1]], L = text_lens[b] (columns
+ * > L of the n + 1 wide row are excluded); CTC with blank 0, targets 1 .. L, S = 2 L + 1 states, every skip between labels allowed
+ * (they are distinct); zero_infinity (an infeasible utterance gives loss 0, gradient 0); fs_loss = mean_b(nll_b / max(L_b, 1)).
+ * One workgroup per utterance runs the alpha recursion over the frames, the states spread over its lanes, and keeps alpha
+ * [B, T, 2 n + 1] in the workspace.  Arithmetic: fp64 on probabilities scaled per frame by a power of two (the exponent of the frame
+ * before's maximum: exact, and the sum of the exponents gives nll) -- an fp32 log-space recursion leaves the gradient 300 .. 10000 x 2^-24
+ * of its largest element off (so does torch's fp32 ctc_loss); emissions below e^-700 count as e^-700.
+ * Bin: bin_loss = sum(hard log_softmax(aln_log over the columns <= L)) / B, hard [B, n, T] the 0/1 path (column L is kept, as upstream:
+ * it holds the aligner's -FLT_MAX).
+ * ns2_align_losses_bwd (same aln_log, hard, lengths, blank_logprob and the workspace the forward filled): d_log [B, 1, T, n] =
+ * g_fs (softmax - occupancy) / (max(L, 1) B) on the live cells of the frames t < mel_len (beta recursion, the occupancies of a frame
+ * normalised to sum 1 over its states; the blank column's share is dropped) + g_bin (hard - softmax sum_i hard) / B on the columns <= L; exactly 0 elsewhere.  g_fs, g_bin: device scalars, the
+ * gradients of the two losses (null = that loss takes no part).
+ * workspace = ns2_align_losses_workspace_bytes bytes: 4 floats per frame, B doubles, 2 B T (2 n + 1) floats (alpha, and the backward's
+ * alpha + beta: the forward's part is only read, so a backward may be repeated). */
+int64_t ns2_align_losses_workspace_bytes(int B, int T, int n);
+int ns2_align_losses_fwd(const float* aln_log, const float* hard, const int* text_lens, const int* mel_lens, int B, int T, int n,
+                         float blank_logprob, float* fs_loss, float* bin_loss, void* workspace, int64_t workspace_bytes, void* stream);
+int ns2_align_losses_bwd(const float* aln_log, const float* hard, const int* text_lens, const int* mel_lens, const float* g_fs,
+                         const float* g_bin, int B, int T, int n, float blank_logprob, float* d_log, void* workspace,
+                         int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -185,6 +185,14 @@ SIGNATURES = {
     "ns2_groupnorm_silu_bwd": (I, [P, L, P, I, I, I, I, P, P, F, P, L, P, P, P, L, P]),
     "ns2_row_dot_relu_bwd_workspace_bytes": (L, [L, I]),
     "ns2_row_dot_relu_bwd": (I, [P, P, P, L, P, L, I, P, L, P, P, L, P]),
+    # ---- training of the Aligner
+    "ns2_relu_fwd": (I, [P, L, L, I, P, L, P]),
+    "ns2_relu_bwd": (I, [P, L, P, L, L, I, P, L, P]),
+    "ns2_align_attn_bwd_workspace_bytes": (L, [I, I, I, I]),
+    "ns2_align_attn_bwd": (I, [P, P, P, P, P, P, P, I, I, I, I, P, P, P, L, P]),
+    "ns2_align_losses_workspace_bytes": (L, [I, I, I]),
+    "ns2_align_losses_fwd": (I, [P, P, P, P, I, I, I, F, P, P, P, L, P]),
+    "ns2_align_losses_bwd": (I, [P, P, P, P, P, P, I, I, I, F, P, P, L, P]),
 }
 
 NS2_UNAVAILABLE = 1          # include/ns2hip.h: "this fast path does not apply here" (not an error)

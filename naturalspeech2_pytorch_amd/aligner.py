@@ -6,8 +6,12 @@ the shifted-row GEMMs (conv_taps = 3, pad_left = 1, and plain 1x1 products) with
 kernel for the distances + mask + softmax and the monotonic alignment search `ns2_maximum_path`.  Otherwise the PyTorch
 composite of autograd_path.py runs; its alignment search is HIP on CUDA and a PyTorch loop on the CPU.  The HIP path takes
 prefix masks (what `create_mask` builds): masks passed to the public module are reduced to lengths once (one host read) and
-any other mask goes to the composite.  The losses are PyTorch (CTC is torch's).  Same constructor keywords, forward
-signatures, outputs and state_dict keys as the reference.
+any other mask goes to the composite.  Same constructor keywords, forward signatures, outputs and state_dict keys as the reference.
+
+Training.  By default (`train_backend="composite"`, `backend="composite"` of the two losses) the Aligner under autograd is the PyTorch
+composite and the losses are PyTorch (CTC is torch's).  With `train_backend="hip"` on the GPU `training.aligner_forward_train` runs forward
+and backward on the HIP kernels, and `ForwardSumLoss` / `BinLoss` with `backend="hip"` are autograd Functions over
+ns2_align_losses_fwd / _bwd: int lengths on the device, no host read anywhere.
 """
 import torch
 from torch import nn
@@ -73,15 +77,71 @@ class AlignerNet(nn.Module):
         return aligner_net_autograd(self, queries, keys, mask)
 
 
-class ForwardSumLoss(nn.Module):
-    """aligner.py:132-167: CTC over the alignment log-probabilities, blank = a constant column in front"""
+TRAIN_BACKENDS = ("composite", "hip")
 
-    def __init__(self, blank_logprob=-1):
+
+def _i32(lens, device):
+    return lens.to(device=device, dtype=torch.int32).contiguous()
+
+
+class _ForwardSumFn(torch.autograd.Function):
+    """the forward-sum loss on ns2_align_losses_fwd / _bwd: aln_log [b, 1, T, n], int32 lengths on the device -> a 0-dim loss"""
+
+    @staticmethod
+    def forward(ctx, logp, key_lens, query_lens, blank):
+        from .training import backend
+        ctx.bk = bk = backend()
+        x = logp.detach().float().contiguous()
+        loss, _, ws = bk.align_losses_fwd(x, key_lens, query_lens, blank, want_fs=True)
+        ctx.save_for_backward(x, key_lens, query_lens, ws)
+        ctx.blank, ctx.dtype = blank, logp.dtype
+        return loss.to(logp.dtype)
+
+    @staticmethod
+    def backward(ctx, g):
+        x, key_lens, query_lens, ws = ctx.saved_tensors
+        d = ctx.bk.align_losses_bwd(x, key_lens, query_lens, ctx.blank, ws, g_fs=g.detach().float().reshape(1).contiguous())
+        return d.to(ctx.dtype), None, None, None
+
+
+class _BinFn(torch.autograd.Function):
+    """the bin loss on the same kernels: hard [b, n, T] 0/1, aln_log [b, 1, T, n] -> a 0-dim loss (no gradient for `hard`: it is a path)"""
+
+    @staticmethod
+    def forward(ctx, hard, logp, key_lens):
+        from .training import backend
+        ctx.bk = bk = backend()
+        x, h = logp.detach().float().contiguous(), hard.detach().float().contiguous()
+        _, loss, ws = bk.align_losses_fwd(x, key_lens, None, 0., hard=h, want_fs=False, want_bin=True)
+        ctx.save_for_backward(x, h, key_lens, ws)
+        ctx.dtype = logp.dtype
+        return loss.to(logp.dtype)
+
+    @staticmethod
+    def backward(ctx, g):
+        x, h, key_lens, ws = ctx.saved_tensors
+        d = ctx.bk.align_losses_bwd(x, key_lens, None, 0., ws, hard=h, g_bin=g.detach().float().reshape(1).contiguous())
+        return None, d.to(ctx.dtype), None
+
+
+def _hip_loss_ok(logp):
+    return logp.is_cuda and logp.shape[-1] <= 1024 and logp.shape[-2] <= 8192
+
+
+class ForwardSumLoss(nn.Module):
+    """aligner.py:132-167: CTC over the alignment log-probabilities, blank = a constant column in front.  `backend="hip"` (not in the
+    reference): CUDA tensors take the kernels of csrc/aligner.hip (no host read of the lengths); CPU tensors always take the composite"""
+
+    def __init__(self, blank_logprob=-1, backend="composite"):
         super().__init__()
-        self.blank_logprob = blank_logprob
+        assert backend in TRAIN_BACKENDS, f"backend must be one of {TRAIN_BACKENDS}"
+        self.blank_logprob, self.backend = blank_logprob, backend
         self.ctc_loss = nn.CTCLoss(blank=0, zero_infinity=True)
 
     def forward(self, attn_logprob, key_lens, query_lens):
+        if self.backend == "hip" and _hip_loss_ok(attn_logprob):
+            dev = attn_logprob.device
+            return _ForwardSumFn.apply(attn_logprob, _i32(key_lens, dev), _i32(query_lens, dev), float(self.blank_logprob))
         n = attn_logprob.shape[-1]
         lp = F.pad(attn_logprob[:, 0].permute(1, 0, 2), (1, 0), value=self.blank_logprob)      # [T, b, n + 1]
         cols = torch.arange(n + 1, device=lp.device)
@@ -91,9 +151,16 @@ class ForwardSumLoss(nn.Module):
 
 
 class BinLoss(nn.Module):
-    """aligner.py:169-183 (the reference fills the caller's attn_logprob in place; this one works on a copy)"""
+    """aligner.py:169-183 (the reference fills the caller's attn_logprob in place; this one works on a copy).  `backend`: as ForwardSumLoss"""
+
+    def __init__(self, backend="composite"):
+        super().__init__()
+        assert backend in TRAIN_BACKENDS, f"backend must be one of {TRAIN_BACKENDS}"
+        self.backend = backend
 
     def forward(self, attn_hard, attn_logprob, key_lens):
+        if self.backend == "hip" and _hip_loss_ok(attn_logprob):
+            return _BinFn.apply(attn_hard, attn_logprob, _i32(key_lens, attn_logprob.device))
         b, n = attn_logprob.shape[0], attn_logprob.shape[-1]
         lp = attn_logprob[:, 0].permute(1, 0, 2)                                                # [T, b, n]
         cols = torch.arange(n, device=lp.device)
@@ -105,9 +172,11 @@ class Aligner(nn.Module):
     """aligner.py:185-229.  forward(x [b, n, dim_hidden] phoneme encodings, x_mask [b, 1, n], y [b, dim_in, T] mel,
     y_mask [b, 1, T]) -> (aln_hard int32 [b, n], aln_soft [b, n, T], aln_log [b, 1, T, n], aln_mask [b, n, T])"""
 
-    def __init__(self, dim_in, dim_hidden, attn_channels=80, temperature=0.0005, precision="exact"):
+    def __init__(self, dim_in, dim_hidden, attn_channels=80, temperature=0.0005, precision="exact", train_backend="composite"):
         super().__init__()
         assert precision in _PRECISIONS, f"precision must be one of {sorted(_PRECISIONS)}"
+        assert train_backend in TRAIN_BACKENDS, f"train_backend must be one of {TRAIN_BACKENDS}"
+        self.train_backend = train_backend  # not in the reference: "hip" = forward and backward on the HIP kernels (training/aligner_pass.py)
         self.dim_in, self.dim_hidden, self.attn_channels, self.temperature = dim_in, dim_hidden, attn_channels, temperature
         self.precision = precision          # not in the reference: arithmetic of the HIP convolutions
         self.aligner = AlignerNet(dim_in=dim_in, dim_hidden=dim_hidden, attn_channels=attn_channels, temperature=temperature)
@@ -118,7 +187,27 @@ class Aligner(nn.Module):
             tl, ml = prefix_lengths(x_mask), prefix_lengths(y_mask)
             if tl is not None and ml is not None:
                 return self.forward_lengths(x, tl, y, ml)
+        elif self.train_backend == "hip" and x.is_cuda:            # (on the GPU this branch is entered under autograd only)
+            if self.train_ready(x, y):
+                tl, ml = prefix_lengths(x_mask), prefix_lengths(y_mask)
+                if tl is not None and ml is not None:
+                    return self.forward_lengths_train(x, tl, y, ml)
         return self._forward_composite(x, x_mask, y, y_mask)
+
+    def train_ready(self, x, y):
+        """does the HIP training pass take these inputs (`train_backend="hip"`, CUDA, nothing `aligner_unsupported_reason` names)"""
+        if self.train_backend != "hip" or not x.is_cuda:
+            return False
+        from . import training
+        return training.available(x.device) and training.aligner_unsupported_reason(self, x, y) is None
+
+    def forward_lengths_train(self, x, text_lens, y, mel_lens):
+        """the differentiable HIP path with int lengths [b] on the device in place of the masks (no host read).  -> as forward"""
+        if x.shape[-1] != self.dim_hidden or y.shape[1] != self.dim_in or x.shape[0] != y.shape[0]:
+            raise ValueError(f"expected phoneme encodings [b, n, {self.dim_hidden}] and mel [b, {self.dim_in}, T]; got "
+                             f"{tuple(x.shape)} and {tuple(y.shape)}")
+        from . import training
+        return training.aligner_forward_train(self, x, text_lens, y, mel_lens)
 
     def _forward_composite(self, x, x_mask, y, y_mask):
         soft, logp = self.aligner(y, x.transpose(1, 2), x_mask)

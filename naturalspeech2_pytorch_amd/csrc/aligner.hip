@@ -383,6 +383,554 @@ __global__ __launch_bounds__(64) void ex_dtable_kernel(const float* d_enc, const
   if (c < D) d_table[(long)bin * D + c] = s;
 }
 
+// ---------------------------------------------------------------- training: backward of the distances + softmax (aligner.py:72-90)
+// With G = g_log + soft (g_soft - sum_i soft g_soft) on the live cells (i < text_len) and w = G / dist (0 where masked or dist == 0,
+// torch.cdist's convention):  dq_t = sum_i w (q_t - k_i),  dk_i = sum_t w (k_i - q_t) -- the DIRECT form: rowsum(w) q - w K cancels
+// where q ~ k.  Three kernels: w [B, T, n] once; dq sums over the phonemes in ascending order; dk sums over fixed slices of
+// AB_SLICE frames into slots that the slice reducer (backward.hip) adds in a fixed order.  No atomics: two runs give the same bits.
+constexpr int AB_SLICE = 256;             // frames per dk slot
+
+// grid (ceil(T / AA_TQ), B), 256 threads
+__global__ __launch_bounds__(256) void align_w_kernel(const float* aln_log, const float* aln_soft, const float* g_log, const float* g_soft,
+                                                      const int* text_lens, int T, int n, float* w) {
+  __shared__ float part[16][AA_TQ + 1];
+  __shared__ float srow[AA_TQ];
+  const int b = blockIdx.y, t0 = blockIdx.x * AA_TQ, t = threadIdx.x;
+  const int tl = min(max(text_lens[b], 0), n);
+  const int nq = min(AA_TQ, T - t0);
+  {                                                   // sum_i soft g_soft per frame: 16 phoneme groups, added in group order
+    const int f = t & (AA_TQ - 1), pg = t >> 4;
+    float s = 0.f;
+    if (g_soft && f < nq)
+      for (int ph = pg; ph < tl; ph += 16) {
+        const long o = ((long)b * n + ph) * T + t0 + f;
+        s += aln_soft[o] * g_soft[o];
+      }
+    part[pg][f] = s;
+  }
+  __syncthreads();
+  if (t < AA_TQ) {
+    float s = part[0][t];
+#pragma unroll
+    for (int g = 1; g < 16; ++g) s += part[g][t];
+    srow[t] = s;
+  }
+  __syncthreads();
+  const int wv = t >> 6, lane = t & 63;
+  for (int f = wv; f < nq; f += 4) {
+    const long row = ((long)b * T + t0 + f) * n;
+    const float sr = srow[f];
+    for (int i = lane; i < n; i += 64) {
+      float r = 0.f;
+      if (i < tl) {
+        const float d = aln_log[row + i];
+        float G = g_log ? g_log[row + i] : 0.f;
+        if (g_soft) {
+          const long o = ((long)b * n + i) * T + t0 + f;
+          G += aln_soft[o] * (g_soft[o] - sr);
+        }
+        r = d > 0.f ? G / d : 0.f;
+      }
+      w[row + i] = r;
+    }
+  }
+}
+
+// grid (ceil(T / AA_TQ), B), 256 threads: thread (f = t / 16, c = t % 16 + 16 e) owns dq[t0 + f, c]; dynamic LDS:
+// q [AA_TQ][C] | k [AA_TK][C + 1] | w [AA_TQ][AA_TK]
+template <int NJ>
+__global__ __launch_bounds__(256) void align_dq_kernel(const float* q, const float* k, const float* w, const int* text_lens, int T, int n,
+                                                       int C, float* dq) {
+  extern __shared__ float sm[];
+  float* qs = sm;
+  float* ks = qs + AA_TQ * C;
+  float* ws = ks + AA_TK * (C + 1);
+  const int b = blockIdx.y, t0 = blockIdx.x * AA_TQ, t = threadIdx.x;
+  const int tl = min(max(text_lens[b], 0), n);
+  const int nq = min(AA_TQ, T - t0);
+  for (int i = t; i < AA_TQ * C; i += 256) {
+    const int f = i / C, c = i % C;
+    qs[i] = f < nq ? q[((long)b * T + t0 + f) * C + c] : 0.f;
+  }
+  const int f = t >> 4, c0 = t & 15;
+  int cc[NJ];
+  float acc[NJ];
+#pragma unroll
+  for (int e = 0; e < NJ; ++e) { cc[e] = min(c0 + 16 * e, C - 1); acc[e] = 0.f; }
+  for (int k0 = 0; k0 < tl; k0 += AA_TK) {              // tl is the block's own: every thread runs the same trips
+    __syncthreads();
+    for (int i = t; i < AA_TK * C; i += 256) {
+      const int j = i / C, c = i % C;
+      ks[j * (C + 1) + c] = k0 + j < n ? k[((long)b * n + k0 + j) * C + c] : 0.f;
+    }
+    for (int i = t; i < AA_TQ * AA_TK; i += 256) {
+      const int ff = i / AA_TK, j = i % AA_TK;
+      ws[i] = (ff < nq && k0 + j < n) ? w[((long)b * T + t0 + ff) * n + k0 + j] : 0.f;
+    }
+    __syncthreads();
+    const int jn = min(AA_TK, tl - k0);
+    for (int j = 0; j < jn; ++j) {
+      const float wv = ws[f * AA_TK + j];
+#pragma unroll
+      for (int e = 0; e < NJ; ++e) acc[e] += wv * (qs[f * C + cc[e]] - ks[j * (C + 1) + cc[e]]);
+    }
+  }
+  if (f < nq) {
+#pragma unroll
+    for (int e = 0; e < NJ; ++e)
+      if (c0 + 16 * e < C) dq[((long)b * T + t0 + f) * C + c0 + 16 * e] = acc[e];
+  }
+}
+
+// grid (ceil(n / 16), slices, B), 256 threads: thread (p = t / 16, c = t % 16 + 16 e) owns slot[slice][i0 + p, c]; dynamic LDS:
+// k [16][C] | q [AA_TK][C + 1] | w [AA_TK][16]
+template <int NJ>
+__global__ __launch_bounds__(256) void align_dk_kernel(const float* q, const float* k, const float* w, const int* text_lens, int T, int n,
+                                                       int C, float* partial) {
+  extern __shared__ float sm[];
+  float* ks = sm;
+  float* qs = ks + 16 * C;
+  float* ws = qs + AA_TK * (C + 1);
+  const int b = blockIdx.z, sl = blockIdx.y, S = gridDim.y, i0 = blockIdx.x * 16, t = threadIdx.x;
+  const int tl = min(max(text_lens[b], 0), n);
+  const int p = t >> 4, c0 = t & 15;
+  float* out = partial + ((long)b * S + sl) * n * C;
+  if (i0 >= tl) {                                     // a tile of masked phonemes (the whole block leaves): exact zeros
+    if (i0 + p < n)
+      for (int c = c0; c < C; c += 16) out[(long)(i0 + p) * C + c] = 0.f;
+    return;
+  }
+  const int ta = sl * AB_SLICE, tb = min(T, ta + AB_SLICE);
+  for (int i = t; i < 16 * C; i += 256) {
+    const int pp = i / C, c = i % C;
+    ks[i] = i0 + pp < n ? k[((long)b * n + i0 + pp) * C + c] : 0.f;
+  }
+  int cc[NJ];
+  float acc[NJ];
+#pragma unroll
+  for (int e = 0; e < NJ; ++e) { cc[e] = min(c0 + 16 * e, C - 1); acc[e] = 0.f; }
+  for (int f0 = ta; f0 < tb; f0 += AA_TK) {
+    __syncthreads();
+    for (int i = t; i < AA_TK * C; i += 256) {
+      const int j = i / C, c = i % C;
+      qs[j * (C + 1) + c] = f0 + j < tb ? q[((long)b * T + f0 + j) * C + c] : 0.f;
+    }
+    for (int i = t; i < AA_TK * 16; i += 256) {
+      const int j = i >> 4, pp = i & 15;
+      ws[i] = (f0 + j < tb && i0 + pp < n) ? w[((long)b * T + f0 + j) * n + i0 + pp] : 0.f;
+    }
+    __syncthreads();
+    const int jn = min(AA_TK, tb - f0);
+    for (int j = 0; j < jn; ++j) {
+      const float wv = ws[j * 16 + p];
+#pragma unroll
+      for (int e = 0; e < NJ; ++e) acc[e] += wv * (ks[p * C + cc[e]] - qs[j * (C + 1) + cc[e]]);
+    }
+  }
+  if (i0 + p < n) {
+#pragma unroll
+    for (int e = 0; e < NJ; ++e)
+      if (c0 + 16 * e < C) out[(long)(i0 + p) * C + c0 + 16 * e] = acc[e];
+  }
+}
+
+template <int NJ>
+static hipError_t align_bwd_launch(const float* q, const float* k, const float* w, const int* tl, int B, int T, int n, int C, float* dq,
+                                   float* partial, int S, hipStream_t s) {
+  static DynLdsAttr aq, ak;
+  const size_t ldq = sizeof(float) * ((size_t)AA_TQ * C + (size_t)AA_TK * (C + 1) + (size_t)AA_TQ * AA_TK);
+  const size_t ldk = sizeof(float) * ((size_t)16 * C + (size_t)AA_TK * (C + 1) + (size_t)AA_TK * 16);
+  hipError_t e = aq.ensure(reinterpret_cast<const void*>(&align_dq_kernel<NJ>), (int)ldq);
+  if (e != hipSuccess) return e;
+  e = ak.ensure(reinterpret_cast<const void*>(&align_dk_kernel<NJ>), (int)ldk);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL((align_dq_kernel<NJ>), dim3((T + AA_TQ - 1) / AA_TQ, B), dim3(256), ldq, s, q, k, w, tl, T, n, C, dq);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL((align_dk_kernel<NJ>), dim3((n + 15) / 16, S, B), dim3(256), ldk, s, q, k, w, tl, T, n, C, partial);
+  return hipGetLastError();
+}
+
+static inline int64_t ab_w_bytes(int B, int T, int n) { return ((int64_t)B * T * n * 4 + 255) / 256 * 256; }
+
+int64_t align_attn_bwd_workspace_bytes(int B, int T, int n, int C) {
+  if (B <= 0 || T <= 0 || n <= 0 || C <= 0) return 0;
+  const int S = (T + AB_SLICE - 1) / AB_SLICE;
+  return ab_w_bytes(B, T, n) + (int64_t)B * S * n * C * 4;
+}
+
+hipError_t launch_align_attn_bwd(const float* q, const float* k, const float* aln_log, const float* aln_soft, const float* g_log,
+                                 const float* g_soft, const int* text_lens, int B, int T, int n, int C, float* dq, float* dk,
+                                 void* workspace, hipStream_t s) {
+  if (B <= 0 || B > 65535 || T <= 0 || T > 8192 || n <= 0 || n > 1024 || C <= 0 || C > 256) return hipErrorInvalidValue;
+  float* w = reinterpret_cast<float*>(workspace);
+  float* partial = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + ab_w_bytes(B, T, n));
+  const int S = (T + AB_SLICE - 1) / AB_SLICE;
+  hipLaunchKernelGGL(align_w_kernel, dim3((T + AA_TQ - 1) / AA_TQ, B), dim3(256), 0, s, aln_log, aln_soft, g_log, g_soft, text_lens, T, n, w);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  const int nj = (C + 15) / 16;
+  if (nj <= 2) e = align_bwd_launch<2>(q, k, w, text_lens, B, T, n, C, dq, partial, S, s);
+  else if (nj <= 3) e = align_bwd_launch<3>(q, k, w, text_lens, B, T, n, C, dq, partial, S, s);
+  else if (nj <= 5) e = align_bwd_launch<5>(q, k, w, text_lens, B, T, n, C, dq, partial, S, s);
+  else if (nj <= 8) e = align_bwd_launch<8>(q, k, w, text_lens, B, T, n, C, dq, partial, S, s);
+  else e = align_bwd_launch<16>(q, k, w, text_lens, B, T, n, C, dq, partial, S, s);
+  if (e != hipSuccess) return e;
+  return launch_reduce_slices(partial, B, S, (long)n * C, dk, 0, s);
+}
+
+// ---------------------------------------------------------------- training: forward-sum (CTC) and bin losses (aligner.py:132-183)
+// Forward-sum: per frame t < mel_len the log-softmax over [blank | aln_log[t, 0 .. L - 1]] (L = text_len; the padded row's columns
+// > L are excluded), CTC with blank 0 and the targets 1 .. L (distinct labels: a label state may always skip the blank before it),
+// S = 2 L + 1 states, zero_infinity, mean over the batch of nll / max(L, 1).  Bin: sum hard log_softmax(aln_log) over the columns
+// <= L (column L is kept, as upstream: it holds the aligner's -FLT_MAX), divided by B.
+// Workspace: stats [B T][4] fp32 = (-, lse of the bin row, sum_i hard, sum_i hard logp) | lse of the forward-sum row [B T] fp64 | nll [B]
+// fp64 | alpha [B][T][2 n + 1] fp64 | e [B][T][2 n + 1] fp64 (the backward's; the forward's part stays as it is, so a backward may be
+// repeated).  The recursions run one workgroup per utterance in log space, state s of lane l = l + 256 j, the previous column in LDS
+// (two buffers, one barrier per frame); every barrier is unconditional and mel_len is the workgroup's own trip count.
+// Arithmetic: the row statistics of the forward-sum rows, the recursions and the occupancies are fp64.  The gradient softmax -
+// occupancy cancels (a one-label utterance has both at 1 - 5e-5), and the states that carry mass sit ~10 below the frame's maximum, where
+// an fp32 recursion loses 1e-6 per frame: measured on the tests' inputs, fp32 left the gradient 300 .. 10000 x 2^-24 of its largest
+// element off, as torch's own fp32 ctc_loss does; fp64 leaves what the fp32 inputs and output allow.
+constexpr int AL_STATS = 4;
+static inline int64_t al_stats_floats(int B, int T) { return ((int64_t)B * T * AL_STATS + 63) / 64 * 64; }
+static inline int64_t al_lse_floats(int B, int T) { return ((int64_t)B * T + 31) / 32 * 64; }      // B T doubles
+static inline int64_t al_nll_floats(int B) { return ((int64_t)B + 31) / 32 * 64; }                 // B doubles
+
+int64_t align_losses_workspace_bytes(int B, int T, int n) {
+  if (B <= 0 || T <= 0 || n <= 0) return 0;
+  return 4 * (al_stats_floats(B, T) + al_lse_floats(B, T) + al_nll_floats(B) + 4 * (int64_t)B * T * (2 * n + 1));
+}
+
+NS2_DEVINL double wave_max_d(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+  return v;
+}
+NS2_DEVINL double wave_sum_d(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// grid (ceil(T / AA_TQ), B), 256 threads: one wave per frame, four frames each
+__global__ __launch_bounds__(256) void al_rowstat_kernel(const float* aln_log, const float* hard, const int* text_lens, int T, int n,
+                                                         float blank, float* stats, double* lse_fs) {
+  const int b = blockIdx.y, t0 = blockIdx.x * AA_TQ, wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int L = min(max(text_lens[b], 0), n), Lb = min(L + 1, n);
+  for (int f = wv; f < AA_TQ && t0 + f < T; f += 4) {
+    const int t = t0 + f;
+    const float* x = aln_log + ((long)b * T + t) * n;
+    float m = blank, m2 = -FLT_MAX;
+    for (int i = lane; i < Lb; i += 64) {
+      const float v = x[i];
+      if (i < L) m = fmaxf(m, v);
+      m2 = fmaxf(m2, v);
+    }
+    m = wave_max(m);
+    m2 = wave_max(m2);
+    double s = 0.0;
+    float s2 = 0.f;
+    for (int i = lane; i < Lb; i += 64) {
+      const float v = x[i];
+      if (i < L && lse_fs) s += exp((double)v - (double)m);
+      s2 += expf(v - m2);
+    }
+    s = wave_sum_d(s) + exp((double)blank - (double)m);
+    s2 = wave_sum(s2);
+    const float ls2 = logf(s2);
+    float hs = 0.f, br = 0.f;
+    if (hard)
+      for (int i = lane; i < Lb; i += 64) {
+        const float h = hard[((long)b * n + i) * T + t];
+        hs += h;
+        br += h * ((x[i] - m2) - ls2);
+      }
+    hs = wave_sum(hs);
+    br = wave_sum(br);
+    if (lane == 0) {
+      float* st = stats + ((long)b * T + t) * AL_STATS;
+      st[0] = 0.f;
+      if (lse_fs) lse_fs[(long)b * T + t] = (double)m + log(s);
+      st[1] = m2 + ls2;
+      st[2] = hs;
+      st[3] = br;
+    }
+  }
+}
+
+// The recursions run on SCALED PROBABILITIES, not logs: A_t(s) = (A_{t-1}(s) + A_{t-1}(s - 1) [+ A_{t-1}(s - 2) for a label state]) y_t(s) 2^-k,
+// y_t(s) = exp(max(lp_t(s), -700)), k = the binary exponent of the previous frame's maximum (every wave leaves its maximum in LDS before
+// that frame's barrier).  A power of two scales exactly, costs one ldexp and keeps the frame's maximum in [0.5, 1) y whatever the length;
+// the sums add positive numbers only.  Per state and frame that is one exp off the LDS dependency chain where the log-space form has three
+// exps and a log on it (measured: 1.7 us per frame at 3 states per lane in log space).  The clamp at -700 keeps a state of a feasible path
+// above the smallest normal double.
+NS2_DEVINL double al_emit(float x, double lse) { return exp(fmax((double)x - lse, -700.0)); }
+
+// grid (B), 256 threads: A[b, t, s] for t < mel_len and nll[b] = -(K ln 2 + log(A[S - 1] + A[S - 2])) at the last frame, K = the sum of the
+// exponents taken out (an integer: exact)
+template <int NSJ>
+__global__ __launch_bounds__(256) void al_alpha_kernel(const float* aln_log, const int* text_lens, const int* mel_lens, int T, int n,
+                                                       float blank, const double* lse_fs, double* alpha, double* nll) {
+  constexpr int SP = 256 * NSJ + 2;
+  __shared__ double cs[2 * SP];
+  __shared__ double wm[2][4];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int L = min(max(text_lens[b], 0), n), ml = min(max(mel_lens[b], 0), T), S = 2 * L + 1;
+  if (tid < 2) { cs[tid] = 0.0; cs[SP + tid] = 0.0; }
+  const float* xb = aln_log + (long)b * T * n;
+  const double* sb = lse_fs + (long)b * T;
+  double* ab = alpha + (long)b * T * (2 * n + 1);
+  float xv[NSJ], xn[NSJ];
+  double l = 0.0, ln = 0.0;
+#pragma unroll
+  for (int j = 0; j < NSJ; ++j) xn[j] = 0.f;
+  auto loadx = [&](int t, float (&dst)[NSJ], double& lse) {
+    lse = sb[t];
+#pragma unroll
+    for (int j = 0; j < NSJ; ++j) {
+      const int s = tid + 256 * j;
+      dst[j] = (s < S && (s & 1)) ? xb[(long)t * n + (s >> 1)] : blank;
+    }
+  };
+  if (ml > 0) loadx(0, xv, l);
+  long K = 0;
+  __syncthreads();
+  for (int t = 0; t < ml; ++t) {                       // ml is the workgroup's own: the same trips for every thread
+    if (t + 1 < ml) loadx(t + 1, xn, ln);              // the next frame's loads fly during this frame's recursion
+    double* cur = cs + ((t & 1) ? SP : 0) + 2;
+    const double* prev = cs + ((t & 1) ? 0 : SP) + 2;
+    double y[NSJ];
+#pragma unroll
+    for (int j = 0; j < NSJ; ++j) y[j] = al_emit(xv[j], l);
+    int k = 0;
+    if (t > 0) {
+      const double* w = wm[(t & 1) ^ 1];
+      frexp(fmax(fmax(w[0], w[1]), fmax(w[2], w[3])), &k);
+      K += k;
+    }
+    double mx = 0.0;
+#pragma unroll
+    for (int j = 0; j < NSJ; ++j) {
+      const int s = tid + 256 * j;
+      double a;
+      if (t == 0) a = s < 2 ? y[j] : 0.0;
+      else a = ldexp((prev[s] + prev[s - 1] + ((s & 1) ? prev[s - 2] : 0.0)) * y[j], -k);
+      if (s >= S) a = 0.0;
+      cur[s] = a;
+      mx = fmax(mx, a);
+      if (s < S) ab[(long)t * (2 * n + 1) + s] = a;
+    }
+    mx = wave_max_d(mx);
+    if ((tid & 63) == 0) wm[t & 1][tid >> 6] = mx;
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < NSJ; ++j) xv[j] = xn[j];
+    l = ln;
+  }
+  if (tid == 0) {
+    double r = L == 0 ? 0.0 : (double)__builtin_inff();  // no frame: feasible only for the empty target
+    if (ml > 0) {
+      const double* last = cs + (((ml - 1) & 1) ? SP : 0) + 2;
+      r = -((double)K * 0.69314718055994530942 + log(last[S - 1] + last[S - 2]));     // last[-1] is the zero pad when S == 1; log(0) = -inf: infeasible
+    }
+    nll[b] = r;
+  }
+}
+
+// grid (1), 256 threads: fs_loss = mean_b (nll_b / max(L_b, 1), 0 where infinite), bin_loss = sum of the rows' terms / B; fixed order
+__global__ __launch_bounds__(256) void al_finish_kernel(const float* stats, const double* nll, const int* text_lens, int B, int T, int n,
+                                                        float* fs_loss, float* bin_loss) {
+  __shared__ double red[256];
+  const int tid = threadIdx.x;
+  for (int which = 0; which < 2; ++which) {
+    float* out = which ? bin_loss : fs_loss;           // (uniform: the barriers below are reached by every thread or by none)
+    if (!out) continue;
+    double s = 0.0;
+    if (which == 0) {
+      for (int b = tid; b < B; b += 256) {
+        const double v = nll[b];
+        const int L = min(max(text_lens[b], 0), n);
+        if (v < (double)__builtin_inff()) s += v / (double)max(L, 1);
+      }
+    } else {
+      for (long r = tid; r < (long)B * T; r += 256) s += (double)stats[r * AL_STATS + 3];
+    }
+    red[tid] = s;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+      if (tid < o) red[tid] += red[tid + o];
+      __syncthreads();
+    }
+    if (tid == 0) *out = (float)(red[0] / (double)B);
+    __syncthreads();
+  }
+}
+
+// grid (ceil(T / AA_TQ), B), 256 threads: d_log <- the bin term g_bin (hard - softmax sum_i hard) / B on the columns <= L, 0 elsewhere
+__global__ __launch_bounds__(256) void al_bin_bwd_kernel(const float* aln_log, const float* hard, const int* text_lens, const float* g_bin,
+                                                         int B, int T, int n, const float* stats, float* d_log) {
+  const int b = blockIdx.y, t0 = blockIdx.x * AA_TQ, wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int L = min(max(text_lens[b], 0), n), Lb = (g_bin && hard) ? min(L + 1, n) : 0;
+  const float sc = Lb ? g_bin[0] / (float)B : 0.f;
+  for (int f = wv; f < AA_TQ && t0 + f < T; f += 4) {
+    const int t = t0 + f;
+    const long row = ((long)b * T + t) * n;
+    const float lse = stats[((long)b * T + t) * AL_STATS + 1], hs = stats[((long)b * T + t) * AL_STATS + 2];
+    for (int i = lane; i < n; i += 64) {
+      float v = 0.f;
+      if (i < Lb) v = sc * (hard[((long)b * n + i) * T + t] - expf(aln_log[row + i] - lse) * hs);
+      d_log[row + i] = v;
+    }
+  }
+}
+
+// grid (B), 256 threads: the backward recursion over t = mel_len - 1 .. 0 in the same scaling: Bt_t(s) = the probability of the rest of the
+// target from state s at frame t, the frame's own emission left out: Bt_t(s) = (W_{t+1}(s) + W_{t+1}(s + 1) [+ W_{t+1}(s + 2)]) 2^-k with
+// W_t(s) = y_t(s) Bt_t(s) in LDS.  e[b, t, s] = A_t(s) Bt_t(s), proportional to the occupancy, goes to the workspace's second half.
+// Nothing for an infeasible utterance (zero trips for the whole workgroup).
+template <int NSJ>
+__global__ __launch_bounds__(256) void al_beta_kernel(const float* aln_log, const int* text_lens, const int* mel_lens, int T, int n,
+                                                      float blank, const double* lse_fs, const double* alpha, const double* nll, double* e) {
+  constexpr int SP = 256 * NSJ + 2;
+  __shared__ double cs[2 * SP];
+  __shared__ double wm[2][4];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int L = min(max(text_lens[b], 0), n), S = 2 * L + 1;
+  const int ml = nll[b] < (double)__builtin_inff() ? min(max(mel_lens[b], 0), T) : 0;
+  if (tid < 2) { cs[SP - 2 + tid] = 0.0; cs[2 * SP - 2 + tid] = 0.0; }
+  const float* xb = aln_log + (long)b * T * n;
+  const double* sb = lse_fs + (long)b * T;
+  const double* ab = alpha + (long)b * T * (2 * n + 1);
+  double* eb = e + (long)b * T * (2 * n + 1);
+  float xv[NSJ], xn[NSJ];
+  double av[NSJ], an[NSJ], l = 0.0, ln = 0.0;
+#pragma unroll
+  for (int j = 0; j < NSJ; ++j) { xn[j] = 0.f; an[j] = 0.0; }
+  auto loadx = [&](int t, float (&dst)[NSJ], double (&da)[NSJ], double& lse) {
+    lse = sb[t];
+#pragma unroll
+    for (int j = 0; j < NSJ; ++j) {
+      const int s = tid + 256 * j;
+      dst[j] = (s < S && (s & 1)) ? xb[(long)t * n + (s >> 1)] : blank;
+      da[j] = s < S ? ab[(long)t * (2 * n + 1) + s] : 0.0;
+    }
+  };
+  if (ml > 0) loadx(ml - 1, xv, av, l);
+  __syncthreads();
+  for (int t = ml - 1; t >= 0; --t) {
+    if (t > 0) loadx(t - 1, xn, an, ln);
+    double* cur = cs + ((t & 1) ? SP : 0);
+    const double* nxt = cs + ((t & 1) ? 0 : SP);
+    double y[NSJ];
+#pragma unroll
+    for (int j = 0; j < NSJ; ++j) y[j] = al_emit(xv[j], l);
+    int k = 0;
+    if (t < ml - 1) {
+      const double* w = wm[(t & 1) ^ 1];
+      frexp(fmax(fmax(w[0], w[1]), fmax(w[2], w[3])), &k);
+    }
+    double mx = 0.0;
+#pragma unroll
+    for (int j = 0; j < NSJ; ++j) {
+      const int s = tid + 256 * j;
+      double bt;
+      if (t == ml - 1) bt = (s == S - 1 || s == S - 2) ? 1.0 : 0.0;
+      else bt = ldexp(nxt[s] + nxt[s + 1] + ((s & 1) ? nxt[s + 2] : 0.0), -k);
+      if (s >= S) bt = 0.0;
+      const double wv = y[j] * bt;
+      cur[s] = wv;
+      mx = fmax(mx, wv);
+      if (s < S) eb[(long)t * (2 * n + 1) + s] = av[j] * bt;
+    }
+    mx = wave_max_d(mx);
+    if ((tid & 63) == 0) wm[t & 1][tid >> 6] = mx;
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < NSJ; ++j) { xv[j] = xn[j]; av[j] = an[j]; }
+    l = ln;
+  }
+}
+
+// grid (ceil(T / AA_TQ), B), 256 threads, one wave per frame t < mel_len of a feasible utterance: the occupancies of a frame sum to 1
+// over its S states, so occupancy(s) = e[s] / sum_s e[s] -- no scale, no nll enters.  d_log[b, t, i] += (softmax - occupancy of label i)
+// scale on the live cells (the blank column's share is dropped), scale = g_fs / (max(L, 1) B).
+__global__ __launch_bounds__(256) void al_fs_grad_kernel(const float* aln_log, const int* text_lens, const int* mel_lens, const float* g_fs,
+                                                         int B, int T, int n, const double* lse_fs, const double* e, const double* nll,
+                                                         float* d_log) {
+  const int b = blockIdx.y, t0 = blockIdx.x * AA_TQ, wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int L = min(max(text_lens[b], 0), n), S = 2 * L + 1;
+  const int ml = nll[b] < (double)__builtin_inff() ? min(max(mel_lens[b], 0), T) : 0;
+  const double scale = (double)g_fs[0] / ((double)max(L, 1) * (double)B);
+  for (int f = wv; f < AA_TQ && t0 + f < ml; f += 4) {
+    const int t = t0 + f;
+    const double* er = e + ((long)b * T + t) * (2 * n + 1);
+    double sum = 0.0;
+    for (int s = lane; s < S; s += 64) sum += er[s];
+    const double inv = 1.0 / wave_sum_d(sum);
+    const long row = ((long)b * T + t) * n;
+    const double lse = lse_fs[(long)b * T + t];
+    for (int i = lane; i < L; i += 64)
+      d_log[row + i] += (float)((exp((double)aln_log[row + i] - lse) - er[2 * i + 1] * inv) * scale);
+  }
+}
+
+static inline int al_nsj(int n) { return (2 * n + 1 + 255) / 256; }
+
+struct AlWs { float* stats; double* lse_fs; double* nll; double* alpha; double* e; };
+static inline AlWs al_ws(void* workspace, int B, int T, int n) {
+  AlWs w;
+  w.stats = reinterpret_cast<float*>(workspace);
+  w.lse_fs = reinterpret_cast<double*>(w.stats + al_stats_floats(B, T));
+  w.nll = w.lse_fs + al_lse_floats(B, T) / 2;
+  w.alpha = w.nll + al_nll_floats(B) / 2;
+  w.e = w.alpha + (int64_t)B * T * (2 * n + 1);
+  return w;
+}
+
+#define AL_BY_NSJ(kernel, nsj, ...)                                                                     \
+  do {                                                                                                  \
+    if (nsj <= 1) hipLaunchKernelGGL((kernel<1>), dim3(B), dim3(256), 0, s, __VA_ARGS__);               \
+    else if (nsj <= 2) hipLaunchKernelGGL((kernel<2>), dim3(B), dim3(256), 0, s, __VA_ARGS__);          \
+    else if (nsj <= 3) hipLaunchKernelGGL((kernel<3>), dim3(B), dim3(256), 0, s, __VA_ARGS__);          \
+    else if (nsj <= 5) hipLaunchKernelGGL((kernel<5>), dim3(B), dim3(256), 0, s, __VA_ARGS__);          \
+    else hipLaunchKernelGGL((kernel<9>), dim3(B), dim3(256), 0, s, __VA_ARGS__);                        \
+  } while (0)
+
+hipError_t launch_align_losses_fwd(const float* aln_log, const float* hard, const int* text_lens, const int* mel_lens, int B, int T, int n,
+                                   float blank, float* fs_loss, float* bin_loss, void* workspace, hipStream_t s) {
+  if (B <= 0 || B > 65535 || T <= 0 || T > 8192 || n <= 0 || n > 1024 || (bin_loss && !hard)) return hipErrorInvalidValue;
+  const AlWs w = al_ws(workspace, B, T, n);
+  hipLaunchKernelGGL(al_rowstat_kernel, dim3((T + AA_TQ - 1) / AA_TQ, B), dim3(256), 0, s, aln_log, bin_loss ? hard : nullptr, text_lens, T,
+                     n, blank, w.stats, fs_loss ? w.lse_fs : nullptr);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  if (fs_loss) {
+    const int nsj = al_nsj(n);
+    AL_BY_NSJ(al_alpha_kernel, nsj, aln_log, text_lens, mel_lens, T, n, blank, w.lse_fs, w.alpha, w.nll);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(al_finish_kernel, dim3(1), dim3(256), 0, s, w.stats, w.nll, text_lens, B, T, n, fs_loss, bin_loss);
+  return hipGetLastError();
+}
+
+hipError_t launch_align_losses_bwd(const float* aln_log, const float* hard, const int* text_lens, const int* mel_lens, const float* g_fs,
+                                   const float* g_bin, int B, int T, int n, float blank, float* d_log, void* workspace, hipStream_t s) {
+  if (B <= 0 || B > 65535 || T <= 0 || T > 8192 || n <= 0 || n > 1024 || (g_bin && !hard)) return hipErrorInvalidValue;
+  const AlWs w = al_ws(workspace, B, T, n);
+  const dim3 rows((T + AA_TQ - 1) / AA_TQ, B);
+  hipLaunchKernelGGL(al_bin_bwd_kernel, rows, dim3(256), 0, s, aln_log, hard, text_lens, g_bin, B, T, n, w.stats, d_log);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess || !g_fs) return e;
+  const int nsj = al_nsj(n);
+  AL_BY_NSJ(al_beta_kernel, nsj, aln_log, text_lens, mel_lens, T, n, blank, w.lse_fs, w.alpha, w.nll, w.e);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(al_fs_grad_kernel, rows, dim3(256), 0, s, aln_log, text_lens, mel_lens, g_fs, B, T, n, w.lse_fs, w.e, w.nll, d_log);
+  return hipGetLastError();
+}
+
 }  // namespace ns2
 
 using namespace ns2;

@@ -924,7 +924,8 @@ hipError_t launch_attention_bwd(const AttnBwdArgs& a, hipStream_t s) {
 // The inference path runs SiLU in the GEMM epilogue (act = 1) and keeps no pre-activation; training keeps the fp32 pre-activation
 // and uses this pointwise pair: y = x / (1 + exp(-x)) ; dx = dy s (1 + x (1 - s)), s = 1 / (1 + exp(-x)).  A thread owns 4 columns of a row
 // (one float4 each way), one pass.
-template <bool BWD>
+// RELU: the same pass for the Aligner's ReLUs between its convolutions (aligner.py:30-51): y = max(x, 0) ; dx = dy where x > 0.
+template <bool BWD, bool RELU = false>
 __global__ __launch_bounds__(256) void silu_kernel(const float* x, long ldx, const float* dy, long lddy, long M, int C, float* out, long ldo) {
   const int chunks = (C + 3) >> 2;
   const long idx = (long)blockIdx.x * 256 + threadIdx.x;
@@ -950,7 +951,9 @@ __global__ __launch_bounds__(256) void silu_kernel(const float* x, long ldx, con
   }
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
-    if constexpr (BWD) {
+    if constexpr (RELU) {
+      o[e] = BWD ? (xv[e] > 0.f ? gv[e] : 0.f) : fmaxf(xv[e], 0.f);
+    } else if constexpr (BWD) {
       const float sg = 1.0f / (1.0f + expf(-xv[e]));
       o[e] = gv[e] * sg * (1.0f + xv[e] * (1.0f - sg));
     } else {
@@ -977,6 +980,19 @@ hipError_t launch_silu_bwd(const float* dy, long lddy, const float* x, long ldx,
     return hipErrorInvalidValue;
   const long n = M * ((C + 3) >> 2);
   hipLaunchKernelGGL((silu_kernel<true>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, ldx, dy, lddy, M, C, dx, lddx);
+  return hipGetLastError();
+}
+hipError_t launch_relu_fwd(const float* x, long ldx, long M, int C, float* out, long ldo, hipStream_t s) {
+  if (M <= 0 || C <= 0 || ldx < C || ldo < C || !silu_vec_ok(x, ldx) || !silu_vec_ok(out, ldo)) return hipErrorInvalidValue;
+  const long n = M * ((C + 3) >> 2);
+  hipLaunchKernelGGL((silu_kernel<false, true>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, ldx, (const float*)nullptr, 0L, M, C, out, ldo);
+  return hipGetLastError();
+}
+hipError_t launch_relu_bwd(const float* dy, long lddy, const float* x, long ldx, long M, int C, float* dx, long lddx, hipStream_t s) {
+  if (M <= 0 || C <= 0 || ldx < C || lddy < C || lddx < C || !silu_vec_ok(x, ldx) || !silu_vec_ok(dy, lddy) || !silu_vec_ok(dx, lddx))
+    return hipErrorInvalidValue;
+  const long n = M * ((C + 3) >> 2);
+  hipLaunchKernelGGL((silu_kernel<true, true>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, ldx, dy, lddy, M, C, dx, lddx);
   return hipGetLastError();
 }
 

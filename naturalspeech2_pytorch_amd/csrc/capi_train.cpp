@@ -314,3 +314,55 @@ extern "C" int ns2_row_dot_relu_bwd(const float* dout, const float* out, const f
   HIPRET(launch_row_dot_relu_bwd(dout, out, h, (long)ldh, w, (long)M, K, dh, (long)lddh, dw_db, (float*)workspace, (hipStream_t)stream));
   return NS2_OK;
 }
+
+// ---- training of the Aligner (kernels: aligner.hip, the ReLU pair in backward.hip)
+extern "C" int ns2_relu_fwd(const float* x, int64_t ldx, int64_t M, int C, float* out, int64_t ldo, void* stream) {
+  ARGCHK(x && out, "ns2_relu_fwd: null pointer");
+  HIPRET(launch_relu_fwd(x, (long)ldx, (long)M, C, out, (long)ldo, (hipStream_t)stream));
+  return NS2_OK;
+}
+extern "C" int ns2_relu_bwd(const float* dy, int64_t lddy, const float* x, int64_t ldx, int64_t M, int C, float* dx, int64_t lddx, void* stream) {
+  ARGCHK(dy && x && dx, "ns2_relu_bwd: null pointer");
+  HIPRET(launch_relu_bwd(dy, (long)lddy, x, (long)ldx, (long)M, C, dx, (long)lddx, (hipStream_t)stream));
+  return NS2_OK;
+}
+extern "C" int64_t ns2_align_attn_bwd_workspace_bytes(int B, int T, int n, int C) {
+  if (T > 8192 || n > 1024 || C > 256) return 0;
+  return align_attn_bwd_workspace_bytes(B, T, n, C);
+}
+extern "C" int ns2_align_attn_bwd(const float* queries, const float* keys, const float* aln_log, const float* aln_soft, const float* g_log,
+                                  const float* g_soft, const int* text_lens, int B, int T, int n, int C, float* dq, float* dk, void* workspace,
+                                  int64_t workspace_bytes, void* stream) {
+  ARGCHK(queries && keys && aln_log && aln_soft && text_lens && dq && dk && workspace && B > 0 && T > 0 && n > 0 && C > 0,
+         "ns2_align_attn_bwd: bad arguments");
+  ARGCHK(n <= 1024 && C <= 256 && T <= 8192 && B <= 65535, "ns2_align_attn_bwd: at most 1024 phonemes, 256 channels, 8192 mel frames");
+  ARGCHK(workspace_bytes >= align_attn_bwd_workspace_bytes(B, T, n, C), "ns2_align_attn_bwd: workspace too small (ns2_align_attn_bwd_workspace_bytes)");
+  ARGCHK((uintptr_t)workspace % 16 == 0, "ns2_align_attn_bwd: the workspace must be 16-byte aligned");
+  HIPRET(launch_align_attn_bwd(queries, keys, aln_log, aln_soft, g_log, g_soft, text_lens, B, T, n, C, dq, dk, workspace, (hipStream_t)stream));
+  return NS2_OK;
+}
+extern "C" int64_t ns2_align_losses_workspace_bytes(int B, int T, int n) {
+  if (T > 8192 || n > 1024) return 0;
+  return align_losses_workspace_bytes(B, T, n);
+}
+extern "C" int ns2_align_losses_fwd(const float* aln_log, const float* hard, const int* text_lens, const int* mel_lens, int B, int T, int n,
+                                    float blank_logprob, float* fs_loss, float* bin_loss, void* workspace, int64_t workspace_bytes, void* stream) {
+  ARGCHK(aln_log && text_lens && workspace && (fs_loss || bin_loss) && B > 0 && T > 0 && n > 0, "ns2_align_losses_fwd: bad arguments");
+  ARGCHK(!fs_loss || mel_lens, "ns2_align_losses_fwd: the forward-sum loss needs mel_lens");
+  ARGCHK(!bin_loss || hard, "ns2_align_losses_fwd: the bin loss needs the hard alignment");
+  ARGCHK(n <= 1024 && T <= 8192 && B <= 65535, "ns2_align_losses_fwd: at most 1024 phonemes and 8192 mel frames");
+  ARGCHK(workspace_bytes >= align_losses_workspace_bytes(B, T, n), "ns2_align_losses_fwd: workspace too small (ns2_align_losses_workspace_bytes)");
+  HIPRET(launch_align_losses_fwd(aln_log, hard, text_lens, mel_lens, B, T, n, blank_logprob, fs_loss, bin_loss, workspace, (hipStream_t)stream));
+  return NS2_OK;
+}
+extern "C" int ns2_align_losses_bwd(const float* aln_log, const float* hard, const int* text_lens, const int* mel_lens, const float* g_fs,
+                                    const float* g_bin, int B, int T, int n, float blank_logprob, float* d_log, void* workspace,
+                                    int64_t workspace_bytes, void* stream) {
+  ARGCHK(aln_log && text_lens && workspace && d_log && (g_fs || g_bin) && B > 0 && T > 0 && n > 0, "ns2_align_losses_bwd: bad arguments");
+  ARGCHK(!g_fs || mel_lens, "ns2_align_losses_bwd: the forward-sum loss needs mel_lens");
+  ARGCHK(!g_bin || hard, "ns2_align_losses_bwd: the bin loss needs the hard alignment");
+  ARGCHK(n <= 1024 && T <= 8192 && B <= 65535, "ns2_align_losses_bwd: at most 1024 phonemes and 8192 mel frames");
+  ARGCHK(workspace_bytes >= align_losses_workspace_bytes(B, T, n), "ns2_align_losses_bwd: workspace = the one ns2_align_losses_fwd filled (too small)");
+  HIPRET(launch_align_losses_bwd(aln_log, hard, text_lens, mel_lens, g_fs, g_bin, B, T, n, blank_logprob, d_log, workspace, (hipStream_t)stream));
+  return NS2_OK;
+}

@@ -332,7 +332,20 @@ hipError_t launch_attention_bwd(const AttnBwdArgs& a, hipStream_t s);
 // dropout keep mask of dropout_keep.h as bytes [B, H, Nq, Nk]
 hipError_t launch_silu_fwd(const float* x, long ldx, long M, int C, float* out, long ldo, hipStream_t s);
 hipError_t launch_silu_bwd(const float* dy, long lddy, const float* x, long ldx, long M, int C, float* dx, long lddx, hipStream_t s);
+hipError_t launch_relu_fwd(const float* x, long ldx, long M, int C, float* out, long ldo, hipStream_t s);
+hipError_t launch_relu_bwd(const float* dy, long lddy, const float* x, long ldx, long M, int C, float* dx, long lddx, hipStream_t s);
 hipError_t launch_embedding_bwd(const long long* ids, long M, int pad_id, const float* dy, long lddy, int rows, int d, float* dw, hipStream_t s);
 hipError_t launch_dropout_keep_mask(const uint32_t* seed, uint32_t call, float p, int B, int H, int Nq, int Nk, unsigned char* out, hipStream_t s);
+
+// training the Aligner (aligner.hip): backward of the distances + softmax, the forward-sum (CTC) and bin losses and their gradient
+int64_t align_attn_bwd_workspace_bytes(int B, int T, int n, int C);
+hipError_t launch_align_attn_bwd(const float* q, const float* k, const float* aln_log, const float* aln_soft, const float* g_log,
+                                 const float* g_soft, const int* text_lens, int B, int T, int n, int C, float* dq, float* dk,
+                                 void* workspace, hipStream_t s);
+int64_t align_losses_workspace_bytes(int B, int T, int n);
+hipError_t launch_align_losses_fwd(const float* aln_log, const float* hard, const int* text_lens, const int* mel_lens, int B, int T, int n,
+                                   float blank, float* fs_loss, float* bin_loss, void* workspace, hipStream_t s);
+hipError_t launch_align_losses_bwd(const float* aln_log, const float* hard, const int* text_lens, const int* mel_lens, const float* g_fs,
+                                   const float* g_bin, int B, int T, int n, float blank, float* d_log, void* workspace, hipStream_t s);
 
 }  // namespace ns2

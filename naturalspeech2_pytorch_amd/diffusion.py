@@ -86,7 +86,8 @@ class NaturalSpeech2(nn.Module):
                  build_duration_pitch: bool = False,   # not in the reference: build the DurationPitchPredictor (sample(text=...))
                  build_aligner: bool = False,          # not in the reference: build the Aligner (forward(text=..., mel=..., pitch=...))
                  encoder_train_backend="composite",    # not in the reference: "hip" trains phoneme_enc / prompt_enc on the HIP kernels (training/encoder_pass.py)
-                 duration_pitch_train_backend="composite"):   # not in the reference: "hip" trains the DurationPitchPredictor on them (training/duration_pitch_pass.py)
+                 duration_pitch_train_backend="composite",    # not in the reference: "hip" trains the DurationPitchPredictor on them (training/duration_pitch_pass.py)
+                 aligner_train_backend="composite"):   # not in the reference: "hip" trains the Aligner and runs its two losses on them (training/aligner_pass.py)
         super().__init__()
         assert _is_denoiser(model), "model must be a Model (this package's, or compat.HipBackedModel over the reference's class)"
         self.conditional = model.condition_on_prompt
@@ -117,9 +118,9 @@ class NaturalSpeech2(nn.Module):
             if build_aligner:                                                         # NS2:1235, 1238-1239
                 from .aligner import Aligner, BinLoss, ForwardSumLoss
                 self.aligner = Aligner(dim_in=aligner_dim_in, dim_hidden=aligner_dim_hidden, attn_channels=aligner_attn_channels,
-                                       precision=encoder_precision)
-                self.aligner_loss = ForwardSumLoss()
-                self.bin_loss = BinLoss()
+                                       precision=encoder_precision, train_backend=aligner_train_backend)
+                self.aligner_loss = ForwardSumLoss(backend=aligner_train_backend)
+                self.bin_loss = BinLoss(backend=aligner_train_backend)
         else:
             assert not build_aligner, "the Aligner belongs to a conditional model (condition_on_prompt=True)"
 
@@ -331,7 +332,8 @@ class NaturalSpeech2(nn.Module):
         of the phoneme encodings + pitch embeddings into exactly T_mel = mel.shape[-1] frames.  Unlike the reference, the
         caller's `text_lens` / `mel_lens` are not clamped in place: clamped copies are used.  On CUDA the Aligner runs its HIP
         path under no_grad (the returned loss depends on it only through the hard path) and the lengths go straight to the
-        kernels: no host read.  With return_aux_losses the Aligner runs its differentiable composite and the auxiliary terms
+        kernels: no host read.  With return_aux_losses the Aligner runs its differentiable composite (or, built with
+        `aligner_train_backend="hip"`, its HIP training pass on the lengths: still no host read) and the auxiliary terms
         of NS2:1587-1602 are returned as a dict.  -> (cond, aux or None)"""
         from .aligner import average_over_durations, create_mask, expand_encodings
         b, n = text.shape[0], text.shape[-1]
@@ -340,7 +342,10 @@ class NaturalSpeech2(nn.Module):
         T = mel.shape[-1]
         mel_lens = torch.full((b,), T, device=dev, dtype=torch.long) if mel_lens is None else mel_lens.clamp(max=T)
         phoneme_enc = self.phoneme_enc(text)                                           # [b, n, dim_hidden]
-        if return_aux_losses or not phoneme_enc.is_cuda:
+        if return_aux_losses and torch.is_grad_enabled() and self.aligner.train_ready(phoneme_enc, mel):
+            # aligner_train_backend="hip": the clamped lengths go straight to the kernels -- no masks, no host read
+            aln_hard, aln_soft, aln_log, aln_mask = self.aligner.forward_lengths_train(phoneme_enc, text_lens, mel, mel_lens)
+        elif return_aux_losses or not phoneme_enc.is_cuda:
             text_mask, mel_mask = create_mask(text_lens, n)[:, None], create_mask(mel_lens, T)[:, None]
             with torch.set_grad_enabled(return_aux_losses and torch.is_grad_enabled()):
                 aln_hard, aln_soft, aln_log, aln_mask = self.aligner._forward_composite(phoneme_enc, text_mask, mel, mel_mask)

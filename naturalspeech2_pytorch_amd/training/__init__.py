@@ -30,7 +30,9 @@ trained jointly: NS2:1538-1543) run on the same Functions -- `transformer_forwar
 `speech_prompt_encoder_forward_train`: `AttnFn` / `FeedForwardFn` with a learned-gamma RMSNorm in front,
 key-padding mask and dropout in the attention forward / backward (csrc/dropout_keep.h), `GemmFn(pad_left=)` for the "same" k = 9
 convolutions, `SiluFn`, `EmbeddingFn`; exact arithmetic only (DESIGN.md §9).  The `DurationPitchPredictor` (`train_backend="hip"`;
-NS2:344-527) adds `GroupNormSiluFn`, `RowDotReluFn` and the `resid` operand of `AttnFn`: `duration_pitch_forward_train`.
+NS2:344-527) adds `GroupNormSiluFn`, `RowDotReluFn` and the `resid` operand of `AttnFn`: `duration_pitch_forward_train`.  The `Aligner`
+(`train_backend="hip"`; aligner.py) adds `ReluFn` and `AlignAttnFn`: `aligner_forward_train` (aligner_pass.py); its two losses are
+Functions of their own in aligner.py (`ForwardSumLoss` / `BinLoss` with `backend="hip"`).
 
 `Backend` is the seam the CPU tests use: `tests/emu_backend.py` restates every backend call with plain torch ops on CPU, so the
 chain rule, tap flips, shifts and layouts of THIS package are checked against torch autograd without a GPU; the kernels behind
@@ -38,10 +40,11 @@ chain rule, tap flips, shifts and layouts of THIS package are checked against to
 
 Where things are; each module imports only from those before it: packs.py (the packed-weight cache), backend.py (`TPlanes`, `HipBackend`),
 passes.py (what "the current pass" is: `training_pass`, `backend()` and its registries, `weights_unchanged`, the loss scale `_Scale`),
-functions.py (the autograd Functions), model_pass.py / encoder_pass.py / duration_pitch_pass.py (the `*_forward_train` of `Model`, of the
-conditioning encoders and of the predictor), graph.py (`GraphedTrainStep`, on passes.py alone).  The names below are the package's interface; tests and tools take an
+functions.py (the autograd Functions), model_pass.py / encoder_pass.py / duration_pitch_pass.py / aligner_pass.py (the `*_forward_train` of `Model`, of the
+conditioning encoders, of the predictor and of the aligner), graph.py (`GraphedTrainStep`, on passes.py alone).  The names below are the package's interface; tests and tools take an
 underscore name from the module that holds it.
 """
+from .aligner_pass import aligner_forward_train, aligner_unsupported_reason
 from .backend import HipBackend, TPlanes
 from .duration_pitch_pass import duration_pitch_forward_train, duration_pitch_unsupported_reason
 from .encoder_pass import (encoder_unsupported_reason, phoneme_encoder_forward_train, speech_prompt_encoder_forward_train,
@@ -50,6 +53,6 @@ from .graph import GraphedTrainStep
 from .model_pass import available, model_forward_train, unsupported_reason
 from .passes import TRAIN_PRECISIONS, backend, set_backend, weights_unchanged
 
-__all__ = ["HipBackend", "TPlanes", "duration_pitch_forward_train", "duration_pitch_unsupported_reason", "encoder_unsupported_reason", "phoneme_encoder_forward_train", "speech_prompt_encoder_forward_train",
+__all__ = ["HipBackend", "TPlanes", "aligner_forward_train", "aligner_unsupported_reason", "duration_pitch_forward_train", "duration_pitch_unsupported_reason", "encoder_unsupported_reason", "phoneme_encoder_forward_train", "speech_prompt_encoder_forward_train",
            "transformer_forward_train", "GraphedTrainStep", "available", "model_forward_train", "unsupported_reason", "TRAIN_PRECISIONS",
            "backend", "set_backend", "weights_unchanged"]

@@ -108,6 +108,54 @@ class HipBackend:
               "ns2_silu_bwd")
         return dx
 
+    def relu_fwd(self, pre, C):
+        """ReLU of the fp32 pre-activation pre [M, >= C] -> fp32 [M, round_up(C, 32)] (columns >= C not written): the Aligner's conv stacks"""
+        out = torch.empty(pre.shape[0], round_up(C, 32), dtype=torch.float32, device=pre.device)
+        check(self.lib.ns2_relu_fwd(pre.data_ptr(), pre.stride(0), pre.shape[0], C, out.data_ptr(), out.stride(0), _stream()), "ns2_relu_fwd")
+        return out
+
+    def relu_bwd(self, dy, pre, C):
+        dx = torch.empty(pre.shape[0], round_up(C, 32), dtype=torch.float32, device=pre.device)
+        check(self.lib.ns2_relu_bwd(dy.data_ptr(), dy.stride(0), pre.data_ptr(), pre.stride(0), pre.shape[0], C, dx.data_ptr(), dx.stride(0), _stream()),
+              "ns2_relu_bwd")
+        return dx
+
+    # ---- Aligner: distances + softmax and their backward, the forward-sum / bin losses (aligner.py:62-90, 132-183)
+    def align_attn(self, q, k, text_lens, B):
+        """queries [B T, C], keys [B n, C] fp32 -> (aln_log [B, 1, T, n], aln_soft [B, n, T]): ns2_align_attn, the inference kernel"""
+        return ops.align_attn(q, k, text_lens, B)
+
+    def align_attn_bwd(self, q, k, log, soft, g_log, g_soft, text_lens):
+        """-> (dq [B T, C], dk [B n, C]); g_log [B, 1, T, n] / g_soft [B, n, T]: either may be None"""
+        B, _, T, n = log.shape
+        C = q.shape[1]
+        dq, dk = torch.empty_like(q), torch.empty_like(k)
+        nbytes = self.lib.ns2_align_attn_bwd_workspace_bytes(B, T, n, C)
+        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=q.device)
+        check(self.lib.ns2_align_attn_bwd(q.data_ptr(), k.data_ptr(), log.data_ptr(), soft.data_ptr(), _p(g_log), _p(g_soft), text_lens.data_ptr(),
+                                          B, T, n, C, dq.data_ptr(), dk.data_ptr(), ws.data_ptr(), nbytes, _stream()), "ns2_align_attn_bwd")
+        return dq, dk
+
+    def align_losses_fwd(self, log, text_lens, mel_lens, blank, hard=None, want_fs=True, want_bin=False):
+        """aln_log [B, 1, T, n] fp32 contiguous, int32 lengths on the device, hard [B, n, T] (bin loss) -> (fs_loss, bin_loss, workspace):
+        0-dim device tensors (None where not wanted); `workspace` is what `align_losses_bwd` reads"""
+        B, _, T, n = log.shape
+        out = torch.empty(2, dtype=torch.float32, device=log.device)
+        nbytes = self.lib.ns2_align_losses_workspace_bytes(B, T, n)
+        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=log.device)
+        check(self.lib.ns2_align_losses_fwd(log.data_ptr(), _p(hard), text_lens.data_ptr(), _p(mel_lens), B, T, n, float(blank),
+                                            out[0:].data_ptr() if want_fs else None, out[1:].data_ptr() if want_bin else None, ws.data_ptr(), nbytes,
+                                            _stream()), "ns2_align_losses_fwd")
+        return (out[0] if want_fs else None), (out[1] if want_bin else None), ws
+
+    def align_losses_bwd(self, log, text_lens, mel_lens, blank, ws, hard=None, g_fs=None, g_bin=None):
+        """-> d aln_log [B, 1, T, n]; g_fs / g_bin: fp32 device scalars (None = that loss takes no part)"""
+        B, _, T, n = log.shape
+        d_log = torch.empty_like(log)
+        check(self.lib.ns2_align_losses_bwd(log.data_ptr(), _p(hard), text_lens.data_ptr(), _p(mel_lens), _p(g_fs), _p(g_bin), B, T, n, float(blank),
+                                            d_log.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "ns2_align_losses_bwd")
+        return d_log
+
     def embedding(self, ids, table, pad_id):
         return ops.embedding(ids, table, pad_id)
 

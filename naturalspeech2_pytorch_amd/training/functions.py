@@ -377,6 +377,44 @@ class SiluFn(torch.autograd.Function):
         return ctx.bk.silu_bwd(dy, pre, pre.shape[1])[:, :pre.shape[1]]
 
 
+class ReluFn(torch.autograd.Function):
+    """ReLU on fp32 rows with the pre-activation kept: between the Aligner's convolutions (aligner.py:30-51; inference runs ns2_relu_split and
+    keeps nothing)"""
+
+    @staticmethod
+    def forward(ctx, pre):
+        bk = _begin(ctx)
+        ctx.save_for_backward(pre)
+        return bk.relu_fwd(pre, pre.shape[1])[:, :pre.shape[1]]
+
+    @staticmethod
+    def backward(ctx, dy):
+        pre, = ctx.saved_tensors
+        dy = _rowmajor(dy)
+        return ctx.bk.relu_bwd(dy, pre, pre.shape[1])[:, :pre.shape[1]]
+
+
+class AlignAttnFn(torch.autograd.Function):
+    """AlignerNet's attention (aligner.py:72-90): queries [B T, C], keys [B n, C], int32 text lengths [B] on the device -> (aln_log [B, 1, T, n]
+    = the distances, -FLT_MAX at masked phonemes; aln_soft [B, n, T] = their softmax).  Forward: the inference kernel ns2_align_attn, the same
+    bits; backward: ns2_align_attn_bwd (direct-form sums in fixed orders)"""
+
+    @staticmethod
+    def forward(ctx, q, k, text_lens, B):
+        bk = _begin(ctx)
+        log, soft = bk.align_attn(q, k, text_lens, B)
+        ctx.save_for_backward(q, k, log, soft, text_lens)
+        return log, soft
+
+    @staticmethod
+    def backward(ctx, g_log, g_soft):
+        q, k, log, soft, text_lens = ctx.saved_tensors
+        g_log = None if g_log is None else _c(g_log.float())
+        g_soft = None if g_soft is None else _c(g_soft.float())
+        dq, dk = ctx.bk.align_attn_bwd(q, k, log, soft, g_log, g_soft, text_lens)
+        return dq, dk, None, None
+
+
 class GroupNormSiluFn(torch.autograd.Function):
     """silu(GroupNorm(x)) (+ resid) over the rows of utterances of `seq_len` tokens: a Block of the DurationPitchPredictor's ResnetBlock, the
     last one with the ResnetBlock's input as `resid` (NS2:346-400).  The backward normalises with the forward's own statistics slots."""
