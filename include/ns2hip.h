@@ -374,6 +374,21 @@ int ns2_rvq_encode(const float* x, const float* codebooks, const float* cb_norm,
                    float* residual, int* near_tie_count, int M, int Q, int C, int D, float tie_eps, void* stream);
 int ns2_rvq_decode(const int64_t* codes, const float* codebooks, float* emb, int M, int Q, int C, int D, void* stream);
 
+/* RVQ cross-entropy of the training loss (NS2:1668-1684, `codec.rq(x_start, codes)`; csrc/rvq_ce.hip), everything fp32.  For the M rows of
+ * x [M, D] and per quantizer q: dist_c = |r_q - E_q[c]|, row_loss[m][q] = log sum_c exp(-dist_c) + dist_target with target =
+ * indices[m][q]; r_{q+1} = r_q - (the code nearest to r_q); loss[0] = sum_q mean_m row_loss[m][q], summed in a fixed order.
+ * Optional outputs (null = not wanted): quantized_out [M, D] = 0 + E_0[nearest_0] + E_1[nearest_1] + ... in fp32, in stage order;
+ * grad [M, D] = d loss / d x (the nearest codes are constants: sum_q d row_loss_q / d r_q, divided by M) -- null skips the second
+ * sweep over the codebooks that forms it.  No atomics: loss and grad are bit-reproducible, and the loss does not depend on whether grad is asked for.
+ * Defined edge behaviour: an index outside [0, C) (-1 included) makes that row's losses, hence loss[0], and its row of grad NaN -- no
+ * error code, no host read; a residual that equals a code (dist = 0) gives the well-defined loss and that code contributes 0 to grad;
+ * near-ties of the nearest code are decided by the fp32 scores (ns2_rvq_encode re-decides them in fp64, this one does not).
+ * cb_norm: what ns2_rvq_prepare filled.  workspace: ns2_rvq_ce_workspace_bytes(M, Q, quantized_out != null) bytes (0 without
+ * quantized_out).  NS2_ERR_ARG for D != 128 or C % 64 != 0, as ns2_rvq_encode. */
+int64_t ns2_rvq_ce_workspace_bytes(int M, int Q, int want_quantized);
+int ns2_rvq_ce(const float* x, const float* codebooks, const float* cb_norm, const int64_t* indices, float* row_loss, float* loss,
+               float* quantized_out, float* grad, int M, int Q, int C, int D, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------ Model (NS2:811-1000) */
 typedef struct ns2_model ns2_model;
 typedef struct {

@@ -193,6 +193,9 @@ SIGNATURES = {
     "ns2_align_losses_workspace_bytes": (L, [I, I, I]),
     "ns2_align_losses_fwd": (I, [P, P, P, P, I, I, I, F, P, P, P, L, P]),
     "ns2_align_losses_bwd": (I, [P, P, P, P, P, P, I, I, I, F, P, P, L, P]),
+    # ---- the RVQ cross-entropy term of the training loss
+    "ns2_rvq_ce_workspace_bytes": (L, [I, I, I]),
+    "ns2_rvq_ce": (I, [P, P, P, P, P, P, P, P, I, I, I, I, P, L, P]),
 }
 
 NS2_UNAVAILABLE = 1          # include/ns2hip.h: "this fast path does not apply here" (not an error)

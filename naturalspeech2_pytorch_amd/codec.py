@@ -22,6 +22,9 @@ from . import ops
 from ._cache import PackedCache
 
 
+RQ_BACKENDS = ("composite", "hip")           # of `codec.rq`, the RVQ cross-entropy term of the training loss
+
+
 class HipRVQ(nn.Module):
     """EnCodec residual vector quantizer (HFENC:424-447) over `codebooks` [Q, C, 128]."""
 
@@ -57,13 +60,43 @@ class ResidualVQCrossEntropy(nn.Module):
     `>=1.4.1`, no lock file; not vendored, not installed here).  Restated from its published algorithm: per quantizer the
     logits are the NEGATIVE EUCLIDEAN distances (with the square root) of the running residual to every code, the loss is
     `F.cross_entropy(logits, indices[..., q])`, the residual is reduced by the nearest code (detached), and the layer losses
-    are summed.  Differentiable in `x` (autograd composite: the term only exists in training)."""
+    are summed.  Differentiable in `x`.
 
-    def __init__(self, owner: HipRVQ):
+    `backend` (settable; not in the reference): "composite" (default) is the autograd composite below; "hip" runs the term on the fused
+    kernel of csrc/rvq_ce.hip through `training.RvqCrossEntropyFn` -- one launch for the loss and its unit gradient, nothing of size
+    [b, n, C] kept, no host read (capturable by `training.GraphedTrainStep`), fp32.  It falls back to the composite for what
+    `training.rvq_ce_unsupported_reason` names (CPU tensors, non-fp32 `x`, indices that are not int64, no library).  Where the kernel differs:
+      * an index outside [0, C) -- the -1 of a dropped-out quantizer included, which the composite asserts against after reading the device
+        -- makes the loss NaN (and that row's gradient): loud, without a synchronisation;
+      * a residual that equals a code (distance 0) gives the well-defined loss and that code adds 0 to the gradient, where the composite's
+        gradient of sqrt at 0 is not finite;
+      * the nearest code of a stage is decided by the fp32 scores r.e - |e|^2/2; on a near-tie either code is a valid stage result."""
+
+    def __init__(self, owner: HipRVQ, backend: str = "composite"):
         super().__init__()
+        assert backend in RQ_BACKENDS, f"backend must be one of {RQ_BACKENDS}"
         self._owner = [owner]              # not registered: the codebooks stay owned (and moved) by the HipRVQ
+        self.backend = backend
 
     def forward(self, x, indices):
+        assert self.backend in RQ_BACKENDS, f"backend must be one of {RQ_BACKENDS}"
+        if self.backend == "hip":
+            from . import training
+            if training.rvq_ce_unsupported_reason(self, x, indices) is None:
+                return self._forward_hip(x, indices)
+        return self._forward_composite(x, indices)
+
+    def _forward_hip(self, x, indices):
+        from .training.functions import RvqCrossEntropyFn
+        owner = self._owner[0]
+        assert indices.shape[:-1] == x.shape[:-1] and indices.shape[-1] == owner.codebooks.shape[0]
+        d = x.shape[-1]
+        xr = x.reshape(-1, d)
+        loss, quant = RvqCrossEntropyFn.apply(xr if xr.is_contiguous() else xr.contiguous(), owner.codebooks, owner._cb_norm(),
+                                              indices.reshape(-1, indices.shape[-1]))
+        return quant.reshape(x.shape), loss
+
+    def _forward_composite(self, x, indices):
         cb = self._owner[0].codebooks.to(x.dtype)
         assert indices.shape[:-1] == x.shape[:-1] and indices.shape[-1] == cb.shape[0]
         assert not torch.any(indices == -1), "some of the residual vq indices were dropped out"
@@ -84,19 +117,21 @@ class EncodecWrapperHIP(nn.Module):
     seq_len_multiple_of = 320          # strides 2*4*5*8
     codebook_dim = 128
 
-    def __init__(self, codebooks: torch.Tensor, encoder: Optional[Callable] = None, decoder: Optional[Callable] = None):
+    def __init__(self, codebooks: torch.Tensor, encoder: Optional[Callable] = None, decoder: Optional[Callable] = None,
+                 rq_backend: str = "composite"):
+        """rq_backend (not in the reference): the backend of `self.rq`, the RVQ cross-entropy term (`ResidualVQCrossEntropy`)"""
         super().__init__()
-        self._hip_codec_init(codebooks, encoder, decoder)
+        self._hip_codec_init(codebooks, encoder, decoder, rq_backend)
 
-    def _hip_codec_init(self, codebooks, encoder=None, decoder=None):
+    def _hip_codec_init(self, codebooks, encoder=None, decoder=None, rq_backend="composite"):
         """everything but nn.Module's own set-up: compat.hip_backed_codec_class builds a subclass of the REFERENCE's codec class whose
         own __init__ (it fetches pretrained EnCodec weights) must not run"""
         self.rvq = HipRVQ(codebooks)
-        self.rq = ResidualVQCrossEntropy(self.rvq)
+        self.rq = ResidualVQCrossEntropy(self.rvq, backend=rq_backend)
         self.encoder, self.decoder = encoder, decoder
 
     @classmethod
-    def from_hf(cls, hf_model, num_quantizers: int = 8, hip_seanet: bool = True, precision: str = "exact"):
+    def from_hf(cls, hf_model, num_quantizers: int = 8, hip_seanet: bool = True, precision: str = "exact", rq_backend: str = "composite"):
         """wire a `transformers.EncodecModel`'s SEANet encoder / decoder and its first `num_quantizers` codebooks (6 kbps at
         24 kHz = 8, what audiolm's EncodecWrapper uses).  hip_seanet=True (default): the SEANet stacks run on the HIP kernels
         (seanet.py) with the model's own (weight-normalised) parameters; False: HF's PyTorch modules are called as they are."""
@@ -106,7 +141,7 @@ class EncodecWrapperHIP(nn.Module):
         if hip_seanet:
             from .seanet import SEANetDecoderHIP, SEANetEncoderHIP
             enc, dec = SEANetEncoderHIP(enc, precision=precision), SEANetDecoderHIP(dec, precision=precision)
-        return cls(cbs, encoder=enc, decoder=dec)
+        return cls(cbs, encoder=enc, decoder=dec, rq_backend=rq_backend)
 
     @property
     def num_quantizers(self):

@@ -69,7 +69,7 @@ def hip_backed_codec_class(reference_codec_cls):
     whatever the reference's `codec:` annotation accepts, NS2:1166) and this package's `EncodecWrapperHIP`, whose residual-VQ
     encode / decode (csrc/rvq.hip) and SEANet encoder / decoder (seanet.py) run on the HIP kernels.  The reference class's own
     `__init__` is NOT run (audiolm's downloads the pretrained EnCodec checkpoint and builds the PyTorch codec this class replaces):
-    construct it like `EncodecWrapperHIP` -- `HipBackedEncodec(codebooks, encoder=, decoder=)` or `.from_hf(hf_encodec_model)`.
+    construct it like `EncodecWrapperHIP` -- `HipBackedEncodec(codebooks, encoder=, decoder=, rq_backend=)` or `.from_hf(hf_encodec_model)`.
     Everything the reference touches comes from `EncodecWrapperHIP`: target_sample_hz / seq_len_multiple_of / codebook_dim, forward(x,
     return_encoded=, curtail_from_left=) -> (emb, codes, None), decode(emb), rq(x, codes) (codec.py)."""
     from torch import nn
@@ -77,9 +77,9 @@ def hip_backed_codec_class(reference_codec_cls):
     from .codec import EncodecWrapperHIP
 
     class HipBackedEncodec(EncodecWrapperHIP, reference_codec_cls):
-        def __init__(self, codebooks, encoder=None, decoder=None):
+        def __init__(self, codebooks, encoder=None, decoder=None, rq_backend="composite"):
             nn.Module.__init__(self)
-            self._hip_codec_init(codebooks, encoder, decoder)
+            self._hip_codec_init(codebooks, encoder, decoder, rq_backend)
 
     HipBackedEncodec.__qualname__ = HipBackedEncodec.__name__ = "HipBackedEncodec"
     return HipBackedEncodec

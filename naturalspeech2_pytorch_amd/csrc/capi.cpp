@@ -48,7 +48,7 @@ using namespace ns2;
 static inline int prec_ok(int p) { return p >= 1 && p <= 4; }
 
 extern "C" const char* ns2_last_error(void) { return g_err; }
-extern "C" int ns2_version(void) { return 122; }   // 122: training of the Aligner: ns2_relu_fwd / _bwd, ns2_align_attn_bwd (+ _workspace_bytes), ns2_align_losses_fwd / _bwd (+ _workspace_bytes); 121: two utterance chains: ns2_debug_force_chains / _chains_last / _chain_rule, ns2_model_profile_end counts logical products; 120: one argument block per Linear / Conv1d product: ns2_linear(ns2_linear_args) replaces ns2_linear_f32 / _split / _split_as / _geglu / _qkv; 119: one argument block per attention direction: ns2_attention_fwd(ns2_attn_args) replaces ns2_attention / _hd / _lse / _lse_masked, ns2_attn_bwd_args carries the mask and dropout of the removed bwd_masked entry; 118: ns2_debug_force_attention, ns2_debug_attention_fast_launches (attn_fast_kernel.h); 117: the range-guard counters register themselves: ns2_saturation_counters / _counter_name / _peek replace ns2_saturation_peek_async / _peek_train_async; 116: ns2_groupnorm_silu, ns2_length_regulate(_totals), ns2_row_dot (duration_pitch.hip); 115: ns2_weights_retile; 114: ns2_attention_hd (head dims 32 / 64 / 128), ns2_model_create takes dim_head 32 / 128; 113: ns2_weight_tile_conv3 + ns2_conv3_input_ld (the dedicated FF causal conv kernel, ffconv_kernel.h), ns2_weight_tile_linear (gemm3_kernel.h), ns2_weight_tile_wavenet (wavenet3_kernel.h), ns2_debug_force_gemm(4 / 5); 112: ns2_seanet_resblock_narrow; 111: training entry points take a precision (3 = bf16 x3, 4 = mixed on FMT_H8 lines), ns2_linear_split_as; 110: backward pass (capi_train.cpp: ns2_wgrad, ns2_attention_bwd, ...), ns2_weight_update; 109: ns2_seanet_conv_narrow; 108: ns2_seanet_prep2; 107: ns2_lstm2 (two LSTM layers, one launch); 106: ns2_saturation_peek_async; 105: ns2_lstm_layer takes the scratch size (persistent recurrence); 104: model precision 5 (per-site plan); 103: precision 2 / 4 at op level, caller-owned skinny-linear scratch
+extern "C" int ns2_version(void) { return 123; }   // 123: the RVQ cross-entropy of the training loss: ns2_rvq_ce (+ _workspace_bytes); 122: training of the Aligner: ns2_relu_fwd / _bwd, ns2_align_attn_bwd (+ _workspace_bytes), ns2_align_losses_fwd / _bwd (+ _workspace_bytes); 121: two utterance chains: ns2_debug_force_chains / _chains_last / _chain_rule, ns2_model_profile_end counts logical products; 120: one argument block per Linear / Conv1d product: ns2_linear(ns2_linear_args) replaces ns2_linear_f32 / _split / _split_as / _geglu / _qkv; 119: one argument block per attention direction: ns2_attention_fwd(ns2_attn_args) replaces ns2_attention / _hd / _lse / _lse_masked, ns2_attn_bwd_args carries the mask and dropout of the removed bwd_masked entry; 118: ns2_debug_force_attention, ns2_debug_attention_fast_launches (attn_fast_kernel.h); 117: the range-guard counters register themselves: ns2_saturation_counters / _counter_name / _peek replace ns2_saturation_peek_async / _peek_train_async; 116: ns2_groupnorm_silu, ns2_length_regulate(_totals), ns2_row_dot (duration_pitch.hip); 115: ns2_weights_retile; 114: ns2_attention_hd (head dims 32 / 64 / 128), ns2_model_create takes dim_head 32 / 128; 113: ns2_weight_tile_conv3 + ns2_conv3_input_ld (the dedicated FF causal conv kernel, ffconv_kernel.h), ns2_weight_tile_linear (gemm3_kernel.h), ns2_weight_tile_wavenet (wavenet3_kernel.h), ns2_debug_force_gemm(4 / 5); 112: ns2_seanet_resblock_narrow; 111: training entry points take a precision (3 = bf16 x3, 4 = mixed on FMT_H8 lines), ns2_linear_split_as; 110: backward pass (capi_train.cpp: ns2_wgrad, ns2_attention_bwd, ...), ns2_weight_update; 109: ns2_seanet_conv_narrow; 108: ns2_seanet_prep2; 107: ns2_lstm2 (two LSTM layers, one launch); 106: ns2_saturation_peek_async; 105: ns2_lstm_layer takes the scratch size (persistent recurrence); 104: model precision 5 (per-site plan); 103: precision 2 / 4 at op level, caller-owned skinny-linear scratch
 extern "C" int ns2_debug_force_gemm(int kernel) {
   ARGCHK(kernel >= 0 && kernel <= 5, "ns2_debug_force_gemm: 0 auto, 1 = 128x128 kernel, 2 = 256x256 kernel, 3 = auto without split-K, 4 = auto without the dedicated kernels (FF conv, lean linear, lean Wavenet), 5 = auto without split-K, the dedicated kernels whenever eligible");
   force_gemm_kernel(kernel);

@@ -366,3 +366,20 @@ extern "C" int ns2_align_losses_bwd(const float* aln_log, const float* hard, con
   HIPRET(launch_align_losses_bwd(aln_log, hard, text_lens, mel_lens, g_fs, g_bin, B, T, n, blank_logprob, d_log, workspace, (hipStream_t)stream));
   return NS2_OK;
 }
+
+// ---- the RVQ cross-entropy term of the training loss (rvq_ce.hip)
+extern "C" int64_t ns2_rvq_ce_workspace_bytes(int M, int Q, int want_quantized) {
+  if (M <= 0 || Q <= 0) return 0;
+  return want_quantized ? (int64_t)M * Q * (int64_t)sizeof(int64_t) : 0;
+}
+extern "C" int ns2_rvq_ce(const float* x, const float* codebooks, const float* cb_norm, const int64_t* indices, float* row_loss, float* loss,
+                          float* quantized_out, float* grad, int M, int Q, int C, int D, void* workspace, int64_t workspace_bytes, void* stream) {
+  ARGCHK(x && codebooks && cb_norm && indices && row_loss && loss, "ns2_rvq_ce: null pointer");
+  ARGCHK(M > 0 && Q > 0 && C > 0, "ns2_rvq_ce: M, Q and C must be positive");
+  ARGCHK(D == 128 && C % 64 == 0, "ns2_rvq_ce: needs codebook_dim 128 and codebook_size % 64 == 0 (EnCodec: 128 / 1024)");
+  ARGCHK(!quantized_out || (workspace && workspace_bytes >= ns2_rvq_ce_workspace_bytes(M, Q, 1)),
+         "ns2_rvq_ce: quantized_out needs a workspace (ns2_rvq_ce_workspace_bytes)");
+  RvqCeArgs a{x, codebooks, cb_norm, indices, row_loss, loss, quantized_out ? (int64_t*)workspace : nullptr, quantized_out, grad, M, Q, C, D};
+  HIPRET(launch_rvq_ce(a, (hipStream_t)stream));
+  return NS2_OK;
+}

@@ -258,6 +258,22 @@ hipError_t launch_rvq_encode(const RvqArgs& a, hipStream_t s);
 hipError_t launch_rvq_decode(const int64_t* codes, const float* codebooks, float* emb, int M, int Q, int C, int D,
                              hipStream_t s);
 
+// RVQ cross-entropy of the training loss (rvq_ce.hip; NS2:1668-1684): row losses, their fixed-order mean, and optionally the sum of the
+// nearest codes and the unit gradient G = d loss / d x, all from one walk over the codebooks
+struct RvqCeArgs {
+  const float* x;            // [M, D] rows (the predicted x_start)
+  const float* codebooks;    // [Q, C, D]
+  const float* cb_norm;      // [Q, C] 0.5*|e|^2 (from launch_rvq_prepare)
+  const int64_t* targets;    // [M, Q] the codec's own codes; outside [0, C): that row's loss (and row of G) is NaN
+  float* row_loss;           // [M, Q] lse_c(-dist) + dist_target
+  float* loss;               // [1] sum_q mean_m row_loss
+  int64_t* nearest;          // [M, Q] nearest code per stage (null unless quantized_out is wanted)
+  float* quantized_out;      // [M, D] 0 + E_0[nearest_0] + E_1[nearest_1] + ... (may be null)
+  float* grad;               // [M, D] G, already divided by M (may be null: no second sweep)
+  int M, Q, C, D;
+};
+hipError_t launch_rvq_ce(const RvqCeArgs& a, hipStream_t s);
+
 // ---------------------------------------------------------------------------------------------- backward pass (backward.hip)
 // fp32 [M, C] (xf) or operand planes (in_hi / in_lo, interleaved bf16 hi/lo) -> row planes and / or TRANSPOSED planes
 // T[c][m] (the operands of the weight-gradient GEMMs and of the attention backward), optionally shifted along the token axis

@@ -87,7 +87,8 @@ class NaturalSpeech2(nn.Module):
                  build_aligner: bool = False,          # not in the reference: build the Aligner (forward(text=..., mel=..., pitch=...))
                  encoder_train_backend="composite",    # not in the reference: "hip" trains phoneme_enc / prompt_enc on the HIP kernels (training/encoder_pass.py)
                  duration_pitch_train_backend="composite",    # not in the reference: "hip" trains the DurationPitchPredictor on them (training/duration_pitch_pass.py)
-                 aligner_train_backend="composite"):   # not in the reference: "hip" trains the Aligner and runs its two losses on them (training/aligner_pass.py)
+                 aligner_train_backend="composite",    # not in the reference: "hip" trains the Aligner and runs its two losses on them (training/aligner_pass.py)
+                 rvq_ce_backend=None):                 # not in the reference: "composite" / "hip" sets codec.rq.backend, the RVQ cross-entropy term (csrc/rvq_ce.hip); None leaves the codec's own
         super().__init__()
         assert _is_denoiser(model), "model must be a Model (this package's, or compat.HipBackedModel over the reference's class)"
         self.conditional = model.condition_on_prompt
@@ -139,6 +140,10 @@ class NaturalSpeech2(nn.Module):
         self.train_prob_self_cond = train_prob_self_cond
         self.min_snr_loss_weight, self.min_snr_gamma = min_snr_loss_weight, min_snr_gamma
         self.rvq_cross_entropy_loss_weight = rvq_cross_entropy_loss_weight
+        if rvq_ce_backend is not None:
+            assert codec is not None and hasattr(codec, "rq") and hasattr(codec.rq, "backend"), "rvq_ce_backend needs a codec whose rq has a backend (codec.py)"
+            assert rvq_ce_backend in ("composite", "hip"), "rvq_ce_backend must be 'composite' or 'hip'"
+            codec.rq.backend = rvq_ce_backend
         self.duration_loss_weight, self.pitch_loss_weight, self.aligner_loss_weight = \
             duration_loss_weight, pitch_loss_weight, aligner_loss_weight
 

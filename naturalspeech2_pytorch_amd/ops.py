@@ -445,6 +445,29 @@ def rvq_decode(codes: torch.Tensor, codebooks: torch.Tensor) -> torch.Tensor:
     return emb
 
 
+def rvq_cross_entropy(x: torch.Tensor, codebooks: torch.Tensor, cb_norm: Optional[torch.Tensor], indices: torch.Tensor, need_grad: bool,
+                       need_quantized: bool = True):
+    """the RVQ cross-entropy of the training loss in one launch (ns2_rvq_ce, csrc/rvq_ce.hip): x [M, 128] fp32, codebooks [Q, C, 128],
+    indices [M, Q] int64 -> (loss 0-dim, row_loss [M, Q], quantized_out [M, 128] or None, G [M, 128] = d loss / d x or None).
+    An index outside [0, C) gives a NaN loss; nothing is read back to the host."""
+    x, cb = _f32(x), _f32(codebooks)
+    M, D = x.shape
+    Q, C, _ = cb.shape
+    assert indices.dtype == torch.int64 and tuple(indices.shape) == (M, Q), "indices must be int64 [M, Q]"
+    idx = indices if indices.is_contiguous() else indices.contiguous()
+    cb_norm = rvq_prepare(cb) if cb_norm is None else cb_norm
+    lib = _lib.load()
+    row_loss = torch.empty(M, Q, dtype=torch.float32, device=x.device)
+    loss = torch.empty(1, dtype=torch.float32, device=x.device)
+    quant = torch.empty(M, D, dtype=torch.float32, device=x.device) if need_quantized else None
+    grad = torch.empty(M, D, dtype=torch.float32, device=x.device) if need_grad else None
+    nbytes = lib.ns2_rvq_ce_workspace_bytes(M, Q, int(need_quantized))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device) if nbytes else None
+    check(lib.ns2_rvq_ce(x.data_ptr(), cb.data_ptr(), cb_norm.data_ptr(), idx.data_ptr(), row_loss.data_ptr(), loss.data_ptr(), _p(quant),
+                         _p(grad), M, Q, C, D, _p(ws), nbytes, _stream()), "ns2_rvq_ce")
+    return loss[0], row_loss, quant, grad
+
+
 # ---- Aligner and the text-conditioned training pass (csrc/aligner.hip).  Lengths are int32 [B] device tensors.
 def _lens(t: torch.Tensor) -> torch.Tensor:
     assert t.is_cuda and t.dim() == 1, "lengths are [B] CUDA tensors"

@@ -32,7 +32,8 @@ key-padding mask and dropout in the attention forward / backward (csrc/dropout_k
 convolutions, `SiluFn`, `EmbeddingFn`; exact arithmetic only (DESIGN.md §9).  The `DurationPitchPredictor` (`train_backend="hip"`;
 NS2:344-527) adds `GroupNormSiluFn`, `RowDotReluFn` and the `resid` operand of `AttnFn`: `duration_pitch_forward_train`.  The `Aligner`
 (`train_backend="hip"`; aligner.py) adds `ReluFn` and `AlignAttnFn`: `aligner_forward_train` (aligner_pass.py); its two losses are
-Functions of their own in aligner.py (`ForwardSumLoss` / `BinLoss` with `backend="hip"`).
+Functions of their own in aligner.py (`ForwardSumLoss` / `BinLoss` with `backend="hip"`).  The RVQ cross-entropy term of the loss
+(`codec.rq`, `ResidualVQCrossEntropy(backend="hip")`; NS2:1668-1684) is `RvqCrossEntropyFn`: one launch, fp32 under either arithmetic.
 
 `Backend` is the seam the CPU tests use: `tests/emu_backend.py` restates every backend call with plain torch ops on CPU, so the
 chain rule, tap flips, shifts and layouts of THIS package are checked against torch autograd without a GPU; the kernels behind
@@ -50,9 +51,9 @@ from .duration_pitch_pass import duration_pitch_forward_train, duration_pitch_un
 from .encoder_pass import (encoder_unsupported_reason, phoneme_encoder_forward_train, speech_prompt_encoder_forward_train,
                            transformer_forward_train)
 from .graph import GraphedTrainStep
-from .model_pass import available, model_forward_train, unsupported_reason
+from .model_pass import available, model_forward_train, rvq_ce_unsupported_reason, unsupported_reason
 from .passes import TRAIN_PRECISIONS, backend, set_backend, weights_unchanged
 
 __all__ = ["HipBackend", "TPlanes", "aligner_forward_train", "aligner_unsupported_reason", "duration_pitch_forward_train", "duration_pitch_unsupported_reason", "encoder_unsupported_reason", "phoneme_encoder_forward_train", "speech_prompt_encoder_forward_train",
-           "transformer_forward_train", "GraphedTrainStep", "available", "model_forward_train", "unsupported_reason", "TRAIN_PRECISIONS",
+           "transformer_forward_train", "GraphedTrainStep", "available", "model_forward_train", "rvq_ce_unsupported_reason", "unsupported_reason", "TRAIN_PRECISIONS",
            "backend", "set_backend", "weights_unchanged"]

@@ -156,6 +156,13 @@ class HipBackend:
                                             d_log.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "ns2_align_losses_bwd")
         return d_log
 
+    # ---- the RVQ cross-entropy term of the training loss (codec.py ResidualVQCrossEntropy; csrc/rvq_ce.hip)
+    def rvq_cross_entropy(self, x, codebooks, cb_norm, indices, need_grad=True):
+        """x [M, 128] fp32, indices [M, Q] int64 -> (loss 0-dim, quantized_out [M, 128], G [M, 128] = d loss / d x or None); fp32 whatever
+        the arithmetic of the pass"""
+        loss, _, quant, G = ops.rvq_cross_entropy(x, codebooks, cb_norm, indices, need_grad)
+        return loss, quant, G
+
     def embedding(self, ids, table, pad_id):
         return ops.embedding(ids, table, pad_id)
 

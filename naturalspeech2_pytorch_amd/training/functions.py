@@ -415,6 +415,26 @@ class AlignAttnFn(torch.autograd.Function):
         return dq, dk, None, None
 
 
+class RvqCrossEntropyFn(torch.autograd.Function):
+    """the RVQ cross-entropy term of the training loss (NS2:1668-1684; codec.py `ResidualVQCrossEntropy`): x [M, 128] fp32, codebooks [Q, C, 128]
+    and their half-norms [Q, C], indices [M, Q] int64 -> (loss 0-dim, quantized_out [M, 128]).  One launch (ns2_rvq_ce) computes the loss and
+    the unit gradient G = d loss / d x, the only tensor kept; the backward is grad_out * G.  The codebooks are buffers and the indices
+    integers: neither gets a gradient; quantized_out is a sum of (detached) codes."""
+
+    @staticmethod
+    def forward(ctx, x, codebooks, cb_norm, indices):
+        bk = _begin(ctx)
+        loss, quant, G = bk.rvq_cross_entropy(x, codebooks, cb_norm, indices, need_grad=ctx.needs_input_grad[0])
+        ctx.save_for_backward(G)
+        ctx.mark_non_differentiable(quant)
+        return loss, quant
+
+    @staticmethod
+    def backward(ctx, g_loss, _g_quant):
+        G, = ctx.saved_tensors
+        return (g_loss * G if G is not None else None), None, None, None
+
+
 class GroupNormSiluFn(torch.autograd.Function):
     """silu(GroupNorm(x)) (+ resid) over the rows of utterances of `seq_len` tokens: a Block of the DurationPitchPredictor's ResnetBlock, the
     last one with the ResnetBlock's input as `resid` (NS2:346-400).  The backward normalises with the forward's own statistics slots."""

@@ -145,3 +145,20 @@ def unsupported_reason(m):
         if p.dtype != torch.float32:
             return f"parameter {name} is {p.dtype} (fp32 master weights are required)"
     return None
+
+
+def rvq_ce_unsupported_reason(rq, x, indices):
+    """None when `codec.rq` with `backend="hip"` (codec.py `ResidualVQCrossEntropy`) can run these tensors on ns2_rvq_ce, else why not: the
+    caller falls back to the composite, as `Model`, the encoders, the predictor and the aligner do.  Checks metadata only: no host read."""
+    if not (x.is_cuda and indices.is_cuda):
+        return "CPU tensors (the kernel runs on the GPU)"
+    if x.dtype != torch.float32:
+        return f"x is {x.dtype} (the kernel is fp32)"
+    if indices.dtype != torch.int64:
+        return f"indices are {indices.dtype} (the kernel reads int64 codes, what the codec returns)"
+    from .. import _lib
+    try:
+        _lib.load()
+    except (_lib.Ns2Error, OSError) as e:
+        return f"no library ({e})"
+    return None
