@@ -13,7 +13,8 @@
 //     branch; 0 x w = 0 exactly) -- no zero page, no per-lane test at issue time;
 //   * the K loops are unrolled so that stage parity AND tap are immediates (6 tile bodies per iteration).
 // Summation order per accumulator = the old kernel's (chunk-major, tap-minor, k chunks in order; then the res-conv tiles): results are
-// bit-identical.  Mid-gate and epilogue: gemm_epi.h / gemm_epi_dispatch.h, untouched.
+// bit-identical.  The gate between the phases is the kernel's own (midgate below: full tiles inside one utterance, no tests, packed fp32:
+// 9.6 -> 4.3 us of a 91 us workgroup, profiles/wavenet_gate_share.txt); epilogue: gemm_epi_dispatch.h, untouched.
 #pragma once
 #include "gemm3_kernel.h"
 
@@ -109,6 +110,42 @@ template <int S, int TAP, bool R1, bool R2, bool R1P, bool R2P> NS2_DEVINL void 
   c.sW0 += REGION; c.sW1 += REGION;
 }
 
+// The gate's per-column parameters of this lane's two columns (bias, FiLM gamma / beta, the res conv's bias).  A 256-row tile lies inside
+// one utterance (wavenet3_eligible), so the FiLM row is the workgroup's.  Loaded in front of phase 1 and held across it (eight VGPRs; the
+// kernel stays at 252 without scratch): loaded at the gate they cost it an exposed L2 round trip.
+struct Gate { float bc[2], gam[2], bet[2], b2[2]; };
+
+// wavenet_midgate (gemm_epi.h) for this kernel's tiles: full, inside one utterance -- no column or row test, no row / seq_len.  Per value
+// the same operations in the same order, so the same bits: fma(acc + bc, gam, bet); u = exp2(-log2e |h|); (1 - u) * (h < 0 ? u : 1) *
+// rcp(fma(u, u, 1)); copysign; + b2 -- the full-rate ones on register pairs (v_pk_add / fma / mul_f32 round each half as the scalar
+// forms do).  One accumulator tile at a time: the scheduler may not pool the 128 values (gemm_epi.h on what a straight-line gate costs).
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+NS2_DEVINL void midgate(f32x16 (&acc)[4][2], const Gate& p) {
+  const f32x2 one = {1.f, 1.f};
+#pragma unroll
+  for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+    for (int ni = 0; ni < 2; ++ni) {
+      const f32x2 bc = {p.bc[ni], p.bc[ni]}, gam = {p.gam[ni], p.gam[ni]}, bet = {p.bet[ni], p.bet[ni]}, b2 = {p.b2[ni], p.b2[ni]};
+#pragma unroll
+      for (int r = 0; r < 16; r += 2) {
+        const f32x2 a = {acc[mi][ni][r], acc[mi][ni][r + 1]};
+        const f32x2 h = __builtin_elementwise_fma(a + bc, gam, bet);
+        const f32x2 u = {__builtin_amdgcn_exp2f(-1.4426950408889634f * fabsf(h.x)), __builtin_amdgcn_exp2f(-1.4426950408889634f * fabsf(h.y))};
+        const f32x2 d = __builtin_elementwise_fma(u, u, one);
+        const f32x2 rc = {__builtin_amdgcn_rcpf(d.x), __builtin_amdgcn_rcpf(d.y)};
+        const f32x2 sel = {h.x < 0.f ? u.x : 1.f, h.y < 0.f ? u.y : 1.f};
+        const f32x2 t = (one - u) * sel * rc;
+        const f32x2 v = f32x2{copysignf(t.x, h.x), copysignf(t.y, h.y)} + b2;
+        acc[mi][ni][r] = v.x; acc[mi][ni][r + 1] = v.y;
+      }
+      // the gated tile exists HERE: a register-only computation is otherwise free to sink below the inline-assembly requests, wait and
+      // barrier of phase 2's prologue, to its first use (the first MFMA).  The gate stays where the record measured it.
+      asm volatile("" : "+v"(acc[mi][ni]));
+      __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
 NS2_DEVINL void run(const GemmArgs& g) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -180,6 +217,18 @@ NS2_DEVINL void run(const GemmArgs& g) {
   const int T1 = 3 * C;
   c.sW0 = reinterpret_cast<const unsigned char*>(g.w_tw1) + ((long)z * ntn + tn) * T1 * REGION;
   c.sW1 = c.sW0;
+  // the gate's parameters: requested in front of phase 1, whose loop hides their latency (see Gate)
+  Gate p;
+  {
+    const long zb = (long)z * g.bias_zs;
+    const float* film = g.film + (long)z * g.film_zs + (long)(m0 / g.seq_len) * g.film_ld;
+#pragma unroll
+    for (int ni = 0; ni < 2; ++ni) {
+      const int col = tn * G2_BN + wn * 64 + ni * 32 + l31;
+      p.bc[ni] = g.bias[zb + col]; p.b2[ni] = g.bias2[zb + col];
+      p.gam[ni] = film[col]; p.bet[ni] = film[g.N + col];
+    }
+  }
   // ---- phase 1: prologue (tile 0 = chunk 0 / tap 0 whole, A0 / B0 of tile 1), steady tiles, the last two
   issue_a1<0, 0, 0>(c); mx3::issue_w<0, 0>(c); mx3::issue_w<0, 1>(c); issue_a1<0, 1, 0>(c);
   c.sW0 += REGION;
@@ -198,8 +247,7 @@ NS2_DEVINL void run(const GemmArgs& g) {
   tile1<1, 2, false, false, true, false>(c);
   if (wave < 4) bar();
   // ---- FiLM + gate on the accumulators (NS2:629-636), then phase 2: res_conv on the unshifted rows, mixed arithmetic
-  const int row_base = m0 + wm * 128, col_base = tn * G2_BN + wn * 64;
-  wavenet_midgate<4, 2>(c.acc, g, z, row_base, col_base, l31, hi, (g.seq_len & 127) == 0);
+  midgate(c.acc, p);
   const int T2 = C * 2;
   mx3::setup(c, a_col + (long)m0 * lda_b, reinterpret_cast<const unsigned char*>(g.w_tw2) + ((long)z * ntn + tn) * T2 * REGION, lda_b, wave, lane);
   mx3::kloop(c, T2, wave);
