@@ -1,204 +1,110 @@
-"""ctypes binding of libns2hip.so (C ABI: include/ns2hip.h).
+"""ctypes binding of libns2hip.so, derived from its C ABI: include/ns2hip.h is parsed once, at import.
 
-The HIP library is the product: importing this module FAILS LOUDLY when the shared object is missing or does
-not export the full ABI — there is no CPU / PyTorch fallback for the hot path.
+The HIP library is the product: importing this module FAILS LOUDLY when the header or the shared object is missing or the
+library does not export the full ABI -- there is no CPU / PyTorch fallback for the hot path.
+
+The header is the one owner of the ABI.  Its `#define NS2_<NAME> <int>` lines become the status constants, every
+`typedef struct { ... } name;` a ctypes.Structure, every `ret ns2_name(args);` a row of SIGNATURES.  A new entry point needs
+its declaration there and nothing here.  One mapping rule, and nothing is guessed (what it does not cover raises Ns2Error
+naming the declaration):
+    int -> c_int;  unsigned, unsigned int -> c_uint;  uint32_t -> c_uint32;  int64_t -> c_int64;  float -> c_float;
+    double -> c_double;  a void return -> None;  const char* -> c_char_p;
+    a pointer to a struct whose body the header gives -> POINTER(that class);  a pointer to a pointer -> POINTER(c_void_p);
+    every other pointer (to a scalar, to void, to the opaque ns2_model / ns2_weight) -> c_void_p;
+    a struct field that is a pointer -> c_void_p.
+The header cannot say whether an `int*` is a host out-parameter or device memory (most are device pointers, passed as
+integers), so host out-parameters are c_void_p too: byref(), a ctypes array and None all pass, but ctypes no longer checks
+their element type.  That is the accepted price of having no second, hand-kept table.
 """
 import ctypes
 import os
-from ctypes import c_char_p, c_float, c_int, c_int64, c_void_p, POINTER
+import re
+from ctypes import c_char_p, c_void_p, POINTER
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NS2_LIB", os.path.join(_HERE, "libns2hip.so"))   # NS2_LIB: experiment builds (tools/)
+HEADER_PATH = os.path.join(_HERE, "..", "include", "ns2hip.h")
 
 
 class Ns2Error(RuntimeError):
     pass
 
 
-class ModelConfig(ctypes.Structure):
-    _fields_ = [(n, c_int) for n in (
-        "dim", "depth", "dim_head", "heads", "ff_mult", "wavenet_layers", "wavenet_stacks", "dim_cond_mult",
-        "condition_on_prompt", "dim_prompt", "num_latents_m", "resampler_depth", "precision")]
+_SCALARS = {"int": ctypes.c_int, "unsigned": ctypes.c_uint, "unsigned int": ctypes.c_uint, "uint32_t": ctypes.c_uint32,
+            "int64_t": ctypes.c_int64, "float": ctypes.c_float, "double": ctypes.c_double}
 
 
-P = c_void_p
-I = c_int
-F = c_float
-L = c_int64
+def _ctype(ctype, structs, decl, field=False):
+    """the ctypes type of the C type `ctype` (declarator name removed) by the module's rule; an Ns2Error naming `decl` if it has none"""
+    stars = ctype.count("*")
+    base = " ".join(w for w in ctype.replace("*", " ").split() if w != "const")
+    if stars == 0 and base in _SCALARS:
+        return _SCALARS[base]
+    if stars not in (1, 2) or not re.fullmatch(r"\w+( \w+)?", base):
+        raise Ns2Error(f"include/ns2hip.h: no ctypes mapping for `{ctype.strip()}` in `{decl}`")
+    if field:
+        return c_void_p
+    if stars == 2:
+        return POINTER(c_void_p)
+    if base == "char" and "const" in ctype.split():
+        return c_char_p
+    return POINTER(structs[base]) if base in structs else c_void_p
 
 
-class LinearArgs(ctypes.Structure):
-    """ns2_linear_args (include/ns2hip.h), field for field"""
-    _fields_ = [("w", P), ("a_hi", P), ("a_lo", P), ("lda", I), ("M", I), ("precision", I),
-                ("conv_taps", I), ("dilation", I), ("seq_len", I), ("pad_left", I),
-                ("bias", P), ("act", I),
-                ("out_f32", P), ("ldo_f", I), ("resid", P), ("ldr", I),
-                ("out_hi", P), ("out_lo", P), ("ldo", I), ("out_precision", I),
-                ("split_col", I), ("vt_hi", P), ("vt_lo", P), ("vt_ld", I)]
+def _declarator(text, decl):
+    """`type name` -> (type, name)"""
+    m = re.fullmatch(r"([\w\s*]*[\s*])(\w+)", text.strip())
+    if not m:
+        raise Ns2Error(f"include/ns2hip.h: cannot read `{text.strip()}` in `{decl}`")
+    return m.group(1), m.group(2)
 
 
-class AttnArgs(ctypes.Structure):
-    """ns2_attn_args (include/ns2hip.h), field for field"""
-    _fields_ = [("q_hi", P), ("q_lo", P), ("ldq", I), ("q_col0", I),
-                ("k_hi", P), ("k_lo", P), ("ldk", I), ("k_col0", I),
-                ("vt_hi", P), ("vt_lo", P), ("vt_ld", I),
-                ("o_hi", P), ("o_lo", P), ("ldo", I),
-                ("B", I), ("H", I), ("Nq", I), ("Nk", I), ("scale", F),
-                ("head_dim", I), ("precision", I), ("o_precision", I),
-                ("key_mask", P),
-                ("lse", P),
-                ("dropout_p", F), ("dropout_seed", P), ("dropout_call", ctypes.c_uint)]
+def parse_header(text):
+    """(constants, structs, signatures) of a header text: {NS2_NAME: int}, {typedef name: ctypes.Structure subclass},
+    {ns2_name: (restype, argtypes)}.  Plain `re`, no C front end; every statement is one of the three forms or an Ns2Error."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    consts = {}
+    for name, value in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(NS2_\w+)[ \t]+(.*?)[ \t]*$", text, flags=re.M):
+        if not re.fullmatch(r"-?\d+", value):
+            raise Ns2Error(f"include/ns2hip.h: `#define {name} {value}` is not an integer")
+        consts[name] = int(value)
+    text = re.sub(r"^[ \t]*#ifdef __cplusplus\n.*?\n[ \t]*#endif[^\n]*$", " ", text, flags=re.S | re.M)   # extern "C" { / }
+    text = re.sub(r"^[ \t]*#[^\n]*$", " ", text, flags=re.M)
+    structs = {}
+
+    def struct(m):
+        name, fields = m.group(2), []
+        for decl in filter(None, (" ".join(d.split()) for d in m.group(1).split(";"))):
+            first, *more = decl.split(",")                      # `int ldq, q_col0;`: the type belongs to every declarator
+            ctype, field = _declarator(first, f"{name}: {decl}")
+            if more and ("*" in decl or not all(f.strip().isidentifier() for f in more)):
+                raise Ns2Error(f"include/ns2hip.h: cannot read `{decl}` in `{name}`")
+            ct = _ctype(ctype, structs, f"{name}: {decl}", field=True)
+            fields += [(f.strip(), ct) for f in [field] + more]
+        structs[name] = type(name, (ctypes.Structure,), {"_fields_": fields, "__doc__": f"{name} (include/ns2hip.h)"})
+        return " "
+    text = re.sub(r"\btypedef\s+struct\s*\{([^{}]*)\}\s*(\w+)\s*;", struct, text)
+    sigs = {}
+    for decl in filter(None, (" ".join(d.split()) for d in text.split(";"))):
+        if re.fullmatch(r"typedef struct (\w+) \1", decl):       # an opaque handle: its pointers are c_void_p
+            continue
+        m = re.fullmatch(r"([\w\s*]+?)\b(ns2_\w+) ?\(([^()]*)\)", decl)
+        if not m:
+            raise Ns2Error(f"include/ns2hip.h: cannot read `{decl}`")
+        ret, name, args = m.group(1).strip(), m.group(2), m.group(3).strip()
+        args = [] if args == "void" else [_ctype(_declarator(a, decl)[0], structs, decl) for a in args.split(",")]
+        sigs[name] = (None if ret == "void" else _ctype(ret, structs, decl), args)
+    return consts, structs, sigs
 
 
-class AttnBwdArgs(ctypes.Structure):
-    """ns2_attn_bwd_args (include/ns2hip.h), field for field"""
-    _fields_ = [("q_hi", P), ("q_lo", P), ("ldq", I), ("q_col0", I),
-                ("k_hi", P), ("k_lo", P), ("ldk", I), ("k_col0", I),
-                ("v_hi", P), ("v_lo", P), ("ldv", I), ("v_col0", I),
-                ("do_hi", P), ("do_lo", P), ("lddo", I),
-                ("lse", P), ("delta", P),
-                ("dq", P), ("lddq", I), ("dq_col0", I),
-                ("dk", P), ("lddk", I), ("dk_col0", I),
-                ("dv", P), ("lddv", I), ("dv_col0", I),
-                ("B", I), ("H", I), ("Nq", I), ("Nk", I), ("scale", F),
-                ("gp_hi", P), ("gp_lo", P), ("gp_ld", I), ("gp_precision", I), ("gp_q", I), ("gp_kv", I),
-                ("key_mask", P), ("dropout_p", F), ("dropout_seed", P), ("dropout_call", ctypes.c_uint)]
-
-
-class RepackPart(ctypes.Structure):
-    """ns2_repack_part (include/ns2hip.h), field for field"""
-    _fields_ = [("w", P), ("src", P), ("sr", L), ("sc", L), ("st", L), ("row0", I), ("rows", I), ("col0", I), ("cols", I)]
-
-
-# name -> (restype, argtypes); mirrors include/ns2hip.h line by line
-SIGNATURES = {
-    "ns2_last_error": (c_char_p, []),
-    "ns2_version": (I, []),
-    "ns2_debug_force_gemm": (I, [I]),
-    "ns2_debug_force_attention": (I, [I]),
-    "ns2_debug_attention_fast_launches": (L, []),
-    "ns2_debug_force_chains": (I, [I]),
-    "ns2_debug_chains_last": (I, []),
-    "ns2_debug_chain_rule": (I, [POINTER(ModelConfig), I, I, POINTER(c_int)]),
-    "ns2_splitk_scratch_bytes": (L, []),
-    "ns2_debug_splitk_plan": (I, [I, I, I, I, I, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
-    "ns2_debug_lend_splitk_scratch": (I, [P, L]),
-    "ns2_weight_pack": (I, [P, I, I, I, I, P, I, POINTER(c_void_p), P]),
-    "ns2_weight_free": (None, [P]),
-    "ns2_split_f32": (I, [P, I, I, I, P, P, I, I, P]),
-    "ns2_join_f32": (I, [P, P, I, P, I, L, I, I, P]),
-    "ns2_linear": (I, [POINTER(LinearArgs), P]),
-    "ns2_geglu_pack_bias": (I, [P, I, P, I, P]),
-    "ns2_wavenet_block": (I, [P, P, P, I, I, I, I, P, P, P, I, P, P, I, I, P]),
-    "ns2_attention_fwd": (I, [POINTER(AttnArgs), P]),
-    "ns2_rmsnorm": (I, [P, I, I, I, I, P, P, I, P, P, I, P, I, I, P]),
-    "ns2_skinny_linear_workspace_bytes": (L, [I, I, I]),
-    "ns2_skinny_linear": (I, [P, I, P, P, P, I, I, I, I, I, P, L, P]),
-    "ns2_time_embed": (I, [P, P, P, P, P, P, I, I, I, I, P, L, P]),
-    "ns2_transpose_f32": (I, [P, I, I, I, P, P]),
-    "ns2_embedding": (I, [P, P, P, L, I, L, P]),
-    "ns2_groupnorm_workspace_bytes": (L, [I, I, I, I]),
-    "ns2_groupnorm_silu": (I, [P, I, I, I, I, P, P, F, P, P, P, P, I, I, P, L, P]),
-    "ns2_length_regulate_totals": (I, [P, I, I, P, P]),
-    "ns2_length_regulate": (I, [P, P, P, P, I, I, I, I, F, F, P, P]),
-    "ns2_row_dot": (I, [P, I, I, I, P, P, I, P, P]),
-    "ns2_relu_split": (I, [P, I, I, P, P, I, I, P]),
-    "ns2_align_attn": (I, [P, P, P, I, I, I, I, P, P, P]),
-    "ns2_maximum_path_workspace_bytes": (L, [I, I, I]),
-    "ns2_maximum_path": (I, [P, P, P, I, I, I, P, P, P, L, P]),
-    "ns2_average_over_durations": (I, [P, P, I, I, I, P, P]),
-    "ns2_expand_backward_workspace_bytes": (L, [I, I]),
-    "ns2_expand_backward": (I, [P, P, P, I, I, I, I, I, F, F, P, P, P, L, P]),
-    "ns2_audio_to_mel": (I, [P, I, L, I, I, P, P, P, P, I, I, I, I, P, P]),
-    "ns2_ddim_step": (I, [P, P, P, P, P, I, L, I, I, F, P]),
-    "ns2_cfg_mix": (I, [P, P, P, L, F, P]),
-    "ns2_seanet_prep": (I, [P, I, I, P, I, I, L, I, I, I, I, P, P, I, I, P]),
-    "ns2_seanet_prep2": (I, [P, I, I, I, L, I, I, P, P, I, I, I, P, P, I, I, I, I, P]),
-    "ns2_seanet_conv_narrow": (I, [P, L, I, I, L, I, I, I, I, P, P, P, L, P]),
-    "ns2_seanet_resblock_narrow": (I, [P, L, I, I, L, I, P, P, P, P, P, P, L, P]),
-    "ns2_seanet_unpad": (I, [P, L, I, P, L, I, L, I, P]),
-    "ns2_lstm_state_floats": (L, [I, I]),
-    "ns2_lstm_layer": (I, [P, L, P, P, P, L, P, L, P, L, I, L, I, P]),
-    "ns2_lstm2_state_floats": (L, []),
-    "ns2_lstm2": (I, [P, L, P, P, P, P, P, P, P, L, P, L, P, L, I, L, P]),
-    "ns2_lstm_abort_count": (I, [I, POINTER(c_int64)]),
-    "ns2_debug_lstm_inject_abort": (I, [I]),
-    "ns2_saturation_count": (I, [I, POINTER(c_int64)]),
-    "ns2_saturation_counters": (I, []),
-    "ns2_saturation_counter_name": (c_char_p, [I]),
-    "ns2_saturation_peek": (I, [P, I, P]),
-    "ns2_rvq_prepare": (I, [P, P, I, I, I, P]),
-    "ns2_rvq_encode": (I, [P, P, P, P, P, P, P, I, I, I, I, F, P]),
-    "ns2_rvq_decode": (I, [P, P, P, I, I, I, I, P]),
-    "ns2_model_create": (I, [POINTER(ModelConfig), POINTER(c_void_p)]),
-    "ns2_model_set_param": (I, [P, c_char_p, P, I, POINTER(c_int64)]),
-    "ns2_model_finalize": (I, [P, P]),
-    "ns2_model_workspace_bytes": (L, [P, I, I, I, I]),
-    "ns2_model_cond_bytes": (L, [P, I, I, I, I]),
-    "ns2_model_prepare_cond": (I, [P, P, I, P, I, I, I, I, P, P, L, P]),
-    "ns2_model_cond_stack": (I, [P, P, P, I, I, I, P, P]),
-    "ns2_model_forward": (I, [P, P, P, P, I, P, I, I, P, L, P]),
-    "ns2_model_table_cols": (I, [P]),
-    "ns2_model_time_table_workspace_bytes": (L, [P, I]),
-    "ns2_model_time_table": (I, [P, P, I, I, P, P, L, P]),
-    "ns2_model_forward_row": (I, [P, P, P, P, I, P, I, I, P, L, P]),
-    "ns2_model_param_count": (I, [P]),
-    "ns2_model_param_checksum": (I, [P, P, I, P]),
-    "ns2_model_debug_tap": (I, [P, c_char_p, P, L]),
-    "ns2_model_profile_begin": (I, [P, ctypes.c_uint]),
-    "ns2_model_profile_end": (I, [P, POINTER(ctypes.c_double), POINTER(c_int64)]),
-    "ns2_model_destroy": (None, [P]),
-    # ---- training: the backward pass
-    "ns2_weight_update": (I, [P, P, P, P]),
-    "ns2_weight_tile_conv3": (I, [P, P]),
-    "ns2_weight_tile_linear": (I, [P, P]),
-    "ns2_weight_tile_wavenet": (I, [P, P]),
-    "ns2_conv3_input_ld": (I, [I]),
-    "ns2_grad_prep_slices": (L, [I, L]),
-    "ns2_grad_prep": (I, [P, L, I, I, I, I, P, P, I, P, P, L, I, I, P, I, P]),
-    "ns2_planes_transpose": (I, [P, P, I, I, I, I, I, I, P, P, L, I, I, I, P]),
-    "ns2_reduce_slices": (I, [P, L, I, L, P, I, P]),
-    "ns2_weights_repack_table_bytes": (L, [I]),
-    "ns2_weights_repack_build": (I, [P, I, P, L, POINTER(c_int64), P]),
-    "ns2_weights_repack": (I, [P, I, L, P]),
-    "ns2_weights_retile": (I, [P, I, P]),
-    "ns2_wgrad_workspace_bytes": (L, [I, I, L]),
-    "ns2_wgrad": (I, [P, P, P, P, L, I, I, I, I, P, P, L, I, P]),
-    "ns2_wgrad_rows_preferred": (I, [I, I, L]),
-    "ns2_wgrad_rows": (I, [P, P, I, P, P, I, L, I, I, I, I, I, I, P, P, L, I, P]),
-    "ns2_film_gate_fwd": (I, [P, L, P, I, I, L, I, P, L, P]),
-    "ns2_film_gate_slices": (I, [I]),
-    "ns2_film_gate_bwd": (I, [P, L, P, L, P, I, I, I, I, P, L, P, P]),
-    "ns2_geglu_fwd": (I, [P, L, L, I, P, P, I, I, P]),
-    "ns2_geglu_bwd": (I, [P, L, P, L, L, I, P, L, P]),
-    "ns2_rmsnorm_bwd_slices": (I, [I]),
-    "ns2_rmsnorm_bwd": (I, [P, L, P, L, P, P, I, I, I, I, P, P, L, P, P, P]),
-    "ns2_attention_delta": (I, [P, L, P, P, I, I, I, I, P, I, P]),
-    "ns2_attention_bwd": (I, [POINTER(AttnBwdArgs), P]),
-    # ---- training of the conditioning encoders
-    "ns2_dropout_keep_mask": (I, [P, ctypes.c_uint, F, I, I, I, I, P, P]),
-    "ns2_silu_fwd": (I, [P, L, L, I, P, L, P]),
-    "ns2_silu_bwd": (I, [P, L, P, L, L, I, P, L, P]),
-    "ns2_embedding_bwd": (I, [P, L, I, P, L, I, I, P, P]),
-    # ---- training of the DurationPitchPredictor
-    "ns2_groupnorm_silu_bwd_workspace_bytes": (L, [I, I, I]),
-    "ns2_groupnorm_silu_bwd": (I, [P, L, P, I, I, I, I, P, P, F, P, L, P, P, P, L, P]),
-    "ns2_row_dot_relu_bwd_workspace_bytes": (L, [L, I]),
-    "ns2_row_dot_relu_bwd": (I, [P, P, P, L, P, L, I, P, L, P, P, L, P]),
-    # ---- training of the Aligner
-    "ns2_relu_fwd": (I, [P, L, L, I, P, L, P]),
-    "ns2_relu_bwd": (I, [P, L, P, L, L, I, P, L, P]),
-    "ns2_align_attn_bwd_workspace_bytes": (L, [I, I, I, I]),
-    "ns2_align_attn_bwd": (I, [P, P, P, P, P, P, P, I, I, I, I, P, P, P, L, P]),
-    "ns2_align_losses_workspace_bytes": (L, [I, I, I]),
-    "ns2_align_losses_fwd": (I, [P, P, P, P, I, I, I, F, P, P, P, L, P]),
-    "ns2_align_losses_bwd": (I, [P, P, P, P, P, P, I, I, I, F, P, P, L, P]),
-    # ---- the RVQ cross-entropy term of the training loss
-    "ns2_rvq_ce_workspace_bytes": (L, [I, I, I]),
-    "ns2_rvq_ce": (I, [P, P, P, P, P, P, P, P, I, I, I, I, P, L, P]),
-}
-
-NS2_UNAVAILABLE = 1          # include/ns2hip.h: "this fast path does not apply here" (not an error)
+if not os.path.exists(HEADER_PATH):
+    raise Ns2Error(f"{HEADER_PATH} not found: the binding is derived from the header, it ships with the package's source tree")
+with open(HEADER_PATH) as _f:
+    CONSTANTS, STRUCTS, SIGNATURES = parse_header(_f.read())     # SIGNATURES: name -> (restype, argtypes)
+NS2_OK, NS2_ERR_ARG, NS2_ERR_HIP, NS2_ERR_STATE, NS2_UNAVAILABLE = (
+    CONSTANTS[k] for k in ("NS2_OK", "NS2_ERR_ARG", "NS2_ERR_HIP", "NS2_ERR_STATE", "NS2_UNAVAILABLE"))
+ModelConfig, LinearArgs, AttnArgs, AttnBwdArgs, RepackPart = (
+    STRUCTS[k] for k in ("ns2_model_config", "ns2_linear_args", "ns2_attn_args", "ns2_attn_bwd_args", "ns2_repack_part"))
 
 _lib = None
 
@@ -231,6 +137,4 @@ def check(rc, what=""):
 
 def header_symbols():
     """Symbols declared in include/ns2hip.h (used by the CPU test that the .so exports the whole ABI)."""
-    import re
-    hdr = os.path.join(_HERE, "..", "include", "ns2hip.h")
-    return sorted(set(re.findall(r"\b(ns2_[a-z0-9_]+)\(", open(hdr).read())))
+    return sorted(SIGNATURES)

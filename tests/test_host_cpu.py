@@ -2,6 +2,7 @@
 composite against the reference goldens, and the world_size-2 data-parallel path over gloo."""
 import glob
 import os
+import re
 import subprocess
 import sys
 
@@ -19,8 +20,32 @@ GOLD = os.path.join(ROOT, "tests", "golden")
 
 
 def test_library_exports_whole_abi():
+    """_lib derives SIGNATURES, the argument structs and the status constants from include/ns2hip.h, so header and table cannot disagree
+    by construction.  What still binds: the count, the constants, and rows pinned as the hand-written table had them -- one or more per
+    rule of the mapping (_lib's docstring), the long ones included -- so a change of the parser or of the rule shows."""
+    import ctypes
+    from ctypes import POINTER, c_char_p, c_void_p
     lib = _lib.load()                                   # raises if the .so or any symbol is missing
-    assert set(_lib.header_symbols()) == set(_lib.SIGNATURES)
+    assert len(_lib.SIGNATURES) == 119 and _lib.header_symbols() == sorted(_lib.SIGNATURES)
+    assert (_lib.NS2_OK, _lib.NS2_ERR_ARG, _lib.NS2_ERR_HIP, _lib.NS2_ERR_STATE, _lib.NS2_UNAVAILABLE) == (0, -1, -2, -3, 1)
+    P, I, F, L = c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_int64
+    LinearArgs, ModelConfig = _lib.LinearArgs, _lib.ModelConfig
+    pinned = {
+        "ns2_last_error": (c_char_p, []),
+        "ns2_weight_free": (None, [P]),
+        "ns2_splitk_scratch_bytes": (L, []),
+        "ns2_linear": (I, [POINTER(LinearArgs), P]),
+        "ns2_model_create": (I, [POINTER(ModelConfig), POINTER(c_void_p)]),
+        "ns2_dropout_keep_mask": (I, [P, ctypes.c_uint, F, I, I, I, I, P, P]),
+        "ns2_model_profile_begin": (I, [P, ctypes.c_uint]),
+        "ns2_groupnorm_silu": (I, [P, I, I, I, I, P, P, F, P, P, P, P, I, I, P, L, P]),
+        "ns2_grad_prep": (I, [P, L, I, I, I, I, P, P, I, P, P, L, I, I, P, I, P]),
+        "ns2_wgrad_rows": (I, [P, P, I, P, P, I, L, I, I, I, I, I, I, P, P, L, I, P]),
+        "ns2_rvq_ce": (I, [P, P, P, P, P, P, P, P, I, I, I, I, P, L, P]),
+        "ns2_model_set_param": (I, [P, c_char_p, P, I, P]),          # dims: a host int64_t*, c_void_p under the one rule
+    }
+    for name, row in pinned.items():
+        assert _lib.SIGNATURES[name] == row, (name, _lib.SIGNATURES[name])
     assert lib.ns2_version() >= 100
     out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True).stdout
     exported = {l.split()[-1] for l in out.splitlines() if " T ns2_" in l}
@@ -138,6 +163,70 @@ int main(void) {
     assert [int(v) for v in out[4 + len(fwd):4 + len(fwd) + len(bwd)]] == bwd, (out, bwd)
     lin = layout(_lib.LinearArgs, ("a_hi", "lda", "out_f32", "out_precision", "vt_hi", "vt_ld"))
     assert [int(v) for v in out[4 + len(fwd) + len(bwd):]] == lin and len(out) == 4 + len(fwd) + len(bwd) + len(lin), (out, lin)
+
+
+def test_derived_structs_have_the_layout_gcc_gives_every_field(tmp_path):
+    """every field of every struct _lib derived from the header: a C program generated from the parsed field names prints sizeof of
+    the struct and offsetof / sizeof of each field as gcc lays include/ns2hip.h out, and the ctypes classes must say the same (the
+    compiler is the independent witness, not the parser)"""
+    import ctypes
+    import shutil
+    if shutil.which("gcc") is None:
+        pytest.skip("needs gcc")
+    assert sorted(_lib.STRUCTS) == ["ns2_attn_args", "ns2_attn_bwd_args", "ns2_linear_args", "ns2_model_config", "ns2_repack_part"]
+    lines = ["#include <stdio.h>", "#include <stddef.h>", '#include "ns2hip.h"', "int main(void) {"]
+    for name, cls in _lib.STRUCTS.items():
+        lines.append(f'  printf("{name} %d\\n", (int)sizeof({name}));')
+        for f, _ in cls._fields_:
+            lines.append(f'  printf("{name}.{f} %d %d\\n", (int)offsetof({name}, {f}), (int)sizeof((({name}*)0)->{f}));')
+    lines += ["  return 0;", "}", ""]
+    src, exe = tmp_path / "layout.c", tmp_path / "layout"
+    src.write_text("\n".join(lines))
+    subprocess.run(["gcc", "-std=c99", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
+    got = subprocess.run([str(exe)], check=True, capture_output=True, text=True, timeout=60).stdout.splitlines()
+    want = []
+    for name, cls in _lib.STRUCTS.items():
+        want.append(f"{name} {ctypes.sizeof(cls)}")
+        want += [f"{name}.{f} {getattr(cls, f).offset} {getattr(cls, f).size}" for f, _ in cls._fields_]
+    assert got == want and len(want) == 5 + 13 + 24 + 27 + 41 + 9
+
+
+def test_header_parser_maps_by_one_rule_and_refuses_what_it_does_not_cover():
+    """_lib.parse_header on header texts of its own: every rule of the mapping on a small header, and an Ns2Error that names the
+    declaration for what the rule does not cover -- a `long double` parameter, a struct passed by value -- instead of a guess"""
+    import ctypes
+    from ctypes import POINTER, c_char_p, c_void_p
+    good = """
+    /* a comment with a prototype: int ns2_not_this(int x); */
+    #define NS2_SEVEN 7   // trailing comment
+    #define NS2_MINUS -4
+    typedef struct ns2_thing ns2_thing;
+    typedef struct {
+      const float* p; ns2_thing* const* pp; int a, b;   /* multi-declarator */
+      unsigned u; uint32_t w; int64_t l; double d; float f;
+    } ns2_blk;
+    const char* ns2_name(void);
+    void ns2_free(ns2_thing* t);
+    double ns2_all(const ns2_blk* blk, ns2_thing** out, ns2_thing* const* in, unsigned int n, uint32_t w, unsigned m,
+                   int64_t* host_count, const uint16_t* planes, const char* s, char* buf, float x, void* stream);
+    """
+    consts, structs, sigs = _lib.parse_header(good)
+    assert consts == {"NS2_SEVEN": 7, "NS2_MINUS": -4} and list(structs) == ["ns2_blk"]
+    blk = structs["ns2_blk"]
+    assert blk._fields_ == [("p", c_void_p), ("pp", c_void_p), ("a", ctypes.c_int), ("b", ctypes.c_int), ("u", ctypes.c_uint),
+                            ("w", ctypes.c_uint32), ("l", ctypes.c_int64), ("d", ctypes.c_double), ("f", ctypes.c_float)]
+    assert sigs == {"ns2_name": (c_char_p, []), "ns2_free": (None, [c_void_p]),
+                    "ns2_all": (ctypes.c_double, [POINTER(blk), POINTER(c_void_p), POINTER(c_void_p), ctypes.c_uint, ctypes.c_uint32,
+                                                  ctypes.c_uint, c_void_p, c_void_p, c_char_p, c_void_p, ctypes.c_float, c_void_p])}
+    for bad, named in (("int ns2_wide(int n, long double x);", "ns2_wide"),
+                       ("typedef struct { int a; } ns2_blk;\nint ns2_by_value(ns2_blk blk, void* stream);", "ns2_by_value"),
+                       ("long ns2_ret(void);", "ns2_ret"),
+                       ("typedef struct { int a; char tag[4]; } ns2_arr;", "tag[4]"),
+                       ("typedef struct { int *a, *b; } ns2_stars;", "int *a, *b"),
+                       ("int ns2_cb(void (*fn)(int));", "ns2_cb"),
+                       ("#define NS2_WORD sizeof(int)", "NS2_WORD")):
+        with pytest.raises(_lib.Ns2Error, match=re.escape(named)):
+            _lib.parse_header(bad)
 
 
 def test_attention_entries_refuse_bad_argument_blocks_before_any_device_call():
