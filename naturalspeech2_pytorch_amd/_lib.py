@@ -1,4 +1,5 @@
-"""ctypes binding of libns2hip.so, derived from its C ABI: include/ns2hip.h is parsed once, at import.
+"""ctypes binding of libns2hip.so, derived from its C ABI: include/ns2hip.h (and include/ns2hip_optim.h, the optimizer step, into
+tables of its own) is parsed once, at import.
 
 The HIP library is the product: importing this module FAILS LOUDLY when the header or the shared object is missing or the
 library does not export the full ABI -- there is no CPU / PyTorch fallback for the hot path.
@@ -24,6 +25,7 @@ from ctypes import c_char_p, c_void_p, POINTER
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NS2_LIB", os.path.join(_HERE, "libns2hip.so"))   # NS2_LIB: experiment builds (tools/)
 HEADER_PATH = os.path.join(_HERE, "..", "include", "ns2hip.h")
+OPTIM_HEADER_PATH = os.path.join(_HERE, "..", "include", "ns2hip_optim.h")   # the optimizer step: a header and tables of its own
 
 
 class Ns2Error(RuntimeError):
@@ -106,6 +108,12 @@ NS2_OK, NS2_ERR_ARG, NS2_ERR_HIP, NS2_ERR_STATE, NS2_UNAVAILABLE = (
 ModelConfig, LinearArgs, AttnArgs, AttnBwdArgs, RepackPart = (
     STRUCTS[k] for k in ("ns2_model_config", "ns2_linear_args", "ns2_attn_args", "ns2_attn_bwd_args", "ns2_repack_part"))
 
+if not os.path.exists(OPTIM_HEADER_PATH):
+    raise Ns2Error(f"{OPTIM_HEADER_PATH} not found: the binding is derived from the header, it ships with the package's source tree")
+with open(OPTIM_HEADER_PATH) as _f:                              # same rule, tables of its own: SIGNATURES / STRUCTS / header_symbols()
+    OPTIM_CONSTANTS, OPTIM_STRUCTS, OPTIM_SIGNATURES = parse_header(_f.read())      # keep describing ns2hip.h alone
+OptimTensor, OptimConfig = (OPTIM_STRUCTS[k] for k in ("ns2_optim_tensor", "ns2_optim_config"))
+
 _lib = None
 
 
@@ -118,7 +126,7 @@ def load():
         raise Ns2Error(f"{LIB_PATH} not found: build it with `python __graft_entry__.py` "
                        f"(or naturalspeech2_pytorch_amd/csrc/build.sh); there is no fallback path")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in {**SIGNATURES, **OPTIM_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -138,3 +146,8 @@ def check(rc, what=""):
 def header_symbols():
     """Symbols declared in include/ns2hip.h (used by the CPU test that the .so exports the whole ABI)."""
     return sorted(SIGNATURES)
+
+
+def optim_header_symbols():
+    """Symbols declared in include/ns2hip_optim.h"""
+    return sorted(OPTIM_SIGNATURES)

@@ -70,7 +70,7 @@ NS2_DEVINL void split2(float a, float b, uint32_t& hi, uint32_t& lo) {
 // at precisions 2 and 4, 1e-5 at precision 3 whose bf16 planes have the fp32 exponent range).  Every conversion that clamps
 // (or meets a NaN) bumps a per-device counter; the host reads it after a sampling run (ns2_saturation_count) and fails
 // loudly.  One static counter per translation unit (no relocatable device code).  Including this header is all it takes to be
-// guarded: the translation unit registers its counter's two host-side readers when the library is loaded (ns2_sat_registry.h), and
+// guarded: the translation unit registers its counter's host-side readers when the library is loaded (ns2_sat_registry.h), and
 // capi.cpp's ns2_saturation_count / ns2_saturation_peek loop over the registry.
 static __device__ unsigned int ns2_sat_counter;
 NS2_DEVINL void note_out_of_range(float a, float b, float limit) {
@@ -86,8 +86,12 @@ unsigned int sat_read_tu(bool reset) {
 hipError_t sat_peek_tu(unsigned int* dst, hipStream_t s) {
   return hipMemcpyFromSymbolAsync(dst, HIP_SYMBOL(ns2_sat_counter), sizeof(unsigned int), 0, hipMemcpyDeviceToHost, s);
 }
+void* sat_address_tu() {
+  void* p = nullptr;
+  return hipGetSymbolAddress(&p, HIP_SYMBOL(ns2_sat_counter)) == hipSuccess ? p : nullptr;
+}
 const struct SatRegistrar {
-  SatRegistrar() { ns2::register_sat_counter({sat_read_tu, sat_peek_tu, __BASE_FILE__}); }
+  SatRegistrar() { ns2::register_sat_counter({sat_read_tu, sat_peek_tu, sat_address_tu, __BASE_FILE__}); }
 } sat_registrar;
 }  // namespace
 

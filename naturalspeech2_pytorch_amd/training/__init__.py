@@ -42,7 +42,8 @@ chain rule, tap flips, shifts and layouts of THIS package are checked against to
 Where things are; each module imports only from those before it: packs.py (the packed-weight cache), backend.py (`TPlanes`, `HipBackend`),
 passes.py (what "the current pass" is: `training_pass`, `backend()` and its registries, `weights_unchanged`, the loss scale `_Scale`),
 functions.py (the autograd Functions), model_pass.py / encoder_pass.py / duration_pitch_pass.py / aligner_pass.py (the `*_forward_train` of `Model`, of the
-conditioning encoders, of the predictor and of the aligner), graph.py (`GraphedTrainStep`, on passes.py alone).  The names below are the package's interface; tests and tools take an
+conditioning encoders, of the predictor and of the aligner), graph.py (`GraphedTrainStep`, on passes.py alone), optim.py (`HipAdam`: clip, Adam and EMA
+as one capturable step, csrc/optim.hip; on _lib alone), trainer.py (`Trainer`, the reference's loop over graph.py and optim.py).  The names below are the package's interface; tests and tools take an
 underscore name from the module that holds it.
 """
 from .aligner_pass import aligner_forward_train, aligner_unsupported_reason
@@ -52,8 +53,10 @@ from .encoder_pass import (encoder_unsupported_reason, phoneme_encoder_forward_t
                            transformer_forward_train)
 from .graph import GraphedTrainStep
 from .model_pass import available, model_forward_train, rvq_ce_unsupported_reason, unsupported_reason
+from .optim import HipAdam
 from .passes import TRAIN_PRECISIONS, backend, set_backend, weights_unchanged
+from .trainer import Trainer
 
 __all__ = ["HipBackend", "TPlanes", "aligner_forward_train", "aligner_unsupported_reason", "duration_pitch_forward_train", "duration_pitch_unsupported_reason", "encoder_unsupported_reason", "phoneme_encoder_forward_train", "speech_prompt_encoder_forward_train",
-           "transformer_forward_train", "GraphedTrainStep", "available", "model_forward_train", "rvq_ce_unsupported_reason", "unsupported_reason", "TRAIN_PRECISIONS",
+           "transformer_forward_train", "GraphedTrainStep", "HipAdam", "Trainer", "available", "model_forward_train", "rvq_ce_unsupported_reason", "unsupported_reason", "TRAIN_PRECISIONS",
            "backend", "set_backend", "weights_unchanged"]

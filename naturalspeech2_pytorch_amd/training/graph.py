@@ -36,7 +36,17 @@ class GraphedTrainStep:
 
         step = GraphedTrainStep(lambda a, t, n: diffusion(a, times=t, noise=n), (audio, times, noise), model)
         loss = step(audio, times, noise)          # .grad of every trainable parameter of `model` is now this batch's gradient
-        optimizer.step()                          # outside the graph (`zero_grad` between replays is unnecessary and harmless)
+        optimizer.step()                          # any in-place torch optimizer, after the replay (`zero_grad` between replays is
+                                                  # unnecessary and harmless) -- or hand the graph a `HipAdam` and drop this line:
+
+        step = GraphedTrainStep(..., model, optimizer=training.HipAdam(model.parameters(), max_grad_norm=1.0, ema=True))
+        loss = step(audio, times, noise)          # a whole training step: mark, loss, backward, gradient norm + clip, Adam, EMA
+
+    With `optimizer=` (a `HipAdam` over `module`'s trainable parameters) the captured graph is `optimizer.mark()`, loss and backward,
+    then the optimizer's norm and update launches (training/optim.py), bound to the graph's own gradient tensors; leaves the loss does not
+    reach have no gradient there either.  A step whose conversions left the IEEE-half range, or whose gradient norm is not finite, is
+    skipped ON THE DEVICE (`optimizer.skipped`), so `overflowed()` and its host round trip are not needed on that path.  Constructing the
+    object moves neither a parameter nor any optimizer state: the warm passes run no optimizer step and a capture executes nothing.
 
     `module`: the nn.Module (or a list of them) whose trainable parameters `loss_fn` reaches.  During the warm passes and the capture
     the module runs on SUBSTITUTE leaves over the same storage (torch.func.functional_call): a parameter's own AccumulateGrad node lives
@@ -49,13 +59,21 @@ class GraphedTrainStep:
     Tensor hooks on the parameters do not run during a replay (`distributed.GradientAllReducer` overlaps its all-reduces with an EAGER
     backward through such hooks): a data-parallel loop on the graph all-reduces `step.grads` after the call instead."""
 
-    def __init__(self, loss_fn, example_inputs, module, warmup=2):
+    def __init__(self, loss_fn, example_inputs, module, warmup=2, optimizer=None):
         root = module if isinstance(module, torch.nn.Module) else torch.nn.ModuleList(list(module))
         named = [(k, p) for k, p in root.named_parameters() if p.requires_grad]
         assert named, "GraphedTrainStep: no trainable parameter"
         self.inputs = [t.detach().clone() for t in example_inputs]
         assert self.inputs and self.inputs[0].is_cuda, "GraphedTrainStep captures a HIP graph: inputs live on the GPU"
         self.params = [p for _, p in named]
+        self.optimizer = optimizer
+        if optimizer is not None:
+            from .optim import HipAdam
+            assert isinstance(optimizer, HipAdam), "GraphedTrainStep(optimizer=): a training.HipAdam (its step is capturable and reads no device value on the host)"
+            mine = {id(p) for p in self.params}
+            assert all(id(p) in mine for p in optimizer.param_groups[0]["params"]), "GraphedTrainStep(optimizer=): the optimizer holds a parameter that is not a trainable parameter of `module`"
+            optimizer.bind(None, None)
+            optimizer.prepare()                           # state block and tensor table: synchronising set-up, before any capture
         self._subs = {"root." + k: p.detach().requires_grad_(True) for k, p in named}
         self._backends = {}                               # the HipBackends of the warm passes and the capture: what the replays read
         leaves = list(self._subs.values())
@@ -70,10 +88,16 @@ class GraphedTrainStep:
         cur.wait_stream(side)
         self.graph = torch.cuda.CUDAGraph()
         with _registry(self._backends), torch.cuda.graph(self.graph):
+            if optimizer is not None:
+                optimizer.mark()
             loss = run()
             grads = torch.autograd.grad(loss, leaves, allow_unused=True)
+            if optimizer is not None:
+                optimizer.bind(self.params, grads)        # the graph's own tensors; their addresses travel as launch arguments
+                optimizer.step()
         self.loss = loss.detach()
         self.grads = list(grads)                          # the graph's own tensors: every replay writes them, __call__ attaches them as .grad
+        self._opt_grads = None if optimizer is None else optimizer.table_grads()
         self._before = None
 
     def __call__(self, *inputs):
@@ -83,6 +107,9 @@ class GraphedTrainStep:
                 s.copy_(t)
         self._before = RangePeek().take(self.inputs[0].device)
         self.graph.replay()
+        if self.optimizer is not None:                    # (an eager optimizer.step() in between may have pointed the table elsewhere;
+            self.optimizer.bind(self.params, self.grads)  # the replay pointed it back at the graph's gradients)
+            self.optimizer.table_grads(self._opt_grads)
         for p, g in zip(self.params, self.grads):         # (whatever a zero_grad(set_to_none=True) or an eager pass in between left there)
             p.grad = g
         return self.loss
