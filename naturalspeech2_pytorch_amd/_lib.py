@@ -1,5 +1,5 @@
-"""ctypes binding of libns2hip.so, derived from its C ABI: include/ns2hip.h (and include/ns2hip_optim.h, the optimizer step, into
-tables of its own) is parsed once, at import.
+"""ctypes binding of libns2hip.so, derived from its C ABI: include/ns2hip.h (and include/ns2hip_optim.h, the optimizer step, and
+include/ns2hip_pitch.h, the pitch extractor, each into tables of its own) is parsed once, at import.
 
 The HIP library is the product: importing this module FAILS LOUDLY when the header or the shared object is missing or the
 library does not export the full ABI -- there is no CPU / PyTorch fallback for the hot path.
@@ -26,6 +26,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NS2_LIB", os.path.join(_HERE, "libns2hip.so"))   # NS2_LIB: experiment builds (tools/)
 HEADER_PATH = os.path.join(_HERE, "..", "include", "ns2hip.h")
 OPTIM_HEADER_PATH = os.path.join(_HERE, "..", "include", "ns2hip_optim.h")   # the optimizer step: a header and tables of its own
+PITCH_HEADER_PATH = os.path.join(_HERE, "..", "include", "ns2hip_pitch.h")   # the pitch extractor: likewise
 
 
 class Ns2Error(RuntimeError):
@@ -114,6 +115,11 @@ with open(OPTIM_HEADER_PATH) as _f:                              # same rule, ta
     OPTIM_CONSTANTS, OPTIM_STRUCTS, OPTIM_SIGNATURES = parse_header(_f.read())      # keep describing ns2hip.h alone
 OptimTensor, OptimConfig = (OPTIM_STRUCTS[k] for k in ("ns2_optim_tensor", "ns2_optim_config"))
 
+if not os.path.exists(PITCH_HEADER_PATH):
+    raise Ns2Error(f"{PITCH_HEADER_PATH} not found: the binding is derived from the header, it ships with the package's source tree")
+with open(PITCH_HEADER_PATH) as _f:
+    _, _, PITCH_SIGNATURES = parse_header(_f.read())
+
 _lib = None
 
 
@@ -126,7 +132,7 @@ def load():
         raise Ns2Error(f"{LIB_PATH} not found: build it with `python __graft_entry__.py` "
                        f"(or naturalspeech2_pytorch_amd/csrc/build.sh); there is no fallback path")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in {**SIGNATURES, **OPTIM_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **OPTIM_SIGNATURES, **PITCH_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -151,3 +157,8 @@ def header_symbols():
 def optim_header_symbols():
     """Symbols declared in include/ns2hip_optim.h"""
     return sorted(OPTIM_SIGNATURES)
+
+
+def pitch_header_symbols():
+    """Symbols declared in include/ns2hip_pitch.h"""
+    return sorted(PITCH_SIGNATURES)

@@ -7,6 +7,7 @@
 #include <cstring>
 #include <vector>
 
+#include "../../include/ns2hip_pitch.h"
 #include "ns2_host.h"
 
 namespace ns2 {
@@ -308,6 +309,21 @@ extern "C" int ns2_ddim_step(const float* audio, const float* model_out, float* 
 extern "C" int ns2_cfg_mix(const float* cond_out, const float* null_out, float* out, int64_t n, float cond_scale, void* stream) {
   ARGCHK(cond_out && null_out && out, "ns2_cfg_mix: null pointer");
   HIPRET(launch_cfg_mix(cond_out, null_out, out, (long)n, cond_scale, (hipStream_t)stream));
+  return NS2_OK;
+}
+
+// include/ns2hip_pitch.h
+extern "C" int ns2_pitch_yin(const float* audio, int B, int64_t L, int sample_rate, int hop_length, int tau_min, int tau_max,
+                             float threshold, float* f0, void* stream) {
+  ARGCHK(audio && f0, "ns2_pitch_yin: null pointer");
+  ARGCHK(B >= 1 && B <= 65535, "ns2_pitch_yin: B must be in [1, 65535]");
+  ARGCHK(L >= 1, "ns2_pitch_yin: L must be at least 1");
+  ARGCHK(sample_rate >= 1 && hop_length >= 1, "ns2_pitch_yin: sample_rate and hop_length must be at least 1");
+  ARGCHK(tau_min >= 2 && tau_min < tau_max && tau_max <= PITCH_TAU_MAX, "ns2_pitch_yin: the lags must satisfy 2 <= tau_min < tau_max <= 1024");
+  ARGCHK(threshold == threshold, "ns2_pitch_yin: threshold is NaN");
+  const int64_t T = 1 + L / hop_length;
+  ARGCHK(T <= 0x7fffffffLL, "ns2_pitch_yin: too many frames");
+  HIPRET(launch_pitch_yin(audio, B, (long)L, (long)T, sample_rate, hop_length, tau_min, tau_max, threshold, f0, (hipStream_t)stream));
   return NS2_OK;
 }
 

@@ -364,4 +364,10 @@ hipError_t launch_align_losses_fwd(const float* aln_log, const float* hard, cons
 hipError_t launch_align_losses_bwd(const float* aln_log, const float* hard, const int* text_lens, const int* mel_lens, const float* g_fs,
                                    const float* g_bin, int B, int T, int n, float blank, float* d_log, void* workspace, hipStream_t s);
 
+// the YIN pitch estimator (pitch.hip; include/ns2hip_pitch.h states the formula): audio [B, L] -> f0 [B, 1 + L / hop] in Hz, 0 unvoiced.
+// The caller (capi.cpp) has checked 2 <= tau_min < tau_max <= PITCH_TAU_MAX, hop >= 1, L >= 1, 1 <= B <= 65535
+constexpr int PITCH_TAU_MAX = 1024;
+hipError_t launch_pitch_yin(const float* audio, int B, long L, long T, int sample_rate, int hop, int tau_min, int tau_max, float threshold,
+                            float* f0, hipStream_t s);
+
 }  // namespace ns2

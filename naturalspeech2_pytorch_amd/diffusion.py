@@ -11,9 +11,10 @@ built from the plain Transformer (`prompt_enc` = SpeechPromptEncoder, `phoneme_e
 `build_duration_pitch=True`, the DurationPitchPredictor and the length regulator behind `sample(text=...)` (NS2:1476-1483;
 duration_pitch.py) and, with `build_aligner=True`, the Aligner and the expansion behind `forward(text=..., mel=..., pitch=...)`
 (NS2:1524-1602; aligner.py) are HIP, and so is AudioToMel (audio_to_mel.py), which turns raw audio into the Aligner's mel
-frames when `forward` gets no `mel`.  The rest of the conditioning front-end — pitch extraction, the tokenizer (SURVEY
-§2: OUT OF SCOPE) — is not rebuilt.  By default (no predictor: the state_dict has no `duration_pitch.*` keys) and for
-`forward`, a caller hands over what those modules would have produced through two extra keyword arguments that the reference
+frames when `forward` gets no `mel`.  With `build_pitch_extractor=True`, PitchExtractor (pitch.py: an own YIN estimator on a HIP
+kernel, no parity with pyworld / Kaldi claimed) gives the F0 of those frames when `forward` gets no `pitch`.  The rest of the
+conditioning front-end — the tokenizer (OUT OF SCOPE) — is not rebuilt.  By default (no predictor: the state_dict
+has no `duration_pitch.*` keys) and for `forward`, a caller hands over what those modules would have produced through two extra keyword arguments that the reference
 signature tolerates (`forward` takes **kwargs):
 
     cond        [b, dim_prompt, n_c]   the frame-aligned phoneme+pitch conditioning (reference: `expand_encodings`, NS2:1449-1455)
@@ -85,6 +86,7 @@ class NaturalSpeech2(nn.Module):
                  encoder_precision="exact",            # not in the reference: precision mode of the HIP encoders (and predictor)
                  build_duration_pitch: bool = False,   # not in the reference: build the DurationPitchPredictor (sample(text=...))
                  build_aligner: bool = False,          # not in the reference: build the Aligner (forward(text=..., mel=..., pitch=...))
+                 build_pitch_extractor: bool = False,  # not in the reference: build the PitchExtractor (forward(text=...) without pitch=; pitch.py, own YIN estimator)
                  encoder_train_backend="composite",    # not in the reference: "hip" trains phoneme_enc / prompt_enc on the HIP kernels (training/encoder_pass.py)
                  duration_pitch_train_backend="composite",    # not in the reference: "hip" trains the DurationPitchPredictor on them (training/duration_pitch_pass.py)
                  aligner_train_backend="composite",    # not in the reference: "hip" trains the Aligner and runs its two losses on them (training/aligner_pass.py)
@@ -106,7 +108,10 @@ class NaturalSpeech2(nn.Module):
             if self.target_sample_hz is not None:
                 audio_to_mel_kwargs.update(sampling_rate=self.target_sample_hz)
             self.audio_to_mel = AudioToMel(n_mels=aligner_dim_in, hop_length=mel_hop_length, **audio_to_mel_kwargs)
-            self.calc_pitch_with_pyworld = calc_pitch_with_pyworld
+            self.calc_pitch_with_pyworld = calc_pitch_with_pyworld                    # accepted and stored; selects nothing
+            if build_pitch_extractor:                                                 # no parameters, no buffers
+                from .pitch import PitchExtractor
+                self.pitch_extractor = PitchExtractor(sample_rate=self.target_sample_hz, hop_length=mel_hop_length)
             self.phoneme_enc = PhonemeEncoder(tokenizer=tokenizer, num_tokens=num_phoneme_tokens, precision=encoder_precision,
                                               train_backend=encoder_train_backend)
             self.prompt_enc = SpeechPromptEncoder(dim_codebook=dim_codebook, precision=encoder_precision, train_backend=encoder_train_backend)
@@ -124,6 +129,7 @@ class NaturalSpeech2(nn.Module):
                 self.bin_loss = BinLoss(backend=aligner_train_backend)
         else:
             assert not build_aligner, "the Aligner belongs to a conditional model (condition_on_prompt=True)"
+            assert not build_pitch_extractor, "the PitchExtractor belongs to a conditional model (condition_on_prompt=True)"
 
         assert codec is None or model.dim == codec.codebook_dim, \
             f"transformer model dimension {model.dim} must be equal to codec dimension {codec.codebook_dim}"   # NS2:1244
@@ -380,7 +386,9 @@ class NaturalSpeech2(nn.Module):
 
         With `build_aligner=True` and no `cond`, `text`, `mel` [b, aligner_dim_in, T_mel] and `pitch` [b, 1, T_mel] derive the
         conditioning as NS2:1524-1602 does (text_forward_cond).  The value returned is the reference's: its auxiliary duration /
-        pitch / alignment losses are computed and dropped upstream, so they are not computed here.  `return_aux_losses=True`
+        pitch / alignment losses are computed and dropped upstream, so they are not computed here.  Without `mel`, raw audio
+        goes through AudioToMel; without `pitch`, a wrapper built with `build_pitch_extractor=True` runs its PitchExtractor on
+        the raw audio (without one, the missing `pitch` raises as before).  `return_aux_losses=True`
         (not in the reference, needs build_duration_pitch=True) returns (loss, dict(duration=, pitch=, align=, bin=, aux=)),
         the only way to train the Aligner and the predictor."""
         is_raw = audio.ndim == 2
@@ -396,6 +404,12 @@ class NaturalSpeech2(nn.Module):
                     raise NotImplementedError("forward(text=...) without `mel` computes it with AudioToMel (NS2:1561-1567), which "
                                               "needs raw audio [b, samples], not latents: pass the raw audio, or the mel frames as "
                                               "`mel=` [b, aligner_dim_in, T_mel]")
+                if pitch is None and hasattr(self, "pitch_extractor"):
+                    if not is_raw:
+                        raise NotImplementedError("forward(text=...) without `pitch` computes it with PitchExtractor, which needs raw "
+                                                  "audio [b, samples], not latents: pass the raw audio, or `pitch=` [b, 1, T_mel]")
+                    with torch.no_grad():                                             # one value per AudioToMel frame, Hz, 0 unvoiced
+                        pitch = self.pitch_extractor(audio)[:, None]
                 if pitch is None:
                     raise NotImplementedError("forward(text=...) without `pitch` needs the pyworld / kaldi pitch extraction "
                                               "(NS2:1546-1559), which is outside the HIP hot path: pass `pitch=` [b, 1, T_mel]")

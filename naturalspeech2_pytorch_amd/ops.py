@@ -563,3 +563,17 @@ def audio_to_mel(audio: torch.Tensor, n_fft: int, hop_length: int, n_mels: int, 
                                    plan["twiddle"].data_ptr(), plan["meta"].data_ptr(), plan["weights"].data_ptr(), plan["n_w"],
                                    n_mels, plan["n_bins"], int(bool(log)), out[b0].data_ptr(), _stream()), "ns2_audio_to_mel")
     return out
+
+
+# ---- PitchExtractor (csrc/pitch.hip)
+def pitch_yin(audio: torch.Tensor, sample_rate: int, hop_length: int, tau_min: int, tau_max: int, threshold: float) -> torch.Tensor:
+    """audio [B, L] fp32 -> f0 [B, 1 + L // hop_length] in Hz, 0 where unvoiced (ns2_pitch_yin, include/ns2hip_pitch.h)"""
+    audio = _f32(audio)
+    B, L = audio.shape
+    out = torch.empty(B, 1 + L // hop_length, dtype=torch.float32, device=audio.device)
+    lib = _lib.load()
+    for b0 in range(0, B, 65535):                 # grid.y holds at most 65535 utterances
+        nb = min(65535, B - b0)
+        check(lib.ns2_pitch_yin(audio[b0].data_ptr(), nb, L, sample_rate, hop_length, tau_min, tau_max, threshold, out[b0].data_ptr(),
+                                _stream()), "ns2_pitch_yin")
+    return out
