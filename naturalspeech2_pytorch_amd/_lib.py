@@ -1,5 +1,5 @@
 """ctypes binding of libns2hip.so, derived from its C ABI: include/ns2hip.h (and include/ns2hip_optim.h, the optimizer step, and
-include/ns2hip_pitch.h, the pitch extractor, each into tables of its own) is parsed once, at import.
+include/ns2hip_pitch.h, the pitch extractor, and include/ns2hip_ragged.h, ragged batches, each into tables of its own) is parsed once, at import.
 
 The HIP library is the product: importing this module FAILS LOUDLY when the header or the shared object is missing or the
 library does not export the full ABI -- there is no CPU / PyTorch fallback for the hot path.
@@ -27,6 +27,7 @@ LIB_PATH = os.environ.get("NS2_LIB", os.path.join(_HERE, "libns2hip.so"))   # NS
 HEADER_PATH = os.path.join(_HERE, "..", "include", "ns2hip.h")
 OPTIM_HEADER_PATH = os.path.join(_HERE, "..", "include", "ns2hip_optim.h")   # the optimizer step: a header and tables of its own
 PITCH_HEADER_PATH = os.path.join(_HERE, "..", "include", "ns2hip_pitch.h")   # the pitch extractor: likewise
+RAGGED_HEADER_PATH = os.path.join(_HERE, "..", "include", "ns2hip_ragged.h")   # per-utterance lengths: likewise
 
 
 class Ns2Error(RuntimeError):
@@ -120,6 +121,11 @@ if not os.path.exists(PITCH_HEADER_PATH):
 with open(PITCH_HEADER_PATH) as _f:
     _, _, PITCH_SIGNATURES = parse_header(_f.read())
 
+if not os.path.exists(RAGGED_HEADER_PATH):
+    raise Ns2Error(f"{RAGGED_HEADER_PATH} not found: the binding is derived from the header, it ships with the package's source tree")
+with open(RAGGED_HEADER_PATH) as _f:                             # ns2_attn_args / ns2_model are ns2hip.h's (its #include is not followed): their
+    _, _, RAGGED_SIGNATURES = parse_header(_f.read())            # pointers are c_void_p here -- pass ctypes.byref(block)
+
 _lib = None
 
 
@@ -132,7 +138,7 @@ def load():
         raise Ns2Error(f"{LIB_PATH} not found: build it with `python __graft_entry__.py` "
                        f"(or naturalspeech2_pytorch_amd/csrc/build.sh); there is no fallback path")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in {**SIGNATURES, **OPTIM_SIGNATURES, **PITCH_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **OPTIM_SIGNATURES, **PITCH_SIGNATURES, **RAGGED_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -162,3 +168,8 @@ def optim_header_symbols():
 def pitch_header_symbols():
     """Symbols declared in include/ns2hip_pitch.h"""
     return sorted(PITCH_SIGNATURES)
+
+
+def ragged_header_symbols():
+    """Symbols declared in include/ns2hip_ragged.h"""
+    return sorted(RAGGED_SIGNATURES)

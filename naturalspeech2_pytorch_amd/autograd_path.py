@@ -53,8 +53,16 @@ def _feedforward(x, ff, causal_conv):
     return getattr(ff, "2")(h)
 
 
-def model_forward_autograd(m, x, times, prompt=None, cond=None, cond_drop_prob=None):
+def model_forward_autograd(m, x, times, prompt=None, cond=None, cond_drop_prob=None, lens=None):
+    """`lens` (not in the reference; Model.forward's): frames per utterance of a ragged batch, integer [b].  The self-attention is the
+    one place where a frame sees later frames, so it alone gets the key mask arange(n) < lens[:, None]: out[i, :lens[i]] is what
+    utterance i gives alone.  The restatement of the HIP kernels' rule (include/ns2hip_ragged.h), lengths clamped into [1, n] as there."""
     b, n, _ = x.shape
+    self_mask = None
+    if lens is not None:
+        ln = torch.as_tensor(lens, device=x.device).long().clamp(1, n)
+        assert ln.shape == (b,), f"lens must hold one frame count per utterance: [{b}]"
+        self_mask = torch.arange(n, device=x.device)[None] < ln[:, None]
     p = m.cond_drop_prob if cond_drop_prob is None else cond_drop_prob
     w = getattr(m.to_time_cond, "0").weights
     tt = times[:, None]
@@ -107,7 +115,7 @@ def model_forward_autograd(m, x, times, prompt=None, cond=None, cond_drop_prob=N
         cols = nxt
     h = _causal_conv(torch.stack(skips).sum(0), wn.final_conv)
     for layer in m.transformer.layers:
-        h = _attention(_rmsnorm(h, getattr(layer, "0"), t), getattr(layer, "1"), m.heads) + h
+        h = _attention(_rmsnorm(h, getattr(layer, "0"), t), getattr(layer, "1"), m.heads, key_mask=self_mask) + h
         if m.condition_on_prompt:
             h = _attention(_rmsnorm(h, getattr(layer, "2"), t), getattr(layer, "3"), m.heads, context=c) + h
         h = _feedforward(_rmsnorm(h, getattr(layer, "4"), t), getattr(layer, "5"), True) + h
@@ -180,11 +188,12 @@ def f0_to_coarse(f0, f0_bin=256, f0_max=1100.0, f0_min=50.0):
     return (f0_mel + 0.5).int()
 
 
-def length_regulate(duration, pitch, enc, pitch_table):
+def length_regulate(duration, pitch, enc, pitch_table, return_totals=False):
     """generate_mask_from_repeats + expand_encodings (NS2:87-104, 1449-1455) as a gather: frame f of utterance b takes the
     phoneme whose [exclusive, inclusive) prefix of int(duration) holds f, zeros past the utterance's total.  The reference's 0/1
     mask einsum sums one product x * 1 with zeros, so enc[ph] + pitch_table[coarse[ph]] is bit-identical to it.  Negative
-    durations (the predictor's ReLU never makes one) count as 0 frames.  -> [B, D, n_frames]"""
+    durations (the predictor's ReLU never makes one) count as 0 frames.  -> [B, D, n_frames]; return_totals: (that, the utterances' own
+    frame totals [B])"""
     reps = duration.int().clamp(min=0)
     cum = reps.cumsum(dim=-1)
     totals = cum[:, -1]
@@ -197,7 +206,7 @@ def length_regulate(duration, pitch, enc, pitch_table):
     pe = F.embedding(f0_to_coarse(pitch).long(), pitch_table)
     pe = torch.gather(pe, 1, ph[..., None].expand(-1, -1, pe.shape[-1]))
     out = torch.where(valid[..., None], e + pe, torch.zeros((), dtype=e.dtype, device=e.device))
-    return out.transpose(1, 2)
+    return (out.transpose(1, 2), totals) if return_totals else out.transpose(1, 2)
 
 
 # ---- Aligner (aligner.py of the reference) and the text-conditioned training pass (utils.py:4-26, NS2:1449-1455)

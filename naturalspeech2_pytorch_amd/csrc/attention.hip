@@ -21,7 +21,7 @@
 //   * attn_kernel<NSPLIT, F16, NW, WLSE, D, DROP> below: every case -- all precisions, head dimensions 32 / 64 / 128, ragged and masked
 //     keys, the training forward with its log-sum-exp and dropout;
 //   * attn_fast_kernel<PF> (attn_fast_kernel.h): the inference self-attention of the one-half-product plans (precisions 2 / 4, D = 64,
-//     whole 64-key tiles, whole 256-row workgroups, no mask): a wave owns two query blocks, so every K / V^T fragment read from LDS and every staged tile
+//     whole 64-key tiles, whole 256-row workgroups, no mask; <PF, true>: per-utterance key counts, AttnArgs::klens): a wave owns two query blocks, so every K / V^T fragment read from LDS and every staged tile
 //     serves twice the query rows, and O leaves through LDS as 16-byte stores.  Same arithmetic in the same order: bit-identical to
 //     attn_kernel<1, true, 4, false, 64>, which stays its reference and A/B partner behind ns2_debug_force_attention(1) / NS2_ATTN=1.
 // launch_attention routes: attn_fast_eligible() is the whole test.
@@ -90,6 +90,9 @@ __global__ __launch_bounds__(64 * NW, ((NSPLIT == 3 && D == 128) ? 1 : (NSPLIT =
   const int h = bid % a.H, b = bid / a.H;
   const int qrow = qt * QB + wave * 32 + l31;
   const bool q_ok = qrow < a.Nq;
+  // keys this utterance attends to: a.Nk, or its own count (AttnArgs::klens, clamped into [1, Nk]); a.Nk stays the stride of every address
+  int nk = a.Nk;
+  if (a.klens) nk = min(max(a.klens[b], 1), a.Nk);
 
   const bf16_t* q_pl[2] = {a.q_hi, a.q_lo};
   const bf16_t* k_pl[2] = {a.k_hi, a.k_lo};
@@ -125,10 +128,10 @@ __global__ __launch_bounds__(64 * NW, ((NSPLIT == 3 && D == 128) ? 1 : (NSPLIT =
 #pragma unroll
     for (int i = 0; i < CPT; ++i) {
       const int key = key0 + krow[i];
-      const bool kok = key < a.Nk;
+      const bool kok = key < nk;
       const long koff = ((long)b * a.Nk + key) * pld(a.ldk, kil) + pcol(a.k_col0 + h * D + kch[i] * 8, kil);
       const int vkey = key0 + sch[i] * 8;
-      const int nvalid = a.Nk - vkey;
+      const int nvalid = nk - vkey;
       const long voff = ((long)b * a.H * D + h * D + srow[i]) * pld(a.vt_ld, vil) + pcol(vkey, vil);
 #pragma unroll
       for (int p = 0; p < NP; ++p) {
@@ -170,7 +173,7 @@ __global__ __launch_bounds__(64 * NW, ((NSPLIT == 3 && D == 128) ? 1 : (NSPLIT =
   uint32_t drop_row = 0u;                              // head key + q * (its multiplier): the part of the counter this lane's query fixes
   if constexpr (DROP) drop_row = drop_head_key(a.drop_seed[0], a.drop_seed[1], a.drop_call, (uint32_t)(b * a.H + h)) + (uint32_t)qrow * 0x9E3779B1u;
 
-  const int ntiles = (a.Nk + 63) / 64;
+  const int ntiles = (nk + 63) / 64;
   Regs rg;
   load_tile(rg, 0);
   store_tile(rg, 0);
@@ -204,15 +207,15 @@ __global__ __launch_bounds__(64 * NW, ((NSPLIT == 3 && D == 128) ? 1 : (NSPLIT =
 
     // ---- online softmax for query l31; register r of sub-tile js is key key0 + 32js + 16(r>>3) + 8hi + (r&7).
     // st holds RAW scores; the scale (and log2 e) is folded into the exponent's fma.  Key masking is a wave-uniform
-    // slow path: only the last tile of a ragged key length, or a call with a key-padding mask, takes it.
+    // slow path: only the last tile of a ragged key length (a.Nk, or the utterance's own count), or a call with a key-padding mask, takes it.
     const unsigned char* km = a.kmask ? a.kmask + (long)b * a.Nk : nullptr;
-    if (key0 + 64 > a.Nk || km) {
+    if (key0 + 64 > nk || km) {
 #pragma unroll
       for (int js = 0; js < 2; ++js)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int key = key0 + 32 * js + 16 * (r >> 3) + 8 * hi + (r & 7);
-          if (key >= a.Nk) st[js][r] = -INFINITY;
+          if (key >= nk) st[js][r] = -INFINITY;
           else if (km && !km[key]) st[js][r] = -3.0e38f;   // ATT:136-138 masked_fill(~mask, -finfo.max): finite, like the reference
         }
     }
@@ -351,7 +354,8 @@ static bool attn_fast_allowed() {
 
 // Does attn_fast_kernel (attn_fast_kernel.h) take this call?  One IEEE-half product (the caller is launch_attn_t<1, true>: no lo
 // planes), head dimension 64, nothing but the plain forward (no log-sum-exp, dropout or key mask), whole 64-key tiles and whole
-// 256-row workgroups, an IEEE-half output format whose rows take 16-byte stores.  Everything else keeps attn_kernel.
+// 256-row workgroups, an IEEE-half output format whose rows take 16-byte stores.  Everything else keeps attn_kernel.  Per-utterance
+// key counts (klens) are taken under the same shape conditions -- Nk is the stride and must be whole tiles, the counts need not be.
 static bool attn_fast_eligible(const AttnArgs& a) {
   if (!attn_fast_allowed()) return false;
   if ((a.D != 0 && a.D != 64) || a.lse || a.drop_seed || a.kmask) return false;
@@ -364,15 +368,15 @@ static bool attn_fast_eligible(const AttnArgs& a) {
 // kernels give the same bits and the output cannot tell which one ran.
 static std::atomic<long long> g_fast_launches{0};
 long long attention_fast_launches() { return g_fast_launches.load(std::memory_order_relaxed); }
-template <int PF>
+template <int PF, bool LENS = false>
 static hipError_t launch_attn_fast(const AttnArgs& a, hipStream_t s) {
   static DynLdsAttr attr;
   g_fast_launches.fetch_add(1, std::memory_order_relaxed);
   {
-    hipError_t e = attr.ensure(reinterpret_cast<const void*>(&attn_fast_kernel<PF>), AF_LDS);
+    hipError_t e = attr.ensure(reinterpret_cast<const void*>(&attn_fast_kernel<PF, LENS>), AF_LDS);
     if (e != hipSuccess) return e;
   }
-  hipLaunchKernelGGL((attn_fast_kernel<PF>), dim3((a.Nq / AF_QB) * a.H * a.B), dim3(256), AF_LDS, s, a);
+  hipLaunchKernelGGL((attn_fast_kernel<PF, LENS>), dim3((a.Nq / AF_QB) * a.H * a.B), dim3(256), AF_LDS, s, a);
   return hipGetLastError();
 }
 
@@ -389,13 +393,17 @@ hipError_t launch_attention(const AttnArgs& a_in, int nsplit, hipStream_t s) {
   if (!planes_ok(a.q_hi, a.q_lo) || !planes_ok(a.k_hi, a.k_lo) || !planes_ok(a.vt_hi, a.vt_lo) || !planes_ok(a.o_hi, a.o_lo))
     return hipErrorInvalidValue;
   if (a.vt_lo && (a.vt_ld & 31)) return hipErrorInvalidValue;   // interleaved rows come in 32-column blocks
+  if (a.klens && (a.kmask || a.lse || a.drop_seed)) return hipErrorInvalidValue;   // key counts belong to the plain inference forward
   if (nsplit == 3) {
     if (!a.q_lo || !a.k_lo || !a.vt_lo) return hipErrorInvalidValue;
     return launch_attn_t<3, false>(a, s);
   }
   if (nsplit == 2) {                                  // "half" precision: fp16 hi-only planes, one product
     if (a.q_lo || a.k_lo || a.vt_lo) return hipErrorInvalidValue;
-    if (attn_fast_eligible(a)) return a.o_fmt == FMT_H8 ? launch_attn_fast<PF_H8>(a, s) : launch_attn_fast<PF_F16>(a, s);
+    if (attn_fast_eligible(a)) {
+      if (a.klens) return a.o_fmt == FMT_H8 ? launch_attn_fast<PF_H8, true>(a, s) : launch_attn_fast<PF_F16, true>(a, s);
+      return a.o_fmt == FMT_H8 ? launch_attn_fast<PF_H8>(a, s) : launch_attn_fast<PF_F16>(a, s);
+    }
     return launch_attn_t<1, true>(a, s);
   }
   if (a.o_fmt != FMT_BF16) return hipErrorInvalidValue;

@@ -18,8 +18,14 @@
 // exponent's fma, same m / alpha / l recurrences including the contracted l * alpha + psum, psum in (js, r) order, the alpha != 1
 // skip, the same conversions): the two kernels agree bit for bit, which tests/test_attention_fast_gpu.py asserts.
 // Eligibility: attn_fast_eligible() in attention.hip.  No key masking, no ragged tiles, no lo planes: none of those branches exist here.
+// LENS (a separate instantiation, as WLSE / DROP are of attn_kernel: the kernels without it compile to what they were): per-utterance key
+// counts (AttnArgs::klens).  Utterance b walks ceil(len_b / 64) key tiles -- whole tiles beyond its length are never staged -- and its
+// partial last tile takes a workgroup-uniform slow path (peeled out of the loop over whole tiles) that does what attn_kernel does with keys
+// at or beyond Nk: K rows staged as zeros, the V^T chunk cut with mask_chunk, scores set to -inf.  Nk stays the stride of every address.
 #pragma once
 #include "gemm_epi_fast.h"
+
+#include <type_traits>
 
 namespace ns2 {
 
@@ -48,7 +54,7 @@ NS2_DEVINL void af_put4(unsigned char* rowp, int c, float v0, float v1, float v2
   }
 }
 
-template <int PF>
+template <int PF, bool LENS = false>
 __global__ __launch_bounds__(256, 2) void attn_fast_kernel(const AttnArgs a) {
   using G = AtGeom<64>;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -62,6 +68,8 @@ __global__ __launch_bounds__(256, 2) void attn_fast_kernel(const AttnArgs a) {
   bid /= nqt;
   const int h = bid % a.H, b = bid / a.H;
   const int qrow0 = qt * AF_QB + wave * 64;            // block A: rows qrow0 + l31, block B: 32 further
+  int nk = a.Nk;                                       // keys this utterance attends to
+  if constexpr (LENS) nk = min(max(a.klens[b], 1), a.Nk);
 
   // ---- Q fragments (B operand of S^T = K Q^T): lane holds Q[q = l31][d = 16c + 8hi .. +7] of each block
   bf16x8 qf[2][4];
@@ -88,7 +96,20 @@ __global__ __launch_bounds__(256, 2) void attn_fast_kernel(const AttnArgs a) {
       rv[i] = ld16g(vp + key0 + i * vstep);
     }
   };
-  auto store_tile = [&](int s) {
+  auto store_tile = [&](int s, int key0) {               // key0: first key of the tile in the registers (read with LENS only)
+    if constexpr (LENS) {
+      // the utterance's partial last tile: what lies at or beyond its length may hold anything.  Cut here, where the loaded registers are
+      // waited for anyway, not behind the loads: the loop's issue order stays that of the kernel without lengths
+      if (key0 + 64 > nk) {
+        const int nvalid = nk - key0 - sch * 8;          // of this thread's 8-key V^T chunks
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+          if (key0 + srow + 32 * i >= nk) rk[i] = make_uint4(0u, 0u, 0u, 0u);
+          if (nvalid <= 0) rv[i] = make_uint4(0u, 0u, 0u, 0u);
+          else if (nvalid < 8) rv[i] = mask_chunk(rv[i], nvalid);
+        }
+      }
+    }
     unsigned char* base = smem + s * AF_STAGE + st_off;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -180,25 +201,40 @@ __global__ __launch_bounds__(256, 2) void attn_fast_kernel(const AttnArgs a) {
         }
   };
 
-  const int ntiles = a.Nk / 64;
+  const int ntiles = LENS ? (nk + 63) / 64 : a.Nk / 64;
   load_tile(0);
-  store_tile(0);
+  store_tile(0, 0);
   __syncthreads();
 
-  for (int t = 0; t < ntiles; ++t) {
-    const bool more = (t + 1) < ntiles;
+  // one key tile.  masked (a type: the whole tiles' body has no branch for it): the utterance's partial last tile, scores of keys at or
+  // beyond its length are -inf before the softmax
+  auto tile = [&](int t, bool more, auto masked) {
     if (more) load_tile((t + 1) * 64);                   // in flight during this tile's products
     const unsigned char* sb = smem + (t & 1) * AF_STAGE;
     f32x16 sa[2], sbk[2];
     uint4 pa[2][2], pb[2][2];
     scores(sa, qf[0], sb);
     scores(sbk, qf[1], sb);                              // same K fragments as S_A; the compiler issues all 16 MFMAs before softmax_A
+    if constexpr (decltype(masked)::value) {             // register r of sub-tile js is key 64 t + 32 js + 16 (r >> 3) + 8 hi + (r & 7) (attn_kernel)
+#pragma unroll
+      for (int js = 0; js < 2; ++js)
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+          if (t * 64 + 32 * js + 16 * (r >> 3) + 8 * hi + (r & 7) >= nk) { sa[js][r] = -INFINITY; sbk[js][r] = -INFINITY; }
+    }
     softmax(sa, m_run[0], l_run[0], ot[0], pa);
     pv(ot[0], pa, sb);                                   // the compiler places block B's maximum and exponentials in PV_A's and PV_B's gaps
     softmax(sbk, m_run[1], l_run[1], ot[1], pb);
     pv(ot[1], pb, sb);                                   // same V^T fragments as PV_A
-    if (more) store_tile((t + 1) & 1);                   // the other stage: every wave left it at the previous barrier
+    if (more) store_tile((t + 1) & 1, (t + 1) * 64);     // the other stage: every wave left it at the previous barrier
     __syncthreads();
+  };
+  if constexpr (!LENS) {
+    for (int t = 0; t < ntiles; ++t) tile(t, (t + 1) < ntiles, std::false_type{});
+  } else {
+    const int nfull = nk / 64;                           // whole tiles, then at most one partial tile: a workgroup-uniform path of its own
+    for (int t = 0; t < nfull; ++t) tile(t, (t + 1) < ntiles, std::false_type{});
+    if (nfull < ntiles) tile(nfull, false, std::true_type{});
   }
 
   // ---- normalise, convert, stage through the wave's share of the tile buffers (free after the last barrier), store whole row segments

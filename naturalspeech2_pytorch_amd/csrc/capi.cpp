@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/ns2hip_pitch.h"
+#include "../../include/ns2hip_ragged.h"
 #include "ns2_host.h"
 
 namespace ns2 {
@@ -252,6 +253,20 @@ static int attn_args_from(const ns2_attn_args* p, AttnArgs* out) {
 extern "C" int ns2_attention_fwd(const ns2_attn_args* p, void* stream) {
   AttnArgs a;
   if (int rc = attn_args_from(p, &a)) return rc;
+  HIPRET(launch_attention(a, p->precision, (hipStream_t)stream));
+  return NS2_OK;
+}
+
+// include/ns2hip_ragged.h: what this entry refuses comes first, under its own name; the block itself is ns2_attention_fwd's
+extern "C" int ns2_attention_fwd_lens(const ns2_attn_args* p, const int* key_lens, void* stream) {
+  ARGCHK(p != nullptr, "ns2_attention_fwd_lens: null argument block");
+  ARGCHK(key_lens != nullptr, "ns2_attention_fwd_lens: key_lens is null (ns2_attention_fwd is the call without lengths)");
+  ARGCHK(!p->key_mask, "ns2_attention_fwd_lens: key_mask together with key_lens (one way of shortening the keys per call)");
+  ARGCHK(!p->lse, "ns2_attention_fwd_lens: lse together with key_lens (the training forward takes no lengths)");
+  ARGCHK(p->dropout_p == 0.f, "ns2_attention_fwd_lens: dropout together with key_lens (the training forward takes no lengths)");
+  AttnArgs a;
+  if (int rc = attn_args_from(p, &a)) return rc;
+  a.klens = key_lens;
   HIPRET(launch_attention(a, p->precision, (hipStream_t)stream));
   return NS2_OK;
 }

@@ -22,6 +22,7 @@
 #include <string>
 #include <vector>
 
+#include "../../include/ns2hip_ragged.h"
 #include "ns2_host.h"
 #include "gemm_route.h"
 
@@ -942,6 +943,7 @@ struct StepArgs {                // what forward_impl resolved for the whole bat
   const float* x; float* out;
   const float* call; int cld;    // [gamma | beta] blocks of all FiLM / adaptive-norm projections; row b at call + b * cld
   int n_cond, N;
+  const int* lens = nullptr;     // ragged batch (include/ns2hip_ragged.h): frames per utterance, int32 [B] on the device; null = N each
 };
 
 int enqueue(ns2_model* m, const Launch& l, bool counted, hipStream_t s);
@@ -1068,7 +1070,10 @@ void describe_rows(const ns2_model* m, const Work& w0, const CondState* cs, cons
     GemmArgs qkv = product(ly.qkv, xn, dp, M);
     set_qkv(qkv, prec, N, 2 * a, qk.hi, qk.lo, 2 * a); qkv.vt_hi = vt.hi; qkv.vt_lo = vt.lo; qkv.vt_ld = w0.Nkp;
     gemm(qkv, prec, PC_GEMM_QKV);
-    attention(attn_args(qk.hi, qk.lo, 2 * a, 0, qk.hi, qk.lo, 2 * a, a, vt, w0.Nkp, o, a, B, H, N, N, m->cfg.dim_head), prec);
+    // the one place of a step where a frame sees later frames: a ragged batch hands its utterances' own key counts to it, and to nothing else
+    AttnArgs sa = attn_args(qk.hi, qk.lo, 2 * a, 0, qk.hi, qk.lo, 2 * a, a, vt, w0.Nkp, o, a, B, H, N, N, m->cfg.dim_head);
+    if (st.lens) sa.klens = st.lens + b0;
+    attention(sa, prec);
     // out-projection + residual, then the norm of what follows: the cross attention (conditioned) or the feed-forward
     update_then_norm(ly.out, o, a, nullptr, true, prec, nullptr, layer_cond(l, cond ? 1 : m->nnorm - 1), cond ? xn : xn_ff,
                      l == 0 ? Launch::OUT_PROJ : Launch::NONE);
@@ -1175,7 +1180,7 @@ extern "C" int ns2_debug_chains_last(void) { return g_chains_last.load(std::memo
 // cond_row != null: the step's time conditioning comes from a row of the table ns2_model_time_table built ahead of the run
 // (the sampler's times are known up front and shared by the batch, NS2:1303-1308): no projection is launched in the step
 static int forward_impl(ns2_model* m, const float* x, const float* times, const float* cond_row, const void* cond_state, int n_cond, float* out,
-                        int B, int N, void* workspace, int64_t workspace_bytes, void* stream) {
+                        int B, int N, void* workspace, int64_t workspace_bytes, void* stream, const int* lens = nullptr) {
   if (!m || !m->finalized) { set_error("model not finalized"); return NS2_ERR_STATE; }
   if (!x || (!times && !cond_row) || !out || B <= 0 || N <= 0) { set_error("bad forward arguments"); return NS2_ERR_ARG; }
   const bool cond = m->cfg.condition_on_prompt;
@@ -1194,6 +1199,7 @@ static int forward_impl(ns2_model* m, const float* x, const float* times, const 
   // ---- t = to_time_cond(times) [, prompt_cond]  (NS2:944-960), then every conditioning projection of the step at once: the only
   // batch-wide work of a step, on the caller's stream in front of the chains
   StepArgs st{x, out, w.condall, Jtot, n_cond, N};
+  st.lens = lens;                          // not part of the chain rule's cached verdict: the rule reads the GEMMs' routes, and each step describes its chains anew
   if (cond_row) {
     if (cond) HIPRET(launch_add_row(cond_row, cs.pbias, w.condall, B, Jtot, s));     // time half (hoisted) + prompt half (per utterance)
     else { st.call = cond_row; st.cld = 0; }                                          // every utterance reads the same row
@@ -1347,6 +1353,14 @@ extern "C" int ns2_model_forward_row(ns2_model* m, const float* x, const float* 
                                      int B, int N, void* workspace, int64_t workspace_bytes, void* stream) {
   if (!cond_row) { set_error("ns2_model_forward_row: null conditioning row"); return NS2_ERR_ARG; }
   return forward_impl(m, x, nullptr, cond_row, cond_state, n_cond, out, B, N, workspace, workspace_bytes, stream);
+}
+
+// include/ns2hip_ragged.h
+extern "C" int ns2_model_forward_lens(ns2_model* m, const float* x, const float* times, const float* cond_row, const int* frame_lens,
+                                      const void* cond_state, int n_cond, float* out, int B, int N, void* workspace, int64_t workspace_bytes,
+                                      void* stream) {
+  if ((times != nullptr) == (cond_row != nullptr)) { set_error("ns2_model_forward_lens: exactly one of times / cond_row"); return NS2_ERR_ARG; }
+  return forward_impl(m, x, times, cond_row, cond_state, n_cond, out, B, N, workspace, workspace_bytes, stream, frame_lens);
 }
 
 // ------------------------------------------------------------------------------------------------ hoisted time conditioning

@@ -138,6 +138,11 @@ struct AttnArgs {
   // attention dropout of the training kernel (dropout_keep.h; needs lse and precision 3): drop_seed = two 32-bit words in DEVICE memory
   // (null = no dropout), drop_thr = round(p 2^32), drop_scale = 1 / (1 - p), drop_call = index of this attention inside the pass
   const uint32_t* drop_seed = nullptr; uint32_t drop_thr = 0u, drop_call = 0u; float drop_scale = 1.f;
+  // ragged batches (include/ns2hip_ragged.h): per-utterance key counts in DEVICE memory, int32 [B], read by the kernels alone (never on
+  // the host: a captured launch follows rewritten values).  Utterance b attends to keys [0, clamp(klens[b], 1, Nk)); keys beyond are
+  // treated as keys beyond Nk are (score -inf, K rows and V^T columns read as zeros, so they may hold anything); Nk stays the stride.
+  // null = every utterance has Nk keys.  Excludes kmask, lse and dropout.
+  const int* klens = nullptr;
 };                                                       // precision: 3 bf16x3, 1 bf16, 2 and 4: one IEEE-half product
 hipError_t launch_attention(const AttnArgs& a, int precision, hipStream_t s);
 long long attention_fast_launches();                                   // test hook: launches that took attn_fast_kernel so far (ns2_debug_attention_fast_launches)

@@ -3,6 +3,7 @@ reference's own call signatures:
 
     NaturalSpeech2(model, codec=None, *, timesteps=1000, use_ddim=True, noise_schedule='sigmoid', objective='v', ...)   NS2:1163-1197
     .sample(*, length, prompt=None, batch_size=1, cond_scale=1., text=None, text_lens=None)                              NS2:1457-1466
+            (`length` may also be one frame count per utterance, or None with `text`: a ragged batch, see `sample`)
     .forward(audio, text=None, text_lens=None, mel=None, mel_lens=None, codes=None, prompt=None, pitch=None, ...)       NS2:1503-1515
     .ddim_sample(shape, prompt=None, time_difference=None, cond_scale=1., cond=None)                                     NS2:1380
 
@@ -32,6 +33,7 @@ kernel (`ns2_ddim_step`), the step-invariant conditioning is computed once per `
 update) can be captured into a HIP graph and replayed (`use_graph=True`).
 """
 import math
+import numbers
 from functools import partial
 
 import torch
@@ -169,8 +171,12 @@ class NaturalSpeech2(nn.Module):
     # ------------------------------------------------------------------ sampling (NS2:1379-1431)
     @torch.no_grad()
     def ddim_sample(self, shape, prompt=None, time_difference=None, cond_scale=1., cond=None, noise=None, use_graph=False,
-                    on_saturation="demote"):
+                    on_saturation="demote", lens=None):
         """`prompt` here is what the reference passes at NS2:1486-1491: the ENCODED prompt [b, n_p, dim_prompt].
+
+        lens (not in the reference): frames per utterance of a ragged batch, integer [b], each in [1, shape[1]].  Every step hands
+        them to the model (`Model.forward(lens=)`: the self-attention kernels read them on the device), so utterance i is denoised as
+        it would be alone at lens[i] frames; latent frames at or beyond lens[i] come back as exactly 0.
 
         on_saturation (not in the reference): what to do when a checkpoint's activations leave the IEEE-half range in one of the
         fast precisions (half / mixed / hybrid: conversions clamp at 65504 -- finite but wrong; the model counts them on the
@@ -181,13 +187,18 @@ class NaturalSpeech2(nn.Module):
         from ._lib import Ns2Error
         batch, device = shape[0], self.device
         start = torch.randn(shape, device=device) if noise is None else noise.to(device).float().clone()
+        if lens is not None:                             # one device buffer for the run: what a captured step keeps reading
+            lens = torch.as_tensor(lens).to(device=device, dtype=torch.int32).contiguous()
+            assert lens.shape == (batch,), f"lens must hold one frame count per utterance: [{batch}]"
         for attempt in (0, 1):
             if hasattr(self.model, "refresh_weights"):
                 self.model.refresh_weights()        # parameters rewritten through `.data` since the last pack (EMA) -> re-pack
             if hasattr(self.model, "clear_cond_cache"):
                 self.model.clear_cond_cache()
             try:
-                audio = self._ddim_loop(start.clone(), prompt, cond, cond_scale, use_graph)
+                audio = self._ddim_loop(start.clone(), prompt, cond, cond_scale, use_graph, lens)
+                if lens is not None:
+                    audio = audio.masked_fill(torch.arange(audio.shape[1], device=audio.device)[None, :, None] >= lens[:, None, None], 0.)
                 if hasattr(self.model, "check_saturation") and audio.is_cuda:
                     # the model polls the device counters every few forwards on its own (any caller); the end of a run takes one
                     # synchronous look (Ns2Error on a new count)
@@ -202,44 +213,49 @@ class NaturalSpeech2(nn.Module):
                               f"the sampling run with precision='exact' and keeping the model there ({e})")
                 self.model.precision = "exact"
 
-    def _ddim_loop(self, audio, prompt, cond, cond_scale, use_graph):
+    def _ddim_loop(self, audio, prompt, cond, cond_scale, use_graph, lens=None):
         batch, device = audio.shape[0], audio.device
         pairs = self.get_sampling_timesteps(batch, device=device)
         # `time_difference` only shifts times_next AFTER gamma_next was taken (NS2:1396-1406): it has no effect upstream either
         if not self._fused_ddim_ok():
-            return self._ddim_sample_unfused(audio, pairs, prompt, cond, cond_scale)
+            return self._ddim_sample_unfused(audio, pairs, prompt, cond, cond_scale, lens)
         # the run's times are known here and shared by the batch, so every time-conditioning projection of the run is
         # computed once, ahead of the loop; step i reads row i (Model.time_table)
         table = None
         if hasattr(self.model, "time_table") and audio.is_cuda:
             table = self.model.time_table(torch.stack([p[0][0] for p in pairs]), batch)
         if use_graph:
-            return self._ddim_sample_graph(audio, pairs, prompt, cond, cond_scale, table)
+            return self._ddim_sample_graph(audio, pairs, prompt, cond, cond_scale, table, lens)
+        ragged = {} if lens is None else dict(lens=lens)
         for i, (times, times_next) in enumerate(pairs):
-            kw = {} if table is None else dict(cond_row=table[i])
+            kw = dict(ragged) if table is None else dict(ragged, cond_row=table[i])
             out = self.model.forward_with_cond_scale(audio, times, prompt=prompt, cond_scale=cond_scale, cond=cond, **kw)
             ops.ddim_step(audio, out, times, times_next, self.objective, self.noise_schedule, self.scale, out=audio)
         return audio
 
-    def _ddim_sample_unfused(self, audio, pairs, prompt, cond, cond_scale):
+    def _ddim_sample_unfused(self, audio, pairs, prompt, cond, cond_scale, lens=None):
         """non-default `schedule_kwargs`: the schedule is evaluated by the host-side functions above, the model step is HIP"""
+        ragged = {} if lens is None else dict(lens=lens)
         for times, times_next in pairs:
             g, gn = self.gamma_schedule(times)[:, None, None], self.gamma_schedule(times_next)[:, None, None]
             alpha, sigma = torch.sqrt(g) * self.scale, torch.sqrt(1 - g)
             alpha_n, sigma_n = torch.sqrt(gn) * self.scale, torch.sqrt(1 - gn)
-            out = self.model.forward_with_cond_scale(audio, times, prompt=prompt, cond_scale=cond_scale, cond=cond)
+            out = self.model.forward_with_cond_scale(audio, times, prompt=prompt, cond_scale=cond_scale, cond=cond, **ragged)
             x0 = {"x0": lambda: out, "eps": lambda: _safe_div(audio - sigma * out, alpha),
                   "v": lambda: alpha * audio - sigma * out}[self.objective]()
             eps = _safe_div(audio - alpha * x0, sigma)
             audio = x0 * alpha_n + eps * sigma_n
         return audio
 
-    def _ddim_sample_graph(self, audio, pairs, prompt, cond, cond_scale, table=None):
+    def _ddim_sample_graph(self, audio, pairs, prompt, cond, cond_scale, table=None, lens=None):
         """one (model + DDIM update) step captured in a HIP graph; times (and the step's row of the conditioning table) are device
-        buffers rewritten per step."""
+        buffers rewritten per step.  The lengths of a ragged batch are a device buffer the captured kernels read: nothing of the
+        step reads them on the host."""
         t_buf, tn_buf = pairs[0][0].clone(), pairs[0][1].clone()
         row = table[0].clone() if table is not None else None
         kw = {} if row is None else dict(cond_row=row)
+        if lens is not None:
+            kw["lens"] = lens
         step = lambda: ops.ddim_step(                                                   # noqa: E731
             audio, self.model.forward_with_cond_scale(audio, t_buf, prompt=prompt, cond_scale=cond_scale, cond=cond, **kw),
             t_buf, tn_buf, self.objective, self.noise_schedule, self.scale, out=audio)
@@ -290,30 +306,50 @@ class NaturalSpeech2(nn.Module):
                 mod.refresh_weights()
 
     @torch.no_grad()
-    def text_to_cond(self, text, prompt_enc):
+    def text_to_cond(self, text, prompt_enc, text_lens=None, return_lens=False):
         """NS2:1476-1483: phoneme_enc(text) -> DurationPitchPredictor -> the length regulator (durations truncated to whole
         frames, pitch embedded through f0_to_coarse) -> the frame-aligned conditioning [b, dim_prompt, n_frames], n_frames = the
         longest utterance (one host read, the reference's `.item()`).  Every duration truncating to 0 frames leaves nothing to
-        condition on: the reference fails there inside cond_to_model_dim; here it is a ValueError."""
+        condition on: the reference fails there inside cond_to_model_dim; here it is a ValueError.
+        Not in the reference (the ragged mode of `sample`): `text_lens` [b] -- phonemes at or beyond text_lens[i] contribute no
+        frames (their predicted durations count as 0); `return_lens=True` -> (cond, the utterances' own frame totals, integer [b])."""
         assert hasattr(self, "duration_pitch"), "construct NaturalSpeech2 with build_duration_pitch=True"
         phoneme_enc = self.phoneme_enc(text)
         duration, pitch = self.duration_pitch(phoneme_enc, prompt_enc)
+        if text_lens is not None:
+            pad = torch.arange(duration.shape[1], device=duration.device)[None] >= torch.as_tensor(text_lens, device=duration.device)[:, None]
+            duration = duration.masked_fill(pad, 0.)
         table = self.pitch_emb.weight
         if phoneme_enc.is_cuda:
-            cond = ops.length_regulate(duration.float().contiguous(), pitch.float().contiguous(),
-                                       phoneme_enc.float().contiguous(), table.detach().float().contiguous())
+            cond, totals = ops.length_regulate(duration.float().contiguous(), pitch.float().contiguous(),
+                                               phoneme_enc.float().contiguous(), table.detach().float().contiguous(), return_totals=True)
         else:
             from .autograd_path import length_regulate
-            cond = length_regulate(duration, pitch, phoneme_enc, table)
+            cond, totals = length_regulate(duration, pitch, phoneme_enc, table, return_totals=True)
         if cond.shape[-1] == 0:
             raise ValueError("every predicted duration truncates to 0 frames: there is no aligned conditioning to sample from")
-        return cond
+        return (cond, totals) if return_lens else cond
 
     @torch.no_grad()
-    def sample(self, *, length, prompt=None, batch_size=1, cond_scale=1., text=None, text_lens=None,
-               cond=None, prompt_enc=None, noise=None, use_graph=False):
+    def sample(self, *, length=None, prompt=None, batch_size=1, cond_scale=1., text=None, text_lens=None,
+               cond=None, prompt_enc=None, noise=None, use_graph=False, return_lens=False):
         """NS2:1457-1501.  Extra keywords (not in the reference): `cond` / `prompt_enc` = pre-computed conditioning (module
-        docstring), `noise` = injected initial latents (parity tests), `use_graph` = HIP-graph replay of the step."""
+        docstring), `noise` = injected initial latents (parity tests), `use_graph` = HIP-graph replay of the step.
+
+        Ragged batches (not in the reference, which accepts `text_lens` and ignores it).  `length` an int: every utterance has that
+        many frames, as upstream.  `length` a 1-D integer tensor / sequence of one frame count per utterance, or `length=None` with
+        `text=` (the counts are then the utterances' own totals of predicted durations, and phonemes at or beyond `text_lens[i]`
+        contribute no frames): the batch is denoised at max(length) frames with the counts handed to the self-attention kernels, so
+        utterance i is what `sample` gives for it alone at its own length; its frames (samples, with a codec) past its end come back
+        as exactly 0.  `return_lens=True` -> (audio, lens): integer [b], in frames without a codec, in samples with one."""
+        if length is None and (text is None or cond is not None):
+            raise ValueError("sample(length=None) takes the utterances' lengths from the predicted durations: it needs text= (and no cond=)")
+        lens = None
+        if length is not None and not isinstance(length, numbers.Integral):
+            lens = torch.as_tensor(length)
+            if lens.ndim != 1 or lens.dtype.is_floating_point or lens.numel() == 0:
+                raise ValueError("length must be an int or a 1-D integer tensor / sequence of one frame count per utterance")
+            lens = lens.long()
         self.refresh_weights()
         p_enc = None
         if self.conditional:
@@ -324,18 +360,38 @@ class NaturalSpeech2(nn.Module):
                     "sample(text=...) derives the aligned conditioning with the DurationPitchPredictor (NS2:1478-1483), which is "
                     "not built by default: construct with `build_duration_pitch=True`, or pass the aligned conditioning as "
                     "`cond=` [b, dim_prompt, n_frames]")
-            if cond is None:
+            if cond is None and length is None:
+                cond, lens = self.text_to_cond(text, p_enc, text_lens=text_lens, return_lens=True)
+                lens = lens.long()
+            elif cond is None:
                 cond = self.text_to_cond(text, p_enc)
             batch_size = p_enc.shape[0]
+        elif length is None:
+            raise ValueError("sample(length=None) needs a conditional model: the lengths come from the predicted durations of text=")
         elif prompt is not None:
             batch_size = prompt.shape[0]                                               # NS2:1485-1486
+        if lens is not None:
+            if lens.shape[0] != batch_size:
+                raise ValueError(f"length holds {lens.shape[0]} frame counts for a batch of {batch_size}")
+            lens = lens.to(self.device)
+            length = int(lens.max().item())                                           # one host read, before the loop (length_regulate has the same)
+            if length < 1:
+                raise ValueError("every utterance has 0 frames")
         audio = self.ddim_sample((batch_size, length, self.dim), prompt=p_enc, cond=cond, cond_scale=cond_scale, noise=noise,
-                                 use_graph=use_graph)
+                                 use_graph=use_graph, **({} if lens is None else dict(lens=lens)))
+        ragged = lens is not None
+        if return_lens and not ragged:
+            lens = torch.full((batch_size,), length, dtype=torch.long, device=audio.device)
         if self.codec is not None:
+            # the 24 kHz SEANet decoder is causal: the padded batch decodes in one pass, an utterance's samples do not see its padding
             audio = self.codec.decode(audio)
             if audio.ndim == 3:
                 audio = audio[:, 0]
-        return audio
+            if lens is not None:
+                lens = lens.to(audio.device) * self.seq_len_multiple_of
+            if ragged:
+                audio = audio.masked_fill(torch.arange(audio.shape[-1], device=audio.device)[None] >= lens[:, None], 0.)
+        return (audio, lens) if return_lens else audio
 
     # ------------------------------------------------------------------ training loss (NS2:1503-1684)
     def text_forward_cond(self, text, text_lens, mel, mel_lens, pitch, prompt_enc, return_aux_losses=False):

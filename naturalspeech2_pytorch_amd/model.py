@@ -376,7 +376,7 @@ class HipDenoiserMixin:
     CFG_ONE_BATCH_MAX = 8
 
     @torch.no_grad()
-    def _forward_hip_cfg(self, x, times, prompt, cond, cond_scale, cond_row=None):
+    def _forward_hip_cfg(self, x, times, prompt, cond, cond_scale, cond_row=None, lens=None):
         from . import ops
         dim = self._hip_cfg["dim"]
         self._guards()
@@ -391,7 +391,17 @@ class HipDenoiserMixin:
         x2 = torch.cat((xin, xin), dim=0)
         out2 = torch.empty_like(x2)
         lib = _lib.load()
-        if cond_row is None:
+        if lens is not None:                             # the null half has the conditioned half's lengths
+            l1 = _device_lens(lens, B, xin.device)
+            t2 = None
+            if cond_row is None:
+                t = times.to(device=xin.device, dtype=torch.float32).contiguous()
+                t2 = torch.cat((t, t))
+            check(lib.ns2_model_forward_lens(ns.handle, x2.data_ptr(), None if t2 is None else t2.data_ptr(),
+                                             None if cond_row is None else cond_row.data_ptr(), torch.cat((l1, l1)).data_ptr(),
+                                             state.data_ptr(), n_c, out2.data_ptr(), 2 * B, N, ws.data_ptr(), ws.numel(),
+                                             torch.cuda.current_stream().cuda_stream), "ns2_model_forward_lens")
+        elif cond_row is None:
             t = times.to(device=xin.device, dtype=torch.float32).contiguous()
             check(lib.ns2_model_forward(ns.handle, x2.data_ptr(), torch.cat((t, t)).data_ptr(), state.data_ptr(), n_c, out2.data_ptr(), 2 * B, N,
                                         ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream), "ns2_model_forward")
@@ -427,8 +437,11 @@ class HipDenoiserMixin:
         return table
 
     # ---- forward (NS2:929-1000)
-    def forward(self, x, times, prompt=None, prompt_mask=None, cond=None, cond_drop_prob=None, *, cond_row=None):
-        """`cond_row` (not in the reference): a row of `time_table()` standing in for `times` (inference only)"""
+    def forward(self, x, times, prompt=None, prompt_mask=None, cond=None, cond_drop_prob=None, *, cond_row=None, lens=None):
+        """`cond_row` (not in the reference): a row of `time_table()` standing in for `times` (inference only).
+        `lens` (not in the reference): frames per utterance of a ragged batch, integer [b], each in [1, n] -- out[i, :lens[i]] is
+        what utterance i gives alone at its own length, whatever x (and cond) hold from lens[i] on; rows from lens[i] on are
+        finite and meaningless.  The self-attention kernels read the lengths on the device (sampling only)."""
         p = self.cond_drop_prob if cond_drop_prob is None else cond_drop_prob
         needs_grad = torch.is_grad_enabled() and (x.requires_grad or any(q.requires_grad for q in self.parameters()))
         stochastic = self._hip_cfg["condition_on_prompt"] and p not in (0, 0., 1, 1.)
@@ -436,12 +449,16 @@ class HipDenoiserMixin:
             # training (loss.backward(), NS2:1635/1886) and per-utterance stochastic conditioning dropout (a training /
             # validation feature, NS2:79-85) run the differentiable path: on an MI355X the HIP training kernels (training/model_pass.py),
             # on the CPU the PyTorch composite; sampling never gets here
+            if lens is not None:
+                raise NotImplementedError("lens: per-utterance lengths are a sampling feature (torch.no_grad()); the training pass and the "
+                                          "backward kernels take equal-length batches")
             self._native.autograd_seen = True
             return self._forward_autograd(x, times, prompt=prompt, prompt_mask=prompt_mask, cond=cond, cond_drop_prob=cond_drop_prob)
-        return self._forward_hip(x, times, prompt, prompt_mask, cond, cond_drop_prob, cond_row=cond_row)
+        ragged = {} if lens is None else dict(lens=lens)
+        return self._forward_hip(x, times, prompt, prompt_mask, cond, cond_drop_prob, cond_row=cond_row, **ragged)
 
     @torch.no_grad()
-    def _forward_hip(self, x, times, prompt=None, prompt_mask=None, cond=None, cond_drop_prob=None, out=None, cond_row=None):
+    def _forward_hip(self, x, times, prompt=None, prompt_mask=None, cond=None, cond_drop_prob=None, out=None, cond_row=None, lens=None):
         if prompt_mask is not None:
             raise NotImplementedError(_PROMPT_MASK_MSG)
         p = self.cond_drop_prob if cond_drop_prob is None else cond_drop_prob
@@ -471,7 +488,12 @@ class HipDenoiserMixin:
             ws = self._workspace(ns, B, N, pr.shape[1], n_c)
         else:
             ws = self._workspace(ns, B, N, 0, 0)
-        if cond_row is None:
+        if lens is not None:
+            check(_lib.load().ns2_model_forward_lens(ns.handle, xin.data_ptr(), t.data_ptr() if cond_row is None else None,
+                                                     None if cond_row is None else cond_row.data_ptr(), _device_lens(lens, B, xin.device).data_ptr(),
+                                                     state_ptr, n_c, out.data_ptr(), B, N, ws.data_ptr(), ws.numel(),
+                                                     torch.cuda.current_stream().cuda_stream), "ns2_model_forward_lens")
+        elif cond_row is None:
             check(_lib.load().ns2_model_forward(ns.handle, xin.data_ptr(), t.data_ptr(), state_ptr, n_c, out.data_ptr(), B, N,
                                                 ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream), "ns2_model_forward")
         else:
@@ -493,9 +515,10 @@ class HipDenoiserMixin:
         """NS2:914-927."""
         if (cond_scale != 1. and self._hip_cfg["condition_on_prompt"] and not torch.is_grad_enabled() and len(args) == 2 and args[0].is_cuda
                 and args[0].shape[0] <= self.CFG_ONE_BATCH_MAX and kwargs.get("prompt") is not None and kwargs.get("cond") is not None
-                and kwargs.get("prompt_mask") is None and set(kwargs) <= {"prompt", "cond", "cond_row", "prompt_mask"}
+                and kwargs.get("prompt_mask") is None and set(kwargs) <= {"prompt", "cond", "cond_row", "prompt_mask", "lens"}
                 and not torch.cuda.is_current_stream_capturing()):
-            return self._forward_hip_cfg(args[0], args[1], kwargs["prompt"], kwargs["cond"], cond_scale, cond_row=kwargs.get("cond_row"))
+            return self._forward_hip_cfg(args[0], args[1], kwargs["prompt"], kwargs["cond"], cond_scale, cond_row=kwargs.get("cond_row"),
+                                         lens=kwargs.get("lens"))
         logits = self.forward(*args, cond_drop_prob=0., **kwargs)
         if cond_scale == 1.:
             return logits
@@ -527,6 +550,14 @@ class HipDenoiserMixin:
             for k in bufs:
                 lib.ns2_model_debug_tap(ns.handle, k.encode(), None, 0)
         return out, bufs
+
+
+def _device_lens(lens, B, device):
+    """`lens` of a ragged batch as the kernels read it: int32 [B], contiguous, on `device`.  A tensor that already is one comes back
+    as it is -- no copy, no host read: a captured step keeps reading the caller's buffer, whose values may change between replays."""
+    l = torch.as_tensor(lens).to(device=device, dtype=torch.int32).contiguous()
+    assert l.shape == (B,), f"lens must hold one frame count per utterance: [{B}]"
+    return l
 
 
 # `prompt_mask` is in the reference's signature (NS2:929-937) but upstream cannot run with one: the resampler's attention

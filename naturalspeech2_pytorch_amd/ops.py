@@ -3,6 +3,7 @@
 PyTorch is plumbing here: device memory and the current HIP stream.  Every function launches hand-written HIP
 kernels through ctypes; nothing in this module computes with torch ops.
 """
+import ctypes
 from typing import Optional
 
 import torch
@@ -242,10 +243,11 @@ def wavenet_block(w: PackedWeight, a: Planes, seq_len: int, dilation: int, conv_
 
 
 def _attention_fwd(q: Planes, q_col0, k: Planes, k_col0, vt_hi, vt_lo, vt_ld, B, H, Nq, Nk, scale, precision, head_dim=64, o_precision=0,
-                   key_mask=None, want_lse=False, drop=None):
+                   key_mask=None, want_lse=False, drop=None, key_lens=None):
     """The one place that fills a ns2_attn_args (include/ns2hip.h) and calls ns2_attention_fwd -> (o, lse or None).  vt_hi / vt_lo:
     device addresses of the transposed value planes; o_precision: the format of o when it is not the operands' (0 = `precision`);
-    key_mask: uint8 [B, Nk] on the device; drop = (p, seed tensor on the device, call index) or None."""
+    key_mask: uint8 [B, Nk] on the device; drop = (p, seed tensor on the device, call index) or None; key_lens: int32 [B] on the
+    device, the call then goes through ns2_attention_fwd_lens (include/ns2hip_ragged.h)."""
     o = _out_planes(B * Nq, H * head_dim, q.device, o_precision or precision)
     lse = torch.empty(B, H, Nq, dtype=torch.float32, device=q.device) if want_lse else None
     p, seed, call = drop if drop is not None else (0.0, None, 0)
@@ -253,21 +255,31 @@ def _attention_fwd(q: Planes, q_col0, k: Planes, k_col0, vt_hi, vt_lo, vt_ld, B,
                       vt_hi=vt_hi, vt_lo=vt_lo, vt_ld=vt_ld, o_hi=o.hi, o_lo=o.lo, ldo=o.ld, B=B, H=H, Nq=Nq, Nk=Nk, scale=scale,
                       head_dim=head_dim, precision=precision, o_precision=o_precision, key_mask=_p(key_mask), lse=_p(lse),
                       dropout_p=p, dropout_seed=_p(seed), dropout_call=call)
-    check(_lib.load().ns2_attention_fwd(a, _stream()), "ns2_attention_fwd")
+    if key_lens is not None:
+        check(_lib.load().ns2_attention_fwd_lens(ctypes.byref(a), key_lens.data_ptr(), _stream()), "ns2_attention_fwd_lens")
+    else:
+        check(_lib.load().ns2_attention_fwd(a, _stream()), "ns2_attention_fwd")
     return o, lse
 
 
 def attention(q: Planes, k: Planes, vt: Planes, B: int, H: int, Nq: int, Nk: int, q_col0=0, k_col0=0, scale=None,
-              precision=3, key_mask: Optional[torch.Tensor] = None, head_dim: int = 64) -> Planes:
+              precision=3, key_mask: Optional[torch.Tensor] = None, head_dim: int = 64, key_lens: Optional[torch.Tensor] = None) -> Planes:
     """vt: transposed value planes [B * H*head_dim, vt_ld]; key_mask: optional bool/uint8 [B, Nk], True = attend (ATT:92-94);
-    head_dim 32 / 64 / 128, scale defaults to head_dim ** -0.5 (ATT:128)."""
+    head_dim 32 / 64 / 128, scale defaults to head_dim ** -0.5 (ATT:128).  key_lens (not in the reference): optional integer [B]
+    on the device, utterance b attends to keys [0, key_lens[b]) -- read by the kernel alone, clamped into [1, Nk]; Nk stays the
+    stride, and what lies at or beyond a length may hold anything.  Not together with key_mask."""
     if scale is None:
         scale = head_dim ** -0.5
     km = None
     if key_mask is not None:
         km = key_mask.to(torch.uint8).contiguous()
         assert km.shape == (B, Nk)
-    return _attention_fwd(q, q_col0, k, k_col0, vt.hi, vt.lo, vt.ld, B, H, Nq, Nk, scale, precision, head_dim=head_dim, key_mask=km)[0]
+    kl = None
+    if key_lens is not None:
+        kl = key_lens.to(device=q.device, dtype=torch.int32).contiguous()
+        assert kl.shape == (B,)
+    return _attention_fwd(q, q_col0, k, k_col0, vt.hi, vt.lo, vt.ld, B, H, Nq, Nk, scale, precision, head_dim=head_dim, key_mask=km,
+                          key_lens=kl)[0]
 
 
 def rmsnorm(x: torch.Tensor, seq_len: int = 0, gamma=None, cond=None, want_f32=False, precision: int = 3):
@@ -315,10 +327,10 @@ F0_MEL_MIN = float(1127 * torch.log(1 + torch.tensor(50.0) / 700))
 F0_MEL_MAX = float(1127 * torch.log(1 + torch.tensor(1100.0) / 700))
 
 
-def length_regulate(duration: torch.Tensor, pitch: torch.Tensor, enc: torch.Tensor, pitch_table: torch.Tensor) -> torch.Tensor:
+def length_regulate(duration: torch.Tensor, pitch: torch.Tensor, enc: torch.Tensor, pitch_table: torch.Tensor, return_totals: bool = False):
     """duration / pitch [B, n_ph], enc [B, n_ph, D], pitch_table [>= 256, D] -> the frame-aligned conditioning [B, D, n_frames]
     of NaturalSpeech2.sample (ns2_length_regulate).  n_frames = the longest utterance's sum of int(duration): one host read,
-    as the reference's `.item()` (NS2:92)."""
+    as the reference's `.item()` (NS2:92).  return_totals: (that, the utterances' own frame totals, int32 [B] on the device)."""
     duration, pitch, enc, table = _f32(duration), _f32(pitch), _f32(enc), _f32(pitch_table)
     B, n_ph = duration.shape
     D = enc.shape[-1]
@@ -331,7 +343,7 @@ def length_regulate(duration: torch.Tensor, pitch: torch.Tensor, enc: torch.Tens
     if n_frames > 0:
         check(lib.ns2_length_regulate(duration.data_ptr(), pitch.data_ptr(), enc.data_ptr(), table.data_ptr(), B, n_ph, D, n_frames,
                                       F0_MEL_MIN, F0_MEL_MAX, out.data_ptr(), _stream()), "ns2_length_regulate")
-    return out
+    return (out, totals) if return_totals else out
 
 
 def row_dot(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, relu: bool = False) -> torch.Tensor:
