@@ -1,5 +1,6 @@
 """ctypes binding of libns2hip.so, derived from its C ABI: include/ns2hip.h (and include/ns2hip_optim.h, the optimizer step, and
-include/ns2hip_pitch.h, the pitch extractor, and include/ns2hip_ragged.h, ragged batches, each into tables of its own) is parsed once, at import.
+include/ns2hip_pitch.h, the pitch extractor, include/ns2hip_ragged.h, ragged batches, and include/ns2hip_ragged_front.h, ragged prompts
+and text, each into tables of its own) is parsed once, at import.
 
 The HIP library is the product: importing this module FAILS LOUDLY when the header or the shared object is missing or the
 library does not export the full ABI -- there is no CPU / PyTorch fallback for the hot path.
@@ -28,6 +29,7 @@ HEADER_PATH = os.path.join(_HERE, "..", "include", "ns2hip.h")
 OPTIM_HEADER_PATH = os.path.join(_HERE, "..", "include", "ns2hip_optim.h")   # the optimizer step: a header and tables of its own
 PITCH_HEADER_PATH = os.path.join(_HERE, "..", "include", "ns2hip_pitch.h")   # the pitch extractor: likewise
 RAGGED_HEADER_PATH = os.path.join(_HERE, "..", "include", "ns2hip_ragged.h")   # per-utterance lengths: likewise
+FRONT_HEADER_PATH = os.path.join(_HERE, "..", "include", "ns2hip_ragged_front.h")   # ... through the front-end: likewise
 
 
 class Ns2Error(RuntimeError):
@@ -126,6 +128,11 @@ if not os.path.exists(RAGGED_HEADER_PATH):
 with open(RAGGED_HEADER_PATH) as _f:                             # ns2_attn_args / ns2_model are ns2hip.h's (its #include is not followed): their
     _, _, RAGGED_SIGNATURES = parse_header(_f.read())            # pointers are c_void_p here -- pass ctypes.byref(block)
 
+if not os.path.exists(FRONT_HEADER_PATH):
+    raise Ns2Error(f"{FRONT_HEADER_PATH} not found: the binding is derived from the header, it ships with the package's source tree")
+with open(FRONT_HEADER_PATH) as _f:
+    _, _, FRONT_SIGNATURES = parse_header(_f.read())
+
 _lib = None
 
 
@@ -138,7 +145,7 @@ def load():
         raise Ns2Error(f"{LIB_PATH} not found: build it with `python __graft_entry__.py` "
                        f"(or naturalspeech2_pytorch_amd/csrc/build.sh); there is no fallback path")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in {**SIGNATURES, **OPTIM_SIGNATURES, **PITCH_SIGNATURES, **RAGGED_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **OPTIM_SIGNATURES, **PITCH_SIGNATURES, **RAGGED_SIGNATURES, **FRONT_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -173,3 +180,8 @@ def pitch_header_symbols():
 def ragged_header_symbols():
     """Symbols declared in include/ns2hip_ragged.h"""
     return sorted(RAGGED_SIGNATURES)
+
+
+def front_header_symbols():
+    """Symbols declared in include/ns2hip_ragged_front.h"""
+    return sorted(FRONT_SIGNATURES)

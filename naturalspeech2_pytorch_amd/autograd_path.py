@@ -53,8 +53,23 @@ def _feedforward(x, ff, causal_conv):
     return getattr(ff, "2")(h)
 
 
-def model_forward_autograd(m, x, times, prompt=None, cond=None, cond_drop_prob=None, lens=None):
-    """`lens` (not in the reference; Model.forward's): frames per utterance of a ragged batch, integer [b].  The self-attention is the
+def _prefix_mask(lens, b, n, device):
+    """[b, n] bool, True on the rows [0, lens[i]) of utterance i; lengths clamped into [1, n] as the kernels do (include/ns2hip_ragged.h)"""
+    ln = torch.as_tensor(lens, device=device).long().clamp(1, n)
+    assert ln.shape == (b,), f"lengths must hold one count per utterance: [{b}]"
+    return torch.arange(n, device=device)[None] < ln[:, None]
+
+
+def _keep_rows(x_bnc, mask):
+    """rows outside the mask become exactly 0 -- a select, not a product: what lies there may be NaN"""
+    return x_bnc if mask is None else torch.where(mask[..., None], x_bnc, torch.zeros((), dtype=x_bnc.dtype, device=x_bnc.device))
+
+
+def model_forward_autograd(m, x, times, prompt=None, cond=None, cond_drop_prob=None, lens=None, prompt_lens=None):
+    """`prompt_lens` (not in the reference; Model.forward's): prompt rows per utterance, integer [b].  The prompt is seen in two places,
+    the mean of to_prompt_cond and the keys of the perceiver resampler: the mean runs over rows [0, prompt_lens[i]) and the resampler's
+    keys cat(latents, prompt) get the mask [all latents | those rows] (include/ns2hip_ragged_front.h).
+    `lens` (not in the reference; Model.forward's): frames per utterance of a ragged batch, integer [b].  The self-attention is the
     one place where a frame sees later frames, so it alone gets the key mask arange(n) < lens[:, None]: out[i, :lens[i]] is what
     utterance i gives alone.  The restatement of the HIP kernels' rule (include/ns2hip_ragged.h), lengths clamped into [1, n] as there."""
     b, n, _ = x.shape
@@ -81,14 +96,22 @@ def model_forward_autograd(m, x, times, prompt=None, cond=None, cond_drop_prob=N
             return torch.rand(b, device=x.device) < p
 
         dm = mask()
-        pc = F.silu(getattr(m.to_prompt_cond, "1")(prompt.mean(dim=1)))
+        res_mask = None
+        if prompt_lens is not None:
+            pm = _prefix_mask(prompt_lens, b, prompt.shape[1], x.device)
+            prompt = _keep_rows(prompt, pm)
+            pmean = prompt.sum(dim=1) / pm.sum(dim=1, keepdim=True).to(prompt.dtype)
+            res_mask = torch.cat((torch.ones(b, m.perceiver_resampler.latents.shape[0], dtype=torch.bool, device=x.device), pm), dim=1)
+        else:
+            pmean = prompt.mean(dim=1)
+        pc = F.silu(getattr(m.to_prompt_cond, "1")(pmean))
         pc = torch.where(dm[:, None], m.null_prompt_cond, pc)
         t = torch.cat((t, pc), dim=-1)
         pr = m.perceiver_resampler
         px = pr.proj_context(prompt) if hasattr(pr, "proj_context") else prompt
         lat = pr.latents[None].expand(b, -1, -1)
         for attn, ff in pr.layers:
-            lat = _attention(lat, attn, m.heads, context=px, include_queries=True) + lat
+            lat = _attention(lat, attn, m.heads, context=px, include_queries=True, key_mask=res_mask) + lat
             lat = _feedforward(lat, ff, False) + lat
         c = torch.where(dm[:, None, None], m.null_prompt_tokens, _rmsnorm(lat, pr.norm))
         cm = F.conv1d(cond, m.cond_to_model_dim.weight, m.cond_to_model_dim.bias)
@@ -134,12 +157,16 @@ def transformer_forward_autograd(tr, x, mask=None):
     return _rmsnorm(x, tr.norm) if hasattr(tr.norm, "gamma") else x
 
 
-def speech_prompt_encoder_autograd(enc, x):
-    h = x.transpose(1, 2)
+def speech_prompt_encoder_autograd(enc, x, lens=None):
+    """lens (not in the reference): prompt rows per utterance, integer [b].  The "same" convolutions read zeros behind a length (the input
+    and every convolution's output are zeroed there, as behind the end of an utterance alone), the Transformer's keys stop at it, and the
+    output rows from lens[i] on are 0: rows [0, lens[i]) are what utterance i gives alone (include/ns2hip_ragged_front.h)."""
+    mask = None if lens is None else _prefix_mask(lens, x.shape[0], x.shape[1], x.device)
+    h = _keep_rows(x, mask).transpose(1, 2)
     for m in enc.conv:
         if isinstance(m, torch.nn.Conv1d):
-            h = F.silu(F.conv1d(h, m.weight, m.bias, padding=enc.padding))
-    return transformer_forward_autograd(enc.transformer, h.transpose(1, 2))
+            h = _keep_rows(F.silu(F.conv1d(h, m.weight, m.bias, padding=enc.padding)).transpose(1, 2), mask).transpose(1, 2)
+    return _keep_rows(transformer_forward_autograd(enc.transformer, h.transpose(1, 2), mask=mask), mask)
 
 
 def phoneme_encoder_autograd(enc, ids, mask=None):
@@ -151,7 +178,23 @@ def phoneme_encoder_autograd(enc, ids, mask=None):
 
 
 # ---- DurationPitchPredictor (NS2:344-527) and the length regulator of text-conditioned sampling (NS2:87-104, 164-175, 1449-1455)
-def _dp_trunk_autograd(tr, x, prompts, training):
+def _group_norm_rows(h_bcn, norm, mask):
+    """nn.GroupNorm whose statistics of utterance i run over the rows inside mask[i] (biased variance, as F.group_norm)"""
+    if mask is None:
+        return F.group_norm(h_bcn, norm.num_groups, norm.weight, norm.bias, norm.eps)
+    b, c, n = h_bcn.shape
+    g = norm.num_groups
+    hg = h_bcn.reshape(b, g, c // g, n)
+    mm = mask[:, None, None, :]
+    zero = torch.zeros((), dtype=hg.dtype, device=hg.device)
+    cnt = (mask.sum(dim=1) * (c // g)).to(hg.dtype)[:, None, None, None]
+    mean = torch.where(mm, hg, zero).sum(dim=(2, 3), keepdim=True) / cnt
+    var = torch.where(mm, (hg - mean) ** 2, zero).sum(dim=(2, 3), keepdim=True) / cnt
+    out = ((hg - mean) * torch.rsqrt(var + norm.eps)).reshape(b, c, n)
+    return out * norm.weight[None, :, None] + norm.bias[None, :, None]
+
+
+def _dp_trunk_autograd(tr, x, prompts, training, text_mask=None, key_mask=None):
     # the trunk hands `dropout` to its Attention only; Block / ConvBlock keep their own default 0 (NS2:430-446): no dropout after the convolutions
     p = tr.dropout if training else 0.
     k = tr.kernel_size
@@ -161,19 +204,33 @@ def _dp_trunk_autograd(tr, x, prompts, training):
                 h = x.transpose(1, 2)
                 for b in blk.blocks:
                     h = F.conv1d(h, b.proj.weight, b.proj.bias, padding=k // 2)
-                    h = F.silu(F.group_norm(h, b.norm.num_groups, b.norm.weight, b.norm.bias, b.norm.eps))
-                x = (h + x.transpose(1, 2)).transpose(1, 2)
+                    h = _keep_rows(F.silu(_group_norm_rows(h, b.norm, text_mask)).transpose(1, 2), text_mask).transpose(1, 2)
+                x = _keep_rows((h + x.transpose(1, 2)).transpose(1, 2), text_mask)
             else:                                                     # ConvBlock (NS2:402-409)
-                x = F.silu(F.conv1d(x.transpose(1, 2), blk[1].weight, blk[1].bias, padding=k // 2)).transpose(1, 2)
-        x = _attention(_rmsnorm(x, norm), attn, tr.heads, context=prompts, include_queries=True, dropout_p=p) + x
+                x = _keep_rows(F.silu(F.conv1d(x.transpose(1, 2), blk[1].weight, blk[1].bias, padding=k // 2)).transpose(1, 2), text_mask)
+        x = _keep_rows(_attention(_rmsnorm(x, norm), attn, tr.heads, context=prompts, include_queries=True, key_mask=key_mask, dropout_p=p) + x,
+                       text_mask)
     head = tr.to_pred[0]
-    return F.relu(F.linear(x, head.weight, head.bias)[..., 0])
+    out = F.relu(F.linear(x, head.weight, head.bias)[..., 0])
+    return out if text_mask is None else torch.where(text_mask, out, torch.zeros((), dtype=out.dtype, device=out.device))
 
 
-def duration_pitch_autograd(dp, x, prompts):
+def duration_pitch_autograd(dp, x, prompts, text_lens=None, prompt_lens=None):
+    """text_lens / prompt_lens (not in the reference): phonemes / prompt rows per utterance, integer [b]; either alone is allowed, the
+    other side then counts as full.  Rows behind a length are zeros for the "same" convolutions, the GroupNorm statistics of utterance i
+    run over its own phonemes, the attention keys cat(norm(x), prompts) are [0, text_lens[i]) and [n, n + prompt_lens[i]), and the
+    durations and pitches from text_lens[i] on come back 0 (include/ns2hip_ragged_front.h)."""
     if isinstance(dp.phoneme_token_emb, torch.nn.Embedding):
         x = dp.phoneme_token_emb(x)
-    return tuple(_dp_trunk_autograd(tr, x, prompts, dp.training) for tr in (dp.to_duration_pred, dp.to_pitch_pred))
+    text_mask = key_mask = None
+    if text_lens is not None or prompt_lens is not None:
+        b, n, n_p = x.shape[0], x.shape[1], prompts.shape[1]
+        text_mask = None if text_lens is None else _prefix_mask(text_lens, b, n, x.device)
+        pm = None if prompt_lens is None else _prefix_mask(prompt_lens, b, n_p, x.device)
+        x, prompts = _keep_rows(x, text_mask), _keep_rows(prompts, pm)
+        ones = lambda k: torch.ones(b, k, dtype=torch.bool, device=x.device)          # noqa: E731
+        key_mask = torch.cat((ones(n) if text_mask is None else text_mask, ones(n_p) if pm is None else pm), dim=1)
+    return tuple(_dp_trunk_autograd(tr, x, prompts, dp.training, text_mask, key_mask) for tr in (dp.to_duration_pred, dp.to_pitch_pred))
 
 
 def f0_to_coarse(f0, f0_bin=256, f0_max=1100.0, f0_min=50.0):

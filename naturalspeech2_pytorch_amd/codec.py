@@ -116,6 +116,10 @@ class EncodecWrapperHIP(nn.Module):
     target_sample_hz = 24000
     seq_len_multiple_of = 320          # strides 2*4*5*8
     codebook_dim = 128
+    # The SEANet encoder is causal, but its reflect padding mirrors the first rows of an utterance: the last convolution (k = 7, at the
+    # frame rate) reads frames 1 .. 6 for its prefix.  A prompt of a padded batch keeps its padding out of its frames only from this
+    # many frames on (NaturalSpeech2.sample(prompt_lens=) with a raw-audio prompt checks it); the HIP encoder takes no shorter input.
+    min_causal_prompt_frames = 7
 
     def __init__(self, codebooks: torch.Tensor, encoder: Optional[Callable] = None, decoder: Optional[Callable] = None,
                  rq_backend: str = "composite"):

@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "../../include/ns2hip_ragged.h"
+#include "../../include/ns2hip_ragged_front.h"
 #include "ns2_host.h"
 #include "gemm_route.h"
 
@@ -581,6 +582,7 @@ struct Work {
   float *pmean, *ctxf, *latf, *condT, *projf;
   Planes ctxp, latp, cpl, rkv, rvt;
   int Nctx, Nctxp;
+  int* rklens;                                  // [B]: Lm + prompt length, the resampler's key counts (ns2_model_prepare_cond_lens)
 };
 static int64_t carve_work(const ns2_model* m, Work* w, void* base, int64_t cap, int B, int N, int n_prompt, int n_cond) {
   Carver c(base, cap);
@@ -631,6 +633,7 @@ static int64_t carve_work(const ns2_model* m, Work* w, void* base, int64_t cap, 
     w->cpl = take_planes(c, (int64_t)B * Lm * dp, il, f16);
     w->rkv = take_planes(c, (int64_t)B * w->Nctx * a, ail, afmt);
     w->rvt = take_planes(c, (int64_t)B * a * w->Nctxp, ail, afmt);
+    w->rklens = c.take<int>(B);
   }
   return rup64(c.off, 256);
 }
@@ -765,8 +768,11 @@ extern "C" int ns2_model_cond_stack(ns2_model* m, const void* state_a, const voi
   return NS2_OK;
 }
 
-extern "C" int ns2_model_prepare_cond(ns2_model* m, const float* prompt, int n_prompt, const float* cond, int n_cond, int drop,
-                                      int B, int N, void* cond_state, void* workspace, int64_t workspace_bytes, void* stream) {
+// prompt_lens: null, or the prompt rows that count per utterance (include/ns2hip_ragged_front.h): the mean of to_prompt_cond and the
+// resampler's keys stop there.  Rows behind a length may hold NaN: proj_context and the kv projection keep a row to itself, and the
+// attention kernel reads K rows and V^T columns beyond a key count as zeros.
+static int prepare_cond_impl(ns2_model* m, const float* prompt, int n_prompt, const int* prompt_lens, const float* cond, int n_cond, int drop,
+                             int B, int N, void* cond_state, void* workspace, int64_t workspace_bytes, void* stream) {
   if (!m || !m->finalized) { set_error("model not finalized"); return NS2_ERR_STATE; }
   if (!m->cfg.condition_on_prompt) { set_error("model is unconditional"); return NS2_ERR_STATE; }
   if (!prompt || !cond || !cond_state || n_prompt <= 0 || n_cond <= 0) { set_error("prompt and cond are required"); return NS2_ERR_ARG; }
@@ -794,7 +800,12 @@ extern "C" int ns2_model_prepare_cond(ns2_model* m, const float* prompt, int n_p
     HIPRET(launch_bcast_rows(m->null_cond, cs.condadd, B * n_cond, dim, dim, s));
   } else {
     // to_prompt_cond: mean over n -> Linear -> SiLU (NS2:858-862)
-    HIPRET(launch_mean_rows(prompt, B, n_prompt, dprompt, w.pmean, s));
+    if (prompt_lens) {
+      HIPRET(launch_mean_rows_lens(prompt, B, n_prompt, dprompt, prompt_lens, w.pmean, s));
+      HIPRET(launch_offset_lens(prompt_lens, B, n_prompt, Lm, w.rklens, s));
+    } else {
+      HIPRET(launch_mean_rows(prompt, B, n_prompt, dprompt, w.pmean, s));
+    }
     HIPRET(launch_skinny_linear(w.pmean, dprompt, m->wt_prompt, m->b_prompt, cs.prompt_cond, m->dt, B, dprompt, m->dt, 1, w.skinny_ws,
                                 w.skinny_ws_bytes, s));
     // perceiver resampler (NS2:532-579)
@@ -823,7 +834,9 @@ extern "C" int ns2_model_prepare_cond(ns2_model* m, const float* prompt, int n_p
       NSCHK(run_gemm(q, prec, s));
       set_qkv(kv, prec, Nctx, a, w.rkv.hi, w.rkv.lo, a); kv.vt_hi = w.rvt.hi; kv.vt_lo = w.rvt.lo; kv.vt_ld = w.Nctxp;
       NSCHK(run_gemm(kv, prec, s));
-      NSCHK(attention_call(w.qk.hi, w.qk.lo, a, 0, w.rkv.hi, w.rkv.lo, a, 0, w.rvt, w.Nctxp, w.o, a, B, H, Lm, Nctx, prec, s, m->cfg.dim_head));
+      AttnArgs ra = attn_args(w.qk.hi, w.qk.lo, a, 0, w.rkv.hi, w.rkv.lo, a, 0, w.rvt, w.Nctxp, w.o, a, B, H, Lm, Nctx, m->cfg.dim_head);
+      if (prompt_lens) ra.klens = w.rklens;
+      HIPRET(launch_attention(ra, prec, s));
       GemmArgs o = product(r.out, w.o, a, B * Lm);
       o.resid = w.latf; o.ldr = dim; o.out_f = w.latf; o.ldo_f = dim;
       NSCHK(run_gemm(o, prec, s));
@@ -855,6 +868,23 @@ extern "C" int ns2_model_prepare_cond(ns2_model* m, const float* prompt, int n_p
     NSCHK(run_gemm(kv, prec, s));
   }
   return NS2_OK;
+}
+
+extern "C" int ns2_model_prepare_cond(ns2_model* m, const float* prompt, int n_prompt, const float* cond, int n_cond, int drop,
+                                      int B, int N, void* cond_state, void* workspace, int64_t workspace_bytes, void* stream) {
+  return prepare_cond_impl(m, prompt, n_prompt, nullptr, cond, n_cond, drop, B, N, cond_state, workspace, workspace_bytes, stream);
+}
+
+extern "C" int ns2_model_prepare_cond_lens(ns2_model* m, const float* prompt, int n_prompt, const int* prompt_lens, const float* cond,
+                                           int n_cond, int drop, int B, int N, void* cond_state, void* workspace, int64_t workspace_bytes,
+                                           void* stream) {
+  if (!m) { set_error("ns2_model_prepare_cond_lens: null model"); return NS2_ERR_ARG; }
+  if (B <= 0 || N <= 0) { set_error("ns2_model_prepare_cond_lens: B and N must be positive"); return NS2_ERR_ARG; }
+  if (!prompt || !cond || !cond_state || !workspace || n_prompt <= 0 || n_cond <= 0) {
+    set_error("ns2_model_prepare_cond_lens: prompt, cond, cond_state and workspace are required");
+    return NS2_ERR_ARG;
+  }
+  return prepare_cond_impl(m, prompt, n_prompt, prompt_lens, cond, n_cond, drop, B, N, cond_state, workspace, workspace_bytes, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ live profiling

@@ -183,6 +183,9 @@ hipError_t launch_transpose_f32(const float* in, int batch, int R, int C, float*
 
 // mean over n of [B, n, d] -> [B, d]
 hipError_t launch_mean_rows(const float* in, int B, int n, int d, float* out, hipStream_t s);
+// ragged_front.hip: the mean over rows [0, clamp(lens[b], 1, n)) of utterance b (ascending rows); out[b] = offset + clamp(lens[b], 1, n)
+hipError_t launch_mean_rows_lens(const float* in, int B, int n, int d, const int* lens, float* out, hipStream_t s);
+hipError_t launch_offset_lens(const int* lens, int B, int n, int offset, int* out, hipStream_t s);
 
 // out[b*ld_out + e] = src[e] for e < row_elems (broadcast a parameter row over the batch)
 hipError_t launch_bcast_rows(const float* src, float* out, int B, long row_elems, long ld_out, hipStream_t s);

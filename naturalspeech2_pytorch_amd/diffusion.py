@@ -171,12 +171,15 @@ class NaturalSpeech2(nn.Module):
     # ------------------------------------------------------------------ sampling (NS2:1379-1431)
     @torch.no_grad()
     def ddim_sample(self, shape, prompt=None, time_difference=None, cond_scale=1., cond=None, noise=None, use_graph=False,
-                    on_saturation="demote", lens=None):
+                    on_saturation="demote", lens=None, prompt_lens=None):
         """`prompt` here is what the reference passes at NS2:1486-1491: the ENCODED prompt [b, n_p, dim_prompt].
 
         lens (not in the reference): frames per utterance of a ragged batch, integer [b], each in [1, shape[1]].  Every step hands
         them to the model (`Model.forward(lens=)`: the self-attention kernels read them on the device), so utterance i is denoised as
         it would be alone at lens[i] frames; latent frames at or beyond lens[i] come back as exactly 0.
+
+        prompt_lens (not in the reference): rows per utterance of the encoded prompt, integer [b], each in [1, n_p]; handed to the model
+        (`Model.forward(prompt_lens=)`), whose conditioning then sees rows [0, prompt_lens[i]) of prompt i alone.
 
         on_saturation (not in the reference): what to do when a checkpoint's activations leave the IEEE-half range in one of the
         fast precisions (half / mixed / hybrid: conversions clamp at 65504 -- finite but wrong; the model counts them on the
@@ -190,13 +193,16 @@ class NaturalSpeech2(nn.Module):
         if lens is not None:                             # one device buffer for the run: what a captured step keeps reading
             lens = torch.as_tensor(lens).to(device=device, dtype=torch.int32).contiguous()
             assert lens.shape == (batch,), f"lens must hold one frame count per utterance: [{batch}]"
+        if prompt_lens is not None:                      # likewise: one tensor for the run, so the model's conditioning cache holds
+            prompt_lens = torch.as_tensor(prompt_lens).to(device=device, dtype=torch.int32).contiguous()
+            assert prompt_lens.shape == (batch,), f"prompt_lens must hold one prompt length per utterance: [{batch}]"
         for attempt in (0, 1):
             if hasattr(self.model, "refresh_weights"):
                 self.model.refresh_weights()        # parameters rewritten through `.data` since the last pack (EMA) -> re-pack
             if hasattr(self.model, "clear_cond_cache"):
                 self.model.clear_cond_cache()
             try:
-                audio = self._ddim_loop(start.clone(), prompt, cond, cond_scale, use_graph, lens)
+                audio = self._ddim_loop(start.clone(), prompt, cond, cond_scale, use_graph, lens, prompt_lens)
                 if lens is not None:
                     audio = audio.masked_fill(torch.arange(audio.shape[1], device=audio.device)[None, :, None] >= lens[:, None, None], 0.)
                 if hasattr(self.model, "check_saturation") and audio.is_cuda:
@@ -213,29 +219,37 @@ class NaturalSpeech2(nn.Module):
                               f"the sampling run with precision='exact' and keeping the model there ({e})")
                 self.model.precision = "exact"
 
-    def _ddim_loop(self, audio, prompt, cond, cond_scale, use_graph, lens=None):
+    @staticmethod
+    def _ragged_kw(lens, prompt_lens):
+        """the lengths a step hands to the model: each keyword only when it was given, so a model without it is called as before"""
+        kw = {} if lens is None else dict(lens=lens)
+        if prompt_lens is not None:
+            kw["prompt_lens"] = prompt_lens
+        return kw
+
+    def _ddim_loop(self, audio, prompt, cond, cond_scale, use_graph, lens=None, prompt_lens=None):
         batch, device = audio.shape[0], audio.device
         pairs = self.get_sampling_timesteps(batch, device=device)
         # `time_difference` only shifts times_next AFTER gamma_next was taken (NS2:1396-1406): it has no effect upstream either
         if not self._fused_ddim_ok():
-            return self._ddim_sample_unfused(audio, pairs, prompt, cond, cond_scale, lens)
+            return self._ddim_sample_unfused(audio, pairs, prompt, cond, cond_scale, lens, prompt_lens)
         # SURVEY §8f-1: the run's times are known here and shared by the batch, so every time-conditioning projection of the run is
         # computed once, ahead of the loop; step i reads row i (Model.time_table)
         table = None
         if hasattr(self.model, "time_table") and audio.is_cuda:
             table = self.model.time_table(torch.stack([p[0][0] for p in pairs]), batch)
         if use_graph:
-            return self._ddim_sample_graph(audio, pairs, prompt, cond, cond_scale, table, lens)
-        ragged = {} if lens is None else dict(lens=lens)
+            return self._ddim_sample_graph(audio, pairs, prompt, cond, cond_scale, table, lens, prompt_lens)
+        ragged = self._ragged_kw(lens, prompt_lens)
         for i, (times, times_next) in enumerate(pairs):
             kw = dict(ragged) if table is None else dict(ragged, cond_row=table[i])
             out = self.model.forward_with_cond_scale(audio, times, prompt=prompt, cond_scale=cond_scale, cond=cond, **kw)
             ops.ddim_step(audio, out, times, times_next, self.objective, self.noise_schedule, self.scale, out=audio)
         return audio
 
-    def _ddim_sample_unfused(self, audio, pairs, prompt, cond, cond_scale, lens=None):
+    def _ddim_sample_unfused(self, audio, pairs, prompt, cond, cond_scale, lens=None, prompt_lens=None):
         """non-default `schedule_kwargs`: the schedule is evaluated by the host-side functions above, the model step is HIP"""
-        ragged = {} if lens is None else dict(lens=lens)
+        ragged = self._ragged_kw(lens, prompt_lens)
         for times, times_next in pairs:
             g, gn = self.gamma_schedule(times)[:, None, None], self.gamma_schedule(times_next)[:, None, None]
             alpha, sigma = torch.sqrt(g) * self.scale, torch.sqrt(1 - g)
@@ -247,15 +261,15 @@ class NaturalSpeech2(nn.Module):
             audio = x0 * alpha_n + eps * sigma_n
         return audio
 
-    def _ddim_sample_graph(self, audio, pairs, prompt, cond, cond_scale, table=None, lens=None):
+    def _ddim_sample_graph(self, audio, pairs, prompt, cond, cond_scale, table=None, lens=None, prompt_lens=None):
         """one (model + DDIM update) step captured in a HIP graph; times (and the step's row of the conditioning table) are device
         buffers rewritten per step.  The lengths of a ragged batch are a device buffer the captured kernels read: nothing of the
-        step reads them on the host."""
+        step reads them on the host.  The conditioning (prompt_lens included) is computed by the warm-up step, before the capture, and
+        the captured step finds it in the model's cache."""
         t_buf, tn_buf = pairs[0][0].clone(), pairs[0][1].clone()
         row = table[0].clone() if table is not None else None
         kw = {} if row is None else dict(cond_row=row)
-        if lens is not None:
-            kw["lens"] = lens
+        kw.update(self._ragged_kw(lens, prompt_lens))
         step = lambda: ops.ddim_step(                                                   # noqa: E731
             audio, self.model.forward_with_cond_scale(audio, t_buf, prompt=prompt, cond_scale=cond_scale, cond=cond, **kw),
             t_buf, tn_buf, self.objective, self.noise_schedule, self.scale, out=audio)
@@ -291,6 +305,31 @@ class NaturalSpeech2(nn.Module):
                 prompt, _, _ = self.codec(prompt, curtail_from_left=True, return_encoded=True)
         return prompt
 
+    def _prompt_frame_lens(self, prompt_lens, prompt, prompt_enc):
+        """sample(prompt_lens=) -> the lengths in rows of the encoded prompt, an integer tensor [b] on the model's device.  They count
+        rows of `prompt_enc=`, frames of prompt latents [b, n_p, dim_codebook], samples of a raw-audio prompt [b, samples]: there the
+        codec makes one frame of every `seq_len_multiple_of` samples, so each length and the padded length must be a positive multiple
+        of it (one host read, before the loop)."""
+        lens = torch.as_tensor(prompt_lens)
+        given = prompt_enc if prompt_enc is not None else prompt
+        if lens.ndim != 1 or lens.dtype.is_floating_point or lens.shape[0] != given.shape[0]:
+            raise ValueError(f"prompt_lens must hold one integer prompt length per utterance: [{given.shape[0]}]")
+        lens = lens.to(self.device).long()
+        if prompt_enc is None and prompt.ndim == 2:
+            assert self.codec is not None, "codec must be passed in if one were to sample from a raw prompt"
+            hop = int(self.seq_len_multiple_of)
+            ok = (prompt.shape[-1] > 0 and prompt.shape[-1] % hop == 0 and bool(((lens > 0) & (lens % hop == 0) & (lens <= prompt.shape[-1])).all().item()))
+            if not ok:
+                raise ValueError(f"a raw-audio prompt with prompt_lens: every length, and the padded length {prompt.shape[-1]}, must be a "
+                                 f"positive multiple of the codec's seq_len_multiple_of ({hop}) samples")
+            least = int(getattr(self.codec, "min_causal_prompt_frames", 1))
+            if least > 1 and not bool((lens >= least * hop).all().item()):
+                raise ValueError(f"a raw-audio prompt with prompt_lens: every prompt must be at least {least} codec frames ({least * hop} "
+                                 f"samples) long -- the encoder's reflect padding mirrors that many of an utterance's first frames, and "
+                                 f"would read a shorter prompt's padding")
+            lens = lens // hop
+        return lens
+
     def _encode_prompt(self, prompt, prompt_enc):
         if prompt_enc is not None:
             return prompt_enc
@@ -306,16 +345,28 @@ class NaturalSpeech2(nn.Module):
                 mod.refresh_weights()
 
     @torch.no_grad()
-    def text_to_cond(self, text, prompt_enc, text_lens=None, return_lens=False):
+    def text_to_cond(self, text, prompt_enc, text_lens=None, return_lens=False, prompt_lens=None):
         """NS2:1476-1483: phoneme_enc(text) -> DurationPitchPredictor -> the length regulator (durations truncated to whole
         frames, pitch embedded through f0_to_coarse) -> the frame-aligned conditioning [b, dim_prompt, n_frames], n_frames = the
         longest utterance (one host read, the reference's `.item()`).  Every duration truncating to 0 frames leaves nothing to
         condition on: the reference fails there inside cond_to_model_dim; here it is a ValueError.
         Not in the reference (the ragged mode of `sample`): `text_lens` [b] -- phonemes at or beyond text_lens[i] contribute no
-        frames (their predicted durations count as 0); `return_lens=True` -> (cond, the utterances' own frame totals, integer [b])."""
+        frames (their predicted durations count as 0); `return_lens=True` -> (cond, the utterances' own frame totals, integer [b]).
+        `prompt_lens` [b] (rows of prompt_enc per utterance) switches the ragged front-end on: the phoneme encoder gets the key mask of
+        `text_lens` (missing: full) and the predictor both length vectors, so the durations and pitches of utterance i are what it
+        gives alone with its text cut to text_lens[i] and its prompt to prompt_lens[i].  Without it, today's calls."""
         assert hasattr(self, "duration_pitch"), "construct NaturalSpeech2 with build_duration_pitch=True"
-        phoneme_enc = self.phoneme_enc(text)
-        duration, pitch = self.duration_pitch(phoneme_enc, prompt_enc)
+        if prompt_lens is not None:
+            from .aligner import create_mask
+            b, n = text.shape[0], text.shape[-1]
+            text_lens = torch.full((b,), n, dtype=torch.long, device=text.device) if text_lens is None else \
+                torch.as_tensor(text_lens).to(device=text.device).long().clamp(1, n)
+            phoneme_enc = self.phoneme_enc(text, mask=create_mask(text_lens, n))
+            duration, pitch = self.duration_pitch(phoneme_enc, prompt_enc, text_lens=text_lens,
+                                                  prompt_lens=torch.as_tensor(prompt_lens).to(text.device))
+        else:
+            phoneme_enc = self.phoneme_enc(text)
+            duration, pitch = self.duration_pitch(phoneme_enc, prompt_enc)
         if text_lens is not None:
             pad = torch.arange(duration.shape[1], device=duration.device)[None] >= torch.as_tensor(text_lens, device=duration.device)[:, None]
             duration = duration.masked_fill(pad, 0.)
@@ -332,7 +383,7 @@ class NaturalSpeech2(nn.Module):
 
     @torch.no_grad()
     def sample(self, *, length=None, prompt=None, batch_size=1, cond_scale=1., text=None, text_lens=None,
-               cond=None, prompt_enc=None, noise=None, use_graph=False, return_lens=False):
+               cond=None, prompt_enc=None, noise=None, use_graph=False, return_lens=False, prompt_lens=None):
         """NS2:1457-1501.  Extra keywords (not in the reference): `cond` / `prompt_enc` = pre-computed conditioning (module
         docstring), `noise` = injected initial latents (parity tests), `use_graph` = HIP-graph replay of the step.
 
@@ -341,7 +392,17 @@ class NaturalSpeech2(nn.Module):
         `text=` (the counts are then the utterances' own totals of predicted durations, and phonemes at or beyond `text_lens[i]`
         contribute no frames): the batch is denoised at max(length) frames with the counts handed to the self-attention kernels, so
         utterance i is what `sample` gives for it alone at its own length; its frames (samples, with a codec) past its end come back
-        as exactly 0.  `return_lens=True` -> (audio, lens): integer [b], in frames without a codec, in samples with one."""
+        as exactly 0.  `return_lens=True` -> (audio, lens): integer [b], in frames without a codec, in samples with one.
+
+        Ragged prompts and text (not in the reference): `prompt_lens`, integer [b], switches the ragged front-end on -- prompt i counts
+        up to prompt_lens[i] and text i up to text_lens[i] (missing: full) in `prompt_enc`, `phoneme_enc`, the DurationPitchPredictor and
+        the model's conditioning, so the whole result of utterance i is what `sample` gives for it alone with its own prompt and text; a
+        batch whose prompts are all full but whose texts are ragged passes `prompt_lens` full.  The lengths count rows of `prompt_enc=`
+        when that is given, frames of prompt latents [b, n_p, dim_codebook], and samples of a raw-audio prompt [b, samples] -- there
+        each length, and the padded length, must be a positive multiple of the codec's `seq_len_multiple_of`, and at least the codec's
+        `min_causal_prompt_frames` frames (7 for the 24 kHz SEANet: its reflect padding mirrors frames 1 .. 6) -- ValueError otherwise,
+        one host check before the loop; the encoder being causal then keeps the padding out of an utterance's frames.
+        Without `prompt_lens`, `text_lens` does exactly what it did: it zeroes the padding phonemes' durations."""
         if length is None and (text is None or cond is not None):
             raise ValueError("sample(length=None) takes the utterances' lengths from the predicted durations: it needs text= (and no cond=)")
         lens = None
@@ -350,21 +411,29 @@ class NaturalSpeech2(nn.Module):
             if lens.ndim != 1 or lens.dtype.is_floating_point or lens.numel() == 0:
                 raise ValueError("length must be an int or a 1-D integer tensor / sequence of one frame count per utterance")
             lens = lens.long()
+        if prompt_lens is not None:
+            if not self.conditional or (prompt is None and prompt_enc is None):
+                raise ValueError("prompt_lens needs a prompt: a conditional model called with prompt= or prompt_enc=")
+            prompt_lens = self._prompt_frame_lens(prompt_lens, prompt, prompt_enc)
         self.refresh_weights()
         p_enc = None
+        front = {} if prompt_lens is None else dict(prompt_lens=prompt_lens)
         if self.conditional:
             assert (prompt is not None or prompt_enc is not None) and (text is not None or cond is not None)   # NS2:1473
-            p_enc = self._encode_prompt(prompt, prompt_enc)
+            if prompt_lens is None or prompt_enc is not None:
+                p_enc = self._encode_prompt(prompt, prompt_enc)
+            else:
+                p_enc = self.prompt_enc(self.process_prompt(prompt), lens=prompt_lens)
             if cond is None and not hasattr(self, "duration_pitch"):
                 raise NotImplementedError(
                     "sample(text=...) derives the aligned conditioning with the DurationPitchPredictor (NS2:1478-1483), which is "
                     "not built by default: construct with `build_duration_pitch=True`, or pass the aligned conditioning as "
                     "`cond=` [b, dim_prompt, n_frames]")
             if cond is None and length is None:
-                cond, lens = self.text_to_cond(text, p_enc, text_lens=text_lens, return_lens=True)
+                cond, lens = self.text_to_cond(text, p_enc, text_lens=text_lens, return_lens=True, **front)
                 lens = lens.long()
             elif cond is None:
-                cond = self.text_to_cond(text, p_enc)
+                cond = self.text_to_cond(text, p_enc, **(dict(front, text_lens=text_lens) if front else {}))
             batch_size = p_enc.shape[0]
         elif length is None:
             raise ValueError("sample(length=None) needs a conditional model: the lengths come from the predicted durations of text=")
@@ -378,7 +447,7 @@ class NaturalSpeech2(nn.Module):
             if length < 1:
                 raise ValueError("every utterance has 0 frames")
         audio = self.ddim_sample((batch_size, length, self.dim), prompt=p_enc, cond=cond, cond_scale=cond_scale, noise=noise,
-                                 use_graph=use_graph, **({} if lens is None else dict(lens=lens)))
+                                 use_graph=use_graph, **({} if lens is None else dict(lens=lens)), **front)
         ragged = lens is not None
         if return_lens and not ragged:
             lens = torch.full((batch_size,), length, dtype=torch.long, device=audio.device)

@@ -81,15 +81,29 @@ class DurationPitchPredictor(nn.Module):
         self.precision, self.dim_hidden, self.dropout = precision, dim_hidden, dropout
         self._cache = PackedCache(fingerprint_every=1)      # once per utterance: check the content on every call (EMA copies)
 
-    def forward(self, x, encoded_prompts, prompt_mask=None):
+    def forward(self, x, encoded_prompts, prompt_mask=None, *, text_lens=None, prompt_lens=None):
         """x: token ids [b, n] (with num_phoneme_tokens) or phoneme encodings [b, n, dim_hidden]; encoded_prompts [b, n_p,
-        dim_hidden].  Returns (duration, pitch), each [b, n]."""
+        dim_hidden].  Returns (duration, pitch), each [b, n].
+
+        text_lens / prompt_lens (not in the reference; sampling only): phonemes / prompt rows per utterance of a padded batch, integer
+        [b], read on the device and clamped into [1, n] / [1, n_p]; either alone is allowed, the other side then counts as full.  The
+        durations and pitches [0, text_lens[i]) are what utterance i gives alone with its text and prompt cut to its lengths, whatever
+        lies behind them (NaN included); from text_lens[i] on they are exactly 0."""
         if not torch.is_tensor(x):
             raise NotImplementedError("List[str] input needs the tokenizer / espeak front-end (out of scope); pass token ids or "
                                       "phoneme encodings")
         if prompt_mask is not None:
             raise NotImplementedError("prompt_mask is not supported: the reference's Attend applies it to keys = cat(queries, "
                                       "prompts), which a [b, n_p] mask does not cover (NS2:1060-1066)")
+        if text_lens is not None or prompt_lens is not None:
+            if needs_autograd(self, x if x.is_floating_point() else None):
+                raise NotImplementedError(f"{'text_lens' if text_lens is not None else 'prompt_lens'}: per-utterance lengths are a sampling "
+                                          f"feature (torch.no_grad()); the training passes take equal-length batches")
+            if not x.is_cuda:
+                from .autograd_path import duration_pitch_autograd
+                with torch.no_grad():
+                    return duration_pitch_autograd(self, x, encoded_prompts, text_lens=text_lens, prompt_lens=prompt_lens)
+            return self._forward_hip(x, encoded_prompts, text_lens, prompt_lens)
         if needs_autograd(self, x if x.is_floating_point() else None) or not x.is_cuda:
             if self.train_backend == "hip" and x.is_cuda:          # (on the GPU this branch is entered under autograd only)
                 from . import training
@@ -126,7 +140,7 @@ class DurationPitchPredictor(nn.Module):
         return trunks
 
     @torch.no_grad()
-    def _forward_hip(self, x, encoded_prompts):
+    def _forward_hip(self, x, encoded_prompts, text_lens=None, prompt_lens=None):
         if self.training and self.dropout > 0:
             raise NotImplementedError("dropout is a training-time feature; the HIP path is inference-only (call .eval(), or run "
                                       "under autograd for the composite)")
@@ -143,14 +157,37 @@ class DurationPitchPredictor(nn.Module):
         prec = _PRECISIONS[self.precision]
         packed = self._cache.get(self.parameters(), self._build_packed, extra=(self.precision,))
         h0 = x.reshape(b * n, d).float().contiguous()
+        p0 = encoded_prompts.reshape(b * np_, d).float().contiguous()
+        key_mask = None
+        if text_lens is not None or prompt_lens is not None:
+            # rows behind a length become zeros once, in copies (the callers' tensors are not written): the "same" convolutions then
+            # read what they read behind the end of the utterance alone, and every context row the key mask hides is finite.  ONE byte
+            # mask [b, n + n_p] for all layers of both trunks: keys [0, text_lens[i]) and [n, n + prompt_lens[i]), made on the device
+            def side(lens_, rows, k):
+                if lens_ is None:
+                    return rows, torch.ones(b, k, dtype=torch.bool, device=x.device)
+                l = ops._front_lens(lens_, b, x.device)
+                return ops.zero_rows(rows.clone(), b, k, l), torch.arange(k, device=x.device)[None] < l.clamp(1, k)[:, None]
+
+            (h0, tm), (p0, pm) = side(text_lens, h0, n), side(prompt_lens, p0, np_)
+            parts = [tm, pm]
+            key_mask = torch.cat(parts, dim=1).to(torch.uint8).contiguous()
+            text_lens = None if text_lens is None else ops._front_lens(text_lens, b, x.device)
         # the prompt rows of every attention context, split once: context planes [b, n + n_p] = [norm(x) rows | prompt rows]
-        pp = ops.split(encoded_prompts.reshape(b * np_, d).float().contiguous(), precision=prec)
+        pp = ops.split(p0, precision=prec)
         ctx = ops._out_planes(b * (n + np_), d, x.device, prec)
         ctx.buf.view(b, n + np_, -1)[:, n:].copy_(pp.buf.view(b, np_, -1))
-        outs = [self._trunk_hip(tr, h0, b, n, np_, ctx, prec) for tr in packed]
+        outs = [self._trunk_hip(tr, h0, b, n, np_, ctx, prec, text_lens, key_mask) for tr in packed]
+        if text_lens is not None:
+            pad = torch.arange(n, device=x.device)[None] >= text_lens.clamp(1, n)[:, None]
+            outs = [o.reshape(b, n).masked_fill(pad, 0.) for o in outs]
         return outs[0].reshape(b, n).to(x.dtype), outs[1].reshape(b, n).to(x.dtype)
 
-    def _trunk_hip(self, tr, h, b, n, np_, ctx, prec):
+    def _trunk_hip(self, tr, h, b, n, np_, ctx, prec, text_lens=None, key_mask=None):
+        """text_lens: int32 [b] on the device or None -- rows of h from text_lens[i] on are zeros on entry and after every layer;
+        key_mask: uint8 [b, n + np_] or None, the keys of every attention"""
+        gn_kw = {} if text_lens is None else dict(lens=text_lens)
+        att_kw = {} if key_mask is None else dict(key_mask=key_mask)
         k = self.to_pitch_pred.kernel_size
         H, dh = self.to_pitch_pred.heads, self.to_pitch_pred.dim_head
         conv_kw = dict(conv_taps=k, dilation=1, seq_len=n, pad_left=k // 2, precision=prec)
@@ -162,20 +199,26 @@ class DurationPitchPredictor(nn.Module):
                     for j, (pw, cb, gw, gb, groups, eps) in enumerate(rb):
                         y = ops.linear_f32(pw, a, bias=cb, **conv_kw)
                         if j < last:
-                            a = ops.groupnorm_silu(y, b, gw, gb, groups, eps, want_f32=False, precision=prec)
+                            a = ops.groupnorm_silu(y, b, gw, gb, groups, eps, want_f32=False, precision=prec, **gn_kw)
                         else:
-                            h, a = ops.groupnorm_silu(y, b, gw, gb, groups, eps, resid=xin, precision=prec)
+                            h, a = ops.groupnorm_silu(y, b, gw, gb, groups, eps, resid=xin, precision=prec, **gn_kw)
             else:
                 for i, (pw, cb) in enumerate(L["convs"]):   # ConvBlock: conv + SiLU in the GEMM epilogue
                     if i + 1 < len(L["convs"]):
                         a = ops.linear_split(pw, a, bias=cb, act=1, **conv_kw)
+                        if text_lens is not None:            # no GroupNorm here to zero the rows behind the end
+                            ops.zero_rows(a, b, n, text_lens)
                     else:
                         h = ops.linear_f32(pw, a, bias=cb, act=1, **conv_kw)
+                        if text_lens is not None:
+                            ops.zero_rows(h, b, n, text_lens)
             xn = ops.rmsnorm(h, gamma=L["gamma"], precision=prec)
             ctx.buf.view(b, n + np_, -1)[:, :n].copy_(xn.buf.view(b, n, -1))
             inner = H * dh
             q = ops.linear_split(L["q"], xn, precision=prec, out_precision=2 if prec == 4 else None)   # attention operand format
             kk, vt = ops.linear_qkv(L["kv"], ctx, seq_len=n + np_, split_col=inner, precision=prec)
-            o = ops.attention(q, kk, vt, b, H, n, n + np_, precision=prec, head_dim=dh)
+            o = ops.attention(q, kk, vt, b, H, n, n + np_, precision=prec, head_dim=dh, **att_kw)
             h = ops.linear_f32(L["out"], o, resid=h, precision=prec)
+            if text_lens is not None:                        # a padding query's output is finite but not 0: the next convolution reads it
+                ops.zero_rows(h, b, n, text_lens)
         return ops.row_dot(h, tr["w_pred"], tr["b_pred"], relu=True)

@@ -52,10 +52,23 @@ class SpeechPromptEncoder(nn.Module):
                                        use_flash=use_flash_attn, precision=precision, train_backend=train_backend)
         self._stack = _ConvStack()
 
-    def forward(self, x):
+    def forward(self, x, *, lens=None):
         """Under autograd (the reference trains prompt_enc jointly, NS2:1542-1543) the HIP training path (`train_backend="hip"`) or the
-        differentiable composite runs; inference runs in the forward-only HIP kernels."""
+        differentiable composite runs; inference runs in the forward-only HIP kernels.
+
+        lens (not in the reference; sampling only): prompt rows per utterance of a padded batch, integer [b], read on the device and
+        clamped into [1, n].  Output rows [0, lens[i]) are what utterance i gives alone with its prompt cut to lens[i] rows, whatever
+        x holds from lens[i] on (NaN included); output rows from lens[i] on are exactly 0."""
         assert x.shape[-1] == self.dim
+        if lens is not None:
+            if needs_autograd(self, x):
+                raise NotImplementedError("lens: per-utterance prompt lengths are a sampling feature (torch.no_grad()); the training "
+                                          "passes take equal-length batches")
+            if not x.is_cuda:
+                from .autograd_path import speech_prompt_encoder_autograd
+                with torch.no_grad():
+                    return speech_prompt_encoder_autograd(self, x, lens=lens)
+            return self._forward_hip(x, lens=lens)
         if needs_autograd(self, x):
             if use_hip_training(self, x):
                 from .training import speech_prompt_encoder_forward_train
@@ -70,19 +83,30 @@ class SpeechPromptEncoder(nn.Module):
         self.transformer.refresh_weights()
 
     @torch.no_grad()
-    def _forward_hip(self, x):
+    def _forward_hip(self, x, lens=None):
         b, n, _ = x.shape
         prec = _PRECISIONS[self.precision]
         convs = [m for m in self.conv if isinstance(m, nn.Conv1d)]
         packed = self._stack.packed_for(convs, prec)
-        h = ops.split(x.reshape(b * n, self.dim).float().contiguous(), precision=prec)
+        x0 = x.reshape(b * n, self.dim).float().contiguous()
+        if lens is not None:
+            # the "same" convolutions read zeros behind an utterance's end, as they do behind the end of the utterance alone: the input
+            # (a copy: the caller's rows are not written) and every convolution's output are zeroed from lens[i] on
+            lens = ops._front_lens(lens, b, x.device)
+            x0 = ops.zero_rows(x0.clone() if x0.data_ptr() == x.data_ptr() else x0, b, n, lens)
+        h = ops.split(x0, precision=prec)
         for i, (pw, bias) in enumerate(packed):
             kw = dict(bias=bias, conv_taps=self.kernel_size, dilation=1, seq_len=n, pad_left=self.padding, act=1, precision=prec)
             if i + 1 < len(packed):
                 h = ops.linear_split(pw, h, **kw)
             else:
                 h = ops.linear_f32(pw, h, **kw)
-        return self.transformer._forward_hip(h.reshape(b, n, self.dim_out)).to(x.dtype)
+            if lens is not None:
+                ops.zero_rows(h, b, n, lens)
+        if lens is None:
+            return self.transformer._forward_hip(h.reshape(b, n, self.dim_out)).to(x.dtype)
+        out = self.transformer._forward_hip(h.reshape(b, n, self.dim_out), key_lens=lens)
+        return ops.zero_rows(out, b, n, lens).to(x.dtype)
 
 
 class PhonemeEncoder(nn.Module):

@@ -338,9 +338,13 @@ class HipDenoiserMixin:
             ns.ws = torch.empty(need, dtype=torch.uint8, device=dev)
         return ns.ws
 
-    def _cond_state(self, ns, prompt, cond, drop, B, N):
+    def _cond_state(self, ns, prompt, cond, drop, B, N, prompt_lens=None):
+        """prompt_lens: None, or the caller's lengths tensor (any integer dtype / device): its identity and version are part of the
+        cache key, so a state computed for other lengths -- the tensor rewritten in place included -- is not served"""
         key = (prompt.data_ptr(), prompt._version, tuple(prompt.shape), cond.data_ptr(), cond._version, tuple(cond.shape),
                bool(drop), B, N)
+        if prompt_lens is not None:
+            key += (prompt_lens.data_ptr(), prompt_lens._version, tuple(prompt_lens.shape), prompt_lens.dtype, prompt_lens.device)
         hit = ns.cond_cache.get(bool(drop))
         if hit is not None and hit[0] == key:
             return hit[1]
@@ -349,15 +353,21 @@ class HipDenoiserMixin:
         nbytes = lib.ns2_model_cond_bytes(ns.handle, B, N, n_p, n_c)
         state = torch.empty(nbytes, dtype=torch.uint8, device=prompt.device)
         ws = self._workspace(ns, B, N, n_p, n_c)
-        check(lib.ns2_model_prepare_cond(ns.handle, prompt.data_ptr(), n_p, cond.data_ptr(), n_c, int(drop), B, N,
-                                         state.data_ptr(), ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream),
-              "ns2_model_prepare_cond")
-        ns.cond_cache[bool(drop)] = (key, state, prompt, cond)     # keep the inputs alive with the cache entry
+        if prompt_lens is not None:
+            pl = _device_lens(prompt_lens, B, prompt.device)
+            check(lib.ns2_model_prepare_cond_lens(ns.handle, prompt.data_ptr(), n_p, pl.data_ptr(), cond.data_ptr(), n_c, int(drop), B, N,
+                                                  state.data_ptr(), ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream),
+                  "ns2_model_prepare_cond_lens")
+        else:
+            check(lib.ns2_model_prepare_cond(ns.handle, prompt.data_ptr(), n_p, cond.data_ptr(), n_c, int(drop), B, N,
+                                             state.data_ptr(), ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream),
+                  "ns2_model_prepare_cond")
+        ns.cond_cache[bool(drop)] = (key, state, prompt, cond, prompt_lens)     # keep the inputs alive with the cache entry
         return state
 
-    def _cond_state_cfg(self, ns, prompt, cond, B, N):
+    def _cond_state_cfg(self, ns, prompt, cond, B, N, prompt_lens=None):
         """the conditioning of ONE 2B-utterance batch [conditioned | null substitutes] (ns2_model_cond_stack), cached like the two states"""
-        sa, sb = self._cond_state(ns, prompt, cond, False, B, N), self._cond_state(ns, prompt, cond, True, B, N)
+        sa, sb = self._cond_state(ns, prompt, cond, False, B, N, prompt_lens), self._cond_state(ns, prompt, cond, True, B, N, prompt_lens)
         key = (sa.data_ptr(), sb.data_ptr(), ns.cond_cache[False][0], B, N)
         hit = ns.cond_cache.get("cfg")
         if hit is not None and hit[0] == key:
@@ -376,7 +386,7 @@ class HipDenoiserMixin:
     CFG_ONE_BATCH_MAX = 8
 
     @torch.no_grad()
-    def _forward_hip_cfg(self, x, times, prompt, cond, cond_scale, cond_row=None, lens=None):
+    def _forward_hip_cfg(self, x, times, prompt, cond, cond_scale, cond_row=None, lens=None, prompt_lens=None):
         from . import ops
         dim = self._hip_cfg["dim"]
         self._guards()
@@ -385,7 +395,7 @@ class HipDenoiserMixin:
         xin = x if (x.dtype == torch.float32 and x.is_contiguous()) else x.float().contiguous()
         pr = prompt if (prompt.dtype == torch.float32 and prompt.is_contiguous()) else prompt.float().contiguous()
         cd = cond if (cond.dtype == torch.float32 and cond.is_contiguous()) else cond.float().contiguous()
-        state = self._cond_state_cfg(ns, pr, cd, B, N)
+        state = self._cond_state_cfg(ns, pr, cd, B, N, _prompt_lens_tensor(prompt_lens, B))
         n_c = cd.shape[2]
         ws = self._workspace(ns, 2 * B, N, pr.shape[1], n_c)
         x2 = torch.cat((xin, xin), dim=0)
@@ -437,11 +447,16 @@ class HipDenoiserMixin:
         return table
 
     # ---- forward (NS2:929-1000)
-    def forward(self, x, times, prompt=None, prompt_mask=None, cond=None, cond_drop_prob=None, *, cond_row=None, lens=None):
+    def forward(self, x, times, prompt=None, prompt_mask=None, cond=None, cond_drop_prob=None, *, cond_row=None, lens=None, prompt_lens=None):
         """`cond_row` (not in the reference): a row of `time_table()` standing in for `times` (inference only).
         `lens` (not in the reference): frames per utterance of a ragged batch, integer [b], each in [1, n] -- out[i, :lens[i]] is
         what utterance i gives alone at its own length, whatever x (and cond) hold from lens[i] on; rows from lens[i] on are
-        finite and meaningless.  The self-attention kernels read the lengths on the device (sampling only)."""
+        finite and meaningless.  The self-attention kernels read the lengths on the device (sampling only).
+        `prompt_lens` (not in the reference): prompt rows per utterance of a padded prompt batch, integer [b], each in [1, n_p] -- the
+        output of utterance i is what it gives with its prompt cut to prompt_lens[i] rows, whatever the prompt holds from there on
+        (NaN included): the mean of to_prompt_cond and the perceiver resampler's keys stop at the length, on the device (sampling only)."""
+        if prompt_lens is not None and (not self._hip_cfg["condition_on_prompt"] or prompt is None):
+            raise ValueError("prompt_lens needs a prompt: a conditional model (condition_on_prompt=True) called with prompt=")
         p = self.cond_drop_prob if cond_drop_prob is None else cond_drop_prob
         needs_grad = torch.is_grad_enabled() and (x.requires_grad or any(q.requires_grad for q in self.parameters()))
         stochastic = self._hip_cfg["condition_on_prompt"] and p not in (0, 0., 1, 1.)
@@ -452,13 +467,19 @@ class HipDenoiserMixin:
             if lens is not None:
                 raise NotImplementedError("lens: per-utterance lengths are a sampling feature (torch.no_grad()); the training pass and the "
                                           "backward kernels take equal-length batches")
+            if prompt_lens is not None:
+                raise NotImplementedError("prompt_lens: per-utterance prompt lengths are a sampling feature (torch.no_grad()); the training "
+                                          "pass and the backward kernels take equal-length batches")
             self._native.autograd_seen = True
             return self._forward_autograd(x, times, prompt=prompt, prompt_mask=prompt_mask, cond=cond, cond_drop_prob=cond_drop_prob)
         ragged = {} if lens is None else dict(lens=lens)
+        if prompt_lens is not None:
+            ragged["prompt_lens"] = prompt_lens
         return self._forward_hip(x, times, prompt, prompt_mask, cond, cond_drop_prob, cond_row=cond_row, **ragged)
 
     @torch.no_grad()
-    def _forward_hip(self, x, times, prompt=None, prompt_mask=None, cond=None, cond_drop_prob=None, out=None, cond_row=None, lens=None):
+    def _forward_hip(self, x, times, prompt=None, prompt_mask=None, cond=None, cond_drop_prob=None, out=None, cond_row=None, lens=None,
+                     prompt_lens=None):
         if prompt_mask is not None:
             raise NotImplementedError(_PROMPT_MASK_MSG)
         p = self.cond_drop_prob if cond_drop_prob is None else cond_drop_prob
@@ -483,7 +504,7 @@ class HipDenoiserMixin:
             assert prompt is not None and cond is not None, "conditional model needs prompt [b, n_p, dim_prompt] and cond [b, dim_prompt, n_c]"
             pr = prompt if (prompt.dtype == torch.float32 and prompt.is_contiguous()) else prompt.float().contiguous()
             cd = cond if (cond.dtype == torch.float32 and cond.is_contiguous()) else cond.float().contiguous()
-            state = self._cond_state(ns, pr, cd, p == 1, B, N)
+            state = self._cond_state(ns, pr, cd, p == 1, B, N, _prompt_lens_tensor(prompt_lens, B))
             state_ptr, n_c = state.data_ptr(), cd.shape[2]
             ws = self._workspace(ns, B, N, pr.shape[1], n_c)
         else:
@@ -515,10 +536,10 @@ class HipDenoiserMixin:
         """NS2:914-927."""
         if (cond_scale != 1. and self._hip_cfg["condition_on_prompt"] and not torch.is_grad_enabled() and len(args) == 2 and args[0].is_cuda
                 and args[0].shape[0] <= self.CFG_ONE_BATCH_MAX and kwargs.get("prompt") is not None and kwargs.get("cond") is not None
-                and kwargs.get("prompt_mask") is None and set(kwargs) <= {"prompt", "cond", "cond_row", "prompt_mask", "lens"}
+                and kwargs.get("prompt_mask") is None and set(kwargs) <= {"prompt", "cond", "cond_row", "prompt_mask", "lens", "prompt_lens"}
                 and not torch.cuda.is_current_stream_capturing()):
             return self._forward_hip_cfg(args[0], args[1], kwargs["prompt"], kwargs["cond"], cond_scale, cond_row=kwargs.get("cond_row"),
-                                         lens=kwargs.get("lens"))
+                                         lens=kwargs.get("lens"), prompt_lens=kwargs.get("prompt_lens"))
         logits = self.forward(*args, cond_drop_prob=0., **kwargs)
         if cond_scale == 1.:
             return logits
@@ -558,6 +579,16 @@ def _device_lens(lens, B, device):
     l = torch.as_tensor(lens).to(device=device, dtype=torch.int32).contiguous()
     assert l.shape == (B,), f"lens must hold one frame count per utterance: [{B}]"
     return l
+
+
+def _prompt_lens_tensor(prompt_lens, B):
+    """None, or `prompt_lens` as a tensor [B] (a list becomes one): what _cond_state keys its cache on and keeps alive"""
+    if prompt_lens is None:
+        return None
+    t = torch.as_tensor(prompt_lens)
+    if t.shape != (B,) or t.dtype.is_floating_point:
+        raise ValueError(f"prompt_lens must hold one integer prompt length per utterance: [{B}]")
+    return t
 
 
 # `prompt_mask` is in the reference's signature (NS2:929-937) but upstream cannot run with one: the resampler's attention

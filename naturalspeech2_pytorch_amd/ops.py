@@ -303,9 +303,12 @@ def embedding(ids: torch.Tensor, table: torch.Tensor, pad_id: int) -> torch.Tens
 
 
 def groupnorm_silu(x: torch.Tensor, B: int, weight: torch.Tensor, bias: torch.Tensor, groups: int = 8, eps: float = 1e-5,
-                   resid: Optional[torch.Tensor] = None, want_f32: bool = True, precision: Optional[int] = None):
+                   resid: Optional[torch.Tensor] = None, want_f32: bool = True, precision: Optional[int] = None,
+                   lens: Optional[torch.Tensor] = None):
     """GroupNorm(groups, C) + SiLU (+ resid after the SiLU) over token-major fp32 rows x [B * n, C] (ns2_groupnorm_silu).
-    Returns the fp32 rows, the operand planes of `precision` (when given), or (rows, planes)."""
+    Returns the fp32 rows, the operand planes of `precision` (when given), or (rows, planes).  lens (not in the reference): optional
+    integer [B] on the device, rows per utterance (ns2_groupnorm_silu_lens, include/ns2hip_ragged_front.h) -- the statistics of
+    utterance b run over its rows [0, lens[b]) and are bit-equal to the utterance alone; rows from lens[b] on come out as zeros."""
     x = _f32(x)
     M, C = x.shape
     n = M // B
@@ -314,12 +317,39 @@ def groupnorm_silu(x: torch.Tensor, B: int, weight: torch.Tensor, bias: torch.Te
     ws = torch.empty(max(lib.ns2_groupnorm_workspace_bytes(B, n, C, groups), 16), dtype=torch.uint8, device=x.device)
     of = torch.empty(M, C, dtype=torch.float32, device=x.device) if want_f32 else None
     pl = _out_planes(M, C, x.device, precision) if precision is not None else None
-    check(lib.ns2_groupnorm_silu(x.data_ptr(), B, n, C, groups, _f32(weight).data_ptr(), _f32(bias).data_ptr(), float(eps),
-                                 _p(None if resid is None else _f32(resid)), _p(of), pl.hi if pl else None, pl.lo if pl else None,
-                                 C, pl.precision if pl else 3, ws.data_ptr(), ws.numel(), _stream()), "ns2_groupnorm_silu")
+    if lens is not None:
+        rl = _front_lens(lens, B, x.device)          # held until the launch
+        check(lib.ns2_groupnorm_silu_lens(x.data_ptr(), B, n, C, groups, _f32(weight).data_ptr(), _f32(bias).data_ptr(), float(eps),
+                                          _p(None if resid is None else _f32(resid)), rl.data_ptr(), _p(of), pl.hi if pl else None,
+                                          pl.lo if pl else None, C, pl.precision if pl else 3, ws.data_ptr(), ws.numel(), _stream()),
+              "ns2_groupnorm_silu_lens")
+    else:
+        check(lib.ns2_groupnorm_silu(x.data_ptr(), B, n, C, groups, _f32(weight).data_ptr(), _f32(bias).data_ptr(), float(eps),
+                                     _p(None if resid is None else _f32(resid)), _p(of), pl.hi if pl else None, pl.lo if pl else None,
+                                     C, pl.precision if pl else 3, ws.data_ptr(), ws.numel(), _stream()), "ns2_groupnorm_silu")
     if of is not None and pl is not None:
         return of, pl
     return of if of is not None else pl
+
+
+def _front_lens(lens, B: int, device) -> torch.Tensor:
+    """lengths as the kernels of include/ns2hip_ragged_front.h read them: int32 [B], contiguous, on `device` (no host read; a tensor
+    that already is one comes back as it is)"""
+    l = torch.as_tensor(lens).to(device=device, dtype=torch.int32).contiguous()
+    assert l.shape == (B,), f"lengths must hold one count per utterance: [{B}]"
+    return l
+
+
+def zero_rows(t, B: int, n: int, lens: torch.Tensor):
+    """Zero rows [lens[b], n) of every utterance of `t` IN PLACE and return it (ns2_zero_rows_lens): `t` is operand Planes of
+    B * n rows, or a contiguous tensor whose B * n rows are whole 16-byte vectors (fp32 [B * n, C] with C % 4 == 0, [B, n, C]
+    likewise).  All-zero bits are 0.0 in fp32 and in every plane format.  lens: integer [B] on the device, clamped into [1, n]."""
+    buf = t.buf if isinstance(t, Planes) else t
+    assert buf.is_cuda and buf.is_contiguous() and buf.numel() % (B * n) == 0, "expected B * n contiguous rows on the device"
+    row_bytes = buf.numel() // (B * n) * buf.element_size()
+    rl = _front_lens(lens, B, buf.device)            # held until the launch
+    check(_lib.load().ns2_zero_rows_lens(buf.data_ptr(), row_bytes, B, n, rl.data_ptr(), _stream()), "ns2_zero_rows_lens")
+    return t
 
 
 # f0_to_coarse's fp32 constants, evaluated as the reference does (NS2:164-166)

@@ -114,7 +114,9 @@ class Transformer(nn.Module):
         return self._forward_hip(x, mask)
 
     @torch.no_grad()
-    def _forward_hip(self, x, mask=None):
+    def _forward_hip(self, x, mask=None, key_lens=None):
+        """key_lens (SpeechPromptEncoder's lens): integer [b] on the device, utterance i attends to keys [0, key_lens[i]) -- the
+        attention kernels' own key counts (ops.attention), not together with mask"""
         if self.causal:
             raise NotImplementedError("causal=True is not used by any reference caller of Transformer (NS2:252, 315)")
         if self.training and self.dropout > 0:
@@ -127,7 +129,8 @@ class Transformer(nn.Module):
         for pk in self._pack():
             xn = ops.rmsnorm(h, gamma=pk["g1"], precision=prec)
             qk, vt = ops.linear_qkv(pk["qkv"], xn, seq_len=n, split_col=2 * a, precision=prec)
-            o = ops.attention(qk, qk, vt, b, self.heads, n, n, q_col0=0, k_col0=a, precision=prec, key_mask=mask, head_dim=self.dim_head)
+            o = ops.attention(qk, qk, vt, b, self.heads, n, n, q_col0=0, k_col0=a, precision=prec, key_mask=mask, head_dim=self.dim_head,
+                              **({} if key_lens is None else dict(key_lens=key_lens)))
             h = ops.linear_f32(pk["out"], o, resid=h, precision=prec)
             xn = ops.rmsnorm(h, gamma=pk["g2"], precision=prec)
             ffh = ops.linear_geglu(pk["w1"], xn, pk["b1"], precision=prec)
