@@ -146,6 +146,19 @@ def model_forward_autograd(m, x, times, prompt=None, cond=None, cond_drop_prob=N
     return getattr(tp, "1")(_rmsnorm(h, getattr(tp, "0")))
 
 
+def model_forward_autograd_ragged(m, x, times, lens, prompt=None, cond=None, cond_drop_prob=None):
+    """`model_forward_autograd` with `lens` as the TRAINING pass of a ragged batch runs it (Model.forward under autograd with
+    `ragged_training`; the restatement of training/model_pass.py's rule, include/ns2hip_ragged_train.h): frames of x and cond from a
+    length on are selected to 0 at the entry (NaN may lie there, and a masked key's 0 * NaN would reach the rows before it), and the
+    returned rows from a length on are selected to 0, which zeroes their cotangent: utterance i contributes to the output and to
+    every gradient what it contributes alone at lens[i] frames.  Lengths may be a device tensor: nothing here reads them on the host."""
+    b, n, _ = x.shape
+    mask = _prefix_mask(lens, b, n, x.device)
+    if cond is not None:
+        cond = _keep_rows(cond.transpose(1, 2), _prefix_mask(lens, b, cond.shape[-1], x.device)).transpose(1, 2)
+    return _keep_rows(model_forward_autograd(m, _keep_rows(x, mask), times, prompt=prompt, cond=cond, cond_drop_prob=cond_drop_prob, lens=lens), mask)
+
+
 # ---- the plain Transformer and the two conditioning encoders under autograd (NS2:1073-1115, 228-341): joint training of
 # prompt_enc / phoneme_enc with the denoiser (NS2:1538-1543) needs gradients through them.  The default (`train_backend="composite"`), the
 # CPU path, and the fall-back of `train_backend="hip"` (training/encoder_pass.py: `*_forward_train`) for what `training.encoder_unsupported_reason` names.

@@ -66,7 +66,11 @@ NS2_DEVINL uint4 mask_chunk(uint4 v, int nvalid) {
 // DROP (with WLSE only): the attention dropout of the encoders' training pass (ATT:100-101) -- P is multiplied by keep / (1 - p)
 // AFTER the running sum l is taken, so O = sum_k P_k keep_k / (1 - p) v_k and the log-sum-exp is the plain one; keep = dropout_keep.h.
 // Again a separate instantiation: every kernel without it compiles to what it was.
-template <int NSPLIT, bool F16, int NW, bool WLSE, int D = 64, bool DROP = false>
+// QLENS (with WLSE only): the training forward of a ragged batch (include/ns2hip_ragged_train.h; self-attention, Nq == Nk): AttnArgs::klens
+// are the utterances' lengths on the QUERY side too.  Query rows from the length on load no q, and leave as o = zero bits in the output
+// format and lse = +inf (the backward's statistic of a query beyond Nq); a workgroup whose whole query tile lies there writes those and
+// returns before anything is staged.  Rows before the length see what they see alone at Nq = Nk = length.  Once more a separate instantiation.
+template <int NSPLIT, bool F16, int NW, bool WLSE, int D = 64, bool DROP = false, bool QLENS = false>
 __global__ __launch_bounds__(64 * NW, ((NSPLIT == 3 && D == 128) ? 1 : (NSPLIT == 3 || D == 128) ? 2 : 3)) void attn_kernel(const AttnArgs a) {
   using G = AtGeom<D>;
   constexpr int DC = D / 16;                         // 16-deep k chunks of the q . k contraction
@@ -76,6 +80,7 @@ __global__ __launch_bounds__(64 * NW, ((NSPLIT == 3 && D == 128) ? 1 : (NSPLIT =
   constexpr int NT = 64 * NW;                        // threads
   constexpr int CPT = 8 * D / NT;                    // 16-B chunks of one plane per thread: the K tile has 64 x D / 8, the V^T tile D x 8
   static_assert(CPT >= 1 && CPT * NT == 8 * D, "whole chunks per thread");
+  static_assert(!QLENS || (WLSE && !DROP), "query lengths belong to the training forward without dropout");
   constexpr int STAGE_BYTES = NP * (G::KPLANE + G::VPLANE);     // K planes then V^T planes
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
@@ -84,7 +89,7 @@ __global__ __launch_bounds__(64 * NW, ((NSPLIT == 3 && D == 128) ? 1 : (NSPLIT =
   // 1-D grid, XCD-aware: the query tiles of one (batch, head) get consecutive remapped ids and therefore share one
   // XCD's L2 for their K / V^T re-reads (rocprofv3 FETCH_SIZE showed ~3x over-fetch with the default round-robin).
   const int nqt = (a.Nq + QB - 1) / QB;
-  int bid = xcd_remap(blockIdx.x, gridDim.x);
+  int bid = QLENS ? xcd_spread(blockIdx.x, gridDim.x, nqt) : xcd_remap(blockIdx.x, gridDim.x);      // (QLENS: the pairs differ in work)
   const int qt = bid % nqt;
   bid /= nqt;
   const int h = bid % a.H, b = bid / a.H;
@@ -93,6 +98,21 @@ __global__ __launch_bounds__(64 * NW, ((NSPLIT == 3 && D == 128) ? 1 : (NSPLIT =
   // keys this utterance attends to: a.Nk, or its own count (AttnArgs::klens, clamped into [1, Nk]); a.Nk stays the stride of every address
   int nk = a.Nk;
   if (a.klens) nk = min(max(a.klens[b], 1), a.Nk);
+  bool q_live = q_ok;                                  // QLENS: the row exists AND lies inside its utterance
+  if constexpr (QLENS) {
+    q_live = qrow < nk;
+    if (qt * QB >= nk) {                               // the whole query tile lies beyond the utterance
+      if (q_ok) {
+        if (hi == 0) a.lse[((long)b * a.H + h) * a.Nq + qrow] = INFINITY;
+        bf16_t* orow = a.o_hi + ((long)b * a.Nq + qrow) * pld(a.ldo, a.o_lo != nullptr);
+#pragma unroll
+        for (int dt = 0; dt < D / 32; ++dt)
+#pragma unroll
+          for (int gq = 0; gq < 4; ++gq) store_cols4(orow, h * D + 32 * dt + 8 * gq + 4 * hi, 0.f, 0.f, 0.f, 0.f, a.o_fmt, a.o_lo != nullptr);
+      }
+      return;
+    }
+  }
 
   const bf16_t* q_pl[2] = {a.q_hi, a.q_lo};
   const bf16_t* k_pl[2] = {a.k_hi, a.k_lo};
@@ -107,7 +127,7 @@ __global__ __launch_bounds__(64 * NW, ((NSPLIT == 3 && D == 128) ? 1 : (NSPLIT =
 #pragma unroll
     for (int c = 0; c < DC; ++c) {
       uint4 v = make_uint4(0u, 0u, 0u, 0u);
-      if (q_ok) v = ld16g(q_pl[p] + ((long)b * a.Nq + qrow) * pld(a.ldq, qil) + pcol(a.q_col0 + h * D + 16 * c + 8 * hi, qil));
+      if (q_live) v = ld16g(q_pl[p] + ((long)b * a.Nq + qrow) * pld(a.ldq, qil) + pcol(a.q_col0 + h * D + 16 * c + 8 * hi, qil));
       qf[p][c] = *reinterpret_cast<bf16x8*>(&v);
     }
 
@@ -291,8 +311,18 @@ __global__ __launch_bounds__(64 * NW, ((NSPLIT == 3 && D == 128) ? 1 : (NSPLIT =
 
   // ---- normalise and write O[q][h*64 + d]: lane holds d = 32dt + 8g + 4hi + e for its query
   const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
-  const float inv = 1.0f / l_tot;
-  if constexpr (WLSE) if (q_ok && hi == 0) a.lse[((long)b * a.H + h) * a.Nq + qrow] = m_run + log2f(l_tot);   // training: P is recomputed from this
+  float inv = 1.0f / l_tot;
+  float lse_row = m_run + log2f(l_tot);
+  if constexpr (QLENS) {
+    if (!q_live) {                                     // a row of the tensor beyond the utterance: zero bits, lse = +inf
+      inv = 1.0f; lse_row = INFINITY;
+#pragma unroll
+      for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) ot[dt][r] = 0.f;
+    }
+  }
+  if constexpr (WLSE) if (q_ok && hi == 0) a.lse[((long)b * a.H + h) * a.Nq + qrow] = lse_row;   // training: P is recomputed from this
   if (q_ok) {
     bf16_t* orow = a.o_hi + ((long)b * a.Nq + qrow) * pld(a.ldo, oil);
 #pragma unroll
@@ -310,16 +340,16 @@ __global__ __launch_bounds__(64 * NW, ((NSPLIT == 3 && D == 128) ? 1 : (NSPLIT =
 
 namespace ns2 {
 
-template <int NSPLIT, bool F16, int NW, bool WLSE, int D = 64, bool DROP = false>
+template <int NSPLIT, bool F16, int NW, bool WLSE, int D = 64, bool DROP = false, bool QLENS = false>
 static hipError_t launch_attn_w(const AttnArgs& a, hipStream_t s) {
   const size_t lds = 2 * (NSPLIT == 3 ? 2 : 1) * (AtGeom<D>::KPLANE + AtGeom<D>::VPLANE);
   static DynLdsAttr attr;
   {
-    hipError_t e = attr.ensure(reinterpret_cast<const void*>(&attn_kernel<NSPLIT, F16, NW, WLSE, D, DROP>), (int)lds);
+    hipError_t e = attr.ensure(reinterpret_cast<const void*>(&attn_kernel<NSPLIT, F16, NW, WLSE, D, DROP, QLENS>), (int)lds);
     if (e != hipSuccess) return e;
   }
   dim3 grid(((a.Nq + 32 * NW - 1) / (32 * NW)) * a.H * a.B);
-  hipLaunchKernelGGL((attn_kernel<NSPLIT, F16, NW, WLSE, D, DROP>), grid, dim3(64 * NW), lds, s, a);
+  hipLaunchKernelGGL((attn_kernel<NSPLIT, F16, NW, WLSE, D, DROP, QLENS>), grid, dim3(64 * NW), lds, s, a);
   return hipGetLastError();
 }
 template <int NSPLIT, bool F16>
@@ -332,7 +362,10 @@ static hipError_t launch_attn_t(const AttnArgs& a, hipStream_t s) {
     if constexpr (NSPLIT == 3) { if (a.lse) return launch_attn_w<NSPLIT, F16, 4, true, 64, true>(a, s); }
     return hipErrorInvalidValue;
   }
-  if constexpr (NSPLIT == 3) { if (a.lse) return launch_attn_w<NSPLIT, F16, 4, true>(a, s); }   // training runs in precision 3
+  if constexpr (NSPLIT == 3) {                                                                  // training runs in precision 3
+    if (a.lse && a.klens) return launch_attn_w<NSPLIT, F16, 4, true, 64, false, true>(a, s);    // ... on a ragged batch
+    if (a.lse) return launch_attn_w<NSPLIT, F16, 4, true>(a, s);
+  }
   else if (a.lse) return hipErrorInvalidValue;
   return launch_attn_w<NSPLIT, F16, 4, false>(a, s);
 }
@@ -393,7 +426,8 @@ hipError_t launch_attention(const AttnArgs& a_in, int nsplit, hipStream_t s) {
   if (!planes_ok(a.q_hi, a.q_lo) || !planes_ok(a.k_hi, a.k_lo) || !planes_ok(a.vt_hi, a.vt_lo) || !planes_ok(a.o_hi, a.o_lo))
     return hipErrorInvalidValue;
   if (a.vt_lo && (a.vt_ld & 31)) return hipErrorInvalidValue;   // interleaved rows come in 32-column blocks
-  if (a.klens && (a.kmask || a.lse || a.drop_seed)) return hipErrorInvalidValue;   // key counts belong to the plain inference forward
+  if (a.klens && (a.kmask || a.drop_seed)) return hipErrorInvalidValue;            // key counts: the plain inference forward, or ...
+  if (a.klens && a.lse && (nsplit != 3 || a.Nq != a.Nk)) return hipErrorInvalidValue;   // ... the training forward of a self-attention (QLENS)
   if (nsplit == 3) {
     if (!a.q_lo || !a.k_lo || !a.vt_lo) return hipErrorInvalidValue;
     return launch_attn_t<3, false>(a, s);

@@ -582,25 +582,82 @@ typedef __attribute__((address_space(3))) ab2_v4s ab2_lds_v4s_t;
 constexpr int AB2_ROW = 256, AB2_MAT = 64 * AB2_ROW, AB2_STAGE = 2 * AB2_MAT;
 NS2_DEVINL int ab2_f(int r) { return ((r & 3) << 2) | ((r >> 2) & 3); }
 
+// The own row's results leave the kernel: lane holds d = 32 dt + 8 gq + 4 hi + e of row `orow` of utterance b (Sown rows per utterance);
+// acc1 = dQ^T (role 0) / dK^T (role 1), still without the softmax scale, acc2 = dV^T (role 1)
+template <int ROLE>
+NS2_DEVINL void ab2_store_own(const AttnBwdArgs& a, int b, int h, int orow, int hi, int Sown, const f32x16 (&acc1)[2], const f32x16 (&acc2)[2]) {
+  if (ROLE == 0 ? a.gp_q : a.gp_kv) {
+    // operand planes: the lane's 4-column groups of its own row (lanes l31 and l31 + 32 interleave the groups of a 32-column line)
+    bf16_t* prow = a.gp_hi + ((long)b * Sown + orow) * 2L * a.gp_ld;
+    const int c1 = (ROLE == 0 ? a.dq_col0 : a.dk_col0) + h * 64, c2 = a.dv_col0 + h * 64;
+#pragma unroll
+    for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+      for (int gq = 0; gq < 4; ++gq) {
+        const int dcol = 32 * dt + 8 * gq + 4 * hi;
+        store_cols4(prow, c1 + dcol, acc1[dt][4 * gq] * a.scale, acc1[dt][4 * gq + 1] * a.scale, acc1[dt][4 * gq + 2] * a.scale,
+                    acc1[dt][4 * gq + 3] * a.scale, a.gp_fmt, true);
+        if constexpr (ROLE == 1)
+          store_cols4(prow, c2 + dcol, acc2[dt][4 * gq], acc2[dt][4 * gq + 1], acc2[dt][4 * gq + 2], acc2[dt][4 * gq + 3], a.gp_fmt, true);
+      }
+    return;
+  }
+  float* o1 = ROLE == 0 ? a.dq + ((long)b * a.Nq + orow) * a.lddq + a.dq_col0 + h * 64
+                        : a.dk + ((long)b * a.Nk + orow) * a.lddk + a.dk_col0 + h * 64;
+#pragma unroll
+  for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+    for (int gq = 0; gq < 4; ++gq) {
+      const int dcol = 32 * dt + 8 * gq + 4 * hi;
+      *reinterpret_cast<float4*>(o1 + dcol) = make_float4(acc1[dt][4 * gq] * a.scale, acc1[dt][4 * gq + 1] * a.scale,
+                                                          acc1[dt][4 * gq + 2] * a.scale, acc1[dt][4 * gq + 3] * a.scale);
+      if constexpr (ROLE == 1) {
+        float* o2 = a.dv + ((long)b * a.Nk + orow) * a.lddv + a.dv_col0 + h * 64;
+        *reinterpret_cast<float4*>(o2 + dcol) = make_float4(acc2[dt][4 * gq], acc2[dt][4 * gq + 1], acc2[dt][4 * gq + 2], acc2[dt][4 * gq + 3]);
+      }
+    }
+}
+
 // MD = the encoders' training pass (a separate instantiation: the kernels of the denoiser's pass keep their code and registers): a
 // key-padding mask -- masked keys have P = 0: role 0 per walked row (the tile's 64 mask bytes arrive in LDS with the tile), role 1 for
 // the whole own row, which ends with dK = dV = 0 -- and the
 // attention dropout of dropout_keep.h: with keep' = keep / (1 - p),  dP = (dO V^T) keep' ; dS = P (dP - delta) ; dV^T += dO^T (P keep'),
 // delta = rowsum(dO * O) of the post-dropout O as attn_delta_kernel computes it.
-template <int ROLE, bool MD = false>
+// LENS = the denoiser's pass on a ragged batch (include/ns2hip_ragged_train.h; self-attention, Nq == Nk; a third instantiation: the other
+// two keep their code): len_b = clamp(lens[b], 1, N), read once per workgroup into a scalar register, stands in for Nown and Nwalk in every
+// BOUND -- ceil(len_b / 64) tiles walked, rows of the boundary tile from len_b on out of the zero page (role 1: their statistics out of
+// ab2_inf_zero), whatever memory holds there -- while a.Nq / a.Nk stay the strides of every address.  Own rows from len_b on are written
+// as exact zeros; a workgroup whose own tile lies wholly beyond len_b writes them and returns before its first DMA piece and barrier.
+template <int ROLE, bool MD = false, bool LENS = false>
 __global__ __launch_bounds__(256, 2) void attn_bwd2_kernel(const AttnBwdArgs a) {
+  static_assert(!(MD && LENS), "lengths exclude the key mask and dropout");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   float* s_stat = reinterpret_cast<float*>(smem + 2 * AB2_STAGE);       // [stage][lse 64 | delta 64] (role 1)
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l31 = lane & 31, hi = lane >> 5;
-  const int Nown = ROLE == 0 ? a.Nq : a.Nk, Nwalk = ROLE == 0 ? a.Nk : a.Nq;
-  const int nown_t = (Nown + 127) / 128;
-  int bid = xcd_remap(blockIdx.x, gridDim.x);
+  const int Sown = ROLE == 0 ? a.Nq : a.Nk, Swalk = ROLE == 0 ? a.Nk : a.Nq;      // row counts of the tensors: the strides of every address
+  const int nown_t = (Sown + 127) / 128;
+  int bid = LENS ? xcd_spread(blockIdx.x, gridDim.x, nown_t) : xcd_remap(blockIdx.x, gridDim.x);
   const int ot = bid % nown_t;
   bid /= nown_t;
   const int h = bid % a.H, b = bid / a.H;
   const int orow = ot * 128 + wave * 32 + l31;
+  int Nown = Sown, Nwalk = Swalk;                                                  // the bounds: rows that exist for this utterance
+  if constexpr (LENS) {
+    Nown = Nwalk = __builtin_amdgcn_readfirstlane(min(max(a.lens[b], 1), Sown));
+    if (ot * 128 >= Nown) {                                                        // nothing of this utterance in the own tile
+      if (orow < Sown) {
+        f32x16 z[2];
+#pragma unroll
+        for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) z[dt][r] = 0.f;
+        ab2_store_own<ROLE>(a, b, h, orow, hi, Sown, z, z);
+      }
+      return;
+    }
+  }
   const bool own_ok = orow < Nown;
 
   // own-side fragments (B operands): X = Q (role 0) / K (role 1); G = dO (role 0) / V (role 1)
@@ -615,8 +672,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd2_kernel(const AttnBwdArgs a) 
     for (int c = 0; c < 4; ++c) {
       uint4 vx = make_uint4(0u, 0u, 0u, 0u), vg = make_uint4(0u, 0u, 0u, 0u);
       if (own_ok) {
-        vx = *reinterpret_cast<const uint4*>(xb + ((long)b * Nown + orow) * 2L * ldx + pcol(xcol + h * 64 + 16 * c + 8 * hi, true) + 32 * p);
-        vg = *reinterpret_cast<const uint4*>(gb + ((long)b * Nown + orow) * 2L * ldg + pcol(gcol + h * 64 + 16 * c + 8 * hi, true) + 32 * p);
+        vx = *reinterpret_cast<const uint4*>(xb + ((long)b * Sown + orow) * 2L * ldx + pcol(xcol + h * 64 + 16 * c + 8 * hi, true) + 32 * p);
+        vg = *reinterpret_cast<const uint4*>(gb + ((long)b * Sown + orow) * 2L * ldg + pcol(gcol + h * 64 + 16 * c + 8 * hi, true) + 32 * p);
       }
       xf[p][c] = *reinterpret_cast<bf16x8*>(&vx);
       gf[p][c] = *reinterpret_cast<bf16x8*>(&vg);
@@ -656,8 +713,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd2_kernel(const AttnBwdArgs a) 
     const int tr = 4 * (j & 15) + drow;
     const int lc = dpos ^ ((drow << 2) | (i & 3));
     dtr[i] = tr;
-    dsrc[i] = mat == 0 ? yb + ((long)b * Nwalk + tr) * 2L * ldy + pcol(ycol + h * 64, true) + lc * 8
-                       : ygb + ((long)b * Nwalk + tr) * 2L * ldyg + pcol(ygcol + h * 64, true) + lc * 8;
+    dsrc[i] = mat == 0 ? yb + ((long)b * Swalk + tr) * 2L * ldy + pcol(ycol + h * 64, true) + lc * 8
+                       : ygb + ((long)b * Swalk + tr) * 2L * ldyg + pcol(ygcol + h * 64, true) + lc * 8;
   }
   auto issue_tile = [&](int t, int stage) __attribute__((always_inline)) {
     const int r0 = t * 64;
@@ -689,7 +746,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd2_kernel(const AttnBwdArgs a) 
       // same in-order queue BEHIND the pieces above, and the compiler's wait for it would wait for them too
       if (wave < 2) {
         const int q = r0 + lane;
-        const float* p = q < a.Nq ? (wave == 0 ? a.lse : a.delta) + ((long)b * a.H + h) * a.Nq + q : ab2_inf_zero + wave;
+        const float* p = q < Nwalk ? (wave == 0 ? a.lse : a.delta) + ((long)b * a.H + h) * a.Nq + q : ab2_inf_zero + wave;
         const unsigned dst = (unsigned)(size_t)(s_stat + stage * 128 + wave * 64);
         asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dword %0, off" :: "v"(p), "s"(dst) : "memory", "m0");
       }
@@ -850,49 +907,30 @@ __global__ __launch_bounds__(256, 2) void attn_bwd2_kernel(const AttnBwdArgs a) 
     }
   }
 
-  // ---- store: lane holds d = 32 dt + 8 gq + 4 hi + e of its own row
-  if (!own_ok) return;
-  if (ROLE == 0 ? a.gp_q : a.gp_kv) {
-    // operand planes: the lane's 4-column groups of its own row (lanes l31 and l31 + 32 interleave the groups of a 32-column line)
-    bf16_t* prow = a.gp_hi + ((long)b * Nown + orow) * 2L * a.gp_ld;
-    const int c1 = (ROLE == 0 ? a.dq_col0 : a.dk_col0) + h * 64, c2 = a.dv_col0 + h * 64;
+  // ---- store (ab2_store_own)
+  if constexpr (LENS) {
+    if (orow >= Sown) return;
+    if (!own_ok) {                                   // a row of the tensor beyond the utterance: exact zeros
 #pragma unroll
-    for (int dt = 0; dt < 2; ++dt)
+      for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
-      for (int gq = 0; gq < 4; ++gq) {
-        const int dcol = 32 * dt + 8 * gq + 4 * hi;
-        store_cols4(prow, c1 + dcol, acc1[dt][4 * gq] * a.scale, acc1[dt][4 * gq + 1] * a.scale, acc1[dt][4 * gq + 2] * a.scale,
-                    acc1[dt][4 * gq + 3] * a.scale, a.gp_fmt, true);
-        if constexpr (ROLE == 1)
-          store_cols4(prow, c2 + dcol, acc2[dt][4 * gq], acc2[dt][4 * gq + 1], acc2[dt][4 * gq + 2], acc2[dt][4 * gq + 3], a.gp_fmt, true);
-      }
-    return;
-  }
-  float* o1 = ROLE == 0 ? a.dq + ((long)b * a.Nq + orow) * a.lddq + a.dq_col0 + h * 64
-                        : a.dk + ((long)b * a.Nk + orow) * a.lddk + a.dk_col0 + h * 64;
-#pragma unroll
-  for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-    for (int gq = 0; gq < 4; ++gq) {
-      const int dcol = 32 * dt + 8 * gq + 4 * hi;
-      *reinterpret_cast<float4*>(o1 + dcol) = make_float4(acc1[dt][4 * gq] * a.scale, acc1[dt][4 * gq + 1] * a.scale,
-                                                          acc1[dt][4 * gq + 2] * a.scale, acc1[dt][4 * gq + 3] * a.scale);
-      if constexpr (ROLE == 1) {
-        float* o2 = a.dv + ((long)b * a.Nk + orow) * a.lddv + a.dv_col0 + h * 64;
-        *reinterpret_cast<float4*>(o2 + dcol) = make_float4(acc2[dt][4 * gq], acc2[dt][4 * gq + 1], acc2[dt][4 * gq + 2], acc2[dt][4 * gq + 3]);
-      }
+        for (int r = 0; r < 16; ++r) { acc1[dt][r] = 0.f; acc2[dt][r] = 0.f; }
     }
+  } else {
+    if (!own_ok) return;
+  }
+  ab2_store_own<ROLE>(a, b, h, orow, hi, Sown, acc1, acc2);
 }
 
-template <int ROLE, bool MD = false>
+template <int ROLE, bool MD = false, bool LENS = false>
 static hipError_t launch_attn_bwd2_role(const AttnBwdArgs& a, hipStream_t s) {
   const size_t lds = 2 * AB2_STAGE + 2 * 128 * sizeof(float);
   static DynLdsAttr attr;
-  hipError_t e = attr.ensure(reinterpret_cast<const void*>(&attn_bwd2_kernel<ROLE, MD>), (int)lds);
+  hipError_t e = attr.ensure(reinterpret_cast<const void*>(&attn_bwd2_kernel<ROLE, MD, LENS>), (int)lds);
   if (e != hipSuccess) return e;
   const int nown = ROLE == 0 ? a.Nq : a.Nk;
   dim3 grid(((nown + 127) / 128) * a.H * a.B);
-  hipLaunchKernelGGL((attn_bwd2_kernel<ROLE, MD>), grid, dim3(256), lds, s, a);
+  hipLaunchKernelGGL((attn_bwd2_kernel<ROLE, MD, LENS>), grid, dim3(256), lds, s, a);
   return hipGetLastError();
 }
 
@@ -909,6 +947,12 @@ hipError_t launch_attention_bwd(const AttnBwdArgs& a, hipStream_t s) {
   }
   if (want_kv && !a.gp_kv && (!a.dk || !a.dv || ((a.lddk | a.lddv | a.dk_col0 | a.dv_col0) & 3))) return hipErrorInvalidValue;
   if (want_q && !a.gp_q && ((a.lddq & 3) || (a.dq_col0 & 3))) return hipErrorInvalidValue;
+  if (a.lens) {                                        // the denoiser's pass on a ragged batch: self-attention, no mask, no dropout
+    if (a.kmask || a.drop_seed || a.Nq != a.Nk) return hipErrorInvalidValue;
+    if (want_q) { hipError_t e = launch_attn_bwd2_role<0, false, true>(a, s); if (e != hipSuccess) return e; }
+    if (want_kv) { hipError_t e = launch_attn_bwd2_role<1, false, true>(a, s); if (e != hipSuccess) return e; }
+    return hipSuccess;
+  }
   if (a.kmask || a.drop_seed) {                        // the encoders' pass: mask and / or dropout
     if (a.drop_seed ? !(a.drop_scale >= 1.f) : (a.drop_thr != 0u || a.drop_scale != 1.f)) return hipErrorInvalidValue;
     if (want_q) { hipError_t e = launch_attn_bwd2_role<0, true>(a, s); if (e != hipSuccess) return e; }

@@ -232,7 +232,7 @@ extern "C" int ns2_wavenet_block(const ns2_weight* w, const uint16_t* a_hi, cons
 
 // The one translation of the C argument block into the kernels' (ns2_kernels.h AttnArgs, whose defaults are "nothing optional").
 // Everything ns2_attention_fwd refuses, it refuses here, before any HIP call; launch_attention judges the rest.
-static int attn_args_from(const ns2_attn_args* p, AttnArgs* out) {
+int ns2::attn_args_from(const ns2_attn_args* p, AttnArgs* out) {
   ARGCHK(p != nullptr, "ns2_attention_fwd: null argument block");
   ARGCHK(p->q_hi && p->k_hi && p->vt_hi && p->o_hi && prec_ok(p->precision), "ns2_attention_fwd: bad arguments");
   ARGCHK(p->head_dim == 0 || p->head_dim == 32 || p->head_dim == 64 || p->head_dim == 128, "ns2_attention_fwd: head_dim must be 32, 64 or 128 (0 = 64)");

@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <cstring>
 
+#include "../../include/ns2hip_ragged_train.h"
 #include "ns2_host.h"
 
 using namespace ns2;
@@ -242,8 +243,7 @@ extern "C" int ns2_attention_delta(const float* d_out, int64_t ld_dout, const ui
   HIPRET(launch_attn_delta(d_out, (long)ld_dout, o_hi, o_lo, ldo, B, H, Nq, delta, (hipStream_t)stream, operand_fmt(o_precision)));
   return NS2_OK;
 }
-extern "C" int ns2_attention_bwd(const ns2_attn_bwd_args* p, void* stream) {
-  ARGCHK(p != nullptr, "ns2_attention_bwd: null argument block");
+static int attention_bwd(const ns2_attn_bwd_args* p, const int* lens, void* stream) {
   ARGCHK(p->gp_precision == 0 || p->gp_precision == 3 || p->gp_precision == 4, "ns2_attention_bwd: gp_precision 3 (bf16 hi / lo planes) or 4 (FMT_H8 lines)");
   AttnBwdArgs a;
   if (const char* bad = set_attn_dropout(a, p->dropout_p, p->dropout_seed, p->dropout_call)) { set_error("ns2_attention_bwd: %s", bad); return NS2_ERR_ARG; }
@@ -259,8 +259,38 @@ extern "C" int ns2_attention_bwd(const ns2_attn_bwd_args* p, void* stream) {
   a.gp_hi = p->gp_hi; a.gp_lo = p->gp_lo; a.gp_ld = p->gp_ld; a.gp_q = p->gp_q; a.gp_kv = p->gp_kv;
   a.gp_fmt = operand_fmt(p->gp_precision);
   a.kmask = p->key_mask;
+  a.lens = lens;
   HIPRET(launch_attention_bwd(a, (hipStream_t)stream));
   return NS2_OK;
+}
+extern "C" int ns2_attention_bwd(const ns2_attn_bwd_args* p, void* stream) {
+  ARGCHK(p != nullptr, "ns2_attention_bwd: null argument block");
+  return attention_bwd(p, nullptr, stream);
+}
+
+// ---- ragged training batches (include/ns2hip_ragged_train.h): what these entries refuse comes first, under their own names; the blocks
+// themselves are ns2_attention_fwd's and ns2_attention_bwd's
+extern "C" int ns2_attention_train_fwd_lens(const ns2_attn_args* p, const int* lens, void* stream) {
+  ARGCHK(p != nullptr, "ns2_attention_train_fwd_lens: null argument block");
+  ARGCHK(lens != nullptr, "ns2_attention_train_fwd_lens: lens is null (ns2_attention_fwd is the call without lengths)");
+  ARGCHK(p->lse, "ns2_attention_train_fwd_lens: lse is missing (this is the training forward; ns2_attention_fwd_lens is the inference one)");
+  ARGCHK(p->Nq == p->Nk, "ns2_attention_train_fwd_lens: Nq != Nk (lengths belong to a self-attention)");
+  ARGCHK(!p->key_mask, "ns2_attention_train_fwd_lens: key_mask together with lens (one way of shortening the keys per call)");
+  ARGCHK(p->dropout_p == 0.f, "ns2_attention_train_fwd_lens: dropout together with lens (the denoiser's self-attention has none)");
+  AttnArgs a;
+  if (int rc = attn_args_from(p, &a)) return rc;
+  a.klens = lens;
+  HIPRET(launch_attention(a, p->precision, (hipStream_t)stream));
+  return NS2_OK;
+}
+extern "C" int ns2_attention_bwd_lens(const ns2_attn_bwd_args* p, const int* lens, void* stream) {
+  ARGCHK(p != nullptr, "ns2_attention_bwd_lens: null argument block");
+  ARGCHK(lens != nullptr, "ns2_attention_bwd_lens: lens is null (ns2_attention_bwd is the call without lengths)");
+  ARGCHK(p->lse, "ns2_attention_bwd_lens: lse is missing");
+  ARGCHK(p->Nq == p->Nk, "ns2_attention_bwd_lens: Nq != Nk (lengths belong to a self-attention)");
+  ARGCHK(!p->key_mask, "ns2_attention_bwd_lens: key_mask together with lens (one way of shortening the keys per call)");
+  ARGCHK(p->dropout_p == 0.f, "ns2_attention_bwd_lens: dropout together with lens (the denoiser's self-attention has none)");
+  return attention_bwd(p, lens, stream);
 }
 extern "C" int ns2_dropout_keep_mask(const uint32_t* seed, unsigned call, float dropout_p, int B, int H, int Nq, int Nk, uint8_t* out, void* stream) {
   ARGCHK(seed && out, "ns2_dropout_keep_mask: null pointer");

@@ -47,6 +47,10 @@ inline const char* set_attn_dropout(KernelArgs& a, float p, const uint32_t* seed
   return nullptr;
 }
 
+// capi.cpp: the one translation of ns2_attn_args into the kernels' block (default-constructed by the caller); refuses what
+// ns2_attention_fwd refuses, before any HIP call.  Shared with capi_train.cpp (ns2_attention_train_fwd_lens).
+int attn_args_from(const ns2_attn_args* p, AttnArgs* out);
+
 struct PackedW {                 // bf16 split-plane weight, rows padded to 256, K contiguous
   bf16_t* hi = nullptr; bf16_t* lo = nullptr;
   int rows_p = 0, ldk = 0, N = 0, nkt = 0, kt_per_tap = 0;

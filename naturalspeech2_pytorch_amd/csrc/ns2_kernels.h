@@ -141,7 +141,9 @@ struct AttnArgs {
   // ragged batches (include/ns2hip_ragged.h): per-utterance key counts in DEVICE memory, int32 [B], read by the kernels alone (never on
   // the host: a captured launch follows rewritten values).  Utterance b attends to keys [0, clamp(klens[b], 1, Nk)); keys beyond are
   // treated as keys beyond Nk are (score -inf, K rows and V^T columns read as zeros, so they may hold anything); Nk stays the stride.
-  // null = every utterance has Nk keys.  Excludes kmask, lse and dropout.
+  // null = every utterance has Nk keys.  Excludes kmask and dropout.  Together with lse (the training forward of a ragged batch,
+  // include/ns2hip_ragged_train.h; precision 3, Nq == Nk): the counts are the utterances' lengths on the query side too -- o rows from the
+  // length on are written as zero bits, their lse as +inf.
   const int* klens = nullptr;
 };                                                       // precision: 3 bf16x3, 1 bf16, 2 and 4: one IEEE-half product
 hipError_t launch_attention(const AttnArgs& a, int precision, hipStream_t s);
@@ -349,6 +351,10 @@ struct AttnBwdArgs {                                                // (every fi
   // the encoders' training pass: key-padding mask [B, Nk] (1 = attend; null = none) and attention dropout as in AttnArgs (drop_seed null =
   // none).  Either one selects the MD instantiations of the kernel; without them the kernels of the denoiser's pass run, unchanged.
   const unsigned char* kmask = nullptr; const uint32_t* drop_seed = nullptr; uint32_t drop_thr = 0u, drop_call = 0u; float drop_scale = 1.f;
+  // ragged training batches (include/ns2hip_ragged_train.h): per-utterance lengths in DEVICE memory, int32 [B], read by the kernels alone.
+  // Self-attention only (Nq == Nk); utterance b's gradients are those of rows [0, clamp(lens[b], 1, N)) alone, rows beyond are written as
+  // zeros, N stays the stride.  Selects the LENS instantiations; excludes kmask and dropout.  null = every utterance has N rows.
+  const int* lens = nullptr;
 };
 hipError_t launch_attention_bwd(const AttnBwdArgs& a, hipStream_t s);
 

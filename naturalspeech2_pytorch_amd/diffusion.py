@@ -505,7 +505,7 @@ class NaturalSpeech2(nn.Module):
         return cond, dict(duration=duration_loss, pitch=pitch_loss, align=align_loss, bin=bin_loss, aux=aux)
 
     def forward(self, audio, text=None, text_lens=None, mel=None, mel_lens=None, codes=None, prompt=None, pitch=None,
-                *args, cond=None, prompt_enc=None, times=None, noise=None, return_aux_losses=False, **kwargs):
+                *args, cond=None, prompt_enc=None, times=None, noise=None, return_aux_losses=False, audio_lens=None, **kwargs):
         """Reference signature; `cond`, `prompt_enc` (module docstring) and `times`, `noise` (deterministic parity tests) are
         the keyword-only extras.  The model call runs the autograd composite when gradients are required.
 
@@ -515,8 +515,30 @@ class NaturalSpeech2(nn.Module):
         goes through AudioToMel; without `pitch`, a wrapper built with `build_pitch_extractor=True` runs its PitchExtractor on
         the raw audio (without one, the missing `pitch` raises as before).  `return_aux_losses=True`
         (not in the reference, needs build_duration_pitch=True) returns (loss, dict(duration=, pitch=, align=, bin=, aux=)),
-        the only way to train the Aligner and the predictor."""
+        the only way to train the Aligner and the predictor.
+
+        `audio_lens` (not in the reference; needs a model built with `ragged_training=True`): latent frames per utterance of a padded
+        batch, integer [b].  The lengths go to the model as `lens=`, and the loss of utterance i is the mean of the squared error over
+        its own frames [0, audio_lens[i]) x dim -- what it is for the utterance alone -- before the reference's (loss * weight).mean().
+        Mask and divisor are formed on the device from the lengths (no host read: a captured step follows rewritten lengths); what
+        audio, noise and cond hold from a length on never reaches the loss or a gradient.  Latents only: raw audio, the RVQ
+        cross-entropy term and `prompt_lens` are not taken together with it (NotImplementedError)."""
         is_raw = audio.ndim == 2
+        if audio_lens is not None:
+            if is_raw:
+                raise NotImplementedError("audio_lens with raw audio: the frozen codec's encode of a padded batch is not shown to equal the "
+                                          "utterance alone -- pass the latents [b, n, dim] and their frame counts")
+            if self.rvq_cross_entropy_loss_weight > 0 and codes is not None:
+                raise NotImplementedError("audio_lens with the RVQ cross-entropy term (rvq_cross_entropy_loss_weight > 0 and codes=): "
+                                          "ns2_rvq_ce averages over all frames, it takes no per-utterance lengths")
+            if kwargs.get("prompt_lens") is not None:
+                raise NotImplementedError("prompt_lens in training: per-utterance prompt lengths are a sampling feature; audio_lens "
+                                          "shortens the utterances, not their prompts")
+            audio_lens = torch.as_tensor(audio_lens)
+            if audio_lens.dtype.is_floating_point or audio_lens.dtype == torch.bool:
+                raise ValueError(f"audio_lens must be integers (frame counts), got {audio_lens.dtype}")
+            if audio_lens.shape != (audio.shape[0],):
+                raise ValueError(f"audio_lens must hold one frame count per utterance: [{audio.shape[0]}], got {list(audio_lens.shape)}")
         p_enc = None
         aux = None
         if return_aux_losses and (not self.conditional or cond is not None):
@@ -560,9 +582,18 @@ class NaturalSpeech2(nn.Module):
         gamma = self.gamma_schedule(times)[:, None, None]
         alpha, sigma = torch.sqrt(gamma) * self.scale, torch.sqrt(1 - gamma)         # NS2:1152-1153
         noised = alpha * audio + sigma * noise
-        pred = self.model(noised, times, prompt=p_enc, cond=cond)                     # NS2:1635
         target = {"eps": noise, "x0": audio, "v": alpha * noise - sigma * audio}[self.objective]
-        loss = F.mse_loss(pred, target, reduction="none").flatten(1).mean(dim=1)      # [b]
+        if audio_lens is None:
+            pred = self.model(noised, times, prompt=p_enc, cond=cond)                 # NS2:1635
+            loss = F.mse_loss(pred, target, reduction="none").flatten(1).mean(dim=1)  # [b]
+        else:
+            lens = audio_lens.to(device=device, dtype=torch.int32)                    # (an int32 device tensor stays the caller's buffer)
+            pred = self.model(noised, times, prompt=p_enc, cond=cond, lens=lens)
+            ln = lens.clamp(1, n)                                                     # as the kernels clamp
+            keep = (torch.arange(n, device=device)[None] < ln[:, None])[..., None]
+            # a select, not a product (NaN may lie beyond a length), on the difference: the padding's cotangent is an exact 0
+            err = torch.where(keep, pred - target, torch.zeros((), dtype=pred.dtype, device=device))
+            loss = (err * err).flatten(1).sum(dim=1) / (ln * d).to(err.dtype)         # [b]: the mean over the utterance's own frames x dim
         snr = (alpha * alpha) / (sigma * sigma)                                       # [b, 1, 1]
         clipped = snr.clamp(max=self.min_snr_gamma) if self.min_snr_loss_weight else snr
         weight = {"eps": clipped / snr, "x0": clipped, "v": clipped / (snr + 1)}[self.objective]

@@ -451,7 +451,10 @@ class HipDenoiserMixin:
         """`cond_row` (not in the reference): a row of `time_table()` standing in for `times` (inference only).
         `lens` (not in the reference): frames per utterance of a ragged batch, integer [b], each in [1, n] -- out[i, :lens[i]] is
         what utterance i gives alone at its own length, whatever x (and cond) hold from lens[i] on; rows from lens[i] on are
-        finite and meaningless.  The self-attention kernels read the lengths on the device (sampling only).
+        finite and meaningless.  The self-attention kernels read the lengths on the device.  Under autograd a model with
+        `ragged_training = True` takes them too (include/ns2hip_ragged_train.h): utterance i then contributes to the output and to every
+        gradient what it contributes alone at lens[i] frames, and the returned rows from lens[i] on are exactly 0; without the switch the
+        training pass raises on `lens`.
         `prompt_lens` (not in the reference): prompt rows per utterance of a padded prompt batch, integer [b], each in [1, n_p] -- the
         output of utterance i is what it gives with its prompt cut to prompt_lens[i] rows, whatever the prompt holds from there on
         (NaN included): the mean of to_prompt_cond and the perceiver resampler's keys stop at the length, on the device (sampling only)."""
@@ -464,14 +467,15 @@ class HipDenoiserMixin:
             # training (loss.backward(), NS2:1635/1886) and per-utterance stochastic conditioning dropout (a training /
             # validation feature, NS2:79-85) run the differentiable path: on an MI355X the HIP training kernels (training/model_pass.py),
             # on the CPU the PyTorch composite; sampling never gets here
-            if lens is not None:
+            if lens is not None and not getattr(self, "ragged_training", False):
                 raise NotImplementedError("lens: per-utterance lengths are a sampling feature (torch.no_grad()); the training pass and the "
-                                          "backward kernels take equal-length batches")
+                                          "backward kernels take equal-length batches (a model with ragged_training=True trains on them)")
             if prompt_lens is not None:
                 raise NotImplementedError("prompt_lens: per-utterance prompt lengths are a sampling feature (torch.no_grad()); the training "
                                           "pass and the backward kernels take equal-length batches")
             self._native.autograd_seen = True
-            return self._forward_autograd(x, times, prompt=prompt, prompt_mask=prompt_mask, cond=cond, cond_drop_prob=cond_drop_prob)
+            ragged = {} if lens is None else dict(lens=lens)                # (ragged_training: the host class's _forward_autograd takes lens=)
+            return self._forward_autograd(x, times, prompt=prompt, prompt_mask=prompt_mask, cond=cond, cond_drop_prob=cond_drop_prob, **ragged)
         ragged = {} if lens is None else dict(lens=lens)
         if prompt_lens is not None:
             ragged["prompt_lens"] = prompt_lens
@@ -600,7 +604,8 @@ _PROMPT_MASK_MSG = ("prompt_mask: the reference itself raises on it (the Perceiv
                     "32 + n_p keys, NS2:962-968 / 1060-1061 / ATT:92-94) and no reference caller passes one")
 
 
-def _train_forward(m, x, times, prompt, cond, cond_drop_prob, prompt_mask=None):
+def _train_forward(m, x, times, prompt, cond, cond_drop_prob, prompt_mask=None, lens=None):
+    """lens: frames per utterance of a ragged batch (Model.forward's, `ragged_training`), or None"""
     import os
     from . import training
     if prompt_mask is not None:
@@ -609,10 +614,13 @@ def _train_forward(m, x, times, prompt, cond, cond_drop_prob, prompt_mask=None):
     if which == "hip" and training.available(next(m.parameters()).device):
         why = training.unsupported_reason(m)
         if why is None:
-            return training.model_forward_train(m, x, times, prompt=prompt, cond=cond, cond_drop_prob=cond_drop_prob)
+            ragged = {} if lens is None else dict(lens=lens)
+            return training.model_forward_train(m, x, times, prompt=prompt, cond=cond, cond_drop_prob=cond_drop_prob, **ragged)
         import warnings
         warnings.warn(f"HIP training path not usable for this Model ({why}): running the PyTorch composite")
-    from .autograd_path import model_forward_autograd
+    from .autograd_path import model_forward_autograd, model_forward_autograd_ragged
+    if lens is not None:
+        return model_forward_autograd_ragged(m, x, times, lens, prompt=prompt, cond=cond, cond_drop_prob=cond_drop_prob)
     return model_forward_autograd(m, x, times, prompt=prompt, cond=cond, cond_drop_prob=cond_drop_prob)
 
 
@@ -636,6 +644,7 @@ class Model(HipDenoiserMixin, nn.Module):
         cond_drop_prob=0.,
         condition_on_prompt=False,
         precision="exact",
+        ragged_training=False,
     ):
         super().__init__()
         self.dim = dim
@@ -707,6 +716,7 @@ class Model(HipDenoiserMixin, nn.Module):
 
         self.train_backend = "hip"                    # "composite": the PyTorch composite also on the GPU (A/B, tests)
         self.train_precision = "exact"                # "mixed": half product + fp8 correction terms under a loss scale (training/passes.py `_Scale`)
+        self.ragged_training = ragged_training        # True: forward(lens=) under autograd trains on a ragged batch (else it raises)
         self._hip_init(dict(dim=dim, depth=depth, dim_head=dim_head, heads=heads, ff_mult=ff_mult, wavenet_layers=wavenet_layers,
                             wavenet_stacks=wavenet_stacks, dim_cond_mult=dim_cond_mult, condition_on_prompt=condition_on_prompt,
                             dim_prompt=dim_prompt, num_latents_m=num_latents_m, resampler_depth=resampler_depth), precision)
@@ -716,9 +726,9 @@ class Model(HipDenoiserMixin, nn.Module):
     def device(self):
         return next(self.parameters()).device
 
-    def _forward_autograd(self, x, times, prompt=None, prompt_mask=None, cond=None, cond_drop_prob=None):
+    def _forward_autograd(self, x, times, prompt=None, prompt_mask=None, cond=None, cond_drop_prob=None, lens=None):
         """forward under autograd (loss.backward(), NS2:1635 / 1886).  Parameters on an MI355X: the HIP training path
         (training/model_pass.py: forward and backward kernels of libns2hip behind torch.autograd.Functions).  `train_backend = "composite"`
         (or NS2_TRAIN_BACKEND=composite), and parameters on the CPU (BASELINE config 1 as the reference runs it): the PyTorch
         composite of autograd_path.py."""
-        return _train_forward(self, x, times, prompt, cond, cond_drop_prob, prompt_mask=prompt_mask)
+        return _train_forward(self, x, times, prompt, cond, cond_drop_prob, prompt_mask=prompt_mask, lens=lens)

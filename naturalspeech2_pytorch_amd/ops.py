@@ -243,11 +243,12 @@ def wavenet_block(w: PackedWeight, a: Planes, seq_len: int, dilation: int, conv_
 
 
 def _attention_fwd(q: Planes, q_col0, k: Planes, k_col0, vt_hi, vt_lo, vt_ld, B, H, Nq, Nk, scale, precision, head_dim=64, o_precision=0,
-                   key_mask=None, want_lse=False, drop=None, key_lens=None):
+                   key_mask=None, want_lse=False, drop=None, key_lens=None, train_lens=None):
     """The one place that fills a ns2_attn_args (include/ns2hip.h) and calls ns2_attention_fwd -> (o, lse or None).  vt_hi / vt_lo:
     device addresses of the transposed value planes; o_precision: the format of o when it is not the operands' (0 = `precision`);
     key_mask: uint8 [B, Nk] on the device; drop = (p, seed tensor on the device, call index) or None; key_lens: int32 [B] on the
-    device, the call then goes through ns2_attention_fwd_lens (include/ns2hip_ragged.h)."""
+    device, the call then goes through ns2_attention_fwd_lens (include/ns2hip_ragged.h); train_lens: int32 [B] on the device, the
+    utterances' lengths of a ragged TRAINING batch (with want_lse): ns2_attention_train_fwd_lens (include/ns2hip_ragged_train.h)."""
     o = _out_planes(B * Nq, H * head_dim, q.device, o_precision or precision)
     lse = torch.empty(B, H, Nq, dtype=torch.float32, device=q.device) if want_lse else None
     p, seed, call = drop if drop is not None else (0.0, None, 0)
@@ -255,7 +256,9 @@ def _attention_fwd(q: Planes, q_col0, k: Planes, k_col0, vt_hi, vt_lo, vt_ld, B,
                       vt_hi=vt_hi, vt_lo=vt_lo, vt_ld=vt_ld, o_hi=o.hi, o_lo=o.lo, ldo=o.ld, B=B, H=H, Nq=Nq, Nk=Nk, scale=scale,
                       head_dim=head_dim, precision=precision, o_precision=o_precision, key_mask=_p(key_mask), lse=_p(lse),
                       dropout_p=p, dropout_seed=_p(seed), dropout_call=call)
-    if key_lens is not None:
+    if train_lens is not None:
+        check(_lib.load().ns2_attention_train_fwd_lens(ctypes.byref(a), train_lens.data_ptr(), _stream()), "ns2_attention_train_fwd_lens")
+    elif key_lens is not None:
         check(_lib.load().ns2_attention_fwd_lens(ctypes.byref(a), key_lens.data_ptr(), _stream()), "ns2_attention_fwd_lens")
     else:
         check(_lib.load().ns2_attention_fwd(a, _stream()), "ns2_attention_fwd")

@@ -35,6 +35,14 @@ NS2:344-527) adds `GroupNormSiluFn`, `RowDotReluFn` and the `resid` operand of `
 Functions of their own in aligner.py (`ForwardSumLoss` / `BinLoss` with `backend="hip"`).  The RVQ cross-entropy term of the loss
 (`codec.rq`, `ResidualVQCrossEntropy(backend="hip")`; NS2:1668-1684) is `RvqCrossEntropyFn`: one launch, fp32 under either arithmetic.
 
+Ragged batches (`Model(ragged_training=True)`, `model_forward_train(..., lens=)`; include/ns2hip_ragged_train.h): with
+per-utterance frame counts -- int32 [B] on the device, read by kernels alone -- utterance i contributes to the output and to every gradient
+what it contributes alone at lens[i] frames.  Rows of x and of the projected cond from a length on are selected to 0 at the entry, every
+self-attention `AttnFn` gets `lens` (`HipBackend.attention(..., lens=)` / `attention_bwd(..., lens=)`: the length-aware instantiations of
+the training forward and of the backward kernel, which write exact zeros from the length on), and the returned rows from a length on are
+selected to 0, which zeroes the cotangent there.  Every gradient row of the padding is then an exact 0, so the weight-gradient GEMMs,
+the bias sums and the FiLM partial sums need no lengths.
+
 `Backend` is the seam the CPU tests use: `tests/emu_backend.py` restates every backend call with plain torch ops on CPU, so the
 chain rule, tap flips, shifts and layouts of THIS package are checked against torch autograd without a GPU; the kernels behind
 `HipBackend` are checked one by one and end to end on the MI355X (`tests/test_backward_gpu.py`).

@@ -1,4 +1,6 @@
 """The ctypes backend: every method of `HipBackend` = launches of libns2hip on the current stream (C ABI: include/ns2hip.h "training")"""
+import ctypes
+
 import torch
 
 from .. import _lib, ops
@@ -78,10 +80,12 @@ class HipBackend:
         check(self.lib.ns2_geglu_fwd(pre.data_ptr(), pre.stride(0), M, f, out.hi, out.lo, out.ld, self.prec, _stream()), "ns2_geglu_fwd")
         return out
 
-    def attention(self, q, q_col0, k, k_col0, vt, B, H, Nq, Nk):
-        """bf16 x3 products on bf16 operands; the output o (the out-projection's operand) in the GEMM format"""
+    def attention(self, q, q_col0, k, k_col0, vt, B, H, Nq, Nk, lens=None):
+        """bf16 x3 products on bf16 operands; the output o (the out-projection's operand) in the GEMM format.  lens: int32 [B] on the
+        device, the utterances' lengths of a ragged batch (self-attention; include/ns2hip_ragged_train.h): rows of o from a length on are
+        zero bits, their lse +inf"""
         return ops._attention_fwd(q, q_col0, k, k_col0, vt.ptr(), vt.ptr() + 64, vt.ld, B, H, Nq, Nk, 0.125, 3, o_precision=self.prec,
-                                  want_lse=True)
+                                  want_lse=True, train_lens=lens)
 
     def attention_masked(self, q, q_col0, k, k_col0, vt, B, H, Nq, Nk, kmask=None, drop=None):
         """`attention` with a key-padding mask (uint8 [B, Nk], 1 = attend) and / or dropout on P (`drop` = (p, seed tensor on the device, call
@@ -365,11 +369,12 @@ class HipBackend:
         self.attention_bwd(*args, **kw, kmask=kmask, drop=drop)
 
     def attention_bwd(self, q, q_col0, k, k_col0, v, v_col0, do_row, lse, delta, B, H, Nq, Nk, dq=None, dkv=None, planes=None, kmask=None,
-                      drop=None):
+                      drop=None, lens=None):
         """dq: (fp32 tensor [B*Nq, ld], col0) or None; dkv: (tensor [B*Nk, ld], k col0, v col0) or None;
         planes: (operand planes [B*N, ld], dq col0, dk col0, dv col0) -- self attention: the three gradients leave the kernels as the
         operand of the q | k | v projection's dgrad / wgrad GEMMs instead of fp32 + a conversion pass;
-        kmask / drop: what the forward (`attention_masked`) got, None = neither"""
+        kmask / drop: what the forward (`attention_masked`) got, None = neither; lens: what the forward (`attention`) got -- gradient rows
+        from a length on are written as zeros"""
         a = _lib.AttnBwdArgs()
         a.q_hi, a.q_lo, a.ldq, a.q_col0 = q.hi, q.lo, q.ld, q_col0
         a.k_hi, a.k_lo, a.ldk, a.k_col0 = k.hi, k.lo, k.ld, k_col0
@@ -389,4 +394,7 @@ class HipBackend:
         a.key_mask = _p(kmask)
         if drop is not None:
             a.dropout_p, a.dropout_seed, a.dropout_call = drop[0], _p(drop[1]), drop[2]
-        check(self.lib.ns2_attention_bwd(a, _stream()), "ns2_attention_bwd")
+        if lens is not None:
+            check(self.lib.ns2_attention_bwd_lens(ctypes.byref(a), lens.data_ptr(), _stream()), "ns2_attention_bwd_lens")
+        else:
+            check(self.lib.ns2_attention_bwd(a, _stream()), "ns2_attention_bwd")

@@ -179,11 +179,15 @@ class AttnFn(torch.autograd.Function):
     1 = attend (ATT:92-94); `drop` = (p, seed tensor, call index) -- dropout on the softmax output (ATT:100-101; csrc/dropout_keep.h).
     The DurationPitchPredictor's attention (NS2:464, 1060-1061) reads an `h` that IS the norm's output (it is also part of the context, so
     the caller forms it) and adds the PRE-norm rows: `resid` [M, d] replaces `h` as the residual (with `film = gamma = None`); `h` then gets
-    the q path's gradient only and `resid` the incoming one.  Absent by default, like the others."""
+    the q path's gradient only and `resid` the incoming one.  Absent by default, like the others.
+    `lens` -- int32 [B] on the device, the utterances' lengths of a ragged batch (self-attention only, without kmask / drop;
+    include/ns2hip_ragged_train.h): keys stop at the length, and the rows of o and of dq | dk | dv from the length on are exact zeros.
+    The kernels alone read it.  Absent by default: same kernels, same bits."""
 
     @staticmethod
-    def forward(ctx, h, film, ctxt, wq, wkv, wout, seq_len, heads, ctx_len, gamma=None, kmask=None, drop=None, resid=None):
+    def forward(ctx, h, film, ctxt, wq, wkv, wout, seq_len, heads, ctx_len, gamma=None, kmask=None, drop=None, resid=None, lens=None):
         assert resid is None or (film is None and gamma is None)
+        assert lens is None or (ctxt is None and kmask is None and drop is None), "lens: the plain self-attention only"
         bk = _begin(ctx)
         M, d = h.shape
         B, a = M // seq_len, heads * 64
@@ -199,13 +203,15 @@ class AttnFn(torch.autograd.Function):
             kv = bk.gemm_split(_fwd_pack(bk, wkv), cp, attn=True)
             k, v, qc, kc, vc, Nk = kv, kv, 0, 0, a, ctx_len
         vt = bk.transpose(v, vc, a, Nk, per_batch=True)
-        if kmask is None and drop is None:
+        if lens is not None:
+            o, lse = bk.attention(q, qc, k, kc, vt, B, heads, seq_len, Nk, lens=lens)
+        elif kmask is None and drop is None:
             o, lse = bk.attention(q, qc, k, kc, vt, B, heads, seq_len, Nk)
         else:
             o, lse = bk.attention_masked(q, qc, k, kc, vt, B, heads, seq_len, Nk, kmask=kmask, drop=drop)
         y = bk.gemm_f32(_fwd_pack(bk, wout), o, resid=h if resid is None else resid)
         ctx.save_for_backward(h, film, wq, wkv, wout, lse, gamma)
-        ctx.pl, ctx.cfg, ctx.md = (xn, q, k, v, o, cp), (seq_len, heads, Nk, qc, kc, vc, ctxt is not None), (kmask, drop)
+        ctx.pl, ctx.cfg, ctx.md, ctx.lens = (xn, q, k, v, o, cp), (seq_len, heads, Nk, qc, kc, vc, ctxt is not None), (kmask, drop), lens
         ctx.own_resid = resid is None
         return y[:, :d]
 
@@ -220,7 +226,10 @@ class AttnFn(torch.autograd.Function):
         B, a = M // seq_len, heads * 64
         dy = _rowmajor(dy)
         ng = ctx.needs_input_grad                                           # (h, film, ctxt, wq, wkv, wout, ...)
-        if kmask is None and drop is None:
+        if ctx.lens is not None:
+            def attention_bwd(*args, **kw):
+                bk.attention_bwd(*args, lens=ctx.lens, **kw)
+        elif kmask is None and drop is None:
             attention_bwd = bk.attention_bwd
         else:
             def attention_bwd(*args, **kw):
@@ -262,7 +271,7 @@ class AttnFn(torch.autograd.Function):
         else:
             dh, dfilm, dgamma, dresid = dxn[:, :d], None, None, dy
         dfilm, dwq, dwkv, dwout, dgamma = _un(ctx, dfilm, dwq, dwkv, dwout, dgamma)
-        return dh, dfilm, dctx, dwq, dwkv, dwout, None, None, None, dgamma, None, None, dresid
+        return dh, dfilm, dctx, dwq, dwkv, dwout, None, None, None, dgamma, None, None, dresid, None
 
 
 class FeedForwardFn(torch.autograd.Function):

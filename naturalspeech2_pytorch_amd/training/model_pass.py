@@ -28,21 +28,42 @@ def _resampler(pr, prompt, heads):
     return RmsNormFn.apply(_c(lat), pr.norm.gamma).reshape(b, Lm, d)
 
 
-def model_forward_train(m, x, times, prompt=None, cond=None, cond_drop_prob=None):
+def _lens_and_mask(lens, b, n, device):
+    """`lens` of a ragged batch -> (int32 [b] on the device, what the kernels read; bool [b, n, 1], True on the rows [0, clamp(lens[i], 1, n))).
+    An int32 device tensor comes back as it is: no copy and no host read, so a captured pass follows values rewritten between replays."""
+    ln = torch.as_tensor(lens).to(device=device, dtype=torch.int32).contiguous()
+    assert ln.shape == (b,), f"lens must hold one frame count per utterance: [{b}]"
+    return ln, (torch.arange(n, device=device)[None] < ln.clamp(1, n)[:, None])[..., None]
+
+
+def _keep(t_bnd, mask):
+    """rows outside the mask become exactly 0 -- a select, not a product: what lies there may be NaN (its cotangent there becomes 0 too)"""
+    return torch.where(mask, t_bnd, torch.zeros((), dtype=t_bnd.dtype, device=t_bnd.device))
+
+
+def model_forward_train(m, x, times, prompt=None, cond=None, cond_drop_prob=None, lens=None):
     """`Model.forward` (NS2:929-1000) as a differentiable graph whose token-sized arithmetic is HIP (package docstring).
     `m` owns the reference's parameters (this package's `Model` or `compat.HipBackedModel`).  `m.train_precision`: "exact"
-    (default: bf16 x3) or "mixed" (IEEE-half product + fp8 correction terms on FMT_H8 operands under a loss scale, `passes._Scale`)."""
+    (default: bf16 x3) or "mixed" (IEEE-half product + fp8 correction terms on FMT_H8 operands under a loss scale, `passes._Scale`).
+    `lens` (not in the reference): frames per utterance of a ragged batch, integer [b] (include/ns2hip_ragged_train.h).  Rows
+    of x and of the projected cond from a length on are selected to 0 at the entry, every self-attention stops at the length in both
+    directions, and the returned rows from a length on are selected to 0 -- which also zeroes the cotangent there.  No host read."""
     tp = getattr(m, "train_precision", "exact")
     assert tp in TRAIN_PRECISIONS, f"train_precision must be one of {sorted(TRAIN_PRECISIONS)}"
     with training_pass(TRAIN_PRECISIONS[tp], x) as p:
-        out = _forward_train(m, x, times, prompt, cond, cond_drop_prob)
+        if lens is None:
+            out = _forward_train(m, x, times, prompt, cond, cond_drop_prob)
+        else:
+            ln, keep = _lens_and_mask(lens, x.shape[0], x.shape[1], x.device)
+            out = _keep(_forward_train(m, x, times, prompt, cond, cond_drop_prob, ln, keep), keep)
         if p.scale is not None:
             m._last_loss_scale = p.scale             # (inspection / tests: the scale the last backward chose)
             out = _ScaleIn.apply(out, p.scale)
         return out
 
 
-def _forward_train(m, x, times, prompt, cond, cond_drop_prob):
+def _forward_train(m, x, times, prompt, cond, cond_drop_prob, lens=None, keep=None):
+    """lens / keep: `_lens_and_mask` of a ragged batch, or neither"""
     b, n, d = x.shape
     M = b * n
     p = m.cond_drop_prob if cond_drop_prob is None else cond_drop_prob
@@ -53,7 +74,7 @@ def _forward_train(m, x, times, prompt, cond, cond_drop_prob):
     fr = tt * w[None] * 2 * math.pi
     t = F.silu(_lin(getattr(m.to_time_cond, "1"), torch.cat((tt, fr.sin(), fr.cos()), dim=-1)))
     c = None
-    h = _enter(x.float().reshape(M, d))              # (mixed arithmetic: the token-sized gradients below here are loss-scaled)
+    h = _enter((x.float() if keep is None else _keep(x.float(), keep)).reshape(M, d))   # (mixed arithmetic: the token-sized gradients below here are loss-scaled)
     if m.condition_on_prompt:
         assert prompt is not None and cond is not None
 
@@ -73,6 +94,9 @@ def _forward_train(m, x, times, prompt, cond, cond_drop_prob):
         c = torch.where(dm[:, None, None], _enter(m.null_prompt_tokens), _resampler(m.perceiver_resampler, _enter(prompt.float()), heads))   # [b, Lm, d]
         # cond_to_model_dim: 1x1 conv over channel-first cond (NS2:978) = a Linear over the frames
         n_c = cond.shape[-1]
+        if keep is not None:
+            # (the frames of cond itself first: a NaN there would reach the projection's weight gradient as 0 * NaN)
+            cond = _keep(cond.float().transpose(1, 2), torch.arange(n_c, device=x.device)[None, :, None] < lens.clamp(1, n)[:, None, None]).transpose(1, 2)
         cm = GemmFn.apply(_enter(_c(cond.float().transpose(1, 2)).reshape(b * n_c, -1)), m.cond_to_model_dim.weight, m.cond_to_model_dim.bias, None,
                           n_c, 1)
         cm = cm.reshape(b, n_c, d)
@@ -81,6 +105,8 @@ def _forward_train(m, x, times, prompt, cond, cond_drop_prob):
             cm = cm[:, :n]
         elif n_c < n:
             cm = F.pad(cm, (0, 0, 0, n - n_c))
+        if keep is not None:
+            cm = _keep(cm, keep)
         h = h + _c(cm).reshape(M, d)
         c2 = _c(c.float()).reshape(b * c.shape[1], d)
     t = _c(t)
@@ -113,7 +139,11 @@ def _forward_train(m, x, times, prompt, cond, cond_drop_prob):
     h = GemmFn.apply(_c(skip), wn.final_conv.weight, wn.final_conv.bias, None, n, 1)
     for layer in m.transformer.layers:
         a1 = getattr(layer, "1")
-        h = AttnFn.apply(_c(h), film_of(getattr(layer, "0").to_gamma_beta), None, a1.to_q.weight, a1.to_kv.weight, a1.to_out.weight, n, heads, 0)
+        if lens is None:
+            h = AttnFn.apply(_c(h), film_of(getattr(layer, "0").to_gamma_beta), None, a1.to_q.weight, a1.to_kv.weight, a1.to_out.weight, n, heads, 0)
+        else:
+            h = AttnFn.apply(_c(h), film_of(getattr(layer, "0").to_gamma_beta), None, a1.to_q.weight, a1.to_kv.weight, a1.to_out.weight, n, heads, 0,
+                             None, None, None, None, lens)
         if m.condition_on_prompt:
             a3 = getattr(layer, "3")
             h = AttnFn.apply(_c(h), film_of(getattr(layer, "2").to_gamma_beta), c2, a3.to_q.weight, a3.to_kv.weight, a3.to_out.weight, n,

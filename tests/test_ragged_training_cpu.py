@@ -1,0 +1,332 @@
+"""Ragged TRAINING batches on the CPU (include/ns2hip_ragged_train.h): the sixth header of the C ABI and what its two entries refuse,
+the `ragged_training` switch of Model, the composite restatement of the rule -- utterance i of a ragged batch contributes to the output
+and to every gradient what it contributes alone at lens[i] frames --, the host logic of the HIP pass (functions.py / model_pass.py on
+tests/emu_backend_ragged.py) against the composite's autograd, and the masked loss of NaturalSpeech2.forward(audio_lens=)."""
+import ctypes
+import subprocess
+
+import pytest
+import torch
+
+from naturalspeech2_pytorch_amd import _lib, Model, NaturalSpeech2, training
+from naturalspeech2_pytorch_amd.autograd_path import model_forward_autograd, model_forward_autograd_ragged
+from tests.emu_backend_ragged import EmuBackendRagged
+from tests.golden.gen import make_input, make_weights
+
+B, N, LENS = 4, 64, [64, 47, 16, 1]
+CONFIGS = {"uncond": dict(dim=64, depth=2),
+           "cond": dict(dim=64, depth=2, dim_prompt=48, condition_on_prompt=True, num_latents_m=16)}
+# Batch against solo: output rows and every parameter gradient (the sum of the four solo gradients), worst tensor, relative Frobenius
+# error.  The yardstick is the same comparison with no lengths involved -- the equal-length batch [4, 64, 64] of the composite without
+# `lens` against its four utterances alone, a pure reduction-order effect of the CPU's GEMM / SDPA / conv routes -- measured on the
+# code before this feature (profiles/ragged_training.json "cpu_batch_vs_solo": yardstick and, beside it, what the ragged batch measures).
+# The bound is twice the yardstick.
+YARDSTICK = {"uncond": 1.40e-6, "cond": 1.02e-6}
+BATCH_VS_SOLO = {k: 2 * v for k, v in YARDSTICK.items()}
+
+
+def rel(a, b):
+    return ((a.double() - b.double()).norm() / b.double().norm().clamp(min=1e-300)).item()
+
+
+def _model(name, **kw):
+    m = Model(**CONFIGS[name], **kw).train()
+    m.load_state_dict(make_weights({k: tuple(v.shape) for k, v in m.state_dict().items()}, seed=1))
+    return m
+
+
+def _inputs(name):
+    x = make_input("x", (B, N, 64), seed=2)
+    t = make_input("times", (B,), seed=2, uniform=True)
+    cot = make_input("gw", (B, N, 64), seed=3)
+    prompt = cond = None
+    if CONFIGS[name].get("condition_on_prompt"):
+        prompt, cond = make_input("prompt", (B, 7, 48), seed=2), make_input("cond", (B, 48, N), seed=2)
+    return x, t, prompt, cond, cot
+
+
+def _run(m, fwd, x, t, prompt, cond, cot):
+    """-> (output, {parameter name: gradient or None}) of sum(fwd(...) * cot)"""
+    for p in m.parameters():
+        p.grad = None
+    kw = {} if prompt is None else dict(prompt=prompt, cond=cond, cond_drop_prob=0.)
+    y = fwd(x, t, **kw)
+    (y * cot).sum().backward()
+    return y.detach(), {k: (None if p.grad is None else p.grad.clone()) for k, p in m.named_parameters()}
+
+
+def _solo_sum(m, fwd, x, t, prompt, cond, cot, lens):
+    """every utterance alone at its own length through `fwd` -> (outputs, the sum of their gradients)"""
+    outs, total = [], None
+    for i, n in enumerate(lens):
+        y, g = _run(m, fwd, x[i:i + 1, :n], t[i:i + 1], None if prompt is None else prompt[i:i + 1], None if cond is None else cond[i:i + 1, :, :n],
+                    cot[i:i + 1, :n])
+        outs.append(y)
+        total = g if total is None else {k: (v if g[k] is None else (g[k] if v is None else v + g[k])) for k, v in total.items()}
+    return outs, total
+
+
+def _worst(y, g, outs, total, lens):
+    worst = ("", 0.0)
+    for i, n in enumerate(lens):
+        worst = max(worst, (f"out[{i}]", rel(y[i:i + 1, :n], outs[i])), key=lambda z: z[1])
+    for k, ref in total.items():
+        if ref is None or ref.norm() == 0:                 # (null_* parameters at cond_drop_prob = 0: no gradient either way)
+            assert g[k] is None or g[k].norm() == 0, k
+            continue
+        worst = max(worst, (k, rel(g[k], ref)), key=lambda z: z[1])
+    return worst
+
+
+@pytest.fixture(scope="module", params=sorted(CONFIGS))
+def case(request):
+    name = request.param
+    m = _model(name, ragged_training=True)
+    x, t, prompt, cond, cot = _inputs(name)
+    fwd = lambda xs, ts, **kw: model_forward_autograd(m, xs, ts, **kw)      # noqa: E731  the existing pass: the utterances alone
+    outs, total = _solo_sum(m, fwd, x, t, prompt, cond, cot, LENS)          # computed once, shared, left unchanged
+    return dict(name=name, m=m, x=x, t=t, prompt=prompt, cond=cond, cot=cot, outs=outs, total=total)
+
+
+# ---- the C ABI
+def test_ragged_train_header_parses_and_the_library_exports_it():
+    P, I = ctypes.c_void_p, ctypes.c_int
+    assert _lib.ragged_train_header_symbols() == ["ns2_attention_bwd_lens", "ns2_attention_train_fwd_lens"]
+    assert _lib.RAGGED_TRAIN_SIGNATURES["ns2_attention_train_fwd_lens"] == (I, [P, P, P])
+    assert _lib.RAGGED_TRAIN_SIGNATURES["ns2_attention_bwd_lens"] == (I, [P, P, P])
+    others = [_lib.SIGNATURES, _lib.OPTIM_SIGNATURES, _lib.PITCH_SIGNATURES, _lib.RAGGED_SIGNATURES, _lib.FRONT_SIGNATURES]
+    assert len(_lib.SIGNATURES) == 119 and not any(set(_lib.RAGGED_TRAIN_SIGNATURES) & set(s) for s in others)
+    _lib.load()
+    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True).stdout
+    exported = {l.split()[-1] for l in out.splitlines() if " T ns2_" in l}
+    assert set(_lib.ragged_train_header_symbols()) <= exported
+
+
+def test_the_two_entries_refuse_before_any_device_call():
+    """no GPU here: an entry that reached a device call would come back with a HIP error, not with the argument error"""
+    lib = _lib.load()
+    fake = 1 << 20                                          # addresses that are compared against null and never read
+    lens = (ctypes.c_int * 2)(3, 1)
+
+    def fwd_block(**kw):
+        f = dict(q_hi=fake, q_lo=fake + 64, k_hi=fake, k_lo=fake + 64, vt_hi=fake, vt_lo=fake + 64, o_hi=fake, o_lo=fake + 64, ldq=128, ldk=128,
+                 vt_ld=64, ldo=64, B=2, H=1, Nq=64, Nk=64, scale=0.125, head_dim=64, precision=3, lse=fake)
+        f.update(kw)
+        return _lib.AttnArgs(**f)
+
+    def bwd_block(**kw):
+        f = dict(q_hi=fake, q_lo=fake + 64, k_hi=fake, k_lo=fake + 64, v_hi=fake, v_lo=fake + 64, do_hi=fake, do_lo=fake + 64, ldq=64, ldk=64, ldv=64,
+                 lddo=64, lse=fake, delta=fake, dq=fake, lddq=64, dk=fake, lddk=64, dv=fake, lddv=64, B=2, H=1, Nq=64, Nk=64, scale=0.125)
+        f.update(kw)
+        return _lib.AttnBwdArgs(**f)
+
+    for entry, block in ((lib.ns2_attention_train_fwd_lens, fwd_block), (lib.ns2_attention_bwd_lens, bwd_block)):
+        name = entry.__name__
+
+        def refused(blk, ln, word):
+            rc = entry(None if blk is None else ctypes.byref(blk), ln, None)
+            msg = lib.ns2_last_error().decode()
+            assert rc == _lib.NS2_ERR_ARG and msg.startswith(name + ":") and word in msg, (name, rc, msg)
+
+        refused(None, lens, "null argument block")
+        refused(block(), None, "lens is null")
+        refused(block(lse=None), lens, "lse is missing")
+        refused(block(Nk=32), lens, "Nq != Nk")
+        refused(block(key_mask=fake), lens, "key_mask")
+        refused(block(dropout_p=0.1, dropout_seed=fake), lens, "dropout")
+    # the inference entry keeps refusing lse
+    rc = lib.ns2_attention_fwd_lens(ctypes.byref(fwd_block()), lens, None)
+    assert rc == _lib.NS2_ERR_ARG and lib.ns2_last_error().decode().startswith("ns2_attention_fwd_lens: lse")
+
+
+# ---- the switch
+def test_switch_off_the_training_pass_raises_on_lens():
+    m = Model(dim=64, depth=1).train()
+    assert m.ragged_training is False
+    with pytest.raises(NotImplementedError, match="lens"):
+        m(torch.zeros(2, 8, 64), torch.zeros(2), lens=torch.tensor([8, 3]))
+    m.ragged_training = True                                # a plain attribute, like train_precision
+    assert m(torch.zeros(2, 8, 64), torch.zeros(2), lens=torch.tensor([8, 3])).shape == (2, 8, 64)
+    mc = Model(dim=64, depth=1, dim_prompt=32, condition_on_prompt=True, num_latents_m=8, ragged_training=True).train()
+    with pytest.raises(NotImplementedError, match="prompt_lens"):
+        mc(torch.zeros(2, 8, 64), torch.zeros(2), prompt=torch.zeros(2, 4, 32), cond=torch.zeros(2, 32, 8), lens=[8, 3], prompt_lens=[4, 2])
+
+
+# ---- switch on: the composite
+def test_composite_ragged_batch_equals_the_utterances_alone(case):
+    c = case
+    fwd = lambda xs, ts, **kw: c["m"](xs, ts, lens=torch.tensor(LENS), **kw)      # noqa: E731  Model.forward under autograd, on the CPU
+    y, g = _run(c["m"], fwd, c["x"], c["t"], c["prompt"], c["cond"], c["cot"])
+    for i, n in enumerate(LENS):
+        assert torch.count_nonzero(y[i, n:]) == 0, i                              # rows from a length on: exactly 0
+    who, e = _worst(y, g, c["outs"], c["total"], LENS)
+    print(f"{c['name']}: ragged batch vs the utterances alone, worst tensor {who} {e:.3e} (bound {BATCH_VS_SOLO[c['name']]:.3e})")
+    assert e <= BATCH_VS_SOLO[c["name"]], (who, e)
+    # without the lengths the padding is attended to and takes part in the loss: the test sees it
+    y0, g0 = _run(c["m"], lambda xs, ts, **kw: c["m"](xs, ts, **kw), c["x"], c["t"], c["prompt"], c["cond"], c["cot"])
+    assert rel(y0[1:2, :LENS[1]], c["outs"][1]) > 1e-3      # (hundreds of times the bound)
+
+
+def test_equal_length_yardstick_of_the_existing_pass(case):
+    """the figure the bound above is twice of, re-measured on this host (printed; the existing pass, no lengths anywhere)"""
+    c = case
+    fwd = lambda xs, ts, **kw: model_forward_autograd(c["m"], xs, ts, **kw)      # noqa: E731
+    outs, total = _solo_sum(c["m"], fwd, c["x"], c["t"], c["prompt"], c["cond"], c["cot"], [N] * B)
+    y, g = _run(c["m"], fwd, c["x"], c["t"], c["prompt"], c["cond"], c["cot"])
+    who, e = _worst(y, g, outs, total, [N] * B)
+    print(f"{c['name']}: equal-length batch vs the utterances alone, worst tensor {who} {e:.3e} (recorded {YARDSTICK[c['name']]:.3e})")
+    assert e <= BATCH_VS_SOLO[c["name"]]                     # another host's routes may differ; twice the recorded figure holds them too
+
+
+def test_nan_beyond_the_lengths_changes_nothing(case):
+    c = case
+    fwd = lambda xs, ts, **kw: c["m"](xs, ts, lens=LENS, **kw)      # noqa: E731  (a list this time)
+    y, g = _run(c["m"], fwd, c["x"], c["t"], c["prompt"], c["cond"], c["cot"])
+    x, cond, cot = c["x"].clone(), None if c["cond"] is None else c["cond"].clone(), c["cot"].clone()
+    for i, n in enumerate(LENS):
+        x[i, n:] = float("nan")
+        cot[i, n:] = 0.                                     # (the caller's cotangent there is finite: the exit select drops it)
+        if cond is not None:
+            cond[i, :, n:] = float("nan")
+    yn, gn = _run(c["m"], fwd, x, c["t"], c["prompt"], cond, cot)
+    assert torch.isfinite(yn).all() and torch.equal(yn, y)
+    for k, v in g.items():
+        assert (v is None) == (gn[k] is None) and (v is None or (torch.isfinite(gn[k]).all() and torch.equal(gn[k], v))), k
+    xr = x.clone().requires_grad_(True)                     # the input's gradient: exact zeros from a length on
+    kw = {} if c["prompt"] is None else dict(prompt=c["prompt"], cond=cond, cond_drop_prob=0.)
+    (c["m"](xr, c["t"], lens=LENS, **kw) * cot).sum().backward()
+    assert torch.isfinite(xr.grad).all() and all(torch.count_nonzero(xr.grad[i, n:]) == 0 for i, n in enumerate(LENS))
+
+
+# ---- the host logic of the HIP pass
+@pytest.fixture()
+def emu():
+    bk = EmuBackendRagged()
+    prev = training.set_backend(bk)
+    yield bk
+    training.set_backend(prev)
+
+
+@pytest.mark.parametrize("name", sorted(CONFIGS))
+def test_training_functions_with_lens_match_the_composite(emu, name):
+    """functions.py / model_pass.py with `lens` on the emulated backend against torch autograd through the composite with the same
+    lengths; the tolerances of tests/test_training_cpu.py.  NaN lies beyond the lengths in x and cond."""
+    m = _model(name, ragged_training=True)
+    x, t, prompt, cond, cot = _inputs(name)
+    x, cond = x.clone(), None if cond is None else cond.clone()
+    for i, n in enumerate(LENS):
+        x[i, n:] = float("nan")
+        if cond is not None:
+            cond[i, :, n:] = float("nan")
+    lens = torch.tensor(LENS, dtype=torch.int32)
+    y0, g0 = _run(m, lambda xs, ts, **kw: model_forward_autograd_ragged(m, xs, ts, lens, **kw), x, t, prompt, cond, cot)
+    y1, g1 = _run(m, lambda xs, ts, **kw: training.model_forward_train(m, xs, ts, lens=lens, **kw), x, t, prompt, cond, cot)
+    n_attn = sum(1 for c in emu.calls if isinstance(c, tuple) and c[0] == "attention_lens")
+    n_bwd = sum(1 for c in emu.calls if isinstance(c, tuple) and c[0] == "attention_bwd_lens")
+    assert n_attn == 2 and n_bwd == 2                      # every SELF attention got the lengths; the cross attention and the resampler none
+    assert all(c[1] is lens for c in emu.calls if isinstance(c, tuple))     # ... the caller's own int32 tensor: no copy, no host read
+    assert torch.isfinite(y1).all() and all(torch.count_nonzero(y1[i, n:]) == 0 for i, n in enumerate(LENS))
+    assert rel(y1, y0) < 1e-5
+    worst = ("", 0.0)
+    for k, ref in g0.items():
+        if ref is None or ref.norm() == 0:
+            assert g1[k] is None or g1[k].abs().max() == 0, k
+            continue
+        assert g1[k] is not None and g1[k].shape == ref.shape and torch.isfinite(g1[k]).all(), k
+        e = rel(g1[k], ref)
+        worst = max(worst, (k, e), key=lambda z: z[1])
+        assert e < 2e-4, (k, e)
+    print("worst parameter gradient:", worst)
+    xr = x.clone().requires_grad_(True)
+    kw = {} if prompt is None else dict(prompt=prompt, cond=cond, cond_drop_prob=0.)
+    (training.model_forward_train(m, xr, t, lens=lens, **kw) * cot).sum().backward()
+    xc = x.clone().requires_grad_(True)
+    (model_forward_autograd_ragged(m, xc, t, lens, **kw) * cot).sum().backward()
+    assert rel(xr.grad, xc.grad) < 1e-4 and all(torch.count_nonzero(xr.grad[i, n:]) == 0 for i, n in enumerate(LENS))
+
+
+# ---- the loss
+OUTPUT_BAR = 1e-4                                           # the project's output bar (tests/test_backward_gpu._compare)
+
+
+def _wrapper(**kw):
+    m = _model("uncond", ragged_training=True)
+    return NaturalSpeech2(m, codec=None, target_sample_hz=24000, timesteps=2, **kw)
+
+
+def _loss_inputs():
+    return (make_input("latents", (B, N, 64), seed=4), make_input("times", (B,), seed=4, uniform=True), make_input("noise", (B, N, 64), seed=5))
+
+
+def _loss_and_grads(d, *a, **kw):
+    for p in d.parameters():
+        p.grad = None
+    loss = d(*a, **kw)
+    loss.backward()
+    return loss.detach(), {k: p.grad.clone() for k, p in d.named_parameters() if p.grad is not None}
+
+
+def test_loss_is_the_mean_of_the_solo_losses_when_the_weight_is_one():
+    d = _wrapper(objective="eps", min_snr_loss_weight=False)
+    lat, t, noise = _loss_inputs()
+    loss, g = _loss_and_grads(d, lat, audio_lens=torch.tensor(LENS), times=t, noise=noise)
+    solo, gs = [], None
+    for i, n in enumerate(LENS):
+        l, gi = _loss_and_grads(d, lat[i:i + 1, :n], times=t[i:i + 1], noise=noise[i:i + 1, :n])
+        solo.append(l)
+        gs = gi if gs is None else {k: gs[k] + gi[k] for k in gs}
+    worst = ("loss", rel(loss, torch.stack(solo).mean()))
+    for k in gs:
+        worst = max(worst, (k, rel(g[k], gs[k] / B)), key=lambda z: z[1])
+    print(f"audio_lens loss and gradients vs the mean of the solos: worst {worst[0]} {worst[1]:.3e}")
+    assert worst[1] < OUTPUT_BAR, worst
+    # NaN beyond the lengths in the latents and the noise: the same loss, the same gradients
+    latn, noisen = lat.clone(), noise.clone()
+    for i, n in enumerate(LENS):
+        latn[i, n:] = float("nan")
+        noisen[i, n:] = float("nan")
+    loss_n, g_n = _loss_and_grads(d, latn, audio_lens=LENS, times=t, noise=noisen)
+    assert torch.equal(loss_n, loss) and all(torch.equal(g_n[k], g[k]) for k in g)
+    # without the lengths the padding is in the mean: the test sees it
+    assert rel(_loss_and_grads(d, lat, times=t, noise=noise)[0], torch.stack(solo).mean()) > 1e-3
+
+
+def test_default_objective_with_min_snr_against_an_fp64_restatement():
+    d = _wrapper()                                          # objective "v", min-SNR weight
+    lat, t, noise = _loss_inputs()
+    lens = torch.tensor(LENS)
+    loss = d(lat, audio_lens=lens, times=t, noise=noise)
+    with torch.no_grad():
+        gamma = d.gamma_schedule(t).double()[:, None, None]
+        alpha, sigma = gamma.sqrt() * d.scale, (1 - gamma).sqrt()
+        noised = (alpha * lat.double() + sigma * noise.double()).float()
+        pred = model_forward_autograd_ragged(d.model, noised, t, lens).double()
+        target = alpha * noise.double() - sigma * lat.double()
+        per = torch.stack([((pred[i, :n] - target[i, :n]) ** 2).sum() / (n * 64) for i, n in enumerate(LENS)])
+        snr = (alpha * alpha / (sigma * sigma)).flatten()
+        weight = snr.clamp(max=d.min_snr_gamma) / (snr + 1)
+        ref = (per[None, :] * weight[:, None]).mean()       # NS2:1666 as written upstream: [b] * [b, 1, 1] broadcasts to [b, 1, b]
+    e = rel(loss.detach(), ref)
+    print(f"objective v + min-SNR: audio_lens loss vs the fp64 restatement {e:.3e}")
+    assert e < OUTPUT_BAR
+
+
+def test_what_audio_lens_refuses():
+    d = _wrapper()
+    lat, t, noise = _loss_inputs()
+    with pytest.raises(NotImplementedError, match="raw audio"):
+        d(torch.zeros(B, 2400), audio_lens=LENS)
+    with pytest.raises(NotImplementedError, match="prompt_lens"):
+        d(lat, audio_lens=LENS, prompt_lens=[3] * B)
+    dce = _wrapper(rvq_cross_entropy_loss_weight=0.1)
+    with pytest.raises(NotImplementedError, match="RVQ cross-entropy"):
+        dce(lat, codes=torch.zeros(B, N, 8, dtype=torch.long), audio_lens=LENS)
+    with pytest.raises(ValueError, match="integers"):
+        d(lat, audio_lens=torch.tensor([64., 47., 16., 1.]))
+    with pytest.raises(ValueError, match="one frame count per utterance"):
+        d(lat, audio_lens=[64, 47, 16])
+    with pytest.raises(ValueError, match="one frame count per utterance"):
+        d(lat, audio_lens=torch.tensor([LENS]))
+    off = NaturalSpeech2(_model("uncond"), codec=None, target_sample_hz=24000, timesteps=2)
+    with pytest.raises(NotImplementedError, match="ragged_training"):     # Model's own error comes through
+        off(lat, audio_lens=LENS, times=t, noise=noise)
