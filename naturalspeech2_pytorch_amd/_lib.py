@@ -1,6 +1,7 @@
 """ctypes binding of libns2hip.so, derived from its C ABI: include/ns2hip.h (and include/ns2hip_optim.h, the optimizer step, and
 include/ns2hip_pitch.h, the pitch extractor, include/ns2hip_ragged.h, ragged batches, include/ns2hip_ragged_front.h, ragged prompts
-and text, and include/ns2hip_ragged_train.h, ragged training batches, each into tables of its own) is parsed once, at import.
+and text, include/ns2hip_ragged_train.h, ragged training batches, and include/ns2hip_head_dim_train.h, training at head dims 32 and
+128, each into tables of its own) is parsed once, at import.
 
 The HIP library is the product: importing this module FAILS LOUDLY when the header or the shared object is missing or the
 library does not export the full ABI -- there is no CPU / PyTorch fallback for the hot path.
@@ -31,6 +32,7 @@ PITCH_HEADER_PATH = os.path.join(_HERE, "..", "include", "ns2hip_pitch.h")   # t
 RAGGED_HEADER_PATH = os.path.join(_HERE, "..", "include", "ns2hip_ragged.h")   # per-utterance lengths: likewise
 FRONT_HEADER_PATH = os.path.join(_HERE, "..", "include", "ns2hip_ragged_front.h")   # ... through the front-end: likewise
 RAGGED_TRAIN_HEADER_PATH = os.path.join(_HERE, "..", "include", "ns2hip_ragged_train.h")   # ... in the training pass: likewise
+HEAD_DIM_TRAIN_HEADER_PATH = os.path.join(_HERE, "..", "include", "ns2hip_head_dim_train.h")   # training at head dims 32 / 128: likewise
 
 
 class Ns2Error(RuntimeError):
@@ -139,6 +141,11 @@ if not os.path.exists(RAGGED_TRAIN_HEADER_PATH):
 with open(RAGGED_TRAIN_HEADER_PATH) as _f:                       # (ns2_attn_args / ns2_attn_bwd_args: c_void_p here, as in RAGGED_SIGNATURES)
     _, _, RAGGED_TRAIN_SIGNATURES = parse_header(_f.read())
 
+if not os.path.exists(HEAD_DIM_TRAIN_HEADER_PATH):
+    raise Ns2Error(f"{HEAD_DIM_TRAIN_HEADER_PATH} not found: the binding is derived from the header, it ships with the package's source tree")
+with open(HEAD_DIM_TRAIN_HEADER_PATH) as _f:                     # (the argument blocks: c_void_p here too)
+    _, _, HEAD_DIM_TRAIN_SIGNATURES = parse_header(_f.read())
+
 _lib = None
 
 
@@ -152,7 +159,7 @@ def load():
                        f"(or naturalspeech2_pytorch_amd/csrc/build.sh); there is no fallback path")
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in {**SIGNATURES, **OPTIM_SIGNATURES, **PITCH_SIGNATURES, **RAGGED_SIGNATURES, **FRONT_SIGNATURES,
-                              **RAGGED_TRAIN_SIGNATURES}.items():
+                              **RAGGED_TRAIN_SIGNATURES, **HEAD_DIM_TRAIN_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -197,3 +204,8 @@ def front_header_symbols():
 def ragged_train_header_symbols():
     """Symbols declared in include/ns2hip_ragged_train.h"""
     return sorted(RAGGED_TRAIN_SIGNATURES)
+
+
+def head_dim_train_header_symbols():
+    """Symbols declared in include/ns2hip_head_dim_train.h"""
+    return sorted(HEAD_DIM_TRAIN_SIGNATURES)

@@ -35,7 +35,8 @@ def hip_backed_model_class(reference_model_cls):
     defaults = {k: v.default for k, v in sig.parameters.items() if v.default is not inspect.Parameter.empty}
 
     class HipBackedModel(HipDenoiserMixin, reference_model_cls):
-        def __init__(self, dim, *args, precision="exact", train_backend="reference", train_precision="exact", ragged_training=False, **kwargs):
+        def __init__(self, dim, *args, precision="exact", train_backend="reference", train_precision="exact", ragged_training=False,
+                     head_dim_training=False, **kwargs):
             reference_model_cls.__init__(self, dim, *args, **kwargs)
             bound = sig.bind(self, dim, *args, **kwargs)
             cfg = dict(defaults)
@@ -45,6 +46,7 @@ def hip_backed_model_class(reference_model_cls):
             self.train_backend = train_backend
             self.train_precision = train_precision            # arithmetic of train_backend="hip" (training/passes.py: TRAIN_PRECISIONS)
             self.ragged_training = ragged_training            # True: forward(lens=) under autograd (train_backend="hip"; model.py `Model`)
+            self.head_dim_training = head_dim_training        # True: dim_head 32 / 128 on the HIP training kernels (model.py `Model`)
 
         def _forward_autograd(self, x, times, prompt=None, prompt_mask=None, cond=None, cond_drop_prob=None, lens=None):
             """train_backend="reference" (default): the reference's own forward under torch autograd -- the loss is upstream's bit for

@@ -352,11 +352,23 @@ static hipError_t launch_attn_w(const AttnArgs& a, hipStream_t s) {
   hipLaunchKernelGGL((attn_kernel<NSPLIT, F16, NW, WLSE, D, DROP, QLENS>), grid, dim3(64 * NW), lds, s, a);
   return hipGetLastError();
 }
+// the training forward (precision 3, lse) at head dims 32 / 128: plain, with dropout (and key mask), on a ragged batch -- the three
+// variants of D = 64 below, reached through launch_attention_train_hd alone (include/ns2hip_head_dim_train.h)
+template <int D>
+static hipError_t launch_attn_train_d(const AttnArgs& a, hipStream_t s) {
+  if (a.drop_seed) return launch_attn_w<3, false, 4, true, D, true>(a, s);
+  if (a.klens) return launch_attn_w<3, false, 4, true, D, false, true>(a, s);
+  return launch_attn_w<3, false, 4, true, D>(a, s);
+}
 template <int NSPLIT, bool F16>
-static hipError_t launch_attn_t(const AttnArgs& a, hipStream_t s) {
+static hipError_t launch_attn_t(const AttnArgs& a, hipStream_t s, bool train_hd) {
   const int D = a.D > 0 ? a.D : 64;
-  if (D == 32) return a.lse ? hipErrorInvalidValue : launch_attn_w<NSPLIT, F16, 4, false, 32>(a, s);      // (the backward kernels have a head dim of 64:
-  if (D == 128) return a.lse ? hipErrorInvalidValue : launch_attn_w<NSPLIT, F16, 4, false, 128>(a, s);    //  training.unsupported_reason)
+  if ((D == 32 || D == 128) && a.lse) {                // launch_attention keeps refusing it: its callers' backward has a head dim of 64
+    if constexpr (NSPLIT == 3) { if (train_hd) return D == 32 ? launch_attn_train_d<32>(a, s) : launch_attn_train_d<128>(a, s); }
+    return hipErrorInvalidValue;
+  }
+  if (D == 32) return a.drop_seed ? hipErrorInvalidValue : launch_attn_w<NSPLIT, F16, 4, false, 32>(a, s);
+  if (D == 128) return a.drop_seed ? hipErrorInvalidValue : launch_attn_w<NSPLIT, F16, 4, false, 128>(a, s);
   if (D != 64) return hipErrorInvalidValue;
   if (a.drop_seed) {                                   // attention dropout: the training kernel of precision 3 only
     if constexpr (NSPLIT == 3) { if (a.lse) return launch_attn_w<NSPLIT, F16, 4, true, 64, true>(a, s); }
@@ -413,7 +425,7 @@ static hipError_t launch_attn_fast(const AttnArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 
-hipError_t launch_attention(const AttnArgs& a_in, int nsplit, hipStream_t s) {
+static hipError_t launch_attention_any(const AttnArgs& a_in, int nsplit, hipStream_t s, bool train_hd) {
   AttnArgs a = a_in;
   if (nsplit < 1 || nsplit > 4) return hipErrorInvalidValue;
   // precision 4 ("mixed"): the attention products themselves run as ONE IEEE-half product (they contribute nothing
@@ -430,7 +442,7 @@ hipError_t launch_attention(const AttnArgs& a_in, int nsplit, hipStream_t s) {
   if (a.klens && a.lse && (nsplit != 3 || a.Nq != a.Nk)) return hipErrorInvalidValue;   // ... the training forward of a self-attention (QLENS)
   if (nsplit == 3) {
     if (!a.q_lo || !a.k_lo || !a.vt_lo) return hipErrorInvalidValue;
-    return launch_attn_t<3, false>(a, s);
+    return launch_attn_t<3, false>(a, s, train_hd);
   }
   if (nsplit == 2) {                                  // "half" precision: fp16 hi-only planes, one product
     if (a.q_lo || a.k_lo || a.vt_lo) return hipErrorInvalidValue;
@@ -438,10 +450,16 @@ hipError_t launch_attention(const AttnArgs& a_in, int nsplit, hipStream_t s) {
       if (a.klens) return a.o_fmt == FMT_H8 ? launch_attn_fast<PF_H8, true>(a, s) : launch_attn_fast<PF_F16, true>(a, s);
       return a.o_fmt == FMT_H8 ? launch_attn_fast<PF_H8>(a, s) : launch_attn_fast<PF_F16>(a, s);
     }
-    return launch_attn_t<1, true>(a, s);
+    return launch_attn_t<1, true>(a, s, false);
   }
   if (a.o_fmt != FMT_BF16) return hipErrorInvalidValue;
-  return launch_attn_t<1, false>(a, s);
+  return launch_attn_t<1, false>(a, s, false);
+}
+hipError_t launch_attention(const AttnArgs& a, int nsplit, hipStream_t s) { return launch_attention_any(a, nsplit, s, false); }
+// the training forward at a.D = 32, 64 or 128: precision 3 with lse; D = 64 launches the very kernels launch_attention(a, 3) does
+hipError_t launch_attention_train_hd(const AttnArgs& a, hipStream_t s) {
+  if (!a.lse) return hipErrorInvalidValue;
+  return launch_attention_any(a, 3, s, true);
 }
 
 }  // namespace ns2

@@ -499,11 +499,12 @@ hipError_t launch_rmsnorm_bwd(const NormBwdArgs& a, hipStream_t s) {
 }
 
 // ================================================================================================ attention backward (ATT:77-155)
-// delta[b, h, q] = sum_d dO[q, 64 h + d] * O[q, 64 h + d]   (O from its operand planes, hi + lo)
-// One wave per token row, a lane owns 8 consecutive features (lane = 8 * head-in-group + part; 64 lanes = 512 features, wider rows
-// take several passes): two float4 of dO and the matching 16-byte chunks of the o line per lane, 3 xor-shuffles inside the 8 lanes of
-// a head.  (Round 4's kernel gave every (row, head) ONE thread reading 64 strided floats: 475 us per call, 5.7 ms of a training
+// delta[b, h, q] = sum_d dO[q, D h + d] * O[q, D h + d]   (O from its operand planes, hi + lo; head dim D = 32 / 64 / 128)
+// One wave per token row, a lane owns 8 consecutive features (lane = D / 8 * head-in-group + part; 64 lanes = 512 features, wider rows
+// take several passes): two float4 of dO and the matching 16-byte chunks of the o line per lane, log2(D / 8) xor-shuffles inside the
+// D / 8 lanes of a head.  (Round 4's kernel gave every (row, head) ONE thread reading 64 strided floats: 475 us per call, 5.7 ms of a training
 // step, for 128 MB of traffic; this one streams.)
+template <int D = 64>
 __global__ __launch_bounds__(256) void attn_delta_kernel(const float* dO, long lddo, const bf16_t* o_hi, int ldo, int B, int H, int Nq,
                                                          float* delta, int o_fmt) {
   const int lane = threadIdx.x & 63;
@@ -511,9 +512,10 @@ __global__ __launch_bounds__(256) void attn_delta_kernel(const float* dO, long l
   const long M = (long)B * Nq;
   if (m >= M) return;
   const long b = m / Nq, q = m - b * Nq;
-  // The trip count is uniform per HEAD, not per wave: for H not a multiple of 8 the lanes 8 (H % 8) .. 63 run one pass fewer.  64 H is
-  // a multiple of 64, so the 8 lanes of a head leave the loop together and the xor-shuffles below (distances 1, 2, 4) stay among active lanes.
-  for (int f0 = 8 * lane; f0 < 64 * H; f0 += 512) {
+  // The trip count is uniform per HEAD, not per wave: for D H not a multiple of 512 the lanes D / 8 (H % (512 / D)) .. 63 run one pass
+  // fewer.  D H is a multiple of D and so is the step 512, so the D / 8 lanes of a head leave the loop together and the xor-shuffles below
+  // (distances 1 .. D / 16) stay among active lanes.
+  for (int f0 = 8 * lane; f0 < D * H; f0 += 512) {
     const float4 g0 = *reinterpret_cast<const float4*>(dO + m * lddo + f0), g1 = *reinterpret_cast<const float4*>(dO + m * lddo + f0 + 4);
     const float g[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
     const bf16_t* line = o_hi + m * 2L * ldo + ((f0 & ~31) << 1);     // the 128-byte line of 32 features
@@ -538,18 +540,32 @@ __global__ __launch_bounds__(256) void attn_delta_kernel(const float* dO, long l
     float s = 0.f;
 #pragma unroll
     for (int e = 0; e < 8; ++e) s = fmaf(g[e], o[e], s);
-    s += __shfl_xor(s, 1, 64); s += __shfl_xor(s, 2, 64); s += __shfl_xor(s, 4, 64);
-    if ((lane & 7) == 0) delta[(b * H + (f0 >> 6)) * Nq + q] = s;
+    s += __shfl_xor(s, 1, 64); s += __shfl_xor(s, 2, 64);
+    if constexpr (D >= 64) s += __shfl_xor(s, 4, 64);
+    if constexpr (D >= 128) s += __shfl_xor(s, 8, 64);
+    if ((lane & (D / 8 - 1)) == 0) delta[(b * H + f0 / D) * Nq + q] = s;
   }
 }
-hipError_t launch_attn_delta(const float* dO, long lddo, const bf16_t* o_hi, const bf16_t* o_lo, int ldo, int B, int H, int Nq, float* delta,
-                             hipStream_t s, int o_fmt) {
-  if (B <= 0 || H <= 0 || Nq <= 0 || !o_lo || o_lo != o_hi + 32 || (ldo & 31) || ldo < 64 * H) return hipErrorInvalidValue;
+template <int D>
+static hipError_t launch_attn_delta_d(const float* dO, long lddo, const bf16_t* o_hi, const bf16_t* o_lo, int ldo, int B, int H, int Nq, float* delta,
+                                      hipStream_t s, int o_fmt) {
+  if (B <= 0 || H <= 0 || Nq <= 0 || !o_lo || o_lo != o_hi + 32 || (ldo & 31) || ldo < D * H) return hipErrorInvalidValue;
   if (o_fmt != FMT_BF16 && o_fmt != FMT_H8) return hipErrorInvalidValue;
   if ((lddo & 3) || (reinterpret_cast<uintptr_t>(dO) & 15) || (reinterpret_cast<uintptr_t>(o_hi) & 15)) return hipErrorInvalidValue;
   const long n = (long)B * Nq;
-  hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, dO, lddo, o_hi, ldo, B, H, Nq, delta, o_fmt);
+  hipLaunchKernelGGL(attn_delta_kernel<D>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, dO, lddo, o_hi, ldo, B, H, Nq, delta, o_fmt);
   return hipGetLastError();
+}
+hipError_t launch_attn_delta(const float* dO, long lddo, const bf16_t* o_hi, const bf16_t* o_lo, int ldo, int B, int H, int Nq, float* delta,
+                             hipStream_t s, int o_fmt) {
+  return launch_attn_delta_d<64>(dO, lddo, o_hi, o_lo, ldo, B, H, Nq, delta, s, o_fmt);
+}
+hipError_t launch_attn_delta_hd(const float* dO, long lddo, const bf16_t* o_hi, const bf16_t* o_lo, int ldo, int B, int H, int Nq, int D,
+                                float* delta, hipStream_t s, int o_fmt) {
+  if (D == 32) return launch_attn_delta_d<32>(dO, lddo, o_hi, o_lo, ldo, B, H, Nq, delta, s, o_fmt);
+  if (D == 128) return launch_attn_delta_d<128>(dO, lddo, o_hi, o_lo, ldo, B, H, Nq, delta, s, o_fmt);
+  if (D != 64) return hipErrorInvalidValue;
+  return launch_attn_delta_d<64>(dO, lddo, o_hi, o_lo, ldo, B, H, Nq, delta, s, o_fmt);
 }
 
 // Flash backward.  ROLE 0 (dQ): the workgroup OWNS 128 queries (4 waves x 32), walks 64-key tiles:
@@ -579,19 +595,42 @@ typedef __attribute__((address_space(3))) void ab2_lds_void_t;
 typedef const __attribute__((address_space(1))) void ab2_gbl_void_t;
 typedef __attribute__((ext_vector_type(4))) short ab2_v4s;
 typedef __attribute__((address_space(3))) ab2_v4s ab2_lds_v4s_t;
-constexpr int AB2_ROW = 256, AB2_MAT = 64 * AB2_ROW, AB2_STAGE = 2 * AB2_MAT;
-NS2_DEVINL int ab2_f(int r) { return ((r & 3) << 2) | ((r >> 2) & 3); }
+// Head dim D (32 / 64 / 128): a row is the head's D columns as they lie in memory, 4 D bytes = D / 32 interleaved [hi 32 | lo 32] lines
+// = D / 4 chunks.  What has to stay conflict free is counted in the 256 bytes the 64 banks take per cycle:
+//   D = 128: a row is two 256-byte halves.  f(r) above is xor-ed into the low four bits of the chunk index and bit 4 (the half) stays, so
+//     inside each half the picture is that of D = 64: the 16 rows of a ds_read_b128 group take 16 bank positions, the 4 rows of a
+//     transpose block four 64-byte quarters.
+//   D = 32: a row is 128 bytes, so rows r and r ^ 1 share 256 bytes and bit 0 of r already picks the 128-byte half.  The chunk index has
+//     three bits; f32(r) = (bit 1 of r) << 2 | bits 2-3 of r is a bijection of r >> 1 (r < 16) onto them: with bit 0 the 16 rows of a
+//     ds_read_b128 group take all 16 bank positions.  The 4 chunks of a transpose block share bit 2 (the plane), which f32 flips with bit 1
+//     of r, and bit 0 of r picks the half: rows 4 k .. 4 k + 3 land in four different 64-byte quarters.
+// A DMA instruction moves 1024 bytes whatever D is: 256 / D rows; a matrix takes D / 4 instructions, a wave issues D / 8 per tile.
+template <int D> struct Ab2Geom {
+  static_assert(D == 32 || D == 64 || D == 128, "head dim 32, 64 or 128");
+  static constexpr int ROW = 4 * D, MAT = 64 * ROW, STAGE = 2 * MAT;
+  static constexpr int NC = D / 16;                  // 16-deep chunks of the contraction over d (own fragments per plane)
+  static constexpr int ND = D / 32;                  // 32-column accumulator tiles
+  static constexpr int NCH = D / 4;                  // 16-byte chunks per row
+  static constexpr int IPW = D / 8;                  // DMA instructions per wave and tile
+  static constexpr int RPI = 256 / D;                // rows per DMA instruction
+  static constexpr size_t LDS = 2 * STAGE + 2 * 128 * sizeof(float);      // 33 / 65 / 129 KiB
+};
+template <int D>
+NS2_DEVINL int ab2_f(int r) {
+  if constexpr (D == 32) return (((r >> 1) & 1) << 2) | ((r >> 2) & 3);
+  else return ((r & 3) << 2) | ((r >> 2) & 3);
+}
 
 // The own row's results leave the kernel: lane holds d = 32 dt + 8 gq + 4 hi + e of row `orow` of utterance b (Sown rows per utterance);
 // acc1 = dQ^T (role 0) / dK^T (role 1), still without the softmax scale, acc2 = dV^T (role 1)
-template <int ROLE>
-NS2_DEVINL void ab2_store_own(const AttnBwdArgs& a, int b, int h, int orow, int hi, int Sown, const f32x16 (&acc1)[2], const f32x16 (&acc2)[2]) {
+template <int ROLE, int D>
+NS2_DEVINL void ab2_store_own(const AttnBwdArgs& a, int b, int h, int orow, int hi, int Sown, const f32x16 (&acc1)[D / 32], const f32x16 (&acc2)[D / 32]) {
   if (ROLE == 0 ? a.gp_q : a.gp_kv) {
     // operand planes: the lane's 4-column groups of its own row (lanes l31 and l31 + 32 interleave the groups of a 32-column line)
     bf16_t* prow = a.gp_hi + ((long)b * Sown + orow) * 2L * a.gp_ld;
-    const int c1 = (ROLE == 0 ? a.dq_col0 : a.dk_col0) + h * 64, c2 = a.dv_col0 + h * 64;
+    const int c1 = (ROLE == 0 ? a.dq_col0 : a.dk_col0) + h * D, c2 = a.dv_col0 + h * D;
 #pragma unroll
-    for (int dt = 0; dt < 2; ++dt)
+    for (int dt = 0; dt < D / 32; ++dt)
 #pragma unroll
       for (int gq = 0; gq < 4; ++gq) {
         const int dcol = 32 * dt + 8 * gq + 4 * hi;
@@ -602,17 +641,17 @@ NS2_DEVINL void ab2_store_own(const AttnBwdArgs& a, int b, int h, int orow, int 
       }
     return;
   }
-  float* o1 = ROLE == 0 ? a.dq + ((long)b * a.Nq + orow) * a.lddq + a.dq_col0 + h * 64
-                        : a.dk + ((long)b * a.Nk + orow) * a.lddk + a.dk_col0 + h * 64;
+  float* o1 = ROLE == 0 ? a.dq + ((long)b * a.Nq + orow) * a.lddq + a.dq_col0 + h * D
+                        : a.dk + ((long)b * a.Nk + orow) * a.lddk + a.dk_col0 + h * D;
 #pragma unroll
-  for (int dt = 0; dt < 2; ++dt)
+  for (int dt = 0; dt < D / 32; ++dt)
 #pragma unroll
     for (int gq = 0; gq < 4; ++gq) {
       const int dcol = 32 * dt + 8 * gq + 4 * hi;
       *reinterpret_cast<float4*>(o1 + dcol) = make_float4(acc1[dt][4 * gq] * a.scale, acc1[dt][4 * gq + 1] * a.scale,
                                                           acc1[dt][4 * gq + 2] * a.scale, acc1[dt][4 * gq + 3] * a.scale);
       if constexpr (ROLE == 1) {
-        float* o2 = a.dv + ((long)b * a.Nk + orow) * a.lddv + a.dv_col0 + h * 64;
+        float* o2 = a.dv + ((long)b * a.Nk + orow) * a.lddv + a.dv_col0 + h * D;
         *reinterpret_cast<float4*>(o2 + dcol) = make_float4(acc2[dt][4 * gq], acc2[dt][4 * gq + 1], acc2[dt][4 * gq + 2], acc2[dt][4 * gq + 3]);
       }
     }
@@ -628,9 +667,13 @@ NS2_DEVINL void ab2_store_own(const AttnBwdArgs& a, int b, int h, int orow, int 
 // BOUND -- ceil(len_b / 64) tiles walked, rows of the boundary tile from len_b on out of the zero page (role 1: their statistics out of
 // ab2_inf_zero), whatever memory holds there -- while a.Nq / a.Nk stay the strides of every address.  Own rows from len_b on are written
 // as exact zeros; a workgroup whose own tile lies wholly beyond len_b writes them and returns before its first DMA piece and barrier.
-template <int ROLE, bool MD = false, bool LENS = false>
-__global__ __launch_bounds__(256, 2) void attn_bwd2_kernel(const AttnBwdArgs a) {
+// D = 128: 128 VGPRs of own fragments and 128 of accumulators need the whole register file of a SIMD, and two stages of two 32 KiB
+// matrices its LDS: one workgroup per CU.
+template <int ROLE, bool MD = false, bool LENS = false, int D = 64>
+__global__ __launch_bounds__(256, D == 128 ? 1 : 2) void attn_bwd2_kernel(const AttnBwdArgs a) {
   static_assert(!(MD && LENS), "lengths exclude the key mask and dropout");
+  using G = Ab2Geom<D>;
+  constexpr int AB2_ROW = G::ROW, AB2_MAT = G::MAT, AB2_STAGE = G::STAGE, NC = G::NC, ND = G::ND;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   float* s_stat = reinterpret_cast<float*>(smem + 2 * AB2_STAGE);       // [stage][lse 64 | delta 64] (role 1)
   const int tid = threadIdx.x, lane = tid & 63;
@@ -648,12 +691,12 @@ __global__ __launch_bounds__(256, 2) void attn_bwd2_kernel(const AttnBwdArgs a) 
     Nown = Nwalk = __builtin_amdgcn_readfirstlane(min(max(a.lens[b], 1), Sown));
     if (ot * 128 >= Nown) {                                                        // nothing of this utterance in the own tile
       if (orow < Sown) {
-        f32x16 z[2];
+        f32x16 z[ND];
 #pragma unroll
-        for (int dt = 0; dt < 2; ++dt)
+        for (int dt = 0; dt < ND; ++dt)
 #pragma unroll
           for (int r = 0; r < 16; ++r) z[dt][r] = 0.f;
-        ab2_store_own<ROLE>(a, b, h, orow, hi, Sown, z, z);
+        ab2_store_own<ROLE, D>(a, b, h, orow, hi, Sown, z, z);
       }
       return;
     }
@@ -665,15 +708,15 @@ __global__ __launch_bounds__(256, 2) void attn_bwd2_kernel(const AttnBwdArgs a) 
   const int ldx = ROLE == 0 ? a.ldq : a.ldk, xcol = ROLE == 0 ? a.q_col0 : a.k_col0;
   const bf16_t* gb = ROLE == 0 ? a.do_hi : a.v_hi;
   const int ldg = ROLE == 0 ? a.lddo : a.ldv, gcol = ROLE == 0 ? 0 : a.v_col0;
-  bf16x8 xf[2][4], gf[2][4];
+  bf16x8 xf[2][NC], gf[2][NC];
 #pragma unroll
   for (int p = 0; p < 2; ++p)
 #pragma unroll
-    for (int c = 0; c < 4; ++c) {
+    for (int c = 0; c < NC; ++c) {
       uint4 vx = make_uint4(0u, 0u, 0u, 0u), vg = make_uint4(0u, 0u, 0u, 0u);
       if (own_ok) {
-        vx = *reinterpret_cast<const uint4*>(xb + ((long)b * Sown + orow) * 2L * ldx + pcol(xcol + h * 64 + 16 * c + 8 * hi, true) + 32 * p);
-        vg = *reinterpret_cast<const uint4*>(gb + ((long)b * Sown + orow) * 2L * ldg + pcol(gcol + h * 64 + 16 * c + 8 * hi, true) + 32 * p);
+        vx = *reinterpret_cast<const uint4*>(xb + ((long)b * Sown + orow) * 2L * ldx + pcol(xcol + h * D + 16 * c + 8 * hi, true) + 32 * p);
+        vg = *reinterpret_cast<const uint4*>(gb + ((long)b * Sown + orow) * 2L * ldg + pcol(gcol + h * D + 16 * c + 8 * hi, true) + 32 * p);
       }
       xf[p][c] = *reinterpret_cast<bf16x8*>(&vx);
       gf[p][c] = *reinterpret_cast<bf16x8*>(&vg);
@@ -701,34 +744,36 @@ __global__ __launch_bounds__(256, 2) void attn_bwd2_kernel(const AttnBwdArgs a) 
   const bf16_t* ygb = ROLE == 0 ? a.v_hi : a.do_hi;
   const int ldyg = ROLE == 0 ? a.ldv : a.lddo, ygcol = ROLE == 0 ? a.v_col0 : 0;
 
-  // ---- DMA pieces: instruction j = 8 wave + i of the tile's 32 (matrix j >> 4, tile rows 4 (j & 15) ...); the lane's row = .. + (lane >> 4),
-  // stored position lane & 15, i.e. it fetches logical chunk (lane & 15) ^ f(row); f(row) = ((lane >> 4) << 2) | (i & 3)
-  const int drow = lane >> 4, dpos = lane & 15;
-  const bf16_t* dsrc[8];           // source of tile 0 (advanced by 64 rows per tile)
-  int dtr[8];                      // tile row of the lane
+  // ---- DMA pieces: instruction j = IPW wave + i of the tile's 4 IPW (D = 64: 8 wave + i of 32; matrix j / IPM, tile rows RPI (j % IPM) ...);
+  // the lane's row = .. + lane / NCH, stored position lane % NCH, i.e. it fetches logical chunk (lane % NCH) ^ f(row)
+  // (D = 64: f(row) = ((lane >> 4) << 2) | (i & 3))
+  constexpr int IPW = G::IPW, IPM = 2 * G::IPW;
+  const int drow = lane / G::NCH, dpos = lane % G::NCH;
+  const bf16_t* dsrc[IPW];         // source of tile 0 (advanced by 64 rows per tile)
+  int dtr[IPW];                    // tile row of the lane
   const long ystep = 64L * 2 * ldy, ygstep = 64L * 2 * ldyg;
 #pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const int j = 8 * wave + i, mat = j >> 4;
-    const int tr = 4 * (j & 15) + drow;
-    const int lc = dpos ^ ((drow << 2) | (i & 3));
+  for (int i = 0; i < IPW; ++i) {
+    const int j = IPW * wave + i, mat = j / IPM;
+    const int tr = G::RPI * (j % IPM) + drow;
+    const int lc = dpos ^ ab2_f<D>(tr);
     dtr[i] = tr;
-    dsrc[i] = mat == 0 ? yb + ((long)b * Swalk + tr) * 2L * ldy + pcol(ycol + h * 64, true) + lc * 8
-                       : ygb + ((long)b * Swalk + tr) * 2L * ldyg + pcol(ygcol + h * 64, true) + lc * 8;
+    dsrc[i] = mat == 0 ? yb + ((long)b * Swalk + tr) * 2L * ldy + pcol(ycol + h * D, true) + lc * 8
+                       : ygb + ((long)b * Swalk + tr) * 2L * ldyg + pcol(ygcol + h * D, true) + lc * 8;
   }
   auto issue_tile = [&](int t, int stage) __attribute__((always_inline)) {
     const int r0 = t * 64;
     const bool full = r0 + 64 <= Nwalk;
     unsigned char* sb = smem + stage * AB2_STAGE;
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const int j = 8 * wave + i;
-      const bf16_t* p = dsrc[i] + (long)t * ((j >> 4) == 0 ? ystep : ygstep);
+    for (int i = 0; i < IPW; ++i) {
+      const int j = IPW * wave + i;
+      const bf16_t* p = dsrc[i] + (long)t * (j / IPM == 0 ? ystep : ygstep);
       if (!full && r0 + dtr[i] >= Nwalk) p = ab2_zero_page;                       // rows beyond Nwalk are zeros (as in the staged kernel)
       // As inline assembly: behind the builtin the waitcnt pass assumes every later LDS read may alias the DMA's destination and puts
       // `s_waitcnt vmcnt(0)` in front of the first read of the tile being multiplied -- the prefetch would be waited for at once.
       // The ordering that matters (this wave's vmcnt(0) + the barrier at the top of the next iteration) is explicit below.
-      const unsigned dst = (unsigned)(size_t)(sb + (j >> 4) * AB2_MAT + (j & 15) * 1024);
+      const unsigned dst = (unsigned)(size_t)(sb + (j / IPM) * AB2_MAT + (j % IPM) * 1024);
       asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" :: "v"(p), "s"(dst) : "memory", "m0");
     }
     if constexpr (ROLE == 0 && MD) {
@@ -755,18 +800,20 @@ __global__ __launch_bounds__(256, 2) void attn_bwd2_kernel(const AttnBwdArgs a) 
 
   // ---- fragment addressing
   const int pi_row = (l31 & 0x13) | ((l31 & 4) << 1) | ((l31 & 8) >> 1);
-  const int fy = ab2_f(pi_row);                    // (js * 32 does not touch bits 0-3)
+  const int fy = ab2_f<D>(pi_row);                 // (js * 32 does not touch bits 0-3)
   const int y_row_off = pi_row * AB2_ROW;
   // transpose reads: i16 = the lane's place in its 16-lane group, tg = which 16 d columns of the 32 (l31 = 16 tg + i16 = the d it receives).
   // read q (0, 1) of (js, g1): supplies row 32 js + 16 g1 + 8 hi + 4 q + (i16 >> 2), d columns 16 tg + 4 (i16 & 3) .. + 3 of plane p, 32-column half dt
   const int i16 = lane & 15, tg = (lane >> 4) & 1;
-  int t_off[2][2][2];                              // [q][dt][p]: byte offset inside a matrix, rows 32 js + 16 g1 to be added
+  // (D = 128: f touches the low four bits of the chunk only, so the tiles dt = 2, 3 lie 256 bytes behind dt = 0, 1: an immediate)
+  constexpr int NDT = ND < 2 ? ND : 2;
+  int t_off[2][NDT][2];                            // [q][dt][p]: byte offset inside a matrix, rows 32 js + 16 g1 to be added
 #pragma unroll
   for (int q = 0; q < 2; ++q) {
     const int row = 8 * hi + 4 * q + (i16 >> 2);
-    const int f = ab2_f(row);                      // (32 js + 16 g1 does not touch bits 0-3)
+    const int f = ab2_f<D>(row);                   // (32 js + 16 g1 does not touch bits 0-3)
 #pragma unroll
-    for (int dt = 0; dt < 2; ++dt)
+    for (int dt = 0; dt < NDT; ++dt)
 #pragma unroll
       for (int p = 0; p < 2; ++p) {
         const int lc = dt * 8 + p * 4 + 2 * tg + ((i16 >> 1) & 1);
@@ -774,15 +821,15 @@ __global__ __launch_bounds__(256, 2) void attn_bwd2_kernel(const AttnBwdArgs a) 
       }
   }
   auto tfrag = [&](const unsigned char* mat, int js, int g1, int dt, int p) __attribute__((always_inline)) {
-    const unsigned char* base = mat + (32 * js + 16 * g1) * AB2_ROW;
-    const ab2_v4s lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((ab2_lds_v4s_t*)(base + t_off[0][dt][p]));
-    const ab2_v4s hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((ab2_lds_v4s_t*)(base + t_off[1][dt][p]));
+    const unsigned char* base = mat + (32 * js + 16 * g1) * AB2_ROW + (dt >> 1) * 256;
+    const ab2_v4s lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((ab2_lds_v4s_t*)(base + t_off[0][dt & 1][p]));
+    const ab2_v4s hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((ab2_lds_v4s_t*)(base + t_off[1][dt & 1][p]));
     return bf16x8{lo[0], lo[1], lo[2], lo[3], hi4[0], hi4[1], hi4[2], hi4[3]};
   };
 
-  f32x16 acc1[2], acc2[2];
+  f32x16 acc1[ND], acc2[ND];
 #pragma unroll
-  for (int dt = 0; dt < 2; ++dt)
+  for (int dt = 0; dt < ND; ++dt)
 #pragma unroll
     for (int r = 0; r < 16; ++r) { acc1[dt][r] = 0.f; acc2[dt][r] = 0.f; }
   const float sl2 = a.scale * 1.4426950408889634f;
@@ -795,7 +842,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd2_kernel(const AttnBwdArgs a) 
 #pragma unroll
   for (int p = 0; p < 2; ++p)
 #pragma unroll
-    for (int c = 0; c < 4; ++c) asm volatile("" :: "v"(xf[p][c]), "v"(gf[p][c]));
+    for (int c = 0; c < NC; ++c) asm volatile("" :: "v"(xf[p][c]), "v"(gf[p][c]));
   issue_tile(0, 0);
   for (int t = 0; t < ntiles; ++t) {
     const int r0 = t * 64, st = t & 1;
@@ -813,11 +860,11 @@ __global__ __launch_bounds__(256, 2) void attn_bwd2_kernel(const AttnBwdArgs a) 
 #pragma unroll
       for (int r = 0; r < 16; ++r) { stt[r] = 0.f; dp[r] = 0.f; }
 #pragma unroll
-      for (int c = 0; c < 4; ++c) {
+      for (int c = 0; c < NC; ++c) {
         bf16x8 yf[2], ygf[2];
 #pragma unroll
         for (int p = 0; p < 2; ++p) {
-          const int off = js * 32 * AB2_ROW + y_row_off + ((((c >> 1) * 8 + p * 4 + 2 * (c & 1) + hi) ^ fy) << 4);
+          const int off = js * 32 * AB2_ROW + y_row_off + (c >> 2) * 256 + (((((c >> 1) & 1) * 8 + p * 4 + 2 * (c & 1) + hi) ^ fy) << 4);
           yf[p] = *reinterpret_cast<const bf16x8*>(my + off);
           ygf[p] = *reinterpret_cast<const bf16x8*>(myg + off);
         }
@@ -891,7 +938,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd2_kernel(const AttnBwdArgs a) 
           pf[1] = *reinterpret_cast<const bf16x8*>(&ul);
         }
 #pragma unroll
-        for (int dt = 0; dt < 2; ++dt) {
+        for (int dt = 0; dt < ND; ++dt) {
           const bf16x8 t1h = tfrag(my, js, g1, dt, 0), t1l = tfrag(my, js, g1, dt, 1);
           acc1[dt] = mma16<false>(t1l, dsf[0], acc1[dt]);
           acc1[dt] = mma16<false>(t1h, dsf[1], acc1[dt]);
@@ -912,29 +959,30 @@ __global__ __launch_bounds__(256, 2) void attn_bwd2_kernel(const AttnBwdArgs a) 
     if (orow >= Sown) return;
     if (!own_ok) {                                   // a row of the tensor beyond the utterance: exact zeros
 #pragma unroll
-      for (int dt = 0; dt < 2; ++dt)
+      for (int dt = 0; dt < ND; ++dt)
 #pragma unroll
         for (int r = 0; r < 16; ++r) { acc1[dt][r] = 0.f; acc2[dt][r] = 0.f; }
     }
   } else {
     if (!own_ok) return;
   }
-  ab2_store_own<ROLE>(a, b, h, orow, hi, Sown, acc1, acc2);
+  ab2_store_own<ROLE, D>(a, b, h, orow, hi, Sown, acc1, acc2);
 }
 
-template <int ROLE, bool MD = false, bool LENS = false>
+template <int ROLE, bool MD = false, bool LENS = false, int D = 64>
 static hipError_t launch_attn_bwd2_role(const AttnBwdArgs& a, hipStream_t s) {
-  const size_t lds = 2 * AB2_STAGE + 2 * 128 * sizeof(float);
+  const size_t lds = Ab2Geom<D>::LDS;
   static DynLdsAttr attr;
-  hipError_t e = attr.ensure(reinterpret_cast<const void*>(&attn_bwd2_kernel<ROLE, MD, LENS>), (int)lds);
+  hipError_t e = attr.ensure(reinterpret_cast<const void*>(&attn_bwd2_kernel<ROLE, MD, LENS, D>), (int)lds);
   if (e != hipSuccess) return e;
   const int nown = ROLE == 0 ? a.Nq : a.Nk;
   dim3 grid(((nown + 127) / 128) * a.H * a.B);
-  hipLaunchKernelGGL((attn_bwd2_kernel<ROLE, MD, LENS>), grid, dim3(256), lds, s, a);
+  hipLaunchKernelGGL((attn_bwd2_kernel<ROLE, MD, LENS, D>), grid, dim3(256), lds, s, a);
   return hipGetLastError();
 }
 
-hipError_t launch_attention_bwd(const AttnBwdArgs& a, hipStream_t s) {
+template <int D>
+static hipError_t launch_attention_bwd_d(const AttnBwdArgs& a, hipStream_t s) {
   if (a.B <= 0 || a.H <= 0 || a.Nq <= 0 || a.Nk <= 0 || !a.lse || !a.delta) return hipErrorInvalidValue;
   auto il = [](const bf16_t* hi_, const bf16_t* lo_) { return hi_ && lo_ == hi_ + 32; };
   if (!il(a.q_hi, a.q_lo) || !il(a.k_hi, a.k_lo) || !il(a.v_hi, a.v_lo) || !il(a.do_hi, a.do_lo)) return hipErrorInvalidValue;
@@ -949,19 +997,27 @@ hipError_t launch_attention_bwd(const AttnBwdArgs& a, hipStream_t s) {
   if (want_q && !a.gp_q && ((a.lddq & 3) || (a.dq_col0 & 3))) return hipErrorInvalidValue;
   if (a.lens) {                                        // the denoiser's pass on a ragged batch: self-attention, no mask, no dropout
     if (a.kmask || a.drop_seed || a.Nq != a.Nk) return hipErrorInvalidValue;
-    if (want_q) { hipError_t e = launch_attn_bwd2_role<0, false, true>(a, s); if (e != hipSuccess) return e; }
-    if (want_kv) { hipError_t e = launch_attn_bwd2_role<1, false, true>(a, s); if (e != hipSuccess) return e; }
+    if (want_q) { hipError_t e = launch_attn_bwd2_role<0, false, true, D>(a, s); if (e != hipSuccess) return e; }
+    if (want_kv) { hipError_t e = launch_attn_bwd2_role<1, false, true, D>(a, s); if (e != hipSuccess) return e; }
     return hipSuccess;
   }
   if (a.kmask || a.drop_seed) {                        // the encoders' pass: mask and / or dropout
     if (a.drop_seed ? !(a.drop_scale >= 1.f) : (a.drop_thr != 0u || a.drop_scale != 1.f)) return hipErrorInvalidValue;
-    if (want_q) { hipError_t e = launch_attn_bwd2_role<0, true>(a, s); if (e != hipSuccess) return e; }
-    if (want_kv) { hipError_t e = launch_attn_bwd2_role<1, true>(a, s); if (e != hipSuccess) return e; }
+    if (want_q) { hipError_t e = launch_attn_bwd2_role<0, true, false, D>(a, s); if (e != hipSuccess) return e; }
+    if (want_kv) { hipError_t e = launch_attn_bwd2_role<1, true, false, D>(a, s); if (e != hipSuccess) return e; }
     return hipSuccess;
   }
-  if (want_q) { hipError_t e = launch_attn_bwd2_role<0>(a, s); if (e != hipSuccess) return e; }
-  if (want_kv) { hipError_t e = launch_attn_bwd2_role<1>(a, s); if (e != hipSuccess) return e; }
+  if (want_q) { hipError_t e = launch_attn_bwd2_role<0, false, false, D>(a, s); if (e != hipSuccess) return e; }
+  if (want_kv) { hipError_t e = launch_attn_bwd2_role<1, false, false, D>(a, s); if (e != hipSuccess) return e; }
   return hipSuccess;
+}
+hipError_t launch_attention_bwd(const AttnBwdArgs& a, hipStream_t s) { return launch_attention_bwd_d<64>(a, s); }
+// head h at columns col0 + D h (include/ns2hip_head_dim_train.h); D = 64 launches the very kernels of launch_attention_bwd
+hipError_t launch_attention_bwd_hd(const AttnBwdArgs& a, int D, hipStream_t s) {
+  if (D == 32) return launch_attention_bwd_d<32>(a, s);
+  if (D == 128) return launch_attention_bwd_d<128>(a, s);
+  if (D != 64) return hipErrorInvalidValue;
+  return launch_attention_bwd_d<64>(a, s);
 }
 
 // ================================================================================================ SiLU of the k = 9 convolutions (NS2:247, 306-311)

@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <cstring>
 
+#include "../../include/ns2hip_head_dim_train.h"
 #include "../../include/ns2hip_ragged_train.h"
 #include "ns2_host.h"
 
@@ -243,7 +244,7 @@ extern "C" int ns2_attention_delta(const float* d_out, int64_t ld_dout, const ui
   HIPRET(launch_attn_delta(d_out, (long)ld_dout, o_hi, o_lo, ldo, B, H, Nq, delta, (hipStream_t)stream, operand_fmt(o_precision)));
   return NS2_OK;
 }
-static int attention_bwd(const ns2_attn_bwd_args* p, const int* lens, void* stream) {
+static int attention_bwd(const ns2_attn_bwd_args* p, const int* lens, void* stream, int head_dim = 0) {
   ARGCHK(p->gp_precision == 0 || p->gp_precision == 3 || p->gp_precision == 4, "ns2_attention_bwd: gp_precision 3 (bf16 hi / lo planes) or 4 (FMT_H8 lines)");
   AttnBwdArgs a;
   if (const char* bad = set_attn_dropout(a, p->dropout_p, p->dropout_seed, p->dropout_call)) { set_error("ns2_attention_bwd: %s", bad); return NS2_ERR_ARG; }
@@ -260,7 +261,8 @@ static int attention_bwd(const ns2_attn_bwd_args* p, const int* lens, void* stre
   a.gp_fmt = operand_fmt(p->gp_precision);
   a.kmask = p->key_mask;
   a.lens = lens;
-  HIPRET(launch_attention_bwd(a, (hipStream_t)stream));
+  if (head_dim) HIPRET(launch_attention_bwd_hd(a, head_dim, (hipStream_t)stream));
+  else HIPRET(launch_attention_bwd(a, (hipStream_t)stream));
   return NS2_OK;
 }
 extern "C" int ns2_attention_bwd(const ns2_attn_bwd_args* p, void* stream) {
@@ -291,6 +293,55 @@ extern "C" int ns2_attention_bwd_lens(const ns2_attn_bwd_args* p, const int* len
   ARGCHK(!p->key_mask, "ns2_attention_bwd_lens: key_mask together with lens (one way of shortening the keys per call)");
   ARGCHK(p->dropout_p == 0.f, "ns2_attention_bwd_lens: dropout together with lens (the denoiser's self-attention has none)");
   return attention_bwd(p, lens, stream);
+}
+
+// ---- training at head dims 32 / 128 (include/ns2hip_head_dim_train.h): every refusal is made here, before any device call
+static bool head_dim_ok(int d) { return d == 0 || d == 32 || d == 64 || d == 128; }
+extern "C" int ns2_attention_train_fwd_hd(const ns2_attn_args* p, const int* lens, void* stream) {
+  ARGCHK(p != nullptr, "ns2_attention_train_fwd_hd: null argument block");
+  ARGCHK(head_dim_ok(p->head_dim), "ns2_attention_train_fwd_hd: head_dim must be 32, 64 or 128 (0 = 64)");
+  ARGCHK(p->lse, "ns2_attention_train_fwd_hd: lse is missing (this is the training forward; ns2_attention_fwd is the inference one)");
+  ARGCHK(p->precision == 3, "ns2_attention_train_fwd_hd: the training forward runs in precision 3");
+  ARGCHK(p->q_lo && p->k_lo && p->vt_lo && p->o_lo, "ns2_attention_train_fwd_hd: precision 3 operands and o come with their lo planes");
+  ARGCHK(((p->q_col0 | p->k_col0) & 31) == 0, "ns2_attention_train_fwd_hd: q_col0 and k_col0 must be multiples of 32 (interleaved lines)");
+  if (lens) {
+    ARGCHK(p->Nq == p->Nk, "ns2_attention_train_fwd_hd: Nq != Nk (lengths belong to a self-attention)");
+    ARGCHK(!p->key_mask, "ns2_attention_train_fwd_hd: key_mask together with lens (one way of shortening the keys per call)");
+    ARGCHK(p->dropout_p == 0.f, "ns2_attention_train_fwd_hd: dropout together with lens (the denoiser's self-attention has none)");
+  }
+  ns2_attn_args q = *p;            // attn_args_from is ns2_attention_fwd's translation, which ties lse to a head dim of 64
+  q.head_dim = 0;
+  AttnArgs a;
+  if (int rc = attn_args_from(&q, &a)) return rc;
+  a.D = p->head_dim ? p->head_dim : 64;
+  a.klens = lens;
+  HIPRET(launch_attention_train_hd(a, (hipStream_t)stream));
+  return NS2_OK;
+}
+extern "C" int ns2_attention_delta_hd(const float* d_out, int64_t ld_dout, const uint16_t* o_hi, const uint16_t* o_lo, int ldo, int B, int H,
+                                      int Nq, int head_dim, float* delta, int o_precision, void* stream) {
+  ARGCHK(d_out && o_hi && delta, "ns2_attention_delta_hd: null pointer");
+  ARGCHK(head_dim_ok(head_dim), "ns2_attention_delta_hd: head_dim must be 32, 64 or 128 (0 = 64)");
+  ARGCHK(o_precision == 3 || o_precision == 4, "ns2_attention_delta_hd: o_precision 3 (bf16 hi / lo planes) or 4 (FMT_H8 lines)");
+  HIPRET(launch_attn_delta_hd(d_out, (long)ld_dout, o_hi, o_lo, ldo, B, H, Nq, head_dim ? head_dim : 64, delta, (hipStream_t)stream,
+                              operand_fmt(o_precision)));
+  return NS2_OK;
+}
+extern "C" int ns2_attention_bwd_hd(const ns2_attn_bwd_args* p, int head_dim, const int* lens, void* stream) {
+  ARGCHK(p != nullptr, "ns2_attention_bwd_hd: null argument block");
+  ARGCHK(head_dim_ok(head_dim), "ns2_attention_bwd_hd: head_dim must be 32, 64 or 128 (0 = 64)");
+  ARGCHK(p->lse && p->delta, "ns2_attention_bwd_hd: lse or delta is missing");
+  ARGCHK(((p->q_col0 | p->k_col0 | p->v_col0) & 31) == 0, "ns2_attention_bwd_hd: q_col0, k_col0 and v_col0 must be multiples of 32 (interleaved lines)");
+  ARGCHK(!p->gp_q || (p->dq_col0 & 31) == 0, "ns2_attention_bwd_hd: dq_col0 of a plane output must be a multiple of 32");
+  ARGCHK(!p->gp_kv || ((p->dk_col0 | p->dv_col0) & 31) == 0, "ns2_attention_bwd_hd: dk_col0 and dv_col0 of a plane output must be multiples of 32");
+  ARGCHK(p->gp_q || !p->dq || (p->dq_col0 & 3) == 0, "ns2_attention_bwd_hd: dq_col0 must be a multiple of 4");
+  ARGCHK(p->gp_kv || !(p->dk || p->dv) || ((p->dk_col0 | p->dv_col0) & 3) == 0, "ns2_attention_bwd_hd: dk_col0 and dv_col0 must be multiples of 4");
+  if (lens) {
+    ARGCHK(p->Nq == p->Nk, "ns2_attention_bwd_hd: Nq != Nk (lengths belong to a self-attention)");
+    ARGCHK(!p->key_mask, "ns2_attention_bwd_hd: key_mask together with lens (one way of shortening the keys per call)");
+    ARGCHK(p->dropout_p == 0.f, "ns2_attention_bwd_hd: dropout together with lens (the denoiser's self-attention has none)");
+  }
+  return attention_bwd(p, lens, stream, head_dim ? head_dim : 64);
 }
 extern "C" int ns2_dropout_keep_mask(const uint32_t* seed, unsigned call, float dropout_p, int B, int H, int Nq, int Nk, uint8_t* out, void* stream) {
   ARGCHK(seed && out, "ns2_dropout_keep_mask: null pointer");

@@ -147,6 +147,7 @@ struct AttnArgs {
   const int* klens = nullptr;
 };                                                       // precision: 3 bf16x3, 1 bf16, 2 and 4: one IEEE-half product
 hipError_t launch_attention(const AttnArgs& a, int precision, hipStream_t s);
+hipError_t launch_attention_train_hd(const AttnArgs& a, hipStream_t s);   // the training forward (lse, precision 3) at a.D = 32 / 64 / 128
 long long attention_fast_launches();                                   // test hook: launches that took attn_fast_kernel so far (ns2_debug_attention_fast_launches)
 void force_attention_kernel(int k);                                     // test hook, the modes of ns2_debug_force_attention (include/ns2hip.h); decoded in attention.hip
 
@@ -334,6 +335,8 @@ int rmsnorm_bwd_slices(int seq_len);
 hipError_t launch_rmsnorm_bwd(const NormBwdArgs& a, hipStream_t s);
 hipError_t launch_attn_delta(const float* dO, long lddo, const bf16_t* o_hi, const bf16_t* o_lo, int ldo, int B, int H, int Nq, float* delta,
                              hipStream_t s, int o_fmt = 0);
+hipError_t launch_attn_delta_hd(const float* dO, long lddo, const bf16_t* o_hi, const bf16_t* o_lo, int ldo, int B, int H, int Nq, int D,
+                                float* delta, hipStream_t s, int o_fmt);      // heads of D = 32 / 64 / 128 columns
 struct AttnBwdArgs {                                                // (every field defaulted, as in AttnArgs)
   const bf16_t* q_hi = nullptr; const bf16_t* q_lo = nullptr; int ldq = 0, q_col0 = 0;    // [B*Nq, ldq], head h at columns q_col0 + 64 h
   const bf16_t* k_hi = nullptr; const bf16_t* k_lo = nullptr; int ldk = 0, k_col0 = 0;    // [B*Nk, ldk]
@@ -357,6 +360,7 @@ struct AttnBwdArgs {                                                // (every fi
   const int* lens = nullptr;
 };
 hipError_t launch_attention_bwd(const AttnBwdArgs& a, hipStream_t s);
+hipError_t launch_attention_bwd_hd(const AttnBwdArgs& a, int D, hipStream_t s);      // head h at columns col0 + D h, D = 32 / 64 / 128
 
 // the encoders' training pass (backward.hip): SiLU forward / backward on fp32 rows, the deterministic embedding gradient, and the
 // dropout keep mask of dropout_keep.h as bytes [B, H, Nq, Nk]

@@ -55,10 +55,11 @@ class DurationPitchPredictorTrunk(nn.Module):   # NS2:411-481
 class DurationPitchPredictor(nn.Module):
     def __init__(self, *, dim, num_phoneme_tokens=None, tokenizer=None, dim_encoded_prompts=None, num_convolutions_per_block=3,
                  use_resnet_block=True, num_convs_per_resnet_block=2, depth=10, kernel_size=3, heads=8, dim_head=64,
-                 dim_hidden=512, dropout=0.2, use_flash_attn=False, precision="exact", train_backend="composite"):
+                 dim_hidden=512, dropout=0.2, use_flash_attn=False, precision="exact", train_backend="composite", head_dim_training=False):
         super().__init__()
         assert train_backend in TRAIN_BACKENDS, f"train_backend must be one of {TRAIN_BACKENDS}"
         self.train_backend = train_backend
+        self.head_dim_training = head_dim_training      # True: train_backend="hip" takes dim_head 32 / 128 too (else: the composite, as before)
         self.dropout_seed = None                # train_backend="hip": an int64 tensor [1] replaces the per-pass draw of the attention dropout seed
         if kernel_size % 2 == 0:
             raise ValueError(f"kernel_size must be odd: Conv1d(padding=k // 2) with an even k ({kernel_size}) changes the length")

@@ -35,7 +35,7 @@ class _ConvStack(PackedCache):
 
 class SpeechPromptEncoder(nn.Module):
     def __init__(self, dim_codebook, dims: Tuple[int, ...] = (256, 2048, 2048, 2048, 2048, 512, 512, 512), *, depth=6, heads=8,
-                 dim_head=64, dropout=0.2, kernel_size=9, padding=4, use_flash_attn=True, precision="exact", train_backend="composite"):
+                 dim_head=64, dropout=0.2, kernel_size=9, padding=4, use_flash_attn=True, precision="exact", train_backend="composite", head_dim_training=False):
         super().__init__()
         assert train_backend in TRAIN_BACKENDS, f"train_backend must be one of {TRAIN_BACKENDS}"
         self.train_backend = train_backend
@@ -49,7 +49,7 @@ class SpeechPromptEncoder(nn.Module):
         mods.append(_NoParams())
         self.conv = nn.Sequential(*mods)                      # same indices as the reference Sequential (Rearrange, conv, SiLU, ...)
         self.transformer = Transformer(dim=dims[-1], depth=depth, heads=heads, dim_head=dim_head, dropout=dropout,
-                                       use_flash=use_flash_attn, precision=precision, train_backend=train_backend)
+                                       use_flash=use_flash_attn, precision=precision, train_backend=train_backend, head_dim_training=head_dim_training)
         self._stack = _ConvStack()
 
     def forward(self, x, *, lens=None):
@@ -111,7 +111,7 @@ class SpeechPromptEncoder(nn.Module):
 
 class PhonemeEncoder(nn.Module):
     def __init__(self, *, tokenizer=None, num_tokens=None, dim=512, dim_hidden=512, kernel_size=9, depth=6, dim_head=64, heads=8,
-                 conv_dropout=0.2, attn_dropout=0., use_flash=False, precision="exact", train_backend="composite"):
+                 conv_dropout=0.2, attn_dropout=0., use_flash=False, precision="exact", train_backend="composite", head_dim_training=False):
         super().__init__()
         assert train_backend in TRAIN_BACKENDS, f"train_backend must be one of {TRAIN_BACKENDS}"
         self.train_backend = train_backend
@@ -125,7 +125,7 @@ class PhonemeEncoder(nn.Module):
         self.kernel_size, self.dim_hidden, self.precision, self.conv_dropout = kernel_size, dim_hidden, precision, conv_dropout
         self.conv = nn.Sequential(_NoParams(), nn.Conv1d(dim, dim_hidden, kernel_size), _NoParams(), _NoParams(), _NoParams())
         self.transformer = Transformer(dim=dim_hidden, depth=depth, dim_head=dim_head, heads=heads, dropout=attn_dropout,
-                                       use_flash=use_flash, precision=precision, train_backend=train_backend)
+                                       use_flash=use_flash, precision=precision, train_backend=train_backend, head_dim_training=head_dim_training)
         self._stack = _ConvStack()
 
     def forward(self, x, mask=None):

@@ -645,6 +645,7 @@ class Model(HipDenoiserMixin, nn.Module):
         condition_on_prompt=False,
         precision="exact",
         ragged_training=False,
+        head_dim_training=False,
     ):
         super().__init__()
         self.dim = dim
@@ -717,6 +718,7 @@ class Model(HipDenoiserMixin, nn.Module):
         self.train_backend = "hip"                    # "composite": the PyTorch composite also on the GPU (A/B, tests)
         self.train_precision = "exact"                # "mixed": half product + fp8 correction terms under a loss scale (training/passes.py `_Scale`)
         self.ragged_training = ragged_training        # True: forward(lens=) under autograd trains on a ragged batch (else it raises)
+        self.head_dim_training = head_dim_training    # True: dim_head 32 / 128 train on the HIP kernels too (else: the composite, as before)
         self._hip_init(dict(dim=dim, depth=depth, dim_head=dim_head, heads=heads, ff_mult=ff_mult, wavenet_layers=wavenet_layers,
                             wavenet_stacks=wavenet_stacks, dim_cond_mult=dim_cond_mult, condition_on_prompt=condition_on_prompt,
                             dim_prompt=dim_prompt, num_latents_m=num_latents_m, resampler_depth=resampler_depth), precision)

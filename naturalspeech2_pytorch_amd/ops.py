@@ -248,7 +248,9 @@ def _attention_fwd(q: Planes, q_col0, k: Planes, k_col0, vt_hi, vt_lo, vt_ld, B,
     device addresses of the transposed value planes; o_precision: the format of o when it is not the operands' (0 = `precision`);
     key_mask: uint8 [B, Nk] on the device; drop = (p, seed tensor on the device, call index) or None; key_lens: int32 [B] on the
     device, the call then goes through ns2_attention_fwd_lens (include/ns2hip_ragged.h); train_lens: int32 [B] on the device, the
-    utterances' lengths of a ragged TRAINING batch (with want_lse): ns2_attention_train_fwd_lens (include/ns2hip_ragged_train.h)."""
+    utterances' lengths of a ragged TRAINING batch (with want_lse): ns2_attention_train_fwd_lens (include/ns2hip_ragged_train.h).
+    want_lse at a head_dim other than 64 -- the training forward at head dims 32 / 128 -- goes through ns2_attention_train_fwd_hd
+    (include/ns2hip_head_dim_train.h), with or without train_lens."""
     o = _out_planes(B * Nq, H * head_dim, q.device, o_precision or precision)
     lse = torch.empty(B, H, Nq, dtype=torch.float32, device=q.device) if want_lse else None
     p, seed, call = drop if drop is not None else (0.0, None, 0)
@@ -256,7 +258,9 @@ def _attention_fwd(q: Planes, q_col0, k: Planes, k_col0, vt_hi, vt_lo, vt_ld, B,
                       vt_hi=vt_hi, vt_lo=vt_lo, vt_ld=vt_ld, o_hi=o.hi, o_lo=o.lo, ldo=o.ld, B=B, H=H, Nq=Nq, Nk=Nk, scale=scale,
                       head_dim=head_dim, precision=precision, o_precision=o_precision, key_mask=_p(key_mask), lse=_p(lse),
                       dropout_p=p, dropout_seed=_p(seed), dropout_call=call)
-    if train_lens is not None:
+    if want_lse and head_dim != 64:
+        check(_lib.load().ns2_attention_train_fwd_hd(ctypes.byref(a), _p(train_lens), _stream()), "ns2_attention_train_fwd_hd")
+    elif train_lens is not None:
         check(_lib.load().ns2_attention_train_fwd_lens(ctypes.byref(a), train_lens.data_ptr(), _stream()), "ns2_attention_train_fwd_lens")
     elif key_lens is not None:
         check(_lib.load().ns2_attention_fwd_lens(ctypes.byref(a), key_lens.data_ptr(), _stream()), "ns2_attention_fwd_lens")

@@ -43,6 +43,11 @@ the training forward and of the backward kernel, which write exact zeros from th
 selected to 0, which zeroes the cotangent there.  Every gradient row of the padding is then an exact 0, so the weight-gradient GEMMs,
 the bias sums and the FiLM partial sums need no lengths.
 
+Head dims 32 and 128 (`head_dim_training=True` on `Model`, `compat.HipBackedModel`, `Transformer`, the encoders, `DurationPitchPredictor`;
+include/ns2hip_head_dim_train.h): the three `*_unsupported_reason` functions then accept `dim_head` 32 and 128, and the passes
+hand `dim_head` to every `AttnFn` (`functions.attn_apply`), which hands it to `HipBackend.attention*` only when it is not 64.  Without the
+switch such a module trains on the composite, as before.
+
 `Backend` is the seam the CPU tests use: `tests/emu_backend.py` restates every backend call with plain torch ops on CPU, so the
 chain rule, tap flips, shifts and layouts of THIS package are checked against torch autograd without a GPU; the kernels behind
 `HipBackend` are checked one by one and end to end on the MI355X (`tests/test_backward_gpu.py`).

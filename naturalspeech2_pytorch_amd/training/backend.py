@@ -80,19 +80,19 @@ class HipBackend:
         check(self.lib.ns2_geglu_fwd(pre.data_ptr(), pre.stride(0), M, f, out.hi, out.lo, out.ld, self.prec, _stream()), "ns2_geglu_fwd")
         return out
 
-    def attention(self, q, q_col0, k, k_col0, vt, B, H, Nq, Nk, lens=None):
+    def attention(self, q, q_col0, k, k_col0, vt, B, H, Nq, Nk, lens=None, head_dim=64):
         """bf16 x3 products on bf16 operands; the output o (the out-projection's operand) in the GEMM format.  lens: int32 [B] on the
         device, the utterances' lengths of a ragged batch (self-attention; include/ns2hip_ragged_train.h): rows of o from a length on are
-        zero bits, their lse +inf"""
-        return ops._attention_fwd(q, q_col0, k, k_col0, vt.ptr(), vt.ptr() + 64, vt.ld, B, H, Nq, Nk, 0.125, 3, o_precision=self.prec,
-                                  want_lse=True, train_lens=lens)
+        zero bits, their lse +inf.  head_dim 32 / 64 / 128 (include/ns2hip_head_dim_train.h): head h at columns col0 + head_dim h"""
+        return ops._attention_fwd(q, q_col0, k, k_col0, vt.ptr(), vt.ptr() + 64, vt.ld, B, H, Nq, Nk, head_dim ** -0.5, 3, head_dim=head_dim,
+                                  o_precision=self.prec, want_lse=True, train_lens=lens)
 
-    def attention_masked(self, q, q_col0, k, k_col0, vt, B, H, Nq, Nk, kmask=None, drop=None):
+    def attention_masked(self, q, q_col0, k, k_col0, vt, B, H, Nq, Nk, kmask=None, drop=None, head_dim=64):
         """`attention` with a key-padding mask (uint8 [B, Nk], 1 = attend) and / or dropout on P (`drop` = (p, seed tensor on the device, call
         index): csrc/dropout_keep.h) -- the attention of the conditioning encoders' training pass"""
         assert self.prec == 3, "the encoders train in the exact arithmetic"
-        return ops._attention_fwd(q, q_col0, k, k_col0, vt.ptr(), vt.ptr() + 64, vt.ld, B, H, Nq, Nk, 0.125, 3, o_precision=self.prec,
-                                  key_mask=kmask, want_lse=True, drop=drop)
+        return ops._attention_fwd(q, q_col0, k, k_col0, vt.ptr(), vt.ptr() + 64, vt.ld, B, H, Nq, Nk, head_dim ** -0.5, 3, head_dim=head_dim,
+                                  o_precision=self.prec, key_mask=kmask, want_lse=True, drop=drop)
 
     def dropout_keep_mask(self, seed, call, p, B, H, Nq, Nk):
         """debugging / tests: the keep mask the training attention kernels apply for these arguments, uint8 [B, H, Nq, Nk]"""
@@ -354,8 +354,12 @@ class HipBackend:
             check(self.lib.ns2_reduce_slices(gpart.data_ptr(), 1, B * S, d, dgamma.data_ptr(), 0, _stream()), "ns2_reduce_slices")
         return dx, dcond, dgamma
 
-    def attention_delta(self, do, o, B, H, Nq):
+    def attention_delta(self, do, o, B, H, Nq, head_dim=64):
         delta = torch.empty(B, H, Nq, dtype=torch.float32, device=do.device)
+        if head_dim != 64:
+            check(self.lib.ns2_attention_delta_hd(do.data_ptr(), do.stride(0), o.hi, o.lo, o.ld, B, H, Nq, head_dim, delta.data_ptr(), o.precision,
+                                                  _stream()), "ns2_attention_delta_hd")
+            return delta
         check(self.lib.ns2_attention_delta(do.data_ptr(), do.stride(0), o.hi, o.lo, o.ld, B, H, Nq, delta.data_ptr(), o.precision, _stream()),
               "ns2_attention_delta")
         return delta
@@ -369,12 +373,12 @@ class HipBackend:
         self.attention_bwd(*args, **kw, kmask=kmask, drop=drop)
 
     def attention_bwd(self, q, q_col0, k, k_col0, v, v_col0, do_row, lse, delta, B, H, Nq, Nk, dq=None, dkv=None, planes=None, kmask=None,
-                      drop=None, lens=None):
+                      drop=None, lens=None, head_dim=64):
         """dq: (fp32 tensor [B*Nq, ld], col0) or None; dkv: (tensor [B*Nk, ld], k col0, v col0) or None;
         planes: (operand planes [B*N, ld], dq col0, dk col0, dv col0) -- self attention: the three gradients leave the kernels as the
         operand of the q | k | v projection's dgrad / wgrad GEMMs instead of fp32 + a conversion pass;
         kmask / drop: what the forward (`attention_masked`) got, None = neither; lens: what the forward (`attention`) got -- gradient rows
-        from a length on are written as zeros"""
+        from a length on are written as zeros; head_dim: what the forward got (other than 64: ns2_attention_bwd_hd)"""
         a = _lib.AttnBwdArgs()
         a.q_hi, a.q_lo, a.ldq, a.q_col0 = q.hi, q.lo, q.ld, q_col0
         a.k_hi, a.k_lo, a.ldk, a.k_col0 = k.hi, k.lo, k.ld, k_col0
@@ -390,11 +394,13 @@ class HipBackend:
             gp, a.dq_col0, a.dk_col0, a.dv_col0 = planes
             assert gp.precision == self.prec
             a.gp_hi, a.gp_lo, a.gp_ld, a.gp_precision, a.gp_q, a.gp_kv = gp.hi, gp.lo, gp.ld, self.prec, 1, 1
-        a.B, a.H, a.Nq, a.Nk, a.scale = B, H, Nq, Nk, 0.125
+        a.B, a.H, a.Nq, a.Nk, a.scale = B, H, Nq, Nk, head_dim ** -0.5
         a.key_mask = _p(kmask)
         if drop is not None:
             a.dropout_p, a.dropout_seed, a.dropout_call = drop[0], _p(drop[1]), drop[2]
-        if lens is not None:
+        if head_dim != 64:
+            check(self.lib.ns2_attention_bwd_hd(ctypes.byref(a), head_dim, _p(lens), _stream()), "ns2_attention_bwd_hd")
+        elif lens is not None:
             check(self.lib.ns2_attention_bwd_lens(ctypes.byref(a), lens.data_ptr(), _stream()), "ns2_attention_bwd_lens")
         else:
             check(self.lib.ns2_attention_bwd(a, _stream()), "ns2_attention_bwd")

@@ -2,13 +2,13 @@
 Functions of functions.py, in the exact arithmetic like the conditioning encoders (encoder_pass.py)."""
 import torch
 
-from .functions import AttnFn, EmbeddingFn, GemmFn, GroupNormSiluFn, RmsNormFn, RowDotReluFn, SiluFn, _c
+from .functions import HEAD_DIMS_TRAIN, attn_apply, train_head_dim, EmbeddingFn, GemmFn, GroupNormSiluFn, RmsNormFn, RowDotReluFn, SiluFn, _c
 from .passes import TRAIN_PRECISIONS, training_pass
 
 _EXACT = TRAIN_PRECISIONS["exact"]
 
 
-def _trunk_train(tr, h, prompts, b, n, drop, call0):
+def _trunk_train(tr, h, prompts, b, n, drop, call0, head_dim=64):
     """one `DurationPitchPredictorTrunk` (NS2:456-466): h [b n, d] fp32, prompts [b, n_p, d] -> [b n].  `drop` = (p, seed) or None;
     the attention of layer i is dropout call `call0 + i`"""
     d, k = tr.dim, tr.kernel_size
@@ -27,8 +27,8 @@ def _trunk_train(tr, h, prompts, b, n, drop, call0):
         # torch's cat hands the first n rows of the context gradient back to it, the rest to `prompts`
         xn = RmsNormFn.apply(_c(h), norm.gamma)
         ctxt = torch.cat((xn.reshape(b, n, d), prompts), dim=1).reshape(b * (n + n_p), d)
-        h = AttnFn.apply(xn, None, ctxt, attn.to_q.weight, attn.to_kv.weight, attn.to_out.weight, n, tr.heads, n + n_p, None, None,
-                         (drop[0], drop[1], call0 + li) if drop is not None else None, _c(h))
+        h = attn_apply(xn, None, ctxt, attn.to_q.weight, attn.to_kv.weight, attn.to_out.weight, n, tr.heads, n + n_p, None, None,
+                       (drop[0], drop[1], call0 + li) if drop is not None else None, _c(h), head_dim=head_dim)
     head = tr.to_pred[0]
     return RowDotReluFn.apply(_c(h), head.weight, head.bias)
 
@@ -60,14 +60,18 @@ def duration_pitch_forward_train(dp, x, prompts):
             dp.last_dropout_seed = seed
             drop = (p, seed)
         depth = len(trunks[0].layers)
-        return tuple(_trunk_train(tr, h, pr, b, n, drop, ti * depth).reshape(b, n).to(dtype) for ti, tr in enumerate(trunks))
+        hd = train_head_dim(dp, trunks[0].dim_head)
+        return tuple(_trunk_train(tr, h, pr, b, n, drop, ti * depth, hd).reshape(b, n).to(dtype) for ti, tr in enumerate(trunks))
 
 
 def duration_pitch_unsupported_reason(dp):
     """None when `duration_pitch_forward_train` can run `dp`, else why not: the caller falls back to the composite, as `Model` and the
     encoders do"""
     tr = dp.to_pitch_pred
-    if tr.dim_head != 64:
+    if getattr(dp, "head_dim_training", False):
+        if tr.dim_head not in HEAD_DIMS_TRAIN:
+            return f"dim_head={tr.dim_head} (the HIP training attention kernels have head dims 32, 64 and 128)"
+    elif tr.dim_head != 64:
         return f"dim_head={tr.dim_head} (the HIP attention backward kernels have a head dim of 64)"
     if tr.dim % 32:
         return f"dim_hidden={tr.dim} is not a multiple of 32"

@@ -4,7 +4,7 @@ has left its scaled domain (`_ScaleOut` on prompt / cond in model_pass.py)."""
 import torch
 import torch.nn.functional as F
 
-from .functions import AttnFn, EmbeddingFn, FeedForwardFn, GemmFn, RmsNormFn, SiluFn, _c
+from .functions import HEAD_DIMS_TRAIN, attn_apply, train_head_dim, EmbeddingFn, FeedForwardFn, GemmFn, RmsNormFn, SiluFn, _c
 from .passes import TRAIN_PRECISIONS, training_pass
 
 _EXACT = TRAIN_PRECISIONS["exact"]
@@ -38,8 +38,8 @@ def _transformer_train(tr, h, b, n, mask):
         assert seed.dtype == torch.int64 and seed.numel() == 1 and seed.device == h.device
         tr.last_dropout_seed = seed
     for li, (norm1, attn, norm2, ff) in enumerate(tr.layers):
-        h = AttnFn.apply(_c(h), None, None, attn.to_q.weight, attn.to_kv.weight, attn.to_out.weight, n, tr.heads, 0, norm1.gamma, km,
-                         (p, seed, li) if p > 0 else None)
+        h = attn_apply(_c(h), None, None, attn.to_q.weight, attn.to_kv.weight, attn.to_out.weight, n, tr.heads, 0, norm1.gamma, km,
+                       (p, seed, li) if p > 0 else None, head_dim=train_head_dim(tr, tr.dim_head))
         l1, l2 = getattr(ff, "0"), getattr(ff, "2")
         h = FeedForwardFn.apply(_c(h), None, l1.weight, l1.bias, None, None, l2.weight, l2.bias, n, norm2.gamma)
     if hasattr(tr.norm, "gamma"):
@@ -83,7 +83,10 @@ def encoder_unsupported_reason(module, mask=None):
     """None when the `*_forward_train` functions above can run `module` (a `Transformer`, `PhonemeEncoder` or `SpeechPromptEncoder`) with
     this key mask, else why not -- the counterpart of `unsupported_reason` for `Model`: the caller falls back to the composite"""
     tr = getattr(module, "transformer", module)
-    if tr.dim_head != 64:
+    if getattr(tr, "head_dim_training", False):
+        if tr.dim_head not in HEAD_DIMS_TRAIN:
+            return f"dim_head={tr.dim_head} (the HIP training attention kernels have head dims 32, 64 and 128)"
+    elif tr.dim_head != 64:
         return f"dim_head={tr.dim_head} (the HIP attention backward kernels have a head dim of 64)"
     if tr.dim % 32:
         return f"dim={tr.dim} is not a multiple of 32"

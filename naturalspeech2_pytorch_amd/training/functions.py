@@ -182,15 +182,19 @@ class AttnFn(torch.autograd.Function):
     the q path's gradient only and `resid` the incoming one.  Absent by default, like the others.
     `lens` -- int32 [B] on the device, the utterances' lengths of a ragged batch (self-attention only, without kmask / drop;
     include/ns2hip_ragged_train.h): keys stop at the length, and the rows of o and of dq | dk | dv from the length on are exact zeros.
-    The kernels alone read it.  Absent by default: same kernels, same bits."""
+    The kernels alone read it.  Absent by default: same kernels, same bits.
+    `head_dim` -- 32 or 128 instead of the heads of 64 (include/ns2hip_head_dim_train.h; `head_dim_training`).  The backend is handed it
+    only when it is not 64, as it is handed `lens` only when there are lengths: same calls, same kernels, same bits by default."""
 
     @staticmethod
-    def forward(ctx, h, film, ctxt, wq, wkv, wout, seq_len, heads, ctx_len, gamma=None, kmask=None, drop=None, resid=None, lens=None):
+    def forward(ctx, h, film, ctxt, wq, wkv, wout, seq_len, heads, ctx_len, gamma=None, kmask=None, drop=None, resid=None, lens=None,
+                head_dim=64):
         assert resid is None or (film is None and gamma is None)
         assert lens is None or (ctxt is None and kmask is None and drop is None), "lens: the plain self-attention only"
         bk = _begin(ctx)
         M, d = h.shape
-        B, a = M // seq_len, heads * 64
+        B, a = M // seq_len, heads * head_dim
+        hd = {} if head_dim == 64 else {"head_dim": head_dim}
         xn = _norm_in_front(bk, h, seq_len, film, gamma)
         if ctxt is None:                                                    # self attention: one GEMM for q | k | v
             wqkv = bk.pack(("qkv", id(wq), id(wkv)), (wq, wkv), lambda: torch.cat((wq.detach(), wkv.detach()), 0),
@@ -204,15 +208,15 @@ class AttnFn(torch.autograd.Function):
             k, v, qc, kc, vc, Nk = kv, kv, 0, 0, a, ctx_len
         vt = bk.transpose(v, vc, a, Nk, per_batch=True)
         if lens is not None:
-            o, lse = bk.attention(q, qc, k, kc, vt, B, heads, seq_len, Nk, lens=lens)
+            o, lse = bk.attention(q, qc, k, kc, vt, B, heads, seq_len, Nk, lens=lens, **hd)
         elif kmask is None and drop is None:
-            o, lse = bk.attention(q, qc, k, kc, vt, B, heads, seq_len, Nk)
+            o, lse = bk.attention(q, qc, k, kc, vt, B, heads, seq_len, Nk, **hd)
         else:
-            o, lse = bk.attention_masked(q, qc, k, kc, vt, B, heads, seq_len, Nk, kmask=kmask, drop=drop)
+            o, lse = bk.attention_masked(q, qc, k, kc, vt, B, heads, seq_len, Nk, kmask=kmask, drop=drop, **hd)
         y = bk.gemm_f32(_fwd_pack(bk, wout), o, resid=h if resid is None else resid)
         ctx.save_for_backward(h, film, wq, wkv, wout, lse, gamma)
         ctx.pl, ctx.cfg, ctx.md, ctx.lens = (xn, q, k, v, o, cp), (seq_len, heads, Nk, qc, kc, vc, ctxt is not None), (kmask, drop), lens
-        ctx.own_resid = resid is None
+        ctx.own_resid, ctx.hd = resid is None, hd
         return y[:, :d]
 
     @staticmethod
@@ -223,20 +227,22 @@ class AttnFn(torch.autograd.Function):
         seq_len, heads, Nk, qc, kc, vc, cross = ctx.cfg
         kmask, drop = ctx.md
         M, d = h.shape
-        B, a = M // seq_len, heads * 64
+        hd = ctx.hd
+        B, a = M // seq_len, heads * hd.get("head_dim", 64)
         dy = _rowmajor(dy)
         ng = ctx.needs_input_grad                                           # (h, film, ctxt, wq, wkv, wout, ...)
         if ctx.lens is not None:
             def attention_bwd(*args, **kw):
-                bk.attention_bwd(*args, lens=ctx.lens, **kw)
+                bk.attention_bwd(*args, lens=ctx.lens, **hd, **kw)
         elif kmask is None and drop is None:
-            attention_bwd = bk.attention_bwd
+            def attention_bwd(*args, **kw):
+                bk.attention_bwd(*args, **hd, **kw)
         else:
             def attention_bwd(*args, **kw):
-                bk.attention_bwd_masked(*args, kmask=kmask, drop=drop, **kw)
+                bk.attention_bwd_masked(*args, kmask=kmask, drop=drop, **hd, **kw)
         dy_row, dwout, _ = _grads(bk, dy, d, o, a, need_w=ng[5])
         do = bk.gemm_f32(_bwd_pack(bk, wout), dy_row)                       # [M, a]
-        delta = bk.attention_delta(do, o, B, heads, seq_len)
+        delta = bk.attention_delta(do, o, B, heads, seq_len, **hd)
         # (the backward kernels form K^T, Q^T and dO^T inside the CU: LDS transpose reads of the row-major tiles)
         do_row, _, _ = bk.grad_prep(do, a, want_row=True, attn=True)
         if not cross:
@@ -271,7 +277,23 @@ class AttnFn(torch.autograd.Function):
         else:
             dh, dfilm, dgamma, dresid = dxn[:, :d], None, None, dy
         dfilm, dwq, dwkv, dwout, dgamma = _un(ctx, dfilm, dwq, dwkv, dwout, dgamma)
-        return dh, dfilm, dctx, dwq, dwkv, dwout, None, None, None, dgamma, None, None, dresid, None
+        return dh, dfilm, dctx, dwq, dwkv, dwout, None, None, None, dgamma, None, None, dresid, None, None
+
+
+def attn_apply(*args, head_dim=64):
+    """`AttnFn.apply(*args)`; a head dim other than 64 (`head_dim_training`) is appended behind the optional arguments, 64 leaves the
+    call exactly what it was"""
+    if head_dim == 64:
+        return AttnFn.apply(*args)
+    return AttnFn.apply(*args, *([None] * (14 - len(args))), head_dim)
+
+
+def train_head_dim(owner, dim_head):
+    """the head dim a training pass hands to `AttnFn`: `dim_head` where `owner` has `head_dim_training` on, else the kernels' 64"""
+    return dim_head if getattr(owner, "head_dim_training", False) else 64
+
+
+HEAD_DIMS_TRAIN = (32, 64, 128)                 # what `head_dim_training=True` accepts (include/ns2hip_head_dim_train.h)
 
 
 class FeedForwardFn(torch.autograd.Function):

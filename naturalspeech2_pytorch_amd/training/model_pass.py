@@ -4,11 +4,11 @@ import math
 import torch
 import torch.nn.functional as F
 
-from .functions import AttnFn, CondProjectionsFn, FeedForwardFn, GemmFn, NormLinearFn, RmsNormFn, WavenetBlockFn, _c, _lin
+from .functions import HEAD_DIMS_TRAIN, attn_apply, train_head_dim, CondProjectionsFn, FeedForwardFn, GemmFn, NormLinearFn, RmsNormFn, WavenetBlockFn, _c, _lin
 from .passes import TRAIN_PRECISIONS, _enter, _ScaleIn, training_pass
 
 
-def _resampler(pr, prompt, heads):
+def _resampler(pr, prompt, heads, head_dim=64):
     """PerceiverResampler (NS2:532-579) on the Functions of functions.py: per layer latents += Attention(latents, context = cat(latents,
     proj(prompt))) and latents += FeedForward(latents) (no norms in front, no conv), then RMSNorm * gamma.  Round 4 ran this part of
     the conditioned model's graph as the PyTorch composite (0.2 % of the FLOPs, but the one piece of `Model`'s backward on torch ops)."""
@@ -22,7 +22,7 @@ def _resampler(pr, prompt, heads):
     lat = _enter(pr.latents)[None].expand(b, -1, -1).reshape(b * Lm, d)      # (a copy: its gradient sums over the batch into pr.latents)
     for attn, ff in pr.layers:
         context = torch.cat((lat.reshape(b, Lm, d), px), dim=1).reshape(b * (Lm + n_p), d)     # cross_attn_include_queries, NS2:1060-1061
-        lat = AttnFn.apply(_c(lat), None, context, attn.to_q.weight, attn.to_kv.weight, attn.to_out.weight, Lm, heads, Lm + n_p)
+        lat = attn_apply(_c(lat), None, context, attn.to_q.weight, attn.to_kv.weight, attn.to_out.weight, Lm, heads, Lm + n_p, head_dim=head_dim)
         l1, l2 = getattr(ff, "0"), getattr(ff, "2")
         lat = FeedForwardFn.apply(_c(lat), None, l1.weight, l1.bias, None, None, l2.weight, l2.bias, Lm)
     return RmsNormFn.apply(_c(lat), pr.norm.gamma).reshape(b, Lm, d)
@@ -68,6 +68,7 @@ def _forward_train(m, x, times, prompt, cond, cond_drop_prob, lens=None, keep=No
     M = b * n
     p = m.cond_drop_prob if cond_drop_prob is None else cond_drop_prob
     heads = m._hip_cfg["heads"]
+    hd = train_head_dim(m, m._hip_cfg["dim_head"])                           # (64 unless `head_dim_training`)
     # ---- rows = batch entries: time embedding and every conditioning projection (PyTorch ops, see the package docstring)
     w = getattr(m.to_time_cond, "0").weights
     tt = times.float()[:, None]
@@ -91,7 +92,7 @@ def _forward_train(m, x, times, prompt, cond, cond_drop_prob, lens=None, keep=No
         t = torch.cat((t, pc), dim=-1)
         # (`prompt` and `cond` come from trainable modules upstream -- the prompt / phoneme encoders, NS2:1635 -- so their gradients
         # leave the scaled domain like x's: ADVICE r5)
-        c = torch.where(dm[:, None, None], _enter(m.null_prompt_tokens), _resampler(m.perceiver_resampler, _enter(prompt.float()), heads))   # [b, Lm, d]
+        c = torch.where(dm[:, None, None], _enter(m.null_prompt_tokens), _resampler(m.perceiver_resampler, _enter(prompt.float()), heads, hd))   # [b, Lm, d]
         # cond_to_model_dim: 1x1 conv over channel-first cond (NS2:978) = a Linear over the frames
         n_c = cond.shape[-1]
         if keep is not None:
@@ -140,14 +141,15 @@ def _forward_train(m, x, times, prompt, cond, cond_drop_prob, lens=None, keep=No
     for layer in m.transformer.layers:
         a1 = getattr(layer, "1")
         if lens is None:
-            h = AttnFn.apply(_c(h), film_of(getattr(layer, "0").to_gamma_beta), None, a1.to_q.weight, a1.to_kv.weight, a1.to_out.weight, n, heads, 0)
+            h = attn_apply(_c(h), film_of(getattr(layer, "0").to_gamma_beta), None, a1.to_q.weight, a1.to_kv.weight, a1.to_out.weight, n, heads, 0,
+                           head_dim=hd)
         else:
-            h = AttnFn.apply(_c(h), film_of(getattr(layer, "0").to_gamma_beta), None, a1.to_q.weight, a1.to_kv.weight, a1.to_out.weight, n, heads, 0,
-                             None, None, None, None, lens)
+            h = attn_apply(_c(h), film_of(getattr(layer, "0").to_gamma_beta), None, a1.to_q.weight, a1.to_kv.weight, a1.to_out.weight, n, heads, 0,
+                           None, None, None, None, lens, head_dim=hd)
         if m.condition_on_prompt:
             a3 = getattr(layer, "3")
-            h = AttnFn.apply(_c(h), film_of(getattr(layer, "2").to_gamma_beta), c2, a3.to_q.weight, a3.to_kv.weight, a3.to_out.weight, n,
-                             heads, c.shape[1])
+            h = attn_apply(_c(h), film_of(getattr(layer, "2").to_gamma_beta), c2, a3.to_q.weight, a3.to_kv.weight, a3.to_out.weight, n,
+                           heads, c.shape[1], head_dim=hd)
         ff = getattr(layer, "5")
         l1, cv, l2 = getattr(ff, "0"), getattr(getattr(ff, "2"), "1"), getattr(ff, "3")
         h = FeedForwardFn.apply(_c(h), film_of(getattr(layer, "4").to_gamma_beta), l1.weight, l1.bias, cv.weight, cv.bias, l2.weight, l2.bias, n)
@@ -165,10 +167,14 @@ def unsupported_reason(m):
     """None when `model_forward_train` can run `m`, else why not.  The Functions are written for what the inference executor
     accepts (ns2_model_create): heads of 64 (q / k / v column offsets, the attention kernels' head dim, scale 1/8), dim a multiple
     of 32 (whole 32-column lines per operand row), fp32 parameters (the packs and the returned gradients are fp32).  Anything else
-    must not reach the kernels (a `dim_head=32` model would read past its packed qkv planes)."""
+    must not reach the kernels (a `dim_head=32` model would read past its packed qkv planes).  A model with
+    `head_dim_training = True` trains at dim_head 32 and 128 too (include/ns2hip_head_dim_train.h: the passes hand dim_head to AttnFn)."""
     cfg = m._hip_cfg
-    if cfg["dim_head"] != 64:
-        return f"dim_head={cfg['dim_head']} (the HIP attention kernels have a head dim of 64)"
+    if getattr(m, "head_dim_training", False):
+        if cfg["dim_head"] not in HEAD_DIMS_TRAIN:
+            return f"dim_head={cfg['dim_head']} (the HIP training attention kernels have head dims 32, 64 and 128)"
+    elif cfg["dim_head"] != 64:
+        return f"dim_head={cfg['dim_head']} (the HIP attention backward has a head dim of 64 unless the model is built with head_dim_training=True)"
     if cfg["dim"] % 32:
         return f"dim={cfg['dim']} is not a multiple of 32"
     for name, p in m.named_parameters():

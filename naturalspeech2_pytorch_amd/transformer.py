@@ -58,10 +58,11 @@ def use_hip_training(module, x, mask=None):
 
 class Transformer(nn.Module):
     def __init__(self, dim, *, depth, causal=False, dim_head=64, heads=8, use_flash=False, dropout=0., ff_mult=4,
-                 final_norm=False, precision="exact", train_backend="composite"):
+                 final_norm=False, precision="exact", train_backend="composite", head_dim_training=False):
         super().__init__()
         assert train_backend in TRAIN_BACKENDS, f"train_backend must be one of {TRAIN_BACKENDS}"
         self.train_backend = train_backend
+        self.head_dim_training = head_dim_training      # True: train_backend="hip" takes dim_head 32 / 128 too (else: the composite, as before)
         self.dropout_seed = None                # train_backend="hip": an int64 tensor [1] replaces the per-pass draw of the attention dropout seed
         assert dim_head in (32, 64, 128), "the HIP attention kernel is built for head dims 32, 64 (the reference default) and 128"
         self.dim, self.depth, self.heads, self.causal, self.dropout, self.dim_head = dim, depth, heads, causal, dropout, dim_head
