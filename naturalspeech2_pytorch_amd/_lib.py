@@ -1,7 +1,7 @@
 """ctypes binding of libns2hip.so, derived from its C ABI: include/ns2hip.h (and include/ns2hip_optim.h, the optimizer step, and
 include/ns2hip_pitch.h, the pitch extractor, include/ns2hip_ragged.h, ragged batches, include/ns2hip_ragged_front.h, ragged prompts
-and text, include/ns2hip_ragged_train.h, ragged training batches, and include/ns2hip_head_dim_train.h, training at head dims 32 and
-128, each into tables of its own) is parsed once, at import.
+and text, include/ns2hip_ragged_train.h, ragged training batches, include/ns2hip_head_dim_train.h, training at head dims 32 and 128, and
+include/ns2hip_ragged_audio.h, ragged raw audio, each into tables of its own) is parsed once, at import.
 
 The HIP library is the product: importing this module FAILS LOUDLY when the header or the shared object is missing or the
 library does not export the full ABI -- there is no CPU / PyTorch fallback for the hot path.
@@ -33,6 +33,7 @@ RAGGED_HEADER_PATH = os.path.join(_HERE, "..", "include", "ns2hip_ragged.h")   #
 FRONT_HEADER_PATH = os.path.join(_HERE, "..", "include", "ns2hip_ragged_front.h")   # ... through the front-end: likewise
 RAGGED_TRAIN_HEADER_PATH = os.path.join(_HERE, "..", "include", "ns2hip_ragged_train.h")   # ... in the training pass: likewise
 HEAD_DIM_TRAIN_HEADER_PATH = os.path.join(_HERE, "..", "include", "ns2hip_head_dim_train.h")   # training at head dims 32 / 128: likewise
+RAGGED_AUDIO_HEADER_PATH = os.path.join(_HERE, "..", "include", "ns2hip_ragged_audio.h")   # lengths in mel, pitch and the RVQ term: likewise
 
 
 class Ns2Error(RuntimeError):
@@ -146,6 +147,11 @@ if not os.path.exists(HEAD_DIM_TRAIN_HEADER_PATH):
 with open(HEAD_DIM_TRAIN_HEADER_PATH) as _f:                     # (the argument blocks: c_void_p here too)
     _, _, HEAD_DIM_TRAIN_SIGNATURES = parse_header(_f.read())
 
+if not os.path.exists(RAGGED_AUDIO_HEADER_PATH):
+    raise Ns2Error(f"{RAGGED_AUDIO_HEADER_PATH} not found: the binding is derived from the header, it ships with the package's source tree")
+with open(RAGGED_AUDIO_HEADER_PATH) as _f:
+    _, _, RAGGED_AUDIO_SIGNATURES = parse_header(_f.read())
+
 _lib = None
 
 
@@ -159,7 +165,7 @@ def load():
                        f"(or naturalspeech2_pytorch_amd/csrc/build.sh); there is no fallback path")
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in {**SIGNATURES, **OPTIM_SIGNATURES, **PITCH_SIGNATURES, **RAGGED_SIGNATURES, **FRONT_SIGNATURES,
-                              **RAGGED_TRAIN_SIGNATURES, **HEAD_DIM_TRAIN_SIGNATURES}.items():
+                              **RAGGED_TRAIN_SIGNATURES, **HEAD_DIM_TRAIN_SIGNATURES, **RAGGED_AUDIO_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -209,3 +215,8 @@ def ragged_train_header_symbols():
 def head_dim_train_header_symbols():
     """Symbols declared in include/ns2hip_head_dim_train.h"""
     return sorted(HEAD_DIM_TRAIN_SIGNATURES)
+
+
+def ragged_audio_header_symbols():
+    """Symbols declared in include/ns2hip_ragged_audio.h"""
+    return sorted(RAGGED_AUDIO_SIGNATURES)

@@ -14,6 +14,13 @@ On a GPU, `forward` runs one HIP kernel (csrc/audio_to_mel.hip: ns2_audio_to_mel
 requires grad (under autograd) take the PyTorch composite above.  The module has no parameters and no buffers: the kernel's
 tables (window, twiddles, compact filterbank) are cached per device and configuration, so `forward` makes no device -> host
 synchronisation after the first call on a device.
+
+`forward(audio, lens=)` (not in the reference) is the ragged batch: sample counts per utterance, integer [b].  Utterance i's frames
+t < T_i = 1 + lens[i] // hop_length are those of the module on `audio[i, :lens[i]]` alone -- the reflect padding mirrors about the
+utterance's own last sample, not about the end of the batch -- and frames from T_i on are exactly 0 (padding, not the -100 dB of
+silence).  On a GPU that is ns2_audio_to_mel_lens (include/ns2hip_ragged_audio.h): the lengths stay on the device, nothing reads them on
+the host, and a value outside [n_fft // 2 + 1, L] is clamped into it.  Elsewhere a composite does the same per utterance (slice, today's
+composite, zero-fill), which reads the lengths.
 """
 import math
 
@@ -95,16 +102,34 @@ class AudioToMel(nn.Module):
     def hip_supported(self) -> bool:
         return _hip_supported(self.n_fft, self.win_length, self.hop_length, self.n_mels)
 
-    def forward(self, audio: torch.Tensor) -> torch.Tensor:
-        """audio [..., L] -> [..., n_mels, 1 + L // hop_length] fp32"""
+    def forward(self, audio: torch.Tensor, lens=None) -> torch.Tensor:
+        """audio [..., L] -> [..., n_mels, 1 + L // hop_length] fp32; lens: sample counts [b] of a ragged batch [b, L] (module docstring)"""
         audio = audio.float()
         L = audio.shape[-1]
         if L <= self.n_fft // 2:
             raise ValueError(f"AudioToMel needs more than n_fft // 2 = {self.n_fft // 2} samples for the reflect padding, got {L}")
         grad = audio.requires_grad and torch.is_grad_enabled()
+        if lens is not None:
+            lens = torch.as_tensor(lens)
+            if audio.ndim != 2 or lens.dtype.is_floating_point or lens.dtype == torch.bool or lens.shape != (audio.shape[0],):
+                raise ValueError(f"AudioToMel(lens=) takes audio [b, L] and one integer sample count per utterance [b], got "
+                                 f"{list(audio.shape)} and {lens.dtype} {list(lens.shape)}")
+            if not (audio.is_cuda and not grad and self.hip_supported()):
+                return self._forward_composite_lens(audio, lens)
+            return self._forward_hip(audio, lens.to(audio.device))
         if audio.is_cuda and not grad and self.hip_supported():
             return self._forward_hip(audio)
         return self._forward_composite(audio)
+
+    def _forward_composite_lens(self, audio, lens):
+        """per utterance: slice, the composite, zero-fill (reads the lengths on the host)"""
+        L = audio.shape[-1]
+        out = audio.new_zeros(audio.shape[0], self.n_mels, 1 + L // self.hop_length)
+        for i, s in enumerate(lens.tolist()):
+            s = min(max(int(s), self.n_fft // 2 + 1), L)                # as the kernel clamps
+            mel = self._forward_composite(audio[i:i + 1, :s])
+            out[i, :, :mel.shape[-1]] = mel[0]
+        return out
 
     def _forward_composite(self, audio):
         shape = audio.shape
@@ -119,12 +144,12 @@ class AudioToMel(nn.Module):
             mel = 10.0 * torch.log10(torch.clamp(mel, min=1e-10))
         return mel.reshape(shape[:-1] + mel.shape[-2:])
 
-    def _forward_hip(self, audio):
+    def _forward_hip(self, audio, lens=None):
         shape = audio.shape
         x = audio.reshape(-1, shape[-1]).contiguous()
         T = 1 + shape[-1] // self.hop_length
         if x.shape[0] == 0:
             return audio.new_empty(shape[:-1] + (self.n_mels, T))
         p = _plan(x.device, self.n_fft, self.win_length, self.n_mels, self.sampling_rate, self.f_max)
-        mel = ops.audio_to_mel(x, self.n_fft, self.hop_length, self.n_mels, self.log, p)
+        mel = ops.audio_to_mel(x, self.n_fft, self.hop_length, self.n_mels, self.log, p, **({} if lens is None else dict(lens=lens)))
         return mel.reshape(shape[:-1] + (self.n_mels, T))

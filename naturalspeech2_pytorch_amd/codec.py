@@ -70,7 +70,14 @@ class ResidualVQCrossEntropy(nn.Module):
         -- makes the loss NaN (and that row's gradient): loud, without a synchronisation;
       * a residual that equals a code (distance 0) gives the well-defined loss and that code adds 0 to the gradient, where the composite's
         gradient of sqrt at 0 is not finite;
-      * the nearest code of a stage is decided by the fp32 scores r.e - |e|^2/2; on a near-tie either code is a valid stage result."""
+      * the nearest code of a stage is decided by the fp32 scores r.e - |e|^2/2; on a near-tie either code is a valid stage result.
+
+    `forward(x [b, n, d], indices [b, n, Q], lens=)` (not in the reference) is the ragged batch: frames per utterance, integer [b], clamped
+    into [1, n].  The loss is the mean over the utterances of each utterance's OWN loss (its cross-entropies averaged over its own
+    frames [0, lens[i])), so utterance i adds to it, and to the gradient, what it adds alone divided by b.  What x and indices hold at or
+    behind a length -- NaN, -1 -- reaches neither; quantized_out and the gradient are exact zeros there.  backend="hip" runs
+    ns2_rvq_ce_lens (include/ns2hip_ragged_audio.h; no host read, capturable); the composite selects x and indices to 0 behind the lengths
+    before use and masks the per-frame cross-entropies with a select."""
 
     def __init__(self, owner: HipRVQ, backend: str = "composite"):
         super().__init__()
@@ -78,23 +85,55 @@ class ResidualVQCrossEntropy(nn.Module):
         self._owner = [owner]              # not registered: the codebooks stay owned (and moved) by the HipRVQ
         self.backend = backend
 
-    def forward(self, x, indices):
+    def forward(self, x, indices, lens=None):
         assert self.backend in RQ_BACKENDS, f"backend must be one of {RQ_BACKENDS}"
+        if lens is not None:
+            lens = torch.as_tensor(lens)
+            if x.ndim != 3 or lens.dtype.is_floating_point or lens.dtype == torch.bool or lens.shape != (x.shape[0],):
+                raise ValueError(f"rq(lens=) takes x [b, n, d] and one integer frame count per utterance [b], got {list(x.shape)} and "
+                                 f"{lens.dtype} {list(lens.shape)}")
+            lens = lens.to(x.device)
         if self.backend == "hip":
             from . import training
             if training.rvq_ce_unsupported_reason(self, x, indices) is None:
-                return self._forward_hip(x, indices)
+                return self._forward_hip(x, indices, lens)
+        if lens is not None:
+            return self._forward_composite_lens(x, indices, lens)
         return self._forward_composite(x, indices)
 
-    def _forward_hip(self, x, indices):
+    def _forward_hip(self, x, indices, lens=None):
         from .training.functions import RvqCrossEntropyFn
         owner = self._owner[0]
         assert indices.shape[:-1] == x.shape[:-1] and indices.shape[-1] == owner.codebooks.shape[0]
         d = x.shape[-1]
         xr = x.reshape(-1, d)
+        extra = () if lens is None else (lens.to(torch.int32).contiguous(),)
         loss, quant = RvqCrossEntropyFn.apply(xr if xr.is_contiguous() else xr.contiguous(), owner.codebooks, owner._cb_norm(),
-                                              indices.reshape(-1, indices.shape[-1]))
+                                              indices.reshape(-1, indices.shape[-1]), *extra)
         return quant.reshape(x.shape), loss
+
+    def _forward_composite_lens(self, x, indices, lens):
+        cb = self._owner[0].codebooks.to(x.dtype)
+        assert indices.shape[:-1] == x.shape[:-1] and indices.shape[-1] == cb.shape[0]
+        b, n = x.shape[:2]
+        ln = lens.long().clamp(1, n)                                             # as the kernel clamps
+        keep = torch.arange(n, device=x.device)[None] < ln[:, None]             # [b, n]
+        # selects, not products: NaN and -1 may lie behind a length
+        x = torch.where(keep[..., None], x, torch.zeros((), dtype=x.dtype, device=x.device))
+        indices = torch.where(keep[..., None], indices, torch.zeros((), dtype=indices.dtype, device=x.device))
+        assert not torch.any(indices == -1), "some of the residual vq indices were dropped out"
+        zero = torch.zeros((), dtype=x.dtype, device=x.device)
+        residual, out, ce = x, torch.zeros_like(x), 0.
+        for q in range(cb.shape[0]):
+            e = cb[q]
+            d2 = residual.pow(2).sum(-1, keepdim=True) - 2 * residual @ e.t() + e.pow(2).sum(-1)
+            logits = -d2.clamp(min=0).sqrt()                                     # [b, n, C]
+            rows = F.cross_entropy(logits.transpose(1, 2), indices[..., q], reduction="none")    # [b, n]
+            ce = ce + (torch.where(keep, rows, zero).sum(-1) / ln.to(x.dtype)).mean()            # own frames, then the mean over b
+            quantized = F.embedding(logits.argmax(dim=-1), e)
+            residual = residual - quantized.detach()
+            out = out + quantized
+        return torch.where(keep[..., None], out, zero), ce
 
     def _forward_composite(self, x, indices):
         cb = self._owner[0].codebooks.to(x.dtype)

@@ -14,10 +14,16 @@
 //     10 log10(max(mel, 1e-10)), the log10 taken in fp64 and rounded to fp32;
 //   - results are staged as [mel][frame] in LDS so that each store writes a contiguous run of frames of one mel row.
 // No atomics: a frame's values depend on its samples alone, so an utterance's output is bit-identical whatever batch it is in.
+//
+// LENS (ns2_audio_to_mel_lens, include/ns2hip_ragged_audio.h): utterance b ends at its own sample_lens[b], clamped into
+// [n_fft / 2 + 1, L].  The reflection is taken about ITS last sample -- the one index map at the staging of smp -- so frames
+// t < T_b = 1 + len / hop are those of the utterance alone; frames from T_b on are stored as 0.0f, and a block that holds only such
+// frames stages nothing and runs no FFT.  The instantiation without LENS is the kernel as it was.
 #include <hip/hip_runtime.h>
 
 #include <climits>
 
+#include "../../include/ns2hip_ragged_audio.h"
 #include "ns2_common.h"
 #include "ns2_host.h"
 
@@ -52,11 +58,12 @@ inline size_t am_lds_bytes(int N, int fpb, int hop, int n_mels, int n_bins, int 
 }
 
 // grid (ceil(T / fpb), B), AM_THREADS threads, dynamic LDS am_lds_bytes
-template <int N>
+template <int N, bool LENS>
 __global__ __launch_bounds__(AM_THREADS) void audio_to_mel_kernel(const float* __restrict__ audio, long L, long T, int hop, int fpb,
                                                                   const float* __restrict__ window, const float2* __restrict__ twiddle,
                                                                   const int* __restrict__ fb_meta, const float* __restrict__ fb_w,
-                                                                  int n_w, int n_mels, int n_bins, int log_db, float* __restrict__ out) {
+                                                                  int n_w, int n_mels, int n_bins, int log_db, float* __restrict__ out,
+                                                                  const int* __restrict__ sample_lens) {
   constexpr int NFFT = 2 * N, FB = AM_POINTS / N, NP = N + N / 32, Q = N / 4;
   extern __shared__ float2 am_sm[];
   float2* tw = am_sm;
@@ -71,7 +78,20 @@ __global__ __launch_bounds__(AM_THREADS) void audio_to_mel_kernel(const float* _
   const int t = threadIdx.x;
   const long b = blockIdx.y;
   const long f0 = (long)blockIdx.x * fpb;
-  const int nf = (int)min((long)fpb, T - f0);
+  const int nfo = (int)min((long)fpb, T - f0);                  // frames this block stores
+  int nf = nfo;                                                 // ... of which it computes the first nf; the rest are 0
+  long Le = L;                                                  // where the utterance ends: the reflection's mirror
+  if constexpr (LENS) {
+    Le = min(max((long)sample_lens[b], (long)N + 1), L);
+    nf = (int)min(max(1 + Le / hop - f0, 0L), (long)nfo);
+    if (nf == 0) {                                              // block-uniform: nothing staged, no FFT, no barrier passed
+      for (int i = t; i < n_mels * fpb; i += AM_THREADS) {
+        const int m = i / fpb, f = i % fpb;
+        if (f < nfo) out[(b * n_mels + m) * T + f0 + f] = 0.f;
+      }
+      return;
+    }
+  }
   const float* x = audio + b * L;
   for (int i = t; i < NFFT; i += AM_THREADS) {
     tw[i] = twiddle[i];
@@ -85,7 +105,7 @@ __global__ __launch_bounds__(AM_THREADS) void audio_to_mel_kernel(const float* _
     float v = 0.f;
     if (i < valid) {
       long s = s0 + i;
-      s = s < 0 ? -s : (s >= L ? 2 * (L - 1) - s : s);        // reflect; L > n_fft / 2 keeps one reflection in range
+      s = s < 0 ? -s : (s >= Le ? 2 * (Le - 1) - s : s);      // reflect; Le > n_fft / 2 keeps one reflection in range
       v = x[s];
     }
     smp[i] = v;
@@ -188,7 +208,11 @@ __global__ __launch_bounds__(AM_THREADS) void audio_to_mel_kernel(const float* _
   __syncthreads();
   for (int i = t; i < n_mels * fpb; i += AM_THREADS) {
     const int m = i / fpb, f = i % fpb;
-    if (f < nf) out[(b * n_mels + m) * T + f0 + f] = os[m * (fpb + 1) + f];
+    if constexpr (LENS) {
+      if (f < nfo) out[(b * n_mels + m) * T + f0 + f] = f < nf ? os[m * (fpb + 1) + f] : 0.f;
+    } else {
+      if (f < nf) out[(b * n_mels + m) * T + f0 + f] = os[m * (fpb + 1) + f];
+    }
   }
 }
 
@@ -200,25 +224,54 @@ __global__ __launch_bounds__(AM_THREADS) void audio_to_mel_kernel(const float* _
       return NS2_ERR_HIP;                                                            \
     }                                                                                \
   } while (0)
-#define AM_ARGCHK(cond, msg) \
-  do {                       \
-    if (!(cond)) {           \
-      set_error("%s", msg);  \
-      return NS2_ERR_ARG;    \
-    }                        \
+#define AM_ARGCHK(cond, msg)           \
+  do {                                 \
+    if (!(cond)) {                     \
+      set_error("%s: %s", who, msg);   \
+      return NS2_ERR_ARG;              \
+    }                                  \
   } while (0)
 
-template <int N>
+template <int N, bool LENS>
 static int launch_audio_to_mel(const float* audio, int B, int64_t L, int64_t T, int hop, int fpb, size_t lds, const float* window,
                                const float* twiddle, const int* fb_meta, const float* fb_w, int n_w, int n_mels, int n_bins,
-                               int log_db, float* out, hipStream_t s) {
+                               int log_db, float* out, const int* sample_lens, hipStream_t s) {
   static DynLdsAttr attr;
-  AM_HIPRET(attr.ensure(reinterpret_cast<const void*>(&audio_to_mel_kernel<N>), (int)lds));
+  AM_HIPRET(attr.ensure(reinterpret_cast<const void*>(&audio_to_mel_kernel<N, LENS>), (int)lds));
   const dim3 grid((unsigned)((T + fpb - 1) / fpb), (unsigned)B);
-  hipLaunchKernelGGL(audio_to_mel_kernel<N>, grid, dim3(AM_THREADS), lds, s, audio, (long)L, (long)T, hop, fpb, window,
-                     reinterpret_cast<const float2*>(twiddle), fb_meta, fb_w, n_w, n_mels, n_bins, log_db, out);
+  hipLaunchKernelGGL((audio_to_mel_kernel<N, LENS>), grid, dim3(AM_THREADS), lds, s, audio, (long)L, (long)T, hop, fpb, window,
+                     reinterpret_cast<const float2*>(twiddle), fb_meta, fb_w, n_w, n_mels, n_bins, log_db, out, sample_lens);
   AM_HIPRET(hipGetLastError());
   return NS2_OK;
+}
+
+// the argument checks and the launch of both entries; `who` names the entry in the messages
+template <bool LENS>
+static int audio_to_mel_entry(const char* who, const float* audio, int B, int64_t L, int n_fft, int hop_length, const float* window,
+                              const float* twiddle, const int* fb_meta, const float* fb_w, int n_w, int n_mels, int n_bins, int log_db,
+                              float* out, const int* sample_lens, void* stream) {
+  AM_ARGCHK(audio && window && twiddle && fb_meta && fb_w && out && B > 0 && B <= 65535, "bad arguments");
+  if (LENS) AM_ARGCHK(sample_lens, "sample_lens is null (ns2_audio_to_mel is the call without lengths)");
+  AM_ARGCHK(n_fft >= 256 && n_fft <= 2048 && (n_fft & (n_fft - 1)) == 0, "n_fft must be a power of two in [256, 2048]");
+  AM_ARGCHK(hop_length >= 1 && hop_length <= n_fft, "hop_length must be in [1, n_fft]");
+  AM_ARGCHK(n_mels >= 1 && n_mels <= 256, "n_mels must be in [1, 256]");
+  const int N = n_fft / 2;
+  AM_ARGCHK(n_bins >= 1 && n_bins <= N + 1 && n_w >= 0 && n_w <= 2 * (N + 1), "bad filterbank table sizes");
+  AM_ARGCHK(L > N, "reflect padding needs more than n_fft / 2 samples");
+  const int64_t T = 1 + L / hop_length;
+  int fpb = AM_FPB;
+  const int fb = AM_POINTS / N;
+  while (fpb > fb && am_lds_bytes(N, fpb, hop_length, n_mels, n_bins, n_w) > (size_t)AM_LDS_SOFT) fpb /= 2;
+  const size_t lds = am_lds_bytes(N, fpb, hop_length, n_mels, n_bins, n_w);
+  AM_ARGCHK(lds <= (size_t)AM_LDS_MAX, "configuration exceeds the LDS");
+  AM_ARGCHK((T + fpb - 1) / fpb <= INT_MAX, "too many frames");
+  const hipStream_t s = (hipStream_t)stream;
+  switch (N) {
+    case 128: return launch_audio_to_mel<128, LENS>(audio, B, L, T, hop_length, fpb, lds, window, twiddle, fb_meta, fb_w, n_w, n_mels, n_bins, log_db, out, sample_lens, s);
+    case 256: return launch_audio_to_mel<256, LENS>(audio, B, L, T, hop_length, fpb, lds, window, twiddle, fb_meta, fb_w, n_w, n_mels, n_bins, log_db, out, sample_lens, s);
+    case 512: return launch_audio_to_mel<512, LENS>(audio, B, L, T, hop_length, fpb, lds, window, twiddle, fb_meta, fb_w, n_w, n_mels, n_bins, log_db, out, sample_lens, s);
+    default: return launch_audio_to_mel<1024, LENS>(audio, B, L, T, hop_length, fpb, lds, window, twiddle, fb_meta, fb_w, n_w, n_mels, n_bins, log_db, out, sample_lens, s);
+  }
 }
 
 }  // namespace ns2
@@ -228,25 +281,14 @@ using namespace ns2;
 extern "C" int ns2_audio_to_mel(const float* audio, int B, int64_t L, int n_fft, int hop_length, const float* window, const float* twiddle,
                                 const int* fb_meta, const float* fb_w, int n_w, int n_mels, int n_bins, int log_db, float* out,
                                 void* stream) {
-  AM_ARGCHK(audio && window && twiddle && fb_meta && fb_w && out && B > 0 && B <= 65535, "ns2_audio_to_mel: bad arguments");
-  AM_ARGCHK(n_fft >= 256 && n_fft <= 2048 && (n_fft & (n_fft - 1)) == 0, "ns2_audio_to_mel: n_fft must be a power of two in [256, 2048]");
-  AM_ARGCHK(hop_length >= 1 && hop_length <= n_fft, "ns2_audio_to_mel: hop_length must be in [1, n_fft]");
-  AM_ARGCHK(n_mels >= 1 && n_mels <= 256, "ns2_audio_to_mel: n_mels must be in [1, 256]");
-  const int N = n_fft / 2;
-  AM_ARGCHK(n_bins >= 1 && n_bins <= N + 1 && n_w >= 0 && n_w <= 2 * (N + 1), "ns2_audio_to_mel: bad filterbank table sizes");
-  AM_ARGCHK(L > N, "ns2_audio_to_mel: reflect padding needs more than n_fft / 2 samples");
-  const int64_t T = 1 + L / hop_length;
-  int fpb = AM_FPB;
-  const int fb = AM_POINTS / N;
-  while (fpb > fb && am_lds_bytes(N, fpb, hop_length, n_mels, n_bins, n_w) > (size_t)AM_LDS_SOFT) fpb /= 2;
-  const size_t lds = am_lds_bytes(N, fpb, hop_length, n_mels, n_bins, n_w);
-  AM_ARGCHK(lds <= (size_t)AM_LDS_MAX, "ns2_audio_to_mel: configuration exceeds the LDS");
-  AM_ARGCHK((T + fpb - 1) / fpb <= INT_MAX, "ns2_audio_to_mel: too many frames");
-  const hipStream_t s = (hipStream_t)stream;
-  switch (N) {
-    case 128: return launch_audio_to_mel<128>(audio, B, L, T, hop_length, fpb, lds, window, twiddle, fb_meta, fb_w, n_w, n_mels, n_bins, log_db, out, s);
-    case 256: return launch_audio_to_mel<256>(audio, B, L, T, hop_length, fpb, lds, window, twiddle, fb_meta, fb_w, n_w, n_mels, n_bins, log_db, out, s);
-    case 512: return launch_audio_to_mel<512>(audio, B, L, T, hop_length, fpb, lds, window, twiddle, fb_meta, fb_w, n_w, n_mels, n_bins, log_db, out, s);
-    default: return launch_audio_to_mel<1024>(audio, B, L, T, hop_length, fpb, lds, window, twiddle, fb_meta, fb_w, n_w, n_mels, n_bins, log_db, out, s);
-  }
+  return audio_to_mel_entry<false>("ns2_audio_to_mel", audio, B, L, n_fft, hop_length, window, twiddle, fb_meta, fb_w, n_w, n_mels, n_bins,
+                                   log_db, out, nullptr, stream);
+}
+
+// include/ns2hip_ragged_audio.h
+extern "C" int ns2_audio_to_mel_lens(const float* audio, int B, int64_t L, int n_fft, int hop_length, const float* window,
+                                     const float* twiddle, const int* fb_meta, const float* fb_w, int n_w, int n_mels, int n_bins,
+                                     int log_db, float* out, const int* sample_lens, void* stream) {
+  return audio_to_mel_entry<true>("ns2_audio_to_mel_lens", audio, B, L, n_fft, hop_length, window, twiddle, fb_meta, fb_w, n_w, n_mels,
+                                  n_bins, log_db, out, sample_lens, stream);
 }

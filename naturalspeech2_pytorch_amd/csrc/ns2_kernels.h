@@ -284,6 +284,13 @@ struct RvqCeArgs {
   int M, Q, C, D;
 };
 hipError_t launch_rvq_ce(const RvqCeArgs& a, hipStream_t s);
+// ... of a ragged batch (include/ns2hip_ragged_audio.h): M = B n rows, utterance b owns rows [b n, b n + row_lens[b]); the loss is the mean
+// over utterances of each utterance's own mean, G of a row is divided by B row_lens[b], and every output row at or behind a length is 0
+struct RvqCeLensArgs : RvqCeArgs {
+  const int* row_lens;       // [B] on the device, clamped into [1, n] by the kernels
+  int B, n;
+};
+hipError_t launch_rvq_ce_lens(const RvqCeLensArgs& a, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------- backward pass (backward.hip)
 // fp32 [M, C] (xf) or operand planes (in_hi / in_lo, interleaved bf16 hi/lo) -> row planes and / or TRANSPOSED planes
@@ -386,6 +393,6 @@ hipError_t launch_align_losses_bwd(const float* aln_log, const float* hard, cons
 // The caller (capi.cpp) has checked 2 <= tau_min < tau_max <= PITCH_TAU_MAX, hop >= 1, L >= 1, 1 <= B <= 65535
 constexpr int PITCH_TAU_MAX = 1024;
 hipError_t launch_pitch_yin(const float* audio, int B, long L, long T, int sample_rate, int hop, int tau_min, int tau_max, float threshold,
-                            float* f0, hipStream_t s);
+                            float* f0, hipStream_t s, const int* sample_lens = nullptr);   // sample_lens [B] on the device: ns2_pitch_yin_lens
 
 }  // namespace ns2

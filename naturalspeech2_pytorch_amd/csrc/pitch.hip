@@ -17,6 +17,9 @@
 //     before it carried in (a fixed shape), d'(tau) back into the lag's LDS slot, then two ascending ballot searches -- the
 //     first lag below the threshold, and from there the first lag whose successor is not lower.
 // A frame's value depends on its own samples alone, so an utterance's row is bit-identical alone or in any batch.
+// LENS (ns2_pitch_yin_lens, include/ns2hip_ragged_audio.h): utterance b ends at its own sample_lens[b], clamped into [1, L]: the
+// staging reads zeros from there on, frames from T_b = 1 + len / hop on are stored as 0 (unvoiced), and a block that holds only such
+// frames returns after storing them.  The instantiation without LENS is the kernel as it was.
 // This translation unit converts nothing to half: it includes no ns2_common.h and owns no range counter.
 #include <hip/hip_runtime.h>
 
@@ -37,23 +40,34 @@ inline int py_dp(int tau_max) { return (tau_max + 1 + 63) / 64 * 64; }
 inline int py_groups(int tau_max) { return (tau_max + PY_R) / PY_R; }  // lanes per frame: lags 0 .. tau_max, PY_R each
 
 // grid (ceil(T / F), B), PY_THREADS threads, dynamic LDS 4 F (SP + DP) bytes
+template <bool LENS>
 __global__ __launch_bounds__(PY_THREADS) void pitch_yin_kernel(const float* __restrict__ audio, long L, long T, int hop, int F, int G,
                                                                int SP, int DP, int tau_min, int tau_max, float fs, float thr,
-                                                               float* __restrict__ f0) {
+                                                               float* __restrict__ f0, const int* __restrict__ sample_lens) {
   extern __shared__ float4 py_sm[];
   float* smp = reinterpret_cast<float*>(py_sm);
   float* dd = smp + F * SP;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const long b = blockIdx.y;
   const long fr0 = (long)blockIdx.x * F;
-  const int nf = (int)min((long)F, T - fr0);
+  const int nfo = (int)min((long)F, T - fr0);                     // frames this block stores
+  int nf = nfo;                                                   // ... of which it computes the first nf; the rest are 0
+  long Le = L;                                                    // where the utterance ends
+  if constexpr (LENS) {
+    Le = min(max((long)sample_lens[b], 1L), L);
+    nf = (int)min(max(1 + Le / hop - fr0, 0L), (long)nfo);
+    if (nf == 0) {                                                // block-uniform, before any barrier
+      if (t < nfo) f0[b * T + fr0 + t] = 0.f;
+      return;
+    }
+  }
   const int S = 3 * tau_max, W = 2 * tau_max, W4 = W & ~3;
   const float* x = audio + b * L;
 
   for (int i = t; i < nf * SP; i += PY_THREADS) {
     const int f = i / SP, idx = i - f * SP;
     const long src = (fr0 + f) * hop - S / 2 + idx;
-    smp[i] = (idx < S && src >= 0 && src < L) ? x[src] : 0.f;
+    smp[i] = (idx < S && src >= 0 && src < Le) ? x[src] : 0.f;
   }
   __syncthreads();
 
@@ -159,13 +173,17 @@ __global__ __launch_bounds__(PY_THREADS) void pitch_yin_kernel(const float* __re
       }
       if (lane == 0) f0[b * T + fr0 + f] = out;
     }
+    if constexpr (LENS) {
+      if (!active && f < nfo && lane == 0) f0[b * T + fr0 + f] = 0.f;
+    }
   }
 }
 
 }  // namespace
 
+// sample_lens null: the call without lengths
 hipError_t launch_pitch_yin(const float* audio, int B, long L, long T, int sample_rate, int hop, int tau_min, int tau_max, float threshold,
-                            float* f0, hipStream_t s) {
+                            float* f0, hipStream_t s, const int* sample_lens) {
   const int G = py_groups(tau_max), SP = py_sp(tau_max), DP = py_dp(tau_max);
   const size_t per_frame = 4 * (size_t)(SP + DP);
   int F = 1;
@@ -175,8 +193,12 @@ hipError_t launch_pitch_yin(const float* audio, int B, long L, long T, int sampl
     if (n * best_d > best_n * d) { F = f; best_n = n; best_d = d; }
   }
   const dim3 grid((unsigned)((T + F - 1) / F), (unsigned)B);
-  hipLaunchKernelGGL(pitch_yin_kernel, grid, dim3(PY_THREADS), F * per_frame, s, audio, L, T, hop, F, G, SP, DP, tau_min, tau_max,
-                     (float)sample_rate, threshold, f0);
+  if (sample_lens)
+    hipLaunchKernelGGL(pitch_yin_kernel<true>, grid, dim3(PY_THREADS), F * per_frame, s, audio, L, T, hop, F, G, SP, DP, tau_min, tau_max,
+                       (float)sample_rate, threshold, f0, sample_lens);
+  else
+    hipLaunchKernelGGL(pitch_yin_kernel<false>, grid, dim3(PY_THREADS), F * per_frame, s, audio, L, T, hop, F, G, SP, DP, tau_min, tau_max,
+                       (float)sample_rate, threshold, f0, sample_lens);
   return hipGetLastError();
 }
 

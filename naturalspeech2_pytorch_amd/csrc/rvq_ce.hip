@@ -17,6 +17,14 @@
 //   * near-ties of the nearest code are not re-decided in fp64 (rvq_encode_kernel does): either code is a valid stage result.
 // Distances: the sweeps use the expanded form |r|^2 - 2 (r.e - |e|^2/2) clamped at 0 (what the MFMA yields, and what the PyTorch
 // composite computes); the target's own distance -- the term the loss is most sensitive to -- is the direct form sum (r - e)^2.
+//
+// Ragged batches (ns2_rvq_ce_lens, include/ns2hip_ragged_audio.h): the same kernel instantiated on RvqCeLensArgs.  A row at or behind its
+// utterance's length is a DEAD row: its x and its targets are not read (the residual starts at 0, the target is code 0, so nothing of it
+// is NaN), its rows of row_loss and G are stored as 0, and a workgroup of dead rows alone returns before the first codebook tile.  A live
+// row's arithmetic is unchanged (rows never mix: a row is one column of every MFMA), and its G is divided by B len instead of M.  The
+// instantiations on RvqCeArgs are the kernels as they were.
+#include <type_traits>
+
 #include "ns2_common.h"
 #include "ns2_kernels.h"
 
@@ -33,13 +41,35 @@ constexpr int RC_ROWS = 128;                      // rows per workgroup: 8 waves
 // 4 m + kt, resp. 64 + 4 m + (kt - 4), of k-tile kt, so that a lane reads its A operands as two conflict-free 16-byte LDS loads).
 NS2_DEVINL int rc_col(int g, int s) { return (s < 16 ? 0 : 48) + 16 * g + s; }
 
-template <bool GRAD>
-__global__ __launch_bounds__(512, 2) void rvq_ce_kernel(const RvqCeArgs a) {
+// the length of the utterance that owns `row` (< B n), clamped into [1, n], and the row's place in it
+NS2_DEVINL bool rc_row_live(const RvqCeLensArgs& a, long row, int* len) {
+  const long b = row / a.n;
+  *len = min(max(a.row_lens[b], 1), a.n);
+  return row - b * a.n < *len;
+}
+
+template <bool GRAD, typename Args>
+__global__ __launch_bounds__(512, 2) void rvq_ce_kernel(const Args a) {
+  constexpr bool LENS = std::is_same<Args, RvqCeLensArgs>::value;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int l15 = lane & 15, g = lane >> 4;
   const long row = (long)blockIdx.x * RC_ROWS + wave * 16 + l15;
-  const bool row_ok = row < a.M;
+  bool row_ok = row < a.M;
+  if constexpr (LENS) {
+    const bool in_batch = row_ok;
+    int len;
+    row_ok = in_batch && rc_row_live(a, row, &len);
+    if (in_batch && !row_ok) {                                                   // a dead row: its outputs, and nothing else of it
+      if (g == 0)
+        for (int q = 0; q < a.Q; ++q) a.row_loss[row * a.Q + q] = 0.f;
+      if constexpr (GRAD) {
+#pragma unroll
+        for (int s4 = 0; s4 < 8; ++s4) *reinterpret_cast<float4*>(a.grad + row * RC_D + rc_col(g, 4 * s4)) = make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+    }
+    if (!__syncthreads_or((int)row_ok)) return;                                  // no live row in this workgroup: no codebook tile
+  }
 
   float rf[32];                                   // rf[s] = r[row][K(g, s)]
 #pragma unroll
@@ -239,7 +269,12 @@ __global__ __launch_bounds__(512, 2) void rvq_ce_kernel(const RvqCeArgs a) {
 
   if constexpr (GRAD) {
     if (row_ok) {
-      const float m = (float)a.M;
+      float m = (float)a.M;
+      if constexpr (LENS) {
+        int len;
+        rc_row_live(a, row, &len);
+        m = (float)(a.B * len);                                                // <= M
+      }
 #pragma unroll
       for (int hf = 0; hf < 2; ++hf)
 #pragma unroll
@@ -264,23 +299,78 @@ __global__ __launch_bounds__(1024) void rvq_ce_reduce_kernel(const float* row_lo
   if (threadIdx.x == 0) loss[0] = (float)(part[0] / (double)M);
 }
 
-hipError_t launch_rvq_ce(const RvqCeArgs& a, hipStream_t s) {
+// loss = (1 / B) sum_b (1 / len_b) sum_{t < len_b} sum_q row_loss[b][t][q]: one workgroup; per utterance a thread sums its part of the
+// utterance's own len_b Q contiguous values in index order and adds it, divided by len_b, to its fp64 partial sum; then a fixed tree
+__global__ __launch_bounds__(1024) void rvq_ce_reduce_lens_kernel(const float* row_loss, const int* row_lens, int B, int n, int Q, float* loss) {
+  __shared__ double part[1024];
+  double s = 0.0;
+  for (int b = 0; b < B; ++b) {
+    const int len = min(max(row_lens[b], 1), n);
+    const float* r = row_loss + (long)b * n * Q;
+    double u = 0.0;
+    for (long i = threadIdx.x; i < (long)len * Q; i += 1024) u += (double)r[i];
+    s += u / (double)len;
+  }
+  part[threadIdx.x] = s;
+  __syncthreads();
+  for (int off = 512; off > 0; off >>= 1) {
+    if ((int)threadIdx.x < off) part[threadIdx.x] += part[threadIdx.x + off];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) loss[0] = (float)(part[0] / (double)B);
+}
+
+// rvq_decode_kernel (rvq.hip) with lengths: the same sum in the same order for a live row, 0 and no read of `codes` for a dead one
+__global__ void rvq_ce_decode_lens_kernel(const int64_t* codes, const float* cb, float* emb, const int* row_lens, int B, int n, int Q, int C) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (long)B * n * RC_D) return;
+  const long m = i / RC_D;
+  const int k = (int)(i - m * RC_D);
+  const long b = m / n;
+  float acc = 0.f;
+  if (m - b * n < min(max(row_lens[b], 1), n))
+    for (int q = 0; q < Q; ++q) {
+      const long c = codes[m * Q + q];
+      acc += cb[((long)q * C + c) * RC_D + k];
+    }
+  emb[i] = acc;
+}
+
+template <typename Args>
+static hipError_t launch_rvq_ce_main(const Args& a, hipStream_t s) {
   if (a.M <= 0 || a.Q <= 0 || a.D != RC_D || a.C <= 0 || (a.C % RC_TILE)) return hipErrorInvalidValue;
   if (a.quantized_out && !a.nearest) return hipErrorInvalidValue;
   const size_t lds = 2 * RC_STAGE_F * sizeof(float);
   const dim3 grid((a.M + RC_ROWS - 1) / RC_ROWS);
   if (a.grad) {
     static DynLdsAttr attr;
-    hipError_t e = attr.ensure(reinterpret_cast<const void*>(&rvq_ce_kernel<true>), (int)lds);
+    hipError_t e = attr.ensure(reinterpret_cast<const void*>(&rvq_ce_kernel<true, Args>), (int)lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(rvq_ce_kernel<true>, grid, dim3(512), lds, s, a);
+    hipLaunchKernelGGL((rvq_ce_kernel<true, Args>), grid, dim3(512), lds, s, a);
   } else {
     static DynLdsAttr attr;
-    hipError_t e = attr.ensure(reinterpret_cast<const void*>(&rvq_ce_kernel<false>), (int)lds);
+    hipError_t e = attr.ensure(reinterpret_cast<const void*>(&rvq_ce_kernel<false, Args>), (int)lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(rvq_ce_kernel<false>, grid, dim3(512), lds, s, a);
+    hipLaunchKernelGGL((rvq_ce_kernel<false, Args>), grid, dim3(512), lds, s, a);
   }
-  hipError_t e = hipGetLastError();
+  return hipGetLastError();
+}
+
+hipError_t launch_rvq_ce_lens(const RvqCeLensArgs& a, hipStream_t s) {
+  if (!a.row_lens || a.B <= 0 || a.n <= 0 || (long)a.B * a.n != (long)a.M) return hipErrorInvalidValue;
+  hipError_t e = launch_rvq_ce_main(a, s);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(rvq_ce_reduce_lens_kernel, dim3(1), dim3(1024), 0, s, a.row_loss, a.row_lens, a.B, a.n, a.Q, a.loss);
+  e = hipGetLastError();
+  if (e != hipSuccess || !a.quantized_out) return e;
+  const long n = (long)a.M * RC_D;
+  hipLaunchKernelGGL(rvq_ce_decode_lens_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a.nearest, a.codebooks, a.quantized_out,
+                     a.row_lens, a.B, a.n, a.Q, a.C);
+  return hipGetLastError();
+}
+
+hipError_t launch_rvq_ce(const RvqCeArgs& a, hipStream_t s) {
+  hipError_t e = launch_rvq_ce_main(a, s);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(rvq_ce_reduce_kernel, dim3(1), dim3(1024), 0, s, a.row_loss, (long)a.M * a.Q, a.M, a.loss);
   e = hipGetLastError();

@@ -76,6 +76,21 @@ def _is_denoiser(m):
     return all(hasattr(m, a) for a in ("forward_with_cond_scale", "dim", "condition_on_prompt")) and isinstance(m, nn.Module)
 
 
+def _check_raw_sample_lens(codec, hop, lens, total, what, noun):
+    """the one check of per-utterance SAMPLE counts of raw audio that the codec encodes as a padded batch (a raw-audio prompt of
+    `sample(prompt_lens=)`, raw audio of `forward(audio_lens=)` with `ragged_audio=True`): every length, and the padded length, a
+    positive multiple of the codec's hop, and at least `min_causal_prompt_frames` frames.  One host read."""
+    ok = (total > 0 and total % hop == 0 and bool(((lens > 0) & (lens % hop == 0) & (lens <= total)).all().item()))
+    if not ok:
+        raise ValueError(f"{what}: every length, and the padded length {total}, must be a "
+                         f"positive multiple of the codec's seq_len_multiple_of ({hop}) samples")
+    least = int(getattr(codec, "min_causal_prompt_frames", 1))
+    if least > 1 and not bool((lens >= least * hop).all().item()):
+        raise ValueError(f"{what}: every {noun} must be at least {least} codec frames ({least * hop} "
+                         f"samples) long -- the encoder's reflect padding mirrors that many of an utterance's first frames, and "
+                         f"would read a shorter {noun}'s padding")
+
+
 class NaturalSpeech2(nn.Module):
     def __init__(self, model, codec=None, *, tokenizer=None, target_sample_hz=None, timesteps=1000, use_ddim=True,
                  noise_schedule="sigmoid", objective="v", schedule_kwargs: dict = dict(), time_difference=0.,
@@ -92,7 +107,8 @@ class NaturalSpeech2(nn.Module):
                  encoder_train_backend="composite",    # not in the reference: "hip" trains phoneme_enc / prompt_enc on the HIP kernels (training/encoder_pass.py)
                  duration_pitch_train_backend="composite",    # not in the reference: "hip" trains the DurationPitchPredictor on them (training/duration_pitch_pass.py)
                  aligner_train_backend="composite",    # not in the reference: "hip" trains the Aligner and runs its two losses on them (training/aligner_pass.py)
-                 rvq_ce_backend=None):                 # not in the reference: "composite" / "hip" sets codec.rq.backend, the RVQ cross-entropy term (csrc/rvq_ce.hip); None leaves the codec's own
+                 rvq_ce_backend=None,                  # not in the reference: "composite" / "hip" sets codec.rq.backend, the RVQ cross-entropy term (csrc/rvq_ce.hip); None leaves the codec's own
+                 ragged_audio: bool = False):          # not in the reference: forward(raw audio, audio_lens=samples) and audio_lens with the RVQ term (include/ns2hip_ragged_audio.h)
         super().__init__()
         assert _is_denoiser(model), "model must be a Model (this package's, or compat.HipBackedModel over the reference's class)"
         self.conditional = model.condition_on_prompt
@@ -148,6 +164,7 @@ class NaturalSpeech2(nn.Module):
         self.train_prob_self_cond = train_prob_self_cond
         self.min_snr_loss_weight, self.min_snr_gamma = min_snr_loss_weight, min_snr_gamma
         self.rvq_cross_entropy_loss_weight = rvq_cross_entropy_loss_weight
+        self.ragged_audio = ragged_audio
         if rvq_ce_backend is not None:
             assert codec is not None and hasattr(codec, "rq") and hasattr(codec.rq, "backend"), "rvq_ce_backend needs a codec whose rq has a backend (codec.py)"
             assert rvq_ce_backend in ("composite", "hip"), "rvq_ce_backend must be 'composite' or 'hip'"
@@ -318,15 +335,7 @@ class NaturalSpeech2(nn.Module):
         if prompt_enc is None and prompt.ndim == 2:
             assert self.codec is not None, "codec must be passed in if one were to sample from a raw prompt"
             hop = int(self.seq_len_multiple_of)
-            ok = (prompt.shape[-1] > 0 and prompt.shape[-1] % hop == 0 and bool(((lens > 0) & (lens % hop == 0) & (lens <= prompt.shape[-1])).all().item()))
-            if not ok:
-                raise ValueError(f"a raw-audio prompt with prompt_lens: every length, and the padded length {prompt.shape[-1]}, must be a "
-                                 f"positive multiple of the codec's seq_len_multiple_of ({hop}) samples")
-            least = int(getattr(self.codec, "min_causal_prompt_frames", 1))
-            if least > 1 and not bool((lens >= least * hop).all().item()):
-                raise ValueError(f"a raw-audio prompt with prompt_lens: every prompt must be at least {least} codec frames ({least * hop} "
-                                 f"samples) long -- the encoder's reflect padding mirrors that many of an utterance's first frames, and "
-                                 f"would read a shorter prompt's padding")
+            _check_raw_sample_lens(self.codec, hop, lens, prompt.shape[-1], "a raw-audio prompt with prompt_lens", "prompt")
             lens = lens // hop
         return lens
 
@@ -522,13 +531,31 @@ class NaturalSpeech2(nn.Module):
         its own frames [0, audio_lens[i]) x dim -- what it is for the utterance alone -- before the reference's (loss * weight).mean().
         Mask and divisor are formed on the device from the lengths (no host read: a captured step follows rewritten lengths); what
         audio, noise and cond hold from a length on never reaches the loss or a gradient.  Latents only: raw audio, the RVQ
-        cross-entropy term and `prompt_lens` are not taken together with it (NotImplementedError)."""
+        cross-entropy term and `prompt_lens` are not taken together with it (NotImplementedError).
+
+        Built with `ragged_audio=True` (not in the reference; also a plain attribute), the first two are taken:
+          * raw audio [b, S] with `audio_lens` counting SAMPLES.  Each length and S must be a positive multiple of the codec's
+            `seq_len_multiple_of` and at least its `min_causal_prompt_frames` frames (ValueError; the check of sample(prompt_lens=) with a
+            raw-audio prompt, for the same reason: the SEANet encoder is causal and its reflect padding is a left prefix, so an
+            utterance's frames do not see its padding).  The check is one host read: it is made only when the lengths arrive as a list
+            or a CPU tensor, and never while the stream is capturing; a CUDA tensor is TRUSTED and stays on the device.  The padded
+            batch is encoded in one pass and the frame counts audio_lens // hop go on as above;
+          * the RVQ cross-entropy term: the frame counts go to `codec.rq(x_start, codes, lens=)`, the mean over the utterances of each
+            one's own term (codec.py);
+          * with `text=` and the Aligner: `mel` (when not given) is `audio_to_mel(audio, lens=audio_lens)`, `pitch` (when not given)
+            `pitch_extractor(audio, lens=audio_lens)`, and `mel_lens` defaults to 1 + audio_lens // mel_hop_length, formed on the device;
+            the Aligner and its losses run on lengths already.  NOT claimed: the phoneme encoder, the prompt encoder and the predictor
+            still see no lengths in training, so "equals the utterance alone" holds there for mel, pitch and mel_lens, and for the
+            diffusion and RVQ terms GIVEN the conditioning, not for the whole text-conditioned loss.
+        `prompt_lens` with `audio_lens` keeps raising, and the model still needs `ragged_training=True`."""
         is_raw = audio.ndim == 2
+        ragged_audio = bool(getattr(self, "ragged_audio", False))
+        sample_lens = None                                                            # ragged raw audio: the sample counts, on the device
         if audio_lens is not None:
-            if is_raw:
+            if is_raw and not ragged_audio:
                 raise NotImplementedError("audio_lens with raw audio: the frozen codec's encode of a padded batch is not shown to equal the "
                                           "utterance alone -- pass the latents [b, n, dim] and their frame counts")
-            if self.rvq_cross_entropy_loss_weight > 0 and codes is not None:
+            if self.rvq_cross_entropy_loss_weight > 0 and codes is not None and not ragged_audio:
                 raise NotImplementedError("audio_lens with the RVQ cross-entropy term (rvq_cross_entropy_loss_weight > 0 and codes=): "
                                           "ns2_rvq_ce averages over all frames, it takes no per-utterance lengths")
             if kwargs.get("prompt_lens") is not None:
@@ -539,6 +566,13 @@ class NaturalSpeech2(nn.Module):
                 raise ValueError(f"audio_lens must be integers (frame counts), got {audio_lens.dtype}")
             if audio_lens.shape != (audio.shape[0],):
                 raise ValueError(f"audio_lens must hold one frame count per utterance: [{audio.shape[0]}], got {list(audio_lens.shape)}")
+            if is_raw:
+                assert self.codec is not None, "codec must be passed in if one were to train on raw audio"
+                if not audio_lens.is_cuda and not (audio.is_cuda and torch.cuda.is_current_stream_capturing()):
+                    _check_raw_sample_lens(self.codec, int(self.seq_len_multiple_of), audio_lens.long(), audio.shape[-1],
+                                           "raw audio with audio_lens", "utterance")
+                sample_lens = audio_lens.to(audio.device)
+                audio_lens = sample_lens // int(self.seq_len_multiple_of)             # frames, as the latent path counts
         p_enc = None
         aux = None
         if return_aux_losses and (not self.conditional or cond is not None):
@@ -556,13 +590,15 @@ class NaturalSpeech2(nn.Module):
                         raise NotImplementedError("forward(text=...) without `pitch` computes it with PitchExtractor, which needs raw "
                                                   "audio [b, samples], not latents: pass the raw audio, or `pitch=` [b, 1, T_mel]")
                     with torch.no_grad():                                             # one value per AudioToMel frame, Hz, 0 unvoiced
-                        pitch = self.pitch_extractor(audio)[:, None]
+                        pitch = self.pitch_extractor(audio, **({} if sample_lens is None else dict(lens=sample_lens)))[:, None]
                 if pitch is None:
                     raise NotImplementedError("forward(text=...) without `pitch` needs the pyworld / kaldi pitch extraction "
                                               "(NS2:1546-1559), which is outside the HIP hot path: pass `pitch=` [b, 1, T_mel]")
                 if mel is None:                                                       # NS2:1561-1567; mel_lens default to full
                     with torch.no_grad():
-                        mel = self.audio_to_mel(audio)[..., :pitch.shape[-1]]
+                        mel = self.audio_to_mel(audio, **({} if sample_lens is None else dict(lens=sample_lens)))[..., :pitch.shape[-1]]
+                if mel_lens is None and sample_lens is not None:                      # the utterances' own frames (no host read)
+                    mel_lens = 1 + sample_lens.long() // self.mel_hop_length
                 cond, aux = self.text_forward_cond(text, text_lens, mel, mel_lens, pitch, p_enc, return_aux_losses)
             if cond is None:
                 raise NotImplementedError(
@@ -605,6 +641,6 @@ class NaturalSpeech2(nn.Module):
         x_start = {"x0": lambda: pred, "eps": lambda: _safe_div(audio - sigma * pred, alpha),
                    "v": lambda: alpha * audio - sigma * pred}[self.objective]()
         assert self.codec is not None and hasattr(self.codec, "rq"), "the RVQ cross-entropy term needs codec.rq (NS2:1682)"
-        _, ce_loss = self.codec.rq(x_start, codes)
+        _, ce_loss = self.codec.rq(x_start, codes, **({} if audio_lens is None else dict(lens=audio_lens)))
         loss = loss + self.rvq_cross_entropy_loss_weight * ce_loss                    # NS2:1684 (duration_pitch_loss is 0 upstream)
         return loss if aux is None else (loss, aux)

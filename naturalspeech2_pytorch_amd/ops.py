@@ -495,10 +495,12 @@ def rvq_decode(codes: torch.Tensor, codebooks: torch.Tensor) -> torch.Tensor:
 
 
 def rvq_cross_entropy(x: torch.Tensor, codebooks: torch.Tensor, cb_norm: Optional[torch.Tensor], indices: torch.Tensor, need_grad: bool,
-                       need_quantized: bool = True):
+                       need_quantized: bool = True, lens: Optional[torch.Tensor] = None):
     """the RVQ cross-entropy of the training loss in one launch (ns2_rvq_ce, csrc/rvq_ce.hip): x [M, 128] fp32, codebooks [Q, C, 128],
     indices [M, Q] int64 -> (loss 0-dim, row_loss [M, Q], quantized_out [M, 128] or None, G [M, 128] = d loss / d x or None).
-    An index outside [0, C) gives a NaN loss; nothing is read back to the host."""
+    An index outside [0, C) gives a NaN loss; nothing is read back to the host.
+    lens [B] (a CUDA integer tensor; M = B n): the ragged batch of ns2_rvq_ce_lens (include/ns2hip_ragged_audio.h) -- the loss is the mean
+    over utterances of each one's own mean, and every output row at or behind a length is 0 whatever x and indices hold there."""
     x, cb = _f32(x), _f32(codebooks)
     M, D = x.shape
     Q, C, _ = cb.shape
@@ -512,6 +514,13 @@ def rvq_cross_entropy(x: torch.Tensor, codebooks: torch.Tensor, cb_norm: Optiona
     grad = torch.empty(M, D, dtype=torch.float32, device=x.device) if need_grad else None
     nbytes = lib.ns2_rvq_ce_workspace_bytes(M, Q, int(need_quantized))
     ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device) if nbytes else None
+    if lens is not None:
+        ln = _lens(lens)              # held until the launch
+        B = ln.shape[0]
+        assert B > 0 and M % B == 0, f"lens [{B}] must divide the {M} rows into utterances of equal padded length"
+        check(lib.ns2_rvq_ce_lens(x.data_ptr(), cb.data_ptr(), cb_norm.data_ptr(), idx.data_ptr(), row_loss.data_ptr(), loss.data_ptr(),
+                                  _p(quant), _p(grad), B, M // B, ln.data_ptr(), Q, C, D, _p(ws), nbytes, _stream()), "ns2_rvq_ce_lens")
+        return loss[0], row_loss, quant, grad
     check(lib.ns2_rvq_ce(x.data_ptr(), cb.data_ptr(), cb_norm.data_ptr(), idx.data_ptr(), row_loss.data_ptr(), loss.data_ptr(), _p(quant),
                          _p(grad), M, Q, C, D, _p(ws), nbytes, _stream()), "ns2_rvq_ce")
     return loss[0], row_loss, quant, grad
@@ -598,16 +607,26 @@ def expand_backward(d_cond: torch.Tensor, duration: torch.Tensor, pitch: torch.T
 
 
 # ---- AudioToMel (csrc/audio_to_mel.hip)
-def audio_to_mel(audio: torch.Tensor, n_fft: int, hop_length: int, n_mels: int, log: bool, plan: dict) -> torch.Tensor:
+def audio_to_mel(audio: torch.Tensor, n_fft: int, hop_length: int, n_mels: int, log: bool, plan: dict,
+                 lens: Optional[torch.Tensor] = None) -> torch.Tensor:
     """audio [B, L] fp32 -> [B, n_mels, 1 + L // hop_length] (ns2_audio_to_mel); `plan`: the device tables of
-    audio_to_mel._plan (window, twiddle, meta, weights) and their sizes n_w, n_bins"""
+    audio_to_mel._plan (window, twiddle, meta, weights) and their sizes n_w, n_bins.
+    lens [B] (a CUDA integer tensor of sample counts): ns2_audio_to_mel_lens (include/ns2hip_ragged_audio.h)"""
     audio = _f32(audio)
     B, L = audio.shape
     T = 1 + L // hop_length
     out = torch.empty(B, n_mels, T, dtype=torch.float32, device=audio.device)
     lib = _lib.load()
+    ln = None if lens is None else _lens(lens)     # held until the launch
+    assert ln is None or ln.shape[0] == B, f"lens must hold one sample count per utterance: [{B}]"
     for b0 in range(0, B, 65535):                 # grid.y holds at most 65535 utterances
         nb = min(65535, B - b0)
+        if lens is not None:
+            check(lib.ns2_audio_to_mel_lens(audio[b0].data_ptr(), nb, L, n_fft, hop_length, plan["window"].data_ptr(),
+                                            plan["twiddle"].data_ptr(), plan["meta"].data_ptr(), plan["weights"].data_ptr(), plan["n_w"],
+                                            n_mels, plan["n_bins"], int(bool(log)), out[b0].data_ptr(), ln[b0:].data_ptr(), _stream()),
+                  "ns2_audio_to_mel_lens")
+            continue
         check(lib.ns2_audio_to_mel(audio[b0].data_ptr(), nb, L, n_fft, hop_length, plan["window"].data_ptr(),
                                    plan["twiddle"].data_ptr(), plan["meta"].data_ptr(), plan["weights"].data_ptr(), plan["n_w"],
                                    n_mels, plan["n_bins"], int(bool(log)), out[b0].data_ptr(), _stream()), "ns2_audio_to_mel")
@@ -615,14 +634,22 @@ def audio_to_mel(audio: torch.Tensor, n_fft: int, hop_length: int, n_mels: int, 
 
 
 # ---- PitchExtractor (csrc/pitch.hip)
-def pitch_yin(audio: torch.Tensor, sample_rate: int, hop_length: int, tau_min: int, tau_max: int, threshold: float) -> torch.Tensor:
-    """audio [B, L] fp32 -> f0 [B, 1 + L // hop_length] in Hz, 0 where unvoiced (ns2_pitch_yin, include/ns2hip_pitch.h)"""
+def pitch_yin(audio: torch.Tensor, sample_rate: int, hop_length: int, tau_min: int, tau_max: int, threshold: float,
+              lens: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """audio [B, L] fp32 -> f0 [B, 1 + L // hop_length] in Hz, 0 where unvoiced (ns2_pitch_yin, include/ns2hip_pitch.h).
+    lens [B] (a CUDA integer tensor of sample counts): ns2_pitch_yin_lens (include/ns2hip_ragged_audio.h)"""
     audio = _f32(audio)
     B, L = audio.shape
     out = torch.empty(B, 1 + L // hop_length, dtype=torch.float32, device=audio.device)
     lib = _lib.load()
+    ln = None if lens is None else _lens(lens)     # held until the launch
+    assert ln is None or ln.shape[0] == B, f"lens must hold one sample count per utterance: [{B}]"
     for b0 in range(0, B, 65535):                 # grid.y holds at most 65535 utterances
         nb = min(65535, B - b0)
+        if lens is not None:
+            check(lib.ns2_pitch_yin_lens(audio[b0].data_ptr(), nb, L, sample_rate, hop_length, tau_min, tau_max, threshold,
+                                         out[b0].data_ptr(), ln[b0:].data_ptr(), _stream()), "ns2_pitch_yin_lens")
+            continue
         check(lib.ns2_pitch_yin(audio[b0].data_ptr(), nb, L, sample_rate, hop_length, tau_min, tau_max, threshold, out[b0].data_ptr(),
                                 _stream()), "ns2_pitch_yin")
     return out

@@ -30,6 +30,11 @@ never carries a gradient (the reference's pitch does not either).  The composite
 training batches: it materialises every (frame, lag, sample) difference, about 32 MiB per pass of a Python loop (36 frames at the
 defaults, some 1800 passes for 32 utterances of 13.6 s).  The module has no parameters and no buffers, and `forward`
 reads nothing back from the device.
+
+`forward(audio, lens=)` is the ragged batch: sample counts per utterance, integer [b].  Frame t of utterance i reads zeros outside
+[0, lens[i]), so frames t < T_i = 1 + lens[i] // hop_length are those of the module on `audio[i, :lens[i]]` alone, and frames from T_i
+on are exactly 0 (unvoiced).  On a GPU that is ns2_pitch_yin_lens (include/ns2hip_ragged_audio.h): the lengths stay on the device and a
+value outside [1, L] is clamped into it.  The composite does the same per utterance (slice, compute, zero-fill) and reads the lengths.
 """
 import math
 
@@ -103,13 +108,19 @@ class PitchExtractor(nn.Module):
     def hip_supported(self) -> bool:
         return self.tau_max <= TAU_MAX_HIP
 
-    def forward(self, audio: torch.Tensor) -> torch.Tensor:
-        """audio [..., L] -> f0 [..., 1 + L // hop_length] fp32, Hz, 0 where unvoiced; never carries a gradient"""
+    def forward(self, audio: torch.Tensor, lens=None) -> torch.Tensor:
+        """audio [..., L] -> f0 [..., 1 + L // hop_length] fp32, Hz, 0 where unvoiced; never carries a gradient.
+        lens: sample counts [b] of a ragged batch [b, L] (module docstring)"""
         grad = audio.requires_grad and torch.is_grad_enabled()    # under autograd: the composite, as AudioToMel does
+        if lens is not None:
+            lens = torch.as_tensor(lens)
+            if audio.ndim != 2 or lens.dtype.is_floating_point or lens.dtype == torch.bool or lens.shape != (audio.shape[0],):
+                raise ValueError(f"PitchExtractor(lens=) takes audio [b, L] and one integer sample count per utterance [b], got "
+                                 f"{list(audio.shape)} and {lens.dtype} {list(lens.shape)}")
         with torch.no_grad():
-            return self._forward(audio.detach().float(), grad)
+            return self._forward(audio.detach().float(), grad, lens)
 
-    def _forward(self, audio, grad):
+    def _forward(self, audio, grad, lens=None):
         shape = audio.shape
         if shape[-1] < 1:
             raise ValueError("PitchExtractor needs at least one sample")
@@ -118,7 +129,14 @@ class PitchExtractor(nn.Module):
         if x.shape[0] == 0:
             return audio.new_zeros(shape[:-1] + (T,))
         args = (self.sample_rate, self.hop_length, self.tau_min, self.tau_max, self.threshold)
-        if x.is_cuda and not grad and self.hip_supported():
+        if lens is not None and x.is_cuda and not grad and self.hip_supported():
+            f0 = ops.pitch_yin(x.contiguous(), *args, lens=lens.to(x.device))
+        elif lens is not None:                                    # per utterance: slice, the composite, zero-fill (reads the lengths)
+            f0 = x.new_zeros(x.shape[0], T)
+            for i, s in enumerate(lens.tolist()):
+                s = min(max(int(s), 1), shape[-1])                # as the kernel clamps
+                f0[i, :1 + s // self.hop_length] = yin_composite(x[i:i + 1, :s], *args)[0][0]
+        elif x.is_cuda and not grad and self.hip_supported():
             f0 = ops.pitch_yin(x.contiguous(), *args)
         else:
             f0 = yin_composite(x, *args)[0]

@@ -161,10 +161,10 @@ class HipBackend:
         return d_log
 
     # ---- the RVQ cross-entropy term of the training loss (codec.py ResidualVQCrossEntropy; csrc/rvq_ce.hip)
-    def rvq_cross_entropy(self, x, codebooks, cb_norm, indices, need_grad=True):
+    def rvq_cross_entropy(self, x, codebooks, cb_norm, indices, need_grad=True, lens=None):
         """x [M, 128] fp32, indices [M, Q] int64 -> (loss 0-dim, quantized_out [M, 128], G [M, 128] = d loss / d x or None); fp32 whatever
-        the arithmetic of the pass"""
-        loss, _, quant, G = ops.rvq_cross_entropy(x, codebooks, cb_norm, indices, need_grad)
+        the arithmetic of the pass.  lens [B] int32 on the device: the ragged batch of ns2_rvq_ce_lens (M = B n)"""
+        loss, _, quant, G = ops.rvq_cross_entropy(x, codebooks, cb_norm, indices, need_grad, **({} if lens is None else dict(lens=lens)))
         return loss, quant, G
 
     def embedding(self, ids, table, pad_id):

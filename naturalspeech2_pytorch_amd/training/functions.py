@@ -450,12 +450,15 @@ class RvqCrossEntropyFn(torch.autograd.Function):
     """the RVQ cross-entropy term of the training loss (NS2:1668-1684; codec.py `ResidualVQCrossEntropy`): x [M, 128] fp32, codebooks [Q, C, 128]
     and their half-norms [Q, C], indices [M, Q] int64 -> (loss 0-dim, quantized_out [M, 128]).  One launch (ns2_rvq_ce) computes the loss and
     the unit gradient G = d loss / d x, the only tensor kept; the backward is grad_out * G.  The codebooks are buffers and the indices
-    integers: neither gets a gradient; quantized_out is a sum of (detached) codes."""
+    integers: neither gets a gradient; quantized_out is a sum of (detached) codes.
+    lens [B] int32 on the device (M = B n; None: today's call): the ragged batch of ns2_rvq_ce_lens -- the loss is the mean over utterances
+    of each one's own mean, G's rows at or behind a length are exact zeros, and nothing reads the lengths on the host."""
 
     @staticmethod
-    def forward(ctx, x, codebooks, cb_norm, indices):
+    def forward(ctx, x, codebooks, cb_norm, indices, lens=None):
         bk = _begin(ctx)
-        loss, quant, G = bk.rvq_cross_entropy(x, codebooks, cb_norm, indices, need_grad=ctx.needs_input_grad[0])
+        kw = {} if lens is None else dict(lens=lens)
+        loss, quant, G = bk.rvq_cross_entropy(x, codebooks, cb_norm, indices, need_grad=ctx.needs_input_grad[0], **kw)
         ctx.save_for_backward(G)
         ctx.mark_non_differentiable(quant)
         return loss, quant
@@ -463,7 +466,7 @@ class RvqCrossEntropyFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_loss, _g_quant):
         G, = ctx.saved_tensors
-        return (g_loss * G if G is not None else None), None, None, None
+        return (g_loss * G if G is not None else None), None, None, None, None
 
 
 class GroupNormSiluFn(torch.autograd.Function):
