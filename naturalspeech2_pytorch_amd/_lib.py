@@ -1,7 +1,8 @@
 """ctypes binding of libns2hip.so, derived from its C ABI: include/ns2hip.h (and include/ns2hip_optim.h, the optimizer step, and
 include/ns2hip_pitch.h, the pitch extractor, include/ns2hip_ragged.h, ragged batches, include/ns2hip_ragged_front.h, ragged prompts
 and text, include/ns2hip_ragged_train.h, ragged training batches, include/ns2hip_head_dim_train.h, training at head dims 32 and 128, and
-include/ns2hip_ragged_audio.h, ragged raw audio, each into tables of its own) is parsed once, at import.
+include/ns2hip_ragged_audio.h, ragged raw audio, and include/ns2hip_fold.h, the feed-forward fold, each into tables of its own) is
+parsed once, at import.
 
 The HIP library is the product: importing this module FAILS LOUDLY when the header or the shared object is missing or the
 library does not export the full ABI -- there is no CPU / PyTorch fallback for the hot path.
@@ -34,6 +35,7 @@ FRONT_HEADER_PATH = os.path.join(_HERE, "..", "include", "ns2hip_ragged_front.h"
 RAGGED_TRAIN_HEADER_PATH = os.path.join(_HERE, "..", "include", "ns2hip_ragged_train.h")   # ... in the training pass: likewise
 HEAD_DIM_TRAIN_HEADER_PATH = os.path.join(_HERE, "..", "include", "ns2hip_head_dim_train.h")   # training at head dims 32 / 128: likewise
 RAGGED_AUDIO_HEADER_PATH = os.path.join(_HERE, "..", "include", "ns2hip_ragged_audio.h")   # lengths in mel, pitch and the RVQ term: likewise
+FOLD_HEADER_PATH = os.path.join(_HERE, "..", "include", "ns2hip_fold.h")   # the feed-forward fold: likewise
 
 
 class Ns2Error(RuntimeError):
@@ -152,6 +154,11 @@ if not os.path.exists(RAGGED_AUDIO_HEADER_PATH):
 with open(RAGGED_AUDIO_HEADER_PATH) as _f:
     _, _, RAGGED_AUDIO_SIGNATURES = parse_header(_f.read())
 
+if not os.path.exists(FOLD_HEADER_PATH):
+    raise Ns2Error(f"{FOLD_HEADER_PATH} not found: the binding is derived from the header, it ships with the package's source tree")
+with open(FOLD_HEADER_PATH) as _f:
+    _, _, FOLD_SIGNATURES = parse_header(_f.read())
+
 _lib = None
 
 
@@ -165,7 +172,7 @@ def load():
                        f"(or naturalspeech2_pytorch_amd/csrc/build.sh); there is no fallback path")
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in {**SIGNATURES, **OPTIM_SIGNATURES, **PITCH_SIGNATURES, **RAGGED_SIGNATURES, **FRONT_SIGNATURES,
-                              **RAGGED_TRAIN_SIGNATURES, **HEAD_DIM_TRAIN_SIGNATURES, **RAGGED_AUDIO_SIGNATURES}.items():
+                              **RAGGED_TRAIN_SIGNATURES, **HEAD_DIM_TRAIN_SIGNATURES, **RAGGED_AUDIO_SIGNATURES, **FOLD_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -220,3 +227,8 @@ def head_dim_train_header_symbols():
 def ragged_audio_header_symbols():
     """Symbols declared in include/ns2hip_ragged_audio.h"""
     return sorted(RAGGED_AUDIO_SIGNATURES)
+
+
+def fold_header_symbols():
+    """Symbols declared in include/ns2hip_fold.h"""
+    return sorted(FOLD_SIGNATURES)

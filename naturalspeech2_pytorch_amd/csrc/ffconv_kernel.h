@@ -1,7 +1,8 @@
 // The feed-forward causal conv as a kernel of its own (round 6):  out[m, n] = bias[n] + sum_{tap, c} A[m - (2 - tap), c] W[n, c, tap]
 // with rows in front of the utterance read as zeros -- FeedForward's CausalConv1d(f, f, 3), NS2:1016 / 583-595 -- for the plans whose
 // conv runs as ONE IEEE-half product (model precisions 2, 5, 6): dense half activations [M, lda] x half weights -> FMT_H8 lines or
-// dense half planes.  43 % of the step's FLOPs go through it.
+// dense half planes, or (PF_F32, the feed-forward fold of model_exec.cpp: the conv folded with the Linear behind it, N = dim) fp32 rows
+// + residual.  43 % of the step's FLOPs went through it unfolded, a third of that folded.
 //
 // Why not another instantiation of gemm2_kernel: that kernel's steady-state loop carried its generality inside the loop (680
 // instructions per 96 MFMAs at 253 VGPRs and 137 spilled SGPRs: tap arithmetic, zero-page selects, 64-bit per-lane addresses,
@@ -39,10 +40,14 @@
 #pragma once
 #include <algorithm>
 
-#include "gemm_epi_fast.h"
+#include "gemm_epi_dispatch.h"
 
 namespace ns2 {
 namespace ffc3 {
+
+// third output mode beside the plane formats PF_H8 / PF_F16 (gemm_epi_fast.h): fp32 out = acc + bias (+ resid), the EPI_F32 epilogue --
+// the feed-forward's causal conv folded with the Linear behind it writes the residual stream (model_exec.cpp, "the fold")
+constexpr int PF_F32 = 8;
 
 constexpr int RB = 128;                       // LDS row bytes = 64 halves = one K tile of one row
 constexpr int A_ROWS = 264;                   // A'(it): input rows m0 - 8 ... m0 + 255 (33 pieces of 8 rows)
@@ -62,6 +67,9 @@ struct Args {                    // 16 dwords
   int seq_len, tpt;              // tpt = lda / 64 K tiles per tap (even)
   int kv;                        // columns per tap that hold data (a multiple of 32, lda - 127 ... lda): K tiles beyond are not multiplied
   int out_ncols;                 // columns [N, out_ncols) are written as zeros
+  // PF_F32 only (behind the 16 dwords the plane modes read): out is fp32 [M, ldo]; resid [M, ldr] fp32 or null
+  const float* resid;
+  int ldr;
 };
 
 // ---- LDS-DMA as inline assembly: the compiler must not count these loads (its waitcnt pass drains every outstanding one with
@@ -260,17 +268,28 @@ struct Kern {
     if constexpr (!ACTIVE) return;
     // ---- epilogue: bias + plane conversion through the wave's private 18 KiB of LDS (gemm_epi_fast.h), edge tiles on the generic path
     const int row_base = m0 + wm * 128, col_base = tn * 256 + wn * 64;
-    if (col_base >= max(g.N, g.out_ncols)) return;
-    GemmArgs ga{};
-    ga.M = g.M; ga.N = g.N; ga.bias = g.bias; ga.out_hi = g.out; ga.out_lo = (PF == PF_H8) ? g.out + 32 : nullptr;
-    ga.ldo_s = g.ldo; ga.out_ncols = g.out_ncols; ga.out_fmt = (PF == PF_H8) ? FMT_H8 : FMT_F16; ga.epi = EPI_SPLIT;
-    if (col_base + 64 <= g.N) epi_planes_fast<PF, true>(c.acc, ga, 0, row_base, col_base, lane, smem + wave * EPI_LDS_WAVE_BYTES);
-    else gemm_epilogue<EPI_SPLIT, 4>(c.acc, ga, 0, row_base, col_base, 0, lane);
+    if constexpr (PF == PF_F32) {
+      // the epilogue layer's own decision (gemm_epi_dispatch.h): the staged fp32 tile, its EDGE variant on a ragged last column tile --
+      // what gemm2_kernel's EPI_F32 instantiations run, so a row's bits do not depend on the kernel that computed it
+      if (col_base >= g.N) return;
+      GemmArgs ga{};
+      ga.M = g.M; ga.N = g.N; ga.bias = g.bias; ga.resid = g.resid; ga.ldr = g.ldr;
+      ga.out_f = reinterpret_cast<float*>(g.out); ga.ldo_f = g.ldo; ga.epi = EPI_F32;
+      wave_tile_epilogue<EPI_F32, 4, EpiFormats<true, false, false>, EPI_LDS_WAVE_BYTES>(c.acc, ga, 0, row_base, col_base, 0, lane,
+                                                                                         smem + wave * EPI_LDS_WAVE_BYTES);
+    } else {
+      if (col_base >= max(g.N, g.out_ncols)) return;
+      GemmArgs ga{};
+      ga.M = g.M; ga.N = g.N; ga.bias = g.bias; ga.out_hi = g.out; ga.out_lo = (PF == PF_H8) ? g.out + 32 : nullptr;
+      ga.ldo_s = g.ldo; ga.out_ncols = g.out_ncols; ga.out_fmt = (PF == PF_H8) ? FMT_H8 : FMT_F16; ga.epi = EPI_SPLIT;
+      if (col_base + 64 <= g.N) epi_planes_fast<PF, true>(c.acc, ga, 0, row_base, col_base, lane, smem + wave * EPI_LDS_WAVE_BYTES);
+      else gemm_epilogue<EPI_SPLIT, 4>(c.acc, ga, 0, row_base, col_base, 0, lane);
+    }
   }
 
   static NS2_DEVINL void run(const Args& g) {
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int ncols = max(g.N, g.out_ncols);
+    const int ncols = PF == PF_F32 ? g.N : max(g.N, g.out_ncols);
     const int ntn = (ncols + 255) >> 8;
     const int bid = xcd_remap(blockIdx.x, gridDim.x);             // column tile fastest: the six blocks of a row tile share A' in one XCD's L2
     const int tn = __builtin_amdgcn_readfirstlane(bid % ntn), tm = __builtin_amdgcn_readfirstlane(bid / ntn);
@@ -326,11 +345,14 @@ inline hipError_t launch_ffconv3_tile(const bf16_t* w_hi, int ldw, int Cp, int r
 
 // Does this product take the dedicated kernel?  (launch_gemm asks; everything else keeps gemm2_kernel / gemm_kernel)
 inline bool ffconv3_eligible(const GemmArgs& g, int precision) {
-  if (!g.w_t3 || precision != 2 || g.epi != EPI_SPLIT || g.conv_taps != 3 || g.nkt != 3 * g.kt_per_tap || g.dil != 1 || g.dil_z) return false;
+  if (!g.w_t3 || precision != 2 || (g.epi != EPI_SPLIT && g.epi != EPI_F32) || g.conv_taps != 3 || g.nkt != 3 * g.kt_per_tap || g.dil != 1 || g.dil_z) return false;
   if (g.nz > 1 || g.pad_left >= 0 || g.act != 0 || g.ksplit != 0 || g.a_lo || g.w_lo) return false;
   if (g.seq_len <= 0 || (g.seq_len & 255) || g.M <= 0 || (g.M & 255)) return false;
   const int Cp = g.kt_per_tap * 32, tpt = ffconv3_tiles_per_tap(Cp);
   if (g.lda != tpt * 64 || (reinterpret_cast<uintptr_t>(g.a_hi) & 15)) return false;
+  if (g.epi == EPI_F32)      // fp32 rows (+ residual) the staged epilogue can store as 16-byte chunks; a fused norm keeps the routes that own whole rows
+    return g.out_f && !g.nrm_hi && g.out_f_zs == 0 && (g.ldo_f & 3) == 0 && (reinterpret_cast<uintptr_t>(g.out_f) & 15) == 0 &&
+           (!g.resid || ((g.ldr & 3) == 0 && (reinterpret_cast<uintptr_t>(g.resid) & 15) == 0));
   if (!g.out_hi || (reinterpret_cast<uintptr_t>(g.out_hi) & 15) || (g.ldo_s & 31) || g.out_ncols > g.ldo_s) return false;
   if ((std::max(g.N, g.out_ncols) + 255) / 256 != (g.N + 255) / 256) return false;      // the zero columns beyond N stay inside the image's last column tile
   if (g.out_fmt == FMT_H8) return g.out_lo == g.out_hi + 32;
@@ -342,7 +364,15 @@ inline hipError_t launch_ffconv3(const GemmArgs& g, hipStream_t s) {
   a.A = reinterpret_cast<const unsigned char*>(g.a_hi); a.Wt = reinterpret_cast<const unsigned char*>(g.w_t3);
   a.bias = g.bias; a.out = g.out_hi;
   a.M = g.M; a.N = g.N; a.lda = g.lda; a.ldo = g.ldo_s; a.seq_len = g.seq_len; a.tpt = g.lda / 64; a.kv = g.kt_per_tap * 32;
-  a.out_ncols = g.out_ncols;
+  a.out_ncols = g.out_ncols; a.resid = nullptr; a.ldr = 0;
+  if (g.epi == EPI_F32) {
+    a.out = reinterpret_cast<bf16_t*>(g.out_f); a.ldo = g.ldo_f; a.out_ncols = g.N; a.resid = g.resid; a.ldr = g.ldr;
+    static DynLdsAttr attr_f32;
+    const hipError_t e = attr_f32.ensure(reinterpret_cast<const void*>(&ffc3::ffconv3_kernel<ffc3::PF_F32>), ffc3::LDS_BYTES);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(ffc3::ffconv3_kernel<ffc3::PF_F32>, dim3(((g.N + 255) / 256) * (g.M / 256)), dim3(512), ffc3::LDS_BYTES, s, a);
+    return hipGetLastError();
+  }
   const int ntn = (std::max(g.N, g.out_ncols) + 255) / 256, grid = ntn * (g.M / 256);
   const bool h8 = g.out_fmt == FMT_H8;
   static DynLdsAttr attr_h8, attr_f16;

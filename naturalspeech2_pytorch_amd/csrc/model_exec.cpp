@@ -22,6 +22,7 @@
 #include <string>
 #include <vector>
 
+#include "../../include/ns2hip_fold.h"
 #include "../../include/ns2hip_ragged.h"
 #include "../../include/ns2hip_ragged_front.h"
 #include "ns2_host.h"
@@ -73,8 +74,15 @@ struct ns2_model {
   struct Layer {
     PackedW qkv, out, ffin, conv, ffout, cq, ckv, cout;
     float* b_ffin; const float* b_conv; const float* b_ffout;
+    PackedW fffold; float* b_fold = nullptr;      // the fold (below): conv and ffout as ONE causal conv f -> dim; then conv / ffout stay empty
   };
   std::vector<Layer> layers;
+  // The fold: FeedForward is Sequential(Linear, GEGLU, CausalConv1d(f, f, 3), Linear(f, dim)) (NS2:1009-1025) with nothing between the conv
+  // and the last Linear, so the pair is one causal conv of kernel 3 from f to dim channels, W'[n, c, t] = sum_j W_out[n, j] W_conv[j, c, t]
+  // (zero padding in front of an utterance included: the padded input is the same).  ns2_model_finalize folds the fp32 parameters once
+  // (elementwise.hip ff_fold_kernel) and packs W' in the conv site's format; a step then runs 2 M 3f dim FLOPs per layer instead of
+  // 2 M f (3f + dim) and the conv's output planes do not exist.  false (ns2_debug_force_fold(0) / NS2_FOLD=0 at finalize): both products.
+  bool fold = false;
   const float* g_pred; PackedW w_pred;
   // conditional-only
   float* wt_prompt; const float* b_prompt; const float* null_prompt_cond; const float* null_prompt_tokens;
@@ -114,8 +122,8 @@ static int dev_alloc(std::vector<void*>* owned, void** p, size_t bytes) {
 struct PackCtx { std::vector<void*>* owned; bool il; int fmt; };   // il: interleaved 128-B lines (bf16 hi/lo or FMT_H8); fmt: PlaneFmt
 // Model precision 5 ("hybrid") is a per-site plan on top of precision 4: every contraction keeps the fp8 correction terms
 // except (a) the feed-forward causal conv (43 % of the FLOPs), which runs as ONE IEEE-half product: its input arrives as dense
-// half planes from the GEGLU epilogue and it writes FMT_H8 lines for FF-out; (b) the dilated k = 3 convs of the Wavenet
-// blocks (16 % of the FLOPs), which multiply the half parts of the same FMT_H8 operands as one product while the block's
+// half planes from the GEGLU epilogue and it writes FMT_H8 lines for FF-out (folded with FF-out, ns2_model::fold: the residual
+// stream in fp32); (b) the dilated k = 3 convs of the Wavenet blocks (16 % of the FLOPs), which multiply the half parts of the same FMT_H8 operands as one product while the block's
 // res_conv keeps the correction terms (gemm2.hip, P1).  tools/precision_study.py: these are the two sites whose rounding
 // error reaches the output least (4.1e-5 -> 9.4e-5 for both at d128; every other site costs 1.6e-4 ... 3.5e-4).
 // Model precision 6 ("hybrid_ff") extends the plan to the whole feed-forward branch: FF-in (+ GEGLU) and FF-out run as one IEEE-half
@@ -278,6 +286,25 @@ GemmArgs gemm_args(const PackedW& w, const bf16_t* a_hi, const bf16_t* a_lo, int
 
 // ================================================================================================ model
 
+// Test hook (ns2_debug_force_fold / NS2_FOLD) in the manner of gemm2.hip's gemm_hook(): process-wide, atomic, read by ns2_model_finalize
+// (and by ns2_debug_chain_rule, which shapes a model as a finalize would).  -1: read NS2_FOLD once; 0: the feed-forward's causal conv and
+// FF-out stay two products; 1 (the default): they are folded into one (ns2_model::fold).
+static std::atomic<int> g_forced_fold{-1};
+static bool fold_wanted() {
+  int f = g_forced_fold.load(std::memory_order_relaxed);
+  if (f < 0) {
+    const char* e = getenv("NS2_FOLD");
+    f = (e && atoi(e) == 0) ? 0 : 1;
+    g_forced_fold.store(f, std::memory_order_relaxed);
+  }
+  return f != 0;
+}
+extern "C" int ns2_debug_force_fold(int fold) {
+  ARGCHK(fold == 0 || fold == 1, "ns2_debug_force_fold: 0 = the causal conv and FF-out as two products, 1 = folded into one");
+  g_forced_fold.store(fold, std::memory_order_relaxed);
+  return NS2_OK;
+}
+
 static const Param* find_param(const ns2_model* m, const std::string& k) {
   auto it = m->params.find(k);
   return it == m->params.end() ? nullptr : &it->second;
@@ -353,6 +380,7 @@ extern "C" int ns2_model_finalize(ns2_model* m, void* stream) {
   const PackCtx pc_ff = ff_half_plan(m->cfg.precision) ? pack_ctx_for(&m->owned, 2) : pc;       // FF-in / FF-out weights
   const PackCtx pc_cond = pack_ctx_for(&m->owned, cond_precision(op_precision(m->cfg.precision)));   // weights of prepare_cond
   const bool il = pc.il;
+  m->fold = fold_wanted();
 
   // ---- time conditioning (NS2:839-843)
   { GETP(fw, "to_time_cond.0.weights"); m->freqs = fw->p; }
@@ -426,6 +454,7 @@ extern "C" int ns2_model_finalize(ns2_model* m, void* stream) {
 
   // ---- transformer (NS2:748-809)
   m->layers.resize(m->cfg.depth);
+  struct FoldScratch { float* p = nullptr; ~FoldScratch() { if (p) (void)hipFree(p); } } w_fold;   // one layer's folded fp32 weight [dim, f, 3]
   for (int l = 0; l < m->cfg.depth; ++l) {
     ns2_model::Layer& ly = m->layers[l];
     snprintf(key, sizeof key, "transformer.layers.%d", l);
@@ -447,9 +476,21 @@ extern "C" int ns2_model_finalize(ns2_model* m, void* stream) {
       if (w1->dims[0] != 2 * f) { set_error("FF inner dim mismatch: expected %d got %lld", 2 * f, (long long)w1->dims[0]); return NS2_ERR_STATE; }
       NSCHK(pack_geglu(pc_ff, &ly.ffin, w1->p, f, dim, s));
       NSCHK(pack_geglu_bias(&m->owned, &ly.b_ffin, b1->p, f, ly.ffin.rows_p));
-      NSCHK(pack_linear(pc_conv, &ly.conv, cw->p, f, f, 3, s)); ly.b_conv = cb->p;
-      if (pc_conv.fmt == FMT_F16) NSCHK(build_conv3_tiles(&m->owned, &ly.conv, s));
-      NSCHK(pack_linear(pc_ff, &ly.ffout, w2->p, dim, f, 1, s)); ly.b_ffout = b2->p; }
+      ly.b_conv = cb->p; ly.b_ffout = b2->p;
+      if (m->fold) {
+        if (cw->dims.size() != 3 || cw->dims[0] != f || cw->dims[1] != f || cw->dims[2] != 3 || w2->dims[0] != dim || w2->dims[1] != f) {
+          set_error("FF conv / FF-out weights have unexpected shapes"); return NS2_ERR_STATE;
+        }
+        if (!w_fold.p) HIPRET(hipMalloc((void**)&w_fold.p, (size_t)dim * f * 3 * sizeof(float)));
+        NSCHK(dev_alloc(&m->owned, (void**)&ly.b_fold, dim * sizeof(float)));
+        HIPRET(launch_ff_fold(w2->p, cw->p, cb->p, b2->p, dim, f, w_fold.p, ly.b_fold, s));
+        NSCHK(pack_linear(pc_conv, &ly.fffold, w_fold.p, dim, f, 3, s));       // (synchronises: the scratch is free for the next layer)
+        if (pc_conv.fmt == FMT_F16) NSCHK(build_conv3_tiles(&m->owned, &ly.fffold, s));
+      } else {
+        NSCHK(pack_linear(pc_conv, &ly.conv, cw->p, f, f, 3, s));
+        if (pc_conv.fmt == FMT_F16) NSCHK(build_conv3_tiles(&m->owned, &ly.conv, s));
+        NSCHK(pack_linear(pc_ff, &ly.ffout, w2->p, dim, f, 1, s));
+      } }
   }
   { GETP(g, "transformer.to_pred.0.gamma"); GETP(w, "transformer.to_pred.1.weight");
     m->g_pred = g->p; NSCHK(pack_linear(pc, &m->w_pred, w->p, dim, dim, 1, s)); }
@@ -616,7 +657,8 @@ static int64_t carve_work(const ns2_model* m, Work* w, void* base, int64_t cap, 
   w->vt = take_planes(c, (int64_t)B * a * w->Nkp, ail, afmt);
   w->o = take_planes(c, Mq * a, il, f16);
   w->ffh = take_planes(c, Mq * std::max(fp, m->fpc), il, f16);      // (the conv's dense-half input view has rows of fpc elements)
-  w->ffc = take_planes(c, M * fp, il, f16);
+  if (m->fold) w->ffc = Planes{nullptr, nullptr, f16};      // the conv's output planes do not exist: the folded conv writes the residual stream
+  else w->ffc = take_planes(c, M * fp, il, f16);
   if (m->cfg.condition_on_prompt && n_prompt > 0) {
     const int Lm = m->Lm;
     const Fmts CF = fmts_for(cond_precision(op_precision(m->cfg.precision)));     // formats of the prepare_cond pass
@@ -1002,7 +1044,7 @@ void describe_rows(const ns2_model* m, const Work& w0, const CondState* cs, cons
   float* xres = w0.xres + r0 * dim;
   const float* call = st.call + (size_t)b0 * cld;
   const Planes xs = rows_of(w0.xs, r0, dp), h0 = rows_of(w0.h0, r0, dp), ssum = rows_of(w0.ssum, r0, dp), xn = rows_of(w0.xn, r0, dp);
-  const Planes qk = rows_of(w0.qk, r0, 2 * a), o = rows_of(w0.o, r0, a), ffc = rows_of(w0.ffc, r0, fp);
+  const Planes qk = rows_of(w0.qk, r0, 2 * a), o = rows_of(w0.o, r0, a), ffc = m->fold ? w0.ffc : rows_of(w0.ffc, r0, fp);
   const Planes vt = rows_of(w0.vt, b0, (int64_t)a * w0.Nkp);
   const Planes ffh = rows_of(w0.ffh, r0, std::max(fp, fpc));
   // views of the same rows in another format: cross-attention queries [M, a] (M x a interleaved fits M x 2a dense 16-bit), the FF conv's
@@ -1071,16 +1113,18 @@ void describe_rows(const ns2_model* m, const Work& w0, const CondState* cs, cons
   // the pair as one launch where the GEMM's workgroups own whole rows (dim = 128: the 128 x 128 kernel, gemm.hip; gemm_fuses_norm says
   // so), else as the GEMM + rmsnorm_kernel.  cld == 0 with ncond != null: every utterance reads the same (gamma, beta) row (the time table).
   const float* cbase = call + (size_t)S * L * 2 * dim;
+  // conv3: the product is a causal conv of kernel 3 over the utterances (the folded feed-forward conv), timed as category `cat`
   auto update_then_norm = [&](const PackedW& pw, const Planes& ap, int lda, const float* bias, bool add_resid, int gprec, const float* gamma,
-                              const float* ncond, const Planes& nout, int mark = Launch::NONE) {
+                              const float* ncond, const Planes& nout, int mark = Launch::NONE, bool conv3 = false, int cat = PC_GEMM_F32) {
     GemmArgs g = product(pw, ap, lda, M);
+    if (conv3) set_conv(g, pw, 3, 1, N);
     g.bias = bias; g.resid = add_resid ? xres : nullptr; g.ldr = dim; g.out_f = xres; g.ldo_f = dim;
     const bool fused = gemm_fuses_norm(g, gprec);
     if (fused) {
       g.nrm_hi = nout.hi; g.nrm_lo = nout.lo; g.nrm_ld = dp; g.nrm_fmt = nout.fmt;
       g.nrm_gamma = gamma; g.nrm_cond = ncond; g.nrm_cond_ld = cld; g.nrm_seq_len = N;
     }
-    gemm(g, gprec, PC_GEMM_F32, mark);
+    gemm(g, gprec, cat, mark);
     if (!fused) {
       Launch l; l.kind = Launch::NORM; l.cat = PC_NORM;
       l.n = norm_args(xres, dim, M, dim, N, gamma, ncond, cld, nout, dp, nullptr, 0);
@@ -1118,14 +1162,23 @@ void describe_rows(const ns2_model* m, const Work& w0, const CondState* cs, cons
       update_then_norm(ly.cout, o, a, nullptr, true, prec, nullptr, layer_cond(l, m->nnorm - 1), xn_ff);
     }
     // feedforward: Linear -> GEGLU -> causal conv k3 -> Linear (NS2:1009-1025); precision 6: the whole branch on dense IEEE-half planes
-    GemmArgs ffin = product(ly.ffin, xn_ff, dp, M), conv = product(ly.conv, ffh_conv, fpc, M);
+    GemmArgs ffin = product(ly.ffin, xn_ff, dp, M);
     set_geglu(ffin, ffh_conv.hi, ffh_conv.lo, fpc, fp); ffin.bias = ly.b_ffin; ffin.out_fmt = ffh_conv.fmt;
     gemm(ffin, ff_prec, PC_GEMM_GEGLU);
-    set_conv(conv, ly.conv, 3, 1, N);
-    set_out_planes(conv, EPI_SPLIT, ffc_ff.hi, ffc_ff.lo, fp); conv.bias = ly.b_conv; conv.out_fmt = ffc_ff.fmt;
-    gemm(conv, conv_prec, PC_GEMM_FFCONV);
-    // FF-out + residual, then the next layer's self-attention norm -- or to_pred's RMSNorm (learned gamma, NS2:781-784) after the last
-    update_then_norm(ly.ffout, ffc_ff, fp, ly.b_ffout, true, ff_prec, last ? m->g_pred : nullptr, last ? nullptr : layer_cond(l + 1, 0), xn);
+    const float* next_gamma = last ? m->g_pred : nullptr;
+    const float* next_cond = last ? nullptr : layer_cond(l + 1, 0);
+    if (m->fold) {
+      // conv and FF-out as ONE causal conv f -> dim in the conv site's arithmetic (ns2_model::fold) + residual, then the next layer's
+      // self-attention norm -- or to_pred's RMSNorm (learned gamma, NS2:781-784) after the last
+      update_then_norm(ly.fffold, ffh_conv, fpc, ly.b_fold, true, conv_prec, next_gamma, next_cond, xn, Launch::NONE, true, PC_GEMM_FFCONV);
+    } else {
+      GemmArgs conv = product(ly.conv, ffh_conv, fpc, M);
+      set_conv(conv, ly.conv, 3, 1, N);
+      set_out_planes(conv, EPI_SPLIT, ffc_ff.hi, ffc_ff.lo, fp); conv.bias = ly.b_conv; conv.out_fmt = ffc_ff.fmt;
+      gemm(conv, conv_prec, PC_GEMM_FFCONV);
+      // FF-out + residual, then the norm of what follows (as above)
+      update_then_norm(ly.ffout, ffc_ff, fp, ly.b_ffout, true, ff_prec, next_gamma, next_cond, xn);
+    }
     snprintf(name, sizeof name, "layer%d", l);
     tap_f(name, xres);
   }
@@ -1330,6 +1383,7 @@ extern "C" int ns2_debug_chain_rule(const ns2_model_config* cfg, int B, int N, i
   ns2_model mm;
   ns2_model* m = &mm;
   NSCHK(derive_dims(m, cfg));
+  m->fold = fold_wanted();
   bf16_t* const fake = reinterpret_cast<bf16_t*>(uintptr_t(1) << 40);
   float* const fakef = reinterpret_cast<float*>(fake);
   const PackCtx pc = pack_ctx_for(nullptr, op_precision(cfg->precision));
@@ -1357,9 +1411,15 @@ extern "C" int ns2_debug_chain_rule(const ns2_model_config* cfg, int B, int N, i
     shape(&ly.qkv, pc, 3 * a, dim, 1); shape(&ly.out, pc, dim, a, 1);
     if (cond) { shape(&ly.cq, pc, a, dim, 1); shape(&ly.cout, pc, dim, a, 1); }
     shape(&ly.ffin, pc_ff, 2 * rup(f, 32), dim, 1); ly.b_ffin = fakef;
-    shape(&ly.conv, pc_conv, f, f, 3); ly.b_conv = fakef;
-    if (pc_conv.fmt == FMT_F16) ly.conv.t3 = fake;
-    shape(&ly.ffout, pc_ff, dim, f, 1); ly.b_ffout = fakef;
+    ly.b_conv = fakef; ly.b_ffout = fakef;
+    if (m->fold) {
+      shape(&ly.fffold, pc_conv, dim, f, 3); ly.b_fold = fakef;
+      if (pc_conv.fmt == FMT_F16) ly.fffold.t3 = fake;
+    } else {
+      shape(&ly.conv, pc_conv, f, f, 3);
+      if (pc_conv.fmt == FMT_F16) ly.conv.t3 = fake;
+      shape(&ly.ffout, pc_ff, dim, f, 1);
+    }
   }
   Work w;
   carve_work(m, &w, fake, 0, B, N, 0, 0);

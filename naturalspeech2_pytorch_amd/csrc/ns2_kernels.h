@@ -223,6 +223,10 @@ struct RepackDesc {
 hipError_t launch_repack(const RepackDesc* tab, int n, long total_blocks, hipStream_t s);
 hipError_t launch_pack_weight(const float* src, int C, int T, int Cp, const int* row_map, int rows_p, bf16_t* dst_hi,
                               bf16_t* dst_lo, int ldk, int k_off, hipStream_t s, int fmt = 0);
+// the feed-forward fold (elementwise.hip): w_fold [dim, f, 3] = w_out [dim, f] . w_conv [f, f, 3], b_fold [dim] = w_out . b_conv + b_out
+// (b_out may be null), fp32 FMAs in ascending order of the contracted index
+hipError_t launch_ff_fold(const float* w_out, const float* w_conv, const float* b_conv, const float* b_out, int dim, int f, float* w_fold,
+                          float* b_fold, hipStream_t s);
 
 // EnCodec residual VQ encode (HFENC:364-369, 424-447)
 struct RvqArgs {
