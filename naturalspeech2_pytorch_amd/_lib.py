@@ -1,8 +1,8 @@
 """ctypes binding of libns2hip.so, derived from its C ABI: include/ns2hip.h (and include/ns2hip_optim.h, the optimizer step, and
 include/ns2hip_pitch.h, the pitch extractor, include/ns2hip_ragged.h, ragged batches, include/ns2hip_ragged_front.h, ragged prompts
 and text, include/ns2hip_ragged_train.h, ragged training batches, include/ns2hip_head_dim_train.h, training at head dims 32 and 128, and
-include/ns2hip_ragged_audio.h, ragged raw audio, and include/ns2hip_fold.h, the feed-forward fold, each into tables of its own) is
-parsed once, at import.
+include/ns2hip_ragged_audio.h, ragged raw audio, include/ns2hip_fold.h, the feed-forward fold, and include/ns2hip_ragged_cond_train.h,
+ragged text and prompts in training, each into tables of its own) is parsed once, at import.
 
 The HIP library is the product: importing this module FAILS LOUDLY when the header or the shared object is missing or the
 library does not export the full ABI -- there is no CPU / PyTorch fallback for the hot path.
@@ -36,6 +36,7 @@ RAGGED_TRAIN_HEADER_PATH = os.path.join(_HERE, "..", "include", "ns2hip_ragged_t
 HEAD_DIM_TRAIN_HEADER_PATH = os.path.join(_HERE, "..", "include", "ns2hip_head_dim_train.h")   # training at head dims 32 / 128: likewise
 RAGGED_AUDIO_HEADER_PATH = os.path.join(_HERE, "..", "include", "ns2hip_ragged_audio.h")   # lengths in mel, pitch and the RVQ term: likewise
 FOLD_HEADER_PATH = os.path.join(_HERE, "..", "include", "ns2hip_fold.h")   # the feed-forward fold: likewise
+RAGGED_COND_TRAIN_HEADER_PATH = os.path.join(_HERE, "..", "include", "ns2hip_ragged_cond_train.h")   # lengths through the conditioning's training pass: likewise
 
 
 class Ns2Error(RuntimeError):
@@ -159,6 +160,11 @@ if not os.path.exists(FOLD_HEADER_PATH):
 with open(FOLD_HEADER_PATH) as _f:
     _, _, FOLD_SIGNATURES = parse_header(_f.read())
 
+if not os.path.exists(RAGGED_COND_TRAIN_HEADER_PATH):
+    raise Ns2Error(f"{RAGGED_COND_TRAIN_HEADER_PATH} not found: the binding is derived from the header, it ships with the package's source tree")
+with open(RAGGED_COND_TRAIN_HEADER_PATH) as _f:
+    _, _, RAGGED_COND_TRAIN_SIGNATURES = parse_header(_f.read())
+
 _lib = None
 
 
@@ -172,7 +178,8 @@ def load():
                        f"(or naturalspeech2_pytorch_amd/csrc/build.sh); there is no fallback path")
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in {**SIGNATURES, **OPTIM_SIGNATURES, **PITCH_SIGNATURES, **RAGGED_SIGNATURES, **FRONT_SIGNATURES,
-                              **RAGGED_TRAIN_SIGNATURES, **HEAD_DIM_TRAIN_SIGNATURES, **RAGGED_AUDIO_SIGNATURES, **FOLD_SIGNATURES}.items():
+                              **RAGGED_TRAIN_SIGNATURES, **HEAD_DIM_TRAIN_SIGNATURES, **RAGGED_AUDIO_SIGNATURES, **FOLD_SIGNATURES,
+                              **RAGGED_COND_TRAIN_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -232,3 +239,8 @@ def ragged_audio_header_symbols():
 def fold_header_symbols():
     """Symbols declared in include/ns2hip_fold.h"""
     return sorted(FOLD_SIGNATURES)
+
+
+def ragged_cond_train_header_symbols():
+    """Symbols declared in include/ns2hip_ragged_cond_train.h"""
+    return sorted(RAGGED_COND_TRAIN_SIGNATURES)

@@ -146,7 +146,7 @@ def model_forward_autograd(m, x, times, prompt=None, cond=None, cond_drop_prob=N
     return getattr(tp, "1")(_rmsnorm(h, getattr(tp, "0")))
 
 
-def model_forward_autograd_ragged(m, x, times, lens, prompt=None, cond=None, cond_drop_prob=None):
+def model_forward_autograd_ragged(m, x, times, lens, prompt=None, cond=None, cond_drop_prob=None, prompt_lens=None):
     """`model_forward_autograd` with `lens` as the TRAINING pass of a ragged batch runs it (Model.forward under autograd with
     `ragged_training`; the restatement of training/model_pass.py's rule, include/ns2hip_ragged_train.h): frames of x and cond from a
     length on are selected to 0 at the entry (NaN may lie there, and a masked key's 0 * NaN would reach the rows before it), and the
@@ -156,7 +156,8 @@ def model_forward_autograd_ragged(m, x, times, lens, prompt=None, cond=None, con
     mask = _prefix_mask(lens, b, n, x.device)
     if cond is not None:
         cond = _keep_rows(cond.transpose(1, 2), _prefix_mask(lens, b, cond.shape[-1], x.device)).transpose(1, 2)
-    return _keep_rows(model_forward_autograd(m, _keep_rows(x, mask), times, prompt=prompt, cond=cond, cond_drop_prob=cond_drop_prob, lens=lens), mask)
+    return _keep_rows(model_forward_autograd(m, _keep_rows(x, mask), times, prompt=prompt, cond=cond, cond_drop_prob=cond_drop_prob, lens=lens,
+                                             prompt_lens=prompt_lens), mask)
 
 
 # ---- the plain Transformer and the two conditioning encoders under autograd (NS2:1073-1115, 228-341): joint training of

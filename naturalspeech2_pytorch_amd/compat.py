@@ -36,7 +36,7 @@ def hip_backed_model_class(reference_model_cls):
 
     class HipBackedModel(HipDenoiserMixin, reference_model_cls):
         def __init__(self, dim, *args, precision="exact", train_backend="reference", train_precision="exact", ragged_training=False,
-                     head_dim_training=False, **kwargs):
+                     head_dim_training=False, ragged_conditioning=False, **kwargs):
             reference_model_cls.__init__(self, dim, *args, **kwargs)
             bound = sig.bind(self, dim, *args, **kwargs)
             cfg = dict(defaults)
@@ -47,8 +47,9 @@ def hip_backed_model_class(reference_model_cls):
             self.train_precision = train_precision            # arithmetic of train_backend="hip" (training/passes.py: TRAIN_PRECISIONS)
             self.ragged_training = ragged_training            # True: forward(lens=) under autograd (train_backend="hip"; model.py `Model`)
             self.head_dim_training = head_dim_training        # True: dim_head 32 / 128 on the HIP training kernels (model.py `Model`)
+            self.ragged_conditioning = ragged_conditioning    # True: forward(prompt_lens=) under autograd (train_backend="hip"; model.py `Model`)
 
-        def _forward_autograd(self, x, times, prompt=None, prompt_mask=None, cond=None, cond_drop_prob=None, lens=None):
+        def _forward_autograd(self, x, times, prompt=None, prompt_mask=None, cond=None, cond_drop_prob=None, lens=None, prompt_lens=None):
             """train_backend="reference" (default): the reference's own forward under torch autograd -- the loss is upstream's bit for
             bit.  "hip": forward AND backward in libns2hip (training/model_pass.py), through the reference's own parameters; the unmodified
             reference `Trainer` / `NaturalSpeech2.forward` (NS2:1635, 1886) then trains on the HIP kernels."""
@@ -58,11 +59,13 @@ def hip_backed_model_class(reference_model_cls):
                 why = training.unsupported_reason(self)
                 if why is None:
                     ragged = {} if lens is None else dict(lens=lens)
+                    if prompt_lens is not None:
+                        ragged["prompt_lens"] = prompt_lens
                     return training.model_forward_train(self, x, times, prompt=prompt, cond=cond, cond_drop_prob=cond_drop_prob, **ragged)
                 import warnings
                 warnings.warn(f"HIP training path not usable for this Model ({why}): running the reference's own forward")
-            if lens is not None:
-                raise NotImplementedError("lens: the reference's own forward has no per-utterance lengths (ragged training needs "
+            if lens is not None or prompt_lens is not None:
+                raise NotImplementedError("lens / prompt_lens: the reference's own forward has no per-utterance lengths (ragged training needs "
                                           "train_backend='hip' on an MI355X)")
             return reference_model_cls.forward(self, x, times, prompt=prompt, prompt_mask=prompt_mask, cond=cond,
                                                cond_drop_prob=cond_drop_prob)

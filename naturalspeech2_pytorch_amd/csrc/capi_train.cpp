@@ -6,6 +6,7 @@
 #include <cstring>
 
 #include "../../include/ns2hip_head_dim_train.h"
+#include "../../include/ns2hip_ragged_cond_train.h"
 #include "../../include/ns2hip_ragged_train.h"
 #include "ns2_host.h"
 
@@ -381,6 +382,29 @@ extern "C" int ns2_groupnorm_silu_bwd(const float* dy, int64_t lddy, const float
   float* slots = (float*)workspace;
   float* colsum = slots + (int64_t)B * gn_bwd_row_chunks(n) * 2 * C;
   HIPRET(launch_groupnorm_silu_bwd(dy, (long)lddy, x, B, n, C, groups, weight, bias, eps, stats, dx, dweight_dbias, slots, colsum, (hipStream_t)stream));
+  return NS2_OK;
+}
+// ... of a ragged batch (include/ns2hip_ragged_cond_train.h): the same launches on the <true> kernels
+extern "C" int ns2_groupnorm_silu_bwd_lens(const float* dy, int64_t lddy, const float* x, int B, int n, int C, int groups, const float* weight,
+                                           const float* bias, float eps, const void* stats, int64_t stats_bytes, const int* row_lens, float* dx,
+                                           float* dweight_dbias, void* workspace, int64_t workspace_bytes, void* stream) {
+  if (!row_lens)
+    return ns2_groupnorm_silu_bwd(dy, lddy, x, B, n, C, groups, weight, bias, eps, stats, stats_bytes, dx, dweight_dbias, workspace,
+                                  workspace_bytes, stream);
+  ARGCHK(dy && x && weight && bias && stats && dx && dweight_dbias && workspace, "ns2_groupnorm_silu_bwd_lens: null pointer");
+  ARGCHK(B > 0 && B <= 65535 && n > 0 && groups > 0 && groups <= 1024, "ns2_groupnorm_silu_bwd_lens: bad arguments (at most 65535 utterances, 1024 groups)");
+  ARGCHK(C > 0 && C % groups == 0 && (C / groups) % 4 == 0 && C / groups <= 4096,
+         "ns2_groupnorm_silu_bwd_lens: C / groups must be a multiple of 4, at most 4096");
+  ARGCHK(lddy >= C && lddy % 4 == 0, "ns2_groupnorm_silu_bwd_lens: lddy must be a multiple of 4, at least C");
+  ARGCHK(stats_bytes >= ns2_groupnorm_workspace_bytes(B, n, C, groups), "ns2_groupnorm_silu_bwd_lens: stats = the workspace ns2_groupnorm_silu_lens filled (too small)");
+  ARGCHK(workspace_bytes >= ns2_groupnorm_silu_bwd_workspace_bytes(B, n, C), "ns2_groupnorm_silu_bwd_lens: workspace too small");
+  ARGCHK(((uintptr_t)dy | (uintptr_t)x | (uintptr_t)weight | (uintptr_t)bias | (uintptr_t)stats | (uintptr_t)dx | (uintptr_t)workspace) % 16 == 0,
+         "ns2_groupnorm_silu_bwd_lens: buffers must be 16-byte aligned");
+  ARGCHK((uintptr_t)row_lens % 4 == 0, "ns2_groupnorm_silu_bwd_lens: row_lens must be 4-byte aligned");
+  float* slots = (float*)workspace;
+  float* colsum = slots + (int64_t)B * gn_bwd_row_chunks(n) * 2 * C;
+  HIPRET(launch_groupnorm_silu_bwd(dy, (long)lddy, x, B, n, C, groups, weight, bias, eps, stats, dx, dweight_dbias, slots, colsum, (hipStream_t)stream,
+                                   row_lens));
   return NS2_OK;
 }
 extern "C" int64_t ns2_row_dot_relu_bwd_workspace_bytes(int64_t M, int K) {

@@ -51,14 +51,25 @@ struct GnBwdArgs {
   const float* colsum;     // [B][2][C]: the slots of an utterance added up
   float* dx;
   int B, n, C, groups, cg, nchunks, rchunks; float eps;
+  const int* row_lens = nullptr;   // <true> kernels: rows per utterance, int32 [B] in device memory, clamped into [1, n]
 };
+
+// rows of utterance b that count: n, or its own length (gn_rows of the forward)
+template <bool LENS>
+NS2_DEVINL int gnb_rows(const GnBwdArgs& a, int b) {
+  if constexpr (LENS) return min(max(a.row_lens[b], 1), a.n);
+  return a.n;
+}
 
 NS2_DEVINL float silu_grad(float z) {
   const float sg = 1.0f / (1.0f + expf(-z));
   return sg * (1.0f + z * (1.0f - sg));
 }
 
-// grid (ceil(C / 1024), rchunks, B); dynamic LDS: 3 * groups floats
+// grid (ceil(C / 1024), rchunks, B); dynamic LDS: 3 * groups floats.  <true>: the chunk's rows stop at the utterance's length -- a chunk
+// wholly behind it reads nothing and writes a slot of zeros, the boundary chunk sums its rows before the length, so the slots that count
+// are those of the utterance alone at n = its length, bit for bit (the reducer adds the zero slots behind them: x + 0 = x).
+template <bool LENS>
 __global__ __launch_bounds__(COLS_THREADS) void gn_bwd_cols_kernel(const GnBwdArgs a) {
   const int tile = blockIdx.x, rc = blockIdx.y, b = blockIdx.z, t = threadIdx.x;
   extern __shared__ float gs[];
@@ -79,7 +90,7 @@ __global__ __launch_bounds__(COLS_THREADS) void gn_bwd_cols_kernel(const GnBwdAr
     const float4 wv = *reinterpret_cast<const float4*>(a.weight + c);
     const float4 bv = *reinterpret_cast<const float4*>(a.bias + c);
     const float w[4] = {wv.x, wv.y, wv.z, wv.w}, bi[4] = {bv.x, bv.y, bv.z, bv.w};
-    const int r1 = min(a.n, (rc + 1) * GNB_ROWS);
+    const int r1 = min(gnb_rows<LENS>(a, b), (rc + 1) * GNB_ROWS);
     for (int r = rc * GNB_ROWS + rsub; r < r1; r += rows_par) {
       const long row = (long)b * a.n + r;
       const float4 xv = *reinterpret_cast<const float4*>(a.x + row * a.C + c);
@@ -102,12 +113,15 @@ __global__ __launch_bounds__(COLS_THREADS) void gn_bwd_cols_kernel(const GnBwdAr
   }
 }
 
-// grid (ceil(n / GN_APPLY_ROWS), B); dynamic LDS: 5 * groups floats
+// grid (ceil(n / GN_APPLY_ROWS), B); dynamic LDS: 5 * groups floats.  <true>: N = len * cg; a row at or beyond the utterance's length is
+// not read (x and dy may hold NaN there) and its dx is written as zeros.
+template <bool LENS>
 __global__ __launch_bounds__(GN_THREADS) void gn_bwd_apply_kernel(const GnBwdArgs a) {
   const int b = blockIdx.y, t = threadIdx.x;
   extern __shared__ float gs[];
   float* sK = gs; float* sM = gs + a.groups; float* sR = gs + 2 * a.groups; float* s1 = gs + 3 * a.groups; float* s2 = gs + 4 * a.groups;
-  const float inv_n = 1.0f / ((float)a.n * (float)a.cg);
+  const int len = gnb_rows<LENS>(a, b);
+  const float inv_n = 1.0f / ((float)len * (float)a.cg);
   for (int g = t; g < a.groups; g += GN_THREADS) {
     gn_group_stats(a.part, a.x, b, g, a.groups, a.nchunks, a.n, a.C, a.cg, a.eps, sK[g], sM[g], sR[g]);
     const float* cs = a.colsum + (long)b * 2 * a.C;
@@ -124,7 +138,7 @@ __global__ __launch_bounds__(GN_THREADS) void gn_bwd_apply_kernel(const GnBwdArg
   const int q = a.C >> 2;
   for (int it = t; it < GN_APPLY_ROWS * q; it += GN_THREADS) {
     const int r = r0 + it / q, c = (it % q) * 4;
-    if (r >= a.n) break;
+    if (r >= len) break;                               // (rows ascend with `it`; <false>: len = n)
     const long row = (long)b * a.n + r;
     const int g = c / a.cg;
     const float4 xv = *reinterpret_cast<const float4*>(a.x + row * a.C + c);
@@ -142,6 +156,13 @@ __global__ __launch_bounds__(GN_THREADS) void gn_bwd_apply_kernel(const GnBwdArg
       o[e] = rs * (dxh - u - xh * v);
     }
     *reinterpret_cast<float4*>(a.dx + row * a.C + c) = make_float4(o[0], o[1], o[2], o[3]);
+  }
+  if constexpr (LENS) {                                // a loop of its own: the one above keeps the <false> kernel's body, hence its bits
+    for (int it = t; it < GN_APPLY_ROWS * q; it += GN_THREADS) {
+      const int r = r0 + it / q, c = (it % q) * 4;
+      if (r >= a.n) break;
+      if (r >= len) *reinterpret_cast<float4*>(a.dx + ((long)b * a.n + r) * a.C + c) = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
   }
 }
 
@@ -293,10 +314,12 @@ __global__ __launch_bounds__(256) void row_dot_kernel(const float* x, int ldx, i
 int gn_bwd_row_chunks(int n) { return (n + GNB_ROWS - 1) / GNB_ROWS; }
 int row_dot_bwd_chunks(long M) { return (int)((M + RDB_ROWS - 1) / RDB_ROWS); }
 
-// stats = the workspace the forward (ns2_groupnorm_silu) left; slots [B * gn_bwd_row_chunks(n)][2 C]; colsum [B][2 C]; dwb [2 C] = dweight | dbias
+// stats = the workspace the forward (ns2_groupnorm_silu) left; slots [B * gn_bwd_row_chunks(n)][2 C]; colsum [B][2 C]; dwb [2 C] = dweight | dbias.
+// row_lens (include/ns2hip_ragged_cond_train.h): int32 [B] on the device and stats = what ns2_groupnorm_silu_lens left, or nullptr: the
+// <true> kernels in the same grids, the same two reductions between them.
 hipError_t launch_groupnorm_silu_bwd(const float* dy, long lddy, const float* x, int B, int n, int C, int groups, const float* weight,
                                      const float* bias, float eps, const void* stats, float* dx, float* dwb, float* slots, float* colsum,
-                                     hipStream_t s) {
+                                     hipStream_t s, const int* row_lens) {
   if (B <= 0 || n <= 0 || groups <= 0 || groups > 1024 || C <= 0 || C % groups || (C / groups) % 4 || C / groups > GN_CHUNK || lddy < C ||
       (lddy & 3) || B > 65535)
     return hipErrorInvalidValue;
@@ -304,17 +327,24 @@ hipError_t launch_groupnorm_silu_bwd(const float* dy, long lddy, const float* x,
   a.x = x; a.dy = dy; a.lddy = lddy; a.weight = weight; a.bias = bias; a.part = reinterpret_cast<const float4*>(stats);
   a.slots = slots; a.colsum = colsum; a.dx = dx;
   a.B = B; a.n = n; a.C = C; a.groups = groups; a.cg = C / groups; a.nchunks = gn_chunks(n, a.cg); a.rchunks = gn_bwd_row_chunks(n);
-  a.eps = eps;
+  a.eps = eps; a.row_lens = row_lens;
   const int q = C >> 2;
-  hipLaunchKernelGGL(gn_bwd_cols_kernel, dim3((q + COLS_THREADS - 1) / COLS_THREADS, a.rchunks, B), dim3(COLS_THREADS),
-                     3 * groups * sizeof(float), s, a);
+  const dim3 cols_grid((q + COLS_THREADS - 1) / COLS_THREADS, a.rchunks, B);
+  if (row_lens)
+    hipLaunchKernelGGL(gn_bwd_cols_kernel<true>, cols_grid, dim3(COLS_THREADS), 3 * groups * sizeof(float), s, a);
+  else
+    hipLaunchKernelGGL(gn_bwd_cols_kernel<false>, cols_grid, dim3(COLS_THREADS), 3 * groups * sizeof(float), s, a);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   e = launch_reduce_slices(slots, B, a.rchunks, 2L * C, colsum, 0, s);          // per utterance: what the group sums need
   if (e != hipSuccess) return e;
   e = launch_reduce_slices(colsum, 1, B, 2L * C, dwb, 0, s);                    // over the utterances: dweight | dbias
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(gn_bwd_apply_kernel, dim3((n + GN_APPLY_ROWS - 1) / GN_APPLY_ROWS, B), dim3(GN_THREADS), 5 * groups * sizeof(float), s, a);
+  const dim3 apply_grid((n + GN_APPLY_ROWS - 1) / GN_APPLY_ROWS, B);
+  if (row_lens)
+    hipLaunchKernelGGL(gn_bwd_apply_kernel<true>, apply_grid, dim3(GN_THREADS), 5 * groups * sizeof(float), s, a);
+  else
+    hipLaunchKernelGGL(gn_bwd_apply_kernel<false>, apply_grid, dim3(GN_THREADS), 5 * groups * sizeof(float), s, a);
   return hipGetLastError();
 }
 

@@ -321,7 +321,7 @@ int gn_bwd_row_chunks(int n);
 int row_dot_bwd_chunks(long M);
 hipError_t launch_groupnorm_silu_bwd(const float* dy, long lddy, const float* x, int B, int n, int C, int groups, const float* weight,
                                      const float* bias, float eps, const void* stats, float* dx, float* dwb, float* slots, float* colsum,
-                                     hipStream_t s);
+                                     hipStream_t s, const int* row_lens = nullptr);   // row_lens: ns2_groupnorm_silu_bwd_lens
 hipError_t launch_row_dot_relu_bwd(const float* dout, const float* out, const float* h, long ldh, const float* w, long M, int K, float* dh,
                                    long lddh, float* dwb, float* slots, hipStream_t s);
 hipError_t launch_wgrad_reduce(const float* partial, int S, int R, long ldp, int T, int Kp, int K, float* out, hipStream_t s);

@@ -108,7 +108,8 @@ class NaturalSpeech2(nn.Module):
                  duration_pitch_train_backend="composite",    # not in the reference: "hip" trains the DurationPitchPredictor on them (training/duration_pitch_pass.py)
                  aligner_train_backend="composite",    # not in the reference: "hip" trains the Aligner and runs its two losses on them (training/aligner_pass.py)
                  rvq_ce_backend=None,                  # not in the reference: "composite" / "hip" sets codec.rq.backend, the RVQ cross-entropy term (csrc/rvq_ce.hip); None leaves the codec's own
-                 ragged_audio: bool = False):          # not in the reference: forward(raw audio, audio_lens=samples) and audio_lens with the RVQ term (include/ns2hip_ragged_audio.h)
+                 ragged_audio: bool = False,           # not in the reference: forward(raw audio, audio_lens=samples) and audio_lens with the RVQ term (include/ns2hip_ragged_audio.h)
+                 ragged_conditioning: bool = False):   # not in the reference: forward(text_lens=, prompt_lens=) trains on ragged text and prompts (include/ns2hip_ragged_cond_train.h)
         super().__init__()
         assert _is_denoiser(model), "model must be a Model (this package's, or compat.HipBackedModel over the reference's class)"
         self.conditional = model.condition_on_prompt
@@ -165,6 +166,11 @@ class NaturalSpeech2(nn.Module):
         self.min_snr_loss_weight, self.min_snr_gamma = min_snr_loss_weight, min_snr_gamma
         self.rvq_cross_entropy_loss_weight = rvq_cross_entropy_loss_weight
         self.ragged_audio = ragged_audio
+        self.ragged_conditioning = ragged_conditioning
+        if ragged_conditioning:                                                       # the switch goes on the members that take lengths under autograd
+            for mod in (self.model, getattr(self, "prompt_enc", None), getattr(self, "phoneme_enc", None), getattr(self, "duration_pitch", None)):
+                if mod is not None:
+                    mod.ragged_conditioning = True
         if rvq_ce_backend is not None:
             assert codec is not None and hasattr(codec, "rq") and hasattr(codec.rq, "backend"), "rvq_ce_backend needs a codec whose rq has a backend (codec.py)"
             assert rvq_ce_backend in ("composite", "hip"), "rvq_ce_backend must be 'composite' or 'hip'"
@@ -322,11 +328,12 @@ class NaturalSpeech2(nn.Module):
                 prompt, _, _ = self.codec(prompt, curtail_from_left=True, return_encoded=True)
         return prompt
 
-    def _prompt_frame_lens(self, prompt_lens, prompt, prompt_enc):
+    def _prompt_frame_lens(self, prompt_lens, prompt, prompt_enc, trust_device=False):
         """sample(prompt_lens=) -> the lengths in rows of the encoded prompt, an integer tensor [b] on the model's device.  They count
         rows of `prompt_enc=`, frames of prompt latents [b, n_p, dim_codebook], samples of a raw-audio prompt [b, samples]: there the
         codec makes one frame of every `seq_len_multiple_of` samples, so each length and the padded length must be a positive multiple
-        of it (one host read, before the loop)."""
+        of it (one host read, before the loop).  trust_device (the training pass): lengths that arrive as a CUDA tensor are not read on
+        the host, as `forward(audio_lens=)` trusts them."""
         lens = torch.as_tensor(prompt_lens)
         given = prompt_enc if prompt_enc is not None else prompt
         if lens.ndim != 1 or lens.dtype.is_floating_point or lens.shape[0] != given.shape[0]:
@@ -335,7 +342,8 @@ class NaturalSpeech2(nn.Module):
         if prompt_enc is None and prompt.ndim == 2:
             assert self.codec is not None, "codec must be passed in if one were to sample from a raw prompt"
             hop = int(self.seq_len_multiple_of)
-            _check_raw_sample_lens(self.codec, hop, lens, prompt.shape[-1], "a raw-audio prompt with prompt_lens", "prompt")
+            if not (trust_device and torch.as_tensor(prompt_lens).is_cuda):
+                _check_raw_sample_lens(self.codec, hop, lens, prompt.shape[-1], "a raw-audio prompt with prompt_lens", "prompt")
             lens = lens // hop
         return lens
 
@@ -472,21 +480,40 @@ class NaturalSpeech2(nn.Module):
         return (audio, lens) if return_lens else audio
 
     # ------------------------------------------------------------------ training loss (NS2:1503-1684)
-    def text_forward_cond(self, text, text_lens, mel, mel_lens, pitch, prompt_enc, return_aux_losses=False):
+    def text_forward_cond(self, text, text_lens, mel, mel_lens, pitch, prompt_enc, return_aux_losses=False, prompt_lens=None, ragged=False):
         """NS2:1524-1602 up to the conditioning: masks from the lengths, the Aligner, average_over_durations and the expansion
         of the phoneme encodings + pitch embeddings into exactly T_mel = mel.shape[-1] frames.  Unlike the reference, the
         caller's `text_lens` / `mel_lens` are not clamped in place: clamped copies are used.  On CUDA the Aligner runs its HIP
         path under no_grad (the returned loss depends on it only through the hard path) and the lengths go straight to the
         kernels: no host read.  With return_aux_losses the Aligner runs its differentiable composite (or, built with
         `aligner_train_backend="hip"`, its HIP training pass on the lengths: still no host read) and the auxiliary terms
-        of NS2:1587-1602 are returned as a dict.  -> (cond, aux or None)"""
+        of NS2:1587-1602 are returned as a dict.  -> (cond, aux or None)
+        ragged (`ragged_conditioning`, with `text_lens` and / or `prompt_lens`): the phoneme encoder runs under the key mask of text_lens
+        and its rows from text_lens[i] on are selected to 0, the predictor gets both length vectors, and the duration / pitch terms are the
+        mean over the utterances of each one's own mean absolute error over its phonemes [0, text_lens[i]) -- mask and divisor formed on the
+        device with a select, the convention of `codec.rq(..., lens=)`."""
         from .aligner import average_over_durations, create_mask, expand_encodings
         b, n = text.shape[0], text.shape[-1]
         dev = text.device
-        text_lens = torch.full((b,), n, device=dev, dtype=torch.long) if text_lens is None else text_lens.clamp(max=n)
+        text_lens_given = text_lens is not None
+        text_lens = torch.full((b,), n, device=dev, dtype=torch.long) if text_lens is None else (text_lens if torch.is_tensor(text_lens) else torch.as_tensor(text_lens, device=dev)).clamp(max=n)
         T = mel.shape[-1]
+        mel_lens_given = mel_lens is not None
         mel_lens = torch.full((b,), T, device=dev, dtype=torch.long) if mel_lens is None else mel_lens.clamp(max=T)
-        phoneme_enc = self.phoneme_enc(text)                                           # [b, n, dim_hidden]
+        ragged = ragged and (text_lens_given or prompt_lens is not None)
+        if ragged and mel_lens_given:
+            # mel and pitch frames behind mel_lens are selected to 0, what AudioToMel / PitchExtractor leave there with lens=: the Aligner's
+            # k = 3 convolutions then read behind an utterance's last frame what they read behind the end of the utterance alone
+            frame_keep = (torch.arange(T, device=dev)[None] < mel_lens.clamp(min=1)[:, None])[:, None]
+            mel = torch.where(frame_keep, mel, torch.zeros((), dtype=mel.dtype, device=dev))
+            pitch = torch.where(frame_keep, pitch, torch.zeros((), dtype=pitch.dtype, device=dev))
+        if ragged:
+            tl = text_lens.clamp(1, n)
+            text_keep = torch.arange(n, device=dev)[None] < tl[:, None]                  # [b, n]
+            phoneme_enc = self.phoneme_enc(text, lens=tl)
+            phoneme_enc = torch.where(text_keep[..., None], phoneme_enc, torch.zeros((), dtype=phoneme_enc.dtype, device=dev))
+        else:
+            phoneme_enc = self.phoneme_enc(text)                                       # [b, n, dim_hidden]
         if return_aux_losses and torch.is_grad_enabled() and self.aligner.train_ready(phoneme_enc, mel):
             # aligner_train_backend="hip": the clamped lengths go straight to the kernels -- no masks, no host read
             aln_hard, aln_soft, aln_log, aln_mask = self.aligner.forward_lengths_train(phoneme_enc, text_lens, mel, mel_lens)
@@ -502,9 +529,18 @@ class NaturalSpeech2(nn.Module):
         if not return_aux_losses:
             return cond, None
         assert hasattr(self, "duration_pitch"), "return_aux_losses needs the predictor: construct with build_duration_pitch=True"
-        duration_pred, pitch_pred = self.duration_pitch(phoneme_enc, prompt_enc)
-        duration_loss = F.l1_loss(aln_hard, duration_pred)
-        pitch_loss = F.l1_loss(pitch[:, 0], pitch_pred)
+        if ragged:
+            duration_pred, pitch_pred = self.duration_pitch(phoneme_enc, prompt_enc, text_lens=tl if text_lens_given else None,
+                                                            prompt_lens=prompt_lens)
+
+            def own_l1(target, pred):                                                  # the mean over utterances of each one's own mean
+                err = torch.where(text_keep, (target - pred).abs(), torch.zeros((), dtype=pred.dtype, device=dev))
+                return (err.sum(dim=1) / tl.to(err.dtype)).mean()
+            duration_loss, pitch_loss = own_l1(aln_hard, duration_pred), own_l1(pitch[:, 0], pitch_pred)
+        else:
+            duration_pred, pitch_pred = self.duration_pitch(phoneme_enc, prompt_enc)
+            duration_loss = F.l1_loss(aln_hard, duration_pred)
+            pitch_loss = F.l1_loss(pitch[:, 0], pitch_pred)
         align_loss = self.aligner_loss(aln_log, text_lens, mel_lens)
         bin_loss = None
         if self.aligner_bin_loss_weight > 0.:
@@ -531,7 +567,7 @@ class NaturalSpeech2(nn.Module):
         its own frames [0, audio_lens[i]) x dim -- what it is for the utterance alone -- before the reference's (loss * weight).mean().
         Mask and divisor are formed on the device from the lengths (no host read: a captured step follows rewritten lengths); what
         audio, noise and cond hold from a length on never reaches the loss or a gradient.  Latents only: raw audio, the RVQ
-        cross-entropy term and `prompt_lens` are not taken together with it (NotImplementedError).
+        cross-entropy term and `prompt_lens` are not taken together with it (NotImplementedError; `ragged_audio` / `ragged_conditioning` below).
 
         Built with `ragged_audio=True` (not in the reference; also a plain attribute), the first two are taken:
           * raw audio [b, S] with `audio_lens` counting SAMPLES.  Each length and S must be a positive multiple of the codec's
@@ -544,12 +580,20 @@ class NaturalSpeech2(nn.Module):
             one's own term (codec.py);
           * with `text=` and the Aligner: `mel` (when not given) is `audio_to_mel(audio, lens=audio_lens)`, `pitch` (when not given)
             `pitch_extractor(audio, lens=audio_lens)`, and `mel_lens` defaults to 1 + audio_lens // mel_hop_length, formed on the device;
-            the Aligner and its losses run on lengths already.  NOT claimed: the phoneme encoder, the prompt encoder and the predictor
-            still see no lengths in training, so "equals the utterance alone" holds there for mel, pitch and mel_lens, and for the
-            diffusion and RVQ terms GIVEN the conditioning, not for the whole text-conditioned loss.
-        `prompt_lens` with `audio_lens` keeps raising, and the model still needs `ragged_training=True`."""
+            the Aligner and its losses run on lengths already.  The phoneme encoder, the prompt encoder and the predictor see lengths
+            under `ragged_conditioning=True` (below); without it they see none, and `prompt_lens` with `audio_lens` keeps raising.
+        The model still needs `ragged_training=True` for `audio_lens`.
+
+        Built with `ragged_conditioning=True` (not in the reference; also a plain attribute; include/ns2hip_ragged_cond_train.h), `text_lens` and
+        `prompt_lens` (a keyword the reference signature tolerates) reach the conditioning under autograd: `prompt_lens` -- rows of
+        `prompt_enc=`, frames of prompt latents or samples of a raw-audio prompt (`_prompt_frame_lens`; a CUDA tensor is trusted) -- goes to
+        `prompt_enc`, the predictor and the model, together with `audio_lens` or without it; `text_lens` goes to the phoneme encoder's key
+        mask and the predictor; and with `return_aux_losses=True` the duration and pitch terms are the mean over the utterances of each one's
+        own mean absolute error over its phonemes [0, text_lens[i]) (text_forward_cond).  What ids, prompt rows, mel and pitch frames hold
+        behind their lengths reaches no term of the loss and no gradient."""
         is_raw = audio.ndim == 2
         ragged_audio = bool(getattr(self, "ragged_audio", False))
+        ragged_cond = bool(getattr(self, "ragged_conditioning", False))
         sample_lens = None                                                            # ragged raw audio: the sample counts, on the device
         if audio_lens is not None:
             if is_raw and not ragged_audio:
@@ -558,9 +602,9 @@ class NaturalSpeech2(nn.Module):
             if self.rvq_cross_entropy_loss_weight > 0 and codes is not None and not ragged_audio:
                 raise NotImplementedError("audio_lens with the RVQ cross-entropy term (rvq_cross_entropy_loss_weight > 0 and codes=): "
                                           "ns2_rvq_ce averages over all frames, it takes no per-utterance lengths")
-            if kwargs.get("prompt_lens") is not None:
+            if kwargs.get("prompt_lens") is not None and not ragged_cond:
                 raise NotImplementedError("prompt_lens in training: per-utterance prompt lengths are a sampling feature; audio_lens "
-                                          "shortens the utterances, not their prompts")
+                                          "shortens the utterances, not their prompts (a wrapper built with ragged_conditioning=True takes both)")
             audio_lens = torch.as_tensor(audio_lens)
             if audio_lens.dtype.is_floating_point or audio_lens.dtype == torch.bool:
                 raise ValueError(f"audio_lens must be integers (frame counts), got {audio_lens.dtype}")
@@ -577,8 +621,15 @@ class NaturalSpeech2(nn.Module):
         aux = None
         if return_aux_losses and (not self.conditional or cond is not None):
             raise ValueError("return_aux_losses needs the text-conditioned path: text=, mel=, pitch= and no cond=")
+        prompt_lens = None                                                            # ragged_conditioning: rows of the encoded prompt, on the device
         if self.conditional:
-            p_enc = self._encode_prompt(prompt, prompt_enc)
+            if ragged_cond and kwargs.get("prompt_lens") is not None:
+                if prompt is None and prompt_enc is None:
+                    raise ValueError("prompt_lens needs a prompt: a conditional model called with prompt= or prompt_enc=")
+                prompt_lens = self._prompt_frame_lens(kwargs["prompt_lens"], prompt, prompt_enc, trust_device=True)
+                p_enc = prompt_enc if prompt_enc is not None else self.prompt_enc(self.process_prompt(prompt), lens=prompt_lens)
+            else:
+                p_enc = self._encode_prompt(prompt, prompt_enc)
             if cond is None and hasattr(self, "aligner"):
                 assert text is not None, "forward(text=...) needs the phoneme ids"
                 if mel is None and not is_raw:
@@ -599,7 +650,8 @@ class NaturalSpeech2(nn.Module):
                         mel = self.audio_to_mel(audio, **({} if sample_lens is None else dict(lens=sample_lens)))[..., :pitch.shape[-1]]
                 if mel_lens is None and sample_lens is not None:                      # the utterances' own frames (no host read)
                     mel_lens = 1 + sample_lens.long() // self.mel_hop_length
-                cond, aux = self.text_forward_cond(text, text_lens, mel, mel_lens, pitch, p_enc, return_aux_losses)
+                front = dict(prompt_lens=prompt_lens, ragged=True) if ragged_cond else {}
+                cond, aux = self.text_forward_cond(text, text_lens, mel, mel_lens, pitch, p_enc, return_aux_losses, **front)
             if cond is None:
                 raise NotImplementedError(
                     "forward(text=..., mel=..., pitch=...) derives the aligned conditioning with the Aligner, the "
@@ -619,12 +671,13 @@ class NaturalSpeech2(nn.Module):
         alpha, sigma = torch.sqrt(gamma) * self.scale, torch.sqrt(1 - gamma)         # NS2:1152-1153
         noised = alpha * audio + sigma * noise
         target = {"eps": noise, "x0": audio, "v": alpha * noise - sigma * audio}[self.objective]
+        pl_kw = {} if prompt_lens is None else dict(prompt_lens=prompt_lens)
         if audio_lens is None:
-            pred = self.model(noised, times, prompt=p_enc, cond=cond)                 # NS2:1635
+            pred = self.model(noised, times, prompt=p_enc, cond=cond, **pl_kw)        # NS2:1635
             loss = F.mse_loss(pred, target, reduction="none").flatten(1).mean(dim=1)  # [b]
         else:
             lens = audio_lens.to(device=device, dtype=torch.int32)                    # (an int32 device tensor stays the caller's buffer)
-            pred = self.model(noised, times, prompt=p_enc, cond=cond, lens=lens)
+            pred = self.model(noised, times, prompt=p_enc, cond=cond, lens=lens, **pl_kw)
             ln = lens.clamp(1, n)                                                     # as the kernels clamp
             keep = (torch.arange(n, device=device)[None] < ln[:, None])[..., None]
             # a select, not a product (NaN may lie beyond a length), on the difference: the padding's cotangent is an exact 0

@@ -16,7 +16,7 @@ from torch import nn
 from . import ops
 from ._cache import PackedCache
 from .model import _Attention, _NoParams, _RMSNorm, _PRECISIONS
-from .transformer import TRAIN_BACKENDS, needs_autograd
+from .transformer import TRAIN_BACKENDS, host_full_lens, needs_autograd
 
 
 class _Block(nn.Module):                        # Block (NS2:346-369): Conv1d -> GroupNorm -> SiLU -> Dropout
@@ -55,10 +55,12 @@ class DurationPitchPredictorTrunk(nn.Module):   # NS2:411-481
 class DurationPitchPredictor(nn.Module):
     def __init__(self, *, dim, num_phoneme_tokens=None, tokenizer=None, dim_encoded_prompts=None, num_convolutions_per_block=3,
                  use_resnet_block=True, num_convs_per_resnet_block=2, depth=10, kernel_size=3, heads=8, dim_head=64,
-                 dim_hidden=512, dropout=0.2, use_flash_attn=False, precision="exact", train_backend="composite", head_dim_training=False):
+                 dim_hidden=512, dropout=0.2, use_flash_attn=False, precision="exact", train_backend="composite", head_dim_training=False,
+                 ragged_conditioning=False):
         super().__init__()
         assert train_backend in TRAIN_BACKENDS, f"train_backend must be one of {TRAIN_BACKENDS}"
         self.train_backend = train_backend
+        self.ragged_conditioning = ragged_conditioning      # True: forward(text_lens=, prompt_lens=) runs under autograd too (else it raises, as before)
         self.head_dim_training = head_dim_training      # True: train_backend="hip" takes dim_head 32 / 128 too (else: the composite, as before)
         self.dropout_seed = None                # train_backend="hip": an int64 tensor [1] replaces the per-pass draw of the attention dropout seed
         if kernel_size % 2 == 0:
@@ -86,10 +88,12 @@ class DurationPitchPredictor(nn.Module):
         """x: token ids [b, n] (with num_phoneme_tokens) or phoneme encodings [b, n, dim_hidden]; encoded_prompts [b, n_p,
         dim_hidden].  Returns (duration, pitch), each [b, n].
 
-        text_lens / prompt_lens (not in the reference; sampling only): phonemes / prompt rows per utterance of a padded batch, integer
+        text_lens / prompt_lens (not in the reference): phonemes / prompt rows per utterance of a padded batch, integer
         [b], read on the device and clamped into [1, n] / [1, n_p]; either alone is allowed, the other side then counts as full.  The
         durations and pitches [0, text_lens[i]) are what utterance i gives alone with its text and prompt cut to its lengths, whatever
-        lies behind them (NaN included); from text_lens[i] on they are exactly 0."""
+        lies behind them (NaN included); from text_lens[i] on they are exactly 0.  Under autograd they need `ragged_conditioning=True`
+        (training/duration_pitch_pass.py with lengths, or the composite with the same lengths: the gradients are those of the utterances
+        alone too); without the switch they raise, as before."""
         if not torch.is_tensor(x):
             raise NotImplementedError("List[str] input needs the tokenizer / espeak front-end (out of scope); pass token ids or "
                                       "phoneme encodings")
@@ -97,6 +101,18 @@ class DurationPitchPredictor(nn.Module):
             raise NotImplementedError("prompt_mask is not supported: the reference's Attend applies it to keys = cat(queries, "
                                       "prompts), which a [b, n_p] mask does not cover (NS2:1060-1066)")
         if text_lens is not None or prompt_lens is not None:
+            if needs_autograd(self, x if x.is_floating_point() else None) and getattr(self, "ragged_conditioning", False):
+                b = x.shape[0]                                         # full on the host: that side takes the call without its lengths, same bits
+                text_lens = None if host_full_lens(text_lens, x.shape[1], b) else text_lens
+                prompt_lens = None if host_full_lens(prompt_lens, encoded_prompts.shape[1], b) else prompt_lens
+                if text_lens is None and prompt_lens is None:
+                    return self.forward(x, encoded_prompts)
+                if self.train_backend == "hip" and x.is_cuda:
+                    from . import training
+                    if training.available(x.device) and training.duration_pitch_unsupported_reason(self) is None:
+                        return training.duration_pitch_forward_train(self, x, encoded_prompts, text_lens=text_lens, prompt_lens=prompt_lens)
+                from .autograd_path import duration_pitch_autograd
+                return duration_pitch_autograd(self, x, encoded_prompts, text_lens=text_lens, prompt_lens=prompt_lens)
             if needs_autograd(self, x if x.is_floating_point() else None):
                 raise NotImplementedError(f"{'text_lens' if text_lens is not None else 'prompt_lens'}: per-utterance lengths are a sampling "
                                           f"feature (torch.no_grad()); the training passes take equal-length batches")

@@ -17,7 +17,7 @@ from torch import nn
 from . import ops
 from ._cache import PackedCache
 from .model import _NoParams, _PRECISIONS
-from .transformer import TRAIN_BACKENDS, Transformer, needs_autograd, use_hip_training
+from .transformer import TRAIN_BACKENDS, Transformer, host_full_lens, needs_autograd, use_hip_training
 
 
 class _ConvStack(PackedCache):
@@ -35,10 +35,12 @@ class _ConvStack(PackedCache):
 
 class SpeechPromptEncoder(nn.Module):
     def __init__(self, dim_codebook, dims: Tuple[int, ...] = (256, 2048, 2048, 2048, 2048, 512, 512, 512), *, depth=6, heads=8,
-                 dim_head=64, dropout=0.2, kernel_size=9, padding=4, use_flash_attn=True, precision="exact", train_backend="composite", head_dim_training=False):
+                 dim_head=64, dropout=0.2, kernel_size=9, padding=4, use_flash_attn=True, precision="exact", train_backend="composite", head_dim_training=False,
+                 ragged_conditioning=False):
         super().__init__()
         assert train_backend in TRAIN_BACKENDS, f"train_backend must be one of {TRAIN_BACKENDS}"
         self.train_backend = train_backend
+        self.ragged_conditioning = ragged_conditioning      # True: forward(x, lens=) runs under autograd too (else it raises, as before)
         dims = [dim_codebook, *dims]
         self.dim, self.dim_out = dims[0], dims[-1]
         assert precision in _PRECISIONS, f"precision must be one of {sorted(_PRECISIONS)}"
@@ -56,11 +58,21 @@ class SpeechPromptEncoder(nn.Module):
         """Under autograd (the reference trains prompt_enc jointly, NS2:1542-1543) the HIP training path (`train_backend="hip"`) or the
         differentiable composite runs; inference runs in the forward-only HIP kernels.
 
-        lens (not in the reference; sampling only): prompt rows per utterance of a padded batch, integer [b], read on the device and
+        lens (not in the reference): prompt rows per utterance of a padded batch, integer [b], read on the device and
         clamped into [1, n].  Output rows [0, lens[i]) are what utterance i gives alone with its prompt cut to lens[i] rows, whatever
-        x holds from lens[i] on (NaN included); output rows from lens[i] on are exactly 0."""
+        x holds from lens[i] on (NaN included); output rows from lens[i] on are exactly 0.  Under autograd it needs
+        `ragged_conditioning=True` (the training pass with lengths of training/encoder_pass.py, or the composite with the same lengths:
+        the gradients are those of the utterances alone too); without the switch it raises, as before."""
         assert x.shape[-1] == self.dim
         if lens is not None:
+            if needs_autograd(self, x) and getattr(self, "ragged_conditioning", False):
+                if host_full_lens(lens, x.shape[1], x.shape[0]):             # full on the host: the call without lengths, same bits
+                    return self.forward(x)
+                if use_hip_training(self, x):
+                    from .training import speech_prompt_encoder_forward_train
+                    return speech_prompt_encoder_forward_train(self, x, lens=lens)
+                from .autograd_path import speech_prompt_encoder_autograd
+                return speech_prompt_encoder_autograd(self, x, lens=lens)
             if needs_autograd(self, x):
                 raise NotImplementedError("lens: per-utterance prompt lengths are a sampling feature (torch.no_grad()); the training "
                                           "passes take equal-length batches")
@@ -128,9 +140,23 @@ class PhonemeEncoder(nn.Module):
                                        use_flash=use_flash, precision=precision, train_backend=train_backend, head_dim_training=head_dim_training)
         self._stack = _ConvStack()
 
-    def forward(self, x, mask=None):
+    def forward(self, x, mask=None, *, lens=None):
+        """lens (not in the reference; instead of `mask`): phonemes per utterance, integer [b] -- the key mask arange(n) < lens[:, None],
+        formed on the device without a host read (a clamped length always leaves one key).  The conv is causal, so the rows before a
+        length are those of the utterance alone; the rows from it on are finite and meaningless (the caller selects them to 0)."""
         if not torch.is_tensor(x):
             raise NotImplementedError("List[str] input needs the tokenizer / espeak front-end (out of scope); pass token ids")
+        if lens is not None:
+            assert mask is None, "pass the key-padding mask or the lengths it is made from, not both"
+            ln = torch.as_tensor(lens).to(x.device)
+            if needs_autograd(self) and use_hip_training(self, x):
+                from .training import phoneme_encoder_forward_train
+                return phoneme_encoder_forward_train(self, x, lens=ln)
+            mask = torch.arange(x.shape[1], device=x.device)[None] < ln.clamp(1, x.shape[1])[:, None]
+            if needs_autograd(self):
+                from .autograd_path import phoneme_encoder_autograd
+                return phoneme_encoder_autograd(self, x, mask)
+            return self._forward_hip(x, mask)
         if needs_autograd(self):
             if use_hip_training(self, x, mask):
                 from .training import phoneme_encoder_forward_train

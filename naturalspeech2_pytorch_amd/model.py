@@ -457,7 +457,9 @@ class HipDenoiserMixin:
         training pass raises on `lens`.
         `prompt_lens` (not in the reference): prompt rows per utterance of a padded prompt batch, integer [b], each in [1, n_p] -- the
         output of utterance i is what it gives with its prompt cut to prompt_lens[i] rows, whatever the prompt holds from there on
-        (NaN included): the mean of to_prompt_cond and the perceiver resampler's keys stop at the length, on the device (sampling only)."""
+        (NaN included): the mean of to_prompt_cond and the perceiver resampler's keys stop at the length, on the device.  Under autograd a
+        model with `ragged_conditioning = True` takes them too, with and without `lens` (include/ns2hip_ragged_cond_train.h): the prompt rows
+        behind a length then reach no gradient either; without the switch the training pass raises on `prompt_lens`."""
         if prompt_lens is not None and (not self._hip_cfg["condition_on_prompt"] or prompt is None):
             raise ValueError("prompt_lens needs a prompt: a conditional model (condition_on_prompt=True) called with prompt=")
         p = self.cond_drop_prob if cond_drop_prob is None else cond_drop_prob
@@ -470,11 +472,16 @@ class HipDenoiserMixin:
             if lens is not None and not getattr(self, "ragged_training", False):
                 raise NotImplementedError("lens: per-utterance lengths are a sampling feature (torch.no_grad()); the training pass and the "
                                           "backward kernels take equal-length batches (a model with ragged_training=True trains on them)")
-            if prompt_lens is not None:
+            if prompt_lens is not None and not getattr(self, "ragged_conditioning", False):
                 raise NotImplementedError("prompt_lens: per-utterance prompt lengths are a sampling feature (torch.no_grad()); the training "
-                                          "pass and the backward kernels take equal-length batches")
+                                          "pass and the backward kernels take equal-length batches (a model with ragged_conditioning=True "
+                                          "trains on them)")
             self._native.autograd_seen = True
             ragged = {} if lens is None else dict(lens=lens)                # (ragged_training: the host class's _forward_autograd takes lens=)
+            if prompt_lens is not None:                                     # (ragged_conditioning: ... and prompt_lens=)
+                from .transformer import host_full_lens
+                if not host_full_lens(prompt_lens, prompt.shape[1], x.shape[0]):     # (full on the host: the call without them, same bits)
+                    ragged["prompt_lens"] = prompt_lens
             return self._forward_autograd(x, times, prompt=prompt, prompt_mask=prompt_mask, cond=cond, cond_drop_prob=cond_drop_prob, **ragged)
         ragged = {} if lens is None else dict(lens=lens)
         if prompt_lens is not None:
@@ -604,8 +611,9 @@ _PROMPT_MASK_MSG = ("prompt_mask: the reference itself raises on it (the Perceiv
                     "32 + n_p keys, NS2:962-968 / 1060-1061 / ATT:92-94) and no reference caller passes one")
 
 
-def _train_forward(m, x, times, prompt, cond, cond_drop_prob, prompt_mask=None, lens=None):
-    """lens: frames per utterance of a ragged batch (Model.forward's, `ragged_training`), or None"""
+def _train_forward(m, x, times, prompt, cond, cond_drop_prob, prompt_mask=None, lens=None, prompt_lens=None):
+    """lens: frames per utterance of a ragged batch (Model.forward's, `ragged_training`), or None; prompt_lens: prompt rows per utterance
+    (`ragged_conditioning`), or None"""
     import os
     from . import training
     if prompt_mask is not None:
@@ -615,13 +623,16 @@ def _train_forward(m, x, times, prompt, cond, cond_drop_prob, prompt_mask=None, 
         why = training.unsupported_reason(m)
         if why is None:
             ragged = {} if lens is None else dict(lens=lens)
+            if prompt_lens is not None:
+                ragged["prompt_lens"] = prompt_lens
             return training.model_forward_train(m, x, times, prompt=prompt, cond=cond, cond_drop_prob=cond_drop_prob, **ragged)
         import warnings
         warnings.warn(f"HIP training path not usable for this Model ({why}): running the PyTorch composite")
     from .autograd_path import model_forward_autograd, model_forward_autograd_ragged
+    pl = {} if prompt_lens is None else dict(prompt_lens=prompt_lens)
     if lens is not None:
-        return model_forward_autograd_ragged(m, x, times, lens, prompt=prompt, cond=cond, cond_drop_prob=cond_drop_prob)
-    return model_forward_autograd(m, x, times, prompt=prompt, cond=cond, cond_drop_prob=cond_drop_prob)
+        return model_forward_autograd_ragged(m, x, times, lens, prompt=prompt, cond=cond, cond_drop_prob=cond_drop_prob, **pl)
+    return model_forward_autograd(m, x, times, prompt=prompt, cond=cond, cond_drop_prob=cond_drop_prob, **pl)
 
 
 # ------------------------------------------------------------------------------------------ Model
@@ -646,6 +657,7 @@ class Model(HipDenoiserMixin, nn.Module):
         precision="exact",
         ragged_training=False,
         head_dim_training=False,
+        ragged_conditioning=False,
     ):
         super().__init__()
         self.dim = dim
@@ -719,6 +731,7 @@ class Model(HipDenoiserMixin, nn.Module):
         self.train_precision = "exact"                # "mixed": half product + fp8 correction terms under a loss scale (training/passes.py `_Scale`)
         self.ragged_training = ragged_training        # True: forward(lens=) under autograd trains on a ragged batch (else it raises)
         self.head_dim_training = head_dim_training    # True: dim_head 32 / 128 train on the HIP kernels too (else: the composite, as before)
+        self.ragged_conditioning = ragged_conditioning    # True: forward(prompt_lens=) under autograd trains on ragged prompts (else it raises)
         self._hip_init(dict(dim=dim, depth=depth, dim_head=dim_head, heads=heads, ff_mult=ff_mult, wavenet_layers=wavenet_layers,
                             wavenet_stacks=wavenet_stacks, dim_cond_mult=dim_cond_mult, condition_on_prompt=condition_on_prompt,
                             dim_prompt=dim_prompt, num_latents_m=num_latents_m, resampler_depth=resampler_depth), precision)
@@ -728,9 +741,9 @@ class Model(HipDenoiserMixin, nn.Module):
     def device(self):
         return next(self.parameters()).device
 
-    def _forward_autograd(self, x, times, prompt=None, prompt_mask=None, cond=None, cond_drop_prob=None, lens=None):
+    def _forward_autograd(self, x, times, prompt=None, prompt_mask=None, cond=None, cond_drop_prob=None, lens=None, prompt_lens=None):
         """forward under autograd (loss.backward(), NS2:1635 / 1886).  Parameters on an MI355X: the HIP training path
         (training/model_pass.py: forward and backward kernels of libns2hip behind torch.autograd.Functions).  `train_backend = "composite"`
         (or NS2_TRAIN_BACKEND=composite), and parameters on the CPU (BASELINE config 1 as the reference runs it): the PyTorch
         composite of autograd_path.py."""
-        return _train_forward(self, x, times, prompt, cond, cond_drop_prob, prompt_mask=prompt_mask, lens=lens)
+        return _train_forward(self, x, times, prompt, cond, cond_drop_prob, prompt_mask=prompt_mask, lens=lens, prompt_lens=prompt_lens)

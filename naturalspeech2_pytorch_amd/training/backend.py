@@ -89,8 +89,10 @@ class HipBackend:
 
     def attention_masked(self, q, q_col0, k, k_col0, vt, B, H, Nq, Nk, kmask=None, drop=None, head_dim=64):
         """`attention` with a key-padding mask (uint8 [B, Nk], 1 = attend) and / or dropout on P (`drop` = (p, seed tensor on the device, call
-        index): csrc/dropout_keep.h) -- the attention of the conditioning encoders' training pass"""
-        assert self.prec == 3, "the encoders train in the exact arithmetic"
+        index): csrc/dropout_keep.h) -- the attention of the conditioning encoders' training pass.  The products are bf16 x3 on bf16 operands
+        whatever the backend's arithmetic; with a key mask alone the output o takes the GEMM format like `attention`'s (the kernel writes
+        o in the format it is handed: `Model`'s resampler under `prompt_lens` in the mixed arithmetic).  Dropout stays with the exact one."""
+        assert self.prec == 3 or drop is None, "the encoders train in the exact arithmetic"
         return ops._attention_fwd(q, q_col0, k, k_col0, vt.ptr(), vt.ptr() + 64, vt.ld, B, H, Nq, Nk, head_dim ** -0.5, 3, head_dim=head_dim,
                                   o_precision=self.prec, key_mask=kmask, want_lse=True, drop=drop)
 
@@ -180,29 +182,54 @@ class HipBackend:
         return dw
 
     # ---- DurationPitchPredictor: GroupNorm + SiLU (+ residual) of a ResnetBlock, the Linear(dim, 1) + ReLU heads
-    def groupnorm_silu_fwd(self, x, B, n, weight, bias, groups, eps, resid=None):
+    def groupnorm_silu_fwd(self, x, B, n, weight, bias, groups, eps, resid=None, row_lens=None):
         """x fp32 [B n, >= C] -> (y [B n, C] fp32, the rows [B n, C] the kernel read, stats): `stats` holds the per-chunk statistics slots
-        of ns2_groupnorm_silu, which `groupnorm_silu_bwd` recombines (the same mean and rstd, bit for bit)"""
+        of ns2_groupnorm_silu, which `groupnorm_silu_bwd` recombines (the same mean and rstd, bit for bit).  row_lens: int32 [B] on the
+        device, rows per utterance of a ragged batch (ns2_groupnorm_silu_lens: statistics over the rows before a length, rows of x and
+        resid from it on not read, rows of y there zeros); hand the same lengths to `groupnorm_silu_bwd`"""
         C = weight.shape[0]
         x = self._rows(x[:, :C], C)
         if resid is not None:
             resid = self._rows(resid[:, :C], C)
         y = torch.empty(B * n, C, dtype=torch.float32, device=x.device)
         stats = torch.empty(self.lib.ns2_groupnorm_workspace_bytes(B, n, C, groups), dtype=torch.uint8, device=x.device)
+        if row_lens is not None:
+            assert row_lens.dtype == torch.int32 and row_lens.is_cuda and row_lens.shape == (B,) and row_lens.is_contiguous()
+            check(self.lib.ns2_groupnorm_silu_lens(x.data_ptr(), B, n, C, groups, weight.data_ptr(), bias.data_ptr(), float(eps), _p(resid),
+                                                   row_lens.data_ptr(), y.data_ptr(), None, None, 0, 3, stats.data_ptr(), stats.numel(), _stream()),
+                  "ns2_groupnorm_silu_lens")
+            return y, x, stats
         check(self.lib.ns2_groupnorm_silu(x.data_ptr(), B, n, C, groups, weight.data_ptr(), bias.data_ptr(), float(eps), _p(resid), y.data_ptr(), None, None,
                                           0, 3, stats.data_ptr(), stats.numel(), _stream()), "ns2_groupnorm_silu")
         return y, x, stats
 
-    def groupnorm_silu_bwd(self, dy, x, stats, B, n, weight, bias, groups, eps):
-        """-> (dx [B n, C], dweight [C], dbias [C]); x, stats: what `groupnorm_silu_fwd` returned"""
+    def groupnorm_silu_bwd(self, dy, x, stats, B, n, weight, bias, groups, eps, row_lens=None):
+        """-> (dx [B n, C], dweight [C], dbias [C]); x, stats: what `groupnorm_silu_fwd` returned.  row_lens: what it got
+        (ns2_groupnorm_silu_bwd_lens, include/ns2hip_ragged_cond_train.h): rows of dy and x from a length on are not read, rows of dx
+        there are zero bits"""
         C = weight.shape[0]
         dx = torch.empty(B * n, C, dtype=torch.float32, device=x.device)
         dwb = torch.empty(2 * C, dtype=torch.float32, device=x.device)
         ws = torch.empty(self.lib.ns2_groupnorm_silu_bwd_workspace_bytes(B, n, C), dtype=torch.uint8, device=x.device)
+        if row_lens is not None:
+            assert row_lens.dtype == torch.int32 and row_lens.is_cuda and row_lens.shape == (B,) and row_lens.is_contiguous()
+            check(self.lib.ns2_groupnorm_silu_bwd_lens(dy.data_ptr(), dy.stride(0), x.data_ptr(), B, n, C, groups, weight.data_ptr(), bias.data_ptr(),
+                                                       float(eps), stats.data_ptr(), stats.numel(), row_lens.data_ptr(), dx.data_ptr(), dwb.data_ptr(),
+                                                       ws.data_ptr(), ws.numel(), _stream()), "ns2_groupnorm_silu_bwd_lens")
+            return dx, dwb[:C], dwb[C:]
         check(self.lib.ns2_groupnorm_silu_bwd(dy.data_ptr(), dy.stride(0), x.data_ptr(), B, n, C, groups, weight.data_ptr(), bias.data_ptr(), float(eps),
                                               stats.data_ptr(), stats.numel(), dx.data_ptr(), dwb.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
               "ns2_groupnorm_silu_bwd")
         return dx, dwb[:C], dwb[C:]
+
+    def keep_rows(self, t, B, n, lens):
+        """a fresh contiguous copy of the fp32 rows t [B n, C] (C % 4 == 0) whose rows from lens[b] on are zero bits (ns2_zero_rows_lens):
+        the select of a ragged conditioning pass, and its backward on the cotangent.  lens: int32 [B] on the device.  Rows that are not
+        whole 16-byte vectors (C % 4 != 0: a codebook dimension) take the same select as a torch.where on the device"""
+        if t.shape[1] % 4:
+            keep = torch.arange(n, device=t.device)[None] < lens.clamp(1, n)[:, None]
+            return torch.where(keep.reshape(B * n, 1), t, torch.zeros((), dtype=t.dtype, device=t.device))
+        return ops.zero_rows(t.clone(memory_format=torch.contiguous_format), B, n, lens)
 
     def row_dot_relu(self, h, w, b):
         """relu(h[:, :K] . w + b) -> [M]"""

@@ -4,7 +4,8 @@ has left its scaled domain (`_ScaleOut` on prompt / cond in model_pass.py)."""
 import torch
 import torch.nn.functional as F
 
-from .functions import HEAD_DIMS_TRAIN, attn_apply, train_head_dim, EmbeddingFn, FeedForwardFn, GemmFn, RmsNormFn, SiluFn, _c
+from .. import ops
+from .functions import HEAD_DIMS_TRAIN, attn_apply, train_head_dim, EmbeddingFn, FeedForwardFn, GemmFn, KeepRowsFn, RmsNormFn, SiluFn, _c
 from .passes import TRAIN_PRECISIONS, training_pass
 
 _EXACT = TRAIN_PRECISIONS["exact"]
@@ -23,9 +24,20 @@ def _key_mask(mask, b, n):
     return mask.to(torch.uint8).contiguous()
 
 
-def _transformer_train(tr, h, b, n, mask):
+def lens_key_mask(lens, n):
+    """the byte mask of keys [0, clamp(lens[i], 1, n)) of every utterance, uint8 [b, n], formed on the device from int32 lengths: no host read
+    (`_key_mask`'s check has nothing to find: a clamped length always leaves one key), so a captured pass follows lengths rewritten between
+    replays"""
+    return (torch.arange(n, device=lens.device)[None] < lens.clamp(1, n)[:, None]).to(torch.uint8).contiguous()
+
+
+def _transformer_train(tr, h, b, n, mask, km=None, row_lens=None):
+    """km: a byte mask already made (`lens_key_mask`) instead of `mask`; row_lens: the int32 lengths it was made from -- the rows of h from a
+    length on are zeros on entry and are selected to 0 again behind every layer (an attention's output for a padding query and a
+    FeedForward's biases are finite but not 0), so every attention sees zero rows where its mask hides keys (`AttnFn` masked_rows_zero)"""
     d = tr.dim
-    km = _key_mask(mask, b, n)
+    if km is None:
+        km = _key_mask(mask, b, n)
     p = float(tr.dropout) if tr.training else 0.
     seed = None
     if p > 0:
@@ -39,9 +51,11 @@ def _transformer_train(tr, h, b, n, mask):
         tr.last_dropout_seed = seed
     for li, (norm1, attn, norm2, ff) in enumerate(tr.layers):
         h = attn_apply(_c(h), None, None, attn.to_q.weight, attn.to_kv.weight, attn.to_out.weight, n, tr.heads, 0, norm1.gamma, km,
-                       (p, seed, li) if p > 0 else None, head_dim=train_head_dim(tr, tr.dim_head))
+                       (p, seed, li) if p > 0 else None, head_dim=train_head_dim(tr, tr.dim_head), masked_rows_zero=row_lens is not None)
         l1, l2 = getattr(ff, "0"), getattr(ff, "2")
         h = FeedForwardFn.apply(_c(h), None, l1.weight, l1.bias, None, None, l2.weight, l2.bias, n, norm2.gamma)
+        if row_lens is not None:
+            h = KeepRowsFn.apply(h, n, row_lens)
     if hasattr(tr.norm, "gamma"):
         h = RmsNormFn.apply(_c(h), tr.norm.gamma)
     return h.reshape(b, n, d)
@@ -55,27 +69,44 @@ def transformer_forward_train(tr, x, mask=None):
         return _transformer_train(tr, _c(x.float()).reshape(b * n, d), b, n, mask).to(x.dtype)
 
 
-def speech_prompt_encoder_forward_train(enc, x):
+def speech_prompt_encoder_forward_train(enc, x, lens=None):
     """`SpeechPromptEncoder.forward` (NS2:289-341): the "same" k = 9 convolutions as GEMMs with pad_left = padding, SiLU on the kept fp32
-    pre-activation, then the Transformer"""
+    pre-activation, then the Transformer.
+    `lens` (`ragged_conditioning`; include/ns2hip_ragged_cond_train.h): prompt rows per utterance, integer [b].  The input and every
+    convolution's output are selected to 0 from lens[i] on (`KeepRowsFn`: the same select on the cotangent), so the "same" convolutions read
+    what they read behind the end of the utterance alone; the Transformer runs under the key mask arange(n) < lens[:, None] on the existing
+    key-mask / dropout kernels; the output rows from lens[i] on are selected to 0.  Nothing reads a device tensor of lengths on the host."""
     b, n, _ = x.shape
     with training_pass(_EXACT, x):
         h = _c(x.float()).reshape(b * n, enc.dim)
+        if lens is None:
+            for m in enc.conv:
+                if isinstance(m, torch.nn.Conv1d):
+                    h = SiluFn.apply(_c(GemmFn.apply(_c(h), m.weight, m.bias, None, n, 1, enc.padding)))
+            return _transformer_train(enc.transformer, h, b, n, None).to(x.dtype)
+        ln = ops._front_lens(lens, b, x.device)
+        h = KeepRowsFn.apply(h, n, ln)
         for m in enc.conv:
             if isinstance(m, torch.nn.Conv1d):
-                h = SiluFn.apply(_c(GemmFn.apply(_c(h), m.weight, m.bias, None, n, 1, enc.padding)))
-        return _transformer_train(enc.transformer, h, b, n, None).to(x.dtype)
+                h = KeepRowsFn.apply(SiluFn.apply(_c(GemmFn.apply(_c(h), m.weight, m.bias, None, n, 1, enc.padding))), n, ln)
+        out = _transformer_train(enc.transformer, h, b, n, None, km=lens_key_mask(ln, n), row_lens=ln)
+        return KeepRowsFn.apply(_c(out).reshape(b * n, -1), n, ln).reshape(b, n, -1).to(x.dtype)
 
 
-def phoneme_encoder_forward_train(enc, ids, mask=None):
+def phoneme_encoder_forward_train(enc, ids, mask=None, lens=None):
     """`PhonemeEncoder.forward` on token ids (NS2:228-287): embedding (padded ids -> pad_id), CausalConv1d k = 9 + SiLU, conv dropout
-    (F.dropout on the fp32 activations: pointwise plumbing), then the Transformer under the key-padding mask"""
+    (F.dropout on the fp32 activations: pointwise plumbing), then the Transformer under the key-padding mask.
+    lens (instead of mask): phonemes per utterance, integer [b] on the device -- the byte mask is formed there (`lens_key_mask`: no host read)"""
     b, n = ids.shape
     with training_pass(_EXACT, ids):
         h = EmbeddingFn.apply(ids, enc.token_emb.weight, enc.pad_id)
         conv = enc.conv[1]
         h = SiluFn.apply(_c(GemmFn.apply(_c(h), conv.weight, conv.bias, None, n, 1)))
         h = F.dropout(h, enc.conv_dropout, enc.training)
+        if lens is not None:
+            assert mask is None
+            ln = ops._front_lens(lens, b, ids.device)
+            return _transformer_train(enc.transformer, KeepRowsFn.apply(h, n, ln), b, n, None, km=lens_key_mask(ln, n), row_lens=ln)
         return _transformer_train(enc.transformer, h, b, n, mask)
 
 

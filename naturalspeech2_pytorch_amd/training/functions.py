@@ -183,12 +183,20 @@ class AttnFn(torch.autograd.Function):
     `lens` -- int32 [B] on the device, the utterances' lengths of a ragged batch (self-attention only, without kmask / drop;
     include/ns2hip_ragged_train.h): keys stop at the length, and the rows of o and of dq | dk | dv from the length on are exact zeros.
     The kernels alone read it.  Absent by default: same kernels, same bits.
+    `masked_rows_zero` -- a promise of the ragged conditioning passes (include/ns2hip_ragged_cond_train.h), with `kmask` and without `drop`:
+    the rows of h / the context that the mask hides are ZEROS (so their k and v are zeros: no bias in to_q / to_kv, RMSNorm(0) = 0), the
+    cotangent of every query row they stand for is 0, and the caller selects the returned gradient rows of the hidden rows to 0.  The
+    backward then runs the PLAIN attention backward -- the instantiation the pass without lengths runs at dropout 0, i.e. what each
+    utterance alone gets: a hidden key has P = exp2(-lse) there instead of 0, but k = v = 0 keeps it out of dq, a zero dO row keeps the
+    hidden queries out of dk | dv, the hidden rows' own dk | dv meet zero operand rows in the weight gradient, and what they leave in the
+    input gradient is selected away.  (The key-mask backward instantiation gives other last bits than the plain one on the same operands;
+    with dropout both the ragged batch and the utterance alone run it.)  Absent by default.
     `head_dim` -- 32 or 128 instead of the heads of 64 (include/ns2hip_head_dim_train.h; `head_dim_training`).  The backend is handed it
     only when it is not 64, as it is handed `lens` only when there are lengths: same calls, same kernels, same bits by default."""
 
     @staticmethod
     def forward(ctx, h, film, ctxt, wq, wkv, wout, seq_len, heads, ctx_len, gamma=None, kmask=None, drop=None, resid=None, lens=None,
-                head_dim=64):
+                head_dim=64, masked_rows_zero=False):
         assert resid is None or (film is None and gamma is None)
         assert lens is None or (ctxt is None and kmask is None and drop is None), "lens: the plain self-attention only"
         bk = _begin(ctx)
@@ -217,6 +225,7 @@ class AttnFn(torch.autograd.Function):
         ctx.save_for_backward(h, film, wq, wkv, wout, lse, gamma)
         ctx.pl, ctx.cfg, ctx.md, ctx.lens = (xn, q, k, v, o, cp), (seq_len, heads, Nk, qc, kc, vc, ctxt is not None), (kmask, drop), lens
         ctx.own_resid, ctx.hd = resid is None, hd
+        ctx.plain_bwd = bool(masked_rows_zero) and kmask is not None and drop is None
         return y[:, :d]
 
     @staticmethod
@@ -234,7 +243,7 @@ class AttnFn(torch.autograd.Function):
         if ctx.lens is not None:
             def attention_bwd(*args, **kw):
                 bk.attention_bwd(*args, lens=ctx.lens, **hd, **kw)
-        elif kmask is None and drop is None:
+        elif (kmask is None and drop is None) or ctx.plain_bwd:
             def attention_bwd(*args, **kw):
                 bk.attention_bwd(*args, **hd, **kw)
         else:
@@ -277,12 +286,14 @@ class AttnFn(torch.autograd.Function):
         else:
             dh, dfilm, dgamma, dresid = dxn[:, :d], None, None, dy
         dfilm, dwq, dwkv, dwout, dgamma = _un(ctx, dfilm, dwq, dwkv, dwout, dgamma)
-        return dh, dfilm, dctx, dwq, dwkv, dwout, None, None, None, dgamma, None, None, dresid, None, None
+        return dh, dfilm, dctx, dwq, dwkv, dwout, None, None, None, dgamma, None, None, dresid, None, None, None
 
 
-def attn_apply(*args, head_dim=64):
+def attn_apply(*args, head_dim=64, masked_rows_zero=False):
     """`AttnFn.apply(*args)`; a head dim other than 64 (`head_dim_training`) is appended behind the optional arguments, 64 leaves the
-    call exactly what it was"""
+    call exactly what it was; `masked_rows_zero` (the ragged conditioning passes) likewise behind the head dim"""
+    if masked_rows_zero:
+        return AttnFn.apply(*args, *([None] * (14 - len(args))), head_dim, True)
     if head_dim == 64:
         return AttnFn.apply(*args)
     return AttnFn.apply(*args, *([None] * (14 - len(args))), head_dim)
@@ -471,15 +482,20 @@ class RvqCrossEntropyFn(torch.autograd.Function):
 
 class GroupNormSiluFn(torch.autograd.Function):
     """silu(GroupNorm(x)) (+ resid) over the rows of utterances of `seq_len` tokens: a Block of the DurationPitchPredictor's ResnetBlock, the
-    last one with the ResnetBlock's input as `resid` (NS2:346-400).  The backward normalises with the forward's own statistics slots."""
+    last one with the ResnetBlock's input as `resid` (NS2:346-400).  The backward normalises with the forward's own statistics slots.
+    `row_lens` -- int32 [B] on the device, the utterances' row counts of a ragged batch (include/ns2hip_ragged_cond_train.h): statistics
+    and gradient sums stop at a length, rows of y and of dx from it on are exact zeros (so `resid` gets no gradient there either), and
+    nothing there is read.  The kernels alone read it.  Absent by default: the backend gets the calls without it, same kernels, same bits."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, resid, seq_len, groups, eps):
+    def forward(ctx, x, weight, bias, resid, seq_len, groups, eps, row_lens=None):
         bk = _begin(ctx)
         B = x.shape[0] // seq_len
-        y, rows, stats = bk.groupnorm_silu_fwd(x, B, seq_len, weight.detach(), bias.detach(), groups, eps, resid=resid)
+        kw = {} if row_lens is None else dict(row_lens=row_lens)
+        y, rows, stats = bk.groupnorm_silu_fwd(x, B, seq_len, weight.detach(), bias.detach(), groups, eps, resid=resid, **kw)
         ctx.save_for_backward(rows, weight, bias, stats)
         ctx.cfg = (B, seq_len, groups, eps, resid is not None)
+        ctx.kw = kw
         return y
 
     @staticmethod
@@ -487,8 +503,28 @@ class GroupNormSiluFn(torch.autograd.Function):
         rows, weight, bias, stats = ctx.saved_tensors
         B, seq_len, groups, eps, has_resid = ctx.cfg
         dy = _rowmajor(dy)
-        dx, dw, db = ctx.bk.groupnorm_silu_bwd(dy, rows, stats, B, seq_len, weight.detach(), bias.detach(), groups, eps)
-        return dx, *_un(ctx, dw, db), (dy if has_resid else None), None, None, None
+        dx, dw, db = ctx.bk.groupnorm_silu_bwd(dy, rows, stats, B, seq_len, weight.detach(), bias.detach(), groups, eps, **ctx.kw)
+        dres = None
+        if has_resid:
+            # the residual was not added behind a length: its gradient there is 0, whatever dy holds (a "same" conv's dgrad reaches back there)
+            dres = ctx.bk.keep_rows(dy, B, seq_len, ctx.kw["row_lens"]) if ctx.kw else dy
+        return dx, *_un(ctx, dw, db), dres, None, None, None, None
+
+
+class KeepRowsFn(torch.autograd.Function):
+    """the rows [B seq_len, C] of a ragged batch with those from lens[b] on selected to exact 0 -- a select, not a product: what lies there
+    may be NaN -- in a fresh buffer (ns2_zero_rows_lens); the backward is the same select on the cotangent.  lens: int32 [B] on the
+    device, read by the kernel alone."""
+
+    @staticmethod
+    def forward(ctx, x, seq_len, lens):
+        bk = _begin(ctx)
+        ctx.cfg = (x.shape[0] // seq_len, seq_len, lens)
+        return bk.keep_rows(x, *ctx.cfg)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return ctx.bk.keep_rows(dy, *ctx.cfg), None, None
 
 
 class RowDotReluFn(torch.autograd.Function):

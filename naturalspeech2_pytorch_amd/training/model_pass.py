@@ -8,10 +8,12 @@ from .functions import HEAD_DIMS_TRAIN, attn_apply, train_head_dim, CondProjecti
 from .passes import TRAIN_PRECISIONS, _enter, _ScaleIn, training_pass
 
 
-def _resampler(pr, prompt, heads, head_dim=64):
+def _resampler(pr, prompt, heads, head_dim=64, key_mask=None):
     """PerceiverResampler (NS2:532-579) on the Functions of functions.py: per layer latents += Attention(latents, context = cat(latents,
     proj(prompt))) and latents += FeedForward(latents) (no norms in front, no conv), then RMSNorm * gamma.  Round 4 ran this part of
-    the conditioned model's graph as the PyTorch composite (0.2 % of the FLOPs, but the one piece of `Model`'s backward on torch ops)."""
+    the conditioned model's graph as the PyTorch composite (0.2 % of the FLOPs, but the one piece of `Model`'s backward on torch ops).
+    key_mask: uint8 [b, Lm + n_p] or None -- the keys [0, Lm + prompt_lens[i]) of cat(latents, prompt) of a ragged prompt batch: every
+    attention then runs on the key-mask training kernels (the rows of `prompt` behind a length are zeros: the caller's select)."""
     b, n_p, _ = prompt.shape
     pc = getattr(pr, "proj_context", None)
     px = _c(prompt).reshape(b * n_p, -1)
@@ -19,10 +21,16 @@ def _resampler(pr, prompt, heads, head_dim=64):
         px = GemmFn.apply(px, pc.weight, pc.bias, None, 0, 1)
     Lm, d = pr.latents.shape
     px = px.reshape(b, n_p, d)
+    if key_mask is not None:                                                 # (proj_context's bias: the hidden rows are zeros again -- AttnFn masked_rows_zero)
+        px = _keep(px, key_mask[:, -n_p:, None].bool())
     lat = _enter(pr.latents)[None].expand(b, -1, -1).reshape(b * Lm, d)      # (a copy: its gradient sums over the batch into pr.latents)
     for attn, ff in pr.layers:
         context = torch.cat((lat.reshape(b, Lm, d), px), dim=1).reshape(b * (Lm + n_p), d)     # cross_attn_include_queries, NS2:1060-1061
-        lat = attn_apply(_c(lat), None, context, attn.to_q.weight, attn.to_kv.weight, attn.to_out.weight, Lm, heads, Lm + n_p, head_dim=head_dim)
+        if key_mask is None:
+            lat = attn_apply(_c(lat), None, context, attn.to_q.weight, attn.to_kv.weight, attn.to_out.weight, Lm, heads, Lm + n_p, head_dim=head_dim)
+        else:
+            lat = attn_apply(_c(lat), None, context, attn.to_q.weight, attn.to_kv.weight, attn.to_out.weight, Lm, heads, Lm + n_p, None, key_mask,
+                             head_dim=head_dim, masked_rows_zero=True)
         l1, l2 = getattr(ff, "0"), getattr(ff, "2")
         lat = FeedForwardFn.apply(_c(lat), None, l1.weight, l1.bias, None, None, l2.weight, l2.bias, Lm)
     return RmsNormFn.apply(_c(lat), pr.norm.gamma).reshape(b, Lm, d)
@@ -41,29 +49,36 @@ def _keep(t_bnd, mask):
     return torch.where(mask, t_bnd, torch.zeros((), dtype=t_bnd.dtype, device=t_bnd.device))
 
 
-def model_forward_train(m, x, times, prompt=None, cond=None, cond_drop_prob=None, lens=None):
+def model_forward_train(m, x, times, prompt=None, cond=None, cond_drop_prob=None, lens=None, prompt_lens=None):
     """`Model.forward` (NS2:929-1000) as a differentiable graph whose token-sized arithmetic is HIP (package docstring).
     `m` owns the reference's parameters (this package's `Model` or `compat.HipBackedModel`).  `m.train_precision`: "exact"
     (default: bf16 x3) or "mixed" (IEEE-half product + fp8 correction terms on FMT_H8 operands under a loss scale, `passes._Scale`).
     `lens` (not in the reference): frames per utterance of a ragged batch, integer [b] (include/ns2hip_ragged_train.h).  Rows
     of x and of the projected cond from a length on are selected to 0 at the entry, every self-attention stops at the length in both
-    directions, and the returned rows from a length on are selected to 0 -- which also zeroes the cotangent there.  No host read."""
+    directions, and the returned rows from a length on are selected to 0 -- which also zeroes the cotangent there.  No host read.
+    `prompt_lens` (not in the reference; `ragged_conditioning`): prompt rows per utterance, integer [b] (include/ns2hip_ragged_cond_train.h;
+    DESIGN §9).  The prompt rows behind a length are selected to 0 at the entry, the mean of to_prompt_cond is a masked sum over rows
+    [0, prompt_lens[i]) divided by the clamped length, and the perceiver resampler's attentions run under the key mask
+    [0, Lm + prompt_lens[i]) of cat(latents, prompt), all formed on the device.  With and without `lens`."""
     tp = getattr(m, "train_precision", "exact")
     assert tp in TRAIN_PRECISIONS, f"train_precision must be one of {sorted(TRAIN_PRECISIONS)}"
     with training_pass(TRAIN_PRECISIONS[tp], x) as p:
+        pl = {}
+        if prompt_lens is not None:
+            pl = dict(prompt_keep=_lens_and_mask(prompt_lens, x.shape[0], prompt.shape[1], x.device)[1])
         if lens is None:
-            out = _forward_train(m, x, times, prompt, cond, cond_drop_prob)
+            out = _forward_train(m, x, times, prompt, cond, cond_drop_prob, **pl)
         else:
             ln, keep = _lens_and_mask(lens, x.shape[0], x.shape[1], x.device)
-            out = _keep(_forward_train(m, x, times, prompt, cond, cond_drop_prob, ln, keep), keep)
+            out = _keep(_forward_train(m, x, times, prompt, cond, cond_drop_prob, ln, keep, **pl), keep)
         if p.scale is not None:
             m._last_loss_scale = p.scale             # (inspection / tests: the scale the last backward chose)
             out = _ScaleIn.apply(out, p.scale)
         return out
 
 
-def _forward_train(m, x, times, prompt, cond, cond_drop_prob, lens=None, keep=None):
-    """lens / keep: `_lens_and_mask` of a ragged batch, or neither"""
+def _forward_train(m, x, times, prompt, cond, cond_drop_prob, lens=None, keep=None, prompt_keep=None):
+    """lens / keep: `_lens_and_mask` of a ragged batch, or neither; prompt_keep: the bool [b, n_p, 1] of `_lens_and_mask(prompt_lens)`, or None"""
     b, n, d = x.shape
     M = b * n
     p = m.cond_drop_prob if cond_drop_prob is None else cond_drop_prob
@@ -87,12 +102,22 @@ def _forward_train(m, x, times, prompt, cond, cond_drop_prob, lens=None, keep=No
             return torch.rand(b, device=x.device) < p
 
         dm = mask()
-        pc = F.silu(_lin(getattr(m.to_prompt_cond, "1"), prompt.float().mean(dim=1)))
+        res_mask = None
+        if prompt_keep is None:
+            pmean = prompt.float().mean(dim=1)
+        else:
+            # [b, d]-sized work on the device: a masked sum over the rows before a length / the clamped length (the mask has that many rows)
+            prompt = _keep(prompt.float(), prompt_keep)
+            # (sum times the reciprocal, the form of torch's mean: a device tensor of full lengths gives prompt.mean(dim=1))
+            pmean = prompt.sum(dim=1) * (1.0 / prompt_keep.sum(dim=1).to(prompt.dtype))
+            Lm = m.perceiver_resampler.latents.shape[0]
+            res_mask = torch.cat((torch.ones(b, Lm, dtype=torch.bool, device=x.device), prompt_keep[..., 0]), dim=1).to(torch.uint8).contiguous()
+        pc = F.silu(_lin(getattr(m.to_prompt_cond, "1"), pmean))
         pc = torch.where(dm[:, None], m.null_prompt_cond, pc)
         t = torch.cat((t, pc), dim=-1)
         # (`prompt` and `cond` come from trainable modules upstream -- the prompt / phoneme encoders, NS2:1635 -- so their gradients
         # leave the scaled domain like x's: ADVICE r5)
-        c = torch.where(dm[:, None, None], _enter(m.null_prompt_tokens), _resampler(m.perceiver_resampler, _enter(prompt.float()), heads, hd))   # [b, Lm, d]
+        c = torch.where(dm[:, None, None], _enter(m.null_prompt_tokens), _resampler(m.perceiver_resampler, _enter(prompt.float()), heads, hd, res_mask))   # [b, Lm, d]
         # cond_to_model_dim: 1x1 conv over channel-first cond (NS2:978) = a Linear over the frames
         n_c = cond.shape[-1]
         if keep is not None:

@@ -85,16 +85,18 @@ class _PackedCache:
             parts, keys = [], set()
             for k, v in self.map.items():
                 params = [r() for r in v.refs]
+                if any(p is None for p in params):                     # (collected since the check above: a cycle freed in between)
+                    return False
                 if not any(p.requires_grad for p in params):
                     continue
                 keys.add(k)
+                dev = params[0].device
                 for (idx, mode, row0, col0) in v.parts:
                     parts.append(self._part(_lib.RepackPart, v.pw, params[idx], mode, row0, col0))
             if not parts:
                 return False
             arr = (_lib.RepackPart * len(parts))(*parts)
             nbytes = lib.ns2_weights_repack_table_bytes(len(parts))
-            dev = next(r() for v in self.map.values() for r in v.refs).device
             table = torch.empty(nbytes, dtype=torch.uint8, device=dev)
             total = ctypes.c_int64(0)
             check(lib.ns2_weights_repack_build(arr, len(parts), table.data_ptr(), nbytes, ctypes.byref(total), _stream()), "ns2_weights_repack_build")

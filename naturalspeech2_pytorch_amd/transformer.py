@@ -47,6 +47,17 @@ def needs_autograd(module, x=None):
 TRAIN_BACKENDS = ("composite", "hip")
 
 
+def host_full_lens(lens, n, b):
+    """are these per-utterance lengths known ON THE HOST to be full (None, or a list / CPU tensor of b entries, every one >= n)?  A training pass
+    with `ragged_conditioning` then takes the call without lengths -- the same kernels, the same bits.  A device tensor is never read: it
+    counts as ragged, and the pass follows values rewritten between replays of a captured graph."""
+    if lens is None:
+        return True
+    if torch.is_tensor(lens):
+        return (not lens.is_cuda) and tuple(lens.shape) == (b,) and bool((lens >= n).all())
+    return len(lens) == b and all(int(l) >= n for l in lens)
+
+
 def use_hip_training(module, x, mask=None):
     """does a call that needs autograd run the HIP training path of training/encoder_pass.py (`train_backend="hip"`, GPU tensors, a module and mask the
     kernels are written for) -- else the PyTorch composite, exactly as `Model` falls back through `training.unsupported_reason`"""
