@@ -37,6 +37,7 @@ HEAD_DIM_TRAIN_HEADER_PATH = os.path.join(_HERE, "..", "include", "ns2hip_head_d
 RAGGED_AUDIO_HEADER_PATH = os.path.join(_HERE, "..", "include", "ns2hip_ragged_audio.h")   # lengths in mel, pitch and the RVQ term: likewise
 FOLD_HEADER_PATH = os.path.join(_HERE, "..", "include", "ns2hip_fold.h")   # the feed-forward fold: likewise
 RAGGED_COND_TRAIN_HEADER_PATH = os.path.join(_HERE, "..", "include", "ns2hip_ragged_cond_train.h")   # lengths through the conditioning's training pass: likewise
+RAGGED_SKIP_HEADER_PATH = os.path.join(_HERE, "..", "include", "ns2hip_ragged_skip.h")   # skipping the hidden row tiles of a ragged sampling batch: likewise
 
 
 class Ns2Error(RuntimeError):
@@ -165,6 +166,11 @@ if not os.path.exists(RAGGED_COND_TRAIN_HEADER_PATH):
 with open(RAGGED_COND_TRAIN_HEADER_PATH) as _f:
     _, _, RAGGED_COND_TRAIN_SIGNATURES = parse_header(_f.read())
 
+if not os.path.exists(RAGGED_SKIP_HEADER_PATH):
+    raise Ns2Error(f"{RAGGED_SKIP_HEADER_PATH} not found: the binding is derived from the header, it ships with the package's source tree")
+with open(RAGGED_SKIP_HEADER_PATH) as _f:                        # (the argument blocks, ns2_weight and ns2_model_config: c_void_p here too)
+    _, _, RAGGED_SKIP_SIGNATURES = parse_header(_f.read())
+
 _lib = None
 
 
@@ -179,7 +185,7 @@ def load():
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in {**SIGNATURES, **OPTIM_SIGNATURES, **PITCH_SIGNATURES, **RAGGED_SIGNATURES, **FRONT_SIGNATURES,
                               **RAGGED_TRAIN_SIGNATURES, **HEAD_DIM_TRAIN_SIGNATURES, **RAGGED_AUDIO_SIGNATURES, **FOLD_SIGNATURES,
-                              **RAGGED_COND_TRAIN_SIGNATURES}.items():
+                              **RAGGED_COND_TRAIN_SIGNATURES, **RAGGED_SKIP_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -244,3 +250,8 @@ def fold_header_symbols():
 def ragged_cond_train_header_symbols():
     """Symbols declared in include/ns2hip_ragged_cond_train.h"""
     return sorted(RAGGED_COND_TRAIN_SIGNATURES)
+
+
+def ragged_skip_header_symbols():
+    """Symbols declared in include/ns2hip_ragged_skip.h"""
+    return sorted(RAGGED_SKIP_SIGNATURES)

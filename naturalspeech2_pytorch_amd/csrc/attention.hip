@@ -70,7 +70,11 @@ NS2_DEVINL uint4 mask_chunk(uint4 v, int nvalid) {
 // are the utterances' lengths on the QUERY side too.  Query rows from the length on load no q, and leave as o = zero bits in the output
 // format and lse = +inf (the backward's statistic of a query beyond Nq); a workgroup whose whole query tile lies there writes those and
 // returns before anything is staged.  Rows before the length see what they see alone at Nq = Nk = length.  Once more a separate instantiation.
-template <int NSPLIT, bool F16, int NW, bool WLSE, int D = 64, bool DROP = false, bool QLENS = false>
+// QSKIP (the plain inference forward only): ragged skipping (include/ns2hip_ragged_skip.h) -- AttnArgs::qlens are the utterances' lengths on
+// the query side; a workgroup whose query rows all lie at or behind the utterance's computed extent (256-row granules, ns2_common.h
+// ragged_extent) returns before anything is loaded and leaves its o rows as they were.  The (utterance, head) pairs differ in work, so
+// they are spread over the XCDs as QLENS spreads them.  Once more a separate instantiation.
+template <int NSPLIT, bool F16, int NW, bool WLSE, int D = 64, bool DROP = false, bool QLENS = false, bool QSKIP = false>
 __global__ __launch_bounds__(64 * NW, ((NSPLIT == 3 && D == 128) ? 1 : (NSPLIT == 3 || D == 128) ? 2 : 3)) void attn_kernel(const AttnArgs a) {
   using G = AtGeom<D>;
   constexpr int DC = D / 16;                         // 16-deep k chunks of the q . k contraction
@@ -81,6 +85,7 @@ __global__ __launch_bounds__(64 * NW, ((NSPLIT == 3 && D == 128) ? 1 : (NSPLIT =
   constexpr int CPT = 8 * D / NT;                    // 16-B chunks of one plane per thread: the K tile has 64 x D / 8, the V^T tile D x 8
   static_assert(CPT >= 1 && CPT * NT == 8 * D, "whole chunks per thread");
   static_assert(!QLENS || (WLSE && !DROP), "query lengths belong to the training forward without dropout");
+  static_assert(!QSKIP || (!WLSE && !DROP && !QLENS), "skipping belongs to the plain inference forward");
   constexpr int STAGE_BYTES = NP * (G::KPLANE + G::VPLANE);     // K planes then V^T planes
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
@@ -89,10 +94,13 @@ __global__ __launch_bounds__(64 * NW, ((NSPLIT == 3 && D == 128) ? 1 : (NSPLIT =
   // 1-D grid, XCD-aware: the query tiles of one (batch, head) get consecutive remapped ids and therefore share one
   // XCD's L2 for their K / V^T re-reads (rocprofv3 FETCH_SIZE showed ~3x over-fetch with the default round-robin).
   const int nqt = (a.Nq + QB - 1) / QB;
-  int bid = QLENS ? xcd_spread(blockIdx.x, gridDim.x, nqt) : xcd_remap(blockIdx.x, gridDim.x);      // (QLENS: the pairs differ in work)
+  int bid = (QLENS || QSKIP) ? xcd_spread(blockIdx.x, gridDim.x, nqt) : xcd_remap(blockIdx.x, gridDim.x);      // (QLENS, QSKIP: the pairs differ in work)
   const int qt = bid % nqt;
   bid /= nqt;
   const int h = bid % a.H, b = bid / a.H;
+  if constexpr (QSKIP) {
+    if (qt * QB >= ragged_extent(a.qlens[b], a.Nq)) return;      // workgroup-uniform, before the first load and barrier
+  }
   const int qrow = qt * QB + wave * 32 + l31;
   const bool q_ok = qrow < a.Nq;
   // keys this utterance attends to: a.Nk, or its own count (AttnArgs::klens, clamped into [1, Nk]); a.Nk stays the stride of every address
@@ -340,16 +348,16 @@ __global__ __launch_bounds__(64 * NW, ((NSPLIT == 3 && D == 128) ? 1 : (NSPLIT =
 
 namespace ns2 {
 
-template <int NSPLIT, bool F16, int NW, bool WLSE, int D = 64, bool DROP = false, bool QLENS = false>
+template <int NSPLIT, bool F16, int NW, bool WLSE, int D = 64, bool DROP = false, bool QLENS = false, bool QSKIP = false>
 static hipError_t launch_attn_w(const AttnArgs& a, hipStream_t s) {
   const size_t lds = 2 * (NSPLIT == 3 ? 2 : 1) * (AtGeom<D>::KPLANE + AtGeom<D>::VPLANE);
   static DynLdsAttr attr;
   {
-    hipError_t e = attr.ensure(reinterpret_cast<const void*>(&attn_kernel<NSPLIT, F16, NW, WLSE, D, DROP, QLENS>), (int)lds);
+    hipError_t e = attr.ensure(reinterpret_cast<const void*>(&attn_kernel<NSPLIT, F16, NW, WLSE, D, DROP, QLENS, QSKIP>), (int)lds);
     if (e != hipSuccess) return e;
   }
   dim3 grid(((a.Nq + 32 * NW - 1) / (32 * NW)) * a.H * a.B);
-  hipLaunchKernelGGL((attn_kernel<NSPLIT, F16, NW, WLSE, D, DROP, QLENS>), grid, dim3(64 * NW), lds, s, a);
+  hipLaunchKernelGGL((attn_kernel<NSPLIT, F16, NW, WLSE, D, DROP, QLENS, QSKIP>), grid, dim3(64 * NW), lds, s, a);
   return hipGetLastError();
 }
 // the training forward (precision 3, lse) at head dims 32 / 128: plain, with dropout (and key mask), on a ragged batch -- the three
@@ -366,6 +374,11 @@ static hipError_t launch_attn_t(const AttnArgs& a, hipStream_t s, bool train_hd)
   if ((D == 32 || D == 128) && a.lse) {                // launch_attention keeps refusing it: its callers' backward has a head dim of 64
     if constexpr (NSPLIT == 3) { if (train_hd) return D == 32 ? launch_attn_train_d<32>(a, s) : launch_attn_train_d<128>(a, s); }
     return hipErrorInvalidValue;
+  }
+  if (a.qlens) {                                       // ragged skipping (launch_attention_any: no lse, mask or dropout with it)
+    if (D == 32) return launch_attn_w<NSPLIT, F16, 4, false, 32, false, false, true>(a, s);
+    if (D == 128) return launch_attn_w<NSPLIT, F16, 4, false, 128, false, false, true>(a, s);
+    return D == 64 ? launch_attn_w<NSPLIT, F16, 4, false, 64, false, false, true>(a, s) : hipErrorInvalidValue;
   }
   if (D == 32) return a.drop_seed ? hipErrorInvalidValue : launch_attn_w<NSPLIT, F16, 4, false, 32>(a, s);
   if (D == 128) return a.drop_seed ? hipErrorInvalidValue : launch_attn_w<NSPLIT, F16, 4, false, 128>(a, s);
@@ -413,15 +426,16 @@ static bool attn_fast_eligible(const AttnArgs& a) {
 // kernels give the same bits and the output cannot tell which one ran.
 static std::atomic<long long> g_fast_launches{0};
 long long attention_fast_launches() { return g_fast_launches.load(std::memory_order_relaxed); }
-template <int PF, bool LENS = false>
+template <int PF, bool LENS = false, bool QSKIP = false>
 static hipError_t launch_attn_fast(const AttnArgs& a, hipStream_t s) {
+  if constexpr (!QSKIP) { if (a.qlens) return launch_attn_fast<PF, LENS, true>(a, s); }
   static DynLdsAttr attr;
   g_fast_launches.fetch_add(1, std::memory_order_relaxed);
   {
-    hipError_t e = attr.ensure(reinterpret_cast<const void*>(&attn_fast_kernel<PF, LENS>), AF_LDS);
+    hipError_t e = attr.ensure(reinterpret_cast<const void*>(&attn_fast_kernel<PF, LENS, QSKIP>), AF_LDS);
     if (e != hipSuccess) return e;
   }
-  hipLaunchKernelGGL((attn_fast_kernel<PF, LENS>), dim3((a.Nq / AF_QB) * a.H * a.B), dim3(256), AF_LDS, s, a);
+  hipLaunchKernelGGL((attn_fast_kernel<PF, LENS, QSKIP>), dim3((a.Nq / AF_QB) * a.H * a.B), dim3(256), AF_LDS, s, a);
   return hipGetLastError();
 }
 
@@ -440,6 +454,7 @@ static hipError_t launch_attention_any(const AttnArgs& a_in, int nsplit, hipStre
   if (a.vt_lo && (a.vt_ld & 31)) return hipErrorInvalidValue;   // interleaved rows come in 32-column blocks
   if (a.klens && (a.kmask || a.drop_seed)) return hipErrorInvalidValue;            // key counts: the plain inference forward, or ...
   if (a.klens && a.lse && (nsplit != 3 || a.Nq != a.Nk)) return hipErrorInvalidValue;   // ... the training forward of a self-attention (QLENS)
+  if (a.qlens && (a.kmask || a.drop_seed || a.lse || (a.Nq & 255))) return hipErrorInvalidValue;   // ragged skipping: the plain forward on whole 256-row granules
   if (nsplit == 3) {
     if (!a.q_lo || !a.k_lo || !a.vt_lo) return hipErrorInvalidValue;
     return launch_attn_t<3, false>(a, s, train_hd);

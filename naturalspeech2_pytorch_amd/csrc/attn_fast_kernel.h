@@ -54,7 +54,9 @@ NS2_DEVINL void af_put4(unsigned char* rowp, int c, float v0, float v1, float v2
   }
 }
 
-template <int PF, bool LENS = false>
+// QSKIP: ragged skipping (attn_kernel's QSKIP) -- a 256-row query workgroup at or behind the utterance's computed extent returns before its
+// first load; a separate instantiation
+template <int PF, bool LENS = false, bool QSKIP = false>
 __global__ __launch_bounds__(256, 2) void attn_fast_kernel(const AttnArgs a) {
   using G = AtGeom<64>;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -63,10 +65,13 @@ __global__ __launch_bounds__(256, 2) void attn_fast_kernel(const AttnArgs a) {
   const int l31 = lane & 31, hi = lane >> 5;
   // the query tiles of one (batch, head) get consecutive remapped ids: one XCD's L2 serves their K / V^T re-reads (attn_kernel)
   const int nqt = a.Nq / AF_QB;
-  int bid = xcd_remap(blockIdx.x, gridDim.x);
+  int bid = QSKIP ? xcd_spread(blockIdx.x, gridDim.x, nqt) : xcd_remap(blockIdx.x, gridDim.x);
   const int qt = bid % nqt;
   bid /= nqt;
   const int h = bid % a.H, b = bid / a.H;
+  if constexpr (QSKIP) {
+    if (qt * AF_QB >= ragged_extent(a.qlens[b], a.Nq)) return;
+  }
   const int qrow0 = qt * AF_QB + wave * 64;            // block A: rows qrow0 + l31, block B: 32 further
   int nk = a.Nk;                                       // keys this utterance attends to
   if constexpr (LENS) nk = min(max(a.klens[b], 1), a.Nk);

@@ -10,7 +10,9 @@
 #include "../../include/ns2hip_pitch.h"
 #include "../../include/ns2hip_fold.h"
 #include "../../include/ns2hip_ragged.h"
+#include "../../include/ns2hip_ragged_skip.h"
 #include "ns2_host.h"
+#include "gemm_route.h"
 
 namespace ns2 {
 
@@ -201,6 +203,21 @@ extern "C" int ns2_linear(const ns2_linear_args* p, void* stream) {
   HIPRET(launch_gemm(g, p->precision, (hipStream_t)stream));
   return NS2_OK;
 }
+// include/ns2hip_ragged_skip.h: what the entry refuses on its own account comes first, under its own name, before any device call
+#define SKIP_SHAPE_CHK(name, row_lens, seq_len, M)                                                                                  \
+  ARGCHK((row_lens) != nullptr, name ": row_lens is null (the entry without lengths is the call that computes every row)");          \
+  ARGCHK((seq_len) > 0 && ((seq_len) & 255) == 0, name ": seq_len must be a positive multiple of 256 (whole skipping granules per utterance)"); \
+  ARGCHK((M) > 0 && (M) % (seq_len) == 0, name ": M must be whole utterances of seq_len rows")
+extern "C" int ns2_linear_lens(const ns2_linear_args* p, const int* row_lens, int seq_len, void* stream) {
+  ARGCHK(p != nullptr, "ns2_linear_lens: null argument block");
+  SKIP_SHAPE_CHK("ns2_linear_lens", row_lens, seq_len, p->M);
+  ARGCHK(p->seq_len == 0 || p->seq_len == seq_len, "ns2_linear_lens: args->seq_len differs from seq_len");
+  GemmArgs g;
+  if (int rc = linear_args_from(p, &g)) return rc;
+  g.row_lens = row_lens; g.lens_seq = seq_len;
+  HIPRET(launch_gemm(g, p->precision, (hipStream_t)stream));
+  return NS2_OK;
+}
 extern "C" int ns2_geglu_pack_bias(const float* bias, int f, float* packed, int packed_len, void* stream) {
   ARGCHK(bias && packed && f > 0, "ns2_geglu_pack_bias: bad arguments");
   const int rows_p = ((2 * ((f + 31) / 32 * 32)) + 255) / 256 * 256;
@@ -220,9 +237,9 @@ extern "C" int ns2_ff_fold(const float* w_out, const float* w_conv, const float*
   HIPRET(launch_ff_fold(w_out, w_conv, b_conv, b_out, dim, f, w_fold, b_fold, (hipStream_t)stream));
   return NS2_OK;
 }
-extern "C" int ns2_wavenet_block(const ns2_weight* w, const uint16_t* a_hi, const uint16_t* a_lo, int lda, int M, int seq_len,
-                                 int dilation, const float* conv_bias, const float* res_bias, const float* film, int film_ld,
-                                 uint16_t* out_hi, uint16_t* out_lo, int ldo, int precision, void* stream) {
+static int wavenet_block_impl(const ns2_weight* w, const uint16_t* a_hi, const uint16_t* a_lo, int lda, int M, int seq_len,
+                              int dilation, const float* conv_bias, const float* res_bias, const float* film, int film_ld,
+                              uint16_t* out_hi, uint16_t* out_lo, int ldo, int precision, const int* row_lens, void* stream) {
   // precision 5 (this entry point only) = precision 4 operands, the dilated conv as one half product, res_conv with the correction terms
   const int p1_half = precision == 5;
   if (p1_half) precision = 4;
@@ -233,8 +250,20 @@ extern "C" int ns2_wavenet_block(const ns2_weight* w, const uint16_t* a_hi, cons
   set_wavenet(g, w->w, dilation, seq_len, precision, p1_half);
   g.bias = conv_bias; g.bias2 = res_bias; g.film = film; g.film_ld = film_ld;
   set_out_planes(g, EPI_WAVENET, out_hi, out_lo, ldo);
+  if (row_lens) { g.row_lens = row_lens; g.lens_seq = seq_len; }
   HIPRET(launch_gemm(g, precision, (hipStream_t)stream));
   return NS2_OK;
+}
+extern "C" int ns2_wavenet_block(const ns2_weight* w, const uint16_t* a_hi, const uint16_t* a_lo, int lda, int M, int seq_len,
+                                 int dilation, const float* conv_bias, const float* res_bias, const float* film, int film_ld,
+                                 uint16_t* out_hi, uint16_t* out_lo, int ldo, int precision, void* stream) {
+  return wavenet_block_impl(w, a_hi, a_lo, lda, M, seq_len, dilation, conv_bias, res_bias, film, film_ld, out_hi, out_lo, ldo, precision, nullptr, stream);
+}
+extern "C" int ns2_wavenet_block_lens(const ns2_weight* w, const uint16_t* a_hi, const uint16_t* a_lo, int lda, int M, int seq_len,
+                                      int dilation, const float* conv_bias, const float* res_bias, const float* film, int film_ld,
+                                      uint16_t* out_hi, uint16_t* out_lo, int ldo, int precision, const int* row_lens, void* stream) {
+  SKIP_SHAPE_CHK("ns2_wavenet_block_lens", row_lens, seq_len, M);
+  return wavenet_block_impl(w, a_hi, a_lo, lda, M, seq_len, dilation, conv_bias, res_bias, film, film_ld, out_hi, out_lo, ldo, precision, row_lens, stream);
 }
 
 // The one translation of the C argument block into the kernels' (ns2_kernels.h AttnArgs, whose defaults are "nothing optional").
@@ -274,6 +303,20 @@ extern "C" int ns2_attention_fwd_lens(const ns2_attn_args* p, const int* key_len
   AttnArgs a;
   if (int rc = attn_args_from(p, &a)) return rc;
   a.klens = key_lens;
+  HIPRET(launch_attention(a, p->precision, (hipStream_t)stream));
+  return NS2_OK;
+}
+
+extern "C" int64_t ns2_debug_gemm_route_launches(int route) { return gemm_route_launches(route); }
+// include/ns2hip_ragged_skip.h
+extern "C" int ns2_attention_fwd_skip(const ns2_attn_args* p, const int* key_lens, const int* query_lens, void* stream) {
+  ARGCHK(p != nullptr, "ns2_attention_fwd_skip: null argument block");
+  ARGCHK(query_lens != nullptr, "ns2_attention_fwd_skip: query_lens is null (ns2_attention_fwd / _lens are the calls without them)");
+  ARGCHK(p->Nq > 0 && (p->Nq & 255) == 0, "ns2_attention_fwd_skip: Nq must be a positive multiple of 256 (whole skipping granules per utterance)");
+  ARGCHK(!p->key_mask && !p->lse && p->dropout_p == 0.f, "ns2_attention_fwd_skip: key_mask, lse and dropout exclude query lengths (the plain inference forward)");
+  AttnArgs a;
+  if (int rc = attn_args_from(p, &a)) return rc;
+  a.klens = key_lens; a.qlens = query_lens;
   HIPRET(launch_attention(a, p->precision, (hipStream_t)stream));
   return NS2_OK;
 }

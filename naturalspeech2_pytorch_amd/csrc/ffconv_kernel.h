@@ -70,6 +70,9 @@ struct Args {                    // 16 dwords
   // PF_F32 only (behind the 16 dwords the plane modes read): out is fp32 [M, ldo]; resid [M, ldr] fp32 or null
   const float* resid;
   int ldr;
+  // the SKIP instantiations only (ragged skipping, GemmArgs::row_lens / lens_seq): frames per utterance [M / lens_seq] on the device
+  int lens_seq;
+  const int* row_lens;
 };
 
 // ---- LDS-DMA as inline assembly: the compiler must not count these loads (its waitcnt pass drains every outstanding one with
@@ -287,13 +290,24 @@ struct Kern {
     }
   }
 
+  // SKIP (ragged skipping): a separate instantiation -- row tile tm on XCD tm % 8 (its column tiles still share one L2), a hidden row tile
+  // returns before the first DMA request, barrier and accumulator; an fp32 output without a residual gets zeros there
+  template <bool SKIP = false>
   static NS2_DEVINL void run(const Args& g) {
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int ncols = PF == PF_F32 ? g.N : max(g.N, g.out_ncols);
     const int ntn = (ncols + 255) >> 8;
-    const int bid = xcd_remap(blockIdx.x, gridDim.x);             // column tile fastest: the six blocks of a row tile share A' in one XCD's L2
+    const int bid = SKIP ? xcd_spread(blockIdx.x, gridDim.x, ntn) : xcd_remap(blockIdx.x, gridDim.x);   // column tile fastest: the six blocks of a row tile share A' in one XCD's L2
     const int tn = __builtin_amdgcn_readfirstlane(bid % ntn), tm = __builtin_amdgcn_readfirstlane(bid / ntn);
     const int m0 = tm * 256;
+    if constexpr (SKIP) {
+      if (row_tile_hidden(g.row_lens, g.lens_seq, m0, g.M)) {
+        if constexpr (PF == PF_F32) {
+          if (!g.resid) zero_tile_f32(reinterpret_cast<float*>(g.out), g.ldo, m0, 256, tn * 256, min(256, g.N - tn * 256), threadIdx.x, 512);
+        }
+        return;
+      }
+    }
     const bool first = __builtin_amdgcn_readfirstlane(m0 % g.seq_len) == 0;   // the 8 rows in front of the tile belong to the previous utterance
     const bool last_half = tn * 256 + 128 >= ncols;               // at most half of the column tile is valid
     if (!last_half) body<2, true>(g, tn, m0, first);
@@ -302,8 +316,8 @@ struct Kern {
   }
 };
 
-template <int PF>
-__global__ __launch_bounds__(512, 2) void ffconv3_kernel(const Args g) { Kern<PF>::run(g); }
+template <int PF, bool SKIP = false>
+__global__ __launch_bounds__(512, 2) void ffconv3_kernel(const Args g) { Kern<PF>::template run<SKIP>(g); }
 
 // ---- weights: the row-major dense-half pack [rows_p][3 * Cp] (model_exec.cpp pack_linear) -> tiled LDS images.  Image of (column tile
 // tn, step s = 3 it + tap): row n of the tile (output column tn * 256 + n) lives in half b = (n >> 5) & 1, quarter wn = n >> 6, row
@@ -359,29 +373,32 @@ inline bool ffconv3_eligible(const GemmArgs& g, int precision) {
   return g.out_fmt == FMT_F16 && !g.out_lo;
 }
 
-inline hipError_t launch_ffconv3(const GemmArgs& g, hipStream_t s) {
+template <bool SKIP>
+inline hipError_t launch_ffconv3_as(const GemmArgs& g, hipStream_t s) {
   ffc3::Args a;
   a.A = reinterpret_cast<const unsigned char*>(g.a_hi); a.Wt = reinterpret_cast<const unsigned char*>(g.w_t3);
   a.bias = g.bias; a.out = g.out_hi;
   a.M = g.M; a.N = g.N; a.lda = g.lda; a.ldo = g.ldo_s; a.seq_len = g.seq_len; a.tpt = g.lda / 64; a.kv = g.kt_per_tap * 32;
   a.out_ncols = g.out_ncols; a.resid = nullptr; a.ldr = 0;
+  a.row_lens = g.row_lens; a.lens_seq = g.lens_seq;
   if (g.epi == EPI_F32) {
     a.out = reinterpret_cast<bf16_t*>(g.out_f); a.ldo = g.ldo_f; a.out_ncols = g.N; a.resid = g.resid; a.ldr = g.ldr;
     static DynLdsAttr attr_f32;
-    const hipError_t e = attr_f32.ensure(reinterpret_cast<const void*>(&ffc3::ffconv3_kernel<ffc3::PF_F32>), ffc3::LDS_BYTES);
+    const hipError_t e = attr_f32.ensure(reinterpret_cast<const void*>(&ffc3::ffconv3_kernel<ffc3::PF_F32, SKIP>), ffc3::LDS_BYTES);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(ffc3::ffconv3_kernel<ffc3::PF_F32>, dim3(((g.N + 255) / 256) * (g.M / 256)), dim3(512), ffc3::LDS_BYTES, s, a);
+    hipLaunchKernelGGL((ffc3::ffconv3_kernel<ffc3::PF_F32, SKIP>), dim3(((g.N + 255) / 256) * (g.M / 256)), dim3(512), ffc3::LDS_BYTES, s, a);
     return hipGetLastError();
   }
   const int ntn = (std::max(g.N, g.out_ncols) + 255) / 256, grid = ntn * (g.M / 256);
   const bool h8 = g.out_fmt == FMT_H8;
   static DynLdsAttr attr_h8, attr_f16;
-  const void* fn = h8 ? reinterpret_cast<const void*>(&ffc3::ffconv3_kernel<PF_H8>) : reinterpret_cast<const void*>(&ffc3::ffconv3_kernel<PF_F16>);
+  const void* fn = h8 ? reinterpret_cast<const void*>(&ffc3::ffconv3_kernel<PF_H8, SKIP>) : reinterpret_cast<const void*>(&ffc3::ffconv3_kernel<PF_F16, SKIP>);
   hipError_t e = (h8 ? attr_h8 : attr_f16).ensure(fn, ffc3::LDS_BYTES);
   if (e != hipSuccess) return e;
-  if (h8) hipLaunchKernelGGL(ffc3::ffconv3_kernel<PF_H8>, dim3(grid), dim3(512), ffc3::LDS_BYTES, s, a);
-  else hipLaunchKernelGGL(ffc3::ffconv3_kernel<PF_F16>, dim3(grid), dim3(512), ffc3::LDS_BYTES, s, a);
+  if (h8) hipLaunchKernelGGL((ffc3::ffconv3_kernel<PF_H8, SKIP>), dim3(grid), dim3(512), ffc3::LDS_BYTES, s, a);
+  else hipLaunchKernelGGL((ffc3::ffconv3_kernel<PF_F16, SKIP>), dim3(grid), dim3(512), ffc3::LDS_BYTES, s, a);
   return hipGetLastError();
 }
+inline hipError_t launch_ffconv3(const GemmArgs& g, hipStream_t s) { return g.row_lens ? launch_ffconv3_as<true>(g, s) : launch_ffconv3_as<false>(g, s); }
 
 }  // namespace ns2

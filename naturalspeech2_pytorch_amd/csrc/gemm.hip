@@ -40,7 +40,10 @@ struct Stage {                                // registers holding one prefetche
 NS2_DEVINL uint4 ld16(const bf16_t* p) { return *reinterpret_cast<const uint4*>(p); }
 NS2_DEVINL uint4 zero16() { return make_uint4(0u, 0u, 0u, 0u); }
 
-template <int NSPLIT, int EPI, bool F16>
+// SKIP (ragged skipping, GemmArgs::row_lens): a separate instantiation -- row tile tm goes to XCD tm % 8 with its column tiles kept
+// together (xcd_spread: a batch sorted by length no longer leaves one XCD the long utterances), and a workgroup whose row tile is hidden
+// returns before anything is loaded, staged or accumulated.  Every instantiation without it compiles to what it was.
+template <int NSPLIT, int EPI, bool F16, bool SKIP = false>
 __global__ __launch_bounds__(256, 2) void gemm_kernel(const GemmArgs g) {
   static_assert(NSPLIT != 2 || F16, "the mixed mode multiplies IEEE-half operands");
   constexpr int NP = (NSPLIT == 1) ? 1 : 2;   // 64-B halves of the interleaved line staged per operand
@@ -54,11 +57,19 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const GemmArgs g) {
 
   const int ntn = (g.N + BN - 1) / BN;
   const int ntm = (g.M + BM - 1) / BM;
-  int bid = xcd_remap(blockIdx.x, gridDim.x);
+  int bid = SKIP ? xcd_spread(blockIdx.x, gridDim.x, ntn) : xcd_remap(blockIdx.x, gridDim.x);
   const int tn = bid % ntn;
   bid /= ntn;
   const int tm = bid % ntm;
   const int z = bid / ntm;
+  if constexpr (SKIP) {
+    if (row_tile_hidden(g.row_lens, g.lens_seq, tm * BM, g.M)) {
+      if constexpr (EPI == EPI_F32) {
+        if (!g.resid) zero_tile_f32(g.out_f + z * g.out_f_zs, g.ldo_f, tm * BM, min(BM, g.M - tm * BM), tn * BN, min(BN, g.N - tn * BN), threadIdx.x, 256);
+      }
+      return;
+    }
+  }
 
   // interleaved [hi32|lo32] rows when the operand has a lo plane (ns2_common.h); a_zs = logical column offset per z
   const bool ail = g.a_lo != nullptr, wil = g.w_lo != nullptr;
@@ -252,17 +263,18 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const GemmArgs g) {
   wave_tile_epilogue<EPI, 2, G1Formats<NSPLIT, F16>, WBUF>(acc, g, z, row_base, col_base, tn * 64 + wn * 32, lane, smem + wave * WBUF);
 }
 
-template <int NSPLIT, int EPI, bool F16>
+template <int NSPLIT, int EPI, bool F16, bool SKIP = false>
 static hipError_t launch_one(const GemmArgs& g, hipStream_t s) {
+  if constexpr (!SKIP) { if (g.row_lens) return launch_one<NSPLIT, EPI, F16, true>(g, s); }
   const int ntn = (g.N + BN - 1) / BN, ntm = (g.M + BM - 1) / BM;
   const int nz = g.nz > 0 ? g.nz : 1;
   const size_t lds = 2 * 2 * (NSPLIT == 1 ? 1 : 2) * PLANE;
   static DynLdsAttr attr;
   {
-    hipError_t e = attr.ensure(reinterpret_cast<const void*>(&gemm_kernel<NSPLIT, EPI, F16>), (int)lds);
+    hipError_t e = attr.ensure(reinterpret_cast<const void*>(&gemm_kernel<NSPLIT, EPI, F16, SKIP>), (int)lds);
     if (e != hipSuccess) return e;
   }
-  hipLaunchKernelGGL((gemm_kernel<NSPLIT, EPI, F16>), dim3(ntn * ntm * nz), dim3(256), lds, s, g);
+  hipLaunchKernelGGL((gemm_kernel<NSPLIT, EPI, F16, SKIP>), dim3(ntn * ntm * nz), dim3(256), lds, s, g);
   return hipGetLastError();
 }
 
@@ -409,6 +421,7 @@ hipError_t launch_gemm_splitk(const GemmArgs& g, int precision, int S, int c, hi
   const long slot = (long)g.M * ldp;
   if (!g.sk_ws || S < 2 || c < 1 || S * slot > g.sk_ws_floats) return hipErrorInvalidValue;
   GemmArgs p = g;
+  p.row_lens = nullptr; p.lens_seq = 0;                          // (the split-K route takes no lengths)
   p.epi = EPI_F32; p.bias = nullptr; p.bias2 = nullptr; p.resid = nullptr; p.act = 0; p.film = nullptr;
   p.out_f = g.sk_ws; p.ldo_f = ldp; p.out_f_zs = slot;
   p.out_hi = nullptr; p.out_lo = nullptr; p.vt_hi = nullptr; p.vt_lo = nullptr; p.nrm_hi = nullptr; p.nrm_lo = nullptr;

@@ -131,9 +131,13 @@ NS2_DEVINL void tr_wait(f32x16& c0, f32x16& c1) {                 // every trans
 // tools/probe/tr_probe.hip) -- two reads per 16-deep MFMA fragment, four per 32 fp8 bytes; A and B use the same token -> k
 // assignment, so the permutation inside a k block cancels.  The conv taps of a weight gradient are column blocks of N (tap =
 // n / tr_kp) whose source rows are shifted by (tr_taps - 1 - tap) * dil TOKENS inside the utterance: no shifted copies either.
-template <int NSPLIT, int EPI, bool F16, int P1 = 0, bool TR = false>
+//
+// SKIP (ragged skipping, GemmArgs::row_lens): as in gemm_kernel -- a separate instantiation whose row tile tm goes to XCD tm % 8 and whose
+// workgroups return on a hidden row tile before the first DMA request, barrier or accumulator; the others compile to what they were.
+template <int NSPLIT, int EPI, bool F16, int P1 = 0, bool TR = false, bool SKIP = false>
 __global__ __launch_bounds__(512, 2) void gemm2_kernel(const GemmArgs g) {
   const bf16_t* zero_page = g2_zero_page;
+  static_assert(!(SKIP && TR), "weight gradients take no lengths");
   static_assert(!TR || (EPI == EPI_F32 && P1 == 0 && NSPLIT != 1), "transposed operands: weight gradients (fp32 slots) on interleaved lines");
   static_assert(NSPLIT != 2 || F16, "the mixed mode multiplies IEEE-half operands");
   static_assert(P1 == 0 || (EPI == EPI_WAVENET && P1 == 1 && NSPLIT == 2), "phase-1 override: half product under the mixed mode");
@@ -164,11 +168,19 @@ __global__ __launch_bounds__(512, 2) void gemm2_kernel(const GemmArgs g) {
 
   const int ntn = (g.N + G2_BN - 1) / G2_BN;
   const int ntm = (g.M + G2_BM - 1) / G2_BM;
-  int bid = xcd_remap(blockIdx.x, gridDim.x);
+  int bid = SKIP ? xcd_spread(blockIdx.x, gridDim.x, ntn) : xcd_remap(blockIdx.x, gridDim.x);
   const int tn = bid % ntn;
   bid /= ntn;
   const int tm = bid % ntm;
   const int z = bid / ntm;
+  if constexpr (SKIP) {
+    if (row_tile_hidden(g.row_lens, g.lens_seq, tm * G2_BM, g.M)) {
+      if constexpr (EPI == EPI_F32) {
+        if (!g.resid) zero_tile_f32(g.out_f + z * g.out_f_zs, g.ldo_f, tm * G2_BM, min(G2_BM, g.M - tm * G2_BM), tn * G2_BN, min(G2_BN, g.N - tn * G2_BN), tid, 512);
+      }
+      return;
+    }
+  }
   const int dil = g.dil_z ? (g.dil << z) : g.dil;
 
   // operand layouts (ns2_common.h): exact mode requires interleaved operands (checked by launch_gemm); the fast kernel
@@ -944,15 +956,16 @@ extern "C" int ns2_debug_read_blocks(unsigned long long* out, int nblk) {
 }
 #endif
 
-template <int NSPLIT, int EPI, bool F16, int P1 = 0, bool TR = false>
+template <int NSPLIT, int EPI, bool F16, int P1 = 0, bool TR = false, bool SKIP = false>
 static hipError_t launch2_one(const GemmArgs& g, hipStream_t s) {
+  if constexpr (!SKIP && !TR) { if (g.row_lens) return launch2_one<NSPLIT, EPI, F16, P1, TR, true>(g, s); }
   const int ntn = (g.N + G2_BN - 1) / G2_BN, ntm = (g.M + G2_BM - 1) / G2_BM;
   const int nz = g.nz > 0 ? g.nz : 1;
   const size_t lds = 8 * EPI_LDS_WAVE_BYTES;          // 144 KiB: 2 x 64 KiB K stages, reused as 8 x 18 KiB epilogue regions
   static DynLdsAttr attr;
-  hipError_t e = attr.ensure(reinterpret_cast<const void*>(&gemm2_kernel<NSPLIT, EPI, F16, P1, TR>), (int)lds);
+  hipError_t e = attr.ensure(reinterpret_cast<const void*>(&gemm2_kernel<NSPLIT, EPI, F16, P1, TR, SKIP>), (int)lds);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((gemm2_kernel<NSPLIT, EPI, F16, P1, TR>), dim3(ntn * ntm * nz), dim3(512), lds, s, g);
+  hipLaunchKernelGGL((gemm2_kernel<NSPLIT, EPI, F16, P1, TR, SKIP>), dim3(ntn * ntm * nz), dim3(512), lds, s, g);
   return hipGetLastError();
 }
 
@@ -1099,13 +1112,19 @@ static hipError_t resolve_gemm_args(GemmArgs& g, int precision) {
   return hipSuccess;
 }
 
+// the routing tests read these around a call: kernels of different routes may give the same bits, the output cannot tell which one ran
+static std::atomic<long long> g_route_launches[6];
+long long gemm_route_launches(int route) { return route >= 0 && route < 6 ? g_route_launches[route].load(std::memory_order_relaxed) : -1; }
+
 hipError_t launch_gemm(const GemmArgs& g_in, int precision, hipStream_t s) {
   GemmArgs g = g_in;
   const hipError_t e = resolve_gemm_args(g, precision);
   if (e != hipSuccess) return e;
+  if (g.row_lens && !gemm_lens_ok(g)) return hipErrorInvalidValue;      // ragged skipping: whole 256-row granules per utterance
   const GemmPlan p = plan_gemm(g, precision);
+  g_route_launches[static_cast<int>(p.route)].fetch_add(1, std::memory_order_relaxed);
   switch (p.route) {
-    case GemmRoute::SplitK: return launch_gemm_splitk(g, precision, p.S, p.c, s);
+    case GemmRoute::SplitK: return launch_gemm_splitk(g, precision, p.S, p.c, s);      // (takes no lengths: every row is computed)
     case GemmRoute::Tile128: return launch_gemm1(g, precision, s);
     case GemmRoute::FfConv3: return launch_ffconv3(g, s);
     case GemmRoute::Linear3: return launch_gemm3(g, s);

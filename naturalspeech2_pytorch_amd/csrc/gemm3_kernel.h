@@ -192,15 +192,25 @@ NS2_DEVINL void kloop(Ctx& c, const int T, const int wave) {
   if (wave < 4) bar();                                          // ... and the first waits for its last MFMA phase
 }
 
-template <int EPI>
+// SKIP (ragged skipping, GemmArgs::row_lens): as in gemm2_kernel -- a separate instantiation; row tile tm on XCD tm % 8, a hidden row tile
+// returns before the first DMA request, barrier and accumulator
+template <int EPI, bool SKIP = false>
 struct Kern {
   static NS2_DEVINL void run(const GemmArgs& g) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int ntn = (g.N + G2_BN - 1) / G2_BN;
-    const int bid = xcd_remap(blockIdx.x, gridDim.x);
+    const int bid = SKIP ? xcd_spread(blockIdx.x, gridDim.x, ntn) : xcd_remap(blockIdx.x, gridDim.x);
     const int tn = __builtin_amdgcn_readfirstlane(bid % ntn), tm = __builtin_amdgcn_readfirstlane(bid / ntn);
+    if constexpr (SKIP) {
+      if (row_tile_hidden(g.row_lens, g.lens_seq, tm * G2_BM, g.M)) {
+        if constexpr (EPI == EPI_F32) {
+          if (!g.resid) zero_tile_f32(g.out_f, g.ldo_f, tm * G2_BM, G2_BM, tn * G2_BN, min(G2_BN, g.N - tn * G2_BN), tid, 512);
+        }
+        return;
+      }
+    }
     const int T = g.nkt;
     const long lda_b = 4L * g.lda;                               // FMT_H8 lines: 4 bytes per logical column
     Ctx c;
@@ -217,8 +227,8 @@ struct Kern {
   }
 };
 
-template <int EPI>
-__global__ __launch_bounds__(512, 2) void gemm3_kernel(const GemmArgs g) { Kern<EPI>::run(g); }
+template <int EPI, bool SKIP = false>
+__global__ __launch_bounds__(512, 2) void gemm3_kernel(const GemmArgs g) { Kern<EPI, SKIP>::run(g); }
 
 // ---- weights: the row-major FMT_H8 pack [rows_p][ldk / 32 lines of 128 B] -> tiled LDS images.  Image of (column tile tn, K tile t): row n
 // of the tile lives in half b = (n >> 5) & 1, quarter wn = n >> 6, row r = n & 31 at byte b * 16384 + wn * 4096 + r * 128, chunk q of its
@@ -257,26 +267,28 @@ inline bool gemm3_eligible(const GemmArgs& g, int precision) {
   return g.a_lo == g.a_hi + 32 && (reinterpret_cast<uintptr_t>(g.a_hi) & 15) == 0;
 }
 
-inline hipError_t launch_gemm3(const GemmArgs& g, hipStream_t s) {
+template <bool SKIP>
+inline hipError_t launch_gemm3_as(const GemmArgs& g, hipStream_t s) {
   const int ntn = (g.N + G2_BN - 1) / G2_BN, grid = ntn * (g.M / G2_BM);
   static DynLdsAttr attr[4];
   const void* fn; int slot;
   switch (g.epi) {
-    case EPI_F32: fn = reinterpret_cast<const void*>(&mx3::gemm3_kernel<EPI_F32>); slot = 0; break;
-    case EPI_SPLIT: fn = reinterpret_cast<const void*>(&mx3::gemm3_kernel<EPI_SPLIT>); slot = 1; break;
-    case EPI_QKV: fn = reinterpret_cast<const void*>(&mx3::gemm3_kernel<EPI_QKV>); slot = 2; break;
-    case EPI_GEGLU: fn = reinterpret_cast<const void*>(&mx3::gemm3_kernel<EPI_GEGLU>); slot = 3; break;
+    case EPI_F32: fn = reinterpret_cast<const void*>(&mx3::gemm3_kernel<EPI_F32, SKIP>); slot = 0; break;
+    case EPI_SPLIT: fn = reinterpret_cast<const void*>(&mx3::gemm3_kernel<EPI_SPLIT, SKIP>); slot = 1; break;
+    case EPI_QKV: fn = reinterpret_cast<const void*>(&mx3::gemm3_kernel<EPI_QKV, SKIP>); slot = 2; break;
+    case EPI_GEGLU: fn = reinterpret_cast<const void*>(&mx3::gemm3_kernel<EPI_GEGLU, SKIP>); slot = 3; break;
     default: return hipErrorInvalidValue;
   }
   hipError_t e = attr[slot].ensure(fn, mx3::LDS_BYTES);
   if (e != hipSuccess) return e;
   switch (g.epi) {
-    case EPI_F32: hipLaunchKernelGGL(mx3::gemm3_kernel<EPI_F32>, dim3(grid), dim3(512), mx3::LDS_BYTES, s, g); break;
-    case EPI_SPLIT: hipLaunchKernelGGL(mx3::gemm3_kernel<EPI_SPLIT>, dim3(grid), dim3(512), mx3::LDS_BYTES, s, g); break;
-    case EPI_QKV: hipLaunchKernelGGL(mx3::gemm3_kernel<EPI_QKV>, dim3(grid), dim3(512), mx3::LDS_BYTES, s, g); break;
-    default: hipLaunchKernelGGL(mx3::gemm3_kernel<EPI_GEGLU>, dim3(grid), dim3(512), mx3::LDS_BYTES, s, g); break;
+    case EPI_F32: hipLaunchKernelGGL((mx3::gemm3_kernel<EPI_F32, SKIP>), dim3(grid), dim3(512), mx3::LDS_BYTES, s, g); break;
+    case EPI_SPLIT: hipLaunchKernelGGL((mx3::gemm3_kernel<EPI_SPLIT, SKIP>), dim3(grid), dim3(512), mx3::LDS_BYTES, s, g); break;
+    case EPI_QKV: hipLaunchKernelGGL((mx3::gemm3_kernel<EPI_QKV, SKIP>), dim3(grid), dim3(512), mx3::LDS_BYTES, s, g); break;
+    default: hipLaunchKernelGGL((mx3::gemm3_kernel<EPI_GEGLU, SKIP>), dim3(grid), dim3(512), mx3::LDS_BYTES, s, g); break;
   }
   return hipGetLastError();
 }
+inline hipError_t launch_gemm3(const GemmArgs& g, hipStream_t s) { return g.row_lens ? launch_gemm3_as<true>(g, s) : launch_gemm3_as<false>(g, s); }
 
 }  // namespace ns2

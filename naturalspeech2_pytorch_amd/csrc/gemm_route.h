@@ -16,6 +16,8 @@ struct GemmPlan {
 
 // The kernel launch_gemm runs g on, under the test hook's current mode (force_gemm_kernel).  Pure host arithmetic: no HIP call.
 GemmPlan plan_gemm(const GemmArgs& g, int precision);
+// test hook (ns2_debug_gemm_route_launches): products launch_gemm has sent down `route` (the enum's order, 0 = SplitK ... 5 = Wavenet3) so far
+long long gemm_route_launches(int route);
 
 // gemm.hip.  g: validated by launch_gemm, formats resolved.
 hipError_t launch_gemm1(const GemmArgs& g, int precision, hipStream_t s);                      // the 128 x 128 register-staged kernel

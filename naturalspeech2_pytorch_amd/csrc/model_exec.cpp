@@ -25,6 +25,7 @@
 #include "../../include/ns2hip_fold.h"
 #include "../../include/ns2hip_ragged.h"
 #include "../../include/ns2hip_ragged_front.h"
+#include "../../include/ns2hip_ragged_skip.h"
 #include "ns2_host.h"
 #include "gemm_route.h"
 
@@ -106,6 +107,8 @@ struct ns2_model {
   // the chain rule's last verdict and what it was asked for: the verdict depends on the shape, the alignment of the caller's buffers and
   // the GEMM test hook alone, so a run of steps asks once
   struct { int B = 0, N = 0, n_cond = 0; unsigned hook_epoch = 0; uintptr_t align = 0; int chains = 0; } rule;
+  // the skip rule's last verdict (include/ns2hip_ragged_skip.h), likewise: it depends on the shape and the GEMM test hook alone; -1 = not asked
+  struct { int B = 0, N = 0, n_cond = 0; unsigned hook_epoch = 0; uintptr_t align = 0; int skips = -1; } skip_rule;
 };
 
 namespace ns2 {
@@ -1016,6 +1019,7 @@ struct StepArgs {                // what forward_impl resolved for the whole bat
   const float* call; int cld;    // [gamma | beta] blocks of all FiLM / adaptive-norm projections; row b at call + b * cld
   int n_cond, N;
   const int* lens = nullptr;     // ragged batch (include/ns2hip_ragged.h): frames per utterance, int32 [B] on the device; null = N each
+  bool skip = false;             // ... and every product and both attentions skip the row tiles hidden behind them (include/ns2hip_ragged_skip.h)
 };
 
 int enqueue(ns2_model* m, const Launch& l, bool counted, hipStream_t s);
@@ -1055,12 +1059,17 @@ void describe_rows(const ns2_model* m, const Work& w0, const CondState* cs, cons
   const Planes ffc_ff = ff_half_plan(m->cfg.precision) ? view_as(ffc, false, FMT_F16) : ffc;
   const bool taps = !m->taps.empty();
 
+  // A skipping step (st.skip; DESIGN section 4, "Skipping hidden row tiles"): every product gets this part's lengths as row lengths and
+  // every attention gets them as query lengths.  The launches, their order and their routes are those of the step without skipping.
+  const int* skip_lens = st.skip ? st.lens + b0 : nullptr;
   auto gemm = [&](const GemmArgs& g, int gprec, int cat, int mark = Launch::NONE) {
     Launch l; l.kind = Launch::GEMM; l.g = g; l.prec = gprec; l.cat = cat; l.mark = mark;
+    if (skip_lens) { l.g.row_lens = skip_lens; l.g.lens_seq = N; }
     prog->push_back(l);
   };
   auto attention = [&](const AttnArgs& at, int aprec) {
     Launch l; l.kind = Launch::ATTN; l.a = at; l.prec = aprec; l.cat = PC_ATTENTION;
+    l.a.qlens = skip_lens;
     prog->push_back(l);
   };
   auto tap_f = [&](const char* name, const float* src) {
@@ -1231,6 +1240,17 @@ int chains_by_rule(const ns2_model* m, const Work& w, const CondState* cs, const
   return same_plan(*whole, *c0) && same_plan(*whole, *c1) ? 2 : 1;
 }
 
+// ---- the skip rule (include/ns2hip_ragged_skip.h).  A step skips its hidden row tiles only if every utterance is whole 256-row granules
+// and no product of the whole batch's described step is planned on the split-K route (its slices and its finishing launch take no
+// lengths).  Pure host arithmetic over the described launches; two chains of a skipping step passed same_plan, which admits no split either.
+bool skip_by_rule(const std::vector<Launch>& whole, int N) {
+  if (N <= 0 || (N & 255)) return false;
+  for (const Launch& l : whole)
+    if (l.kind == Launch::GEMM && plan_gemm(l.g, l.prec).route == GemmRoute::SplitK) return false;
+  return true;
+}
+std::atomic<int> g_skip_last{0};
+
 // Test hook (ns2_debug_force_chains / NS2_CHAINS) in the manner of gemm2.hip's gemm_hook(): process-wide, atomic.  -1: read NS2_CHAINS
 // once.  0: the library's default (NS2_CHAINS_DEFAULT below), 1: one chain, 2: two chains wherever the rule allows.
 std::atomic<int> g_forced_chains{-1};
@@ -1259,11 +1279,12 @@ extern "C" int ns2_debug_force_chains(int chains) {
   return NS2_OK;
 }
 extern "C" int ns2_debug_chains_last(void) { return g_chains_last.load(std::memory_order_relaxed); }
+extern "C" int ns2_debug_skip_last(void) { return g_skip_last.load(std::memory_order_relaxed); }
 
 // cond_row != null: the step's time conditioning comes from a row of the table ns2_model_time_table built ahead of the run
 // (the sampler's times are known up front and shared by the batch, NS2:1303-1308): no projection is launched in the step
 static int forward_impl(ns2_model* m, const float* x, const float* times, const float* cond_row, const void* cond_state, int n_cond, float* out,
-                        int B, int N, void* workspace, int64_t workspace_bytes, void* stream, const int* lens = nullptr) {
+                        int B, int N, void* workspace, int64_t workspace_bytes, void* stream, const int* lens = nullptr, bool want_skip = false) {
   if (!m || !m->finalized) { set_error("model not finalized"); return NS2_ERR_STATE; }
   if (!x || (!times && !cond_row) || !out || B <= 0 || N <= 0) { set_error("bad forward arguments"); return NS2_ERR_ARG; }
   const bool cond = m->cfg.condition_on_prompt;
@@ -1295,6 +1316,27 @@ static int forward_impl(ns2_model* m, const float* x, const float* times, const 
     HIPRET(launch_skinny_linear(w.t, m->Tc, m->wt_cond, m->b_cond, w.condall, Jtot, B, m->Tc, Jtot, 0, w.skinny_ws, w.skinny_ws_bytes, s));
   }
 
+  // ---- ragged skipping: asked for (ns2_model_forward_lens_skip) and allowed by the skip rule, whose verdict is asked once per (shape, GEMM hook)
+  const CondState* csp = cond ? &cs : nullptr;
+  if (want_skip && lens) {
+    // (what plan_gemm reads besides the shape: the hook, the alignment of the buffers -- the dedicated kernels' eligibility -- and whether
+    // split-K scratch is lent; the key of the chain rule's cache, for the same reason)
+    const unsigned epoch = g_gemm_hook_epoch.load(std::memory_order_relaxed);
+    const uintptr_t align = ((reinterpret_cast<uintptr_t>(workspace) | reinterpret_cast<uintptr_t>(cond_state) | reinterpret_cast<uintptr_t>(x) |
+                              reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(st.call)) & 255) | (w.sk_ws ? 256 : 0);
+    auto& r = m->skip_rule;
+    if (r.skips < 0 || r.B != B || r.N != N || r.n_cond != n_cond || r.hook_epoch != epoch || r.align != align) {
+      std::vector<Launch>& whole = m->prog[0]->v;
+      whole.clear();
+      Sink list{&whole, nullptr, nullptr, NS2_OK};
+      describe_rows(m, w, csp, st, 0, B, &list);
+      r.skips = skip_by_rule(whole, N) ? 1 : 0;
+      r.B = B; r.N = N; r.n_cond = n_cond; r.hook_epoch = epoch; r.align = align;
+    }
+    st.skip = r.skips == 1;
+  }
+  g_skip_last.store(st.skip ? 1 : 0, std::memory_order_relaxed);
+
   // ---- the row-dependent part: one chain on the caller's stream, or two on two streams
   bool may_chain = chains_wanted() == 2 && B >= 2 && m->taps.empty();
   if (may_chain) {
@@ -1304,7 +1346,6 @@ static int forward_impl(ns2_model* m, const float* x, const float* times, const 
     may_chain = cap == hipStreamCaptureStatusNone;
   }
   // the rule's verdict: asked once per (shape, buffer alignment, GEMM hook), from the described launches of the whole batch and of both chains
-  const CondState* csp = cond ? &cs : nullptr;
   int chains = 1;
   bool described = false;                 // prog[1] / prog[2] hold this step's chains
   if (may_chain) {
@@ -1378,8 +1419,8 @@ static void destroy_chain_state(ns2_model* m) {
 // The chain rule for a configuration, without a device: the packed weights of a step as ns2_model_finalize shapes them (sizes, formats,
 // which tiled images exist) behind placeholder addresses that are never read, the workspace carved at a placeholder base, and the same
 // describe_rows / chains_by_rule a forward runs.  *chains = what a forward of B x N frames runs where two chains are wanted.
-extern "C" int ns2_debug_chain_rule(const ns2_model_config* cfg, int B, int N, int* chains) {
-  if (!cfg || !chains || B <= 0 || N <= 0) { set_error("ns2_debug_chain_rule: bad arguments"); return NS2_ERR_ARG; }
+// (ns2_debug_skip_rule asks the skip rule of the same described step: *skips)
+static int debug_rules(const ns2_model_config* cfg, int B, int N, int* chains, int* skips) {
   ns2_model mm;
   ns2_model* m = &mm;
   NSCHK(derive_dims(m, cfg));
@@ -1430,8 +1471,17 @@ extern "C" int ns2_debug_chain_rule(const ns2_model_config* cfg, int B, int N, i
   std::vector<Launch> whole, c0, c1;
   Sink list{&whole, nullptr, nullptr, NS2_OK};
   describe_rows(m, w, cond ? &cs : nullptr, st, 0, B, &list);
-  *chains = chains_by_rule(m, w, cond ? &cs : nullptr, st, B, &whole, &c0, &c1);
+  if (chains) *chains = chains_by_rule(m, w, cond ? &cs : nullptr, st, B, &whole, &c0, &c1);
+  if (skips) *skips = skip_by_rule(whole, N) ? 1 : 0;
   return NS2_OK;
+}
+extern "C" int ns2_debug_chain_rule(const ns2_model_config* cfg, int B, int N, int* chains) {
+  if (!cfg || !chains || B <= 0 || N <= 0) { set_error("ns2_debug_chain_rule: bad arguments"); return NS2_ERR_ARG; }
+  return debug_rules(cfg, B, N, chains, nullptr);
+}
+extern "C" int ns2_debug_skip_rule(const ns2_model_config* cfg, int B, int N, int* skips) {
+  if (!cfg || !skips || B <= 0 || N <= 0) { set_error("ns2_debug_skip_rule: bad arguments"); return NS2_ERR_ARG; }
+  return debug_rules(cfg, B, N, nullptr, skips);
 }
 
 extern "C" int ns2_model_forward(ns2_model* m, const float* x, const float* times, const void* cond_state, int n_cond, float* out,
@@ -1451,6 +1501,15 @@ extern "C" int ns2_model_forward_lens(ns2_model* m, const float* x, const float*
                                       void* stream) {
   if ((times != nullptr) == (cond_row != nullptr)) { set_error("ns2_model_forward_lens: exactly one of times / cond_row"); return NS2_ERR_ARG; }
   return forward_impl(m, x, times, cond_row, cond_state, n_cond, out, B, N, workspace, workspace_bytes, stream, frame_lens);
+}
+
+// include/ns2hip_ragged_skip.h
+extern "C" int ns2_model_forward_lens_skip(ns2_model* m, const float* x, const float* times, const float* cond_row, const int* frame_lens,
+                                           const void* cond_state, int n_cond, float* out, int B, int N, void* workspace,
+                                           int64_t workspace_bytes, void* stream) {
+  if (!frame_lens) { set_error("ns2_model_forward_lens_skip: frame_lens is null (ns2_model_forward_lens is the call that allows it)"); return NS2_ERR_ARG; }
+  if ((times != nullptr) == (cond_row != nullptr)) { set_error("ns2_model_forward_lens_skip: exactly one of times / cond_row"); return NS2_ERR_ARG; }
+  return forward_impl(m, x, times, cond_row, cond_state, n_cond, out, B, N, workspace, workspace_bytes, stream, frame_lens, true);
 }
 
 // ------------------------------------------------------------------------------------------------ hoisted time conditioning

@@ -264,3 +264,25 @@ NS2_DEVINL int xcd_spread(int bid, int nwg, int ntile) {
   const int xcd = bid % nx, j = bid / nx;             // the j-th workgroup this XCD runs
   return ((j / ntile) * nx + xcd) * ntile + j % ntile;
 }
+
+// Ragged skipping (include/ns2hip_ragged_skip.h).  The computed extent of an utterance of seq_len frames (seq_len % 256 == 0) with
+// lens[b] real ones is H = min(seq_len, 256 ceil(clamp(lens[b], 1, seq_len) / 256)): ONE granule of 256 rows for every kernel, whatever
+// its own tile height, so that producers and consumers agree on which rows exist.  A tile of rows [row0, row0 + h) with h dividing 256
+// lies inside one utterance and inside one granule: it is hidden iff its first row is.  Scalars only (row0 is workgroup-uniform, the
+// length comes through the scalar cache): the same verdict in every wave.  row0 >= M (no such tile where seq_len divides M): not hidden,
+// the kernel's own bounds handle it -- and lens is never read past the batch.
+NS2_DEVINL int ragged_extent(int len, int seq_len) { return min(seq_len, (min(max(len, 1), seq_len) + 255) & ~255); }
+NS2_DEVINL bool row_tile_hidden(const int* lens, int seq_len, int row0, int M) {
+  if (row0 >= M) return false;
+  const int b = row0 / seq_len;
+  return row0 - b * seq_len >= ragged_extent(lens[b], seq_len);
+}
+// a hidden tile of an fp32 output that nothing accumulates into (no residual): exact zeros, so that the row-wise readers that do not skip
+// (rmsnorm_kernel, the caller of to_pred's output) find defined values.  Rows [row0, row0 + rows) x columns [col0, col0 + cols)
+NS2_DEVINL void zero_tile_f32(float* out, long ldo, int row0, int rows, int col0, int cols, int tid, int nthreads) {
+  if (rows <= 0 || cols <= 0) return;
+  for (int i = tid; i < rows * cols; i += nthreads) {
+    const int r = i / cols;
+    out[(long)(row0 + r) * ldo + col0 + (i - r * cols)] = 0.f;
+  }
+}

@@ -99,7 +99,15 @@ struct GemmArgs {
   // launch_gemm_tr only (weight gradients from token-major planes, gemm2.hip TR): tokens the operands have, channels per tap block of
   // the N dimension (a multiple of 32), taps (0 / 1: no shift; tap t of a causal conv reads token m - (tr_taps - 1 - t) * dil)
   int tr_tokens = 0, tr_kp = 0, tr_taps = 0;
+  // ragged skipping (include/ns2hip_ragged_skip.h; last in the block: no other field moves): per-utterance frame counts in DEVICE
+  // memory, int32 [M / lens_seq], read by the kernels alone, and the frames per utterance (a multiple of 256 that divides M).  Selects
+  // the SKIP instantiations: a workgroup whose whole row tile lies at or behind its utterance's computed extent
+  // min(lens_seq, 256 ceil(clamp(len, 1, lens_seq) / 256)) returns before its first load -- an fp32 output without a residual gets
+  // zeros there, every other output keeps what it held.  null = every row is computed.  The split-K route takes no lengths.
+  const int* row_lens = nullptr; int lens_seq = 0;
 };
+// may g carry row_lens?  (what launch_gemm checks, and the stand-alone entries before any device call)
+inline bool gemm_lens_ok(const GemmArgs& g) { return g.lens_seq > 0 && (g.lens_seq & 255) == 0 && g.M > 0 && (g.M % g.lens_seq) == 0; }
 
 // precision: 3 = bf16 x3 ("exact"), 1 = bf16 ("fast"), 2 = one IEEE-half product ("half"), 4 = half product + both
 // first-order correction terms on the fp8 MFMA ("mixed", FMT_H8 operands).  Dispatches gemm.hip / gemm2.hip by shape.
@@ -145,6 +153,11 @@ struct AttnArgs {
   // include/ns2hip_ragged_train.h; precision 3, Nq == Nk): the counts are the utterances' lengths on the query side too -- o rows from the
   // length on are written as zero bits, their lse as +inf.
   const int* klens = nullptr;
+  // ragged skipping (include/ns2hip_ragged_skip.h; last in the block): per-utterance frame counts on the QUERY side, int32 [B] in DEVICE
+  // memory; needs Nq % 256 == 0.  A query workgroup whose rows all lie at or behind min(Nq, 256 ceil(clamp(qlens[b], 1, Nq) / 256)) returns
+  // before its first load and leaves its o rows as they were; every other row is computed as without it.  With or without klens (the
+  // cross attention to the resampled prompt has query lengths alone).  Excludes lse, kmask and dropout.  null = every query row is computed.
+  const int* qlens = nullptr;
 };                                                       // precision: 3 bf16x3, 1 bf16, 2 and 4: one IEEE-half product
 hipError_t launch_attention(const AttnArgs& a, int precision, hipStream_t s);
 hipError_t launch_attention_train_hd(const AttnArgs& a, hipStream_t s);   // the training forward (lse, precision 3) at a.D = 32 / 64 / 128

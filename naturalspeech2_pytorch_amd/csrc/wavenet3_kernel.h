@@ -146,16 +146,22 @@ NS2_DEVINL void midgate(f32x16 (&acc)[4][2], const Gate& p) {
     }
 }
 
+// SKIP (ragged skipping, GemmArgs::row_lens): a separate instantiation (wavenet3_skip_kernel) -- (layer, row tile) pair p on XCD p % 8, a
+// hidden row tile of any grid-z layer returns before the first DMA request, barrier and accumulator
+template <bool SKIP = false>
 NS2_DEVINL void run(const GemmArgs& g) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave & 1, wn = wave >> 1, l31 = lane & 31, hi = lane >> 5;
   const int ntn = (g.N + G2_BN - 1) / G2_BN, ntm = g.M / G2_BM;
-  int bid = xcd_remap(blockIdx.x, gridDim.x);
+  int bid = SKIP ? xcd_spread(blockIdx.x, gridDim.x, ntn) : xcd_remap(blockIdx.x, gridDim.x);
   const int tn = __builtin_amdgcn_readfirstlane(bid % ntn);
   bid /= ntn;
   const int tm = __builtin_amdgcn_readfirstlane(bid % ntm), z = __builtin_amdgcn_readfirstlane(bid / ntm);
+  if constexpr (SKIP) {
+    if (row_tile_hidden(g.row_lens, g.lens_seq, tm * G2_BM, g.M)) return;
+  }
   const int dil = g.dil_z ? (g.dil << z) : g.dil;
   const int dp = g.kt_per_tap * 32;                              // input channels per tap (a multiple of 128)
   const int C = dp >> 6;                                         // 64-column chunks per tap (even)
@@ -255,6 +261,7 @@ NS2_DEVINL void run(const GemmArgs& g) {
 }
 
 __global__ __launch_bounds__(512, 2) void wavenet3_kernel(const GemmArgs g) { run(g); }
+__global__ __launch_bounds__(512, 2) void wavenet3_skip_kernel(const GemmArgs g) { run<true>(g); }
 
 // ---- weights: pack [nz][rows_p][4 dp] FMT_H8 (3 dilated taps + the 1x1 res conv along K) -> per z and column tile
 //   phase-1 images: (chunk c, tap) tiles of 64 columns of HALF values: LDS row = [half part of line (tap dp + 64 c) / 32 | of the next line]
@@ -323,10 +330,12 @@ inline bool wavenet3_eligible(const GemmArgs& g, int precision) {
 inline hipError_t launch_wavenet3(const GemmArgs& g, hipStream_t s) {
   const int nz = g.nz > 0 ? g.nz : 1;
   const int grid = (g.N / G2_BN) * (g.M / G2_BM) * nz;
-  static DynLdsAttr attr;
-  hipError_t e = attr.ensure(reinterpret_cast<const void*>(&wn3::wavenet3_kernel), mx3::LDS_BYTES);
+  static DynLdsAttr attr, attr_skip;
+  hipError_t e = g.row_lens ? attr_skip.ensure(reinterpret_cast<const void*>(&wn3::wavenet3_skip_kernel), mx3::LDS_BYTES)
+                            : attr.ensure(reinterpret_cast<const void*>(&wn3::wavenet3_kernel), mx3::LDS_BYTES);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(wn3::wavenet3_kernel, dim3(grid), dim3(512), mx3::LDS_BYTES, s, g);
+  if (g.row_lens) hipLaunchKernelGGL(wn3::wavenet3_skip_kernel, dim3(grid), dim3(512), mx3::LDS_BYTES, s, g);
+  else hipLaunchKernelGGL(wn3::wavenet3_kernel, dim3(grid), dim3(512), mx3::LDS_BYTES, s, g);
   return hipGetLastError();
 }
 

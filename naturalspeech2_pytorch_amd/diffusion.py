@@ -199,7 +199,8 @@ class NaturalSpeech2(nn.Module):
 
         lens (not in the reference): frames per utterance of a ragged batch, integer [b], each in [1, shape[1]].  Every step hands
         them to the model (`Model.forward(lens=)`: the self-attention kernels read them on the device), so utterance i is denoised as
-        it would be alone at lens[i] frames; latent frames at or beyond lens[i] come back as exactly 0.
+        it would be alone at lens[i] frames; latent frames at or beyond lens[i] come back as exactly 0.  A model with `ragged_skip = True`
+        also skips the 256-row tiles wholly behind a length in every product of the step (model.py `Model`), eager and captured alike.
 
         prompt_lens (not in the reference): rows per utterance of the encoded prompt, integer [b], each in [1, n_p]; handed to the model
         (`Model.forward(prompt_lens=)`), whose conditioning then sees rows [0, prompt_lens[i]) of prompt i alone.

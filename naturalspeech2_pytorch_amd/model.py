@@ -407,10 +407,11 @@ class HipDenoiserMixin:
             if cond_row is None:
                 t = times.to(device=xin.device, dtype=torch.float32).contiguous()
                 t2 = torch.cat((t, t))
-            check(lib.ns2_model_forward_lens(ns.handle, x2.data_ptr(), None if t2 is None else t2.data_ptr(),
-                                             None if cond_row is None else cond_row.data_ptr(), torch.cat((l1, l1)).data_ptr(),
-                                             state.data_ptr(), n_c, out2.data_ptr(), 2 * B, N, ws.data_ptr(), ws.numel(),
-                                             torch.cuda.current_stream().cuda_stream), "ns2_model_forward_lens")
+            entry = _lens_entry(self)
+            check(getattr(lib, entry)(ns.handle, x2.data_ptr(), None if t2 is None else t2.data_ptr(),
+                                      None if cond_row is None else cond_row.data_ptr(), torch.cat((l1, l1)).data_ptr(),
+                                      state.data_ptr(), n_c, out2.data_ptr(), 2 * B, N, ws.data_ptr(), ws.numel(),
+                                      torch.cuda.current_stream().cuda_stream), entry)
         elif cond_row is None:
             t = times.to(device=xin.device, dtype=torch.float32).contiguous()
             check(lib.ns2_model_forward(ns.handle, x2.data_ptr(), torch.cat((t, t)).data_ptr(), state.data_ptr(), n_c, out2.data_ptr(), 2 * B, N,
@@ -454,7 +455,9 @@ class HipDenoiserMixin:
         finite and meaningless.  The self-attention kernels read the lengths on the device.  Under autograd a model with
         `ragged_training = True` takes them too (include/ns2hip_ragged_train.h): utterance i then contributes to the output and to every
         gradient what it contributes alone at lens[i] frames, and the returned rows from lens[i] on are exactly 0; without the switch the
-        training pass raises on `lens`.
+        training pass raises on `lens`.  With `ragged_skip = True` (torch.no_grad() only; include/ns2hip_ragged_skip.h) the step does not compute
+        the 256-row tiles that lie wholly behind a length: rows before H_i = min(n, 256 ceil(lens[i] / 256)) keep their bits, rows of the
+        output from H_i on are exactly 0; it needs n % 256 == 0 and a batch large enough not to split K, else it does nothing.
         `prompt_lens` (not in the reference): prompt rows per utterance of a padded prompt batch, integer [b], each in [1, n_p] -- the
         output of utterance i is what it gives with its prompt cut to prompt_lens[i] rows, whatever the prompt holds from there on
         (NaN included): the mean of to_prompt_cond and the perceiver resampler's keys stop at the length, on the device.  Under autograd a
@@ -521,10 +524,11 @@ class HipDenoiserMixin:
         else:
             ws = self._workspace(ns, B, N, 0, 0)
         if lens is not None:
-            check(_lib.load().ns2_model_forward_lens(ns.handle, xin.data_ptr(), t.data_ptr() if cond_row is None else None,
-                                                     None if cond_row is None else cond_row.data_ptr(), _device_lens(lens, B, xin.device).data_ptr(),
-                                                     state_ptr, n_c, out.data_ptr(), B, N, ws.data_ptr(), ws.numel(),
-                                                     torch.cuda.current_stream().cuda_stream), "ns2_model_forward_lens")
+            entry = _lens_entry(self)
+            check(getattr(_lib.load(), entry)(ns.handle, xin.data_ptr(), t.data_ptr() if cond_row is None else None,
+                                              None if cond_row is None else cond_row.data_ptr(), _device_lens(lens, B, xin.device).data_ptr(),
+                                              state_ptr, n_c, out.data_ptr(), B, N, ws.data_ptr(), ws.numel(),
+                                              torch.cuda.current_stream().cuda_stream), entry)
         elif cond_row is None:
             check(_lib.load().ns2_model_forward(ns.handle, xin.data_ptr(), t.data_ptr(), state_ptr, n_c, out.data_ptr(), B, N,
                                                 ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream), "ns2_model_forward")
@@ -582,6 +586,12 @@ class HipDenoiserMixin:
             for k in bufs:
                 lib.ns2_model_debug_tap(ns.handle, k.encode(), None, 0)
         return out, bufs
+
+
+def _lens_entry(m):
+    """the library entry a forward with lengths calls: with `ragged_skip` the one whose step skips the row tiles hidden behind the lengths
+    (include/ns2hip_ragged_skip.h; the library's skip rule decides per shape, and falls back to the other's launches)"""
+    return "ns2_model_forward_lens_skip" if getattr(m, "ragged_skip", False) else "ns2_model_forward_lens"
 
 
 def _device_lens(lens, B, device):
@@ -658,6 +668,7 @@ class Model(HipDenoiserMixin, nn.Module):
         ragged_training=False,
         head_dim_training=False,
         ragged_conditioning=False,
+        ragged_skip=False,
     ):
         super().__init__()
         self.dim = dim
@@ -732,6 +743,11 @@ class Model(HipDenoiserMixin, nn.Module):
         self.ragged_training = ragged_training        # True: forward(lens=) under autograd trains on a ragged batch (else it raises)
         self.head_dim_training = head_dim_training    # True: dim_head 32 / 128 train on the HIP kernels too (else: the composite, as before)
         self.ragged_conditioning = ragged_conditioning    # True: forward(prompt_lens=) under autograd trains on ragged prompts (else it raises)
+        # True: under torch.no_grad(), forward(lens=) / forward_with_cond_scale(lens=) skip the 256-row tiles that lie wholly behind an utterance's
+        # length in every product and both attentions (include/ns2hip_ragged_skip.h): rows before H_i = min(n, 256 ceil(lens_i / 256)) keep
+        # their bits, rows of the output from H_i on come back as exact zeros.  Does nothing without lens=; ignored under autograd (the
+        # training pass computes every row).
+        self.ragged_skip = ragged_skip
         self._hip_init(dict(dim=dim, depth=depth, dim_head=dim_head, heads=heads, ff_mult=ff_mult, wavenet_layers=wavenet_layers,
                             wavenet_stacks=wavenet_stacks, dim_cond_mult=dim_cond_mult, condition_on_prompt=condition_on_prompt,
                             dim_prompt=dim_prompt, num_latents_m=num_latents_m, resampler_depth=resampler_depth), precision)
