@@ -2,7 +2,8 @@
 include/ns2hip_pitch.h, the pitch extractor, include/ns2hip_ragged.h, ragged batches, include/ns2hip_ragged_front.h, ragged prompts
 and text, include/ns2hip_ragged_train.h, ragged training batches, include/ns2hip_head_dim_train.h, training at head dims 32 and 128, and
 include/ns2hip_ragged_audio.h, ragged raw audio, include/ns2hip_fold.h, the feed-forward fold, and include/ns2hip_ragged_cond_train.h,
-ragged text and prompts in training, each into tables of its own) is parsed once, at import.
+ragged text and prompts in training, include/ns2hip_ragged_skip.h, skipping in a ragged sampling batch, and
+include/ns2hip_ragged_skip_train.h, skipping in a ragged training batch, each into tables of its own) is parsed once, at import.
 
 The HIP library is the product: importing this module FAILS LOUDLY when the header or the shared object is missing or the
 library does not export the full ABI -- there is no CPU / PyTorch fallback for the hot path.
@@ -38,6 +39,7 @@ RAGGED_AUDIO_HEADER_PATH = os.path.join(_HERE, "..", "include", "ns2hip_ragged_a
 FOLD_HEADER_PATH = os.path.join(_HERE, "..", "include", "ns2hip_fold.h")   # the feed-forward fold: likewise
 RAGGED_COND_TRAIN_HEADER_PATH = os.path.join(_HERE, "..", "include", "ns2hip_ragged_cond_train.h")   # lengths through the conditioning's training pass: likewise
 RAGGED_SKIP_HEADER_PATH = os.path.join(_HERE, "..", "include", "ns2hip_ragged_skip.h")   # skipping the hidden row tiles of a ragged sampling batch: likewise
+RAGGED_SKIP_TRAIN_HEADER_PATH = os.path.join(_HERE, "..", "include", "ns2hip_ragged_skip_train.h")   # ... of a ragged training batch: likewise
 
 
 class Ns2Error(RuntimeError):
@@ -171,6 +173,11 @@ if not os.path.exists(RAGGED_SKIP_HEADER_PATH):
 with open(RAGGED_SKIP_HEADER_PATH) as _f:                        # (the argument blocks, ns2_weight and ns2_model_config: c_void_p here too)
     _, _, RAGGED_SKIP_SIGNATURES = parse_header(_f.read())
 
+if not os.path.exists(RAGGED_SKIP_TRAIN_HEADER_PATH):
+    raise Ns2Error(f"{RAGGED_SKIP_TRAIN_HEADER_PATH} not found: the binding is derived from the header, it ships with the package's source tree")
+with open(RAGGED_SKIP_TRAIN_HEADER_PATH) as _f:                  # (ns2_linear_args: c_void_p here too -- pass ctypes.byref(block))
+    _, _, RAGGED_SKIP_TRAIN_SIGNATURES = parse_header(_f.read())
+
 _lib = None
 
 
@@ -185,7 +192,7 @@ def load():
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in {**SIGNATURES, **OPTIM_SIGNATURES, **PITCH_SIGNATURES, **RAGGED_SIGNATURES, **FRONT_SIGNATURES,
                               **RAGGED_TRAIN_SIGNATURES, **HEAD_DIM_TRAIN_SIGNATURES, **RAGGED_AUDIO_SIGNATURES, **FOLD_SIGNATURES,
-                              **RAGGED_COND_TRAIN_SIGNATURES, **RAGGED_SKIP_SIGNATURES}.items():
+                              **RAGGED_COND_TRAIN_SIGNATURES, **RAGGED_SKIP_SIGNATURES, **RAGGED_SKIP_TRAIN_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -255,3 +262,8 @@ def ragged_cond_train_header_symbols():
 def ragged_skip_header_symbols():
     """Symbols declared in include/ns2hip_ragged_skip.h"""
     return sorted(RAGGED_SKIP_SIGNATURES)
+
+
+def ragged_skip_train_header_symbols():
+    """Symbols declared in include/ns2hip_ragged_skip_train.h"""
+    return sorted(RAGGED_SKIP_TRAIN_SIGNATURES)

@@ -36,7 +36,7 @@ def hip_backed_model_class(reference_model_cls):
 
     class HipBackedModel(HipDenoiserMixin, reference_model_cls):
         def __init__(self, dim, *args, precision="exact", train_backend="reference", train_precision="exact", ragged_training=False,
-                     head_dim_training=False, ragged_conditioning=False, ragged_skip=False, **kwargs):
+                     head_dim_training=False, ragged_conditioning=False, ragged_skip=False, ragged_skip_training=False, **kwargs):
             reference_model_cls.__init__(self, dim, *args, **kwargs)
             bound = sig.bind(self, dim, *args, **kwargs)
             cfg = dict(defaults)
@@ -49,6 +49,7 @@ def hip_backed_model_class(reference_model_cls):
             self.head_dim_training = head_dim_training        # True: dim_head 32 / 128 on the HIP training kernels (model.py `Model`)
             self.ragged_conditioning = ragged_conditioning    # True: forward(prompt_lens=) under autograd (train_backend="hip"; model.py `Model`)
             self.ragged_skip = ragged_skip                    # True: forward(lens=) under torch.no_grad() skips the hidden row tiles (model.py `Model`)
+            self.ragged_skip_training = ragged_skip_training  # True: ... and under autograd the training pass's products do (model.py `Model`)
 
         def _forward_autograd(self, x, times, prompt=None, prompt_mask=None, cond=None, cond_drop_prob=None, lens=None, prompt_lens=None):
             """train_backend="reference" (default): the reference's own forward under torch autograd -- the loss is upstream's bit for

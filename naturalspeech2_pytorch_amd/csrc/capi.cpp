@@ -4,6 +4,7 @@
 
 #include <cstdarg>
 #include <cstdio>
+#include <atomic>
 #include <cstring>
 #include <vector>
 
@@ -11,6 +12,7 @@
 #include "../../include/ns2hip_fold.h"
 #include "../../include/ns2hip_ragged.h"
 #include "../../include/ns2hip_ragged_skip.h"
+#include "../../include/ns2hip_ragged_skip_train.h"
 #include "ns2_host.h"
 #include "gemm_route.h"
 
@@ -216,6 +218,23 @@ extern "C" int ns2_linear_lens(const ns2_linear_args* p, const int* row_lens, in
   if (int rc = linear_args_from(p, &g)) return rc;
   g.row_lens = row_lens; g.lens_seq = seq_len;
   HIPRET(launch_gemm(g, p->precision, (hipStream_t)stream));
+  return NS2_OK;
+}
+// include/ns2hip_ragged_skip_train.h: the same entry under the training rule (zero bits in the hidden tiles of every output), and the
+// host counter of the launches that went out with lengths (capi_train.cpp's ns2_wgrad_rows_lens bumps it too)
+static std::atomic<long long> g_train_skip_launches{0};
+void ns2::note_train_skip_launch() { g_train_skip_launches.fetch_add(1, std::memory_order_relaxed); }
+extern "C" int64_t ns2_debug_train_skip_launches(void) { return g_train_skip_launches.load(std::memory_order_relaxed); }
+extern "C" int ns2_linear_lens_zero(const ns2_linear_args* p, const int* row_lens, int seq_len, void* stream) {
+  ARGCHK(p != nullptr, "ns2_linear_lens_zero: null argument block");
+  SKIP_SHAPE_CHK("ns2_linear_lens_zero", row_lens, seq_len, p->M);
+  ARGCHK(p->seq_len == 0 || p->seq_len == seq_len, "ns2_linear_lens_zero: args->seq_len differs from seq_len");
+  GemmArgs g;
+  if (int rc = linear_args_from(p, &g)) return rc;
+  g.row_lens = row_lens; g.lens_seq = seq_len; g.zero_hidden = 1;
+  const bool with_lens = plan_gemm(g, p->precision).route != GemmRoute::SplitK;      // (split K takes no lengths: every row is computed)
+  HIPRET(launch_gemm(g, p->precision, (hipStream_t)stream));
+  if (with_lens) note_train_skip_launch();
   return NS2_OK;
 }
 extern "C" int ns2_geglu_pack_bias(const float* bias, int f, float* packed, int packed_len, void* stream) {

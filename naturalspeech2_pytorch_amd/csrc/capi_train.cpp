@@ -8,6 +8,7 @@
 #include "../../include/ns2hip_head_dim_train.h"
 #include "../../include/ns2hip_ragged_cond_train.h"
 #include "../../include/ns2hip_ragged_train.h"
+#include "../../include/ns2hip_ragged_skip_train.h"
 #include "ns2_host.h"
 
 using namespace ns2;
@@ -173,9 +174,10 @@ extern "C" int ns2_wgrad_rows_preferred(int R, int ncols, int64_t M) {
   const long blocks256 = (long)((R + 255) / 256) * ((ncols + 255) / 256) * wgrad_split(R, ncols, ld_t);
   return blocks256 > 64;
 }
-extern "C" int ns2_wgrad_rows(const uint16_t* dy_hi, const uint16_t* dy_lo, int ld_dy, const uint16_t* x_hi, const uint16_t* x_lo, int ld_x,
-                              int64_t M, int R, int T, int Kp, int K, int dil, int seq_len, float* dw, void* workspace, int64_t workspace_bytes,
-                              int precision, void* stream) {
+// row_lens: null = ns2_wgrad_rows; else ns2_wgrad_rows_lens (seq_len checked by it), the LENS instantiations of the TR kernel
+static int wgrad_rows_impl(const uint16_t* dy_hi, const uint16_t* dy_lo, int ld_dy, const uint16_t* x_hi, const uint16_t* x_lo, int ld_x,
+                           int64_t M, int R, int T, int Kp, int K, int dil, int seq_len, float* dw, void* workspace, int64_t workspace_bytes,
+                           int precision, const int* row_lens, void* stream) {
   ARGCHK(dy_hi && dy_lo == dy_hi + 32 && x_hi && x_lo == x_hi + 32 && dw && workspace, "ns2_wgrad_rows: null pointer / operands must be interleaved lines (lo = hi + 32)");
   ARGCHK(precision == 3 || precision == 4, "ns2_wgrad_rows: precision 3 (bf16 x3) or 4 (half product + fp8 correction terms on FMT_H8 lines)");
   ARGCHK(M > 0 && M < (1LL << 30) && R > 0 && T > 0 && K > 0 && Kp >= K && (Kp & 31) == 0 && (ld_dy & 31) == 0 && (ld_x & 31) == 0 && ld_dy >= R && ld_x >= Kp,
@@ -193,9 +195,25 @@ extern "C" int ns2_wgrad_rows(const uint16_t* dy_hi, const uint16_t* dy_lo, int 
   g.nz = S; g.out_f_zs = (long)R * ncols;
   g.epi = EPI_F32; g.out_f = (float*)workspace; g.ldo_f = ncols;
   g.tr_tokens = (int)M; g.tr_kp = Kp; g.tr_taps = T > 1 ? T : 0;
+  if (row_lens) { g.row_lens = row_lens; g.lens_seq = seq_len; }
   HIPRET(launch_gemm_tr(g, precision, (hipStream_t)stream));
+  if (row_lens) note_train_skip_launch();
   HIPRET(launch_wgrad_reduce((const float*)workspace, S, R, ncols, T, Kp, K, dw, (hipStream_t)stream));
   return NS2_OK;
+}
+extern "C" int ns2_wgrad_rows(const uint16_t* dy_hi, const uint16_t* dy_lo, int ld_dy, const uint16_t* x_hi, const uint16_t* x_lo, int ld_x,
+                              int64_t M, int R, int T, int Kp, int K, int dil, int seq_len, float* dw, void* workspace, int64_t workspace_bytes,
+                              int precision, void* stream) {
+  return wgrad_rows_impl(dy_hi, dy_lo, ld_dy, x_hi, x_lo, ld_x, M, R, T, Kp, K, dil, seq_len, dw, workspace, workspace_bytes, precision, nullptr, stream);
+}
+// include/ns2hip_ragged_skip_train.h: what the entry refuses on its own account comes first, under its own name
+extern "C" int ns2_wgrad_rows_lens(const uint16_t* dy_hi, const uint16_t* dy_lo, int ld_dy, const uint16_t* x_hi, const uint16_t* x_lo, int ld_x,
+                                   int64_t M, int R, int T, int Kp, int K, int dil, int seq_len, float* dw, void* workspace,
+                                   int64_t workspace_bytes, int precision, const int* row_lens, void* stream) {
+  ARGCHK(row_lens != nullptr, "ns2_wgrad_rows_lens: row_lens is null (ns2_wgrad_rows is the call that multiplies every token)");
+  ARGCHK(seq_len > 0 && (seq_len & 255) == 0, "ns2_wgrad_rows_lens: seq_len must be a positive multiple of 256 (whole skipping granules per utterance)");
+  ARGCHK(M > 0 && M % seq_len == 0, "ns2_wgrad_rows_lens: M must be whole utterances of seq_len rows");
+  return wgrad_rows_impl(dy_hi, dy_lo, ld_dy, x_hi, x_lo, ld_x, M, R, T, Kp, K, dil, seq_len, dw, workspace, workspace_bytes, precision, row_lens, stream);
 }
 
 extern "C" int ns2_film_gate_fwd(const float* h, int64_t ldh, const float* film, int film_ld, int seq_len, int64_t M, int d, float* out,

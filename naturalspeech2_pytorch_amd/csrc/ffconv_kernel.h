@@ -73,6 +73,7 @@ struct Args {                    // 16 dwords
   // the SKIP instantiations only (ragged skipping, GemmArgs::row_lens / lens_seq): frames per utterance [M / lens_seq] on the device
   int lens_seq;
   const int* row_lens;
+  int zero_hidden;               // GemmArgs::zero_hidden (the training rule: zero bits in the hidden tiles of whatever the mode writes)
 };
 
 // ---- LDS-DMA as inline assembly: the compiler must not count these loads (its waitcnt pass drains every outstanding one with
@@ -302,6 +303,11 @@ struct Kern {
     const int m0 = tm * 256;
     if constexpr (SKIP) {
       if (row_tile_hidden(g.row_lens, g.lens_seq, m0, g.M)) {
+        if (g.zero_hidden) {
+          if constexpr (PF == PF_F32) zero_tile_f32(reinterpret_cast<float*>(g.out), g.ldo, m0, 256, tn * 256, min(256, g.N - tn * 256), threadIdx.x, 512);
+          else zero_tile_planes(g.out, g.ldo, PF == PF_H8, PF == PF_H8 ? FMT_H8 : FMT_F16, m0, 256, tn * 256, min(tn * 256 + 256, g.out_ncols), threadIdx.x, 512);
+          return;
+        }
         if constexpr (PF == PF_F32) {
           if (!g.resid) zero_tile_f32(reinterpret_cast<float*>(g.out), g.ldo, m0, 256, tn * 256, min(256, g.N - tn * 256), threadIdx.x, 512);
         }
@@ -380,7 +386,7 @@ inline hipError_t launch_ffconv3_as(const GemmArgs& g, hipStream_t s) {
   a.bias = g.bias; a.out = g.out_hi;
   a.M = g.M; a.N = g.N; a.lda = g.lda; a.ldo = g.ldo_s; a.seq_len = g.seq_len; a.tpt = g.lda / 64; a.kv = g.kt_per_tap * 32;
   a.out_ncols = g.out_ncols; a.resid = nullptr; a.ldr = 0;
-  a.row_lens = g.row_lens; a.lens_seq = g.lens_seq;
+  a.row_lens = g.row_lens; a.lens_seq = g.lens_seq; a.zero_hidden = g.zero_hidden;
   if (g.epi == EPI_F32) {
     a.out = reinterpret_cast<bf16_t*>(g.out_f); a.ldo = g.ldo_f; a.out_ncols = g.N; a.resid = g.resid; a.ldr = g.ldr;
     static DynLdsAttr attr_f32;

@@ -64,6 +64,7 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const GemmArgs g) {
   const int z = bid / ntm;
   if constexpr (SKIP) {
     if (row_tile_hidden(g.row_lens, g.lens_seq, tm * BM, g.M)) {
+      if (g.zero_hidden) { zero_hidden_tile<EPI>(g, z, tm * BM, min(BM, g.M - tm * BM), tn * BN, BN, threadIdx.x, 256); return; }
       if constexpr (EPI == EPI_F32) {
         if (!g.resid) zero_tile_f32(g.out_f + z * g.out_f_zs, g.ldo_f, tm * BM, min(BM, g.M - tm * BM), tn * BN, min(BN, g.N - tn * BN), threadIdx.x, 256);
       }

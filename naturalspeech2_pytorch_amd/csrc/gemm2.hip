@@ -134,10 +134,19 @@ NS2_DEVINL void tr_wait(f32x16& c0, f32x16& c1) {                 // every trans
 //
 // SKIP (ragged skipping, GemmArgs::row_lens): as in gemm_kernel -- a separate instantiation whose row tile tm goes to XCD tm % 8 and whose
 // workgroups return on a hidden row tile before the first DMA request, barrier or accumulator; the others compile to what they were.
+//
+// TR with SKIP = LENS (ragged skipping in training, include/ns2hip_ragged_skip_train.h): the contraction runs over the TOKENS, so the
+// lengths shorten the K loop, not the grid.  With lens_seq % 256 == 0 a 32-token K tile lies inside one utterance and one granule: it
+// is hidden iff its first token is, and a visible tile's causal taps (token m - shift) read visible rows only.  The slice plan is the
+// caller's: slice z still owns tokens [z nkt 32, (z + 1) nkt 32), but its loop visits the VISIBLE tiles among them only, as one
+// compacted sequence -- run_k8 sees a shorter loop of consecutive iterations, so stage parity (by iteration) and the counted waits
+// (same requests per iteration) are what they were; only the running token counters of issue_half step over a hidden run.  A slice
+// without a visible tile stores its zero accumulators.  The skipped terms were products of the exact zeros of dY's hidden rows.
 template <int NSPLIT, int EPI, bool F16, int P1 = 0, bool TR = false, bool SKIP = false>
 __global__ __launch_bounds__(512, 2) void gemm2_kernel(const GemmArgs g) {
   const bf16_t* zero_page = g2_zero_page;
-  static_assert(!(SKIP && TR), "weight gradients take no lengths");
+  constexpr bool LENS = TR && SKIP;                  // weight gradients: the lengths shorten the K loop
+  constexpr bool RSKIP = SKIP && !TR;                // everything else: hidden row tiles return
   static_assert(!TR || (EPI == EPI_F32 && P1 == 0 && NSPLIT != 1), "transposed operands: weight gradients (fp32 slots) on interleaved lines");
   static_assert(NSPLIT != 2 || F16, "the mixed mode multiplies IEEE-half operands");
   static_assert(P1 == 0 || (EPI == EPI_WAVENET && P1 == 1 && NSPLIT == 2), "phase-1 override: half product under the mixed mode");
@@ -168,13 +177,14 @@ __global__ __launch_bounds__(512, 2) void gemm2_kernel(const GemmArgs g) {
 
   const int ntn = (g.N + G2_BN - 1) / G2_BN;
   const int ntm = (g.M + G2_BM - 1) / G2_BM;
-  int bid = SKIP ? xcd_spread(blockIdx.x, gridDim.x, ntn) : xcd_remap(blockIdx.x, gridDim.x);
+  int bid = RSKIP ? xcd_spread(blockIdx.x, gridDim.x, ntn) : xcd_remap(blockIdx.x, gridDim.x);
   const int tn = bid % ntn;
   bid /= ntn;
   const int tm = bid % ntm;
   const int z = bid / ntm;
-  if constexpr (SKIP) {
+  if constexpr (RSKIP) {
     if (row_tile_hidden(g.row_lens, g.lens_seq, tm * G2_BM, g.M)) {
+      if (g.zero_hidden) { zero_hidden_tile<EPI>(g, z, tm * G2_BM, min(G2_BM, g.M - tm * G2_BM), tn * G2_BN, G2_BN, tid, 512); return; }
       if constexpr (EPI == EPI_F32) {
         if (!g.resid) zero_tile_f32(g.out_f + z * g.out_f_zs, g.ldo_f, tm * G2_BM, min(G2_BM, g.M - tm * G2_BM), tn * G2_BN, min(G2_BN, g.N - tn * G2_BN), tid, 512);
       }
@@ -494,11 +504,31 @@ __global__ __launch_bounds__(512, 2) void gemm2_kernel(const GemmArgs g) {
 
   int tr_tok0[4], tr_n0[4];      // TR: per half tile, the first token of the NEXT tile to request and its position inside the utterance
   long tr_off[4];                //     ... and the element offset of that tile from the slice's first (added to psrc)
-  if constexpr (TR) {
+  int tr_ext[4];                 // LENS: per half tile, the computed extent of the utterance the NEXT tile to request lies in
+  int tr_vis = 0;                // LENS: visible K tiles of this slice (the length of its compacted loop)
+  if constexpr (TR && !LENS) {
     const int t0 = z * g.nkt * 32;
     const int nb = g.seq_len > 0 ? t0 % g.seq_len : 0;
 #pragma unroll
     for (int h = 0; h < 4; ++h) { tr_tok0[h] = t0; tr_n0[h] = nb; tr_off[h] = 0; }
+  }
+  if constexpr (LENS) {
+    // Scalars only (z is workgroup-uniform, the lengths come through the scalar cache).  Tokens [t0, tend) of the slice, walked
+    // utterance by utterance: lens is read for utterances that start before tend <= tr_tokens = B lens_seq, never past the batch.
+    const int sl = g.lens_seq;
+    const int t0 = z * g.nkt * 32, tend = min(t0 + g.nkt * 32, g.tr_tokens);
+    int first = -1, first_n = 0, first_ext = 0;
+    for (int b = t0 / sl; b * sl < tend; ++b) {
+      const int ext = ragged_extent(g.row_lens[b], sl);
+      const int lo_t = max(t0, b * sl), hi_t = min(tend, b * sl + ext);
+      if (hi_t > lo_t) {
+        if (first < 0) { first = lo_t; first_n = lo_t - b * sl; first_ext = ext; }
+        tr_vis += (hi_t - lo_t) >> 5;
+      }
+    }
+    if (first < 0) first = t0;                         // no visible tile: nothing is requested
+#pragma unroll
+    for (int h = 0; h < 4; ++h) { tr_tok0[h] = first; tr_n0[h] = first_n; tr_ext[h] = first_ext; tr_off[h] = (long)(first - t0) * (h < 2 ? a_rs : w_rs); }
   }
   // (not in the single-product EPI_SPLIT instantiation = the FF causal conv of the hybrid plan, the dominant kernel: it runs the
   // tap-shared loop below, and a second issue path in its unused general loop cost it 2.6 % through register allocation)
@@ -553,6 +583,20 @@ __global__ __launch_bounds__(512, 2) void gemm2_kernel(const GemmArgs g) {
       }
 #pragma unroll
       for (int e = 0; e < 2; ++e) glds16(p[e], sbase + pldst[H][e]);
+      if constexpr (LENS) {
+        // the next VISIBLE tile: the one behind this, or -- at the utterance's extent -- the first tile of the next utterance (every
+        // extent is >= 256, so that one is visible).  The state behind the slice's last visible tile is never used; lens is not read
+        // past the batch.
+        int tok1 = tok0 + 32, n1 = n0 + 32;
+        if (n1 >= tr_ext[H]) {
+          tok1 += g.lens_seq - n1;
+          n1 = 0;
+          tr_ext[H] = tok1 < g.tr_tokens ? ragged_extent(g.row_lens[tok1 / g.lens_seq], g.lens_seq) : g.lens_seq;
+        }
+        tr_off[H] = off + (long)(tok1 - tok0) * (H < 2 ? a_rs : w_rs);
+        tr_tok0[H] = tok1; tr_n0[H] = n1;
+        return;
+      }
       tr_tok0[H] = tok0 + 32;
       tr_off[H] = off + 32 * (H < 2 ? a_rs : w_rs);
       if (g.seq_len > 0) { const int n1 = n0 + 32; tr_n0[H] = n1 >= g.seq_len ? n1 - g.seq_len : n1; }
@@ -926,6 +970,8 @@ __global__ __launch_bounds__(512, 2) void gemm2_kernel(const GemmArgs g) {
     } else {
       run_k8(ModeMain{}, 0, ntaps * tiles_per_tap(ModeMain{}));
     }
+  } else if constexpr (LENS) {
+    run_k8(ModeMain{}, 0, tr_vis);
   } else {
     run_k8(ModeMain{}, 0, ntaps * tiles_per_tap(ModeMain{}));
   }
@@ -979,6 +1025,10 @@ hipError_t launch_gemm_tr(const GemmArgs& g, int precision, hipStream_t s) {
   if (g.tr_tokens <= 0 || g.tr_kp <= 0 || (g.tr_kp & 31) || (g.lda & 31) || (g.ldw & 31) || g.tr_taps < 0) return hipErrorInvalidValue;
   if (g.tr_taps > 1 && (g.seq_len < 32 || g.dil < 1)) return hipErrorInvalidValue;      // the in-tile utterance position wraps at most once
   if ((long)g.nz * g.nkt * 32 < g.tr_tokens) return hipErrorInvalidValue;                // the slices cover every token
+  if (g.row_lens) {      // the LENS instantiations (ragged skipping in training): whole granules per utterance, the utterances of a conv's taps are the lengths'
+    if (g.lens_seq <= 0 || (g.lens_seq & 255) || (g.tr_tokens % g.lens_seq) || (g.seq_len > 0 && g.seq_len != g.lens_seq)) return hipErrorInvalidValue;
+    return precision == 3 ? launch2_one<3, EPI_F32, false, 0, true, true>(g, s) : launch2_one<2, EPI_F32, true, 0, true, true>(g, s);
+  }
   return precision == 3 ? launch2_one<3, EPI_F32, false, 0, true>(g, s) : launch2_one<2, EPI_F32, true, 0, true>(g, s);
 }
 

@@ -205,6 +205,7 @@ struct Kern {
     const int tn = __builtin_amdgcn_readfirstlane(bid % ntn), tm = __builtin_amdgcn_readfirstlane(bid / ntn);
     if constexpr (SKIP) {
       if (row_tile_hidden(g.row_lens, g.lens_seq, tm * G2_BM, g.M)) {
+        if (g.zero_hidden) { zero_hidden_tile<EPI>(g, 0, tm * G2_BM, G2_BM, tn * G2_BN, G2_BN, tid, 512); return; }
         if constexpr (EPI == EPI_F32) {
           if (!g.resid) zero_tile_f32(g.out_f, g.ldo_f, tm * G2_BM, G2_BM, tn * G2_BN, min(G2_BN, g.N - tn * G2_BN), tid, 512);
         }

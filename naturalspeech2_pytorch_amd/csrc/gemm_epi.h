@@ -95,6 +95,77 @@ NS2_DEVINL void norm_gamma4(const GemmArgs& g, int c, float (&gm)[4]) {
   if (g.nrm_gamma) { const float4 t = *reinterpret_cast<const float4*>(g.nrm_gamma + c); gm[0] = t.x; gm[1] = t.y; gm[2] = t.z; gm[3] = t.w; }
 }
 
+// ---- Ragged skipping in the training pass (GemmArgs::zero_hidden, include/ns2hip_ragged_skip_train.h): a hidden tile of EVERY output
+// of the product gets zero bits -- what the tile's epilogue would have covered, nothing else.  Zero bits are the value 0 in every
+// format (fp32, bf16 hi / lo, IEEE half, the e5m2 bytes of FMT_H8).  Rows [row0, row0 + rows) lie inside one utterance and one skipping
+// granule (the caller's tile height divides 256 and lens_seq % 256 == 0); col0 / bn: the tile's first (packed) column and its width, a
+// multiple of 128.  Called by the whole workgroup on its early return; no barrier, no LDS.
+// logical columns [c0, c1) (c0 % 32 == 0, c1 even) of the rows of split-plane matrix `hi` (interleaved lines when il)
+NS2_DEVINL void zero_tile_planes(bf16_t* hi, int ld, bool il, int fmt, int row0, int rows, int c0, int c1, int tid, int nthreads) {
+  if (rows <= 0 || c1 <= c0) return;
+  const long rs = pld(ld, il);                                  // physical row stride, 16-bit elements
+  const int c1w = il ? (c1 & ~31) : c1;                         // whole lines / the dense range: physically contiguous
+  const int p0 = il ? 2 * c0 : c0, p1 = il ? 2 * c1w : c1w;     // physical element range of it
+  bf16_t* base = hi + (long)row0 * rs;
+  if (p1 > p0) {
+    const bool v16 = ((reinterpret_cast<uintptr_t>(base + p0) & 15) == 0) && ((rs & 7) == 0) && (((p1 - p0) & 7) == 0);
+    if (v16) {
+      const int per = (p1 - p0) >> 3;
+      for (int i = tid; i < rows * per; i += nthreads) {
+        const int r = i / per;
+        *reinterpret_cast<uint4*>(base + (long)r * rs + p0 + ((i - r * per) << 3)) = make_uint4(0u, 0u, 0u, 0u);
+      }
+    } else {
+      const int per = (p1 - p0) >> 1;
+      for (int i = tid; i < rows * per; i += nthreads) {
+        const int r = i / per;
+        *reinterpret_cast<uint32_t*>(base + (long)r * rs + p0 + ((i - r * per) << 1)) = 0u;
+      }
+    }
+  }
+  if (c1w < c1) {                                               // the started line of an interleaved matrix: column pairs, as store_cols2 addresses them
+    const int per = (c1 - c1w) >> 1;
+    for (int i = tid; i < rows * per; i += nthreads) {
+      const int r = i / per, c = c1w + ((i - r * per) << 1);
+      bf16_t* line = base + (long)r * rs + ((c & ~31) << 1);
+      *reinterpret_cast<uint32_t*>(line + (c & 31)) = 0u;
+      if (fmt == FMT_H8) {
+        unsigned char* bytes = reinterpret_cast<unsigned char*>(line) + 64 + (c & 31);
+        *reinterpret_cast<uint16_t*>(bytes) = 0; *reinterpret_cast<uint16_t*>(bytes + 32) = 0;
+      } else {
+        *reinterpret_cast<uint32_t*>(line + 32 + (c & 31)) = 0u;
+      }
+    }
+  }
+}
+template <int EPI>
+NS2_DEVINL void zero_hidden_tile(const GemmArgs& g, int z, int row0, int rows, int col0, int bn, int tid, int nthreads) {
+  if constexpr (EPI == EPI_F32) {
+    zero_tile_f32(g.out_f + z * g.out_f_zs, g.ldo_f, row0, rows, col0, min(bn, g.N - col0), tid, nthreads);
+  } else {
+    const bool il = g.out_lo != nullptr;
+    bf16_t* out_hi = g.out_hi + pcol((int)(z * g.out_zs), il);
+    if constexpr (EPI == EPI_GEGLU) {                           // packed [x 32 | gate 32] column blocks -> 32 output columns each
+      zero_tile_planes(out_hi, g.ldo_s, il, g.out_fmt, row0, rows, col0 >> 1, min((col0 + bn) >> 1, g.out_ncols), tid, nthreads);
+    } else {
+      zero_tile_planes(out_hi, g.ldo_s, il, g.out_fmt, row0, rows, col0, min(col0 + bn, g.out_ncols), tid, nthreads);
+      if constexpr (EPI == EPI_QKV) {                           // V^T[b][feature][n]: 4 tokens per store, as the epilogue writes them
+        const int f0 = max(col0, g.split_col) - g.split_col, f1 = min(col0 + bn, g.N) - g.split_col;
+        if (f1 > f0 && g.seq_len > 0 && rows >= 4) {
+          const bool vil = g.vt_lo != nullptr;
+          const int b = row0 / g.seq_len, n0 = row0 - b * g.seq_len, per = rows >> 2;
+          for (int i = tid; i < (f1 - f0) * per; i += nthreads) {
+            const int f = i / per, n = n0 + ((i - f * per) << 2);
+            const long o = ((long)b * g.vt_rows + f0 + f) * pld(g.vt_ld, vil) + pcol(n, vil);
+            *reinterpret_cast<uint2*>(g.vt_hi + o) = make_uint2(0u, 0u);
+            if (vil) *reinterpret_cast<uint2*>(g.vt_lo + o) = make_uint2(0u, 0u);
+          }
+        }
+      }
+    }
+  }
+}
+
 // The generic epilogue.  ocol_base: first output column of this wave for EPI_GEGLU (= half of the packed column index)
 template <int EPI, int MI>
 NS2_DEVINL void gemm_epilogue(f32x16 (&acc)[MI][2], const GemmArgs& g, int z, int row_base, int col_base, int ocol_base, int lane) {

@@ -11,6 +11,7 @@
 namespace ns2 {
 
 void set_error(const char* fmt, ...);
+void note_train_skip_launch();  // capi.cpp: a training product went out with lengths (ns2_debug_train_skip_launches)
 void gemm_hook_changed();      // model_exec.cpp: ns2_debug_force_gemm was called (a cached verdict of the chain rule is stale)
 
 // how an entry point gives up: a failed HIP call / a refused argument / a failed step -> the last error + the C ABI's code

@@ -105,6 +105,12 @@ struct GemmArgs {
   // min(lens_seq, 256 ceil(clamp(len, 1, lens_seq) / 256)) returns before its first load -- an fp32 output without a residual gets
   // zeros there, every other output keeps what it held.  null = every row is computed.  The split-K route takes no lengths.
   const int* row_lens = nullptr; int lens_seq = 0;
+  // ragged skipping in the TRAINING pass (include/ns2hip_ragged_skip_train.h; appended: no other field moves).  With row_lens: a hidden
+  // tile of EVERY output -- fp32 with or without a residual, operand planes of either format, V^T -- is stored as zero bits instead of
+  // being left as it was (gemm_epi.h zero_hidden_tile): the buffers of the pass come uninitialised, and the anticausal dgrads and the
+  // kernels that do not skip read behind an utterance's extent.  0 = the sampling rule above.  launch_gemm_tr (weight gradients) with
+  // row_lens: the LENS instantiations, which step over the 32-token K tiles behind an extent; it has no hidden output.
+  int zero_hidden = 0;
 };
 // may g carry row_lens?  (what launch_gemm checks, and the stand-alone entries before any device call)
 inline bool gemm_lens_ok(const GemmArgs& g) { return g.lens_seq > 0 && (g.lens_seq & 255) == 0 && g.M > 0 && (g.M % g.lens_seq) == 0; }

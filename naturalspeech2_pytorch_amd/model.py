@@ -669,6 +669,7 @@ class Model(HipDenoiserMixin, nn.Module):
         head_dim_training=False,
         ragged_conditioning=False,
         ragged_skip=False,
+        ragged_skip_training=False,
     ):
         super().__init__()
         self.dim = dim
@@ -748,6 +749,11 @@ class Model(HipDenoiserMixin, nn.Module):
         # their bits, rows of the output from H_i on come back as exact zeros.  Does nothing without lens=; ignored under autograd (the
         # training pass computes every row).
         self.ragged_skip = ragged_skip
+        # True: under autograd, with ragged_training and forward(lens=), the forward products, the dgrads and the weight gradients of the HIP
+        # training pass skip the same hidden 256-row tiles (include/ns2hip_ragged_skip_train.h): loss, returned rows and every
+        # parameter's gradient keep the bits of the switch off.  Does nothing without lens=, with n % 256 != 0, on the CPU or for a model
+        # the HIP pass does not take.
+        self.ragged_skip_training = ragged_skip_training
         self._hip_init(dict(dim=dim, depth=depth, dim_head=dim_head, heads=heads, ff_mult=ff_mult, wavenet_layers=wavenet_layers,
                             wavenet_stacks=wavenet_stacks, dim_cond_mult=dim_cond_mult, condition_on_prompt=condition_on_prompt,
                             dim_prompt=dim_prompt, num_latents_m=num_latents_m, resampler_depth=resampler_depth), precision)

@@ -170,19 +170,28 @@ class PackedWeight:
             pass
 
 
-def _linear(w: PackedWeight, a: Planes, M: int, precision: int, **fields):
+def _linear(w: PackedWeight, a: Planes, M: int, precision: int, row_lens=None, **fields):
     """The one place that fills a ns2_linear_args (include/ns2hip.h) and calls ns2_linear.  `fields`: the block's other fields by name
-    (device addresses or ints; what is not named stays zero = feature off)."""
+    (device addresses or ints; what is not named stays zero = feature off).  row_lens = (int32 [B] on the device, frames per utterance)
+    of a ragged TRAINING batch: the same block goes to ns2_linear_lens_zero (include/ns2hip_ragged_skip_train.h) -- hidden row tiles are
+    skipped and stored as zero bits in every output; None (the default): ns2_linear, the same call and bits as ever."""
     args = _lib.LinearArgs(w=w.handle, a_hi=a.hi, a_lo=a.lo, lda=a.ld, M=M, precision=precision, **fields)
+    if row_lens is not None:
+        lens, n = row_lens
+        assert lens.dtype == torch.int32 and lens.is_cuda and lens.is_contiguous() and lens.numel() * n == M
+        import ctypes
+        check(_lib.load().ns2_linear_lens_zero(ctypes.byref(args), lens.data_ptr(), n, _stream()), "ns2_linear_lens_zero")
+        return
     check(_lib.load().ns2_linear(args, _stream()), "ns2_linear")
 
 
 def linear_f32(w: PackedWeight, a: Planes, M: Optional[int] = None, bias=None, resid=None, conv_taps=0, dilation=1,
-               seq_len=0, precision=3, pad_left=-1, act=0, ldo: Optional[int] = None) -> torch.Tensor:
-    """-> fp32 [M, ldo] (ldo defaults to the weight's rows; columns beyond them are NOT written); resid: fp32 rows of any row stride"""
+               seq_len=0, precision=3, pad_left=-1, act=0, ldo: Optional[int] = None, row_lens=None) -> torch.Tensor:
+    """-> fp32 [M, ldo] (ldo defaults to the weight's rows; columns beyond them are NOT written); resid: fp32 rows of any row stride;
+    row_lens: `_linear`'s (a ragged training batch: hidden row tiles come back as zeros)"""
     M = M or a.rows
     out = torch.empty(M, ldo or w.rows, dtype=torch.float32, device=a.device)
-    _linear(w, a, M, precision, conv_taps=conv_taps, dilation=dilation, seq_len=seq_len, pad_left=pad_left, bias=_p(bias), act=act,
+    _linear(w, a, M, precision, row_lens=row_lens, conv_taps=conv_taps, dilation=dilation, seq_len=seq_len, pad_left=pad_left, bias=_p(bias), act=act,
             out_f32=out.data_ptr(), ldo_f=out.shape[1], resid=_p(resid), ldr=resid.stride(0) if resid is not None else 0)
     return out
 
@@ -193,13 +202,13 @@ def conv3_input_ld(cols: int) -> int:
 
 
 def linear_split(w: PackedWeight, a: Planes, bias=None, conv_taps=0, dilation=1, seq_len=0, precision=3, ldo=None, pad_left=-1,
-                 act=0, out_precision=None) -> Planes:
+                 act=0, out_precision=None, row_lens=None) -> Planes:
     """out_precision: write the output planes in the operand format of another precision, e.g. FMT_H8 lines (4) from a precision-2
     product -- what the hybrid plan's FF causal conv does -- or bf16 hi / lo lines (3) for the attention of the mixed training arithmetic"""
     M = a.rows
     ldo = ldo or round_up(w.rows, 32)
     out = _out_planes(M, ldo, a.device, out_precision or precision)
-    _linear(w, a, M, precision, conv_taps=conv_taps, dilation=dilation, seq_len=seq_len, pad_left=pad_left, bias=_p(bias), act=act,
+    _linear(w, a, M, precision, row_lens=row_lens, conv_taps=conv_taps, dilation=dilation, seq_len=seq_len, pad_left=pad_left, bias=_p(bias), act=act,
             out_hi=out.hi, out_lo=out.lo, ldo=ldo, out_precision=out_precision or 0)
     return out
 

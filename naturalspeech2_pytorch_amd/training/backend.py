@@ -58,15 +58,24 @@ class HipBackend:
         """RMSNorm(x) * gamma as fp32 [M, d] (the resampler's final norm, NS2:579: its output is a tensor of the graph, not an operand)"""
         return ops.rmsnorm(x, seq_len=0, gamma=gamma, want_f32=True, precision=3)[1]
 
-    def gemm_f32(self, pw, a, bias=None, resid=None, taps=0, dil=1, seq_len=0, pad_left=-1):
-        """-> fp32 [M, ldo] with ldo = round_up(N, 32); columns >= N are NOT written"""
-        return ops.linear_f32(pw, a, bias=bias, resid=resid, conv_taps=taps, dilation=dil, seq_len=seq_len, precision=self.prec,
-                              pad_left=pad_left, ldo=round_up(pw.rows, 32))
+    @staticmethod
+    def _lens_kw(row_lens):
+        """`row_lens` is handed on only when present: by default the calls below are the calls they were"""
+        return {} if row_lens is None else {"row_lens": row_lens}
 
-    def gemm_split(self, pw, a, bias=None, taps=0, dil=1, seq_len=0, attn=False):
-        """-> operand planes; attn=True: attention operands (q | k | v), bf16 hi / lo lines whatever the GEMM arithmetic"""
+    def gemm_f32(self, pw, a, bias=None, resid=None, taps=0, dil=1, seq_len=0, pad_left=-1, row_lens=None):
+        """-> fp32 [M, ldo] with ldo = round_up(N, 32); columns >= N are NOT written.  row_lens = (int32 [B] on the device, frames per
+        utterance) of a ragged batch whose products skip (include/ns2hip_ragged_skip_train.h): the row tiles hidden behind a length are
+        not computed and come back as zero bits (with a residual too); an anticausal product (pad_left = 0 under taps > 1) needs zeros in
+        the hidden rows of `a`"""
+        return ops.linear_f32(pw, a, bias=bias, resid=resid, conv_taps=taps, dilation=dil, seq_len=seq_len, precision=self.prec,
+                              pad_left=pad_left, ldo=round_up(pw.rows, 32), **self._lens_kw(row_lens))
+
+    def gemm_split(self, pw, a, bias=None, taps=0, dil=1, seq_len=0, attn=False, row_lens=None):
+        """-> operand planes; attn=True: attention operands (q | k | v), bf16 hi / lo lines whatever the GEMM arithmetic; row_lens: as in
+        `gemm_f32` (hidden row tiles of the planes are zero bits)"""
         return ops.linear_split(pw, a, bias=bias, conv_taps=taps, dilation=dil, seq_len=seq_len, precision=self.prec,
-                                out_precision=3 if attn and self.prec != 3 else None)
+                                out_precision=3 if attn and self.prec != 3 else None, **self._lens_kw(row_lens))
 
     def film_gate_fwd(self, h, film, seq_len, d):
         out = torch.empty(h.shape[0], d, dtype=torch.float32, device=h.device)
@@ -330,15 +339,23 @@ class HipBackend:
         """does ns2_wgrad_rows form this gradient from the token-major planes (else: transposed copies + ns2_wgrad)"""
         return (T == 1 or seq_len >= 32) and bool(self.lib.ns2_wgrad_rows_preferred(R, T * round_up(K, 32), M))
 
-    def wgrad_rows(self, dy, x, R, T, K, dil=1, seq_len=0):
+    def wgrad_rows(self, dy, x, R, T, K, dil=1, seq_len=0, row_lens=None):
         """dW [R, K, T] = sum_m dY[m, r] X[m - (T - 1 - t) dil, k] from the ROW planes dy [M, >= R] and x [M, >= round_up(K, 32)] themselves
-        (gemm2.hip TR: LDS transpose reads; the shifts of a conv's taps are row offsets of the loads)"""
+        (gemm2.hip TR: LDS transpose reads; the shifts of a conv's taps are row offsets of the loads).  row_lens = (int32 [B] on the
+        device, frames per utterance): ns2_wgrad_rows_lens -- the 32-token K tiles hidden behind a length are neither fetched nor
+        multiplied; same slots, same order of their sum"""
         Kp = round_up(K, 32)
         assert dy.precision == x.precision == self.prec and dy.rows == x.rows, "wgrad operands must be planes of the same tokens in the backend's GEMM format"
         M = dy.rows
         nbytes = self.lib.ns2_wgrad_workspace_bytes(R, T * Kp, round_up(M, 32))
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dy.device)
         dw = torch.empty(R, K, T, dtype=torch.float32, device=dy.device)
+        if row_lens is not None:
+            lens, n = row_lens
+            assert lens.dtype == torch.int32 and lens.is_cuda and lens.is_contiguous() and lens.numel() * n == M and seq_len in (0, n)
+            check(self.lib.ns2_wgrad_rows_lens(dy.hi, dy.lo, dy.ld, x.hi, x.lo, x.ld, M, R, T, Kp, K, dil, n, dw.data_ptr(), ws.data_ptr(),
+                                               nbytes, self.prec, lens.data_ptr(), _stream()), "ns2_wgrad_rows_lens")
+            return dw
         check(self.lib.ns2_wgrad_rows(dy.hi, dy.lo, dy.ld, x.hi, x.lo, x.ld, M, R, T, Kp, K, dil, seq_len if T > 1 else 0, dw.data_ptr(), ws.data_ptr(),
                                       nbytes, self.prec, _stream()), "ns2_wgrad_rows")
         return dw

@@ -27,20 +27,28 @@ def _shifts(taps, dil):
     return tuple((taps - 1 - t) * dil for t in range(taps)) if taps else (0,)
 
 
-def _grads(bk, dy, C, xp, K, taps=0, dil=1, seq_len=0, need_row=True, need_w=True, need_b=False, pad_left=-1):
+def _rl(lens, seq_len):
+    """the `row_lens=` keyword of the backend's products over the b * n frame rows of a pass that skips (`ragged_skip_training`;
+    include/ns2hip_ragged_skip_train.h): lens = int32 [b] on the device, or None -- then no keyword at all: the same calls as ever"""
+    return {} if lens is None else {"row_lens": (lens, seq_len)}
+
+
+def _grads(bk, dy, C, xp, K, taps=0, dil=1, seq_len=0, need_row=True, need_w=True, need_b=False, pad_left=-1, rl={}):
     """what the backward of y = conv_or_linear(x) (+ b) needs from dy fp32 [M, >= C]: its row planes (the dgrad GEMM's operand), the
     weight gradient dW against xp = the operand planes the forward GEMM read, the bias gradient.  The weight gradient comes
     from the row planes themselves where the kernel can (ns2_wgrad_rows: LDS transpose reads), else through transposed copies
     (narrow gradients: the dim = 128 model).  `pad_left` >= 0 and != taps - 1: a NON-causal conv (SpeechPromptEncoder's Conv1d(k = 9, padding = 4),
     NS2:306-311): tap t read x[n - (pad_left - t) dil], rows shifted in BOTH directions -- the transposed copies take any signed shift
     (tplanes_kernel zero-fills outside the utterance), the row-plane kernel's tap offsets are the causal ones, so this case always goes
-    through the copies.  -> (dy_row or None, dW or None, db or None); dW in the parameter's own shape: [C, K, taps], a Linear's (taps = 0) [C, K]"""
+    through the copies.  `rl`: `_rl(...)` of a skipping pass, handed to the row-plane weight gradient (the transposed route takes no lengths:
+    it adds the exact zeros of dy's hidden rows).  -> (dy_row or None, dW or None, db or None); dW in the parameter's own shape: [C, K, taps],
+    a Linear's (taps = 0) [C, K]"""
     T = max(taps, 1)
     causal = pad_left < 0 or pad_left == taps - 1
     dw = None
     if causal and need_w and bk.wgrad_rows_ok(C, T, K, seq_len, dy.shape[0]):
         row, _, db = bk.grad_prep(dy, C, want_row=True, want_colsum=need_b)
-        dw = bk.wgrad_rows(row, xp, C, T, K, dil, seq_len)
+        dw = bk.wgrad_rows(row, xp, C, T, K, dil, seq_len, **rl)
     else:
         row, dy_t, db = bk.grad_prep(dy, C, want_row=need_row, want_t=need_w, want_colsum=need_b)
         if need_w:
@@ -95,14 +103,17 @@ class GemmFn(torch.autograd.Function):
     padding = pad_left), NS2:306-311): its dgrad is the forward kernel on the tap-flipped weight with pad_left' = k - 1 - pad_left"""
 
     @staticmethod
-    def forward(ctx, x, w, b, resid, seq_len, dil, pad_left=-1):
+    def forward(ctx, x, w, b, resid, seq_len, dil, pad_left=-1, lens=None):
+        """lens: int32 [b] on the device when the rows are the b * seq_len frame rows of a pass that skips (`_rl`), else None"""
         bk = _begin(ctx)
         taps = _taps(w)
         if pad_left == taps - 1 or not taps:
             pad_left = -1
+        assert lens is None or pad_left < 0, "a skipping product is causal or plain in the forward"
         xp = bk.split(x)
         kw = {} if pad_left < 0 else {"pad_left": pad_left}
-        y = bk.gemm_f32(_fwd_pack(bk, w), xp, bias=b, resid=resid, taps=taps, dil=dil, seq_len=seq_len if taps else 0, **kw)
+        ctx.rl = _rl(lens, seq_len)
+        y = bk.gemm_f32(_fwd_pack(bk, w), xp, bias=b, resid=resid, taps=taps, dil=dil, seq_len=seq_len if taps else 0, **kw, **ctx.rl)
         ctx.save_for_backward(w, b)
         ctx.xp, ctx.cfg, ctx.pad_left = xp, (taps, dil, seq_len, x.shape[1], resid is not None), pad_left
         return y[:, :w.shape[0]]
@@ -118,25 +129,26 @@ class GemmFn(torch.autograd.Function):
         need_w, need_b = ctx.needs_input_grad[1], b is not None and ctx.needs_input_grad[2]
         pl = ctx.pad_left
         dy_row, dw, db = _grads(bk, dy, cout, ctx.xp, cin, taps, dil, seq_len, need_row=ctx.needs_input_grad[0], need_w=need_w, need_b=need_b,
-                                pad_left=pl)
+                                pad_left=pl, rl=ctx.rl)
         dx = None
         if ctx.needs_input_grad[0]:
             pl_b = (0 if pl < 0 else taps - 1 - pl) if taps else -1
-            dx = bk.gemm_f32(_bwd_pack(bk, w), dy_row, taps=taps, dil=dil, seq_len=seq_len if taps else 0, pad_left=pl_b)[:, :cin]
-        return dx, *_un(ctx, dw, db), (dy if has_resid else None), None, None, None
+            dx = bk.gemm_f32(_bwd_pack(bk, w), dy_row, taps=taps, dil=dil, seq_len=seq_len if taps else 0, pad_left=pl_b, **ctx.rl)[:, :cin]
+        return dx, *_un(ctx, dw, db), (dy if has_resid else None), None, None, None, None
 
 
 class WavenetBlockFn(torch.autograd.Function):
     """WavenetResBlock (NS2:597-642) without its skip conv: out = tanh(z) sigmoid(z) + res_conv(u), z = conv_dil(u) gamma + beta"""
 
     @staticmethod
-    def forward(ctx, u, film, wc, bc, wr, br, seq_len, dil):
+    def forward(ctx, u, film, wc, bc, wr, br, seq_len, dil, lens=None):
         bk = _begin(ctx)
         d = u.shape[1]
         up = bk.split(u)
-        hc = bk.gemm_f32(_fwd_pack(bk, wc), up, bias=bc, taps=3, dil=dil, seq_len=seq_len)
+        rl = ctx.rl = _rl(lens, seq_len)
+        hc = bk.gemm_f32(_fwd_pack(bk, wc), up, bias=bc, taps=3, dil=dil, seq_len=seq_len, **rl)
         g = bk.film_gate_fwd(hc, film, seq_len, d)
-        out = bk.gemm_f32(_fwd_pack(bk, wr), up, bias=br, resid=g, taps=1, dil=1, seq_len=seq_len)
+        out = bk.gemm_f32(_fwd_pack(bk, wr), up, bias=br, resid=g, taps=1, dil=1, seq_len=seq_len, **rl)
         ctx.save_for_backward(film, wc, wr, hc)
         ctx.up, ctx.cfg = up, (seq_len, dil, d)
         return out[:, :d]
@@ -148,11 +160,12 @@ class WavenetBlockFn(torch.autograd.Function):
         seq_len, dil, d = ctx.cfg
         B = dout.shape[0] // seq_len
         dout = _rowmajor(dout)
-        ng = ctx.needs_input_grad                                           # (u, film, wc, bc, wr, br, -, -)
+        ng = ctx.needs_input_grad                                           # (u, film, wc, bc, wr, br, -, -, -)
+        rl = ctx.rl
         if bk.wgrad_rows_ok(d, 3, d, seq_len, dout.shape[0]) and bk.wgrad_rows_ok(d, 1, d, seq_len, dout.shape[0]):
-            dout_row, dwr, dbr = _grads(bk, dout, d, ctx.up, d, 1, 1, seq_len, need_w=ng[4], need_b=ng[5])
+            dout_row, dwr, dbr = _grads(bk, dout, d, ctx.up, d, 1, 1, seq_len, need_w=ng[4], need_b=ng[5], rl=rl)
             dhc, dfilm = bk.film_gate_bwd(dout, hc, film, B, seq_len, d)
-            dhc_row, dwc, dbc = _grads(bk, dhc, d, ctx.up, d, 3, dil, seq_len, need_w=ng[2], need_b=ng[3])
+            dhc_row, dwc, dbc = _grads(bk, dhc, d, ctx.up, d, 3, dil, seq_len, need_w=ng[2], need_b=ng[3], rl=rl)
         else:                                                               # narrow model: transposed copies, one set for both gradients
             dout_row, dout_t, dbr = bk.grad_prep(dout, d, want_row=True, want_t=ng[4], want_colsum=ng[5])
             dhc, dfilm = bk.film_gate_bwd(dout, hc, film, B, seq_len, d)
@@ -164,9 +177,9 @@ class WavenetBlockFn(torch.autograd.Function):
                     dwc = bk.wgrad(dhc_t, xt, d, 3, d)
                 if ng[4]:
                     dwr = bk.wgrad(dout_t, xt, d, 1, d, row_off=2 * round_up(d, 32))    # res_conv reads the unshifted block (tap 2)
-        du = bk.gemm_f32(_bwd_pack(bk, wc), dhc_row, taps=3, dil=dil, seq_len=seq_len, pad_left=0)
-        du = bk.gemm_f32(_bwd_pack(bk, wr), dout_row, resid=du, taps=1, dil=1, seq_len=seq_len, pad_left=0)
-        return du[:, :d], *_un(ctx, dfilm, dwc, dbc, dwr, dbr), None, None
+        du = bk.gemm_f32(_bwd_pack(bk, wc), dhc_row, taps=3, dil=dil, seq_len=seq_len, pad_left=0, **rl)
+        du = bk.gemm_f32(_bwd_pack(bk, wr), dout_row, resid=du, taps=1, dil=1, seq_len=seq_len, pad_left=0, **rl)
+        return du[:, :d], *_un(ctx, dfilm, dwc, dbc, dwr, dbr), None, None, None
 
 
 class AttnFn(torch.autograd.Function):
@@ -192,25 +205,30 @@ class AttnFn(torch.autograd.Function):
     input gradient is selected away.  (The key-mask backward instantiation gives other last bits than the plain one on the same operands;
     with dropout both the ragged batch and the utterance alone run it.)  Absent by default.
     `head_dim` -- 32 or 128 instead of the heads of 64 (include/ns2hip_head_dim_train.h; `head_dim_training`).  The backend is handed it
-    only when it is not 64, as it is handed `lens` only when there are lengths: same calls, same kernels, same bits by default."""
+    only when it is not 64, as it is handed `lens` only when there are lengths: same calls, same kernels, same bits by default.
+    `row_lens` -- int32 [B] on the device, a pass that skips (`ragged_skip_training`; include/ns2hip_ragged_skip_train.h): the products
+    over the B seq_len frame rows -- q | k | v or the cross attention's q, to_out, their dgrads and row-plane weight gradients -- are
+    handed the lengths (`_rl`); the cross attention's k | v projection, whose rows are the context's, never is.  The attention kernels
+    keep `lens`.  Absent by default, like the others."""
 
     @staticmethod
     def forward(ctx, h, film, ctxt, wq, wkv, wout, seq_len, heads, ctx_len, gamma=None, kmask=None, drop=None, resid=None, lens=None,
-                head_dim=64, masked_rows_zero=False):
+                head_dim=64, masked_rows_zero=False, row_lens=None):
         assert resid is None or (film is None and gamma is None)
         assert lens is None or (ctxt is None and kmask is None and drop is None), "lens: the plain self-attention only"
         bk = _begin(ctx)
         M, d = h.shape
         B, a = M // seq_len, heads * head_dim
         hd = {} if head_dim == 64 else {"head_dim": head_dim}
+        rl = ctx.rl = _rl(row_lens, seq_len)
         xn = _norm_in_front(bk, h, seq_len, film, gamma)
         if ctxt is None:                                                    # self attention: one GEMM for q | k | v
             wqkv = bk.pack(("qkv", id(wq), id(wkv)), (wq, wkv), lambda: torch.cat((wq.detach(), wkv.detach()), 0),
                            parts=[(0, "n", 0, 0), (1, "n", a, 0)])
-            qkv = bk.gemm_split(wqkv, xn, attn=True)
+            qkv = bk.gemm_split(wqkv, xn, attn=True, **rl)
             q, k, v, qc, kc, vc, Nk, cp = qkv, qkv, qkv, 0, a, 2 * a, seq_len, None
         else:
-            q = bk.gemm_split(_fwd_pack(bk, wq), xn, attn=True)
+            q = bk.gemm_split(_fwd_pack(bk, wq), xn, attn=True, **rl)
             cp = bk.split(ctxt)
             kv = bk.gemm_split(_fwd_pack(bk, wkv), cp, attn=True)
             k, v, qc, kc, vc, Nk = kv, kv, 0, 0, a, ctx_len
@@ -221,7 +239,7 @@ class AttnFn(torch.autograd.Function):
             o, lse = bk.attention(q, qc, k, kc, vt, B, heads, seq_len, Nk, **hd)
         else:
             o, lse = bk.attention_masked(q, qc, k, kc, vt, B, heads, seq_len, Nk, kmask=kmask, drop=drop, **hd)
-        y = bk.gemm_f32(_fwd_pack(bk, wout), o, resid=h if resid is None else resid)
+        y = bk.gemm_f32(_fwd_pack(bk, wout), o, resid=h if resid is None else resid, **rl)
         ctx.save_for_backward(h, film, wq, wkv, wout, lse, gamma)
         ctx.pl, ctx.cfg, ctx.md, ctx.lens = (xn, q, k, v, o, cp), (seq_len, heads, Nk, qc, kc, vc, ctxt is not None), (kmask, drop), lens
         ctx.own_resid, ctx.hd = resid is None, hd
@@ -240,6 +258,7 @@ class AttnFn(torch.autograd.Function):
         B, a = M // seq_len, heads * hd.get("head_dim", 64)
         dy = _rowmajor(dy)
         ng = ctx.needs_input_grad                                           # (h, film, ctxt, wq, wkv, wout, ...)
+        rl = ctx.rl
         if ctx.lens is not None:
             def attention_bwd(*args, **kw):
                 bk.attention_bwd(*args, lens=ctx.lens, **hd, **kw)
@@ -249,8 +268,8 @@ class AttnFn(torch.autograd.Function):
         else:
             def attention_bwd(*args, **kw):
                 bk.attention_bwd_masked(*args, kmask=kmask, drop=drop, **hd, **kw)
-        dy_row, dwout, _ = _grads(bk, dy, d, o, a, need_w=ng[5])
-        do = bk.gemm_f32(_bwd_pack(bk, wout), dy_row)                       # [M, a]
+        dy_row, dwout, _ = _grads(bk, dy, d, o, a, need_w=ng[5], rl=rl)
+        do = bk.gemm_f32(_bwd_pack(bk, wout), dy_row, **rl)                 # [M, a]
         delta = bk.attention_delta(do, o, B, heads, seq_len, **hd)
         # (the backward kernels form K^T, Q^T and dO^T inside the CU: LDS transpose reads of the row-major tiles)
         do_row, _, _ = bk.grad_prep(do, a, want_row=True, attn=True)
@@ -260,24 +279,24 @@ class AttnFn(torch.autograd.Function):
                 # dq | dk | dv feed two GEMMs only (the projection's dgrad and wgrad): they leave the attention backward as operand planes
                 g_row = bk.new_planes(M, 3 * a)
                 attention_bwd(q, qc, k, kc, v, vc, do_row, lse, delta, B, heads, seq_len, Nk, planes=(g_row, 0, a, 2 * a))
-                dwqkv = bk.wgrad_rows(g_row, xn, 3 * a, 1, d)[:, :, 0] if need_w else None
+                dwqkv = bk.wgrad_rows(g_row, xn, 3 * a, 1, d, **rl)[:, :, 0] if need_w else None
             else:
                 dqkv = torch.empty(M, 3 * a, dtype=torch.float32, device=h.device)
                 attention_bwd(q, qc, k, kc, v, vc, do_row, lse, delta, B, heads, seq_len, Nk, dq=(dqkv, 0), dkv=(dqkv, a, 2 * a))
-                g_row, dwqkv, _ = _grads(bk, dqkv, 3 * a, xn, d, need_w=need_w)
+                g_row, dwqkv, _ = _grads(bk, dqkv, 3 * a, xn, d, need_w=need_w, rl=rl)
             dwq = dwkv = None
             if need_w:
                 dwq, dwkv = dwqkv[:a], dwqkv[a:]
             wqkv = bk.pack(("qkv_b", id(wq), id(wkv)), (wq, wkv), lambda: torch.cat((wq.detach(), wkv.detach()), 0).t(),
                            parts=[(0, "t", 0, 0), (1, "t", 0, a)])
-            dxn = bk.gemm_f32(wqkv, g_row)
+            dxn = bk.gemm_f32(wqkv, g_row, **rl)
             dctx = None
         else:
             dq = torch.empty(M, a, dtype=torch.float32, device=h.device)
             dkv = torch.empty(B * Nk, 2 * a, dtype=torch.float32, device=h.device)
             attention_bwd(q, qc, k, kc, v, vc, do_row, lse, delta, B, heads, seq_len, Nk, dq=(dq, 0), dkv=(dkv, 0, a))
-            q_row, dwq, _ = _grads(bk, dq, a, xn, d, need_w=ng[3])
-            dxn = bk.gemm_f32(_bwd_pack(bk, wq), q_row)
+            q_row, dwq, _ = _grads(bk, dq, a, xn, d, need_w=ng[3], rl=rl)
+            dxn = bk.gemm_f32(_bwd_pack(bk, wq), q_row, **rl)
             kv_row, dwkv, _ = _grads(bk, dkv, 2 * a, cp, d, need_row=ng[2], need_w=ng[4])
             dctx = bk.gemm_f32(_bwd_pack(bk, wkv), kv_row)[:, :d] if ng[2] else None
         if ctx.own_resid:
@@ -286,12 +305,15 @@ class AttnFn(torch.autograd.Function):
         else:
             dh, dfilm, dgamma, dresid = dxn[:, :d], None, None, dy
         dfilm, dwq, dwkv, dwout, dgamma = _un(ctx, dfilm, dwq, dwkv, dwout, dgamma)
-        return dh, dfilm, dctx, dwq, dwkv, dwout, None, None, None, dgamma, None, None, dresid, None, None, None
+        return dh, dfilm, dctx, dwq, dwkv, dwout, None, None, None, dgamma, None, None, dresid, None, None, None, None
 
 
-def attn_apply(*args, head_dim=64, masked_rows_zero=False):
+def attn_apply(*args, head_dim=64, masked_rows_zero=False, row_lens=None):
     """`AttnFn.apply(*args)`; a head dim other than 64 (`head_dim_training`) is appended behind the optional arguments, 64 leaves the
-    call exactly what it was; `masked_rows_zero` (the ragged conditioning passes) likewise behind the head dim"""
+    call exactly what it was; `masked_rows_zero` (the ragged conditioning passes) likewise behind the head dim, and `row_lens` (a pass
+    that skips, `ragged_skip_training`) behind that"""
+    if row_lens is not None:
+        return AttnFn.apply(*args, *([None] * (14 - len(args))), head_dim, masked_rows_zero, row_lens)
     if masked_rows_zero:
         return AttnFn.apply(*args, *([None] * (14 - len(args))), head_dim, True)
     if head_dim == 64:
@@ -313,15 +335,16 @@ class FeedForwardFn(torch.autograd.Function):
     learned-gamma RMSNorm in front -- the plain Transformer's FeedForward (NS2:1098-1101)"""
 
     @staticmethod
-    def forward(ctx, h, film, w1, b1, wc, bc, w2, b2, seq_len, gamma=None):
+    def forward(ctx, h, film, w1, b1, wc, bc, w2, b2, seq_len, gamma=None, lens=None):
         bk = _begin(ctx)
         M, d = h.shape
         f = w2.shape[1]
+        rl = ctx.rl = _rl(lens, seq_len)
         xn = _norm_in_front(bk, h, seq_len, film, gamma)
-        pre = bk.gemm_f32(_fwd_pack(bk, w1), xn, bias=b1)                   # [M, 2 f]: x | gate
+        pre = bk.gemm_f32(_fwd_pack(bk, w1), xn, bias=b1, **rl)             # [M, 2 f]: x | gate
         hp = bk.geglu_fwd(pre, f)
-        cp = bk.gemm_split(_fwd_pack(bk, wc), hp, bias=bc, taps=3, dil=1, seq_len=seq_len) if wc is not None else hp
-        y = bk.gemm_f32(_fwd_pack(bk, w2), cp, bias=b2, resid=h)
+        cp = bk.gemm_split(_fwd_pack(bk, wc), hp, bias=bc, taps=3, dil=1, seq_len=seq_len, **rl) if wc is not None else hp
+        y = bk.gemm_f32(_fwd_pack(bk, w2), cp, bias=b2, resid=h, **rl)
         ctx.save_for_backward(h, film, w1, wc, w2, pre, gamma)
         ctx.pl, ctx.cfg = (xn, hp, cp), (seq_len, f)
         return y[:, :d]
@@ -336,39 +359,41 @@ class FeedForwardFn(torch.autograd.Function):
         B = M // seq_len
         dy = _rowmajor(dy)
         ng = ctx.needs_input_grad                                           # (h, film, w1, b1, wc, bc, w2, b2, -)
+        rl = ctx.rl
         planes_dc = wc is not None and bk.wgrad_rows_ok(f, 3, f, seq_len, M)
-        dy_row, dw2, db2 = _grads(bk, dy, d, cp, f, need_w=ng[6], need_b=ng[7] or (planes_dc and ng[5]))
+        dy_row, dw2, db2 = _grads(bk, dy, d, cp, f, need_w=ng[6], need_b=ng[7] or (planes_dc and ng[5]), rl=rl)
         dwc = dbc = None
         if planes_dc:
             # dc = dy W2 feeds two GEMMs only (the conv's dgrad and wgrad): it leaves the dgrad GEMM as operand planes and never exists in
             # fp32; the conv's bias gradient, colsum(dy W2), is colsum(dy) W2 -- a [d] x [d, f] product of what the FF-out bias gradient sums anyway
-            dc_row = bk.gemm_split(_bwd_pack(bk, w2), dy_row)
-            dwc = bk.wgrad_rows(dc_row, hp, f, 3, f, 1, seq_len) if ng[4] else None
+            dc_row = bk.gemm_split(_bwd_pack(bk, w2), dy_row, **rl)
+            dwc = bk.wgrad_rows(dc_row, hp, f, 3, f, 1, seq_len, **rl) if ng[4] else None
             dbc = db2 @ w2.detach() if ng[5] else None
             db2 = db2 if ng[7] else None
-            dhh = bk.gemm_f32(_bwd_pack(bk, wc), dc_row, taps=3, dil=1, seq_len=seq_len, pad_left=0)
+            dhh = bk.gemm_f32(_bwd_pack(bk, wc), dc_row, taps=3, dil=1, seq_len=seq_len, pad_left=0, **rl)
         else:
-            dc = bk.gemm_f32(_bwd_pack(bk, w2), dy_row)                     # [M, f]
+            dc = bk.gemm_f32(_bwd_pack(bk, w2), dy_row, **rl)               # [M, f]
             if wc is not None:
-                dc_row, dwc, dbc = _grads(bk, dc, f, hp, f, 3, 1, seq_len, need_w=ng[4], need_b=ng[5])
-                dhh = bk.gemm_f32(_bwd_pack(bk, wc), dc_row, taps=3, dil=1, seq_len=seq_len, pad_left=0)
+                dc_row, dwc, dbc = _grads(bk, dc, f, hp, f, 3, 1, seq_len, need_w=ng[4], need_b=ng[5], rl=rl)
+                dhh = bk.gemm_f32(_bwd_pack(bk, wc), dc_row, taps=3, dil=1, seq_len=seq_len, pad_left=0, **rl)
             else:
                 dhh = dc
         dpre = bk.geglu_bwd(dhh, pre, f)                                    # [M, 2 f]
-        p_row, dw1, db1 = _grads(bk, dpre, 2 * f, xn, d, need_w=ng[2], need_b=ng[3])
-        dxn = bk.gemm_f32(_bwd_pack(bk, w1), p_row)
+        p_row, dw1, db1 = _grads(bk, dpre, 2 * f, xn, d, need_w=ng[2], need_b=ng[3], rl=rl)
+        dxn = bk.gemm_f32(_bwd_pack(bk, w1), p_row, **rl)
         dh, dfilm, dgamma = _norm_in_front_bwd(bk, h, dxn, dy, B, seq_len, film, gamma)
-        return dh, *_un(ctx, dfilm, dw1, db1, dwc, dbc, dw2, db2), None, *_un(ctx, dgamma)
+        return dh, *_un(ctx, dfilm, dw1, db1, dwc, dbc, dw2, db2), None, *_un(ctx, dgamma), None
 
 
 class NormLinearFn(torch.autograd.Function):
     """Linear(RMSNorm(h) * gamma), no bias: `to_pred` (NS2:781-784)"""
 
     @staticmethod
-    def forward(ctx, h, gamma, w, seq_len):
+    def forward(ctx, h, gamma, w, seq_len, lens=None):
         bk = _begin(ctx)
         xn = bk.rmsnorm(h, seq_len, gamma=gamma)
-        y = bk.gemm_f32(_fwd_pack(bk, w), xn)
+        ctx.rl = _rl(lens, seq_len)
+        y = bk.gemm_f32(_fwd_pack(bk, w), xn, **ctx.rl)
         ctx.save_for_backward(h, gamma, w)
         ctx.xn, ctx.seq_len = xn, seq_len
         return y[:, :w.shape[0]]
@@ -379,10 +404,10 @@ class NormLinearFn(torch.autograd.Function):
         h, gamma, w = ctx.saved_tensors
         M, d = h.shape
         dy = _rowmajor(dy)
-        dy_row, dw, _ = _grads(bk, dy, w.shape[0], ctx.xn, d, need_w=ctx.needs_input_grad[2])
-        dxn = bk.gemm_f32(_bwd_pack(bk, w), dy_row)
+        dy_row, dw, _ = _grads(bk, dy, w.shape[0], ctx.xn, d, need_w=ctx.needs_input_grad[2], rl=ctx.rl)
+        dxn = bk.gemm_f32(_bwd_pack(bk, w), dy_row, **ctx.rl)
         dh, _, dgamma = bk.rmsnorm_bwd(h, dxn, M // ctx.seq_len, ctx.seq_len, d, gamma=gamma)
-        return dh, *_un(ctx, dgamma, dw), None
+        return dh, *_un(ctx, dgamma, dw), None, None
 
 
 class RmsNormFn(torch.autograd.Function):

@@ -59,7 +59,10 @@ def model_forward_train(m, x, times, prompt=None, cond=None, cond_drop_prob=None
     `prompt_lens` (not in the reference; `ragged_conditioning`): prompt rows per utterance, integer [b] (include/ns2hip_ragged_cond_train.h;
     DESIGN §9).  The prompt rows behind a length are selected to 0 at the entry, the mean of to_prompt_cond is a masked sum over rows
     [0, prompt_lens[i]) divided by the clamped length, and the perceiver resampler's attentions run under the key mask
-    [0, Lm + prompt_lens[i]) of cat(latents, prompt), all formed on the device.  With and without `lens`."""
+    [0, Lm + prompt_lens[i]) of cat(latents, prompt), all formed on the device.  With and without `lens`.
+    `m.ragged_skip_training` (include/ns2hip_ragged_skip_train.h): with `lens` and n % 256 == 0 the products over the b n frame
+    rows -- forward, dgrad, row-plane weight gradient -- are handed the lengths and skip the 256-row tiles hidden behind them, writing
+    zeros there; decided here, once per pass.  Same loss, rows and gradients, bit for bit."""
     tp = getattr(m, "train_precision", "exact")
     assert tp in TRAIN_PRECISIONS, f"train_precision must be one of {sorted(TRAIN_PRECISIONS)}"
     with training_pass(TRAIN_PRECISIONS[tp], x) as p:
@@ -70,6 +73,8 @@ def model_forward_train(m, x, times, prompt=None, cond=None, cond_drop_prob=None
             out = _forward_train(m, x, times, prompt, cond, cond_drop_prob, **pl)
         else:
             ln, keep = _lens_and_mask(lens, x.shape[0], x.shape[1], x.device)
+            if getattr(m, "ragged_skip_training", False) and x.shape[1] % 256 == 0:
+                pl["skip"] = ln
             out = _keep(_forward_train(m, x, times, prompt, cond, cond_drop_prob, ln, keep, **pl), keep)
         if p.scale is not None:
             m._last_loss_scale = p.scale             # (inspection / tests: the scale the last backward chose)
@@ -77,8 +82,10 @@ def model_forward_train(m, x, times, prompt=None, cond=None, cond_drop_prob=None
         return out
 
 
-def _forward_train(m, x, times, prompt, cond, cond_drop_prob, lens=None, keep=None, prompt_keep=None):
-    """lens / keep: `_lens_and_mask` of a ragged batch, or neither; prompt_keep: the bool [b, n_p, 1] of `_lens_and_mask(prompt_lens)`, or None"""
+def _forward_train(m, x, times, prompt, cond, cond_drop_prob, lens=None, keep=None, prompt_keep=None, skip=None):
+    """lens / keep: `_lens_and_mask` of a ragged batch, or neither; prompt_keep: the bool [b, n_p, 1] of `_lens_and_mask(prompt_lens)`, or None;
+    skip: `lens` again when the products over the b n frame rows skip their hidden row tiles (`ragged_skip_training`), else None -- then
+    every call below is the call it was.  The resampler, cond_to_model_dim and the cross attention's k | v are not frame-row products."""
     b, n, d = x.shape
     M = b * n
     p = m.cond_drop_prob if cond_drop_prob is None else cond_drop_prob
@@ -149,20 +156,21 @@ def _forward_train(m, x, times, prompt, cond, cond_drop_prob, lens=None, keep=No
         f = films.get(id(lin))
         return f if f is not None else _lin(lin, t)
 
+    sk = () if skip is None else (skip,)                                     # the trailing `lens` of the Functions, only when present
     wn = m.wavenet
-    h0 = GemmFn.apply(h, wn.init_conv.weight, wn.init_conv.bias, None, n, 1)
+    h0 = GemmFn.apply(h, wn.init_conv.weight, wn.init_conv.bias, None, n, 1, *((-1,) + sk if sk else ()))
     cols = [h0] * m._hip_cfg["wavenet_layers"]
-    skip = None
+    acc = None
     for st in wn.stacks:
         nxt = []
         for i, blk in enumerate(st.blocks):
             z = WavenetBlockFn.apply(_c(cols[i]), film_of(blk.to_time_cond), blk.conv.weight, blk.conv.bias, blk.res_conv.weight,
-                                     blk.res_conv.bias, n, 2 ** i)
+                                     blk.res_conv.bias, n, 2 ** i, *sk)
             nxt.append(z)
             if blk.skip_conv is not None:                                    # sum of the skip convs (NS2:685-686, 725) as a chain of residuals
-                skip = GemmFn.apply(_c(z), blk.skip_conv.weight, blk.skip_conv.bias, skip if skip is None else _c(skip), n, 1)
+                acc = GemmFn.apply(_c(z), blk.skip_conv.weight, blk.skip_conv.bias, acc if acc is None else _c(acc), n, 1, *((-1,) + sk if sk else ()))
         cols = nxt
-    h = GemmFn.apply(_c(skip), wn.final_conv.weight, wn.final_conv.bias, None, n, 1)
+    h = GemmFn.apply(_c(acc), wn.final_conv.weight, wn.final_conv.bias, None, n, 1, *((-1,) + sk if sk else ()))
     for layer in m.transformer.layers:
         a1 = getattr(layer, "1")
         if lens is None:
@@ -170,16 +178,17 @@ def _forward_train(m, x, times, prompt, cond, cond_drop_prob, lens=None, keep=No
                            head_dim=hd)
         else:
             h = attn_apply(_c(h), film_of(getattr(layer, "0").to_gamma_beta), None, a1.to_q.weight, a1.to_kv.weight, a1.to_out.weight, n, heads, 0,
-                           None, None, None, None, lens, head_dim=hd)
+                           None, None, None, None, lens, head_dim=hd, row_lens=skip)
         if m.condition_on_prompt:
             a3 = getattr(layer, "3")
             h = attn_apply(_c(h), film_of(getattr(layer, "2").to_gamma_beta), c2, a3.to_q.weight, a3.to_kv.weight, a3.to_out.weight, n,
-                           heads, c.shape[1], head_dim=hd)
+                           heads, c.shape[1], head_dim=hd, row_lens=skip)
         ff = getattr(layer, "5")
         l1, cv, l2 = getattr(ff, "0"), getattr(getattr(ff, "2"), "1"), getattr(ff, "3")
-        h = FeedForwardFn.apply(_c(h), film_of(getattr(layer, "4").to_gamma_beta), l1.weight, l1.bias, cv.weight, cv.bias, l2.weight, l2.bias, n)
+        h = FeedForwardFn.apply(_c(h), film_of(getattr(layer, "4").to_gamma_beta), l1.weight, l1.bias, cv.weight, cv.bias, l2.weight, l2.bias, n,
+                                *((None,) + sk if sk else ()))
     tp = m.transformer.to_pred
-    out = NormLinearFn.apply(_c(h), getattr(tp, "0").gamma, getattr(tp, "1").weight, n)
+    out = NormLinearFn.apply(_c(h), getattr(tp, "0").gamma, getattr(tp, "1").weight, n, *sk)
     return out.reshape(b, n, d).to(x.dtype)
 
 
