@@ -121,6 +121,14 @@ int ns2_join_f32(const uint16_t* hi, const uint16_t* lo, int ld, float* out, int
  *   GEGLU      selected by the weight having been packed with geglu = 1: FeedForward's first half GEGLU(Linear(x)) (NS2:1004-1007, 1021).
  *              bias is then the packed bias of ns2_geglu_pack_bias and required; out planes [M, ldo] with ldo = round_up(f, 32); excludes
  *              conv_taps, act, out_f32, vt_hi, out_precision.
+ * Destinations (tests/test_gemm_dest_gpu.py pins every line):
+ *   alignment  none beyond the element's own: any out_f32 / resid address, any ldo_f / ldr >= N; planes: ldo even (interleaved lines:
+ *              a multiple of 32) and out_lo == out_hi + 32; vt_ld a multiple of 8 (interleaved V^T lines: of 32).  A 16-byte aligned
+ *              base with ldo_f % 4 == 0 (resid, ldr the same) / ldo % 32 == 0 only selects the faster stores: the bits are the same.
+ *   written    rows < M; fp32: columns < N; planes: columns < ldo, zero bits from N on -- so ldo <= round_up(N, 128), no kernel's column
+ *              tiles reach further and a larger ldo is refused (ns2_wavenet_block: the same); q | k | v: columns < split_col of out
+ *              (ldo >= split_col, a smaller one is refused: rows would overlap) and keys < seq_len of every vt row.
+ *   never      fp32 columns >= N (up to ldo_f), rows >= M, q | k columns >= split_col, V^T keys >= seq_len (up to vt_ld), resid.
  * Every refusal is an NS2_ERR_ARG whose message starts "ns2_linear:" and names the field, made before any device call. */
 typedef struct {
   const ns2_weight* w;

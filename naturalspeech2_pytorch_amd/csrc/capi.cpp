@@ -168,6 +168,8 @@ static int linear_args_from(const ns2_linear_args* p, GemmArgs* out) {
   ARGCHK(!qkv || !(p->bias || p->act || p->conv_taps || p->out_precision), "ns2_linear: vt_hi (the fused q | k | v) excludes bias, act, conv_taps and out_precision");
   ARGCHK(!qkv || (p->seq_len > 0 && p->M % p->seq_len == 0 && (p->split_col % 32) == 0 && p->vt_ld >= p->seq_len && (p->vt_ld & 7) == 0),
          "ns2_linear: bad q | k | v shapes (seq_len divides M, split_col a multiple of 32, vt_ld >= seq_len and a multiple of 8)");
+  ARGCHK(!qkv || p->ldo >= p->split_col, "ns2_linear: ldo smaller than split_col (the q | k rows would overlap)");
+  ARGCHK(!qkv || !p->vt_lo || (p->vt_ld & 31) == 0, "ns2_linear: vt_ld must be a multiple of 32 with vt_lo (interleaved lines of 32 keys; the last line of a row would overlap the next row)");
   ARGCHK(!planes || qkv || (p->ldo & 1) == 0, "ns2_linear: ldo must be even");
   const ns2_weight& w = *p->w;
   // the weight's element format must be the one the requested precision multiplies in (fp16 for 2, bf16 planes for 1 / 3)
@@ -176,6 +178,8 @@ static int linear_args_from(const ns2_linear_args* p, GemmArgs* out) {
          "ns2_linear: the packing of w does not match conv_taps (a weight with extra1x1 belongs to ns2_wavenet_block)");
   ARGCHK(p->lda >= w.cols_p, "ns2_linear: lda smaller than the padded K of w");
   ARGCHK(!qkv || p->split_col < w.w.N, "ns2_linear: split_col must lie below the rows of w");
+  // no route's column tiles reach further (128 columns per tile on the 128 x 128 kernel and the split-K finish): the zeros of [N, ldo) would stay unwritten
+  ARGCHK(!planes || qkv || w.geglu || p->ldo <= (w.w.N + 127) / 128 * 128, "ns2_linear: ldo larger than the rows of w rounded up to 128 (the columns beyond would stay unwritten)");
   GemmArgs& g = *out;
   g = gemm_args(w.w, p->a_hi, p->a_lo, p->lda, p->M);
   g.bias = p->bias;
@@ -265,6 +269,7 @@ static int wavenet_block_impl(const ns2_weight* w, const uint16_t* a_hi, const u
   ARGCHK(w && a_hi && out_hi && conv_bias && res_bias && film && prec_ok(precision), "ns2_wavenet_block: bad arguments");
   ARGCHK(operand_fmt(precision) == w->w.fmt, "ns2_wavenet_block: weight was packed for a different precision");
   ARGCHK(w->taps == 3 && w->has_extra && seq_len > 0, "ns2_wavenet_block: weight must be packed with taps=3 and extra1x1");
+  ARGCHK(ldo <= (w->w.N + 127) / 128 * 128, "ns2_wavenet_block: ldo larger than the channels rounded up to 128 (the columns beyond would stay unwritten)");
   GemmArgs g = gemm_args(w->w, a_hi, a_lo, lda, M);
   set_wavenet(g, w->w, dilation, seq_len, precision, p1_half);
   g.bias = conv_bias; g.bias2 = res_bias; g.film = film; g.film_ld = film_ld;

@@ -1159,6 +1159,8 @@ static hipError_t resolve_gemm_args(GemmArgs& g, int precision) {
   if (g.M <= 0 || g.N <= 0 || g.nkt <= 0 || g.kt_per_tap <= 0 || (g.nkt % g.kt_per_tap)) return hipErrorInvalidValue;
   if (!planes_ok(g.a_hi, g.a_lo) || !planes_ok(g.w_hi, g.w_lo) || !planes_ok(g.out_hi, g.out_lo) || !planes_ok(g.vt_hi, g.vt_lo))
     return hipErrorInvalidValue;
+  // "zero beyond N" reaches as far as the column tiles of every route do: the 128-wide tiles of gemm_kernel and the split-K finish
+  if ((g.epi == EPI_SPLIT || g.epi == EPI_WAVENET) && g.out_ncols > (g.N + 127) / 128 * 128) return hipErrorInvalidValue;
   return hipSuccess;
 }
 

@@ -6,7 +6,8 @@
 //   gemm_epi_dispatch.h  wave_tile_epilogue: the one place that decides between the two.
 // A wave owns MI x 2 accumulator tiles of v_mfma_f32_32x32x16_bf16 (C layout: col = lane & 31, row = acc_row(r, lane >> 5)),
 // rows [row_base, row_base + 32 * MI), cols [col_base, col_base + 64).  A row's stored bits do not depend on the path its tile took
-// (tests/test_kernels_gpu.py, test_epilogue_paths_store_identical_bits).
+// (tests/test_kernels_gpu.py, test_epilogue_paths_store_identical_bits), nor on the alignment or the strides of its destination, and no
+// path stores outside the rectangle the call owns (tests/test_gemm_dest_gpu.py: sentinel arenas, every route).
 #pragma once
 #include "ns2_common.h"
 #include "ns2_kernels.h"

@@ -56,6 +56,20 @@ def test_linear_blocks_on_real_weights_refusals_and_the_zeroed_block_is_the_plai
     assert refused(block(geglu, bias=gbias.data_ptr(), **but(to_planes, ldo=32)), "ldo must be round_up(f, 32)")
     assert refused(block(lin, **but(to_qkv, split_col=48)), "q | k | v shapes")
     assert refused(block(lin, **but(to_qkv, split_col=64, ldo=64)), "split_col must lie below")
+    # ---- destinations no kernel covers (tests/test_gemm_dest_gpu.py): q | k rows that overlap, interleaved V^T lines that overlap, plane
+    # columns beyond the last column tile of the 128 x 128 kernel and the split-K finish (also on ns2_wavenet_block)
+    assert refused(block(lin, **but(to_qkv, ldo=0)), "ldo smaller than split_col")
+    assert refused(block(lin, **but(to_qkv, vt_ld=40)), "vt_ld must be a multiple of 32 with vt_lo")
+    assert refused(block(lin, **but(to_planes, ldo=160)), "ldo larger than the rows of w rounded up to 128")
+    wide = ops.empty_planes(M, 160, DEV, zero=True)
+    assert refused(block(lin, out_hi=wide.hi, out_lo=wide.lo, ldo=160), "ldo larger than")
+    wn = ops.PackedWeight(rnd(64, K, 3), extra1x1=rnd(64, K, 1))
+    cb, film = rnd(64), rnd(M // seq_len, 128)
+    rc = lib.ns2_wavenet_block(wn.handle, a.hi, a.lo, a.ld, M, seq_len, 1, cb.data_ptr(), cb.data_ptr(), film.data_ptr(), 128, wide.hi, wide.lo, 160, 3, stream)
+    msg = (lib.ns2_last_error() or b"").decode()
+    assert rc != 0 and msg.startswith("ns2_wavenet_block:") and "ldo larger than" in msg
+    torch.cuda.synchronize()
+    assert not bool(wide.buf.view(torch.int16).any())                                      # refused before any launch: nothing was written
     # ---- combinations no old entry point offered
     assert refused(block(lin, bias=gbias.data_ptr(), **to_qkv), "vt_hi (the fused q | k | v) excludes bias")
     assert refused(block(lin, out_precision=3, **to_f32), "out_precision need out_hi")
