@@ -3,7 +3,8 @@ include/ns2hip_pitch.h, the pitch extractor, include/ns2hip_ragged.h, ragged bat
 and text, include/ns2hip_ragged_train.h, ragged training batches, include/ns2hip_head_dim_train.h, training at head dims 32 and 128, and
 include/ns2hip_ragged_audio.h, ragged raw audio, include/ns2hip_fold.h, the feed-forward fold, and include/ns2hip_ragged_cond_train.h,
 ragged text and prompts in training, include/ns2hip_ragged_skip.h, skipping in a ragged sampling batch, and
-include/ns2hip_ragged_skip_train.h, skipping in a ragged training batch, each into tables of its own) is parsed once, at import.
+include/ns2hip_ragged_skip_train.h, skipping in a ragged training batch, and include/ns2hip_tail_fold.h, the Wavenet tail fold and the
+wide RMSNorm kernel, each into tables of its own) is parsed once, at import.
 
 The HIP library is the product: importing this module FAILS LOUDLY when the header or the shared object is missing or the
 library does not export the full ABI -- there is no CPU / PyTorch fallback for the hot path.
@@ -40,6 +41,7 @@ FOLD_HEADER_PATH = os.path.join(_HERE, "..", "include", "ns2hip_fold.h")   # the
 RAGGED_COND_TRAIN_HEADER_PATH = os.path.join(_HERE, "..", "include", "ns2hip_ragged_cond_train.h")   # lengths through the conditioning's training pass: likewise
 RAGGED_SKIP_HEADER_PATH = os.path.join(_HERE, "..", "include", "ns2hip_ragged_skip.h")   # skipping the hidden row tiles of a ragged sampling batch: likewise
 RAGGED_SKIP_TRAIN_HEADER_PATH = os.path.join(_HERE, "..", "include", "ns2hip_ragged_skip_train.h")   # ... of a ragged training batch: likewise
+TAIL_FOLD_HEADER_PATH = os.path.join(_HERE, "..", "include", "ns2hip_tail_fold.h")   # the Wavenet tail fold, the wide RMSNorm kernel: likewise
 
 
 class Ns2Error(RuntimeError):
@@ -178,6 +180,11 @@ if not os.path.exists(RAGGED_SKIP_TRAIN_HEADER_PATH):
 with open(RAGGED_SKIP_TRAIN_HEADER_PATH) as _f:                  # (ns2_linear_args: c_void_p here too -- pass ctypes.byref(block))
     _, _, RAGGED_SKIP_TRAIN_SIGNATURES = parse_header(_f.read())
 
+if not os.path.exists(TAIL_FOLD_HEADER_PATH):
+    raise Ns2Error(f"{TAIL_FOLD_HEADER_PATH} not found: the binding is derived from the header, it ships with the package's source tree")
+with open(TAIL_FOLD_HEADER_PATH) as _f:
+    _, _, TAIL_FOLD_SIGNATURES = parse_header(_f.read())
+
 _lib = None
 
 
@@ -192,7 +199,8 @@ def load():
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in {**SIGNATURES, **OPTIM_SIGNATURES, **PITCH_SIGNATURES, **RAGGED_SIGNATURES, **FRONT_SIGNATURES,
                               **RAGGED_TRAIN_SIGNATURES, **HEAD_DIM_TRAIN_SIGNATURES, **RAGGED_AUDIO_SIGNATURES, **FOLD_SIGNATURES,
-                              **RAGGED_COND_TRAIN_SIGNATURES, **RAGGED_SKIP_SIGNATURES, **RAGGED_SKIP_TRAIN_SIGNATURES}.items():
+                              **RAGGED_COND_TRAIN_SIGNATURES, **RAGGED_SKIP_SIGNATURES, **RAGGED_SKIP_TRAIN_SIGNATURES,
+                              **TAIL_FOLD_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -267,3 +275,8 @@ def ragged_skip_header_symbols():
 def ragged_skip_train_header_symbols():
     """Symbols declared in include/ns2hip_ragged_skip_train.h"""
     return sorted(RAGGED_SKIP_TRAIN_SIGNATURES)
+
+
+def tail_fold_header_symbols():
+    """Symbols declared in include/ns2hip_tail_fold.h"""
+    return sorted(TAIL_FOLD_SIGNATURES)

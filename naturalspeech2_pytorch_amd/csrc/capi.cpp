@@ -10,6 +10,7 @@
 
 #include "../../include/ns2hip_pitch.h"
 #include "../../include/ns2hip_fold.h"
+#include "../../include/ns2hip_tail_fold.h"
 #include "../../include/ns2hip_ragged.h"
 #include "../../include/ns2hip_ragged_skip.h"
 #include "../../include/ns2hip_ragged_skip_train.h"
@@ -55,7 +56,7 @@ using namespace ns2;
 static inline int prec_ok(int p) { return p >= 1 && p <= 4; }
 
 extern "C" const char* ns2_last_error(void) { return g_err; }
-extern "C" int ns2_version(void) { return 124; }   // 124: the feed-forward fold (include/ns2hip_fold.h): ns2_ff_fold, ns2_debug_force_fold, the FF conv kernel writes fp32; 123: the RVQ cross-entropy of the training loss: ns2_rvq_ce (+ _workspace_bytes); 122: training of the Aligner: ns2_relu_fwd / _bwd, ns2_align_attn_bwd (+ _workspace_bytes), ns2_align_losses_fwd / _bwd (+ _workspace_bytes); 121: two utterance chains: ns2_debug_force_chains / _chains_last / _chain_rule, ns2_model_profile_end counts logical products; 120: one argument block per Linear / Conv1d product: ns2_linear(ns2_linear_args) replaces ns2_linear_f32 / _split / _split_as / _geglu / _qkv; 119: one argument block per attention direction: ns2_attention_fwd(ns2_attn_args) replaces ns2_attention / _hd / _lse / _lse_masked, ns2_attn_bwd_args carries the mask and dropout of the removed bwd_masked entry; 118: ns2_debug_force_attention, ns2_debug_attention_fast_launches (attn_fast_kernel.h); 117: the range-guard counters register themselves: ns2_saturation_counters / _counter_name / _peek replace ns2_saturation_peek_async / _peek_train_async; 116: ns2_groupnorm_silu, ns2_length_regulate(_totals), ns2_row_dot (duration_pitch.hip); 115: ns2_weights_retile; 114: ns2_attention_hd (head dims 32 / 64 / 128), ns2_model_create takes dim_head 32 / 128; 113: ns2_weight_tile_conv3 + ns2_conv3_input_ld (the dedicated FF causal conv kernel, ffconv_kernel.h), ns2_weight_tile_linear (gemm3_kernel.h), ns2_weight_tile_wavenet (wavenet3_kernel.h), ns2_debug_force_gemm(4 / 5); 112: ns2_seanet_resblock_narrow; 111: training entry points take a precision (3 = bf16 x3, 4 = mixed on FMT_H8 lines), ns2_linear_split_as; 110: backward pass (capi_train.cpp: ns2_wgrad, ns2_attention_bwd, ...), ns2_weight_update; 109: ns2_seanet_conv_narrow; 108: ns2_seanet_prep2; 107: ns2_lstm2 (two LSTM layers, one launch); 106: ns2_saturation_peek_async; 105: ns2_lstm_layer takes the scratch size (persistent recurrence); 104: model precision 5 (per-site plan); 103: precision 2 / 4 at op level, caller-owned skinny-linear scratch
+extern "C" int ns2_version(void) { return 125; }   // 125: the Wavenet tail fold and the wide RMSNorm kernel (include/ns2hip_tail_fold.h): ns2_tail_fold, ns2_debug_force_tail_fold, ns2_debug_force_norm, ns2_debug_norm_last; 124: the feed-forward fold (include/ns2hip_fold.h): ns2_ff_fold, ns2_debug_force_fold, the FF conv kernel writes fp32; 123: the RVQ cross-entropy of the training loss: ns2_rvq_ce (+ _workspace_bytes); 122: training of the Aligner: ns2_relu_fwd / _bwd, ns2_align_attn_bwd (+ _workspace_bytes), ns2_align_losses_fwd / _bwd (+ _workspace_bytes); 121: two utterance chains: ns2_debug_force_chains / _chains_last / _chain_rule, ns2_model_profile_end counts logical products; 120: one argument block per Linear / Conv1d product: ns2_linear(ns2_linear_args) replaces ns2_linear_f32 / _split / _split_as / _geglu / _qkv; 119: one argument block per attention direction: ns2_attention_fwd(ns2_attn_args) replaces ns2_attention / _hd / _lse / _lse_masked, ns2_attn_bwd_args carries the mask and dropout of the removed bwd_masked entry; 118: ns2_debug_force_attention, ns2_debug_attention_fast_launches (attn_fast_kernel.h); 117: the range-guard counters register themselves: ns2_saturation_counters / _counter_name / _peek replace ns2_saturation_peek_async / _peek_train_async; 116: ns2_groupnorm_silu, ns2_length_regulate(_totals), ns2_row_dot (duration_pitch.hip); 115: ns2_weights_retile; 114: ns2_attention_hd (head dims 32 / 64 / 128), ns2_model_create takes dim_head 32 / 128; 113: ns2_weight_tile_conv3 + ns2_conv3_input_ld (the dedicated FF causal conv kernel, ffconv_kernel.h), ns2_weight_tile_linear (gemm3_kernel.h), ns2_weight_tile_wavenet (wavenet3_kernel.h), ns2_debug_force_gemm(4 / 5); 112: ns2_seanet_resblock_narrow; 111: training entry points take a precision (3 = bf16 x3, 4 = mixed on FMT_H8 lines), ns2_linear_split_as; 110: backward pass (capi_train.cpp: ns2_wgrad, ns2_attention_bwd, ...), ns2_weight_update; 109: ns2_seanet_conv_narrow; 108: ns2_seanet_prep2; 107: ns2_lstm2 (two LSTM layers, one launch); 106: ns2_saturation_peek_async; 105: ns2_lstm_layer takes the scratch size (persistent recurrence); 104: model precision 5 (per-site plan); 103: precision 2 / 4 at op level, caller-owned skinny-linear scratch
 extern "C" int ns2_debug_force_gemm(int kernel) {
   ARGCHK(kernel >= 0 && kernel <= 5, "ns2_debug_force_gemm: 0 auto, 1 = 128x128 kernel, 2 = 256x256 kernel, 3 = auto without split-K, 4 = auto without the dedicated kernels (FF conv, lean linear, lean Wavenet), 5 = auto without split-K, the dedicated kernels whenever eligible");
   force_gemm_kernel(kernel);
@@ -260,6 +261,18 @@ extern "C" int ns2_ff_fold(const float* w_out, const float* w_conv, const float*
   HIPRET(launch_ff_fold(w_out, w_conv, b_conv, b_out, dim, f, w_fold, b_fold, (hipStream_t)stream));
   return NS2_OK;
 }
+extern "C" int ns2_tail_fold(const float* w_final, const float* w_skip, const float* b_skip, const float* b_final, int dim, int layers,
+                             float* w_fold, float* b_fold, void* stream) {
+  ARGCHK(w_final && w_skip && b_skip && w_fold && b_fold && dim > 0 && layers > 0, "ns2_tail_fold: bad arguments");
+  HIPRET(launch_tail_fold(w_final, w_skip, b_skip, b_final, dim, layers, w_fold, b_fold, (hipStream_t)stream));
+  return NS2_OK;
+}
+extern "C" int ns2_debug_force_norm(int kernel) {
+  ARGCHK(kernel == 0 || kernel == 1, "ns2_debug_force_norm: 0 = by shape, 1 = rmsnorm_kernel for every call (never rmsnorm_wide_kernel)");
+  force_norm_kernel(kernel);
+  return NS2_OK;
+}
+extern "C" int ns2_debug_norm_last(void) { return norm_kernel_last(); }
 static int wavenet_block_impl(const ns2_weight* w, const uint16_t* a_hi, const uint16_t* a_lo, int lda, int M, int seq_len,
                               int dilation, const float* conv_bias, const float* res_bias, const float* film, int film_ld,
                               uint16_t* out_hi, uint16_t* out_lo, int ldo, int precision, const int* row_lens, void* stream) {

@@ -1,6 +1,8 @@
 // HBM-bound and tiny kernels of the NaturalSpeech2 denoiser on gfx950: RMSNorm (wavefront reduction), fp32 ->
 // split-plane conversion, time embedding, the batched skinny conditioning projections, DDIM update, CFG mix,
 // weight packing.  All vectorised to 16 B per lane where the layout allows (guide G13).
+#include <atomic>
+#include <cstdlib>
 #include "ns2_common.h"
 #include "ns2_kernels.h"
 
@@ -67,10 +69,188 @@ __global__ __launch_bounds__(256) void rmsnorm_kernel(const NormArgs a) {
   }
 }
 
+// The hot case (a step's 25 norms: d = 256 * CH <= 1024, ldo == d, FMT_H8 / dense IEEE-half / interleaved bf16 planes, 16-byte aligned
+// operands, an utterance made of whole 16-row tiles) with the memory side rebuilt and the arithmetic of rmsnorm_kernel kept, operation for
+// operation: the lane-to-column map of the loads, the per-lane sum of squares over j, wave_sum, inv, scale, gamma, then t * gg + bb -- the
+// same bits.  A wave owns WIDE_ROWS rows and issues all their loads before the first reduction (and the next tile's before this tile's
+// stores); a workgroup's (gamma_t, beta_t) row is loaded once per tile; a row's output is assembled in the wave's own LDS region in its
+// memory layout and leaves as 16 bytes per lane, 1 KB of whole 128-byte lines per wave-instruction (the half part and the correction
+// parts of an FMT_H8 line together).  LDS is in order for one wave, so write -> read -> next row's write need no barrier, only the
+// compiler kept from reordering them (wave_lds_order).  The grid is sized for the chip and strides over the tiles.
+constexpr int WIDE_ROWS = 4;                    // rows per wave
+constexpr int WIDE_TILE = 4 * WIDE_ROWS;        // rows per workgroup (and per iteration)
+NS2_DEVINL void wave_lds_order() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+template <int CH, int FMT, bool GAMMA, bool COND, bool OUTF>
+__global__ __launch_bounds__(256) void rmsnorm_wide_kernel(const NormArgs a, const int ntiles) {
+  constexpr bool IL = FMT != FMT_F16;                       // interleaved 128-byte lines (FMT_H8, bf16 hi | lo)
+  constexpr int ROWB = CH * 256 * (IL ? 4 : 2);             // bytes of one output row
+  __shared__ __attribute__((aligned(16))) unsigned char stage_all[4 * ROWB];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  unsigned char* const stage = stage_all + wave * ROWB;
+  const float scale = sqrtf((float)a.d);
+  float4 gm[CH];
+  if constexpr (GAMMA) {
+#pragma unroll
+    for (int j = 0; j < CH; ++j) gm[j] = *reinterpret_cast<const float4*>(a.gamma + lane * 4 + 256 * j);
+  }
+  auto load_tile = [&](int tile, float4 (&v)[WIDE_ROWS][CH]) {
+#pragma unroll
+    for (int r = 0; r < WIDE_ROWS; ++r) {
+      long row = (long)tile * WIDE_TILE + wave * WIDE_ROWS + r;
+      if (row >= a.M) row = a.M - 1;                        // (rows past M: loaded again, never stored)
+      const float* x = a.x + row * a.ldx;
+#pragma unroll
+      for (int j = 0; j < CH; ++j) v[r][j] = *reinterpret_cast<const float4*>(x + lane * 4 + 256 * j);
+    }
+  };
+  float4 v[WIDE_ROWS][CH];
+  int tile = blockIdx.x;
+  if (tile < ntiles) load_tile(tile, v);
+  for (; tile < ntiles; tile += gridDim.x) {
+    const long row0 = (long)tile * WIDE_TILE + wave * WIDE_ROWS;
+    float4 gg[CH], bb[CH];
+    if constexpr (COND) {                                   // the tile lies inside one utterance (launch_rmsnorm's routing)
+      const int b = a.seq_len > 0 ? (int)(((long)tile * WIDE_TILE) / a.seq_len) : 0;
+      const float* gc = a.cond + (long)b * a.cond_ld;
+#pragma unroll
+      for (int j = 0; j < CH; ++j) {
+        gg[j] = *reinterpret_cast<const float4*>(gc + lane * 4 + 256 * j);
+        bb[j] = *reinterpret_cast<const float4*>(gc + a.d + lane * 4 + 256 * j);
+      }
+    }
+    float inv[WIDE_ROWS];
+#pragma unroll
+    for (int r = 0; r < WIDE_ROWS; ++r) {
+      float ss = 0.f;
+#pragma unroll
+      for (int j = 0; j < CH; ++j) ss += v[r][j].x * v[r][j].x + v[r][j].y * v[r][j].y + v[r][j].z * v[r][j].z + v[r][j].w * v[r][j].w;
+      ss = wave_sum(ss);
+      inv[r] = 1.0f / fmaxf(sqrtf(ss), 1e-12f);
+    }
+    float4 nv[WIDE_ROWS][CH];
+    const int next = tile + gridDim.x;
+    if (next < ntiles) load_tile(next, nv);
+#pragma unroll
+    for (int r = 0; r < WIDE_ROWS; ++r) {
+      const long row = row0 + r;
+      if (row >= a.M) break;                                // (wave-uniform)
+#pragma unroll
+      for (int j = 0; j < CH; ++j) {
+        const float xv[4] = {v[r][j].x, v[r][j].y, v[r][j].z, v[r][j].w};
+        float o[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          float t = xv[e] * inv[r] * scale;
+          if constexpr (GAMMA) t *= (e == 0 ? gm[j].x : e == 1 ? gm[j].y : e == 2 ? gm[j].z : gm[j].w);
+          if constexpr (COND) t = t * (e == 0 ? gg[j].x : e == 1 ? gg[j].y : e == 2 ? gg[j].z : gg[j].w) +
+                                  (e == 0 ? bb[j].x : e == 1 ? bb[j].y : e == 2 ? bb[j].z : bb[j].w);
+          // rmsnorm_kernel converts the ROUNDED t (its run-time gamma / cond branches stand between the last multiply and the conversion);
+          // here they are compile-time, and without this the compiler contracts `t * gm - bf16(hi)` of the bf16 split into one fma on
+          // the unrounded product: another lo plane.  An empty statement that makes t opaque costs no instruction.
+          asm volatile("" : "+v"(t));
+          o[e] = t;
+        }
+        if constexpr (OUTF) *reinterpret_cast<float4*>(a.out_f + row * a.ldo_f + lane * 4 + 256 * j) = make_float4(o[0], o[1], o[2], o[3]);
+        // this lane's pieces of the row, where store_cols4 would put them in memory
+        if constexpr (FMT == FMT_H8) {
+          uint32_t ha, hb, h8a, h8b, l8a, l8b;
+          cvt2_h8(o[0], o[1], ha, h8a, l8a);
+          cvt2_h8(o[2], o[3], hb, h8b, l8b);
+          unsigned char* line = stage + j * 1024 + (lane >> 3) * 128;
+          *reinterpret_cast<uint2*>(line + (lane & 7) * 8) = make_uint2(ha, hb);
+          *reinterpret_cast<uint32_t*>(line + 64 + (lane & 7) * 4) = h8a | (h8b << 16);
+          *reinterpret_cast<uint32_t*>(line + 96 + (lane & 7) * 4) = l8a | (l8b << 16);
+        } else if constexpr (FMT == FMT_F16) {
+          *reinterpret_cast<uint2*>(stage + j * 512 + lane * 8) = make_uint2(cvt2h(o[0], o[1]), cvt2h(o[2], o[3]));
+        } else {
+          uint32_t h01, l01, h23, l23;
+          split2(o[0], o[1], h01, l01);
+          split2(o[2], o[3], h23, l23);
+          unsigned char* line = stage + j * 1024 + (lane >> 3) * 128;
+          *reinterpret_cast<uint2*>(line + (lane & 7) * 8) = make_uint2(h01, h23);
+          *reinterpret_cast<uint2*>(line + 64 + (lane & 7) * 8) = make_uint2(l01, l23);
+        }
+      }
+      wave_lds_order();
+      unsigned char* dst = reinterpret_cast<unsigned char*>(a.out_hi) + row * ROWB;
+#pragma unroll
+      for (int k = 0; k < ROWB; k += 1024)
+        if (ROWB - k >= 1024 || lane < 32)                  // (dense halves at d = 256: a 512-byte row, half a wave)
+          *reinterpret_cast<uint4*>(dst + k + lane * 16) = *reinterpret_cast<const uint4*>(stage + k + lane * 16);
+      wave_lds_order();
+    }
+#pragma unroll
+    for (int r = 0; r < WIDE_ROWS; ++r)
+#pragma unroll
+      for (int j = 0; j < CH; ++j) v[r][j] = nv[r][j];
+  }
+}
+
+// Test hook (ns2_debug_force_norm / NS2_NORM) in the manner of gemm2.hip's gemm_hook(): process-wide, atomic.  -1: read NS2_NORM once;
+// 0: by shape; 1: rmsnorm_kernel for every call.  norm_kernel_last: 1 = rmsnorm_kernel, 2 = rmsnorm_wide_kernel ran the last launch.
+static std::atomic<int> g_forced_norm{-1};
+static std::atomic<int> g_norm_last{0};
+void force_norm_kernel(int k) { g_forced_norm.store(k, std::memory_order_relaxed); }
+int norm_kernel_last() { return g_norm_last.load(std::memory_order_relaxed); }
+static bool norm_wide_allowed() {
+  int f = g_forced_norm.load(std::memory_order_relaxed);
+  if (f < 0) {
+    const char* e = getenv("NS2_NORM");
+    f = (e && atoi(e) == 1) ? 1 : 0;
+    g_forced_norm.store(f, std::memory_order_relaxed);
+  }
+  return f == 0;
+}
+static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+// the hot case of rmsnorm_wide_kernel; everything else keeps rmsnorm_kernel
+static bool norm_wide_eligible(const NormArgs& a) {
+  if (!a.out_hi || a.d <= 0 || (a.d & 255) || a.d > 1024 || a.ldo != a.d) return false;
+  if (!((a.fmt == FMT_H8 && a.out_lo) || (a.fmt == FMT_F16 && !a.out_lo) || (a.fmt == FMT_BF16 && a.out_lo))) return false;
+  if (!aligned16(a.x) || !aligned16(a.out_hi) || !aligned16(a.gamma) || !aligned16(a.cond) || (a.cond && (a.cond_ld & 3))) return false;
+  if (a.out_f && (!aligned16(a.out_f) || (a.ldo_f & 3))) return false;
+  return !a.cond || a.seq_len <= 0 || (a.seq_len % WIDE_TILE) == 0;
+}
+template <int CH, int FMT, bool OUTF>
+static void launch_rmsnorm_wide_as(const NormArgs& a, int grid, int ntiles, hipStream_t s) {
+  const dim3 g(grid), b(256);
+  if (a.gamma && a.cond) hipLaunchKernelGGL((rmsnorm_wide_kernel<CH, FMT, true, true, OUTF>), g, b, 0, s, a, ntiles);
+  else if (a.gamma) hipLaunchKernelGGL((rmsnorm_wide_kernel<CH, FMT, true, false, OUTF>), g, b, 0, s, a, ntiles);
+  else if (a.cond) hipLaunchKernelGGL((rmsnorm_wide_kernel<CH, FMT, false, true, OUTF>), g, b, 0, s, a, ntiles);
+  else hipLaunchKernelGGL((rmsnorm_wide_kernel<CH, FMT, false, false, OUTF>), g, b, 0, s, a, ntiles);
+}
+template <int CH, int FMT>
+static void launch_rmsnorm_wide_fmt(const NormArgs& a, int grid, int ntiles, hipStream_t s) {
+  if (a.out_f) launch_rmsnorm_wide_as<CH, FMT, true>(a, grid, ntiles, s);
+  else launch_rmsnorm_wide_as<CH, FMT, false>(a, grid, ntiles, s);
+}
+template <int CH>
+static void launch_rmsnorm_wide(const NormArgs& a, hipStream_t s) {
+  const int ntiles = (a.M + WIDE_TILE - 1) / WIDE_TILE;
+  const int grid = ntiles < 256 * 4 ? ntiles : 256 * 4;     // four workgroups (16 waves) per CU of the 256, striding over the tiles
+  if (a.fmt == FMT_H8) launch_rmsnorm_wide_fmt<CH, FMT_H8>(a, grid, ntiles, s);
+  else if (a.fmt == FMT_F16) launch_rmsnorm_wide_fmt<CH, FMT_F16>(a, grid, ntiles, s);
+  else launch_rmsnorm_wide_fmt<CH, FMT_BF16>(a, grid, ntiles, s);
+}
+
 hipError_t launch_rmsnorm(const NormArgs& a, hipStream_t s) {
   if (a.M <= 0 || (a.d & 3) || (a.ldo & 3) || (a.ldx & 3) || a.ldo > 2048 || a.d > 2048) return hipErrorInvalidValue;
   if (!planes_ok(a.out_hi, a.out_lo) || (a.out_lo && (a.ldo & 31))) return hipErrorInvalidValue;
   if (a.out_hi && ((a.fmt == FMT_H8 && !a.out_lo) || (a.fmt == FMT_F16 && a.out_lo))) return hipErrorInvalidValue;
+  if (norm_wide_allowed() && norm_wide_eligible(a)) {
+    switch (a.d >> 8) {
+      case 1: launch_rmsnorm_wide<1>(a, s); break;
+      case 2: launch_rmsnorm_wide<2>(a, s); break;
+      case 3: launch_rmsnorm_wide<3>(a, s); break;
+      default: launch_rmsnorm_wide<4>(a, s); break;
+    }
+    g_norm_last.store(2, std::memory_order_relaxed);
+    return hipGetLastError();
+  }
+  g_norm_last.store(1, std::memory_order_relaxed);
   const dim3 grid((a.M + 3) / 4), block(256);
   const int width = a.ldo > a.d ? a.ldo : a.d;
   if (width <= 256) hipLaunchKernelGGL(rmsnorm_kernel<1>, grid, block, 0, s, a);
@@ -481,6 +661,50 @@ hipError_t launch_ff_fold(const float* w_out, const float* w_conv, const float* 
   if (!w_out || !w_conv || !b_conv || !w_fold || !b_fold || dim <= 0 || f <= 0) return hipErrorInvalidValue;
   hipLaunchKernelGGL(ff_fold_kernel, dim3((3 * f + 1 + 255) / 256, (dim + FF_FOLD_NB - 1) / FF_FOLD_NB), dim3(256), 0, s, w_out, w_conv, b_conv,
                      b_out, dim, f, w_fold, b_fold);
+  return hipGetLastError();
+}
+
+// The Wavenet tail fold (model_exec.cpp; NS2:639-640, 685-686, 725): the sum of the L skip convs (1 x 1) and final_conv (1 x 1) behind it
+// are one Linear over the concatenated block outputs,
+//   W'[n, l * dim + c] = sum_j W_final[n, j] W_skip[l][j, c]        b'[n] = sum_j W_final[n, j] (sum_l b_skip[l][j]) + b_final[n]
+// under ff_fold_kernel's rules: fp32 FMAs over ascending j (the bias sum over ascending l first), one accumulator per output, no atomics.
+// A thread owns column e = l * dim + c (e == L * dim: the bias) for FF_FOLD_NB output rows.  Once per finalize: 2.1 GFLOP at dim 512, L 8.
+__global__ __launch_bounds__(256) void tail_fold_kernel(const float* __restrict__ w_final, const float* __restrict__ w_skip,
+                                                        const float* __restrict__ b_skip, const float* __restrict__ b_final, int dim, int L,
+                                                        float* __restrict__ w_fold, float* __restrict__ b_fold) {
+  const int E = L * dim;
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e > E) return;
+  const int n0 = blockIdx.y * FF_FOLD_NB;
+  const int l = e / dim, c = e - l * dim;
+  const float* src = w_skip + (long)l * dim * dim + c;      // (read only where e < E)
+  const float* wf[FF_FOLD_NB];
+  float acc[FF_FOLD_NB];
+#pragma unroll
+  for (int i = 0; i < FF_FOLD_NB; ++i) { wf[i] = w_final + (long)min(n0 + i, dim - 1) * dim; acc[i] = 0.f; }
+  for (int j = 0; j < dim; ++j) {
+    float v;
+    if (e < E) v = src[(long)j * dim];
+    else {
+      v = 0.f;
+      for (int k = 0; k < L; ++k) v += b_skip[(long)k * dim + j];
+    }
+#pragma unroll
+    for (int i = 0; i < FF_FOLD_NB; ++i) acc[i] = fmaf(wf[i][j], v, acc[i]);
+  }
+#pragma unroll
+  for (int i = 0; i < FF_FOLD_NB; ++i) {
+    const int n = n0 + i;
+    if (n >= dim) break;
+    if (e < E) w_fold[(long)n * E + e] = acc[i];
+    else b_fold[n] = acc[i] + (b_final ? b_final[n] : 0.f);
+  }
+}
+hipError_t launch_tail_fold(const float* w_final, const float* w_skip, const float* b_skip, const float* b_final, int dim, int L,
+                            float* w_fold, float* b_fold, hipStream_t s) {
+  if (!w_final || !w_skip || !b_skip || !w_fold || !b_fold || dim <= 0 || L <= 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(tail_fold_kernel, dim3((L * dim + 1 + 255) / 256, (dim + FF_FOLD_NB - 1) / FF_FOLD_NB), dim3(256), 0, s, w_final, w_skip,
+                     b_skip, b_final, dim, L, w_fold, b_fold);
   return hipGetLastError();
 }
 

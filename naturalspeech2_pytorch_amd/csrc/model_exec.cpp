@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "../../include/ns2hip_fold.h"
+#include "../../include/ns2hip_tail_fold.h"
 #include "../../include/ns2hip_ragged.h"
 #include "../../include/ns2hip_ragged_front.h"
 #include "../../include/ns2hip_ragged_skip.h"
@@ -72,6 +73,13 @@ struct ns2_model {
   std::vector<float*> b_wn_conv, b_wn_res;
   PackedW w_skip; float* b_skip;
   PackedW w_final; const float* b_final;
+  // The tail fold (include/ns2hip_tail_fold.h): the skip sum (one Linear over the L concatenated block outputs) and final_conv (1 x 1)
+  // behind it (NS2:725) as ONE Linear of K = L * dim, W' = W_final . [W_skip_0 | ... | W_skip_{L-1}], b' = W_final . sum_l b_skip_l + b_final,
+  // folded once from the fp32 parameters by ns2_model_finalize (elementwise.hip tail_fold_kernel).  A step then runs one product into the
+  // residual stream; the w_skip / w_final packs and the ssum planes do not exist.  false (ns2_debug_force_tail_fold(0) / NS2_TAIL_FOLD=0
+  // at finalize): both products.
+  bool tail_fold = false;
+  PackedW w_tail; float* b_tail = nullptr;
   struct Layer {
     PackedW qkv, out, ffin, conv, ffout, cq, ckv, cout;
     float* b_ffin; const float* b_conv; const float* b_ffout;
@@ -308,6 +316,24 @@ extern "C" int ns2_debug_force_fold(int fold) {
   return NS2_OK;
 }
 
+// Likewise for the Wavenet tail (ns2_debug_force_tail_fold / NS2_TAIL_FOLD): 0: the skip sum and final_conv stay two products; 1 (the
+// default): one (ns2_model::tail_fold).
+static std::atomic<int> g_forced_tail_fold{-1};
+static bool tail_fold_wanted() {
+  int f = g_forced_tail_fold.load(std::memory_order_relaxed);
+  if (f < 0) {
+    const char* e = getenv("NS2_TAIL_FOLD");
+    f = (e && atoi(e) == 0) ? 0 : 1;
+    g_forced_tail_fold.store(f, std::memory_order_relaxed);
+  }
+  return f != 0;
+}
+extern "C" int ns2_debug_force_tail_fold(int fold) {
+  ARGCHK(fold == 0 || fold == 1, "ns2_debug_force_tail_fold: 0 = the skip sum and final_conv as two products, 1 = folded into one");
+  g_forced_tail_fold.store(fold, std::memory_order_relaxed);
+  return NS2_OK;
+}
+
 static const Param* find_param(const ns2_model* m, const std::string& k) {
   auto it = m->params.find(k);
   return it == m->params.end() ? nullptr : &it->second;
@@ -384,6 +410,7 @@ extern "C" int ns2_model_finalize(ns2_model* m, void* stream) {
   const PackCtx pc_cond = pack_ctx_for(&m->owned, cond_precision(op_precision(m->cfg.precision)));   // weights of prepare_cond
   const bool il = pc.il;
   m->fold = fold_wanted();
+  m->tail_fold = tail_fold_wanted();
 
   // ---- time conditioning (NS2:839-843)
   { GETP(fw, "to_time_cond.0.weights"); m->freqs = fw->p; }
@@ -439,21 +466,41 @@ extern "C" int ns2_model_finalize(ns2_model* m, void* stream) {
       HIPRET(hipMemcpyAsync(m->b_wn_res[st] + (size_t)i * dim, rb->p, dim * sizeof(float), hipMemcpyDeviceToDevice, s));
     }
   }
-  { // skip convs of the last stack, concatenated along K; summed bias (NS2:639-640, 685-686, 725)
-    NSCHK(alloc_packed(pc, &m->w_skip, dim, L * m->dp, L * m->dp / 32));
-    std::vector<float> bsum(dim, 0.f), hb(dim);
+  if (m->tail_fold) {   // skip convs of the last stack and final_conv as one Linear of K = L * dim (ns2_model::tail_fold)
+    struct Scratch { float* p = nullptr; ~Scratch() { if (p) (void)hipFree(p); } } ws, bs, wf;     // [L, dim, dim], [L, dim], W' [dim, L * dim]
+    const size_t dd = (size_t)dim * dim;
+    HIPRET(hipMalloc((void**)&ws.p, L * dd * sizeof(float)));
+    HIPRET(hipMalloc((void**)&bs.p, (size_t)L * dim * sizeof(float)));
+    HIPRET(hipMalloc((void**)&wf.p, L * dd * sizeof(float)));
     for (int i = 0; i < L; ++i) {
       snprintf(key, sizeof key, "wavenet.stacks.%d.blocks.%d.skip_conv", S - 1, i);
       GETP(w, std::string(key) + ".weight"); GETP(b, std::string(key) + ".bias");
-      NSCHK(pack_into(&m->w_skip, w->p, dim, 1, m->dp, identity_map(dim, m->w_skip.rows_p), 0, i * m->dp, s));
-      HIPRET(hipMemcpy(hb.data(), b->p, dim * sizeof(float), hipMemcpyDeviceToHost));
-      for (int c = 0; c < dim; ++c) bsum[c] += hb[c];
+      if (w->dims.size() < 2 || w->dims[0] != dim || w->dims[1] != dim) { set_error("%s.weight has unexpected shape", key); return NS2_ERR_STATE; }
+      HIPRET(hipMemcpyAsync(ws.p + i * dd, w->p, dd * sizeof(float), hipMemcpyDeviceToDevice, s));
+      HIPRET(hipMemcpyAsync(bs.p + (size_t)i * dim, b->p, dim * sizeof(float), hipMemcpyDeviceToDevice, s));
     }
-    NSCHK(dev_alloc(&m->owned, (void**)&m->b_skip, dim * sizeof(float)));
-    HIPRET(hipMemcpy(m->b_skip, bsum.data(), dim * sizeof(float), hipMemcpyHostToDevice));
+    GETP(w, "wavenet.final_conv.weight"); GETP(b, "wavenet.final_conv.bias");
+    if (w->dims.size() < 2 || w->dims[0] != dim || w->dims[1] != dim) { set_error("wavenet.final_conv.weight has unexpected shape"); return NS2_ERR_STATE; }
+    NSCHK(dev_alloc(&m->owned, (void**)&m->b_tail, dim * sizeof(float)));
+    HIPRET(launch_tail_fold(w->p, ws.p, bs.p, b->p, dim, L, wf.p, m->b_tail, s));
+    NSCHK(pack_linear(pc, &m->w_tail, wf.p, dim, L * dim, 1, s));       // (synchronises: the scratch may go); dp == dim: column l * dp + c
+  } else {
+    { // skip convs of the last stack, concatenated along K; summed bias (NS2:639-640, 685-686, 725)
+      NSCHK(alloc_packed(pc, &m->w_skip, dim, L * m->dp, L * m->dp / 32));
+      std::vector<float> bsum(dim, 0.f), hb(dim);
+      for (int i = 0; i < L; ++i) {
+        snprintf(key, sizeof key, "wavenet.stacks.%d.blocks.%d.skip_conv", S - 1, i);
+        GETP(w, std::string(key) + ".weight"); GETP(b, std::string(key) + ".bias");
+        NSCHK(pack_into(&m->w_skip, w->p, dim, 1, m->dp, identity_map(dim, m->w_skip.rows_p), 0, i * m->dp, s));
+        HIPRET(hipMemcpy(hb.data(), b->p, dim * sizeof(float), hipMemcpyDeviceToHost));
+        for (int c = 0; c < dim; ++c) bsum[c] += hb[c];
+      }
+      NSCHK(dev_alloc(&m->owned, (void**)&m->b_skip, dim * sizeof(float)));
+      HIPRET(hipMemcpy(m->b_skip, bsum.data(), dim * sizeof(float), hipMemcpyHostToDevice));
+    }
+    { GETP(w, "wavenet.final_conv.weight"); GETP(b, "wavenet.final_conv.bias");
+      NSCHK(pack_linear(pc, &m->w_final, w->p, dim, dim, 1, s)); m->b_final = b->p; }
   }
-  { GETP(w, "wavenet.final_conv.weight"); GETP(b, "wavenet.final_conv.bias");
-    NSCHK(pack_linear(pc, &m->w_final, w->p, dim, dim, 1, s)); m->b_final = b->p; }
 
   // ---- transformer (NS2:748-809)
   m->layers.resize(m->cfg.depth);
@@ -540,7 +587,9 @@ extern "C" int ns2_model_finalize(ns2_model* m, void* stream) {
       HIPRET(wavenet3_build_tiles(W.hi, W.rows_p, m->dp, L, W.tw1, W.tw2, s));
     }
   // tiled images of the per-step mixed linear weights (gemm3_kernel.h): +1 copy of 12.6 MB per layer at d512
-  NSCHK(build_lin_tiles(&m->owned, &m->w_skip, s)); NSCHK(build_lin_tiles(&m->owned, &m->w_final, s)); NSCHK(build_lin_tiles(&m->owned, &m->w_pred, s));
+  if (m->tail_fold) NSCHK(build_lin_tiles(&m->owned, &m->w_tail, s));
+  else { NSCHK(build_lin_tiles(&m->owned, &m->w_skip, s)); NSCHK(build_lin_tiles(&m->owned, &m->w_final, s)); }
+  NSCHK(build_lin_tiles(&m->owned, &m->w_pred, s));
   for (auto& ly : m->layers) {
     NSCHK(build_lin_tiles(&m->owned, &ly.qkv, s)); NSCHK(build_lin_tiles(&m->owned, &ly.out, s));
     NSCHK(build_lin_tiles(&m->owned, &ly.ffin, s)); NSCHK(build_lin_tiles(&m->owned, &ly.ffout, s));
@@ -653,7 +702,8 @@ static int64_t carve_work(const ns2_model* m, Work* w, void* base, int64_t cap, 
   w->h0 = take_planes(c, M * dp, il, f16);
   w->wA = take_planes(c, M * L * dp, il, f16);
   w->wB = take_planes(c, M * L * dp, il, f16);
-  w->ssum = take_planes(c, M * dp, il, f16);
+  if (m->tail_fold) w->ssum = Planes{nullptr, nullptr, f16};      // the skip sum's planes do not exist: the folded tail writes the residual stream
+  else w->ssum = take_planes(c, M * dp, il, f16);
   w->xn = take_planes(c, M * dp, il, f16);
   w->qk = take_planes(c, Mq * 2 * a, ail, afmt);
   w->Nkp = rup(N, kpad);
@@ -1047,7 +1097,7 @@ void describe_rows(const ns2_model* m, const Work& w0, const CondState* cs, cons
   float* out = st.out + r0 * dim;
   float* xres = w0.xres + r0 * dim;
   const float* call = st.call + (size_t)b0 * cld;
-  const Planes xs = rows_of(w0.xs, r0, dp), h0 = rows_of(w0.h0, r0, dp), ssum = rows_of(w0.ssum, r0, dp), xn = rows_of(w0.xn, r0, dp);
+  const Planes xs = rows_of(w0.xs, r0, dp), h0 = rows_of(w0.h0, r0, dp), ssum = m->tail_fold ? w0.ssum : rows_of(w0.ssum, r0, dp), xn = rows_of(w0.xn, r0, dp);
   const Planes qk = rows_of(w0.qk, r0, 2 * a), o = rows_of(w0.o, r0, a), ffc = m->fold ? w0.ffc : rows_of(w0.ffc, r0, fp);
   const Planes vt = rows_of(w0.vt, b0, (int64_t)a * w0.Nkp);
   const Planes ffh = rows_of(w0.ffh, r0, std::max(fp, fpc));
@@ -1112,8 +1162,8 @@ void describe_rows(const ns2_model* m, const Work& w0, const CondState* cs, cons
     tap_p(name, cur, L * dp, L * dp);
     std::swap(prev, cur);
   }
-  // sum of the 8 skip convs == one GEMM over the concatenated columns (NS2:639-640, 685-686, 725), then final_conv
-  {
+  // sum of the 8 skip convs == one GEMM over the concatenated columns (NS2:639-640, 685-686, 725), then final_conv -- folded: below
+  if (!m->tail_fold) {
     GemmArgs g = product(m->w_skip, prev, L * dp, M);
     set_out_planes(g, EPI_SPLIT, ssum.hi, ssum.lo, dp); g.bias = m->b_skip;
     gemm(g, prec, PC_GEMM_SPLIT);
@@ -1142,7 +1192,10 @@ void describe_rows(const ns2_model* m, const Work& w0, const CondState* cs, cons
   };
   auto layer_cond = [&](int l, int which) { return cbase + (size_t)l * m->nnorm * 2 * dim + (size_t)which * 2 * dim; };
   // final_conv of the Wavenet -> the residual stream, normed for layer 0's self attention
-  update_then_norm(m->w_final, ssum, dp, m->b_final, false, prec, nullptr, layer_cond(0, 0), xn);
+  // (folded, ns2_model::tail_fold: skip sum and final_conv as one product over the last stack's L * dp columns.  It keeps the skip sum's
+  // profile category: it multiplies exactly the skip sum's 2 M dim L dim FLOPs, which is what a reader of category 1 credits it with)
+  if (m->tail_fold) update_then_norm(m->w_tail, prev, L * dp, m->b_tail, false, prec, nullptr, layer_cond(0, 0), xn, Launch::NONE, false, PC_GEMM_SPLIT);
+  else update_then_norm(m->w_final, ssum, dp, m->b_final, false, prec, nullptr, layer_cond(0, 0), xn);
   tap_f("wavenet.out", xres);
 
   // ---- transformer (NS2:786-809)
@@ -1425,6 +1478,7 @@ static int debug_rules(const ns2_model_config* cfg, int B, int N, int* chains, i
   ns2_model* m = &mm;
   NSCHK(derive_dims(m, cfg));
   m->fold = fold_wanted();
+  m->tail_fold = tail_fold_wanted();
   bf16_t* const fake = reinterpret_cast<bf16_t*>(uintptr_t(1) << 40);
   float* const fakef = reinterpret_cast<float*>(fake);
   const PackCtx pc = pack_ctx_for(nullptr, op_precision(cfg->precision));
@@ -1444,8 +1498,11 @@ static int debug_rules(const ns2_model_config* cfg, int B, int N, int* chains, i
     shape(&W, pc, dim, m->dp, 4); W.kt_per_tap = m->dp / 32;
     if (hybrid_plan(cfg->precision) && (m->dp % 128) == 0 && (dim % 256) == 0 && W.fmt == FMT_H8) { W.tw1 = fake; W.tw2 = fake; }
   }
-  shape(&m->w_skip, pc, dim, L * m->dp, 1); m->b_skip = fakef;
-  shape(&m->w_final, pc, dim, dim, 1); m->b_final = fakef;
+  if (m->tail_fold) { shape(&m->w_tail, pc, dim, L * m->dp, 1); m->b_tail = fakef; }
+  else {
+    shape(&m->w_skip, pc, dim, L * m->dp, 1); m->b_skip = fakef;
+    shape(&m->w_final, pc, dim, dim, 1); m->b_final = fakef;
+  }
   shape(&m->w_pred, pc, dim, dim, 1); m->g_pred = fakef;
   m->layers.resize(cfg->depth);
   for (ns2_model::Layer& ly : m->layers) {

@@ -181,6 +181,8 @@ struct NormArgs {
   int fmt;                           // PlaneFmt of the output planes
 };
 hipError_t launch_rmsnorm(const NormArgs& a, hipStream_t s);
+void force_norm_kernel(int k);      // test hook, the modes of ns2_debug_force_norm (include/ns2hip_tail_fold.h): 0 by shape, 1 = rmsnorm_kernel for every call
+int norm_kernel_last();             // which kernel the last launch_rmsnorm ran: 1 = rmsnorm_kernel, 2 = rmsnorm_wide_kernel (0: none yet)
 
 // x (+ add) -> split planes, with optional zero padding to ldo columns
 hipError_t launch_split(const float* x, int ldx, const float* add, int ldadd, int add_rows_per_batch, int add_valid_rows,
@@ -246,6 +248,10 @@ hipError_t launch_pack_weight(const float* src, int C, int T, int Cp, const int*
 // (b_out may be null), fp32 FMAs in ascending order of the contracted index
 hipError_t launch_ff_fold(const float* w_out, const float* w_conv, const float* b_conv, const float* b_out, int dim, int f, float* w_fold,
                           float* b_fold, hipStream_t s);
+// the Wavenet tail fold (elementwise.hip): w_fold [dim, L * dim] = w_final [dim, dim] . [w_skip[0] | ... | w_skip[L - 1]] (w_skip [L, dim, dim]),
+// b_fold [dim] = w_final . sum_l b_skip[l] + b_final (b_skip [L, dim]; b_final may be null), under the same rules
+hipError_t launch_tail_fold(const float* w_final, const float* w_skip, const float* b_skip, const float* b_final, int dim, int L,
+                            float* w_fold, float* b_fold, hipStream_t s);
 
 // EnCodec residual VQ encode (HFENC:364-369, 424-447)
 struct RvqArgs {

@@ -3,6 +3,8 @@ built at each chain skew, alternating in fresh processes on one MI355X, then `--
 
     # the four skew builds: csrc/model_exec.cpp compiled with -DNS2_CHAIN_SKEW=0 ... 3, linked like csrc/build.sh
     python tools/chains_ab.py --parent DIR_OF_BUILT_PARENT_CHECKOUT --lib skew0=PATH --lib skew1=PATH ... [--rounds 3] [--full]
+    # a later A/B with switches read from the environment (profiles/tail_fold_norm_ab.json): this tree's library under each setting
+    python tools/chains_ab.py --parent DIR --no-one-chain --side norm_old:NS2_NORM=1 --side both_off:NS2_NORM=1,NS2_TAIL_FOLD=0
 
 Prints one JSON line per run (`ms_per_step`; with --full also the three side workloads the chains may touch) and one per identity check.
 Every run has its own time limit; the first abnormal exit ends the job (nothing more is started on the GPU).
@@ -48,6 +50,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parent", required=True, help="a checkout of the parent commit with its library built")
     ap.add_argument("--lib", action="append", default=[], metavar="TAG=PATH", help="a library of this tree to run through NS2_LIB")
+    ap.add_argument("--side", action="append", default=[], metavar="TAG:K=V[,K=V]", help="one more side: this tree's first library with these environment variables")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--full", action="store_true", help="run bench.py --full (side workloads) instead of the plain headline")
     ap.add_argument("--no-dump", action="store_true")
@@ -55,6 +58,9 @@ def main():
     a = ap.parse_args()
     libs = [s.split("=", 1) for s in a.lib] or [["new", os.path.join(ROOT, "naturalspeech2_pytorch_amd", "libns2hip.so")]]
     sides = [("parent", a.parent, {})] + [(t, ROOT, {"NS2_LIB": os.path.abspath(p)}) for t, p in libs]
+    for spec in a.side:
+        tag, _, kv = spec.partition(":")
+        sides.append((tag, ROOT, dict({"NS2_LIB": os.path.abspath(libs[0][1])}, **dict(p.split("=", 1) for p in kv.split(",") if p))))
     if not a.no_one_chain:
         sides.append(("new_one_chain", ROOT, {"NS2_LIB": os.path.abspath(libs[0][1]), "NS2_CHAINS": "1"}))
     for _ in range(a.rounds):
