@@ -1,6 +1,5 @@
-/* The feed-forward fold in libns2hip.  One more header of the C ABI, parsed by _lib.py under the same rule as ns2hip.h into a table of
- * its own (FOLD_SIGNATURES); the tables of the other headers are unchanged.  Status codes and ns2_last_error are those of ns2hip.h,
- * which this header includes.
+/* The feed-forward fold in libns2hip.  Part of the C ABI: listed in _lib.HEADERS (naturalspeech2_pytorch_amd/_lib.py).  Status codes
+ * and ns2_last_error are those of ns2hip.h, which this header includes.
  *
  * FeedForward is Sequential(Linear(dim, 2f), GEGLU(), CausalConv1d(f, f, 3), Linear(f, dim)) (NS2:1009-1025).  Nothing stands between
  * the causal conv and the last Linear and both are linear maps, so the pair is one causal conv of kernel 3 from f to dim channels:

@@ -1,7 +1,6 @@
 /* Head dims 32 and 128 in the TRAINING pass of libns2hip: the attention forward with its log-sum-exp, the delta reduction and the
- * flash backward for heads of 32, 64 or 128 columns.  A seventh header of the C ABI, parsed by _lib.py under the same rule as ns2hip.h
- * into tables of its own (HEAD_DIM_TRAIN_SIGNATURES); the tables of the other six headers are unchanged.  Status codes, ns2_last_error,
- * ns2_attn_args and ns2_attn_bwd_args are those of ns2hip.h, which this header includes.
+ * flash backward for heads of 32, 64 or 128 columns.  Part of the C ABI: listed in _lib.HEADERS (naturalspeech2_pytorch_amd/_lib.py).
+ * Status codes, ns2_last_error, ns2_attn_args and ns2_attn_bwd_args are those of ns2hip.h, which this header includes.
  *
  * The entries of ns2hip.h and ns2hip_ragged_train.h keep their head dim of 64 (ns2_attention_fwd refuses lse at any other).  These take
  * the head dim as an argument: head h lies at columns col0 + head_dim * h of every operand, output and gradient, and `scale` is the

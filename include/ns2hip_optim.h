@@ -1,11 +1,12 @@
-/* libns2hip, second header: the optimizer step of the training loop on the device.
+/* libns2hip: the optimizer step of the training loop on the device.  Part of the C ABI: listed in _lib.HEADERS
+ * (naturalspeech2_pytorch_amd/_lib.py).
  *
  * Reference: what follows `accelerator.backward(loss)` in Trainer.train (NS2:1888-1901) --
  * `clip_grad_norm_(parameters, max_grad_norm)`, `Adam.step()` (weight_decay 0, amsgrad off), `ema.update()` every
  * `update_every` steps -- as three stream-ordered launches with no host read, so the whole loop body can live in one HIP graph.
  *
  * The conventions of ns2hip.h hold (device pointers unless named host_*, caller-owned memory, 0 = ok, ns2_last_error()); this header
- * declares its own entry points only and is parsed by the same rule (naturalspeech2_pytorch_amd/_lib.py parse_header).
+ * declares its own entry points, structs and constants only.
  *
  * Memory, all caller-owned:
  *   table   ns2_optim_table_bytes(n, chunks) bytes, 16-byte aligned: the tensors, their cut into chunks of NS2_OPTIM_CHUNK values

@@ -1,6 +1,5 @@
-/* The pitch extractor of libns2hip (csrc/pitch.hip, pitch.py): a third header of the C ABI, parsed by _lib.py under the same
- * rule as ns2hip.h into tables of its own (PITCH_SIGNATURES); the tables of ns2hip.h and ns2hip_optim.h are unchanged.
- * Status codes and ns2_last_error are those of ns2hip.h. */
+/* The pitch extractor of libns2hip (csrc/pitch.hip, pitch.py).  Part of the C ABI: listed in _lib.HEADERS
+ * (naturalspeech2_pytorch_amd/_lib.py).  Status codes and ns2_last_error are those of ns2hip.h. */
 #ifndef NS2HIP_PITCH_H
 #define NS2HIP_PITCH_H
 

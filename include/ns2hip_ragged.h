@@ -1,6 +1,5 @@
-/* Ragged batches in libns2hip: per-utterance lengths in the attention kernels.  A fourth header of the C ABI, parsed by _lib.py under
- * the same rule as ns2hip.h into tables of its own (RAGGED_SIGNATURES); the tables of ns2hip.h, ns2hip_optim.h and ns2hip_pitch.h
- * are unchanged.  Status codes, ns2_last_error, ns2_attn_args and ns2_model are those of ns2hip.h, which this header includes.
+/* Ragged batches in libns2hip: per-utterance lengths in the attention kernels.  Part of the C ABI: listed in _lib.HEADERS
+ * (naturalspeech2_pytorch_amd/_lib.py).  Status codes, ns2_last_error, ns2_attn_args and ns2_model are those of ns2hip.h, which this header includes.
  *
  * The definition: utterance i of a ragged batch equals utterance i run alone at its own length.  In Model the self-attention is the
  * one thing through which a frame sees later frames (the convolutions are causal; norms, FiLM and the cross-attention to the

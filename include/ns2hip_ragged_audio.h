@@ -1,7 +1,6 @@
 /* Ragged RAW AUDIO in the training pass of libns2hip: per-utterance sample counts in the mel spectrogram and the pitch extractor, and
- * per-utterance frame counts in the RVQ cross-entropy term.  An eighth header of the C ABI, parsed by _lib.py under the same rule as
- * ns2hip.h into a table of its own (RAGGED_AUDIO_SIGNATURES); the tables of the other seven headers are unchanged.  Status codes and
- * ns2_last_error are those of ns2hip.h.
+ * per-utterance frame counts in the RVQ cross-entropy term.  Part of the C ABI: listed in _lib.HEADERS
+ * (naturalspeech2_pytorch_amd/_lib.py).  Status codes and ns2_last_error are those of ns2hip.h.
  *
  * The definition is that of ns2hip_ragged.h and ns2hip_ragged_train.h: what utterance i yields in the padded batch is what it yields
  * ALONE, cut to its length.  Whatever lies at or behind a length -- NaN included -- reaches no value and no gradient before it, and what

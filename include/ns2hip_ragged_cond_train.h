@@ -1,7 +1,6 @@
 /* Ragged text and prompts in the TRAINING pass of libns2hip: per-utterance lengths through the conditioning (SpeechPromptEncoder,
- * PhonemeEncoder, DurationPitchPredictor, the conditioning of Model).  A tenth header of the C ABI, parsed by _lib.py under the same rule
- * as ns2hip.h into a table of its own (RAGGED_COND_TRAIN_SIGNATURES); the tables of the other nine headers are unchanged.  Status codes
- * and ns2_last_error are those of ns2hip.h.
+ * PhonemeEncoder, DurationPitchPredictor, the conditioning of Model).  Part of the C ABI: listed in _lib.HEADERS (naturalspeech2_pytorch_amd/_lib.py).
+ * Status codes and ns2_last_error are those of ns2hip.h.
  *
  * The definition is that of ns2hip_ragged_front.h: utterance i of a padded batch is utterance i run alone with its text cut to
  * text_lens[i] and its prompt cut to prompt_lens[i] -- here for the gradients too.  The attention kernels are unchanged: every attention

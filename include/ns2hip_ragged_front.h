@@ -1,7 +1,6 @@
 /* Ragged prompts and text in libns2hip: per-utterance lengths through the front-end (SpeechPromptEncoder, DurationPitchPredictor, the
- * conditioning of Model).  A fifth header of the C ABI, parsed by _lib.py under the same rule as ns2hip.h into tables of its own
- * (FRONT_SIGNATURES); the tables of the other four headers are unchanged.  Status codes, ns2_last_error and ns2_model are those of
- * ns2hip.h, which this header includes.
+ * conditioning of Model).  Part of the C ABI: listed in _lib.HEADERS (naturalspeech2_pytorch_amd/_lib.py).  Status codes, ns2_last_error
+ * and ns2_model are those of ns2hip.h, which this header includes.
  *
  * The definition is that of ns2hip_ragged.h: utterance i of a ragged batch equals utterance i run alone, here with its text cut to
  * text_lens[i] and its prompt cut to prompt_lens[i].  The GEMM and attention kernels are unchanged: a row never sees another row in a

@@ -1,6 +1,5 @@
-/* Ragged batches in libns2hip: skipping the hidden row tiles of a sampling batch in every product.  An eleventh header of the C ABI,
- * parsed by _lib.py under the same rule as ns2hip.h into a table of its own (RAGGED_SKIP_SIGNATURES); the tables of the ten headers
- * before it are unchanged.  Status codes, ns2_last_error, ns2_linear_args, ns2_attn_args, ns2_weight, ns2_model and ns2_model_config
+/* Ragged batches in libns2hip: skipping the hidden row tiles of a sampling batch in every product.  Part of the C ABI: listed in
+ * _lib.HEADERS (naturalspeech2_pytorch_amd/_lib.py).  Status codes, ns2_last_error, ns2_linear_args, ns2_attn_args, ns2_weight, ns2_model and ns2_model_config
  * are those of ns2hip.h, which this header includes.
  *
  * ns2hip_ragged.h made a ragged batch correct: the lengths go to the self-attention, every other kernel computes every row.  Here the

@@ -1,6 +1,5 @@
-/* Ragged batches in libns2hip: skipping the hidden row tiles of a TRAINING batch in the products.  A twelfth header of the C ABI,
- * parsed by _lib.py under the same rule as ns2hip.h into a table of its own (RAGGED_SKIP_TRAIN_SIGNATURES); the tables of the eleven
- * headers before it are unchanged.  Status codes, ns2_last_error, ns2_linear_args and ns2_weight are those of ns2hip.h, which this
+/* Ragged batches in libns2hip: skipping the hidden row tiles of a TRAINING batch in the products.  Part of the C ABI: listed in
+ * _lib.HEADERS (naturalspeech2_pytorch_amd/_lib.py).  Status codes, ns2_last_error, ns2_linear_args and ns2_weight are those of ns2hip.h, which this
  * header includes.
  *
  * ns2hip_ragged_train.h made a ragged training batch correct: the lengths go to the self-attention in both directions, every other

@@ -1,6 +1,5 @@
-/* Ragged batches in the TRAINING pass of libns2hip: per-utterance lengths in the denoiser's self-attention, forward and backward.  A
- * sixth header of the C ABI, parsed by _lib.py under the same rule as ns2hip.h into tables of its own (RAGGED_TRAIN_SIGNATURES); the
- * tables of the other five headers are unchanged.  Status codes, ns2_last_error, ns2_attn_args and ns2_attn_bwd_args are those of
+/* Ragged batches in the TRAINING pass of libns2hip: per-utterance lengths in the denoiser's self-attention, forward and backward.
+ * Part of the C ABI: listed in _lib.HEADERS (naturalspeech2_pytorch_amd/_lib.py).  Status codes, ns2_last_error, ns2_attn_args and ns2_attn_bwd_args are those of
  * ns2hip.h, which this header includes.
  *
  * The definition is that of ns2hip_ragged.h, carried through the gradient: with lengths lens[i] in [1, N], utterance i contributes to

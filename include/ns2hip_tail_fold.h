@@ -1,6 +1,5 @@
-/* The Wavenet tail fold and the wide RMSNorm kernel in libns2hip.  One more header of the C ABI, parsed by _lib.py under the same rule as
- * ns2hip.h into a table of its own (TAIL_FOLD_SIGNATURES); the tables of the other headers are unchanged.  Status codes and
- * ns2_last_error are those of ns2hip.h, which this header includes.
+/* The Wavenet tail fold and the wide RMSNorm kernel in libns2hip.  Part of the C ABI: listed in _lib.HEADERS
+ * (naturalspeech2_pytorch_amd/_lib.py).  Status codes and ns2_last_error are those of ns2hip.h, which this header includes.
  *
  * Wavenet ends in `final_conv(sum of the blocks' skip convs)` (NS2:639-640, 685-686, 725): a Conv1d(dim, dim, 1) directly behind a sum of
  * L Conv1d(dim, dim, 1), i.e. a Linear behind a Linear over the L concatenated block outputs.  The pair is one Linear of K = L * dim:

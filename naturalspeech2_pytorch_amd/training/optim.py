@@ -12,7 +12,7 @@ import torch
 
 from .. import _lib
 
-_C = _lib.OPTIM_CONSTANTS
+_C = _lib.ABI["ns2hip_optim.h"].constants
 _ADAM_DEFAULTS = torch.optim.Adam([torch.zeros(1)]).defaults       # the keys a torch.optim.Adam param group has in this torch
 
 

@@ -3,7 +3,6 @@ entries refuse, the `head_dim_training` switch of Model / Transformer / the enco
 HIP pass (functions.py AttnFn: column offsets heads * head_dim, scale head_dim ** -0.5; model_pass.py: self, cross and perceiver attention)
 on tests/emu_backend_head_dim.py against the composite's autograd."""
 import ctypes
-import subprocess
 
 import pytest
 import torch
@@ -21,17 +20,13 @@ def rel(a, b):
 # ---- the C ABI
 def test_head_dim_train_header_parses_and_the_library_exports_it():
     P, I, L = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
-    assert _lib.head_dim_train_header_symbols() == ["ns2_attention_bwd_hd", "ns2_attention_delta_hd", "ns2_attention_train_fwd_hd"]
-    assert _lib.HEAD_DIM_TRAIN_SIGNATURES["ns2_attention_train_fwd_hd"] == (I, [P, P, P])
-    assert _lib.HEAD_DIM_TRAIN_SIGNATURES["ns2_attention_delta_hd"] == (I, [P, L, P, P, I, I, I, I, I, P, I, P])
-    assert _lib.HEAD_DIM_TRAIN_SIGNATURES["ns2_attention_bwd_hd"] == (I, [P, I, P, P])
-    others = [_lib.SIGNATURES, _lib.OPTIM_SIGNATURES, _lib.PITCH_SIGNATURES, _lib.RAGGED_SIGNATURES, _lib.FRONT_SIGNATURES,
-              _lib.RAGGED_TRAIN_SIGNATURES]
-    assert len(_lib.SIGNATURES) == 119 and not any(set(_lib.HEAD_DIM_TRAIN_SIGNATURES) & set(s) for s in others)
-    _lib.load()
-    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True).stdout
-    exported = {l.split()[-1] for l in out.splitlines() if " T ns2_" in l}
-    assert set(_lib.head_dim_train_header_symbols()) <= exported
+    assert _lib.header_symbols("ns2hip_head_dim_train.h") == ["ns2_attention_bwd_hd", "ns2_attention_delta_hd", "ns2_attention_train_fwd_hd"]
+    S = _lib.ABI["ns2hip_head_dim_train.h"].signatures
+    assert S["ns2_attention_train_fwd_hd"] == (I, [ctypes.POINTER(_lib.AttnArgs), P, P])
+    assert S["ns2_attention_delta_hd"] == (I, [P, L, P, P, I, I, I, I, I, P, I, P])
+    assert S["ns2_attention_bwd_hd"] == (I, [ctypes.POINTER(_lib.AttnBwdArgs), I, P, P])
+    assert len(_lib.ABI["ns2hip.h"].signatures) == 119
+    _lib.load()                                                                  # raises unless the library exports them
 
 
 def test_the_three_entries_refuse_before_any_device_call():

@@ -20,13 +20,25 @@ GOLD = os.path.join(ROOT, "tests", "golden")
 
 
 def test_library_exports_whole_abi():
-    """_lib derives SIGNATURES, the argument structs and the status constants from include/ns2hip.h, so header and table cannot disagree
-    by construction.  What still binds: the count, the constants, and rows pinned as the hand-written table had them -- one or more per
-    rule of the mapping (_lib's docstring), the long ones included -- so a change of the parser or of the rule shows."""
+    """_lib derives SIGNATURES, the argument structs and the status constants from the headers that _lib.HEADERS lists, so header and
+    table cannot disagree by construction.  What still binds, here for the whole ABI: the headers and the count of each, the unions as
+    the merge of the per-header tables (no name in two of them), the constants, and rows pinned as the hand-written table had them --
+    one or more per rule of the mapping (_lib's docstring), the long ones included -- so a change of the parser or of the rule shows."""
     import ctypes
     from ctypes import POINTER, c_char_p, c_void_p
     lib = _lib.load()                                   # raises if the .so or any symbol is missing
-    assert len(_lib.SIGNATURES) == 119 and _lib.header_symbols() == sorted(_lib.SIGNATURES)
+    counts = {"ns2hip.h": 119, "ns2hip_optim.h": 7, "ns2hip_pitch.h": 1, "ns2hip_ragged.h": 2, "ns2hip_ragged_front.h": 4,
+              "ns2hip_ragged_train.h": 2, "ns2hip_head_dim_train.h": 3, "ns2hip_ragged_audio.h": 3, "ns2hip_fold.h": 2,
+              "ns2hip_ragged_cond_train.h": 1, "ns2hip_ragged_skip.h": 7, "ns2hip_ragged_skip_train.h": 3, "ns2hip_tail_fold.h": 4}
+    assert list(_lib.ABI) == list(_lib.HEADERS) == list(counts)
+    assert {h: len(t.signatures) for h, t in _lib.ABI.items()} == counts
+    assert len(_lib.SIGNATURES) == 158 == sum(counts.values())
+    for i, union in enumerate((_lib.CONSTANTS, _lib.STRUCTS, _lib.SIGNATURES)):
+        pairs = [kv for t in _lib.ABI.values() for kv in t[i].items()]
+        assert len(pairs) == len(union) and dict(pairs) == union          # the merge, and no name in two headers
+    assert {h: len(t.constants) for h, t in _lib.ABI.items() if t.constants} == {"ns2hip.h": 5, "ns2hip_optim.h": 14}
+    assert _lib.header_symbols() == sorted(_lib.SIGNATURES)
+    assert all(_lib.header_symbols(h) == sorted(t.signatures) for h, t in _lib.ABI.items())
     assert (_lib.NS2_OK, _lib.NS2_ERR_ARG, _lib.NS2_ERR_HIP, _lib.NS2_ERR_STATE, _lib.NS2_UNAVAILABLE) == (0, -1, -2, -3, 1)
     P, I, F, L = c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_int64
     LinearArgs, ModelConfig = _lib.LinearArgs, _lib.ModelConfig
@@ -49,7 +61,9 @@ def test_library_exports_whole_abi():
     assert lib.ns2_version() >= 100
     out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True).stdout
     exported = {l.split()[-1] for l in out.splitlines() if " T ns2_" in l}
-    assert set(_lib.header_symbols()) <= exported
+    assert set(_lib.SIGNATURES) <= exported
+    for n, (res, args) in _lib.SIGNATURES.items():     # load() bound every entry as its header declares it
+        assert getattr(lib, n).argtypes == args and getattr(lib, n).restype == res, n
 
 
 def test_split_k_plan_host_arithmetic():
@@ -173,9 +187,10 @@ def test_derived_structs_have_the_layout_gcc_gives_every_field(tmp_path):
     import shutil
     if shutil.which("gcc") is None:
         pytest.skip("needs gcc")
-    assert sorted(_lib.STRUCTS) == ["ns2_attn_args", "ns2_attn_bwd_args", "ns2_linear_args", "ns2_model_config", "ns2_repack_part"]
+    structs = _lib.ABI["ns2hip.h"].structs
+    assert sorted(structs) == ["ns2_attn_args", "ns2_attn_bwd_args", "ns2_linear_args", "ns2_model_config", "ns2_repack_part"]
     lines = ["#include <stdio.h>", "#include <stddef.h>", '#include "ns2hip.h"', "int main(void) {"]
-    for name, cls in _lib.STRUCTS.items():
+    for name, cls in structs.items():
         lines.append(f'  printf("{name} %d\\n", (int)sizeof({name}));')
         for f, _ in cls._fields_:
             lines.append(f'  printf("{name}.{f} %d %d\\n", (int)offsetof({name}, {f}), (int)sizeof((({name}*)0)->{f}));')
@@ -185,7 +200,7 @@ def test_derived_structs_have_the_layout_gcc_gives_every_field(tmp_path):
     subprocess.run(["gcc", "-std=c99", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
     got = subprocess.run([str(exe)], check=True, capture_output=True, text=True, timeout=60).stdout.splitlines()
     want = []
-    for name, cls in _lib.STRUCTS.items():
+    for name, cls in structs.items():
         want.append(f"{name} {ctypes.sizeof(cls)}")
         want += [f"{name}.{f} {getattr(cls, f).offset} {getattr(cls, f).size}" for f, _ in cls._fields_]
     assert got == want and len(want) == 5 + 13 + 24 + 27 + 41 + 9
@@ -227,6 +242,49 @@ def test_header_parser_maps_by_one_rule_and_refuses_what_it_does_not_cover():
                        ("#define NS2_WORD sizeof(int)", "NS2_WORD")):
         with pytest.raises(_lib.Ns2Error, match=re.escape(named)):
             _lib.parse_header(bad)
+
+
+def _include_dir(tmp_path, texts):
+    """an include directory of the test's own: {file name: header text}"""
+    for name, text in texts.items():
+        (tmp_path / name).write_text(text)
+    return str(tmp_path)
+
+
+def test_load_abi_types_a_pointer_to_a_struct_of_an_earlier_header(tmp_path):
+    """a struct typedef'd in the first header and taken by `const T*` in the second: POINTER(the first header's class), the identical
+    class object, listed under the first header alone; in the other order the pointer is c_void_p, as the rule says"""
+    from ctypes import POINTER, c_int, c_void_p
+    texts = {"a.h": "#define NS2_A 1\ntypedef struct { int n; float* p; } ns2_blk;\nint ns2_first(const ns2_blk* blk);\n",
+             "b.h": '#include "a.h"\n#define NS2_B 2\nint ns2_second(const ns2_blk* blk, void* stream);\n'}
+    abi = _lib.load_abi(_include_dir(tmp_path, texts), ("a.h", "b.h"))
+    assert list(abi) == ["a.h", "b.h"] and all(isinstance(h, _lib.Header) for h in abi.values())
+    blk = abi["a.h"].structs["ns2_blk"]
+    assert list(abi["a.h"].structs) == ["ns2_blk"] and abi["b.h"].structs == {}
+    assert abi["a.h"].signatures == {"ns2_first": (c_int, [POINTER(blk)])}
+    assert abi["b.h"].signatures == {"ns2_second": (c_int, [POINTER(blk), c_void_p])}
+    assert abi["b.h"].signatures["ns2_second"][1][0]._type_ is blk
+    assert (abi["a.h"].constants, abi["b.h"].constants) == ({"NS2_A": 1}, {"NS2_B": 2})
+    assert _lib.load_abi(str(tmp_path), ("b.h", "a.h"))["b.h"].signatures == {"ns2_second": (c_int, [c_void_p, c_void_p])}
+
+
+@pytest.mark.parametrize("decl, symbol", (("int ns2_twice(int n);", "ns2_twice"), ("#define NS2_X 3", "NS2_X"),
+                                          ("typedef struct { int n; } ns2_blk;", "ns2_blk")), ids=("function", "constant", "struct"))
+def test_load_abi_refuses_a_name_declared_in_two_headers(tmp_path, decl, symbol):
+    inc = _include_dir(tmp_path, {"a.h": decl + "\nint ns2_a(void);\n", "b.h": "int ns2_b(void);\n" + decl + "\n"})
+    with pytest.raises(_lib.Ns2Error) as e:
+        _lib.load_abi(inc, ("a.h", "b.h"))
+    assert symbol in str(e.value) and "a.h" in str(e.value) and "b.h" in str(e.value)
+    assert list(_lib.load_abi(inc, ("a.h",))) == ["a.h"] and list(_lib.load_abi(inc, ("b.h",))) == ["b.h"]     # each alone is fine
+
+
+def test_load_abi_names_the_file_it_misses_and_the_file_it_cannot_read(tmp_path):
+    inc = _include_dir(tmp_path, {"a.h": "int ns2_a(void);\n", "b.h": "int ns2_b(void);\nlong ns2_ret(void);\n"})
+    with pytest.raises(_lib.Ns2Error, match=re.escape(os.path.join(inc, "c.h") + " not found: the binding is derived from the header")):
+        _lib.load_abi(inc, ("a.h", "c.h"))
+    with pytest.raises(_lib.Ns2Error) as e:
+        _lib.load_abi(inc, ("a.h", "b.h"))
+    assert "ns2_ret" in str(e.value) and "b.h:" in str(e.value) and "a.h" not in str(e.value) and "ns2hip.h" not in str(e.value)
 
 
 def test_attention_entries_refuse_bad_argument_blocks_before_any_device_call():

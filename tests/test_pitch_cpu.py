@@ -2,7 +2,6 @@
 whose F0 is known, the shape contract, the C ABI's argument checks, and NaturalSpeech2.forward(raw audio, text=...) computing
 its own pitch.  No parity with pyworld / Kaldi is claimed, so none is tested."""
 import ctypes
-import subprocess
 
 import pytest
 import torch
@@ -95,12 +94,10 @@ def test_unsupported_configuration_takes_the_composite(monkeypatch):
 def test_abi_symbol_and_argument_checks():
     """no GPU here: an entry point that reached a device call would fail with NS2_ERR_HIP, not NS2_ERR_ARG"""
     P, I, L, F = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
-    assert _lib.PITCH_SIGNATURES == {"ns2_pitch_yin": (I, [P, I, L, I, I, I, I, F, P, P])}
-    assert _lib.pitch_header_symbols() == ["ns2_pitch_yin"] and "ns2_pitch_yin" not in _lib.SIGNATURES
-    lib = _lib.load()
-    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True).stdout
-    assert any(line.split()[-1] == "ns2_pitch_yin" and " T " in line for line in out.splitlines())
-    assert lib.ns2_pitch_yin.argtypes == _lib.PITCH_SIGNATURES["ns2_pitch_yin"][1]
+    assert _lib.ABI["ns2hip_pitch.h"].signatures == {"ns2_pitch_yin": (I, [P, I, L, I, I, I, I, F, P, P])}
+    assert _lib.header_symbols("ns2hip_pitch.h") == ["ns2_pitch_yin"]
+    lib = _lib.load()                                 # raises unless the library exports it
+    assert lib.ns2_pitch_yin.argtypes == _lib.SIGNATURES["ns2_pitch_yin"][1] == [P, I, L, I, I, I, I, F, P, P]
     err = lambda: lib.ns2_last_error().decode()       # noqa: E731
     ok = dict(audio=16, B=1, L=4000, fs=24000, hop=160, tau_min=37, tau_max=339, thr=0.1, f0=16)
 

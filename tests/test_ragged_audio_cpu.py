@@ -26,26 +26,21 @@ HOP = EncodecWrapperHIP.seq_len_multiple_of                 # 320 samples per co
 # ---- 1. the C ABI
 def test_ragged_audio_header_is_plain_c_parses_and_the_library_exports_it(tmp_path):
     P, I, L, F = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
-    assert _lib.ragged_audio_header_symbols() == ["ns2_audio_to_mel_lens", "ns2_pitch_yin_lens", "ns2_rvq_ce_lens"]
-    sig = _lib.RAGGED_AUDIO_SIGNATURES
+    assert _lib.header_symbols("ns2hip_ragged_audio.h") == ["ns2_audio_to_mel_lens", "ns2_pitch_yin_lens", "ns2_rvq_ce_lens"]
+    sig = _lib.ABI["ns2hip_ragged_audio.h"].signatures
     assert sig["ns2_audio_to_mel_lens"] == (I, [P, I, L, I, I, P, P, P, P, I, I, I, I, P, P, P])
     assert sig["ns2_pitch_yin_lens"] == (I, [P, I, L, I, I, I, I, F, P, P, P])
     assert sig["ns2_rvq_ce_lens"] == (I, [P, P, P, P, P, P, P, P, I, I, P, I, I, I, P, L, P])
     # each is the entry without lengths plus the lengths (ns2_rvq_ce: M replaced by B, n, row_lens)
-    mel, yin, ce = _lib.SIGNATURES["ns2_audio_to_mel"][1], _lib.PITCH_SIGNATURES["ns2_pitch_yin"][1], _lib.SIGNATURES["ns2_rvq_ce"][1]
+    mel, yin, ce = (_lib.SIGNATURES[k][1] for k in ("ns2_audio_to_mel", "ns2_pitch_yin", "ns2_rvq_ce"))
     assert sig["ns2_audio_to_mel_lens"][1] == mel[:-1] + [P] + mel[-1:] and sig["ns2_pitch_yin_lens"][1] == yin[:-1] + [P] + yin[-1:]
     assert sig["ns2_rvq_ce_lens"][1] == ce[:8] + [I, I, P] + ce[9:]
-    # the tables of the other seven headers are unchanged
-    others = [_lib.SIGNATURES, _lib.OPTIM_SIGNATURES, _lib.PITCH_SIGNATURES, _lib.RAGGED_SIGNATURES, _lib.FRONT_SIGNATURES,
-              _lib.RAGGED_TRAIN_SIGNATURES, _lib.HEAD_DIM_TRAIN_SIGNATURES]
-    assert [len(s) for s in others] == [119, 7, 1, 2, 4, 2, 3] and not any(set(sig) & set(s) for s in others)
+    # the tables of the seven headers before it are unchanged
+    assert [len(_lib.ABI[h].signatures) for h in _lib.HEADERS[:7]] == [119, 7, 1, 2, 4, 2, 3]
     src = tmp_path / "abi.c"
     src.write_text('#include "ns2hip_ragged_audio.h"\nint main(void) { return 0; }\n')
     subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"), "-fsyntax-only", str(src)], check=True)
-    lib = _lib.load()
-    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True).stdout
-    exported = {l.split()[-1] for l in out.splitlines() if " T ns2_" in l}
-    assert set(sig) <= exported
+    lib = _lib.load()                                       # raises unless the library exports them
     assert all(getattr(lib, k).argtypes == v[1] for k, v in sig.items())
 
 

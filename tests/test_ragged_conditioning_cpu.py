@@ -81,10 +81,8 @@ def _same(a, b):
 
 # ------------------------------------------------------------------------------------------------ the ABI
 def test_header_table_and_entry():
-    assert _lib.ragged_cond_train_header_symbols() == ["ns2_groupnorm_silu_bwd_lens"]
-    for other in (_lib.SIGNATURES, _lib.FRONT_SIGNATURES, _lib.RAGGED_TRAIN_SIGNATURES, _lib.RAGGED_AUDIO_SIGNATURES, _lib.FOLD_SIGNATURES):
-        assert not set(_lib.RAGGED_COND_TRAIN_SIGNATURES) & set(other)              # the other tables describe their own headers alone
-    res, args = _lib.RAGGED_COND_TRAIN_SIGNATURES["ns2_groupnorm_silu_bwd_lens"]
+    assert _lib.header_symbols("ns2hip_ragged_cond_train.h") == ["ns2_groupnorm_silu_bwd_lens"]
+    res, args = _lib.ABI["ns2hip_ragged_cond_train.h"].signatures["ns2_groupnorm_silu_bwd_lens"]
     ref_res, ref_args = _lib.SIGNATURES["ns2_groupnorm_silu_bwd"]
     assert res is ref_res and len(args) == len(ref_args) + 1                        # the entry that exists plus row_lens
     src = open(os.path.join(ROOT, "naturalspeech2_pytorch_amd", "csrc", "capi_train.cpp")).read()

@@ -94,14 +94,12 @@ def test_training_path_names_lens():
 # ---- the C ABI
 def test_ragged_header_parses_and_the_library_exports_it():
     P, I, L = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
-    assert _lib.ragged_header_symbols() == ["ns2_attention_fwd_lens", "ns2_model_forward_lens"]
-    assert _lib.RAGGED_SIGNATURES["ns2_attention_fwd_lens"] == (I, [P, P, P])
-    assert _lib.RAGGED_SIGNATURES["ns2_model_forward_lens"] == (I, [P, P, P, P, P, P, I, P, I, I, P, L, P])
-    assert len(_lib.SIGNATURES) == 119 and not set(_lib.RAGGED_SIGNATURES) & set(_lib.SIGNATURES)     # ns2hip.h's tables describe it alone
-    _lib.load()
-    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True).stdout
-    exported = {l.split()[-1] for l in out.splitlines() if " T ns2_" in l}
-    assert set(_lib.ragged_header_symbols()) <= exported
+    assert _lib.header_symbols("ns2hip_ragged.h") == ["ns2_attention_fwd_lens", "ns2_model_forward_lens"]
+    S = _lib.ABI["ns2hip_ragged.h"].signatures
+    assert S["ns2_attention_fwd_lens"] == (I, [ctypes.POINTER(_lib.AttnArgs), P, P])
+    assert S["ns2_model_forward_lens"] == (I, [P, P, P, P, P, P, I, P, I, I, P, L, P])
+    assert len(_lib.ABI["ns2hip.h"].signatures) == 119                           # ns2hip.h's tables describe it alone
+    _lib.load()                                                                  # raises unless the library exports them
 
 
 def test_c99_caller_includes_both_headers_and_links(tmp_path):

@@ -4,7 +4,6 @@ formula of the measurement tool, and the `ragged_skip` switch of Model on a reco
 import ctypes
 import importlib.util
 import os
-import subprocess
 
 import pytest
 import torch
@@ -17,22 +16,17 @@ ENTRIES = ["ns2_attention_fwd_skip", "ns2_debug_gemm_route_launches", "ns2_debug
            "ns2_wavenet_block_lens"]
 
 
-def test_eleventh_header_parses_into_a_table_of_its_own_and_is_exported():
-    P, I, L = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
-    S = _lib.RAGGED_SKIP_SIGNATURES
-    assert _lib.ragged_skip_header_symbols() == ENTRIES
-    assert S["ns2_linear_lens"] == (I, [P, P, I, P]) and S["ns2_attention_fwd_skip"] == (I, [P, P, P, P])
-    assert S["ns2_model_forward_lens_skip"] == _lib.RAGGED_SIGNATURES["ns2_model_forward_lens"] == (I, [P, P, P, P, P, P, I, P, I, I, P, L, P])
+def test_ragged_skip_header_parses_and_the_library_exports_it():
+    P, I, L, PTR = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.POINTER
+    S = _lib.ABI["ns2hip_ragged_skip.h"].signatures
+    assert _lib.header_symbols("ns2hip_ragged_skip.h") == ENTRIES
+    assert S["ns2_linear_lens"] == (I, [PTR(_lib.LinearArgs), P, I, P]) and S["ns2_attention_fwd_skip"] == (I, [PTR(_lib.AttnArgs), P, P, P])
+    assert S["ns2_model_forward_lens_skip"] == _lib.SIGNATURES["ns2_model_forward_lens"] == (I, [P, P, P, P, P, P, I, P, I, I, P, L, P])
     assert S["ns2_wavenet_block_lens"] == (I, [P, P, P, I, I, I, I, P, P, P, I, P, P, I, I, P, P])
-    assert S["ns2_debug_skip_rule"] == (I, [P, I, I, P]) and S["ns2_debug_skip_last"] == (I, []) and S["ns2_debug_gemm_route_launches"] == (L, [I])
-    others = [_lib.SIGNATURES, _lib.OPTIM_SIGNATURES, _lib.PITCH_SIGNATURES, _lib.RAGGED_SIGNATURES, _lib.FRONT_SIGNATURES,
-              _lib.RAGGED_TRAIN_SIGNATURES, _lib.HEAD_DIM_TRAIN_SIGNATURES, _lib.RAGGED_AUDIO_SIGNATURES, _lib.FOLD_SIGNATURES,
-              _lib.RAGGED_COND_TRAIN_SIGNATURES]
-    assert len(_lib.SIGNATURES) == 119 and not any(set(S) & set(o) for o in others)     # the other ten tables describe their headers alone
-    _lib.load()
-    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True).stdout
-    exported = {l.split()[-1] for l in out.splitlines() if " T ns2_" in l}
-    assert set(ENTRIES) <= exported
+    assert S["ns2_debug_skip_rule"] == (I, [PTR(_lib.ModelConfig), I, I, P])
+    assert S["ns2_debug_skip_last"] == (I, []) and S["ns2_debug_gemm_route_launches"] == (L, [I])
+    assert len(_lib.ABI["ns2hip.h"].signatures) == 119
+    _lib.load()                                                                  # raises unless the library exports them
 
 
 def _cfg(dim, depth, precision, heads=8, dim_head=64):

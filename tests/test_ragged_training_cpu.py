@@ -3,7 +3,6 @@ the `ragged_training` switch of Model, the composite restatement of the rule -- 
 and to every gradient what it contributes alone at lens[i] frames --, the host logic of the HIP pass (functions.py / model_pass.py on
 tests/emu_backend_ragged.py) against the composite's autograd, and the masked loss of NaturalSpeech2.forward(audio_lens=)."""
 import ctypes
-import subprocess
 
 import pytest
 import torch
@@ -91,15 +90,12 @@ def case(request):
 # ---- the C ABI
 def test_ragged_train_header_parses_and_the_library_exports_it():
     P, I = ctypes.c_void_p, ctypes.c_int
-    assert _lib.ragged_train_header_symbols() == ["ns2_attention_bwd_lens", "ns2_attention_train_fwd_lens"]
-    assert _lib.RAGGED_TRAIN_SIGNATURES["ns2_attention_train_fwd_lens"] == (I, [P, P, P])
-    assert _lib.RAGGED_TRAIN_SIGNATURES["ns2_attention_bwd_lens"] == (I, [P, P, P])
-    others = [_lib.SIGNATURES, _lib.OPTIM_SIGNATURES, _lib.PITCH_SIGNATURES, _lib.RAGGED_SIGNATURES, _lib.FRONT_SIGNATURES]
-    assert len(_lib.SIGNATURES) == 119 and not any(set(_lib.RAGGED_TRAIN_SIGNATURES) & set(s) for s in others)
-    _lib.load()
-    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True).stdout
-    exported = {l.split()[-1] for l in out.splitlines() if " T ns2_" in l}
-    assert set(_lib.ragged_train_header_symbols()) <= exported
+    assert _lib.header_symbols("ns2hip_ragged_train.h") == ["ns2_attention_bwd_lens", "ns2_attention_train_fwd_lens"]
+    S = _lib.ABI["ns2hip_ragged_train.h"].signatures
+    assert S["ns2_attention_train_fwd_lens"] == (I, [ctypes.POINTER(_lib.AttnArgs), P, P])
+    assert S["ns2_attention_bwd_lens"] == (I, [ctypes.POINTER(_lib.AttnBwdArgs), P, P])
+    assert len(_lib.ABI["ns2hip.h"].signatures) == 119
+    _lib.load()                                                                  # raises unless the library exports them
 
 
 def test_the_two_entries_refuse_before_any_device_call():

@@ -14,9 +14,8 @@ from tests.trainer_ref64 import Ref64
 
 def test_second_header_parses_by_the_one_rule_and_is_exported():
     P, I, L, F = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
-    with open(_lib.OPTIM_HEADER_PATH) as f:
-        consts, structs, sigs = _lib.parse_header(f.read())
-    assert sorted(sigs) == _lib.optim_header_symbols() == sorted(_lib.OPTIM_SIGNATURES)
+    consts, structs, sigs = _lib.ABI["ns2hip_optim.h"]
+    assert sorted(sigs) == _lib.header_symbols("ns2hip_optim.h")
     assert sorted(structs) == ["ns2_optim_config", "ns2_optim_tensor"]
     assert [n for n, _ in structs["ns2_optim_tensor"]._fields_] == ["param", "grad", "exp_avg", "exp_avg_sq", "ema", "numel"]
     assert [n for n, _ in structs["ns2_optim_config"]._fields_] == ["beta1", "beta2", "eps", "max_grad_norm", "ema_update_every"]
@@ -31,17 +30,15 @@ def test_second_header_parses_by_the_one_rule_and_is_exported():
         "ns2_optim_mark": (I, [P, P]),
         "ns2_optim_step": (I, [P, I, L, P, ctypes.POINTER(C), P]),
     }
-    assert _lib.OPTIM_SIGNATURES == pinned
-    assert consts == _lib.OPTIM_CONSTANTS and consts["NS2_OPTIM_CHUNK"] % 1024 == 0 and consts["NS2_OPTIM_STATE_WORDS"] == 128
-    # the tables of ns2hip.h describe ns2hip.h alone
-    assert len(_lib.SIGNATURES) == 119 and not set(_lib.SIGNATURES) & set(sigs) and _lib.header_symbols() == sorted(_lib.SIGNATURES)
-    assert sorted(_lib.STRUCTS) == ["ns2_attn_args", "ns2_attn_bwd_args", "ns2_linear_args", "ns2_model_config", "ns2_repack_part"]
-    assert not any(k.startswith("NS2_OPTIM") for k in _lib.CONSTANTS)
-    lib = _lib.load()                                   # binds both sets
-    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True).stdout
-    exported = {l.split()[-1] for l in out.splitlines() if " T ns2_" in l}
-    assert set(sigs) <= exported
-    assert all(getattr(lib, n).argtypes == a and getattr(lib, n).restype == r for n, (r, a) in _lib.OPTIM_SIGNATURES.items())
+    assert sigs == pinned and all(_lib.SIGNATURES[n] == row for n, row in pinned.items())
+    assert len(consts) == 14 and consts["NS2_OPTIM_CHUNK"] % 1024 == 0 and consts["NS2_OPTIM_STATE_WORDS"] == 128
+    assert (T, C) == (structs["ns2_optim_tensor"], structs["ns2_optim_config"])
+    # the tables of ns2hip.h describe ns2hip.h alone (that no name is in two headers, and that the library exports and binds every
+    # one: test_host_cpu.py::test_library_exports_whole_abi)
+    first = _lib.ABI["ns2hip.h"]
+    assert len(first.signatures) == 119
+    assert sorted(first.structs) == ["ns2_attn_args", "ns2_attn_bwd_args", "ns2_linear_args", "ns2_model_config", "ns2_repack_part"]
+    assert not any(k.startswith("NS2_OPTIM") for k in first.constants)
 
 
 def test_bad_arguments_come_back_as_codes_before_any_device_call():
@@ -183,7 +180,7 @@ def test_ref64_agrees_with_torch_adam_in_fp64():
 
 def test_training_exports():
     assert training.HipAdam is HipAdam and training.Trainer is Trainer
-    assert os.path.exists(_lib.OPTIM_HEADER_PATH)
+    assert os.path.exists(os.path.join(_lib.INCLUDE_DIR, "ns2hip_optim.h")) and "ns2hip_optim.h" in _lib.HEADERS
 
 
 def test_second_header_is_plain_c_and_a_c_caller_links(tmp_path):
@@ -210,7 +207,7 @@ int main(void) {
 }
 ''')
     exe, libdir = tmp_path / "caller", os.path.dirname(_lib.LIB_PATH)
-    inc = os.path.join(os.path.dirname(_lib.OPTIM_HEADER_PATH))
+    inc = _lib.INCLUDE_DIR
     subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-pedantic", "-I", inc, "-fsyntax-only", str(src)], check=True)
     subprocess.run(["gcc", "-std=c99", "-I", inc, str(src), "-o", str(exe), "-L", libdir, "-lns2hip", "-Wl,-rpath," + libdir], check=True)
     out = [int(v) for v in subprocess.run([str(exe)], check=True, capture_output=True, text=True, timeout=120).stdout.split()]

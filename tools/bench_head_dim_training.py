@@ -36,8 +36,6 @@ ap.add_argument("--skip-step", action="store_true")
 args = ap.parse_args()
 
 from naturalspeech2_pytorch_amd import _lib                                                # noqa: E402
-if args.child_bwd64 and os.environ.get("NS2_BENCH_PARENT"):
-    _lib.HEAD_DIM_TRAIN_SIGNATURES.clear()                  # the parent's library has no seventh header; head dim 64 calls none of it
 from naturalspeech2_pytorch_amd import Model, ops, autograd_path                           # noqa: E402
 from naturalspeech2_pytorch_amd.training import HipBackend, model_forward_train           # noqa: E402
 
@@ -148,8 +146,6 @@ if args.parent_lib:
     for _ in range(args.repeats):                           # alternating: a fresh process per library and repeat
         for k, path in libs.items():
             env = dict(os.environ, NS2_LIB=path)
-            if k == "parent":
-                env["NS2_BENCH_PARENT"] = "1"
             out = subprocess.run([sys.executable, os.path.abspath(__file__), "--child-bwd64"], env=env, capture_output=True, text=True, timeout=120)
             assert out.returncode == 0, out.stderr[-2000:]
             ms[k].append(json.loads(out.stdout.strip().splitlines()[-1])["bwd64_ms"])
