@@ -10,6 +10,7 @@ from .duration_pitch import DurationPitchPredictor          # noqa: F401
 from .aligner import Aligner                                # noqa: F401
 from .audio_to_mel import AudioToMel                        # noqa: F401
 from .pitch import PitchExtractor                           # noqa: F401
+from .resample import Resample                              # noqa: F401
 from .seanet import SEANetDecoderHIP, SEANetEncoderHIP      # noqa: F401
 
-__all__ = ["Model", "NaturalSpeech2", "Transformer", "PhonemeEncoder", "SpeechPromptEncoder", "DurationPitchPredictor", "Aligner", "AudioToMel", "PitchExtractor", "EncodecWrapperHIP", "HipRVQ", "SEANetEncoderHIP", "SEANetDecoderHIP", "Ns2Error", "load_library"]
+__all__ = ["Model", "NaturalSpeech2", "Transformer", "PhonemeEncoder", "SpeechPromptEncoder", "DurationPitchPredictor", "Aligner", "AudioToMel", "PitchExtractor", "Resample", "EncodecWrapperHIP", "HipRVQ", "SEANetEncoderHIP", "SEANetDecoderHIP", "Ns2Error", "load_library"]

@@ -20,6 +20,7 @@ import torch.nn.functional as F
 
 from . import ops
 from ._cache import PackedCache
+from .resample import Resample
 
 
 RQ_BACKENDS = ("composite", "hip")           # of `codec.rq`, the RVQ cross-entropy term of the training loss
@@ -199,11 +200,19 @@ class EncodecWrapperHIP(nn.Module):
         self.rvq._norm.refresh([self.rvq.codebooks])
 
     @torch.no_grad()
-    def forward(self, x, return_encoded=True, curtail_from_left=False, **kwargs):
-        """x: raw audio [b, t] (needs `encoder`) or latents [b, n, 128] -> (emb [b,n,128], codes [b,n,Q], None)."""
+    def forward(self, x, return_encoded=True, curtail_from_left=False, input_sample_hz=None, **kwargs):
+        """x: raw audio [b, t] (needs `encoder`) or latents [b, n, 128] -> (emb [b,n,128], codes [b,n,Q], None).
+        input_sample_hz (audiolm_pytorch's keyword): the rate of the raw audio; another rate than `target_sample_hz` is resampled
+        (resample.py) before the audio is curtailed.  Latents have no rate: with them a foreign rate is a ValueError."""
+        foreign = input_sample_hz is not None and int(input_sample_hz) != int(self.target_sample_hz)
+        if foreign and x.ndim != 2:
+            raise ValueError(f"input_sample_hz={input_sample_hz} with latents {list(x.shape)}: only raw audio [b, t] has a sample rate to "
+                             f"convert to {self.target_sample_hz}")
         if x.ndim == 2:
             if self.encoder is None:
                 raise RuntimeError("raw audio needs the SEANet encoder (out of scope of the HIP path): pass encoder=")
+            if foreign:
+                x = Resample(int(input_sample_hz), int(self.target_sample_hz))(x)
             t = x.shape[-1] // self.seq_len_multiple_of * self.seq_len_multiple_of
             if t == 0:
                 raise ValueError(f"audio shorter than one codec frame ({self.seq_len_multiple_of} samples)")   # x[..., -0:] would keep everything

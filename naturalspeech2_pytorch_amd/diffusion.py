@@ -41,6 +41,7 @@ from torch import nn
 import torch.nn.functional as F
 
 from . import ops
+from .resample import Resample
 
 
 def sigmoid_schedule(t, start=-3, end=3, tau=1, clamp_min=1e-9):      # NS2:1144-1148
@@ -348,6 +349,23 @@ class NaturalSpeech2(nn.Module):
             lens = lens // hop
         return lens
 
+    def _resampler(self, sample_hz):
+        """input_sample_hz= / prompt_sample_hz= -> the Resample to the codec's rate; None when there is nothing to convert"""
+        if sample_hz is None or int(sample_hz) == int(self.target_sample_hz):
+            return None
+        return Resample(int(sample_hz), int(self.target_sample_hz))
+
+    def _resample_raw(self, rs, x, lens=None):
+        """raw audio [b, S] at another rate -> (the audio at the codec's rate, the lengths there).  Without lengths that is `rs(x)`.
+        With `lens` (samples of the INPUT per utterance) utterance i is resampled as it is alone (Resample(lens=)), its length becomes
+        out_lens(lens[i]) // hop * hop -- whole codec frames, formed where the lengths live, no host read -- and the batch is cut to
+        whole frames too, so the values can go through _check_raw_sample_lens as lengths given at the codec's rate do."""
+        if lens is None:
+            return rs(x), None
+        hop = int(self.seq_len_multiple_of)
+        y = rs(x, lens=lens)
+        return y[..., :y.shape[-1] // hop * hop], rs.out_lens(lens) // hop * hop
+
     def _encode_prompt(self, prompt, prompt_enc):
         if prompt_enc is not None:
             return prompt_enc
@@ -401,7 +419,7 @@ class NaturalSpeech2(nn.Module):
 
     @torch.no_grad()
     def sample(self, *, length=None, prompt=None, batch_size=1, cond_scale=1., text=None, text_lens=None,
-               cond=None, prompt_enc=None, noise=None, use_graph=False, return_lens=False, prompt_lens=None):
+               cond=None, prompt_enc=None, noise=None, use_graph=False, return_lens=False, prompt_lens=None, prompt_sample_hz=None):
         """NS2:1457-1501.  Extra keywords (not in the reference): `cond` / `prompt_enc` = pre-computed conditioning (module
         docstring), `noise` = injected initial latents (parity tests), `use_graph` = HIP-graph replay of the step.
 
@@ -420,7 +438,17 @@ class NaturalSpeech2(nn.Module):
         each length, and the padded length, must be a positive multiple of the codec's `seq_len_multiple_of`, and at least the codec's
         `min_causal_prompt_frames` frames (7 for the 24 kHz SEANet: its reflect padding mirrors frames 1 .. 6) -- ValueError otherwise,
         one host check before the loop; the encoder being causal then keeps the padding out of an utterance's frames.
-        Without `prompt_lens`, `text_lens` does exactly what it did: it zeroes the padding phonemes' durations."""
+        Without `prompt_lens`, `text_lens` does exactly what it did: it zeroes the padding phonemes' durations.
+
+        `prompt_sample_hz` (not in the reference): the rate of a raw-audio prompt.  Another rate than the codec's is resampled first
+        (resample.py), before `process_prompt`; `prompt_lens` then count samples of the INPUT and become
+        out_lens(prompt_lens) // seq_len_multiple_of * seq_len_multiple_of before the check above.  A prompt that is not raw audio
+        has no rate: ValueError."""
+        rs = self._resampler(prompt_sample_hz)
+        if rs is not None:
+            if prompt is None or prompt.ndim != 2 or prompt_enc is not None:
+                raise ValueError(f"prompt_sample_hz={prompt_sample_hz}: only a raw-audio prompt [b, samples] has a sample rate to convert")
+            prompt, prompt_lens = self._resample_raw(rs, prompt, prompt_lens)
         if length is None and (text is None or cond is not None):
             raise ValueError("sample(length=None) takes the utterances' lengths from the predicted durations: it needs text= (and no cond=)")
         lens = None
@@ -551,7 +579,8 @@ class NaturalSpeech2(nn.Module):
         return cond, dict(duration=duration_loss, pitch=pitch_loss, align=align_loss, bin=bin_loss, aux=aux)
 
     def forward(self, audio, text=None, text_lens=None, mel=None, mel_lens=None, codes=None, prompt=None, pitch=None,
-                *args, cond=None, prompt_enc=None, times=None, noise=None, return_aux_losses=False, audio_lens=None, **kwargs):
+                *args, cond=None, prompt_enc=None, times=None, noise=None, return_aux_losses=False, audio_lens=None,
+                input_sample_hz=None, **kwargs):
         """Reference signature; `cond`, `prompt_enc` (module docstring) and `times`, `noise` (deterministic parity tests) are
         the keyword-only extras.  The model call runs the autograd composite when gradients are required.
 
@@ -591,8 +620,29 @@ class NaturalSpeech2(nn.Module):
         `prompt_enc`, the predictor and the model, together with `audio_lens` or without it; `text_lens` goes to the phoneme encoder's key
         mask and the predictor; and with `return_aux_losses=True` the duration and pitch terms are the mean over the utterances of each one's
         own mean absolute error over its phonemes [0, text_lens[i]) (text_forward_cond).  What ids, prompt rows, mel and pitch frames hold
-        behind their lengths reaches no term of the loss and no gradient."""
+        behind their lengths reaches no term of the loss and no gradient.
+
+        `input_sample_hz` (keyword-only; the keyword of audiolm_pytorch's EncodecWrapper.forward): the rate of the raw `audio` and of a
+        raw `prompt`.  Another rate than the codec's is resampled first (resample.py), so mel, pitch and codec all see the target rate.
+        With `ragged_audio=True` and `audio_lens`, the lengths count samples of the INPUT: utterance i is resampled as it is alone, its
+        length becomes out_lens(audio_lens[i]) // hop * hop (formed on the device) and the resampled batch is cut to whole codec frames;
+        the check above then applies to the converted values (a list or a CPU tensor only, never during capture), so the padded
+        input length need not be a multiple of hop.  `prompt_lens` of a raw prompt are converted the same way.  Latents have no
+        rate: a foreign rate with neither raw audio nor a raw prompt is a ValueError."""
         is_raw = audio.ndim == 2
+        rs = self._resampler(input_sample_hz)
+        if rs is not None:
+            raw_prompt = prompt is not None and prompt.ndim == 2 and prompt_enc is None
+            if not is_raw and not raw_prompt:
+                raise ValueError(f"input_sample_hz={input_sample_hz}: neither `audio` nor `prompt` is raw audio [b, samples]; latents have no "
+                                 f"sample rate to convert")
+            if raw_prompt:
+                # (without ragged_conditioning `prompt_lens` is tolerated and unused, as it is at the codec's rate: the whole prompt counts)
+                prompt, p_lens = self._resample_raw(rs, prompt, kwargs.get("prompt_lens") if getattr(self, "ragged_conditioning", False) else None)
+                if p_lens is not None:
+                    kwargs = dict(kwargs, prompt_lens=p_lens)
+            if is_raw and audio_lens is None:
+                audio = rs(audio)
         ragged_audio = bool(getattr(self, "ragged_audio", False))
         ragged_cond = bool(getattr(self, "ragged_conditioning", False))
         sample_lens = None                                                            # ragged raw audio: the sample counts, on the device
@@ -613,6 +663,8 @@ class NaturalSpeech2(nn.Module):
                 raise ValueError(f"audio_lens must hold one frame count per utterance: [{audio.shape[0]}], got {list(audio_lens.shape)}")
             if is_raw:
                 assert self.codec is not None, "codec must be passed in if one were to train on raw audio"
+                if rs is not None:                                                    # the lengths count input samples
+                    audio, audio_lens = self._resample_raw(rs, audio, audio_lens)
                 if not audio_lens.is_cuda and not (audio.is_cuda and torch.cuda.is_current_stream_capturing()):
                     _check_raw_sample_lens(self.codec, int(self.seq_len_multiple_of), audio_lens.long(), audio.shape[-1],
                                            "raw audio with audio_lens", "utterance")

@@ -662,3 +662,27 @@ def pitch_yin(audio: torch.Tensor, sample_rate: int, hop_length: int, tau_min: i
         check(lib.ns2_pitch_yin(audio[b0].data_ptr(), nb, L, sample_rate, hop_length, tau_min, tau_max, threshold, out[b0].data_ptr(),
                                 _stream()), "ns2_pitch_yin")
     return out
+
+
+# ---- Resample (csrc/resample.hip)
+def resample(audio: torch.Tensor, up: int, down: int, width: int, taps: torch.Tensor, lens: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """audio [B, L] fp32 -> [B, ceil(up L / down)] (ns2_resample, include/ns2hip_resample.h); taps: the transposed table [T, up] fp32 on
+    the device, T = 2 width + down.  lens [B] (a CUDA integer tensor of sample counts): ns2_resample_lens.  A shape the kernel does
+    not take raises (rc NS2_UNAVAILABLE): callers ask ns2_resample_frames_per_block first."""
+    audio, taps = _f32(audio), _f32(taps)
+    B, L = audio.shape
+    assert taps.shape == (2 * width + down, up), f"taps must be the transposed table [{2 * width + down}, {up}]"
+    L_out = (L * up + down - 1) // down
+    out = torch.empty(B, L_out, dtype=torch.float32, device=audio.device)
+    lib = _lib.load()
+    ln = None if lens is None else _lens(lens)     # held until the launch
+    assert ln is None or ln.shape[0] == B, f"lens must hold one sample count per utterance: [{B}]"
+    for b0 in range(0, B, 65535):                 # grid.y holds at most 65535 utterances
+        nb = min(65535, B - b0)
+        if lens is not None:
+            check(lib.ns2_resample_lens(audio[b0].data_ptr(), nb, L, up, down, width, taps.data_ptr(), out[b0].data_ptr(), L_out,
+                                        ln[b0:].data_ptr(), _stream()), "ns2_resample_lens")
+            continue
+        check(lib.ns2_resample(audio[b0].data_ptr(), nb, L, up, down, width, taps.data_ptr(), out[b0].data_ptr(), L_out, _stream()),
+              "ns2_resample")
+    return out
