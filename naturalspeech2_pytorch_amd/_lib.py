@@ -7,7 +7,7 @@ library does not export the full ABI -- there is no CPU / PyTorch fallback for t
 The headers are the one owner of the ABI.  A header's `#define NS2_<NAME> <int>` lines become constants, every
 `typedef struct { ... } name;` a ctypes.Structure, every `ret ns2_name(args);` a row of SIGNATURES; ABI keeps the three tables of
 each header, CONSTANTS / STRUCTS / SIGNATURES are their unions, and no name may be declared twice.  A new entry point needs its
-declaration in a header and nothing here; a new header needs its name in HEADERS.  One mapping rule, and nothing is guessed (what it
+declaration in the header of its concern, behind the entry it varies, and nothing here.  One mapping rule, and nothing is guessed (what it
 does not cover raises Ns2Error naming the file and the declaration):
     int -> c_int;  unsigned, unsigned int -> c_uint;  uint32_t -> c_uint32;  int64_t -> c_int64;  float -> c_float;
     double -> c_double;  a void return -> None;  const char* -> c_char_p;
@@ -18,12 +18,6 @@ does not cover raises Ns2Error naming the file and the declaration):
 A header cannot say whether an `int*` is a host out-parameter or device memory (most are device pointers, passed as
 integers), so host out-parameters are c_void_p too: byref(), a ctypes array and None all pass, but ctypes no longer checks
 their element type.  That is the accepted price of having no second, hand-kept table.
-
-EXTRA_HEADERS is a stopgap.  tests/test_host_cpu.py pins HEADERS, ABI and the unions to the thirteen headers and 158 entry points they
-had when ns2hip_resample.h arrived, and that change could not touch the test.  So the headers since are listed in EXTRA_HEADERS and parsed
-by the same parse_header after the others (ns2hip.h's structs and status codes are known to them) into EXTRA_ABI / EXTRA_SIGNATURES; a
-name that SIGNATURES or an earlier extra header already has is an Ns2Error, load() binds both tables in its one loop, and
-header_symbols(name) answers for either list.  The next refactor that may touch that test folds the tuple into HEADERS.
 """
 import collections
 import ctypes
@@ -35,22 +29,11 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NS2_LIB", os.path.join(_HERE, "libns2hip.so"))   # NS2_LIB: experiment builds (tools/)
 INCLUDE_DIR = os.path.join(_HERE, "..", "include")
 HEADERS = (
-    "ns2hip.h",                      # the model, its kernels and the training pass; first: the others use its structs and status codes
-    "ns2hip_optim.h",                # the optimizer step
-    "ns2hip_pitch.h",                # the pitch extractor
-    "ns2hip_ragged.h",               # per-utterance lengths in the attention kernels
-    "ns2hip_ragged_front.h",         # ... through the front-end
-    "ns2hip_ragged_train.h",         # ... in the training pass
-    "ns2hip_head_dim_train.h",       # training at head dims 32 / 128
-    "ns2hip_ragged_audio.h",         # lengths in mel, pitch and the RVQ term
-    "ns2hip_fold.h",                 # the feed-forward fold
-    "ns2hip_ragged_cond_train.h",    # lengths through the conditioning's training pass
-    "ns2hip_ragged_skip.h",          # skipping the hidden row tiles of a ragged sampling batch
-    "ns2hip_ragged_skip_train.h",    # ... of a ragged training batch
-    "ns2hip_tail_fold.h",            # the Wavenet tail fold, the wide RMSNorm kernel
-)
-EXTRA_HEADERS = (                    # parsed after HEADERS, kept in tables of their own (module docstring: a stopgap)
-    "ns2hip_resample.h",             # the sample-rate converter
+    "ns2hip.h",             # the core that sampling needs; first: the others use its structs and status codes
+    "ns2hip_frontend.h",    # the conditioning front-end: DurationPitchPredictor, Aligner, ragged prompts and text
+    "ns2hip_audio.h",       # raw audio and the codec: mel, pitch, resampling, SEANet / LSTM pieces, RVQ
+    "ns2hip_train.h",       # the training pass
+    "ns2hip_optim.h",       # the optimizer step
 )
 
 
@@ -132,15 +115,10 @@ def parse_header(text, structs=None, where="include/ns2hip.h"):
 Header = collections.namedtuple("Header", "constants structs signatures")
 
 
-def load_abi(include_dir, headers, before=None):
+def load_abi(include_dir, headers):
     """{header file name: Header(constants, structs, signatures)} of the `headers` under `include_dir`, parsed in that order, each with
-    the structs of those before it; an Ns2Error if a file is missing or a name is declared in two of them.  `before`: a table this
-    function returned for headers read earlier -- their structs are known and their names are taken"""
+    the structs of those before it; an Ns2Error if a file is missing or a name is declared in two of them"""
     abi, owner, structs = {}, {}, {}
-    for name, h in (before or {}).items():
-        where = os.path.join(os.path.basename(os.path.normpath(include_dir)), name)
-        owner.update(dict.fromkeys((*h.constants, *h.signatures), where))
-        structs.update(h.structs)
     for name in headers:
         path = os.path.join(include_dir, name)
         where = os.path.join(os.path.basename(os.path.normpath(include_dir)), name)
@@ -165,9 +143,6 @@ ModelConfig, LinearArgs, AttnArgs, AttnBwdArgs, RepackPart, OptimTensor, OptimCo
     STRUCTS[k] for k in ("ns2_model_config", "ns2_linear_args", "ns2_attn_args", "ns2_attn_bwd_args", "ns2_repack_part",
                          "ns2_optim_tensor", "ns2_optim_config"))
 
-EXTRA_ABI = load_abi(INCLUDE_DIR, EXTRA_HEADERS, before=ABI)     # the stopgap of the module docstring
-EXTRA_SIGNATURES = {k: v for h in EXTRA_ABI.values() for k, v in h.signatures.items()}
-
 _lib = None
 
 
@@ -180,7 +155,7 @@ def load():
         raise Ns2Error(f"{LIB_PATH} not found: build it with `python __graft_entry__.py` "
                        f"(or naturalspeech2_pytorch_amd/csrc/build.sh); there is no fallback path")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in (*SIGNATURES.items(), *EXTRA_SIGNATURES.items()):
+    for name, (res, args) in SIGNATURES.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -198,5 +173,5 @@ def check(rc, what=""):
 
 
 def header_symbols(header=None):
-    """The sorted entry points that `header` (a name in HEADERS or EXTRA_HEADERS) declares; of HEADERS' ABI when it is None."""
-    return sorted(SIGNATURES if header is None else (ABI.get(header) or EXTRA_ABI[header]).signatures)
+    """The sorted entry points that `header` (a name in HEADERS) declares; of the whole ABI when it is None."""
+    return sorted(SIGNATURES if header is None else ABI[header].signatures)

@@ -18,7 +18,7 @@ synchronisation after the first call on a device.
 `forward(audio, lens=)` (not in the reference) is the ragged batch: sample counts per utterance, integer [b].  Utterance i's frames
 t < T_i = 1 + lens[i] // hop_length are those of the module on `audio[i, :lens[i]]` alone -- the reflect padding mirrors about the
 utterance's own last sample, not about the end of the batch -- and frames from T_i on are exactly 0 (padding, not the -100 dB of
-silence).  On a GPU that is ns2_audio_to_mel_lens (include/ns2hip_ragged_audio.h): the lengths stay on the device, nothing reads them on
+silence).  On a GPU that is ns2_audio_to_mel_lens (include/ns2hip_audio.h): the lengths stay on the device, nothing reads them on
 the host, and a value outside [n_fft // 2 + 1, L] is clamped into it.  Elsewhere a composite does the same per utterance (slice, today's
 composite, zero-fill), which reads the lengths.
 """

@@ -54,7 +54,7 @@ def _feedforward(x, ff, causal_conv):
 
 
 def _prefix_mask(lens, b, n, device):
-    """[b, n] bool, True on the rows [0, lens[i]) of utterance i; lengths clamped into [1, n] as the kernels do (include/ns2hip_ragged.h)"""
+    """[b, n] bool, True on the rows [0, lens[i]) of utterance i; lengths clamped into [1, n] as the kernels do (include/ns2hip.h)"""
     ln = torch.as_tensor(lens, device=device).long().clamp(1, n)
     assert ln.shape == (b,), f"lengths must hold one count per utterance: [{b}]"
     return torch.arange(n, device=device)[None] < ln[:, None]
@@ -68,10 +68,10 @@ def _keep_rows(x_bnc, mask):
 def model_forward_autograd(m, x, times, prompt=None, cond=None, cond_drop_prob=None, lens=None, prompt_lens=None):
     """`prompt_lens` (not in the reference; Model.forward's): prompt rows per utterance, integer [b].  The prompt is seen in two places,
     the mean of to_prompt_cond and the keys of the perceiver resampler: the mean runs over rows [0, prompt_lens[i]) and the resampler's
-    keys cat(latents, prompt) get the mask [all latents | those rows] (include/ns2hip_ragged_front.h).
+    keys cat(latents, prompt) get the mask [all latents | those rows] (include/ns2hip_frontend.h).
     `lens` (not in the reference; Model.forward's): frames per utterance of a ragged batch, integer [b].  The self-attention is the
     one place where a frame sees later frames, so it alone gets the key mask arange(n) < lens[:, None]: out[i, :lens[i]] is what
-    utterance i gives alone.  The restatement of the HIP kernels' rule (include/ns2hip_ragged.h), lengths clamped into [1, n] as there."""
+    utterance i gives alone.  The restatement of the HIP kernels' rule (include/ns2hip.h), lengths clamped into [1, n] as there."""
     b, n, _ = x.shape
     self_mask = None
     if lens is not None:
@@ -148,7 +148,7 @@ def model_forward_autograd(m, x, times, prompt=None, cond=None, cond_drop_prob=N
 
 def model_forward_autograd_ragged(m, x, times, lens, prompt=None, cond=None, cond_drop_prob=None, prompt_lens=None):
     """`model_forward_autograd` with `lens` as the TRAINING pass of a ragged batch runs it (Model.forward under autograd with
-    `ragged_training`; the restatement of training/model_pass.py's rule, include/ns2hip_ragged_train.h): frames of x and cond from a
+    `ragged_training`; the restatement of training/model_pass.py's rule, include/ns2hip_train.h): frames of x and cond from a
     length on are selected to 0 at the entry (NaN may lie there, and a masked key's 0 * NaN would reach the rows before it), and the
     returned rows from a length on are selected to 0, which zeroes their cotangent: utterance i contributes to the output and to
     every gradient what it contributes alone at lens[i] frames.  Lengths may be a device tensor: nothing here reads them on the host."""
@@ -174,7 +174,7 @@ def transformer_forward_autograd(tr, x, mask=None):
 def speech_prompt_encoder_autograd(enc, x, lens=None):
     """lens (not in the reference): prompt rows per utterance, integer [b].  The "same" convolutions read zeros behind a length (the input
     and every convolution's output are zeroed there, as behind the end of an utterance alone), the Transformer's keys stop at it, and the
-    output rows from lens[i] on are 0: rows [0, lens[i]) are what utterance i gives alone (include/ns2hip_ragged_front.h)."""
+    output rows from lens[i] on are 0: rows [0, lens[i]) are what utterance i gives alone (include/ns2hip_frontend.h)."""
     mask = None if lens is None else _prefix_mask(lens, x.shape[0], x.shape[1], x.device)
     h = _keep_rows(x, mask).transpose(1, 2)
     for m in enc.conv:
@@ -233,7 +233,7 @@ def duration_pitch_autograd(dp, x, prompts, text_lens=None, prompt_lens=None):
     """text_lens / prompt_lens (not in the reference): phonemes / prompt rows per utterance, integer [b]; either alone is allowed, the
     other side then counts as full.  Rows behind a length are zeros for the "same" convolutions, the GroupNorm statistics of utterance i
     run over its own phonemes, the attention keys cat(norm(x), prompts) are [0, text_lens[i]) and [n, n + prompt_lens[i]), and the
-    durations and pitches from text_lens[i] on come back 0 (include/ns2hip_ragged_front.h)."""
+    durations and pitches from text_lens[i] on come back 0 (include/ns2hip_frontend.h)."""
     if isinstance(dp.phoneme_token_emb, torch.nn.Embedding):
         x = dp.phoneme_token_emb(x)
     text_mask = key_mask = None

@@ -77,7 +77,7 @@ class ResidualVQCrossEntropy(nn.Module):
     into [1, n].  The loss is the mean over the utterances of each utterance's OWN loss (its cross-entropies averaged over its own
     frames [0, lens[i])), so utterance i adds to it, and to the gradient, what it adds alone divided by b.  What x and indices hold at or
     behind a length -- NaN, -1 -- reaches neither; quantized_out and the gradient are exact zeros there.  backend="hip" runs
-    ns2_rvq_ce_lens (include/ns2hip_ragged_audio.h; no host read, capturable); the composite selects x and indices to 0 behind the lengths
+    ns2_rvq_ce_lens (include/ns2hip_train.h; no host read, capturable); the composite selects x and indices to 0 behind the lengths
     before use and masks the per-frame cross-entropies with a select."""
 
     def __init__(self, owner: HipRVQ, backend: str = "composite"):

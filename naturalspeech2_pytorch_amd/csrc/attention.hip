@@ -66,11 +66,11 @@ NS2_DEVINL uint4 mask_chunk(uint4 v, int nvalid) {
 // DROP (with WLSE only): the attention dropout of the encoders' training pass (ATT:100-101) -- P is multiplied by keep / (1 - p)
 // AFTER the running sum l is taken, so O = sum_k P_k keep_k / (1 - p) v_k and the log-sum-exp is the plain one; keep = dropout_keep.h.
 // Again a separate instantiation: every kernel without it compiles to what it was.
-// QLENS (with WLSE only): the training forward of a ragged batch (include/ns2hip_ragged_train.h; self-attention, Nq == Nk): AttnArgs::klens
+// QLENS (with WLSE only): the training forward of a ragged batch (include/ns2hip_train.h; self-attention, Nq == Nk): AttnArgs::klens
 // are the utterances' lengths on the QUERY side too.  Query rows from the length on load no q, and leave as o = zero bits in the output
 // format and lse = +inf (the backward's statistic of a query beyond Nq); a workgroup whose whole query tile lies there writes those and
 // returns before anything is staged.  Rows before the length see what they see alone at Nq = Nk = length.  Once more a separate instantiation.
-// QSKIP (the plain inference forward only): ragged skipping (include/ns2hip_ragged_skip.h) -- AttnArgs::qlens are the utterances' lengths on
+// QSKIP (the plain inference forward only): ragged skipping (include/ns2hip.h) -- AttnArgs::qlens are the utterances' lengths on
 // the query side; a workgroup whose query rows all lie at or behind the utterance's computed extent (256-row granules, ns2_common.h
 // ragged_extent) returns before anything is loaded and leaves its o rows as they were.  The (utterance, head) pairs differ in work, so
 // they are spread over the XCDs as QLENS spreads them.  Once more a separate instantiation.
@@ -361,7 +361,7 @@ static hipError_t launch_attn_w(const AttnArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 // the training forward (precision 3, lse) at head dims 32 / 128: plain, with dropout (and key mask), on a ragged batch -- the three
-// variants of D = 64 below, reached through launch_attention_train_hd alone (include/ns2hip_head_dim_train.h)
+// variants of D = 64 below, reached through launch_attention_train_hd alone (include/ns2hip_train.h)
 template <int D>
 static hipError_t launch_attn_train_d(const AttnArgs& a, hipStream_t s) {
   if (a.drop_seed) return launch_attn_w<3, false, 4, true, D, true>(a, s);

@@ -15,7 +15,7 @@
 //   - results are staged as [mel][frame] in LDS so that each store writes a contiguous run of frames of one mel row.
 // No atomics: a frame's values depend on its samples alone, so an utterance's output is bit-identical whatever batch it is in.
 //
-// LENS (ns2_audio_to_mel_lens, include/ns2hip_ragged_audio.h): utterance b ends at its own sample_lens[b], clamped into
+// LENS (ns2_audio_to_mel_lens, include/ns2hip_audio.h): utterance b ends at its own sample_lens[b], clamped into
 // [n_fft / 2 + 1, L].  The reflection is taken about ITS last sample -- the one index map at the staging of smp -- so frames
 // t < T_b = 1 + len / hop are those of the utterance alone; frames from T_b on are stored as 0.0f, and a block that holds only such
 // frames stages nothing and runs no FFT.  The instantiation without LENS is the kernel as it was.
@@ -23,7 +23,6 @@
 
 #include <climits>
 
-#include "../../include/ns2hip_ragged_audio.h"
 #include "ns2_common.h"
 #include "ns2_host.h"
 
@@ -285,7 +284,7 @@ extern "C" int ns2_audio_to_mel(const float* audio, int B, int64_t L, int n_fft,
                                    log_db, out, nullptr, stream);
 }
 
-// include/ns2hip_ragged_audio.h
+// ... of a ragged batch
 extern "C" int ns2_audio_to_mel_lens(const float* audio, int B, int64_t L, int n_fft, int hop_length, const float* window,
                                      const float* twiddle, const int* fb_meta, const float* fb_w, int n_w, int n_mels, int n_bins,
                                      int log_db, float* out, const int* sample_lens, void* stream) {

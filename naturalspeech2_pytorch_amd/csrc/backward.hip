@@ -662,7 +662,7 @@ NS2_DEVINL void ab2_store_own(const AttnBwdArgs& a, int b, int h, int orow, int 
 // the whole own row, which ends with dK = dV = 0 -- and the
 // attention dropout of dropout_keep.h: with keep' = keep / (1 - p),  dP = (dO V^T) keep' ; dS = P (dP - delta) ; dV^T += dO^T (P keep'),
 // delta = rowsum(dO * O) of the post-dropout O as attn_delta_kernel computes it.
-// LENS = the denoiser's pass on a ragged batch (include/ns2hip_ragged_train.h; self-attention, Nq == Nk; a third instantiation: the other
+// LENS = the denoiser's pass on a ragged batch (include/ns2hip_train.h; self-attention, Nq == Nk; a third instantiation: the other
 // two keep their code): len_b = clamp(lens[b], 1, N), read once per workgroup into a scalar register, stands in for Nown and Nwalk in every
 // BOUND -- ceil(len_b / 64) tiles walked, rows of the boundary tile from len_b on out of the zero page (role 1: their statistics out of
 // ab2_inf_zero), whatever memory holds there -- while a.Nq / a.Nk stay the strides of every address.  Own rows from len_b on are written
@@ -1012,7 +1012,7 @@ static hipError_t launch_attention_bwd_d(const AttnBwdArgs& a, hipStream_t s) {
   return hipSuccess;
 }
 hipError_t launch_attention_bwd(const AttnBwdArgs& a, hipStream_t s) { return launch_attention_bwd_d<64>(a, s); }
-// head h at columns col0 + D h (include/ns2hip_head_dim_train.h); D = 64 launches the very kernels of launch_attention_bwd
+// head h at columns col0 + D h (include/ns2hip_train.h); D = 64 launches the very kernels of launch_attention_bwd
 hipError_t launch_attention_bwd_hd(const AttnBwdArgs& a, int D, hipStream_t s) {
   if (D == 32) return launch_attention_bwd_d<32>(a, s);
   if (D == 128) return launch_attention_bwd_d<128>(a, s);

@@ -1,4 +1,5 @@
-// extern "C" surface of libns2hip (declared in include/ns2hip.h): error plumbing + op-level entry points.
+// extern "C" surface of libns2hip (declared in include/ns2hip.h; the codec and pitch entries in include/ns2hip_audio.h): error plumbing +
+// op-level entry points.
 // The Model executor entry points live in model_exec.cpp.
 #include <hip/hip_runtime.h>
 
@@ -8,12 +9,6 @@
 #include <cstring>
 #include <vector>
 
-#include "../../include/ns2hip_pitch.h"
-#include "../../include/ns2hip_fold.h"
-#include "../../include/ns2hip_tail_fold.h"
-#include "../../include/ns2hip_ragged.h"
-#include "../../include/ns2hip_ragged_skip.h"
-#include "../../include/ns2hip_ragged_skip_train.h"
 #include "ns2_host.h"
 #include "gemm_route.h"
 
@@ -56,7 +51,7 @@ using namespace ns2;
 static inline int prec_ok(int p) { return p >= 1 && p <= 4; }
 
 extern "C" const char* ns2_last_error(void) { return g_err; }
-extern "C" int ns2_version(void) { return 125; }   // 125: the Wavenet tail fold and the wide RMSNorm kernel (include/ns2hip_tail_fold.h): ns2_tail_fold, ns2_debug_force_tail_fold, ns2_debug_force_norm, ns2_debug_norm_last; 124: the feed-forward fold (include/ns2hip_fold.h): ns2_ff_fold, ns2_debug_force_fold, the FF conv kernel writes fp32; 123: the RVQ cross-entropy of the training loss: ns2_rvq_ce (+ _workspace_bytes); 122: training of the Aligner: ns2_relu_fwd / _bwd, ns2_align_attn_bwd (+ _workspace_bytes), ns2_align_losses_fwd / _bwd (+ _workspace_bytes); 121: two utterance chains: ns2_debug_force_chains / _chains_last / _chain_rule, ns2_model_profile_end counts logical products; 120: one argument block per Linear / Conv1d product: ns2_linear(ns2_linear_args) replaces ns2_linear_f32 / _split / _split_as / _geglu / _qkv; 119: one argument block per attention direction: ns2_attention_fwd(ns2_attn_args) replaces ns2_attention / _hd / _lse / _lse_masked, ns2_attn_bwd_args carries the mask and dropout of the removed bwd_masked entry; 118: ns2_debug_force_attention, ns2_debug_attention_fast_launches (attn_fast_kernel.h); 117: the range-guard counters register themselves: ns2_saturation_counters / _counter_name / _peek replace ns2_saturation_peek_async / _peek_train_async; 116: ns2_groupnorm_silu, ns2_length_regulate(_totals), ns2_row_dot (duration_pitch.hip); 115: ns2_weights_retile; 114: ns2_attention_hd (head dims 32 / 64 / 128), ns2_model_create takes dim_head 32 / 128; 113: ns2_weight_tile_conv3 + ns2_conv3_input_ld (the dedicated FF causal conv kernel, ffconv_kernel.h), ns2_weight_tile_linear (gemm3_kernel.h), ns2_weight_tile_wavenet (wavenet3_kernel.h), ns2_debug_force_gemm(4 / 5); 112: ns2_seanet_resblock_narrow; 111: training entry points take a precision (3 = bf16 x3, 4 = mixed on FMT_H8 lines), ns2_linear_split_as; 110: backward pass (capi_train.cpp: ns2_wgrad, ns2_attention_bwd, ...), ns2_weight_update; 109: ns2_seanet_conv_narrow; 108: ns2_seanet_prep2; 107: ns2_lstm2 (two LSTM layers, one launch); 106: ns2_saturation_peek_async; 105: ns2_lstm_layer takes the scratch size (persistent recurrence); 104: model precision 5 (per-site plan); 103: precision 2 / 4 at op level, caller-owned skinny-linear scratch
+extern "C" int ns2_version(void) { return 125; }   // 125: the Wavenet tail fold and the wide RMSNorm kernel (include/ns2hip.h): ns2_tail_fold, ns2_debug_force_tail_fold, ns2_debug_force_norm, ns2_debug_norm_last; 124: the feed-forward fold (include/ns2hip.h): ns2_ff_fold, ns2_debug_force_fold, the FF conv kernel writes fp32; 123: the RVQ cross-entropy of the training loss: ns2_rvq_ce (+ _workspace_bytes); 122: training of the Aligner: ns2_relu_fwd / _bwd, ns2_align_attn_bwd (+ _workspace_bytes), ns2_align_losses_fwd / _bwd (+ _workspace_bytes); 121: two utterance chains: ns2_debug_force_chains / _chains_last / _chain_rule, ns2_model_profile_end counts logical products; 120: one argument block per Linear / Conv1d product: ns2_linear(ns2_linear_args) replaces ns2_linear_f32 / _split / _split_as / _geglu / _qkv; 119: one argument block per attention direction: ns2_attention_fwd(ns2_attn_args) replaces ns2_attention / _hd / _lse / _lse_masked, ns2_attn_bwd_args carries the mask and dropout of the removed bwd_masked entry; 118: ns2_debug_force_attention, ns2_debug_attention_fast_launches (attn_fast_kernel.h); 117: the range-guard counters register themselves: ns2_saturation_counters / _counter_name / _peek replace ns2_saturation_peek_async / _peek_train_async; 116: ns2_groupnorm_silu, ns2_length_regulate(_totals), ns2_row_dot (duration_pitch.hip); 115: ns2_weights_retile; 114: ns2_attention_hd (head dims 32 / 64 / 128), ns2_model_create takes dim_head 32 / 128; 113: ns2_weight_tile_conv3 + ns2_conv3_input_ld (the dedicated FF causal conv kernel, ffconv_kernel.h), ns2_weight_tile_linear (gemm3_kernel.h), ns2_weight_tile_wavenet (wavenet3_kernel.h), ns2_debug_force_gemm(4 / 5); 112: ns2_seanet_resblock_narrow; 111: training entry points take a precision (3 = bf16 x3, 4 = mixed on FMT_H8 lines), ns2_linear_split_as; 110: backward pass (capi_train.cpp: ns2_wgrad, ns2_attention_bwd, ...), ns2_weight_update; 109: ns2_seanet_conv_narrow; 108: ns2_seanet_prep2; 107: ns2_lstm2 (two LSTM layers, one launch); 106: ns2_saturation_peek_async; 105: ns2_lstm_layer takes the scratch size (persistent recurrence); 104: model precision 5 (per-site plan); 103: precision 2 / 4 at op level, caller-owned skinny-linear scratch
 extern "C" int ns2_debug_force_gemm(int kernel) {
   ARGCHK(kernel >= 0 && kernel <= 5, "ns2_debug_force_gemm: 0 auto, 1 = 128x128 kernel, 2 = 256x256 kernel, 3 = auto without split-K, 4 = auto without the dedicated kernels (FF conv, lean linear, lean Wavenet), 5 = auto without split-K, the dedicated kernels whenever eligible");
   force_gemm_kernel(kernel);
@@ -210,7 +205,7 @@ extern "C" int ns2_linear(const ns2_linear_args* p, void* stream) {
   HIPRET(launch_gemm(g, p->precision, (hipStream_t)stream));
   return NS2_OK;
 }
-// include/ns2hip_ragged_skip.h: what the entry refuses on its own account comes first, under its own name, before any device call
+// the ragged forms of ns2_linear: what an entry refuses on its own account comes first, under its own name, before any device call
 #define SKIP_SHAPE_CHK(name, row_lens, seq_len, M)                                                                                  \
   ARGCHK((row_lens) != nullptr, name ": row_lens is null (the entry without lengths is the call that computes every row)");          \
   ARGCHK((seq_len) > 0 && ((seq_len) & 255) == 0, name ": seq_len must be a positive multiple of 256 (whole skipping granules per utterance)"); \
@@ -225,7 +220,7 @@ extern "C" int ns2_linear_lens(const ns2_linear_args* p, const int* row_lens, in
   HIPRET(launch_gemm(g, p->precision, (hipStream_t)stream));
   return NS2_OK;
 }
-// include/ns2hip_ragged_skip_train.h: the same entry under the training rule (zero bits in the hidden tiles of every output), and the
+// the same entry under the training rule (zero bits in the hidden tiles of every output), and the
 // host counter of the launches that went out with lengths (capi_train.cpp's ns2_wgrad_rows_lens bumps it too)
 static std::atomic<long long> g_train_skip_launches{0};
 void ns2::note_train_skip_launch() { g_train_skip_launches.fetch_add(1, std::memory_order_relaxed); }
@@ -330,7 +325,7 @@ extern "C" int ns2_attention_fwd(const ns2_attn_args* p, void* stream) {
   return NS2_OK;
 }
 
-// include/ns2hip_ragged.h: what this entry refuses comes first, under its own name; the block itself is ns2_attention_fwd's
+// with key counts: what this entry refuses comes first, under its own name; the block itself is ns2_attention_fwd's
 extern "C" int ns2_attention_fwd_lens(const ns2_attn_args* p, const int* key_lens, void* stream) {
   ARGCHK(p != nullptr, "ns2_attention_fwd_lens: null argument block");
   ARGCHK(key_lens != nullptr, "ns2_attention_fwd_lens: key_lens is null (ns2_attention_fwd is the call without lengths)");
@@ -345,7 +340,7 @@ extern "C" int ns2_attention_fwd_lens(const ns2_attn_args* p, const int* key_len
 }
 
 extern "C" int64_t ns2_debug_gemm_route_launches(int route) { return gemm_route_launches(route); }
-// include/ns2hip_ragged_skip.h
+// ... and with query lengths on top (ragged skipping)
 extern "C" int ns2_attention_fwd_skip(const ns2_attn_args* p, const int* key_lens, const int* query_lens, void* stream) {
   ARGCHK(p != nullptr, "ns2_attention_fwd_skip: null argument block");
   ARGCHK(query_lens != nullptr, "ns2_attention_fwd_skip: query_lens is null (ns2_attention_fwd / _lens are the calls without them)");
@@ -414,19 +409,30 @@ extern "C" int ns2_cfg_mix(const float* cond_out, const float* null_out, float* 
   return NS2_OK;
 }
 
-// include/ns2hip_pitch.h
+// the pitch extractor (pitch.hip): the checks and the launch of ns2_pitch_yin and ns2_pitch_yin_lens, under the caller's `name`;
+// sample_lens = null for the former, device memory for the latter: nothing here reads it
+static int pitch_yin(const char* name, const float* audio, int B, int64_t L, int sample_rate, int hop_length, int tau_min, int tau_max,
+                     float threshold, float* f0, const int* sample_lens, void* stream) {
+  ARGCHK_AS(name, B >= 1 && B <= 65535, "B must be in [1, 65535]");
+  ARGCHK_AS(name, L >= 1, "L must be at least 1");
+  ARGCHK_AS(name, sample_rate >= 1 && hop_length >= 1, "sample_rate and hop_length must be at least 1");
+  ARGCHK_AS(name, tau_min >= 2 && tau_min < tau_max && tau_max <= PITCH_TAU_MAX, "the lags must satisfy 2 <= tau_min < tau_max <= 1024");
+  ARGCHK_AS(name, threshold == threshold, "threshold is NaN");
+  const int64_t T = 1 + L / hop_length;
+  ARGCHK_AS(name, T <= 0x7fffffffLL, "too many frames");
+  HIPRET(launch_pitch_yin(audio, B, (long)L, (long)T, sample_rate, hop_length, tau_min, tau_max, threshold, f0, (hipStream_t)stream, sample_lens));
+  return NS2_OK;
+}
 extern "C" int ns2_pitch_yin(const float* audio, int B, int64_t L, int sample_rate, int hop_length, int tau_min, int tau_max,
                              float threshold, float* f0, void* stream) {
   ARGCHK(audio && f0, "ns2_pitch_yin: null pointer");
-  ARGCHK(B >= 1 && B <= 65535, "ns2_pitch_yin: B must be in [1, 65535]");
-  ARGCHK(L >= 1, "ns2_pitch_yin: L must be at least 1");
-  ARGCHK(sample_rate >= 1 && hop_length >= 1, "ns2_pitch_yin: sample_rate and hop_length must be at least 1");
-  ARGCHK(tau_min >= 2 && tau_min < tau_max && tau_max <= PITCH_TAU_MAX, "ns2_pitch_yin: the lags must satisfy 2 <= tau_min < tau_max <= 1024");
-  ARGCHK(threshold == threshold, "ns2_pitch_yin: threshold is NaN");
-  const int64_t T = 1 + L / hop_length;
-  ARGCHK(T <= 0x7fffffffLL, "ns2_pitch_yin: too many frames");
-  HIPRET(launch_pitch_yin(audio, B, (long)L, (long)T, sample_rate, hop_length, tau_min, tau_max, threshold, f0, (hipStream_t)stream));
-  return NS2_OK;
+  return pitch_yin("ns2_pitch_yin", audio, B, L, sample_rate, hop_length, tau_min, tau_max, threshold, f0, nullptr, stream);
+}
+extern "C" int ns2_pitch_yin_lens(const float* audio, int B, int64_t L, int sample_rate, int hop_length, int tau_min, int tau_max,
+                                  float threshold, float* f0, const int* sample_lens, void* stream) {
+  ARGCHK(audio && f0, "ns2_pitch_yin_lens: null pointer");
+  ARGCHK(sample_lens, "ns2_pitch_yin_lens: sample_lens is null (ns2_pitch_yin is the call without lengths)");
+  return pitch_yin("ns2_pitch_yin_lens", audio, B, L, sample_rate, hop_length, tau_min, tau_max, threshold, f0, sample_lens, stream);
 }
 
 extern "C" int ns2_seanet_prep(const float* x, int ldx, int in_prefix, const float* add, int ldadd, int B, int64_t T, int C, int elu,

@@ -1,14 +1,10 @@
-// extern "C" surface of the backward (training) pass: declared in include/ns2hip.h under "training".  Kernels: backward.hip; the
+// extern "C" surface of the backward (training) pass: declared in include/ns2hip_train.h.  Kernels: backward.hip; the
 // contractions are calls of the forward GEMM family (gemm.hip / gemm2.hip) on re-packed weights / transposed operand planes.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstring>
 
-#include "../../include/ns2hip_head_dim_train.h"
-#include "../../include/ns2hip_ragged_cond_train.h"
-#include "../../include/ns2hip_ragged_train.h"
-#include "../../include/ns2hip_ragged_skip_train.h"
 #include "ns2_host.h"
 
 using namespace ns2;
@@ -206,7 +202,7 @@ extern "C" int ns2_wgrad_rows(const uint16_t* dy_hi, const uint16_t* dy_lo, int 
                               int precision, void* stream) {
   return wgrad_rows_impl(dy_hi, dy_lo, ld_dy, x_hi, x_lo, ld_x, M, R, T, Kp, K, dil, seq_len, dw, workspace, workspace_bytes, precision, nullptr, stream);
 }
-// include/ns2hip_ragged_skip_train.h: what the entry refuses on its own account comes first, under its own name
+// ... on a ragged batch: what the entry refuses on its own account comes first, under its own name
 extern "C" int ns2_wgrad_rows_lens(const uint16_t* dy_hi, const uint16_t* dy_lo, int ld_dy, const uint16_t* x_hi, const uint16_t* x_lo, int ld_x,
                                    int64_t M, int R, int T, int Kp, int K, int dil, int seq_len, float* dw, void* workspace,
                                    int64_t workspace_bytes, int precision, const int* row_lens, void* stream) {
@@ -289,15 +285,20 @@ extern "C" int ns2_attention_bwd(const ns2_attn_bwd_args* p, void* stream) {
   return attention_bwd(p, nullptr, stream);
 }
 
-// ---- ragged training batches (include/ns2hip_ragged_train.h): what these entries refuse comes first, under their own names; the blocks
+// ---- ragged training batches: what these entries refuse comes first, under their own names; the blocks
 // themselves are ns2_attention_fwd's and ns2_attention_bwd's
+// what the four entries that take lengths refuse of a block alike, under the caller's `name`
+static int self_attention_lens_chk(const char* name, int Nq, int Nk, const uint8_t* key_mask, float dropout_p) {
+  ARGCHK_AS(name, Nq == Nk, "Nq != Nk (lengths belong to a self-attention)");
+  ARGCHK_AS(name, !key_mask, "key_mask together with lens (one way of shortening the keys per call)");
+  ARGCHK_AS(name, dropout_p == 0.f, "dropout together with lens (the denoiser's self-attention has none)");
+  return NS2_OK;
+}
 extern "C" int ns2_attention_train_fwd_lens(const ns2_attn_args* p, const int* lens, void* stream) {
   ARGCHK(p != nullptr, "ns2_attention_train_fwd_lens: null argument block");
   ARGCHK(lens != nullptr, "ns2_attention_train_fwd_lens: lens is null (ns2_attention_fwd is the call without lengths)");
   ARGCHK(p->lse, "ns2_attention_train_fwd_lens: lse is missing (this is the training forward; ns2_attention_fwd_lens is the inference one)");
-  ARGCHK(p->Nq == p->Nk, "ns2_attention_train_fwd_lens: Nq != Nk (lengths belong to a self-attention)");
-  ARGCHK(!p->key_mask, "ns2_attention_train_fwd_lens: key_mask together with lens (one way of shortening the keys per call)");
-  ARGCHK(p->dropout_p == 0.f, "ns2_attention_train_fwd_lens: dropout together with lens (the denoiser's self-attention has none)");
+  NSCHK(self_attention_lens_chk("ns2_attention_train_fwd_lens", p->Nq, p->Nk, p->key_mask, p->dropout_p));
   AttnArgs a;
   if (int rc = attn_args_from(p, &a)) return rc;
   a.klens = lens;
@@ -308,13 +309,11 @@ extern "C" int ns2_attention_bwd_lens(const ns2_attn_bwd_args* p, const int* len
   ARGCHK(p != nullptr, "ns2_attention_bwd_lens: null argument block");
   ARGCHK(lens != nullptr, "ns2_attention_bwd_lens: lens is null (ns2_attention_bwd is the call without lengths)");
   ARGCHK(p->lse, "ns2_attention_bwd_lens: lse is missing");
-  ARGCHK(p->Nq == p->Nk, "ns2_attention_bwd_lens: Nq != Nk (lengths belong to a self-attention)");
-  ARGCHK(!p->key_mask, "ns2_attention_bwd_lens: key_mask together with lens (one way of shortening the keys per call)");
-  ARGCHK(p->dropout_p == 0.f, "ns2_attention_bwd_lens: dropout together with lens (the denoiser's self-attention has none)");
+  NSCHK(self_attention_lens_chk("ns2_attention_bwd_lens", p->Nq, p->Nk, p->key_mask, p->dropout_p));
   return attention_bwd(p, lens, stream);
 }
 
-// ---- training at head dims 32 / 128 (include/ns2hip_head_dim_train.h): every refusal is made here, before any device call
+// ---- training at head dims 32 / 128: every refusal is made here, before any device call
 static bool head_dim_ok(int d) { return d == 0 || d == 32 || d == 64 || d == 128; }
 extern "C" int ns2_attention_train_fwd_hd(const ns2_attn_args* p, const int* lens, void* stream) {
   ARGCHK(p != nullptr, "ns2_attention_train_fwd_hd: null argument block");
@@ -323,11 +322,7 @@ extern "C" int ns2_attention_train_fwd_hd(const ns2_attn_args* p, const int* len
   ARGCHK(p->precision == 3, "ns2_attention_train_fwd_hd: the training forward runs in precision 3");
   ARGCHK(p->q_lo && p->k_lo && p->vt_lo && p->o_lo, "ns2_attention_train_fwd_hd: precision 3 operands and o come with their lo planes");
   ARGCHK(((p->q_col0 | p->k_col0) & 31) == 0, "ns2_attention_train_fwd_hd: q_col0 and k_col0 must be multiples of 32 (interleaved lines)");
-  if (lens) {
-    ARGCHK(p->Nq == p->Nk, "ns2_attention_train_fwd_hd: Nq != Nk (lengths belong to a self-attention)");
-    ARGCHK(!p->key_mask, "ns2_attention_train_fwd_hd: key_mask together with lens (one way of shortening the keys per call)");
-    ARGCHK(p->dropout_p == 0.f, "ns2_attention_train_fwd_hd: dropout together with lens (the denoiser's self-attention has none)");
-  }
+  if (lens) NSCHK(self_attention_lens_chk("ns2_attention_train_fwd_hd", p->Nq, p->Nk, p->key_mask, p->dropout_p));
   ns2_attn_args q = *p;            // attn_args_from is ns2_attention_fwd's translation, which ties lse to a head dim of 64
   q.head_dim = 0;
   AttnArgs a;
@@ -355,11 +350,7 @@ extern "C" int ns2_attention_bwd_hd(const ns2_attn_bwd_args* p, int head_dim, co
   ARGCHK(!p->gp_kv || ((p->dk_col0 | p->dv_col0) & 31) == 0, "ns2_attention_bwd_hd: dk_col0 and dv_col0 of a plane output must be multiples of 32");
   ARGCHK(p->gp_q || !p->dq || (p->dq_col0 & 3) == 0, "ns2_attention_bwd_hd: dq_col0 must be a multiple of 4");
   ARGCHK(p->gp_kv || !(p->dk || p->dv) || ((p->dk_col0 | p->dv_col0) & 3) == 0, "ns2_attention_bwd_hd: dk_col0 and dv_col0 must be multiples of 4");
-  if (lens) {
-    ARGCHK(p->Nq == p->Nk, "ns2_attention_bwd_hd: Nq != Nk (lengths belong to a self-attention)");
-    ARGCHK(!p->key_mask, "ns2_attention_bwd_hd: key_mask together with lens (one way of shortening the keys per call)");
-    ARGCHK(p->dropout_p == 0.f, "ns2_attention_bwd_hd: dropout together with lens (the denoiser's self-attention has none)");
-  }
+  if (lens) NSCHK(self_attention_lens_chk("ns2_attention_bwd_hd", p->Nq, p->Nk, p->key_mask, p->dropout_p));
   return attention_bwd(p, lens, stream, head_dim ? head_dim : 64);
 }
 extern "C" int ns2_dropout_keep_mask(const uint32_t* seed, unsigned call, float dropout_p, int B, int H, int Nq, int Nk, uint8_t* out, void* stream) {
@@ -402,7 +393,7 @@ extern "C" int ns2_groupnorm_silu_bwd(const float* dy, int64_t lddy, const float
   HIPRET(launch_groupnorm_silu_bwd(dy, (long)lddy, x, B, n, C, groups, weight, bias, eps, stats, dx, dweight_dbias, slots, colsum, (hipStream_t)stream));
   return NS2_OK;
 }
-// ... of a ragged batch (include/ns2hip_ragged_cond_train.h): the same launches on the <true> kernels
+// ... of a ragged batch: the same launches on the <true> kernels
 extern "C" int ns2_groupnorm_silu_bwd_lens(const float* dy, int64_t lddy, const float* x, int B, int n, int C, int groups, const float* weight,
                                            const float* bias, float eps, const void* stats, int64_t stats_bytes, const int* row_lens, float* dx,
                                            float* dweight_dbias, void* workspace, int64_t workspace_bytes, void* stream) {
@@ -495,14 +486,37 @@ extern "C" int64_t ns2_rvq_ce_workspace_bytes(int M, int Q, int want_quantized) 
   if (M <= 0 || Q <= 0) return 0;
   return want_quantized ? (int64_t)M * Q * (int64_t)sizeof(int64_t) : 0;
 }
+// the codebook shape and the workspace, which ns2_rvq_ce and ns2_rvq_ce_lens check alike once M is known, under the caller's `name`
+static int rvq_ce_chk(const char* name, int M, int Q, int C, int D, const float* quantized_out, const void* workspace, int64_t workspace_bytes) {
+  ARGCHK_AS(name, D == 128 && C % 64 == 0, "needs codebook_dim 128 and codebook_size % 64 == 0 (EnCodec: 128 / 1024)");
+  ARGCHK_AS(name, !quantized_out || (workspace && workspace_bytes >= ns2_rvq_ce_workspace_bytes(M, Q, 1)),
+            "quantized_out needs a workspace (ns2_rvq_ce_workspace_bytes)");
+  return NS2_OK;
+}
 extern "C" int ns2_rvq_ce(const float* x, const float* codebooks, const float* cb_norm, const int64_t* indices, float* row_loss, float* loss,
                           float* quantized_out, float* grad, int M, int Q, int C, int D, void* workspace, int64_t workspace_bytes, void* stream) {
   ARGCHK(x && codebooks && cb_norm && indices && row_loss && loss, "ns2_rvq_ce: null pointer");
   ARGCHK(M > 0 && Q > 0 && C > 0, "ns2_rvq_ce: M, Q and C must be positive");
-  ARGCHK(D == 128 && C % 64 == 0, "ns2_rvq_ce: needs codebook_dim 128 and codebook_size % 64 == 0 (EnCodec: 128 / 1024)");
-  ARGCHK(!quantized_out || (workspace && workspace_bytes >= ns2_rvq_ce_workspace_bytes(M, Q, 1)),
-         "ns2_rvq_ce: quantized_out needs a workspace (ns2_rvq_ce_workspace_bytes)");
+  NSCHK(rvq_ce_chk("ns2_rvq_ce", M, Q, C, D, quantized_out, workspace, workspace_bytes));
   RvqCeArgs a{x, codebooks, cb_norm, indices, row_loss, loss, quantized_out ? (int64_t*)workspace : nullptr, quantized_out, grad, M, Q, C, D};
   HIPRET(launch_rvq_ce(a, (hipStream_t)stream));
+  return NS2_OK;
+}
+// ... of a ragged batch: the same kernel on RvqCeLensArgs; row_lens is device memory, nothing here reads it
+extern "C" int ns2_rvq_ce_lens(const float* x, const float* codebooks, const float* cb_norm, const int64_t* indices, float* row_loss,
+                               float* loss, float* quantized_out, float* grad, int B, int n, const int* row_lens, int Q, int C, int D,
+                               void* workspace, int64_t workspace_bytes, void* stream) {
+  ARGCHK(x && codebooks && cb_norm && indices && row_loss && loss, "ns2_rvq_ce_lens: null pointer");
+  ARGCHK(row_lens, "ns2_rvq_ce_lens: row_lens is null (ns2_rvq_ce is the call without lengths)");
+  ARGCHK(B > 0 && n > 0 && Q > 0 && C > 0, "ns2_rvq_ce_lens: B, n, Q and C must be positive");
+  ARGCHK((int64_t)B * n <= 0x7fffffffLL, "ns2_rvq_ce_lens: B * n must fit an int");
+  const int M = B * n;
+  NSCHK(rvq_ce_chk("ns2_rvq_ce_lens", M, Q, C, D, quantized_out, workspace, workspace_bytes));
+  RvqCeLensArgs a;
+  a.x = x; a.codebooks = codebooks; a.cb_norm = cb_norm; a.targets = indices; a.row_loss = row_loss; a.loss = loss;
+  a.nearest = quantized_out ? (int64_t*)workspace : nullptr; a.quantized_out = quantized_out; a.grad = grad;
+  a.M = M; a.Q = Q; a.C = C; a.D = D;
+  a.row_lens = row_lens; a.B = B; a.n = n;
+  HIPRET(launch_rvq_ce_lens(a, (hipStream_t)stream));
   return NS2_OK;
 }

@@ -315,7 +315,7 @@ int gn_bwd_row_chunks(int n) { return (n + GNB_ROWS - 1) / GNB_ROWS; }
 int row_dot_bwd_chunks(long M) { return (int)((M + RDB_ROWS - 1) / RDB_ROWS); }
 
 // stats = the workspace the forward (ns2_groupnorm_silu) left; slots [B * gn_bwd_row_chunks(n)][2 C]; colsum [B][2 C]; dwb [2 C] = dweight | dbias.
-// row_lens (include/ns2hip_ragged_cond_train.h): int32 [B] on the device and stats = what ns2_groupnorm_silu_lens left, or nullptr: the
+// row_lens (include/ns2hip_train.h): int32 [B] on the device and stats = what ns2_groupnorm_silu_lens left, or nullptr: the
 // <true> kernels in the same grids, the same two reductions between them.
 hipError_t launch_groupnorm_silu_bwd(const float* dy, long lddy, const float* x, int B, int n, int C, int groups, const float* weight,
                                      const float* bias, float eps, const void* stats, float* dx, float* dwb, float* slots, float* colsum,

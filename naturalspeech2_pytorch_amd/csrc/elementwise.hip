@@ -1669,7 +1669,7 @@ hipError_t launch_lstm_layer(const float* xproj, long ld_x, const float* w_hh, c
   if (B <= 0 || T <= 0 || H <= 0 || H > 512 || (H & 3)) return hipErrorInvalidValue;
   if (H == 512 && B <= LP_MAXB && lstm_persistent_enabled()) {
     // the persistent kernel needs 2 x 32 x 512 {h, tag} pairs of exchange + the abort flags: the caller's scratch
-    // (3 x B x H floats at least: h_a, h_b, c contiguous, include/ns2hip.h) is large enough when it was sized by
+    // (3 x B x H floats at least: h_a, h_b, c contiguous, include/ns2hip_audio.h) is large enough when it was sized by
     // ns2_lstm_state_floats; a caller that handed over less takes the step kernel
     if (state_floats >= LP_STATE_FLOATS) {
       float* hbuf = h_a;

@@ -135,7 +135,7 @@ NS2_DEVINL void tr_wait(f32x16& c0, f32x16& c1) {                 // every trans
 // SKIP (ragged skipping, GemmArgs::row_lens): as in gemm_kernel -- a separate instantiation whose row tile tm goes to XCD tm % 8 and whose
 // workgroups return on a hidden row tile before the first DMA request, barrier or accumulator; the others compile to what they were.
 //
-// TR with SKIP = LENS (ragged skipping in training, include/ns2hip_ragged_skip_train.h): the contraction runs over the TOKENS, so the
+// TR with SKIP = LENS (ragged skipping in training, include/ns2hip_train.h): the contraction runs over the TOKENS, so the
 // lengths shorten the K loop, not the grid.  With lens_seq % 256 == 0 a 32-token K tile lies inside one utterance and one granule: it
 // is hidden iff its first token is, and a visible tile's causal taps (token m - shift) read visible rows only.  The slice plan is the
 // caller's: slice z still owns tokens [z nkt 32, (z + 1) nkt 32), but its loop visits the VISIBLE tiles among them only, as one

@@ -96,7 +96,7 @@ NS2_DEVINL void norm_gamma4(const GemmArgs& g, int c, float (&gm)[4]) {
   if (g.nrm_gamma) { const float4 t = *reinterpret_cast<const float4*>(g.nrm_gamma + c); gm[0] = t.x; gm[1] = t.y; gm[2] = t.z; gm[3] = t.w; }
 }
 
-// ---- Ragged skipping in the training pass (GemmArgs::zero_hidden, include/ns2hip_ragged_skip_train.h): a hidden tile of EVERY output
+// ---- Ragged skipping in the training pass (GemmArgs::zero_hidden, include/ns2hip.h): a hidden tile of EVERY output
 // of the product gets zero bits -- what the tile's epilogue would have covered, nothing else.  Zero bits are the value 0 in every
 // format (fp32, bf16 hi / lo, IEEE half, the e5m2 bytes of FMT_H8).  Rows [row0, row0 + rows) lie inside one utterance and one skipping
 // granule (the caller's tile height divides 256 and lens_seq % 256 == 0); col0 / bn: the tile's first (packed) column and its width, a

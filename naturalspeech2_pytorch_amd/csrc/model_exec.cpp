@@ -22,11 +22,6 @@
 #include <string>
 #include <vector>
 
-#include "../../include/ns2hip_fold.h"
-#include "../../include/ns2hip_tail_fold.h"
-#include "../../include/ns2hip_ragged.h"
-#include "../../include/ns2hip_ragged_front.h"
-#include "../../include/ns2hip_ragged_skip.h"
 #include "ns2_host.h"
 #include "gemm_route.h"
 
@@ -73,7 +68,7 @@ struct ns2_model {
   std::vector<float*> b_wn_conv, b_wn_res;
   PackedW w_skip; float* b_skip;
   PackedW w_final; const float* b_final;
-  // The tail fold (include/ns2hip_tail_fold.h): the skip sum (one Linear over the L concatenated block outputs) and final_conv (1 x 1)
+  // The tail fold (include/ns2hip.h): the skip sum (one Linear over the L concatenated block outputs) and final_conv (1 x 1)
   // behind it (NS2:725) as ONE Linear of K = L * dim, W' = W_final . [W_skip_0 | ... | W_skip_{L-1}], b' = W_final . sum_l b_skip_l + b_final,
   // folded once from the fp32 parameters by ns2_model_finalize (elementwise.hip tail_fold_kernel).  A step then runs one product into the
   // residual stream; the w_skip / w_final packs and the ssum planes do not exist.  false (ns2_debug_force_tail_fold(0) / NS2_TAIL_FOLD=0
@@ -115,7 +110,7 @@ struct ns2_model {
   // the chain rule's last verdict and what it was asked for: the verdict depends on the shape, the alignment of the caller's buffers and
   // the GEMM test hook alone, so a run of steps asks once
   struct { int B = 0, N = 0, n_cond = 0; unsigned hook_epoch = 0; uintptr_t align = 0; int chains = 0; } rule;
-  // the skip rule's last verdict (include/ns2hip_ragged_skip.h), likewise: it depends on the shape and the GEMM test hook alone; -1 = not asked
+  // the skip rule's last verdict (include/ns2hip.h), likewise: it depends on the shape and the GEMM test hook alone; -1 = not asked
   struct { int B = 0, N = 0, n_cond = 0; unsigned hook_epoch = 0; uintptr_t align = 0; int skips = -1; } skip_rule;
 };
 
@@ -863,7 +858,7 @@ extern "C" int ns2_model_cond_stack(ns2_model* m, const void* state_a, const voi
   return NS2_OK;
 }
 
-// prompt_lens: null, or the prompt rows that count per utterance (include/ns2hip_ragged_front.h): the mean of to_prompt_cond and the
+// prompt_lens: null, or the prompt rows that count per utterance (include/ns2hip.h): the mean of to_prompt_cond and the
 // resampler's keys stop there.  Rows behind a length may hold NaN: proj_context and the kv projection keep a row to itself, and the
 // attention kernel reads K rows and V^T columns beyond a key count as zeros.
 static int prepare_cond_impl(ns2_model* m, const float* prompt, int n_prompt, const int* prompt_lens, const float* cond, int n_cond, int drop,
@@ -1068,8 +1063,8 @@ struct StepArgs {                // what forward_impl resolved for the whole bat
   const float* x; float* out;
   const float* call; int cld;    // [gamma | beta] blocks of all FiLM / adaptive-norm projections; row b at call + b * cld
   int n_cond, N;
-  const int* lens = nullptr;     // ragged batch (include/ns2hip_ragged.h): frames per utterance, int32 [B] on the device; null = N each
-  bool skip = false;             // ... and every product and both attentions skip the row tiles hidden behind them (include/ns2hip_ragged_skip.h)
+  const int* lens = nullptr;     // ragged batch (include/ns2hip.h): frames per utterance, int32 [B] on the device; null = N each
+  bool skip = false;             // ... and every product and both attentions skip the row tiles hidden behind them (include/ns2hip.h)
 };
 
 int enqueue(ns2_model* m, const Launch& l, bool counted, hipStream_t s);
@@ -1293,7 +1288,7 @@ int chains_by_rule(const ns2_model* m, const Work& w, const CondState* cs, const
   return same_plan(*whole, *c0) && same_plan(*whole, *c1) ? 2 : 1;
 }
 
-// ---- the skip rule (include/ns2hip_ragged_skip.h).  A step skips its hidden row tiles only if every utterance is whole 256-row granules
+// ---- the skip rule (include/ns2hip.h).  A step skips its hidden row tiles only if every utterance is whole 256-row granules
 // and no product of the whole batch's described step is planned on the split-K route (its slices and its finishing launch take no
 // lengths).  Pure host arithmetic over the described launches; two chains of a skipping step passed same_plan, which admits no split either.
 bool skip_by_rule(const std::vector<Launch>& whole, int N) {
@@ -1552,7 +1547,7 @@ extern "C" int ns2_model_forward_row(ns2_model* m, const float* x, const float* 
   return forward_impl(m, x, nullptr, cond_row, cond_state, n_cond, out, B, N, workspace, workspace_bytes, stream);
 }
 
-// include/ns2hip_ragged.h
+// ... of a ragged batch: the lengths go to the self-attention
 extern "C" int ns2_model_forward_lens(ns2_model* m, const float* x, const float* times, const float* cond_row, const int* frame_lens,
                                       const void* cond_state, int n_cond, float* out, int B, int N, void* workspace, int64_t workspace_bytes,
                                       void* stream) {
@@ -1560,7 +1555,7 @@ extern "C" int ns2_model_forward_lens(ns2_model* m, const float* x, const float*
   return forward_impl(m, x, times, cond_row, cond_state, n_cond, out, B, N, workspace, workspace_bytes, stream, frame_lens);
 }
 
-// include/ns2hip_ragged_skip.h
+// ... and to every product where the skip rule holds
 extern "C" int ns2_model_forward_lens_skip(ns2_model* m, const float* x, const float* times, const float* cond_row, const int* frame_lens,
                                            const void* cond_state, int n_cond, float* out, int B, int N, void* workspace,
                                            int64_t workspace_bytes, void* stream) {

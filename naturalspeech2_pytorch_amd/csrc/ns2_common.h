@@ -265,7 +265,7 @@ NS2_DEVINL int xcd_spread(int bid, int nwg, int ntile) {
   return ((j / ntile) * nx + xcd) * ntile + j % ntile;
 }
 
-// Ragged skipping (include/ns2hip_ragged_skip.h).  The computed extent of an utterance of seq_len frames (seq_len % 256 == 0) with
+// Ragged skipping (include/ns2hip.h).  The computed extent of an utterance of seq_len frames (seq_len % 256 == 0) with
 // lens[b] real ones is H = min(seq_len, 256 ceil(clamp(lens[b], 1, seq_len) / 256)): ONE granule of 256 rows for every kernel, whatever
 // its own tile height, so that producers and consumers agree on which rows exist.  A tile of rows [row0, row0 + h) with h dividing 256
 // lies inside one utterance and inside one granule: it is hidden iff its first row is.  Scalars only (row0 is workgroup-uniform, the

@@ -4,7 +4,10 @@
 
 #include <vector>
 
-#include "../../include/ns2hip.h"
+#include "../../include/ns2hip.h"                // every source that defines entry points sees the whole model-side ABI
+#include "../../include/ns2hip_frontend.h"
+#include "../../include/ns2hip_audio.h"
+#include "../../include/ns2hip_train.h"
 #include "ns2_kernels.h"
 #include "dropout_keep.h"
 
@@ -29,6 +32,14 @@ void gemm_hook_changed();      // model_exec.cpp: ns2_debug_force_gemm was calle
       ns2::set_error("%s", msg);     \
       return NS2_ERR_ARG;            \
     }                                \
+  } while (0)
+// the same refusal from a check list that two entry points share: `name` is the entry's, so each keeps its own message prefix
+#define ARGCHK_AS(name, cond, msg)           \
+  do {                                       \
+    if (!(cond)) {                           \
+      ns2::set_error("%s: %s", name, msg);   \
+      return NS2_ERR_ARG;                    \
+    }                                        \
   } while (0)
 #define NSCHK(expr)                  \
   do {                               \

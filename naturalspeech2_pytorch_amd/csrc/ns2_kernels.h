@@ -1,5 +1,5 @@
 // Internal (C++) launcher interface of libns2hip: one launcher per HIP kernel family.
-// The public C ABI is include/ns2hip.h; csrc/capi.cpp and csrc/model_exec.cpp sit on top of these.
+// The public C ABI is the headers under include/; csrc/capi.cpp and csrc/model_exec.cpp sit on top of these.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -99,13 +99,13 @@ struct GemmArgs {
   // launch_gemm_tr only (weight gradients from token-major planes, gemm2.hip TR): tokens the operands have, channels per tap block of
   // the N dimension (a multiple of 32), taps (0 / 1: no shift; tap t of a causal conv reads token m - (tr_taps - 1 - t) * dil)
   int tr_tokens = 0, tr_kp = 0, tr_taps = 0;
-  // ragged skipping (include/ns2hip_ragged_skip.h; last in the block: no other field moves): per-utterance frame counts in DEVICE
+  // ragged skipping (include/ns2hip.h; last in the block: no other field moves): per-utterance frame counts in DEVICE
   // memory, int32 [M / lens_seq], read by the kernels alone, and the frames per utterance (a multiple of 256 that divides M).  Selects
   // the SKIP instantiations: a workgroup whose whole row tile lies at or behind its utterance's computed extent
   // min(lens_seq, 256 ceil(clamp(len, 1, lens_seq) / 256)) returns before its first load -- an fp32 output without a residual gets
   // zeros there, every other output keeps what it held.  null = every row is computed.  The split-K route takes no lengths.
   const int* row_lens = nullptr; int lens_seq = 0;
-  // ragged skipping in the TRAINING pass (include/ns2hip_ragged_skip_train.h; appended: no other field moves).  With row_lens: a hidden
+  // ragged skipping in the TRAINING pass (include/ns2hip_train.h; appended: no other field moves).  With row_lens: a hidden
   // tile of EVERY output -- fp32 with or without a residual, operand planes of either format, V^T -- is stored as zero bits instead of
   // being left as it was (gemm_epi.h zero_hidden_tile): the buffers of the pass come uninitialised, and the anticausal dgrads and the
   // kernels that do not skip read behind an utterance's extent.  0 = the sampling rule above.  launch_gemm_tr (weight gradients) with
@@ -152,14 +152,14 @@ struct AttnArgs {
   // attention dropout of the training kernel (dropout_keep.h; needs lse and precision 3): drop_seed = two 32-bit words in DEVICE memory
   // (null = no dropout), drop_thr = round(p 2^32), drop_scale = 1 / (1 - p), drop_call = index of this attention inside the pass
   const uint32_t* drop_seed = nullptr; uint32_t drop_thr = 0u, drop_call = 0u; float drop_scale = 1.f;
-  // ragged batches (include/ns2hip_ragged.h): per-utterance key counts in DEVICE memory, int32 [B], read by the kernels alone (never on
+  // ragged batches (include/ns2hip.h): per-utterance key counts in DEVICE memory, int32 [B], read by the kernels alone (never on
   // the host: a captured launch follows rewritten values).  Utterance b attends to keys [0, clamp(klens[b], 1, Nk)); keys beyond are
   // treated as keys beyond Nk are (score -inf, K rows and V^T columns read as zeros, so they may hold anything); Nk stays the stride.
   // null = every utterance has Nk keys.  Excludes kmask and dropout.  Together with lse (the training forward of a ragged batch,
-  // include/ns2hip_ragged_train.h; precision 3, Nq == Nk): the counts are the utterances' lengths on the query side too -- o rows from the
+  // include/ns2hip_train.h; precision 3, Nq == Nk): the counts are the utterances' lengths on the query side too -- o rows from the
   // length on are written as zero bits, their lse as +inf.
   const int* klens = nullptr;
-  // ragged skipping (include/ns2hip_ragged_skip.h; last in the block): per-utterance frame counts on the QUERY side, int32 [B] in DEVICE
+  // ragged skipping (include/ns2hip.h; last in the block): per-utterance frame counts on the QUERY side, int32 [B] in DEVICE
   // memory; needs Nq % 256 == 0.  A query workgroup whose rows all lie at or behind min(Nq, 256 ceil(clamp(qlens[b], 1, Nq) / 256)) returns
   // before its first load and leaves its o rows as they were; every other row is computed as without it.  With or without klens (the
   // cross attention to the resampled prompt has query lengths alone).  Excludes lse, kmask and dropout.  null = every query row is computed.
@@ -181,7 +181,7 @@ struct NormArgs {
   int fmt;                           // PlaneFmt of the output planes
 };
 hipError_t launch_rmsnorm(const NormArgs& a, hipStream_t s);
-void force_norm_kernel(int k);      // test hook, the modes of ns2_debug_force_norm (include/ns2hip_tail_fold.h): 0 by shape, 1 = rmsnorm_kernel for every call
+void force_norm_kernel(int k);      // test hook, the modes of ns2_debug_force_norm (include/ns2hip.h): 0 by shape, 1 = rmsnorm_kernel for every call
 int norm_kernel_last();             // which kernel the last launch_rmsnorm ran: 1 = rmsnorm_kernel, 2 = rmsnorm_wide_kernel (0: none yet)
 
 // x (+ add) -> split planes, with optional zero padding to ldo columns
@@ -313,7 +313,7 @@ struct RvqCeArgs {
   int M, Q, C, D;
 };
 hipError_t launch_rvq_ce(const RvqCeArgs& a, hipStream_t s);
-// ... of a ragged batch (include/ns2hip_ragged_audio.h): M = B n rows, utterance b owns rows [b n, b n + row_lens[b]); the loss is the mean
+// ... of a ragged batch (ns2_rvq_ce_lens, include/ns2hip_train.h): M = B n rows, utterance b owns rows [b n, b n + row_lens[b]); the loss is the mean
 // over utterances of each utterance's own mean, G of a row is divided by B row_lens[b], and every output row at or behind a length is 0
 struct RvqCeLensArgs : RvqCeArgs {
   const int* row_lens;       // [B] on the device, clamped into [1, n] by the kernels
@@ -390,7 +390,7 @@ struct AttnBwdArgs {                                                // (every fi
   // the encoders' training pass: key-padding mask [B, Nk] (1 = attend; null = none) and attention dropout as in AttnArgs (drop_seed null =
   // none).  Either one selects the MD instantiations of the kernel; without them the kernels of the denoiser's pass run, unchanged.
   const unsigned char* kmask = nullptr; const uint32_t* drop_seed = nullptr; uint32_t drop_thr = 0u, drop_call = 0u; float drop_scale = 1.f;
-  // ragged training batches (include/ns2hip_ragged_train.h): per-utterance lengths in DEVICE memory, int32 [B], read by the kernels alone.
+  // ragged training batches (include/ns2hip_train.h): per-utterance lengths in DEVICE memory, int32 [B], read by the kernels alone.
   // Self-attention only (Nq == Nk); utterance b's gradients are those of rows [0, clamp(lens[b], 1, N)) alone, rows beyond are written as
   // zeros, N stays the stride.  Selects the LENS instantiations; excludes kmask and dropout.  null = every utterance has N rows.
   const int* lens = nullptr;
@@ -418,7 +418,7 @@ hipError_t launch_align_losses_fwd(const float* aln_log, const float* hard, cons
 hipError_t launch_align_losses_bwd(const float* aln_log, const float* hard, const int* text_lens, const int* mel_lens, const float* g_fs,
                                    const float* g_bin, int B, int T, int n, float blank, float* d_log, void* workspace, hipStream_t s);
 
-// the YIN pitch estimator (pitch.hip; include/ns2hip_pitch.h states the formula): audio [B, L] -> f0 [B, 1 + L / hop] in Hz, 0 unvoiced.
+// the YIN pitch estimator (pitch.hip; include/ns2hip_audio.h states the formula): audio [B, L] -> f0 [B, 1 + L / hop] in Hz, 0 unvoiced.
 // The caller (capi.cpp) has checked 2 <= tau_min < tau_max <= PITCH_TAU_MAX, hop >= 1, L >= 1, 1 <= B <= 65535
 constexpr int PITCH_TAU_MAX = 1024;
 hipError_t launch_pitch_yin(const float* audio, int B, long L, long T, int sample_rate, int hop, int tau_min, int tau_max, float threshold,

@@ -1,4 +1,4 @@
-// The YIN pitch estimator (pitch.py; de Cheveigne & Kawahara, JASA 2002, steps 1-5; include/ns2hip_pitch.h states the formula) in
+// The YIN pitch estimator (pitch.py; de Cheveigne & Kawahara, JASA 2002, steps 1-5; include/ns2hip_audio.h states the formula) in
 // one launch: framing, the difference function, its cumulative-mean normalisation, the threshold search, the descent to the local
 // minimum and the parabolic interpolation.  fp32 throughout, no atomics, every sum in a fixed order.
 //
@@ -17,7 +17,7 @@
 //     before it carried in (a fixed shape), d'(tau) back into the lag's LDS slot, then two ascending ballot searches -- the
 //     first lag below the threshold, and from there the first lag whose successor is not lower.
 // A frame's value depends on its own samples alone, so an utterance's row is bit-identical alone or in any batch.
-// LENS (ns2_pitch_yin_lens, include/ns2hip_ragged_audio.h): utterance b ends at its own sample_lens[b], clamped into [1, L]: the
+// LENS (ns2_pitch_yin_lens, include/ns2hip_audio.h): utterance b ends at its own sample_lens[b], clamped into [1, L]: the
 // staging reads zeros from there on, frames from T_b = 1 + len / hop on are stored as 0 (unvoiced), and a block that holds only such
 // frames returns after storing them.  The instantiation without LENS is the kernel as it was.
 // This translation unit converts nothing to half: it includes no ns2_common.h and owns no range counter.

@@ -1,4 +1,4 @@
-// Ragged prompts and text (include/ns2hip_ragged_front.h): what the front-end needs, beside the attention kernels' key counts and key
+// Ragged prompts and text (include/ns2hip_frontend.h): what the front-end needs, beside the attention kernels' key counts and key
 // masks, so that utterance i of a padded batch equals utterance i alone with its text cut to text_lens[i] and its prompt to prompt_lens[i]:
 //   - GroupNorm + SiLU with a row count per utterance (the <true> kernels of groupnorm_kernel.h);
 //   - zero-filling the rows behind a length, for the "same" convolutions that would otherwise read their neighbours' padding;
@@ -7,7 +7,7 @@
 // masking is a launch of its own.  ns2_model_prepare_cond_lens, the fourth entry of the header, lives with the executor (model_exec.cpp).
 #include <hip/hip_runtime.h>
 
-#include "../../include/ns2hip_ragged_front.h"
+#include "../../include/ns2hip_frontend.h"
 #include "groupnorm_kernel.h"
 
 namespace ns2 {

@@ -1,4 +1,4 @@
-// The sample-rate converter (resample.py; include/ns2hip_resample.h states the formula): polyphase rational resampling by up / down in
+// The sample-rate converter (resample.py; include/ns2hip_audio.h states the formula): polyphase rational resampling by up / down in
 // one launch.  out[f up + p] = sum_i k[p][i] x[f down + i - w], i = 0 .. T - 1, T = 2 w + down, one fp32 fma chain per output in
 // ascending i.  fp32 throughout, no atomics, no sum whose order depends on the shape or the batch.
 //
@@ -20,7 +20,6 @@
 
 #include <cstdint>
 
-#include "../../include/ns2hip_resample.h"
 #include "ns2_host.h"
 
 namespace ns2 {

@@ -11,14 +11,14 @@
 // G = (1 / M) sum_q dL/dr_q (each stage's loss is a mean over the M rows).  Everything is fp32, no atomics, every sum in a fixed order:
 // loss and G are bit-reproducible.
 //
-// Edge behaviour (also in include/ns2hip.h):
+// Edge behaviour (also in include/ns2hip_train.h):
 //   * target outside [0, C) (-1 included): that row's loss and its row of G are NaN -- loud, and no host read;
 //   * dist == 0 (the residual IS a code): the loss is the well-defined value, that code's w_c is 0;
 //   * near-ties of the nearest code are not re-decided in fp64 (rvq_encode_kernel does): either code is a valid stage result.
 // Distances: the sweeps use the expanded form |r|^2 - 2 (r.e - |e|^2/2) clamped at 0 (what the MFMA yields, and what the PyTorch
 // composite computes); the target's own distance -- the term the loss is most sensitive to -- is the direct form sum (r - e)^2.
 //
-// Ragged batches (ns2_rvq_ce_lens, include/ns2hip_ragged_audio.h): the same kernel instantiated on RvqCeLensArgs.  A row at or behind its
+// Ragged batches (ns2_rvq_ce_lens, include/ns2hip_train.h): the same kernel instantiated on RvqCeLensArgs.  A row at or behind its
 // utterance's length is a DEAD row: its x and its targets are not read (the residual starts at 0, the target is code 0, so nothing of it
 // is NaN), its rows of row_loss and G are stored as 0, and a workgroup of dead rows alone returns before the first codebook tile.  A live
 // row's arithmetic is unchanged (rows never mix: a row is one column of every MFMA), and its G is divided by B len instead of M.  The

@@ -109,8 +109,8 @@ class NaturalSpeech2(nn.Module):
                  duration_pitch_train_backend="composite",    # not in the reference: "hip" trains the DurationPitchPredictor on them (training/duration_pitch_pass.py)
                  aligner_train_backend="composite",    # not in the reference: "hip" trains the Aligner and runs its two losses on them (training/aligner_pass.py)
                  rvq_ce_backend=None,                  # not in the reference: "composite" / "hip" sets codec.rq.backend, the RVQ cross-entropy term (csrc/rvq_ce.hip); None leaves the codec's own
-                 ragged_audio: bool = False,           # not in the reference: forward(raw audio, audio_lens=samples) and audio_lens with the RVQ term (include/ns2hip_ragged_audio.h)
-                 ragged_conditioning: bool = False):   # not in the reference: forward(text_lens=, prompt_lens=) trains on ragged text and prompts (include/ns2hip_ragged_cond_train.h)
+                 ragged_audio: bool = False,           # not in the reference: forward(raw audio, audio_lens=samples) and audio_lens with the RVQ term (include/ns2hip_audio.h, include/ns2hip_train.h)
+                 ragged_conditioning: bool = False):   # not in the reference: forward(text_lens=, prompt_lens=) trains on ragged text and prompts (include/ns2hip_train.h)
         super().__init__()
         assert _is_denoiser(model), "model must be a Model (this package's, or compat.HipBackedModel over the reference's class)"
         self.conditional = model.condition_on_prompt
@@ -614,7 +614,7 @@ class NaturalSpeech2(nn.Module):
             under `ragged_conditioning=True` (below); without it they see none, and `prompt_lens` with `audio_lens` keeps raising.
         The model still needs `ragged_training=True` for `audio_lens`.
 
-        Built with `ragged_conditioning=True` (not in the reference; also a plain attribute; include/ns2hip_ragged_cond_train.h), `text_lens` and
+        Built with `ragged_conditioning=True` (not in the reference; also a plain attribute; include/ns2hip_train.h), `text_lens` and
         `prompt_lens` (a keyword the reference signature tolerates) reach the conditioning under autograd: `prompt_lens` -- rows of
         `prompt_enc=`, frames of prompt latents or samples of a raw-audio prompt (`_prompt_frame_lens`; a CUDA tensor is trusted) -- goes to
         `prompt_enc`, the predictor and the model, together with `audio_lens` or without it; `text_lens` goes to the phoneme encoder's key

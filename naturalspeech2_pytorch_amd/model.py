@@ -453,15 +453,15 @@ class HipDenoiserMixin:
         `lens` (not in the reference): frames per utterance of a ragged batch, integer [b], each in [1, n] -- out[i, :lens[i]] is
         what utterance i gives alone at its own length, whatever x (and cond) hold from lens[i] on; rows from lens[i] on are
         finite and meaningless.  The self-attention kernels read the lengths on the device.  Under autograd a model with
-        `ragged_training = True` takes them too (include/ns2hip_ragged_train.h): utterance i then contributes to the output and to every
+        `ragged_training = True` takes them too (include/ns2hip_train.h): utterance i then contributes to the output and to every
         gradient what it contributes alone at lens[i] frames, and the returned rows from lens[i] on are exactly 0; without the switch the
-        training pass raises on `lens`.  With `ragged_skip = True` (torch.no_grad() only; include/ns2hip_ragged_skip.h) the step does not compute
+        training pass raises on `lens`.  With `ragged_skip = True` (torch.no_grad() only; include/ns2hip.h) the step does not compute
         the 256-row tiles that lie wholly behind a length: rows before H_i = min(n, 256 ceil(lens[i] / 256)) keep their bits, rows of the
         output from H_i on are exactly 0; it needs n % 256 == 0 and a batch large enough not to split K, else it does nothing.
         `prompt_lens` (not in the reference): prompt rows per utterance of a padded prompt batch, integer [b], each in [1, n_p] -- the
         output of utterance i is what it gives with its prompt cut to prompt_lens[i] rows, whatever the prompt holds from there on
         (NaN included): the mean of to_prompt_cond and the perceiver resampler's keys stop at the length, on the device.  Under autograd a
-        model with `ragged_conditioning = True` takes them too, with and without `lens` (include/ns2hip_ragged_cond_train.h): the prompt rows
+        model with `ragged_conditioning = True` takes them too, with and without `lens` (include/ns2hip_train.h): the prompt rows
         behind a length then reach no gradient either; without the switch the training pass raises on `prompt_lens`."""
         if prompt_lens is not None and (not self._hip_cfg["condition_on_prompt"] or prompt is None):
             raise ValueError("prompt_lens needs a prompt: a conditional model (condition_on_prompt=True) called with prompt=")
@@ -590,7 +590,7 @@ class HipDenoiserMixin:
 
 def _lens_entry(m):
     """the library entry a forward with lengths calls: with `ragged_skip` the one whose step skips the row tiles hidden behind the lengths
-    (include/ns2hip_ragged_skip.h; the library's skip rule decides per shape, and falls back to the other's launches)"""
+    (include/ns2hip.h; the library's skip rule decides per shape, and falls back to the other's launches)"""
     return "ns2_model_forward_lens_skip" if getattr(m, "ragged_skip", False) else "ns2_model_forward_lens"
 
 
@@ -745,12 +745,12 @@ class Model(HipDenoiserMixin, nn.Module):
         self.head_dim_training = head_dim_training    # True: dim_head 32 / 128 train on the HIP kernels too (else: the composite, as before)
         self.ragged_conditioning = ragged_conditioning    # True: forward(prompt_lens=) under autograd trains on ragged prompts (else it raises)
         # True: under torch.no_grad(), forward(lens=) / forward_with_cond_scale(lens=) skip the 256-row tiles that lie wholly behind an utterance's
-        # length in every product and both attentions (include/ns2hip_ragged_skip.h): rows before H_i = min(n, 256 ceil(lens_i / 256)) keep
+        # length in every product and both attentions (include/ns2hip.h): rows before H_i = min(n, 256 ceil(lens_i / 256)) keep
         # their bits, rows of the output from H_i on come back as exact zeros.  Does nothing without lens=; ignored under autograd (the
         # training pass computes every row).
         self.ragged_skip = ragged_skip
         # True: under autograd, with ragged_training and forward(lens=), the forward products, the dgrads and the weight gradients of the HIP
-        # training pass skip the same hidden 256-row tiles (include/ns2hip_ragged_skip_train.h): loss, returned rows and every
+        # training pass skip the same hidden 256-row tiles (include/ns2hip_train.h): loss, returned rows and every
         # parameter's gradient keep the bits of the switch off.  Does nothing without lens=, with n % 256 != 0, on the CPU or for a model
         # the HIP pass does not take.
         self.ragged_skip_training = ragged_skip_training

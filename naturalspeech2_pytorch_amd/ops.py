@@ -173,7 +173,7 @@ class PackedWeight:
 def _linear(w: PackedWeight, a: Planes, M: int, precision: int, row_lens=None, **fields):
     """The one place that fills a ns2_linear_args (include/ns2hip.h) and calls ns2_linear.  `fields`: the block's other fields by name
     (device addresses or ints; what is not named stays zero = feature off).  row_lens = (int32 [B] on the device, frames per utterance)
-    of a ragged TRAINING batch: the same block goes to ns2_linear_lens_zero (include/ns2hip_ragged_skip_train.h) -- hidden row tiles are
+    of a ragged TRAINING batch: the same block goes to ns2_linear_lens_zero (include/ns2hip.h) -- hidden row tiles are
     skipped and stored as zero bits in every output; None (the default): ns2_linear, the same call and bits as ever."""
     args = _lib.LinearArgs(w=w.handle, a_hi=a.hi, a_lo=a.lo, lda=a.ld, M=M, precision=precision, **fields)
     if row_lens is not None:
@@ -256,10 +256,10 @@ def _attention_fwd(q: Planes, q_col0, k: Planes, k_col0, vt_hi, vt_lo, vt_ld, B,
     """The one place that fills a ns2_attn_args (include/ns2hip.h) and calls ns2_attention_fwd -> (o, lse or None).  vt_hi / vt_lo:
     device addresses of the transposed value planes; o_precision: the format of o when it is not the operands' (0 = `precision`);
     key_mask: uint8 [B, Nk] on the device; drop = (p, seed tensor on the device, call index) or None; key_lens: int32 [B] on the
-    device, the call then goes through ns2_attention_fwd_lens (include/ns2hip_ragged.h); train_lens: int32 [B] on the device, the
-    utterances' lengths of a ragged TRAINING batch (with want_lse): ns2_attention_train_fwd_lens (include/ns2hip_ragged_train.h).
+    device, the call then goes through ns2_attention_fwd_lens (include/ns2hip.h); train_lens: int32 [B] on the device, the
+    utterances' lengths of a ragged TRAINING batch (with want_lse): ns2_attention_train_fwd_lens (include/ns2hip_train.h).
     want_lse at a head_dim other than 64 -- the training forward at head dims 32 / 128 -- goes through ns2_attention_train_fwd_hd
-    (include/ns2hip_head_dim_train.h), with or without train_lens."""
+    (include/ns2hip_train.h), with or without train_lens."""
     o = _out_planes(B * Nq, H * head_dim, q.device, o_precision or precision)
     lse = torch.empty(B, H, Nq, dtype=torch.float32, device=q.device) if want_lse else None
     p, seed, call = drop if drop is not None else (0.0, None, 0)
@@ -323,7 +323,7 @@ def groupnorm_silu(x: torch.Tensor, B: int, weight: torch.Tensor, bias: torch.Te
                    lens: Optional[torch.Tensor] = None):
     """GroupNorm(groups, C) + SiLU (+ resid after the SiLU) over token-major fp32 rows x [B * n, C] (ns2_groupnorm_silu).
     Returns the fp32 rows, the operand planes of `precision` (when given), or (rows, planes).  lens (not in the reference): optional
-    integer [B] on the device, rows per utterance (ns2_groupnorm_silu_lens, include/ns2hip_ragged_front.h) -- the statistics of
+    integer [B] on the device, rows per utterance (ns2_groupnorm_silu_lens, include/ns2hip_frontend.h) -- the statistics of
     utterance b run over its rows [0, lens[b]) and are bit-equal to the utterance alone; rows from lens[b] on come out as zeros."""
     x = _f32(x)
     M, C = x.shape
@@ -349,7 +349,7 @@ def groupnorm_silu(x: torch.Tensor, B: int, weight: torch.Tensor, bias: torch.Te
 
 
 def _front_lens(lens, B: int, device) -> torch.Tensor:
-    """lengths as the kernels of include/ns2hip_ragged_front.h read them: int32 [B], contiguous, on `device` (no host read; a tensor
+    """lengths as the kernels of include/ns2hip_frontend.h read them: int32 [B], contiguous, on `device` (no host read; a tensor
     that already is one comes back as it is)"""
     l = torch.as_tensor(lens).to(device=device, dtype=torch.int32).contiguous()
     assert l.shape == (B,), f"lengths must hold one count per utterance: [{B}]"
@@ -508,7 +508,7 @@ def rvq_cross_entropy(x: torch.Tensor, codebooks: torch.Tensor, cb_norm: Optiona
     """the RVQ cross-entropy of the training loss in one launch (ns2_rvq_ce, csrc/rvq_ce.hip): x [M, 128] fp32, codebooks [Q, C, 128],
     indices [M, Q] int64 -> (loss 0-dim, row_loss [M, Q], quantized_out [M, 128] or None, G [M, 128] = d loss / d x or None).
     An index outside [0, C) gives a NaN loss; nothing is read back to the host.
-    lens [B] (a CUDA integer tensor; M = B n): the ragged batch of ns2_rvq_ce_lens (include/ns2hip_ragged_audio.h) -- the loss is the mean
+    lens [B] (a CUDA integer tensor; M = B n): the ragged batch of ns2_rvq_ce_lens (include/ns2hip_train.h) -- the loss is the mean
     over utterances of each one's own mean, and every output row at or behind a length is 0 whatever x and indices hold there."""
     x, cb = _f32(x), _f32(codebooks)
     M, D = x.shape
@@ -620,7 +620,7 @@ def audio_to_mel(audio: torch.Tensor, n_fft: int, hop_length: int, n_mels: int, 
                  lens: Optional[torch.Tensor] = None) -> torch.Tensor:
     """audio [B, L] fp32 -> [B, n_mels, 1 + L // hop_length] (ns2_audio_to_mel); `plan`: the device tables of
     audio_to_mel._plan (window, twiddle, meta, weights) and their sizes n_w, n_bins.
-    lens [B] (a CUDA integer tensor of sample counts): ns2_audio_to_mel_lens (include/ns2hip_ragged_audio.h)"""
+    lens [B] (a CUDA integer tensor of sample counts): ns2_audio_to_mel_lens (include/ns2hip_audio.h)"""
     audio = _f32(audio)
     B, L = audio.shape
     T = 1 + L // hop_length
@@ -645,8 +645,8 @@ def audio_to_mel(audio: torch.Tensor, n_fft: int, hop_length: int, n_mels: int, 
 # ---- PitchExtractor (csrc/pitch.hip)
 def pitch_yin(audio: torch.Tensor, sample_rate: int, hop_length: int, tau_min: int, tau_max: int, threshold: float,
               lens: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """audio [B, L] fp32 -> f0 [B, 1 + L // hop_length] in Hz, 0 where unvoiced (ns2_pitch_yin, include/ns2hip_pitch.h).
-    lens [B] (a CUDA integer tensor of sample counts): ns2_pitch_yin_lens (include/ns2hip_ragged_audio.h)"""
+    """audio [B, L] fp32 -> f0 [B, 1 + L // hop_length] in Hz, 0 where unvoiced (ns2_pitch_yin, include/ns2hip_audio.h).
+    lens [B] (a CUDA integer tensor of sample counts): ns2_pitch_yin_lens (include/ns2hip_audio.h)"""
     audio = _f32(audio)
     B, L = audio.shape
     out = torch.empty(B, 1 + L // hop_length, dtype=torch.float32, device=audio.device)
@@ -666,7 +666,7 @@ def pitch_yin(audio: torch.Tensor, sample_rate: int, hop_length: int, tau_min: i
 
 # ---- Resample (csrc/resample.hip)
 def resample(audio: torch.Tensor, up: int, down: int, width: int, taps: torch.Tensor, lens: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """audio [B, L] fp32 -> [B, ceil(up L / down)] (ns2_resample, include/ns2hip_resample.h); taps: the transposed table [T, up] fp32 on
+    """audio [B, L] fp32 -> [B, ceil(up L / down)] (ns2_resample, include/ns2hip_audio.h); taps: the transposed table [T, up] fp32 on
     the device, T = 2 width + down.  lens [B] (a CUDA integer tensor of sample counts): ns2_resample_lens.  A shape the kernel does
     not take raises (rc NS2_UNAVAILABLE): callers ask ns2_resample_frames_per_block first."""
     audio, taps = _f32(audio), _f32(taps)

@@ -33,7 +33,7 @@ reads nothing back from the device.
 
 `forward(audio, lens=)` is the ragged batch: sample counts per utterance, integer [b].  Frame t of utterance i reads zeros outside
 [0, lens[i]), so frames t < T_i = 1 + lens[i] // hop_length are those of the module on `audio[i, :lens[i]]` alone, and frames from T_i
-on are exactly 0 (unvoiced).  On a GPU that is ns2_pitch_yin_lens (include/ns2hip_ragged_audio.h): the lengths stay on the device and a
+on are exactly 0 (unvoiced).  On a GPU that is ns2_pitch_yin_lens (include/ns2hip_audio.h): the lengths stay on the device and a
 value outside [1, L] is clamped into it.  The composite does the same per utterance (slice, compute, zero-fill) and reads the lengths.
 """
 import math

@@ -17,7 +17,7 @@ With g = gcd(orig_hz, new_hz), down = orig_hz / g, up = new_hz / g, lpw = lowpas
     L_out = ceil(up L / down); only q = f up + p < L_out is stored
 
 The table is built on the host in fp64 and rounded once to fp32 (`resample_table`).  On a GPU, `forward` runs one HIP kernel
-(csrc/resample.hip: ns2_resample, include/ns2hip_resample.h) when up, down <= 640 and T <= 1024 -- every pair among 8, 16, 22.05, 24, 32,
+(csrc/resample.hip: ns2_resample, include/ns2hip_audio.h) when up, down <= 640 and T <= 1024 -- every pair among 8, 16, 22.05, 24, 32,
 44.1 and 48 kHz.  There each output is one fp32 fma chain in ascending i: bit-reproducible, and a row does not depend on the rest of the
 batch.  Any other pair, the CPU, and audio that requires grad take `resample_composite` (pad, conv1d with stride `down`, transpose,
 crop), which is differentiable.  The module has no parameters and no buffers: its tables are cached per (device, rates, parameters)

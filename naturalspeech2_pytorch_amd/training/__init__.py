@@ -35,20 +35,20 @@ NS2:344-527) adds `GroupNormSiluFn`, `RowDotReluFn` and the `resid` operand of `
 Functions of their own in aligner.py (`ForwardSumLoss` / `BinLoss` with `backend="hip"`).  The RVQ cross-entropy term of the loss
 (`codec.rq`, `ResidualVQCrossEntropy(backend="hip")`; NS2:1668-1684) is `RvqCrossEntropyFn`: one launch, fp32 under either arithmetic.
 
-Ragged batches (`Model(ragged_training=True)`, `model_forward_train(..., lens=)`; include/ns2hip_ragged_train.h): with
+Ragged batches (`Model(ragged_training=True)`, `model_forward_train(..., lens=)`; include/ns2hip_train.h): with
 per-utterance frame counts -- int32 [B] on the device, read by kernels alone -- utterance i contributes to the output and to every gradient
 what it contributes alone at lens[i] frames.  Rows of x and of the projected cond from a length on are selected to 0 at the entry, every
 self-attention `AttnFn` gets `lens` (`HipBackend.attention(..., lens=)` / `attention_bwd(..., lens=)`: the length-aware instantiations of
 the training forward and of the backward kernel, which write exact zeros from the length on), and the returned rows from a length on are
 selected to 0, which zeroes the cotangent there.  Every gradient row of the padding is then an exact 0, so the weight-gradient GEMMs,
 the bias sums and the FiLM partial sums need no lengths.  With `Model(ragged_skip_training=True)` and n % 256 == 0 they get them all the
-same (include/ns2hip_ragged_skip_train.h): `model_pass.py` hands the lengths down as the trailing optional argument of
+same (include/ns2hip_train.h): `model_pass.py` hands the lengths down as the trailing optional argument of
 `GemmFn`, `WavenetBlockFn`, `AttnFn`, `FeedForwardFn` and `NormLinearFn`, whose products over the b n frame rows pass `row_lens=` to
 `HipBackend.gemm_f32` / `gemm_split` / `wgrad_rows`: hidden 256-row tiles are not computed and come back as zero bits, hidden K tiles
 of a weight gradient are stepped over -- the same loss, rows and gradients, bit for bit.
 
 Head dims 32 and 128 (`head_dim_training=True` on `Model`, `compat.HipBackedModel`, `Transformer`, the encoders, `DurationPitchPredictor`;
-include/ns2hip_head_dim_train.h): the three `*_unsupported_reason` functions then accept `dim_head` 32 and 128, and the passes
+include/ns2hip_train.h): the three `*_unsupported_reason` functions then accept `dim_head` 32 and 128, and the passes
 hand `dim_head` to every `AttnFn` (`functions.attn_apply`), which hands it to `HipBackend.attention*` only when it is not 64.  Without the
 switch such a module trains on the composite, as before.
 

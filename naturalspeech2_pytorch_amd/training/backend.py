@@ -65,7 +65,7 @@ class HipBackend:
 
     def gemm_f32(self, pw, a, bias=None, resid=None, taps=0, dil=1, seq_len=0, pad_left=-1, row_lens=None):
         """-> fp32 [M, ldo] with ldo = round_up(N, 32); columns >= N are NOT written.  row_lens = (int32 [B] on the device, frames per
-        utterance) of a ragged batch whose products skip (include/ns2hip_ragged_skip_train.h): the row tiles hidden behind a length are
+        utterance) of a ragged batch whose products skip (include/ns2hip_train.h): the row tiles hidden behind a length are
         not computed and come back as zero bits (with a residual too); an anticausal product (pad_left = 0 under taps > 1) needs zeros in
         the hidden rows of `a`"""
         return ops.linear_f32(pw, a, bias=bias, resid=resid, conv_taps=taps, dilation=dil, seq_len=seq_len, precision=self.prec,
@@ -91,8 +91,8 @@ class HipBackend:
 
     def attention(self, q, q_col0, k, k_col0, vt, B, H, Nq, Nk, lens=None, head_dim=64):
         """bf16 x3 products on bf16 operands; the output o (the out-projection's operand) in the GEMM format.  lens: int32 [B] on the
-        device, the utterances' lengths of a ragged batch (self-attention; include/ns2hip_ragged_train.h): rows of o from a length on are
-        zero bits, their lse +inf.  head_dim 32 / 64 / 128 (include/ns2hip_head_dim_train.h): head h at columns col0 + head_dim h"""
+        device, the utterances' lengths of a ragged batch (self-attention; include/ns2hip_train.h): rows of o from a length on are
+        zero bits, their lse +inf.  head_dim 32 / 64 / 128 (include/ns2hip_train.h): head h at columns col0 + head_dim h"""
         return ops._attention_fwd(q, q_col0, k, k_col0, vt.ptr(), vt.ptr() + 64, vt.ld, B, H, Nq, Nk, head_dim ** -0.5, 3, head_dim=head_dim,
                                   o_precision=self.prec, want_lse=True, train_lens=lens)
 
@@ -214,7 +214,7 @@ class HipBackend:
 
     def groupnorm_silu_bwd(self, dy, x, stats, B, n, weight, bias, groups, eps, row_lens=None):
         """-> (dx [B n, C], dweight [C], dbias [C]); x, stats: what `groupnorm_silu_fwd` returned.  row_lens: what it got
-        (ns2_groupnorm_silu_bwd_lens, include/ns2hip_ragged_cond_train.h): rows of dy and x from a length on are not read, rows of dx
+        (ns2_groupnorm_silu_bwd_lens, include/ns2hip_train.h): rows of dy and x from a length on are not read, rows of dx
         there are zero bits"""
         C = weight.shape[0]
         dx = torch.empty(B * n, C, dtype=torch.float32, device=x.device)

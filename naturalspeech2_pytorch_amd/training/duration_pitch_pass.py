@@ -56,7 +56,7 @@ def duration_pitch_forward_train(dp, x, prompts, text_lens=None, prompt_lens=Non
     (NS2:430-446: the conv blocks keep their own default 0), so in train() mode it acts on the attention probabilities alone -- the stateless
     keep function of csrc/dropout_keep.h under one device-side seed per pass, call index = trunk * depth + layer.  `dp.dropout_seed`
     (an int64 tensor of one element) replaces the draw; `dp.last_dropout_seed` is what the last pass used.
-    text_lens / prompt_lens (`ragged_conditioning`; include/ns2hip_ragged_cond_train.h): phonemes / prompt rows per utterance, integer
+    text_lens / prompt_lens (`ragged_conditioning`; include/ns2hip_train.h): phonemes / prompt rows per utterance, integer
     [b]; either alone is allowed, the other side then counts as full.  Rows of x and of prompts behind their lengths are selected to 0
     once, ONE byte mask [b, n + n_p] -- keys [0, text_lens[i]) and [n, n + prompt_lens[i]), formed on the device -- serves every layer of
     both trunks on the existing key-mask / dropout attention kernels, and the durations and pitches from text_lens[i] on come back as

@@ -72,7 +72,7 @@ def transformer_forward_train(tr, x, mask=None):
 def speech_prompt_encoder_forward_train(enc, x, lens=None):
     """`SpeechPromptEncoder.forward` (NS2:289-341): the "same" k = 9 convolutions as GEMMs with pad_left = padding, SiLU on the kept fp32
     pre-activation, then the Transformer.
-    `lens` (`ragged_conditioning`; include/ns2hip_ragged_cond_train.h): prompt rows per utterance, integer [b].  The input and every
+    `lens` (`ragged_conditioning`; include/ns2hip_train.h): prompt rows per utterance, integer [b].  The input and every
     convolution's output are selected to 0 from lens[i] on (`KeepRowsFn`: the same select on the cotangent), so the "same" convolutions read
     what they read behind the end of the utterance alone; the Transformer runs under the key mask arange(n) < lens[:, None] on the existing
     key-mask / dropout kernels; the output rows from lens[i] on are selected to 0.  Nothing reads a device tensor of lengths on the host."""

@@ -29,7 +29,7 @@ def _shifts(taps, dil):
 
 def _rl(lens, seq_len):
     """the `row_lens=` keyword of the backend's products over the b * n frame rows of a pass that skips (`ragged_skip_training`;
-    include/ns2hip_ragged_skip_train.h): lens = int32 [b] on the device, or None -- then no keyword at all: the same calls as ever"""
+    include/ns2hip_train.h): lens = int32 [b] on the device, or None -- then no keyword at all: the same calls as ever"""
     return {} if lens is None else {"row_lens": (lens, seq_len)}
 
 
@@ -194,9 +194,9 @@ class AttnFn(torch.autograd.Function):
     the caller forms it) and adds the PRE-norm rows: `resid` [M, d] replaces `h` as the residual (with `film = gamma = None`); `h` then gets
     the q path's gradient only and `resid` the incoming one.  Absent by default, like the others.
     `lens` -- int32 [B] on the device, the utterances' lengths of a ragged batch (self-attention only, without kmask / drop;
-    include/ns2hip_ragged_train.h): keys stop at the length, and the rows of o and of dq | dk | dv from the length on are exact zeros.
+    include/ns2hip_train.h): keys stop at the length, and the rows of o and of dq | dk | dv from the length on are exact zeros.
     The kernels alone read it.  Absent by default: same kernels, same bits.
-    `masked_rows_zero` -- a promise of the ragged conditioning passes (include/ns2hip_ragged_cond_train.h), with `kmask` and without `drop`:
+    `masked_rows_zero` -- a promise of the ragged conditioning passes (include/ns2hip_train.h), with `kmask` and without `drop`:
     the rows of h / the context that the mask hides are ZEROS (so their k and v are zeros: no bias in to_q / to_kv, RMSNorm(0) = 0), the
     cotangent of every query row they stand for is 0, and the caller selects the returned gradient rows of the hidden rows to 0.  The
     backward then runs the PLAIN attention backward -- the instantiation the pass without lengths runs at dropout 0, i.e. what each
@@ -204,9 +204,9 @@ class AttnFn(torch.autograd.Function):
     hidden queries out of dk | dv, the hidden rows' own dk | dv meet zero operand rows in the weight gradient, and what they leave in the
     input gradient is selected away.  (The key-mask backward instantiation gives other last bits than the plain one on the same operands;
     with dropout both the ragged batch and the utterance alone run it.)  Absent by default.
-    `head_dim` -- 32 or 128 instead of the heads of 64 (include/ns2hip_head_dim_train.h; `head_dim_training`).  The backend is handed it
+    `head_dim` -- 32 or 128 instead of the heads of 64 (include/ns2hip_train.h; `head_dim_training`).  The backend is handed it
     only when it is not 64, as it is handed `lens` only when there are lengths: same calls, same kernels, same bits by default.
-    `row_lens` -- int32 [B] on the device, a pass that skips (`ragged_skip_training`; include/ns2hip_ragged_skip_train.h): the products
+    `row_lens` -- int32 [B] on the device, a pass that skips (`ragged_skip_training`; include/ns2hip_train.h): the products
     over the B seq_len frame rows -- q | k | v or the cross attention's q, to_out, their dgrads and row-plane weight gradients -- are
     handed the lengths (`_rl`); the cross attention's k | v projection, whose rows are the context's, never is.  The attention kernels
     keep `lens`.  Absent by default, like the others."""
@@ -326,7 +326,7 @@ def train_head_dim(owner, dim_head):
     return dim_head if getattr(owner, "head_dim_training", False) else 64
 
 
-HEAD_DIMS_TRAIN = (32, 64, 128)                 # what `head_dim_training=True` accepts (include/ns2hip_head_dim_train.h)
+HEAD_DIMS_TRAIN = (32, 64, 128)                 # what `head_dim_training=True` accepts (include/ns2hip_train.h)
 
 
 class FeedForwardFn(torch.autograd.Function):
@@ -508,7 +508,7 @@ class RvqCrossEntropyFn(torch.autograd.Function):
 class GroupNormSiluFn(torch.autograd.Function):
     """silu(GroupNorm(x)) (+ resid) over the rows of utterances of `seq_len` tokens: a Block of the DurationPitchPredictor's ResnetBlock, the
     last one with the ResnetBlock's input as `resid` (NS2:346-400).  The backward normalises with the forward's own statistics slots.
-    `row_lens` -- int32 [B] on the device, the utterances' row counts of a ragged batch (include/ns2hip_ragged_cond_train.h): statistics
+    `row_lens` -- int32 [B] on the device, the utterances' row counts of a ragged batch (include/ns2hip_train.h): statistics
     and gradient sums stop at a length, rows of y and of dx from it on are exact zeros (so `resid` gets no gradient there either), and
     nothing there is read.  The kernels alone read it.  Absent by default: the backend gets the calls without it, same kernels, same bits."""
 

@@ -53,14 +53,14 @@ def model_forward_train(m, x, times, prompt=None, cond=None, cond_drop_prob=None
     """`Model.forward` (NS2:929-1000) as a differentiable graph whose token-sized arithmetic is HIP (package docstring).
     `m` owns the reference's parameters (this package's `Model` or `compat.HipBackedModel`).  `m.train_precision`: "exact"
     (default: bf16 x3) or "mixed" (IEEE-half product + fp8 correction terms on FMT_H8 operands under a loss scale, `passes._Scale`).
-    `lens` (not in the reference): frames per utterance of a ragged batch, integer [b] (include/ns2hip_ragged_train.h).  Rows
+    `lens` (not in the reference): frames per utterance of a ragged batch, integer [b] (include/ns2hip_train.h).  Rows
     of x and of the projected cond from a length on are selected to 0 at the entry, every self-attention stops at the length in both
     directions, and the returned rows from a length on are selected to 0 -- which also zeroes the cotangent there.  No host read.
-    `prompt_lens` (not in the reference; `ragged_conditioning`): prompt rows per utterance, integer [b] (include/ns2hip_ragged_cond_train.h;
+    `prompt_lens` (not in the reference; `ragged_conditioning`): prompt rows per utterance, integer [b] (include/ns2hip_train.h;
     DESIGN §9).  The prompt rows behind a length are selected to 0 at the entry, the mean of to_prompt_cond is a masked sum over rows
     [0, prompt_lens[i]) divided by the clamped length, and the perceiver resampler's attentions run under the key mask
     [0, Lm + prompt_lens[i]) of cat(latents, prompt), all formed on the device.  With and without `lens`.
-    `m.ragged_skip_training` (include/ns2hip_ragged_skip_train.h): with `lens` and n % 256 == 0 the products over the b n frame
+    `m.ragged_skip_training` (include/ns2hip_train.h): with `lens` and n % 256 == 0 the products over the b n frame
     rows -- forward, dgrad, row-plane weight gradient -- are handed the lengths and skip the 256-row tiles hidden behind them, writing
     zeros there; decided here, once per pass.  Same loss, rows and gradients, bit for bit."""
     tp = getattr(m, "train_precision", "exact")
@@ -202,7 +202,7 @@ def unsupported_reason(m):
     accepts (ns2_model_create): heads of 64 (q / k / v column offsets, the attention kernels' head dim, scale 1/8), dim a multiple
     of 32 (whole 32-column lines per operand row), fp32 parameters (the packs and the returned gradients are fp32).  Anything else
     must not reach the kernels (a `dim_head=32` model would read past its packed qkv planes).  A model with
-    `head_dim_training = True` trains at dim_head 32 and 128 too (include/ns2hip_head_dim_train.h: the passes hand dim_head to AttnFn)."""
+    `head_dim_training = True` trains at dim_head 32 and 128 too (include/ns2hip_train.h: the passes hand dim_head to AttnFn)."""
     cfg = m._hip_cfg
     if getattr(m, "head_dim_training", False):
         if cfg["dim_head"] not in HEAD_DIMS_TRAIN:

@@ -1,5 +1,5 @@
 """TEST INFRASTRUCTURE: `tests/emu_backend.EmuBackend` plus the `head_dim` keyword of the four attention calls
-(`HipBackend.attention` / `attention_masked` / `attention_delta` / `attention_bwd`, include/ns2hip_head_dim_train.h), restated in plain
+(`HipBackend.attention` / `attention_masked` / `attention_delta` / `attention_bwd`, include/ns2hip_train.h), restated in plain
 torch from the kernels' contract -- so that the host logic of a training pass at head dims 32 and 128 (functions.py AttnFn, model_pass.py:
 column offsets heads * head_dim, scale head_dim ** -0.5) is checked against torch autograd without a GPU
 (tests/test_head_dim_training_cpu.py).  Never imported by the product.

@@ -1,5 +1,5 @@
 """TEST INFRASTRUCTURE: `tests/emu_backend.EmuBackend` plus the two backend calls that take per-utterance lengths
-(`HipBackend.attention(..., lens=)` / `attention_bwd(..., lens=)`, include/ns2hip_ragged_train.h), restated in plain torch from the kernels'
+(`HipBackend.attention(..., lens=)` / `attention_bwd(..., lens=)`, include/ns2hip_train.h), restated in plain torch from the kernels'
 contract -- so that the host logic of a ragged training pass (functions.py AttnFn, model_pass.py) is checked against torch autograd
 without a GPU (tests/test_ragged_training_cpu.py).  Never imported by the product.
 

@@ -1,5 +1,5 @@
 """TEST INFRASTRUCTURE: `tests/duration_pitch_golden.DurationPitchEmuBackend` plus the backend calls that ragged text and prompts add to
-the training pass (include/ns2hip_ragged_cond_train.h), restated in plain torch from the kernels' contract -- so that the host logic of
+the training pass (include/ns2hip_train.h), restated in plain torch from the kernels' contract -- so that the host logic of
 the conditioning passes with lengths (training/encoder_pass.py, duration_pitch_pass.py, model_pass.py) is checked against torch
 autograd without a GPU (tests/test_ragged_conditioning_cpu.py).  Never imported by the product.
 

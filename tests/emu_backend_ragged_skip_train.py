@@ -1,5 +1,5 @@
 """TEST INFRASTRUCTURE: `tests/emu_backend_ragged.EmuBackendRagged` plus the `row_lens=` keyword of the three product calls
-(`HipBackend.gemm_f32` / `gemm_split` / `wgrad_rows`; include/ns2hip_ragged_skip_train.h), restated in plain torch from the two
+(`HipBackend.gemm_f32` / `gemm_split` / `wgrad_rows`; include/ns2hip_train.h), restated in plain torch from the two
 contracts -- so that the host logic of a skipping training pass (which product of functions.py / model_pass.py is handed the lengths,
 and what the others then read) is checked against torch autograd without a GPU (tests/test_ragged_skip_training_cpu.py).  Never imported
 by the product.

@@ -1,4 +1,4 @@
-"""The feed-forward fold (include/ns2hip_fold.h): FeedForward's CausalConv1d(f, f, 3) and the Linear(f, dim) behind it (NS2:1016-1024) as
+"""The feed-forward fold (include/ns2hip.h): FeedForward's CausalConv1d(f, f, 3) and the Linear(f, dim) behind it (NS2:1016-1024) as
 ONE causal conv f -> dim.
 
   * op level: the fold kernel against torch.einsum in fp64; the dedicated FF conv kernel's fp32 output mode (csrc/ffconv_kernel.h) against

@@ -1,4 +1,4 @@
-"""Training at head dims 32 and 128 on the MI355X (include/ns2hip_head_dim_train.h).
+"""Training at head dims 32 and 128 on the MI355X (include/ns2hip_train.h).
 
   1. kernel level: the training forward (o, lse), the delta reduction and the flash backward at D = 32 / 128 against an fp64 attention on the
      values the planes hold -- partial tiles, more than two walked tiles, a context below one tile, 640-feature rows --, the column

@@ -27,12 +27,11 @@ def test_library_exports_whole_abi():
     import ctypes
     from ctypes import POINTER, c_char_p, c_void_p
     lib = _lib.load()                                   # raises if the .so or any symbol is missing
-    counts = {"ns2hip.h": 119, "ns2hip_optim.h": 7, "ns2hip_pitch.h": 1, "ns2hip_ragged.h": 2, "ns2hip_ragged_front.h": 4,
-              "ns2hip_ragged_train.h": 2, "ns2hip_head_dim_train.h": 3, "ns2hip_ragged_audio.h": 3, "ns2hip_fold.h": 2,
-              "ns2hip_ragged_cond_train.h": 1, "ns2hip_ragged_skip.h": 7, "ns2hip_ragged_skip_train.h": 3, "ns2hip_tail_fold.h": 4}
-    assert list(_lib.ABI) == list(_lib.HEADERS) == list(counts)
-    assert {h: len(t.signatures) for h, t in _lib.ABI.items()} == counts
-    assert len(_lib.SIGNATURES) == 158 == sum(counts.values())
+    counts = {"ns2hip.h": 71, "ns2hip_frontend.h": 15, "ns2hip_audio.h": 21, "ns2hip_train.h": 47, "ns2hip_optim.h": 7}
+    assert list(_lib.ABI) == list(_lib.HEADERS) == list(counts)      # the one pin of which header holds how much: a feature's tests
+    assert {h: len(t.signatures) for h, t in _lib.ABI.items()} == counts     # say where its entries are, this says nothing else arrived
+    assert len(_lib.SIGNATURES) == 161 == sum(counts.values())
+    assert not hasattr(_lib, "EXTRA_HEADERS")                        # one table: no second list beside HEADERS
     for i, union in enumerate((_lib.CONSTANTS, _lib.STRUCTS, _lib.SIGNATURES)):
         pairs = [kv for t in _lib.ABI.values() for kv in t[i].items()]
         assert len(pairs) == len(union) and dict(pairs) == union          # the merge, and no name in two headers
@@ -120,8 +119,8 @@ def test_state_dict_contract_matches_reference(path):
 
 
 def test_header_is_plain_c_and_a_c_caller_links_against_the_library(tmp_path):
-    """the drop-in boundary is a C ABI (extern "C", plain pointers and sizes, no torch types): include/ns2hip.h must compile as C99 with gcc, and
-    a C program that takes the address of entry points of every section (and calls the ones that need no GPU) must link against libns2hip.so
+    """the drop-in boundary is a C ABI (extern "C", plain pointers and sizes, no torch types): the headers under include/ must compile as C99 with gcc, and
+    a C program that takes the address of entry points of every section of every one of them (and calls the ones that need no GPU) must link against libns2hip.so
     and run -- the binding a maintainer of another host language would write."""
     import shutil
     import subprocess
@@ -134,13 +133,16 @@ def test_header_is_plain_c_and_a_c_caller_links_against_the_library(tmp_path):
 #include <stddef.h>
 #include <stdint.h>
 #include "ns2hip.h"
+#include "ns2hip_frontend.h"
+#include "ns2hip_audio.h"
+#include "ns2hip_train.h"
 int main(void) {
-  /* addresses of entry points from every section of the header: unresolved symbols fail the link */
+  /* addresses of entry points from every section of the headers: unresolved symbols fail the link */
   typedef void (*fn_t)(void);
   fn_t fns[] = {(fn_t)ns2_weight_pack, (fn_t)ns2_linear, (fn_t)ns2_attention_fwd,
                        (fn_t)ns2_rmsnorm, (fn_t)ns2_rvq_encode, (fn_t)ns2_model_create,
                        (fn_t)ns2_model_forward, (fn_t)ns2_ddim_step, (fn_t)ns2_weights_repack, (fn_t)ns2_weights_retile,
-                       (fn_t)ns2_attention_bwd, (fn_t)ns2_weight_tile_linear, (fn_t)ns2_model_cond_stack};
+                       (fn_t)ns2_attention_bwd, (fn_t)ns2_weight_tile_linear, (fn_t)ns2_model_cond_stack, (fn_t)ns2_groupnorm_silu};
   int n = 0;
   for (unsigned i = 0; i < sizeof fns / sizeof fns[0]; ++i) n += fns[i] != 0;
   ns2_model_config cfg;                       /* the config struct is plain ints */
@@ -165,7 +167,7 @@ int main(void) {
     subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-pedantic", "-I", inc, "-fsyntax-only", str(src)], check=True)
     subprocess.run(["gcc", "-std=c99", "-I", inc, str(src), "-o", str(exe), "-L", libdir, "-lns2hip", "-Wl,-rpath," + libdir], check=True)
     out = subprocess.run([str(exe)], check=True, capture_output=True, text=True, timeout=120).stdout.split()
-    assert out[0] == "13" and int(out[1]) >= 120 and int(out[2]) == 1408 and out[3] == "0", out
+    assert out[0] == "14" and int(out[1]) >= 120 and int(out[2]) == 1408 and out[3] == "0", out
     # ... and the ctypes mirrors of the argument blocks have the header's layout: same size, same field offsets
     import ctypes
 
@@ -181,15 +183,15 @@ int main(void) {
 
 def test_derived_structs_have_the_layout_gcc_gives_every_field(tmp_path):
     """every field of every struct _lib derived from the header: a C program generated from the parsed field names prints sizeof of
-    the struct and offsetof / sizeof of each field as gcc lays include/ns2hip.h out, and the ctypes classes must say the same (the
+    the struct and offsetof / sizeof of each field as gcc lays the headers out, and the ctypes classes must say the same (the
     compiler is the independent witness, not the parser)"""
     import ctypes
     import shutil
     if shutil.which("gcc") is None:
         pytest.skip("needs gcc")
-    structs = _lib.ABI["ns2hip.h"].structs
+    structs = {**_lib.ABI["ns2hip.h"].structs, **_lib.ABI["ns2hip_train.h"].structs}
     assert sorted(structs) == ["ns2_attn_args", "ns2_attn_bwd_args", "ns2_linear_args", "ns2_model_config", "ns2_repack_part"]
-    lines = ["#include <stdio.h>", "#include <stddef.h>", '#include "ns2hip.h"', "int main(void) {"]
+    lines = ["#include <stdio.h>", "#include <stddef.h>", '#include "ns2hip.h"', '#include "ns2hip_train.h"', "int main(void) {"]
     for name, cls in structs.items():
         lines.append(f'  printf("{name} %d\\n", (int)sizeof({name}));')
         for f, _ in cls._fields_:

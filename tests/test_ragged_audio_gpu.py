@@ -1,4 +1,4 @@
-"""Ragged RAW AUDIO on the MI355X (include/ns2hip_ragged_audio.h): ns2_audio_to_mel_lens, ns2_pitch_yin_lens and ns2_rvq_ce_lens against the
+"""Ragged RAW AUDIO on the MI355X (include/ns2hip_audio.h, include/ns2hip_train.h): ns2_audio_to_mel_lens, ns2_pitch_yin_lens and ns2_rvq_ce_lens against the
 entries without lengths on each utterance alone, the frozen codec's encode of a padded batch, and `NaturalSpeech2(ragged_audio=True)` end
 to end -- eager, captured, and in the Trainer.  The definition under test: what utterance i yields in the padded batch is what it yields
 alone, cut to its length; what lies at or behind a length (NaN included) reaches no value and no gradient before it; what is returned at

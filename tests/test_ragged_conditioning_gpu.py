@@ -1,4 +1,4 @@
-"""Ragged text and prompts in TRAINING on the MI355X (include/ns2hip_ragged_cond_train.h): per-utterance lengths through the conditioning.
+"""Ragged text and prompts in TRAINING on the MI355X (include/ns2hip_train.h): per-utterance lengths through the conditioning.
 The definition under test is the one of the ragged front-end, now for the gradients too: utterance i of a padded batch is utterance i run
 alone with its text cut to text_lens[i] and its prompt cut to prompt_lens[i] -- what lies at or beyond a length (NaN included) reaches no
 value and no gradient before it, and what is returned there is an exact 0.

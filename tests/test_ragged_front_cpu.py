@@ -1,4 +1,4 @@
-"""Ragged prompts and text on the CPU: the fifth header of the C ABI (include/ns2hip_ragged_front.h), the composite restatement of the
+"""Ragged prompts and text on the CPU: its entries of the C ABI (include/ns2hip_frontend.h; ns2_model_prepare_cond_lens in include/ns2hip.h), the composite restatement of the
 rule its kernels follow -- every front-end output of utterance i of a padded batch equals what utterance i gives alone with its text cut
 to text_lens[i] and its prompt cut to prompt_lens[i] --, and the keyword rules of NaturalSpeech2.sample(prompt_lens=)."""
 import ctypes
@@ -28,24 +28,24 @@ def rel(a, b):
 # ---- the C ABI
 def test_front_header_parses_and_the_library_exports_it():
     P, I, L, F = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
-    assert _lib.header_symbols("ns2hip_ragged_front.h") == ENTRIES
-    S = _lib.ABI["ns2hip_ragged_front.h"].signatures
+    assert set(ENTRIES) - {"ns2_model_prepare_cond_lens"} <= set(_lib.header_symbols("ns2hip_frontend.h"))
+    assert "ns2_model_prepare_cond_lens" in _lib.header_symbols("ns2hip.h")          # a Model entry: beside ns2_model_prepare_cond
+    S = {**_lib.ABI["ns2hip_frontend.h"].signatures, **_lib.ABI["ns2hip.h"].signatures}
     assert S["ns2_groupnorm_silu_lens"] == (I, [P, I, I, I, I, P, P, F, P, P, P, P, P, I, I, P, L, P])
     assert S["ns2_zero_rows_lens"] == (I, [P, L, I, I, P, P])
     assert S["ns2_mean_rows_lens"] == (I, [P, I, I, I, P, P, P])
     assert S["ns2_model_prepare_cond_lens"] == (I, [P, P, I, P, P, I, I, I, I, P, P, L, P])
-    assert len(_lib.ABI["ns2hip.h"].signatures) == 119                       # the other headers' tables describe them alone
     _lib.load()                                                              # raises unless the library exports them
 
 
-def test_c99_caller_includes_the_fifth_header_and_links(tmp_path):
+def test_c99_caller_includes_the_fifth_header_and_links(tmp_path):     # (ns2hip_frontend.h, the second of five now)
     if shutil.which("gcc") is None or not os.path.exists(_lib.LIB_PATH):
         pytest.skip("needs gcc and the built library")
     src = tmp_path / "front_caller.c"
     src.write_text(r'''
 #include <stdio.h>
 #include "ns2hip.h"
-#include "ns2hip_ragged_front.h"
+#include "ns2hip_frontend.h"
 int main(void) {
   int lens[2] = {3, 1};
   int r0 = ns2_groupnorm_silu_lens(0, 2, 8, 32, 8, 0, 0, 1e-5f, 0, lens, 0, 0, 0, 32, 3, 0, 0, 0);

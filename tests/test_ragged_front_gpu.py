@@ -1,4 +1,4 @@
-"""Ragged prompts and text on the MI355X (include/ns2hip_ragged_front.h): per-utterance lengths through SpeechPromptEncoder,
+"""Ragged prompts and text on the MI355X (include/ns2hip_frontend.h): per-utterance lengths through SpeechPromptEncoder,
 DurationPitchPredictor, the conditioning of Model and NaturalSpeech2.sample(prompt_lens=).  The definition under test: every front-end
 output of utterance i of a padded batch equals what utterance i gives alone with its text cut to text_lens[i] and its prompt cut to
 prompt_lens[i] -- so what lies at or beyond a length (NaN included) must not reach what lies before it."""

@@ -1,4 +1,4 @@
-"""Ragged batches on the MI355X (include/ns2hip_ragged.h): per-utterance lengths in the two attention forward kernels, through the
+"""Ragged batches on the MI355X (include/ns2hip.h): per-utterance lengths in the two attention forward kernels, through the
 executor, Model.forward(lens=) and the sampler.  The definition under test: utterance i of a ragged batch equals utterance i alone at its
 own length -- so what lies at or beyond a length (NaN included, at kernel level) must not reach the frames before it."""
 import pytest

@@ -1,4 +1,4 @@
-"""Skipping the hidden row tiles of a ragged sampling batch (include/ns2hip_ragged_skip.h), the parts that need no GPU: the header and
+"""Skipping the hidden row tiles of a ragged sampling batch (include/ns2hip.h), the parts that need no GPU: the header and
 its exports, the skip rule (host arithmetic over the described step), the refusals that come before any device call, the computed-extent
 formula of the measurement tool, and the `ragged_skip` switch of Model on a recording stand-in for the library."""
 import ctypes
@@ -18,14 +18,13 @@ ENTRIES = ["ns2_attention_fwd_skip", "ns2_debug_gemm_route_launches", "ns2_debug
 
 def test_ragged_skip_header_parses_and_the_library_exports_it():
     P, I, L, PTR = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.POINTER
-    S = _lib.ABI["ns2hip_ragged_skip.h"].signatures
-    assert _lib.header_symbols("ns2hip_ragged_skip.h") == ENTRIES
+    S = _lib.ABI["ns2hip.h"].signatures
+    assert set(ENTRIES) <= set(_lib.header_symbols("ns2hip.h"))
     assert S["ns2_linear_lens"] == (I, [PTR(_lib.LinearArgs), P, I, P]) and S["ns2_attention_fwd_skip"] == (I, [PTR(_lib.AttnArgs), P, P, P])
     assert S["ns2_model_forward_lens_skip"] == _lib.SIGNATURES["ns2_model_forward_lens"] == (I, [P, P, P, P, P, P, I, P, I, I, P, L, P])
     assert S["ns2_wavenet_block_lens"] == (I, [P, P, P, I, I, I, I, P, P, P, I, P, P, I, I, P, P])
     assert S["ns2_debug_skip_rule"] == (I, [PTR(_lib.ModelConfig), I, I, P])
     assert S["ns2_debug_skip_last"] == (I, []) and S["ns2_debug_gemm_route_launches"] == (L, [I])
-    assert len(_lib.ABI["ns2hip.h"].signatures) == 119
     _lib.load()                                                                  # raises unless the library exports them
 
 

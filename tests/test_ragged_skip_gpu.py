@@ -1,4 +1,4 @@
-"""Skipping the hidden row tiles of a ragged sampling batch on the MI355X (include/ns2hip_ragged_skip.h).  The reference in every test is
+"""Skipping the hidden row tiles of a ragged sampling batch on the MI355X (include/ns2hip.h).  The reference in every test is
 the same entry WITHOUT lengths, or with lengths and the switch off -- never the skipping code itself.  Rows before an utterance's computed
 extent H_i = min(N, 256 ceil(lens_i / 256)) must keep their bits; hidden rows must not be touched (sentinels), except an fp32 output
 without a residual, which gets exact zeros.

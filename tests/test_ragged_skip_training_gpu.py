@@ -1,4 +1,4 @@
-"""Skipping the hidden row tiles of a ragged TRAINING batch on the MI355X (include/ns2hip_ragged_skip_train.h): the two kernels entries
+"""Skipping the hidden row tiles of a ragged TRAINING batch on the MI355X (include/ns2hip_train.h): the two kernels entries
 bit for bit against the entries without lengths, `Model(ragged_skip_training=True)` against the same call with the switch off, and a
 captured step whose lengths are rewritten between replays.  The reference is never the skipping code itself.
 
@@ -106,7 +106,7 @@ def test_linear_lens_zero_keeps_visible_bits_and_zeroes_hidden_tiles(precision, 
     """rows before H_i: the bits of ns2_linear on the operand with its hidden rows zeroed; rows from H_i on: zero bits in every output --
     fp32, fp32 + residual, operand planes, attention planes of a precision-4 product -- although each output buffer came full of 0xFF.
     The operand's hidden rows hold 0xFF for the causal and plain products (never read from a visible row) and zeros for the anticausal
-    one (the contract of include/ns2hip_ragged_skip_train.h)."""
+    one (the contract of include/ns2hip_train.h)."""
     hidden = _hidden_rows(KB, KN, KLENS)
     lens = torch.tensor(KLENS, dtype=torch.int32, device=DEV)
     taps = 3 if variant != "plain" else 0

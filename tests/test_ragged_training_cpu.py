@@ -1,4 +1,4 @@
-"""Ragged TRAINING batches on the CPU (include/ns2hip_ragged_train.h): the sixth header of the C ABI and what its two entries refuse,
+"""Ragged TRAINING batches on the CPU (include/ns2hip_train.h): the two attention entries of the C ABI and what they refuse,
 the `ragged_training` switch of Model, the composite restatement of the rule -- utterance i of a ragged batch contributes to the output
 and to every gradient what it contributes alone at lens[i] frames --, the host logic of the HIP pass (functions.py / model_pass.py on
 tests/emu_backend_ragged.py) against the composite's autograd, and the masked loss of NaturalSpeech2.forward(audio_lens=)."""
@@ -90,11 +90,10 @@ def case(request):
 # ---- the C ABI
 def test_ragged_train_header_parses_and_the_library_exports_it():
     P, I = ctypes.c_void_p, ctypes.c_int
-    assert _lib.header_symbols("ns2hip_ragged_train.h") == ["ns2_attention_bwd_lens", "ns2_attention_train_fwd_lens"]
-    S = _lib.ABI["ns2hip_ragged_train.h"].signatures
+    assert {"ns2_attention_bwd_lens", "ns2_attention_train_fwd_lens"} <= set(_lib.header_symbols("ns2hip_train.h"))
+    S = _lib.ABI["ns2hip_train.h"].signatures
     assert S["ns2_attention_train_fwd_lens"] == (I, [ctypes.POINTER(_lib.AttnArgs), P, P])
     assert S["ns2_attention_bwd_lens"] == (I, [ctypes.POINTER(_lib.AttnBwdArgs), P, P])
-    assert len(_lib.ABI["ns2hip.h"].signatures) == 119
     _lib.load()                                                                  # raises unless the library exports them
 
 

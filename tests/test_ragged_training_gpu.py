@@ -1,4 +1,4 @@
-"""Ragged TRAINING batches on the MI355X (include/ns2hip_ragged_train.h): per-utterance lengths in the training forward and the backward
+"""Ragged TRAINING batches on the MI355X (include/ns2hip_train.h): per-utterance lengths in the training forward and the backward
 attention kernels, through AttnFn / model_forward_train, Model.forward(lens=) under autograd, NaturalSpeech2.forward(audio_lens=),
 GraphedTrainStep and Trainer.  The definition under test: utterance i of a ragged batch contributes to the loss and to every gradient what
 it contributes alone at lens[i] frames -- so what lies at or beyond a length (NaN included) must not reach a value or a gradient before

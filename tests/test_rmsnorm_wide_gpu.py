@@ -1,4 +1,4 @@
-"""rmsnorm_wide_kernel (csrc/elementwise.hip; include/ns2hip_tail_fold.h) against rmsnorm_kernel through ns2_rmsnorm: the same bytes in
+"""rmsnorm_wide_kernel (csrc/elementwise.hip; include/ns2hip.h) against rmsnorm_kernel through ns2_rmsnorm: the same bytes in
 the planes and in the fp32 output, the same range-guard counts, nothing written outside the output, and the routing."""
 import pytest
 import torch

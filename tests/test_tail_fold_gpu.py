@@ -1,4 +1,4 @@
-"""The Wavenet tail fold (include/ns2hip_tail_fold.h): the sum of the last stack's skip convs and final_conv behind it (NS2:725) as ONE
+"""The Wavenet tail fold (include/ns2hip.h): the sum of the last stack's skip convs and final_conv behind it (NS2:725) as ONE
 Linear of K = L * dim.
 
   * op level: the fold kernel against torch.einsum in fp64;

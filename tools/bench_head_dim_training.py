@@ -1,4 +1,4 @@
-"""What training at head dims 32 and 128 on the HIP kernels (`head_dim_training=True`, include/ns2hip_head_dim_train.h) costs and saves on
+"""What training at head dims 32 and 128 on the HIP kernels (`head_dim_training=True`, include/ns2hip_train.h) costs and saves on
 one MI355X, and whether the head-dim-64 backward kept its speed:
 
     python tools/bench_head_dim_training.py [--out profiles/head_dim_training.json] [--repeats 7] [--warmup 2] [--parent-lib PATH]

@@ -1,4 +1,4 @@
-"""What per-utterance lengths cost and save in the three kernels of include/ns2hip_ragged_audio.h on one MI355X:
+"""What per-utterance lengths cost and save in the three kernels of include/ns2hip_audio.h on one MI355X:
 
     python tools/bench_ragged_audio.py [--out profiles/ragged_audio.json] [--repeats 7] [--warmup 3]
 

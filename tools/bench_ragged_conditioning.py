@@ -1,4 +1,4 @@
-"""What per-utterance text and prompt lengths cost in the TRAINING pass of the conditioning (include/ns2hip_ragged_cond_train.h) on one MI355X:
+"""What per-utterance text and prompt lengths cost in the TRAINING pass of the conditioning (include/ns2hip_train.h) on one MI355X:
 
     python tools/bench_ragged_conditioning.py [--out profiles/ragged_conditioning.json] [--repeats 7] [--warmup 2]
 

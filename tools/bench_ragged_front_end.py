@@ -1,4 +1,4 @@
-"""What per-utterance prompt and text lengths (include/ns2hip_ragged_front.h) cost in the conditioning front-end on one MI355X:
+"""What per-utterance prompt and text lengths (include/ns2hip_frontend.h) cost in the conditioning front-end on one MI355X:
 
     python tools/bench_ragged_front_end.py [--out profiles/ragged_front_end.json] [--repeats 7] [--warmup 2]
 

@@ -1,4 +1,4 @@
-"""What per-utterance lengths (Model.forward(lens=), include/ns2hip_ragged.h) cost and save on one MI355X:
+"""What per-utterance lengths (Model.forward(lens=), include/ns2hip.h) cost and save on one MI355X:
 
     python tools/bench_ragged_sampling.py [--out profiles/ragged_sampling.json] [--repeats 7] [--warmup 3]
 

@@ -1,4 +1,4 @@
-"""What skipping the hidden row tiles of a ragged sampling batch (Model(ragged_skip=True), include/ns2hip_ragged_skip.h) costs and saves
+"""What skipping the hidden row tiles of a ragged sampling batch (Model(ragged_skip=True), include/ns2hip.h) costs and saves
 on one MI355X:
 
     python tools/bench_ragged_skip.py [--out profiles/ragged_skip.json] [--repeats 7] [--warmup 3]

@@ -1,4 +1,4 @@
-"""What skipping the hidden row tiles of a ragged TRAINING batch (Model(ragged_skip_training=True), include/ns2hip_ragged_skip_train.h)
+"""What skipping the hidden row tiles of a ragged TRAINING batch (Model(ragged_skip_training=True), include/ns2hip_train.h)
 costs and saves on one MI355X:
 
     python tools/bench_ragged_skip_training.py [--out profiles/ragged_skip_training.json] [--repeats 7] [--warmup 2]

@@ -1,5 +1,5 @@
 """What per-utterance lengths in the TRAINING pass (Model(ragged_training=True), NaturalSpeech2.forward(audio_lens=),
-include/ns2hip_ragged_train.h) cost and save on one MI355X:
+include/ns2hip_train.h) cost and save on one MI355X:
 
     python tools/bench_ragged_training.py [--out profiles/ragged_training.json] [--repeats 7] [--warmup 3]
 
